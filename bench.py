@@ -21,8 +21,17 @@ Other modes (never the headline): --mode dist (configs[2]), --mode computeLD (co
 --mode jepegmix (configs[4]), --mode e2e (packed panel file + GWAS file on disk -> result table).
 
 Prints ONE JSON line (rank 0).  "roofline" describes the LD GEMM kernel from HIP events recorded by
-the library on its own stream around every launch; "cpu_baseline" is the CPU oracle timed on a
-bounded sample (N = 1 only).
+the library on its own stream around every launch of the timed steps.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  Everything else the bench measures or
+checks runs only with --full: the CPU baseline, the parity spot against the CPU oracle, the int8 variant, the
+one-stream pass (roofline_solve / _pack / _epilogue), the committed PMC traffic figures, the emulated 8-rank
+shares, the weak-scaling pass (N > 1), the end_to_end block and the other_configs block.  The --no-* options
+below switch single legs of a --full run off.
+
+--dump-outputs DIR writes what the timed job returned in its last timed step, every window's z and info in
+window order (DIR/z.npy, DIR/info.npy, float64) and its status word (DIR/status.npy, float64); the inputs are
+seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -81,7 +90,15 @@ def parse_args(argv=None):
     ap.add_argument("--emulate-steps", type=int, default=10, help="timed steps per emulated share (each share also gets 3 warm-up steps)")
     ap.add_argument("--no-parity-spot", action="store_true", help="skip the oracle spot check of the timed job's own results")
     ap.add_argument("--streams", type=int, default=1, help="split a rank's windows over this many contexts (one stream pair each)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (CPU baseline, parity spot, int8 variant, one-stream pass, PMC "
+                         "traffic, emulated shares, weak scaling, end_to_end, other_configs); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed job's last-step z / info / status as DIR/<name>.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -319,6 +336,39 @@ def result_digest(res):
             int(sum(int(r["status"] != 0) for r in res)), bool(np.all(np.isfinite(z)) and np.all(np.isfinite(info)))]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, rig, mine, res, wins, strong=True):
+    """--dump-outputs: the timed job's results of its last timed step as DIR/z.npy and DIR/info.npy (every window's unmeasured SNPs,
+    window by window in chromosome order, float64) and DIR/status.npy (one status word per window, float64).  With several ranks
+    the pieces travel to rank 0, which puts every window together as one job over the chromosome would have returned it (--scaling
+    weak: every rank imputes a chromosome of its own seed, and rank 0 writes its own).  Should z and info outgrow DUMP_LIMIT_BYTES,
+    a fixed sample of their entries is written (DIR/sample_index.npy holds its positions)."""
+    own = {piece: (r["z"], r["info"], r["status"]) for piece, r in zip(mine, res)}
+    parts = rig.gather(own) if strong else [own]
+    if rig.rank != 0:
+        return
+    got = {}
+    for p in parts:
+        got.update(p)
+    z, info, status = [], [], np.zeros(len(wins), dtype=np.float64)
+    for k in range(len(wins)):
+        for q in sorted(q for q in got if q[0] == k):
+            z.append(np.asarray(got[q][0], dtype=np.float64))
+            info.append(np.asarray(got[q][1], dtype=np.float64))
+            status[k] = max(status[k], float(got[q][2]))
+    out = {"z": np.concatenate(z) if z else np.zeros(0), "info": np.concatenate(info) if info else np.zeros(0), "status": status}
+    n = out["z"].size
+    keep = (DUMP_LIMIT_BYTES - status.nbytes) // (3 * 8)        # z + info + the sample's positions
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        out["z"], out["info"], out["sample_index"] = out["z"][idx], out["info"][idx], idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 SPOT_TOL = 1e-8
 
 
@@ -382,15 +432,16 @@ def run_impute(args, rig, quiet=False, light=False):
 
     panel, ld = synth_panel(rig, ch, seed)
     store, ld2 = pack_store(rig, ch, panel, ld)
+    full = args.full
     keep0 = None
-    if rig.rank == 0 and not args.no_cpu_baseline and rig.world == 1:
+    if full and rig.rank == 0 and not args.no_cpu_baseline and rig.world == 1:
         n0 = 250 if light else 600
         k0 = next((k for k, w in enumerate(wins) if len(w[1]) >= n0 and len(w[2]) >= n0), 0)
         _, mi, ui = wins[k0]                                  # this window also feeds the CPU baseline sample
         keep0 = (k0, panel.index_select(0, torch.from_numpy(mi[:n0]).cuda()).cpu().numpy(),
                  panel.index_select(0, torch.from_numpy(ui[:n0]).cuda()).cpu().numpy())
     spot = None
-    if rig.rank == 0 and rig.world == 1 and not args.no_parity_spot and wins:
+    if full and rig.rank == 0 and rig.world == 1 and not args.no_parity_spot and wins:
         spot = spot_inputs(torch, panel, wins)
     del panel
     full_store = store
@@ -414,6 +465,8 @@ def run_impute(args, rig, quiet=False, light=False):
     snps = rig.reduce(work["imputed_snps"], "sum")
     digests = rig.gather(dict(rank=rig.rank, windows=mine, digest=result_digest(res), dt=dt,
                               resident_rows=int(store.shape[0]), imputed=int(work["imputed_snps"])))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rig, mine, res, wins, strong)
 
     shard_check = None
     if args.verify_shards and strong and rig.world > 1:
@@ -429,7 +482,7 @@ def run_impute(args, rig, quiet=False, light=False):
     # the same job with the LD Gram on the int8 matrix cores (identical integers, identical outputs):
     # reported next to the headline, never as `value`
     i8_variant = None
-    if args.gram_dtype == "f32" and not args.no_i8_variant and args.streams == 1 and rig.world == 1:
+    if full and args.gram_dtype == "f32" and not args.no_i8_variant and args.streams == 1 and rig.world == 1:
         rig.ctx.set_gram_dtype("i8")
         r8 = Runner(rig, window_descs(ch, wins, store, ld2, args.mode), 1)
         rig.ctx.set_gram_dtype("f32")
@@ -446,7 +499,7 @@ def run_impute(args, rig, quiet=False, light=False):
     # chain on the library's side stream, so their stage timers overlap; a short pass on a one-stream context gives
     # the stand-alone figures `roofline_solve` quotes (never `value`)
     tails_alone = None
-    if rig.world == 1 and rig.rank == 0 and runner.jobs and not args.no_tails_alone:
+    if full and rig.world == 1 and rig.rank == 0 and runner.jobs and not args.no_tails_alone:
         from gauss_amd import hotpath
         old_env = os.environ.get("GAUSS_SIDE_STREAM")
         os.environ["GAUSS_SIDE_STREAM"] = "0"
@@ -465,7 +518,7 @@ def run_impute(args, rig, quiet=False, light=False):
         rig.ctx = main_ctx
 
     weak = None
-    if strong and rig.world > 1 and not args.no_weak_line:
+    if full and strong and rig.world > 1 and not args.no_weak_line:
         # second line: every rank imputes the WHOLE chromosome (per-GPU work fixed as N grows)
         runner.close()
         wr = Runner(rig, window_descs(ch, wins, full_store, ld2, args.mode), 1)
@@ -477,8 +530,8 @@ def run_impute(args, rig, quiet=False, light=False):
         wr.close()
 
     emu = None
-    emu_world = args.emulate_world
-    if emu_world < 0:           # default: the driver's N = 1 line records the 8-rank prediction (whole chromosome only)
+    emu_world = args.emulate_world if full else 0
+    if emu_world < 0:           # default of --full: the N = 1 line records the 8-rank prediction (whole chromosome only)
         emu_world = 8 if (rig.world == 1 and strong and not args.windows and args.streams == 1 and len(wins) >= 16) else 0
     if rig.world == 1 and emu_world > 1:
         e_steps = max(1, min(args.steps, args.emulate_steps)) if args.emulate_world < 0 else args.steps
@@ -512,7 +565,7 @@ def run_impute(args, rig, quiet=False, light=False):
                        "time, not a multi-GPU measurement (no 8-GPU node is available to the builder)"}
 
     e2e = None
-    if rig.world == 1 and args.mode == "distmix" and not args.no_e2e and not args.windows and args.streams == 1:
+    if full and rig.world == 1 and args.mode == "distmix" and not args.no_e2e and not args.windows and args.streams == 1:
         runner.close()
         del store, full_store
         torch.cuda.empty_cache()
@@ -645,7 +698,7 @@ def run_impute(args, rig, quiet=False, light=False):
         # the launch the headline runs: ONE launch of the job's full grid (work items x 256 threads).  Counters exist for that grid from
         # the one-stream pass (counter collection serialises the queues: the merged form itself cannot run under it, its evidence is
         # the kernel trace, profiles/README.md); in the two-launch form the two halves' rows add up to the step's traffic
-        out["roofline"].update(pmc_traffic(len(wins) == 36 and len(ch["bp"]) == 100_000 and rig.world == 1, largest=True,
+        out["roofline"].update(pmc_traffic(full and len(wins) == 36 and len(ch["bp"]) == 100_000 and rig.world == 1, largest=True,
                                            grid=stats["items"] * 256 if gram_lps == 1 else None))
         if shard_check is not None:
             out["config"]["shards_bit_identical_to_one_rank"] = shard_check

@@ -252,7 +252,7 @@ def other_configs_block(args, rig, ch, files, tmp):
     # configs[2]
     t0 = time.perf_counter()
     a = argparse.Namespace(**dict(vars(args), steps=5, warmup=2, mode="dist", no_i8_variant=True, no_e2e=True, emulate_world=0,
-                                  no_tails_alone=True, no_other_configs=True, streams=1))
+                                  no_tails_alone=True, no_other_configs=True, streams=1, dump_outputs=None))
     line = bench.run_impute(a, rig, quiet=True, light=True)
     line["seconds"] = time.perf_counter() - t0
     out["dist"] = {k: line[k] for k in ("value", "unit", "ms_per_step", "steps", "config", "roofline", "launch_form", "cpu_baseline", "parity_spot",

@@ -6,7 +6,11 @@ these vectors pin the *oracle* (cross-validated against numpy/scipy in tests/tes
 reference binary: "parity unpinned" in the sense of the task statement.  They guard against silent
 drift of either the oracle or the HIP path between rounds.  Run from the repo root:
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --bgzf      (ref_bgzf.*: needs oracle/_ref/libref_bgzf.so)
 """
+import ctypes
+import hashlib
+import json
 import os
 import sys
 
@@ -55,5 +59,48 @@ def main():
     print("wrote tests/golden/window_small_ext.npz", {k: np.shape(v) for k, v in ext.items()})
 
 
+class _RefBgzf(ctypes.Structure):
+    """The leading fields of the reference's BGZF handle (bgzf.h, built without _USE_KNETFILE): bgzf_tell is a macro over them."""
+    _fields_ = [("file_descriptor", ctypes.c_int), ("open_mode", ctypes.c_char), ("owned_file", ctypes.c_int16),
+                ("compress_level", ctypes.c_int16), ("file", ctypes.c_void_p), ("uncompressed_block_size", ctypes.c_int),
+                ("compressed_block_size", ctypes.c_int), ("uncompressed_block", ctypes.c_void_p), ("compressed_block", ctypes.c_void_p),
+                ("block_address", ctypes.c_int64), ("block_length", ctypes.c_int), ("block_offset", ctypes.c_int)]
+
+
+def bgzf():
+    """tests/golden/ref_bgzf.gz + ref_bgzf.json: a panel-shaped text written by the reference's OWN BGZF writer (oracle/_ref/libref_bgzf.so,
+    built by oracle/Makefile where the reference tree exists), with the virtual offset bgzf_tell gave at the start of every 40th line.
+    tests/test_feeder.py reads it with the project's readers, so the codec stays pinned where the reference cannot be built."""
+    lib = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_bgzf.so"))
+    lib.bgzf_open.restype = ctypes.POINTER(_RefBgzf)
+    lib.bgzf_open.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+    lib.bgzf_write.argtypes = [ctypes.POINTER(_RefBgzf), ctypes.c_void_p, ctypes.c_int]
+    lib.bgzf_close.argtypes = [ctypes.POINTER(_RefBgzf)]
+    rng = np.random.default_rng(20261016)
+    lines = []
+    for i in range(1500):
+        g = "".join(map(str, rng.choice(3, size=int(rng.integers(60, 240)), p=[0.6, 0.3, 0.1])))
+        lines.append(f"rs{1000 + 7 * i}\t22\t{16_050_000 + 211 * i}\t{'ACGT'[i % 4]}\t{'GTAC'[i % 4]}\t{g}")
+    path = os.path.join(ROOT, "tests", "golden", "ref_bgzf.gz")
+    h = lib.bgzf_open(path.encode(), b"w")
+    assert h
+    voff = []
+    for i, line in enumerate(lines):
+        if i % 40 == 0:
+            voff.append([i, (h.contents.block_address << 16) | (h.contents.block_offset & 0xFFFF)])
+        b = (line + "\n").encode()
+        assert lib.bgzf_write(h, b, len(b)) == len(b)
+    assert lib.bgzf_close(h) == 0
+    text = ("\n".join(lines) + "\n").encode()
+    meta = {"lines": len(lines), "text_bytes": len(text), "text_sha256": hashlib.sha256(text).hexdigest(), "line_voffsets": voff,
+            "made_by": "the reference's bgzf_open / bgzf_write / bgzf_close (src/bgzf.c); voffsets from its bgzf_tell"}
+    with open(os.path.join(ROOT, "tests", "golden", "ref_bgzf.json"), "w") as fh:
+        json.dump(meta, fh, indent=0)
+    print("wrote tests/golden/ref_bgzf.gz", os.path.getsize(path), "bytes,", len(text), "bytes of text")
+
+
 if __name__ == "__main__":
-    main()
+    if "--bgzf" in sys.argv:
+        bgzf()
+    else:
+        main()

@@ -514,6 +514,40 @@ def test_bench_pieces_are_put_together_per_window():
     assert not bench.pieces_equal_whole(lap, ref, wins)                 # pieces overlap
 
 
+def test_bench_dump_outputs_puts_the_ranks_pieces_together(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (pure Python): the ranks' pieces land on rank 0 as every window's z / info in window order (float64)
+    plus one status word per window; another rank writes nothing; above the size limit a fixed sample is written with its positions."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(2)
+    wins = [(1 + 1_000_000 * k, np.arange(5 + k), np.arange(30 + 7 * k)) for k in range(4)]
+    ref = [dict(z=rng.standard_normal(len(w[2])), info=rng.random(len(w[2])), status=k % 2) for k, w in enumerate(wins)]
+    shares = [[(0, 0, 30), (2, 0, 20)], [(1, 0, 37), (2, 20, 44)], [(3, 0, 51)]]
+    mine = [[dict(z=ref[k]["z"][a:b], info=ref[k]["info"][a:b], status=ref[k]["status"]) for k, a, b in sh] for sh in shares]
+    parts = [{pc: (r["z"], r["info"], r["status"]) for pc, r in zip(sh, res)} for sh, res in zip(shares, mine)]
+
+    class Rig:
+        def __init__(self, rank):
+            self.rank = rank
+
+        def gather(self, obj):
+            return parts[:self.rank] + [obj] + parts[self.rank + 1:]
+
+    bench.dump_outputs(str(tmp_path / "r1"), Rig(1), shares[1], mine[1], wins)
+    assert not (tmp_path / "r1").exists()
+    bench.dump_outputs(str(tmp_path / "r0"), Rig(0), shares[0], mine[0], wins)
+    got = {n: np.load(tmp_path / "r0" / (n + ".npy")) for n in ("z", "info", "status")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["z"], np.concatenate([r["z"] for r in ref]))
+    assert np.array_equal(got["info"], np.concatenate([r["info"] for r in ref]))
+    assert np.array_equal(got["status"], [r["status"] for r in ref])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 32 * 8 * 3 + 4 * 8)
+    bench.dump_outputs(str(tmp_path / "s"), Rig(0), shares[0], mine[0], wins)
+    idx = np.load(tmp_path / "s" / "sample_index.npy").astype(np.int64)
+    assert len(idx) == 32 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "s" / "z.npy"), got["z"][idx])
+
+
 @pytest.mark.gpu
 def test_gpu_native_chromosome_accepts_the_text_panel(ctx, tmp_path, monkeypatch):
     """The chromosome driver takes the reference's own panel format (BGZF index + data, gauss.cpp:293-399, 720-785):

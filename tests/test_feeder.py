@@ -1,10 +1,15 @@
 """CPU suite: the C++ host data layer (libgauss_host.so) against the Python restatement of the
 reference feeder (oracle/feeder_py.py), and the BGZF codec against the reference's own bgzf.c
-(oracle/_ref/libref_bgzf.so, compiled from /root/reference/src/bgzf.c where that tree exists)."""
+(a file its writer made, tests/golden/ref_bgzf.gz; and oracle/_ref/libref_bgzf.so where oracle/Makefile
+could compile it from the reference's sources)."""
 import ctypes as C
+import gzip
+import hashlib
+import json
 import os
 import sys
 import subprocess
+import zlib
 
 import numpy as np
 import pytest
@@ -28,10 +33,77 @@ def _files(st):
     return p["gwas.txt"], p["index.gz"], p["data.gz"], p["desc.txt"]
 
 
+def _bgzf_members(path):
+    """A BGZF file split into its members the way the reference's bgzf_read_block takes them, asserting every condition it
+    checks (bgzf.c check_header: gzip magic, deflate, FEXTRA, XLEN 6 with the 'BC' subfield of length 2 at byte 12, BSIZE at
+    byte 16; a member inflates into its 64 KB block) and the gzip trailer: [(file offset, inflated bytes)]."""
+    data = open(path, "rb").read()
+    out, pos = [], 0
+    while pos < len(data):
+        h = data[pos:pos + 18]
+        assert len(h) == 18 and h[:3] == b"\x1f\x8b\x08" and h[3] & 4, pos
+        assert int.from_bytes(h[10:12], "little") == 6 and h[12:14] == b"BC" and int.from_bytes(h[14:16], "little") == 2, pos
+        n = int.from_bytes(h[16:18], "little") + 1
+        assert pos + n <= len(data), pos
+        raw = zlib.decompress(data[pos + 18:pos + n - 8], -15)
+        assert len(raw) <= 65536
+        assert zlib.crc32(raw) == int.from_bytes(data[pos + n - 8:pos + n - 4], "little")
+        assert len(raw) == int.from_bytes(data[pos + n - 4:pos + n], "little")
+        out.append((pos, raw))
+        pos += n
+    return out
+
+
 def test_bgzf_against_reference_codec(study, tmp_path):
+    """The project's BGZF reader and writer against the reference's codec (bgzf.c).  Always, from recorded output of the reference
+    (tests/golden/ref_bgzf.gz, written by its bgzf_write; make_golden.py --bgzf): both readers of the project return its lines, also
+    at the virtual offsets its bgzf_tell gave; every member the project's writer emits passes the reference reader's block checks,
+    the index's offsets address the right lines, and the file ends in the reference's EOF block.  Where oracle/_ref holds the
+    reference's codec (oracle/Makefile compiles it from the reference's sources), the reference itself also reads our files."""
+    gold = os.path.join(ROOT, "tests", "golden", "ref_bgzf.gz")
+    with open(os.path.join(ROOT, "tests", "golden", "ref_bgzf.json")) as fh:
+        meta = json.load(fh)
+    with open(gold, "rb") as fh:
+        gold_bytes = fh.read()
+    text = gzip.decompress(gold_bytes)                          # an independent inflater pins the fixture's text
+    assert len(text) == meta["text_bytes"] and hashlib.sha256(text).hexdigest() == meta["text_sha256"]
+    lines = text.decode().split("\n")[:-1]
+    assert len(lines) == meta["lines"]
+    assert b"".join(raw for _, raw in _bgzf_members(gold)) == text
+    assert fp.Bgzf(gold).lines() == lines                       # the Python reader on the reference's file
+    rd = fp.Bgzf(gold)
+    for i, voff in meta["line_voffsets"]:
+        assert rd.line_at(voff) == lines[i]
+    copy_gold = str(tmp_path / "gold_copy.gz")                  # C++ reader on the reference's file, C++ writer out
+    assert api.load_host().gauss_host_bgzf_copy(gold.encode(), copy_gold.encode()) == len(lines)
+    assert b"".join(raw for _, raw in _bgzf_members(copy_gold)) == text
+    eof = _bgzf_members(gold)[-1]
+    assert eof[1] == b"" and gold_bytes[eof[0]:] == gold_bytes[-28:]
+
+    data = study["paths"]["data.gz"]
+    idx = [l.split() for l in fp.Bgzf(study["paths"]["index.gz"]).lines()]
+    copy = str(tmp_path / "copy.gz")                            # C++ reader + writer round trip of our writer's file
+    assert api.load_host().gauss_host_bgzf_copy(data.encode(), copy.encode()) == len(idx)
+    ours = ("\n".join(fp.Bgzf(data).lines()) + "\n").encode()
+    for path in (data, copy, copy_gold):
+        mem = _bgzf_members(path)
+        assert mem[-1][1] == b"" and open(path, "rb").read()[-28:] == gold_bytes[-28:]       # the reference's EOF block
+    mem = _bgzf_members(data)
+    assert b"".join(raw for _, raw in mem) == ours
+    assert b"".join(raw for _, raw in _bgzf_members(copy)) == ours
+    start, at = {}, 0                                           # every fpos in the index is a valid virtual offset (bgzf_seek)
+    for pos, raw in mem:
+        start[pos] = at
+        at += len(raw)
+    for t in idx[::37]:
+        v = int(t[6])
+        assert (v >> 16) in start and (v & 0xFFFF) < max(1, len(dict(mem)[v >> 16]))
+        line = fp.Bgzf(data).line_at(v)
+        assert ours[start[v >> 16] + (v & 0xFFFF):].startswith(line.encode() + b"\n")
+
     ref = os.path.join(ROOT, "oracle", "_ref", "libref_bgzf.so")
     if not os.path.exists(ref):
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
+        return
     lib = C.CDLL(ref)
     lib.bgzf_open.restype = C.c_void_p
     lib.bgzf_open.argtypes = [C.c_char_p, C.c_char_p]
@@ -53,13 +125,10 @@ def test_bgzf_against_reference_codec(study, tmp_path):
         lib.bgzf_close(h)
         return out
 
-    data = study["paths"]["data.gz"]
     want = ref_read_all(data)                                   # the reference codec reads our writer's file
-    ours = "\n".join(fp.Bgzf(data).lines()) + "\n"
-    assert ours.encode() == want
+    assert ours == want
     # every fpos in the index is a valid virtual offset for the reference's bgzf_seek
     h = lib.bgzf_open(data.encode(), b"r")
-    idx = [l.split() for l in fp.Bgzf(study["paths"]["index.gz"]).lines()]
     buf = C.create_string_buffer(64)
     for t in idx[::37]:
         assert lib.bgzf_seek(h, int(t[6]), 0) == 0
@@ -68,10 +137,8 @@ def test_bgzf_against_reference_codec(study, tmp_path):
         assert buf.raw[:32] == line.encode()[:32]
     lib.bgzf_close(h)
     # C++ reader + writer round trip, then read back by the reference codec
-    out = str(tmp_path / "copy.gz")
-    n = api.load_host().gauss_host_bgzf_copy(data.encode(), out.encode())
-    assert n == len(idx)
-    assert ref_read_all(out) == want
+    assert ref_read_all(copy) == want
+    assert ref_read_all(copy_gold) == text
 
 
 @pytest.mark.parametrize("env", [{"GAUSS_NO_LIBDEFLATE": "1"}, {"GAUSS_BGZF_NO_MMAP": "1"}, {"GAUSS_NO_LIBDEFLATE": "1", "GAUSS_BGZF_NO_MMAP": "1"}])

@@ -5,7 +5,7 @@ R=${1:-0}
 OUT=gpurun_out/share_trace_$R
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd - > /dev/null
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 3 --warmup 1 --emulate-world 8 --emulate-rank $R --emulate-steps 12 --no-cpu-baseline --no-i8-variant --no-e2e --no-parity-spot --no-tails-alone --no-from-text > $OUT/bench.json 2> $OUT/log.txt
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --steps 3 --warmup 1 --emulate-world 8 --emulate-rank $R --emulate-steps 12 --no-cpu-baseline --no-i8-variant --no-e2e --no-parity-spot --no-tails-alone --no-from-text > $OUT/bench.json 2> $OUT/log.txt
 python3 - <<PY
 import csv, glob, os
 f = max(glob.glob(os.path.join("$OUT", "**", "*kernel_trace.csv"), recursive=True), key=os.path.getsize)

@@ -4,7 +4,7 @@
 set -e
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/trace_small; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
-rocprofv3 --kernel-trace --output-format csv -d "$OUT/kt" -- python3 bench.py --steps 2 --warmup 1 --no-e2e --no-cpu-baseline --no-i8-variant --emulate-world 8 > "$OUT/bench.json" 2> "$OUT/log.txt"
+rocprofv3 --kernel-trace --output-format csv -d "$OUT/kt" -- python3 bench.py --full --steps 2 --warmup 1 --no-e2e --no-cpu-baseline --no-i8-variant --emulate-world 8 > "$OUT/bench.json" 2> "$OUT/log.txt"
 python3 - <<PY
 import csv, glob
 f = max(glob.glob("$OUT/kt/**/*kernel_trace.csv", recursive=True), key=lambda p: __import__("os").path.getsize(p))
