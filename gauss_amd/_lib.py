@@ -16,6 +16,7 @@ MODE_POOLED = 0
 MODE_WEIGHTED = 1
 ST_CLAMPED = 1
 ST_NONFINITE = 2
+ST_NOCONV = 4
 WIN_IMPUTE = 0
 WIN_QCAT = 1
 WIN_LD = 2
@@ -55,6 +56,7 @@ SYMBOLS = [
     "gauss_ld_rows", "gauss_gene_ld_batch_rows", "gauss_job_run", "gauss_job_fetch", "gauss_job_destroy", "gauss_job_span_ms", "gauss_job_profile",
     "gauss_job_profile_get", "gauss_job_work", "gauss_job_stats", "gauss_synth_device",
     "gauss_store_upload_async", "gauss_store_upload_fd_async", "gauss_store_wait", "gauss_store_alloc", "gauss_store_fill", "gauss_store_fill_fd", "gauss_store_upload_fd", "gauss_hip_context_id", "gauss_hip_add_destroy_hook", "gauss_hip_trim_cache", "gauss_hip_source_hash", "gauss_hip_counters", "gauss_job_counters", "gauss_hip_queues",
+    "gauss_pop_weights",
 ]
 
 
@@ -123,6 +125,7 @@ def load():
     lib.gauss_hip_queues.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.gauss_synth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _ip, C.c_int,
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]
+    lib.gauss_pop_weights.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_double, _dp, _ip]
     _lib = lib
     return lib
 

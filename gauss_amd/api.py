@@ -6,6 +6,7 @@
     distmix(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, ...)
     jepeg(study_pop, input_file, annotation_file, ...)
     jepegmix(pop_wgt_df, input_file, annotation_file, ...)
+    afmix(input_file, reference_index_file, ...) / cpw2(...)   population weights from allele frequencies
 
 Each is a thin ctypes call into libgauss_host.so (C++ host data layer) which delegates the numeric
 hot path to libgauss_hip.so (HIP).  A ``pop_wgt_df`` is anything with two columns (population
@@ -25,7 +26,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libgauss_host.so")
 
 KIND_COMPUTELD, KIND_DIST, KIND_DISTMIX, KIND_JEPEG, KIND_JEPEGMIX, KIND_QCAT, KIND_QCATMIX, \
-    KIND_PREP_QCAT, KIND_PREP_RECESSIVE = range(9)
+    KIND_PREP_QCAT, KIND_PREP_RECESSIVE, KIND_AFMIX, KIND_CPW2 = range(11)
 
 HOST_SYMBOLS = [
     "gauss_host_last_error", "gauss_table_nrow", "gauss_table_ncol", "gauss_table_colname",
@@ -42,6 +43,7 @@ HOST_SYMBOLS = [
     "gauss_table_message", "gauss_table_strcol_fixed", "gauss_host_panel_device_rows", "gauss_prepared_store_rows",
     "gauss_host_jepeg_gene_tail", "gauss_host_plan_cost",
     "gauss_host_jepeg_rank", "gauss_host_jepeg_genome", "gauss_prepared_jepeg_plan", "gauss_prepared_jepeg_finish",
+    "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs",
 ]
 
 
@@ -109,6 +111,9 @@ def load_host():
     h.gauss_host_prep_zmix.argtypes = [_vp, _cp, _cp, _cp, _cp, C.c_int, C.POINTER(_vp)]
     for f in (h.gauss_host_prep_zmix2, h.gauss_host_prep_zmix3, h.gauss_host_prep_zmix4):
         f.argtypes = [_vp, _cp, _cp, _cp, _cp, C.c_int, C.c_int, C.POINTER(_vp)]
+    h.gauss_host_afmix.argtypes = [_vp, _cp, _cp, _cp, _cp, C.c_int, C.POINTER(_vp)]
+    h.gauss_host_cpw2.argtypes = [_vp, _cp, _cp, _cp, _cp, C.c_int, C.POINTER(_vp)]
+    h.gauss_host_popwgt_inputs.argtypes = [C.c_int, _cp, _cp, _cp, _cp, C.c_int, C.POINTER(_vp)]
     h.gauss_host_pack_panel.restype = _i64
     h.gauss_host_pack_panel.argtypes = [_cp, _cp, _cp, _cp]
     h.gauss_prepared_packed_store.argtypes = [_vp, C.POINTER(C.c_void_p), C.POINTER(_i64), C.POINTER(_i64)]
@@ -366,6 +371,57 @@ def prep_zmix_variant(variant, input_file, reference_index_file, reference_data_
     groups = [h.gauss_table_message(out, k).decode() for k in range(h.gauss_table_n_messages(out))]
     df = _table(h, out)[0]
     return dict(data_mat=named["data_mat"], pairs=named["pairs"].astype(np.int64), snps=df, groups=groups)
+
+
+def _popwgt(kind, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval, ctx, detail):
+    h = load_host()
+    out = _vp()
+    fn = h.gauss_host_afmix if kind == KIND_AFMIX else h.gauss_host_cpw2
+    _hcheck(fn(_ctx(ctx), _enc(input_file), _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file),
+               int(interval or 0), C.byref(out)))
+    named = _named(h, out)
+    msgs = [h.gauss_table_message(out, k).decode() for k in range(h.gauss_table_n_messages(out))]
+    df = _table(h, out)[0]
+    if not detail:
+        return df
+    return df, dict(w_raw=named["w_raw"].reshape(-1), w_interval=named["w_interval"].reshape(-1, len(named["w_raw"])),
+                    status=named["status"].reshape(-1).astype(np.int32), messages=msgs)
+
+
+def afmix(input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval=None, ctx=None, detail=False):
+    """afmix() of the reference (afmix.cpp:30-111): ancestry proportions of a study from its allele frequencies.
+
+    input_file: header, then ``rsid chr bp a1 a2 af1`` per line.  interval=None means 1000, as in R.  Returns a DataFrame
+    with columns ``sup.pop, pop, wgt`` (populations with a positive weight, panel order).  detail=True returns
+    ``(df, dict(w_raw, w_interval, status, messages))``: the weights of every population before the clamp at 0 and the
+    rounding, the per-interval weights, their GAUSS_ST_* status bits and any message (e.g. interval <= S < 2 interval:
+    every weight is NaN and the frame is empty, as in the reference).
+
+    To weight distmix / qcatmix / jepegmix / computeLD with the result, pass ``df[["pop", "wgt"]]`` as pop_wgt_df (the
+    entry points read the first two columns, as R does)."""
+    return _popwgt(KIND_AFMIX, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval, ctx, detail)
+
+
+def cpw2(input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval=None, ctx=None, detail=False):
+    """cpw2() of the reference (cpw2.cpp:31-107): afmix on arcsine-square-root transformed allele frequencies.  Returns a
+    DataFrame with columns ``pop, wgt`` -- directly usable as a pop_wgt_df; detail as in afmix."""
+    return _popwgt(KIND_CPW2, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval, ctx, detail)
+
+
+def popwgt_inputs(kind, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval=None):
+    """gauss_host_popwgt_inputs (no GPU): the data layer of afmix (kind=KIND_AFMIX) / cpw2 (KIND_CPW2).  Returns
+    (snps DataFrame rsid chr bp a1 a2 af1study in the reference's order, x [S, P + 1] interval-major matrix as the kernel
+    receives it, interval_off [interval + 1])."""
+    h = load_host()
+    out = _vp()
+    _hcheck(h.gauss_host_popwgt_inputs(int(kind), _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
+                                       _enc(reference_pop_desc_file), int(interval or 0), C.byref(out)))
+    named = _named(h, out)
+    df = _table(h, out)[0]
+    x = named["x"]
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    return df, np.ascontiguousarray(x), named["interval_off"].reshape(-1).astype(np.int64)
 
 
 def jepeg(study_pop, input_file, annotation_file, reference_index_file, reference_data_file, reference_pop_desc_file,

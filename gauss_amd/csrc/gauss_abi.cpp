@@ -388,6 +388,54 @@ int gauss_ld_per_pop_pairs(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64
     return GAUSS_OK;
 }
 
+int gauss_pop_weights(gauss_ctx* ctx, const double* x, const int64_t* interval_off, int n_interval, int n_pop, double min_abs_eig,
+                      double* out_w_interval, int32_t* out_status)
+{
+    if (!ctx || !interval_off || !out_w_interval || n_interval < 1) return fail(GAUSS_E_INVALID, "bad arguments to gauss_pop_weights");
+    if (n_pop < 1 || n_pop > 64)
+        return fail(GAUSS_E_INVALID, "gauss_pop_weights: n_pop = %d populations; the device eigen-solve holds 1 .. 64", n_pop);
+    if (interval_off[0] != 0) return fail(GAUSS_E_INVALID, "gauss_pop_weights: interval_off[0] must be 0");
+    for (int i = 0; i < n_interval; i++)
+        if (interval_off[i + 1] < interval_off[i]) return fail(GAUSS_E_INVALID, "gauss_pop_weights: interval_off is not ascending at %d", i);
+    const int64_t S = interval_off[n_interval];
+    if (S > 0 && !x) return fail(GAUSS_E_INVALID, "gauss_pop_weights: x is NULL");
+    const int nc = n_pop + 1, npair = nc * (nc + 1) / 2;
+    // chunks of at most PW_CHUNK rows, each inside one interval: the split depends on the interval sizes alone
+    constexpr int64_t PW_CHUNK = 512;
+    std::vector<PwChunk> chunks;
+    std::vector<int> chunk_off((size_t)n_interval + 1, 0);
+    for (int i = 0; i < n_interval; i++) {
+        for (int64_t r = interval_off[i]; r < interval_off[i + 1]; r += PW_CHUNK)
+            chunks.push_back(PwChunk{(long long)r, (long long)std::min(r + PW_CHUNK, interval_off[i + 1]), i, 0});
+        if (chunks.size() > (size_t)INT32_MAX / 4) return fail(GAUSS_E_INVALID, "gauss_pop_weights: too many rows");
+        chunk_off[(size_t)i + 1] = (int)chunks.size();
+    }
+    const int n_chunk = (int)chunks.size();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf d_x, d_chunks, d_coff, d_off, d_part1, d_mean, d_part2, d_w, d_status;
+    const size_t x_bytes = sizeof(double) * (size_t)S * nc;
+    if (d_x.alloc(ctx, x_bytes) != hipSuccess || d_chunks.alloc(ctx, sizeof(PwChunk) * chunks.size()) != hipSuccess ||
+        d_coff.alloc(ctx, sizeof(int) * chunk_off.size()) != hipSuccess || d_off.alloc(ctx, sizeof(int64_t) * ((size_t)n_interval + 1)) != hipSuccess ||
+        d_part1.alloc(ctx, sizeof(double) * (size_t)n_chunk * nc) != hipSuccess || d_mean.alloc(ctx, sizeof(double) * (size_t)n_interval * nc) != hipSuccess ||
+        d_part2.alloc(ctx, sizeof(double) * (size_t)n_chunk * npair) != hipSuccess ||
+        d_w.alloc(ctx, sizeof(double) * (size_t)n_interval * n_pop) != hipSuccess || d_status.alloc(ctx, sizeof(int) * (size_t)n_interval) != hipSuccess)
+        return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes of allele frequencies and workspace) failed", x_bytes);
+    if (x_bytes) HIPCHK(hipMemcpyAsync(d_x.p, x, x_bytes, hipMemcpyHostToDevice, st));
+    if (n_chunk) HIPCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(PwChunk) * chunks.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_coff.p, chunk_off.data(), sizeof(int) * chunk_off.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_off.p, interval_off, sizeof(int64_t) * ((size_t)n_interval + 1), hipMemcpyHostToDevice, st));
+    launch_pop_weights(d_x.as<double>(), n_pop, d_chunks.as<PwChunk>(), n_chunk, d_coff.as<int>(), d_off.as<long long>(), n_interval,
+                       min_abs_eig, d_part1.as<double>(), d_mean.as<double>(), d_part2.as<double>(), d_w.as<double>(), d_status.as<int>(), st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_w_interval, d_w.p, sizeof(double) * (size_t)n_interval * n_pop, hipMemcpyDeviceToHost, st));
+    std::vector<int> stat((size_t)n_interval);
+    HIPCHK(hipMemcpyAsync(stat.data(), d_status.p, sizeof(int) * stat.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (out_status) for (int i = 0; i < n_interval; i++) out_status[i] = stat[(size_t)i];
+    return GAUSS_OK;
+}
+
 int gauss_gram_counts(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int n_samples, int64_t ld, int64_t* out_counts)
 {
     if (!out_counts) return fail(GAUSS_E_INVALID, "out_counts is NULL");

@@ -224,6 +224,11 @@ struct ExportD {
     int rows, width, pitch, pad_;
 };
 void launch_export_rows(const ExportD* d_exports, int n, long long max_elems, hipStream_t s);
+// Population weights (k_popwgt.hip): chunk c is rows [r0, r1) of interval iv of the interval-major matrix
+struct PwChunk { long long r0, r1; int iv, pad_; };
+void launch_pop_weights(const double* d_x, int n_pop, const PwChunk* d_chunks, int n_chunk, const int* d_chunk_off,
+                        const long long* d_off, int n_interval, double eps, double* d_part1, double* d_mean, double* d_part2,
+                        double* d_w, int* d_status, hipStream_t s);
 void launch_synth(uint8_t* d_out, int n_snp, long long ld, const int* d_pop_off, int n_pop,
                   int n_samples, const float* d_thr, const float* d_rho, uint64_t seed,
                   hipStream_t s);

@@ -184,6 +184,24 @@ int ReadInputZ(SnpMap& m, const Args& a, bool All)
     return 0;
 }
 
+// ReadInputAf (gauss.cpp:211-262; cpw2's read_input_cpw2 is the same): header, then rsid chr bp a1 a2 af1 -- the layout of a GWAS
+// summary file with the allele frequency where z would be, so the parsed image is shared with ReadInputZ.  No window, no filter;
+// a key listed twice ends with its later row.
+int ReadInputAf(SnpMap& m, const Args& a)
+{
+    std::string err;
+    std::shared_ptr<const GwasCache> gw = load_gwas_cached(a.input_file, err);
+    if (!gw) return herr("%s", err.c_str());
+    for (const GwasRow& r : gw->rows) {
+        SnpPtr s = m.make();
+        s->rsid = r.rsid; s->chr = r.chr; s->bp = r.bp; s->a1 = r.a1; s->a2 = r.a2; s->af1study = r.z;
+        MapKey key{r.chr, r.bp, r.a1, r.a2};
+        auto it = (m.empty() || m.rbegin()->first < key) ? m.emplace_hint(m.end(), std::move(key), SnpPtr()) : m.try_emplace(std::move(key)).first;
+        it->second = std::move(s);
+    }
+    return 0;
+}
+
 // Parsed image of a BGZF text index file (rsid chr bp a1 a2 af1ref fpos per line), kept per process and
 // shared by every call that names the same file (path + size + mtime).  Entries are in file order and carry the
 // reference's parsing state semantics: a field that fails to parse keeps the value of the previous line, as the
@@ -267,6 +285,7 @@ int merge_index_entry(SnpMap& m, const Args& a, bool All, const std::string& rsi
         SnpPtr s = std::move(it2->second);
         m.erase(it2);
         s->rsid = rsid; s->a1 = a1; s->a2 = a2; s->z = s->z * (-1); s->type = 1; s->fpos = fpos;
+        s->af1study = 1 - s->af1study;      // gauss.cpp:496
         m[MapKey{chr, bp, a1, a2}] = std::move(s);
     } else if (it1 == m.end() && it2 == m.end()) {
         if (!All) {       // gauss.cpp:373-385; ReadReferenceIndexAll never adds unmeasured SNPs
@@ -328,6 +347,7 @@ int ReadReferenceIndex(SnpMap& m, const Args& a, bool All)
                         SnpPtr sp = std::move(it->second);
                         m.erase(it);
                         sp->rsid = pk.str(s.rsid); sp->a1 = pa1; sp->a2 = pa2; sp->z = sp->z * (-1); sp->type = 1; sp->fpos = i;
+                        sp->af1study = 1 - sp->af1study;      // gauss.cpp:496
                         m[MapKey{chr, bp, pa1, pa2}] = std::move(sp);
                     }
                 }
@@ -430,6 +450,7 @@ void load_line(BgzfReader& fp, Snp& s, const Args& a, std::vector<double>* af_ou
 // Panel lines are independent: inflate + split them on several host threads, each with its own reader
 // (the reference reads them one by one through a single BGZF handle, gauss.cpp:546-566).
 static std::atomic<int> g_host_threads{4};
+int host_threads() { return g_host_threads.load(); }
 
 static int preload_lines(SnpMap& m, const Args& a, bool want_af, std::vector<std::vector<double>>* afs)
 {

@@ -6,6 +6,7 @@
 //                     packed-panel cache, prepare()
 //   host_tables.cpp   result tables, the JEPEG k x k tail, the table accessors of the C ABI
 //   host_calls.cpp    the one-window / one-call entry points (computeLD, dist, distmix, qcat, prep_*, jepeg, jepegmix)
+//   host_popwgt.cpp   afmix / cpw2: study allele frequencies against the panel's, per-interval weights on the GPU
 //   host_chrom.cpp    resident panels, the chromosome driver's own window, gauss_host_impute_chromosome / _genome
 #pragma once
 #pragma GCC visibility push(default)
@@ -105,6 +106,7 @@ struct Snp {
     long long bp = -1;
     std::string a1 = ".", a2 = ".";
     double af1mix = -1.0, af1ref = -1.0;
+    double af1study = -1.0;        // afmix / cpw2: the study's allele frequency (Snp::af1study_, ReadInputAf gauss.cpp:211-262)
     double z = 0.0, info = -1.0;
     int qcat_m = 0;                // snp.cpp:26-28
     double qcat_t = 0.0, qcat_chisq = 0.0;
@@ -454,6 +456,8 @@ void init_pop_flag_wgt_vec(Args& a);
 void set_pop_wgt_map(Args& a, const char* const* names, const double* w, int n);
 std::shared_ptr<const GwasCache> load_gwas_cached(const std::string& path, std::string& err);
 int ReadInputZ(SnpMap& m, const Args& a, bool All);
+int ReadInputAf(SnpMap& m, const Args& a);
+int host_threads();
 int merge_index_entry(SnpMap& m, const Args& a, bool All, const std::string& rsid, int chr, long long bp,
                              const std::string& a1, const std::string& a2, long long fpos);
 int ReadReferenceIndex(SnpMap& m, const Args& a, bool All);

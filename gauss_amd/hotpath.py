@@ -146,6 +146,21 @@ def ld_per_pop(geno, pop_off, ctx=None):
     return out
 
 
+def pop_weights(x, interval_off, min_abs_eig=1e-5, ctx=None):
+    """gauss_pop_weights: per-interval population weights W_i = MakePosDef(Cxx)^-1 Cxy of an interval-major matrix
+    x [S, P + 1] (rows [af1study, AF_0 .. AF_(P-1)]; interval i = rows interval_off[i] .. interval_off[i+1]).
+    Returns (w [n_interval, P], status [n_interval] of GAUSS_ST_* bits)."""
+    ctx = ctx or default_context()
+    xa = np.ascontiguousarray(x, dtype=np.float64)
+    off = np.ascontiguousarray(interval_off, dtype=np.int64)
+    n_int, P = len(off) - 1, xa.shape[1] - 1
+    w = np.zeros((max(n_int, 0), max(P, 0)))
+    st = np.zeros(max(n_int, 0), dtype=np.int32)
+    check(ctx.lib.gauss_pop_weights(ctx.handle, xa.ctypes.data_as(_dp), off.ctypes.data_as(C.POINTER(C.c_int64)), n_int, P,
+                                    float(min_abs_eig), w.ctypes.data_as(_dp), st.ctypes.data_as(_ip)))
+    return w, st
+
+
 def gene_ld_batch(geno, pop_off, gene_off, pop_wgt=None, mode=MODE_POOLED, diag=1.1, ctx=None):
     """LD blocks of all genes in one launch; returns a list of (n_g, n_g) arrays."""
     ctx = ctx or default_context()

@@ -168,6 +168,14 @@ def write_gwas(path, rsid, chr_, bp, a1, a2, z):
             f.write(f"{rsid[i]} {chr_[i]} {bp[i]} {a1[i]} {a2[i]} {float(z[i])!r}\n")
 
 
+def write_study_af(path, rsid, chr_, bp, a1, a2, af1):
+    """Study allele-frequency file of afmix() / cpw2(): header + ``rsid chr bp a1 a2 af1`` (ReadInputAf, gauss.cpp:211-262)."""
+    with open(path, "w") as f:
+        f.write("rsid chr bp a1 a2 af1\n")
+        for i in range(len(rsid)):
+            f.write(f"{rsid[i]} {chr_[i]} {bp[i]} {a1[i]} {a2[i]} {float(af1[i])!r}\n")
+
+
 def write_annotation(path, rows):
     """rows: iterable of (rsid, chr, bp, a1, a2, geneid, categ, wgt)."""
     with open(path, "w") as f:

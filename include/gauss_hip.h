@@ -54,6 +54,7 @@ extern "C" {
 /* per-window status bits returned in out_status */
 #define GAUSS_ST_CLAMPED    1  /* MakePosDef rebuilt B11 (some eigenvalue < min_abs_eig, util.cpp:310) */
 #define GAUSS_ST_NONFINITE  2  /* B11 not finite / not factorisable: outputs are NaN like the reference's */
+#define GAUSS_ST_NOCONV     4  /* gauss_pop_weights: the Jacobi eigen-clamp hit its sweep cap (outputs NaN, NONFINITE set too) */
 
 typedef struct gauss_ctx gauss_ctx;
 typedef struct gauss_job gauss_job;
@@ -269,6 +270,18 @@ int gauss_ld_per_pop(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64_t ld,
 int gauss_ld_per_pop_pairs(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64_t ld, const int32_t* pop_off, int n_pop,
                            const int32_t* pop_group, int n_group, const int32_t* pair_i, const int32_t* pair_j, int64_t n_pairs,
                            double* out);
+
+/* Population weights from allele frequencies: the numeric core of afmix() / cpw2() (afmix.cpp:114-215, cpw2.cpp:110-211).
+ * x is an interval-major matrix of n_pop + 1 columns, row-major: rows [interval_off[i], interval_off[i+1]) belong to interval i
+ * and hold [af1study, AF_pop0 .. AF_pop(n_pop-1)] (cpw2: already asin(sqrt(.))-transformed by the caller).  For every interval:
+ * the two-pass sample covariance C of the columns (CalCovMat, util.cpp:205-213, 243-253), Cxy = C[1:, 0], Cxx = C[1:, 1:];
+ * MakePosDef(Cxx, min_abs_eig) (util.cpp:302-318: rebuilt as V max(Lambda, min_abs_eig) V^T only if an eigenvalue is below
+ * min_abs_eig); W_i = Cxx^-1 Cxy.  out_w_interval is [n_interval x n_pop] row-major; out_status (may be NULL) gets per interval
+ * GAUSS_ST_CLAMPED when Cxx was rebuilt, GAUSS_ST_NONFINITE when W_i is NaN (non-finite input, an interval of fewer than two
+ * rows), GAUSS_ST_NOCONV with it if the eigen-solve did not converge.  1 <= n_pop <= 64.  Blocking; the bits do not depend on
+ * the run.  The caller accumulates W = sum_i W_i / n_interval in interval order (afmix.cpp:192-195). */
+int gauss_pop_weights(gauss_ctx* ctx, const double* x, const int64_t* interval_off, int n_interval, int n_pop,
+                      double min_abs_eig, double* out_w_interval, int32_t* out_status);
 
 /* Exact co-occurrence counts sum_n x_i[n] x_j[n] over all columns -- the integer the reference
  * accumulates as `sumxy` (util.cpp:62,114).  out: S x S int64, row-major.  Integer parity hook. */

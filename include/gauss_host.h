@@ -17,6 +17,8 @@
  *   prep_recessive_impute(chr,...,pop_wgt_df,...)           gauss_host_prep_recessive_impute
  *                                                           prep_qcatmix.cpp:36-316
  *   prep_zmix5(input_file,...,percentile,interval)          gauss_host_prep_zmix5 zmix.cpp:44-190
+ *   afmix(input_file,...,interval)                          gauss_host_afmix     afmix.cpp:30-215
+ *   cpw2(input_file,...,interval)                           gauss_host_cpw2      cpw2.cpp:31-211
  *
  * Same argument meaning, same defaults (af1_cutoff NaN = R's NULL -> 0.01, dist.cpp:53-57), same
  * row order (std::map order on (chr,bp,a1,a2), gauss.h:72-99), same column names and types as
@@ -56,6 +58,8 @@ typedef struct gauss_prepared gauss_prepared; /* one window/gene set after the h
 #define GAUSS_KIND_QCATMIX   6
 #define GAUSS_KIND_PREP_QCAT 7
 #define GAUSS_KIND_PREP_RECESSIVE 8
+#define GAUSS_KIND_AFMIX     9
+#define GAUSS_KIND_CPW2      10
 
 const char* gauss_host_last_error(void);
 
@@ -196,6 +200,27 @@ int gauss_host_prep_zmix4(gauss_ctx* ctx, const char* input_file, const char* re
                           const char* reference_pop_desc_file, int interval, int offset, gauss_table** out);
 int gauss_host_prep_zmix5_sup(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
                               const char* reference_pop_desc_file, double percentile, int interval, gauss_table** out);
+
+/* afmix() / cpw2(): population weights of a mixed-ancestry study from allele frequencies (afmix.cpp:30-215, cpw2.cpp:31-211).
+ * input_file: header, then "rsid chr bp a1 a2 af1" per line (ReadInputAf, gauss.cpp:211-262; a key listed twice keeps its last
+ * row).  The study is merged with the panel index like ReadReferenceIndexAll (gauss.cpp:431-518: a SNP whose alleles the panel
+ * lists the other way round takes the panel's order and af1 -> 1 - af1; both orders in the study is "ERROR: input file contains
+ * duplicates").  The S measured SNPs, in map order, are dealt round-robin to `interval` intervals (<= 0: 1000, R's NULL); each
+ * interval's rows [af1, AF of every panel population] (cpw2: asin(sqrt(.)) of each) give W_i = MakePosDef(Cxx)^-1 Cxy on the GPU
+ * (gauss_pop_weights); W = sum_i W_i / interval, negative -> 0, else rounded to 3 decimals.  S < interval is an error naming
+ * both.  Result: the populations with wgt > 0 in panel order, columns sup.pop pop wgt (afmix) or pop wgt (cpw2); named matrices
+ * "w_raw" [P x 1] (W of every population before the clamp and rounding, NaN kept), "w_interval" [interval x P] and "status"
+ * [interval x 1] (GAUSS_ST_* bits); a message when weights are NaN -- an interval with one SNP (interval <= S < 2 interval)
+ * has covariance 0/0 and the reference returns no population. */
+int gauss_host_afmix(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                     const char* reference_pop_desc_file, int interval, gauss_table** out);
+int gauss_host_cpw2(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                    const char* reference_pop_desc_file, int interval, gauss_table** out);
+/* The host data layer of afmix / cpw2 alone (no GPU; kind = GAUSS_KIND_AFMIX or GAUSS_KIND_CPW2): the measured SNPs in the
+ * reference's order (rsid chr bp a1 a2 af1study, af1study after the allele flip, untransformed), named matrices "x" [S x (P + 1)],
+ * the interval-major matrix exactly as gauss_pop_weights receives it, and "interval_off" [(interval + 1) x 1]. */
+int gauss_host_popwgt_inputs(int kind, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                             const char* reference_pop_desc_file, int interval, gauss_table** out);
 
 /* ---- packed panel -------------------------------------------------
  * Converts the reference's BGZF text panel (index + data + population description) into one mmap-able
