@@ -43,7 +43,7 @@ HOST_SYMBOLS = [
     "gauss_table_message", "gauss_table_strcol_fixed", "gauss_host_panel_device_rows", "gauss_prepared_store_rows",
     "gauss_host_jepeg_gene_tail", "gauss_host_plan_cost",
     "gauss_host_jepeg_rank", "gauss_host_jepeg_genome", "gauss_prepared_jepeg_plan", "gauss_prepared_jepeg_finish",
-    "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs",
+    "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
 ]
 
 
@@ -114,6 +114,8 @@ def load_host():
     h.gauss_host_afmix.argtypes = [_vp, _cp, _cp, _cp, _cp, C.c_int, C.POINTER(_vp)]
     h.gauss_host_cpw2.argtypes = [_vp, _cp, _cp, _cp, _cp, C.c_int, C.POINTER(_vp)]
     h.gauss_host_popwgt_inputs.argtypes = [C.c_int, _cp, _cp, _cp, _cp, C.c_int, C.POINTER(_vp)]
+    h.gauss_host_zmix.argtypes = [_vp, _cp, _cp, _cp, _cp, _dbl, C.c_int, C.c_int, C.POINTER(_vp)]
+    h.gauss_host_zmix_qp.argtypes = [_dp, _dp, C.c_int, _dp, _dp]
     h.gauss_host_pack_panel.restype = _i64
     h.gauss_host_pack_panel.argtypes = [_cp, _cp, _cp, _cp]
     h.gauss_prepared_packed_store.argtypes = [_vp, C.POINTER(C.c_void_p), C.POINTER(_i64), C.POINTER(_i64)]
@@ -408,7 +410,52 @@ def cpw2(input_file, reference_index_file, reference_data_file, reference_pop_de
     return _popwgt(KIND_CPW2, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval, ctx, detail)
 
 
-def popwgt_inputs(kind, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval=None):
+ZMIX_LEVELS = {"population": 0, "superpopulation": 1}      # GAUSS_ZMIX_POPULATION / GAUSS_ZMIX_SUPERPOPULATION
+
+
+def zmix(input_file, reference_index_file, reference_data_file, reference_pop_desc_file, percentile=0.9, interval=10,
+         level="population", ctx=None, detail=False):
+    """zmix() of the reference (zmix.R): ancestry proportions of a study from its Z-scores.
+
+    input_file: header, then ``rsid chr bp a1 a2 z`` per line.  percentile / interval: the selection of prep_zmix5 (None
+    means zmix.R's defaults 0.9 / 10).  level: "population" (columns ``Population, SuperPopulation, Weight``, every population
+    in description order) or "superpopulation" (``SuperPopulation, Weight``, order of first appearance).  The normal equations
+    of the pair regression are reduced on the GPU; the constrained QP of solve.QP runs on the host.  detail=True returns
+    ``(df, dict(dmat, dvec, w_unrounded, yty, n_snp, n_pairs, n_rows))``.
+
+    To weight distmix / qcatmix / jepegmix / computeLD with a population-level result, pass ``df[["Population", "Weight"]]``
+    as pop_wgt_df."""
+    if level not in ZMIX_LEVELS:
+        raise ValueError(f"level must be one of {sorted(ZMIX_LEVELS)}, not {level!r}")
+    h = load_host()
+    out = _vp()
+    _hcheck(h.gauss_host_zmix(_ctx(ctx), _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
+                              _enc(reference_pop_desc_file), _af(percentile), int(interval or 0), ZMIX_LEVELS[level], C.byref(out)))
+    named = _named(h, out)
+    df = _table(h, out)[0]
+    if not detail:
+        return df
+    G = len(named["dvec"])
+    return df, dict(dmat=np.asarray(named["dmat"]).reshape(G, G), dvec=named["dvec"].reshape(-1),
+                    w_unrounded=named["w_unrounded"].reshape(-1), yty=float(named["yty"][0]),
+                    n_snp=int(named["n_snp"][0]), n_pairs=int(named["n_pairs"][0]), n_rows=int(named["n_rows"][0]))
+
+
+def zmix_qp(D, d):
+    """gauss_host_zmix_qp (no GPU): zmix's constrained QP (quadprog::solve.QP's Goldfarb-Idnani method) on D [P, P], d [P].
+    Returns (w_unrounded: solution / its sum, w_final: rounded to 5 decimals and normalised again)."""
+    Da = np.ascontiguousarray(D, dtype=np.float64)
+    da = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+    P = da.shape[0]
+    if Da.shape != (P, P):
+        raise ValueError(f"D has shape {Da.shape}, expected ({P}, {P})")
+    w_unr, w_fin = np.zeros(P), np.zeros(P)
+    _hcheck(load_host().gauss_host_zmix_qp(Da.ctypes.data_as(_dp), da.ctypes.data_as(_dp), P, w_unr.ctypes.data_as(_dp),
+                                           w_fin.ctypes.data_as(_dp)))
+    return w_unr, w_fin
+
+
+def popwgt_inputs(kind,input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval=None):
     """gauss_host_popwgt_inputs (no GPU): the data layer of afmix (kind=KIND_AFMIX) / cpw2 (KIND_CPW2).  Returns
     (snps DataFrame rsid chr bp a1 a2 af1study in the reference's order, x [S, P + 1] interval-major matrix as the kernel
     receives it, interval_off [interval + 1])."""

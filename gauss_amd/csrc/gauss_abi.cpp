@@ -388,6 +388,67 @@ int gauss_ld_per_pop_pairs(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64
     return GAUSS_OK;
 }
 
+int gauss_zmix_normal_eq(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64_t ld, const int32_t* pop_off, int n_pop,
+                         const int32_t* pop_group, int n_group, const double* z, double* out_xtx, double* out_xty, double* out_yty,
+                         int64_t* out_n_rows)
+{
+    if (!ctx || !geno || !pop_off || !z || !out_xtx || !out_xty || !out_yty || !out_n_rows)
+        return fail(GAUSS_E_INVALID, "bad arguments to gauss_zmix_normal_eq");
+    if (n_snp < 2) return fail(GAUSS_E_INVALID, "need at least two SNPs");
+    if (n_pop < 1) return fail(GAUSS_E_INVALID, "n_pop < 1");
+    if (!pop_group) n_group = n_pop;
+    if (n_group < 1 || n_group > 64)
+        return fail(GAUSS_E_INVALID, "gauss_zmix_normal_eq: %d groups; the normal equations hold 1 .. 64", n_group);
+    if (pop_group)
+        for (int p = 0; p < n_pop; p++)
+            if (pop_group[p] < 0 || pop_group[p] >= n_group) return fail(GAUSS_E_INVALID, "pop_group[%d] = %d is outside 0..%d", p, pop_group[p], n_group - 1);
+    std::vector<double> ones((size_t)n_pop, 1.0);
+    WinSpec w;
+    w.mode = GAUSS_MODE_WEIGHTED; w.n_pop = n_pop; w.pop_off = pop_off; w.pop_wgt = ones.data();
+    w.M = n_snp; w.U = 0; w.geno_m = geno; w.geno_u = nullptr; w.ld = ld; w.z1 = nullptr;
+    w.lambda = 0; w.eps = 0; w.diag = 1.0; w.ld_only = 1; w.gene_off = nullptr; w.n_gene = 0;
+    w.gram_only = 1;
+    gauss_job* job = nullptr;
+    std::vector<WinSpec> specs{w};
+    int rc = job_build(ctx, specs, 0, &job);
+    if (rc) return rc;
+    std::unique_ptr<gauss_job, void (*)(gauss_job*)> guard(job, job_free);
+    // pack + Gram only (as gauss_ld_per_pop_pairs): the correlations are formed and reduced in k_zmix.hip, never stored
+    hipStream_t st = ctx->stream;
+    launch_pack_stats(job->d_probs, job->d_rowmap, job->n_rows, st);
+    launch_gram(job->d_items, job->n_items, job->gram_i8, st);
+    HIPCHK(hipGetLastError());
+    const int npair = job->plans[0].p.npair;
+    const int ne = (n_group + 1) * (n_group + 2) / 2;
+    DevBuf d_z, d_grp, d_part, d_part_n, d_out, d_out_n;
+    const size_t part_bytes = sizeof(double) * (size_t)std::max(npair, 1) * ne;
+    if (d_z.alloc(ctx, sizeof(double) * (size_t)n_snp) != hipSuccess || d_grp.alloc(ctx, sizeof(int) * (size_t)n_pop) != hipSuccess ||
+        d_part.alloc(ctx, part_bytes) != hipSuccess || d_part_n.alloc(ctx, sizeof(long long) * (size_t)std::max(npair, 1)) != hipSuccess ||
+        d_out.alloc(ctx, sizeof(double) * (size_t)ne) != hipSuccess || d_out_n.alloc(ctx, sizeof(long long)) != hipSuccess)
+        return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes of normal-equation partials) failed", part_bytes);
+    HIPCHK(hipMemcpyAsync(d_z.p, z, sizeof(double) * (size_t)n_snp, hipMemcpyHostToDevice, st));
+    if (pop_group) HIPCHK(hipMemcpyAsync(d_grp.p, pop_group, sizeof(int) * (size_t)n_pop, hipMemcpyHostToDevice, st));
+    launch_zmix_normal_eq(job->d_probs, 0, npair, pop_group ? d_grp.as<int>() : nullptr, n_group, d_z.as<double>(), d_part.as<double>(),
+                          d_part_n.as<long long>(), d_out.as<double>(), d_out_n.as<long long>(), st);
+    HIPCHK(hipGetLastError());
+    std::vector<double> tri((size_t)ne);
+    long long nrows = 0;
+    HIPCHK(hipMemcpyAsync(tri.data(), d_out.p, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&nrows, d_out_n.p, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // upper triangle of [y | X]^T [y | X] in row order: (0, 0) = y^T y, (0, b) = (X^T y)[b - 1], (a, b) = (X^T X)[a - 1][b - 1]
+    const int nc = n_group + 1;
+    size_t k = 0;
+    for (int a = 0; a < nc; a++)
+        for (int b = a; b < nc; b++, k++) {
+            const double v = tri[k];
+            if (a == 0) { if (b == 0) *out_yty = v; else out_xty[b - 1] = v; }
+            else { out_xtx[(size_t)(a - 1) * n_group + (b - 1)] = v; out_xtx[(size_t)(b - 1) * n_group + (a - 1)] = v; }
+        }
+    *out_n_rows = (int64_t)nrows;
+    return GAUSS_OK;
+}
+
 int gauss_pop_weights(gauss_ctx* ctx, const double* x, const int64_t* interval_off, int n_interval, int n_pop, double min_abs_eig,
                       double* out_w_interval, int32_t* out_status)
 {

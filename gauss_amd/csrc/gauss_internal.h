@@ -201,6 +201,10 @@ void launch_count_up(unsigned long long* d_count, hipStream_t s);
 void launch_epilogue(const Prob* d_probs, const int2* d_tilemap, int n_tiles, int max_pop, int dtype_i8, hipStream_t s);
 void launch_epilogue_b11_lite(const Prob* d_probs, const int2* d_tilemap, int n_tiles, int dtype_i8, hipStream_t s);
 void launch_pop_cor(const Prob* d_probs, int prob, int npair, double* d_out, hipStream_t s);
+// zmix normal equations (k_zmix.hip): d_part [npair x ne] and d_part_n [npair] are workspace, ne = (G + 1)(G + 2) / 2;
+// d_out [ne] gets the upper triangle of [y | X]^T [y | X] in row order, d_out_n the kept rows
+void launch_zmix_normal_eq(const Prob* d_probs, int prob, int npair, const int* d_pop_group, int n_group, const double* d_z,
+                           double* d_part, long long* d_part_n, double* d_out, long long* d_out_n, hipStream_t s);
 void launch_pair_cor(const Prob* d_probs, int prob, const int2* d_pairs, long long n_pairs, const int* d_pop_group, int n_group,
                      double* d_out, hipStream_t s);
 void launch_gene_epilogue(const Prob* d_probs, int prob, int n_gene, hipStream_t s);

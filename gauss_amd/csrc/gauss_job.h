@@ -405,6 +405,7 @@ struct WinSpec {
     const int32_t* pair_i = nullptr;         // LD-only: only these SNP pairs are wanted (tile pairs they touch), else all
     const int32_t* pair_j = nullptr;
     int64_t n_pairs = 0;
+    int gram_only = 0;                       // LD-only without pairs: every B11 tile pair, but no S x S output (zmix normal equations)
     double* out_b11 = nullptr;               // matrices the caller wants back (the job plans their export at build time)
     double* out_b21 = nullptr;
 };

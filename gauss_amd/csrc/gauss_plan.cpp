@@ -238,7 +238,7 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
             for (int tj = ti; tj < mt; tj++) add_pair(ti, tj);          // B11 (upper tiles)
         for (int tu = mt; tu < p.nT; tu++)
             for (int tj = 0; tj < mt; tj++) add_pair(tu, tj);           // B21
-        if (w.ld_only) pl.out_ld_count = (size_t)w.M * w.M;
+        if (w.ld_only && !w.gram_only) pl.out_ld_count = (size_t)w.M * w.M;
     }
     p.npair = (int)pl.pair_ti.size();
     p.Mld = (int)rup((size_t)w.M, NB);

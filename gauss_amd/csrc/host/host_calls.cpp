@@ -366,17 +366,17 @@ static int r_quantile7(std::vector<double> x, double p, double* q)
     return 0;
 }
 
-int gauss_host_prep_zmix5(gauss_ctx* ctx, const char* input_file, const char* reference_index_file,
-                          const char* reference_data_file, const char* reference_pop_desc_file,
-                          double percentile, int interval, gauss_table** out)
+extern "C++" {    // internal helpers (host_internal.h), defined inside this file's C block
+
+// The reading that prep_zmix5, the prep_zmix selectors and zmix share (read_input_zmix / read_ref_index_zmix, zmix.cpp:44-110,
+// 1078-1181): the panel (replaced by its packed cache when auto-packing is on, opened as a packed panel when it is one), the
+// population table, every population flagged, the study's z merged with the index (allele-flipped to the panel's order) and
+// the measured SNPs in map order.
+int zmix_read(Args& a, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+              const char* reference_pop_desc_file, SnpMap& m, std::vector<Snp*>& measured)
 {
-    if (!ctx || !out) return herr("bad arguments");
-    if (!input_file || !reference_index_file || !reference_data_file || !reference_pop_desc_file) return herr("file name is NULL");
-    Args a;
     a.input_file = input_file; a.reference_index_file = reference_index_file;
     a.reference_data_file = reference_data_file; a.reference_pop_desc_file = reference_pop_desc_file;
-    const double pct = std::isnan(percentile) ? 0.99 : percentile;            // zmix.cpp:57-61
-    const int step = interval > 0 ? interval : 1;                             // zmix.cpp:63-67
     if (auto_pack_mode() != 0 && !PackedPanel::is_packed(a.reference_data_file)) {
         std::string cached, err;
         const int rc = resolve_packed_panel(a.reference_index_file, a.reference_data_file, a.reference_pop_desc_file,
@@ -392,37 +392,98 @@ int gauss_host_prep_zmix5(gauss_ctx* ctx, const char* input_file, const char* re
     if (read_ref_desc(a)) return -1;
     if (a.pk && a.pk->n_pop() != a.num_pops) return herr("packed panel has %d populations, the description file %d", a.pk->n_pop(), a.num_pops);
     a.pop_flag_vec.assign(a.num_pops, 1);                                     // zmix.cpp:148-150: every population
-    SnpMap m;
     if (ReadInputZ(m, a, true)) return -1;                                    // read_input_zmix, zmix.cpp:1078-1113 (no window)
     if (ReadReferenceIndex(m, a, true)) return -1;                            // read_ref_index_zmix, zmix.cpp:1115-1181
-    std::vector<Snp*> measured, snp_vec;
+    measured.clear();
     for (auto& kv : m) if (kv.second->type == 1) measured.push_back(kv.second.get());   // zmix.cpp:88-92
-    for (size_t i = 0; i < measured.size(); i += (size_t)step) snp_vec.push_back(measured[i]);   // zmix.cpp:111-119
+    return 0;
+}
 
-    // cal_af_norm_var (zmix.cpp:1183-1214): variance of the panel AF columns, normalised by mean(1-mean)
+// The ancestry-informative SNPs of prep_zmix5 / prep_zmix5_sup (zmix.cpp:111-139, 257-285): every step-th measured SNP,
+// cal_af_norm_var (zmix.cpp:1183-1214: variance of the panel AF columns, normalised by mean(1-mean)), kept iff its norm_var is
+// above the type-7 quantile `pct`.  kept: indices into `measured`, ascending; kept_nv: their norm_var.
+int zmix_ai_select(Args& a, const std::vector<Snp*>& measured, int step, double pct, std::vector<int>& kept, std::vector<double>& kept_nv)
+{
+    std::vector<int> sub;
+    for (int i = 0; i < (int)measured.size(); i += step) sub.push_back(i);
     std::vector<double> norm_var;
-    {
-        BgzfReader fp;
-        if (!a.pk && !fp.open(a.reference_data_file)) return herr("ERROR: can't open reference data file '%s'", a.reference_data_file.c_str());
-        std::vector<double> af;
-        for (Snp* s : snp_vec) {
-            if (a.pk) af.assign(a.pk->af(s->fpos), a.pk->af(s->fpos) + a.num_pops);
-            else load_line(fp, *s, a, &af);
-            const int n = (int)af.size();
-            double sum = 0.0, sq = 0.0;
-            for (double v : af) sum += v;
-            for (double v : af) sq += v * v;
-            const double mean = sum / n;
-            const double variance = sq / n - mean * mean;
-            norm_var.push_back(variance / (mean * (1 - mean)));
-        }
+    BgzfReader fp;
+    if (!a.pk && !fp.open(a.reference_data_file)) return herr("ERROR: can't open reference data file '%s'", a.reference_data_file.c_str());
+    std::vector<double> af;
+    for (int i : sub) {
+        Snp* s = measured[(size_t)i];
+        if (a.pk) af.assign(a.pk->af(s->fpos), a.pk->af(s->fpos) + a.num_pops);
+        else load_line(fp, *s, a, &af);
+        const int n = (int)af.size();
+        double sum = 0.0, sq = 0.0;
+        for (double v : af) sum += v;
+        for (double v : af) sq += v * v;
+        const double mean = sum / n;
+        const double variance = sq / n - mean * mean;
+        norm_var.push_back(variance / (mean * (1 - mean)));
     }
     double cutoff = 0;
     if (r_quantile7(norm_var, pct, &cutoff)) return -1;                       // zmix.cpp:126-130
-    std::vector<Snp*> sub;
+    kept.clear(); kept_nv.clear();
+    for (size_t i = 0; i < sub.size(); i++)
+        if (norm_var[i] > cutoff) { kept.push_back(sub[i]); kept_nv.push_back(norm_var[i]); }   // zmix.cpp:135-139
+    return 0;
+}
+
+// ReadGenotype of the selected SNPs, all populations (zmix.cpp:148-153): G holds one row of N genotype bytes per SNP, row
+// stride *ld (N rounded up to 16)
+int zmix_genotypes(Args& a, const std::vector<Snp*>& sel, int N, int64_t* ld, std::vector<uint8_t>& G)
+{
+    gauss_prepared tmp;
+    tmp.args = a; tmp.N = N; tmp.ld = ((int64_t)N + 15) / 16 * 16;
+    *ld = tmp.ld;
+    if (a.pk) { unpack_rows(tmp, sel, G); return 0; }
+    BgzfReader fp;
+    if (!fp.open(a.reference_data_file)) return herr("ERROR: can't open reference data file '%s'", a.reference_data_file.c_str());
+    for (Snp* s : sel) {
+        load_line(fp, *s, a, nullptr);
+        int n = 0;
+        for (auto& g : s->geno) n += g.second;
+        if (n != N) return herr("ERROR: genotype line of %s has %d samples, population table says %d", s->rsid.c_str(), n, N);
+    }
+    fill_matrix(G, sel, tmp.ld);
+    return 0;
+}
+
+// prep_zmix5_sup's groups (zmix.cpp:201-361): population k belongs to its super-population, super-populations numbered in
+// order of first appearance; returns their count
+int zmix_sup_groups(const Args& a, std::vector<int32_t>& pop_group, std::vector<std::string>& names)
+{
+    pop_group.clear(); names.clear();
+    for (int k = 0; k < a.num_pops; k++) {
+        const std::string& sp = a.ref_sup_pop_vec[(size_t)k];
+        size_t g = 0;
+        while (g < names.size() && names[g] != sp) g++;
+        if (g == names.size()) names.push_back(sp);
+        pop_group.push_back((int32_t)g);
+    }
+    return (int)names.size();
+}
+
+}  // extern "C++"
+
+int gauss_host_prep_zmix5(gauss_ctx* ctx, const char* input_file, const char* reference_index_file,
+                          const char* reference_data_file, const char* reference_pop_desc_file,
+                          double percentile, int interval, gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    if (!input_file || !reference_index_file || !reference_data_file || !reference_pop_desc_file) return herr("file name is NULL");
+    Args a;
+    const double pct = std::isnan(percentile) ? 0.99 : percentile;            // zmix.cpp:57-61
+    const int step = interval > 0 ? interval : 1;                             // zmix.cpp:63-67
+    SnpMap m;
+    std::vector<Snp*> measured;
+    if (zmix_read(a, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, m, measured)) return -1;
+    std::vector<int> kept;
     std::vector<double> sub_nv;
-    for (size_t i = 0; i < snp_vec.size(); i++)
-        if (norm_var[i] > cutoff) { sub.push_back(snp_vec[i]); sub_nv.push_back(norm_var[i]); }   // zmix.cpp:135-139
+    if (zmix_ai_select(a, measured, step, pct, kept, sub_nv)) return -1;
+    std::vector<Snp*> sub;
+    for (int i : kept) sub.push_back(measured[(size_t)i]);
 
     const int S = (int)sub.size(), P = a.num_pops;
     int N = 0;
@@ -436,26 +497,13 @@ int gauss_host_prep_zmix5(gauss_ctx* ctx, const char* input_file, const char* re
     dm.name = "data_mat"; dm.nrow = (int)npairs; dm.ncol = 1 + P;
     dm.d.assign(npairs * (size_t)(1 + P), 0.0);
     if (S > 1) {
-        // ReadGenotype for the selected SNPs, all populations (zmix.cpp:148-153), then the pair table
-        gauss_prepared tmp;
-        tmp.args = a; tmp.N = N; tmp.ld = ((int64_t)N + 15) / 16 * 16;
+        int64_t ld = 0;
         std::vector<uint8_t> G;
-        if (a.pk) unpack_rows(tmp, sub, G);
-        else {
-            BgzfReader fp;
-            if (!fp.open(a.reference_data_file)) return herr("ERROR: can't open reference data file '%s'", a.reference_data_file.c_str());
-            for (Snp* s : sub) {
-                load_line(fp, *s, a, nullptr);
-                int n = 0;
-                for (auto& g : s->geno) n += g.second;
-                if (n != N) return herr("ERROR: genotype line of %s has %d samples, population table says %d", s->rsid.c_str(), n, N);
-            }
-            fill_matrix(G, sub, tmp.ld);
-        }
+        if (zmix_genotypes(a, sub, N, &ld, G)) return -1;
         size_t row = 0;
         for (int i = 0; i < S; i++)
             for (int j = i + 1; j < S; j++) dm.d[row++] = sub[i]->z * sub[j]->z;         // zmix.cpp:165
-        if (gauss_ld_per_pop(ctx, G.data(), S, tmp.ld, pop_off.data(), P, dm.d.data() + npairs) != 0)
+        if (gauss_ld_per_pop(ctx, G.data(), S, ld, pop_off.data(), P, dm.d.data() + npairs) != 0)
             return herr("%s", gauss_last_error());
     }
     Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chr{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
@@ -493,32 +541,13 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
     if (!ctx || !out) return herr("bad arguments");
     if (!input_file || !reference_index_file || !reference_data_file || !reference_pop_desc_file) return herr("file name is NULL");
     Args a;
-    a.input_file = input_file; a.reference_index_file = reference_index_file;
-    a.reference_data_file = reference_data_file; a.reference_pop_desc_file = reference_pop_desc_file;
     // defaults: zmix.cpp:953-957 (1), 664-675 / 376-387 / 524-535 (1000 and 3 / 3 / 5), 214-224 (0.99, 1)
     const int step = interval > 0 ? interval : ((variant == ZMIX_ALL || variant == ZMIX_5SUP) ? 1 : 1000);
     const int par2 = p2 > 0 ? p2 : (variant == ZMIX_3 ? 5 : 3);
     const double pct = std::isnan(percentile) ? 0.99 : percentile;
-    if (auto_pack_mode() != 0 && !PackedPanel::is_packed(a.reference_data_file)) {
-        std::string cached, err;
-        const int rc = resolve_packed_panel(a.reference_index_file, a.reference_data_file, a.reference_pop_desc_file,
-                                            auto_pack_mode() == 1, cached, err);
-        if (rc < 0) return herr("%s", err.c_str());
-        if (rc == 0) a.reference_data_file = cached;
-    }
-    if (PackedPanel::is_packed(a.reference_data_file)) {
-        std::string err;
-        a.pk = open_packed_shared(a.reference_data_file, err);
-        if (!a.pk) return herr("%s", err.c_str());
-    }
-    if (read_ref_desc(a)) return -1;
-    if (a.pk && a.pk->n_pop() != a.num_pops) return herr("packed panel has %d populations, the description file %d", a.pk->n_pop(), a.num_pops);
-    a.pop_flag_vec.assign(a.num_pops, 1);
     SnpMap m;
-    if (ReadInputZ(m, a, true)) return -1;
-    if (ReadReferenceIndex(m, a, true)) return -1;
     std::vector<Snp*> measured;
-    for (auto& kv : m) if (kv.second->type == 1) measured.push_back(kv.second.get());
+    if (zmix_read(a, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, m, measured)) return -1;
     const int n = (int)measured.size();
 
     // ---- which SNPs, which pairs (indices into `measured`) ----
@@ -527,29 +556,11 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
     std::vector<double> sub_nv;                                  // prep_zmix5_sup: norm_var of the kept SNPs
     if (variant == ZMIX_ALL || variant == ZMIX_3 || variant == ZMIX_5SUP) {
         std::vector<int> sub;
-        for (int i = 0; i < n; i += step) sub.push_back(i);      // zmix.cpp:996-1004, 567-575, 257-265
         if (variant == ZMIX_5SUP) {
-            // cal_af_norm_var + the percentile cut, as in prep_zmix5 (zmix.cpp:268-285)
-            std::vector<double> norm_var;
-            BgzfReader fp;
-            if (!a.pk && !fp.open(a.reference_data_file)) return herr("ERROR: can't open reference data file '%s'", a.reference_data_file.c_str());
-            std::vector<double> af;
-            for (int i : sub) {
-                Snp* s = measured[(size_t)i];
-                if (a.pk) af.assign(a.pk->af(s->fpos), a.pk->af(s->fpos) + a.num_pops);
-                else load_line(fp, *s, a, &af);
-                const int k = (int)af.size();
-                double sum = 0.0, sq = 0.0;
-                for (double v : af) sum += v;
-                for (double v : af) sq += v * v;
-                const double mean = sum / k;
-                norm_var.push_back((sq / k - mean * mean) / (mean * (1 - mean)));
-            }
-            double cutoff = 0;
-            if (r_quantile7(norm_var, pct, &cutoff)) return -1;
-            std::vector<int> kept;
-            for (size_t i = 0; i < sub.size(); i++) if (norm_var[i] > cutoff) { kept.push_back(sub[i]); sub_nv.push_back(norm_var[i]); }
-            sub.swap(kept);
+            // cal_af_norm_var + the percentile cut, as in prep_zmix5 (zmix.cpp:257-285)
+            if (zmix_ai_select(a, measured, step, pct, sub, sub_nv)) return -1;
+        } else {
+            for (int i = 0; i < n; i += step) sub.push_back(i);  // zmix.cpp:996-1004, 567-575
         }
         const int S = (int)sub.size();
         for (int i = 0; i < S; i++) {
@@ -582,17 +593,7 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
     std::vector<int32_t> pop_group;
     int n_group = P;
     std::vector<std::string> group_names = a.ref_pop_vec;
-    if (variant == ZMIX_5SUP) {
-        group_names.clear();
-        for (int k = 0; k < P; k++) {
-            const std::string& sp = a.ref_sup_pop_vec[(size_t)k];
-            size_t g = 0;
-            while (g < group_names.size() && group_names[g] != sp) g++;
-            if (g == group_names.size()) group_names.push_back(sp);
-            pop_group.push_back((int32_t)g);
-        }
-        n_group = (int)group_names.size();
-    }
+    if (variant == ZMIX_5SUP) n_group = zmix_sup_groups(a, pop_group, group_names);
     int N = 0;
     std::vector<int32_t> pop_off(1, 0);
     for (int k = 0; k < P; k++) { N += a.ref_pop_size_vec[(size_t)k]; pop_off.push_back(pop_off.back() + a.ref_pop_size_vec[(size_t)k]); }
@@ -603,28 +604,16 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
     dm.name = "data_mat"; dm.nrow = (int)np; dm.ncol = nlead + 1 + n_group;
     dm.d.assign(np * (size_t)dm.ncol, 0.0);
     if (np > 0) {
-        gauss_prepared tmp;
-        tmp.args = a; tmp.N = N; tmp.ld = ((int64_t)N + 15) / 16 * 16;
+        int64_t ld = 0;
         std::vector<uint8_t> G;
-        if (a.pk) unpack_rows(tmp, sel, G);
-        else {
-            BgzfReader fp;
-            if (!fp.open(a.reference_data_file)) return herr("ERROR: can't open reference data file '%s'", a.reference_data_file.c_str());
-            for (Snp* s : sel) {
-                load_line(fp, *s, a, nullptr);
-                int k = 0;
-                for (auto& g : s->geno) k += g.second;
-                if (k != N) return herr("ERROR: genotype line of %s has %d samples, population table says %d", s->rsid.c_str(), k, N);
-            }
-            fill_matrix(G, sel, tmp.ld);
-        }
+        if (zmix_genotypes(a, sel, N, &ld, G)) return -1;
         std::vector<int32_t> pi(np), pj(np);
         for (size_t k = 0; k < np; k++) {
             pi[k] = row_of[(size_t)pairs[k].first]; pj[k] = row_of[(size_t)pairs[k].second];
             if (nlead) dm.d[k] = lead[k];
             dm.d[(size_t)nlead * np + k] = measured[(size_t)pairs[k].first]->z * measured[(size_t)pairs[k].second]->z;
         }
-        if (gauss_ld_per_pop_pairs(ctx, G.data(), S, tmp.ld, pop_off.data(), P, pop_group.empty() ? nullptr : pop_group.data(), n_group,
+        if (gauss_ld_per_pop_pairs(ctx, G.data(), S, ld, pop_off.data(), P, pop_group.empty() ? nullptr : pop_group.data(), n_group,
                                    pi.data(), pj.data(), (int64_t)np, dm.d.data() + (size_t)(nlead + 1) * np) != 0)
             return herr("%s", gauss_last_error());
     }

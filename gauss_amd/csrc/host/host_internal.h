@@ -479,3 +479,9 @@ gauss_table* qcat_output(gauss_prepared& p);
 gauss_table* prep_output(gauss_prepared& p);
 int panel_make_resident(gauss_ctx* ctx, const std::string& path, void** dev, int64_t* uploaded, bool async = false);
 bool panel_is_resident(gauss_ctx* ctx, const std::string& path, void** dev, bool wait = true);
+// zmix's SNP selection, shared by prep_zmix5, the prep_zmix selectors and zmix (host_calls.cpp)
+int zmix_read(Args& a, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+              const char* reference_pop_desc_file, SnpMap& m, std::vector<Snp*>& measured);
+int zmix_ai_select(Args& a, const std::vector<Snp*>& measured, int step, double pct, std::vector<int>& kept, std::vector<double>& kept_nv);
+int zmix_genotypes(Args& a, const std::vector<Snp*>& sel, int N, int64_t* ld, std::vector<uint8_t>& G);
+int zmix_sup_groups(const Args& a, std::vector<int32_t>& pop_group, std::vector<std::string>& names);

@@ -146,6 +146,29 @@ def ld_per_pop(geno, pop_off, ctx=None):
     return out
 
 
+def zmix_normal_eq(geno, pop_off, z, pop_group=None, ctx=None):
+    """gauss_zmix_normal_eq: normal equations of the zmix regression over every pair i < j of the S genotype rows, row
+    [z_i z_j, r_1(i, j) .. r_G(i, j)] (r_g: correlation inside population g, or inside group g of populations pooled when
+    pop_group [P] is given), non-finite rows dropped.  Returns (XtX [G, G], Xty [G], yty, n_rows)."""
+    ctx = ctx or default_context()
+    g = _lib.as_u8(geno)
+    po, _ = _pops(pop_off, None)
+    S, P = g.shape[0], len(po) - 1
+    za = np.ascontiguousarray(z, dtype=np.float64)
+    if za.shape != (S,):
+        raise ValueError(f"z has shape {za.shape}, expected ({S},)")
+    grp = None if pop_group is None else np.ascontiguousarray(pop_group, dtype=np.int32)
+    G = P if grp is None else (int(grp.max()) + 1 if grp.size else 0)
+    xtx = np.zeros((max(G, 0), max(G, 0)))
+    xty = np.zeros(max(G, 0))
+    yty = C.c_double()
+    n_rows = C.c_int64()
+    check(ctx.lib.gauss_zmix_normal_eq(ctx.handle, g.ctypes.data, S, g.strides[0], po.ctypes.data_as(_ip), P,
+                                       None if grp is None else grp.ctypes.data_as(_ip), G, za.ctypes.data_as(_dp),
+                                       xtx.ctypes.data_as(_dp), xty.ctypes.data_as(_dp), C.byref(yty), C.byref(n_rows)))
+    return xtx, xty, yty.value, int(n_rows.value)
+
+
 def pop_weights(x, interval_off, min_abs_eig=1e-5, ctx=None):
     """gauss_pop_weights: per-interval population weights W_i = MakePosDef(Cxx)^-1 Cxy of an interval-major matrix
     x [S, P + 1] (rows [af1study, AF_0 .. AF_(P-1)]; interval i = rows interval_off[i] .. interval_off[i+1]).

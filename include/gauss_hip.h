@@ -283,6 +283,18 @@ int gauss_ld_per_pop_pairs(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64
 int gauss_pop_weights(gauss_ctx* ctx, const double* x, const int64_t* interval_off, int n_interval, int n_pop,
                       double min_abs_eig, double* out_w_interval, int32_t* out_status);
 
+/* Normal equations of the zmix regression (zmix(), zmix.R): over every pair i < j of the n_snp genotype rows, the row
+ * [y, x_1 .. x_G] = [z[i] * z[j], r_1(i, j) .. r_G(i, j)], r_g the Pearson correlation of the pair inside group g.  pop_group NULL:
+ * one group per population (G = n_pop, the columns of prep_zmix5 and the bits of gauss_ld_per_pop); else population p belongs to
+ * group pop_group[p] in 0 .. n_group - 1 and a group's populations are pooled (G = n_group, prep_zmix5_sup's columns, CalCorSup
+ * zmix.cpp:1221-1246, the bits of gauss_ld_per_pop_pairs).  A row is kept iff all its 1 + G entries are finite
+ * (is.finite(rowSums(mat))).  Out: X^T X [G x G] row-major, X^T y [G], y^T y and the number of kept rows, over the kept rows.
+ * The per-pair rows are never stored: only pack + Gram run, then a fixed-order reduction (no atomics: the bits do not depend on
+ * the run).  1 <= G <= 64; n_snp >= 2.  Blocking. */
+int gauss_zmix_normal_eq(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64_t ld, const int32_t* pop_off, int n_pop,
+                         const int32_t* pop_group, int n_group, const double* z, double* out_xtx, double* out_xty, double* out_yty,
+                         int64_t* out_n_rows);
+
 /* Exact co-occurrence counts sum_n x_i[n] x_j[n] over all columns -- the integer the reference
  * accumulates as `sumxy` (util.cpp:62,114).  out: S x S int64, row-major.  Integer parity hook. */
 int gauss_gram_counts(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int n_samples, int64_t ld,

@@ -19,6 +19,7 @@
  *   prep_zmix5(input_file,...,percentile,interval)          gauss_host_prep_zmix5 zmix.cpp:44-190
  *   afmix(input_file,...,interval)                          gauss_host_afmix     afmix.cpp:30-215
  *   cpw2(input_file,...,interval)                           gauss_host_cpw2      cpw2.cpp:31-211
+ *   zmix(input_file,...,percentile,interval,level)          gauss_host_zmix      zmix.R
  *
  * Same argument meaning, same defaults (af1_cutoff NaN = R's NULL -> 0.01, dist.cpp:53-57), same
  * row order (std::map order on (chr,bp,a1,a2), gauss.h:72-99), same column names and types as
@@ -221,6 +222,26 @@ int gauss_host_cpw2(gauss_ctx* ctx, const char* input_file, const char* referenc
  * the interval-major matrix exactly as gauss_pop_weights receives it, and "interval_off" [(interval + 1) x 1]. */
 int gauss_host_popwgt_inputs(int kind, const char* input_file, const char* reference_index_file, const char* reference_data_file,
                              const char* reference_pop_desc_file, int interval, gauss_table** out);
+
+/* zmix(): ancestry proportions of a study from its Z-scores (zmix.R).  level: GAUSS_ZMIX_POPULATION or
+ * GAUSS_ZMIX_SUPERPOPULATION.  percentile NaN -> 0.9, interval <= 0 -> 10 (zmix.R's defaults, not prep_zmix5's 0.99 / 1).  The SNPs
+ * are prep_zmix5's (every interval-th measured SNP whose norm_var is above the percentile); over every pair i < j of them the row
+ * [z_i z_j, r_1 .. r_G] (r_g per population, or per super-population pooled as prep_zmix5_sup) is kept iff finite, and only
+ * D = X^T X and d = X^T y are formed, on the GPU (gauss_zmix_normal_eq).  Then solve.QP's problem min 1/2 w^T D w - d^T w,
+ * sum w = 1, w >= 0, -w >= -1 (gauss_host_zmix_qp), w / sum w, rounded to 5 decimals, / sum again.  Result: columns
+ * Population SuperPopulation Weight (every population, description order) or SuperPopulation Weight (super-populations in order of
+ * first appearance); named matrices "dmat" [G x G], "dvec" [G x 1], "w_unrounded" [G x 1] (w / sum w before the rounding),
+ * "yty", "n_snp", "n_pairs", "n_rows" [1 x 1].  Errors with zmix.R's / solve.QP's messages: "zmix: no valid rows after
+ * filtering." (fewer than two SNPs, or no finite row), a description file without Population_Abbreviation / Super_Population,
+ * "matrix D in quadratic function is not positive definite!"; more than 64 groups is refused. */
+#define GAUSS_ZMIX_POPULATION      0
+#define GAUSS_ZMIX_SUPERPOPULATION 1
+int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                    const char* reference_pop_desc_file, double percentile, int interval, int level, gauss_table** out);
+/* zmix's quadratic program alone (no context, no GPU): D [P x P] row-major symmetric, d [P]; the Goldfarb-Idnani dual active-set
+ * method of quadprog::solve.QP.  w_unrounded (may be NULL): the solution / its sum; w_final (may be NULL): that rounded to 5
+ * decimals and normalised again.  Returns 0, or -1 with gauss_host_last_error() set (D not positive definite). */
+int gauss_host_zmix_qp(const double* D, const double* d, int P, double* w_unrounded, double* w_final);
 
 /* ---- packed panel -------------------------------------------------
  * Converts the reference's BGZF text panel (index + data + population description) into one mmap-able
