@@ -56,7 +56,7 @@ SYMBOLS = [
     "gauss_ld_rows", "gauss_gene_ld_batch_rows", "gauss_job_run", "gauss_job_fetch", "gauss_job_destroy", "gauss_job_span_ms", "gauss_job_profile",
     "gauss_job_profile_get", "gauss_job_work", "gauss_job_stats", "gauss_synth_device",
     "gauss_store_upload_async", "gauss_store_upload_fd_async", "gauss_store_wait", "gauss_store_alloc", "gauss_store_fill", "gauss_store_fill_fd", "gauss_store_upload_fd", "gauss_hip_context_id", "gauss_hip_add_destroy_hook", "gauss_hip_trim_cache", "gauss_hip_source_hash", "gauss_hip_counters", "gauss_job_counters", "gauss_hip_queues",
-    "gauss_pop_weights", "gauss_zmix_normal_eq",
+    "gauss_pop_weights", "gauss_zmix_normal_eq", "gauss_ld_resampled_rows",
 ]
 
 
@@ -128,6 +128,8 @@ def load():
     lib.gauss_pop_weights.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_double, _dp, _ip]
     lib.gauss_zmix_normal_eq.argtypes = [C.c_void_p, _u8p, C.c_int, C.c_int64, _ip, C.c_int, _ip, C.c_int, _dp, _dp, _dp, _dp,
                                          C.POINTER(C.c_int64)]
+    lib.gauss_ld_resampled_rows.argtypes = [C.c_void_p, _u8p, C.c_int64, C.c_int, _ip, C.c_int, _ip, _ip, C.c_int, _ip, _ip, C.c_int64,
+                                            C.c_int64, C.c_double, C.c_int, _dp]
     _lib = lib
     return lib
 

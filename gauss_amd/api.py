@@ -7,6 +7,7 @@
     jepeg(study_pop, input_file, annotation_file, ...)
     jepegmix(pop_wgt_df, input_file, annotation_file, ...)
     afmix(input_file, reference_index_file, ...) / cpw2(...)   population weights from allele frequencies
+    simulateLD(chr, start_bp, end_bp, pop_wgt_df, sim_size, input_file, ..., seed=None)   LD of a simulated mixed cohort
 
 Each is a thin ctypes call into libgauss_host.so (C++ host data layer) which delegates the numeric
 hot path to libgauss_hip.so (HIP).  A ``pop_wgt_df`` is anything with two columns (population
@@ -44,6 +45,7 @@ HOST_SYMBOLS = [
     "gauss_host_jepeg_gene_tail", "gauss_host_plan_cost",
     "gauss_host_jepeg_rank", "gauss_host_jepeg_genome", "gauss_prepared_jepeg_plan", "gauss_prepared_jepeg_finish",
     "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
+    "gauss_host_simulateLD", "gauss_host_simulate_draws",
 ]
 
 
@@ -116,6 +118,8 @@ def load_host():
     h.gauss_host_popwgt_inputs.argtypes = [C.c_int, _cp, _cp, _cp, _cp, C.c_int, C.POINTER(_vp)]
     h.gauss_host_zmix.argtypes = [_vp, _cp, _cp, _cp, _cp, _dbl, C.c_int, C.c_int, C.POINTER(_vp)]
     h.gauss_host_zmix_qp.argtypes = [_dp, _dp, C.c_int, _dp, _dp]
+    h.gauss_host_simulateLD.argtypes = [_vp, C.c_int, _i64, _i64, _strs, _dp, C.c_int, _i64] + files4 + [_dbl, _i64, C.POINTER(_vp)]
+    h.gauss_host_simulate_draws.argtypes = [_cp, _strs, _dp, C.c_int, _i64, _i64, C.POINTER(_vp)]
     h.gauss_host_pack_panel.restype = _i64
     h.gauss_host_pack_panel.argtypes = [_cp, _cp, _cp, _cp]
     h.gauss_prepared_packed_store.argtypes = [_vp, C.POINTER(C.c_void_p), C.POINTER(_i64), C.POINTER(_i64)]
@@ -255,6 +259,50 @@ def computeLD(chr, start_bp, end_bp, pop_wgt_df, input_file, reference_index_fil
                                    _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
     df, mat = _table(h, out)
     return {"snplist": df, "cormat": mat}
+
+
+def _seed(seed):
+    return -1 if seed is None else int(seed)
+
+
+def _draws(named):
+    d = np.asarray(named["draws"]).reshape(-1, 2) if named["draws"].size else np.zeros((0, 2))
+    counts = named["counts"].reshape(-1).astype(np.int64)
+    return dict(draws=d.astype(np.int64), counts=counts, seed=int(named["seed"].reshape(-1)[0]), n_drawn=int(counts.sum()))
+
+
+def simulateLD(chr, start_bp, end_bp, pop_wgt_df, sim_size, input_file, reference_index_file, reference_data_file,
+               reference_pop_desc_file, af1_cutoff=None, seed=None, ctx=None, detail=False):
+    """simulateLD() of the reference (simulateLD.cpp:34-252): the LD of sim_size subjects drawn with replacement from the panel's
+    populations, (int)(weight * sim_size) from each population of pop_wgt_df (panel order), the rest of the columns zero.  The SNPs
+    and ``snplist`` are computeLD's.  seed: an integer in [0, 2**32) replays a call exactly; None (or -1) draws one from
+    std::random_device as the reference does, and the seed used is in the detail.  Returns ``{"snplist", "cormat"}``; with
+    detail=True also ``draws`` [n_drawn, 2] (index into the weighted populations in panel order, sample), ``counts``, ``seed`` and
+    ``n_drawn``."""
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_simulateLD(_ctx(ctx), int(chr), int(start_bp), int(end_bp), names, w.ctypes.data_as(_dp), n, int(sim_size),
+                                    _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
+                                    _enc(reference_pop_desc_file), _af(af1_cutoff), _seed(seed), C.byref(out)))
+    named = _named(h, out)
+    df, mat = _table(h, out)
+    res = {"snplist": df, "cormat": mat}
+    if detail:
+        res.update(_draws(named))
+    return res
+
+
+def simulate_draws(pop_wgt_df, sim_size, reference_pop_desc_file, seed=None):
+    """gauss_host_simulate_draws (no GPU): simulateLD's draws alone.  Returns (DataFrame pop n count of the weighted populations in
+    panel order, dict(draws, counts, seed, n_drawn))."""
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_simulate_draws(_enc(reference_pop_desc_file), names, w.ctypes.data_as(_dp), n, int(sim_size), _seed(seed),
+                                        C.byref(out)))
+    named = _named(h, out)
+    return _table(h, out)[0], _draws(named)
 
 
 def dist(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,

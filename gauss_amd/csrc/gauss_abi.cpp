@@ -249,6 +249,9 @@ struct RowSource {                 // where the rows of an LD-only call come fro
     const int32_t* rows = nullptr;
     const int32_t* pop_src_off = nullptr;
     int on_device = 0;
+    const int32_t* draw_pop = nullptr;      // resampled window (gauss_ld_resampled_rows)
+    const int32_t* draw_sample = nullptr;
+    int64_t n_drawn = 0, n_cols = 0;
 };
 
 static int ld_common(gauss_ctx* ctx, int mode, const uint8_t* geno, int n_snp, int64_t ld,
@@ -263,6 +266,7 @@ static int ld_common(gauss_ctx* ctx, int mode, const uint8_t* geno, int n_snp, i
     w.M = n_snp; w.U = 0; w.geno_m = geno; w.geno_u = nullptr; w.ld = ld; w.z1 = nullptr;
     w.lambda = 0; w.eps = 0; w.diag = diag; w.ld_only = 1; w.gene_off = gene_off; w.n_gene = n_gene;
     w.geno_fmt = src.geno_fmt; w.rows_m = src.rows; w.pop_src_off = src.pop_src_off;
+    w.draw_pop = src.draw_pop; w.draw_sample = src.draw_sample; w.n_drawn = src.n_drawn; w.n_cols = src.n_cols;
     gauss_job* job = nullptr;
     std::vector<WinSpec> specs{w};
     int rc = job_build(ctx, specs, src.on_device, &job);
@@ -304,6 +308,30 @@ int gauss_ld_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, in
     RowSource src;
     src.geno_fmt = geno_format; src.rows = rows; src.pop_src_off = pop_src_off; src.on_device = on_device;
     return ld_common(ctx, mode, store, n_snp, ld, pop_off, pop_wgt, n_pop, diag, nullptr, 0, out_cor, nullptr, 0, src);
+}
+
+int gauss_ld_resampled_rows(gauss_ctx* ctx, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp,
+                            const int32_t* pop_off, const int32_t* pop_src_off, int n_pop,
+                            const int32_t* draw_pop, const int32_t* draw_sample, int64_t n_drawn, int64_t n_cols,
+                            double diag, int on_device, double* out_cor)
+{
+    if (!ctx || !store || !pop_off || !out_cor) return fail(GAUSS_E_INVALID, "bad arguments to gauss_ld_resampled_rows");
+    if (n_snp < 1) return fail(GAUSS_E_INVALID, "need at least one SNP row (got %d)", n_snp);
+    if (n_cols < 1) return fail(GAUSS_E_INVALID, "n_cols must be >= 1 (got %lld)", (long long)n_cols);
+    if (n_drawn < 0 || n_drawn > n_cols)
+        return fail(GAUSS_E_INVALID, "n_drawn = %lld is outside 0..n_cols (%lld)", (long long)n_drawn, (long long)n_cols);
+    if (n_drawn > 0 && (!draw_pop || !draw_sample)) return fail(GAUSS_E_INVALID, "draw_pop / draw_sample is NULL");
+    if (n_drawn == 0) {
+        // every column is a zero column: CalCor is 0/0 off the diagonal (no Gram work to launch)
+        const size_t S = (size_t)n_snp;
+        for (size_t i = 0; i < S; i++)
+            for (size_t j = 0; j < S; j++) out_cor[i * S + j] = i == j ? diag : NAN;
+        return GAUSS_OK;
+    }
+    RowSource src;
+    src.geno_fmt = geno_format; src.rows = rows; src.pop_src_off = pop_src_off; src.on_device = on_device;
+    src.draw_pop = draw_pop; src.draw_sample = draw_sample; src.n_drawn = n_drawn; src.n_cols = n_cols;
+    return ld_common(ctx, GAUSS_MODE_POOLED, store, n_snp, ld, pop_off, nullptr, n_pop, diag, nullptr, 0, out_cor, nullptr, 0, src);
 }
 
 int gauss_gene_ld_batch_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows,

@@ -119,6 +119,9 @@ struct Prob {
     GP(const int) gene_off;    // gene batches: [n_gene+1], else null
     int n_gene;
     GP(long long) gene_out_off;// [n_gene] offsets into out_ld
+    // resampled windows (simulateLD, k_simld.hip): the packed columns are drawn samples, not the populations' samples
+    GP(const int) draw_col;    // [Kp] source column of every packed column, ascending, -1 past the draws; null: not resampled
+    int row_src_bytes;         // bytes of a source row the resample kernel reads
 };
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
@@ -190,6 +193,11 @@ struct DeviceOnce {
 
 // ---- launchers (host functions defined in the .hip files) ----
 void launch_pack_stats(const Prob* d_probs, const int2* d_rowmap, int n_rows, hipStream_t s);
+// resampled windows (k_simld.hip): the pack stage of a job whose window has Prob::draw_col.  lds_bytes: from
+// resample_pack_lds_bytes (0: the source row is too long to stage in LDS and is read from global memory)
+constexpr int SIMLD_LDS_MAX = 60 << 10;
+int resample_pack_lds_bytes(long long row_src_bytes);
+void launch_resample_pack(const Prob* d_probs, const int2* d_rowmap, int n_rows, int lds_bytes, hipStream_t s);
 // d_b11_done (may be null): items with flag bit 4 count themselves off there when their slabs are out (k_gram.hip)
 void launch_gram(const Item* d_items, int n_items, int dtype_i8, hipStream_t s, unsigned long long* d_b11_done = nullptr);
 // one wave that returns when *d_count >= target (bounded; on timeout d_status[0 .. n_status) = 1)

@@ -238,6 +238,7 @@ struct Plan {
     std::vector<int> run_pk_off, run_src, run_len;     // 2-bit source blocks: packed column range, byte offset in a source row, live samples
     bool run_len_known(size_t q) const { return q < run_len.size(); }
     std::vector<int32_t> rows_m, rows_u;     // store rows; empty = contiguous
+    std::vector<int32_t> draw_col;           // resampled window: Prob::draw_col (empty: not resampled)
     size_t row_bytes = 0;                    // bytes of a source row that the kernels read
     std::vector<int> gene_off;
     std::vector<long long> gene_out_off;
@@ -318,6 +319,8 @@ struct gauss_job {
     std::vector<hipEvent_t> sevp;                          // "group g's rows are packed, their tables made" (aux stream)
     int max_pop = 1;
     int gram_i8 = 0;
+    int resample_lds = -1;                                 // >= 0: the window is resampled (k_simld.hip) and its pack stage is
+                                                           // resample_pack with this much dynamic LDS
     int* d_status = nullptr;                               // [n][4] + 4 job-wide ints
     unsigned long long* d_b11_done = nullptr;              // merged Gram launch: B11's items that have finished, over all runs so far
     bool merged = false;                                   // chain_aside as ONE Gram launch (B11's items first, counted; job_queue_run)
@@ -408,6 +411,11 @@ struct WinSpec {
     int gram_only = 0;                       // LD-only without pairs: every B11 tile pair, but no S x S output (zmix normal equations)
     double* out_b11 = nullptr;               // matrices the caller wants back (the job plans their export at build time)
     double* out_b21 = nullptr;
+    // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample
+    // draw_sample[k] of selected population draw_pop[k] and the other n_cols - n_drawn are zero columns
+    const int32_t* draw_pop = nullptr;
+    const int32_t* draw_sample = nullptr;
+    int64_t n_drawn = 0, n_cols = 0;
 };
 
 // ---- gauss_plan.cpp ----

@@ -29,7 +29,7 @@ static int seg_max_for(const std::vector<WinSpec>& specs)
         for (int c = 0; c < 3; c++) nc += (w.u_codings >> c) & 1;
         const double mt = (w.M + TILE - 1) / TILE, ut = ((double)w.U * std::max(nc, 1) + TILE - 1) / TILE;
         pairs += mt * (mt + 1) / 2 + ut * mt;
-        kp = std::max(kp, (double)w.pop_off[w.n_pop] + 32.0 * w.n_pop);
+        kp = std::max(kp, w.draw_pop ? (double)w.n_drawn + 32.0 : (double)w.pop_off[w.n_pop] + 32.0 * w.n_pop);
     }
     const double want = pairs * kp / 1300.0;
     return (int)std::min<double>(SEG_MAX, std::max<double>(384.0, std::floor(want / KC) * KC));
@@ -142,6 +142,42 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         for (int q = 0; q < w.n_pop; q++)
             for (int b = pl.run_pk_off[q] / 16; b < pl.run_pk_off[q + 1] / 16; b++) pl.word_run[b] = (uint8_t)q;
     }
+    if (w.draw_pop) {
+        // Resampled window (simulateLD.cpp:161-199): the operand row holds the n_drawn drawn samples in ascending source order
+        // (the sums are exact integers: no order changes a bit), the statistics see one pseudo-population of n_cols samples
+        // whose other n_cols - n_drawn are the reference's zero columns.  Only the drawn columns are packed and multiplied.
+        if (w.mode != GAUSS_MODE_POOLED || !w.ld_only || w.U > 0 || w.gene_off || w.pair_i || w.gram_only)
+            return fail(GAUSS_E_INVALID, "a resampled window is a pooled LD-only window of measured rows");
+        if (w.n_drawn < 1 || !w.draw_sample) return fail(GAUSS_E_INVALID, "a resampled window needs at least one draw");
+        if (w.n_cols < w.n_drawn) return fail(GAUSS_E_INVALID, "n_cols (%lld) < n_drawn (%lld)", (long long)w.n_cols, (long long)w.n_drawn);
+        // Prob::N and Kp are ints, and the row sums (15 * 15 per drawn column at most) are int32 on the device
+        if (w.n_cols > INT32_MAX) return fail(GAUSS_E_RANGE, "n_cols = %lld exceeds the int range of a window's sample count", (long long)w.n_cols);
+        if (w.n_drawn * 225 >= (1LL << 31))
+            return fail(GAUSS_E_RANGE, "%lld drawn samples exceed the exact-integer range (9.5 M)", (long long)w.n_drawn);
+        const int nd = (int)w.n_drawn;
+        std::vector<int32_t> col((size_t)nd);
+        for (int k = 0; k < nd; k++) {
+            const int q = w.draw_pop[k], s = w.draw_sample[k];
+            if (q < 0 || q >= w.n_pop) return fail(GAUSS_E_INVALID, "draw %d: population %d is outside 0..%d", k, q, w.n_pop - 1);
+            const int m = w.pop_off[q + 1] - w.pop_off[q];
+            if (s < 0 || s >= m) return fail(GAUSS_E_INVALID, "draw %d: sample %d is outside population %d's 0..%d", k, s, q, m - 1);
+            // a byte index into a one-byte row, a 2-bit sample index into a packed row (run_src: byte offset of the block)
+            const long long c = w.geno_fmt == GAUSS_GENO_2BIT ? 4LL * pl.run_src[(size_t)q] + s : (long long)w.pop_off[q] + s;
+            if (c > INT32_MAX) return fail(GAUSS_E_RANGE, "draw %d: source column %lld exceeds the int range", k, c);
+            col[(size_t)k] = (int32_t)c;
+        }
+        std::sort(col.begin(), col.end());
+        const int Kp = (int)rup((size_t)nd, KC);
+        col.resize((size_t)Kp, -1);
+        pl.draw_col.swap(col);
+        p.N = (int)w.n_cols;
+        pl.pop_raw_off = {0, (int)w.n_cols};
+        pl.pop_w = {1.0};
+        pl.pop_wf = {((double)w.n_cols) / (w.n_cols - 1)};
+        pl.pop_md = {(double)w.n_cols};
+        pl.pop_pk_off = {0, Kp};
+        p.row_src_bytes = (int)std::min<size_t>(pl.row_bytes, INT32_MAX);
+    }
     if (w.rows_m) pl.rows_m.assign(w.rows_m, w.rows_m + w.M);
     if (w.rows_u && w.U > 0) pl.rows_u.assign(w.rows_u, w.rows_u + w.U);
     p.Kp = pl.pop_pk_off[P];
@@ -158,7 +194,9 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         const int units = (samples + 7) / 8;
         if (units >= 1 && units < 8) pl.chunk_live[chunk >> 3] |= (uint32_t)units << (4 * (chunk & 7));
     };
-    if (w.geno_fmt == GAUSS_GENO_2BIT) {
+    if (!pl.draw_col.empty()) {
+        if (w.n_drawn % KC) set_live(p.Kp / KC - 1, (int)(w.n_drawn % KC));      // the draws end in zero padding
+    } else if (w.geno_fmt == GAUSS_GENO_2BIT) {
         for (int q = 0; q < w.n_pop; q++) {
             const int m = w.pop_off[q + 1] - w.pop_off[q], rem = m % KC;
             if (m > 0 && rem) set_live(pl.run_pk_off[q + 1] / KC - 1, rem);
@@ -282,11 +320,14 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->on_device = on_device;
     job->gram_i8 = ctx->gram_i8;
     job->plans.resize(job->n);
+    for (const WinSpec& w : specs)
+        if (w.draw_pop && (specs.size() != 1 || streamed)) return fail(GAUSS_E_INVALID, "a resampled window is a job of its own");
     const int seg_max = seg_max_for(specs);
     for (int i = 0; i < job->n; i++) {
         int rc = plan_problem(specs[i], job->plans[i], seg_max, group_target_for(specs.size()));
         if (rc) return rc;
         job->plans[i].p.gram_i8 = job->gram_i8;
+        if (!job->plans[i].draw_col.empty()) job->resample_lds = resample_pack_lds_bytes(job->plans[i].p.row_src_bytes);
     }
     // Matrix exports (gauss_job.h): which matrices the caller wants back, and where each lands in the pinned mirror
     size_t exp_doubles = 0;
@@ -433,7 +474,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<char>& blob = job->h_tab;
     blob.reserve((size_t)n_prob * ((size_t)320 << 10) + ((size_t)64 << 10));      // (~0.3 MB a window: grown in place, not copied over and over)
     const auto tb2 = std::chrono::steady_clock::now();
-    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch; };
+    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch, dc; };
     std::vector<TabOff> to((size_t)n_prob);
     for (int i = 0; i < n_prob; i++) {
         Plan& pl = plan_of(i);
@@ -459,6 +500,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         to[i].rm = put(blob, ta, pl.rows_m);
         to[i].ru = put(blob, ta, pl.rows_u);
         to[i].ch = put(blob, ta, pl.chunk_live);
+        to[i].dc = put(blob, ta, pl.draw_col);
     }
     // work lists
     struct ItemH { int prob, pair, group, len, b11, ord = 0; };     // b11: an item of B11 (job-wide pairs, or a window's own measured x measured pairs); ord: launch-order key (below)
@@ -942,6 +984,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.out_ld = (double*)(W + w.ld);
         p.gene_off = p.n_gene ? (const int*)(T + to[i].goff) : nullptr;
         p.gene_out_off = p.n_gene ? (long long*)(T + to[i].gout) : nullptr;
+        p.draw_col = pl.draw_col.empty() ? nullptr : (const int*)(T + to[i].dc);
         // the unmeasured part of every row array follows the measured part ...
         p.packed_u = p.packed + (size_t)p.Mp * p.Kp;
         p.sx_u = p.sx + (size_t)p.Mp * p.P; p.sxx_u = p.sxx + (size_t)p.Mp * p.P;

@@ -110,7 +110,8 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
     const bool fused = env_int("GAUSS_FUSED_SOLVE", 1) != 0;           // read per run: the tests drive both forms
     hipStream_t side = (solve && fused && job->n_panels > 0 && job->n_tiles > job->n_tiles_b11) ? ctx->side : nullptr;
     prof_begin(job, 1, st);
-    launch_pack_stats(job->d_probs, job->d_rowmap, job->n_rows, st);
+    if (job->resample_lds >= 0) launch_resample_pack(job->d_probs, job->d_rowmap, job->n_rows, job->resample_lds, st);
+    else launch_pack_stats(job->d_probs, job->d_rowmap, job->n_rows, st);
     // the certificate needs the row tables only and is read by B11's epilogue tiles and the chain: in a merged launch it
     // moves to the head of the chain queue, beside the Gram kernel's start (23 us off the main queue's critical path)
     const bool cert_on_chain = solve && job->chain_aside && merged;

@@ -665,14 +665,15 @@ int gauss_host_prep_zmix5_sup(gauss_ctx* ctx, const char* input_file, const char
     return prep_zmix_variant(ctx, ZMIX_5SUP, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, percentile, interval, 0, out);
 }
 
-int gauss_host_computeLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names,
-                         const double* pop_wgts, int n_pop_wgt, const char* input_file, const char* reference_index_file,
-                         const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,
-                         gauss_table** out)
+}  // extern "C"
+
+// computeLD's SNP selection (computeLD.cpp:26-93, 134-149), shared with simulateLD (simulateLD.cpp:44-124, 226-245).
+// On a sorted packed panel: the window as a merge (host_chrom.cpp:LeanWindow, measured SNPs only), rows from the resident panel --
+// as the one-window imputation calls above; GAUSS_HOST_FULL_MAP=1 or any other panel: the literal path (gauss_host_prepare).
+int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                   int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                   const char* reference_pop_desc_file, double af1_cutoff, LdRows& out)
 {
-    if (!ctx || !out) return herr("bad arguments");
-    // On a sorted packed panel: the window as a merge (host_chrom.cpp:LeanWindow, measured SNPs only), rows from the resident panel --
-    // as the one-window imputation calls above; GAUSS_HOST_FULL_MAP=1 or any other panel: the literal path below.
     if (input_file && reference_index_file && reference_data_file && reference_pop_desc_file && chr > 0 && !env_flag("GAUSS_HOST_FULL_MAP", false)) {
         std::string packed = reference_data_file, err;
         if (auto_pack_mode() != 0 && !PackedPanel::is_packed(packed)) {
@@ -694,16 +695,18 @@ int gauss_host_computeLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_
             const int M = (int)w.measured.size();
             if (M <= cs.a.min_num_measured_snp)                          // computeLD.cpp:89-93
                 return herr("Not enough number of SNPs loaded - computeLD not performed (measured %d)", M);
-            std::unique_ptr<gauss_table> t(new gauss_table());
-            t->matrix.assign((size_t)M * M, 0.0);
-            t->matrix_n = M;
             void* dev = nullptr;
             const int64_t bytes = pk->n_snp() * pk->row_bytes();
             const bool resident = panel_is_resident(ctx, packed, &dev) ||
                                   (bytes <= ((int64_t)4 << 30) && panel_make_resident(ctx, packed, &dev, nullptr) == 0 && gauss_store_wait(ctx, dev, 0) == 0);
-            if (gauss_ld_rows(ctx, GAUSS_MODE_WEIGHTED, resident ? (const uint8_t*)dev : pk->geno(), pk->row_bytes(), GAUSS_GENO_2BIT, w.store_rows_m.data(), M,
-                              cs.pop_off.data(), cs.pop_src_off.data(), cs.pop_wgt.data(), (int)cs.pop_off.size() - 1, 1.0, resident ? 1 : 0,
-                              t->matrix.data()) != 0) return herr("%s", gauss_last_error());
+            out.M = M;
+            out.store = resident ? (const uint8_t*)dev : pk->geno(); out.ld = pk->row_bytes(); out.geno_fmt = GAUSS_GENO_2BIT;
+            out.on_device = resident ? 1 : 0;
+            out.rows = w.store_rows_m;
+            out.pop_off = cs.pop_off; out.pop_src_off = cs.pop_src_off; out.pop_wgt = cs.pop_wgt;
+            out.a = cs.a;
+            out.pk = pk;
+            out.t.reset(new gauss_table());
             Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chrc{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
             Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}}, af{"af1mix", GAUSS_COL_DBL, {}, {}, {}};
             for (int32_t vi : w.measured) {                              // computeLD.cpp:134-149
@@ -712,37 +715,57 @@ int gauss_host_computeLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_
                 rsid.s.emplace_back(pk->str(ps.rsid)); chrc.i.push_back(ps.chr); bp.i.push_back((int)sn.bp);
                 a1.s.emplace_back(pk->str(ps.a1)); a2.s.emplace_back(pk->str(ps.a2)); af.d.push_back(sn.af);
             }
-            t->cols = {rsid, chrc, bp, a1, a2, af};
-            *out = t.release();
+            out.t->cols = {rsid, chrc, bp, a1, a2, af};
             return 0;
         }
     }
     gauss_prepared* p = nullptr;
     if (gauss_host_prepare(GAUSS_KIND_COMPUTELD, chr, start_bp, end_bp, 0, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file,
                            nullptr, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, &p)) return -1;
-    std::unique_ptr<gauss_prepared> hold(p);
+    out.prep.reset(p);
     const int M = (int)p->measured.size();
     if (M <= p->args.min_num_measured_snp)                               // computeLD.cpp:89-93
         return herr("Not enough number of SNPs loaded - computeLD not performed (measured %d)", M);
-    std::unique_ptr<gauss_table> t(new gauss_table());
-    t->matrix.assign((size_t)M * M, 0.0);
-    t->matrix_n = M;
+    out.M = M;
+    out.pop_off = p->pop_off; out.pop_wgt = p->pop_wgt;
+    out.a = p->args;
     if (p->packed_rows) {
-        const uint8_t* store = nullptr;
-        int on_device = 0;
-        if (packed_row_source(ctx, *p, &store, &on_device)) return -1;
-        if (gauss_ld_rows(ctx, GAUSS_MODE_WEIGHTED, store, p->args.pk->row_bytes(), GAUSS_GENO_2BIT, p->store_rows_m.data(), M,
-                          p->pop_off.data(), p->pop_src_off.data(), p->pop_wgt.data(), (int)p->pop_off.size() - 1, 1.0, on_device,
-                          t->matrix.data()) != 0) return herr("%s", gauss_last_error());
-    } else if (gauss_ld(ctx, GAUSS_MODE_WEIGHTED, p->gm.data(), M, p->ld, p->pop_off.data(), p->pop_wgt.data(),
-                        (int)p->pop_off.size() - 1, 1.0, t->matrix.data()) != 0) return herr("%s", gauss_last_error());
+        if (packed_row_source(ctx, *p, &out.store, &out.on_device)) return -1;
+        out.ld = p->args.pk->row_bytes(); out.geno_fmt = GAUSS_GENO_2BIT;
+        out.rows = p->store_rows_m;
+        out.pop_src_off = p->pop_src_off;
+    } else {
+        out.store = p->gm.data(); out.ld = p->ld; out.geno_fmt = GAUSS_GENO_U8; out.on_device = 0;
+    }
+    out.t.reset(new gauss_table());
     Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chrc{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
     Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}}, af{"af1mix", GAUSS_COL_DBL, {}, {}, {}};
     for (Snp* s : p->measured) {                                        // computeLD.cpp:134-149
         rsid.s.push_back(s->rsid); chrc.i.push_back(s->chr); bp.i.push_back((int)s->bp);
         a1.s.push_back(s->a1); a2.s.push_back(s->a2); af.d.push_back(s->af1mix);
     }
-    t->cols = {rsid, chrc, bp, a1, a2, af};
+    out.t->cols = {rsid, chrc, bp, a1, a2, af};
+    return 0;
+}
+
+extern "C" {
+
+int gauss_host_computeLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names,
+                         const double* pop_wgts, int n_pop_wgt, const char* input_file, const char* reference_index_file,
+                         const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,
+                         gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    LdRows s;
+    if (computeld_rows(ctx, chr, start_bp, end_bp, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file, reference_data_file,
+                       reference_pop_desc_file, af1_cutoff, s)) return -1;
+    const int M = s.M;
+    std::unique_ptr<gauss_table> t = std::move(s.t);
+    t->matrix.assign((size_t)M * M, 0.0);
+    t->matrix_n = M;
+    if (gauss_ld_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
+                      s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, 1.0, s.on_device,
+                      t->matrix.data()) != 0) return herr("%s", gauss_last_error());
     *out = t.release();
     return 0;
 }

@@ -485,3 +485,20 @@ int zmix_read(Args& a, const char* input_file, const char* reference_index_file,
 int zmix_ai_select(Args& a, const std::vector<Snp*>& measured, int step, double pct, std::vector<int>& kept, std::vector<double>& kept_nv);
 int zmix_genotypes(Args& a, const std::vector<Snp*>& sel, int N, int64_t* ld, std::vector<uint8_t>& G);
 int zmix_sup_groups(const Args& a, std::vector<int32_t>& pop_group, std::vector<std::string>& names);
+// computeLD's measured SNPs and where their genotype rows are (host_calls.cpp), shared by computeLD and simulateLD
+struct LdRows {
+    std::unique_ptr<gauss_table> t;     // the snplist columns: rsid chr bp a1 a2 af1mix
+    int M = 0;
+    const uint8_t* store = nullptr;     // rows as gauss_ld_rows takes them
+    int64_t ld = 0;
+    int geno_fmt = GAUSS_GENO_U8, on_device = 0;
+    std::vector<int32_t> rows;          // store rows (empty: rows 0 .. M - 1)
+    std::vector<int32_t> pop_off, pop_src_off;      // selected populations, panel order (pop_src_off empty for U8 rows)
+    std::vector<double> pop_wgt;
+    Args a;                             // population table, flags and weight map of the call
+    std::shared_ptr<PackedPanel> pk;    // what keeps `store` alive
+    std::unique_ptr<gauss_prepared> prep;
+};
+int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                   int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                   const char* reference_pop_desc_file, double af1_cutoff, LdRows& out);

@@ -230,6 +230,25 @@ def ld_matrix_rows(store, rows, pop_off, pop_wgt=None, mode=MODE_WEIGHTED, diag=
     return out
 
 
+def ld_resampled(store, rows, pop_off, draw_pop, draw_sample, n_cols, diag=1.0, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
+    """gauss_ld_resampled_rows: pooled LD (CalCor, n = n_cols) of the store rows `rows` (None: rows 0 .. S-1 of a numpy matrix)
+    over the drawn samples -- draw k is sample draw_sample[k] of population draw_pop[k] -- and n_cols - len(draws) zero columns
+    (simulateLD)."""
+    ctx = ctx or default_context()
+    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
+    po, _ = _pops(pop_off, None)
+    dp = np.ascontiguousarray(draw_pop, dtype=np.int32).reshape(-1)
+    ds = np.ascontiguousarray(draw_sample, dtype=np.int32).reshape(-1)
+    if dp.shape != ds.shape:
+        raise ValueError(f"draw_pop has {dp.size} entries, draw_sample {ds.size}")
+    S = len(r) if r is not None else store.shape[0]
+    out = np.zeros((S, S))
+    check(ctx.lib.gauss_ld_resampled_rows(ctx.handle, ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip), _lib.ptr(so, _ip),
+                                          len(po) - 1, dp.ctypes.data_as(_ip), ds.ctypes.data_as(_ip), int(dp.size), int(n_cols),
+                                          float(diag), on_dev, out.ctypes.data_as(_dp)))
+    return out
+
+
 def gene_ld_batch_rows(store, rows, pop_off, gene_off, pop_wgt=None, mode=MODE_POOLED, diag=1.1, fmt=_lib.GENO_2BIT,
                        pop_src_off=None, ctx=None):
     """gauss_gene_ld_batch_rows: LD blocks of all genes whose SNPs are the store rows `rows`."""

@@ -253,6 +253,18 @@ int gauss_gene_ld_batch_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int
                              int n_snp, const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop,
                              const int32_t* gene_off, int n_gene, double diag, int on_device, double* out_blocks);
 
+/* Resampled pooled LD (simulateLD(), simulateLD.cpp:134-199): the correlation matrix of n_snp rows over n_cols samples, of
+ * which sample k < n_drawn is sample draw_sample[k] of selected population draw_pop[k] (0 <= draw_pop[k] < n_pop, 0 <=
+ * draw_sample[k] < pop_off[q + 1] - pop_off[q]; repeats allowed) and the other n_cols - n_drawn are zeros -- CalCor with
+ * n = n_cols (util.cpp:49-70 operation order), `diag` on the diagonal, 0/0 = NaN where a row is constant.  Rows as in
+ * gauss_ld_rows (U8 or 2-bit with pop_src_off, host or resident store).  Only the drawn columns are packed and multiplied; the
+ * order of the draws changes no bit.  n_drawn = 0: NaN off the diagonal, no GPU work.  Sample counts whose exact integer sums
+ * would leave int range (n_drawn >= 9.5 M, n_cols > INT32_MAX) are GAUSS_E_RANGE.  Blocking. */
+int gauss_ld_resampled_rows(gauss_ctx* ctx, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp,
+                            const int32_t* pop_off, const int32_t* pop_src_off, int n_pop,
+                            const int32_t* draw_pop, const int32_t* draw_sample, int64_t n_drawn, int64_t n_cols,
+                            double diag, int on_device, double* out_cor);
+
 /* Per-population Pearson correlations of every SNP pair (prep_zmix5, zmix.cpp:158-176: CalCor on each
  * population's genotype strings, util.cpp:153-169).  out is [n_pop][n_snp*(n_snp-1)/2], population-major,
  * pairs in the reference's row order (i ascending, then j > i): column k+1 of the reference's column-major

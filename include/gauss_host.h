@@ -234,6 +234,25 @@ int gauss_host_popwgt_inputs(int kind, const char* input_file, const char* refer
  * "yty", "n_snp", "n_pairs", "n_rows" [1 x 1].  Errors with zmix.R's / solve.QP's messages: "zmix: no valid rows after
  * filtering." (fewer than two SNPs, or no finite row), a description file without Population_Abbreviation / Super_Population,
  * "matrix D in quadratic function is not positive definite!"; more than 64 groups is refused. */
+/* simulateLD(): the LD of a simulated cohort with the ancestry mix pop_names / pop_wgts (simulateLD.cpp:34-252).  The SNPs are
+ * computeLD's (same arguments, same selection, same snplist, same "Not enough number of SNPs loaded - computeLD not performed"
+ * error).  Every population of the weight map (names upper-cased; unknown names ignored, weight 0 included) gets
+ * (int)(w * sim_size) draws in PANEL order, each uniform_int_distribution<>(0, n_k - 1) -- written out as libstdc++ >= 11 draws it,
+ * Lemire's method on a 64-bit product -- from ONE std::mt19937(seed).  seed = -1 draws the seed from std::random_device (the
+ * reference's behaviour); 0 <= seed < 2^32 replays.  cormat is CalCor with n = sim_size over the drawn columns and
+ * sim_size - n_drawn zero columns (simulateLD.cpp:161-199, util.cpp:49-70), 1.0 on the diagonal, NaN where a row is constant.
+ * Refused where the reference is undefined: sim_size < 1, a negative or non-finite weight, sum of counts > sim_size.  Result:
+ * computeLD's table and matrix, named members "counts" [P x 1] (flagged populations, panel order), "draws" [n_drawn x 2]
+ * (flagged population index, sample) and "seed" [1 x 1], the seed used. */
+int gauss_host_simulateLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names,
+                          const double* pop_wgts, int n_pop_wgt, int64_t sim_size, const char* input_file,
+                          const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                          double af1_cutoff, int64_t seed, gauss_table** out);
+/* The draws of gauss_host_simulateLD alone (no GPU, no panel: the description file gives the population sizes).  Result: columns
+ * pop n count (the flagged populations, panel order) and the named members "counts", "draws", "seed" above. */
+int gauss_host_simulate_draws(const char* reference_pop_desc_file, const char* const* pop_names, const double* pop_wgts,
+                              int n_pop_wgt, int64_t sim_size, int64_t seed, gauss_table** out);
+
 #define GAUSS_ZMIX_POPULATION      0
 #define GAUSS_ZMIX_SUPERPOPULATION 1
 int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
