@@ -244,53 +244,68 @@ int gauss_impute_window(gauss_ctx* ctx, const gauss_window_desc* win)
     return rc;
 }
 
-struct RowSource {                 // where the rows of an LD-only call come from (default: a contiguous host byte matrix)
-    int geno_fmt = GAUSS_GENO_U8;
-    const int32_t* rows = nullptr;
-    const int32_t* pop_src_off = nullptr;
-    int on_device = 0;
-    const int32_t* draw_pop = nullptr;      // resampled window (gauss_ld_resampled_rows)
-    const int32_t* draw_sample = nullptr;
-    int64_t n_drawn = 0, n_cols = 0;
-};
-
-static int ld_common(gauss_ctx* ctx, int mode, const uint8_t* geno, int n_snp, int64_t ld,
-                     const int32_t* pop_off, const double* pop_wgt, int n_pop, double diag,
-                     const int32_t* gene_off, int n_gene, double* out, int64_t* out_counts, int n_samples,
-                     const RowSource& src = RowSource())
+// The window of an LD-only call: M rows of one matrix or store, no unmeasured SNPs, no z.  Whatever else a call sets (row lists, gene
+// blocks, a pair list, draws) it sets on the WinSpec it gets back; job_build copies what it keeps.
+static WinSpec ld_spec(int mode, const uint8_t* geno, int n_snp, int64_t ld, const int32_t* pop_off, const double* pop_wgt, int n_pop, double diag)
 {
-    if (!ctx || !geno || (!out && !out_counts)) return fail(GAUSS_E_INVALID, "bad arguments");
     WinSpec w;
-    int32_t off1[2] = {0, n_samples};
-    w.mode = mode; w.n_pop = out_counts ? 1 : n_pop; w.pop_off = out_counts ? off1 : pop_off; w.pop_wgt = pop_wgt;
+    w.mode = mode; w.n_pop = n_pop; w.pop_off = pop_off; w.pop_wgt = pop_wgt;
     w.M = n_snp; w.U = 0; w.geno_m = geno; w.geno_u = nullptr; w.ld = ld; w.z1 = nullptr;
-    w.lambda = 0; w.eps = 0; w.diag = diag; w.ld_only = 1; w.gene_off = gene_off; w.n_gene = n_gene;
-    w.geno_fmt = src.geno_fmt; w.rows_m = src.rows; w.pop_src_off = src.pop_src_off;
-    w.draw_pop = src.draw_pop; w.draw_sample = src.draw_sample; w.n_drawn = src.n_drawn; w.n_cols = src.n_cols;
+    w.lambda = 0; w.eps = 0; w.diag = diag; w.ld_only = 1; w.gene_off = nullptr; w.n_gene = 0;
+    return w;
+}
+// ... whose rows are named by index in a row store (host or device memory), 2-bit or bytes
+static WinSpec ld_spec_rows(int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp, const int32_t* pop_off,
+                            const int32_t* pop_src_off, const double* pop_wgt, int n_pop, double diag)
+{
+    WinSpec w = ld_spec(mode, store, n_snp, ld, pop_off, pop_wgt, n_pop, diag);
+    w.geno_fmt = geno_format; w.rows_m = rows; w.pop_src_off = pop_src_off;
+    return w;
+}
+
+typedef std::unique_ptr<gauss_job, void (*)(gauss_job*)> JobGuard;
+static int ld_job(gauss_ctx* ctx, const WinSpec& w, int on_device, JobGuard& guard)
+{
     gauss_job* job = nullptr;
     std::vector<WinSpec> specs{w};
-    int rc = job_build(ctx, specs, src.on_device, &job);
+    const int rc = job_build(ctx, specs, on_device, &job);
+    if (rc == 0) guard.reset(job);
+    return rc;
+}
+
+// the LD matrix (or the gene blocks) of w into `out`; out_counts (gauss_gram_counts): the Gram as exact integer counts instead
+static int ld_common(gauss_ctx* ctx, const WinSpec& w, int on_device, double* out, int64_t* out_counts = nullptr)
+{
+    if (!ctx || !w.geno_m || (!out && !out_counts)) return fail(GAUSS_E_INVALID, "bad arguments");
+    JobGuard job(nullptr, job_free);
+    int rc = ld_job(ctx, w, on_device, job);
     if (rc) return rc;
-    std::unique_ptr<gauss_job, void (*)(gauss_job*)> guard(job, job_free);
     if (!out_counts) job->plans[0].out_ld_user = out;
-    rc = job_run(job, false);
+    rc = job_run(job.get(), false);
     if (rc) return rc;
     if (out_counts) {
         DevBuf d_cnt;
-        const size_t bytes = sizeof(long long) * (size_t)n_snp * n_snp;
+        const size_t bytes = sizeof(long long) * (size_t)w.M * w.M;
         if (d_cnt.alloc(ctx, bytes) != hipSuccess) return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes of counts) failed", bytes);
         launch_counts(job->d_probs, 0, job->plans[0].p.npair, d_cnt.as<long long>(), ctx->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(ctx->stream));
         HIPCHK(hipMemcpy(out_counts, d_cnt.p, bytes, hipMemcpyDeviceToHost));
     }
-    return job_fetch(job);
+    return job_fetch(job.get());
+}
+
+int gauss_gram_counts(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int n_samples, int64_t ld, int64_t* out_counts)
+{
+    if (!out_counts) return fail(GAUSS_E_INVALID, "out_counts is NULL");
+    const int32_t off1[2] = {0, n_samples};                 // pooled over one population of n_samples
+    return ld_common(ctx, ld_spec(GAUSS_MODE_POOLED, geno, n_snp, ld, off1, nullptr, 1, 1.0), 0, nullptr, out_counts);
 }
 
 int gauss_ld(gauss_ctx* ctx, int mode, const uint8_t* geno, int n_snp, int64_t ld, const int32_t* pop_off,
              const double* pop_wgt, int n_pop, double diag, double* out_cor)
 {
-    return ld_common(ctx, mode, geno, n_snp, ld, pop_off, pop_wgt, n_pop, diag, nullptr, 0, out_cor, nullptr, 0);
+    return ld_common(ctx, ld_spec(mode, geno, n_snp, ld, pop_off, pop_wgt, n_pop, diag), 0, out_cor);
 }
 
 int gauss_gene_ld_batch(gauss_ctx* ctx, int mode, const uint8_t* geno, int n_snp, int64_t ld,
@@ -298,16 +313,16 @@ int gauss_gene_ld_batch(gauss_ctx* ctx, int mode, const uint8_t* geno, int n_snp
                         const int32_t* gene_off, int n_gene, double diag, double* out_blocks)
 {
     if (!gene_off || n_gene < 1) return fail(GAUSS_E_INVALID, "gene_off is NULL or n_gene < 1");
-    return ld_common(ctx, mode, geno, n_snp, ld, pop_off, pop_wgt, n_pop, diag, gene_off, n_gene, out_blocks, nullptr, 0);
+    WinSpec w = ld_spec(mode, geno, n_snp, ld, pop_off, pop_wgt, n_pop, diag);
+    w.gene_off = gene_off; w.n_gene = n_gene;
+    return ld_common(ctx, w, 0, out_blocks);
 }
 
 int gauss_ld_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp,
                   const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop, double diag,
                   int on_device, double* out_cor)
 {
-    RowSource src;
-    src.geno_fmt = geno_format; src.rows = rows; src.pop_src_off = pop_src_off; src.on_device = on_device;
-    return ld_common(ctx, mode, store, n_snp, ld, pop_off, pop_wgt, n_pop, diag, nullptr, 0, out_cor, nullptr, 0, src);
+    return ld_common(ctx, ld_spec_rows(mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop, diag), on_device, out_cor);
 }
 
 int gauss_ld_resampled_rows(gauss_ctx* ctx, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp,
@@ -328,10 +343,9 @@ int gauss_ld_resampled_rows(gauss_ctx* ctx, const uint8_t* store, int64_t ld, in
             for (size_t j = 0; j < S; j++) out_cor[i * S + j] = i == j ? diag : NAN;
         return GAUSS_OK;
     }
-    RowSource src;
-    src.geno_fmt = geno_format; src.rows = rows; src.pop_src_off = pop_src_off; src.on_device = on_device;
-    src.draw_pop = draw_pop; src.draw_sample = draw_sample; src.n_drawn = n_drawn; src.n_cols = n_cols;
-    return ld_common(ctx, GAUSS_MODE_POOLED, store, n_snp, ld, pop_off, nullptr, n_pop, diag, nullptr, 0, out_cor, nullptr, 0, src);
+    WinSpec w = ld_spec_rows(GAUSS_MODE_POOLED, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, nullptr, n_pop, diag);
+    w.draw_pop = draw_pop; w.draw_sample = draw_sample; w.n_drawn = n_drawn; w.n_cols = n_cols;
+    return ld_common(ctx, w, on_device, out_cor);
 }
 
 int gauss_gene_ld_batch_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows,
@@ -339,9 +353,35 @@ int gauss_gene_ld_batch_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int
                              const int32_t* gene_off, int n_gene, double diag, int on_device, double* out_blocks)
 {
     if (!gene_off || n_gene < 1) return fail(GAUSS_E_INVALID, "gene_off is NULL or n_gene < 1");
-    RowSource src;
-    src.geno_fmt = geno_format; src.rows = rows; src.pop_src_off = pop_src_off; src.on_device = on_device;
-    return ld_common(ctx, mode, store, n_snp, ld, pop_off, pop_wgt, n_pop, diag, gene_off, n_gene, out_blocks, nullptr, 0, src);
+    WinSpec w = ld_spec_rows(mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop, diag);
+    w.gene_off = gene_off; w.n_gene = n_gene;
+    return ld_common(ctx, w, on_device, out_blocks);
+}
+
+// The per-population calls (gauss_ld_per_pop, _pairs, gauss_zmix_normal_eq) run the WEIGHTED layout with every weight 1: it keeps
+// one exact Gram partial per population, which is all they read.  `w` points into `ones`.
+struct UnitWeightSpec {
+    std::vector<double> ones;
+    WinSpec w;
+    UnitWeightSpec(const uint8_t* geno, int n_snp, int64_t ld, const int32_t* pop_off, int n_pop)
+        : ones((size_t)std::max(n_pop, 1), 1.0), w(ld_spec(GAUSS_MODE_WEIGHTED, geno, n_snp, ld, pop_off, ones.data(), n_pop, 1.0)) {}
+};
+
+// pack + Gram only, for the jobs whose Gram partials another kernel reads: the LD epilogue has nothing to write for them
+static int pack_and_gram(gauss_job* job, hipStream_t st)
+{
+    launch_pack_stats(job->d_probs, job->d_rowmap, job->n_rows, st);
+    launch_gram(job->d_items, job->n_items, job->gram_i8, st);
+    HIPCHK(hipGetLastError());
+    return GAUSS_OK;
+}
+
+static int check_pop_group(const int32_t* pop_group, int n_pop, int n_group)
+{
+    if (pop_group)
+        for (int p = 0; p < n_pop; p++)
+            if (pop_group[p] < 0 || pop_group[p] >= n_group) return fail(GAUSS_E_INVALID, "pop_group[%d] = %d is outside 0..%d", p, pop_group[p], n_group - 1);
+    return GAUSS_OK;
 }
 
 int gauss_ld_per_pop(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64_t ld, const int32_t* pop_off, int n_pop,
@@ -349,18 +389,11 @@ int gauss_ld_per_pop(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64_t ld,
 {
     if (!ctx || !geno || !pop_off || !out) return fail(GAUSS_E_INVALID, "bad arguments to gauss_ld_per_pop");
     if (n_snp < 2) return fail(GAUSS_E_INVALID, "need at least two SNPs");
-    // the weighted layout keeps one exact Gram partial per population: all that is needed here
-    std::vector<double> ones((size_t)std::max(n_pop, 1), 1.0);
-    WinSpec w;
-    w.mode = GAUSS_MODE_WEIGHTED; w.n_pop = n_pop; w.pop_off = pop_off; w.pop_wgt = ones.data();
-    w.M = n_snp; w.U = 0; w.geno_m = geno; w.geno_u = nullptr; w.ld = ld; w.z1 = nullptr;
-    w.lambda = 0; w.eps = 0; w.diag = 1.0; w.ld_only = 1; w.gene_off = nullptr; w.n_gene = 0;
-    gauss_job* job = nullptr;
-    std::vector<WinSpec> specs{w};
-    int rc = job_build(ctx, specs, 0, &job);
+    const UnitWeightSpec u(geno, n_snp, ld, pop_off, n_pop);
+    JobGuard job(nullptr, job_free);
+    int rc = ld_job(ctx, u.w, 0, job);
     if (rc) return rc;
-    std::unique_ptr<gauss_job, void (*)(gauss_job*)> guard(job, job_free);
-    rc = job_run(job, false);
+    rc = job_run(job.get(), false);
     if (rc) return rc;
     const size_t npairs = (size_t)n_snp * (n_snp - 1) / 2;
     const size_t bytes = sizeof(double) * npairs * (size_t)n_pop;
@@ -381,25 +414,14 @@ int gauss_ld_per_pop_pairs(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64
     if (n_snp < 2 || n_pairs < 1) return fail(GAUSS_E_INVALID, "need at least two SNPs and one pair");
     if (!pop_group) n_group = n_pop;
     if (n_group < 1) return fail(GAUSS_E_INVALID, "n_group < 1");
-    if (pop_group)
-        for (int p = 0; p < n_pop; p++)
-            if (pop_group[p] < 0 || pop_group[p] >= n_group) return fail(GAUSS_E_INVALID, "pop_group[%d] = %d is outside 0..%d", p, pop_group[p], n_group - 1);
-    std::vector<double> ones((size_t)std::max(n_pop, 1), 1.0);
-    WinSpec w;
-    w.mode = GAUSS_MODE_WEIGHTED; w.n_pop = n_pop; w.pop_off = pop_off; w.pop_wgt = ones.data();
-    w.M = n_snp; w.U = 0; w.geno_m = geno; w.geno_u = nullptr; w.ld = ld; w.z1 = nullptr;
-    w.lambda = 0; w.eps = 0; w.diag = 1.0; w.ld_only = 1; w.gene_off = nullptr; w.n_gene = 0;
-    w.pair_i = pair_i; w.pair_j = pair_j; w.n_pairs = n_pairs;
-    gauss_job* job = nullptr;
-    std::vector<WinSpec> specs{w};
-    int rc = job_build(ctx, specs, 0, &job);
+    int rc = check_pop_group(pop_group, n_pop, n_group);
     if (rc) return rc;
-    std::unique_ptr<gauss_job, void (*)(gauss_job*)> guard(job, job_free);
-    // pack + Gram only: the LD epilogue has nothing to write for a pair list
+    UnitWeightSpec u(geno, n_snp, ld, pop_off, n_pop);
+    u.w.pair_i = pair_i; u.w.pair_j = pair_j; u.w.n_pairs = n_pairs;
+    JobGuard job(nullptr, job_free);
+    if ((rc = ld_job(ctx, u.w, 0, job)) != 0) return rc;
     hipStream_t st = ctx->stream;
-    launch_pack_stats(job->d_probs, job->d_rowmap, job->n_rows, st);
-    launch_gram(job->d_items, job->n_items, job->gram_i8, st);
-    HIPCHK(hipGetLastError());
+    if ((rc = pack_and_gram(job.get(), st)) != 0) return rc;
     std::vector<int2> pairs((size_t)n_pairs);
     for (int64_t k = 0; k < n_pairs; k++) pairs[(size_t)k] = make_int2(pair_i[k], pair_j[k]);
     DevBuf d_pairs, d_grp, d_out;
@@ -427,25 +449,14 @@ int gauss_zmix_normal_eq(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int64_t
     if (!pop_group) n_group = n_pop;
     if (n_group < 1 || n_group > 64)
         return fail(GAUSS_E_INVALID, "gauss_zmix_normal_eq: %d groups; the normal equations hold 1 .. 64", n_group);
-    if (pop_group)
-        for (int p = 0; p < n_pop; p++)
-            if (pop_group[p] < 0 || pop_group[p] >= n_group) return fail(GAUSS_E_INVALID, "pop_group[%d] = %d is outside 0..%d", p, pop_group[p], n_group - 1);
-    std::vector<double> ones((size_t)n_pop, 1.0);
-    WinSpec w;
-    w.mode = GAUSS_MODE_WEIGHTED; w.n_pop = n_pop; w.pop_off = pop_off; w.pop_wgt = ones.data();
-    w.M = n_snp; w.U = 0; w.geno_m = geno; w.geno_u = nullptr; w.ld = ld; w.z1 = nullptr;
-    w.lambda = 0; w.eps = 0; w.diag = 1.0; w.ld_only = 1; w.gene_off = nullptr; w.n_gene = 0;
-    w.gram_only = 1;
-    gauss_job* job = nullptr;
-    std::vector<WinSpec> specs{w};
-    int rc = job_build(ctx, specs, 0, &job);
+    int rc = check_pop_group(pop_group, n_pop, n_group);
     if (rc) return rc;
-    std::unique_ptr<gauss_job, void (*)(gauss_job*)> guard(job, job_free);
-    // pack + Gram only (as gauss_ld_per_pop_pairs): the correlations are formed and reduced in k_zmix.hip, never stored
+    UnitWeightSpec u(geno, n_snp, ld, pop_off, n_pop);
+    u.w.gram_only = 1;                  // the correlations are formed and reduced in k_zmix.hip, never stored
+    JobGuard job(nullptr, job_free);
+    if ((rc = ld_job(ctx, u.w, 0, job)) != 0) return rc;
     hipStream_t st = ctx->stream;
-    launch_pack_stats(job->d_probs, job->d_rowmap, job->n_rows, st);
-    launch_gram(job->d_items, job->n_items, job->gram_i8, st);
-    HIPCHK(hipGetLastError());
+    if ((rc = pack_and_gram(job.get(), st)) != 0) return rc;
     const int npair = job->plans[0].p.npair;
     const int ne = (n_group + 1) * (n_group + 2) / 2;
     DevBuf d_z, d_grp, d_part, d_part_n, d_out, d_out_n;
@@ -523,13 +534,6 @@ int gauss_pop_weights(gauss_ctx* ctx, const double* x, const int64_t* interval_o
     HIPCHK(hipStreamSynchronize(st));
     if (out_status) for (int i = 0; i < n_interval; i++) out_status[i] = stat[(size_t)i];
     return GAUSS_OK;
-}
-
-int gauss_gram_counts(gauss_ctx* ctx, const uint8_t* geno, int n_snp, int n_samples, int64_t ld, int64_t* out_counts)
-{
-    if (!out_counts) return fail(GAUSS_E_INVALID, "out_counts is NULL");
-    return ld_common(ctx, GAUSS_MODE_POOLED, geno, n_snp, ld, nullptr, nullptr, 1, 1.0, nullptr, 0, nullptr,
-                     out_counts, n_samples);
 }
 
 int gauss_pack2bit_device(gauss_ctx* ctx, const uint8_t* d_in, int64_t ld_in, uint8_t* d_out, int64_t ld_out,

@@ -3,47 +3,51 @@
 // hot path delegated to libgauss_hip.so.
 #include "host_internal.h"
 
-// Row store of an LD-only call on a packed panel: the resident copy in HBM when there is one (or the panel is small
-// enough to make resident on the spot: a chromosome is < 1 GB), else the mmap'd rows, gathered while staging.
-static int packed_row_source(gauss_ctx* ctx, const gauss_prepared& p, const uint8_t** store, int* on_device)
+
+// Row store of a call on a packed panel: the resident copy in HBM when there is one, else -- the genotype section is small enough to
+// make resident on the spot (a chromosome of the 33KG panel is 0.85 GB) -- uploaded now, else the mmap'd rows, gathered while
+// staging.  An upload that fails leaves the mapped rows too.  The wait after panel_make_resident is kept for every caller: the
+// upload it starts itself is synchronous, but it may instead FIND the entry of a background upload that a chromosome call on
+// another thread started after panel_is_resident looked, and rows may only be read once they have landed (gauss_store_wait costs a
+// map lookup when there is nothing to wait for, and this branch runs once per panel and context).
+static const int64_t RESIDENT_ON_DEMAND_MAX_BYTES = (int64_t)4 << 30;
+static void panel_rows(gauss_ctx* ctx, const std::string& path, const PackedPanel& pk, const uint8_t** store, int* on_device)
 {
-    const PackedPanel& pk = *p.args.pk;
     void* dev = nullptr;
-    const int64_t bytes = pk.n_snp() * pk.row_bytes();
-    if (panel_is_resident(ctx, p.args.reference_data_file, &dev) ||
-        (bytes <= ((int64_t)4 << 30) && panel_make_resident(ctx, p.args.reference_data_file, &dev, nullptr) == 0)) {
-        *store = (const uint8_t*)dev; *on_device = 1;
-        return 0;
-    }
-    *store = pk.geno(); *on_device = 0;
-    return 0;
+    const bool resident = panel_is_resident(ctx, path, &dev) ||
+                          (pk.n_snp() * pk.row_bytes() <= RESIDENT_ON_DEMAND_MAX_BYTES && panel_make_resident(ctx, path, &dev, nullptr) == 0 &&
+                           gauss_store_wait(ctx, dev, 0) == 0);
+    *store = resident ? (const uint8_t*)dev : pk.geno();
+    *on_device = resident ? 1 : 0;
 }
 
-extern "C" {
-
-static int host_prepare(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
-                        const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
-                        const char* annotation_file, const char* reference_index_file, const char* reference_data_file,
-                        const char* reference_pop_desc_file, double af1_cutoff, bool annotated_only, gauss_prepared** out);
-
-int gauss_host_prepare(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
-                       const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
-                       const char* annotation_file, const char* reference_index_file, const char* reference_data_file,
-                       const char* reference_pop_desc_file, double af1_cutoff, gauss_prepared** out)
+// The window of a one-window call on a sorted packed panel, built as the chromosome driver builds its windows (host_chrom.cpp:
+// LeanWindow -- a merge of the study's rows and the panel's SNP table instead of per-SNP objects in a map: ~0.1 ms against 0.7-1.0).
+// Returns 1 -- take the literal path, prepare_opened -- for an unsorted or text panel, a call over every chromosome or
+// GAUSS_HOST_FULL_MAP=1; errors come in prepare()'s order: arguments, description file, populations, study file.
+struct OneWindow {
+    ChromSetup cs;
+    LeanWindow w;                       // points into cs: a OneWindow stays where it was built
+};
+static int one_window_build(OneWindow& ow, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
+                            const char* const* names, const double* wgts, int nw, const char* input, const std::string& panel_path,
+                            const std::shared_ptr<PackedPanel>& pk, const char* desc, double af1_cutoff)
 {
-    // (the whole study enters the SNP map, as in the reference: gauss_prepared_snps lists it)
-    return host_prepare(kind, chr, start_bp, end_bp, wing_size, study_pop, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file,
-                        reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, false, out);
+    if (chr <= 0 || env_flag("GAUSS_HOST_FULL_MAP", false) || !pk || !pk->header().sorted) return 1;
+    if (chrom_setup(ow.cs, kind, chr, wing, study_pop, names, wgts, nw, input, panel_path, desc, af1_cutoff, pk, nullptr)) return -1;
+    std::string err;
+    ow.cs.gw = load_gwas_cached(input, err);
+    if (!ow.cs.gw) return herr("%s", err.c_str());
+    return lean_window_build(ow.w, ow.cs, start_bp, end_bp) ? -1 : 0;
 }
 
-static int host_prepare(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
-                        const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
-                        const char* annotation_file, const char* reference_index_file, const char* reference_data_file,
-                        const char* reference_pop_desc_file, double af1_cutoff, bool annotated_only, gauss_prepared** out)
+// gauss_host_prepare on a panel that open_panel has resolved already (panel_path, pk: empty for a text panel)
+static int prepare_opened(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                          const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                          const char* annotation_file, const char* reference_index_file, const std::string& panel_path,
+                          const std::shared_ptr<PackedPanel>& pk, const char* reference_pop_desc_file, double af1_cutoff,
+                          bool annotated_only, gauss_prepared** out)
 {
-    if (!out) return herr("out is NULL");
-    if (kind < 0 || kind > GAUSS_KIND_PREP_RECESSIVE) return herr("bad kind %d", kind);
-    if (!input_file || !reference_index_file || !reference_data_file || !reference_pop_desc_file) return herr("file name is NULL");
     std::unique_ptr<gauss_prepared> p(new gauss_prepared());
     p->kind = kind;
     Args& a = p->args;
@@ -51,23 +55,10 @@ static int host_prepare(int kind, int chr, int64_t start_bp, int64_t end_bp, int
     a.wing_size = (kind == GAUSS_KIND_COMPUTELD) ? 0 : wing_size;       // computeLD.cpp:40
     if (study_pop) a.study_pop = study_pop;
     a.input_file = input_file; a.reference_index_file = reference_index_file;
-    a.reference_data_file = reference_data_file; a.reference_pop_desc_file = reference_pop_desc_file;
+    a.reference_data_file = panel_path; a.reference_pop_desc_file = reference_pop_desc_file;
     if (annotation_file) a.annotation_file = annotation_file;
-    if (auto_pack_mode() != 0 && !PackedPanel::is_packed(a.reference_data_file)) {
-        // text panel: the cached packed form, if there is one (GAUSS_AUTO_PACK=1: made now)
-        std::string cached, err;
-        const int rc = resolve_packed_panel(a.reference_index_file, a.reference_data_file, a.reference_pop_desc_file,
-                                            auto_pack_mode() == 1, cached, err);
-        if (rc < 0) return herr("%s", err.c_str());
-        if (rc == 0) a.reference_data_file = cached;
-    }
-    if (PackedPanel::is_packed(a.reference_data_file)) {
-        // a packed panel replaces both the index and the data file (reference_index_file is not opened)
-        std::string err;
-        a.pk = open_packed_shared(a.reference_data_file, err);
-        if (!a.pk) return herr("%s", err.c_str());
-        a.drop_wing_unmeasured = (kind == GAUSS_KIND_DIST || kind == GAUSS_KIND_DISTMIX);
-    }
+    a.pk = pk;
+    a.drop_wing_unmeasured = pk && (kind == GAUSS_KIND_DIST || kind == GAUSS_KIND_DISTMIX);
     a.af1_cutoff = std::isnan(af1_cutoff) ? (kind == GAUSS_KIND_QCAT ? 0.05 : 0.01) : af1_cutoff;   // dist.cpp:53-57, qcat.cpp:53-57
     const bool mix = (kind == GAUSS_KIND_COMPUTELD || kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_JEPEGMIX ||
                       kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_PREP_RECESSIVE);
@@ -80,6 +71,34 @@ static int host_prepare(int kind, int chr, int64_t start_bp, int64_t end_bp, int
     if (prepare(*p)) return -1;
     *out = p.release();
     return 0;
+}
+
+// annotated_only: the gene drivers' SNP map (run_jepeg); gauss_host_prepare enters the whole study, as the reference does
+// (gauss_prepared_snps lists it)
+static int prepare_files(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                         const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                         const char* annotation_file, const char* reference_index_file, const char* reference_data_file,
+                         const char* reference_pop_desc_file, double af1_cutoff, bool annotated_only, gauss_prepared** out)
+{
+    if (!out) return herr("out is NULL");
+    if (kind < 0 || kind > GAUSS_KIND_PREP_RECESSIVE) return herr("bad kind %d", kind);
+    if (files_ok({input_file, reference_index_file, reference_data_file, reference_pop_desc_file})) return -1;
+    std::string panel_path;
+    std::shared_ptr<PackedPanel> pk;
+    if (open_panel(reference_index_file, reference_data_file, reference_pop_desc_file, panel_path, pk)) return -1;
+    return prepare_opened(kind, chr, start_bp, end_bp, wing_size, study_pop, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file,
+                          reference_index_file, panel_path, pk, reference_pop_desc_file, af1_cutoff, annotated_only, out);
+}
+
+extern "C" {
+
+int gauss_host_prepare(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                       const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                       const char* annotation_file, const char* reference_index_file, const char* reference_data_file,
+                       const char* reference_pop_desc_file, double af1_cutoff, gauss_prepared** out)
+{
+    return prepare_files(kind, chr, start_bp, end_bp, wing_size, study_pop, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file,
+                         reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, false, out);
 }
 
 const gauss_table* gauss_prepared_snps(const gauss_prepared* p)
@@ -233,69 +252,51 @@ int gauss_prepared_finish(gauss_prepared* p, gauss_table** out)
 
 // dist() / distmix() / qcat() / qcatmix(): ONE window per call, the reference's own usage (docs/articles/dist_example.md:144-153).
 //
-// On a sorted packed panel the window is built as the chromosome driver builds its windows (host_chrom.cpp:LeanWindow -- a merge of
-// the study's rows and the panel's SNP table instead of per-SNP objects in a map: ~0.1 ms against 0.7-1.0), its genotype rows are
-// read from the panel's resident copy in HBM (made on the first call when the panel's genotype section is at most 4 GB -- a
-// chromosome of the 33KG panel is 0.85 GB -- like the LD-only calls do, packed_row_source) instead of being gathered on the host and
-// copied per call (24 MB a window), and the window runs as a job of one on those rows.  Measured on the chr22 study, window after
-// window (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.  An unsorted panel, a text panel without a cached packed form, a
-// call over every chromosome or GAUSS_HOST_FULL_MAP=1 take the literal path: gauss_host_prepare + gauss_impute_window on host rows.
+// On a sorted packed panel the window is a lean one (one_window_build), its genotype rows are read from the panel's resident copy in
+// HBM (panel_rows) instead of being gathered on the host and copied per call (24 MB a window), and the window runs as a job of one on
+// those rows.  Measured on the chr22 study, window after window (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.  Otherwise
+// the literal path: prepare_opened + gauss_impute_window on host rows.
 static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
                       const char* const* names, const double* wgts, int nw, const char* input, const char* index,
                       const char* data, const char* desc, double af1_cutoff, gauss_table** out)
 {
     if (!ctx || !out) return herr("bad arguments");
-    if (!input || !index || !data || !desc) return herr("file name is NULL");
-    // the packed form of the panel, if there is one (as gauss_host_prepare resolves it)
-    std::string packed = data;
-    if (auto_pack_mode() != 0 && !PackedPanel::is_packed(packed)) {
-        std::string cached, err;
-        const int rc = resolve_packed_panel(index, data, desc, auto_pack_mode() == 1, cached, err);
-        if (rc < 0) return herr("%s", err.c_str());
-        if (rc == 0) packed = cached;
-    }
+    if (files_ok({input, index, data, desc})) return -1;
+    std::string panel_path;
+    std::shared_ptr<PackedPanel> pk;
+    if (open_panel(index, data, desc, panel_path, pk)) return -1;
     const bool lean_kind = (kind == GAUSS_KIND_DIST || kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_QCAT || kind == GAUSS_KIND_QCATMIX);
-    if (lean_kind && chr > 0 && !env_flag("GAUSS_HOST_FULL_MAP", false) && PackedPanel::is_packed(packed)) {
-        std::string err;
-        std::shared_ptr<PackedPanel> pk = open_packed_shared(packed, err);
-        if (!pk) return herr("%s", err.c_str());
-        if (pk->header().sorted) {
-            ChromSetup cs;                                       // (errors in prepare()'s order: arguments, description file, populations, study file)
-            if (chrom_setup(cs, kind, chr, wing, study_pop, names, wgts, nw, input, packed, desc, af1_cutoff, pk, nullptr)) return -1;
-            cs.gw = load_gwas_cached(input, err);
-            if (!cs.gw) return herr("%s", err.c_str());
-            LeanWindow w;
-            if (lean_window_build(w, cs, start_bp, end_bp)) return -1;
-            gauss_window_desc d;
-            if (lean_window_desc(w, &d)) return -1;
-            void* dev = nullptr;
-            const int64_t bytes = pk->n_snp() * pk->row_bytes();
-            const bool resident = panel_is_resident(ctx, packed, &dev) ||
-                                  (bytes <= ((int64_t)4 << 30) && panel_make_resident(ctx, packed, &dev, nullptr) == 0 && gauss_store_wait(ctx, dev, 0) == 0);
-            if (resident) {
-                d.geno_m = d.geno_u = (const uint8_t*)dev;
-                gauss_job* job = nullptr;
-                int rc = gauss_job_create(ctx, &d, 1, 1, &job);
-                if (rc == 0) rc = gauss_job_run(job);
-                if (rc == 0) rc = gauss_job_fetch(job);
-                if (job) gauss_job_destroy(job);
-                if (rc != 0) return herr("%s", gauss_last_error());
-            } else {
-                d.geno_m = d.geno_u = pk->geno();                 // a panel too large to keep in HBM: the window's rows from the mapped file
-                if (gauss_impute_window(ctx, &d) != 0) return herr("%s", gauss_last_error());
-            }
-            *out = lean_window_finish(w);
-            return 0;
+    OneWindow ow;
+    const int lean = lean_kind ? one_window_build(ow, kind, chr, start_bp, end_bp, wing, study_pop, names, wgts, nw, input, panel_path, pk, desc, af1_cutoff) : 1;
+    if (lean < 0) return -1;
+    if (lean == 0) {
+        gauss_window_desc d;                                  // (points into ow.w)
+        if (lean_window_desc(ow.w, &d)) return -1;
+        int on_device = 0;
+        panel_rows(ctx, panel_path, *pk, &d.geno_m, &on_device);
+        d.geno_u = d.geno_m;
+        if (on_device) {
+            gauss_job* job = nullptr;
+            int rc = gauss_job_create(ctx, &d, 1, 1, &job);
+            if (rc == 0) rc = gauss_job_run(job);
+            if (rc == 0) rc = gauss_job_fetch(job);
+            if (job) gauss_job_destroy(job);
+            if (rc != 0) return herr("%s", gauss_last_error());
+        } else if (gauss_impute_window(ctx, &d) != 0) {           // a panel too large to keep in HBM: the window's rows from the mapped file
+            return herr("%s", gauss_last_error());
         }
+        *out = lean_window_finish(ow.w);
+        return 0;
     }
     gauss_prepared* p = nullptr;
-    if (gauss_host_prepare(kind, chr, start_bp, end_bp, wing, study_pop, names, wgts, nw, input, nullptr, index, data, desc, af1_cutoff, &p)) return -1;
+    if (prepare_opened(kind, chr, start_bp, end_bp, wing, study_pop, names, wgts, nw, input, nullptr, index, panel_path, pk, desc, af1_cutoff, false, &p)) return -1;
     std::unique_ptr<gauss_prepared> hold(p);
     gauss_window_desc d;
     if (gauss_prepared_window_desc(p, &d)) return -1;
     if (gauss_impute_window(ctx, &d) != 0) return herr("%s", gauss_last_error());
     return gauss_prepared_finish(p, out);
 }
+
 
 int gauss_host_dist(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
                     const char* input_file, const char* reference_index_file, const char* reference_data_file,
@@ -349,6 +350,8 @@ int gauss_host_prep_recessive_impute(gauss_ctx* ctx, int chr, int64_t start_bp, 
                       n_pop_wgt, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out);
 }
 
+}  // extern "C"
+
 // stats::quantile(x, probs = p) of R, default type 7 (quantile.default): index = 1 + (n-1)p, lo = floor, hi = ceiling,
 // q = x[lo], and if index > lo and x[hi] != q:  q = (1-h) q + h x[hi]  with h = index - lo.  NaN input is an error in R.
 static int r_quantile7(std::vector<double> x, double p, double* q)
@@ -366,44 +369,31 @@ static int r_quantile7(std::vector<double> x, double p, double* q)
     return 0;
 }
 
-extern "C++" {    // internal helpers (host_internal.h), defined inside this file's C block
-
 // The reading that prep_zmix5, the prep_zmix selectors and zmix share (read_input_zmix / read_ref_index_zmix, zmix.cpp:44-110,
-// 1078-1181): the panel (replaced by its packed cache when auto-packing is on, opened as a packed panel when it is one), the
-// population table, every population flagged, the study's z merged with the index (allele-flipped to the panel's order) and
-// the measured SNPs in map order.
-int zmix_read(Args& a, const char* input_file, const char* reference_index_file, const char* reference_data_file,
-              const char* reference_pop_desc_file, SnpMap& m, std::vector<Snp*>& measured)
+// 1078-1181): the panel (open_panel_all_pops), the study's z merged with the index (allele-flipped to the panel's order) and the
+// measured SNPs in map order.
+int zmix_read(ZmixStudy& st, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+              const char* reference_pop_desc_file)
 {
+    Args& a = st.a;
     a.input_file = input_file; a.reference_index_file = reference_index_file;
     a.reference_data_file = reference_data_file; a.reference_pop_desc_file = reference_pop_desc_file;
-    if (auto_pack_mode() != 0 && !PackedPanel::is_packed(a.reference_data_file)) {
-        std::string cached, err;
-        const int rc = resolve_packed_panel(a.reference_index_file, a.reference_data_file, a.reference_pop_desc_file,
-                                            auto_pack_mode() == 1, cached, err);
-        if (rc < 0) return herr("%s", err.c_str());
-        if (rc == 0) a.reference_data_file = cached;
-    }
-    if (PackedPanel::is_packed(a.reference_data_file)) {
-        std::string err;
-        a.pk = open_packed_shared(a.reference_data_file, err);
-        if (!a.pk) return herr("%s", err.c_str());
-    }
-    if (read_ref_desc(a)) return -1;
-    if (a.pk && a.pk->n_pop() != a.num_pops) return herr("packed panel has %d populations, the description file %d", a.pk->n_pop(), a.num_pops);
-    a.pop_flag_vec.assign(a.num_pops, 1);                                     // zmix.cpp:148-150: every population
-    if (ReadInputZ(m, a, true)) return -1;                                    // read_input_zmix, zmix.cpp:1078-1113 (no window)
-    if (ReadReferenceIndex(m, a, true)) return -1;                            // read_ref_index_zmix, zmix.cpp:1115-1181
-    measured.clear();
-    for (auto& kv : m) if (kv.second->type == 1) measured.push_back(kv.second.get());   // zmix.cpp:88-92
+    if (open_panel_all_pops(a, reference_index_file)) return -1;              // zmix.cpp:148-150: every population
+    if (ReadInputZ(st.m, a, true)) return -1;                                 // read_input_zmix, zmix.cpp:1078-1113 (no window)
+    if (ReadReferenceIndex(st.m, a, true)) return -1;                         // read_ref_index_zmix, zmix.cpp:1115-1181
+    st.measured.clear();
+    for (auto& kv : st.m) if (kv.second->type == 1) st.measured.push_back(kv.second.get());   // zmix.cpp:88-92
     return 0;
 }
 
 // The ancestry-informative SNPs of prep_zmix5 / prep_zmix5_sup (zmix.cpp:111-139, 257-285): every step-th measured SNP,
 // cal_af_norm_var (zmix.cpp:1183-1214: variance of the panel AF columns, normalised by mean(1-mean)), kept iff its norm_var is
-// above the type-7 quantile `pct`.  kept: indices into `measured`, ascending; kept_nv: their norm_var.
-int zmix_ai_select(Args& a, const std::vector<Snp*>& measured, int step, double pct, std::vector<int>& kept, std::vector<double>& kept_nv)
+// above the type-7 quantile `pct` (cal_af_norm_var + the percentile cut).  kept: indices into `measured`, ascending; kept_nv: their
+// norm_var; sel, when asked for: the SNPs themselves.
+int zmix_ai_select(ZmixStudy& st, int step, double pct, std::vector<int>& kept, std::vector<double>& kept_nv, std::vector<Snp*>* sel)
 {
+    Args& a = st.a;
+    const std::vector<Snp*>& measured = st.measured;
     std::vector<int> sub;
     for (int i = 0; i < (int)measured.size(); i += step) sub.push_back(i);
     std::vector<double> norm_var;
@@ -427,6 +417,7 @@ int zmix_ai_select(Args& a, const std::vector<Snp*>& measured, int step, double 
     kept.clear(); kept_nv.clear();
     for (size_t i = 0; i < sub.size(); i++)
         if (norm_var[i] > cutoff) { kept.push_back(sub[i]); kept_nv.push_back(norm_var[i]); }   // zmix.cpp:135-139
+    if (sel) { sel->clear(); for (int i : kept) sel->push_back(measured[(size_t)i]); }
     return 0;
 }
 
@@ -465,58 +456,18 @@ int zmix_sup_groups(const Args& a, std::vector<int32_t>& pop_group, std::vector<
     return (int)names.size();
 }
 
-}  // extern "C++"
-
-int gauss_host_prep_zmix5(gauss_ctx* ctx, const char* input_file, const char* reference_index_file,
-                          const char* reference_data_file, const char* reference_pop_desc_file,
-                          double percentile, int interval, gauss_table** out)
+// The table of a prep_zmix call (one row per SNP pair in data_mat: z_i * z_j, then the pair's genotype correlation inside each
+// population or group): the listed SNPs with their z -- and norm_var, for the ancestry-informative selections -- and data_mat
+static std::unique_ptr<gauss_table> prep_zmix_table(const std::vector<Snp*>& sel, const std::vector<double>* norm_var, int nrow, int ncol,
+                                                    std::vector<double> data_mat)
 {
-    if (!ctx || !out) return herr("bad arguments");
-    if (!input_file || !reference_index_file || !reference_data_file || !reference_pop_desc_file) return herr("file name is NULL");
-    Args a;
-    const double pct = std::isnan(percentile) ? 0.99 : percentile;            // zmix.cpp:57-61
-    const int step = interval > 0 ? interval : 1;                             // zmix.cpp:63-67
-    SnpMap m;
-    std::vector<Snp*> measured;
-    if (zmix_read(a, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, m, measured)) return -1;
-    std::vector<int> kept;
-    std::vector<double> sub_nv;
-    if (zmix_ai_select(a, measured, step, pct, kept, sub_nv)) return -1;
-    std::vector<Snp*> sub;
-    for (int i : kept) sub.push_back(measured[(size_t)i]);
-
-    const int S = (int)sub.size(), P = a.num_pops;
-    int N = 0;
-    for (int k = 0; k < P; k++) N += a.ref_pop_size_vec[k];
-    std::vector<int32_t> pop_off(1, 0);
-    for (int k = 0; k < P; k++) pop_off.push_back(pop_off.back() + a.ref_pop_size_vec[k]);
-    const size_t npairs = S > 1 ? (size_t)S * (S - 1) / 2 : 0;
-    gauss_table* t = new gauss_table();
-    std::unique_ptr<gauss_table> hold(t);
-    NamedMat dm;
-    dm.name = "data_mat"; dm.nrow = (int)npairs; dm.ncol = 1 + P;
-    dm.d.assign(npairs * (size_t)(1 + P), 0.0);
-    if (S > 1) {
-        int64_t ld = 0;
-        std::vector<uint8_t> G;
-        if (zmix_genotypes(a, sub, N, &ld, G)) return -1;
-        size_t row = 0;
-        for (int i = 0; i < S; i++)
-            for (int j = i + 1; j < S; j++) dm.d[row++] = sub[i]->z * sub[j]->z;         // zmix.cpp:165
-        if (gauss_ld_per_pop(ctx, G.data(), S, ld, pop_off.data(), P, dm.d.data() + npairs) != 0)
-            return herr("%s", gauss_last_error());
-    }
-    Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chr{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
-    Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}}, z{"z", GAUSS_COL_DBL, {}, {}, {}};
-    Column nv{"norm_var", GAUSS_COL_DBL, {}, {}, {}};
-    for (int i = 0; i < S; i++) {
-        rsid.s.push_back(sub[i]->rsid); chr.i.push_back(sub[i]->chr); bp.i.push_back((int)sub[i]->bp);
-        a1.s.push_back(sub[i]->a1); a2.s.push_back(sub[i]->a2); z.d.push_back(sub[i]->z); nv.d.push_back(sub_nv[i]);
-    }
-    t->cols = {rsid, chr, bp, a1, a2, z, nv};
-    t->named.push_back(std::move(dm));
-    *out = hold.release();
-    return 0;
+    std::unique_ptr<gauss_table> t(new gauss_table());
+    add_ident_columns(*t, sel);
+    Column& z = t->add("z", GAUSS_COL_DBL);
+    for (Snp* s : sel) z.d.push_back(s->z);
+    if (norm_var) t->add("norm_var", GAUSS_COL_DBL).d = *norm_var;
+    t->put_named("data_mat", nrow, ncol, std::move(data_mat));
+    return t;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -539,15 +490,15 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
                              int p2, gauss_table** out)
 {
     if (!ctx || !out) return herr("bad arguments");
-    if (!input_file || !reference_index_file || !reference_data_file || !reference_pop_desc_file) return herr("file name is NULL");
-    Args a;
+    if (files_ok({input_file, reference_index_file, reference_data_file, reference_pop_desc_file})) return -1;
     // defaults: zmix.cpp:953-957 (1), 664-675 / 376-387 / 524-535 (1000 and 3 / 3 / 5), 214-224 (0.99, 1)
     const int step = interval > 0 ? interval : ((variant == ZMIX_ALL || variant == ZMIX_5SUP) ? 1 : 1000);
     const int par2 = p2 > 0 ? p2 : (variant == ZMIX_3 ? 5 : 3);
     const double pct = std::isnan(percentile) ? 0.99 : percentile;
-    SnpMap m;
-    std::vector<Snp*> measured;
-    if (zmix_read(a, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, m, measured)) return -1;
+    ZmixStudy st;
+    if (zmix_read(st, input_file, reference_index_file, reference_data_file, reference_pop_desc_file)) return -1;
+    Args& a = st.a;
+    const std::vector<Snp*>& measured = st.measured;
     const int n = (int)measured.size();
 
     // ---- which SNPs, which pairs (indices into `measured`) ----
@@ -557,8 +508,7 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
     if (variant == ZMIX_ALL || variant == ZMIX_3 || variant == ZMIX_5SUP) {
         std::vector<int> sub;
         if (variant == ZMIX_5SUP) {
-            // cal_af_norm_var + the percentile cut, as in prep_zmix5 (zmix.cpp:257-285)
-            if (zmix_ai_select(a, measured, step, pct, sub, sub_nv)) return -1;
+            if (zmix_ai_select(st, step, pct, sub, sub_nv, nullptr)) return -1;
         } else {
             for (int i = 0; i < n; i += step) sub.push_back(i);  // zmix.cpp:996-1004, 567-575
         }
@@ -595,14 +545,14 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
     std::vector<std::string> group_names = a.ref_pop_vec;
     if (variant == ZMIX_5SUP) n_group = zmix_sup_groups(a, pop_group, group_names);
     int N = 0;
-    std::vector<int32_t> pop_off(1, 0);
-    for (int k = 0; k < P; k++) { N += a.ref_pop_size_vec[(size_t)k]; pop_off.push_back(pop_off.back() + a.ref_pop_size_vec[(size_t)k]); }
+    const std::vector<int32_t> pop_off = panel_pop_off(a, &N);
     const size_t np = pairs.size();
     const int nlead = variant == ZMIX_4 ? 1 : 0;
-    std::unique_ptr<gauss_table> t(new gauss_table());
-    NamedMat dm;
-    dm.name = "data_mat"; dm.nrow = (int)np; dm.ncol = nlead + 1 + n_group;
-    dm.d.assign(np * (size_t)dm.ncol, 0.0);
+    const int ncol = nlead + 1 + n_group;
+    std::vector<double> dm(np * (size_t)ncol, 0.0);
+    // the pairs as rows of the SNP table
+    std::vector<double> pm(np * 2, 0.0);
+    for (size_t k = 0; k < np; k++) { pm[k] = row_of[(size_t)pairs[k].first]; pm[np + k] = row_of[(size_t)pairs[k].second]; }
     if (np > 0) {
         int64_t ld = 0;
         std::vector<uint8_t> G;
@@ -610,32 +560,95 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
         std::vector<int32_t> pi(np), pj(np);
         for (size_t k = 0; k < np; k++) {
             pi[k] = row_of[(size_t)pairs[k].first]; pj[k] = row_of[(size_t)pairs[k].second];
-            if (nlead) dm.d[k] = lead[k];
-            dm.d[(size_t)nlead * np + k] = measured[(size_t)pairs[k].first]->z * measured[(size_t)pairs[k].second]->z;
+            if (nlead) dm[k] = lead[k];
+            dm[(size_t)nlead * np + k] = measured[(size_t)pairs[k].first]->z * measured[(size_t)pairs[k].second]->z;
         }
         if (gauss_ld_per_pop_pairs(ctx, G.data(), S, ld, pop_off.data(), P, pop_group.empty() ? nullptr : pop_group.data(), n_group,
-                                   pi.data(), pj.data(), (int64_t)np, dm.d.data() + (size_t)(nlead + 1) * np) != 0)
+                                   pi.data(), pj.data(), (int64_t)np, dm.data() + (size_t)(nlead + 1) * np) != 0)
             return herr("%s", gauss_last_error());
     }
-    Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chr{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
-    Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}}, z{"z", GAUSS_COL_DBL, {}, {}, {}};
-    for (Snp* s : sel) {
-        rsid.s.push_back(s->rsid); chr.i.push_back(s->chr); bp.i.push_back((int)s->bp);
-        a1.s.push_back(s->a1); a2.s.push_back(s->a2); z.d.push_back(s->z);
-    }
-    t->cols = {rsid, chr, bp, a1, a2, z};
-    if (variant == ZMIX_5SUP) { Column nv{"norm_var", GAUSS_COL_DBL, {}, {}, {}}; nv.d = sub_nv; t->cols.push_back(nv); }
-    t->named.push_back(std::move(dm));
-    {
-        // the groups the correlation columns stand for, and the pairs as rows of the SNP table
-        NamedMat pm;
-        pm.name = "pairs"; pm.nrow = (int)np; pm.ncol = 2;
-        pm.d.assign(np * 2, 0.0);
-        for (size_t k = 0; k < np; k++) { pm.d[k] = row_of[(size_t)pairs[k].first]; pm.d[np + k] = row_of[(size_t)pairs[k].second]; }
-        t->named.push_back(std::move(pm));
-        for (const std::string& g : group_names) t->messages.push_back(g);
-    }
+    std::unique_ptr<gauss_table> t = prep_zmix_table(sel, variant == ZMIX_5SUP ? &sub_nv : nullptr, (int)np, ncol, std::move(dm));
+    t->put_named("pairs", (int)np, 2, std::move(pm));
+    for (const std::string& g : group_names) t->messages.push_back(g);      // the groups the correlation columns stand for
     *out = t.release();
+    return 0;
+}
+
+// computeLD's SNP selection (computeLD.cpp:26-93, 134-149), shared with simulateLD (simulateLD.cpp:44-124, 226-245): a lean window
+// of measured SNPs only with rows from the resident panel where one_window_build allows, else the literal path (prepare_opened).
+int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                   int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                   const char* reference_pop_desc_file, double af1_cutoff, LdRows& out)
+{
+    if (files_ok({input_file, reference_index_file, reference_data_file, reference_pop_desc_file})) return -1;
+    std::string panel_path;
+    if (open_panel(reference_index_file, reference_data_file, reference_pop_desc_file, panel_path, out.pk)) return -1;
+    OneWindow ow;
+    const int lean = one_window_build(ow, GAUSS_KIND_COMPUTELD, chr, start_bp, end_bp, 0, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                      panel_path, out.pk, reference_pop_desc_file, af1_cutoff);
+    if (lean < 0) return -1;
+    gauss_prepared* p = nullptr;
+    if (lean == 1) {
+        if (prepare_opened(GAUSS_KIND_COMPUTELD, chr, start_bp, end_bp, 0, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file, nullptr,
+                           reference_index_file, panel_path, out.pk, reference_pop_desc_file, af1_cutoff, false, &p)) return -1;
+        out.prep.reset(p);
+    }
+    out.a = p ? p->args : ow.cs.a;
+    out.M = (int)(p ? p->measured.size() : ow.w.measured.size());
+    if (out.M <= out.a.min_num_measured_snp)                             // computeLD.cpp:89-93
+        return herr("Not enough number of SNPs loaded - computeLD not performed (measured %d)", out.M);
+    out.pop_off = p ? p->pop_off : ow.cs.pop_off;
+    out.pop_wgt = p ? p->pop_wgt : ow.cs.pop_wgt;
+    if (!p || p->packed_rows) {
+        panel_rows(ctx, panel_path, *out.pk, &out.store, &out.on_device);
+        out.ld = out.pk->row_bytes(); out.geno_fmt = GAUSS_GENO_2BIT;
+        out.rows = p ? p->store_rows_m : ow.w.store_rows_m;
+        out.pop_src_off = p ? p->pop_src_off : ow.cs.pop_src_off;
+    } else {
+        out.store = p->gm.data(); out.ld = p->ld; out.geno_fmt = GAUSS_GENO_U8; out.on_device = 0;
+    }
+    out.t.reset(new gauss_table());                                      // computeLD.cpp:134-149
+    if (p) add_ident_columns(*out.t, p->measured);
+    else add_ident_columns(*out.t, ow.w.measured.size(), [&](size_t i) { return ident_of(*out.pk, ow.w.v[(size_t)ow.w.measured[i]]); });
+    Column& af = out.t->add("af1mix", GAUSS_COL_DBL);
+    if (p) for (Snp* s : p->measured) af.d.push_back(s->af1mix);
+    else for (int32_t vi : ow.w.measured) af.d.push_back(ow.w.v[(size_t)vi].af);
+    return 0;
+}
+
+extern "C" {
+
+int gauss_host_prep_zmix5(gauss_ctx* ctx, const char* input_file, const char* reference_index_file,
+                          const char* reference_data_file, const char* reference_pop_desc_file,
+                          double percentile, int interval, gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    if (files_ok({input_file, reference_index_file, reference_data_file, reference_pop_desc_file})) return -1;
+    const double pct = std::isnan(percentile) ? 0.99 : percentile;            // zmix.cpp:57-61
+    const int step = interval > 0 ? interval : 1;                             // zmix.cpp:63-67
+    ZmixStudy st;
+    if (zmix_read(st, input_file, reference_index_file, reference_data_file, reference_pop_desc_file)) return -1;
+    std::vector<int> kept;
+    std::vector<double> sub_nv;
+    std::vector<Snp*> sub;
+    if (zmix_ai_select(st, step, pct, kept, sub_nv, &sub)) return -1;
+    const int S = (int)sub.size(), P = st.a.num_pops;
+    int N = 0;
+    const std::vector<int32_t> pop_off = panel_pop_off(st.a, &N);
+    const size_t npairs = S > 1 ? (size_t)S * (S - 1) / 2 : 0;
+    std::vector<double> dm(npairs * (size_t)(1 + P), 0.0);
+    if (S > 1) {
+        int64_t ld = 0;
+        std::vector<uint8_t> G;
+        if (zmix_genotypes(st.a, sub, N, &ld, G)) return -1;
+        size_t row = 0;
+        for (int i = 0; i < S; i++)
+            for (int j = i + 1; j < S; j++) dm[row++] = sub[i]->z * sub[j]->z;           // zmix.cpp:165
+        // (all pairs: gauss_ld_per_pop -- no pair list to upload)
+        if (gauss_ld_per_pop(ctx, G.data(), S, ld, pop_off.data(), P, dm.data() + npairs) != 0)
+            return herr("%s", gauss_last_error());
+    }
+    *out = prep_zmix_table(sub, &sub_nv, (int)npairs, 1 + P, std::move(dm)).release();
     return 0;
 }
 
@@ -664,91 +677,6 @@ int gauss_host_prep_zmix5_sup(gauss_ctx* ctx, const char* input_file, const char
 {
     return prep_zmix_variant(ctx, ZMIX_5SUP, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, percentile, interval, 0, out);
 }
-
-}  // extern "C"
-
-// computeLD's SNP selection (computeLD.cpp:26-93, 134-149), shared with simulateLD (simulateLD.cpp:44-124, 226-245).
-// On a sorted packed panel: the window as a merge (host_chrom.cpp:LeanWindow, measured SNPs only), rows from the resident panel --
-// as the one-window imputation calls above; GAUSS_HOST_FULL_MAP=1 or any other panel: the literal path (gauss_host_prepare).
-int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
-                   int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
-                   const char* reference_pop_desc_file, double af1_cutoff, LdRows& out)
-{
-    if (input_file && reference_index_file && reference_data_file && reference_pop_desc_file && chr > 0 && !env_flag("GAUSS_HOST_FULL_MAP", false)) {
-        std::string packed = reference_data_file, err;
-        if (auto_pack_mode() != 0 && !PackedPanel::is_packed(packed)) {
-            std::string cached;
-            const int rc = resolve_packed_panel(reference_index_file, reference_data_file, reference_pop_desc_file, auto_pack_mode() == 1, cached, err);
-            if (rc < 0) return herr("%s", err.c_str());
-            if (rc == 0) packed = cached;
-        }
-        std::shared_ptr<PackedPanel> pk;
-        if (PackedPanel::is_packed(packed) && !(pk = open_packed_shared(packed, err))) return herr("%s", err.c_str());
-        if (pk && pk->header().sorted) {
-            ChromSetup cs;
-            if (chrom_setup(cs, GAUSS_KIND_COMPUTELD, chr, 0, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file, packed, reference_pop_desc_file,
-                            af1_cutoff, pk, nullptr)) return -1;
-            cs.gw = load_gwas_cached(input_file, err);
-            if (!cs.gw) return herr("%s", err.c_str());
-            LeanWindow w;
-            if (lean_window_build(w, cs, start_bp, end_bp)) return -1;
-            const int M = (int)w.measured.size();
-            if (M <= cs.a.min_num_measured_snp)                          // computeLD.cpp:89-93
-                return herr("Not enough number of SNPs loaded - computeLD not performed (measured %d)", M);
-            void* dev = nullptr;
-            const int64_t bytes = pk->n_snp() * pk->row_bytes();
-            const bool resident = panel_is_resident(ctx, packed, &dev) ||
-                                  (bytes <= ((int64_t)4 << 30) && panel_make_resident(ctx, packed, &dev, nullptr) == 0 && gauss_store_wait(ctx, dev, 0) == 0);
-            out.M = M;
-            out.store = resident ? (const uint8_t*)dev : pk->geno(); out.ld = pk->row_bytes(); out.geno_fmt = GAUSS_GENO_2BIT;
-            out.on_device = resident ? 1 : 0;
-            out.rows = w.store_rows_m;
-            out.pop_off = cs.pop_off; out.pop_src_off = cs.pop_src_off; out.pop_wgt = cs.pop_wgt;
-            out.a = cs.a;
-            out.pk = pk;
-            out.t.reset(new gauss_table());
-            Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chrc{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
-            Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}}, af{"af1mix", GAUSS_COL_DBL, {}, {}, {}};
-            for (int32_t vi : w.measured) {                              // computeLD.cpp:134-149
-                const LeanSnp& sn = w.v[(size_t)vi];
-                const PkSnp& ps = pk->snp(sn.row);
-                rsid.s.emplace_back(pk->str(ps.rsid)); chrc.i.push_back(ps.chr); bp.i.push_back((int)sn.bp);
-                a1.s.emplace_back(pk->str(ps.a1)); a2.s.emplace_back(pk->str(ps.a2)); af.d.push_back(sn.af);
-            }
-            out.t->cols = {rsid, chrc, bp, a1, a2, af};
-            return 0;
-        }
-    }
-    gauss_prepared* p = nullptr;
-    if (gauss_host_prepare(GAUSS_KIND_COMPUTELD, chr, start_bp, end_bp, 0, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file,
-                           nullptr, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, &p)) return -1;
-    out.prep.reset(p);
-    const int M = (int)p->measured.size();
-    if (M <= p->args.min_num_measured_snp)                               // computeLD.cpp:89-93
-        return herr("Not enough number of SNPs loaded - computeLD not performed (measured %d)", M);
-    out.M = M;
-    out.pop_off = p->pop_off; out.pop_wgt = p->pop_wgt;
-    out.a = p->args;
-    if (p->packed_rows) {
-        if (packed_row_source(ctx, *p, &out.store, &out.on_device)) return -1;
-        out.ld = p->args.pk->row_bytes(); out.geno_fmt = GAUSS_GENO_2BIT;
-        out.rows = p->store_rows_m;
-        out.pop_src_off = p->pop_src_off;
-    } else {
-        out.store = p->gm.data(); out.ld = p->ld; out.geno_fmt = GAUSS_GENO_U8; out.on_device = 0;
-    }
-    out.t.reset(new gauss_table());
-    Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chrc{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
-    Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}}, af{"af1mix", GAUSS_COL_DBL, {}, {}, {}};
-    for (Snp* s : p->measured) {                                        // computeLD.cpp:134-149
-        rsid.s.push_back(s->rsid); chrc.i.push_back(s->chr); bp.i.push_back((int)s->bp);
-        a1.s.push_back(s->a1); a2.s.push_back(s->a2); af.d.push_back(s->af1mix);
-    }
-    out.t->cols = {rsid, chrc, bp, a1, a2, af};
-    return 0;
-}
-
-extern "C" {
 
 int gauss_host_computeLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names,
                          const double* pop_wgts, int n_pop_wgt, const char* input_file, const char* reference_index_file,
@@ -831,10 +759,7 @@ static gauss_table* jepeg_table(const gauss_prepared& p, int g0, int g1, const d
         ts.s.push_back(r.top_snp); tsp.d.push_back(r.top_snp_pval);
     }
     t->cols = {geneid, chisq, df, jp, ns, tc, tcp, ts, tsp};          // jepeg.cpp:143-151
-    NamedMat gr;
-    gr.name = "gene_range"; gr.nrow = 1; gr.ncol = 3;
-    gr.d = {(double)g0, (double)g1, (double)(p.gene_off.empty() ? 0 : (int)p.gene_off.size() - 1)};
-    t->named.push_back(std::move(gr));
+    t->put_named("gene_range", 1, 3, {(double)g0, (double)g1, (double)(p.gene_off.empty() ? 0 : (int)p.gene_off.size() - 1)});
     return t.release();
 }
 
@@ -860,11 +785,11 @@ static int run_jepeg(gauss_ctx* ctx, int kind, const char* study_pop, const char
     // position at a time: only the study SNPs at positions the annotation names enter the SNP map (plus the positions the study
     // lists more than once or under equal alleles -- the only ones where the reference's duplicate check can fire, so a study that
     // fails there still fails).  A chromosome's study is four times its annotated SNPs: the data layer of a jepegmix() call
-    // 3.9 -> 1.0 ms.  GAUSS_HOST_FULL_MAP=1: the whole study, as gauss_host_prepare does it (same table, bit for bit:
+    // 3.9 -> 1.0 ms.  GAUSS_HOST_FULL_MAP=1: the whole study, as gauss_host_prepare enters it (same table, bit for bit:
     // tests/test_gpu_drivers.py).
     const bool full_map = env_flag("GAUSS_HOST_FULL_MAP", false);
     const double t_begin = now_s();
-    if (host_prepare(kind, 0, 0, 0, 0, study_pop, names, wgts, nw, input, annotation, index, data, desc, af1_cutoff, !full_map, &p)) return -1;
+    if (prepare_files(kind, 0, 0, 0, 0, study_pop, names, wgts, nw, input, annotation, index, data, desc, af1_cutoff, !full_map, &p)) return -1;
     std::unique_ptr<gauss_prepared> hold(p);
     const double t_prepared = now_s();
     const Args& a = p->args;
@@ -889,7 +814,7 @@ static int run_jepeg(gauss_ctx* ctx, int kind, const char* study_pop, const char
         if (p->packed_rows) {
             const uint8_t* store = nullptr;
             int on_device = 0;
-            if (packed_row_source(ctx, *p, &store, &on_device)) return -1;
+            panel_rows(ctx, a.reference_data_file, *a.pk, &store, &on_device);
             if (gauss_gene_ld_batch_rows(ctx, mode, store, a.pk->row_bytes(), GAUSS_GENO_2BIT, p->store_rows_m.data() + r0, S,
                                          p->pop_off.data(), p->pop_src_off.data(), p->pop_wgt.data(), (int)p->pop_off.size() - 1,
                                          goff.data(), ng, 1.0 + a.lambda, on_device, blocks.data()) != 0)

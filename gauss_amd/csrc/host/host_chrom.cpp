@@ -238,11 +238,7 @@ int chrom_setup(ChromSetup& cs, int kind, int chr, int64_t wing_size, const char
         set_pop_wgt_map(a, pop_names, pop_wgts, n_pop_wgt);
     } else if (!study_pop) return herr("study_pop is NULL");
     if (read_ref_desc(a)) return -1;
-    if (pk->n_pop() != a.num_pops) return herr("packed panel has %d populations, the description file %d", pk->n_pop(), a.num_pops);
-    for (int k = 0; k < a.num_pops; k++)
-        if (a.ref_pop_vec[k] != pk->pop(k).name || a.ref_pop_size_vec[k] != (int)pk->pop(k).size)
-            return herr("packed panel population %d is %s (%u samples), the description file says %s (%d)", k,
-                        pk->pop(k).name, pk->pop(k).size, a.ref_pop_vec[k].c_str(), a.ref_pop_size_vec[k]);
+    if (panel_matches_desc(a, *pk, true)) return -1;
     if (cs.mix) init_pop_flag_wgt_vec(a);
     else if (init_pop_flag_vec(a)) return -1;
     cs.pop_off.assign(1, 0);
@@ -403,41 +399,38 @@ void lean_table_prebuild(LeanWindow& w)
     const ChromSetup& cs = *w.cs;
     const PackedPanel& pk = *cs.a.pk;
     std::unique_ptr<gauss_table> t(new gauss_table());
-    Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chr{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
-    Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}};
-    Column af{cs.mix ? "af1mix" : "af1ref", GAUSS_COL_DBL, {}, {}, {}}, z{"z", GAUSS_COL_DBL, {}, {}, {}};
-    Column pval{"pval", GAUSS_COL_DBL, {}, {}, {}}, info{"info", GAUSS_COL_DBL, {}, {}, {}}, type{"type", GAUSS_COL_INT, {}, {}, {}};
-    Column qm{"qcat_m", GAUSS_COL_INT, {}, {}, {}}, qt{"qcat_t", GAUSS_COL_DBL, {}, {}, {}};
-    Column qc{"qcat_chisq", GAUSS_COL_DBL, {}, {}, {}}, qp{"qcat_pval", GAUSS_COL_DBL, {}, {}, {}};
-    size_t n_out = 0;
+    std::vector<size_t> rows;                                                     // of w.v: the prediction window (dist.cpp:92, qcat.cpp:95)
     w.out_row.assign(w.v.size(), -1);
     for (size_t r = 0; r < w.v.size(); r++) {
-        const int ibp = (int)w.v[r].bp;                                           // dist.cpp:92, qcat.cpp:95
-        if (ibp >= w.start_bp && ibp <= w.end_bp) w.out_row[r] = (int32_t)n_out++;
+        const int ibp = (int)w.v[r].bp;
+        if (ibp >= w.start_bp && ibp <= w.end_bp) { w.out_row[r] = (int32_t)rows.size(); rows.push_back(r); }
     }
-    for (Column* c : {&rsid, &a1, &a2}) c->s.reserve(n_out);
-    for (Column* c : {&chr, &bp, &type}) c->i.reserve(n_out);
+    const size_t n_out = rows.size();
+    add_ident_columns(*t, n_out, [&](size_t i) { return ident_of(pk, w.v[rows[i]]); });
+    Column &af = t->add(cs.mix ? "af1mix" : "af1ref", GAUSS_COL_DBL), &z = t->add("z", GAUSS_COL_DBL);
     for (Column* c : {&af, &z}) c->d.reserve(n_out);
-    if (cs.qcat) { qm.i.reserve(n_out); for (Column* c : {&qt, &qc, &qp}) c->d.reserve(n_out); }
-    else for (Column* c : {&pval, &info}) c->d.reserve(n_out);
-    for (size_t r = 0; r < w.v.size(); r++) {
-        if (w.out_row[r] < 0) continue;
-        const LeanSnp& sn = w.v[r];
-        const PkSnp& ps = pk.snp(sn.row);
-        rsid.s.emplace_back(pk.str(ps.rsid)); chr.i.push_back(ps.chr); bp.i.push_back((int)sn.bp);
-        a1.s.emplace_back(pk.str(ps.a1)); a2.s.emplace_back(pk.str(ps.a2));
-        af.d.push_back(sn.af); z.d.push_back(sn.z); type.i.push_back(sn.type);
-        if (cs.qcat) {
+    for (size_t r : rows) { af.d.push_back(w.v[r].af); z.d.push_back(w.v[r].z); }
+    if (cs.qcat) {
+        Column &qm = t->add("qcat_m", GAUSS_COL_INT), &qt = t->add("qcat_t", GAUSS_COL_DBL), &qc = t->add("qcat_chisq", GAUSS_COL_DBL);
+        Column& qp = t->add("qcat_pval", GAUSS_COL_DBL);
+        qm.i.reserve(n_out);
+        for (Column* c : {&qt, &qc, &qp}) c->d.reserve(n_out);
+        for (size_t r : rows) {
+            const LeanSnp& sn = w.v[r];
             qm.i.push_back(sn.qcat_m); qt.d.push_back(sn.qcat_t); qc.d.push_back(sn.qcat_chisq);
             qp.d.push_back(pchisq_upper(sn.qcat_chisq, 1));                       // qcat.cpp:107
-        } else {
-            pval.d.push_back(2 * pnorm_upper(fabs(sn.z)));                        // dist.cpp:101
-            info.d.push_back(sn.info);
+        }
+    } else {
+        Column &pval = t->add("pval", GAUSS_COL_DBL), &info = t->add("info", GAUSS_COL_DBL);
+        for (Column* c : {&pval, &info}) c->d.reserve(n_out);
+        for (size_t r : rows) {
+            pval.d.push_back(2 * pnorm_upper(fabs(w.v[r].z)));                    // dist.cpp:101
+            info.d.push_back(w.v[r].info);
         }
     }
-    t->cols.reserve(12);
-    if (cs.qcat) for (Column* c : {&rsid, &chr, &bp, &a1, &a2, &af, &z, &qm, &qt, &qc, &qp, &type}) t->cols.push_back(std::move(*c));
-    else for (Column* c : {&rsid, &chr, &bp, &a1, &a2, &af, &z, &pval, &info, &type}) t->cols.push_back(std::move(*c));
+    Column& type = t->add("type", GAUSS_COL_INT);
+    type.i.reserve(n_out);
+    for (size_t r : rows) type.i.push_back(w.v[r].type);
     w.pre = std::move(t);
 }
 
@@ -743,11 +736,7 @@ int gauss_host_chrom_window_view(int kind, int chr, int64_t start_bp, int64_t en
     for (const LeanSnp& sn : w.v) type.i.push_back(sn.type);
     Column& fpos = t->add("fpos", GAUSS_COL_DBL);
     for (const LeanSnp& sn : w.v) fpos.d.push_back((double)sn.row);
-    auto named = [&](const char* name, const std::vector<double>& v) {
-        NamedMat nm;
-        nm.name = name; nm.nrow = (int)v.size(); nm.ncol = 1; nm.d = v;
-        t->named.push_back(std::move(nm));
-    };
+    auto named = [&](const char* name, std::vector<double> v) { const int n = (int)v.size(); t->put_named(name, n, 1, std::move(v)); };
     named("rows_m", std::vector<double>(w.store_rows_m.begin(), w.store_rows_m.end()));
     named("rows_u", std::vector<double>(w.store_rows_u.begin(), w.store_rows_u.end()));
     named("z1", w.z1);
@@ -831,32 +820,21 @@ int gauss_host_impute_chromosome(gauss_ctx* ctx, int kind, int chr, int64_t star
 {
     if (!ctx || !out || !input_file || !reference_data_file_in || !reference_pop_desc_file) return herr("bad arguments");
     // the reference's own panel format is accepted: its packed form is made on first use and kept in the panel cache
+    const double t_begin = now_s();
     std::string packed_path;
-    double t_autopack = 0;
-    if (!PackedPanel::is_packed(reference_data_file_in)) {
-        if (auto_pack_mode() == 0 || !reference_index_file)
-            return herr("gauss_host_impute_chromosome needs a packed panel (gauss_host_pack_panel), or the text panel's index file "
-                        "with GAUSS_AUTO_PACK not 0");
-        const double t0 = now_s();
-        std::string err;
-        if (resolve_packed_panel(reference_index_file, reference_data_file_in, reference_pop_desc_file, true, packed_path, err) != 0)
-            return herr("%s", err.c_str());
-        t_autopack = now_s() - t0;
-    } else packed_path = reference_data_file_in;
+    std::shared_ptr<PackedPanel> pk;
+    if (open_panel(reference_index_file, reference_data_file_in, reference_pop_desc_file, packed_path, pk, true)) return -1;
+    const double t_opened = now_s();
     const char* reference_data_file = packed_path.c_str();
     if (kind != GAUSS_KIND_DIST && kind != GAUSS_KIND_DISTMIX && kind != GAUSS_KIND_QCAT && kind != GAUSS_KIND_QCATMIX)
         return herr("gauss_host_impute_chromosome: kind must be dist, distmix, qcat or qcatmix");
     if (window_size < 1 || end_bp < start_bp || world < 1 || rank < 0 || rank >= world) return herr("bad window / rank arguments");
-    const double t_begin = now_s() - t_autopack;
     const bool chrom_trace = host_trace("chrom");
     gauss_chrom_stats st;
     memset(&st, 0, sizeof(st));
 
     // ---- plan: windows, costs, owners (identical on every rank) ----
     std::string err;
-    std::shared_ptr<PackedPanel> pk = open_packed_shared(reference_data_file, err);
-    if (!pk) return herr("%s", err.c_str());
-    const double t_opened = now_s();
     // First use of the panel: its rows start travelling NOW, before the study file is even parsed (2 ms for a chromosome's study) --
     // the upload below then finds the store under way.  (Only the default, background form; an error shows up at that later call.)
     void* dev_probe0 = nullptr;
@@ -1303,17 +1281,16 @@ int gauss_host_impute_chromosome(gauss_ctx* ctx, int kind, int chr, int64_t star
     }
     all->cols.push_back(win_col);
     {
-        NamedMat nm;
-        nm.name = "windows"; nm.nrow = (int)wins.size(); nm.ncol = 6;
-        nm.d.assign((size_t)nm.nrow * 6, 0.0);
-        for (int i = 0; i < nm.nrow; i++) {
+        const int nw = (int)wins.size();
+        std::vector<double> wd((size_t)nw * 6, 0.0);
+        for (int i = 0; i < nw; i++) {
             const ChromWin& w = wins[i];
             const double v[6] = {(double)w.s, (double)w.e, (double)w.owner, (double)w.status, (double)w.M, (double)w.U};
-            for (int c = 0; c < 6; c++) nm.d[(size_t)c * nm.nrow + i] = v[c];
+            for (int c = 0; c < 6; c++) wd[(size_t)c * nw + i] = v[c];
             if (w.status == 1) st.n_skipped++;
             if (w.status == 2) { st.n_failed++; if (all->messages.size() < 64) all->messages.push_back("window " + std::to_string(i) + ": " + w.why); }
         }
-        all->named.push_back(nm);
+        all->put_named("windows", nw, 6, std::move(wd));
     }
     st.t_tables += now_s() - tt;
     st.t_total = now_s() - t_begin;

@@ -690,8 +690,8 @@ static bool dir_usable(const std::string& d, bool create, bool private_only)
 
 // 0: `out` names a packed panel (the data file itself if it already is one).  1: no cached panel and create == false.
 // -1: error (message in err).
-int resolve_packed_panel(const std::string& index_file, const std::string& data_file, const std::string& desc_file,
-                                bool create, std::string& out, std::string& err, int64_t* packed_now)
+static int resolve_packed_panel(const std::string& index_file, const std::string& data_file, const std::string& desc_file,
+                                bool create, std::string& out, std::string& err, int64_t* packed_now = nullptr)
 {
     if (packed_now) *packed_now = 0;
     if (PackedPanel::is_packed(data_file)) { out = data_file; return 0; }
@@ -755,10 +755,75 @@ int resolve_packed_panel(const std::string& index_file, const std::string& data_
 // everywhere.  Unset: a one-window entry point uses a cached panel when one exists but does not make one (packing a
 // genome-wide panel takes minutes; one window from the text files takes a second), the chromosome driver -- which needs
 // the packed form -- packs on first use.
-int auto_pack_mode()
+static int auto_pack_mode()
 {
     const char* e = getenv("GAUSS_AUTO_PACK");
     return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+}
+
+// The panel an entry point works on.  A text panel is replaced by its packed form from the cache when auto-packing is on (made
+// now under GAUSS_AUTO_PACK=1; index_file NULL: the cache is not consulted), and a packed panel -- which stands for both the
+// index and the data file -- is opened: `path` is the data file to use, `pk` its shared mapping or empty for a text panel.
+// require_packed (the chromosome driver, which has no text path): the packed form is made on first use unless GAUSS_AUTO_PACK=0.
+int open_panel(const char* index_file, const std::string& data_file, const char* desc_file, std::string& path,
+               std::shared_ptr<PackedPanel>& pk, bool require_packed)
+{
+    std::string err;
+    path = data_file;
+    pk.reset();
+    if (!PackedPanel::is_packed(path)) {
+        const int mode = auto_pack_mode();
+        if (require_packed && (mode == 0 || !index_file))
+            return herr("gauss_host_impute_chromosome needs a packed panel (gauss_host_pack_panel), or the text panel's index file "
+                        "with GAUSS_AUTO_PACK not 0");
+        if (mode != 0 && index_file) {
+            std::string cached;
+            const int rc = resolve_packed_panel(index_file, data_file, desc_file, require_packed || mode == 1, cached, err);
+            if (rc < 0) return herr("%s", err.c_str());
+            if (rc == 0) path = cached;
+        }
+    }
+    if (PackedPanel::is_packed(path) && !(pk = open_packed_shared(path, err))) return herr("%s", err.c_str());
+    return 0;
+}
+
+// A packed panel against the description file the call names (read_ref_desc): the population count, and with `names` every
+// population's name and size
+int panel_matches_desc(const Args& a, const PackedPanel& pk, bool names)
+{
+    if (pk.n_pop() != a.num_pops) return herr("packed panel has %d populations, the description file %d", pk.n_pop(), a.num_pops);
+    for (int k = 0; names && k < a.num_pops; k++)
+        if (a.ref_pop_vec[k] != pk.pop(k).name || a.ref_pop_size_vec[k] != (int)pk.pop(k).size)
+            return herr("packed panel population %d is %s (%u samples), the description file says %s (%d)", k,
+                        pk.pop(k).name, pk.pop(k).size, a.ref_pop_vec[k].c_str(), a.ref_pop_size_vec[k]);
+    return 0;
+}
+
+// open_panel for the calls that work on EVERY population of the description file (afmix / cpw2, the zmix family): the panel
+// of a.reference_*_file opened into a, the description file read and checked against it, every population flagged
+int open_panel_all_pops(Args& a, const char* index_file)
+{
+    if (open_panel(index_file, std::string(a.reference_data_file), a.reference_pop_desc_file.c_str(), a.reference_data_file, a.pk)) return -1;
+    if (read_ref_desc(a)) return -1;
+    if (a.pk && panel_matches_desc(a, *a.pk, false)) return -1;
+    a.pop_flag_vec.assign(a.num_pops, 1);
+    return 0;
+}
+
+// Sample offsets of ALL populations of the description file, panel order; *N = their samples
+std::vector<int32_t> panel_pop_off(const Args& a, int* N)
+{
+    std::vector<int32_t> off(1, 0);
+    for (int n : a.ref_pop_size_vec) off.push_back(off.back() + n);
+    *N = off.back();
+    return off;
+}
+
+// every file name a call needs is there
+int files_ok(std::initializer_list<const char*> names)
+{
+    for (const char* f : names) if (!f) return herr("file name is NULL");
+    return 0;
 }
 
 
@@ -849,13 +914,7 @@ int prepare(gauss_prepared& p)
     double tt[8] = {0};
     tt[0] = tnow();
     if (read_ref_desc(a)) return -1;
-    if (a.pk) {
-        if (a.pk->n_pop() != a.num_pops) return herr("packed panel has %d populations, the description file %d", a.pk->n_pop(), a.num_pops);
-        for (int k = 0; k < a.num_pops; k++)
-            if (a.ref_pop_vec[k] != a.pk->pop(k).name || a.ref_pop_size_vec[k] != (int)a.pk->pop(k).size)
-                return herr("packed panel population %d is %s (%u samples), the description file says %s (%d)", k,
-                            a.pk->pop(k).name, a.pk->pop(k).size, a.ref_pop_vec[k].c_str(), a.ref_pop_size_vec[k]);
-    }
+    if (a.pk && panel_matches_desc(a, *a.pk, true)) return -1;
     if (mix) init_pop_flag_wgt_vec(a);
     else if (init_pop_flag_vec(a)) return -1;
     tt[1] = tnow();
@@ -986,7 +1045,7 @@ int64_t gauss_host_bgzf_copy(const char* in_path, const char* out_path)
 
 int64_t gauss_host_pack_panel(const char* index_file, const char* data_file, const char* desc_file, const char* out_file)
 {
-    if (!index_file || !data_file || !desc_file || !out_file) { herr("file name is NULL"); return -1; }
+    if (files_ok({index_file, data_file, desc_file, out_file})) return -1;
     std::string err;
     const int64_t n = gauss_host::pack_panel(index_file, data_file, desc_file, out_file, err);
     if (n < 0) herr("%s", err.c_str());

@@ -3,7 +3,7 @@
 // the routines that cross files.  Nothing here is exported: the library is built with -fvisibility=hidden and only the C ABI
 // of include/gauss_host.h is visible.
 //   host_feeder.cpp   the reference's readers and filters (ReadInputZ, ReadReferenceIndex, MakeSnpVec, ReadAnnotation, ...), the
-//                     packed-panel cache, prepare()
+//                     packed-panel cache and open_panel, prepare()
 //   host_tables.cpp   result tables, the JEPEG k x k tail, the table accessors of the C ABI
 //   host_calls.cpp    the one-window / one-call entry points (computeLD, dist, distmix, qcat, prep_*, jepeg, jepegmix)
 //   host_popwgt.cpp   afmix / cpw2: study allele frequencies against the panel's, per-interval weights on the GPU
@@ -94,7 +94,17 @@ struct gauss_table {
         const Column& c = cols[0];
         return (int)(c.type == GAUSS_COL_STR ? c.s.size() : c.type == GAUSS_COL_INT ? c.i.size() : c.d.size());
     }
-    Column& add(const char* name, int type) { Column c; c.name = name; c.type = type; cols.push_back(std::move(c)); return cols.back(); }
+    // room for MAX_COLS columns (the widest table, qcat's) is reserved on first use, so the reference add() returns stays valid
+    // while the caller adds the columns that follow
+    enum { MAX_COLS = 12 };
+    Column& add(const char* name, int type) { cols.reserve(MAX_COLS); Column c; c.name = name; c.type = type; cols.push_back(std::move(c)); return cols.back(); }
+    // a named matrix from column-major data (NamedMat's own layout), taken over without a copy
+    void put_named(const char* name, int nrow, int ncol, std::vector<double> colmajor)
+    {
+        NamedMat nm;
+        nm.name = name; nm.nrow = nrow; nm.ncol = ncol; nm.d = std::move(colmajor);
+        named.push_back(std::move(nm));
+    }
 };
 
 // ------------------------------------------------------------------------------------------
@@ -449,6 +459,30 @@ int lean_window_desc(LeanWindow& w, gauss_window_desc* d);
 void lean_table_prebuild(LeanWindow& w);
 gauss_table* lean_window_finish(LeanWindow& w);
 
+// The columns every SNP table opens with -- rsid chr bp a1 a2 -- for rows 0 .. n - 1, each described by at(i): a Snp of the SNP
+// map, or a row of the packed panel's SNP table (LeanSnp::bp is that row's position).  The caller adds its own columns after.
+struct SnpIdent { const char* rsid; int chr; long long bp; const char* a1; const char* a2; };
+inline SnpIdent ident_of(const Snp& s) { return {s.rsid.c_str(), s.chr, s.bp, s.a1.c_str(), s.a2.c_str()}; }
+inline SnpIdent ident_of(const PackedPanel& pk, const LeanSnp& sn)
+{
+    const PkSnp& ps = pk.snp(sn.row);
+    return {pk.str(ps.rsid), ps.chr, sn.bp, pk.str(ps.a1), pk.str(ps.a2)};
+}
+template <class F>
+inline void add_ident_columns(gauss_table& t, size_t n, F at)
+{
+    Column &rsid = t.add("rsid", GAUSS_COL_STR), &chr = t.add("chr", GAUSS_COL_INT), &bp = t.add("bp", GAUSS_COL_INT);
+    Column &a1 = t.add("a1", GAUSS_COL_STR), &a2 = t.add("a2", GAUSS_COL_STR);
+    for (Column* c : {&rsid, &a1, &a2}) c->s.reserve(n);
+    for (Column* c : {&chr, &bp}) c->i.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        const SnpIdent s = at(i);
+        rsid.s.emplace_back(s.rsid); chr.i.push_back(s.chr); bp.i.push_back((int)s.bp);
+        a1.s.emplace_back(s.a1); a2.s.emplace_back(s.a2);
+    }
+}
+inline void add_ident_columns(gauss_table& t, const std::vector<Snp*>& rows) { add_ident_columns(t, rows.size(), [&](size_t i) { return ident_of(*rows[i]); }); }
+
 // ---- routines that cross translation units ----
 int read_ref_desc(Args& a);
 int init_pop_flag_vec(Args& a);
@@ -463,9 +497,13 @@ int merge_index_entry(SnpMap& m, const Args& a, bool All, const std::string& rsi
 int ReadReferenceIndex(SnpMap& m, const Args& a, bool All);
 void load_line(BgzfReader& fp, Snp& s, const Args& a, std::vector<double>* af_out);
 std::shared_ptr<PackedPanel> open_packed_shared(const std::string& path, std::string& err);
-int resolve_packed_panel(const std::string& index_file, const std::string& data_file, const std::string& desc_file,
-                                bool create, std::string& out, std::string& err, int64_t* packed_now = nullptr);
-int auto_pack_mode();
+// the panel of a call: its packed form from the cache where GAUSS_AUTO_PACK allows, opened when packed (host_feeder.cpp)
+int open_panel(const char* index_file, const std::string& data_file, const char* desc_file, std::string& path,
+               std::shared_ptr<PackedPanel>& pk, bool require_packed = false);
+int open_panel_all_pops(Args& a, const char* index_file);
+int panel_matches_desc(const Args& a, const PackedPanel& pk, bool names);
+std::vector<int32_t> panel_pop_off(const Args& a, int* N);
+int files_ok(std::initializer_list<const char*> names);       // "file name is NULL"
 void fill_matrix(std::vector<uint8_t>& G, const std::vector<Snp*>& rows, int64_t ld);
 void unpack_rows(const gauss_prepared& p, const std::vector<Snp*>& rows, std::vector<uint8_t>& G);
 void materialise_from_packed(gauss_prepared& p);
@@ -480,9 +518,10 @@ gauss_table* prep_output(gauss_prepared& p);
 int panel_make_resident(gauss_ctx* ctx, const std::string& path, void** dev, int64_t* uploaded, bool async = false);
 bool panel_is_resident(gauss_ctx* ctx, const std::string& path, void** dev, bool wait = true);
 // zmix's SNP selection, shared by prep_zmix5, the prep_zmix selectors and zmix (host_calls.cpp)
-int zmix_read(Args& a, const char* input_file, const char* reference_index_file, const char* reference_data_file,
-              const char* reference_pop_desc_file, SnpMap& m, std::vector<Snp*>& measured);
-int zmix_ai_select(Args& a, const std::vector<Snp*>& measured, int step, double pct, std::vector<int>& kept, std::vector<double>& kept_nv);
+struct ZmixStudy { Args a; SnpMap m; std::vector<Snp*> measured; };       // the panel, the merged SNP map, its type-1 SNPs in map order
+int zmix_read(ZmixStudy& st, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+              const char* reference_pop_desc_file);
+int zmix_ai_select(ZmixStudy& st, int step, double pct, std::vector<int>& kept, std::vector<double>& kept_nv, std::vector<Snp*>* sel);
 int zmix_genotypes(Args& a, const std::vector<Snp*>& sel, int N, int64_t* ld, std::vector<uint8_t>& G);
 int zmix_sup_groups(const Args& a, std::vector<int32_t>& pop_group, std::vector<std::string>& names);
 // computeLD's measured SNPs and where their genotype rows are (host_calls.cpp), shared by computeLD and simulateLD

@@ -22,28 +22,14 @@ int popwgt_inputs(int kind, const char* input_file, const char* reference_index_
                   const char* reference_pop_desc_file, int interval, PwInputs& in)
 {
     if (kind != GAUSS_KIND_AFMIX && kind != GAUSS_KIND_CPW2) return herr("kind %d is neither GAUSS_KIND_AFMIX nor GAUSS_KIND_CPW2", kind);
-    if (!input_file || !reference_data_file || !reference_pop_desc_file) return herr("file name is NULL");
+    if (files_ok({input_file, reference_data_file, reference_pop_desc_file})) return -1;
     Args& a = in.a;
     a.input_file = input_file; a.reference_index_file = reference_index_file ? reference_index_file : "";
     a.reference_data_file = reference_data_file; a.reference_pop_desc_file = reference_pop_desc_file;
     in.interval = interval > 0 ? interval : 1000;                              // afmix.cpp:47-51 (R NULL -> 1000)
-    if (auto_pack_mode() != 0 && !PackedPanel::is_packed(a.reference_data_file) && reference_index_file) {
-        std::string cached, err;
-        const int rc = resolve_packed_panel(a.reference_index_file, a.reference_data_file, a.reference_pop_desc_file,
-                                            auto_pack_mode() == 1, cached, err);
-        if (rc < 0) return herr("%s", err.c_str());
-        if (rc == 0) a.reference_data_file = cached;
-    }
-    if (PackedPanel::is_packed(a.reference_data_file)) {
-        std::string err;
-        a.pk = open_packed_shared(a.reference_data_file, err);
-        if (!a.pk) return herr("%s", err.c_str());
-    } else if (!reference_index_file) {
+    if (!reference_index_file && !PackedPanel::is_packed(reference_data_file))
         return herr("reference_index_file is NULL and '%s' is not a packed panel", reference_data_file);
-    }
-    if (read_ref_desc(a)) return -1;
-    if (a.pk && a.pk->n_pop() != a.num_pops) return herr("packed panel has %d populations, the description file %d", a.pk->n_pop(), a.num_pops);
-    a.pop_flag_vec.assign(a.num_pops, 1);                                      // every population of the description file
+    if (open_panel_all_pops(a, reference_index_file)) return -1;              // every population of the description file
     in.P = a.num_pops;
     if (ReadInputAf(in.m, a)) return -1;
     if (ReadReferenceIndex(in.m, a, true)) return -1;
@@ -103,13 +89,6 @@ int popwgt_inputs(int kind, const char* input_file, const char* reference_index_
     return 0;
 }
 
-void add_named(gauss_table& t, const char* name, int nrow, int ncol, std::vector<double> d)
-{
-    NamedMat nm;
-    nm.name = name; nm.nrow = nrow; nm.ncol = ncol; nm.d = std::move(d);
-    t.named.push_back(std::move(nm));
-}
-
 int run_popwgt(gauss_ctx* ctx, int kind, const char* input_file, const char* reference_index_file, const char* reference_data_file,
                const char* reference_pop_desc_file, int interval, gauss_table** out)
 {
@@ -141,14 +120,14 @@ int run_popwgt(gauss_ctx* ctx, int kind, const char* input_file, const char* ref
             t->cols[(size_t)c0 + 1].d.push_back(w);
         }
     }
-    add_named(*t, "w_raw", P, 1, W);
+    t->put_named("w_raw", P, 1, W);
     std::vector<double> wi((size_t)iv * P), st((size_t)iv);
     for (int i = 0; i < iv; i++) {
         for (int p = 0; p < P; p++) wi[(size_t)p * iv + i] = w_int[(size_t)i * P + p];       // column-major
         st[(size_t)i] = status[(size_t)i];
     }
-    add_named(*t, "w_interval", iv, P, std::move(wi));
-    add_named(*t, "status", iv, 1, std::move(st));
+    t->put_named("w_interval", iv, P, std::move(wi));
+    t->put_named("status", iv, 1, std::move(st));
     int n_nan = 0;
     for (int i = 0; i < iv; i++) n_nan += (status[(size_t)i] & GAUSS_ST_NONFINITE) ? 1 : 0;
     if (n_nan) {
@@ -189,20 +168,17 @@ int gauss_host_popwgt_inputs(int kind, const char* input_file, const char* refer
     PwInputs in;
     if (popwgt_inputs(kind, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, interval, in)) return -1;
     std::unique_ptr<gauss_table> t(new gauss_table());
-    t->add("rsid", GAUSS_COL_STR); t->add("chr", GAUSS_COL_INT); t->add("bp", GAUSS_COL_INT);
-    t->add("a1", GAUSS_COL_STR); t->add("a2", GAUSS_COL_STR); t->add("af1study", GAUSS_COL_DBL);
-    for (Snp* s : in.measured) {
-        t->cols[0].s.push_back(s->rsid); t->cols[1].i.push_back(s->chr); t->cols[2].i.push_back((int32_t)s->bp);
-        t->cols[3].s.push_back(s->a1); t->cols[4].s.push_back(s->a2); t->cols[5].d.push_back(s->af1study);
-    }
+    add_ident_columns(*t, in.measured);
+    Column& af = t->add("af1study", GAUSS_COL_DBL);
+    for (Snp* s : in.measured) af.d.push_back(s->af1study);
     const int64_t S = (int64_t)in.measured.size();
     const int nc = in.P + 1;
     std::vector<double> x((size_t)S * nc);
     for (int64_t r = 0; r < S; r++)
         for (int c = 0; c < nc; c++) x[(size_t)c * S + r] = in.x[(size_t)r * nc + c];         // column-major
-    add_named(*t, "x", (int)S, nc, std::move(x));
+    t->put_named("x", (int)S, nc, std::move(x));
     std::vector<double> off(in.off.begin(), in.off.end());
-    add_named(*t, "interval_off", (int)in.off.size(), 1, std::move(off));
+    t->put_named("interval_off", (int)in.off.size(), 1, std::move(off));
     *out = t.release();
     return 0;
 }

@@ -7,13 +7,6 @@
 
 namespace {
 
-void put_named(gauss_table& t, const char* name, int nrow, int ncol, std::vector<double> d)
-{
-    NamedMat nm;
-    nm.name = name; nm.nrow = nrow; nm.ncol = ncol; nm.d = std::move(d);
-    t.named.push_back(std::move(nm));
-}
-
 // uniform_int_distribution<>(0, n - 1) on a 32-bit generator as libstdc++ >= 11 draws it: Lemire's nearly-divisionless method on
 // a 64-bit product, rejecting while the low word is below (2^32 - n) mod n.  Written out, it gives the same draws everywhere.
 inline uint32_t bounded_draw(std::mt19937& gen, uint32_t n)
@@ -81,12 +74,12 @@ int simulate_draws(const Args& a, int64_t sim_size, int64_t seed, SimDraws& d)
 // named members shared by both entry points: counts [P x 1], draws [n_drawn x 2] (flagged population, sample), seed [1 x 1]
 void put_draws(gauss_table& t, const SimDraws& d)
 {
-    put_named(t, "counts", (int)d.counts.size(), 1, std::vector<double>(d.counts.begin(), d.counts.end()));
+    t.put_named("counts", (int)d.counts.size(), 1, std::vector<double>(d.counts.begin(), d.counts.end()));
     const size_t n = d.pop.size();
     std::vector<double> dr(2 * n);
     for (size_t k = 0; k < n; k++) { dr[k] = d.pop[k]; dr[n + k] = d.sample[k]; }
-    put_named(t, "draws", (int)n, 2, std::move(dr));
-    put_named(t, "seed", 1, 1, std::vector<double>(1, (double)d.seed));
+    t.put_named("draws", (int)n, 2, std::move(dr));
+    t.put_named("seed", 1, 1, std::vector<double>(1, (double)d.seed));
 }
 
 }  // namespace

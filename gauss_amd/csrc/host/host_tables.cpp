@@ -194,72 +194,60 @@ GeneResult jepeg_tail(const std::vector<Snp*>& gs, const double* CorG, const Arg
 // ------------------------------------------------------------------------------------------
 // outputs
 // ------------------------------------------------------------------------------------------
+// the SNPs of the prediction window, snp_vec order: what dist / qcat list (dist.cpp:92, qcat.cpp:95)
+static std::vector<Snp*> window_rows(const gauss_prepared& p)
+{
+    std::vector<Snp*> rows;
+    for (Snp* s : p.snp_vec) { const int ibp = (int)s->bp; if (ibp >= p.args.start_bp && ibp <= p.args.end_bp) rows.push_back(s); }
+    return rows;
+}
+
+// (columns are filled in place, reserved to the row count: a chromosome's tables are 92 000 rows)
 gauss_table* dist_output(gauss_prepared& p)     // dist.cpp:91-124 / distmix.cpp:100-133
 {
-    const Args& a = p.args;
     const bool mix = p.kind == GAUSS_KIND_DISTMIX;
     gauss_table* t = new gauss_table();
-    Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chr{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
-    Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}};
-    Column af{mix ? "af1mix" : "af1ref", GAUSS_COL_DBL, {}, {}, {}}, z{"z", GAUSS_COL_DBL, {}, {}, {}};
-    Column pval{"pval", GAUSS_COL_DBL, {}, {}, {}}, info{"info", GAUSS_COL_DBL, {}, {}, {}}, type{"type", GAUSS_COL_INT, {}, {}, {}};
-    size_t n_out = 0;
-    for (Snp* s : p.snp_vec) { const int ibp = (int)s->bp; n_out += (ibp >= a.start_bp && ibp <= a.end_bp) ? 1 : 0; }
-    for (Column* c : {&rsid, &a1, &a2}) c->s.reserve(n_out);
-    for (Column* c : {&chr, &bp, &type}) c->i.reserve(n_out);
-    for (Column* c : {&af, &z, &pval, &info}) c->d.reserve(n_out);
-    for (Snp* s : p.snp_vec) {
-        const int ibp = (int)s->bp;                               // dist.cpp:92
-        if (ibp >= a.start_bp && ibp <= a.end_bp) {
-            rsid.s.push_back(s->rsid); chr.i.push_back(s->chr); bp.i.push_back(ibp);
-            a1.s.push_back(s->a1); a2.s.push_back(s->a2);
-            af.d.push_back(mix ? s->af1mix : s->af1ref);
-            z.d.push_back(s->z);
-            pval.d.push_back(2 * pnorm_upper(fabs(s->z)));        // dist.cpp:101
-            info.d.push_back(s->info); type.i.push_back(s->type);
-        }
+    const std::vector<Snp*> rows = window_rows(p);
+    add_ident_columns(*t, rows);
+    Column &af = t->add(mix ? "af1mix" : "af1ref", GAUSS_COL_DBL), &z = t->add("z", GAUSS_COL_DBL), &pval = t->add("pval", GAUSS_COL_DBL);
+    Column &info = t->add("info", GAUSS_COL_DBL), &type = t->add("type", GAUSS_COL_INT);
+    for (Column* c : {&af, &z, &pval, &info}) c->d.reserve(rows.size());
+    type.i.reserve(rows.size());
+    for (Snp* s : rows) {
+        af.d.push_back(mix ? s->af1mix : s->af1ref);
+        z.d.push_back(s->z);
+        pval.d.push_back(2 * pnorm_upper(fabs(s->z)));            // dist.cpp:101
+        info.d.push_back(s->info); type.i.push_back(s->type);
     }
-    t->cols.reserve(10);                                          // (moved, not copied: a chromosome's tables are 92 000 rows)
-    for (Column* c : {&rsid, &chr, &bp, &a1, &a2, &af, &z, &pval, &info, &type}) t->cols.push_back(std::move(*c));
     return t;
 }
 
 gauss_table* qcat_output(gauss_prepared& p)     // qcat.cpp:94-131 / qcatmix.cpp:102-139
 {
-    const Args& a = p.args;
     const bool mix = p.kind == GAUSS_KIND_QCATMIX;
     gauss_table* t = new gauss_table();
-    Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chr{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
-    Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}};
-    Column af{mix ? "af1mix" : "af1ref", GAUSS_COL_DBL, {}, {}, {}}, z{"z", GAUSS_COL_DBL, {}, {}, {}};
-    Column qm{"qcat_m", GAUSS_COL_INT, {}, {}, {}}, qt{"qcat_t", GAUSS_COL_DBL, {}, {}, {}};
-    Column qc{"qcat_chisq", GAUSS_COL_DBL, {}, {}, {}}, qp{"qcat_pval", GAUSS_COL_DBL, {}, {}, {}};
-    Column type{"type", GAUSS_COL_INT, {}, {}, {}};
-    for (Snp* s : p.snp_vec) {
-        const int ibp = (int)s->bp;                               // qcat.cpp:95
-        if (ibp >= a.start_bp && ibp <= a.end_bp) {
-            rsid.s.push_back(s->rsid); chr.i.push_back(s->chr); bp.i.push_back(ibp);
-            a1.s.push_back(s->a1); a2.s.push_back(s->a2);
-            af.d.push_back(mix ? s->af1mix : s->af1ref);
-            z.d.push_back(s->z);
-            qm.i.push_back(s->qcat_m); qt.d.push_back(s->qcat_t); qc.d.push_back(s->qcat_chisq);
-            qp.d.push_back(pchisq_upper(s->qcat_chisq, 1));       // qcat.cpp:107
-            type.i.push_back(s->type);
-        }
+    const std::vector<Snp*> rows = window_rows(p);
+    add_ident_columns(*t, rows);
+    Column &af = t->add(mix ? "af1mix" : "af1ref", GAUSS_COL_DBL), &z = t->add("z", GAUSS_COL_DBL), &qm = t->add("qcat_m", GAUSS_COL_INT);
+    Column &qt = t->add("qcat_t", GAUSS_COL_DBL), &qc = t->add("qcat_chisq", GAUSS_COL_DBL), &qp = t->add("qcat_pval", GAUSS_COL_DBL);
+    Column& type = t->add("type", GAUSS_COL_INT);
+    for (Snp* s : rows) {
+        af.d.push_back(mix ? s->af1mix : s->af1ref);
+        z.d.push_back(s->z);
+        qm.i.push_back(s->qcat_m); qt.d.push_back(s->qcat_t); qc.d.push_back(s->qcat_chisq);
+        qp.d.push_back(pchisq_upper(s->qcat_chisq, 1));           // qcat.cpp:107
+        type.i.push_back(s->type);
     }
-    t->cols.reserve(12);
-    for (Column* c : {&rsid, &chr, &bp, &a1, &a2, &af, &z, &qm, &qt, &qc, &qp, &type}) t->cols.push_back(std::move(*c));
     return t;
 }
 
-static void add_named(gauss_table* t, const char* name, int nrow, int ncol, const double* row_major)
+// a named matrix from ROW-major data (the window outputs' layout), transposed into NamedMat's column-major one
+static void put_named_rowmajor(gauss_table* t, const char* name, int nrow, int ncol, const double* row_major)
 {
-    NamedMat m;
-    m.name = name; m.nrow = nrow; m.ncol = ncol;
-    m.d.resize((size_t)nrow * ncol);
+    std::vector<double> d((size_t)nrow * ncol);
     for (int r = 0; r < nrow; r++)
-        for (int c = 0; c < ncol; c++) m.d[(size_t)c * nrow + r] = row_major[(size_t)r * ncol + c];
-    t->named.push_back(std::move(m));
+        for (int c = 0; c < ncol; c++) d[(size_t)c * nrow + r] = row_major[(size_t)r * ncol + c];
+    t->put_named(name, nrow, ncol, std::move(d));
 }
 
 gauss_table* prep_output(gauss_prepared& p)     // prep_qcat.cpp:135-204 / prep_qcatmix.cpp:262-315
@@ -267,27 +255,22 @@ gauss_table* prep_output(gauss_prepared& p)     // prep_qcat.cpp:135-204 / prep_
     const bool rec = p.kind == GAUSS_KIND_PREP_RECESSIVE;
     const int M = (int)p.measured.size(), U = (int)p.unmeasured.size();
     gauss_table* t = new gauss_table();
-    Column rsid{"rsid", GAUSS_COL_STR, {}, {}, {}}, chr{"chr", GAUSS_COL_INT, {}, {}, {}}, bp{"bp", GAUSS_COL_INT, {}, {}, {}};
-    Column a1{"a1", GAUSS_COL_STR, {}, {}, {}}, a2{"a2", GAUSS_COL_STR, {}, {}, {}};
-    Column af{rec ? "af1mix" : "af1ref", GAUSS_COL_DBL, {}, {}, {}}, z{"z", GAUSS_COL_DBL, {}, {}, {}};
-    Column type{"type", GAUSS_COL_INT, {}, {}, {}};
     // prep_qcat lists the whole extended window (prep_qcat.cpp:146-155), prep_recessive_impute only the
     // prediction window (prep_qcatmix.cpp:267-276)
     const std::vector<Snp*>& rows = rec ? p.unmeasured : p.snp_vec;
+    add_ident_columns(*t, rows);
+    Column &af = t->add(rec ? "af1mix" : "af1ref", GAUSS_COL_DBL), &z = t->add("z", GAUSS_COL_DBL), &type = t->add("type", GAUSS_COL_INT);
     for (Snp* s : rows) {
-        rsid.s.push_back(s->rsid); chr.i.push_back(s->chr); bp.i.push_back((int)s->bp);
-        a1.s.push_back(s->a1); a2.s.push_back(s->a2);
         af.d.push_back(rec ? s->af1mix : s->af1ref);
         z.d.push_back(s->z); type.i.push_back(s->type);
     }
-    t->cols = {rsid, chr, bp, a1, a2, af, z, type};
-    add_named(t, rec ? "zvec" : "z_vec", M, 1, p.z1.data());
-    add_named(t, rec ? "cormat" : "cor_mat1", M, M, p.out_b11.data());
-    if (!rec) add_named(t, "cor_mat2", U, M, p.out_b21.data());
+    put_named_rowmajor(t, rec ? "zvec" : "z_vec", M, 1, p.z1.data());
+    put_named_rowmajor(t, rec ? "cormat" : "cor_mat1", M, M, p.out_b11.data());
+    if (!rec) put_named_rowmajor(t, "cor_mat2", U, M, p.out_b21.data());
     else {
-        add_named(t, "cormat_add", U, M, p.out_b21.data());
-        add_named(t, "cormat_dom", U, M, p.out_b21.data() + (size_t)U * M);
-        add_named(t, "cormat_rec", U, M, p.out_b21.data() + (size_t)2 * U * M);
+        put_named_rowmajor(t, "cormat_add", U, M, p.out_b21.data());
+        put_named_rowmajor(t, "cormat_dom", U, M, p.out_b21.data() + (size_t)U * M);
+        put_named_rowmajor(t, "cormat_rec", U, M, p.out_b21.data() + (size_t)2 * U * M);
     }
     return t;
 }

@@ -10,13 +10,6 @@
 
 namespace {
 
-void put_named(gauss_table& t, const char* name, int nrow, int ncol, std::vector<double> d)
-{
-    NamedMat nm;
-    nm.name = name; nm.nrow = nrow; nm.ncol = ncol; nm.d = std::move(d);
-    t.named.push_back(std::move(nm));
-}
-
 // Goldfarb & Idnani (1983), "A numerically stable dual method for solving strictly convex quadratic programs", as quadprog's
 // qpgen2 implements it: min 1/2 x^T D x - d^T x subject to N^T x >= b, the first meq constraints equalities.  The dense
 // constraint matrix N is n x m, column-major.  J = L^-T Q and the upper-triangular R with J^T N_A = [R; 0] are kept and updated
@@ -260,21 +253,19 @@ int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* referenc
 {
     if (!ctx || !out) return herr("bad arguments");
     *out = nullptr;
-    if (!input_file || !reference_index_file || !reference_data_file || !reference_pop_desc_file) return herr("file name is NULL");
+    if (files_ok({input_file, reference_index_file, reference_data_file, reference_pop_desc_file})) return -1;
     if (level != GAUSS_ZMIX_POPULATION && level != GAUSS_ZMIX_SUPERPOPULATION)
         return herr("zmix: level %d is neither GAUSS_ZMIX_POPULATION nor GAUSS_ZMIX_SUPERPOPULATION", level);
     const bool sup = level == GAUSS_ZMIX_SUPERPOPULATION;
     const double pct = std::isnan(percentile) ? 0.9 : percentile;              // zmix.R's defaults, not prep_zmix5's
     const int step = interval > 0 ? interval : 10;
-    Args a;
-    SnpMap m;
-    std::vector<Snp*> measured;
-    if (zmix_read(a, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, m, measured)) return -1;
+    ZmixStudy st;
+    if (zmix_read(st, input_file, reference_index_file, reference_data_file, reference_pop_desc_file)) return -1;
+    Args& a = st.a;
     std::vector<int> kept;
     std::vector<double> kept_nv;
-    if (zmix_ai_select(a, measured, step, pct, kept, kept_nv)) return -1;
     std::vector<Snp*> sel;
-    for (int i : kept) sel.push_back(measured[(size_t)i]);
+    if (zmix_ai_select(st, step, pct, kept, kept_nv, &sel)) return -1;
     const int S = (int)sel.size(), P = a.num_pops;
     std::vector<int32_t> pop_group;
     std::vector<std::string> group_names;
@@ -282,8 +273,7 @@ int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* referenc
     if (G > 64) return herr("zmix: %d %s; the normal equations hold 1 .. 64", G, sup ? "super-populations" : "populations");
     if (S < 2) return herr("zmix: no valid rows after filtering.");            // no pairs at all
     int N = 0;
-    std::vector<int32_t> pop_off(1, 0);
-    for (int k = 0; k < P; k++) { N += a.ref_pop_size_vec[(size_t)k]; pop_off.push_back(pop_off.back() + a.ref_pop_size_vec[(size_t)k]); }
+    const std::vector<int32_t> pop_off = panel_pop_off(a, &N);
     int64_t ld = 0;
     std::vector<uint8_t> geno;
     if (zmix_genotypes(a, sel, N, &ld, geno)) return -1;
@@ -316,13 +306,13 @@ int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* referenc
         t->add("SuperPopulation", GAUSS_COL_STR).s = sups;
     }
     t->add("Weight", GAUSS_COL_DBL).d = w;
-    put_named(*t, "dmat", G, G, xtx);                    // symmetric: row- and column-major agree
-    put_named(*t, "dvec", G, 1, xty);
-    put_named(*t, "w_unrounded", G, 1, w_unr);
-    put_named(*t, "n_snp", 1, 1, {(double)S});
-    put_named(*t, "n_pairs", 1, 1, {(double)S * (double)(S - 1) / 2});
-    put_named(*t, "n_rows", 1, 1, {(double)n_rows});
-    put_named(*t, "yty", 1, 1, {yty});
+    t->put_named("dmat", G, G, xtx);                    // symmetric: row- and column-major agree
+    t->put_named("dvec", G, 1, xty);
+    t->put_named("w_unrounded", G, 1, w_unr);
+    t->put_named("n_snp", 1, 1, {(double)S});
+    t->put_named("n_pairs", 1, 1, {(double)S * (double)(S - 1) / 2});
+    t->put_named("n_rows", 1, 1, {(double)n_rows});
+    t->put_named("yty", 1, 1, {yty});
     *out = t.release();
     return 0;
 }
