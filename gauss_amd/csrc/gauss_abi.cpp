@@ -137,6 +137,8 @@ int gauss_job_stats(gauss_job* job, double* out4)
                 k_main += (double)((live + gran - 1) / gran * gran);
             }
         }
+        // packed items (k_gram.hip: two A rows per lane): a wave with any live A half issues one MFMA per live B half (or B group of 16)
+        const bool packed = job->gram_packed && p.slab16;
         int pairs = 0;
         for (int pr = 0; pr < p.npair; pr++) {
             const int ti = pl.pair_ti[pr], tj = pl.pair_tj[pr];
@@ -146,14 +148,15 @@ int gauss_job_stats(gauss_job* job, double* out4)
             for (int wr = 0; wr < 2; wr++)
                 for (int wc = 0; wc < 2; wc++) {
                     if (ti == tj && wr == 1 && wc == 0) continue;
-                    const int na = halves(rows(ti), wr);
+                    int na = halves(rows(ti), wr);
+                    if (packed && na > 1) na = 1;
                     // f32 path: a wave whose last live 32-column half holds at most 16 live columns multiplies 16-column groups
                     // (k_gram.hip, chunk_mfma_edge): 1 or 3 of them
                     int nb16 = (rows(tj) - wc * 64 + 15) / 16;
                     nb16 = nb16 < 0 ? 0 : (nb16 > 4 ? 4 : nb16);
                     if (edge16 && !job->gram_i8 && na > 0 && (nb16 & 1)) { tiles_edge += na * nb16 * 0.5; continue; }
                     double t32 = na * halves(rows(tj), wc);
-                    if (ti == tj && wr == wc && t32 == 4) t32 = 3;      // mirrored 32 x 32 sub-block of a diagonal quadrant
+                    if (ti == tj && wr == wc && t32 == 4) t32 = 3;      // mirrored 32 x 32 sub-block of a diagonal quadrant (not skipped when packed: t32 = 2)
                     tiles32 += t32;
                 }
             flops += 32.0 * 32.0 * 2.0 * (tiles32 * k_main + tiles_edge * p.Kp);

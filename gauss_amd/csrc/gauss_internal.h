@@ -142,7 +142,8 @@ struct Item {
     int k0;                  // first column of the run
     int nseg;                // segments in the run
     int rows_a, rows_b;      // live rows of the two tiles (the rest is zero padding)
-    int flags;               // bit 0: ti == tj (diagonal tile); bit 1: slabs are uint16 pairs (Prob::slab16); bit 4: a B11 item of a
+    int flags;               // bit 0: ti == tj (diagonal tile); bit 1: slabs are uint16 pairs (Prob::slab16); bit 2 (f32 path, only with bit 1: codes <= 3): the
+                             // kernel packs two A rows per lane (k_gram.hip: chunk_mfma_packed); bit 4: a B11 item of a
                              // job built for a merged launch: counts itself off in the launch's `b11_done[0]` when one is passed
                              // (k_gram.hip); bit 5: a B21 item of an "early" window, counted in `b11_done[8]`
 };

@@ -164,6 +164,7 @@ struct gauss_ctx {
     hipStream_t upload = nullptr;            // asynchronous row-store uploads (gauss_store_upload_async)
     std::map<const void*, std::shared_ptr<StoreUpload>> uploads;      // by device pointer (guarded by mu); shared: a waiter keeps its entry alive
     int gram_i8 = 0;
+    int gram_packed = 1;                     // f32 Gram items with 16-bit slabs pack two A rows per lane (k_gram.hip); GAUSS_GRAM_PACKED=0: off
     std::map<const void*, size_t> stores;    // row stores made by gauss_store_upload: base pointer -> bytes
     std::mutex mu;
     BlockCache dev_cache, pin_cache;
@@ -204,6 +205,10 @@ void ctx_pin_release(gauss_ctx* c, void* p);
 // Diagnostics on stderr: GAUSS_TRACE=job,upload,stream (any subset; "all")
 bool trace_on(const char* what);
 
+// A packed f32 Gram item's time per sample over an unpacked one's (k_gram.hip: half the MFMAs, plus the A-side combine and the
+// sub-flushes).  The K-loop model says 0.54-0.57 plus ~3 % of sub-flushes; measured on the 36-window job: Gram launch
+// 36.39 -> 20.37 ms = 0.56.  The planner's estimates rest on it (gauss_plan.cpp: t_b21, wait_bound_us).
+constexpr double GRAM_PACKED_COST = 0.58;
 static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Plan thresholds (measured on MI355X).  Both sides of each are ordinary production forms that a job
@@ -319,6 +324,7 @@ struct gauss_job {
     std::vector<hipEvent_t> sevp;                          // "group g's rows are packed, their tables made" (aux stream)
     int max_pop = 1;
     int gram_i8 = 0;
+    int gram_packed = 0;                                   // 1: the items of windows with 16-bit slabs carry Item::flags bit 2
     int resample_lds = -1;                                 // >= 0: the window is resampled (k_simld.hip) and its pack stage is
                                                            // resample_pack with this much dynamic LDS
     int* d_status = nullptr;                               // [n][4] + 4 job-wide ints

@@ -319,6 +319,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n = (int)specs.size();
     job->on_device = on_device;
     job->gram_i8 = ctx->gram_i8;
+    job->gram_packed = (ctx->gram_packed && !ctx->gram_i8) ? 1 : 0;
     job->plans.resize(job->n);
     for (const WinSpec& w : specs)
         if (w.draw_pop && (specs.size() != 1 || streamed)) return fail(GAUSS_E_INVALID, "a resampled window is a job of its own");
@@ -604,9 +605,11 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             if (job->gram_i8) continue;          // (the int8 kernel is bound by operand delivery: it keeps items of one K range together -- 5.40 against 5.53 ms)
             const Plan& pl = plan_of(h.prob);
             const int ra = live_rows(pl, pl.pair_ti[h.pair]), rb = live_rows(pl, pl.pair_tj[h.pair]);
+            // (packed items, k_gram.hip: a wave with any live A half issues one MFMA per live B half -- 2 at most, half a full unpacked wave)
+            const bool packed = job->gram_packed && pl.p.slab16;
             int mx = 0;
             for (int wr = 0; wr < 2; wr++)
-                for (int wc = 0; wc < 2; wc++) mx = std::max(mx, halves(ra, wr) * halves(rb, wc));
+                for (int wc = 0; wc < 2; wc++) mx = std::max(mx, (packed ? std::min(halves(ra, wr), 1) : halves(ra, wr)) * halves(rb, wc));
             h.ord = std::max(KC, (h.len * std::max(mx, 1) / 4 + KC - 1) / KC * KC);
         }
     }
@@ -644,13 +647,16 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         const int mode = env_int("GAUSS_CHAIN_ASIDE", 1);
         bool genes = false;
         double b21_len = 0.0;
-        for (const ItemH& h : items) if (!is_b11(h)) b21_len += (double)h.len;
+        // an item's K length in the time units of the unpacked f32 kernel (the 120e12 below): a packed item (k_gram.hip) issues half
+        // the MFMAs and pays the A-side combine and the sub-flushes on top -- GRAM_PACKED_COST of the unpacked time per sample
+        auto cost_len = [&](const ItemH& h) { return (double)h.len * ((job->gram_packed && plan_of(h.prob).p.slab16) ? GRAM_PACKED_COST : 1.0); };
+        for (const ItemH& h : items) if (!is_b11(h)) b21_len += cost_len(h);
         for (int i = 0; i < job->n; i++) genes = genes || job->plans[i].p.n_gene > 0;
         // (the int8 Gram kernel is ~8 x faster: an 8-rank share's B21 launch, 0.5 ms, no longer covers its chain)
         const double t_b21 = b21_len * 2.0 * TILE * TILE / (job->gram_i8 ? 960e12 : 120e12), t_chain = 0.5e-3 + 100e-6 * job->max_nblk;
         {
             double all_len = 0.0;
-            for (const ItemH& h : items) all_len += (double)h.len;
+            for (const ItemH& h : items) all_len += cost_len(h);
             job->wait_bound_us = 50.0 * 1e6 * all_len * 2.0 * TILE * TILE / (job->gram_i8 ? 960e12 : 120e12);      // a whole-genome job must not trip a fixed bound
         }
         job->chain_aside = !streamed && mode != 0 && !panelmap.empty() && !tilemap_b21.empty() && !genes && job->ctx->chain &&
@@ -1077,7 +1083,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         it.seg_k1 = p.seg_k1 + gr.first;
         it.chunk_live = (const uint32_t*)(job->d_tab + to[h.prob].ch);
         it.Kp = p.Kp; it.k0 = pl.seg_k0[gr.first]; it.nseg = gr.second - gr.first;
-        it.rows_a = rows(ti); it.rows_b = rows(tj); it.flags = (ti == tj ? 1 : 0) | (p.slab16 ? 2 : 0);
+        it.rows_a = rows(ti); it.rows_b = rows(tj); it.flags = (ti == tj ? 1 : 0) | (p.slab16 ? 2 : 0) | (p.slab16 && job->gram_packed ? 4 : 0);
         if (job->merged && (int)n < job->n_items_b11) it.flags |= 16;         // counts itself off in b11_done[0]
         else if (job->merged && (int)n < job->n_items_b11 + job->n_items_b21_early) it.flags |= 32;      // ... in b11_done[8] (the early windows' B21 items)
         memcpy(blob.data() + o_items + sizeof(Item) * n, &it, sizeof(Item));

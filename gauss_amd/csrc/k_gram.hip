@@ -92,6 +92,80 @@ __device__ __forceinline__ void chunk_mfma(const uint8_t* __restrict__ la, const
 #undef GAUSS_MFMA_PAIR
 }
 
+// ---- two A rows per lane (f32 path, items with Item::flags bit 2: 16-bit slabs, codes <= 3) ---------------------------
+// The A operand of one MFMA is  a_r + 4096 a_r'  for the lane's two rows r = wr * 64 + li and r' = r + 32, so accumulator
+// register (row r, column c) carries  S_rc + 4096 S_r'c : ONE 32 x 32 MFMA yields a 64 x 32 block of sums and a wave issues
+// NB of them per K step instead of NA x NB.  Exact while both sums stay below 4096 (the whole is then an integer below
+// 2^24 and every partial sum of the fmaf chain is one too): a product of two codes is at most PK_CODE_MAX^2 = 9, a chunk
+// adds KC of them, so the accumulators are split into the running sums (sub_flush below) every PK_F = 7 chunks = 448
+// samples at the latest: 9 * 448 = 4032.
+constexpr int PK_SHIFT = 12;                                        // row r' rides 2^12 above row r
+constexpr int PK_CODE_MAX = 3;                                      // 2-bit sources (gauss_plan.cpp: Prob::slab16)
+constexpr int PK_F = ((1 << PK_SHIFT) - 1) / (PK_CODE_MAX * PK_CODE_MAX * KC);      // chunks between two sub-flushes
+static_assert(PK_F == 7 && PK_CODE_MAX * PK_CODE_MAX * KC * PK_F < (1 << PK_SHIFT), "a row's sum between two sub-flushes must stay below 2^PK_SHIFT");
+static_assert(2 * PK_SHIFT <= 24, "both rows' sums together must stay an exact f32 integer");
+
+// fa0 + 2^PK_SHIFT fa1: one plain v_fma_f32 per element.  Written as C, not as inline asm: the compiler must see the consumer
+// of a v_cvt_pk_f32_fp8 to place the wait state that conversion's result needs (an asm statement is opaque to its hazard
+// pass).  (A packed v_pk_fma_f32 beside MFMAs would cost more than two plain ones; the ISA is checked for it.)
+__device__ __forceinline__ float pk_combine(float fa0, float fa1) { return __builtin_fmaf(fa1, (float)(1 << PK_SHIFT), fa0); }
+
+// chunk_mfma with packed A rows: two independent accumulators (columns 0..31 and 32..63 of the wave's block), each holding
+// rows r and r + 32.  NA = 1: the wave's second 32 rows are padding, the A operand is the first rows' alone.
+template <int NA, int NB>
+__device__ __forceinline__ void chunk_mfma_packed(const uint8_t* __restrict__ la, const uint8_t* __restrict__ lb,
+                                                  const int (&aoff)[2], const int (&boff)[2], f32x16& acc0, f32x16& acc1, int nl)
+{
+#define GAUSS_MFMA_PAIR(AW0, AW1, BW0, BW1, HI)                                                       \
+    {                                                                                                  \
+        f32x2 fa = __builtin_amdgcn_cvt_pk_f32_fp8((int)(AW0), HI);                                    \
+        const f32x2 fb0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)(BW0), HI);                             \
+        f32x2 fb1 = fb0;                                                                               \
+        if (NA > 1) {                                                                                  \
+            const f32x2 fa1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)(AW1), HI);                         \
+            fa[0] = pk_combine(fa[0], fa1[0]);                                                         \
+            fa[1] = pk_combine(fa[1], fa1[1]);                                                         \
+        }                                                                                              \
+        if (NB > 1) fb1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)(BW1), HI);                             \
+        _Pragma("unroll") for (int e = 0; e < 2; e++) {                                              \
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb0[e], acc0, 0, 0, 0);                 \
+            if (NB > 1) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb1[e], acc1, 0, 0, 0);     \
+        }                                                                                              \
+    }
+#pragma unroll
+    for (int g = 0; g < 2; g++) {
+        if (4 * g >= nl) break;            // (dead units: as in chunk_mfma)
+        const u32x4 a0 = *reinterpret_cast<const u32x4*>(la + aoff[g]);
+        const u32x4 b0 = *reinterpret_cast<const u32x4*>(lb + boff[g]);
+        u32x4 a1 = a0, b1 = b0;
+        if (NA > 1) a1 = *reinterpret_cast<const u32x4*>(la + aoff[g] + 32 * LROW);
+        if (NB > 1) b1 = *reinterpret_cast<const u32x4*>(lb + boff[g] + 32 * LROW);
+        const uint32_t aw0[4] = {a0.x, a0.y, a0.z, a0.w};
+        const uint32_t aw1[4] = {a1.x, a1.y, a1.z, a1.w};
+        const uint32_t bw0[4] = {b0.x, b0.y, b0.z, b0.w};
+        const uint32_t bw1[4] = {b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (4 * g + q >= nl) break;
+            GAUSS_MFMA_PAIR(aw0[q], aw1[q], bw0[q], bw1[q], false)
+            GAUSS_MFMA_PAIR(aw0[q], aw1[q], bw0[q], bw1[q], true)
+        }
+    }
+#undef GAUSS_MFMA_PAIR
+}
+
+// Sub-flush: accumulator value  S_r + 4096 S_r'  leaves for the running register, which holds the two rows' sums of the
+// SEGMENT as 16-bit halves (a 16-bit-slab segment sums to at most 9 * 7168 < 2^16: gauss_plan.cpp), and starts again at zero.
+__device__ __forceinline__ uint32_t pk_sub_flush(float acc, uint32_t run)
+{
+    // low + 2^16 high = u + (2^16 - 2^PK_SHIFT) high: a shift, a 24-bit multiply-add and an add
+    const uint32_t u = (uint32_t)acc;
+    return run + (u + __umul24(u >> PK_SHIFT, (1u << 16) - (1u << PK_SHIFT)));
+}
+// the running registers of rows (2k, 2k + 32) and (2k + 1, 2k + 33) as the slab's dwords (2k, 2k + 1) and (2k + 32, 2k + 33)
+__device__ __forceinline__ float pk_slab_lo(uint32_t even, uint32_t odd) { return __uint_as_float(__builtin_amdgcn_perm(odd, even, 0x05040100u)); }
+__device__ __forceinline__ float pk_slab_hi(uint32_t even, uint32_t odd) { return __uint_as_float(__builtin_amdgcn_perm(odd, even, 0x07060302u)); }
+
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -194,6 +268,72 @@ __device__ __forceinline__ void flush_edge(OUT out, bool slab16, int erow0, int 
         }
 }
 
+// chunk_mfma_edge with packed A rows: A group ga (16 rows) carries group ga + 2 (the rows 32 further on) 2^PK_SHIFT above it,
+// 2 NC accumulators instead of 4 NC.  (An unpacked edge wave would hold its workgroup, which meets at a barrier every chunk,
+// at the unpacked pace.)
+template <int NA, int NC>
+__device__ __forceinline__ void chunk_mfma_edge_packed(const uint8_t* __restrict__ la, const uint8_t* __restrict__ lb, int eoffa,
+                                                       int eoffb, f32x4 (&acce)[2][NC])
+{
+    uint32_t b[NC][4];
+#pragma unroll
+    for (int nc = 0; nc < NC; nc++) {
+        const u32x4 bw = *reinterpret_cast<const u32x4*>(lb + eoffb + nc * 16 * LROW);
+        b[nc][0] = bw.x; b[nc][1] = bw.y; b[nc][2] = bw.z; b[nc][3] = bw.w;
+    }
+#pragma unroll
+    for (int ga = 0; ga < 2; ga++) {
+        const u32x4 aw = *reinterpret_cast<const u32x4*>(la + eoffa + ga * 16 * LROW);
+        u32x4 aw2 = aw;
+        if (NA > 1) aw2 = *reinterpret_cast<const u32x4*>(la + eoffa + (ga * 16 + 32) * LROW);
+        const uint32_t a[4] = {aw.x, aw.y, aw.z, aw.w};
+        const uint32_t a2[4] = {aw2.x, aw2.y, aw2.z, aw2.w};
+        if (NC > 1) {
+            // (as in chunk_mfma_edge: keeps the B conversions of one A group from staying alive for the next)
+#pragma unroll
+            for (int nc = 0; nc < NC; nc++) asm volatile("" : "+v"(b[nc][0]), "+v"(b[nc][1]), "+v"(b[nc][2]), "+v"(b[nc][3]));
+        }
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+#pragma unroll
+            for (int hi = 0; hi < 2; hi++) {
+                f32x2 fa = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)a[w], true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)a[w], false);
+                if (NA > 1) {
+                    const f32x2 fa2 = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)a2[w], true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)a2[w], false);
+                    fa[0] = pk_combine(fa[0], fa2[0]);
+                    fa[1] = pk_combine(fa[1], fa2[1]);
+                }
+#pragma unroll
+                for (int nc = 0; nc < NC; nc++) {
+                    const f32x2 fb = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)b[nc][w], true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)b[nc][w], false);
+#pragma unroll
+                    for (int e = 0; e < 2; e++) acce[ga][nc] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[e], fb[e], acce[ga][nc], 0, 0, 0);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+// the packed edge routine's running registers of a segment to its 16-bit slab: register reg of (ga, nc) holds rows
+// erow0 + 16 ga + reg and that + 32 of column ecol0 + 16 nc
+template <int NA, int NC, typename OUT>
+__device__ __forceinline__ void flush_edge_packed(OUT out, int erow0, int ecol0, const uint32_t (&rune)[2][NC][4])
+{
+#pragma unroll
+    for (int ga = 0; ga < 2; ga++)
+#pragma unroll
+        for (int nc = 0; nc < NC; nc++) {
+            const int o = ((erow0 + 16 * ga) >> 1) * TILE + ecol0 + 16 * nc;
+            out[o] = pk_slab_lo(rune[ga][nc][0], rune[ga][nc][1]);
+            out[o + TILE] = pk_slab_lo(rune[ga][nc][2], rune[ga][nc][3]);
+            if (NA > 1) {
+                out[o + 16 * TILE] = pk_slab_hi(rune[ga][nc][0], rune[ga][nc][1]);
+                out[o + 17 * TILE] = pk_slab_hi(rune[ga][nc][2], rune[ga][nc][3]);
+            }
+        }
+}
+
 // One work item for a wave with NA x NB live 32-row halves (NA = 0: staging and barriers only).
 // The K loop runs over the whole run of segments without draining the prefetch pipeline; at each
 // segment end the accumulators are flushed to that segment's slab and cleared.
@@ -216,7 +356,9 @@ __device__ __forceinline__ void wait_dma_barrier_dyn(int groups_newer)
 
 // NC > 0 (f32 only, then NB = 0): the wave's live B rows are NC groups of 16 with the last one at most half a 32-row half --
 // 1 or 3 groups -- and all of them go through chunk_mfma_edge.
-template <int NA, int NB, typename ACC, int NS, bool SK10 = false, int NC = 0>
+// PK (f32 only, items with 16-bit slabs): two A rows per lane (chunk_mfma_packed / chunk_mfma_edge_packed): half the accumulators,
+// the other half of the registers holds the segment's running sums.
+template <int NA, int NB, typename ACC, int NS, bool SK10 = false, int NC = 0, bool PK = false>
 __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, int wc)
 {
     const int Kp = it.Kp;
@@ -240,7 +382,12 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
     typedef __attribute__((address_space(3))) uint8_t* lds_ptr;
     typedef __attribute__((address_space(1))) const uint8_t* glb_ptr;
 
-    ACC acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
+    ACC acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};           // (PK: acc00 / acc01 are the two packed accumulators)
+    uint32_t run0[16], run1[16];                                      // PK: the segment's sums, rows r / r + 32 in the low / high half
+    if (PK) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) { run0[r] = 0; run1[r] = 0; }
+    }
 
     const int k0 = it.k0;
     const int nseg = it.nseg;
@@ -282,14 +429,20 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
 
     // 16-column edge: fragment offsets in the (row lane % 16, piece lane / 16) layout, and where its results go
     constexpr bool BE = NC > 0;
-    f32x4 acce[4][BE ? NC : 1];
+    constexpr int NCE = BE ? NC : 1, NGE = PK ? 2 : 4;                // edge accumulators: NGE groups of 16 A rows x NCE groups of 16 columns
+    f32x4 acce[NGE][NCE];
+    uint32_t rune[2][NCE][4];                                         // PK: their running sums
     int eoffa = 0, eoffb = 0, erow0 = 0, ecol0 = 0;
     if (BE) {
         const int r16 = lane & 15, q16 = lane >> 4, sw16 = (r16 >> 2) & 3;
 #pragma unroll
-        for (int ga = 0; ga < 4; ga++)
+        for (int ga = 0; ga < NGE; ga++)
 #pragma unroll
-            for (int nc = 0; nc < (BE ? NC : 1); nc++) acce[ga][nc] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int nc = 0; nc < NCE; nc++) {
+                acce[ga][nc] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int r = 0; r < 4; r++) if (PK) rune[ga & 1][nc][r] = 0;
+            }
         eoffa = (wr * 64 + r16) * LROW + 16 * (q16 ^ sw16);
         eoffb = (wc * 64 + r16) * LROW + 16 * (q16 ^ sw16);
         erow0 = wr * 64 + 4 * q16;
@@ -301,6 +454,7 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
     int nl_next = chunk_live_units(lbits, k0 >> 6);
     for (int seg = 0; seg < nseg; seg++) {
         const int kend = uniform_load<int>(seg_k1, seg);
+        int since = 0;                                                // PK: chunks since the last sub-flush
         for (; k < kend; k += KC) {
             // the image consumed in the previous iteration is free: request the chunk NS - 1 ahead into it
             // (the prefetch runs across segment ends)
@@ -319,8 +473,32 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
                 if ((c1 & 7) == 0) lbits = uniform_load<uint32_t>(live_tab, c1 >> 3);        // scalar load, once per 8 chunks
                 nl_next = chunk_live_units(lbits, c1);
             }
-            if (NA > 0 && NB > 0) chunk_mfma<NA, (NB > 0 ? NB : 1), SK10>(la, lb, aoff, boff, acc00, acc01, acc10, acc11, nl);
-            if (BE) chunk_mfma_edge<(NA > 0 ? NA : 1), (BE ? NC : 1)>(la, lb, eoffa, eoffb, acce);
+            if constexpr (PK) {
+                if (NA > 0 && NB > 0) chunk_mfma_packed<NA, (NB > 0 ? NB : 1)>(la, lb, aoff, boff, acc00, acc01, nl);
+                if (BE) chunk_mfma_edge_packed<(NA > 0 ? NA : 1), NCE>(la, lb, eoffa, eoffb, acce);
+                // every PK_F chunks and at the segment's end the accumulators go to the running sums
+                if (++since == PK_F || k + KC >= kend) {
+                    since = 0;
+                    if (NA > 0 && NB > 0) {
+#pragma unroll
+                        for (int r = 0; r < 16; r++) {
+                            run0[r] = pk_sub_flush(acc00[r], run0[r]); acc00[r] = 0;
+                            if (NB > 1) { run1[r] = pk_sub_flush(acc01[r], run1[r]); acc01[r] = 0; }
+                        }
+                    }
+                    if (BE) {
+#pragma unroll
+                        for (int ga = 0; ga < 2; ga++)
+#pragma unroll
+                            for (int nc = 0; nc < NCE; nc++)
+#pragma unroll
+                                for (int r = 0; r < 4; r++) { rune[ga][nc][r] = pk_sub_flush(acce[ga][nc][r], rune[ga][nc][r]); acce[ga][nc][r] = 0.f; }
+                    }
+                }
+            } else {
+                if (NA > 0 && NB > 0) chunk_mfma<NA, (NB > 0 ? NB : 1), SK10>(la, lb, aoff, boff, acc00, acc01, acc10, acc11, nl);
+                if (BE) chunk_mfma_edge<(NA > 0 ? NA : 1), NCE>(la, lb, eoffa, eoffb, acce);
+            }
             wait_dma_barrier_dyn<NS>(ahead - 1);         // next chunk landed; everyone is done reading this one
             if (ahead > 0) ahead--;
             cur = (cur + 1 == NS) ? 0 : cur + 1;
@@ -328,22 +506,56 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
 #undef GAUSS_STAGE
         // end of a segment: flush its exact partial sums, start the next segment from zero.
         // C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-        if (NA > 0 && NB > 0) {
-            flush_acc<NA, (NB > 0 ? NB : 1), SK10>(out, (it.flags & 2) != 0, obase, obase16, acc00, acc01, acc10, acc11);
+        if constexpr (PK) {
+            // (the accumulators were emptied by the segment's last sub-flush; packed items always have 16-bit slabs)
+            if (NA > 0 && NB > 0) {
+                int ob = obase16;                                     // (store addresses formed here, as for the edge below)
+                asm volatile("" : "+v"(ob));
 #pragma unroll
-            for (int r = 0; r < 16; r++) { acc00[r] = 0; acc01[r] = 0; acc10[r] = 0; acc11[r] = 0; }
+                for (int r = 0; r < 16; r += 2) {
+                    const int o = ob + (((r & 3) + 8 * (r >> 2)) >> 1) * TILE;
+                    out[o] = pk_slab_lo(run0[r], run0[r + 1]);
+                    if (NB > 1) out[o + 32] = pk_slab_lo(run1[r], run1[r + 1]);
+                    if (NA > 1) {
+                        out[o + 16 * TILE] = pk_slab_hi(run0[r], run0[r + 1]);
+                        if (NB > 1) out[o + 16 * TILE + 32] = pk_slab_hi(run1[r], run1[r + 1]);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; r++) { run0[r] = 0; run1[r] = 0; }
+            }
+            if (BE) {
+                int er = erow0, ec = ecol0;
+                asm volatile("" : "+v"(er), "+v"(ec));
+                flush_edge_packed<(NA > 0 ? NA : 1), NCE>(out, er, ec, rune);
+#pragma unroll
+                for (int ga = 0; ga < 2; ga++)
+#pragma unroll
+                    for (int nc = 0; nc < NCE; nc++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++) rune[ga][nc][r] = 0;
+            }
+            out += TILE * TILE / 2;
+        } else {
+            if (NA > 0 && NB > 0) {
+                int ob = obase, ob16 = obase16;                       // (store addresses formed here, as for the edge below)
+                asm volatile("" : "+v"(ob), "+v"(ob16));
+                flush_acc<NA, (NB > 0 ? NB : 1), SK10>(out, (it.flags & 2) != 0, ob, ob16, acc00, acc01, acc10, acc11);
+#pragma unroll
+                for (int r = 0; r < 16; r++) { acc00[r] = 0; acc01[r] = 0; acc10[r] = 0; acc11[r] = 0; }
+            }
+            if (BE) {
+                // (the store addresses are formed here, not ahead of the K loop: twelve 64-bit pointers held across it would spill)
+                int er = erow0, ec = ecol0;
+                asm volatile("" : "+v"(er), "+v"(ec));
+                flush_edge<(NA > 0 ? NA : 1), NCE>(out, (it.flags & 2) != 0, er, ec, acce);
+#pragma unroll
+                for (int ga = 0; ga < 4; ga++)
+#pragma unroll
+                    for (int nc = 0; nc < NCE; nc++) acce[ga][nc] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            out += (it.flags & 2) ? TILE * TILE / 2 : TILE * TILE;
         }
-        if (BE) {
-            // (the store addresses are formed here, not ahead of the K loop: twelve 64-bit pointers held across it would spill)
-            int er = erow0, ec = ecol0;
-            asm volatile("" : "+v"(er), "+v"(ec));
-            flush_edge<(NA > 0 ? NA : 1), (BE ? NC : 1)>(out, (it.flags & 2) != 0, er, ec, acce);
-#pragma unroll
-            for (int ga = 0; ga < 4; ga++)
-#pragma unroll
-                for (int nc = 0; nc < (BE ? NC : 1); nc++) acce[ga][nc] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        out += (it.flags & 2) ? TILE * TILE / 2 : TILE * TILE;
     }
 }
 
@@ -364,15 +576,27 @@ __device__ __forceinline__ void gram_item(const Item& it, uint8_t* lds)
     const bool diag = (it.flags & 1) != 0;
     if (diag && wr == 1 && wc == 0) na = 0;
     // f32 path: a last half of at most 16 live B rows goes to the 16-column edge routine (GAUSS_GRAM_EDGE16 compiled in)
+    int nc = 0;
     if (std::is_same<ACC, f32x16>::value && GAUSS_GRAM_EDGE16 && na > 0) {
         int nb16 = (it.rows_b - wc * 64 + 15) / 16;
         nb16 = nb16 < 0 ? 0 : (nb16 > 4 ? 4 : nb16);
-        if (nb16 & 1) {
-            if (nb16 == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 3>(it, lds, wr, wc); }
-            else { if (na == 2) run_item<2, 0, ACC, NS, false, 1>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 1>(it, lds, wr, wc); }
+        if (nb16 & 1) nc = nb16;
+    }
+    // f32 path, items with flag bit 2 (16-bit slabs, codes <= 3; the planner sets it unless GAUSS_GRAM_PACKED=0): two A rows per lane
+    if constexpr (std::is_same<ACC, f32x16>::value) {
+        if (it.flags & 4) {
+            if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3, true>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 3, true>(it, lds, wr, wc); }
+            else if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1, true>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 1, true>(it, lds, wr, wc); }
+            else if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, wr, wc);
+            else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS, false, 0, true>(it, lds, wr, wc);       // (a diagonal wave too: its mirrored block costs no MFMA here)
+            else if (na == 2) run_item<2, 1, ACC, NS, false, 0, true>(it, lds, wr, wc);
+            else if (nb == 2) run_item<1, 2, ACC, NS, false, 0, true>(it, lds, wr, wc);
+            else run_item<1, 1, ACC, NS, false, 0, true>(it, lds, wr, wc);
             return;
         }
     }
+    if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 3>(it, lds, wr, wc); return; }
+    if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 1>(it, lds, wr, wc); return; }
     if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, wr, wc);
     else if (na == 2 && nb == 2 && diag && wr == wc) run_item<2, 2, ACC, NS, true>(it, lds, wr, wc);
     else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS>(it, lds, wr, wc);
