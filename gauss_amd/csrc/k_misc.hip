@@ -2,6 +2,9 @@
 // generator used by bench.py.
 #include "gauss_internal.h"
 #include <algorithm>
+#include <cstdio>
+
+bool trace_on(const char* what);      // gauss_job.h (GAUSS_TRACE)
 
 namespace gauss {
 
@@ -120,6 +123,8 @@ void launch_jacobi_clamp(const Prob* d_probs, int prob, const Prob& hp, double* 
     unsigned int* d_rot = reinterpret_cast<unsigned int*>(delta + 2 * (size_t)n);
     const int nb2 = (int)(((size_t)n * n + 255) / 256);
     hipLaunchKernelGGL(jacobi_init_kernel, dim3(nb2), dim3(256), 0, st, hp.A, G, V, n, hp.status);
+    int sweeps = 0;
+    unsigned int last_rot = 0;
     for (int sweep = 0; sweep < 30; sweep++) {
         hipMemsetAsync(d_rot, 0, sizeof(unsigned int), st);
         for (int r = 0; r < n - 1; r++)
@@ -127,8 +132,12 @@ void launch_jacobi_clamp(const Prob* d_probs, int prob, const Prob& hp, double* 
         unsigned int h_rot = 0;
         hipMemcpyAsync(&h_rot, d_rot, sizeof(unsigned int), hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
+        sweeps++;
+        last_rot = h_rot;
         if (h_rot == 0) break;
     }
+    if (trace_on("job"))
+        fprintf(stderr, "[job] jacobi clamp: n = %d, %d sweeps, %u rotations in the last one\n", n, sweeps, last_rot);
     hipLaunchKernelGGL(jacobi_lambda_kernel, dim3(n), dim3(256), 0, st, G, V, n, hp.eps, delta, hp.status);
     if (apply) hipLaunchKernelGGL(jacobi_apply_kernel, dim3(nb2), dim3(256), 0, st, hp.A, V, delta, n);
 }
