@@ -40,6 +40,7 @@ class WindowDesc(C.Structure):
         ("kind", C.c_int), ("n_head_measured", C.c_int), ("n_pred_measured", C.c_int), ("eig_cutoff", C.c_double),
         ("out_r", _dp), ("out_num_eig", _ip), ("u_codings", C.c_int),
         ("geno_format", C.c_int), ("rows_m", _ip), ("rows_u", _ip), ("pop_src_off", _ip),
+        ("out_loo_z", _dp), ("out_loo_info", _dp), ("out_loo_t", _dp),
     ]
 
 

@@ -46,6 +46,7 @@ HOST_SYMBOLS = [
     "gauss_host_jepeg_rank", "gauss_host_jepeg_genome", "gauss_prepared_jepeg_plan", "gauss_prepared_jepeg_finish",
     "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
+    "gauss_host_dist_loo", "gauss_host_distmix_loo",
 ]
 
 
@@ -131,6 +132,8 @@ def load_host():
     h.gauss_table_named.restype = _dp
     h.gauss_table_named.argtypes = [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     h.gauss_host_qcat.argtypes = h.gauss_host_dist.argtypes
+    h.gauss_host_dist_loo.argtypes = h.gauss_host_dist.argtypes
+    h.gauss_host_distmix_loo.argtypes = h.gauss_host_distmix.argtypes
     h.gauss_host_qcatmix.argtypes = h.gauss_host_distmix.argtypes
     h.gauss_prepared_qcat_counts.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     h.gauss_host_prepare.argtypes = [C.c_int, C.c_int, _i64, _i64, _i64, _cp, _strs, _dp, C.c_int, _cp, _cp, _cp, _cp, _cp,
@@ -323,6 +326,31 @@ def distmix(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_
     _hcheck(h.gauss_host_distmix(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
                                  w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
                                  _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
+    return _table(h, out)[0]
+
+
+def dist_loo(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
+             reference_pop_desc_file, af1_cutoff=None, ctx=None):
+    """Leave-one-out check of a dist() window (gauss_host_dist_loo): every measured SNP inside [start_bp, end_bp] re-imputed from
+    the other measured SNPs of the extended window.  Columns rsid chr bp a1 a2 af1ref z z_loo info_loo t pval; t is the
+    standardised residual (N(0, 1) under the model), pval = 2 pnorm(-|t|): a flipped or misplaced study SNP has a large |t|."""
+    h = load_host()
+    out = _vp()
+    _hcheck(h.gauss_host_dist_loo(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
+                                  _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
+                                  _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
+    return _table(h, out)[0]
+
+
+def distmix_loo(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
+                reference_pop_desc_file, af1_cutoff=None, ctx=None):
+    """Leave-one-out check of a distmix() window (gauss_host_distmix_loo); columns as dist_loo with af1mix."""
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_distmix_loo(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
+                                     w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
+                                     _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
     return _table(h, out)[0]
 
 

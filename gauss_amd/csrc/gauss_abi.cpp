@@ -19,6 +19,7 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.u_codings = d.u_codings;
     w.geno_fmt = d.geno_format; w.rows_m = d.rows_m; w.rows_u = d.rows_u; w.pop_src_off = d.pop_src_off;
     w.out_b11 = d.out_b11; w.out_b21 = d.out_b21;
+    w.out_loo_z = d.out_loo_z; w.out_loo_info = d.out_loo_info; w.out_loo_t = d.out_loo_t;
     return w;
 }
 extern "C" {

@@ -122,6 +122,8 @@ struct Prob {
     // resampled windows (simulateLD, k_simld.hip): the packed columns are drawn samples, not the populations' samples
     GP(const int) draw_col;    // [Kp] source column of every packed column, ascending, -1 past the draws; null: not resampled
     int row_src_bytes;         // bytes of a source row the resample kernel reads
+    // leave-one-out re-imputation of the measured SNPs (k_loo.hip): [3][M] loo_z, loo_info, loo_t in the result block; null: not asked
+    GP(double) out_loo;
 };
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
@@ -225,6 +227,8 @@ void launch_shift_cert(const Prob* d_probs, int n_prob, hipStream_t s);
 void launch_solve(const Prob* d_probs, const int2* d_panelmap, int n_panels, hipStream_t s);
 void launch_impute_gemm(const Prob* d_probs, const int2* d_gmap, int n_tiles, int u_tile, const int2* d_fmap, int n_chunks, hipStream_t s);
 void launch_solve_last(const Prob* d_probs, const int2* d_panelmap, int n_panels, int max_nblk, int split, hipStream_t s);
+// leave-one-out values of the measured SNPs from [X | y] (k_loo.hip): d_loomap = (window, 64-column panel of X) of the windows that asked
+void launch_loo(const Prob* d_probs, const int2* d_loomap, int n_panels, hipStream_t s);
 void launch_counts(const Prob* d_probs, int prob, int npair, long long* d_out, hipStream_t s);
 void launch_pack2bit(const uint8_t* d_in, long long ld_in, uint8_t* d_out, long long ld_out, int n_snp,
                      const int* d_pop_off, const int* d_blk_off, int n_pop, hipStream_t s);

@@ -261,6 +261,10 @@ struct Plan {
     double* out_b21 = nullptr;
     double* out_r = nullptr;
     int32_t* out_num_eig = nullptr;
+    bool loo = false;                        // the window asked for leave-one-out values: [3][M] behind its z / info in the result block
+    double* out_loo_z = nullptr;
+    double* out_loo_info = nullptr;
+    double* out_loo_t = nullptr;
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
     size_t out_ld_count = 0;
@@ -313,6 +317,7 @@ struct gauss_job {
     int2* d_gemmmap = nullptr;  int n_gemm = 0;            // (window, rhs panel of gemm_ut << 8 | k block of 128), longest first
     int gemm_ut = 128;                                     // right-hand sides per tile of the product: 128, small jobs 64
     int2* d_finmap = nullptr;   int n_fin = 0;             // (window, chunk of 256 right-hand sides)
+    int2* d_loomap = nullptr;   int n_loo = 0;             // leave-one-out: (window, 64-column panel of X) of the windows that asked
     int max_nblk = 0;
     int max_npanel = 0;                                    // most solve panels of any one window
     int solve_split = 0;                                   // rows of the inverse with at least this many products are cut (0: none)
@@ -417,6 +422,9 @@ struct WinSpec {
     int gram_only = 0;                       // LD-only without pairs: every B11 tile pair, but no S x S output (zmix normal equations)
     double* out_b11 = nullptr;               // matrices the caller wants back (the job plans their export at build time)
     double* out_b21 = nullptr;
+    double* out_loo_z = nullptr;             // leave-one-out values of the measured SNPs (any non-null: the window asks)
+    double* out_loo_info = nullptr;
+    double* out_loo_t = nullptr;
     // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample
     // draw_sample[k] of selected population draw_pop[k] and the other n_cols - n_drawn are zero columns
     const int32_t* draw_pop = nullptr;

@@ -78,6 +78,11 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         return fail(GAUSS_E_INVALID, "bad u_codings mask %d", w.u_codings);
     if (w.kind == GAUSS_WIN_QCAT && (w.n_head < 0 || w.n_predm < 0 || w.n_head + w.n_predm > w.M))
         return fail(GAUSS_E_INVALID, "QCAT: n_head_measured + n_pred_measured exceeds n_measured");
+    // leave-one-out values come from the rows of L^-1 that an imputation window's solve leaves behind (k_loo.hip)
+    const bool loo = w.out_loo_z || w.out_loo_info || w.out_loo_t;
+    if (loo && (w.ld_only || w.kind != GAUSS_WIN_IMPUTE))
+        return fail(GAUSS_E_INVALID, "leave-one-out values (out_loo_z / out_loo_info / out_loo_t) are for imputation windows only (%s window)",
+                    w.kind == GAUSS_WIN_QCAT ? "QCAT" : "LD");
 
     Prob& p = pl.p;
     memset(&p, 0, sizeof(p));
@@ -288,6 +293,7 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
     if (w.z1) pl.z1.assign(w.z1, w.z1 + w.M);
     pl.h_geno_m = w.geno_m; pl.h_geno_u = w.geno_u; pl.user_ld = w.ld;
     pl.out_b11 = w.out_b11; pl.out_b21 = w.out_b21;
+    pl.loo = loo; pl.out_loo_z = w.out_loo_z; pl.out_loo_info = w.out_loo_info; pl.out_loo_t = w.out_loo_t;
     return GAUSS_OK;
 }
 
@@ -416,7 +422,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             q.M = (int)gl.size(); q.U = 0; q.U_raw = 1; q.n_rhs = 0;
             q.Mp = (int)rup((size_t)q.M, TILE); q.Up = 0; q.Sp = q.Mp; q.nT = q.Mp / TILE;
             q.Mld = 0; q.nblk = 0; q.npanel = 0; q.npi = 0; q.kind = 0; q.ld_only = 0; q.n_head = q.n_predm = 0;
-            g.U_user = 0; g.h_geno_u = nullptr;
+            g.U_user = 0; g.h_geno_u = nullptr; g.loo = false;
             // job-wide B11 pairs: the tile pairs some window lies in
             g.pair_ti.clear(); g.pair_tj.clear(); g.pair_lut.assign((size_t)q.nT * q.nT, -1);
             for (int i = 0; i < job->n; i++) {
@@ -507,7 +513,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     struct ItemH { int prob, pair, group, len, b11, ord = 0; };     // b11: an item of B11 (job-wide pairs, or a window's own measured x measured pairs); ord: launch-order key (below)
     std::vector<ItemH> items;
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
-    std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap;
+    std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
     job->max_nblk = 0;
     {
         // tiles of the closing product at 128 right-hand sides each: a small job (an 8-rank share: ~570) cannot fill the
@@ -574,6 +580,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             }
         for (int pn = 0; pn < p.npi; pn++) panelmap.push_back(make_int2(i, pn));
         for (int pn = 0; pn < p.npanel; pn++) dpanelmap.push_back(make_int2(i, pn));
+        if (job->plans[i].loo)
+            for (int pn = 0; pn < (p.M + NR - 1) / NR; pn++) loomap.push_back(make_int2(i, pn));      // the panels that hold columns of X
         if (p.npanel > 0) {
             job->max_nblk = std::max(job->max_nblk, p.nblk); job->max_npanel = std::max(job->max_npanel, p.npi);
             for (int up = 0; up < p.Up128 / job->gemm_ut; up++)
@@ -776,6 +784,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     const size_t o_dpanelmap = put(blob, ta, dpanelmap);
     const size_t o_gemmmap = put(blob, ta, gemmmap);
     const size_t o_finmap = put(blob, ta, finmap);
+    const size_t o_loomap = put(blob, ta, loomap);
     const size_t o_probs = ta.take(sizeof(Prob) * (size_t)n_prob);
     const size_t o_exports = ta.take(sizeof(ExportD) * std::max<size_t>(job->exports.size(), 1));
     blob.resize(ta.off);
@@ -786,6 +795,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n_dpanels = (int)dpanelmap.size();
     job->n_gemm = (int)gemmmap.size();
     job->n_fin = (int)finmap.size();
+    job->n_loo = (int)loomap.size();
 
     // ---- workspace arena ----
     Arena wa;         // zeroed once per job: operand padding, B21 padding and the solve matrices rely on it
@@ -847,7 +857,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         }
         w.ld = wa.take(std::max<size_t>(pl.out_ld_count, 1) * sizeof(double));
         pl.res_off = res;
-        res += 2 * (size_t)p.n_rhs;
+        res += 2 * (size_t)p.n_rhs + (pl.loo ? 3 * (size_t)p.M : 0);      // z, info [, loo_z, loo_info, loo_t]
     }
     // job-wide measured rows (shared measured rows): one more tile of rows than Mp, because a window's last row tile
     // starts wherever the window starts and may reach past the chromosome's last measured SNP (zero rows there)
@@ -986,6 +996,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         }
         p.out_z = job->d_results + pl.res_off;
         p.out_info = job->d_results + pl.res_off + p.n_rhs;
+        p.out_loo = pl.loo ? job->d_results + pl.res_off + 2 * (size_t)p.n_rhs : nullptr;
         p.status = job->d_status + 4 * i;
         p.out_ld = (double*)(W + w.ld);
         p.gene_off = p.n_gene ? (const int*)(T + to[i].goff) : nullptr;
@@ -1057,7 +1068,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         q.run_pk_off = (const int*)(T + to[n].rpk); q.run_src = (const int*)(T + to[n].rsrc);
         q.slab = (float*)(W + go.slab); q.slab_g = q.slab; q.gpair_ti = q.pair_ti; q.gpair_tj = q.pair_tj; q.g0 = 0; q.n_gpair = q.npair;
         q.z1 = nullptr; q.A = nullptr; q.B21 = nullptr; q.Linv = nullptr; q.V = nullptr; q.Gsum = nullptr; q.Part = nullptr;
-        q.out_z = q.out_info = nullptr; q.out_ld = nullptr; q.status = job->d_status;      // never written for this descriptor
+        q.out_z = q.out_info = nullptr; q.out_loo = nullptr; q.out_ld = nullptr; q.status = job->d_status;      // never written for this descriptor
         q.gene_off = nullptr; q.gene_out_off = nullptr; q.n_gene = 0;
         memcpy(blob.data() + o_probs + sizeof(Prob) * n, &q, sizeof(Prob));
     }
@@ -1118,6 +1129,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->d_dpanelmap = (int2*)(job->d_tab + o_dpanelmap);
     job->d_gemmmap = (int2*)(job->d_tab + o_gemmmap);
     job->d_finmap = (int2*)(job->d_tab + o_finmap);
+    job->d_loomap = (int2*)(job->d_tab + o_loomap);
     job->d_exports = (ExportD*)(job->d_tab + o_exports);
     if (!on_device && !streamed) HIPCHK(hipStreamSynchronize(st));   // uploads from pageable user memory are complete
     std::vector<char>().swap(job->h_tab);

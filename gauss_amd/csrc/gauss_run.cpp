@@ -107,7 +107,9 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
                                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_run0).count());
     // fused tail: the factorisation chain needs B11 only and the closing product is the first reader of B21, so B21's
     // tiles of the epilogue (85 % of them) go to the side stream and run beside the chain
-    const bool fused = env_int("GAUSS_FUSED_SOLVE", 1) != 0;           // read per run: the tests drive both forms
+    // (a job with a window that asks for leave-one-out values always takes the fused form: they are read off the rows of L^-1 that
+    // only the fused solve forms, k_loo.hip)
+    const bool fused = env_int("GAUSS_FUSED_SOLVE", 1) != 0 || job->n_loo > 0;           // read per run: the tests drive both forms
     hipStream_t side = (solve && fused && job->n_panels > 0 && job->n_tiles > job->n_tiles_b11) ? ctx->side : nullptr;
     prof_begin(job, 1, st);
     if (job->resample_lds >= 0) launch_resample_pack(job->d_probs, job->d_rowmap, job->n_rows, job->resample_lds, st);
@@ -185,6 +187,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         }
         HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
         prof_begin(job, 4, st);
+        launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);       // the chain has been joined: [X | y] is complete
         launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
         prof_end(job, st);
         return job_queue_results(job, par, st);
@@ -221,6 +224,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         if (fused) {
             launch_solve_last(job->d_probs, job->d_panelmap, job->n_panels, job->max_nblk, job->solve_split, st);
             if (side) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
+            launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
             launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
         } else launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
         prof_end(job, st);
@@ -395,6 +399,7 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
     }
     launch_epilogue(job->d_probs, job->d_tilemap + job->n_tiles_b11, job->n_tiles - job->n_tiles_b11, job->max_pop, job->gram_i8, st);
     if (ch != st) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
+    launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
     launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
     const int rc = job_queue_results(job, (int)(job->run_seq & 1u), st);
     if (rc) return rc;
@@ -414,7 +419,7 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     // Re-run the epilogue for this problem only to restore A[0] (the factorisation overwrote it)
     std::vector<int2> tm;
     tm = job->win_tiles[(size_t)i];                   // this window's epilogue tiles (job-wide B11 pairs included)
-    DevBuf d_tm, d_work, d_pm;
+    DevBuf d_tm, d_work, d_pm, d_lm;
     HIPCHK(d_tm.alloc(job->ctx, sizeof(int2) * tm.size()));
     HIPCHK(hipMemcpyAsync(d_tm.p, tm.data(), sizeof(int2) * tm.size(), hipMemcpyHostToDevice, st));
     launch_epilogue(job->d_probs, d_tm.as<int2>(), (int)tm.size(), job->max_pop, job->gram_i8, st);
@@ -431,15 +436,30 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     HIPCHK(hipMemcpyAsync(d_pm.p, pm.data(), sizeof(int2) * pm.size(), hipMemcpyHostToDevice, st));
     if (pl.out_b11) HIPCHK(hipMemcpyAsync(pl.d_b11_copy, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(p.A + 4 * n * n, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));   // W0 = clamped B11
+    // a window that asked for leave-one-out values: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this
+    // factorisation as they do in a run's (same L either way), k_loo.hip reads them, and only then does the stand-alone
+    // solve below take V as its scratch
+    const bool loo = pl.loo;
     for (int s = 0; s < p.nblk; s++) {
         // launch over all problems would redo the others; use a single-problem launch instead
-        launch_factor_step(job->d_probs + i, 1, s, p.nblk, 0, 0, 0, st);
+        launch_factor_step(job->d_probs + i, 1, s, p.nblk, loo ? p.npi : 0, loo ? job->solve_split : 0, 0, st);
+    }
+    if (loo) {
+        std::vector<int2> lm;
+        for (int pn = 0; pn < p.npi; pn++) lm.push_back(make_int2(i, pn));
+        const int n_x = (p.M + NR - 1) / NR;                 // the panels that hold columns of X come first
+        HIPCHK(d_lm.alloc(job->ctx, sizeof(int2) * lm.size()));
+        HIPCHK(hipMemcpyAsync(d_lm.p, lm.data(), sizeof(int2) * lm.size(), hipMemcpyHostToDevice, st));
+        launch_solve_last(job->d_probs, d_lm.as<int2>(), (int)lm.size(), p.nblk, job->solve_split, st);
+        launch_loo(job->d_probs, d_lm.as<int2>(), n_x, st);
+        HIPCHK(hipStreamSynchronize(st));                    // (`lm` is pageable: the copy has read it)
     }
     launch_solve(job->d_probs, d_pm.as<int2>(), (int)pm.size(), st);
     HIPCHK(hipGetLastError());
     int h_status[4];
     HIPCHK(hipMemcpyAsync(h_status, p.status, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(job->h_results + pl.res_off, job->d_results + pl.res_off, sizeof(double) * 2 * p.n_rhs, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(job->h_results + pl.res_off, job->d_results + pl.res_off, sizeof(double) * (2 * (size_t)p.n_rhs + (loo ? 3 * (size_t)p.M : 0)),
+                          hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *status_bits = (h_status[2] || h_status[0]) ? GAUSS_ST_NONFINITE : GAUSS_ST_CLAMPED;
     return GAUSS_OK;
@@ -629,10 +649,17 @@ int job_fetch(gauss_job* job)
         if (p.npanel > 0) {
             if (bits & GAUSS_ST_NONFINITE) {
                 // the reference's eigen-solver / LU propagate non-finite values to every output
-                for (int u = 0; u < 2 * p.U; u++) job->h_results[pl.res_off + u] = NAN;
+                for (size_t u = 0; u < 2 * (size_t)p.U + (pl.loo ? 3 * (size_t)p.M : 0); u++) job->h_results[pl.res_off + u] = NAN;
             }
             if (pl.out_z) memcpy(pl.out_z, job->h_results + pl.res_off, sizeof(double) * p.U);
             if (pl.out_info) memcpy(pl.out_info, job->h_results + pl.res_off + p.U, sizeof(double) * p.U);
+            if (pl.loo) {
+                // leave-one-out values of the measured SNPs (k_loo.hip): [3][M] behind z / info
+                const double* lo = job->h_results + pl.res_off + 2 * (size_t)p.U;
+                if (pl.out_loo_z) memcpy(pl.out_loo_z, lo, sizeof(double) * p.M);
+                if (pl.out_loo_info) memcpy(pl.out_loo_info, lo + p.M, sizeof(double) * p.M);
+                if (pl.out_loo_t) memcpy(pl.out_loo_t, lo + 2 * (size_t)p.M, sizeof(double) * p.M);
+            }
             if (pl.out_b11 && (!exporting || clamped))
                 { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }
             if (pl.out_b21 && p.U > 0 && !exporting)

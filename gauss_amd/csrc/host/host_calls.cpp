@@ -258,10 +258,19 @@ int gauss_prepared_finish(gauss_prepared* p, gauss_table** out)
 // the literal path: prepare_opened + gauss_impute_window on host rows.
 static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
                       const char* const* names, const double* wgts, int nw, const char* input, const char* index,
-                      const char* data, const char* desc, double af1_cutoff, gauss_table** out)
+                      const char* data, const char* desc, double af1_cutoff, gauss_table** out, bool loo = false)
 {
     if (!ctx || !out) return herr("bad arguments");
     if (files_ok({input, index, data, desc})) return -1;
+    // loo (dist_loo / distmix_loo): the same window and the same single job, with the three leave-one-out arrays of
+    // gauss_window_desc set; the table lists the measured SNPs of the prediction window instead (the wings only contribute to B11)
+    const bool mix = kind == GAUSS_KIND_DISTMIX;
+    std::vector<double> lz, li, lt;
+    auto ask = [&](gauss_window_desc& d) {
+        lz.assign((size_t)d.n_measured, 0.0); li = lz; lt = lz;
+        d.out_loo_z = lz.data(); d.out_loo_info = li.data(); d.out_loo_t = lt.data();
+    };
+    auto in_window = [&](long long bp) { const int ibp = (int)bp; return ibp >= start_bp && ibp <= end_bp; };      // dist.cpp:92
     std::string panel_path;
     std::shared_ptr<PackedPanel> pk;
     if (open_panel(index, data, desc, panel_path, pk)) return -1;
@@ -272,6 +281,7 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
     if (lean == 0) {
         gauss_window_desc d;                                  // (points into ow.w)
         if (lean_window_desc(ow.w, &d)) return -1;
+        if (loo) ask(d);
         int on_device = 0;
         panel_rows(ctx, panel_path, *pk, &d.geno_m, &on_device);
         d.geno_u = d.geno_m;
@@ -285,6 +295,15 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
         } else if (gauss_impute_window(ctx, &d) != 0) {           // a panel too large to keep in HBM: the window's rows from the mapped file
             return herr("%s", gauss_last_error());
         }
+        if (loo) {
+            std::vector<LooRow> rows;
+            for (size_t i = 0; i < ow.w.measured.size(); i++) {
+                const LeanSnp& sn = ow.w.v[(size_t)ow.w.measured[i]];
+                if (in_window(sn.bp)) rows.push_back(LooRow{ident_of(*pk, sn), sn.af, sn.z, (int)i});
+            }
+            *out = loo_output(mix, rows, lz.data(), li.data(), lt.data());
+            return 0;
+        }
         *out = lean_window_finish(ow.w);
         return 0;
     }
@@ -293,7 +312,17 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
     std::unique_ptr<gauss_prepared> hold(p);
     gauss_window_desc d;
     if (gauss_prepared_window_desc(p, &d)) return -1;
+    if (loo) ask(d);
     if (gauss_impute_window(ctx, &d) != 0) return herr("%s", gauss_last_error());
+    if (loo) {
+        std::vector<LooRow> rows;
+        for (size_t i = 0; i < p->measured.size(); i++) {
+            const Snp& s = *p->measured[i];
+            if (in_window(s.bp)) rows.push_back(LooRow{ident_of(s), mix ? s.af1mix : s.af1ref, s.z, (int)i});
+        }
+        *out = loo_output(mix, rows, lz.data(), li.data(), lt.data());
+        return 0;
+    }
     return gauss_prepared_finish(p, out);
 }
 
@@ -313,6 +342,23 @@ int gauss_host_distmix(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp
 {
     return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
                       input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out);
+}
+
+int gauss_host_dist_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                        const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                        const char* reference_pop_desc_file, double af1_cutoff, gauss_table** out)
+{
+    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
+                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, true);
+}
+
+int gauss_host_distmix_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                           const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                           const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                           double af1_cutoff, gauss_table** out)
+{
+    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
+                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, true);
 }
 
 int gauss_host_qcat(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,

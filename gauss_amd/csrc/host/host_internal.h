@@ -514,6 +514,10 @@ double pchisq_upper(double x, int df);
 GeneResult jepeg_tail(const std::vector<Snp*>& gs, const double* CorG, const Args& a);
 gauss_table* dist_output(gauss_prepared& p);
 gauss_table* qcat_output(gauss_prepared& p);
+// dist_loo / distmix_loo: one row per measured SNP of the prediction window, `idx` its row among the window's measured SNPs (the
+// index into the three leave-one-out arrays of gauss_window_desc)
+struct LooRow { SnpIdent id; double af, z; int idx; };
+gauss_table* loo_output(bool mix, const std::vector<LooRow>& rows, const double* loo_z, const double* loo_info, const double* loo_t);
 gauss_table* prep_output(gauss_prepared& p);
 int panel_make_resident(gauss_ctx* ctx, const std::string& path, void** dev, int64_t* uploaded, bool async = false);
 bool panel_is_resident(gauss_ctx* ctx, const std::string& path, void** dev, bool wait = true);

@@ -222,6 +222,23 @@ gauss_table* dist_output(gauss_prepared& p)     // dist.cpp:91-124 / distmix.cpp
     return t;
 }
 
+// rsid chr bp a1 a2 af1ref|af1mix z z_loo info_loo t pval: the measured SNPs of the prediction window, each re-imputed from the
+// other measured SNPs of the extended window; pval = 2 pnorm(-|t|) of the standardised residual
+gauss_table* loo_output(bool mix, const std::vector<LooRow>& rows, const double* loo_z, const double* loo_info, const double* loo_t)
+{
+    gauss_table* t = new gauss_table();
+    add_ident_columns(*t, rows.size(), [&](size_t i) { return rows[i].id; });
+    Column &af = t->add(mix ? "af1mix" : "af1ref", GAUSS_COL_DBL), &z = t->add("z", GAUSS_COL_DBL), &zl = t->add("z_loo", GAUSS_COL_DBL);
+    Column &il = t->add("info_loo", GAUSS_COL_DBL), &tt = t->add("t", GAUSS_COL_DBL), &pval = t->add("pval", GAUSS_COL_DBL);
+    for (Column* c : {&af, &z, &zl, &il, &tt, &pval}) c->d.reserve(rows.size());
+    for (const LooRow& r : rows) {
+        af.d.push_back(r.af); z.d.push_back(r.z);
+        zl.d.push_back(loo_z[r.idx]); il.d.push_back(loo_info[r.idx]); tt.d.push_back(loo_t[r.idx]);
+        pval.d.push_back(2 * pnorm_upper(fabs(loo_t[r.idx])));
+    }
+    return t;
+}
+
 gauss_table* qcat_output(gauss_prepared& p)     // qcat.cpp:94-131 / qcatmix.cpp:102-139
 {
     const bool mix = p.kind == GAUSS_KIND_QCATMIX;

@@ -272,7 +272,7 @@ class _Win:
     """Keeps the numpy buffers of one window alive next to its C descriptor."""
 
     def __init__(self, desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig,
-                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None):
+                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False):
         self.po, self.w = _pops(pop_off, pop_wgt)
         self.z1 = np.ascontiguousarray(z1, dtype=np.float64)
         if dev_ptrs is None:
@@ -311,6 +311,10 @@ class _Win:
         desc.out_status = self.status.ctypes.data_as(_ip)
         desc.out_b11 = _lib.ptr(self.b11, _dp)
         desc.out_b21 = _lib.ptr(self.b21, _dp)
+        # leave-one-out re-imputation of the measured SNPs (out_loo_* of gauss_window_desc): [3, M] z, info, t
+        self.loo = np.zeros((3, M)) if loo else None
+        if loo:
+            desc.out_loo_z, desc.out_loo_info, desc.out_loo_t = (self.loo[k].ctypes.data_as(_dp) for k in range(3))
         if packed is not None:
             # packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=): rows taken from a row store (dev_ptrs or
             # geno_m/geno_u give its base pointer and stride), optionally 2-bit packed (include/gauss_hip.h)
@@ -351,15 +355,19 @@ class _Win:
         out = dict(z=self.z, info=self.info, status=int(self.status[0]))
         if self.b11 is not None:
             out["b11"], out["b21"] = self.b11, self.b21
+        if self.loo is not None:
+            out["loo_z"], out["loo_info"], out["loo_t"] = self.loo[0], self.loo[1], self.loo[2]
         return out
 
 
 def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_eig=1e-5,
-                  want_mats=False, ctx=None):
-    """run_dist (mode 0, dist.cpp:129-227) / run_distmix (mode 1, distmix.cpp:138-253)."""
+                  want_mats=False, ctx=None, loo=False):
+    """run_dist (mode 0, dist.cpp:129-227) / run_distmix (mode 1, distmix.cpp:138-253).
+    loo=True adds loo_z, loo_info, loo_t [M]: every measured SNP re-imputed from the other measured SNPs, and its
+    standardised residual (include/gauss_hip.h, out_loo_*)."""
     ctx = ctx or default_context()
     desc = WindowDesc()
-    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats)
+    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo)
     check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
     return win.result()
 
@@ -491,8 +499,9 @@ class Job:
     """A batch of windows sharing every launch (gauss_job_*)."""
 
     def __init__(self, windows, ctx=None, on_device=False, want_mats=False):
-        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig])
-        or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays."""
+        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo])
+        or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
+        loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs)."""
         self.ctx = ctx or default_context()
         n = len(windows)
         self.descs = (WindowDesc * n)()
@@ -500,7 +509,8 @@ class Job:
         for i, w in enumerate(windows):
             self.wins.append(_Win(self.descs[i], w["mode"], w.get("geno_m"), w.get("geno_u"),
                                   w["pop_off"], w.get("pop_wgt"), w["z1"], w.get("lam", 0.1),
-                                  w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed")))
+                                  w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed"),
+                                  loo=bool(w.get("loo", False))))
         h = C.c_void_p()
         check(self.ctx.lib.gauss_job_create(self.ctx.handle, self.descs, n, 1 if on_device else 0,
                                             C.byref(h)))

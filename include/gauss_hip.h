@@ -108,6 +108,19 @@ typedef struct gauss_window_desc {
     const int32_t* rows_m;    /* [M] store row of each measured SNP, or NULL          host pointer */
     const int32_t* rows_u;    /* [U] store row of each geno_u SNP, or NULL            host pointer */
     const int32_t* pop_src_off; /* [P] 2-bit format: byte offset of each population block, or NULL */
+    /* ---- leave-one-out re-imputation of the measured SNPs (GAUSS_WIN_IMPUTE windows only) ------------------------
+     * The input check of summary-statistics imputation: measured SNP i re-imputed from the other M - 1 measured SNPs of
+     * the window, i.e. what run_dist / run_distmix return for SNP i when it is presented as the only unmeasured SNP.  With
+     * B = B11 (lambda on the diagonal, after MakePosDef if it acted), d = diag(B^-1), g = B^-1 z1:
+     *   mean_i = z1_i - g_i / d_i;  out_loo_info[i] = |B_ii - 1 / d_i| (dist.cpp:198);  out_loo_z[i] = mean_i / sqrt(info_i)
+     *   (dist.cpp:200);  out_loo_t[i] = (z1_i - mean_i) sqrt(d_i) = g_i / sqrt(d_i), the standardised residual -- N(0, 1) under
+     *   z1 ~ N(0, B): a flipped allele or a misplaced SNP shows as a large |t|.
+     * Any of the three being non-NULL switches the computation on for that window (one pass over L^-1, which the solve
+     * holds anyway); NULL = not wanted.  GAUSS_ST_NONFINITE windows return NaN; M = 1 returns info 0, z NaN,
+     * t = z1 / sqrt(1 + lambda).  QCAT and LD windows that set one of them are GAUSS_E_INVALID. */
+    double* out_loo_z;        /* [M] optional                                          host pointer */
+    double* out_loo_info;     /* [M] optional                                          host pointer */
+    double* out_loo_t;        /* [M] optional                                          host pointer */
 } gauss_window_desc;
 
 #define GAUSS_GENO_U8   0

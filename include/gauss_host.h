@@ -138,6 +138,24 @@ int gauss_host_jepeg_genome(gauss_ctx* ctx, int kind, int n_calls, const char* s
 int gauss_prepared_jepeg_plan(const gauss_prepared* p, int world, int32_t* first);
 int gauss_prepared_jepeg_finish(const gauss_prepared* p, int g0, int g1, const double* blocks, gauss_table** out);
 
+/* Leave-one-out re-imputation of the measured SNPs: the input check before a dist() / distmix() result is trusted.  Same
+ * arguments, same window (wings included), same data layer and the same single job as gauss_host_dist / gauss_host_distmix; the
+ * job's window sets out_loo_z / out_loo_info / out_loo_t (include/gauss_hip.h).  The table lists the MEASURED SNPs inside
+ * [start_bp, end_bp] in the reference's SNP order -- the wings' SNPs contribute to B11 and are not reported, as with QCAT --
+ * with columns rsid chr bp a1 a2 af1ref|af1mix z z_loo info_loo t pval: z the study's Z-score, z_loo / info_loo what
+ * dist() / distmix() would return for the SNP were it deleted from the study file, t = (z - mean_loo) sqrt((B11^-1)_ii) the
+ * standardised residual (N(0, 1) under the model), pval = 2 pnorm(-|t|).  A flipped allele, a strand mix-up or a misplaced
+ * SNP shows as a large |t|. */
+int gauss_host_dist_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                        const char* study_pop, const char* input_file, const char* reference_index_file,
+                        const char* reference_data_file, const char* reference_pop_desc_file,
+                        double af1_cutoff, gauss_table** out);
+int gauss_host_distmix_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                           const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                           const char* input_file, const char* reference_index_file,
+                           const char* reference_data_file, const char* reference_pop_desc_file,
+                           double af1_cutoff, gauss_table** out);
+
 /* QCAT / QCATMIX: same feeder as dist / distmix, the window core is
  * run_qcat (qcat.cpp:134-262) / run_qcatmix (qcatmix.cpp:144-297).  af1_cutoff NaN -> 0.05 for qcat
  * (qcat.cpp:53-57), 0.01 for qcatmix (qcatmix.cpp:61-65).  Output columns: rsid chr bp a1 a2
