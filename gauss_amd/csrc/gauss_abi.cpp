@@ -540,10 +540,25 @@ int gauss_pop_weights(gauss_ctx* ctx, const double* x, const int64_t* interval_o
     return GAUSS_OK;
 }
 
+// The bench plumbing's kernels index a caller's device buffer by pop_off and a row stride: offsets that start below 0 or
+// decrease, or a stride shorter than a row of pop_off[n_pop] samples, would put them outside it.
+static int check_pop_off(const char* who, const int32_t* pop_off, int n_pop, const char* ld_name, int64_t ld)
+{
+    if (pop_off[0] < 0) return fail(GAUSS_E_INVALID, "%s: pop_off[0] = %d is negative", who, pop_off[0]);
+    for (int q = 0; q < n_pop; q++)
+        if (pop_off[q + 1] < pop_off[q])
+            return fail(GAUSS_E_INVALID, "%s: pop_off is not ascending at %d (%d after %d)", who, q + 1, pop_off[q + 1], pop_off[q]);
+    if (ld < pop_off[n_pop])
+        return fail(GAUSS_E_INVALID, "%s: %s = %lld is shorter than a row of pop_off[n_pop] = %d samples", who, ld_name, (long long)ld,
+                    pop_off[n_pop]);
+    return GAUSS_OK;
+}
+
 int gauss_pack2bit_device(gauss_ctx* ctx, const uint8_t* d_in, int64_t ld_in, uint8_t* d_out, int64_t ld_out,
                           int n_snp, const int32_t* pop_off, int n_pop)
 {
     if (!ctx || !d_in || !d_out || !pop_off || n_snp < 1 || n_pop < 1) return fail(GAUSS_E_INVALID, "bad arguments");
+    if (int rc = check_pop_off("gauss_pack2bit_device", pop_off, n_pop, "ld_in", ld_in)) return rc;
     std::vector<int> blk(n_pop + 1, 0);
     for (int q = 0; q < n_pop; q++) blk[q + 1] = blk[q] + (int)rup((size_t)(pop_off[q + 1] - pop_off[q]), 64) / 4;
     if (ld_out % 16 || ld_out < blk[n_pop]) return fail(GAUSS_E_INVALID, "ld_out must be a multiple of 16 and >= %d", blk[n_pop]);
@@ -564,6 +579,7 @@ int gauss_synth_device(gauss_ctx* ctx, uint8_t* d_out, int n_snp, int64_t ld, co
                        const float* thr, const float* rho, uint64_t seed)
 {
     if (!ctx || !d_out || !pop_off || !thr || !rho || n_snp < 1 || n_pop < 1) return fail(GAUSS_E_INVALID, "bad arguments");
+    if (int rc = check_pop_off("gauss_synth_device", pop_off, n_pop, "ld", ld)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     const int N = pop_off[n_pop];
     DevBuf b_off, b_thr, b_rho;

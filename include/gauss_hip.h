@@ -364,14 +364,18 @@ int gauss_job_stats(gauss_job* job, double* out4);
 /* Device-side conversion of one-byte genotype rows [n_snp x ld_in] into GAUSS_GENO_2BIT rows [n_snp x ld_out]
  * (population blocks consecutive, 16-byte aligned, zero padded to 64 samples; ld_out >= their total and a
  * multiple of 16).  Both pointers are device pointers.  Used to build a resident row store from rows that are
- * already in HBM (bench plumbing; a packed panel file is uploaded as it is). */
+ * already in HBM (bench plumbing; a packed panel file is uploaded as it is).  The packer keeps the low two bits
+ * of every byte, so the codes must be 0..3 or the ASCII digits '0'..'3'.  pop_off starts at 0 or above and never
+ * decreases, and ld_in >= pop_off[n_pop]: anything else is GAUSS_E_INVALID, and d_out is left as it was. */
 int gauss_pack2bit_device(gauss_ctx* ctx, const uint8_t* d_in, int64_t ld_in, uint8_t* d_out, int64_t ld_out,
                           int n_snp, const int32_t* pop_off, int n_pop);
 
 /* Synthetic genotype generator on the device (bench plumbing; mirrors gauss_amd/synth.py's
  * model with a counter-based RNG).  Writes n_snp rows of n_samples bytes {0,1,2} at d_out with
  * row stride ld.  thr is a host array [n_snp x n_pop] of per-population latent thresholds,
- * rho a host array [n_snp] of AR(1) coefficients. */
+ * rho a host array [n_snp] of AR(1) coefficients (rho[0] is not used).  n_samples = pop_off[n_pop];
+ * pop_off starts at 0 or above and never decreases, and ld >= pop_off[n_pop]: anything else is
+ * GAUSS_E_INVALID, and d_out is left as it was.  Bytes n_samples .. ld of a row are not written. */
 int gauss_synth_device(gauss_ctx* ctx, uint8_t* d_out, int n_snp, int64_t ld,
                        const int32_t* pop_off, int n_pop, const float* thr, const float* rho,
                        uint64_t seed);
