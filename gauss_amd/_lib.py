@@ -21,6 +21,8 @@ WIN_IMPUTE = 0
 WIN_QCAT = 1
 WIN_LD = 2
 GENO_U8, GENO_2BIT = 0, 1
+SLCT_MAX = 32            # GAUSS_SLCT_MAX
+ST_SLCT_SKIPPED = 8      # GAUSS_ST_SLCT_SKIPPED
 CODE_ADDITIVE, CODE_DOMINANT, CODE_RECESSIVE = 1, 2, 4
 GRAM_F32 = 0
 GRAM_I8 = 1
@@ -40,6 +42,9 @@ class WindowDesc(C.Structure):
         ("kind", C.c_int), ("n_head_measured", C.c_int), ("n_pred_measured", C.c_int), ("eig_cutoff", C.c_double),
         ("out_r", _dp), ("out_num_eig", _ip), ("u_codings", C.c_int),
         ("geno_format", C.c_int), ("rows_m", _ip), ("rows_u", _ip), ("pop_src_off", _ip),
+        ("slct_max", C.c_int), ("slct_chi2_stop", C.c_double), ("slct_min_var_frac", C.c_double),
+        ("slct_forced", _ip), ("n_slct_forced", C.c_int), ("out_slct_n", _ip), ("out_slct_idx", _ip),
+        ("out_slct_zin", _dp), ("out_slct_joint", _dp), ("out_slct_zc", _dp), ("out_slct_var", _dp),
         ("out_loo_z", _dp), ("out_loo_info", _dp), ("out_loo_t", _dp),
     ]
 

@@ -47,6 +47,7 @@ HOST_SYMBOLS = [
     "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
+    "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2",
 ]
 
 
@@ -134,6 +135,10 @@ def load_host():
     h.gauss_host_qcat.argtypes = h.gauss_host_dist.argtypes
     h.gauss_host_dist_loo.argtypes = h.gauss_host_dist.argtypes
     h.gauss_host_distmix_loo.argtypes = h.gauss_host_distmix.argtypes
+    slct_tail = [_dbl, _dbl, C.c_int, _strs, C.c_int, C.POINTER(_vp)]      # p_cutoff, collin, max_signals, cond_rsids, n_cond, out
+    h.gauss_host_dist_slct.argtypes = h.gauss_host_dist.argtypes[:-1] + slct_tail
+    h.gauss_host_distmix_slct.argtypes = h.gauss_host_distmix.argtypes[:-1] + slct_tail
+    h.gauss_host_slct_chi2.argtypes = [_dbl, _dp]
     h.gauss_host_qcatmix.argtypes = h.gauss_host_distmix.argtypes
     h.gauss_prepared_qcat_counts.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     h.gauss_host_prepare.argtypes = [C.c_int, C.c_int, _i64, _i64, _i64, _cp, _strs, _dp, C.c_int, _cp, _cp, _cp, _cp, _cp,
@@ -352,6 +357,51 @@ def distmix_loo(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, refere
                                      w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
                                      _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
     return _table(h, out)[0]
+
+
+def _slct_args(p_cutoff, collin, max_signals, cond_rsids):
+    cond = [os.fsencode(r) for r in (cond_rsids or ())]
+    arr = (C.c_char_p * max(len(cond), 1))(*cond)
+    return (0.0 if p_cutoff is None else float(p_cutoff), 0.0 if collin is None else float(collin),
+            0 if max_signals is None else int(max_signals), arr, len(cond))
+
+
+def dist_slct(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
+              reference_pop_desc_file, af1_cutoff=None, p_cutoff=None, collin=None, max_signals=None, cond_rsids=None, ctx=None):
+    """Stepwise conditional signal selection in a dist() window (gauss_host_dist_slct): how many independent signals the window holds.
+    A SNP enters while its conditional p-value is below p_cutoff (None: 5e-8); SNPs whose un-ridged r^2 with the selected set reaches
+    collin (None: 0.9) are not considered; at most max_signals (None: 32) enter; cond_rsids enter first, in their order, whatever
+    their p-value.  One row per measured SNP of the extended window, wings included: rsid chr bp a1 a2 af1ref z wing order z_entry
+    z_joint z_cond pval_cond var_left (include/gauss_host.h)."""
+    h = load_host()
+    out = _vp()
+    _hcheck(h.gauss_host_dist_slct(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
+                                   _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
+                                   _enc(reference_pop_desc_file), _af(af1_cutoff), *_slct_args(p_cutoff, collin, max_signals, cond_rsids),
+                                   C.byref(out)))
+    return _table(h, out)[0]
+
+
+def distmix_slct(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
+                 reference_pop_desc_file, af1_cutoff=None, p_cutoff=None, collin=None, max_signals=None, cond_rsids=None, ctx=None):
+    """Signal selection in a distmix() window (gauss_host_distmix_slct) on the ancestry-weighted LD; columns as dist_slct with af1mix."""
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_distmix_slct(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
+                                      w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
+                                      _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
+                                      *_slct_args(p_cutoff, collin, max_signals, cond_rsids), C.byref(out)))
+    return _table(h, out)[0]
+
+
+def slct_chi2(p):
+    """The chi^2 (1 df) threshold of a two-sided p-value in the library's own normal tail (gauss_host_slct_chi2): the smallest chi2
+    with 2 pnorm(-sqrt(chi2)) < p."""
+    h = load_host()
+    out = C.c_double()
+    _hcheck(h.gauss_host_slct_chi2(float(p), C.byref(out)))
+    return out.value
 
 
 def qcat(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,

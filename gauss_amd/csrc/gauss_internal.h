@@ -124,7 +124,18 @@ struct Prob {
     int row_src_bytes;         // bytes of a source row the resample kernel reads
     // leave-one-out re-imputation of the measured SNPs (k_loo.hip): [3][M] loo_z, loo_info, loo_t in the result block; null: not asked
     GP(double) out_loo;
+    // stepwise conditional signal selection (k_slct.hip); slct_max = 0: not asked
+    int slct_max, n_slct_forced;           // K <= SLCT_K; forced SNPs that enter first
+    double slct_chi2_stop, slct_min_var_frac;
+    GP(const int) slct_forced;             // [n_slct_forced]
+    GP(double) slct_W;                     // [SLCT_K][Mld] scratch: row s = column sel[s] of the partial Cholesky factor
+    GP(double) out_slct;                   // [slct_doubles(M, K)] in the result block: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M]
 };
+constexpr int SLCT_K = 32;             // GAUSS_SLCT_MAX
+constexpr int SLCT_T = 512;            // threads of slct_kernel; a thread keeps the "selected" flags of its SNPs in one 64-bit word
+constexpr int SLCT_M_MAX = 64 * SLCT_T;
+// doubles a window's selection takes in the result block (indices, n and the skipped flag travel as exact doubles)
+constexpr size_t slct_doubles(int M, int K) { return 2 * (size_t)M + 3 * (size_t)K + 2; }
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
 // streams the whole run without draining its load pipeline and flushes the accumulators into one
@@ -229,6 +240,9 @@ void launch_impute_gemm(const Prob* d_probs, const int2* d_gmap, int n_tiles, in
 void launch_solve_last(const Prob* d_probs, const int2* d_panelmap, int n_panels, int max_nblk, int split, hipStream_t s);
 // leave-one-out values of the measured SNPs from [X | y] (k_loo.hip): d_loomap = (window, 64-column panel of X) of the windows that asked
 void launch_loo(const Prob* d_probs, const int2* d_loomap, int n_panels, hipStream_t s);
+// stepwise conditional signal selection on B11 and z1 (k_slct.hip): one workgroup per asking window; d_slctmap = the windows that asked
+// (null: the n windows from d_probs on)
+void launch_slct(const Prob* d_probs, const int* d_slctmap, int n, hipStream_t s);
 void launch_counts(const Prob* d_probs, int prob, int npair, long long* d_out, hipStream_t s);
 void launch_pack2bit(const uint8_t* d_in, long long ld_in, uint8_t* d_out, long long ld_out, int n_snp,
                      const int* d_pop_off, const int* d_blk_off, int n_pop, hipStream_t s);

@@ -265,6 +265,16 @@ struct Plan {
     double* out_loo_z = nullptr;
     double* out_loo_info = nullptr;
     double* out_loo_t = nullptr;
+    int slct_K = 0;                          // signal selection (k_slct.hip): slct_doubles(M, K) behind z / info / loo in the result block; 0: not asked
+    std::vector<int> slct_forced;
+    int32_t* out_slct_n = nullptr;
+    int32_t* out_slct_idx = nullptr;
+    double* out_slct_zin = nullptr;
+    double* out_slct_joint = nullptr;
+    double* out_slct_zc = nullptr;
+    double* out_slct_var = nullptr;
+    size_t res_count() const                 // doubles of this window in the result block
+    { return 2 * (size_t)p.n_rhs + (loo ? 3 * (size_t)p.M : 0) + (slct_K ? slct_doubles(p.M, slct_K) : 0); }
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
     size_t out_ld_count = 0;
@@ -317,6 +327,7 @@ struct gauss_job {
     int2* d_gemmmap = nullptr;  int n_gemm = 0;            // (window, rhs panel of gemm_ut << 8 | k block of 128), longest first
     int gemm_ut = 128;                                     // right-hand sides per tile of the product: 128, small jobs 64
     int2* d_finmap = nullptr;   int n_fin = 0;             // (window, chunk of 256 right-hand sides)
+    int* d_slctmap = nullptr;   int n_slct = 0;            // signal selection: the windows that asked
     int2* d_loomap = nullptr;   int n_loo = 0;             // leave-one-out: (window, 64-column panel of X) of the windows that asked
     int max_nblk = 0;
     int max_npanel = 0;                                    // most solve panels of any one window
@@ -425,6 +436,16 @@ struct WinSpec {
     double* out_loo_z = nullptr;             // leave-one-out values of the measured SNPs (any non-null: the window asks)
     double* out_loo_info = nullptr;
     double* out_loo_t = nullptr;
+    int slct_max = 0;                        // signal selection among the measured SNPs (gauss_window_desc.slct_*); 0: not asked
+    double slct_chi2_stop = 0.0, slct_min_var_frac = 0.0;
+    const int32_t* slct_forced = nullptr;
+    int n_slct_forced = 0;
+    int32_t* out_slct_n = nullptr;
+    int32_t* out_slct_idx = nullptr;
+    double* out_slct_zin = nullptr;
+    double* out_slct_joint = nullptr;
+    double* out_slct_zc = nullptr;
+    double* out_slct_var = nullptr;
     // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample
     // draw_sample[k] of selected population draw_pop[k] and the other n_cols - n_drawn are zero columns
     const int32_t* draw_pop = nullptr;

@@ -188,6 +188,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
         prof_begin(job, 4, st);
         launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);       // the chain has been joined: [X | y] is complete
+        launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);    // (B11 sits in A[0], untouched by the factorisation)
         launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
         prof_end(job, st);
         return job_queue_results(job, par, st);
@@ -225,8 +226,12 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
             launch_solve_last(job->d_probs, job->d_panelmap, job->n_panels, job->max_nblk, job->solve_split, st);
             if (side) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
             launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
+            launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
             launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
-        } else launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
+        } else {
+            launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);      // B11 and z1 are all it reads: it needs no fused solve
+            launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
+        }
         prof_end(job, st);
     }
     return job_queue_results(job, par, st);
@@ -400,6 +405,7 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
     launch_epilogue(job->d_probs, job->d_tilemap + job->n_tiles_b11, job->n_tiles - job->n_tiles_b11, job->max_pop, job->gram_i8, st);
     if (ch != st) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
     launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
+    launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
     launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
     const int rc = job_queue_results(job, (int)(job->run_seq & 1u), st);
     if (rc) return rc;
@@ -436,6 +442,7 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     HIPCHK(hipMemcpyAsync(d_pm.p, pm.data(), sizeof(int2) * pm.size(), hipMemcpyHostToDevice, st));
     if (pl.out_b11) HIPCHK(hipMemcpyAsync(pl.d_b11_copy, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(p.A + 4 * n * n, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));   // W0 = clamped B11
+    if (pl.slct_K) launch_slct(job->d_probs + i, nullptr, 1, st);      // signal selection again, on the REPAIRED B11 in A[0]
     // a window that asked for leave-one-out values: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this
     // factorisation as they do in a run's (same L either way), k_loo.hip reads them, and only then does the stand-alone
     // solve below take V as its scratch
@@ -458,7 +465,7 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     HIPCHK(hipGetLastError());
     int h_status[4];
     HIPCHK(hipMemcpyAsync(h_status, p.status, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(job->h_results + pl.res_off, job->d_results + pl.res_off, sizeof(double) * (2 * (size_t)p.n_rhs + (loo ? 3 * (size_t)p.M : 0)),
+    HIPCHK(hipMemcpyAsync(job->h_results + pl.res_off, job->d_results + pl.res_off, sizeof(double) * pl.res_count(),
                           hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *status_bits = (h_status[2] || h_status[0]) ? GAUSS_ST_NONFINITE : GAUSS_ST_CLAMPED;
@@ -649,7 +656,12 @@ int job_fetch(gauss_job* job)
         if (p.npanel > 0) {
             if (bits & GAUSS_ST_NONFINITE) {
                 // the reference's eigen-solver / LU propagate non-finite values to every output
-                for (size_t u = 0; u < 2 * (size_t)p.U + (pl.loo ? 3 * (size_t)p.M : 0); u++) job->h_results[pl.res_off + u] = NAN;
+                for (size_t u = 0; u < pl.res_count(); u++) job->h_results[pl.res_off + u] = NAN;
+                if (pl.slct_K) {                   // nothing selected: n = 0, no skipped SNP, indices -1
+                    double* sl = job->h_results + pl.res_off + pl.res_count() - slct_doubles(p.M, pl.slct_K);
+                    sl[0] = sl[1] = 0.0;
+                    for (int a = 0; a < pl.slct_K; a++) sl[2 + a] = -1.0;
+                }
             }
             if (pl.out_z) memcpy(pl.out_z, job->h_results + pl.res_off, sizeof(double) * p.U);
             if (pl.out_info) memcpy(pl.out_info, job->h_results + pl.res_off + p.U, sizeof(double) * p.U);
@@ -659,6 +671,18 @@ int job_fetch(gauss_job* job)
                 if (pl.out_loo_z) memcpy(pl.out_loo_z, lo, sizeof(double) * p.M);
                 if (pl.out_loo_info) memcpy(pl.out_loo_info, lo + p.M, sizeof(double) * p.M);
                 if (pl.out_loo_t) memcpy(pl.out_loo_t, lo + 2 * (size_t)p.M, sizeof(double) * p.M);
+            }
+            if (pl.slct_K) {
+                // signal selection (k_slct.hip): n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] behind z / info / loo
+                const int K = pl.slct_K;
+                const double* sl = job->h_results + pl.res_off + pl.res_count() - slct_doubles(p.M, K);
+                if (pl.out_slct_n) *pl.out_slct_n = (int32_t)sl[0];
+                if (sl[1] != 0.0) bits |= GAUSS_ST_SLCT_SKIPPED;
+                if (pl.out_slct_idx) for (int a = 0; a < K; a++) pl.out_slct_idx[a] = (int32_t)sl[2 + a];
+                if (pl.out_slct_zin) memcpy(pl.out_slct_zin, sl + 2 + K, sizeof(double) * K);
+                if (pl.out_slct_joint) memcpy(pl.out_slct_joint, sl + 2 + 2 * (size_t)K, sizeof(double) * K);
+                if (pl.out_slct_zc) memcpy(pl.out_slct_zc, sl + 2 + 3 * (size_t)K, sizeof(double) * p.M);
+                if (pl.out_slct_var) memcpy(pl.out_slct_var, sl + 2 + 3 * (size_t)K + p.M, sizeof(double) * p.M);
             }
             if (pl.out_b11 && (!exporting || clamped))
                 { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }

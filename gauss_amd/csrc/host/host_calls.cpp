@@ -2,6 +2,7 @@
 // distmix.cpp:30-135, qcat.cpp / qcatmix.cpp, prep_qcat.cpp, zmix.cpp:201-1076, jepeg.cpp:28-153, jepegmix.cpp:26-161 with the numeric
 // hot path delegated to libgauss_hip.so.
 #include "host_internal.h"
+#include <functional>
 
 
 // Row store of a call on a packed panel: the resident copy in HBM when there is one, else -- the genotype section is small enough to
@@ -256,12 +257,42 @@ int gauss_prepared_finish(gauss_prepared* p, gauss_table** out)
 // HBM (panel_rows) instead of being gathered on the host and copied per call (24 MB a window), and the window runs as a job of one on
 // those rows.  Measured on the chr22 study, window after window (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.  Otherwise
 // the literal path: prepare_opened + gauss_impute_window on host rows.
+struct SlctAsk { double p_cutoff, collin; int max_signals; const char* const* cond; int n_cond; };      // the extra arguments of the *_slct calls
 static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
                       const char* const* names, const double* wgts, int nw, const char* input, const char* index,
-                      const char* data, const char* desc, double af1_cutoff, gauss_table** out, bool loo = false)
+                      const char* data, const char* desc, double af1_cutoff, gauss_table** out, bool loo = false, const SlctAsk* slct = nullptr)
 {
     if (!ctx || !out) return herr("bad arguments");
     if (files_ok({input, index, data, desc})) return -1;
+    // slct (dist_slct / distmix_slct): the same window and the same single job again, with the slct_* fields of gauss_window_desc set;
+    // the table lists every measured SNP of the extended window (a signal in a wing must be conditioned on, not hidden)
+    std::vector<int32_t> s_idx, s_forced;
+    std::vector<double> s_zin, s_joint, s_zc, s_var;
+    int32_t s_n = 0;
+    auto ask_slct = [&](gauss_window_desc& d, const std::function<const char*(size_t)>& rsid_of) -> int {
+        const int K = slct->max_signals <= 0 ? GAUSS_SLCT_MAX : slct->max_signals;
+        const double collin = slct->collin <= 0 ? 0.9 : slct->collin;
+        if (K > GAUSS_SLCT_MAX) return herr("max_signals = %d: at most %d signals are selected", K, GAUSS_SLCT_MAX);
+        if (slct->n_cond < 0 || (slct->n_cond > 0 && !slct->cond)) return herr("bad cond_rsids");
+        if (slct->n_cond > K) return herr("%d conditioning SNPs, but max_signals = %d", slct->n_cond, K);
+        for (int c = 0; c < slct->n_cond; c++) {
+            int at = -1;
+            for (size_t i = 0; i < (size_t)d.n_measured && at < 0; i++)
+                if (slct->cond[c] && !strcmp(slct->cond[c], rsid_of(i))) at = (int)i;
+            if (at < 0) return herr("cond_rsids: %s is not a measured SNP of the extended window", slct->cond[c] ? slct->cond[c] : "(null)");
+            for (int32_t f : s_forced) if (f == at) return herr("cond_rsids: %s is listed twice", slct->cond[c]);
+            s_forced.push_back(at);
+        }
+        s_idx.assign((size_t)K, -1); s_zin.assign((size_t)K, NAN); s_joint = s_zin;
+        s_zc.assign((size_t)d.n_measured, NAN); s_var = s_zc;
+        d.slct_max = K;
+        d.slct_chi2_stop = slct_chi2_of(slct->p_cutoff <= 0 ? 5e-8 : slct->p_cutoff);
+        d.slct_min_var_frac = 1.0 - collin / ((1.0 + d.lambda) * (1.0 + d.lambda));      // "un-ridged r^2 >= collin" (include/gauss_hip.h)
+        d.slct_forced = s_forced.empty() ? nullptr : s_forced.data(); d.n_slct_forced = (int)s_forced.size();
+        d.out_slct_n = &s_n; d.out_slct_idx = s_idx.data(); d.out_slct_zin = s_zin.data(); d.out_slct_joint = s_joint.data();
+        d.out_slct_zc = s_zc.data(); d.out_slct_var = s_var.data();
+        return 0;
+    };
     // loo (dist_loo / distmix_loo): the same window and the same single job, with the three leave-one-out arrays of
     // gauss_window_desc set; the table lists the measured SNPs of the prediction window instead (the wings only contribute to B11)
     const bool mix = kind == GAUSS_KIND_DISTMIX;
@@ -282,6 +313,7 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
         gauss_window_desc d;                                  // (points into ow.w)
         if (lean_window_desc(ow.w, &d)) return -1;
         if (loo) ask(d);
+        if (slct && ask_slct(d, [&](size_t i) { return ident_of(*pk, ow.w.v[(size_t)ow.w.measured[i]]).rsid; })) return -1;
         int on_device = 0;
         panel_rows(ctx, panel_path, *pk, &d.geno_m, &on_device);
         d.geno_u = d.geno_m;
@@ -304,6 +336,15 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
             *out = loo_output(mix, rows, lz.data(), li.data(), lt.data());
             return 0;
         }
+        if (slct) {
+            std::vector<SlctRow> rows;
+            for (size_t i = 0; i < ow.w.measured.size(); i++) {
+                const LeanSnp& sn = ow.w.v[(size_t)ow.w.measured[i]];
+                rows.push_back(SlctRow{ident_of(*pk, sn), sn.af, sn.z, in_window(sn.bp) ? 0 : 1});
+            }
+            *out = slct_output(mix, rows, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data());
+            return 0;
+        }
         *out = lean_window_finish(ow.w);
         return 0;
     }
@@ -313,7 +354,17 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
     gauss_window_desc d;
     if (gauss_prepared_window_desc(p, &d)) return -1;
     if (loo) ask(d);
+    if (slct && ask_slct(d, [&](size_t i) { return p->measured[i]->rsid.c_str(); })) return -1;
     if (gauss_impute_window(ctx, &d) != 0) return herr("%s", gauss_last_error());
+    if (slct) {
+        std::vector<SlctRow> rows;
+        for (size_t i = 0; i < p->measured.size(); i++) {
+            const Snp& s = *p->measured[i];
+            rows.push_back(SlctRow{ident_of(s), mix ? s.af1mix : s.af1ref, s.z, in_window(s.bp) ? 0 : 1});
+        }
+        *out = slct_output(mix, rows, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data());
+        return 0;
+    }
     if (loo) {
         std::vector<LooRow> rows;
         for (size_t i = 0; i < p->measured.size(); i++) {
@@ -359,6 +410,35 @@ int gauss_host_distmix_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t en
 {
     return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
                       input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, true);
+}
+
+int gauss_host_dist_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                         const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                         const char* reference_pop_desc_file, double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                         const char* const* cond_rsids, int n_cond, gauss_table** out)
+{
+    const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond};
+    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
+                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+}
+
+int gauss_host_distmix_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                            const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                            const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                            double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                            const char* const* cond_rsids, int n_cond, gauss_table** out)
+{
+    const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond};
+    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
+                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+}
+
+int gauss_host_slct_chi2(double p, double* out_chi2)
+{
+    if (!out_chi2) return herr("bad arguments");
+    if (!(p > 0)) return herr("gauss_host_slct_chi2: p must be positive (got %g)", p);
+    *out_chi2 = slct_chi2_of(p);
+    return 0;
 }
 
 int gauss_host_qcat(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,

@@ -94,9 +94,9 @@ struct gauss_table {
         const Column& c = cols[0];
         return (int)(c.type == GAUSS_COL_STR ? c.s.size() : c.type == GAUSS_COL_INT ? c.i.size() : c.d.size());
     }
-    // room for MAX_COLS columns (the widest table, qcat's) is reserved on first use, so the reference add() returns stays valid
-    // while the caller adds the columns that follow
-    enum { MAX_COLS = 12 };
+    // room for MAX_COLS columns (the widest table, the signal selection's 14) is reserved on first use, so the reference add() returns
+    // stays valid while the caller adds the columns that follow
+    enum { MAX_COLS = 16 };
     Column& add(const char* name, int type) { cols.reserve(MAX_COLS); Column c; c.name = name; c.type = type; cols.push_back(std::move(c)); return cols.back(); }
     // a named matrix from column-major data (NamedMat's own layout), taken over without a copy
     void put_named(const char* name, int nrow, int ncol, std::vector<double> colmajor)
@@ -518,6 +518,12 @@ gauss_table* qcat_output(gauss_prepared& p);
 // index into the three leave-one-out arrays of gauss_window_desc)
 struct LooRow { SnpIdent id; double af, z; int idx; };
 gauss_table* loo_output(bool mix, const std::vector<LooRow>& rows, const double* loo_z, const double* loo_info, const double* loo_t);
+// dist_slct / distmix_slct: one row per measured SNP of the EXTENDED window, matrix row order (row i = index i of the selection's arrays)
+struct SlctRow { SnpIdent id; double af, z; int wing; };
+gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, const int32_t* idx, const double* zin, const double* joint,
+                         const double* zc, const double* var_left);
+// the smallest chi^2 (1 df) whose two-sided p-value 2 pnorm_upper(sqrt(chi2)) is below p, to the bit
+double slct_chi2_of(double p);
 gauss_table* prep_output(gauss_prepared& p);
 int panel_make_resident(gauss_ctx* ctx, const std::string& path, void** dev, int64_t* uploaded, bool async = false);
 bool panel_is_resident(gauss_ctx* ctx, const std::string& path, void** dev, bool wait = true);

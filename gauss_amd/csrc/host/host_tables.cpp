@@ -239,6 +239,46 @@ gauss_table* loo_output(bool mix, const std::vector<LooRow>& rows, const double*
     return t;
 }
 
+// rsid chr bp a1 a2 af1ref|af1mix z wing order z_entry z_joint z_cond pval_cond var_left: every measured SNP of the extended window
+// (wing = 1 outside the prediction window: a signal in a wing is conditioned on, not hidden); order = 1 .. n for the selected SNPs in
+// order of entry, 0 otherwise; z_entry / z_joint NaN unless selected; pval_cond = 2 pnorm(-|z_cond|)
+gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, const int32_t* idx, const double* zin, const double* joint,
+                         const double* zc, const double* var_left)
+{
+    gauss_table* t = new gauss_table();
+    add_ident_columns(*t, rows.size(), [&](size_t i) { return rows[i].id; });
+    Column &af = t->add(mix ? "af1mix" : "af1ref", GAUSS_COL_DBL), &z = t->add("z", GAUSS_COL_DBL), &wing = t->add("wing", GAUSS_COL_INT);
+    Column &order = t->add("order", GAUSS_COL_INT), &ze = t->add("z_entry", GAUSS_COL_DBL), &zj = t->add("z_joint", GAUSS_COL_DBL);
+    Column &zcond = t->add("z_cond", GAUSS_COL_DBL), &pval = t->add("pval_cond", GAUSS_COL_DBL), &vl = t->add("var_left", GAUSS_COL_DBL);
+    std::vector<int> ord(rows.size(), 0);
+    for (int a = 0; a < n_sel; a++) ord[(size_t)idx[a]] = a + 1;
+    for (size_t i = 0; i < rows.size(); i++) {
+        const int o = ord[i];
+        af.d.push_back(rows[i].af); z.d.push_back(rows[i].z); wing.i.push_back(rows[i].wing); order.i.push_back(o);
+        ze.d.push_back(o ? zin[o - 1] : NAN); zj.d.push_back(o ? joint[o - 1] : NAN);
+        zcond.d.push_back(zc[i]); pval.d.push_back(2 * pnorm_upper(fabs(zc[i]))); vl.d.push_back(var_left[i]);
+    }
+    return t;
+}
+
+// Positive doubles order as their bit patterns do: bisection on the pattern ends at the last bit that changes the comparison.
+double slct_chi2_of(double p)
+{
+    auto below = [&](double chi2) { return 2 * pnorm_upper(sqrt(chi2)) < p; };
+    if (below(0.0)) return 0.0;                               // p > 1: everything passes
+    double hi_d = 1e5;                                        // (erfc has underflowed to 0 long before: below(hi) holds for every p > 0)
+    uint64_t lo = 0, hi;
+    memcpy(&hi, &hi_d, sizeof(hi));
+    while (hi - lo > 1) {                                     // invariant: !below(lo), below(hi)
+        const uint64_t mid = lo + (hi - lo) / 2;
+        double m;
+        memcpy(&m, &mid, sizeof(m));
+        if (below(m)) hi = mid; else lo = mid;
+    }
+    memcpy(&hi_d, &hi, sizeof(hi));
+    return hi_d;
+}
+
 gauss_table* qcat_output(gauss_prepared& p)     // qcat.cpp:94-131 / qcatmix.cpp:102-139
 {
     const bool mix = p.kind == GAUSS_KIND_QCATMIX;

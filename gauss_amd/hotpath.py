@@ -272,7 +272,7 @@ class _Win:
     """Keeps the numpy buffers of one window alive next to its C descriptor."""
 
     def __init__(self, desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig,
-                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False):
+                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None):
         self.po, self.w = _pops(pop_off, pop_wgt)
         self.z1 = np.ascontiguousarray(z1, dtype=np.float64)
         if dev_ptrs is None:
@@ -315,6 +315,22 @@ class _Win:
         self.loo = np.zeros((3, M)) if loo else None
         if loo:
             desc.out_loo_z, desc.out_loo_info, desc.out_loo_t = (self.loo[k].ctypes.data_as(_dp) for k in range(3))
+        # stepwise conditional signal selection (slct_* of gauss_window_desc): slct=dict(max=, chi2_stop=, collin=, forced=)
+        self.slct = None
+        if slct is not None:
+            K = int(slct.get("max", _lib.SLCT_MAX))
+            self.slct = dict(n=np.zeros(1, dtype=np.int32), idx=np.full(max(K, 0), -1, dtype=np.int32), zin=np.full(max(K, 0), np.nan),
+                             joint=np.full(max(K, 0), np.nan), zc=np.full(M, np.nan), var=np.full(M, np.nan),
+                             forced=np.ascontiguousarray(slct.get("forced", ()), dtype=np.int32))
+            s = self.slct
+            desc.slct_max = K
+            desc.slct_chi2_stop = float(slct.get("chi2_stop", 0.0))
+            # "un-ridged r^2 >= collin" (include/gauss_hip.h); min_var_frac= passes the guard as it is
+            desc.slct_min_var_frac = float(slct["min_var_frac"]) if "min_var_frac" in slct else 1.0 - float(slct.get("collin", 0.9)) / (1.0 + float(lam)) ** 2
+            desc.slct_forced, desc.n_slct_forced = _lib.ptr(s["forced"] if len(s["forced"]) else None, _ip), len(s["forced"])
+            desc.out_slct_n, desc.out_slct_idx = s["n"].ctypes.data_as(_ip), s["idx"].ctypes.data_as(_ip)
+            desc.out_slct_zin, desc.out_slct_joint = s["zin"].ctypes.data_as(_dp), s["joint"].ctypes.data_as(_dp)
+            desc.out_slct_zc, desc.out_slct_var = s["zc"].ctypes.data_as(_dp), s["var"].ctypes.data_as(_dp)
         if packed is not None:
             # packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=): rows taken from a row store (dev_ptrs or
             # geno_m/geno_u give its base pointer and stride), optionally 2-bit packed (include/gauss_hip.h)
@@ -357,17 +373,24 @@ class _Win:
             out["b11"], out["b21"] = self.b11, self.b21
         if self.loo is not None:
             out["loo_z"], out["loo_info"], out["loo_t"] = self.loo[0], self.loo[1], self.loo[2]
+        if self.slct is not None:
+            s, n = self.slct, int(self.slct["n"][0])
+            out.update(slct_n=n, slct_idx=s["idx"][:n].copy(), slct_zin=s["zin"][:n].copy(), slct_joint=s["joint"][:n].copy(),
+                       slct_zc=s["zc"], slct_var=s["var"], slct_raw=dict(idx=s["idx"], zin=s["zin"], joint=s["joint"]))
         return out
 
 
 def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_eig=1e-5,
-                  want_mats=False, ctx=None, loo=False):
+                  want_mats=False, ctx=None, loo=False, slct=None):
     """run_dist (mode 0, dist.cpp:129-227) / run_distmix (mode 1, distmix.cpp:138-253).
     loo=True adds loo_z, loo_info, loo_t [M]: every measured SNP re-imputed from the other measured SNPs, and its
-    standardised residual (include/gauss_hip.h, out_loo_*)."""
+    standardised residual (include/gauss_hip.h, out_loo_*).
+    slct=dict(max=K, chi2_stop=, collin=0.9, forced=[...]) adds the stepwise conditional signal selection among the measured SNPs
+    (include/gauss_hip.h, slct_*): slct_n, slct_idx / slct_zin / slct_joint [n] in order of entry, slct_zc / slct_var [M]; status bit
+    8 when a forced SNP failed the collinearity guard."""
     ctx = ctx or default_context()
     desc = WindowDesc()
-    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo)
+    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct)
     check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
     return win.result()
 
@@ -499,9 +522,10 @@ class Job:
     """A batch of windows sharing every launch (gauss_job_*)."""
 
     def __init__(self, windows, ctx=None, on_device=False, want_mats=False):
-        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo])
+        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct])
         or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
-        loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs)."""
+        loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs).
+        slct=dict(max=, chi2_stop=, collin=, forced=) in a window's dict: its result carries the signal selection (impute_window)."""
         self.ctx = ctx or default_context()
         n = len(windows)
         self.descs = (WindowDesc * n)()
@@ -510,7 +534,7 @@ class Job:
             self.wins.append(_Win(self.descs[i], w["mode"], w.get("geno_m"), w.get("geno_u"),
                                   w["pop_off"], w.get("pop_wgt"), w["z1"], w.get("lam", 0.1),
                                   w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed"),
-                                  loo=bool(w.get("loo", False))))
+                                  loo=bool(w.get("loo", False)), slct=w.get("slct")))
         h = C.c_void_p()
         check(self.ctx.lib.gauss_job_create(self.ctx.handle, self.descs, n, 1 if on_device else 0,
                                             C.byref(h)))

@@ -55,6 +55,7 @@ extern "C" {
 #define GAUSS_ST_CLAMPED    1  /* MakePosDef rebuilt B11 (some eigenvalue < min_abs_eig, util.cpp:310) */
 #define GAUSS_ST_NONFINITE  2  /* B11 not finite / not factorisable: outputs are NaN like the reference's */
 #define GAUSS_ST_NOCONV     4  /* gauss_pop_weights: the Jacobi eigen-clamp hit its sweep cap (outputs NaN, NONFINITE set too) */
+#define GAUSS_ST_SLCT_SKIPPED 8 /* signal selection: a forced SNP failed the collinearity guard and was left out */
 
 typedef struct gauss_ctx gauss_ctx;
 typedef struct gauss_job gauss_job;
@@ -108,6 +109,39 @@ typedef struct gauss_window_desc {
     const int32_t* rows_m;    /* [M] store row of each measured SNP, or NULL          host pointer */
     const int32_t* rows_u;    /* [U] store row of each geno_u SNP, or NULL            host pointer */
     const int32_t* pop_src_off; /* [P] 2-bit format: byte offset of each population block, or NULL */
+    /* ---- stepwise conditional signal selection among the measured SNPs (GAUSS_WIN_IMPUTE windows only) -----------
+     * How many independent signals the window holds: condition on the top SNPs and look at what is left.  With B = B11
+     * (lambda on the diagonal, after MakePosDef if it acted), z = z1 and S the ordered set of selected SNPs, the statistic
+     * of SNP i given S is
+     *   zc_i = (z_i - B_iS B_SS^-1 z_S) / sqrt(B_ii - B_iS B_SS^-1 B_Si).
+     * Selection is greedy: at every step the admissible SNP with the largest zc_i^2 enters (ties: the smallest index; a
+     * NaN never wins), until the largest falls below slct_chi2_stop or slct_max SNPs are in -- a partial Cholesky
+     * factorisation of B whose pivot is the largest conditional chi^2, all in fp64 (k_slct.hip).
+     * The collinearity guard: SNP i is admissible while it is not selected and its variance left,
+     * v_i = B_ii - B_iS B_SS^-1 B_Si, exceeds slct_min_var_frac * B_ii.  The ridge caps what a duplicate SNP can explain:
+     * for two identical rows B_ij = 1 and B_ii = 1 + lambda, so the explained share 1 - v_i / B_ii is 1 / (1 + lambda)^2
+     * (0.826 at lambda = 0.1) and a plain "r^2 >= 0.9" test on it would never fire.  A caller that means "un-ridged
+     * r^2 >= collin" passes slct_min_var_frac = 1 - collin / (1 + lambda)^2 (gauss_host_dist_slct does, collin = 0.9):
+     * for one selected SNP that is exactly the pair's un-ridged r^2 >= collin, for several the same rule applied to the
+     * explained share.
+     * Forced SNPs (slct_forced, window-relative measured indices, distinct) enter first, in the caller's order, whatever
+     * their chi^2; one that fails the guard is left out and sets GAUSS_ST_SLCT_SKIPPED, and it still uses up one of the
+     * slct_max steps.  slct_max == n_slct_forced is a pure conditional analysis on a given list.
+     * slct_max = 0: off.  Every output is optional.  GAUSS_ST_NONFINITE windows return n = 0, indices -1 and NaN;
+     * M = 1 is computed normally (it enters iff z^2 / (1 + lambda) >= slct_chi2_stop).  QCAT and LD windows that set
+     * slct_max, slct_max > GAUSS_SLCT_MAX, a bad forced index and n_measured > 32768 are GAUSS_E_INVALID.
+     * (The block sits in front of the leave-one-out arrays, which stay the descriptor's last three fields.) */
+    int slct_max;             /* K: most SNPs to select; 0 = off; at most GAUSS_SLCT_MAX                            */
+    double slct_chi2_stop;    /* selection stops when the best conditional chi^2 is below this                      */
+    double slct_min_var_frac; /* the collinearity guard (above)                                                     */
+    const int32_t* slct_forced; /* [n_slct_forced] SNPs that enter first, in [0, M), distinct   host pointer / NULL */
+    int n_slct_forced;        /* <= slct_max                                                                        */
+    int32_t* out_slct_n;      /* [1] number of SNPs selected                           host pointer / NULL          */
+    int32_t* out_slct_idx;    /* [slct_max] selected indices in order of entry, -1 beyond n            optional     */
+    double* out_slct_zin;     /* [slct_max] conditional z at entry, NaN beyond n                       optional     */
+    double* out_slct_joint;   /* [slct_max] joint z: (B_SS^-1 z_S)_a / sqrt((B_SS^-1)_aa), NaN beyond n  optional   */
+    double* out_slct_zc;      /* [M] final conditional z, NaN where the SNP is not admissible          optional     */
+    double* out_slct_var;     /* [M] variance left v_i / B_ii, every SNP                               optional     */
     /* ---- leave-one-out re-imputation of the measured SNPs (GAUSS_WIN_IMPUTE windows only) ------------------------
      * The input check of summary-statistics imputation: measured SNP i re-imputed from the other M - 1 measured SNPs of
      * the window, i.e. what run_dist / run_distmix return for SNP i when it is presented as the only unmeasured SNP.  With
@@ -122,6 +156,8 @@ typedef struct gauss_window_desc {
     double* out_loo_info;     /* [M] optional                                          host pointer */
     double* out_loo_t;        /* [M] optional                                          host pointer */
 } gauss_window_desc;
+
+#define GAUSS_SLCT_MAX 32
 
 #define GAUSS_GENO_U8   0
 #define GAUSS_GENO_2BIT 1

@@ -156,6 +156,39 @@ int gauss_host_distmix_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t en
                            const char* reference_data_file, const char* reference_pop_desc_file,
                            double af1_cutoff, gauss_table** out);
 
+/* Stepwise conditional signal selection: how many independent signals a dist() / distmix() window holds.  Same arguments, same
+ * window (wings included), same data layer and the same single job as gauss_host_dist / gauss_host_distmix; the job's window sets the
+ * slct_* fields of gauss_window_desc (include/gauss_hip.h: the statistic, the greedy rule and the collinearity guard), so the
+ * ancestry-weighted B11 of a mixed cohort serves where the usual tools need one homogeneous LD panel.
+ *   p_cutoff     a SNP enters while its conditional two-sided p-value is below this (<= 0: 5e-8); the chi^2 threshold is
+ *                gauss_host_slct_chi2(p_cutoff)
+ *   collin       a SNP whose un-ridged r^2 with the selected set reaches this is not considered (<= 0: 0.9); passed on as
+ *                slct_min_var_frac = 1 - collin / (1 + lambda)^2
+ *   max_signals  at most this many SNPs are selected (<= 0: 32 = GAUSS_SLCT_MAX, the most)
+ *   cond_rsids   n_cond SNPs that enter first, in this order, whatever their p-value (max_signals == n_cond: a pure conditional
+ *                analysis on the list).  One that is not a measured SNP of the extended window is an error that names it.
+ * The table lists EVERY measured SNP of the extended window in the reference's SNP order -- the wings take part: a signal in a wing
+ * must be conditioned on, not hidden -- with columns rsid chr bp a1 a2 af1ref|af1mix z wing order z_entry z_joint z_cond pval_cond
+ * var_left: wing 1 outside [start_bp, end_bp]; order 1 .. n for the selected SNPs in order of entry, else 0; z_entry the conditional z
+ * at entry and z_joint the joint z of the selected SNPs (NaN unless selected); z_cond the z given all selected SNPs (NaN for the
+ * selected SNPs and those the guard excludes), pval_cond = 2 pnorm(-|z_cond|); var_left the share of the SNP's variance the
+ * selected SNPs leave.  A window without unmeasured SNPs is refused, as by dist() / distmix(). */
+int gauss_host_dist_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                         const char* study_pop, const char* input_file, const char* reference_index_file,
+                         const char* reference_data_file, const char* reference_pop_desc_file,
+                         double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                         const char* const* cond_rsids, int n_cond, gauss_table** out);
+int gauss_host_distmix_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                            const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                            const char* input_file, const char* reference_index_file,
+                            const char* reference_data_file, const char* reference_pop_desc_file,
+                            double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                            const char* const* cond_rsids, int n_cond, gauss_table** out);
+/* The chi^2 (1 df) threshold of a two-sided p-value: the smallest double chi2 with 2 pnorm(-sqrt(chi2)) < p in the library's own
+ * normal tail, found by bisection on the bit pattern -- monotone in p, and exact to the last bit that changes the comparison.
+ * p must be positive. */
+int gauss_host_slct_chi2(double p, double* out_chi2);
+
 /* QCAT / QCATMIX: same feeder as dist / distmix, the window core is
  * run_qcat (qcat.cpp:134-262) / run_qcatmix (qcatmix.cpp:144-297).  af1_cutoff NaN -> 0.05 for qcat
  * (qcat.cpp:53-57), 0.01 for qcatmix (qcatmix.cpp:61-65).  Output columns: rsid chr bp a1 a2
