@@ -22,6 +22,8 @@ static int seg_max_for(const std::vector<WinSpec>& specs)
     // (below that the epilogue's reads of the partial slabs cost what the Gram launch gains).  Measured on that window, Gram
     // launch / LD epilogue in us: 2048: 196 / 59 (46 TFLOP/s); 1024: 154 / 67; 768: 140 / 69; 512: 127 / 74; 384: 120 / 81
     // (75 TFLOP/s); 256: 116 / 92.  Any cut is exact (integer partial sums); listed-pair and gene jobs keep 2 048.
+    // (tests/percor_ref.py restates this rule and plan_problem's cut -- 1 300, 384, 2 048, the chunk arithmetic -- to place its
+    // population tables on the cuts: change them together, or its multi-segment cases quietly become single-segment ones.)
     double pairs = 0, kp = 0;
     for (const WinSpec& w : specs) {
         if (w.gene_off || w.pair_i || w.M < 1 || w.n_pop < 1 || w.n_pop > 64 || !w.pop_off) return SEG_MAX;      // (plan_problem reports what is wrong)
