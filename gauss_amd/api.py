@@ -48,6 +48,7 @@ HOST_SYMBOLS = [
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2",
+    "gauss_host_dist_traits", "gauss_host_distmix_traits",
 ]
 
 
@@ -139,6 +140,9 @@ def load_host():
     h.gauss_host_dist_slct.argtypes = h.gauss_host_dist.argtypes[:-1] + slct_tail
     h.gauss_host_distmix_slct.argtypes = h.gauss_host_distmix.argtypes[:-1] + slct_tail
     h.gauss_host_slct_chi2.argtypes = [_dbl, _dp]
+    traits_tail = [_strs, C.c_int, C.POINTER(_vp)]                           # more_input_files, n_more, out
+    h.gauss_host_dist_traits.argtypes = h.gauss_host_dist.argtypes[:-1] + traits_tail
+    h.gauss_host_distmix_traits.argtypes = h.gauss_host_distmix.argtypes[:-1] + traits_tail
     h.gauss_host_qcatmix.argtypes = h.gauss_host_distmix.argtypes
     h.gauss_prepared_qcat_counts.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     h.gauss_host_prepare.argtypes = [C.c_int, C.c_int, _i64, _i64, _i64, _cp, _strs, _dp, C.c_int, _cp, _cp, _cp, _cp, _cp,
@@ -425,6 +429,54 @@ def qcatmix(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_
                                  w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
                                  _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
     return _table(h, out)[0]
+
+
+def _traits_files(input_files):
+    files = [os.fsencode(f) for f in input_files]
+    if not files:
+        raise ValueError("input_files: at least the first trait's study file")
+    more = files[1:]
+    return files[0], (C.c_char_p * max(len(more), 1))(*more), len(more)
+
+
+def _traits_frame(h, out):
+    """The trait-1 frame with z_2, pval_2, ..., z_T, pval_T appended (the named matrices z_traits / pval_traits, column 0 = z / pval)."""
+    named = _named(h, out)
+    df = _table(h, out)[0]
+    z, pv = (np.asarray(named[k]).reshape(len(df), -1) for k in ("z_traits", "pval_traits"))
+    for k in range(1, z.shape[1]):
+        df[f"z_{k + 1}"], df[f"pval_{k + 1}"] = z[:, k], pv[:, k]
+    return df
+
+
+def dist_traits(chr, start_bp, end_bp, wing_size, study_pop, input_files, reference_index_file, reference_data_file,
+                reference_pop_desc_file, af1_cutoff=None, ctx=None):
+    """dist() for many traits measured at the same SNPs, from ONE LD build and one factorisation (gauss_host_dist_traits).
+    input_files: a list of study files (rsid chr bp a1 a2 z), at most 64; the first is trait 1 and defines the window, the measured
+    set, the allele orientation and the AF filter exactly as dist() does.  Every measured SNP of the extended window must be in each
+    further file (swapped alleles flip the sign, a key listed twice ends with its later row, other rows are ignored).  Returns dist()'s
+    frame of trait 1 with columns z_2, pval_2, ..., z_T, pval_T appended: a measured SNP's own study z, an unmeasured SNP's imputed z
+    (info is shared)."""
+    h = load_host()
+    first, more, n_more = _traits_files(input_files)
+    out = _vp()
+    _hcheck(h.gauss_host_dist_traits(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop), first,
+                                     _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file),
+                                     _af(af1_cutoff), more, n_more, C.byref(out)))
+    return _traits_frame(h, out)
+
+
+def distmix_traits(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_files, reference_index_file, reference_data_file,
+                   reference_pop_desc_file, af1_cutoff=None, ctx=None):
+    """distmix() for many traits measured at the same SNPs (gauss_host_distmix_traits); input_files and the frame as dist_traits."""
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    first, more, n_more = _traits_files(input_files)
+    out = _vp()
+    _hcheck(h.gauss_host_distmix_traits(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
+                                        w.ctypes.data_as(_dp), n, first, _enc(reference_index_file), _enc(reference_data_file),
+                                        _enc(reference_pop_desc_file), _af(af1_cutoff), more, n_more, C.byref(out)))
+    return _traits_frame(h, out)
 
 
 def _named(h, t):

@@ -130,7 +130,15 @@ struct Prob {
     GP(const int) slct_forced;             // [n_slct_forced]
     GP(double) slct_W;                     // [SLCT_K][Mld] scratch: row s = column sel[s] of the partial Cholesky factor
     GP(double) out_slct;                   // [slct_doubles(M, K)] in the result block: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M]
+    // further traits on the same window (k_traits.hip); traits_T = 0: not asked
+    int traits_T;                          // T <= TRAITS_MAX further Z-score vectors
+    GP(const double) traits_Z;             // [Mld][T16] their Z-scores, SNP-major, zero beyond M and T (T16 = T rounded up to 16)
+    GP(double) traits_Y;                   // [Mld][T16] scratch: Y = X Z
+    GP(double) traits_G;                   // [Mld][T16] scratch: G = X^T Y = B11^-1 Z
+    GP(double) out_traits;                 // [T][U] in the result block
 };
+constexpr int TRAITS_MAX = 63;         // GAUSS_TRAITS_MORE_MAX
+constexpr int traits_t16(int T) { return (T + 15) & ~15; }
 constexpr int SLCT_K = 32;             // GAUSS_SLCT_MAX
 constexpr int SLCT_T = 512;            // threads of slct_kernel; a thread keeps the "selected" flags of its SNPs in one 64-bit word
 constexpr int SLCT_M_MAX = 64 * SLCT_T;
@@ -243,6 +251,11 @@ void launch_loo(const Prob* d_probs, const int2* d_loomap, int n_panels, hipStre
 // stepwise conditional signal selection on B11 and z1 (k_slct.hip): one workgroup per asking window; d_slctmap = the windows that asked
 // (null: the n windows from d_probs on)
 void launch_slct(const Prob* d_probs, const int* d_slctmap, int n, hipStream_t s);
+// further traits (k_traits.hip).  launch_traits_weights: G = X^T (X Z) of the windows that asked, d_map = (window, 64-row block of X),
+// two launches (Y = X Z, then G = X^T Y); it runs where launch_loo runs.  launch_traits_impute: out_traits = B21 G / sqrt(out_info),
+// d_umap = (window, strip of 64 unmeasured SNPs); it runs behind the kernel that writes out_info
+void launch_traits_weights(const Prob* d_probs, const int2* d_map, int n_blocks, hipStream_t s);
+void launch_traits_impute(const Prob* d_probs, const int2* d_umap, int n_strips, hipStream_t s);
 void launch_counts(const Prob* d_probs, int prob, int npair, long long* d_out, hipStream_t s);
 void launch_pack2bit(const uint8_t* d_in, long long ld_in, uint8_t* d_out, long long ld_out, int n_snp,
                      const int* d_pop_off, const int* d_blk_off, int n_pop, hipStream_t s);

@@ -273,8 +273,11 @@ struct Plan {
     double* out_slct_joint = nullptr;
     double* out_slct_zc = nullptr;
     double* out_slct_var = nullptr;
+    int traits_T = 0;                        // further traits (k_traits.hip): [T][U] behind z / info / loo, in front of the selection; 0: not asked
+    std::vector<double> traits_z;            // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
+    double* out_z_more = nullptr;
     size_t res_count() const                 // doubles of this window in the result block
-    { return 2 * (size_t)p.n_rhs + (loo ? 3 * (size_t)p.M : 0) + (slct_K ? slct_doubles(p.M, slct_K) : 0); }
+    { return 2 * (size_t)p.n_rhs + (loo ? 3 * (size_t)p.M : 0) + (size_t)traits_T * p.U + (slct_K ? slct_doubles(p.M, slct_K) : 0); }
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
     size_t out_ld_count = 0;
@@ -328,6 +331,8 @@ struct gauss_job {
     int gemm_ut = 128;                                     // right-hand sides per tile of the product: 128, small jobs 64
     int2* d_finmap = nullptr;   int n_fin = 0;             // (window, chunk of 256 right-hand sides)
     int* d_slctmap = nullptr;   int n_slct = 0;            // signal selection: the windows that asked
+    int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
+    int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
     int2* d_loomap = nullptr;   int n_loo = 0;             // leave-one-out: (window, 64-column panel of X) of the windows that asked
     int max_nblk = 0;
     int max_npanel = 0;                                    // most solve panels of any one window
@@ -436,6 +441,9 @@ struct WinSpec {
     double* out_loo_z = nullptr;             // leave-one-out values of the measured SNPs (any non-null: the window asks)
     double* out_loo_info = nullptr;
     double* out_loo_t = nullptr;
+    int n_traits_more = 0;                   // further traits on the same window (gauss_window_desc.n_traits_more); 0: not asked
+    const double* z_more = nullptr;          // [T x M]
+    double* out_z_more = nullptr;            // [T x U]
     int slct_max = 0;                        // signal selection among the measured SNPs (gauss_window_desc.slct_*); 0: not asked
     double slct_chi2_stop = 0.0, slct_min_var_frac = 0.0;
     const int32_t* slct_forced = nullptr;

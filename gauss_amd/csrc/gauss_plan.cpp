@@ -104,6 +104,16 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
                     return fail(GAUSS_E_INVALID, "slct_forced[%d] = slct_forced[%d] = %d: forced SNPs must be distinct", b, a, (int)w.slct_forced[a]);
         }
     }
+    // further traits ride on the window's LD and on the rows of L^-1 its solve leaves behind (k_traits.hip)
+    if (w.n_traits_more < 0 || w.n_traits_more > TRAITS_MAX)
+        return fail(GAUSS_E_INVALID, "n_traits_more = %d: a window takes 0 .. %d further traits", w.n_traits_more, TRAITS_MAX);
+    if (w.n_traits_more > 0) {
+        if (w.ld_only || w.kind != GAUSS_WIN_IMPUTE)
+            return fail(GAUSS_E_INVALID, "further traits (n_traits_more) are for imputation windows only (%s window)",
+                        w.kind == GAUSS_WIN_QCAT ? "QCAT" : "LD");
+        if (!w.z_more || !w.out_z_more)
+            return fail(GAUSS_E_INVALID, "n_traits_more = %d needs z_more and out_z_more (%s is NULL)", w.n_traits_more, !w.z_more ? "z_more" : "out_z_more");
+    }
 
     Prob& p = pl.p;
     memset(&p, 0, sizeof(p));
@@ -322,6 +332,16 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         p.slct_max = w.slct_max; p.n_slct_forced = w.n_slct_forced;
         p.slct_chi2_stop = w.slct_chi2_stop; p.slct_min_var_frac = w.slct_min_var_frac;
     }
+    pl.traits_T = w.n_traits_more; pl.out_z_more = w.out_z_more;
+    pl.traits_z.clear();
+    if (w.n_traits_more > 0) {
+        // SNP-major and padded to the kernels' tiles: row g = the T traits' Z-scores at measured SNP g
+        const int T16 = traits_t16(w.n_traits_more);
+        pl.traits_z.assign((size_t)p.Mld * T16, 0.0);
+        for (int t = 0; t < w.n_traits_more; t++)
+            for (int g = 0; g < w.M; g++) pl.traits_z[(size_t)g * T16 + t] = w.z_more[(size_t)t * w.M + g];
+        p.traits_T = w.n_traits_more;
+    }
     pl.out_slct_n = w.out_slct_n; pl.out_slct_idx = w.out_slct_idx; pl.out_slct_zin = w.out_slct_zin;
     pl.out_slct_joint = w.out_slct_joint; pl.out_slct_zc = w.out_slct_zc; pl.out_slct_var = w.out_slct_var;
     return GAUSS_OK;
@@ -452,7 +472,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             q.M = (int)gl.size(); q.U = 0; q.U_raw = 1; q.n_rhs = 0;
             q.Mp = (int)rup((size_t)q.M, TILE); q.Up = 0; q.Sp = q.Mp; q.nT = q.Mp / TILE;
             q.Mld = 0; q.nblk = 0; q.npanel = 0; q.npi = 0; q.kind = 0; q.ld_only = 0; q.n_head = q.n_predm = 0;
-            g.U_user = 0; g.h_geno_u = nullptr; g.loo = false; g.slct_K = 0; g.slct_forced.clear(); q.slct_max = 0;
+            g.U_user = 0; g.h_geno_u = nullptr; g.loo = false; g.slct_K = 0; g.slct_forced.clear(); q.slct_max = 0; g.traits_T = 0; g.traits_z.clear(); q.traits_T = 0;
             // job-wide B11 pairs: the tile pairs some window lies in
             g.pair_ti.clear(); g.pair_tj.clear(); g.pair_lut.assign((size_t)q.nT * q.nT, -1);
             for (int i = 0; i < job->n; i++) {
@@ -511,7 +531,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<char>& blob = job->h_tab;
     blob.reserve((size_t)n_prob * ((size_t)320 << 10) + ((size_t)64 << 10));      // (~0.3 MB a window: grown in place, not copied over and over)
     const auto tb2 = std::chrono::steady_clock::now();
-    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch, dc, sf; };
+    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch, dc, sf, tz; };
     std::vector<TabOff> to((size_t)n_prob);
     for (int i = 0; i < n_prob; i++) {
         Plan& pl = plan_of(i);
@@ -539,6 +559,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         to[i].ch = put(blob, ta, pl.chunk_live);
         to[i].dc = put(blob, ta, pl.draw_col);
         to[i].sf = pl.slct_forced.empty() ? 0 : put(blob, ta, pl.slct_forced);
+        to[i].tz = pl.traits_z.empty() ? 0 : put(blob, ta, pl.traits_z);
     }
     // work lists
     struct ItemH { int prob, pair, group, len, b11, ord = 0; };     // b11: an item of B11 (job-wide pairs, or a window's own measured x measured pairs); ord: launch-order key (below)
@@ -546,6 +567,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
     std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
     std::vector<int> slctmap;
+    std::vector<int2> traitsmap, traitsumap;
     job->max_nblk = 0;
     {
         // tiles of the closing product at 128 right-hand sides each: a small job (an 8-rank share: ~570) cannot fill the
@@ -615,6 +637,10 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (job->plans[i].loo)
             for (int pn = 0; pn < (p.M + NR - 1) / NR; pn++) loomap.push_back(make_int2(i, pn));      // the panels that hold columns of X
         if (job->plans[i].slct_K) slctmap.push_back(i);
+        if (job->plans[i].traits_T) {
+            for (int b = 0; b < p.nblk; b++) traitsmap.push_back(make_int2(i, b));
+            for (int us = 0; us < (p.U + NB - 1) / NB; us++) traitsumap.push_back(make_int2(i, us));
+        }
         if (p.npanel > 0) {
             job->max_nblk = std::max(job->max_nblk, p.nblk); job->max_npanel = std::max(job->max_npanel, p.npi);
             for (int up = 0; up < p.Up128 / job->gemm_ut; up++)
@@ -819,6 +845,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     const size_t o_finmap = put(blob, ta, finmap);
     const size_t o_loomap = put(blob, ta, loomap);
     const size_t o_slctmap = slctmap.empty() ? 0 : put(blob, ta, slctmap);      // (a job in which nobody asks takes nothing)
+    const size_t o_traitsmap = traitsmap.empty() ? 0 : put(blob, ta, traitsmap);
+    const size_t o_traitsumap = traitsumap.empty() ? 0 : put(blob, ta, traitsumap);
     const size_t o_probs = ta.take(sizeof(Prob) * (size_t)n_prob);
     const size_t o_exports = ta.take(sizeof(ExportD) * std::max<size_t>(job->exports.size(), 1));
     blob.resize(ta.off);
@@ -831,11 +859,13 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n_fin = (int)finmap.size();
     job->n_loo = (int)loomap.size();
     job->n_slct = (int)slctmap.size();
+    job->n_traits = (int)traitsmap.size();
+    job->n_traits_u = (int)traitsumap.size();
 
     // ---- workspace arena ----
     Arena wa;         // zeroed once per job: operand padding, B21 padding and the solve matrices rely on it
     Arena wslab;      // partial slabs: every entry a reader keeps is written by the Gram kernel first, so no zeroing
-    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct; long long ldraw; };
+    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct, ty, tg; long long ldraw; };
     std::vector<WsOff> wo(job->n);
     size_t res = 0;
     {
@@ -891,9 +921,14 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             w.b11c = wa.take((size_t)p.Mld * p.Mld * sizeof(double));
         }
         w.slct = pl.slct_K ? wa.take((size_t)SLCT_K * p.Mld * sizeof(double)) : 0;      // the selected columns of the partial factor
+        w.ty = w.tg = 0;
+        if (pl.traits_T) {                  // Y = X Z and G = X^T Y of the further traits
+            w.ty = wa.take((size_t)p.Mld * traits_t16(pl.traits_T) * sizeof(double));
+            w.tg = wa.take((size_t)p.Mld * traits_t16(pl.traits_T) * sizeof(double));
+        }
         w.ld = wa.take(std::max<size_t>(pl.out_ld_count, 1) * sizeof(double));
         pl.res_off = res;
-        res += pl.res_count();      // z, info [, loo_z, loo_info, loo_t] [, the selection]
+        res += pl.res_count();      // z, info [, loo_z, loo_info, loo_t] [, the further traits] [, the selection]
     }
     // job-wide measured rows (shared measured rows): one more tile of rows than Mp, because a window's last row tile
     // starts wherever the window starts and may reach past the chromosome's last measured SNP (zero rows there)
@@ -1035,6 +1070,10 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.out_loo = pl.loo ? job->d_results + pl.res_off + 2 * (size_t)p.n_rhs : nullptr;
         p.out_slct = pl.slct_K ? job->d_results + pl.res_off + pl.res_count() - slct_doubles(p.M, pl.slct_K) : nullptr;
         p.slct_W = pl.slct_K ? (double*)(W + w.slct) : nullptr;
+        p.out_traits = pl.traits_T ? job->d_results + pl.res_off + 2 * (size_t)p.n_rhs + (pl.loo ? 3 * (size_t)p.M : 0) : nullptr;
+        p.traits_Z = pl.traits_T ? (const double*)(T + to[i].tz) : nullptr;
+        p.traits_Y = pl.traits_T ? (double*)(W + w.ty) : nullptr;
+        p.traits_G = pl.traits_T ? (double*)(W + w.tg) : nullptr;
         p.slct_forced = pl.slct_forced.empty() ? nullptr : (const int*)(T + to[i].sf);
         p.status = job->d_status + 4 * i;
         p.out_ld = (double*)(W + w.ld);
@@ -1107,7 +1146,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         q.run_pk_off = (const int*)(T + to[n].rpk); q.run_src = (const int*)(T + to[n].rsrc);
         q.slab = (float*)(W + go.slab); q.slab_g = q.slab; q.gpair_ti = q.pair_ti; q.gpair_tj = q.pair_tj; q.g0 = 0; q.n_gpair = q.npair;
         q.z1 = nullptr; q.A = nullptr; q.B21 = nullptr; q.Linv = nullptr; q.V = nullptr; q.Gsum = nullptr; q.Part = nullptr;
-        q.out_z = q.out_info = nullptr; q.out_loo = nullptr; q.out_slct = nullptr; q.slct_W = nullptr; q.slct_forced = nullptr; q.slct_max = 0; q.out_ld = nullptr; q.status = job->d_status;      // never written for this descriptor
+        q.out_z = q.out_info = nullptr; q.out_loo = nullptr; q.out_slct = nullptr; q.slct_W = nullptr; q.slct_forced = nullptr; q.slct_max = 0; q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr; q.out_ld = nullptr; q.status = job->d_status;      // never written for this descriptor
         q.gene_off = nullptr; q.gene_out_off = nullptr; q.n_gene = 0;
         memcpy(blob.data() + o_probs + sizeof(Prob) * n, &q, sizeof(Prob));
     }
@@ -1170,6 +1209,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->d_finmap = (int2*)(job->d_tab + o_finmap);
     job->d_loomap = (int2*)(job->d_tab + o_loomap);
     job->d_slctmap = (int*)(job->d_tab + o_slctmap);
+    job->d_traitsmap = (int2*)(job->d_tab + o_traitsmap);
+    job->d_traitsumap = (int2*)(job->d_tab + o_traitsumap);
     job->d_exports = (ExportD*)(job->d_tab + o_exports);
     if (!on_device && !streamed) HIPCHK(hipStreamSynchronize(st));   // uploads from pageable user memory are complete
     std::vector<char>().swap(job->h_tab);

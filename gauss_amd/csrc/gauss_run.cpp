@@ -108,8 +108,8 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
     // fused tail: the factorisation chain needs B11 only and the closing product is the first reader of B21, so B21's
     // tiles of the epilogue (85 % of them) go to the side stream and run beside the chain
     // (a job with a window that asks for leave-one-out values always takes the fused form: they are read off the rows of L^-1 that
-    // only the fused solve forms, k_loo.hip)
-    const bool fused = env_int("GAUSS_FUSED_SOLVE", 1) != 0 || job->n_loo > 0;           // read per run: the tests drive both forms
+    // only the fused solve forms, k_loo.hip; so does a job with a window that carries further traits, k_traits.hip)
+    const bool fused = env_int("GAUSS_FUSED_SOLVE", 1) != 0 || job->n_loo > 0 || job->n_traits > 0;           // read per run: the tests drive both forms
     hipStream_t side = (solve && fused && job->n_panels > 0 && job->n_tiles > job->n_tiles_b11) ? ctx->side : nullptr;
     prof_begin(job, 1, st);
     if (job->resample_lds >= 0) launch_resample_pack(job->d_probs, job->d_rowmap, job->n_rows, job->resample_lds, st);
@@ -189,7 +189,9 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         prof_begin(job, 4, st);
         launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);       // the chain has been joined: [X | y] is complete
         launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);    // (B11 sits in A[0], untouched by the factorisation)
+        launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
         launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
+        launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);      // behind the finish kernel: it divides by its info
         prof_end(job, st);
         return job_queue_results(job, par, st);
     }
@@ -227,7 +229,9 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
             if (side) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
             launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
             launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
+            launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
             launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
+            launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
         } else {
             launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);      // B11 and z1 are all it reads: it needs no fused solve
             launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
@@ -406,7 +410,9 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
     if (ch != st) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
     launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
     launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
+    launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
     launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
+    launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
     const int rc = job_queue_results(job, (int)(job->run_seq & 1u), st);
     if (rc) return rc;
     job->run_seq++;
@@ -446,22 +452,28 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     // a window that asked for leave-one-out values: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this
     // factorisation as they do in a run's (same L either way), k_loo.hip reads them, and only then does the stand-alone
     // solve below take V as its scratch
-    const bool loo = pl.loo;
+    // (a window that carries further traits needs the same rows: G = X^T (X Z) is formed before the solve takes V, and B21 G is
+    // divided by the info the solve leaves -- the stand-alone solve only reads B21)
+    const bool loo = pl.loo, traits = pl.traits_T > 0, ride = loo || traits;
     for (int s = 0; s < p.nblk; s++) {
         // launch over all problems would redo the others; use a single-problem launch instead
-        launch_factor_step(job->d_probs + i, 1, s, p.nblk, loo ? p.npi : 0, loo ? job->solve_split : 0, 0, st);
+        launch_factor_step(job->d_probs + i, 1, s, p.nblk, ride ? p.npi : 0, ride ? job->solve_split : 0, 0, st);
     }
-    if (loo) {
+    const int n_us = (p.U + NB - 1) / NB;                    // strips of unmeasured SNPs of the further traits' product
+    if (ride) {
+        // (window, 0 .. n): read as panels by solve_last / loo, as blocks of X and as strips of unmeasured SNPs by the traits kernels
         std::vector<int2> lm;
-        for (int pn = 0; pn < p.npi; pn++) lm.push_back(make_int2(i, pn));
+        for (int pn = 0; pn < std::max(p.npi, traits ? n_us : 0); pn++) lm.push_back(make_int2(i, pn));
         const int n_x = (p.M + NR - 1) / NR;                 // the panels that hold columns of X come first
         HIPCHK(d_lm.alloc(job->ctx, sizeof(int2) * lm.size()));
         HIPCHK(hipMemcpyAsync(d_lm.p, lm.data(), sizeof(int2) * lm.size(), hipMemcpyHostToDevice, st));
-        launch_solve_last(job->d_probs, d_lm.as<int2>(), (int)lm.size(), p.nblk, job->solve_split, st);
-        launch_loo(job->d_probs, d_lm.as<int2>(), n_x, st);
+        launch_solve_last(job->d_probs, d_lm.as<int2>(), p.npi, p.nblk, job->solve_split, st);
+        if (loo) launch_loo(job->d_probs, d_lm.as<int2>(), n_x, st);
+        if (traits) launch_traits_weights(job->d_probs, d_lm.as<int2>(), p.nblk, st);
         HIPCHK(hipStreamSynchronize(st));                    // (`lm` is pageable: the copy has read it)
     }
     launch_solve(job->d_probs, d_pm.as<int2>(), (int)pm.size(), st);
+    if (traits) launch_traits_impute(job->d_probs, d_lm.as<int2>(), n_us, st);
     HIPCHK(hipGetLastError());
     int h_status[4];
     HIPCHK(hipMemcpyAsync(h_status, p.status, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
@@ -672,6 +684,8 @@ int job_fetch(gauss_job* job)
                 if (pl.out_loo_info) memcpy(pl.out_loo_info, lo + p.M, sizeof(double) * p.M);
                 if (pl.out_loo_t) memcpy(pl.out_loo_t, lo + 2 * (size_t)p.M, sizeof(double) * p.M);
             }
+            if (pl.traits_T && pl.out_z_more)      // the further traits (k_traits.hip): [T][U] behind z / info / loo
+                memcpy(pl.out_z_more, job->h_results + pl.res_off + 2 * (size_t)p.U + (pl.loo ? 3 * (size_t)p.M : 0), sizeof(double) * pl.traits_T * p.U);
             if (pl.slct_K) {
                 // signal selection (k_slct.hip): n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] behind z / info / loo
                 const int K = pl.slct_K;

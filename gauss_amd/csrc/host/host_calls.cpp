@@ -258,12 +258,35 @@ int gauss_prepared_finish(gauss_prepared* p, gauss_table** out)
 // those rows.  Measured on the chr22 study, window after window (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.  Otherwise
 // the literal path: prepare_opened + gauss_impute_window on host rows.
 struct SlctAsk { double p_cutoff, collin; int max_signals; const char* const* cond; int n_cond; };      // the extra arguments of the *_slct calls
+struct TraitsAsk { const char* const* files; int n; };                                                  // ... of the *_traits calls
 static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
                       const char* const* names, const double* wgts, int nw, const char* input, const char* index,
-                      const char* data, const char* desc, double af1_cutoff, gauss_table** out, bool loo = false, const SlctAsk* slct = nullptr)
+                      const char* data, const char* desc, double af1_cutoff, gauss_table** out, bool loo = false, const SlctAsk* slct = nullptr,
+                      const TraitsAsk* traits = nullptr)
 {
     if (!ctx || !out) return herr("bad arguments");
     if (files_ok({input, index, data, desc})) return -1;
+    // traits (dist_traits / distmix_traits): `input` is trait 1 and defines the window exactly as in the plain call; every further file
+    // is matched to the window's measured SNPs (traits_match) and rides in the same single job as n_traits_more / z_more of
+    // gauss_window_desc; the table is the plain call's with the named matrices z_traits / pval_traits added (traits_output)
+    std::vector<double> t_z, t_out;
+    auto ask_traits = [&](gauss_window_desc& d, const std::function<SnpIdent(size_t)>& at) -> int {
+        const size_t M = (size_t)d.n_measured, U = (size_t)d.n_unmeasured;
+        t_z.assign((size_t)traits->n * M, 0.0); t_out.assign((size_t)traits->n * U, 0.0);
+        for (int k = 0; k < traits->n; k++) {
+            std::string err;
+            std::shared_ptr<const GwasCache> gw = load_gwas_cached(traits->files[k], err);
+            if (!gw) return herr("%s", err.c_str());
+            if (traits_match(*gw, traits->files[k], M, at, t_z.data() + (size_t)k * M)) return -1;
+        }
+        if (traits->n > 0) { d.n_traits_more = traits->n; d.z_more = t_z.data(); d.out_z_more = t_out.data(); }
+        return 0;
+    };
+    if (traits) {
+        if (traits->n < 0 || (traits->n > 0 && !traits->files)) return herr("bad more_input_files");
+        if (traits->n > GAUSS_TRAITS_MORE_MAX) return herr("%d further traits: a call takes at most %d", traits->n, GAUSS_TRAITS_MORE_MAX);
+        for (int k = 0; k < traits->n; k++) if (files_ok({traits->files[k]})) return -1;
+    }
     // slct (dist_slct / distmix_slct): the same window and the same single job again, with the slct_* fields of gauss_window_desc set;
     // the table lists every measured SNP of the extended window (a signal in a wing must be conditioned on, not hidden)
     std::vector<int32_t> s_idx, s_forced;
@@ -314,6 +337,7 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
         if (lean_window_desc(ow.w, &d)) return -1;
         if (loo) ask(d);
         if (slct && ask_slct(d, [&](size_t i) { return ident_of(*pk, ow.w.v[(size_t)ow.w.measured[i]]).rsid; })) return -1;
+        if (traits && ask_traits(d, [&](size_t i) { return ident_of(*pk, ow.w.v[(size_t)ow.w.measured[i]]); })) return -1;
         int on_device = 0;
         panel_rows(ctx, panel_path, *pk, &d.geno_m, &on_device);
         d.geno_u = d.geno_m;
@@ -346,6 +370,12 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
             return 0;
         }
         *out = lean_window_finish(ow.w);
+        if (traits) {
+            std::vector<int32_t> row_m, row_u;
+            for (int32_t vi : ow.w.measured) row_m.push_back(ow.w.out_row[(size_t)vi]);
+            for (int32_t vi : ow.w.unmeasured) row_u.push_back(ow.w.out_row[(size_t)vi]);
+            traits_output(**out, traits->n, row_m, row_u, t_z.data(), t_out.data());
+        }
         return 0;
     }
     gauss_prepared* p = nullptr;
@@ -355,6 +385,7 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
     if (gauss_prepared_window_desc(p, &d)) return -1;
     if (loo) ask(d);
     if (slct && ask_slct(d, [&](size_t i) { return p->measured[i]->rsid.c_str(); })) return -1;
+    if (traits && ask_traits(d, [&](size_t i) { return ident_of(*p->measured[i]); })) return -1;
     if (gauss_impute_window(ctx, &d) != 0) return herr("%s", gauss_last_error());
     if (slct) {
         std::vector<SlctRow> rows;
@@ -374,7 +405,18 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
         *out = loo_output(mix, rows, lz.data(), li.data(), lt.data());
         return 0;
     }
-    return gauss_prepared_finish(p, out);
+    if (gauss_prepared_finish(p, out)) return -1;
+    if (traits) {
+        std::map<const Snp*, int32_t> row_of;                // dist_output's rows: the SNPs of the prediction window, snp_vec order
+        for (Snp* sn : p->snp_vec) if (in_window(sn->bp)) { const int32_t r = (int32_t)row_of.size(); row_of[sn] = r; }
+        auto rows = [&](const std::vector<Snp*>& v) {
+            std::vector<int32_t> r;
+            for (const Snp* sn : v) { auto it = row_of.find(sn); r.push_back(it == row_of.end() ? -1 : it->second); }
+            return r;
+        };
+        traits_output(**out, traits->n, rows(p->measured), rows(p->unmeasured), t_z.data(), t_out.data());
+    }
+    return 0;
 }
 
 
@@ -431,6 +473,26 @@ int gauss_host_distmix_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t e
     const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond};
     return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
                       input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+}
+
+int gauss_host_dist_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                           const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                           const char* reference_pop_desc_file, double af1_cutoff, const char* const* more_input_files, int n_more,
+                           gauss_table** out)
+{
+    const TraitsAsk ask = {more_input_files, n_more};
+    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
+                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
+}
+
+int gauss_host_distmix_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                              const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                              const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                              double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out)
+{
+    const TraitsAsk ask = {more_input_files, n_more};
+    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
+                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
 }
 
 int gauss_host_slct_chi2(double p, double* out_chi2)

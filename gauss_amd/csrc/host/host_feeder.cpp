@@ -116,7 +116,7 @@ std::shared_ptr<const GwasCache> load_gwas_cached(const std::string& path, std::
         if ((twice || r.a1 == r.a2) && (c->odd_positions.empty() || c->odd_positions.back() != std::make_pair(r.chr, r.bp)))
             c->odd_positions.emplace_back(r.chr, r.bp);
     }
-    if (cache.size() >= 8) cache.clear();          // a handful of studies per process at most
+    if (cache.size() >= 128) cache.clear();        // a call of dist_traits keeps its 64 studies resident; otherwise a handful per process
     cache[k] = c;
     return c;
 }

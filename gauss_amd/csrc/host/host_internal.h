@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -522,6 +523,18 @@ gauss_table* loo_output(bool mix, const std::vector<LooRow>& rows, const double*
 struct SlctRow { SnpIdent id; double af, z; int wing; };
 gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, const int32_t* idx, const double* zin, const double* joint,
                          const double* zc, const double* var_left);
+// dist_traits / distmix_traits: the Z-scores of one further trait at the n measured SNPs of a window.  SNP i is at(i) -- position and
+// alleles in the window's (the panel's) orientation -- and is looked up in the study `gw` (read from `path`, named in the messages)
+// by (chr, bp, a1, a2): the same allele order gives z, the swapped order -z (gauss.cpp:358-370); of several rows that match, the
+// later one wins; rows for other SNPs are ignored.  Refused: a SNP without a row (the message names the file, the first missing
+// rsid and how many are missing) and a z that is not finite.
+int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out);
+// ... and their part of the table: `t` is dist_output's table of trait 1, unchanged; two named matrices are added, z_traits and
+// pval_traits [nrow x (1 + n_more)], column 0 the table's own z / pval, column 1 + k trait k: for a measured SNP its own study z
+// (z_more [n_more][M]), for an unmeasured one the imputed z (out_z_more [n_more][U]); pval = 2 pnorm(-|z|).  row_m[i] / row_u[i]:
+// the table row of measured / unmeasured SNP i, -1 when the table does not list it (the wings)
+void traits_output(gauss_table& t, int n_more, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                   const double* z_more, const double* out_z_more);
 // the smallest chi^2 (1 df) whose two-sided p-value 2 pnorm_upper(sqrt(chi2)) is below p, to the bit
 double slct_chi2_of(double p);
 gauss_table* prep_output(gauss_prepared& p);

@@ -261,6 +261,52 @@ gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, 
     return t;
 }
 
+int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out)
+{
+    size_t missing = 0;
+    std::string first_missing;
+    for (size_t i = 0; i < n; i++) {
+        const SnpIdent s = at(i);
+        auto before = [&](uint32_t x, long long bp) { const GwasRow& r = gw.rows[x]; return r.chr < s.chr || (r.chr == s.chr && r.bp < bp); };
+        bool found = false;
+        double z = 0.0;
+        // the rows of one position keep their file order in by_pos: the last match is the later row
+        for (auto it = std::lower_bound(gw.by_pos.begin(), gw.by_pos.end(), s.bp, before); it != gw.by_pos.end(); ++it) {
+            const GwasRow& r = gw.rows[*it];
+            if (r.chr != s.chr || r.bp != s.bp) break;
+            if (r.a1 == s.a1 && r.a2 == s.a2) { z = r.z; found = true; }
+            else if (r.a1 == s.a2 && r.a2 == s.a1) { z = -r.z; found = true; }        // gauss.cpp:358-370
+        }
+        if (!found) { if (!missing++) first_missing = s.rsid; continue; }
+        if (!std::isfinite(z)) return herr("ERROR: %s: the z of %s is not finite", path, s.rsid);
+        z_out[i] = z;
+    }
+    if (missing)
+        return herr("ERROR: %s lacks %zu of the window's %zu measured SNPs, the first is %s: every trait must be measured at the SNPs of the first",
+                    path, missing, n, first_missing.c_str());
+    return 0;
+}
+
+void traits_output(gauss_table& t, int n_more, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                   const double* z_more, const double* out_z_more)
+{
+    const size_t nrow = (size_t)t.nrow(), M = row_m.size(), U = row_u.size();
+    std::vector<double> z(nrow * (size_t)(1 + n_more), NAN), pv(nrow * (size_t)(1 + n_more), NAN);
+    for (const Column& c : t.cols) {
+        if (c.name == "z") std::copy(c.d.begin(), c.d.end(), z.begin());
+        if (c.name == "pval") std::copy(c.d.begin(), c.d.end(), pv.begin());
+    }
+    for (int k = 0; k < n_more; k++) {
+        double* zc = z.data() + nrow * (size_t)(1 + k);
+        double* pc = pv.data() + nrow * (size_t)(1 + k);
+        for (size_t i = 0; i < M; i++) if (row_m[i] >= 0) zc[(size_t)row_m[i]] = z_more[(size_t)k * M + i];
+        for (size_t i = 0; i < U; i++) if (row_u[i] >= 0) zc[(size_t)row_u[i]] = out_z_more[(size_t)k * U + i];
+        for (size_t r = 0; r < nrow; r++) pc[r] = 2 * pnorm_upper(fabs(zc[r]));       // dist.cpp:101
+    }
+    t.put_named("z_traits", (int)nrow, 1 + n_more, std::move(z));
+    t.put_named("pval_traits", (int)nrow, 1 + n_more, std::move(pv));
+}
+
 // Positive doubles order as their bit patterns do: bisection on the pattern ends at the last bit that changes the comparison.
 double slct_chi2_of(double p)
 {

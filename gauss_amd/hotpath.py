@@ -272,7 +272,7 @@ class _Win:
     """Keeps the numpy buffers of one window alive next to its C descriptor."""
 
     def __init__(self, desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig,
-                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None):
+                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None, z_more=None):
         self.po, self.w = _pops(pop_off, pop_wgt)
         self.z1 = np.ascontiguousarray(z1, dtype=np.float64)
         if dev_ptrs is None:
@@ -331,6 +331,16 @@ class _Win:
             desc.out_slct_n, desc.out_slct_idx = s["n"].ctypes.data_as(_ip), s["idx"].ctypes.data_as(_ip)
             desc.out_slct_zin, desc.out_slct_joint = s["zin"].ctypes.data_as(_dp), s["joint"].ctypes.data_as(_dp)
             desc.out_slct_zc, desc.out_slct_var = s["zc"].ctypes.data_as(_dp), s["var"].ctypes.data_as(_dp)
+        # further traits on the same window (n_traits_more / z_more / out_z_more of gauss_window_desc): z_more [T, M] -> [T, U]
+        self.z_more = self.out_z_more = None
+        if z_more is not None:
+            self.z_more = np.ascontiguousarray(z_more, dtype=np.float64)
+            if self.z_more.ndim != 2 or self.z_more.shape[1] != M:
+                raise ValueError(f"z_more must be [T, {M}] (one row per further trait), got {self.z_more.shape}")
+            T = self.z_more.shape[0]
+            self.out_z_more = np.zeros((T, U))
+            desc.n_traits_more = T
+            desc.z_more, desc.out_z_more = _lib.ptr(self.z_more if T else None, _dp), _lib.ptr(self.out_z_more if T else None, _dp)
         if packed is not None:
             # packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=): rows taken from a row store (dev_ptrs or
             # geno_m/geno_u give its base pointer and stride), optionally 2-bit packed (include/gauss_hip.h)
@@ -373,6 +383,8 @@ class _Win:
             out["b11"], out["b21"] = self.b11, self.b21
         if self.loo is not None:
             out["loo_z"], out["loo_info"], out["loo_t"] = self.loo[0], self.loo[1], self.loo[2]
+        if self.out_z_more is not None:
+            out["z_more"] = self.out_z_more
         if self.slct is not None:
             s, n = self.slct, int(self.slct["n"][0])
             out.update(slct_n=n, slct_idx=s["idx"][:n].copy(), slct_zin=s["zin"][:n].copy(), slct_joint=s["joint"][:n].copy(),
@@ -381,16 +393,18 @@ class _Win:
 
 
 def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_eig=1e-5,
-                  want_mats=False, ctx=None, loo=False, slct=None):
+                  want_mats=False, ctx=None, loo=False, slct=None, z_more=None):
     """run_dist (mode 0, dist.cpp:129-227) / run_distmix (mode 1, distmix.cpp:138-253).
     loo=True adds loo_z, loo_info, loo_t [M]: every measured SNP re-imputed from the other measured SNPs, and its
     standardised residual (include/gauss_hip.h, out_loo_*).
     slct=dict(max=K, chi2_stop=, collin=0.9, forced=[...]) adds the stepwise conditional signal selection among the measured SNPs
     (include/gauss_hip.h, slct_*): slct_n, slct_idx / slct_zin / slct_joint [n] in order of entry, slct_zc / slct_var [M]; status bit
-    8 when a forced SNP failed the collinearity guard."""
+    8 when a forced SNP failed the collinearity guard.
+    z_more [T, M] (T <= 63) adds z_more [T, U]: the Z-scores of T further traits measured at the same SNPs, imputed from the same LD
+    and the same factorisation (include/gauss_hip.h, n_traits_more); row t is what z would be with z1 = z_more[t]."""
     ctx = ctx or default_context()
     desc = WindowDesc()
-    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct)
+    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct, z_more=z_more)
     check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
     return win.result()
 
@@ -522,10 +536,11 @@ class Job:
     """A batch of windows sharing every launch (gauss_job_*)."""
 
     def __init__(self, windows, ctx=None, on_device=False, want_mats=False):
-        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct])
+        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more])
         or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
         loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs).
-        slct=dict(max=, chi2_stop=, collin=, forced=) in a window's dict: its result carries the signal selection (impute_window)."""
+        slct=dict(max=, chi2_stop=, collin=, forced=) in a window's dict: its result carries the signal selection (impute_window).
+        z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window)."""
         self.ctx = ctx or default_context()
         n = len(windows)
         self.descs = (WindowDesc * n)()
@@ -534,7 +549,7 @@ class Job:
             self.wins.append(_Win(self.descs[i], w["mode"], w.get("geno_m"), w.get("geno_u"),
                                   w["pop_off"], w.get("pop_wgt"), w["z1"], w.get("lam", 0.1),
                                   w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed"),
-                                  loo=bool(w.get("loo", False)), slct=w.get("slct")))
+                                  loo=bool(w.get("loo", False)), slct=w.get("slct"), z_more=w.get("z_more")))
         h = C.c_void_p()
         check(self.ctx.lib.gauss_job_create(self.ctx.handle, self.descs, n, 1 if on_device else 0,
                                             C.byref(h)))

@@ -142,6 +142,23 @@ typedef struct gauss_window_desc {
     double* out_slct_joint;   /* [slct_max] joint z: (B_SS^-1 z_S)_a / sqrt((B_SS^-1)_aa), NaN beyond n  optional   */
     double* out_slct_zc;      /* [M] final conditional z, NaN where the SNP is not admissible          optional     */
     double* out_slct_var;     /* [M] variance left v_i / B_ii, every SNP                               optional     */
+    /* ---- further traits on the same window (GAUSS_WIN_IMPUTE windows only) ---------------------------------------
+     * A study rarely has one trait: the LD of a window depends on the panel, the weights and the measured SNP set only, so
+     * n_traits_more further Z-score vectors measured at the SAME SNPs are imputed from the same B11 / B21 and the same
+     * factorisation.  out_z_more[t][u] is what out_z[u] would be were the window run with z1 = z_more[t]: with B = B11
+     * (lambda on the diagonal, after MakePosDef if it acted), g_t = B^-1 z_t, mean_ut = b21_u . g_t,
+     *   out_z_more[t][u] = mean_ut / sqrt(out_info[u])                                              (dist.cpp:194-202);
+     * out_info is the same for every trait.  Two kernels (k_traits.hip) form G = X^T (X Z) from the rows of X = L^-1 the
+     * solve holds anyway and B21 G on the fp64 matrix cores.  out_z, out_info and the status are untouched, z1 keeps its own
+     * path bit for bit; the further traits take another, equally valid order of fp64 sums.  A trait's values depend on its
+     * own row of z_more only: not on n_traits_more, not on the other rows (a non-finite z_more[t] makes row t of the output
+     * non-finite and moves no bit of another row).  Leave-one-out values and the signal selection stay statistics of z1.
+     * n_traits_more = 0: off.  GAUSS_ST_NONFINITE windows return NaN for every trait.  QCAT and LD windows that ask,
+     * n_traits_more < 0 or > GAUSS_TRAITS_MORE_MAX, and n_traits_more > 0 with z_more or out_z_more NULL are
+     * GAUSS_E_INVALID.  (The block sits in front of the leave-one-out arrays, which stay the descriptor's last three fields.) */
+    int n_traits_more;        /* T: further traits; 0 = none; at most GAUSS_TRAITS_MORE_MAX                          */
+    const double* z_more;     /* [T x M] row-major: Z-scores of the further traits at the measured SNPs  host pointer */
+    double* out_z_more;       /* [T x U] row-major: their imputed Z-scores at the unmeasured SNPs        host pointer */
     /* ---- leave-one-out re-imputation of the measured SNPs (GAUSS_WIN_IMPUTE windows only) ------------------------
      * The input check of summary-statistics imputation: measured SNP i re-imputed from the other M - 1 measured SNPs of
      * the window, i.e. what run_dist / run_distmix return for SNP i when it is presented as the only unmeasured SNP.  With
@@ -158,6 +175,7 @@ typedef struct gauss_window_desc {
 } gauss_window_desc;
 
 #define GAUSS_SLCT_MAX 32
+#define GAUSS_TRAITS_MORE_MAX 63
 
 #define GAUSS_GENO_U8   0
 #define GAUSS_GENO_2BIT 1

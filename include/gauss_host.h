@@ -189,6 +189,30 @@ int gauss_host_distmix_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t e
  * p must be positive. */
 int gauss_host_slct_chi2(double p, double* out_chi2);
 
+/* Many traits per window from one LD build.  A consortium array or a biobank has tens to hundreds of traits measured at the same
+ * SNPs, and a window's LD -- the Gram products, B11's factorisation: nine tenths of a step -- depends on the panel, the weights
+ * and the measured SNP set only.  Same arguments, same window, same data layer and the same single job as gauss_host_dist /
+ * gauss_host_distmix; the job's window sets n_traits_more / z_more / out_z_more of gauss_window_desc (include/gauss_hip.h).
+ *   input_file         trait 1: it defines the window, the measured set, the allele orientation and the AF filter exactly as in
+ *                      the plain call, and its table is the plain call's, unchanged
+ *   more_input_files   n_more (<= GAUSS_TRAITS_MORE_MAX = 63) further studies in the same format (rsid chr bp a1 a2 z).  Every
+ *                      measured SNP of the extended window is looked up in each by (chr, bp, a1, a2): the same allele order gives
+ *                      z, the swapped order -z (gauss.cpp:358-370), a key listed twice its later row; rows for SNPs trait 1 does
+ *                      not measure are ignored.  A measured SNP that a file lacks (the message names the file, the first missing
+ *                      rsid and the number missing), a z that is not finite and n_more > 63 are refused before any GPU work.
+ * Two named matrices are added to the table (gauss_table_named): z_traits and pval_traits, [nrow x (1 + n_more)], column 0 the
+ * table's own z / pval, column k trait k + 1 -- for a measured SNP its own oriented study z, for an unmeasured one the imputed z;
+ * info is the same for every trait. */
+int gauss_host_dist_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                           const char* study_pop, const char* input_file, const char* reference_index_file,
+                           const char* reference_data_file, const char* reference_pop_desc_file,
+                           double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out);
+int gauss_host_distmix_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                              const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                              const char* input_file, const char* reference_index_file,
+                              const char* reference_data_file, const char* reference_pop_desc_file,
+                              double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out);
+
 /* QCAT / QCATMIX: same feeder as dist / distmix, the window core is
  * run_qcat (qcat.cpp:134-262) / run_qcatmix (qcatmix.cpp:144-297).  af1_cutoff NaN -> 0.05 for qcat
  * (qcat.cpp:53-57), 0.01 for qcatmix (qcatmix.cpp:61-65).  Output columns: rsid chr bp a1 a2
