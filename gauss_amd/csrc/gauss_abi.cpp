@@ -19,12 +19,12 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.u_codings = d.u_codings;
     w.geno_fmt = d.geno_format; w.rows_m = d.rows_m; w.rows_u = d.rows_u; w.pop_src_off = d.pop_src_off;
     w.out_b11 = d.out_b11; w.out_b21 = d.out_b21;
-    w.out_loo_z = d.out_loo_z; w.out_loo_info = d.out_loo_info; w.out_loo_t = d.out_loo_t;
-    w.n_traits_more = d.n_traits_more; w.z_more = d.z_more; w.out_z_more = d.out_z_more;
+    w.out.loo_z = d.out_loo_z; w.out.loo_info = d.out_loo_info; w.out.loo_t = d.out_loo_t;
+    w.n_traits_more = d.n_traits_more; w.z_more = d.z_more; w.out.z_more = d.out_z_more;
     w.slct_max = d.slct_max; w.slct_chi2_stop = d.slct_chi2_stop; w.slct_min_var_frac = d.slct_min_var_frac;
     w.slct_forced = d.slct_forced; w.n_slct_forced = d.n_slct_forced;
-    w.out_slct_n = d.out_slct_n; w.out_slct_idx = d.out_slct_idx; w.out_slct_zin = d.out_slct_zin;
-    w.out_slct_joint = d.out_slct_joint; w.out_slct_zc = d.out_slct_zc; w.out_slct_var = d.out_slct_var;
+    w.out.slct_n = d.out_slct_n; w.out.slct_idx = d.out_slct_idx; w.out.slct_zin = d.out_slct_zin;
+    w.out.slct_joint = d.out_slct_joint; w.out.slct_zc = d.out_slct_zc; w.out.slct_var = d.out_slct_var;
     return w;
 }
 extern "C" {

@@ -122,28 +122,53 @@ struct Prob {
     // resampled windows (simulateLD, k_simld.hip): the packed columns are drawn samples, not the populations' samples
     GP(const int) draw_col;    // [Kp] source column of every packed column, ascending, -1 past the draws; null: not resampled
     int row_src_bytes;         // bytes of a source row the resample kernel reads
-    // leave-one-out re-imputation of the measured SNPs (k_loo.hip): [3][M] loo_z, loo_info, loo_t in the result block; null: not asked
+    // The riders of an imputation window.  Where each one's section lies in the result block: res_layout / slct_layout below.
+    // leave-one-out re-imputation of the measured SNPs (k_loo.hip): [3][M] loo_z, loo_info, loo_t; null: not asked
     GP(double) out_loo;
     // stepwise conditional signal selection (k_slct.hip); slct_max = 0: not asked
     int slct_max, n_slct_forced;           // K <= SLCT_K; forced SNPs that enter first
     double slct_chi2_stop, slct_min_var_frac;
     GP(const int) slct_forced;             // [n_slct_forced]
     GP(double) slct_W;                     // [SLCT_K][Mld] scratch: row s = column sel[s] of the partial Cholesky factor
-    GP(double) out_slct;                   // [slct_doubles(M, K)] in the result block: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M]
+    GP(double) out_slct;                   // [slct_layout(M, K).count]
     // further traits on the same window (k_traits.hip); traits_T = 0: not asked
     int traits_T;                          // T <= TRAITS_MAX further Z-score vectors
     GP(const double) traits_Z;             // [Mld][T16] their Z-scores, SNP-major, zero beyond M and T (T16 = T rounded up to 16)
     GP(double) traits_Y;                   // [Mld][T16] scratch: Y = X Z
     GP(double) traits_G;                   // [Mld][T16] scratch: G = X^T Y = B11^-1 Z
-    GP(double) out_traits;                 // [T][U] in the result block
+    GP(double) out_traits;                 // [T][U]
 };
+// a descriptor derived from a window's (the job-wide measured rows) carries no rider
+inline void clear_riders(Prob& q)
+{
+    q.out_loo = nullptr;
+    q.slct_max = q.n_slct_forced = 0; q.slct_chi2_stop = q.slct_min_var_frac = 0.0;
+    q.slct_forced = nullptr; q.slct_W = nullptr; q.out_slct = nullptr;
+    q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr;
+}
 constexpr int TRAITS_MAX = 63;         // GAUSS_TRAITS_MORE_MAX
 constexpr int traits_t16(int T) { return (T + 15) & ~15; }
 constexpr int SLCT_K = 32;             // GAUSS_SLCT_MAX
 constexpr int SLCT_T = 512;            // threads of slct_kernel; a thread keeps the "selected" flags of its SNPs in one 64-bit word
 constexpr int SLCT_M_MAX = 64 * SLCT_T;
-// doubles a window's selection takes in the result block (indices, n and the skipped flag travel as exact doubles)
-constexpr size_t slct_doubles(int M, int K) { return 2 * (size_t)M + 3 * (size_t)K + 2; }
+
+// ---- the result block ------------------------------------------------------------------------------------------------
+// A window's doubles in the job's result block, in this order and nowhere else written down:
+//     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, the selection]
+// Offsets in doubles from the window's Plan::res_off; a section nobody asked for takes nothing and its offset is that of the next.
+struct ResLayout { size_t z, info, loo, traits, slct, count; };
+// Inside the selection's section, from its start: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] (indices, n and the
+// skipped flag travel as exact doubles).  The host and slct_kernel both read it here.
+struct SlctLayout { size_t n, skipped, idx, zin, joint, zc, var, count; };
+constexpr SlctLayout slct_layout(int M, int K)
+{
+    return {0, 1, 2, 2 + (size_t)K, 2 + 2 * (size_t)K, 2 + 3 * (size_t)K, 2 + 3 * (size_t)K + (size_t)M, 2 + 3 * (size_t)K + 2 * (size_t)M};
+}
+constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K)
+{
+    const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_slct = o_traits + (size_t)T * U;
+    return {0, (size_t)n_rhs, o_loo, o_traits, o_slct, o_slct + (K ? slct_layout(M, K).count : 0)};
+}
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
 // streams the whole run without draining its load pipeline and flushes the accumulators into one

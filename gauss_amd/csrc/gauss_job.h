@@ -232,6 +232,13 @@ struct DevBuf {
     hipError_t alloc(gauss_ctx* c, size_t bytes) { return ctx_malloc_retry(c, &p, bytes ? bytes : 1); }
     template <typename T> T* as() const { return (T*)p; }
 };
+// Where a window's riders put their results (out_loo_* / out_slct_* / out_z_more of gauss_window_desc); every pointer is optional
+struct RiderOuts {
+    double *loo_z = nullptr, *loo_info = nullptr, *loo_t = nullptr;
+    int32_t *slct_n = nullptr, *slct_idx = nullptr;
+    double *slct_zin = nullptr, *slct_joint = nullptr, *slct_zc = nullptr, *slct_var = nullptr;
+    double* z_more = nullptr;
+};
 // Host-side plan of one problem
 struct Plan {
     Prob p;                                  // device descriptor (pointers filled at layout time)
@@ -261,23 +268,19 @@ struct Plan {
     double* out_b21 = nullptr;
     double* out_r = nullptr;
     int32_t* out_num_eig = nullptr;
-    bool loo = false;                        // the window asked for leave-one-out values: [3][M] behind its z / info in the result block
-    double* out_loo_z = nullptr;
-    double* out_loo_info = nullptr;
-    double* out_loo_t = nullptr;
-    int slct_K = 0;                          // signal selection (k_slct.hip): slct_doubles(M, K) behind z / info / loo in the result block; 0: not asked
-    std::vector<int> slct_forced;
-    int32_t* out_slct_n = nullptr;
-    int32_t* out_slct_idx = nullptr;
-    double* out_slct_zin = nullptr;
-    double* out_slct_joint = nullptr;
-    double* out_slct_zc = nullptr;
-    double* out_slct_var = nullptr;
-    int traits_T = 0;                        // further traits (k_traits.hip): [T][U] behind z / info / loo, in front of the selection; 0: not asked
-    std::vector<double> traits_z;            // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
-    double* out_z_more = nullptr;
-    size_t res_count() const                 // doubles of this window in the result block
-    { return 2 * (size_t)p.n_rhs + (loo ? 3 * (size_t)p.M : 0) + (size_t)traits_T * p.U + (slct_K ? slct_doubles(p.M, slct_K) : 0); }
+    // What rides on an imputation window's solve (the sections of the result block: res_layout, gauss_internal.h).  A derived
+    // descriptor clears it with one assignment.
+    struct Riders {
+        bool loo = false;                    // leave-one-out values of the measured SNPs (k_loo.hip)
+        int slct_K = 0;                      // signal selection (k_slct.hip); 0: not asked
+        std::vector<int> slct_forced;
+        int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
+        std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
+        RiderOuts out;
+        bool needs_fused() const { return loo || traits_T > 0; }      // it reads the rows of L^-1 that only the fused solve forms
+    } rd;
+    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K); }
+    size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
     size_t out_ld_count = 0;
@@ -334,6 +337,8 @@ struct gauss_job {
     int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
     int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
     int2* d_loomap = nullptr;   int n_loo = 0;             // leave-one-out: (window, 64-column panel of X) of the windows that asked
+    bool needs_fused() const                               // some window rides on the rows of L^-1
+    { return std::any_of(plans.begin(), plans.end(), [](const Plan& pl) { return pl.rd.needs_fused(); }); }
     int max_nblk = 0;
     int max_npanel = 0;                                    // most solve panels of any one window
     int solve_split = 0;                                   // rows of the inverse with at least this many products are cut (0: none)
@@ -438,22 +443,13 @@ struct WinSpec {
     int gram_only = 0;                       // LD-only without pairs: every B11 tile pair, but no S x S output (zmix normal equations)
     double* out_b11 = nullptr;               // matrices the caller wants back (the job plans their export at build time)
     double* out_b21 = nullptr;
-    double* out_loo_z = nullptr;             // leave-one-out values of the measured SNPs (any non-null: the window asks)
-    double* out_loo_info = nullptr;
-    double* out_loo_t = nullptr;
+    RiderOuts out;                           // (any of loo_z / loo_info / loo_t non-null: the window asks for leave-one-out values)
     int n_traits_more = 0;                   // further traits on the same window (gauss_window_desc.n_traits_more); 0: not asked
     const double* z_more = nullptr;          // [T x M]
-    double* out_z_more = nullptr;            // [T x U]
     int slct_max = 0;                        // signal selection among the measured SNPs (gauss_window_desc.slct_*); 0: not asked
     double slct_chi2_stop = 0.0, slct_min_var_frac = 0.0;
     const int32_t* slct_forced = nullptr;
     int n_slct_forced = 0;
-    int32_t* out_slct_n = nullptr;
-    int32_t* out_slct_idx = nullptr;
-    double* out_slct_zin = nullptr;
-    double* out_slct_joint = nullptr;
-    double* out_slct_zc = nullptr;
-    double* out_slct_var = nullptr;
     // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample
     // draw_sample[k] of selected population draw_pop[k] and the other n_cols - n_drawn are zero columns
     const int32_t* draw_pop = nullptr;

@@ -80,18 +80,18 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         return fail(GAUSS_E_INVALID, "bad u_codings mask %d", w.u_codings);
     if (w.kind == GAUSS_WIN_QCAT && (w.n_head < 0 || w.n_predm < 0 || w.n_head + w.n_predm > w.M))
         return fail(GAUSS_E_INVALID, "QCAT: n_head_measured + n_pred_measured exceeds n_measured");
-    // leave-one-out values come from the rows of L^-1 that an imputation window's solve leaves behind (k_loo.hip)
-    const bool loo = w.out_loo_z || w.out_loo_info || w.out_loo_t;
-    if (loo && (w.ld_only || w.kind != GAUSS_WIN_IMPUTE))
-        return fail(GAUSS_E_INVALID, "leave-one-out values (out_loo_z / out_loo_info / out_loo_t) are for imputation windows only (%s window)",
-                    w.kind == GAUSS_WIN_QCAT ? "QCAT" : "LD");
-    // signal selection works on B11 and z1 of an imputation window (k_slct.hip)
+    // the riders work on B11, z1 and the rows of L^-1 that an imputation window's solve leaves behind: QCAT and LD windows are refused
+    const bool imputes = !w.ld_only && w.kind == GAUSS_WIN_IMPUTE;
+    const char* const not_imputing = w.kind == GAUSS_WIN_QCAT ? "QCAT" : "LD";
+    // leave-one-out values (k_loo.hip)
+    const bool loo = w.out.loo_z || w.out.loo_info || w.out.loo_t;
+    if (loo && !imputes)
+        return fail(GAUSS_E_INVALID, "leave-one-out values (out_loo_z / out_loo_info / out_loo_t) are for imputation windows only (%s window)", not_imputing);
+    // signal selection (k_slct.hip)
     if (w.slct_max < 0 || w.slct_max > SLCT_K)
         return fail(GAUSS_E_INVALID, "slct_max = %d: signal selection takes 0 .. %d SNPs", w.slct_max, SLCT_K);
     if (w.slct_max > 0) {
-        if (w.ld_only || w.kind != GAUSS_WIN_IMPUTE)
-            return fail(GAUSS_E_INVALID, "signal selection (slct_max) is for imputation windows only (%s window)",
-                        w.kind == GAUSS_WIN_QCAT ? "QCAT" : "LD");
+        if (!imputes) return fail(GAUSS_E_INVALID, "signal selection (slct_max) is for imputation windows only (%s window)", not_imputing);
         if (w.M > SLCT_M_MAX)
             return fail(GAUSS_E_INVALID, "signal selection takes windows of at most %d measured SNPs (n_measured = %d)", SLCT_M_MAX, w.M);
         if (w.n_slct_forced < 0 || w.n_slct_forced > w.slct_max || (w.n_slct_forced > 0 && !w.slct_forced))
@@ -104,14 +104,12 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
                     return fail(GAUSS_E_INVALID, "slct_forced[%d] = slct_forced[%d] = %d: forced SNPs must be distinct", b, a, (int)w.slct_forced[a]);
         }
     }
-    // further traits ride on the window's LD and on the rows of L^-1 its solve leaves behind (k_traits.hip)
+    // further traits (k_traits.hip)
     if (w.n_traits_more < 0 || w.n_traits_more > TRAITS_MAX)
         return fail(GAUSS_E_INVALID, "n_traits_more = %d: a window takes 0 .. %d further traits", w.n_traits_more, TRAITS_MAX);
     if (w.n_traits_more > 0) {
-        if (w.ld_only || w.kind != GAUSS_WIN_IMPUTE)
-            return fail(GAUSS_E_INVALID, "further traits (n_traits_more) are for imputation windows only (%s window)",
-                        w.kind == GAUSS_WIN_QCAT ? "QCAT" : "LD");
-        if (!w.z_more || !w.out_z_more)
+        if (!imputes) return fail(GAUSS_E_INVALID, "further traits (n_traits_more) are for imputation windows only (%s window)", not_imputing);
+        if (!w.z_more || !w.out.z_more)
             return fail(GAUSS_E_INVALID, "n_traits_more = %d needs z_more and out_z_more (%s is NULL)", w.n_traits_more, !w.z_more ? "z_more" : "out_z_more");
     }
 
@@ -324,26 +322,25 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
     if (w.z1) pl.z1.assign(w.z1, w.z1 + w.M);
     pl.h_geno_m = w.geno_m; pl.h_geno_u = w.geno_u; pl.user_ld = w.ld;
     pl.out_b11 = w.out_b11; pl.out_b21 = w.out_b21;
-    pl.loo = loo; pl.out_loo_z = w.out_loo_z; pl.out_loo_info = w.out_loo_info; pl.out_loo_t = w.out_loo_t;
-    pl.slct_K = w.slct_max;
-    pl.slct_forced.clear();
+    Plan::Riders& rd = pl.rd;
+    rd = Plan::Riders();
+    rd.out = w.out;
+    rd.loo = loo;
+    rd.slct_K = w.slct_max;
     if (w.slct_max > 0) {
-        pl.slct_forced.assign(w.slct_forced, w.slct_forced + w.n_slct_forced);
+        rd.slct_forced.assign(w.slct_forced, w.slct_forced + w.n_slct_forced);
         p.slct_max = w.slct_max; p.n_slct_forced = w.n_slct_forced;
         p.slct_chi2_stop = w.slct_chi2_stop; p.slct_min_var_frac = w.slct_min_var_frac;
     }
-    pl.traits_T = w.n_traits_more; pl.out_z_more = w.out_z_more;
-    pl.traits_z.clear();
+    rd.traits_T = w.n_traits_more;
     if (w.n_traits_more > 0) {
         // SNP-major and padded to the kernels' tiles: row g = the T traits' Z-scores at measured SNP g
         const int T16 = traits_t16(w.n_traits_more);
-        pl.traits_z.assign((size_t)p.Mld * T16, 0.0);
+        rd.traits_z.assign((size_t)p.Mld * T16, 0.0);
         for (int t = 0; t < w.n_traits_more; t++)
-            for (int g = 0; g < w.M; g++) pl.traits_z[(size_t)g * T16 + t] = w.z_more[(size_t)t * w.M + g];
+            for (int g = 0; g < w.M; g++) rd.traits_z[(size_t)g * T16 + t] = w.z_more[(size_t)t * w.M + g];
         p.traits_T = w.n_traits_more;
     }
-    pl.out_slct_n = w.out_slct_n; pl.out_slct_idx = w.out_slct_idx; pl.out_slct_zin = w.out_slct_zin;
-    pl.out_slct_joint = w.out_slct_joint; pl.out_slct_zc = w.out_slct_zc; pl.out_slct_var = w.out_slct_var;
     return GAUSS_OK;
 }
 
@@ -472,7 +469,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             q.M = (int)gl.size(); q.U = 0; q.U_raw = 1; q.n_rhs = 0;
             q.Mp = (int)rup((size_t)q.M, TILE); q.Up = 0; q.Sp = q.Mp; q.nT = q.Mp / TILE;
             q.Mld = 0; q.nblk = 0; q.npanel = 0; q.npi = 0; q.kind = 0; q.ld_only = 0; q.n_head = q.n_predm = 0;
-            g.U_user = 0; g.h_geno_u = nullptr; g.loo = false; g.slct_K = 0; g.slct_forced.clear(); q.slct_max = 0; g.traits_T = 0; g.traits_z.clear(); q.traits_T = 0;
+            g.U_user = 0; g.h_geno_u = nullptr; g.rd = Plan::Riders(); clear_riders(q);
             // job-wide B11 pairs: the tile pairs some window lies in
             g.pair_ti.clear(); g.pair_tj.clear(); g.pair_lut.assign((size_t)q.nT * q.nT, -1);
             for (int i = 0; i < job->n; i++) {
@@ -558,8 +555,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         to[i].ru = put(blob, ta, pl.rows_u);
         to[i].ch = put(blob, ta, pl.chunk_live);
         to[i].dc = put(blob, ta, pl.draw_col);
-        to[i].sf = pl.slct_forced.empty() ? 0 : put(blob, ta, pl.slct_forced);
-        to[i].tz = pl.traits_z.empty() ? 0 : put(blob, ta, pl.traits_z);
+        to[i].sf = pl.rd.slct_forced.empty() ? 0 : put(blob, ta, pl.rd.slct_forced);
+        to[i].tz = pl.rd.traits_z.empty() ? 0 : put(blob, ta, pl.rd.traits_z);
     }
     // work lists
     struct ItemH { int prob, pair, group, len, b11, ord = 0; };     // b11: an item of B11 (job-wide pairs, or a window's own measured x measured pairs); ord: launch-order key (below)
@@ -634,10 +631,11 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             }
         for (int pn = 0; pn < p.npi; pn++) panelmap.push_back(make_int2(i, pn));
         for (int pn = 0; pn < p.npanel; pn++) dpanelmap.push_back(make_int2(i, pn));
-        if (job->plans[i].loo)
+        const Plan::Riders& rd = job->plans[i].rd;
+        if (rd.loo)
             for (int pn = 0; pn < (p.M + NR - 1) / NR; pn++) loomap.push_back(make_int2(i, pn));      // the panels that hold columns of X
-        if (job->plans[i].slct_K) slctmap.push_back(i);
-        if (job->plans[i].traits_T) {
+        if (rd.slct_K) slctmap.push_back(i);
+        if (rd.traits_T) {
             for (int b = 0; b < p.nblk; b++) traitsmap.push_back(make_int2(i, b));
             for (int us = 0; us < (p.U + NB - 1) / NB; us++) traitsumap.push_back(make_int2(i, us));
         }
@@ -920,15 +918,15 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             w.part = wa.take((size_t)2 * p.npi * 4 * NB * NR * sizeof(double));      // double buffered by row parity
             w.b11c = wa.take((size_t)p.Mld * p.Mld * sizeof(double));
         }
-        w.slct = pl.slct_K ? wa.take((size_t)SLCT_K * p.Mld * sizeof(double)) : 0;      // the selected columns of the partial factor
+        w.slct = pl.rd.slct_K ? wa.take((size_t)SLCT_K * p.Mld * sizeof(double)) : 0;      // the selected columns of the partial factor
         w.ty = w.tg = 0;
-        if (pl.traits_T) {                  // Y = X Z and G = X^T Y of the further traits
-            w.ty = wa.take((size_t)p.Mld * traits_t16(pl.traits_T) * sizeof(double));
-            w.tg = wa.take((size_t)p.Mld * traits_t16(pl.traits_T) * sizeof(double));
+        if (pl.rd.traits_T) {               // Y = X Z and G = X^T Y of the further traits
+            w.ty = wa.take((size_t)p.Mld * traits_t16(pl.rd.traits_T) * sizeof(double));
+            w.tg = wa.take((size_t)p.Mld * traits_t16(pl.rd.traits_T) * sizeof(double));
         }
         w.ld = wa.take(std::max<size_t>(pl.out_ld_count, 1) * sizeof(double));
         pl.res_off = res;
-        res += pl.res_count();      // z, info [, loo_z, loo_info, loo_t] [, the further traits] [, the selection]
+        res += pl.res_count();
     }
     // job-wide measured rows (shared measured rows): one more tile of rows than Mp, because a window's last row tile
     // starts wherever the window starts and may reach past the chromosome's last measured SNP (zero rows there)
@@ -1065,16 +1063,18 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             p.Part = (double*)(W + w.part);
             pl.d_b11_copy = (double*)(W + w.b11c);
         }
-        p.out_z = job->d_results + pl.res_off;
-        p.out_info = job->d_results + pl.res_off + p.n_rhs;
-        p.out_loo = pl.loo ? job->d_results + pl.res_off + 2 * (size_t)p.n_rhs : nullptr;
-        p.out_slct = pl.slct_K ? job->d_results + pl.res_off + pl.res_count() - slct_doubles(p.M, pl.slct_K) : nullptr;
-        p.slct_W = pl.slct_K ? (double*)(W + w.slct) : nullptr;
-        p.out_traits = pl.traits_T ? job->d_results + pl.res_off + 2 * (size_t)p.n_rhs + (pl.loo ? 3 * (size_t)p.M : 0) : nullptr;
-        p.traits_Z = pl.traits_T ? (const double*)(T + to[i].tz) : nullptr;
-        p.traits_Y = pl.traits_T ? (double*)(W + w.ty) : nullptr;
-        p.traits_G = pl.traits_T ? (double*)(W + w.tg) : nullptr;
-        p.slct_forced = pl.slct_forced.empty() ? nullptr : (const int*)(T + to[i].sf);
+        const ResLayout lay = pl.layout();
+        double* const out = job->d_results + pl.res_off;
+        p.out_z = out + lay.z;
+        p.out_info = out + lay.info;
+        p.out_loo = pl.rd.loo ? out + lay.loo : nullptr;
+        p.out_slct = pl.rd.slct_K ? out + lay.slct : nullptr;
+        p.slct_W = pl.rd.slct_K ? (double*)(W + w.slct) : nullptr;
+        p.slct_forced = pl.rd.slct_forced.empty() ? nullptr : (const int*)(T + to[i].sf);
+        p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;
+        p.traits_Z = pl.rd.traits_T ? (const double*)(T + to[i].tz) : nullptr;
+        p.traits_Y = pl.rd.traits_T ? (double*)(W + w.ty) : nullptr;
+        p.traits_G = pl.rd.traits_T ? (double*)(W + w.tg) : nullptr;
         p.status = job->d_status + 4 * i;
         p.out_ld = (double*)(W + w.ld);
         p.gene_off = p.n_gene ? (const int*)(T + to[i].goff) : nullptr;
@@ -1146,7 +1146,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         q.run_pk_off = (const int*)(T + to[n].rpk); q.run_src = (const int*)(T + to[n].rsrc);
         q.slab = (float*)(W + go.slab); q.slab_g = q.slab; q.gpair_ti = q.pair_ti; q.gpair_tj = q.pair_tj; q.g0 = 0; q.n_gpair = q.npair;
         q.z1 = nullptr; q.A = nullptr; q.B21 = nullptr; q.Linv = nullptr; q.V = nullptr; q.Gsum = nullptr; q.Part = nullptr;
-        q.out_z = q.out_info = nullptr; q.out_loo = nullptr; q.out_slct = nullptr; q.slct_W = nullptr; q.slct_forced = nullptr; q.slct_max = 0; q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr; q.out_ld = nullptr; q.status = job->d_status;      // never written for this descriptor
+        q.out_z = q.out_info = nullptr; clear_riders(q); q.out_ld = nullptr; q.status = job->d_status;      // never written for this descriptor
         q.gene_off = nullptr; q.gene_out_off = nullptr; q.n_gene = 0;
         memcpy(blob.data() + o_probs + sizeof(Prob) * n, &q, sizeof(Prob));
     }

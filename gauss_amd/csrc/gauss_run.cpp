@@ -84,6 +84,24 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
     return GAUSS_OK;
 }
 
+// The tail of a fused solve, in the one order its inputs allow:
+//     loo -> selection -> traits weights -> closing step -> traits impute
+//   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
+//     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
+//   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
+//   - traits impute divides B21 G by the info the closing step's finish kernel has just written.
+// The closing step of a run is the product B21 [X | y] with its finish kernel.  A launch for which no window asked is skipped by its
+// launcher.  The clamp path (job_clamp_window) keeps the same order with its single-window map and the stand-alone solve as its
+// closing step; its selection runs in front of the re-factorisation.
+static void queue_tail(gauss_job* job, hipStream_t st)
+{
+    launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
+    launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
+    launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
+    launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
+    launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
+}
+
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
 // allow_merged = false: the two-launch form whatever the job was built for (the re-run after a give-up, job_fetch).
 static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
@@ -107,9 +125,8 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
                                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_run0).count());
     // fused tail: the factorisation chain needs B11 only and the closing product is the first reader of B21, so B21's
     // tiles of the epilogue (85 % of them) go to the side stream and run beside the chain
-    // (a job with a window that asks for leave-one-out values always takes the fused form: they are read off the rows of L^-1 that
-    // only the fused solve forms, k_loo.hip; so does a job with a window that carries further traits, k_traits.hip)
-    const bool fused = env_int("GAUSS_FUSED_SOLVE", 1) != 0 || job->n_loo > 0 || job->n_traits > 0;           // read per run: the tests drive both forms
+    // (a job with a window that rides on the rows of L^-1 always takes the fused form: only the fused solve forms them)
+    const bool fused = env_int("GAUSS_FUSED_SOLVE", 1) != 0 || job->needs_fused();           // read per run: the tests drive both forms
     hipStream_t side = (solve && fused && job->n_panels > 0 && job->n_tiles > job->n_tiles_b11) ? ctx->side : nullptr;
     prof_begin(job, 1, st);
     if (job->resample_lds >= 0) launch_resample_pack(job->d_probs, job->d_rowmap, job->n_rows, job->resample_lds, st);
@@ -187,11 +204,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         }
         HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
         prof_begin(job, 4, st);
-        launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);       // the chain has been joined: [X | y] is complete
-        launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);    // (B11 sits in A[0], untouched by the factorisation)
-        launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
-        launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
-        launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);      // behind the finish kernel: it divides by its info
+        queue_tail(job, st);               // the chain has been joined: [X | y] is complete
         prof_end(job, st);
         return job_queue_results(job, par, st);
     }
@@ -227,11 +240,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         if (fused) {
             launch_solve_last(job->d_probs, job->d_panelmap, job->n_panels, job->max_nblk, job->solve_split, st);
             if (side) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
-            launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
-            launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
-            launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
-            launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
-            launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
+            queue_tail(job, st);
         } else {
             launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);      // B11 and z1 are all it reads: it needs no fused solve
             launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
@@ -408,11 +417,7 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
     }
     launch_epilogue(job->d_probs, job->d_tilemap + job->n_tiles_b11, job->n_tiles - job->n_tiles_b11, job->max_pop, job->gram_i8, st);
     if (ch != st) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
-    launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
-    launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
-    launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
-    launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
-    launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
+    queue_tail(job, st);
     const int rc = job_queue_results(job, (int)(job->run_seq & 1u), st);
     if (rc) return rc;
     job->run_seq++;
@@ -448,13 +453,11 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     HIPCHK(hipMemcpyAsync(d_pm.p, pm.data(), sizeof(int2) * pm.size(), hipMemcpyHostToDevice, st));
     if (pl.out_b11) HIPCHK(hipMemcpyAsync(pl.d_b11_copy, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(p.A + 4 * n * n, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));   // W0 = clamped B11
-    if (pl.slct_K) launch_slct(job->d_probs + i, nullptr, 1, st);      // signal selection again, on the REPAIRED B11 in A[0]
-    // a window that asked for leave-one-out values: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this
-    // factorisation as they do in a run's (same L either way), k_loo.hip reads them, and only then does the stand-alone
-    // solve below take V as its scratch
-    // (a window that carries further traits needs the same rows: G = X^T (X Z) is formed before the solve takes V, and B21 G is
-    // divided by the info the solve leaves -- the stand-alone solve only reads B21)
-    const bool loo = pl.loo, traits = pl.traits_T > 0, ride = loo || traits;
+    if (pl.rd.slct_K) launch_slct(job->d_probs + i, nullptr, 1, st);      // signal selection again, on the REPAIRED B11 in A[0]
+    // a window that rides on the rows of L^-1: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this factorisation
+    // as they do in a run's (same L either way), and the stand-alone solve below is this tail's closing step (queue_tail): it
+    // takes V as its scratch, only reads B21 and leaves the info the further traits are divided by
+    const bool loo = pl.rd.loo, traits = pl.rd.traits_T > 0, ride = pl.rd.needs_fused();
     for (int s = 0; s < p.nblk; s++) {
         // launch over all problems would redo the others; use a single-problem launch instead
         launch_factor_step(job->d_probs + i, 1, s, p.nblk, ride ? p.npi : 0, ride ? job->solve_split : 0, 0, st);
@@ -666,37 +669,38 @@ int job_fetch(gauss_job* job)
             clamped = true;                    // B11's exported copy predates the clamp: fetched again below
         }
         if (p.npanel > 0) {
+            // the window's sections of the result block (res_layout, gauss_internal.h)
+            const Plan::Riders& rd = pl.rd;
+            const ResLayout lay = pl.layout();
+            const SlctLayout sl = slct_layout(p.M, rd.slct_K);
+            double* const res = job->h_results + pl.res_off;
+            double* const sel = res + lay.slct;
             if (bits & GAUSS_ST_NONFINITE) {
                 // the reference's eigen-solver / LU propagate non-finite values to every output
-                for (size_t u = 0; u < pl.res_count(); u++) job->h_results[pl.res_off + u] = NAN;
-                if (pl.slct_K) {                   // nothing selected: n = 0, no skipped SNP, indices -1
-                    double* sl = job->h_results + pl.res_off + pl.res_count() - slct_doubles(p.M, pl.slct_K);
-                    sl[0] = sl[1] = 0.0;
-                    for (int a = 0; a < pl.slct_K; a++) sl[2 + a] = -1.0;
+                for (size_t u = 0; u < lay.count; u++) res[u] = NAN;
+                if (rd.slct_K) {                   // nothing selected: n = 0, no skipped SNP, indices -1
+                    sel[sl.n] = sel[sl.skipped] = 0.0;
+                    for (int a = 0; a < rd.slct_K; a++) sel[sl.idx + a] = -1.0;
                 }
             }
-            if (pl.out_z) memcpy(pl.out_z, job->h_results + pl.res_off, sizeof(double) * p.U);
-            if (pl.out_info) memcpy(pl.out_info, job->h_results + pl.res_off + p.U, sizeof(double) * p.U);
-            if (pl.loo) {
-                // leave-one-out values of the measured SNPs (k_loo.hip): [3][M] behind z / info
-                const double* lo = job->h_results + pl.res_off + 2 * (size_t)p.U;
-                if (pl.out_loo_z) memcpy(pl.out_loo_z, lo, sizeof(double) * p.M);
-                if (pl.out_loo_info) memcpy(pl.out_loo_info, lo + p.M, sizeof(double) * p.M);
-                if (pl.out_loo_t) memcpy(pl.out_loo_t, lo + 2 * (size_t)p.M, sizeof(double) * p.M);
+            auto copy_out = [](double* dst, const double* src, size_t n) { if (dst) memcpy(dst, src, sizeof(double) * n); };
+            copy_out(pl.out_z, res + lay.z, p.U);
+            copy_out(pl.out_info, res + lay.info, p.U);
+            if (rd.loo) {                          // leave-one-out values of the measured SNPs (k_loo.hip)
+                copy_out(rd.out.loo_z, res + lay.loo, p.M);
+                copy_out(rd.out.loo_info, res + lay.loo + p.M, p.M);
+                copy_out(rd.out.loo_t, res + lay.loo + 2 * (size_t)p.M, p.M);
             }
-            if (pl.traits_T && pl.out_z_more)      // the further traits (k_traits.hip): [T][U] behind z / info / loo
-                memcpy(pl.out_z_more, job->h_results + pl.res_off + 2 * (size_t)p.U + (pl.loo ? 3 * (size_t)p.M : 0), sizeof(double) * pl.traits_T * p.U);
-            if (pl.slct_K) {
-                // signal selection (k_slct.hip): n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] behind z / info / loo
-                const int K = pl.slct_K;
-                const double* sl = job->h_results + pl.res_off + pl.res_count() - slct_doubles(p.M, K);
-                if (pl.out_slct_n) *pl.out_slct_n = (int32_t)sl[0];
-                if (sl[1] != 0.0) bits |= GAUSS_ST_SLCT_SKIPPED;
-                if (pl.out_slct_idx) for (int a = 0; a < K; a++) pl.out_slct_idx[a] = (int32_t)sl[2 + a];
-                if (pl.out_slct_zin) memcpy(pl.out_slct_zin, sl + 2 + K, sizeof(double) * K);
-                if (pl.out_slct_joint) memcpy(pl.out_slct_joint, sl + 2 + 2 * (size_t)K, sizeof(double) * K);
-                if (pl.out_slct_zc) memcpy(pl.out_slct_zc, sl + 2 + 3 * (size_t)K, sizeof(double) * p.M);
-                if (pl.out_slct_var) memcpy(pl.out_slct_var, sl + 2 + 3 * (size_t)K + p.M, sizeof(double) * p.M);
+            if (rd.traits_T) copy_out(rd.out.z_more, res + lay.traits, (size_t)rd.traits_T * p.U);      // the further traits (k_traits.hip)
+            if (rd.slct_K) {                       // signal selection (k_slct.hip)
+                const int K = rd.slct_K;
+                if (rd.out.slct_n) *rd.out.slct_n = (int32_t)sel[sl.n];
+                if (sel[sl.skipped] != 0.0) bits |= GAUSS_ST_SLCT_SKIPPED;
+                if (rd.out.slct_idx) for (int a = 0; a < K; a++) rd.out.slct_idx[a] = (int32_t)sel[sl.idx + a];
+                copy_out(rd.out.slct_zin, sel + sl.zin, K);
+                copy_out(rd.out.slct_joint, sel + sl.joint, K);
+                copy_out(rd.out.slct_zc, sel + sl.zc, p.M);
+                copy_out(rd.out.slct_var, sel + sl.var, p.M);
             }
             if (pl.out_b11 && (!exporting || clamped))
                 { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }

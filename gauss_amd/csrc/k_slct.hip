@@ -54,7 +54,8 @@ __global__ __launch_bounds__(SLCT_T) void slct_kernel(const Prob* __restrict__ p
     const auto A = pb.A;                                    // A[0] = B11
     const auto W = pb.slct_W;
     const auto out = pb.out_slct;
-    const auto o_idx = out + 2, o_zin = o_idx + K, o_joint = o_zin + K, o_zc = o_joint + K, o_var = o_zc + M;
+    const SlctLayout o = slct_layout(M, K);
+    const auto o_idx = out + o.idx, o_zin = out + o.zin, o_joint = out + o.joint, o_zc = out + o.zc, o_var = out + o.var;
     const bool in_lds = M <= SLCT_LDS_M;
     double* const r = in_lds ? s_rv : (double*)o_zc;
     double* const v = in_lds ? s_rv + SLCT_LDS_M : (double*)o_var;
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(SLCT_T) void slct_kernel(const Prob* __restrict__ p
         o_zc[i] = adm ? ri / sqrt(vi) : __builtin_nan("");
         o_var[i] = vi / b;
     }
-    if (tid == 0) { out[0] = (double)n; out[1] = (double)skipped; }
+    if (tid == 0) { out[o.n] = (double)n; out[o.skipped] = (double)skipped; }
     if (tid >= n && tid < K) { o_idx[tid] = -1.0; o_zin[tid] = __builtin_nan(""); o_joint[tid] = __builtin_nan(""); }
     __syncthreads();                                        // r, v and diag(B) are done with: their LDS holds L and L^-1 now
     double* const L = s_rv;                                 // L[a][b] = W[b][sel[a]], b <= a: the Cholesky factor of B_SS

@@ -312,6 +312,76 @@ def test_with_leave_one_out_and_selection_in_the_same_window(ctx):
         _same(every, only)
 
 
+_RIDER_KEYS = ("z", "info", "loo_z", "loo_info", "loo_t", "z_more", "slct_idx", "slct_zin", "slct_joint", "slct_zc", "slct_var")
+_LOO_KEYS = ("loo_z", "loo_info", "loo_t")
+_SLCT_KEYS = ("slct_idx", "slct_zin", "slct_joint", "slct_zc", "slct_var")
+
+
+def _same_riders(a, b, what):
+    """Every output two results of the same window with the same asks carry, bit for bit (the unused tails of idx / zin / joint too)."""
+    assert a["status"] == b["status"] and sorted(a) == sorted(b), (what, a["status"], b["status"], sorted(a), sorted(b))
+    for k in _RIDER_KEYS:
+        if k in a:
+            assert np.array_equal(a[k], b[k], equal_nan=True), (what, k)
+    if "slct_n" in a:
+        assert a["slct_n"] == b["slct_n"], what
+        for k in ("idx", "zin", "joint"):
+            assert np.array_equal(a["slct_raw"][k], b["slct_raw"][k], equal_nan=True), (what, "raw " + k)
+
+
+def test_all_three_riders_share_one_result_block(ctx):
+    """Leave-one-out, selection and further traits together where the result block's layout is used most intricately.
+    (a) One job of four windows on shared store rows, two runs in flight, asking all three / the selection / nothing / loo + traits
+    (T = 17, K = 4): a window's place in the block depends on the sections of the windows in front of it, and every output of
+    every window is bit for bit that of the window run alone with the same asks.
+    (b) The smallest clamped window of test_clamped_window_uses_the_repaired_matrix asking all three: each rider's outputs are the bits
+    of the same clamped window asking for that rider alone: the riders read disjoint inputs, so the results are bit-equal.
+    (c) The non-finite window of test_nonfinite_window_is_all_nan asking all three: status bit 2, every double NaN, nothing selected."""
+    T, slct = 17, dict(max=4, chi2_stop=1.0)
+    # (a)
+    p, rows2, src_off, store, wins, host = _store_windows(ctx, spans=((0, 131), (97, 340), (211, 560), (330, None)), T=(T, 0, 0, T))
+    wins = [dict(wins[0], loo=True, slct=slct), dict(wins[1], slct=slct), wins[2], dict(wins[3], loo=True)]
+    alone = [_run(ctx, [w])[0][0] for w in wins]
+    assert all(r["status"] == 0 for r in alone) and alone[0]["slct_n"] > 0 and alone[1]["slct_n"] > 0
+    assert {"loo_z", "z_more", "slct_zc"} <= set(alone[0]) and "loo_z" not in alone[1] and "z_more" not in alone[1]
+    assert not {"loo_z", "z_more", "slct_zc"} & set(alone[2]) and {"loo_z", "z_more"} <= set(alone[3]) and "slct_zc" not in alone[3]
+    for r, run in enumerate(_run(ctx, wins, runs=2)):
+        for k, (got, want) in enumerate(zip(run, alone)):
+            _same_riders(got, want, f"store window {k}, run {r}")
+    store.close()
+    # (b)
+    mode, M0, dup = 0, 30, [0, 1, 2]
+    q = small_panel(n_snp=M0 + 110, scale=0.02, seed=21)
+    gm, gu, z1 = split_window(dict(G=q["G"][: M0 + 80]), M0)
+    gm = np.ascontiguousarray(np.vstack([gm, gm[dup]]))
+    z1 = np.concatenate([z1, z1[dup] - 0.2])
+    Z = _traits(T, gm.shape[0], seed=3)
+    call = lambda **asks: hotpath.impute_window(mode, gm, gu, q["off"], None, z1, lam=0.0, ctx=ctx, **asks)
+    every = call(loo=True, slct=slct, z_more=Z)
+    assert every["status"] & 1 and every["slct_n"] > 0
+    for keys, one in ((_LOO_KEYS, call(loo=True)), (_SLCT_KEYS, call(slct=slct)), (("z_more",), call(z_more=Z))):
+        assert one["status"] == every["status"]
+        for k in ("z", "info") + keys:
+            assert np.array_equal(every[k], one[k], equal_nan=True), k
+        if keys is _SLCT_KEYS:
+            assert one["slct_n"] == every["slct_n"]
+    # (c)
+    q = small_panel(n_snp=60, scale=0.01, n_pops=4)
+    gm, gu, z1 = split_window(q, 25)
+    gm = gm.copy()
+    gm[3, :] = 1                                   # zero variance: CalCor returns 0 / 0
+    got = hotpath.impute_window(0, gm, gu, q["off"], None, z1, ctx=ctx, loo=True, slct=slct, z_more=_traits(T, 25))
+    assert got["status"] & 2
+    assert got["z"].shape == got["info"].shape == (gu.shape[0],) and got["z_more"].shape == (T, gu.shape[0])
+    assert got["slct_zc"].shape == got["slct_var"].shape == got["loo_z"].shape == got["loo_info"].shape == got["loo_t"].shape == (25,)
+    for k in ("z", "info", "loo_z", "loo_info", "loo_t", "z_more", "slct_zc", "slct_var"):
+        assert np.all(np.isnan(got[k])), k
+    raw = got["slct_raw"]
+    assert raw["zin"].shape == raw["joint"].shape == raw["idx"].shape == (4,)
+    assert np.all(np.isnan(raw["zin"])) and np.all(np.isnan(raw["joint"]))
+    assert got["slct_n"] == 0 and np.all(raw["idx"] == -1)
+
+
 def _rand_geno(rng, n, N):
     f = rng.uniform(0.05, 0.95, size=(n, 1))
     return ((rng.random((n, N)) < f).astype(np.uint8) + (rng.random((n, N)) < f).astype(np.uint8))
