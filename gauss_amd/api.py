@@ -48,7 +48,7 @@ HOST_SYMBOLS = [
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2",
-    "gauss_host_dist_traits", "gauss_host_distmix_traits",
+    "gauss_host_dist_traits", "gauss_host_distmix_traits", "gauss_host_dist_traits_miss", "gauss_host_distmix_traits_miss",
 ]
 
 
@@ -143,6 +143,8 @@ def load_host():
     traits_tail = [_strs, C.c_int, C.POINTER(_vp)]                           # more_input_files, n_more, out
     h.gauss_host_dist_traits.argtypes = h.gauss_host_dist.argtypes[:-1] + traits_tail
     h.gauss_host_distmix_traits.argtypes = h.gauss_host_distmix.argtypes[:-1] + traits_tail
+    h.gauss_host_dist_traits_miss.argtypes = h.gauss_host_dist_traits.argtypes
+    h.gauss_host_distmix_traits_miss.argtypes = h.gauss_host_distmix_traits.argtypes
     h.gauss_host_qcatmix.argtypes = h.gauss_host_distmix.argtypes
     h.gauss_prepared_qcat_counts.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     h.gauss_host_prepare.argtypes = [C.c_int, C.c_int, _i64, _i64, _i64, _cp, _strs, _dp, C.c_int, _cp, _cp, _cp, _cp, _cp,
@@ -444,36 +446,55 @@ def _traits_frame(h, out):
     named = _named(h, out)
     df = _table(h, out)[0]
     z, pv = (np.asarray(named[k]).reshape(len(df), -1) for k in ("z_traits", "pval_traits"))
+    if "info_traits" in named:          # missing="impute": every trait has its own info and type (a SNP it lacks is imputed for it)
+        info, typ = (np.asarray(named[k]).reshape(len(df), -1) for k in ("info_traits", "type_traits"))
+        for k in range(1, z.shape[1]):
+            df[f"z_{k + 1}"], df[f"pval_{k + 1}"], df[f"info_{k + 1}"], df[f"type_{k + 1}"] = z[:, k], pv[:, k], info[:, k], typ[:, k].astype(np.int64)
+        df.attrs["n_missing"] = np.asarray(named["n_missing"]).reshape(-1).astype(np.int64)
+        return df
     for k in range(1, z.shape[1]):
         df[f"z_{k + 1}"], df[f"pval_{k + 1}"] = z[:, k], pv[:, k]
     return df
 
 
+def _traits_call(h, name, missing):
+    if missing not in ("refuse", "impute"):
+        raise ValueError(f"missing must be 'refuse' or 'impute', got {missing!r}")
+    return getattr(h, name + ("_miss" if missing == "impute" else ""))
+
+
 def dist_traits(chr, start_bp, end_bp, wing_size, study_pop, input_files, reference_index_file, reference_data_file,
-                reference_pop_desc_file, af1_cutoff=None, ctx=None):
+                reference_pop_desc_file, af1_cutoff=None, ctx=None, missing="refuse"):
     """dist() for many traits measured at the same SNPs, from ONE LD build and one factorisation (gauss_host_dist_traits).
     input_files: a list of study files (rsid chr bp a1 a2 z), at most 64; the first is trait 1 and defines the window, the measured
     set, the allele orientation and the AF filter exactly as dist() does.  Every measured SNP of the extended window must be in each
     further file (swapped alleles flip the sign, a key listed twice ends with its later row, other rows are ignored).  Returns dist()'s
     frame of trait 1 with columns z_2, pval_2, ..., z_T, pval_T appended: a measured SNP's own study z, an unmeasured SNP's imputed z
-    (info is shared)."""
+    (info is shared).
+    missing="impute" (gauss_host_dist_traits_miss): a measured SNP that a further file lacks -- at most 32 per file, 128 distinct per window,
+    more than 10 left -- is imputed for that trait as if the file had been run alone; the columns appended per trait are then
+    z_k, pval_k, info_k, type_k (type 0 where trait k lacks a SNP trait 1 measures), and frame.attrs["n_missing"] counts, per trait, the
+    measured SNPs of the extended window its file lacked.  Column set k equals dist() of file k alone when that file's SNPs in the
+    extended window are a subset of trait 1's."""
     h = load_host()
+    call = _traits_call(h, "gauss_host_dist_traits", missing)
     first, more, n_more = _traits_files(input_files)
     out = _vp()
-    _hcheck(h.gauss_host_dist_traits(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop), first,
+    _hcheck(call(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop), first,
                                      _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file),
                                      _af(af1_cutoff), more, n_more, C.byref(out)))
     return _traits_frame(h, out)
 
 
 def distmix_traits(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_files, reference_index_file, reference_data_file,
-                   reference_pop_desc_file, af1_cutoff=None, ctx=None):
-    """distmix() for many traits measured at the same SNPs (gauss_host_distmix_traits); input_files and the frame as dist_traits."""
+                   reference_pop_desc_file, af1_cutoff=None, ctx=None, missing="refuse"):
+    """distmix() for many traits measured at the same SNPs (gauss_host_distmix_traits); input_files, missing and the frame as dist_traits."""
     h = load_host()
+    call = _traits_call(h, "gauss_host_distmix_traits", missing)
     names, w, n = _pop_wgt(pop_wgt_df)
     first, more, n_more = _traits_files(input_files)
     out = _vp()
-    _hcheck(h.gauss_host_distmix_traits(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
+    _hcheck(call(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
                                         w.ctypes.data_as(_dp), n, first, _enc(reference_index_file), _enc(reference_data_file),
                                         _enc(reference_pop_desc_file), _af(af1_cutoff), more, n_more, C.byref(out)))
     return _traits_frame(h, out)

@@ -34,6 +34,7 @@ HIP_UNITS = {
     "k_loo.hip": ["-ffp-contract=off"],         # leave-one-out sums and tail: plain fp64 multiplies and adds, in a fixed order
     "k_slct.hip": ["-ffp-contract=off"],        # signal selection: the recurrence as written, sums in ascending order
     "k_traits.hip": ["-ffp-contract=off"],      # further traits: MFMA chains in ascending k, the closing division as written
+    "k_traits_miss.hip": ["-ffp-contract=off"], # traits that lack some measured SNPs: the downdate's recurrences as written, sums in ascending order
 }
 
 
@@ -143,7 +144,7 @@ def build_hip(force=False, verbose=False):
     import json
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
-    hdrs = [os.path.join(CSRC, "gauss_internal.h"), os.path.join(CSRC, "gauss_job.h"), os.path.join(CSRC, "k_gram_common.h"), os.path.join(CSRC, "k_solve_common.h"), os.path.join(HERE, "..", "include", "gauss_hip.h")]
+    hdrs = [os.path.join(CSRC, "gauss_internal.h"), os.path.join(CSRC, "gauss_job.h"), os.path.join(CSRC, "k_gram_common.h"), os.path.join(CSRC, "k_solve_common.h"), os.path.join(CSRC, "k_traits_common.h"), os.path.join(HERE, "..", "include", "gauss_hip.h")]
     # an object is rebuilt when its recorded identity (source + headers + command line + compiler) differs -- not by mtime: a
     # flag change or a checkout that restores old timestamps must not link stale objects under a fresh source hash
     ids_path = os.path.join(OBJDIR, "unit_ids.json")

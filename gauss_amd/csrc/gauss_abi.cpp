@@ -21,6 +21,7 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.out_b11 = d.out_b11; w.out_b21 = d.out_b21;
     w.out.loo_z = d.out_loo_z; w.out.loo_info = d.out_loo_info; w.out.loo_t = d.out_loo_t;
     w.n_traits_more = d.n_traits_more; w.z_more = d.z_more; w.out.z_more = d.out_z_more;
+    w.miss_more = d.miss_more; w.out.info_more = d.out_info_more; w.out.z_miss = d.out_z_miss; w.out.info_miss = d.out_info_miss;
     w.slct_max = d.slct_max; w.slct_chi2_stop = d.slct_chi2_stop; w.slct_min_var_frac = d.slct_min_var_frac;
     w.slct_forced = d.slct_forced; w.n_slct_forced = d.n_slct_forced;
     w.out.slct_n = d.out_slct_n; w.out.slct_idx = d.out_slct_idx; w.out.slct_zin = d.out_slct_zin;

@@ -137,6 +137,15 @@ struct Prob {
     GP(double) traits_Y;                   // [Mld][T16] scratch: Y = X Z
     GP(double) traits_G;                   // [Mld][T16] scratch: G = X^T Y = B11^-1 Z
     GP(double) out_traits;                 // [T][U]
+    // further traits that lack some measured SNPs (k_traits_miss.hip); miss_tab = null: no mask was passed
+    int miss_E, miss_nm, miss_n;           // distinct missing SNPs of the window, traits that lack some, set mask bits
+    GP(const int) miss_tab;                // the mask as index lists: MissTab below
+    GP(double) miss_YE;                    // [Mld][E16] scratch: X e_d, the columns of X of the missing SNPs (E16 = miss_E rounded up to 16)
+    GP(double) miss_AE;                    // [Mld][E16] scratch: A[:, E] = X^T (X e_d), the columns of B11^-1
+    GP(double) miss_YU;                    // [E16][U] scratch: (B21 A[:, E])^T, the entries y_u[d]
+    GP(double) miss_LD;                    // [miss_nm][MISS_LD] scratch: L_D ([k][MISS_K] row-major lower triangle), then c
+    GP(double) out_traits_info;            // [T][U] info per trait
+    GP(double) out_traits_miss;            // [2][miss_n] z, then info, of the SNPs the traits lack, in mask order
 };
 // a descriptor derived from a window's (the job-wide measured rows) carries no rider
 inline void clear_riders(Prob& q)
@@ -145,18 +154,29 @@ inline void clear_riders(Prob& q)
     q.slct_max = q.n_slct_forced = 0; q.slct_chi2_stop = q.slct_min_var_frac = 0.0;
     q.slct_forced = nullptr; q.slct_W = nullptr; q.out_slct = nullptr;
     q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr;
+    q.miss_E = q.miss_nm = q.miss_n = 0; q.miss_tab = nullptr;
+    q.miss_YE = q.miss_AE = q.miss_YU = q.miss_LD = q.out_traits_info = q.out_traits_miss = nullptr;
 }
 constexpr int TRAITS_MAX = 63;         // GAUSS_TRAITS_MORE_MAX
 constexpr int traits_t16(int T) { return (T + 15) & ~15; }
+constexpr int MISS_K = 32;             // GAUSS_TRAITS_MISS_MAX: missing SNPs per trait
+constexpr int MISS_E = 128;            // GAUSS_TRAITS_MISS_UNION_MAX: distinct missing SNPs per window
+constexpr int MISS_LD = MISS_K * MISS_K + MISS_K;      // doubles of one trait's L_D and c in Prob::miss_LD
+// Prob::miss_tab, ints: the window's distinct missing SNPs in ascending order (-1 beyond miss_E); per trait its count of
+// missing SNPs, where its entries start in out_traits_miss, their measured indices (ascending) and their places in `e`; the
+// traits that lack some, in ascending order
+struct MissTab { enum { e = 0, k = e + MISS_E, off = k + 64, idx = off + 64, pos = idx + 64 * MISS_K, masked = pos + 64 * MISS_K, count = masked + 64 }; };
 constexpr int SLCT_K = 32;             // GAUSS_SLCT_MAX
 constexpr int SLCT_T = 512;            // threads of slct_kernel; a thread keeps the "selected" flags of its SNPs in one 64-bit word
 constexpr int SLCT_M_MAX = 64 * SLCT_T;
 
 // ---- the result block ------------------------------------------------------------------------------------------------
 // A window's doubles in the job's result block, in this order and nowhere else written down:
-//     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, the selection]
+//     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, traits_info [T][U], traits_miss [2][n_miss]]
+//     [, the selection]
 // Offsets in doubles from the window's Plan::res_off; a section nobody asked for takes nothing and its offset is that of the next.
-struct ResLayout { size_t z, info, loo, traits, slct, count; };
+// traits_info and traits_miss exist when the window passed a mask (miss): n_miss = its set bits.
+struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, count; };
 // Inside the selection's section, from its start: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] (indices, n and the
 // skipped flag travel as exact doubles).  The host and slct_kernel both read it here.
 struct SlctLayout { size_t n, skipped, idx, zin, joint, zc, var, count; };
@@ -164,10 +184,11 @@ constexpr SlctLayout slct_layout(int M, int K)
 {
     return {0, 1, 2, 2 + (size_t)K, 2 + 2 * (size_t)K, 2 + 3 * (size_t)K, 2 + 3 * (size_t)K + (size_t)M, 2 + 3 * (size_t)K + 2 * (size_t)M};
 }
-constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K)
+constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, bool miss = false, int n_miss = 0)
 {
-    const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_slct = o_traits + (size_t)T * U;
-    return {0, (size_t)n_rhs, o_loo, o_traits, o_slct, o_slct + (K ? slct_layout(M, K).count : 0)};
+    const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_tinfo = o_traits + (size_t)T * U;
+    const size_t o_tmiss = o_tinfo + (miss ? (size_t)T * U : 0), o_slct = o_tmiss + (miss ? 2 * (size_t)n_miss : 0);
+    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_slct + (K ? slct_layout(M, K).count : 0)};
 }
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
@@ -281,6 +302,13 @@ void launch_slct(const Prob* d_probs, const int* d_slctmap, int n, hipStream_t s
 // d_umap = (window, strip of 64 unmeasured SNPs); it runs behind the kernel that writes out_info
 void launch_traits_weights(const Prob* d_probs, const int2* d_map, int n_blocks, hipStream_t s);
 void launch_traits_impute(const Prob* d_probs, const int2* d_umap, int n_strips, hipStream_t s);
+// further traits that lack some measured SNPs (k_traits_miss.hip), for the windows that passed a mask.
+// launch_traits_miss_solve: the columns A[:, E] of B11^-1 of the window's missing SNPs (d_map = (window, 64-row block of X), two launches:
+// the columns of X gathered, then X^T of them), then per (window, trait that lacks some) = d_tmap the Cholesky factor of A_DD, c and the
+// section of the missing SNPs; it runs behind launch_traits_weights.  launch_traits_miss_apply: B21 A[:, E], then per
+// d_umap = (window, strip of 64 unmeasured SNPs) every trait's downdated mean and info; it runs behind launch_traits_impute.
+void launch_traits_miss_solve(const Prob* d_probs, const int2* d_map, int n_blocks, const int2* d_tmap, int n_traits, hipStream_t s);
+void launch_traits_miss_apply(const Prob* d_probs, const int2* d_umap, int n_strips, hipStream_t s);
 void launch_counts(const Prob* d_probs, int prob, int npair, long long* d_out, hipStream_t s);
 void launch_pack2bit(const uint8_t* d_in, long long ld_in, uint8_t* d_out, long long ld_out, int n_snp,
                      const int* d_pop_off, const int* d_blk_off, int n_pop, hipStream_t s);

@@ -238,6 +238,7 @@ struct RiderOuts {
     int32_t *slct_n = nullptr, *slct_idx = nullptr;
     double *slct_zin = nullptr, *slct_joint = nullptr, *slct_zc = nullptr, *slct_var = nullptr;
     double* z_more = nullptr;
+    double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
 };
 // Host-side plan of one problem
 struct Plan {
@@ -276,10 +277,13 @@ struct Plan {
         std::vector<int> slct_forced;
         int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
         std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
+        bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
+        int miss_n = 0;                      // set mask bits
+        std::vector<int> miss_tab;           // Prob::miss_tab (MissTab, gauss_internal.h); empty: no mask
         RiderOuts out;
         bool needs_fused() const { return loo || traits_T > 0; }      // it reads the rows of L^-1 that only the fused solve forms
     } rd;
-    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K); }
+    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n); }
     size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
@@ -336,6 +340,9 @@ struct gauss_job {
     int* d_slctmap = nullptr;   int n_slct = 0;            // signal selection: the windows that asked
     int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
     int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
+    int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some
+    int2* d_misstmap = nullptr; int n_miss_t = 0;          // missing SNPs: (window, k-th trait that lacks some)
+    int2* d_missumap = nullptr; int n_miss_u = 0;          // missing SNPs: (window, strip of 64 unmeasured SNPs) of the windows that passed a mask
     int2* d_loomap = nullptr;   int n_loo = 0;             // leave-one-out: (window, 64-column panel of X) of the windows that asked
     bool needs_fused() const                               // some window rides on the rows of L^-1
     { return std::any_of(plans.begin(), plans.end(), [](const Plan& pl) { return pl.rd.needs_fused(); }); }
@@ -446,6 +453,7 @@ struct WinSpec {
     RiderOuts out;                           // (any of loo_z / loo_info / loo_t non-null: the window asks for leave-one-out values)
     int n_traits_more = 0;                   // further traits on the same window (gauss_window_desc.n_traits_more); 0: not asked
     const double* z_more = nullptr;          // [T x M]
+    const uint8_t* miss_more = nullptr;      // [T x M] non-zero: the trait has no score there (gauss_window_desc.miss_more); NULL: no mask
     int slct_max = 0;                        // signal selection among the measured SNPs (gauss_window_desc.slct_*); 0: not asked
     double slct_chi2_stop = 0.0, slct_min_var_frac = 0.0;
     const int32_t* slct_forced = nullptr;

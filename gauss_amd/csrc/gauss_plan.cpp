@@ -112,6 +112,46 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         if (!w.z_more || !w.out.z_more)
             return fail(GAUSS_E_INVALID, "n_traits_more = %d needs z_more and out_z_more (%s is NULL)", w.n_traits_more, !w.z_more ? "z_more" : "out_z_more");
     }
+    // further traits that lack some measured SNPs (k_traits_miss.hip): the mask as index lists (MissTab)
+    std::vector<int> miss_tab;
+    int miss_n = 0, miss_nm = 0, miss_ne = 0;
+    if (w.miss_more) {
+        if (w.n_traits_more <= 0)
+            return fail(GAUSS_E_INVALID, "miss_more says which SNPs the further traits lack: it needs n_traits_more > 0 (n_traits_more = %d)", w.n_traits_more);
+        if (!w.out.info_more || !w.out.z_miss || !w.out.info_miss)
+            return fail(GAUSS_E_INVALID, "miss_more needs out_info_more, out_z_miss and out_info_miss (%s is NULL)",
+                        !w.out.info_more ? "out_info_more" : !w.out.z_miss ? "out_z_miss" : "out_info_miss");
+        miss_tab.assign(MissTab::count, 0);
+        std::vector<int> pos_of((size_t)w.M, -1);
+        for (int t = 0; t < w.n_traits_more; t++)
+            for (int m = 0; m < w.M; m++)
+                if (w.miss_more[(size_t)t * w.M + m]) pos_of[(size_t)m] = 0;
+        for (int e = 0; e < MISS_E; e++) miss_tab[MissTab::e + e] = -1;
+        for (int m = 0; m < w.M; m++)
+            if (pos_of[(size_t)m] == 0) {
+                if (miss_ne < MISS_E) miss_tab[MissTab::e + miss_ne] = m;
+                pos_of[(size_t)m] = miss_ne++;
+            }
+        if (miss_ne > MISS_E)
+            return fail(GAUSS_E_INVALID, "miss_more: %d distinct measured SNPs are missing in some trait; a window takes at most %d", miss_ne, MISS_E);
+        for (int t = 0; t < w.n_traits_more; t++) {
+            int k = 0;
+            for (int m = 0; m < w.M; m++) k += w.miss_more[(size_t)t * w.M + m] ? 1 : 0;
+            if (k > MISS_K)
+                return fail(GAUSS_E_INVALID, "miss_more: further trait %d lacks %d of the window's measured SNPs; a trait may lack at most %d", t, k, MISS_K);
+            if (k >= w.M)
+                return fail(GAUSS_E_INVALID, "miss_more: further trait %d lacks all %d measured SNPs of the window; every trait keeps at least one", t, w.M);
+            miss_tab[MissTab::k + t] = k;
+            miss_tab[MissTab::off + t] = miss_n;
+            if (k) miss_tab[MissTab::masked + miss_nm++] = t;
+            for (int m = 0, j = 0; m < w.M; m++)
+                if (w.miss_more[(size_t)t * w.M + m]) {
+                    miss_tab[MissTab::idx + t * MISS_K + j] = m;
+                    miss_tab[MissTab::pos + t * MISS_K + j++] = pos_of[(size_t)m];
+                }
+            miss_n += k;
+        }
+    }
 
     Prob& p = pl.p;
     memset(&p, 0, sizeof(p));
@@ -338,9 +378,14 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         const int T16 = traits_t16(w.n_traits_more);
         rd.traits_z.assign((size_t)p.Mld * T16, 0.0);
         for (int t = 0; t < w.n_traits_more; t++)
-            for (int g = 0; g < w.M; g++) rd.traits_z[(size_t)g * T16 + t] = w.z_more[(size_t)t * w.M + g];
+            for (int g = 0; g < w.M; g++)      // (a score the trait lacks is not read: an exact zero takes its place)
+                rd.traits_z[(size_t)g * T16 + t] = (w.miss_more && w.miss_more[(size_t)t * w.M + g]) ? 0.0 : w.z_more[(size_t)t * w.M + g];
         p.traits_T = w.n_traits_more;
     }
+    rd.miss = !miss_tab.empty();
+    rd.miss_n = miss_n;
+    rd.miss_tab.swap(miss_tab);
+    p.miss_E = miss_ne; p.miss_nm = miss_nm; p.miss_n = miss_n;
     return GAUSS_OK;
 }
 
@@ -528,7 +573,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<char>& blob = job->h_tab;
     blob.reserve((size_t)n_prob * ((size_t)320 << 10) + ((size_t)64 << 10));      // (~0.3 MB a window: grown in place, not copied over and over)
     const auto tb2 = std::chrono::steady_clock::now();
-    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch, dc, sf, tz; };
+    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch, dc, sf, tz, mt; };
     std::vector<TabOff> to((size_t)n_prob);
     for (int i = 0; i < n_prob; i++) {
         Plan& pl = plan_of(i);
@@ -557,6 +602,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         to[i].dc = put(blob, ta, pl.draw_col);
         to[i].sf = pl.rd.slct_forced.empty() ? 0 : put(blob, ta, pl.rd.slct_forced);
         to[i].tz = pl.rd.traits_z.empty() ? 0 : put(blob, ta, pl.rd.traits_z);
+        to[i].mt = pl.rd.miss_tab.empty() ? 0 : put(blob, ta, pl.rd.miss_tab);
     }
     // work lists
     struct ItemH { int prob, pair, group, len, b11, ord = 0; };     // b11: an item of B11 (job-wide pairs, or a window's own measured x measured pairs); ord: launch-order key (below)
@@ -564,7 +610,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
     std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
     std::vector<int> slctmap;
-    std::vector<int2> traitsmap, traitsumap;
+    std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
     job->max_nblk = 0;
     {
         // tiles of the closing product at 128 right-hand sides each: a small job (an 8-rank share: ~570) cannot fill the
@@ -638,6 +684,11 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (rd.traits_T) {
             for (int b = 0; b < p.nblk; b++) traitsmap.push_back(make_int2(i, b));
             for (int us = 0; us < (p.U + NB - 1) / NB; us++) traitsumap.push_back(make_int2(i, us));
+        }
+        if (rd.miss) {
+            if (p.miss_nm) for (int b = 0; b < p.nblk; b++) missmap.push_back(make_int2(i, b));
+            for (int k = 0; k < p.miss_nm; k++) misstmap.push_back(make_int2(i, k));
+            for (int us = 0; us < (p.U + NB - 1) / NB; us++) missumap.push_back(make_int2(i, us));
         }
         if (p.npanel > 0) {
             job->max_nblk = std::max(job->max_nblk, p.nblk); job->max_npanel = std::max(job->max_npanel, p.npi);
@@ -845,6 +896,9 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     const size_t o_slctmap = slctmap.empty() ? 0 : put(blob, ta, slctmap);      // (a job in which nobody asks takes nothing)
     const size_t o_traitsmap = traitsmap.empty() ? 0 : put(blob, ta, traitsmap);
     const size_t o_traitsumap = traitsumap.empty() ? 0 : put(blob, ta, traitsumap);
+    const size_t o_missmap = missmap.empty() ? 0 : put(blob, ta, missmap);
+    const size_t o_misstmap = misstmap.empty() ? 0 : put(blob, ta, misstmap);
+    const size_t o_missumap = missumap.empty() ? 0 : put(blob, ta, missumap);
     const size_t o_probs = ta.take(sizeof(Prob) * (size_t)n_prob);
     const size_t o_exports = ta.take(sizeof(ExportD) * std::max<size_t>(job->exports.size(), 1));
     blob.resize(ta.off);
@@ -859,11 +913,14 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n_slct = (int)slctmap.size();
     job->n_traits = (int)traitsmap.size();
     job->n_traits_u = (int)traitsumap.size();
+    job->n_miss_blk = (int)missmap.size();
+    job->n_miss_t = (int)misstmap.size();
+    job->n_miss_u = (int)missumap.size();
 
     // ---- workspace arena ----
     Arena wa;         // zeroed once per job: operand padding, B21 padding and the solve matrices rely on it
     Arena wslab;      // partial slabs: every entry a reader keeps is written by the Gram kernel first, so no zeroing
-    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct, ty, tg; long long ldraw; };
+    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct, ty, tg, mye, mae, myu, mld; long long ldraw; };
     std::vector<WsOff> wo(job->n);
     size_t res = 0;
     {
@@ -923,6 +980,14 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (pl.rd.traits_T) {               // Y = X Z and G = X^T Y of the further traits
             w.ty = wa.take((size_t)p.Mld * traits_t16(pl.rd.traits_T) * sizeof(double));
             w.tg = wa.take((size_t)p.Mld * traits_t16(pl.rd.traits_T) * sizeof(double));
+        }
+        w.mye = w.mae = w.myu = w.mld = 0;
+        if (pl.rd.miss && p.miss_nm) {      // the columns of X and of B11^-1 of the missing SNPs, B21 times them, every trait's L_D and c
+            const size_t E16 = (size_t)traits_t16(p.miss_E);
+            w.mye = wa.take((size_t)p.Mld * E16 * sizeof(double));
+            w.mae = wa.take((size_t)p.Mld * E16 * sizeof(double));
+            w.myu = wa.take(E16 * (size_t)p.U * sizeof(double));
+            w.mld = wa.take((size_t)p.miss_nm * MISS_LD * sizeof(double));
         }
         w.ld = wa.take(std::max<size_t>(pl.out_ld_count, 1) * sizeof(double));
         pl.res_off = res;
@@ -1075,6 +1140,14 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.traits_Z = pl.rd.traits_T ? (const double*)(T + to[i].tz) : nullptr;
         p.traits_Y = pl.rd.traits_T ? (double*)(W + w.ty) : nullptr;
         p.traits_G = pl.rd.traits_T ? (double*)(W + w.tg) : nullptr;
+        p.miss_tab = pl.rd.miss ? (const int*)(T + to[i].mt) : nullptr;
+        const bool miss_ws = pl.rd.miss && p.miss_nm;
+        p.miss_YE = miss_ws ? (double*)(W + w.mye) : nullptr;
+        p.miss_AE = miss_ws ? (double*)(W + w.mae) : nullptr;
+        p.miss_YU = miss_ws ? (double*)(W + w.myu) : nullptr;
+        p.miss_LD = miss_ws ? (double*)(W + w.mld) : nullptr;
+        p.out_traits_info = pl.rd.miss ? out + lay.traits_info : nullptr;
+        p.out_traits_miss = pl.rd.miss ? out + lay.traits_miss : nullptr;
         p.status = job->d_status + 4 * i;
         p.out_ld = (double*)(W + w.ld);
         p.gene_off = p.n_gene ? (const int*)(T + to[i].goff) : nullptr;
@@ -1211,6 +1284,9 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->d_slctmap = (int*)(job->d_tab + o_slctmap);
     job->d_traitsmap = (int2*)(job->d_tab + o_traitsmap);
     job->d_traitsumap = (int2*)(job->d_tab + o_traitsumap);
+    job->d_missmap = (int2*)(job->d_tab + o_missmap);
+    job->d_misstmap = (int2*)(job->d_tab + o_misstmap);
+    job->d_missumap = (int2*)(job->d_tab + o_missumap);
     job->d_exports = (ExportD*)(job->d_tab + o_exports);
     if (!on_device && !streamed) HIPCHK(hipStreamSynchronize(st));   // uploads from pageable user memory are complete
     std::vector<char>().swap(job->h_tab);

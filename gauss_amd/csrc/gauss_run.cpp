@@ -85,11 +85,13 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 }
 
 // The tail of a fused solve, in the one order its inputs allow:
-//     loo -> selection -> traits weights -> closing step -> traits impute
+//     loo -> selection -> traits weights -> miss solve -> closing step -> traits impute -> miss apply
 //   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
 //     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
 //   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
-//   - traits impute divides B21 G by the info the closing step's finish kernel has just written.
+//   - traits impute divides B21 G by the info the closing step's finish kernel has just written;
+//   - traits that lack some measured SNPs (k_traits_miss.hip): the solve reads [X | y] like the traits weights, and their G; the
+//     apply step takes the raw means traits impute has left for such traits, and the info.
 // The closing step of a run is the product B21 [X | y] with its finish kernel.  A launch for which no window asked is skipped by its
 // launcher.  The clamp path (job_clamp_window) keeps the same order with its single-window map and the stand-alone solve as its
 // closing step; its selection runs in front of the re-factorisation.
@@ -98,8 +100,10 @@ static void queue_tail(gauss_job* job, hipStream_t st)
     launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
     launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
     launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
+    launch_traits_miss_solve(job->d_probs, job->d_missmap, job->n_miss_blk, job->d_misstmap, job->n_miss_t, st);
     launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
     launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
+    launch_traits_miss_apply(job->d_probs, job->d_missumap, job->n_miss_u, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -457,26 +461,29 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     // a window that rides on the rows of L^-1: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this factorisation
     // as they do in a run's (same L either way), and the stand-alone solve below is this tail's closing step (queue_tail): it
     // takes V as its scratch, only reads B21 and leaves the info the further traits are divided by
-    const bool loo = pl.rd.loo, traits = pl.rd.traits_T > 0, ride = pl.rd.needs_fused();
+    const bool loo = pl.rd.loo, traits = pl.rd.traits_T > 0, miss = pl.rd.miss, ride = pl.rd.needs_fused();
     for (int s = 0; s < p.nblk; s++) {
         // launch over all problems would redo the others; use a single-problem launch instead
         launch_factor_step(job->d_probs + i, 1, s, p.nblk, ride ? p.npi : 0, ride ? job->solve_split : 0, 0, st);
     }
     const int n_us = (p.U + NB - 1) / NB;                    // strips of unmeasured SNPs of the further traits' product
     if (ride) {
-        // (window, 0 .. n): read as panels by solve_last / loo, as blocks of X and as strips of unmeasured SNPs by the traits kernels
+        // (window, 0 .. n): read as panels by solve_last / loo, as blocks of X, as strips of unmeasured SNPs and as the traits that
+        // lack some SNPs by the traits kernels
         std::vector<int2> lm;
-        for (int pn = 0; pn < std::max(p.npi, traits ? n_us : 0); pn++) lm.push_back(make_int2(i, pn));
+        for (int pn = 0; pn < std::max(std::max(p.npi, traits ? n_us : 0), miss ? p.miss_nm : 0); pn++) lm.push_back(make_int2(i, pn));
         const int n_x = (p.M + NR - 1) / NR;                 // the panels that hold columns of X come first
         HIPCHK(d_lm.alloc(job->ctx, sizeof(int2) * lm.size()));
         HIPCHK(hipMemcpyAsync(d_lm.p, lm.data(), sizeof(int2) * lm.size(), hipMemcpyHostToDevice, st));
         launch_solve_last(job->d_probs, d_lm.as<int2>(), p.npi, p.nblk, job->solve_split, st);
         if (loo) launch_loo(job->d_probs, d_lm.as<int2>(), n_x, st);
         if (traits) launch_traits_weights(job->d_probs, d_lm.as<int2>(), p.nblk, st);
+        if (miss) launch_traits_miss_solve(job->d_probs, d_lm.as<int2>(), p.miss_nm ? p.nblk : 0, d_lm.as<int2>(), p.miss_nm, st);
         HIPCHK(hipStreamSynchronize(st));                    // (`lm` is pageable: the copy has read it)
     }
     launch_solve(job->d_probs, d_pm.as<int2>(), (int)pm.size(), st);
     if (traits) launch_traits_impute(job->d_probs, d_lm.as<int2>(), n_us, st);
+    if (miss) launch_traits_miss_apply(job->d_probs, d_lm.as<int2>(), n_us, st);
     HIPCHK(hipGetLastError());
     int h_status[4];
     HIPCHK(hipMemcpyAsync(h_status, p.status, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
@@ -692,6 +699,11 @@ int job_fetch(gauss_job* job)
                 copy_out(rd.out.loo_t, res + lay.loo + 2 * (size_t)p.M, p.M);
             }
             if (rd.traits_T) copy_out(rd.out.z_more, res + lay.traits, (size_t)rd.traits_T * p.U);      // the further traits (k_traits.hip)
+            if (rd.miss) {                         // ... that lack some measured SNPs (k_traits_miss.hip)
+                copy_out(rd.out.info_more, res + lay.traits_info, (size_t)rd.traits_T * p.U);
+                copy_out(rd.out.z_miss, res + lay.traits_miss, (size_t)rd.miss_n);
+                copy_out(rd.out.info_miss, res + lay.traits_miss + rd.miss_n, (size_t)rd.miss_n);
+            }
             if (rd.slct_K) {                       // signal selection (k_slct.hip)
                 const int K = rd.slct_K;
                 if (rd.out.slct_n) *rd.out.slct_n = (int32_t)sel[sl.n];

@@ -258,7 +258,7 @@ int gauss_prepared_finish(gauss_prepared* p, gauss_table** out)
 // those rows.  Measured on the chr22 study, window after window (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.  Otherwise
 // the literal path: prepare_opened + gauss_impute_window on host rows.
 struct SlctAsk { double p_cutoff, collin; int max_signals; const char* const* cond; int n_cond; };      // the extra arguments of the *_slct calls
-struct TraitsAsk { const char* const* files; int n; };                                                  // ... of the *_traits calls
+struct TraitsAsk { const char* const* files; int n; bool miss = false; };                               // ... of the *_traits calls; miss: a SNP a further file lacks is imputed for that trait (*_traits_miss)
 static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
                       const char* const* names, const double* wgts, int nw, const char* input, const char* index,
                       const char* data, const char* desc, double af1_cutoff, gauss_table** out, bool loo = false, const SlctAsk* slct = nullptr,
@@ -269,17 +269,31 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
     // traits (dist_traits / distmix_traits): `input` is trait 1 and defines the window exactly as in the plain call; every further file
     // is matched to the window's measured SNPs (traits_match) and rides in the same single job as n_traits_more / z_more of
     // gauss_window_desc; the table is the plain call's with the named matrices z_traits / pval_traits added (traits_output)
-    std::vector<double> t_z, t_out;
+    // With traits->miss (the *_traits_miss calls) a measured SNP a further file lacks becomes a bit of miss_more instead of an error, and
+    // the window returns that trait's own info and the imputed z of the SNPs it lacks (traits_miss_limits: the limits, before any GPU work)
+    std::vector<double> t_z, t_out, t_info, t_zmiss, t_imiss;
+    std::vector<uint8_t> t_mask;
+    TraitsMiss t_miss = {nullptr, nullptr, nullptr, nullptr};
     auto ask_traits = [&](gauss_window_desc& d, const std::function<SnpIdent(size_t)>& at) -> int {
         const size_t M = (size_t)d.n_measured, U = (size_t)d.n_unmeasured;
         t_z.assign((size_t)traits->n * M, 0.0); t_out.assign((size_t)traits->n * U, 0.0);
+        if (traits->miss) t_mask.assign((size_t)traits->n * M, 0);
+        size_t n_miss = 0;
         for (int k = 0; k < traits->n; k++) {
             std::string err;
             std::shared_ptr<const GwasCache> gw = load_gwas_cached(traits->files[k], err);
             if (!gw) return herr("%s", err.c_str());
-            if (traits_match(*gw, traits->files[k], M, at, t_z.data() + (size_t)k * M)) return -1;
+            size_t lacks = 0;
+            if (traits_match(*gw, traits->files[k], M, at, t_z.data() + (size_t)k * M, traits->miss ? t_mask.data() + (size_t)k * M : nullptr, &lacks)) return -1;
+            n_miss += lacks;
         }
         if (traits->n > 0) { d.n_traits_more = traits->n; d.z_more = t_z.data(); d.out_z_more = t_out.data(); }
+        if (traits->n > 0 && traits->miss) {
+            if (traits_miss_limits(traits->files, traits->n, M, t_mask.data(), Args().min_num_measured_snp)) return -1;
+            t_info.assign((size_t)traits->n * U, 0.0); t_zmiss.assign(std::max<size_t>(n_miss, 1), 0.0); t_imiss = t_zmiss;
+            d.miss_more = t_mask.data(); d.out_info_more = t_info.data(); d.out_z_miss = t_zmiss.data(); d.out_info_miss = t_imiss.data();
+            t_miss = TraitsMiss{t_mask.data(), t_info.data(), t_zmiss.data(), t_imiss.data()};
+        }
         return 0;
     };
     if (traits) {
@@ -374,7 +388,7 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
             std::vector<int32_t> row_m, row_u;
             for (int32_t vi : ow.w.measured) row_m.push_back(ow.w.out_row[(size_t)vi]);
             for (int32_t vi : ow.w.unmeasured) row_u.push_back(ow.w.out_row[(size_t)vi]);
-            traits_output(**out, traits->n, row_m, row_u, t_z.data(), t_out.data());
+            traits_output(**out, traits->n, row_m, row_u, t_z.data(), t_out.data(), t_miss.mask ? &t_miss : nullptr);
         }
         return 0;
     }
@@ -414,7 +428,7 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
             for (const Snp* sn : v) { auto it = row_of.find(sn); r.push_back(it == row_of.end() ? -1 : it->second); }
             return r;
         };
-        traits_output(**out, traits->n, rows(p->measured), rows(p->unmeasured), t_z.data(), t_out.data());
+        traits_output(**out, traits->n, rows(p->measured), rows(p->unmeasured), t_z.data(), t_out.data(), t_miss.mask ? &t_miss : nullptr);
     }
     return 0;
 }
@@ -491,6 +505,26 @@ int gauss_host_distmix_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t
                               double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out)
 {
     const TraitsAsk ask = {more_input_files, n_more};
+    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
+                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
+}
+
+int gauss_host_dist_traits_miss(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                                const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                                const char* reference_pop_desc_file, double af1_cutoff, const char* const* more_input_files, int n_more,
+                                gauss_table** out)
+{
+    const TraitsAsk ask = {more_input_files, n_more, true};
+    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
+                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
+}
+
+int gauss_host_distmix_traits_miss(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                                   const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                                   const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                                   double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out)
+{
+    const TraitsAsk ask = {more_input_files, n_more, true};
     return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
                       input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
 }

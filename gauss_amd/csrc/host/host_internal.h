@@ -528,13 +528,26 @@ gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, 
 // by (chr, bp, a1, a2): the same allele order gives z, the swapped order -z (gauss.cpp:358-370); of several rows that match, the
 // later one wins; rows for other SNPs are ignored.  Refused: a SNP without a row (the message names the file, the first missing
 // rsid and how many are missing) and a z that is not finite.
-int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out);
+// With miss_out [n] (dist_traits_miss / distmix_traits_miss): a SNP without a row sets miss_out[i] = 1 (z_out[i] = 0) instead of being
+// refused, and *n_missing counts them; a z that is present and not finite is still refused.
+int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out,
+                 uint8_t* miss_out = nullptr, size_t* n_missing = nullptr);
+// The limits of a window whose further files lack SNPs, checked before any GPU work; mask [n_more][M] as traits_match filled it, paths
+// [n_more] name the files in the messages.  Refused, naming the file, the count and the limit: a file that lacks more than
+// GAUSS_TRAITS_MISS_MAX of the window's measured SNPs, one left with min_measured or fewer (the reference would refuse that trait:
+// dist.cpp:145-151), and a window in which more than GAUSS_TRAITS_MISS_UNION_MAX distinct SNPs are missing.
+int traits_miss_limits(const char* const* paths, int n_more, size_t M, const uint8_t* mask, int min_measured);
+// what the window returned for the SNPs the further traits lack (miss_more / out_info_more / out_z_miss / out_info_miss of gauss_window_desc)
+struct TraitsMiss { const uint8_t* mask; const double* info_more; const double* z_miss; const double* info_miss; };
 // ... and their part of the table: `t` is dist_output's table of trait 1, unchanged; two named matrices are added, z_traits and
 // pval_traits [nrow x (1 + n_more)], column 0 the table's own z / pval, column 1 + k trait k: for a measured SNP its own study z
 // (z_more [n_more][M]), for an unmeasured one the imputed z (out_z_more [n_more][U]); pval = 2 pnorm(-|z|).  row_m[i] / row_u[i]:
 // the table row of measured / unmeasured SNP i, -1 when the table does not list it (the wings)
+// With `miss` (the *_traits_miss calls): info_traits and type_traits [nrow x (1 + n_more)] are added, column 0 the table's own info /
+// type; a measured SNP that trait k lacks shows its imputed z, its info and type 0 in column 1 + k, an unmeasured SNP the trait's own
+// info; and n_missing [1 + n_more]: how many of the window's measured SNPs (wings included) each trait's file lacked (trait 1: 0).
 void traits_output(gauss_table& t, int n_more, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
-                   const double* z_more, const double* out_z_more);
+                   const double* z_more, const double* out_z_more, const TraitsMiss* miss = nullptr);
 // the smallest chi^2 (1 df) whose two-sided p-value 2 pnorm_upper(sqrt(chi2)) is below p, to the bit
 double slct_chi2_of(double p);
 gauss_table* prep_output(gauss_prepared& p);

@@ -261,7 +261,8 @@ gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, 
     return t;
 }
 
-int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out)
+int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out,
+                 uint8_t* miss_out, size_t* n_missing)
 {
     size_t missing = 0;
     std::string first_missing;
@@ -277,18 +278,38 @@ int traits_match(const GwasCache& gw, const char* path, size_t n, const std::fun
             if (r.a1 == s.a1 && r.a2 == s.a2) { z = r.z; found = true; }
             else if (r.a1 == s.a2 && r.a2 == s.a1) { z = -r.z; found = true; }        // gauss.cpp:358-370
         }
-        if (!found) { if (!missing++) first_missing = s.rsid; continue; }
+        if (miss_out) miss_out[i] = found ? 0 : 1;
+        if (!found) { if (!missing++) first_missing = s.rsid; if (miss_out) z_out[i] = 0.0; continue; }
         if (!std::isfinite(z)) return herr("ERROR: %s: the z of %s is not finite", path, s.rsid);
         z_out[i] = z;
     }
-    if (missing)
+    if (n_missing) *n_missing = missing;
+    if (missing && !miss_out)
         return herr("ERROR: %s lacks %zu of the window's %zu measured SNPs, the first is %s: every trait must be measured at the SNPs of the first",
                     path, missing, n, first_missing.c_str());
     return 0;
 }
 
+int traits_miss_limits(const char* const* paths, int n_more, size_t M, const uint8_t* mask, int min_measured)
+{
+    std::vector<uint8_t> any(M, 0);
+    for (int k = 0; k < n_more; k++) {
+        size_t lacks = 0;
+        for (size_t i = 0; i < M; i++) if (mask[(size_t)k * M + i]) { lacks++; any[i] = 1; }
+        if (lacks > (size_t)GAUSS_TRAITS_MISS_MAX)
+            return herr("ERROR: %s lacks %zu of the window's %zu measured SNPs: a trait may lack at most %d of them", paths[k], lacks, M, GAUSS_TRAITS_MISS_MAX);
+        if (M - lacks <= (size_t)min_measured)
+            return herr("ERROR: %s has %zu of the window's %zu measured SNPs: a trait needs more than %d", paths[k], M - lacks, M, min_measured);
+    }
+    const size_t distinct = (size_t)std::count(any.begin(), any.end(), (uint8_t)1);
+    if (distinct > (size_t)GAUSS_TRAITS_MISS_UNION_MAX)
+        return herr("ERROR: %zu distinct measured SNPs of the window are missing in one of the %d further files (the last is %s): a window takes at most %d",
+                    distinct, n_more, paths[n_more - 1], GAUSS_TRAITS_MISS_UNION_MAX);
+    return 0;
+}
+
 void traits_output(gauss_table& t, int n_more, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
-                   const double* z_more, const double* out_z_more)
+                   const double* z_more, const double* out_z_more, const TraitsMiss* miss)
 {
     const size_t nrow = (size_t)t.nrow(), M = row_m.size(), U = row_u.size();
     std::vector<double> z(nrow * (size_t)(1 + n_more), NAN), pv(nrow * (size_t)(1 + n_more), NAN);
@@ -303,8 +324,37 @@ void traits_output(gauss_table& t, int n_more, const std::vector<int32_t>& row_m
         for (size_t i = 0; i < U; i++) if (row_u[i] >= 0) zc[(size_t)row_u[i]] = out_z_more[(size_t)k * U + i];
         for (size_t r = 0; r < nrow; r++) pc[r] = 2 * pnorm_upper(fabs(zc[r]));       // dist.cpp:101
     }
+    std::vector<double> info, type, n_missing;
+    if (miss) {
+        // a present measured SNP and every SNP's type: as in the table's own columns (the same SNP, the same window)
+        info.assign(nrow * (size_t)(1 + n_more), NAN); type = info;
+        n_missing.assign((size_t)(1 + n_more), 0.0);
+        for (const Column& c : t.cols) {
+            if (c.name == "info") for (int k = 0; k <= n_more; k++) std::copy(c.d.begin(), c.d.end(), info.begin() + nrow * (size_t)k);
+            if (c.name == "type") for (int k = 0; k <= n_more; k++) std::copy(c.i.begin(), c.i.end(), type.begin() + nrow * (size_t)k);
+        }
+        size_t at = 0;                                                 // z_miss / info_miss: one entry per set mask bit, in mask order
+        for (int k = 0; k < n_more; k++) {
+            const size_t col = nrow * (size_t)(1 + k);
+            for (size_t i = 0; i < U; i++) if (row_u[i] >= 0) info[col + (size_t)row_u[i]] = miss->info_more[(size_t)k * U + i];
+            for (size_t i = 0; i < M; i++) {
+                if (!miss->mask[(size_t)k * M + i]) continue;
+                n_missing[(size_t)(1 + k)] += 1.0;
+                if (row_m[i] >= 0) {
+                    const size_t r = col + (size_t)row_m[i];
+                    z[r] = miss->z_miss[at]; pv[r] = 2 * pnorm_upper(fabs(z[r])); info[r] = miss->info_miss[at]; type[r] = 0.0;
+                }
+                at++;
+            }
+        }
+    }
     t.put_named("z_traits", (int)nrow, 1 + n_more, std::move(z));
     t.put_named("pval_traits", (int)nrow, 1 + n_more, std::move(pv));
+    if (miss) {
+        t.put_named("info_traits", (int)nrow, 1 + n_more, std::move(info));
+        t.put_named("type_traits", (int)nrow, 1 + n_more, std::move(type));
+        t.put_named("n_missing", 1 + n_more, 1, std::move(n_missing));
+    }
 }
 
 // Positive doubles order as their bit patterns do: bisection on the pattern ends at the last bit that changes the comparison.

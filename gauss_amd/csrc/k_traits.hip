@@ -16,42 +16,13 @@
 //   traits_weights_kernel, pass 0:  Y = X Z      block row kb of Y from the blocks (kb, 0 .. kb) of X
 //   traits_weights_kernel, pass 1:  G = X^T Y    block row p of G from the blocks (p .. nblk - 1, p) of X, read transposed
 //   traits_impute_kernel:           B21 G, divided by sqrt(out_info): a strip of 64 unmeasured SNPs, every B21 entry read once
+//                                   (a trait that lacks some measured SNPs keeps its raw mean for k_traits_miss.hip, undivided)
 // Pass 1 needs all of Y: the two passes are two launches, no atomics, no parked sums.  A column of the output is a chain of
 // MFMAs over k in ascending order whose B operand is that column alone: trait t depends on its own Z-scores only -- not on T,
 // not on the traits beside it -- and every launch form returns the same bits.  No scratch memory; 34 KB (weights) and 50 KB (product) of LDS.
-#include "gauss_internal.h"
-#include "k_solve_common.h"
+#include "k_traits_common.h"      // the tiles, the MFMA chain and the two K loops, shared with k_traits_miss.hip
 
 namespace gauss {
-
-constexpr int TK = 32;                 // K per stage
-constexpr int TLA = TK + 2;            // LDS leading dimension of the [64 rows][TK] A tile
-constexpr int TLB = NB + 2;            // LDS leading dimension of the [TK][64 columns] B tile
-constexpr int TLO = NB + 2;            // ... of the [64 traits][64 SNPs] output tile of traits_impute_kernel (it reuses the A tile's place)
-
-// acc[n] += A (rows 16 wave .., [row][k], TLA) * B ([k][column], TLB) over one stage; nt = live 16-column tiles (wave-uniform)
-__device__ __forceinline__ void traits_mma(f64x4 (&acc)[4], const double* __restrict__ A, const double* __restrict__ B, int wave, int lane, int nt)
-{
-    const double* ap = A + (16 * wave + (lane & 15)) * TLA + (lane >> 4);
-    const double* bp = B + (lane >> 4) * TLB + (lane & 15);
-#pragma unroll
-    for (int k0 = 0; k0 < TK; k0 += 4) {
-        const double a = ap[k0];
-#pragma unroll
-        for (int n = 0; n < 4; n++)
-            if (n < nt) acc[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bp[k0 * TLB + 16 * n], acc[n], 0, 0, 0);
-    }
-}
-
-// rows [k0, k0 + TK) of a [Mld][T16] matrix into the B tile; the columns from T16 on are never read by traits_mma
-template <typename P>
-__device__ __forceinline__ void traits_load_b(double* __restrict__ TB, P src, int k0, int T16, int tid)
-{
-    for (int e = tid; e < TK * NB; e += 256) {
-        const int r = e >> 6, c = e & 63;
-        if (c < T16) TB[r * TLB + c] = src[(size_t)(k0 + r) * T16 + c];
-    }
-}
 
 __global__ __launch_bounds__(256) void traits_weights_kernel(const Prob* __restrict__ probs, const int2* __restrict__ map, int pass)
 {
@@ -79,26 +50,14 @@ __global__ __launch_bounds__(256) void traits_weights_kernel(const Prob* __restr
                 const double x = xp[(size_t)k * NR + c];           // in range whatever it holds: panel <= blk < npi, k < Mld, column < NR
                 TA[r * TLA + c] = (g <= k && k < M) ? x : 0.0;
             }
-            traits_load_b(TB, pb.traits_Z, g0, T16, tid);
+            traits_load_b(TB, pb.traits_Z, g0, T16, T16, tid);
             __syncthreads();
             traits_mma(acc, TA, TB, wave, lane, nt);
             __syncthreads();
         }
     } else {
         // G[64 blk + c][t] = sum over k >= g of X[k][g] Y[k][t]: stages of 32 rows k from the diagonal block down to row M
-        const auto xp = pb.V + (size_t)blk * ld * NR;
-        for (int k0 = blk * NB; k0 < M; k0 += TK) {
-            for (int e = tid; e < TK * NB; e += 256) {
-                const int r = e >> 6, c = e & 63;                  // c fastest: a row of the panel is 512 contiguous bytes
-                const int k = k0 + r, g = blk * NB + c;
-                const double x = xp[(size_t)k * NR + c];           // in range: k < Mld
-                TA[c * TLA + r] = (g <= k && k < M) ? x : 0.0;
-            }
-            traits_load_b(TB, pb.traits_Y, k0, T16, tid);
-            __syncthreads();
-            traits_mma(acc, TA, TB, wave, lane, nt);
-            __syncthreads();
-        }
+        traits_xt_y(acc, pb.V, pb.traits_Y, blk, M, ld, T16, T16, TA, TB, tid, wave, lane);
     }
     const auto out = pass == 0 ? pb.traits_Y : pb.traits_G;
 #pragma unroll
@@ -126,31 +85,19 @@ __global__ __launch_bounds__(256) void traits_impute_kernel(const Prob* __restri
 #pragma unroll
     for (int n = 0; n < 4; n++) acc[n] = f64x4{0.0, 0.0, 0.0, 0.0};
 
-    for (int m0 = 0; m0 < M; m0 += TK) {
-        for (int e = tid; e < NB * TK; e += 256) {
-            const int r = e / TK, c = e % TK;
-            const int u = u0 + r, m = m0 + c;
-            const double b = pb.B21[(size_t)min(u, U - 1) * ld + m];       // m < Mld
-            TA[r * TLA + c] = (u < U && m < M) ? b : 0.0;
-        }
-        traits_load_b(TB, pb.traits_G, m0, T16, tid);
-        __syncthreads();
-        traits_mma(acc, TA, TB, wave, lane, nt);
-        __syncthreads();
-    }
+    traits_b21_g(acc, pb.B21, pb.traits_G, u0, U, M, ld, T16, T16, TA, TB, tid, wave, lane);
     // through LDS, trait-major: the result block holds [T][U], a wave's accumulators hold 16 SNPs x 16 traits
-#pragma unroll
-    for (int n = 0; n < 4; n++) {
-        if (n >= nt) continue;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            TA[(16 * n + (lane & 15)) * TLO + 16 * wave + (lane >> 4) + 4 * r] = acc[n][r];
-    }
+    traits_acc_to_lds(acc, TA, nt, wave, lane);
     __syncthreads();
+    // a trait that lacks some measured SNPs keeps its raw mean: traits_miss_apply_kernel adds its correction and divides by its own info
+    const auto miss_k = pb.miss_tab ? pb.miss_tab + MissTab::k : pb.miss_tab;
     for (int e = tid; e < NB * NB; e += 256) {
         const int t = e >> 6, r = e & 63;
         const int u = u0 + r;
-        if (t < T && u < U) pb.out_traits[(size_t)t * U + u] = TA[t * TLO + r] / sqrt(pb.out_info[u]);      // dist.cpp:200
+        if (t < T && u < U) {
+            const double raw = TA[t * TLO + r];
+            pb.out_traits[(size_t)t * U + u] = (miss_k && miss_k[t] > 0) ? raw : raw / sqrt(pb.out_info[u]);      // dist.cpp:200
+        }
     }
 }
 

@@ -272,7 +272,7 @@ class _Win:
     """Keeps the numpy buffers of one window alive next to its C descriptor."""
 
     def __init__(self, desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig,
-                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None, z_more=None):
+                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None, z_more=None, miss_more=None):
         self.po, self.w = _pops(pop_off, pop_wgt)
         self.z1 = np.ascontiguousarray(z1, dtype=np.float64)
         if dev_ptrs is None:
@@ -341,6 +341,18 @@ class _Win:
             self.out_z_more = np.zeros((T, U))
             desc.n_traits_more = T
             desc.z_more, desc.out_z_more = _lib.ptr(self.z_more if T else None, _dp), _lib.ptr(self.out_z_more if T else None, _dp)
+        # ... that lack some of the measured SNPs (miss_more / out_info_more / out_z_miss / out_info_miss): mask [T, M], non-zero = no score
+        self.miss = None
+        if miss_more is not None:
+            mask = np.ascontiguousarray(np.asarray(miss_more) != 0, dtype=np.uint8)
+            T = 0 if self.z_more is None else self.z_more.shape[0]
+            if T == 0 or mask.shape != (T, M):
+                raise ValueError(f"miss_more must be [{T}, {M}] like z_more, got {mask.shape}")
+            n = int(mask.sum())
+            self.miss = dict(mask=mask, info_more=np.zeros((T, U)), z=np.zeros(max(n, 1)), info=np.zeros(max(n, 1)))
+            desc.miss_more = mask.ctypes.data
+            desc.out_info_more = self.miss["info_more"].ctypes.data_as(_dp)
+            desc.out_z_miss, desc.out_info_miss = self.miss["z"].ctypes.data_as(_dp), self.miss["info"].ctypes.data_as(_dp)
         if packed is not None:
             # packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=): rows taken from a row store (dev_ptrs or
             # geno_m/geno_u give its base pointer and stride), optionally 2-bit packed (include/gauss_hip.h)
@@ -385,6 +397,14 @@ class _Win:
             out["loo_z"], out["loo_info"], out["loo_t"] = self.loo[0], self.loo[1], self.loo[2]
         if self.out_z_more is not None:
             out["z_more"] = self.out_z_more
+        if self.miss is not None:
+            # the compact arrays hold one entry per set mask bit in mask order: scattered here, NaN where nothing is missing
+            m = self.miss
+            at = m["mask"] != 0
+            n = int(at.sum())
+            out["info_more"] = m["info_more"]
+            out["z_miss"], out["info_miss"] = np.full(at.shape, np.nan), np.full(at.shape, np.nan)
+            out["z_miss"][at], out["info_miss"][at] = m["z"][:n], m["info"][:n]
         if self.slct is not None:
             s, n = self.slct, int(self.slct["n"][0])
             out.update(slct_n=n, slct_idx=s["idx"][:n].copy(), slct_zin=s["zin"][:n].copy(), slct_joint=s["joint"][:n].copy(),
@@ -393,7 +413,7 @@ class _Win:
 
 
 def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_eig=1e-5,
-                  want_mats=False, ctx=None, loo=False, slct=None, z_more=None):
+                  want_mats=False, ctx=None, loo=False, slct=None, z_more=None, miss_more=None):
     """run_dist (mode 0, dist.cpp:129-227) / run_distmix (mode 1, distmix.cpp:138-253).
     loo=True adds loo_z, loo_info, loo_t [M]: every measured SNP re-imputed from the other measured SNPs, and its
     standardised residual (include/gauss_hip.h, out_loo_*).
@@ -401,10 +421,14 @@ def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_e
     (include/gauss_hip.h, slct_*): slct_n, slct_idx / slct_zin / slct_joint [n] in order of entry, slct_zc / slct_var [M]; status bit
     8 when a forced SNP failed the collinearity guard.
     z_more [T, M] (T <= 63) adds z_more [T, U]: the Z-scores of T further traits measured at the same SNPs, imputed from the same LD
-    and the same factorisation (include/gauss_hip.h, n_traits_more); row t is what z would be with z1 = z_more[t]."""
+    and the same factorisation (include/gauss_hip.h, n_traits_more); row t is what z would be with z1 = z_more[t].
+    miss_more [T, M] (non-zero: further trait t has no score at measured SNP m; at most 32 per trait, 128 distinct per window) makes row t
+    what the window returns for trait t alone with those SNPs unmeasured (include/gauss_hip.h, miss_more) and adds info_more [T, U], the
+    info per trait, and z_miss / info_miss [T, M]: the imputed Z-scores and the info of the SNPs a trait lacks, NaN elsewhere."""
     ctx = ctx or default_context()
     desc = WindowDesc()
-    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct, z_more=z_more)
+    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct, z_more=z_more,
+               miss_more=miss_more)
     check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
     return win.result()
 
@@ -536,11 +560,12 @@ class Job:
     """A batch of windows sharing every launch (gauss_job_*)."""
 
     def __init__(self, windows, ctx=None, on_device=False, want_mats=False):
-        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more])
+        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more, miss_more])
         or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
         loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs).
         slct=dict(max=, chi2_stop=, collin=, forced=) in a window's dict: its result carries the signal selection (impute_window).
-        z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window)."""
+        z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window).
+        miss_more=[T, M] beside it: the SNPs each further trait lacks; the result carries info_more, z_miss, info_miss (impute_window)."""
         self.ctx = ctx or default_context()
         n = len(windows)
         self.descs = (WindowDesc * n)()
@@ -549,7 +574,7 @@ class Job:
             self.wins.append(_Win(self.descs[i], w["mode"], w.get("geno_m"), w.get("geno_u"),
                                   w["pop_off"], w.get("pop_wgt"), w["z1"], w.get("lam", 0.1),
                                   w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed"),
-                                  loo=bool(w.get("loo", False)), slct=w.get("slct"), z_more=w.get("z_more")))
+                                  loo=bool(w.get("loo", False)), slct=w.get("slct"), z_more=w.get("z_more"), miss_more=w.get("miss_more")))
         h = C.c_void_p()
         check(self.ctx.lib.gauss_job_create(self.ctx.handle, self.descs, n, 1 if on_device else 0,
                                             C.byref(h)))

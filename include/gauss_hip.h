@@ -156,6 +156,33 @@ typedef struct gauss_window_desc {
      * n_traits_more = 0: off.  GAUSS_ST_NONFINITE windows return NaN for every trait.  QCAT and LD windows that ask,
      * n_traits_more < 0 or > GAUSS_TRAITS_MORE_MAX, and n_traits_more > 0 with z_more or out_z_more NULL are
      * GAUSS_E_INVALID.  (The block sits in front of the leave-one-out arrays, which stay the descriptor's last three fields.) */
+    /* ---- further traits that lack some of the window's measured SNPs (needs n_traits_more > 0) -------------------
+     * Per-trait quality control drops a handful of SNPs from every trait's file.  miss_more[t][m] != 0 says that further trait t
+     * has no score at measured SNP m; z_more[t][m] is then not read as a value (anything, a NaN included, gives the bits 0.0
+     * gives).  With D the set of SNPs trait t lacks (|D| = k), A = B^-1 = X^T X (X = L^-1), z0 = z_more[t] with zeros on D,
+     * g0 = A z0, b_u row u of B21, y_u = A b_u^T and L_D L_D^T = A_DD (a principal block of a positive definite matrix):
+     *   c      = -A_DD^-1 g0_D                    the conditional mean of the missing SNPs themselves
+     *   mean_u = b_u . g0 + sum_{d in D} y_u[d] c_d
+     *   out_info_more[t][u] = | out_info[u] - || L_D^-1 y_u[D] ||^2 |,   out_z_more[t][u] = mean_u / sqrt(out_info_more[t][u])
+     *   for d in D: out_info_miss = | B_dd - (A_DD^-1)_dd |,   out_z_miss = c_d / sqrt(out_info_miss)
+     * which is what run_dist / run_distmix return for trait t alone when the window is run with the measured SNPs outside D as
+     * its measured set and the SNPs of D as further unmeasured SNPs -- a rank-k downdate of what the job holds, no
+     * factorisation per trait; out_loo_* is the case k = 1.
+     * Where MakePosDef does not act on B it does not act on a principal submatrix either (interlacing), so the identity with a
+     * stand-alone run is exact; where it acted the values are defined on the repaired B, like every other rider's.
+     * out_z_miss / out_info_miss hold one entry per set mask bit, in mask order (t ascending, then m ascending).  A trait with
+     * an empty mask row gets its out_z_more bits of a call without a mask and the bits of out_info in out_info_more.
+     * A trait's values depend on its own scores and its own mask row only: not on n_traits_more, not on the other traits'
+     * scores or masks, not on how many distinct SNPs are missing in the window.  z1, out_z, out_info, the status, the
+     * leave-one-out values and the selection stay statistics of trait 1 on all M SNPs, bit for bit.
+     * miss_more = NULL: nobody lacks anything; the three outputs are not written.  More than GAUSS_TRAITS_MISS_MAX missing
+     * SNPs in one trait, more than GAUSS_TRAITS_MISS_UNION_MAX distinct missing SNPs in the window, a trait left without a
+     * measured SNP, miss_more without n_traits_more, miss_more with one of the three outputs NULL, and QCAT / LD windows that
+     * pass it are GAUSS_E_INVALID.  (The block sits in front of the traits block.) */
+    const uint8_t* miss_more; /* [T x M] row-major: non-zero = further trait t has no score at measured SNP m   host pointer / NULL */
+    double* out_info_more;    /* [T x U] row-major: info per further trait                                      host pointer */
+    double* out_z_miss;       /* [n_miss] imputed Z-scores of the SNPs a trait lacks, in mask order             host pointer */
+    double* out_info_miss;    /* [n_miss] their info                                                            host pointer */
     int n_traits_more;        /* T: further traits; 0 = none; at most GAUSS_TRAITS_MORE_MAX                          */
     const double* z_more;     /* [T x M] row-major: Z-scores of the further traits at the measured SNPs  host pointer */
     double* out_z_more;       /* [T x U] row-major: their imputed Z-scores at the unmeasured SNPs        host pointer */
@@ -176,6 +203,8 @@ typedef struct gauss_window_desc {
 
 #define GAUSS_SLCT_MAX 32
 #define GAUSS_TRAITS_MORE_MAX 63
+#define GAUSS_TRAITS_MISS_MAX 32        /* missing SNPs per further trait and window */
+#define GAUSS_TRAITS_MISS_UNION_MAX 128 /* distinct missing SNPs per window          */
 
 #define GAUSS_GENO_U8   0
 #define GAUSS_GENO_2BIT 1

@@ -213,6 +213,32 @@ int gauss_host_distmix_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t
                               const char* reference_data_file, const char* reference_pop_desc_file,
                               double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out);
 
+/* The same two calls for traits whose files lack some of trait 1's measured SNPs -- per-trait quality control (call rate in the
+ * trait's own samples, MAF, HWE) drops a handful of SNPs per window from every file.  Arguments as above.  A measured SNP of the
+ * extended window that a further file lacks is no error here: it becomes a bit of miss_more of gauss_window_desc, and the trait is
+ * imputed as if it had been run alone on the SNPs it has -- the SNP itself is imputed for that trait like an unmeasured one, and
+ * the trait's info at every unmeasured SNP is its own (a rank-|missing| downdate of the window's factorisation, no LD build per
+ * trait; include/gauss_hip.h).  A z that is present and not finite is still refused.  Refused before any GPU work, naming the file,
+ * the count and the limit: a file that lacks more than GAUSS_TRAITS_MISS_MAX = 32 of the window's measured SNPs, a window in which
+ * more than GAUSS_TRAITS_MISS_UNION_MAX = 128 distinct SNPs are missing, and a file left with 10 or fewer of the window's measured
+ * SNPs (min_num_measured_snp: the reference would refuse that trait, dist.cpp:145-151).
+ * The table is trait 1's plain table, unchanged.  Named matrices [nrow x (1 + n_more)]: z_traits, pval_traits, info_traits,
+ * type_traits; column 0 holds the table's own columns, column k trait k + 1.  A SNP that trait k + 1 lacks and that lies in the
+ * prediction window shows its imputed z, its info and type 0 there (one in a wing has no row); n_missing [1 + n_more] gives, per
+ * trait, how many of the window's measured SNPs its file lacked.
+ * Column k is exactly the stand-alone gauss_host_dist / gauss_host_distmix table of file k + 1 (up to the rounding of another,
+ * equally valid order of sums) when that file's SNPs in the extended window are a subset of trait 1's measured SNPs: rows for SNPs
+ * trait 1 does not measure are ignored, as in the calls above, whereas a stand-alone call would use them. */
+int gauss_host_dist_traits_miss(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                                const char* study_pop, const char* input_file, const char* reference_index_file,
+                                const char* reference_data_file, const char* reference_pop_desc_file,
+                                double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out);
+int gauss_host_distmix_traits_miss(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                                   const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                                   const char* input_file, const char* reference_index_file,
+                                   const char* reference_data_file, const char* reference_pop_desc_file,
+                                   double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out);
+
 /* QCAT / QCATMIX: same feeder as dist / distmix, the window core is
  * run_qcat (qcat.cpp:134-262) / run_qcatmix (qcatmix.cpp:144-297).  af1_cutoff NaN -> 0.05 for qcat
  * (qcat.cpp:53-57), 0.01 for qcatmix (qcatmix.cpp:61-65).  Output columns: rsid chr bp a1 a2

@@ -6,6 +6,10 @@
   (b) from a `rocprofv3 --kernel-trace --stats` run of its own: the time of traits_weights_kernel (two launches a step) and
       traits_impute_kernel per step, at 7 and at 63 traits.
 
+`--miss K` adds a masked form of the largest T (key "<T>m"): every further trait lacks K random SNPs of every window, drawn from a pool
+of 128 of the window's measured SNPs (the limit on distinct missing SNPs, include/gauss_hip.h miss_more); its five further launches
+(k_traits_miss.hip) are timed in (b) beside the three of k_traits.hip.
+
 `--traits 0` runs the plain job alone and touches nothing this feature added: the same file times the parent commit's library
 (the yardstick of DESIGN.md section 4, measured in the same session).
 
@@ -13,7 +17,7 @@ GAUSS_PROBE_ROOT names the checkout whose gauss_amd package is timed (default: t
 
 Every GPU step is a child process under its own time limit; this process never opens the GPU.  A child that fails ends the probe.
 
-    python tools/traits_probe.py [--steps 30] [--warmup 5] [--snps 100000] [--traits 0,7,63] [--json out.json] [--skip-trace]
+    python tools/traits_probe.py [--steps 30] [--warmup 5] [--snps 100000] [--traits 0,7,63] [--miss 8] [--json out.json] [--skip-trace]
 """
 import argparse
 import csv
@@ -33,8 +37,24 @@ ROOT = os.environ.get("GAUSS_PROBE_ROOT") or os.path.dirname(os.path.dirname(os.
 sys.path.insert(0, ROOT)
 
 
-def _jobs(snps, ts):
-    """(hotpath, ctx, {T: windows}, keep-alive) of the chr22 study on a synthetic resident store."""
+def _forms(ts, miss):
+    """[(key, T, K)]: every T plain, and with --miss K the largest T once more with a mask"""
+    forms = [(str(T), T, 0) for T in ts]
+    if miss and any(ts):
+        forms.append((f"{max(ts)}m", max(ts), miss))
+    return forms
+
+
+def _mask(rng, T, M, K):
+    pool = rng.choice(M, size=min(128, M), replace=False)
+    mask = np.zeros((T, M), dtype=np.uint8)
+    for t in range(T):
+        mask[t, rng.choice(pool, size=K, replace=False)] = 1
+    return mask
+
+
+def _jobs(snps, forms):
+    """(hotpath, ctx, {key: windows}, keep-alive) of the chr22 study on a synthetic resident store."""
     import ctypes as C
 
     import torch
@@ -60,18 +80,22 @@ def _jobs(snps, ts):
                   dev=(store.data_ptr(), store.data_ptr(), len(mi), len(ui), ld2),
                   packed=dict(fmt=1, rows_m=mi.astype(np.int32), rows_u=ui.astype(np.int32))) for _, mi, ui in wins]
     rng = np.random.default_rng(7)
-    ask = lambda T: [dict(d, z_more=rng.standard_normal((T, d["dev"][2])) * 2.0) for d in descs] if T else descs
-    return hotpath, ctx, {T: ask(T) for T in ts}, store
+    def ask(T, K):
+        if not T:
+            return descs
+        more = lambda d: dict(miss_more=_mask(rng, T, d["dev"][2], K)) if K else {}
+        return [dict(d, z_more=rng.standard_normal((T, d["dev"][2])) * 2.0, **more(d)) for d in descs]
+    return hotpath, ctx, {key: ask(T, K) for key, T, K in forms}, store
 
 
-def _shape(ws, T):
+def _shape(ws, T, K=0):
     ms, us = [d["dev"][2] for d in ws], [d["dev"][3] for d in ws]
-    return dict(windows=len(ws), M_max=max(ms), U_sum=sum(us), result_bytes=8 * sum((2 + T) * u for u in us),
+    return dict(windows=len(ws), M_max=max(ms), U_sum=sum(us), result_bytes=8 * sum((2 + T + (T if K else 0)) * u + 2 * T * K for u in us),
                 flop=sum(2 * m * m * T + 2 * u * m * T for m, u in zip(ms, us)))
 
 
 def child_time(a):
-    hotpath, ctx, jobs, _keep = _jobs(a.snps, a.ts)
+    hotpath, ctx, jobs, _keep = _jobs(a.snps, a.forms)
     made = {T: hotpath.Job(ws, ctx=ctx, on_device=True) for T, ws in jobs.items()}
     rounds = {T: [] for T in jobs}
     for _ in range(2):                                       # 0, 7, 63, 0, 7, 63: two identical runs of each form
@@ -89,23 +113,23 @@ def child_time(a):
     for job in made.values():
         job.close()
     out = {}
-    for T, ws in jobs.items():
-        out[str(T)] = dict(_shape(ws, T), step_ms=rounds[T], spread_ms=round(abs(rounds[T][0] - rounds[T][1]), 4))
+    for key, T, K in a.forms:
+        out[key] = dict(_shape(jobs[key], T, K), step_ms=rounds[key], spread_ms=round(abs(rounds[key][0] - rounds[key][1]), 4))
     print(json.dumps(out), flush=True)
 
 
 def child_trace(a):
-    hotpath, ctx, jobs, _keep = _jobs(a.snps, a.ts)
+    hotpath, ctx, jobs, _keep = _jobs(a.snps, a.forms)
     out = {}
-    for T, ws in jobs.items():
+    for key, T, K in a.forms:
         if not T:
             continue
-        job = hotpath.Job(ws, ctx=ctx, on_device=True)
+        job = hotpath.Job(jobs[key], ctx=ctx, on_device=True)
         for _ in range(a.steps):
             job.run()
             job.fetch()
         job.close()
-        out[str(T)] = dict(steps=a.steps)
+        out[key] = dict(steps=a.steps)
     print(json.dumps(out), flush=True)
 
 
@@ -132,35 +156,41 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--snps", type=int, default=100_000)
     ap.add_argument("--traits", default="0,7,63")
+    ap.add_argument("--miss", type=int, default=0, help="SNPs every further trait lacks in every window, in a masked form of the largest T")
     ap.add_argument("--json")
     ap.add_argument("--skip-trace", action="store_true")
     ap.add_argument("--child", choices=["time", "trace"])
     a = ap.parse_args()
     a.ts = [int(t) for t in a.traits.split(",")]
+    a.forms = _forms(a.ts, a.miss)
     if a.child:
         return (child_time if a.child == "time" else child_trace)(a)
-    common = ["--steps", str(a.steps), "--warmup", str(a.warmup), "--snps", str(a.snps), "--traits", a.traits]
+    common = ["--steps", str(a.steps), "--warmup", str(a.warmup), "--snps", str(a.snps), "--traits", a.traits, "--miss", str(a.miss)]
     out = dict(time=_child(["--child", "time"] + common, 420))
     print(json.dumps(out["time"]), flush=True)
     if not a.skip_trace and any(a.ts) and shutil.which("rocprofv3"):
         d = tempfile.mkdtemp(prefix="traits_probe_")
         try:
             # a kernel trace on its own: no counters, no other tracing beside it; each job runs 5 steps, in the order of --traits
-            tr = _child(["--child", "trace", "--steps", "5", "--snps", str(a.snps), "--traits", a.traits], 420,
+            tr = _child(["--child", "trace", "--steps", "5", "--snps", str(a.snps), "--traits", a.traits, "--miss", str(a.miss)], 420,
                         prefix=["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"])
             rows = []
             for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
                 rows += [r for r in csv.DictReader(open(f)) if "traits_" in r.get("Kernel_Name", "")]
             rows.sort(key=lambda r: int(r["Start_Timestamp"]))
             res, at = {}, 0
-            for T in [t for t in a.ts if t]:                 # per step: two launches of the weights kernel, one of the product
-                n = 3 * tr[str(T)]["steps"]
+            for key, T, K in [f for f in a.forms if f[1]]:   # per step: two launches of the weights kernel, one of the product;
+                n = (8 if K else 3) * tr[key]["steps"]        # with a mask five more (columns x 2, solve, product, apply)
                 mine, at = rows[at:at + n], at + n
                 us = lambda key: [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in mine if key in r["Kernel_Name"]]
-                w, p = us("traits_weights_kernel"), us("traits_impute_kernel")
+                w, p, m = us("traits_weights_kernel"), us("traits_impute_kernel"), us("traits_miss_")
                 if len(w) == 2 * len(p) and p:
-                    res[str(T)] = dict(launches=len(mine), weights_us_per_step=round(sum(w) / len(p), 2),      # both passes
-                                       impute_us_per_step=round(sum(p) / len(p), 2))
+                    res[key] = dict(launches=len(mine), weights_us_per_step=round(sum(w) / len(p), 2),      # both passes
+                                    impute_us_per_step=round(sum(p) / len(p), 2))
+                    if K:
+                        res[key]["miss_us_per_step"] = round(sum(m) / len(p), 2)
+                        for name in ("cols", "solve", "product", "apply"):
+                            res[key][f"miss_{name}_us_per_step"] = round(sum(us(f"traits_miss_{name}_kernel")) / len(p), 2)
             out["trace"] = res
             print(json.dumps(res), flush=True)
         finally:
