@@ -48,6 +48,7 @@ class WindowDesc(C.Structure):
         ("slct_max", C.c_int), ("slct_chi2_stop", C.c_double), ("slct_min_var_frac", C.c_double),
         ("slct_forced", _ip), ("n_slct_forced", C.c_int), ("out_slct_n", _ip), ("out_slct_idx", _ip),
         ("out_slct_zin", _dp), ("out_slct_joint", _dp), ("out_slct_zc", _dp), ("out_slct_var", _dp),
+        ("cond_min_var_frac", C.c_double), ("out_cond_z", _dp), ("out_cond_var", _dp),
         ("miss_more", _u8p), ("out_info_more", _dp), ("out_z_miss", _dp), ("out_info_miss", _dp),
         ("n_traits_more", C.c_int), ("z_more", _dp), ("out_z_more", _dp),
         ("out_loo_z", _dp), ("out_loo_info", _dp), ("out_loo_t", _dp),

@@ -47,7 +47,7 @@ HOST_SYMBOLS = [
     "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
-    "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2",
+    "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
     "gauss_host_dist_traits", "gauss_host_distmix_traits", "gauss_host_dist_traits_miss", "gauss_host_distmix_traits_miss",
 ]
 
@@ -140,6 +140,8 @@ def load_host():
     h.gauss_host_dist_slct.argtypes = h.gauss_host_dist.argtypes[:-1] + slct_tail
     h.gauss_host_distmix_slct.argtypes = h.gauss_host_distmix.argtypes[:-1] + slct_tail
     h.gauss_host_slct_chi2.argtypes = [_dbl, _dp]
+    h.gauss_host_dist_cond.argtypes = h.gauss_host_dist_slct.argtypes
+    h.gauss_host_distmix_cond.argtypes = h.gauss_host_distmix_slct.argtypes
     traits_tail = [_strs, C.c_int, C.POINTER(_vp)]                           # more_input_files, n_more, out
     h.gauss_host_dist_traits.argtypes = h.gauss_host_dist.argtypes[:-1] + traits_tail
     h.gauss_host_distmix_traits.argtypes = h.gauss_host_distmix.argtypes[:-1] + traits_tail
@@ -399,6 +401,45 @@ def distmix_slct(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, refer
                                       _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
                                       *_slct_args(p_cutoff, collin, max_signals, cond_rsids), C.byref(out)))
     return _table(h, out)[0]
+
+
+def _cond_frame(h, out):
+    named = _named(h, out)
+    df = _table(h, out)[0]
+    sig = np.asarray(named["signals"], dtype=np.float64).reshape(-1, 3)
+    df.attrs["signals"] = dict(row=sig[:, 0].astype(np.int64), z_entry=sig[:, 1].copy(), z_joint=sig[:, 2].copy())
+    return df
+
+
+def dist_cond(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
+              reference_pop_desc_file, af1_cutoff=None, p_cutoff=None, collin=None, max_signals=None, cond_rsids=None, ctx=None):
+    """dist() with its imputed SNPs conditioned on the signals dist_slct() selects (gauss_host_dist_cond): is an imputed hit a signal
+    of its own or the shadow of the lead SNP?  Arguments as dist_slct.  The frame opens with dist()'s rows (same order, same bits:
+    rsid chr bp a1 a2 af1ref z pval info type); the measured SNPs of the wings follow, so that every selected SNP has a row.  Appended
+    columns: wing order z_cond pval_cond var_left -- a measured row carries dist_slct()'s values, an imputed row the z of the imputed
+    SNP given the selected ones (variance info, not 1: include/gauss_hip.h), its two-sided p-value and the share of its variance they
+    leave (z_cond NaN below 1 - collin).  frame.attrs["signals"] = dict(row, z_entry, z_joint) of the selected SNPs in order of entry."""
+    h = load_host()
+    out = _vp()
+    _hcheck(h.gauss_host_dist_cond(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
+                                   _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
+                                   _enc(reference_pop_desc_file), _af(af1_cutoff), *_slct_args(p_cutoff, collin, max_signals, cond_rsids),
+                                   C.byref(out)))
+    return _cond_frame(h, out)
+
+
+def distmix_cond(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
+                 reference_pop_desc_file, af1_cutoff=None, p_cutoff=None, collin=None, max_signals=None, cond_rsids=None, ctx=None):
+    """distmix() with its imputed SNPs conditioned on the selected signals (gauss_host_distmix_cond), on the ancestry-weighted LD;
+    columns as dist_cond with af1mix."""
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_distmix_cond(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
+                                      w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
+                                      _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
+                                      *_slct_args(p_cutoff, collin, max_signals, cond_rsids), C.byref(out)))
+    return _cond_frame(h, out)
 
 
 def slct_chi2(p):

@@ -26,6 +26,7 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.slct_forced = d.slct_forced; w.n_slct_forced = d.n_slct_forced;
     w.out.slct_n = d.out_slct_n; w.out.slct_idx = d.out_slct_idx; w.out.slct_zin = d.out_slct_zin;
     w.out.slct_joint = d.out_slct_joint; w.out.slct_zc = d.out_slct_zc; w.out.slct_var = d.out_slct_var;
+    w.cond_min_var_frac = d.cond_min_var_frac; w.out.cond_z = d.out_cond_z; w.out.cond_var = d.out_cond_var;
     return w;
 }
 extern "C" {

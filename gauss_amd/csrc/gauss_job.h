@@ -237,6 +237,7 @@ struct RiderOuts {
     double *loo_z = nullptr, *loo_info = nullptr, *loo_t = nullptr;
     int32_t *slct_n = nullptr, *slct_idx = nullptr;
     double *slct_zin = nullptr, *slct_joint = nullptr, *slct_zc = nullptr, *slct_var = nullptr;
+    double *cond_z = nullptr, *cond_var = nullptr;      // the imputed SNPs conditioned on the selection (gauss_window_desc.out_cond_*)
     double* z_more = nullptr;
     double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
 };
@@ -275,6 +276,7 @@ struct Plan {
         bool loo = false;                    // leave-one-out values of the measured SNPs (k_loo.hip)
         int slct_K = 0;                      // signal selection (k_slct.hip); 0: not asked
         std::vector<int> slct_forced;
+        bool cond = false;                   // the imputed SNPs conditioned on the selection (k_cond.hip); needs slct_K
         int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
         std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
         bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
@@ -283,7 +285,7 @@ struct Plan {
         RiderOuts out;
         bool needs_fused() const { return loo || traits_T > 0; }      // it reads the rows of L^-1 that only the fused solve forms
     } rd;
-    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n); }
+    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond); }
     size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
@@ -338,6 +340,8 @@ struct gauss_job {
     int gemm_ut = 128;                                     // right-hand sides per tile of the product: 128, small jobs 64
     int2* d_finmap = nullptr;   int n_fin = 0;             // (window, chunk of 256 right-hand sides)
     int* d_slctmap = nullptr;   int n_slct = 0;            // signal selection: the windows that asked
+    int* d_condmap = nullptr;   int n_cond = 0;            // imputed SNPs conditioned on the selection: the windows that asked
+    int cond_max_U = 0;                                    // ... and the most unmeasured SNPs one of them has
     int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
     int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
     int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some
@@ -456,6 +460,7 @@ struct WinSpec {
     const uint8_t* miss_more = nullptr;      // [T x M] non-zero: the trait has no score there (gauss_window_desc.miss_more); NULL: no mask
     int slct_max = 0;                        // signal selection among the measured SNPs (gauss_window_desc.slct_*); 0: not asked
     double slct_chi2_stop = 0.0, slct_min_var_frac = 0.0;
+    double cond_min_var_frac = 0.0;          // guard of the imputed SNPs conditioned on the selection (out.cond_z / out.cond_var ask)
     const int32_t* slct_forced = nullptr;
     int n_slct_forced = 0;
     // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample

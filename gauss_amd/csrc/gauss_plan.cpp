@@ -104,6 +104,12 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
                     return fail(GAUSS_E_INVALID, "slct_forced[%d] = slct_forced[%d] = %d: forced SNPs must be distinct", b, a, (int)w.slct_forced[a]);
         }
     }
+    // the imputed SNPs conditioned on the selection (k_cond.hip)
+    const bool cond = w.out.cond_z || w.out.cond_var;
+    if (cond && !imputes)
+        return fail(GAUSS_E_INVALID, "conditional statistics of the imputed SNPs (out_cond_z / out_cond_var) are for imputation windows only (%s window)", not_imputing);
+    if (cond && w.slct_max <= 0)
+        return fail(GAUSS_E_INVALID, "conditional statistics of the imputed SNPs (out_cond_z / out_cond_var) condition on the signal selection: they need slct_max > 0");
     // further traits (k_traits.hip)
     if (w.n_traits_more < 0 || w.n_traits_more > TRAITS_MAX)
         return fail(GAUSS_E_INVALID, "n_traits_more = %d: a window takes 0 .. %d further traits", w.n_traits_more, TRAITS_MAX);
@@ -372,6 +378,8 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         p.slct_max = w.slct_max; p.n_slct_forced = w.n_slct_forced;
         p.slct_chi2_stop = w.slct_chi2_stop; p.slct_min_var_frac = w.slct_min_var_frac;
     }
+    rd.cond = cond;
+    p.cond_min_var_frac = cond ? w.cond_min_var_frac : 0.0;
     rd.traits_T = w.n_traits_more;
     if (w.n_traits_more > 0) {
         // SNP-major and padded to the kernels' tiles: row g = the T traits' Z-scores at measured SNP g
@@ -609,7 +617,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<ItemH> items;
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
     std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
-    std::vector<int> slctmap;
+    std::vector<int> slctmap, condmap;
     std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
     job->max_nblk = 0;
     {
@@ -681,6 +689,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (rd.loo)
             for (int pn = 0; pn < (p.M + NR - 1) / NR; pn++) loomap.push_back(make_int2(i, pn));      // the panels that hold columns of X
         if (rd.slct_K) slctmap.push_back(i);
+        if (rd.cond) { condmap.push_back(i); job->cond_max_U = std::max(job->cond_max_U, p.U); }
         if (rd.traits_T) {
             for (int b = 0; b < p.nblk; b++) traitsmap.push_back(make_int2(i, b));
             for (int us = 0; us < (p.U + NB - 1) / NB; us++) traitsumap.push_back(make_int2(i, us));
@@ -894,6 +903,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     const size_t o_finmap = put(blob, ta, finmap);
     const size_t o_loomap = put(blob, ta, loomap);
     const size_t o_slctmap = slctmap.empty() ? 0 : put(blob, ta, slctmap);      // (a job in which nobody asks takes nothing)
+    const size_t o_condmap = condmap.empty() ? 0 : put(blob, ta, condmap);
     const size_t o_traitsmap = traitsmap.empty() ? 0 : put(blob, ta, traitsmap);
     const size_t o_traitsumap = traitsumap.empty() ? 0 : put(blob, ta, traitsumap);
     const size_t o_missmap = missmap.empty() ? 0 : put(blob, ta, missmap);
@@ -911,6 +921,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n_fin = (int)finmap.size();
     job->n_loo = (int)loomap.size();
     job->n_slct = (int)slctmap.size();
+    job->n_cond = (int)condmap.size();
     job->n_traits = (int)traitsmap.size();
     job->n_traits_u = (int)traitsumap.size();
     job->n_miss_blk = (int)missmap.size();
@@ -1136,6 +1147,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.out_slct = pl.rd.slct_K ? out + lay.slct : nullptr;
         p.slct_W = pl.rd.slct_K ? (double*)(W + w.slct) : nullptr;
         p.slct_forced = pl.rd.slct_forced.empty() ? nullptr : (const int*)(T + to[i].sf);
+        p.out_cond = pl.rd.cond ? out + lay.cond : nullptr;
         p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;
         p.traits_Z = pl.rd.traits_T ? (const double*)(T + to[i].tz) : nullptr;
         p.traits_Y = pl.rd.traits_T ? (double*)(W + w.ty) : nullptr;
@@ -1282,6 +1294,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->d_finmap = (int2*)(job->d_tab + o_finmap);
     job->d_loomap = (int2*)(job->d_tab + o_loomap);
     job->d_slctmap = (int*)(job->d_tab + o_slctmap);
+    job->d_condmap = (int*)(job->d_tab + o_condmap);
     job->d_traitsmap = (int2*)(job->d_tab + o_traitsmap);
     job->d_traitsumap = (int2*)(job->d_tab + o_traitsumap);
     job->d_missmap = (int2*)(job->d_tab + o_missmap);

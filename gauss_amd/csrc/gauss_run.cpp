@@ -85,13 +85,15 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 }
 
 // The tail of a fused solve, in the one order its inputs allow:
-//     loo -> selection -> traits weights -> miss solve -> closing step -> traits impute -> miss apply
+//     loo -> selection -> traits weights -> miss solve -> closing step -> traits impute -> miss apply -> conditional
 //   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
 //     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
 //   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
 //   - traits impute divides B21 G by the info the closing step's finish kernel has just written;
 //   - traits that lack some measured SNPs (k_traits_miss.hip): the solve reads [X | y] like the traits weights, and their G; the
-//     apply step takes the raw means traits impute has left for such traits, and the info.
+//     apply step takes the raw means traits impute has left for such traits, and the info;
+//   - the imputed SNPs conditioned on the selection (k_cond.hip): z and info of the closing step, the selection's W, indices and
+//     zin, and B21, which everything in front of it only reads.
 // The closing step of a run is the product B21 [X | y] with its finish kernel.  A launch for which no window asked is skipped by its
 // launcher.  The clamp path (job_clamp_window) keeps the same order with its single-window map and the stand-alone solve as its
 // closing step; its selection runs in front of the re-factorisation.
@@ -104,6 +106,7 @@ static void queue_tail(gauss_job* job, hipStream_t st)
     launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
     launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
     launch_traits_miss_apply(job->d_probs, job->d_missumap, job->n_miss_u, st);
+    launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -248,6 +251,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         } else {
             launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);      // B11 and z1 are all it reads: it needs no fused solve
             launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
+            launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);      // z, info, the selection and B21: no fused solve either
         }
         prof_end(job, st);
     }
@@ -484,6 +488,7 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     launch_solve(job->d_probs, d_pm.as<int2>(), (int)pm.size(), st);
     if (traits) launch_traits_impute(job->d_probs, d_lm.as<int2>(), n_us, st);
     if (miss) launch_traits_miss_apply(job->d_probs, d_lm.as<int2>(), n_us, st);
+    if (pl.rd.cond) launch_cond(job->d_probs + i, nullptr, 1, p.U, st);      // W, indices and zin are those of the repaired B11 (the selection above)
     HIPCHK(hipGetLastError());
     int h_status[4];
     HIPCHK(hipMemcpyAsync(h_status, p.status, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
@@ -713,6 +718,10 @@ int job_fetch(gauss_job* job)
                 copy_out(rd.out.slct_joint, sel + sl.joint, K);
                 copy_out(rd.out.slct_zc, sel + sl.zc, p.M);
                 copy_out(rd.out.slct_var, sel + sl.var, p.M);
+            }
+            if (rd.cond) {                         // the imputed SNPs conditioned on the selection (k_cond.hip)
+                copy_out(rd.out.cond_z, res + lay.cond, p.U);
+                copy_out(rd.out.cond_var, res + lay.cond + p.U, p.U);
             }
             if (pl.out_b11 && (!exporting || clamped))
                 { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }

@@ -257,7 +257,7 @@ int gauss_prepared_finish(gauss_prepared* p, gauss_table** out)
 // HBM (panel_rows) instead of being gathered on the host and copied per call (24 MB a window), and the window runs as a job of one on
 // those rows.  Measured on the chr22 study, window after window (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.  Otherwise
 // the literal path: prepare_opened + gauss_impute_window on host rows.
-struct SlctAsk { double p_cutoff, collin; int max_signals; const char* const* cond; int n_cond; };      // the extra arguments of the *_slct calls
+struct SlctAsk { double p_cutoff, collin; int max_signals; const char* const* cond; int n_cond; bool unmeasured = false; };      // the extra arguments of the *_slct calls; unmeasured: the imputed SNPs conditioned on the selection too (*_cond)
 struct TraitsAsk { const char* const* files; int n; bool miss = false; };                               // ... of the *_traits calls; miss: a SNP a further file lacks is imputed for that trait (*_traits_miss)
 static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
                       const char* const* names, const double* wgts, int nw, const char* input, const char* index,
@@ -304,7 +304,7 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
     // slct (dist_slct / distmix_slct): the same window and the same single job again, with the slct_* fields of gauss_window_desc set;
     // the table lists every measured SNP of the extended window (a signal in a wing must be conditioned on, not hidden)
     std::vector<int32_t> s_idx, s_forced;
-    std::vector<double> s_zin, s_joint, s_zc, s_var;
+    std::vector<double> s_zin, s_joint, s_zc, s_var, c_z, c_var;
     int32_t s_n = 0;
     auto ask_slct = [&](gauss_window_desc& d, const std::function<const char*(size_t)>& rsid_of) -> int {
         const int K = slct->max_signals <= 0 ? GAUSS_SLCT_MAX : slct->max_signals;
@@ -328,6 +328,13 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
         d.slct_forced = s_forced.empty() ? nullptr : s_forced.data(); d.n_slct_forced = (int)s_forced.size();
         d.out_slct_n = &s_n; d.out_slct_idx = s_idx.data(); d.out_slct_zin = s_zin.data(); d.out_slct_joint = s_joint.data();
         d.out_slct_zc = s_zc.data(); d.out_slct_var = s_var.data();
+        if (slct->unmeasured) {
+            // cond (dist_cond / distmix_cond): the ridge does not cap what the signals explain of an imputed SNP, so "r^2 >= collin" is
+            // 1 - collin here, without the (1 + lambda)^2 of the measured SNPs' guard (include/gauss_hip.h)
+            c_z.assign((size_t)std::max(d.n_unmeasured, 1), NAN); c_var = c_z;
+            d.cond_min_var_frac = 1.0 - collin;
+            d.out_cond_z = c_z.data(); d.out_cond_var = c_var.data();
+        }
         return 0;
     };
     // loo (dist_loo / distmix_loo): the same window and the same single job, with the three leave-one-out arrays of
@@ -380,7 +387,18 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
                 const LeanSnp& sn = ow.w.v[(size_t)ow.w.measured[i]];
                 rows.push_back(SlctRow{ident_of(*pk, sn), sn.af, sn.z, in_window(sn.bp) ? 0 : 1});
             }
-            *out = slct_output(mix, rows, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data());
+            if (!slct->unmeasured) {
+                *out = slct_output(mix, rows, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data());
+                return 0;
+            }
+            *out = lean_window_finish(ow.w);
+            std::vector<int32_t> row_m, row_u;
+            for (int32_t vi : ow.w.measured) row_m.push_back(ow.w.out_row[(size_t)vi]);
+            for (int32_t vi : ow.w.unmeasured) row_u.push_back(ow.w.out_row[(size_t)vi]);
+            if (cond_output(**out, rows, row_m, row_u, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data(), c_z.data(), c_var.data())) {
+                gauss_table_free(*out); *out = nullptr;
+                return -1;
+            }
             return 0;
         }
         *out = lean_window_finish(ow.w);
@@ -401,13 +419,30 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
     if (slct && ask_slct(d, [&](size_t i) { return p->measured[i]->rsid.c_str(); })) return -1;
     if (traits && ask_traits(d, [&](size_t i) { return ident_of(*p->measured[i]); })) return -1;
     if (gauss_impute_window(ctx, &d) != 0) return herr("%s", gauss_last_error());
+    // dist_output's rows: the SNPs of the prediction window, snp_vec order; -1 for a SNP it does not list (the wings)
+    auto table_rows = [&](const std::vector<Snp*>& v) {
+        std::map<const Snp*, int32_t> row_of;
+        for (Snp* sn : p->snp_vec) if (in_window(sn->bp)) { const int32_t r = (int32_t)row_of.size(); row_of[sn] = r; }
+        std::vector<int32_t> r;
+        for (const Snp* sn : v) { auto it = row_of.find(sn); r.push_back(it == row_of.end() ? -1 : it->second); }
+        return r;
+    };
     if (slct) {
         std::vector<SlctRow> rows;
         for (size_t i = 0; i < p->measured.size(); i++) {
             const Snp& s = *p->measured[i];
             rows.push_back(SlctRow{ident_of(s), mix ? s.af1mix : s.af1ref, s.z, in_window(s.bp) ? 0 : 1});
         }
-        *out = slct_output(mix, rows, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data());
+        if (!slct->unmeasured) {
+            *out = slct_output(mix, rows, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data());
+            return 0;
+        }
+        if (gauss_prepared_finish(p, out)) return -1;
+        if (cond_output(**out, rows, table_rows(p->measured), table_rows(p->unmeasured), s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(),
+                        s_var.data(), c_z.data(), c_var.data())) {
+            gauss_table_free(*out); *out = nullptr;
+            return -1;
+        }
         return 0;
     }
     if (loo) {
@@ -421,14 +456,7 @@ static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64
     }
     if (gauss_prepared_finish(p, out)) return -1;
     if (traits) {
-        std::map<const Snp*, int32_t> row_of;                // dist_output's rows: the SNPs of the prediction window, snp_vec order
-        for (Snp* sn : p->snp_vec) if (in_window(sn->bp)) { const int32_t r = (int32_t)row_of.size(); row_of[sn] = r; }
-        auto rows = [&](const std::vector<Snp*>& v) {
-            std::vector<int32_t> r;
-            for (const Snp* sn : v) { auto it = row_of.find(sn); r.push_back(it == row_of.end() ? -1 : it->second); }
-            return r;
-        };
-        traits_output(**out, traits->n, rows(p->measured), rows(p->unmeasured), t_z.data(), t_out.data(), t_miss.mask ? &t_miss : nullptr);
+        traits_output(**out, traits->n, table_rows(p->measured), table_rows(p->unmeasured), t_z.data(), t_out.data(), t_miss.mask ? &t_miss : nullptr);
     }
     return 0;
 }
@@ -485,6 +513,27 @@ int gauss_host_distmix_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t e
                             const char* const* cond_rsids, int n_cond, gauss_table** out)
 {
     const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond};
+    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
+                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+}
+
+int gauss_host_dist_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                         const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                         const char* reference_pop_desc_file, double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                         const char* const* cond_rsids, int n_cond, gauss_table** out)
+{
+    const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond, true};
+    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
+                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+}
+
+int gauss_host_distmix_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                            const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                            const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                            double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                            const char* const* cond_rsids, int n_cond, gauss_table** out)
+{
+    const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond, true};
     return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
                       input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
 }

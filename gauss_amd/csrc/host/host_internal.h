@@ -29,6 +29,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <set>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -95,10 +96,14 @@ struct gauss_table {
         const Column& c = cols[0];
         return (int)(c.type == GAUSS_COL_STR ? c.s.size() : c.type == GAUSS_COL_INT ? c.i.size() : c.d.size());
     }
-    // room for MAX_COLS columns (the widest table, the signal selection's 14) is reserved on first use, so the reference add() returns
-    // stays valid while the caller adds the columns that follow
+    // room for MAX_COLS columns (the widest table, dist_cond's 15) is reserved on first use, so the reference add() returns stays
+    // valid while the caller adds the columns that follow; one column more than that would move them all, so it is refused
     enum { MAX_COLS = 16 };
-    Column& add(const char* name, int type) { cols.reserve(MAX_COLS); Column c; c.name = name; c.type = type; cols.push_back(std::move(c)); return cols.back(); }
+    Column& add(const char* name, int type)
+    {
+        if (cols.size() >= (size_t)MAX_COLS) throw std::length_error("gauss_table::add: more than MAX_COLS columns");
+        cols.reserve(MAX_COLS); Column c; c.name = name; c.type = type; cols.push_back(std::move(c)); return cols.back();
+    }
     // a named matrix from column-major data (NamedMat's own layout), taken over without a copy
     void put_named(const char* name, int nrow, int ncol, std::vector<double> colmajor)
     {
@@ -523,6 +528,14 @@ gauss_table* loo_output(bool mix, const std::vector<LooRow>& rows, const double*
 struct SlctRow { SnpIdent id; double af, z; int wing; };
 gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, const int32_t* idx, const double* zin, const double* joint,
                          const double* zc, const double* var_left);
+// dist_cond / distmix_cond: dist_output's table `t` of the same call, the measured SNPs of the wings appended (rows = every measured
+// SNP of the extended window as for slct_output; row_m[i] / row_u[i] = the table row of measured / unmeasured SNP i, -1 when the
+// table does not list it), the columns wing order z_cond pval_cond var_left added -- imputed rows carry cond_z / cond_var -- and the
+// named matrix `signals` [n_sel x 3]: table row (from 0), z_entry, z_joint.  -1 (message set, `t` untouched) when `t` has a column
+// that is not one of dist_output's
+int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                 int n_sel, const int32_t* idx, const double* zin, const double* joint, const double* zc, const double* var_left,
+                 const double* cond_z, const double* cond_var);
 // dist_traits / distmix_traits: the Z-scores of one further trait at the n measured SNPs of a window.  SNP i is at(i) -- position and
 // alleles in the window's (the panel's) orientation -- and is looked up in the study `gw` (read from `path`, named in the messages)
 // by (chr, bp, a1, a2): the same allele order gives z, the swapped order -z (gauss.cpp:358-370); of several rows that match, the

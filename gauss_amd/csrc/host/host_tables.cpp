@@ -261,6 +261,63 @@ gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, 
     return t;
 }
 
+// dist_cond / distmix_cond: `t` is dist_output's table of the same call (the SNPs of the prediction window, untouched); the measured SNPs
+// of the wings follow it in matrix order (info 1, type 1 like every measured SNP), so that every selected SNP has a row; then the
+// selection's columns wing order z_cond pval_cond var_left are added: a measured row carries what slct_output gives it, an imputed
+// row the statistics conditioned on the selected SNPs and order 0.  z_entry / z_joint of the n selected SNPs go to the named
+// matrix `signals` [n x 3]: table row (from 0), z_entry, z_joint, in order of entry.  Returns 0, or -1 with the message set when `t`
+// holds a column this function does not know how to fill for a wing row (`t` is then left as it came).
+int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                 int n_sel, const int32_t* idx, const double* zin, const double* joint, const double* zc, const double* var_left,
+                 const double* cond_z, const double* cond_var)
+{
+    static const char* const known[] = {"rsid", "chr", "bp", "a1", "a2", "af1ref", "af1mix", "z", "pval", "info", "type"};
+    for (const Column& c : t.cols)
+        if (std::none_of(std::begin(known), std::end(known), [&](const char* k) { return c.name == k; }))
+            return herr("cond_output: no value for column '%s' in the rows of the wings", c.name.c_str());
+    if (t.cols.size() + 5 > (size_t)gauss_table::MAX_COLS) return herr("cond_output: %zu columns leave no room for five more", t.cols.size());
+    size_t nrow = (size_t)t.nrow();
+    std::vector<int32_t> at(row_m);                                   // table row of measured SNP i, the appended ones included
+    for (size_t i = 0; i < rows.size(); i++) {
+        if (at[i] >= 0) continue;
+        at[i] = (int32_t)nrow++;
+        const SlctRow& r = rows[i];
+        for (Column& c : t.cols) {
+            if (c.name == "rsid") c.s.emplace_back(r.id.rsid);
+            else if (c.name == "a1") c.s.emplace_back(r.id.a1);
+            else if (c.name == "a2") c.s.emplace_back(r.id.a2);
+            else if (c.name == "chr") c.i.push_back(r.id.chr);
+            else if (c.name == "bp") c.i.push_back((int)r.id.bp);
+            else if (c.name == "type") c.i.push_back(1);
+            else if (c.name == "z") c.d.push_back(r.z);
+            else if (c.name == "pval") c.d.push_back(2 * pnorm_upper(fabs(r.z)));
+            else if (c.name == "info") c.d.push_back(1.0);
+            else c.d.push_back(r.af);                                 // af1ref | af1mix: the names were checked above
+        }
+    }
+    Column &wing = t.add("wing", GAUSS_COL_INT), &order = t.add("order", GAUSS_COL_INT), &zcond = t.add("z_cond", GAUSS_COL_DBL);
+    Column &pval = t.add("pval_cond", GAUSS_COL_DBL), &vl = t.add("var_left", GAUSS_COL_DBL);
+    wing.i.assign(nrow, 0); order.i.assign(nrow, 0);
+    zcond.d.assign(nrow, NAN); pval.d.assign(nrow, NAN); vl.d.assign(nrow, NAN);
+    for (size_t i = 0; i < rows.size(); i++) {
+        const size_t r = (size_t)at[i];
+        wing.i[r] = rows[i].wing; zcond.d[r] = zc[i]; vl.d[r] = var_left[i];
+    }
+    for (size_t u = 0; u < row_u.size(); u++) {
+        if (row_u[u] < 0) continue;
+        zcond.d[(size_t)row_u[u]] = cond_z[u]; vl.d[(size_t)row_u[u]] = cond_var[u];
+    }
+    for (size_t r = 0; r < nrow; r++) pval.d[r] = 2 * pnorm_upper(fabs(zcond.d[r]));
+    std::vector<double> sig((size_t)n_sel * 3);
+    for (int a = 0; a < n_sel; a++) {
+        const int32_t r = at[(size_t)idx[a]];
+        order.i[(size_t)r] = a + 1;
+        sig[(size_t)a] = (double)r; sig[(size_t)n_sel + a] = zin[a]; sig[2 * (size_t)n_sel + a] = joint[a];
+    }
+    t.put_named("signals", n_sel, 3, std::move(sig));
+    return 0;
+}
+
 int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out,
                  uint8_t* miss_out, size_t* n_missing)
 {

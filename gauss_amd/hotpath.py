@@ -331,6 +331,12 @@ class _Win:
             desc.out_slct_n, desc.out_slct_idx = s["n"].ctypes.data_as(_ip), s["idx"].ctypes.data_as(_ip)
             desc.out_slct_zin, desc.out_slct_joint = s["zin"].ctypes.data_as(_dp), s["joint"].ctypes.data_as(_dp)
             desc.out_slct_zc, desc.out_slct_var = s["zc"].ctypes.data_as(_dp), s["var"].ctypes.data_as(_dp)
+            # unmeasured=True: the imputed SNPs conditioned on the selection (cond_min_var_frac / out_cond_* of gauss_window_desc).  The
+            # ridge does not cap what the signals explain of an imputed SNP: "r^2 >= collin" is 1 - collin here, without (1 + lambda)^2
+            if slct.get("unmeasured"):
+                s["cond_z"], s["cond_var"] = np.full(U, np.nan), np.full(U, np.nan)
+                desc.cond_min_var_frac = float(slct["min_var_frac_u"]) if "min_var_frac_u" in slct else 1.0 - float(slct.get("collin", 0.9))
+                desc.out_cond_z, desc.out_cond_var = s["cond_z"].ctypes.data_as(_dp), s["cond_var"].ctypes.data_as(_dp)
         # further traits on the same window (n_traits_more / z_more / out_z_more of gauss_window_desc): z_more [T, M] -> [T, U]
         self.z_more = self.out_z_more = None
         if z_more is not None:
@@ -409,6 +415,8 @@ class _Win:
             s, n = self.slct, int(self.slct["n"][0])
             out.update(slct_n=n, slct_idx=s["idx"][:n].copy(), slct_zin=s["zin"][:n].copy(), slct_joint=s["joint"][:n].copy(),
                        slct_zc=s["zc"], slct_var=s["var"], slct_raw=dict(idx=s["idx"], zin=s["zin"], joint=s["joint"]))
+            if "cond_z" in s:
+                out.update(cond_z=s["cond_z"], cond_var=s["cond_var"])
         return out
 
 
@@ -419,7 +427,8 @@ def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_e
     standardised residual (include/gauss_hip.h, out_loo_*).
     slct=dict(max=K, chi2_stop=, collin=0.9, forced=[...]) adds the stepwise conditional signal selection among the measured SNPs
     (include/gauss_hip.h, slct_*): slct_n, slct_idx / slct_zin / slct_joint [n] in order of entry, slct_zc / slct_var [M]; status bit
-    8 when a forced SNP failed the collinearity guard.
+    8 when a forced SNP failed the collinearity guard.  unmeasured=True in that dict (with min_var_frac_u= to pass their guard as it
+    is) adds cond_z / cond_var [U]: the imputed SNPs conditioned on the selected ones (include/gauss_hip.h, out_cond_*).
     z_more [T, M] (T <= 63) adds z_more [T, U]: the Z-scores of T further traits measured at the same SNPs, imputed from the same LD
     and the same factorisation (include/gauss_hip.h, n_traits_more); row t is what z would be with z1 = z_more[t].
     miss_more [T, M] (non-zero: further trait t has no score at measured SNP m; at most 32 per trait, 128 distinct per window) makes row t
@@ -563,7 +572,8 @@ class Job:
         """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more, miss_more])
         or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
         loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs).
-        slct=dict(max=, chi2_stop=, collin=, forced=) in a window's dict: its result carries the signal selection (impute_window).
+        slct=dict(max=, chi2_stop=, collin=, forced=[, unmeasured=True]) in a window's dict: its result carries the signal selection
+        (and the imputed SNPs conditioned on it; impute_window).
         z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window).
         miss_more=[T, M] beside it: the SNPs each further trait lacks; the result carries info_more, z_miss, info_miss (impute_window)."""
         self.ctx = ctx or default_context()

@@ -142,6 +142,26 @@ typedef struct gauss_window_desc {
     double* out_slct_joint;   /* [slct_max] joint z: (B_SS^-1 z_S)_a / sqrt((B_SS^-1)_aa), NaN beyond n  optional   */
     double* out_slct_zc;      /* [M] final conditional z, NaN where the SNP is not admissible          optional     */
     double* out_slct_var;     /* [M] variance left v_i / B_ii, every SNP                               optional     */
+    /* ---- the imputed SNPs conditioned on the selected signals (needs slct_max > 0) --------------------------------
+     * Whether an imputed hit is a signal of its own or the shadow of a selected SNP.  With B, z, S as above, L the Cholesky
+     * factor of B_SS, y = L^-1 z_S (out_slct_zin), b_u row u of B21, m_u = b_u B^-1 z the unnormalised mean and
+     * info_u = |b_u B^-1 b_u^T| (out_info):
+     *   w_u = L^-1 b_u[S]^T      (forward substitution, sums in ascending order)
+     *   out_cond_z[u]   = (m_u - w_u . y) / sqrt(info_u - w_u . w_u)
+     *   out_cond_var[u] = (info_u - w_u . w_u) / info_u           the share of the imputed SNP's variance the signals leave
+     * Under z ~ N(0, B), cov(m_u, z_S) = b_u[S], so m_u - b_u[S] B_SS^-1 z_S has variance info_u - b_u[S] B_SS^-1 b_u[S]^T:
+     * out_cond_z is N(0, 1) where S explains everything -- conditioning an imputed z like a measured one (variance 1 in
+     * place of info_u) is not.  m_u is taken as out_z[u] sqrt(out_info[u]).
+     * The guard: u is admissible while info_u - w_u . w_u > cond_min_var_frac * info_u, else out_cond_z[u] is NaN;
+     * out_cond_var is always written.  The ridge does NOT cap what the signals explain of an imputed SNP (an unmeasured
+     * duplicate of an isolated selected SNP has info = 1 / (1 + lambda) and nothing left), so a caller that means
+     * "r^2 >= collin" passes cond_min_var_frac = 1 - collin, without slct_min_var_frac's (1 + lambda)^2.
+     * Nothing selected (n = 0): out_cond_z has the bits of out_z and out_cond_var is 1.  info_u = 0 or a non-finite z: NaN.
+     * GAUSS_ST_NONFINITE windows return NaN.  Either output being non-NULL switches the computation on; with slct_max = 0,
+     * and on QCAT and LD windows, that is GAUSS_E_INVALID. */
+    double cond_min_var_frac; /* the guard of the imputed SNPs (above)                                                      */
+    double* out_cond_z;       /* [U] conditional z of the unmeasured SNPs, NaN where not admissible  host pointer / NULL    */
+    double* out_cond_var;     /* [U] share of variance left                                          host pointer / NULL    */
     /* ---- further traits on the same window (GAUSS_WIN_IMPUTE windows only) ---------------------------------------
      * A study rarely has one trait: the LD of a window depends on the panel, the weights and the measured SNP set only, so
      * n_traits_more further Z-score vectors measured at the SAME SNPs are imputed from the same B11 / B21 and the same

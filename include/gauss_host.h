@@ -184,6 +184,29 @@ int gauss_host_distmix_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t e
                             const char* reference_data_file, const char* reference_pop_desc_file,
                             double af1_cutoff, double p_cutoff, double collin, int max_signals,
                             const char* const* cond_rsids, int n_cond, gauss_table** out);
+/* The imputed SNPs conditioned on the selected signals: is an imputed hit a signal of its own or the shadow of the lead SNP?
+ * Arguments, window, data layer, single job and refusals of gauss_host_dist_slct / gauss_host_distmix_slct; the job's window also sets
+ * out_cond_z / out_cond_var of gauss_window_desc (include/gauss_hip.h: the statistic and why its variance is info, not 1), with
+ * cond_min_var_frac = 1 - collin: the ridge does not cap what the signals explain of an imputed SNP, so the (1 + lambda)^2 of the
+ * measured SNPs' guard has no place here.
+ * The table opens with the rows of gauss_host_dist / gauss_host_distmix for the same call, in the same order and with the same bits
+ * in their columns (rsid chr bp a1 a2 af1ref|af1mix z pval info type); below them follow the measured SNPs of the wings in
+ * gauss_host_dist_slct's order (info 1, type 1), so that every selected SNP has a row.  Appended columns: wing order z_cond pval_cond
+ * var_left.  A measured row carries gauss_host_dist_slct's values; an imputed row carries order 0, z_cond = the conditional z of the
+ * imputed SNP (NaN where the selected SNPs leave it less than 1 - collin of its variance), pval_cond = 2 pnorm(-|z_cond|) and
+ * var_left = the share of its variance they leave.  z_entry / z_joint of the n selected SNPs are the named matrix `signals`
+ * [n x 3], in order of entry: table row (from 0), z_entry, z_joint. */
+int gauss_host_dist_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                         const char* study_pop, const char* input_file, const char* reference_index_file,
+                         const char* reference_data_file, const char* reference_pop_desc_file,
+                         double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                         const char* const* cond_rsids, int n_cond, gauss_table** out);
+int gauss_host_distmix_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                            const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                            const char* input_file, const char* reference_index_file,
+                            const char* reference_data_file, const char* reference_pop_desc_file,
+                            double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                            const char* const* cond_rsids, int n_cond, gauss_table** out);
 /* The chi^2 (1 df) threshold of a two-sided p-value: the smallest double chi2 with 2 pnorm(-sqrt(chi2)) < p in the library's own
  * normal tail, found by bisection on the bit pattern -- monotone in p, and exact to the last bit that changes the comparison.
  * p must be positive. */
