@@ -321,25 +321,33 @@ def simulate_draws(pop_wgt_df, sim_size, reference_pop_desc_file, seed=None):
     return _table(h, out)[0], _draws(named)
 
 
+def _window_call(name, window, pop, files, af1_cutoff, ctx, extra=()):
+    """One one-window host call, symbol `name`: window = (chr, start_bp, end_bp, wing_size); pop = study_pop, or pop_wgt_df where the
+    symbol takes population weights; files = (input, index, data, description), a name or bytes each; extra = the call's own trailing
+    arguments.  Returns (h, out): the library and the result table, for _table / _cond_frame / _traits_frame to read and free."""
+    h = load_host()
+    fn = getattr(h, name)
+    if fn.argtypes[5] is _strs:
+        names, w, n = _pop_wgt(pop)
+        pop = (names, w.ctypes.data_as(_dp), n)
+    else:
+        pop = (_enc(pop),)
+    out = _vp()
+    _hcheck(fn(_ctx(ctx), *(int(v) for v in window), *pop, *(f if isinstance(f, bytes) else _enc(f) for f in files), _af(af1_cutoff),
+               *extra, C.byref(out)))
+    return h, out
+
+
 def dist(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
          reference_pop_desc_file, af1_cutoff=None, ctx=None):
-    h = load_host()
-    out = _vp()
-    _hcheck(h.gauss_host_dist(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
-                              _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
-                              _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
-    return _table(h, out)[0]
+    return _table(*_window_call("gauss_host_dist", (chr, start_bp, end_bp, wing_size), study_pop,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx))[0]
 
 
 def distmix(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
             reference_pop_desc_file, af1_cutoff=None, ctx=None):
-    h = load_host()
-    names, w, n = _pop_wgt(pop_wgt_df)
-    out = _vp()
-    _hcheck(h.gauss_host_distmix(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
-                                 w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
-                                 _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
-    return _table(h, out)[0]
+    return _table(*_window_call("gauss_host_distmix", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx))[0]
 
 
 def dist_loo(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
@@ -347,24 +355,15 @@ def dist_loo(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_
     """Leave-one-out check of a dist() window (gauss_host_dist_loo): every measured SNP inside [start_bp, end_bp] re-imputed from
     the other measured SNPs of the extended window.  Columns rsid chr bp a1 a2 af1ref z z_loo info_loo t pval; t is the
     standardised residual (N(0, 1) under the model), pval = 2 pnorm(-|t|): a flipped or misplaced study SNP has a large |t|."""
-    h = load_host()
-    out = _vp()
-    _hcheck(h.gauss_host_dist_loo(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
-                                  _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
-                                  _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
-    return _table(h, out)[0]
+    return _table(*_window_call("gauss_host_dist_loo", (chr, start_bp, end_bp, wing_size), study_pop,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx))[0]
 
 
 def distmix_loo(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
                 reference_pop_desc_file, af1_cutoff=None, ctx=None):
     """Leave-one-out check of a distmix() window (gauss_host_distmix_loo); columns as dist_loo with af1mix."""
-    h = load_host()
-    names, w, n = _pop_wgt(pop_wgt_df)
-    out = _vp()
-    _hcheck(h.gauss_host_distmix_loo(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
-                                     w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
-                                     _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
-    return _table(h, out)[0]
+    return _table(*_window_call("gauss_host_distmix_loo", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx))[0]
 
 
 def _slct_args(p_cutoff, collin, max_signals, cond_rsids):
@@ -381,26 +380,17 @@ def dist_slct(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference
     collin (None: 0.9) are not considered; at most max_signals (None: 32) enter; cond_rsids enter first, in their order, whatever
     their p-value.  One row per measured SNP of the extended window, wings included: rsid chr bp a1 a2 af1ref z wing order z_entry
     z_joint z_cond pval_cond var_left (include/gauss_host.h)."""
-    h = load_host()
-    out = _vp()
-    _hcheck(h.gauss_host_dist_slct(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
-                                   _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
-                                   _enc(reference_pop_desc_file), _af(af1_cutoff), *_slct_args(p_cutoff, collin, max_signals, cond_rsids),
-                                   C.byref(out)))
-    return _table(h, out)[0]
+    return _table(*_window_call("gauss_host_dist_slct", (chr, start_bp, end_bp, wing_size), study_pop,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                       _slct_args(p_cutoff, collin, max_signals, cond_rsids)))[0]
 
 
 def distmix_slct(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
                  reference_pop_desc_file, af1_cutoff=None, p_cutoff=None, collin=None, max_signals=None, cond_rsids=None, ctx=None):
     """Signal selection in a distmix() window (gauss_host_distmix_slct) on the ancestry-weighted LD; columns as dist_slct with af1mix."""
-    h = load_host()
-    names, w, n = _pop_wgt(pop_wgt_df)
-    out = _vp()
-    _hcheck(h.gauss_host_distmix_slct(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
-                                      w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
-                                      _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
-                                      *_slct_args(p_cutoff, collin, max_signals, cond_rsids), C.byref(out)))
-    return _table(h, out)[0]
+    return _table(*_window_call("gauss_host_distmix_slct", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                       _slct_args(p_cutoff, collin, max_signals, cond_rsids)))[0]
 
 
 def _cond_frame(h, out):
@@ -419,27 +409,18 @@ def dist_cond(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference
     columns: wing order z_cond pval_cond var_left -- a measured row carries dist_slct()'s values, an imputed row the z of the imputed
     SNP given the selected ones (variance info, not 1: include/gauss_hip.h), its two-sided p-value and the share of its variance they
     leave (z_cond NaN below 1 - collin).  frame.attrs["signals"] = dict(row, z_entry, z_joint) of the selected SNPs in order of entry."""
-    h = load_host()
-    out = _vp()
-    _hcheck(h.gauss_host_dist_cond(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
-                                   _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
-                                   _enc(reference_pop_desc_file), _af(af1_cutoff), *_slct_args(p_cutoff, collin, max_signals, cond_rsids),
-                                   C.byref(out)))
-    return _cond_frame(h, out)
+    return _cond_frame(*_window_call("gauss_host_dist_cond", (chr, start_bp, end_bp, wing_size), study_pop,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                       _slct_args(p_cutoff, collin, max_signals, cond_rsids)))
 
 
 def distmix_cond(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
                  reference_pop_desc_file, af1_cutoff=None, p_cutoff=None, collin=None, max_signals=None, cond_rsids=None, ctx=None):
     """distmix() with its imputed SNPs conditioned on the selected signals (gauss_host_distmix_cond), on the ancestry-weighted LD;
     columns as dist_cond with af1mix."""
-    h = load_host()
-    names, w, n = _pop_wgt(pop_wgt_df)
-    out = _vp()
-    _hcheck(h.gauss_host_distmix_cond(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
-                                      w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
-                                      _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
-                                      *_slct_args(p_cutoff, collin, max_signals, cond_rsids), C.byref(out)))
-    return _cond_frame(h, out)
+    return _cond_frame(*_window_call("gauss_host_distmix_cond", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                       _slct_args(p_cutoff, collin, max_signals, cond_rsids)))
 
 
 def slct_chi2(p):
@@ -454,24 +435,15 @@ def slct_chi2(p):
 def qcat(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
          reference_pop_desc_file, af1_cutoff=None, ctx=None):
     """qcat() of the reference (qcat.cpp:30-132); af1_cutoff None -> 0.05."""
-    h = load_host()
-    out = _vp()
-    _hcheck(h.gauss_host_qcat(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
-                              _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
-                              _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
-    return _table(h, out)[0]
+    return _table(*_window_call("gauss_host_qcat", (chr, start_bp, end_bp, wing_size), study_pop,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx))[0]
 
 
 def qcatmix(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
             reference_pop_desc_file, af1_cutoff=None, ctx=None):
     """qcatmix() of the reference (qcatmix.cpp:30-140); af1_cutoff None -> 0.01."""
-    h = load_host()
-    names, w, n = _pop_wgt(pop_wgt_df)
-    out = _vp()
-    _hcheck(h.gauss_host_qcatmix(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
-                                 w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
-                                 _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
-    return _table(h, out)[0]
+    return _table(*_window_call("gauss_host_qcatmix", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx))[0]
 
 
 def _traits_files(input_files):
@@ -498,10 +470,10 @@ def _traits_frame(h, out):
     return df
 
 
-def _traits_call(h, name, missing):
+def _traits_symbol(name, missing):
     if missing not in ("refuse", "impute"):
         raise ValueError(f"missing must be 'refuse' or 'impute', got {missing!r}")
-    return getattr(h, name + ("_miss" if missing == "impute" else ""))
+    return name + ("_miss" if missing == "impute" else "")
 
 
 def dist_traits(chr, start_bp, end_bp, wing_size, study_pop, input_files, reference_index_file, reference_data_file,
@@ -517,28 +489,19 @@ def dist_traits(chr, start_bp, end_bp, wing_size, study_pop, input_files, refere
     z_k, pval_k, info_k, type_k (type 0 where trait k lacks a SNP trait 1 measures), and frame.attrs["n_missing"] counts, per trait, the
     measured SNPs of the extended window its file lacked.  Column set k equals dist() of file k alone when that file's SNPs in the
     extended window are a subset of trait 1's."""
-    h = load_host()
-    call = _traits_call(h, "gauss_host_dist_traits", missing)
+    name = _traits_symbol("gauss_host_dist_traits", missing)
     first, more, n_more = _traits_files(input_files)
-    out = _vp()
-    _hcheck(call(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop), first,
-                                     _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file),
-                                     _af(af1_cutoff), more, n_more, C.byref(out)))
-    return _traits_frame(h, out)
+    return _traits_frame(*_window_call(name, (chr, start_bp, end_bp, wing_size), study_pop,
+                       (first, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx, (more, n_more)))
 
 
 def distmix_traits(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_files, reference_index_file, reference_data_file,
                    reference_pop_desc_file, af1_cutoff=None, ctx=None, missing="refuse"):
     """distmix() for many traits measured at the same SNPs (gauss_host_distmix_traits); input_files, missing and the frame as dist_traits."""
-    h = load_host()
-    call = _traits_call(h, "gauss_host_distmix_traits", missing)
-    names, w, n = _pop_wgt(pop_wgt_df)
+    name = _traits_symbol("gauss_host_distmix_traits", missing)
     first, more, n_more = _traits_files(input_files)
-    out = _vp()
-    _hcheck(call(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
-                                        w.ctypes.data_as(_dp), n, first, _enc(reference_index_file), _enc(reference_data_file),
-                                        _enc(reference_pop_desc_file), _af(af1_cutoff), more, n_more, C.byref(out)))
-    return _traits_frame(h, out)
+    return _traits_frame(*_window_call(name, (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                       (first, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx, (more, n_more)))
 
 
 def _named(h, t):
@@ -557,11 +520,8 @@ def _named(h, t):
 def prep_qcat(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
               reference_pop_desc_file, af1_cutoff=None, ctx=None):
     """prep_qcat() of the reference (prep_qcat.cpp:16-205): list(snplist, z_vec, cor_mat1, cor_mat2)."""
-    h = load_host()
-    out = _vp()
-    _hcheck(h.gauss_host_prep_qcat(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), _enc(study_pop),
-                                   _enc(input_file), _enc(reference_index_file), _enc(reference_data_file),
-                                   _enc(reference_pop_desc_file), _af(af1_cutoff), C.byref(out)))
+    h, out = _window_call("gauss_host_prep_qcat", (chr, start_bp, end_bp, wing_size), study_pop,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx)
     named = _named(h, out)
     return dict(snplist=_table(h, out)[0], **named)
 
@@ -570,13 +530,8 @@ def prep_recessive_impute(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_fi
                           reference_data_file, reference_pop_desc_file, af1_cutoff=None, ctx=None):
     """prep_recessive_impute() of the reference (prep_qcatmix.cpp:36-316): list(snplist, zvec, cormat,
     cormat_add, cormat_dom, cormat_rec)."""
-    h = load_host()
-    names, w, n = _pop_wgt(pop_wgt_df)
-    out = _vp()
-    _hcheck(h.gauss_host_prep_recessive_impute(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names,
-                                               w.ctypes.data_as(_dp), n, _enc(input_file), _enc(reference_index_file),
-                                               _enc(reference_data_file), _enc(reference_pop_desc_file),
-                                               _af(af1_cutoff), C.byref(out)))
+    h, out = _window_call("gauss_host_prep_recessive_impute", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx)
     named = _named(h, out)
     return dict(snplist=_table(h, out)[0], **named)
 

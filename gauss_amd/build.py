@@ -202,8 +202,8 @@ def build_host(force=False, verbose=False):
     os.makedirs(OBJDIR, exist_ok=True)
     hip_so = build_hip(force=False, verbose=verbose)
     hdir = os.path.join(CSRC, "host")
-    # (host_internal.h: what the four host_*.cpp share; -fvisibility=hidden: only the C ABI of include/gauss_host.h is exported)
-    srcs = [os.path.join(hdir, f) for f in ("host_feeder.cpp", "host_tables.cpp", "host_calls.cpp", "host_chrom.cpp", "host_popwgt.cpp", "host_zmix.cpp", "host_simld.cpp", "bgzf_io.cpp", "packed_panel.cpp")]
+    # (host_internal.h: what the host_*.cpp share; -fvisibility=hidden: only the C ABI of include/gauss_host.h is exported)
+    srcs = [os.path.join(hdir, f) for f in ("host_feeder.cpp", "host_tables.cpp", "host_calls.cpp", "host_riders.cpp", "host_chrom.cpp", "host_popwgt.cpp", "host_zmix.cpp", "host_simld.cpp", "bgzf_io.cpp", "packed_panel.cpp")]
     deps = srcs + [EXPORTS_MAP, os.path.join(hdir, "host_internal.h"), os.path.join(hdir, "bgzf_io.h"), os.path.join(hdir, "packed_panel.h"), os.path.join(HERE, "..", "include", "gauss_host.h"),
                    os.path.join(HERE, "..", "include", "gauss_hip.h"), hip_so]
     so = os.path.join(LIBDIR, "libgauss_host.so")

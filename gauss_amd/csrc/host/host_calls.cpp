@@ -22,6 +22,27 @@ static void panel_rows(gauss_ctx* ctx, const std::string& path, const PackedPane
     *on_device = resident ? 1 : 0;
 }
 
+// The arguments every one-window call shares, filled once per entry point: call_pop for the study_pop form, call_mix for the
+// pop_names / pop_wgts / n form
+struct CallArgs {
+    int kind, chr;
+    int64_t start_bp, end_bp, wing;
+    const char* study_pop;
+    const char* const* pop_names; const double* pop_wgts; int n_pop_wgt;
+    const char *input, *index, *data, *desc;
+    double af1_cutoff;
+};
+static CallArgs call_mix(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* const* pop_names, const double* pop_wgts,
+                         int n_pop_wgt, const char* input, const char* index, const char* data, const char* desc, double af1_cutoff)
+{
+    return {kind, chr, start_bp, end_bp, wing, nullptr, pop_names, pop_wgts, n_pop_wgt, input, index, data, desc, af1_cutoff};
+}
+static CallArgs call_pop(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop, const char* input,
+                         const char* index, const char* data, const char* desc, double af1_cutoff)
+{
+    return {kind, chr, start_bp, end_bp, wing, study_pop, nullptr, nullptr, 0, input, index, data, desc, af1_cutoff};
+}
+
 // The window of a one-window call on a sorted packed panel, built as the chromosome driver builds its windows (host_chrom.cpp:
 // LeanWindow -- a merge of the study's rows and the panel's SNP table instead of per-SNP objects in a map: ~0.1 ms against 0.7-1.0).
 // Returns 1 -- take the literal path, prepare_opened -- for an unsorted or text panel, a call over every chromosome or
@@ -30,43 +51,40 @@ struct OneWindow {
     ChromSetup cs;
     LeanWindow w;                       // points into cs: a OneWindow stays where it was built
 };
-static int one_window_build(OneWindow& ow, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
-                            const char* const* names, const double* wgts, int nw, const char* input, const std::string& panel_path,
-                            const std::shared_ptr<PackedPanel>& pk, const char* desc, double af1_cutoff)
+static int one_window_build(OneWindow& ow, const CallArgs& c, const std::string& panel_path, const std::shared_ptr<PackedPanel>& pk)
 {
-    if (chr <= 0 || env_flag("GAUSS_HOST_FULL_MAP", false) || !pk || !pk->header().sorted) return 1;
-    if (chrom_setup(ow.cs, kind, chr, wing, study_pop, names, wgts, nw, input, panel_path, desc, af1_cutoff, pk, nullptr)) return -1;
+    if (c.chr <= 0 || env_flag("GAUSS_HOST_FULL_MAP", false) || !pk || !pk->header().sorted) return 1;
+    if (chrom_setup(ow.cs, c.kind, c.chr, c.wing, c.study_pop, c.pop_names, c.pop_wgts, c.n_pop_wgt, c.input, panel_path, c.desc, c.af1_cutoff, pk,
+                    nullptr)) return -1;
     std::string err;
-    ow.cs.gw = load_gwas_cached(input, err);
+    ow.cs.gw = load_gwas_cached(c.input, err);
     if (!ow.cs.gw) return herr("%s", err.c_str());
-    return lean_window_build(ow.w, ow.cs, start_bp, end_bp) ? -1 : 0;
+    return lean_window_build(ow.w, ow.cs, c.start_bp, c.end_bp) ? -1 : 0;
 }
 
 // gauss_host_prepare on a panel that open_panel has resolved already (panel_path, pk: empty for a text panel)
-static int prepare_opened(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
-                          const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
-                          const char* annotation_file, const char* reference_index_file, const std::string& panel_path,
-                          const std::shared_ptr<PackedPanel>& pk, const char* reference_pop_desc_file, double af1_cutoff,
+static int prepare_opened(const CallArgs& c, const char* annotation_file, const std::string& panel_path, const std::shared_ptr<PackedPanel>& pk,
                           bool annotated_only, gauss_prepared** out)
 {
+    const int kind = c.kind;
     std::unique_ptr<gauss_prepared> p(new gauss_prepared());
     p->kind = kind;
     Args& a = p->args;
-    a.chr = chr; a.start_bp = start_bp; a.end_bp = end_bp;
-    a.wing_size = (kind == GAUSS_KIND_COMPUTELD) ? 0 : wing_size;       // computeLD.cpp:40
-    if (study_pop) a.study_pop = study_pop;
-    a.input_file = input_file; a.reference_index_file = reference_index_file;
-    a.reference_data_file = panel_path; a.reference_pop_desc_file = reference_pop_desc_file;
+    a.chr = c.chr; a.start_bp = c.start_bp; a.end_bp = c.end_bp;
+    a.wing_size = (kind == GAUSS_KIND_COMPUTELD) ? 0 : c.wing;          // computeLD.cpp:40
+    if (c.study_pop) a.study_pop = c.study_pop;
+    a.input_file = c.input; a.reference_index_file = c.index;
+    a.reference_data_file = panel_path; a.reference_pop_desc_file = c.desc;
     if (annotation_file) a.annotation_file = annotation_file;
     a.pk = pk;
     a.drop_wing_unmeasured = pk && (kind == GAUSS_KIND_DIST || kind == GAUSS_KIND_DISTMIX);
-    a.af1_cutoff = std::isnan(af1_cutoff) ? (kind == GAUSS_KIND_QCAT ? 0.05 : 0.01) : af1_cutoff;   // dist.cpp:53-57, qcat.cpp:53-57
+    a.af1_cutoff = std::isnan(c.af1_cutoff) ? (kind == GAUSS_KIND_QCAT ? 0.05 : 0.01) : c.af1_cutoff;   // dist.cpp:53-57, qcat.cpp:53-57
     const bool mix = (kind == GAUSS_KIND_COMPUTELD || kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_JEPEGMIX ||
                       kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_PREP_RECESSIVE);
     if (mix) {
-        if (!pop_names || !pop_wgts || n_pop_wgt < 1) return herr("pop_wgt_df is empty");
-        set_pop_wgt_map(a, pop_names, pop_wgts, n_pop_wgt);
-    } else if (!study_pop) return herr("study_pop is NULL");
+        if (!c.pop_names || !c.pop_wgts || c.n_pop_wgt < 1) return herr("pop_wgt_df is empty");
+        set_pop_wgt_map(a, c.pop_names, c.pop_wgts, c.n_pop_wgt);
+    } else if (!c.study_pop) return herr("study_pop is NULL");
     if ((kind == GAUSS_KIND_JEPEG || kind == GAUSS_KIND_JEPEGMIX) && !annotation_file) return herr("annotation_file is NULL");
     a.annotated_only = annotated_only && (kind == GAUSS_KIND_JEPEG || kind == GAUSS_KIND_JEPEGMIX);
     if (prepare(*p)) return -1;
@@ -76,19 +94,15 @@ static int prepare_opened(int kind, int chr, int64_t start_bp, int64_t end_bp, i
 
 // annotated_only: the gene drivers' SNP map (run_jepeg); gauss_host_prepare enters the whole study, as the reference does
 // (gauss_prepared_snps lists it)
-static int prepare_files(int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
-                         const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
-                         const char* annotation_file, const char* reference_index_file, const char* reference_data_file,
-                         const char* reference_pop_desc_file, double af1_cutoff, bool annotated_only, gauss_prepared** out)
+static int prepare_files(const CallArgs& c, const char* annotation_file, bool annotated_only, gauss_prepared** out)
 {
     if (!out) return herr("out is NULL");
-    if (kind < 0 || kind > GAUSS_KIND_PREP_RECESSIVE) return herr("bad kind %d", kind);
-    if (files_ok({input_file, reference_index_file, reference_data_file, reference_pop_desc_file})) return -1;
+    if (c.kind < 0 || c.kind > GAUSS_KIND_PREP_RECESSIVE) return herr("bad kind %d", c.kind);
+    if (files_ok({c.input, c.index, c.data, c.desc})) return -1;
     std::string panel_path;
     std::shared_ptr<PackedPanel> pk;
-    if (open_panel(reference_index_file, reference_data_file, reference_pop_desc_file, panel_path, pk)) return -1;
-    return prepare_opened(kind, chr, start_bp, end_bp, wing_size, study_pop, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file,
-                          reference_index_file, panel_path, pk, reference_pop_desc_file, af1_cutoff, annotated_only, out);
+    if (open_panel(c.index, c.data, c.desc, panel_path, pk)) return -1;
+    return prepare_opened(c, annotation_file, panel_path, pk, annotated_only, out);
 }
 
 extern "C" {
@@ -98,8 +112,10 @@ int gauss_host_prepare(int kind, int chr, int64_t start_bp, int64_t end_bp, int6
                        const char* annotation_file, const char* reference_index_file, const char* reference_data_file,
                        const char* reference_pop_desc_file, double af1_cutoff, gauss_prepared** out)
 {
-    return prepare_files(kind, chr, start_bp, end_bp, wing_size, study_pop, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file,
-                         reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, false, out);
+    CallArgs c = call_mix(kind, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file,
+                          reference_data_file, reference_pop_desc_file, af1_cutoff);
+    c.study_pop = study_pop;                                 // this entry point takes both forms: the kind says which one is read
+    return prepare_files(c, annotation_file, false, out);
 }
 
 const gauss_table* gauss_prepared_snps(const gauss_prepared* p)
@@ -257,217 +273,94 @@ int gauss_prepared_finish(gauss_prepared* p, gauss_table** out)
 // HBM (panel_rows) instead of being gathered on the host and copied per call (24 MB a window), and the window runs as a job of one on
 // those rows.  Measured on the chr22 study, window after window (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.  Otherwise
 // the literal path: prepare_opened + gauss_impute_window on host rows.
-struct SlctAsk { double p_cutoff, collin; int max_signals; const char* const* cond; int n_cond; bool unmeasured = false; };      // the extra arguments of the *_slct calls; unmeasured: the imputed SNPs conditioned on the selection too (*_cond)
-struct TraitsAsk { const char* const* files; int n; bool miss = false; };                               // ... of the *_traits calls; miss: a SNP a further file lacks is imputed for that trait (*_traits_miss)
-static int run_impute(gauss_ctx* ctx, int kind, int chr, int64_t start_bp, int64_t end_bp, int64_t wing, const char* study_pop,
-                      const char* const* names, const double* wgts, int nw, const char* input, const char* index,
-                      const char* data, const char* desc, double af1_cutoff, gauss_table** out, bool loo = false, const SlctAsk* slct = nullptr,
-                      const TraitsAsk* traits = nullptr)
+
+// The view a rider gets of either window (host_internal.h: WindowView); `plain` is left to the caller
+static int wing_of(long long bp, const CallArgs& c) { const int ibp = (int)bp; return ibp >= c.start_bp && ibp <= c.end_bp ? 0 : 1; }      // dist.cpp:92
+static WindowView view_of_lean(OneWindow& ow, const PackedPanel& pk, const CallArgs& c)
 {
-    if (!ctx || !out) return herr("bad arguments");
-    if (files_ok({input, index, data, desc})) return -1;
-    // traits (dist_traits / distmix_traits): `input` is trait 1 and defines the window exactly as in the plain call; every further file
-    // is matched to the window's measured SNPs (traits_match) and rides in the same single job as n_traits_more / z_more of
-    // gauss_window_desc; the table is the plain call's with the named matrices z_traits / pval_traits added (traits_output)
-    // With traits->miss (the *_traits_miss calls) a measured SNP a further file lacks becomes a bit of miss_more instead of an error, and
-    // the window returns that trait's own info and the imputed z of the SNPs it lacks (traits_miss_limits: the limits, before any GPU work)
-    std::vector<double> t_z, t_out, t_info, t_zmiss, t_imiss;
-    std::vector<uint8_t> t_mask;
-    TraitsMiss t_miss = {nullptr, nullptr, nullptr, nullptr};
-    auto ask_traits = [&](gauss_window_desc& d, const std::function<SnpIdent(size_t)>& at) -> int {
-        const size_t M = (size_t)d.n_measured, U = (size_t)d.n_unmeasured;
-        t_z.assign((size_t)traits->n * M, 0.0); t_out.assign((size_t)traits->n * U, 0.0);
-        if (traits->miss) t_mask.assign((size_t)traits->n * M, 0);
-        size_t n_miss = 0;
-        for (int k = 0; k < traits->n; k++) {
-            std::string err;
-            std::shared_ptr<const GwasCache> gw = load_gwas_cached(traits->files[k], err);
-            if (!gw) return herr("%s", err.c_str());
-            size_t lacks = 0;
-            if (traits_match(*gw, traits->files[k], M, at, t_z.data() + (size_t)k * M, traits->miss ? t_mask.data() + (size_t)k * M : nullptr, &lacks)) return -1;
-            n_miss += lacks;
-        }
-        if (traits->n > 0) { d.n_traits_more = traits->n; d.z_more = t_z.data(); d.out_z_more = t_out.data(); }
-        if (traits->n > 0 && traits->miss) {
-            if (traits_miss_limits(traits->files, traits->n, M, t_mask.data(), Args().min_num_measured_snp)) return -1;
-            t_info.assign((size_t)traits->n * U, 0.0); t_zmiss.assign(std::max<size_t>(n_miss, 1), 0.0); t_imiss = t_zmiss;
-            d.miss_more = t_mask.data(); d.out_info_more = t_info.data(); d.out_z_miss = t_zmiss.data(); d.out_info_miss = t_imiss.data();
-            t_miss = TraitsMiss{t_mask.data(), t_info.data(), t_zmiss.data(), t_imiss.data()};
-        }
-        return 0;
-    };
-    if (traits) {
-        if (traits->n < 0 || (traits->n > 0 && !traits->files)) return herr("bad more_input_files");
-        if (traits->n > GAUSS_TRAITS_MORE_MAX) return herr("%d further traits: a call takes at most %d", traits->n, GAUSS_TRAITS_MORE_MAX);
-        for (int k = 0; k < traits->n; k++) if (files_ok({traits->files[k]})) return -1;
+    WindowView v;
+    v.mix = c.kind == GAUSS_KIND_DISTMIX;
+    LeanWindow& w = ow.w;
+    lean_table_count(w);                                      // out_row: the rows lean_window_finish will list
+    for (int32_t vi : w.measured) {
+        const LeanSnp& sn = w.v[(size_t)vi];
+        v.measured.push_back(ViewSnp{ident_of(pk, sn), sn.af, sn.z, wing_of(sn.bp, c)});
+        v.row_m.push_back(w.out_row[(size_t)vi]);
     }
-    // slct (dist_slct / distmix_slct): the same window and the same single job again, with the slct_* fields of gauss_window_desc set;
-    // the table lists every measured SNP of the extended window (a signal in a wing must be conditioned on, not hidden)
-    std::vector<int32_t> s_idx, s_forced;
-    std::vector<double> s_zin, s_joint, s_zc, s_var, c_z, c_var;
-    int32_t s_n = 0;
-    auto ask_slct = [&](gauss_window_desc& d, const std::function<const char*(size_t)>& rsid_of) -> int {
-        const int K = slct->max_signals <= 0 ? GAUSS_SLCT_MAX : slct->max_signals;
-        const double collin = slct->collin <= 0 ? 0.9 : slct->collin;
-        if (K > GAUSS_SLCT_MAX) return herr("max_signals = %d: at most %d signals are selected", K, GAUSS_SLCT_MAX);
-        if (slct->n_cond < 0 || (slct->n_cond > 0 && !slct->cond)) return herr("bad cond_rsids");
-        if (slct->n_cond > K) return herr("%d conditioning SNPs, but max_signals = %d", slct->n_cond, K);
-        for (int c = 0; c < slct->n_cond; c++) {
-            int at = -1;
-            for (size_t i = 0; i < (size_t)d.n_measured && at < 0; i++)
-                if (slct->cond[c] && !strcmp(slct->cond[c], rsid_of(i))) at = (int)i;
-            if (at < 0) return herr("cond_rsids: %s is not a measured SNP of the extended window", slct->cond[c] ? slct->cond[c] : "(null)");
-            for (int32_t f : s_forced) if (f == at) return herr("cond_rsids: %s is listed twice", slct->cond[c]);
-            s_forced.push_back(at);
-        }
-        s_idx.assign((size_t)K, -1); s_zin.assign((size_t)K, NAN); s_joint = s_zin;
-        s_zc.assign((size_t)d.n_measured, NAN); s_var = s_zc;
-        d.slct_max = K;
-        d.slct_chi2_stop = slct_chi2_of(slct->p_cutoff <= 0 ? 5e-8 : slct->p_cutoff);
-        d.slct_min_var_frac = 1.0 - collin / ((1.0 + d.lambda) * (1.0 + d.lambda));      // "un-ridged r^2 >= collin" (include/gauss_hip.h)
-        d.slct_forced = s_forced.empty() ? nullptr : s_forced.data(); d.n_slct_forced = (int)s_forced.size();
-        d.out_slct_n = &s_n; d.out_slct_idx = s_idx.data(); d.out_slct_zin = s_zin.data(); d.out_slct_joint = s_joint.data();
-        d.out_slct_zc = s_zc.data(); d.out_slct_var = s_var.data();
-        if (slct->unmeasured) {
-            // cond (dist_cond / distmix_cond): the ridge does not cap what the signals explain of an imputed SNP, so "r^2 >= collin" is
-            // 1 - collin here, without the (1 + lambda)^2 of the measured SNPs' guard (include/gauss_hip.h)
-            c_z.assign((size_t)std::max(d.n_unmeasured, 1), NAN); c_var = c_z;
-            d.cond_min_var_frac = 1.0 - collin;
-            d.out_cond_z = c_z.data(); d.out_cond_var = c_var.data();
-        }
-        return 0;
-    };
-    // loo (dist_loo / distmix_loo): the same window and the same single job, with the three leave-one-out arrays of
-    // gauss_window_desc set; the table lists the measured SNPs of the prediction window instead (the wings only contribute to B11)
-    const bool mix = kind == GAUSS_KIND_DISTMIX;
-    std::vector<double> lz, li, lt;
-    auto ask = [&](gauss_window_desc& d) {
-        lz.assign((size_t)d.n_measured, 0.0); li = lz; lt = lz;
-        d.out_loo_z = lz.data(); d.out_loo_info = li.data(); d.out_loo_t = lt.data();
-    };
-    auto in_window = [&](long long bp) { const int ibp = (int)bp; return ibp >= start_bp && ibp <= end_bp; };      // dist.cpp:92
-    std::string panel_path;
-    std::shared_ptr<PackedPanel> pk;
-    if (open_panel(index, data, desc, panel_path, pk)) return -1;
-    const bool lean_kind = (kind == GAUSS_KIND_DIST || kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_QCAT || kind == GAUSS_KIND_QCATMIX);
-    OneWindow ow;
-    const int lean = lean_kind ? one_window_build(ow, kind, chr, start_bp, end_bp, wing, study_pop, names, wgts, nw, input, panel_path, pk, desc, af1_cutoff) : 1;
-    if (lean < 0) return -1;
-    if (lean == 0) {
-        gauss_window_desc d;                                  // (points into ow.w)
-        if (lean_window_desc(ow.w, &d)) return -1;
-        if (loo) ask(d);
-        if (slct && ask_slct(d, [&](size_t i) { return ident_of(*pk, ow.w.v[(size_t)ow.w.measured[i]]).rsid; })) return -1;
-        if (traits && ask_traits(d, [&](size_t i) { return ident_of(*pk, ow.w.v[(size_t)ow.w.measured[i]]); })) return -1;
-        int on_device = 0;
-        panel_rows(ctx, panel_path, *pk, &d.geno_m, &on_device);
-        d.geno_u = d.geno_m;
-        if (on_device) {
-            gauss_job* job = nullptr;
-            int rc = gauss_job_create(ctx, &d, 1, 1, &job);
-            if (rc == 0) rc = gauss_job_run(job);
-            if (rc == 0) rc = gauss_job_fetch(job);
-            if (job) gauss_job_destroy(job);
-            if (rc != 0) return herr("%s", gauss_last_error());
-        } else if (gauss_impute_window(ctx, &d) != 0) {           // a panel too large to keep in HBM: the window's rows from the mapped file
-            return herr("%s", gauss_last_error());
-        }
-        if (loo) {
-            std::vector<LooRow> rows;
-            for (size_t i = 0; i < ow.w.measured.size(); i++) {
-                const LeanSnp& sn = ow.w.v[(size_t)ow.w.measured[i]];
-                if (in_window(sn.bp)) rows.push_back(LooRow{ident_of(*pk, sn), sn.af, sn.z, (int)i});
-            }
-            *out = loo_output(mix, rows, lz.data(), li.data(), lt.data());
-            return 0;
-        }
-        if (slct) {
-            std::vector<SlctRow> rows;
-            for (size_t i = 0; i < ow.w.measured.size(); i++) {
-                const LeanSnp& sn = ow.w.v[(size_t)ow.w.measured[i]];
-                rows.push_back(SlctRow{ident_of(*pk, sn), sn.af, sn.z, in_window(sn.bp) ? 0 : 1});
-            }
-            if (!slct->unmeasured) {
-                *out = slct_output(mix, rows, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data());
-                return 0;
-            }
-            *out = lean_window_finish(ow.w);
-            std::vector<int32_t> row_m, row_u;
-            for (int32_t vi : ow.w.measured) row_m.push_back(ow.w.out_row[(size_t)vi]);
-            for (int32_t vi : ow.w.unmeasured) row_u.push_back(ow.w.out_row[(size_t)vi]);
-            if (cond_output(**out, rows, row_m, row_u, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data(), c_z.data(), c_var.data())) {
-                gauss_table_free(*out); *out = nullptr;
-                return -1;
-            }
-            return 0;
-        }
-        *out = lean_window_finish(ow.w);
-        if (traits) {
-            std::vector<int32_t> row_m, row_u;
-            for (int32_t vi : ow.w.measured) row_m.push_back(ow.w.out_row[(size_t)vi]);
-            for (int32_t vi : ow.w.unmeasured) row_u.push_back(ow.w.out_row[(size_t)vi]);
-            traits_output(**out, traits->n, row_m, row_u, t_z.data(), t_out.data(), t_miss.mask ? &t_miss : nullptr);
-        }
-        return 0;
+    for (int32_t vi : w.unmeasured) v.row_u.push_back(w.out_row[(size_t)vi]);
+    return v;
+}
+static WindowView view_of_prepared(const gauss_prepared& p, const CallArgs& c)
+{
+    WindowView v;
+    v.mix = c.kind == GAUSS_KIND_DISTMIX;
+    // dist_output's rows: the SNPs of the prediction window, snp_vec order
+    std::map<const Snp*, int32_t> row_of;
+    for (const Snp* sn : p.snp_vec) if (!wing_of(sn->bp, c)) { const int32_t r = (int32_t)row_of.size(); row_of[sn] = r; }
+    auto row = [&](const Snp* sn) { auto it = row_of.find(sn); return it == row_of.end() ? -1 : it->second; };
+    for (const Snp* s : p.measured) {
+        v.measured.push_back(ViewSnp{ident_of(*s), v.mix ? s->af1mix : s->af1ref, s->z, wing_of(s->bp, c)});
+        v.row_m.push_back(row(s));
     }
-    gauss_prepared* p = nullptr;
-    if (prepare_opened(kind, chr, start_bp, end_bp, wing, study_pop, names, wgts, nw, input, nullptr, index, panel_path, pk, desc, af1_cutoff, false, &p)) return -1;
-    std::unique_ptr<gauss_prepared> hold(p);
-    gauss_window_desc d;
-    if (gauss_prepared_window_desc(p, &d)) return -1;
-    if (loo) ask(d);
-    if (slct && ask_slct(d, [&](size_t i) { return p->measured[i]->rsid.c_str(); })) return -1;
-    if (traits && ask_traits(d, [&](size_t i) { return ident_of(*p->measured[i]); })) return -1;
-    if (gauss_impute_window(ctx, &d) != 0) return herr("%s", gauss_last_error());
-    // dist_output's rows: the SNPs of the prediction window, snp_vec order; -1 for a SNP it does not list (the wings)
-    auto table_rows = [&](const std::vector<Snp*>& v) {
-        std::map<const Snp*, int32_t> row_of;
-        for (Snp* sn : p->snp_vec) if (in_window(sn->bp)) { const int32_t r = (int32_t)row_of.size(); row_of[sn] = r; }
-        std::vector<int32_t> r;
-        for (const Snp* sn : v) { auto it = row_of.find(sn); r.push_back(it == row_of.end() ? -1 : it->second); }
-        return r;
-    };
-    if (slct) {
-        std::vector<SlctRow> rows;
-        for (size_t i = 0; i < p->measured.size(); i++) {
-            const Snp& s = *p->measured[i];
-            rows.push_back(SlctRow{ident_of(s), mix ? s.af1mix : s.af1ref, s.z, in_window(s.bp) ? 0 : 1});
-        }
-        if (!slct->unmeasured) {
-            *out = slct_output(mix, rows, s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(), s_var.data());
-            return 0;
-        }
-        if (gauss_prepared_finish(p, out)) return -1;
-        if (cond_output(**out, rows, table_rows(p->measured), table_rows(p->unmeasured), s_n, s_idx.data(), s_zin.data(), s_joint.data(), s_zc.data(),
-                        s_var.data(), c_z.data(), c_var.data())) {
-            gauss_table_free(*out); *out = nullptr;
-            return -1;
-        }
-        return 0;
-    }
-    if (loo) {
-        std::vector<LooRow> rows;
-        for (size_t i = 0; i < p->measured.size(); i++) {
-            const Snp& s = *p->measured[i];
-            if (in_window(s.bp)) rows.push_back(LooRow{ident_of(s), mix ? s.af1mix : s.af1ref, s.z, (int)i});
-        }
-        *out = loo_output(mix, rows, lz.data(), li.data(), lt.data());
-        return 0;
-    }
-    if (gauss_prepared_finish(p, out)) return -1;
-    if (traits) {
-        traits_output(**out, traits->n, table_rows(p->measured), table_rows(p->unmeasured), t_z.data(), t_out.data(), t_miss.mask ? &t_miss : nullptr);
-    }
-    return 0;
+    for (const Snp* s : p.unmeasured) v.row_u.push_back(row(s));
+    return v;
 }
 
+// One window on the GPU: with `lean_pk` (a lean window) on the rows panel_rows names -- as a job of one on the resident panel, or,
+// for a panel too large to keep in HBM, the window's rows from the mapped file; otherwise the rows the descriptor already names
+static int run_window(gauss_ctx* ctx, gauss_window_desc& d, const std::string& panel_path, const PackedPanel* lean_pk)
+{
+    int on_device = 0;
+    if (lean_pk) { panel_rows(ctx, panel_path, *lean_pk, &d.geno_m, &on_device); d.geno_u = d.geno_m; }
+    int rc;
+    if (on_device) {
+        gauss_job* job = nullptr;
+        rc = gauss_job_create(ctx, &d, 1, 1, &job);
+        if (rc == 0) rc = gauss_job_run(job);
+        if (rc == 0) rc = gauss_job_fetch(job);
+        if (job) gauss_job_destroy(job);
+    } else rc = gauss_impute_window(ctx, &d);
+    return rc ? herr("%s", gauss_last_error()) : 0;
+}
+
+// rider: what the call asks beyond its plain table (host_internal.h: Rider), or NULL.  The view is built only for a rider: a
+// plain call does not pay for it.
+static int run_impute(gauss_ctx* ctx, const CallArgs& c, Rider* rider, gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    if (files_ok({c.input, c.index, c.data, c.desc})) return -1;
+    if (rider && rider->check()) return -1;
+    std::string panel_path;
+    std::shared_ptr<PackedPanel> pk;
+    if (open_panel(c.index, c.data, c.desc, panel_path, pk)) return -1;
+    // the window, lean or literal, and its descriptor (which points into ow / prep)
+    const bool lean_kind = (c.kind == GAUSS_KIND_DIST || c.kind == GAUSS_KIND_DISTMIX || c.kind == GAUSS_KIND_QCAT || c.kind == GAUSS_KIND_QCATMIX);
+    OneWindow ow;
+    std::unique_ptr<gauss_prepared> prep;
+    const int lean = lean_kind ? one_window_build(ow, c, panel_path, pk) : 1;
+    if (lean < 0) return -1;
+    if (lean) {
+        gauss_prepared* p = nullptr;
+        if (prepare_opened(c, nullptr, panel_path, pk, false, &p)) return -1;
+        prep.reset(p);
+    }
+    gauss_window_desc d;
+    if (lean ? gauss_prepared_window_desc(prep.get(), &d) : lean_window_desc(ow.w, &d)) return -1;
+    auto plain = [&](gauss_table** t) { if (lean) return gauss_prepared_finish(prep.get(), t); *t = lean_window_finish(ow.w); return 0; };
+    if (!rider) return run_window(ctx, d, panel_path, lean ? nullptr : pk.get()) ? -1 : plain(out);
+    WindowView v = lean ? view_of_prepared(*prep, c) : view_of_lean(ow, *pk, c);       // (points into ow / prep)
+    v.plain = plain;
+    if (rider->ask(d, v)) return -1;
+    if (run_window(ctx, d, panel_path, lean ? nullptr : pk.get())) return -1;
+    return rider->table(v, out);
+}
 
 int gauss_host_dist(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
                     const char* input_file, const char* reference_index_file, const char* reference_data_file,
                     const char* reference_pop_desc_file, double af1_cutoff, gauss_table** out)
 {
-    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
-                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out);
+    return run_impute(ctx, call_pop(GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), nullptr, out);
 }
 
 int gauss_host_distmix(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
@@ -475,16 +368,17 @@ int gauss_host_distmix(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp
                        const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
                        double af1_cutoff, gauss_table** out)
 {
-    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
-                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out);
+    return run_impute(ctx, call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), nullptr, out);
 }
 
 int gauss_host_dist_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
                         const char* input_file, const char* reference_index_file, const char* reference_data_file,
                         const char* reference_pop_desc_file, double af1_cutoff, gauss_table** out)
 {
-    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
-                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, true);
+    LooRider r;
+    return run_impute(ctx, call_pop(GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_distmix_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
@@ -492,8 +386,9 @@ int gauss_host_distmix_loo(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t en
                            const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
                            double af1_cutoff, gauss_table** out)
 {
-    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
-                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, true);
+    LooRider r;
+    return run_impute(ctx, call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_dist_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
@@ -501,9 +396,9 @@ int gauss_host_dist_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_
                          const char* reference_pop_desc_file, double af1_cutoff, double p_cutoff, double collin, int max_signals,
                          const char* const* cond_rsids, int n_cond, gauss_table** out)
 {
-    const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond};
-    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
-                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+    SlctRider r(p_cutoff, collin, max_signals, cond_rsids, n_cond, false);
+    return run_impute(ctx, call_pop(GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_distmix_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
@@ -512,9 +407,9 @@ int gauss_host_distmix_slct(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t e
                             double af1_cutoff, double p_cutoff, double collin, int max_signals,
                             const char* const* cond_rsids, int n_cond, gauss_table** out)
 {
-    const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond};
-    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
-                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+    SlctRider r(p_cutoff, collin, max_signals, cond_rsids, n_cond, false);
+    return run_impute(ctx, call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_dist_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
@@ -522,9 +417,9 @@ int gauss_host_dist_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_
                          const char* reference_pop_desc_file, double af1_cutoff, double p_cutoff, double collin, int max_signals,
                          const char* const* cond_rsids, int n_cond, gauss_table** out)
 {
-    const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond, true};
-    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
-                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+    SlctRider r(p_cutoff, collin, max_signals, cond_rsids, n_cond, true);
+    return run_impute(ctx, call_pop(GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_distmix_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
@@ -533,9 +428,9 @@ int gauss_host_distmix_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t e
                             double af1_cutoff, double p_cutoff, double collin, int max_signals,
                             const char* const* cond_rsids, int n_cond, gauss_table** out)
 {
-    const SlctAsk ask = {p_cutoff, collin, max_signals, cond_rsids, n_cond, true};
-    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
-                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, &ask);
+    SlctRider r(p_cutoff, collin, max_signals, cond_rsids, n_cond, true);
+    return run_impute(ctx, call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_dist_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
@@ -543,9 +438,9 @@ int gauss_host_dist_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t en
                            const char* reference_pop_desc_file, double af1_cutoff, const char* const* more_input_files, int n_more,
                            gauss_table** out)
 {
-    const TraitsAsk ask = {more_input_files, n_more};
-    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
-                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
+    TraitsRider r(more_input_files, n_more, false);
+    return run_impute(ctx, call_pop(GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_distmix_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
@@ -553,9 +448,9 @@ int gauss_host_distmix_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t
                               const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
                               double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out)
 {
-    const TraitsAsk ask = {more_input_files, n_more};
-    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
-                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
+    TraitsRider r(more_input_files, n_more, false);
+    return run_impute(ctx, call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_dist_traits_miss(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
@@ -563,9 +458,9 @@ int gauss_host_dist_traits_miss(gauss_ctx* ctx, int chr, int64_t start_bp, int64
                                 const char* reference_pop_desc_file, double af1_cutoff, const char* const* more_input_files, int n_more,
                                 gauss_table** out)
 {
-    const TraitsAsk ask = {more_input_files, n_more, true};
-    return run_impute(ctx, GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
-                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
+    TraitsRider r(more_input_files, n_more, true);
+    return run_impute(ctx, call_pop(GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_distmix_traits_miss(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
@@ -573,9 +468,9 @@ int gauss_host_distmix_traits_miss(gauss_ctx* ctx, int chr, int64_t start_bp, in
                                    const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
                                    double af1_cutoff, const char* const* more_input_files, int n_more, gauss_table** out)
 {
-    const TraitsAsk ask = {more_input_files, n_more, true};
-    return run_impute(ctx, GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
-                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out, false, nullptr, &ask);
+    TraitsRider r(more_input_files, n_more, true);
+    return run_impute(ctx, call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
 int gauss_host_slct_chi2(double p, double* out_chi2)
@@ -590,8 +485,8 @@ int gauss_host_qcat(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, i
                     const char* input_file, const char* reference_index_file, const char* reference_data_file,
                     const char* reference_pop_desc_file, double af1_cutoff, gauss_table** out)
 {
-    return run_impute(ctx, GAUSS_KIND_QCAT, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
-                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out);
+    return run_impute(ctx, call_pop(GAUSS_KIND_QCAT, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), nullptr, out);
 }
 
 int gauss_host_qcatmix(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
@@ -599,16 +494,16 @@ int gauss_host_qcatmix(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp
                        const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
                        double af1_cutoff, gauss_table** out)
 {
-    return run_impute(ctx, GAUSS_KIND_QCATMIX, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts, n_pop_wgt,
-                      input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out);
+    return run_impute(ctx, call_mix(GAUSS_KIND_QCATMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), nullptr, out);
 }
 
 int gauss_host_prep_qcat(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
                          const char* input_file, const char* reference_index_file, const char* reference_data_file,
                          const char* reference_pop_desc_file, double af1_cutoff, gauss_table** out)
 {
-    return run_impute(ctx, GAUSS_KIND_PREP_QCAT, chr, start_bp, end_bp, wing_size, study_pop, nullptr, nullptr, 0, input_file,
-                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out);
+    return run_impute(ctx, call_pop(GAUSS_KIND_PREP_QCAT, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), nullptr, out);
 }
 
 int gauss_host_prep_recessive_impute(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
@@ -617,8 +512,8 @@ int gauss_host_prep_recessive_impute(gauss_ctx* ctx, int chr, int64_t start_bp, 
                                      const char* reference_data_file, const char* reference_pop_desc_file,
                                      double af1_cutoff, gauss_table** out)
 {
-    return run_impute(ctx, GAUSS_KIND_PREP_RECESSIVE, chr, start_bp, end_bp, wing_size, nullptr, pop_names, pop_wgts,
-                      n_pop_wgt, input_file, reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, out);
+    return run_impute(ctx, call_mix(GAUSS_KIND_PREP_RECESSIVE, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), nullptr, out);
 }
 
 }  // extern "C"
@@ -854,14 +749,14 @@ int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, co
     if (files_ok({input_file, reference_index_file, reference_data_file, reference_pop_desc_file})) return -1;
     std::string panel_path;
     if (open_panel(reference_index_file, reference_data_file, reference_pop_desc_file, panel_path, out.pk)) return -1;
+    const CallArgs c = call_mix(GAUSS_KIND_COMPUTELD, chr, start_bp, end_bp, 0, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file,
+                                reference_data_file, reference_pop_desc_file, af1_cutoff);
     OneWindow ow;
-    const int lean = one_window_build(ow, GAUSS_KIND_COMPUTELD, chr, start_bp, end_bp, 0, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file,
-                                      panel_path, out.pk, reference_pop_desc_file, af1_cutoff);
+    const int lean = one_window_build(ow, c, panel_path, out.pk);
     if (lean < 0) return -1;
     gauss_prepared* p = nullptr;
     if (lean == 1) {
-        if (prepare_opened(GAUSS_KIND_COMPUTELD, chr, start_bp, end_bp, 0, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file, nullptr,
-                           reference_index_file, panel_path, out.pk, reference_pop_desc_file, af1_cutoff, false, &p)) return -1;
+        if (prepare_opened(c, nullptr, panel_path, out.pk, false, &p)) return -1;
         out.prep.reset(p);
     }
     out.a = p ? p->args : ow.cs.a;
@@ -1060,7 +955,9 @@ static int run_jepeg(gauss_ctx* ctx, int kind, const char* study_pop, const char
     // tests/test_gpu_drivers.py).
     const bool full_map = env_flag("GAUSS_HOST_FULL_MAP", false);
     const double t_begin = now_s();
-    if (prepare_files(kind, 0, 0, 0, 0, study_pop, names, wgts, nw, input, annotation, index, data, desc, af1_cutoff, !full_map, &p)) return -1;
+    CallArgs c = call_mix(kind, 0, 0, 0, 0, names, wgts, nw, input, index, data, desc, af1_cutoff);
+    c.study_pop = study_pop;                                 // (the rank entry point takes both forms)
+    if (prepare_files(c, annotation, !full_map, &p)) return -1;
     std::unique_ptr<gauss_prepared> hold(p);
     const double t_prepared = now_s();
     const Args& a = p->args;

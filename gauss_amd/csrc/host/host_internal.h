@@ -6,6 +6,7 @@
 //                     packed-panel cache and open_panel, prepare()
 //   host_tables.cpp   result tables, the JEPEG k x k tail, the table accessors of the C ABI
 //   host_calls.cpp    the one-window / one-call entry points (computeLD, dist, distmix, qcat, prep_*, jepeg, jepegmix)
+//   host_riders.cpp   what a one-window call asks beyond its plain table: leave-one-out, signal selection (+ cond), many traits (+ miss)
 //   host_popwgt.cpp   afmix / cpw2: study allele frequencies against the panel's, per-interval weights on the GPU
 //   host_chrom.cpp    resident panels, the chromosome driver's own window, gauss_host_impute_chromosome / _genome
 #pragma once
@@ -563,6 +564,62 @@ void traits_output(gauss_table& t, int n_more, const std::vector<int32_t>& row_m
                    const double* z_more, const double* out_z_more, const TraitsMiss* miss = nullptr);
 // the smallest chi^2 (1 df) whose two-sided p-value 2 pnorm_upper(sqrt(chi2)) is below p, to the bit
 double slct_chi2_of(double p);
+
+// ---- the riders of a one-window call (host_riders.cpp; run by host_calls.cpp:run_impute) ----
+// What a rider reads of the window of its call, filled once from whichever source the call took (host_calls.cpp:view_of_lean, view_of_prepared -- the lean
+// window on a sorted packed panel, or gauss_prepared).  The strings of `id` point into that source: a view does not outlive it.
+struct ViewSnp { SnpIdent id; double af, z; int wing; };     // af: af1mix | af1ref; wing: 0 inside [start_bp, end_bp] (dist.cpp:92), else 1
+struct WindowView {
+    bool mix = false;
+    std::vector<ViewSnp> measured;                  // the measured SNPs of the EXTENDED window, matrix row order
+    std::vector<int32_t> row_m, row_u;              // row of the call's own table for measured / unmeasured SNP i, -1: not listed (the wings)
+    std::function<int(gauss_table**)> plain;        // the call's own table: dist_output / lean_window_finish
+};
+// A rider: what a call asks of its window beyond the plain table.  A call has at most one.  It owns the buffers the window writes.
+//   check()  the refusals that need no window (before the panel is opened)
+//   ask()    sizes the buffers, sets its fields of the descriptor, refuses what the window shows to be wrong
+//   table()  the call's table from the view and the filled buffers
+struct Rider {
+    virtual ~Rider() = default;
+    virtual int check() { return 0; }
+    virtual int ask(gauss_window_desc& d, const WindowView& v) = 0;
+    virtual int table(const WindowView& v, gauss_table** out) = 0;
+};
+// dist_loo / distmix_loo: the three leave-one-out arrays of gauss_window_desc; the table lists the measured SNPs of the prediction
+// window (the wings only contribute to B11)
+struct LooRider : Rider {
+    std::vector<double> z, info, t;
+    int ask(gauss_window_desc& d, const WindowView& v) override;
+    int table(const WindowView& v, gauss_table** out) override;
+};
+// dist_slct / distmix_slct: the slct_* fields; the table lists every measured SNP of the extended window (a signal in a wing must be
+// conditioned on, not hidden).  unmeasured (dist_cond / distmix_cond): the imputed SNPs conditioned on the selection too -- the
+// call's own table with the selection's columns added (cond_output)
+struct SlctRider : Rider {
+    double p_cutoff, collin; int max_signals; const char* const* cond; int n_cond; bool unmeasured;      // the call's own arguments
+    SlctRider(double p_cutoff_, double collin_, int max_signals_, const char* const* cond_, int n_cond_, bool unmeasured_)
+        : p_cutoff(p_cutoff_), collin(collin_), max_signals(max_signals_), cond(cond_), n_cond(n_cond_), unmeasured(unmeasured_) {}
+    int32_t n = 0;
+    std::vector<int32_t> idx, forced;
+    std::vector<double> zin, joint, zc, var, cond_z, cond_var;
+    int ask(gauss_window_desc& d, const WindowView& v) override;
+    int table(const WindowView& v, gauss_table** out) override;
+};
+// dist_traits / distmix_traits: the call's input file is trait 1 and defines the window exactly as in the plain call; every further
+// file is matched to the window's measured SNPs (traits_match) and rides in the same single job as n_traits_more / z_more; the table
+// is the plain call's with the named matrices of traits_output added.  miss (the *_traits_miss calls): a measured SNP a further
+// file lacks becomes a bit of miss_more instead of an error, and the window returns that trait's own info and the imputed z of the
+// SNPs it lacks (traits_miss_limits: the limits, before any GPU work)
+struct TraitsRider : Rider {
+    const char* const* files; int n_more; bool miss;                   // the call's own arguments: the further files
+    TraitsRider(const char* const* files_, int n_more_, bool miss_) : files(files_), n_more(n_more_), miss(miss_) {}
+    std::vector<double> z, out_z, info, z_miss, info_miss;
+    std::vector<uint8_t> mask;
+    int check() override;
+    int ask(gauss_window_desc& d, const WindowView& v) override;
+    int table(const WindowView& v, gauss_table** out) override;
+};
+
 gauss_table* prep_output(gauss_prepared& p);
 int panel_make_resident(gauss_ctx* ctx, const std::string& path, void** dev, int64_t* uploaded, bool async = false);
 bool panel_is_resident(gauss_ctx* ctx, const std::string& path, void** dev, bool wait = true);

@@ -1,0 +1,114 @@
+// libgauss_host.so -- the riders of a one-window call (host_internal.h: Rider): what dist() / distmix() are asked beyond the plain
+// table.  Each rides in the window's single job through its own fields of gauss_window_desc and builds its table from the
+// WindowView of the call, whichever way the window was built.
+#include "host_internal.h"
+
+// ---- loo ----
+int LooRider::ask(gauss_window_desc& d, const WindowView&)
+{
+    z.assign((size_t)d.n_measured, 0.0); info = z; t = z;
+    d.out_loo_z = z.data(); d.out_loo_info = info.data(); d.out_loo_t = t.data();
+    return 0;
+}
+
+int LooRider::table(const WindowView& v, gauss_table** out)
+{
+    std::vector<LooRow> rows;
+    for (size_t i = 0; i < v.measured.size(); i++) {
+        const ViewSnp& s = v.measured[i];
+        if (!s.wing) rows.push_back(LooRow{s.id, s.af, s.z, (int)i});
+    }
+    *out = loo_output(v.mix, rows, z.data(), info.data(), t.data());
+    return 0;
+}
+
+// ---- slct, cond ----
+int SlctRider::ask(gauss_window_desc& d, const WindowView& v)
+{
+    const int K = max_signals <= 0 ? GAUSS_SLCT_MAX : max_signals;
+    const double r2 = collin <= 0 ? 0.9 : collin;
+    if (K > GAUSS_SLCT_MAX) return herr("max_signals = %d: at most %d signals are selected", K, GAUSS_SLCT_MAX);
+    if (n_cond < 0 || (n_cond > 0 && !cond)) return herr("bad cond_rsids");
+    if (n_cond > K) return herr("%d conditioning SNPs, but max_signals = %d", n_cond, K);
+    for (int c = 0; c < n_cond; c++) {
+        int at = -1;
+        for (size_t i = 0; i < v.measured.size() && at < 0; i++)
+            if (cond[c] && !strcmp(cond[c], v.measured[i].id.rsid)) at = (int)i;
+        if (at < 0) return herr("cond_rsids: %s is not a measured SNP of the extended window", cond[c] ? cond[c] : "(null)");
+        for (int32_t f : forced) if (f == at) return herr("cond_rsids: %s is listed twice", cond[c]);
+        forced.push_back(at);
+    }
+    idx.assign((size_t)K, -1); zin.assign((size_t)K, NAN); joint = zin;
+    zc.assign((size_t)d.n_measured, NAN); var = zc;
+    d.slct_max = K;
+    d.slct_chi2_stop = slct_chi2_of(p_cutoff <= 0 ? 5e-8 : p_cutoff);
+    d.slct_min_var_frac = 1.0 - r2 / ((1.0 + d.lambda) * (1.0 + d.lambda));      // "un-ridged r^2 >= collin" (include/gauss_hip.h)
+    d.slct_forced = forced.empty() ? nullptr : forced.data(); d.n_slct_forced = (int)forced.size();
+    d.out_slct_n = &n; d.out_slct_idx = idx.data(); d.out_slct_zin = zin.data(); d.out_slct_joint = joint.data();
+    d.out_slct_zc = zc.data(); d.out_slct_var = var.data();
+    if (unmeasured) {
+        // the ridge does not cap what the signals explain of an imputed SNP, so "r^2 >= collin" is 1 - collin here, without the
+        // (1 + lambda)^2 of the measured SNPs' guard (include/gauss_hip.h)
+        cond_z.assign((size_t)std::max(d.n_unmeasured, 1), NAN); cond_var = cond_z;
+        d.cond_min_var_frac = 1.0 - r2;
+        d.out_cond_z = cond_z.data(); d.out_cond_var = cond_var.data();
+    }
+    return 0;
+}
+
+int SlctRider::table(const WindowView& v, gauss_table** out)
+{
+    std::vector<SlctRow> rows;
+    for (const ViewSnp& s : v.measured) rows.push_back(SlctRow{s.id, s.af, s.z, s.wing});
+    if (!unmeasured) {
+        *out = slct_output(v.mix, rows, n, idx.data(), zin.data(), joint.data(), zc.data(), var.data());
+        return 0;
+    }
+    if (v.plain(out)) return -1;
+    if (cond_output(**out, rows, v.row_m, v.row_u, n, idx.data(), zin.data(), joint.data(), zc.data(), var.data(), cond_z.data(), cond_var.data())) {
+        gauss_table_free(*out); *out = nullptr;
+        return -1;
+    }
+    return 0;
+}
+
+// ---- traits, traits_miss ----
+int TraitsRider::check()
+{
+    if (n_more < 0 || (n_more > 0 && !files)) return herr("bad more_input_files");
+    if (n_more > GAUSS_TRAITS_MORE_MAX) return herr("%d further traits: a call takes at most %d", n_more, GAUSS_TRAITS_MORE_MAX);
+    for (int k = 0; k < n_more; k++) if (files_ok({files[k]})) return -1;
+    return 0;
+}
+
+int TraitsRider::ask(gauss_window_desc& d, const WindowView& v)
+{
+    const size_t M = (size_t)d.n_measured, U = (size_t)d.n_unmeasured;
+    z.assign((size_t)n_more * M, 0.0); out_z.assign((size_t)n_more * U, 0.0);
+    if (miss) mask.assign((size_t)n_more * M, 0);
+    size_t n_miss = 0;
+    for (int k = 0; k < n_more; k++) {
+        std::string err;
+        std::shared_ptr<const GwasCache> gw = load_gwas_cached(files[k], err);
+        if (!gw) return herr("%s", err.c_str());
+        size_t lacks = 0;
+        if (traits_match(*gw, files[k], M, [&](size_t i) { return v.measured[i].id; }, z.data() + (size_t)k * M,
+                         miss ? mask.data() + (size_t)k * M : nullptr, &lacks)) return -1;
+        n_miss += lacks;
+    }
+    if (n_more > 0) { d.n_traits_more = n_more; d.z_more = z.data(); d.out_z_more = out_z.data(); }
+    if (n_more > 0 && miss) {
+        if (traits_miss_limits(files, n_more, M, mask.data(), Args().min_num_measured_snp)) return -1;
+        info.assign((size_t)n_more * U, 0.0); z_miss.assign(std::max<size_t>(n_miss, 1), 0.0); info_miss = z_miss;
+        d.miss_more = mask.data(); d.out_info_more = info.data(); d.out_z_miss = z_miss.data(); d.out_info_miss = info_miss.data();
+    }
+    return 0;
+}
+
+int TraitsRider::table(const WindowView& v, gauss_table** out)
+{
+    if (v.plain(out)) return -1;
+    const TraitsMiss tm = {mask.data(), info.data(), z_miss.data(), info_miss.data()};
+    traits_output(**out, n_more, v.row_m, v.row_u, z.data(), out_z.data(), n_more > 0 && miss ? &tm : nullptr);
+    return 0;
+}
