@@ -45,6 +45,8 @@ class WindowDesc(C.Structure):
         ("kind", C.c_int), ("n_head_measured", C.c_int), ("n_pred_measured", C.c_int), ("eig_cutoff", C.c_double),
         ("out_r", _dp), ("out_num_eig", _ip), ("u_codings", C.c_int),
         ("geno_format", C.c_int), ("rows_m", _ip), ("rows_u", _ip), ("pop_src_off", _ip),
+        ("cs_coverage", C.c_double), ("cs_prior_var", C.c_double), ("out_cs_pip", _dp), ("out_cs_set", _ip), ("out_cs_set_pip", _dp),
+        ("out_cs_size", _ip), ("out_cs_mass", _dp), ("out_cs_lse", _dp),
         ("slct_max", C.c_int), ("slct_chi2_stop", C.c_double), ("slct_min_var_frac", C.c_double),
         ("slct_forced", _ip), ("n_slct_forced", C.c_int), ("out_slct_n", _ip), ("out_slct_idx", _ip),
         ("out_slct_zin", _dp), ("out_slct_joint", _dp), ("out_slct_zc", _dp), ("out_slct_var", _dp),

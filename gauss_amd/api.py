@@ -48,6 +48,7 @@ HOST_SYMBOLS = [
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
+    "gauss_host_dist_cs", "gauss_host_distmix_cs",
     "gauss_host_dist_traits", "gauss_host_distmix_traits", "gauss_host_dist_traits_miss", "gauss_host_distmix_traits_miss",
 ]
 
@@ -142,6 +143,8 @@ def load_host():
     h.gauss_host_slct_chi2.argtypes = [_dbl, _dp]
     h.gauss_host_dist_cond.argtypes = h.gauss_host_dist_slct.argtypes
     h.gauss_host_distmix_cond.argtypes = h.gauss_host_distmix_slct.argtypes
+    h.gauss_host_dist_cs.argtypes = h.gauss_host_dist_slct.argtypes[:-1] + [_dbl, _dbl, C.POINTER(_vp)]      # ..., coverage, prior_var, out
+    h.gauss_host_distmix_cs.argtypes = h.gauss_host_distmix_slct.argtypes[:-1] + [_dbl, _dbl, C.POINTER(_vp)]
     traits_tail = [_strs, C.c_int, C.POINTER(_vp)]                           # more_input_files, n_more, out
     h.gauss_host_dist_traits.argtypes = h.gauss_host_dist.argtypes[:-1] + traits_tail
     h.gauss_host_distmix_traits.argtypes = h.gauss_host_distmix.argtypes[:-1] + traits_tail
@@ -393,11 +396,14 @@ def distmix_slct(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, refer
                        _slct_args(p_cutoff, collin, max_signals, cond_rsids)))[0]
 
 
-def _cond_frame(h, out):
+def _cond_frame(h, out, sets=False):
     named = _named(h, out)
-    df = _table(h, out)[0]
+    df = _table(h, out)[0]                                 # (frees the table: nothing may fail between the two reads and this)
     sig = np.asarray(named["signals"], dtype=np.float64).reshape(-1, 3)
     df.attrs["signals"] = dict(row=sig[:, 0].astype(np.int64), z_entry=sig[:, 1].copy(), z_joint=sig[:, 2].copy())
+    if sets:                                               # the *_cs calls: one row per credible set beside `signals`
+        st = np.asarray(named["sets"], dtype=np.float64).reshape(-1, 4)
+        df.attrs["sets"] = dict(row=st[:, 0].astype(np.int64), size=st[:, 1].astype(np.int64), mass=st[:, 2].copy(), lse=st[:, 3].copy())
     return df
 
 
@@ -421,6 +427,36 @@ def distmix_cond(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, refer
     return _cond_frame(*_window_call("gauss_host_distmix_cond", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
                        (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
                        _slct_args(p_cutoff, collin, max_signals, cond_rsids)))
+
+
+def _cs_args(coverage, prior_var):
+    return (0.0 if coverage is None else float(coverage), 0.0 if prior_var is None else float(prior_var))
+
+
+def dist_cs(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
+            reference_pop_desc_file, af1_cutoff=None, p_cutoff=None, collin=None, max_signals=None, cond_rsids=None,
+            coverage=None, prior_var=None, ctx=None):
+    """dist_cond() with a credible set for each selected signal (gauss_host_dist_cs): which SNPs, measured or imputed, could be the
+    causal one?  Arguments as dist_cond, plus coverage (None: 0.95), the share of a signal's posterior mass its set holds, and
+    prior_var (None: 25.0), the prior variance of the causal SNP's non-centrality in z units.  The frame is dist_cond()'s (same rows,
+    same bits in its columns) with pip, cs and cs_pip appended: the SNP's posterior inclusion probability over all signals, the
+    1-based order of entry of the set that holds it (0: none; the `order` column's numbering) and its pip in that set.
+    frame.attrs["signals"] as dist_cond; frame.attrs["sets"] = dict(row, size, mass, lse) per signal in order of entry.
+    Limits: the candidates are the measured SNPs of the extended window and the unmeasured SNPs of the prediction window, so a signal
+    near a window edge has a truncated set; one causal SNP per signal; uniform prior; z units; at most 32 signals."""
+    return _cond_frame(*_window_call("gauss_host_dist_cs", (chr, start_bp, end_bp, wing_size), study_pop,
+                     (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                     _slct_args(p_cutoff, collin, max_signals, cond_rsids) + _cs_args(coverage, prior_var)), sets=True)
+
+
+def distmix_cs(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
+               reference_pop_desc_file, af1_cutoff=None, p_cutoff=None, collin=None, max_signals=None, cond_rsids=None,
+               coverage=None, prior_var=None, ctx=None):
+    """distmix_cond() with a credible set for each selected signal (gauss_host_distmix_cs), on the ancestry-weighted LD; columns as
+    dist_cs with af1mix."""
+    return _cond_frame(*_window_call("gauss_host_distmix_cs", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                     (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                     _slct_args(p_cutoff, collin, max_signals, cond_rsids) + _cs_args(coverage, prior_var)), sets=True)
 
 
 def slct_chi2(p):

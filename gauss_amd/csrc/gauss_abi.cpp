@@ -27,6 +27,9 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.out.slct_n = d.out_slct_n; w.out.slct_idx = d.out_slct_idx; w.out.slct_zin = d.out_slct_zin;
     w.out.slct_joint = d.out_slct_joint; w.out.slct_zc = d.out_slct_zc; w.out.slct_var = d.out_slct_var;
     w.cond_min_var_frac = d.cond_min_var_frac; w.out.cond_z = d.out_cond_z; w.out.cond_var = d.out_cond_var;
+    w.cs_coverage = d.cs_coverage; w.cs_prior_var = d.cs_prior_var;
+    w.out.cs_pip = d.out_cs_pip; w.out.cs_set = d.out_cs_set; w.out.cs_set_pip = d.out_cs_set_pip;
+    w.out.cs_size = d.out_cs_size; w.out.cs_mass = d.out_cs_mass; w.out.cs_lse = d.out_cs_lse;
     return w;
 }
 extern "C" {

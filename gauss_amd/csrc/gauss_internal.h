@@ -134,6 +134,11 @@ struct Prob {
     // the imputed SNPs conditioned on the selected signals (k_cond.hip); out_cond = null: not asked (it needs slct_max > 0)
     double cond_min_var_frac;
     GP(double) out_cond;                   // [2][U] cond_z, then cond_var
+    // credible sets of the selected signals (k_cs.hip); out_cs = null: not asked (it needs slct_max > 0, and reads cond_min_var_frac)
+    double cs_coverage, cs_prior_var;      // rho in (0, 1], omega > 0
+    GP(double) cs_lbf;                     // [slct_max][cs_tld(M + U)] scratch: log Bayes factors, then pip, of every candidate per signal
+    GP(uint8_t) cs_mem;                    // [slct_max][cs_tld(M + U)] scratch: 1 where the candidate is in the signal's set
+    GP(double) out_cs;                     // [cs_layout(M + U, K).count]
     // further traits on the same window (k_traits.hip); traits_T = 0: not asked
     int traits_T;                          // T <= TRAITS_MAX further Z-score vectors
     GP(const double) traits_Z;             // [Mld][T16] their Z-scores, SNP-major, zero beyond M and T (T16 = T rounded up to 16)
@@ -157,6 +162,7 @@ inline void clear_riders(Prob& q)
     q.slct_max = q.n_slct_forced = 0; q.slct_chi2_stop = q.slct_min_var_frac = 0.0;
     q.slct_forced = nullptr; q.slct_W = nullptr; q.out_slct = nullptr;
     q.cond_min_var_frac = 0.0; q.out_cond = nullptr;
+    q.cs_coverage = q.cs_prior_var = 0.0; q.cs_lbf = nullptr; q.cs_mem = nullptr; q.out_cs = nullptr;
     q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr;
     q.miss_E = q.miss_nm = q.miss_n = 0; q.miss_tab = nullptr;
     q.miss_YE = q.miss_AE = q.miss_YU = q.miss_LD = q.out_traits_info = q.out_traits_miss = nullptr;
@@ -174,15 +180,18 @@ constexpr int SLCT_K = 32;             // GAUSS_SLCT_MAX
 constexpr int SLCT_T = 512;            // threads of slct_kernel; a thread keeps the "selected" flags of its SNPs in one 64-bit word
 constexpr int SLCT_M_MAX = 64 * SLCT_T;
 constexpr int COND_T = 128;            // threads of cond_kernel: one per unmeasured SNP of its block
+constexpr int CS_T = 128;              // threads of cs_lbf_kernel and cs_fold_kernel: one per candidate of its block
+constexpr int CS_SET_T = 512;          // threads of cs_set_kernel
+constexpr int cs_tld(int T) { return (T + 15) & ~15; }      // row pitch of Prob::cs_lbf / cs_mem
 
 // ---- the result block ------------------------------------------------------------------------------------------------
 // A window's doubles in the job's result block, in this order and nowhere else written down:
 //     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, traits_info [T][U], traits_miss [2][n_miss]]
-//     [, the selection] [, cond_z[U], cond_var[U]]
+//     [, the selection] [, cond_z[U], cond_var[U]] [, cs: size[K], mass[K], lse[K], pip[M+U], set[M+U], set_pip[M+U]]
 // Offsets in doubles from the window's Plan::res_off; a section nobody asked for takes nothing and its offset is that of the next.
 // traits_info and traits_miss exist when the window passed a mask (miss): n_miss = its set bits.  The conditional section
-// (cond; k_cond.hip) is the last: every other offset is what it is without it.
-struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, count; };
+// (cond; k_cond.hip) and behind it the credible sets (cs; k_cs.hip) are the last: every other offset is what it is without them.
+struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, count; };
 // Inside the selection's section, from its start: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] (indices, n and the
 // skipped flag travel as exact doubles).  The host and slct_kernel both read it here.
 struct SlctLayout { size_t n, skipped, idx, zin, joint, zc, var, count; };
@@ -190,12 +199,21 @@ constexpr SlctLayout slct_layout(int M, int K)
 {
     return {0, 1, 2, 2 + (size_t)K, 2 + 2 * (size_t)K, 2 + 3 * (size_t)K, 2 + 3 * (size_t)K + (size_t)M, 2 + 3 * (size_t)K + 2 * (size_t)M};
 }
-constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, bool miss = false, int n_miss = 0, bool cond = false)
+// Inside the credible sets' section, from its start: size[K], mass[K], lse[K] per signal, then pip[T], set[T], set_pip[T] per candidate
+// (T = M + U, the measured SNPs first; size and set travel as exact doubles).  The host and the cs kernels both read it here.
+struct CsLayout { size_t size, mass, lse, pip, set, set_pip, count; };
+constexpr CsLayout cs_layout(int T, int K)
+{
+    return {0, (size_t)K, 2 * (size_t)K, 3 * (size_t)K, 3 * (size_t)K + (size_t)T, 3 * (size_t)K + 2 * (size_t)T, 3 * (size_t)K + 3 * (size_t)T};
+}
+constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, bool miss = false, int n_miss = 0, bool cond = false,
+                               bool cs = false)
 {
     const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_tinfo = o_traits + (size_t)T * U;
     const size_t o_tmiss = o_tinfo + (miss ? (size_t)T * U : 0), o_slct = o_tmiss + (miss ? 2 * (size_t)n_miss : 0);
     const size_t o_cond = o_slct + (K ? slct_layout(M, K).count : 0);
-    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cond + (cond ? 2 * (size_t)U : 0)};
+    const size_t o_cs = o_cond + (cond ? 2 * (size_t)U : 0);
+    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_cs + (cs ? cs_layout(M + U, K).count : 0)};
 }
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
@@ -308,6 +326,10 @@ void launch_slct(const Prob* d_probs, const int* d_slctmap, int n, hipStream_t s
 // (d_condmap; null: the windows d_probs[0 .. n)); max_U = the most unmeasured SNPs one of them has.  It runs behind launch_slct
 // and behind the kernel that writes out_z / out_info
 void launch_cond(const Prob* d_probs, const int* d_condmap, int n, int max_U, hipStream_t s);
+// credible sets of the selected signals (k_cs.hip): three launches over the asking windows (d_csmap; null: the windows
+// d_probs[0 .. n)); max_T = the most candidates (M + U) one of them has.  They run behind launch_cond's place: behind launch_slct and
+// behind the kernel that writes out_z / out_info
+void launch_cs(const Prob* d_probs, const int* d_csmap, int n, int max_T, hipStream_t s);
 // further traits (k_traits.hip).  launch_traits_weights: G = X^T (X Z) of the windows that asked, d_map = (window, 64-row block of X),
 // two launches (Y = X Z, then G = X^T Y); it runs where launch_loo runs.  launch_traits_impute: out_traits = B21 G / sqrt(out_info),
 // d_umap = (window, strip of 64 unmeasured SNPs); it runs behind the kernel that writes out_info

@@ -238,6 +238,8 @@ struct RiderOuts {
     int32_t *slct_n = nullptr, *slct_idx = nullptr;
     double *slct_zin = nullptr, *slct_joint = nullptr, *slct_zc = nullptr, *slct_var = nullptr;
     double *cond_z = nullptr, *cond_var = nullptr;      // the imputed SNPs conditioned on the selection (gauss_window_desc.out_cond_*)
+    double *cs_pip = nullptr, *cs_set_pip = nullptr, *cs_mass = nullptr, *cs_lse = nullptr;      // credible sets (gauss_window_desc.out_cs_*)
+    int32_t *cs_set = nullptr, *cs_size = nullptr;
     double* z_more = nullptr;
     double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
 };
@@ -277,6 +279,7 @@ struct Plan {
         int slct_K = 0;                      // signal selection (k_slct.hip); 0: not asked
         std::vector<int> slct_forced;
         bool cond = false;                   // the imputed SNPs conditioned on the selection (k_cond.hip); needs slct_K
+        bool cs = false;                     // credible sets of the selected signals (k_cs.hip); needs slct_K
         int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
         std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
         bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
@@ -285,7 +288,7 @@ struct Plan {
         RiderOuts out;
         bool needs_fused() const { return loo || traits_T > 0; }      // it reads the rows of L^-1 that only the fused solve forms
     } rd;
-    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond); }
+    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs); }
     size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
@@ -342,6 +345,8 @@ struct gauss_job {
     int* d_slctmap = nullptr;   int n_slct = 0;            // signal selection: the windows that asked
     int* d_condmap = nullptr;   int n_cond = 0;            // imputed SNPs conditioned on the selection: the windows that asked
     int cond_max_U = 0;                                    // ... and the most unmeasured SNPs one of them has
+    int* d_csmap = nullptr;     int n_cs = 0;              // credible sets: the windows that asked
+    int cs_max_T = 0;                                      // ... and the most candidates (M + U) one of them has
     int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
     int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
     int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some
@@ -461,6 +466,7 @@ struct WinSpec {
     int slct_max = 0;                        // signal selection among the measured SNPs (gauss_window_desc.slct_*); 0: not asked
     double slct_chi2_stop = 0.0, slct_min_var_frac = 0.0;
     double cond_min_var_frac = 0.0;          // guard of the imputed SNPs conditioned on the selection (out.cond_z / out.cond_var ask)
+    double cs_coverage = 0.0, cs_prior_var = 0.0;      // credible sets of the selected signals (an out.cs_* asks)
     const int32_t* slct_forced = nullptr;
     int n_slct_forced = 0;
     // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample

@@ -110,6 +110,16 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         return fail(GAUSS_E_INVALID, "conditional statistics of the imputed SNPs (out_cond_z / out_cond_var) are for imputation windows only (%s window)", not_imputing);
     if (cond && w.slct_max <= 0)
         return fail(GAUSS_E_INVALID, "conditional statistics of the imputed SNPs (out_cond_z / out_cond_var) condition on the signal selection: they need slct_max > 0");
+    // credible sets of the selected signals (k_cs.hip)
+    const bool cs = w.out.cs_pip || w.out.cs_set || w.out.cs_set_pip || w.out.cs_size || w.out.cs_mass || w.out.cs_lse;
+    if (cs && !imputes)
+        return fail(GAUSS_E_INVALID, "credible sets (out_cs_*) are for imputation windows only (%s window)", not_imputing);
+    if (cs && w.slct_max <= 0)
+        return fail(GAUSS_E_INVALID, "credible sets (out_cs_*) are those of the selected signals: they need slct_max > 0");
+    if (cs && !(w.cs_coverage > 0.0 && w.cs_coverage <= 1.0))
+        return fail(GAUSS_E_INVALID, "cs_coverage = %g: the coverage of a credible set lies in (0, 1]", w.cs_coverage);
+    if (cs && !(w.cs_prior_var > 0.0 && std::isfinite(w.cs_prior_var)))
+        return fail(GAUSS_E_INVALID, "cs_prior_var = %g: the prior variance of the causal SNP's non-centrality is positive and finite", w.cs_prior_var);
     // further traits (k_traits.hip)
     if (w.n_traits_more < 0 || w.n_traits_more > TRAITS_MAX)
         return fail(GAUSS_E_INVALID, "n_traits_more = %d: a window takes 0 .. %d further traits", w.n_traits_more, TRAITS_MAX);
@@ -379,7 +389,10 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         p.slct_chi2_stop = w.slct_chi2_stop; p.slct_min_var_frac = w.slct_min_var_frac;
     }
     rd.cond = cond;
-    p.cond_min_var_frac = cond ? w.cond_min_var_frac : 0.0;
+    p.cond_min_var_frac = cond || cs ? w.cond_min_var_frac : 0.0;
+    rd.cs = cs;
+    p.cs_coverage = cs ? w.cs_coverage : 0.0;
+    p.cs_prior_var = cs ? w.cs_prior_var : 0.0;
     rd.traits_T = w.n_traits_more;
     if (w.n_traits_more > 0) {
         // SNP-major and padded to the kernels' tiles: row g = the T traits' Z-scores at measured SNP g
@@ -617,7 +630,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<ItemH> items;
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
     std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
-    std::vector<int> slctmap, condmap;
+    std::vector<int> slctmap, condmap, csmap;
     std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
     job->max_nblk = 0;
     {
@@ -690,6 +703,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             for (int pn = 0; pn < (p.M + NR - 1) / NR; pn++) loomap.push_back(make_int2(i, pn));      // the panels that hold columns of X
         if (rd.slct_K) slctmap.push_back(i);
         if (rd.cond) { condmap.push_back(i); job->cond_max_U = std::max(job->cond_max_U, p.U); }
+        if (rd.cs) { csmap.push_back(i); job->cs_max_T = std::max(job->cs_max_T, p.M + p.U); }
         if (rd.traits_T) {
             for (int b = 0; b < p.nblk; b++) traitsmap.push_back(make_int2(i, b));
             for (int us = 0; us < (p.U + NB - 1) / NB; us++) traitsumap.push_back(make_int2(i, us));
@@ -904,6 +918,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     const size_t o_loomap = put(blob, ta, loomap);
     const size_t o_slctmap = slctmap.empty() ? 0 : put(blob, ta, slctmap);      // (a job in which nobody asks takes nothing)
     const size_t o_condmap = condmap.empty() ? 0 : put(blob, ta, condmap);
+    const size_t o_csmap = csmap.empty() ? 0 : put(blob, ta, csmap);
     const size_t o_traitsmap = traitsmap.empty() ? 0 : put(blob, ta, traitsmap);
     const size_t o_traitsumap = traitsumap.empty() ? 0 : put(blob, ta, traitsumap);
     const size_t o_missmap = missmap.empty() ? 0 : put(blob, ta, missmap);
@@ -922,6 +937,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n_loo = (int)loomap.size();
     job->n_slct = (int)slctmap.size();
     job->n_cond = (int)condmap.size();
+    job->n_cs = (int)csmap.size();
     job->n_traits = (int)traitsmap.size();
     job->n_traits_u = (int)traitsumap.size();
     job->n_miss_blk = (int)missmap.size();
@@ -931,7 +947,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     // ---- workspace arena ----
     Arena wa;         // zeroed once per job: operand padding, B21 padding and the solve matrices rely on it
     Arena wslab;      // partial slabs: every entry a reader keeps is written by the Gram kernel first, so no zeroing
-    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct, ty, tg, mye, mae, myu, mld; long long ldraw; };
+    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct, cs_lbf, cs_mem, ty, tg, mye, mae, myu, mld; long long ldraw; };
     std::vector<WsOff> wo(job->n);
     size_t res = 0;
     {
@@ -987,6 +1003,11 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             w.b11c = wa.take((size_t)p.Mld * p.Mld * sizeof(double));
         }
         w.slct = pl.rd.slct_K ? wa.take((size_t)SLCT_K * p.Mld * sizeof(double)) : 0;      // the selected columns of the partial factor
+        w.cs_lbf = w.cs_mem = 0;
+        if (pl.rd.cs) {                     // the candidates' log Bayes factors / pips per signal, and their membership bytes
+            w.cs_lbf = wa.take((size_t)pl.rd.slct_K * cs_tld(p.M + p.U) * sizeof(double));
+            w.cs_mem = wa.take((size_t)pl.rd.slct_K * cs_tld(p.M + p.U));
+        }
         w.ty = w.tg = 0;
         if (pl.rd.traits_T) {               // Y = X Z and G = X^T Y of the further traits
             w.ty = wa.take((size_t)p.Mld * traits_t16(pl.rd.traits_T) * sizeof(double));
@@ -1148,6 +1169,9 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.slct_W = pl.rd.slct_K ? (double*)(W + w.slct) : nullptr;
         p.slct_forced = pl.rd.slct_forced.empty() ? nullptr : (const int*)(T + to[i].sf);
         p.out_cond = pl.rd.cond ? out + lay.cond : nullptr;
+        p.out_cs = pl.rd.cs ? out + lay.cs : nullptr;
+        p.cs_lbf = pl.rd.cs ? (double*)(W + w.cs_lbf) : nullptr;
+        p.cs_mem = pl.rd.cs ? (uint8_t*)(W + w.cs_mem) : nullptr;
         p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;
         p.traits_Z = pl.rd.traits_T ? (const double*)(T + to[i].tz) : nullptr;
         p.traits_Y = pl.rd.traits_T ? (double*)(W + w.ty) : nullptr;
@@ -1295,6 +1319,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->d_loomap = (int2*)(job->d_tab + o_loomap);
     job->d_slctmap = (int*)(job->d_tab + o_slctmap);
     job->d_condmap = (int*)(job->d_tab + o_condmap);
+    job->d_csmap = (int*)(job->d_tab + o_csmap);
     job->d_traitsmap = (int2*)(job->d_tab + o_traitsmap);
     job->d_traitsumap = (int2*)(job->d_tab + o_traitsumap);
     job->d_missmap = (int2*)(job->d_tab + o_missmap);

@@ -85,7 +85,7 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 }
 
 // The tail of a fused solve, in the one order its inputs allow:
-//     loo -> selection -> traits weights -> miss solve -> closing step -> traits impute -> miss apply -> conditional
+//     loo -> selection -> traits weights -> miss solve -> closing step -> traits impute -> miss apply -> conditional -> credible sets
 //   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
 //     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
 //   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
@@ -93,7 +93,9 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 //   - traits that lack some measured SNPs (k_traits_miss.hip): the solve reads [X | y] like the traits weights, and their G; the
 //     apply step takes the raw means traits impute has left for such traits, and the info;
 //   - the imputed SNPs conditioned on the selection (k_cond.hip): z and info of the closing step, the selection's W, indices and
-//     zin, and B21, which everything in front of it only reads.
+//     zin, and B21, which everything in front of it only reads;
+//   - the credible sets of the selected signals (k_cs.hip): what the conditional step reads, and the selection's joint z and B11's
+//     diagonal in A[0]; they write a workspace and a result section of their own.
 // The closing step of a run is the product B21 [X | y] with its finish kernel.  A launch for which no window asked is skipped by its
 // launcher.  The clamp path (job_clamp_window) keeps the same order with its single-window map and the stand-alone solve as its
 // closing step; its selection runs in front of the re-factorisation.
@@ -107,6 +109,7 @@ static void queue_tail(gauss_job* job, hipStream_t st)
     launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
     launch_traits_miss_apply(job->d_probs, job->d_missumap, job->n_miss_u, st);
     launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);
+    launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -252,6 +255,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
             launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);      // B11 and z1 are all it reads: it needs no fused solve
             launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
             launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);      // z, info, the selection and B21: no fused solve either
+            launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
         }
         prof_end(job, st);
     }
@@ -489,6 +493,7 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     if (traits) launch_traits_impute(job->d_probs, d_lm.as<int2>(), n_us, st);
     if (miss) launch_traits_miss_apply(job->d_probs, d_lm.as<int2>(), n_us, st);
     if (pl.rd.cond) launch_cond(job->d_probs + i, nullptr, 1, p.U, st);      // W, indices and zin are those of the repaired B11 (the selection above)
+    if (pl.rd.cs) launch_cs(job->d_probs + i, nullptr, 1, p.M + p.U, st);
     HIPCHK(hipGetLastError());
     int h_status[4];
     HIPCHK(hipMemcpyAsync(h_status, p.status, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
@@ -694,6 +699,11 @@ int job_fetch(gauss_job* job)
                     sel[sl.n] = sel[sl.skipped] = 0.0;
                     for (int a = 0; a < rd.slct_K; a++) sel[sl.idx + a] = -1.0;
                 }
+                if (rd.cs) {                       // no sets: size 0, set -1
+                    const CsLayout cl = cs_layout(p.M + p.U, rd.slct_K);
+                    for (int a = 0; a < rd.slct_K; a++) res[lay.cs + cl.size + a] = 0.0;
+                    for (int c = 0; c < p.M + p.U; c++) res[lay.cs + cl.set + c] = -1.0;
+                }
             }
             auto copy_out = [](double* dst, const double* src, size_t n) { if (dst) memcpy(dst, src, sizeof(double) * n); };
             copy_out(pl.out_z, res + lay.z, p.U);
@@ -722,6 +732,17 @@ int job_fetch(gauss_job* job)
             if (rd.cond) {                         // the imputed SNPs conditioned on the selection (k_cond.hip)
                 copy_out(rd.out.cond_z, res + lay.cond, p.U);
                 copy_out(rd.out.cond_var, res + lay.cond + p.U, p.U);
+            }
+            if (rd.cs) {                           // credible sets of the selected signals (k_cs.hip)
+                const int K = rd.slct_K, T = p.M + p.U;
+                const CsLayout cl = cs_layout(T, K);
+                const double* const cs = res + lay.cs;
+                if (rd.out.cs_size) for (int a = 0; a < K; a++) rd.out.cs_size[a] = (int32_t)cs[cl.size + a];
+                copy_out(rd.out.cs_mass, cs + cl.mass, K);
+                copy_out(rd.out.cs_lse, cs + cl.lse, K);
+                copy_out(rd.out.cs_pip, cs + cl.pip, T);
+                if (rd.out.cs_set) for (int c = 0; c < T; c++) rd.out.cs_set[c] = (int32_t)cs[cl.set + c];
+                copy_out(rd.out.cs_set_pip, cs + cl.set_pip, T);
             }
             if (pl.out_b11 && (!exporting || clamped))
                 { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }

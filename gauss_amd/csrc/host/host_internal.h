@@ -98,12 +98,16 @@ struct gauss_table {
         return (int)(c.type == GAUSS_COL_STR ? c.s.size() : c.type == GAUSS_COL_INT ? c.i.size() : c.d.size());
     }
     // room for MAX_COLS columns (the widest table, dist_cond's 15) is reserved on first use, so the reference add() returns stays
-    // valid while the caller adds the columns that follow; one column more than that would move them all, so it is refused
+    // valid while the caller adds the columns that follow; one column more than that would move them all, so it is refused.
+    // A builder that appends to a finished table (cs_output: dist_cond's 15 and three more) asks for its room with widen()
+    // BEFORE its first add(), while it holds no reference into the table
     enum { MAX_COLS = 16 };
+    size_t room = MAX_COLS;
+    void widen(size_t more) { room = std::max(room, cols.size() + more); cols.reserve(room); }
     Column& add(const char* name, int type)
     {
-        if (cols.size() >= (size_t)MAX_COLS) throw std::length_error("gauss_table::add: more than MAX_COLS columns");
-        cols.reserve(MAX_COLS); Column c; c.name = name; c.type = type; cols.push_back(std::move(c)); return cols.back();
+        if (cols.size() >= room) throw std::length_error("gauss_table::add: no room for another column (MAX_COLS, or what widen() asked for)");
+        cols.reserve(room); Column c; c.name = name; c.type = type; cols.push_back(std::move(c)); return cols.back();
     }
     // a named matrix from column-major data (NamedMat's own layout), taken over without a copy
     void put_named(const char* name, int nrow, int ncol, std::vector<double> colmajor)
@@ -537,6 +541,13 @@ gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, 
 int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int n_sel, const int32_t* idx, const double* zin, const double* joint, const double* zc, const double* var_left,
                  const double* cond_z, const double* cond_var);
+// dist_cs / distmix_cs: cond_output's table `t` of the same call (its `at` rows: every measured SNP has one), the columns pip cs
+// cs_pip added -- cs = the 1-based order of entry of the credible set that holds the SNP (the `order` column's numbering), 0 for none
+// -- and the named matrix `sets` [n_sel x 4]: table row of the lead SNP (from 0), size, mass, lse.  pip / set / set_pip are indexed by
+// candidate: the M = rows.size() measured SNPs first, then the unmeasured ones.  -1 (message set) when `t` is not cond_output's
+int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+              int n_sel, const int32_t* idx, const double* pip, const int32_t* set, const double* set_pip,
+              const int32_t* size, const double* mass, const double* lse);
 // dist_traits / distmix_traits: the Z-scores of one further trait at the n measured SNPs of a window.  SNP i is at(i) -- position and
 // alleles in the window's (the panel's) orientation -- and is looked up in the study `gw` (read from `path`, named in the messages)
 // by (chr, bp, a1, a2): the same allele order gives z, the swapped order -z (gauss.cpp:358-370); of several rows that match, the
@@ -610,6 +621,17 @@ struct SlctRider : Rider {
 // is the plain call's with the named matrices of traits_output added.  miss (the *_traits_miss calls): a measured SNP a further
 // file lacks becomes a bit of miss_more instead of an error, and the window returns that trait's own info and the imputed z of the
 // SNPs it lacks (traits_miss_limits: the limits, before any GPU work)
+// dist_cs / distmix_cs: dist_cond's rider (window, selection and conditional columns are built once, by SlctRider with unmeasured set)
+// with the cs_* fields of gauss_window_desc; the table is dist_cond's with the columns and the named matrix of cs_output added
+struct CsRider : SlctRider {
+    double coverage, prior_var;                                        // the call's own arguments; <= 0 or NaN: 0.95 / 25.0
+    CsRider(double p_cutoff_, double collin_, int max_signals_, const char* const* cond_, int n_cond_, double coverage_, double prior_var_)
+        : SlctRider(p_cutoff_, collin_, max_signals_, cond_, n_cond_, true), coverage(coverage_), prior_var(prior_var_) {}
+    std::vector<double> pip, set_pip, mass, lse;
+    std::vector<int32_t> set, size;
+    int ask(gauss_window_desc& d, const WindowView& v) override;
+    int table(const WindowView& v, gauss_table** out) override;
+};
 struct TraitsRider : Rider {
     const char* const* files; int n_more; bool miss;                   // the call's own arguments: the further files
     TraitsRider(const char* const* files_, int n_more_, bool miss_) : files(files_), n_more(n_more_), miss(miss_) {}

@@ -72,6 +72,32 @@ int SlctRider::table(const WindowView& v, gauss_table** out)
     return 0;
 }
 
+// ---- cs ----
+int CsRider::ask(gauss_window_desc& d, const WindowView& v)
+{
+    if (SlctRider::ask(d, v)) return -1;
+    const size_t T = (size_t)std::max(d.n_measured + d.n_unmeasured, 1), K = (size_t)d.slct_max;
+    pip.assign(T, NAN); set_pip = pip; set.assign(T, -1);
+    size.assign(K, 0); mass.assign(K, NAN); lse = mass;
+    d.cs_coverage = coverage > 0 ? coverage : 0.95;                    // (a NaN compares false: the default)
+    d.cs_prior_var = prior_var > 0 ? prior_var : 25.0;                 // a prior s.d. of 5 on the non-centrality: this project's default
+    d.out_cs_pip = pip.data(); d.out_cs_set = set.data(); d.out_cs_set_pip = set_pip.data();
+    d.out_cs_size = size.data(); d.out_cs_mass = mass.data(); d.out_cs_lse = lse.data();
+    return 0;
+}
+
+int CsRider::table(const WindowView& v, gauss_table** out)
+{
+    if (SlctRider::table(v, out)) return -1;
+    std::vector<SlctRow> rows;
+    for (const ViewSnp& s : v.measured) rows.push_back(SlctRow{s.id, s.af, s.z, s.wing});
+    if (cs_output(**out, rows, v.row_m, v.row_u, n, idx.data(), pip.data(), set.data(), set_pip.data(), size.data(), mass.data(), lse.data())) {
+        gauss_table_free(*out); *out = nullptr;
+        return -1;
+    }
+    return 0;
+}
+
 // ---- traits, traits_miss ----
 int TraitsRider::check()
 {

@@ -318,6 +318,40 @@ int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vec
     return 0;
 }
 
+// dist_cs / distmix_cs: `t` is cond_output's table of the same call -- dist_output's rows, then the wings' measured SNPs in matrix order,
+// which is how the table row of a measured SNP the plain table does not list is found again.  Adds pip, cs (1-based order of entry of
+// the set that holds the SNP, 0: none) and cs_pip, and the named matrix `sets` [n x 4]: table row of the lead SNP, size, mass, lse.
+int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+              int n_sel, const int32_t* idx, const double* pip, const int32_t* set, const double* set_pip,
+              const int32_t* size, const double* mass, const double* lse)
+{
+    size_t listed = 0, wings = 0;
+    for (int32_t r : row_m) (r >= 0 ? listed : wings)++;
+    for (int32_t r : row_u) if (r >= 0) listed++;
+    const size_t nrow = (size_t)t.nrow(), M = rows.size();
+    if (t.cols.empty() || t.cols.back().name != "var_left" || row_m.size() != M || nrow < wings)
+        return herr("cs_output: the table is not the conditional one of the same window");
+    std::vector<int32_t> at(row_m);                                   // cond_output's rows: the wings' SNPs follow the plain table
+    int32_t next = (int32_t)(nrow - wings);
+    for (size_t i = 0; i < M; i++) if (at[i] < 0) at[i] = next++;
+    t.widen(3);
+    Column &p = t.add("pip", GAUSS_COL_DBL), &cs = t.add("cs", GAUSS_COL_INT), &cp = t.add("cs_pip", GAUSS_COL_DBL);
+    p.d.assign(nrow, NAN); cs.i.assign(nrow, 0); cp.d.assign(nrow, NAN);
+    auto put = [&](int32_t r, size_t c) {
+        if (r < 0) return;
+        p.d[(size_t)r] = pip[c]; cs.i[(size_t)r] = set[c] + 1; cp.d[(size_t)r] = set_pip[c];
+    };
+    for (size_t i = 0; i < M; i++) put(at[i], i);
+    for (size_t u = 0; u < row_u.size(); u++) put(row_u[u], M + u);
+    std::vector<double> sets((size_t)n_sel * 4);
+    for (int a = 0; a < n_sel; a++) {
+        sets[(size_t)a] = (double)at[(size_t)idx[a]]; sets[(size_t)n_sel + a] = (double)size[a];
+        sets[2 * (size_t)n_sel + a] = mass[a]; sets[3 * (size_t)n_sel + a] = lse[a];
+    }
+    t.put_named("sets", n_sel, 4, std::move(sets));
+    return 0;
+}
+
 int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out,
                  uint8_t* miss_out, size_t* n_missing)
 {

@@ -337,6 +337,17 @@ class _Win:
                 s["cond_z"], s["cond_var"] = np.full(U, np.nan), np.full(U, np.nan)
                 desc.cond_min_var_frac = float(slct["min_var_frac_u"]) if "min_var_frac_u" in slct else 1.0 - float(slct.get("collin", 0.9))
                 desc.out_cond_z, desc.out_cond_var = s["cond_z"].ctypes.data_as(_dp), s["cond_var"].ctypes.data_as(_dp)
+            # cs=dict(coverage=0.95, prior_var=25.0): a credible set for each selected signal (cs_* of gauss_window_desc).  The unmeasured
+            # candidates' guard is cond_min_var_frac, whether or not unmeasured=True asks for the conditional columns
+            if slct.get("cs") is not None:
+                cs = slct["cs"]
+                T, Kc = M + U, max(K, 0)
+                s.update(cs_pip=np.full(T, np.nan), cs_set=np.full(T, -1, dtype=np.int32), cs_set_pip=np.full(T, np.nan),
+                         cs_size=np.zeros(Kc, dtype=np.int32), cs_mass=np.full(Kc, np.nan), cs_lse=np.full(Kc, np.nan))
+                desc.cond_min_var_frac = float(slct["min_var_frac_u"]) if "min_var_frac_u" in slct else 1.0 - float(slct.get("collin", 0.9))
+                desc.cs_coverage, desc.cs_prior_var = float(cs.get("coverage", 0.95)), float(cs.get("prior_var", 25.0))
+                desc.out_cs_pip, desc.out_cs_set, desc.out_cs_set_pip = s["cs_pip"].ctypes.data_as(_dp), s["cs_set"].ctypes.data_as(_ip), s["cs_set_pip"].ctypes.data_as(_dp)
+                desc.out_cs_size, desc.out_cs_mass, desc.out_cs_lse = s["cs_size"].ctypes.data_as(_ip), s["cs_mass"].ctypes.data_as(_dp), s["cs_lse"].ctypes.data_as(_dp)
         # further traits on the same window (n_traits_more / z_more / out_z_more of gauss_window_desc): z_more [T, M] -> [T, U]
         self.z_more = self.out_z_more = None
         if z_more is not None:
@@ -417,6 +428,10 @@ class _Win:
                        slct_zc=s["zc"], slct_var=s["var"], slct_raw=dict(idx=s["idx"], zin=s["zin"], joint=s["joint"]))
             if "cond_z" in s:
                 out.update(cond_z=s["cond_z"], cond_var=s["cond_var"])
+            if "cs_pip" in s:
+                out.update(cs_pip=s["cs_pip"], cs_set=s["cs_set"], cs_set_pip=s["cs_set_pip"], cs_size=s["cs_size"][:n].copy(),
+                           cs_mass=s["cs_mass"][:n].copy(), cs_lse=s["cs_lse"][:n].copy(),
+                           cs_raw=dict(size=s["cs_size"], mass=s["cs_mass"], lse=s["cs_lse"]))
         return out
 
 
@@ -429,6 +444,8 @@ def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_e
     (include/gauss_hip.h, slct_*): slct_n, slct_idx / slct_zin / slct_joint [n] in order of entry, slct_zc / slct_var [M]; status bit
     8 when a forced SNP failed the collinearity guard.  unmeasured=True in that dict (with min_var_frac_u= to pass their guard as it
     is) adds cond_z / cond_var [U]: the imputed SNPs conditioned on the selected ones (include/gauss_hip.h, out_cond_*).
+    cs=dict(coverage=0.95, prior_var=25.0) in that dict adds a credible set for each selected signal (include/gauss_hip.h, out_cs_*):
+    cs_pip / cs_set / cs_set_pip [M + U] per candidate, the measured SNPs first, and cs_size / cs_mass / cs_lse [n] per signal.
     z_more [T, M] (T <= 63) adds z_more [T, U]: the Z-scores of T further traits measured at the same SNPs, imputed from the same LD
     and the same factorisation (include/gauss_hip.h, n_traits_more); row t is what z would be with z1 = z_more[t].
     miss_more [T, M] (non-zero: further trait t has no score at measured SNP m; at most 32 per trait, 128 distinct per window) makes row t
@@ -572,8 +589,8 @@ class Job:
         """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more, miss_more])
         or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
         loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs).
-        slct=dict(max=, chi2_stop=, collin=, forced=[, unmeasured=True]) in a window's dict: its result carries the signal selection
-        (and the imputed SNPs conditioned on it; impute_window).
+        slct=dict(max=, chi2_stop=, collin=, forced=[, unmeasured=True][, cs=dict(coverage=, prior_var=)]) in a window's dict: its
+        result carries the signal selection (and the imputed SNPs conditioned on it, and the signals' credible sets; impute_window).
         z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window).
         miss_more=[T, M] beside it: the SNPs each further trait lacks; the result carries info_more, z_miss, info_miss (impute_window)."""
         self.ctx = ctx or default_context()

@@ -109,6 +109,43 @@ typedef struct gauss_window_desc {
     const int32_t* rows_m;    /* [M] store row of each measured SNP, or NULL          host pointer */
     const int32_t* rows_u;    /* [U] store row of each geno_u SNP, or NULL            host pointer */
     const int32_t* pop_src_off; /* [P] 2-bit format: byte offset of each population block, or NULL */
+    /* ---- credible sets of the selected signals (needs slct_max > 0; the notation is that of the two blocks below) --
+     * For each selected signal, which SNPs could be the causal one?  The candidates are the M measured SNPs (candidate index
+     * 0 .. M-1) and the U unmeasured ones (M .. M+U-1), the latter with the variance an imputed SNP really has.  With B, z, S,
+     * L, y, w_u, m_u, info_u of the selection's and the conditional block, w_i = L^-1 B_Si for a measured SNP, P = B_SS^-1,
+     * beta = P z_S and g = L^-T w:
+     *   given all of S:     measured i:   r_i = z_i - w_i . y,  v_i = B_ii - w_i . w_i
+     *                       unmeasured u: r_u = m_u - w_u . y,  v_u = info_u - w_u . w_u
+     *   signal a left out:  r' = r + g_a beta_a / P_aa,  v' = v + g_a^2 / P_aa,  zc = r' / sqrt(v')
+     *                       (a rank-one update: nothing is factorised per signal)
+     *   share of variance:  s = v' / B_ii (measured),  s = v' (unmeasured: the info scale already)
+     * SNP sel[a] in its own set has zc = out_slct_joint[a] (the same bits) and v' = 1 / P_aa and is always a candidate;
+     * sel[b], b != a, is no candidate of set a.  Any other measured SNP is a candidate of set a while
+     * v' > slct_min_var_frac * B_ii and its z is finite, an unmeasured one while v' > cond_min_var_frac * info_u, info_u > 0 and its z is finite:
+     * the two existing guards, applied to the leave-one-out variance (cond_min_var_frac is read whether or not out_cond_* ask).
+     * With the causal SNP's non-centrality ~ N(0, cs_prior_var = omega), zc ~ N(0, 1 + omega s) under "this SNP is the
+     * causal one of signal a", so
+     *   lbf_ia = ( zc^2 omega s / (1 + omega s) - log1p(omega s) ) / 2         -inf for a non-candidate
+     *   lse_a  = log sum_i exp(lbf_ia),   pip_ia = exp(lbf_ia - lse_a)         uniform prior over the candidates
+     * Candidate i is in credible set a iff pip_ia > 0 and the mass ranked ahead of it (larger pip_ia; ties: the smaller
+     * candidate index) is below cs_coverage = rho: the shortest prefix whose mass reaches rho (rho = 1: every candidate
+     * with pip_ia > 0).  Per candidate:
+     *   out_cs_pip = 1 - prod_a (1 - pip_ia);  out_cs_set = the 0-based signal a of largest pip_ia among the sets that hold
+     *   it (ties: the smaller a), -1 for none;  out_cs_set_pip = that pip_ia, 0 for none.
+     * Per signal: out_cs_size = members, out_cs_mass = the sum of their pip_ia (>= rho), out_cs_lse = lse_a; slots a >= n hold
+     * size 0 and NaN.  Nothing selected (n = 0): pip 0, set -1, set_pip 0.  GAUSS_ST_NONFINITE windows return NaN, size 0
+     * and set -1.  Any out_cs_* being non-NULL switches the computation on; with slct_max = 0, on QCAT and LD windows,
+     * with cs_coverage outside (0, 1] or not finite, and with cs_prior_var <= 0 or not finite, that is GAUSS_E_INVALID.
+     * One causal SNP per signal, z units.  Three kernels behind the conditional step (k_cs.hip), fp64, sums in a fixed
+     * order.  (The block sits in front of the selection's: every later field keeps its neighbours, the leave-one-out arrays stay last.) */
+    double   cs_coverage;      /* rho in (0, 1]                                                             */
+    double   cs_prior_var;     /* omega > 0: prior variance of the causal SNP's non-centrality, in z units  */
+    double*  out_cs_pip;       /* [M+U] measured first   host pointer / NULL; any out_cs_* non-NULL switches it on */
+    int32_t* out_cs_set;       /* [M+U]                                                          optional   */
+    double*  out_cs_set_pip;   /* [M+U]                                                          optional   */
+    int32_t* out_cs_size;      /* [slct_max]                                                     optional   */
+    double*  out_cs_mass;      /* [slct_max]                                                     optional   */
+    double*  out_cs_lse;       /* [slct_max]                                                     optional   */
     /* ---- stepwise conditional signal selection among the measured SNPs (GAUSS_WIN_IMPUTE windows only) -----------
      * How many independent signals the window holds: condition on the top SNPs and look at what is left.  With B = B11
      * (lambda on the diagonal, after MakePosDef if it acted), z = z1 and S the ordered set of selected SNPs, the statistic

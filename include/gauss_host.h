@@ -207,6 +207,30 @@ int gauss_host_distmix_cond(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t e
                             const char* reference_data_file, const char* reference_pop_desc_file,
                             double af1_cutoff, double p_cutoff, double collin, int max_signals,
                             const char* const* cond_rsids, int n_cond, gauss_table** out);
+/* Credible sets of the selected signals: for each signal, which SNPs -- measured or imputed -- could be the causal one?
+ * Arguments, window, data layer, single job, refusals and table of gauss_host_dist_cond / gauss_host_distmix_cond (the same rows, the
+ * same bits in the shared columns); the job's window also sets the cs_* fields of gauss_window_desc (include/gauss_hip.h: the
+ * leave-one-signal-out statistic, the Bayes factor, the membership rule) with
+ *   coverage   rho in (0, 1]: the share of a signal's posterior mass its set holds; <= 0 or NaN: 0.95
+ *   prior_var  omega > 0: prior variance of the causal SNP's non-centrality, in z units; <= 0 or NaN: 25.0 (a prior s.d. of 5: a
+ *              documented default of this project, not a measured value)
+ * coverage > 1 and a non-finite prior_var are refused by the window (GAUSS_E_INVALID).
+ * Appended columns: pip (1 - prod over the signals of 1 - pip_ia), cs (the 1-based order of entry of the set that holds the SNP, as in
+ * the `order` column; 0: in none) and cs_pip (its pip in that set; 0: none).  Named matrices: `signals` as gauss_host_dist_cond has
+ * it, and `sets` [n x 4] in order of entry: table row of the lead SNP (from 0), size, mass, lse.
+ * Limits: the candidates are the measured SNPs of the extended window and the unmeasured SNPs of the prediction window, so a signal
+ * near a window edge has a truncated set; one causal SNP per signal; uniform prior; z units; at most GAUSS_SLCT_MAX signals. */
+int gauss_host_dist_cs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                       const char* study_pop, const char* input_file, const char* reference_index_file,
+                       const char* reference_data_file, const char* reference_pop_desc_file,
+                       double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                       const char* const* cond_rsids, int n_cond, double coverage, double prior_var, gauss_table** out);
+int gauss_host_distmix_cs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                          const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                          const char* input_file, const char* reference_index_file,
+                          const char* reference_data_file, const char* reference_pop_desc_file,
+                          double af1_cutoff, double p_cutoff, double collin, int max_signals,
+                          const char* const* cond_rsids, int n_cond, double coverage, double prior_var, gauss_table** out);
 /* The chi^2 (1 df) threshold of a two-sided p-value: the smallest double chi2 with 2 pnorm(-sqrt(chi2)) < p in the library's own
  * normal tail, found by bisection on the bit pattern -- monotone in p, and exact to the last bit that changes the comparison.
  * p must be positive. */

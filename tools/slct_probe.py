@@ -1,11 +1,14 @@
-"""Times the signal selection (k_slct.hip) and the imputed SNPs conditioned on it (k_cond.hip) on the chr22 study's jobs.
+"""Times the signal selection (k_slct.hip), the imputed SNPs conditioned on it (k_cond.hip) and the credible sets of the selected
+signals (k_cs.hip) on the chr22 study's jobs.
 
   (a) step time of the 36-window chr22 job (distmix, resident 2-bit store, the headline's job) and of its largest window alone
-      (M = 1 213), in three forms: plain, every window selecting (32 steps at the genome-wide threshold, and with `--stop 0` all 32
-      taken), and every window selecting and conditioning its imputed SNPs.  The forms alternate on the same build and the same
-      box, two rounds each: the spread between two identical runs is the margin of the comparison;
-  (b) from a `rocprofv3 --kernel-trace --stats` run of its own for each job: the time of slct_kernel and of cond_kernel per step,
-      grouped by kernel name (one launch each a step; a clamped window's re-launches inside the fetch are counted with their step).
+      (M = 1 213, U = 2 512), in four forms: plain, every window selecting (32 steps at the genome-wide threshold, and with
+      `--stop 0` all 32 taken, so that all 32 sets are built), every window selecting and conditioning its imputed SNPs, and every
+      window asking for credible sets on top.  The forms alternate on the same build and the same box, two rounds each: the spread
+      between two identical runs is the margin of the comparison;
+  (b) from a `rocprofv3 --kernel-trace --stats` run of its own for each job: the time of slct_kernel, of cond_kernel and of the
+      three cs kernels per step, grouped by kernel name (one launch each a step; a clamped window's re-launches inside the fetch
+      are counted with their step).
 
 Every GPU step is a child process under its own time limit; this process never opens the GPU.  A child that fails ends the probe.
 
@@ -27,7 +30,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-FORMS = ("plain", "slct", "cond")
+FORMS = ("plain", "slct", "cond", "cs")
 
 
 def _jobs(snps, stop):
@@ -58,7 +61,8 @@ def _jobs(snps, stop):
                   packed=dict(fmt=1, rows_m=mi.astype(np.int32), rows_u=ui.astype(np.int32))) for _, mi, ui in wins]
     big = max(range(len(descs)), key=lambda k: descs[k]["dev"][2])
     slct = dict(max=32, chi2_stop=stop)
-    forms = lambda ds: dict(plain=ds, slct=[dict(d, slct=slct) for d in ds], cond=[dict(d, slct=dict(slct, unmeasured=True)) for d in ds])
+    forms = lambda ds: dict(plain=ds, slct=[dict(d, slct=slct) for d in ds], cond=[dict(d, slct=dict(slct, unmeasured=True)) for d in ds],
+                            cs=[dict(d, slct=dict(slct, unmeasured=True, cs=dict(coverage=0.95, prior_var=25.0))) for d in ds])
     return hotpath, ctx, dict(chr22=forms(descs), largest=forms([descs[big]])), store
 
 
@@ -69,7 +73,8 @@ def child_time(a):
         made = {k: hotpath.Job(forms[k], ctx=ctx, on_device=True) for k in FORMS}
         rounds = {k: [] for k in FORMS}
         n_sel = []
-        for _ in range(2):                                   # plain, slct, cond, plain, slct, cond: two identical runs of each form
+        set_sizes = []
+        for _ in range(2):                                   # plain, slct, cond, cs, plain, slct, cond, cs: two identical runs of each form
             for key, job in made.items():
                 for _ in range(a.warmup):
                     job.run()
@@ -83,6 +88,8 @@ def child_time(a):
                 rounds[key].append(round(float(np.median(ts)) * 1e3, 4))
                 if key == "cond":
                     n_sel = [int(r["slct_n"]) for r in res]
+                if key == "cs":
+                    set_sizes = [int(r["cs_size"].sum()) for r in res]
         for job in made.values():
             job.close()
         ms, us = [d["dev"][2] for d in forms["plain"]], [d["dev"][3] for d in forms["plain"]]
@@ -91,13 +98,14 @@ def child_time(a):
                          step_ms={k: rounds[k] for k in FORMS},
                          spread_ms=round(max(abs(rounds[k][0] - rounds[k][1]) for k in FORMS), 4),
                          slct_added_ms=round(min(rounds["slct"]) - min(rounds["plain"]), 4),
-                         cond_added_ms=round(min(rounds["cond"]) - min(rounds["slct"]), 4))
+                         cond_added_ms=round(min(rounds["cond"]) - min(rounds["slct"]), 4),
+                         cs_added_ms=round(min(rounds["cs"]) - min(rounds["cond"]), 4), set_members=set_sizes)
     print(json.dumps(out), flush=True)
 
 
 def child_trace(a):
     hotpath, ctx, jobs, _keep = _jobs(a.snps, a.stop)
-    job = hotpath.Job(jobs[a.job]["cond"], ctx=ctx, on_device=True)       # one job a traced process: every kernel row is this job's
+    job = hotpath.Job(jobs[a.job]["cs"], ctx=ctx, on_device=True)       # one job a traced process: every kernel row is this job's
     for _ in range(a.steps):
         job.run()
         job.fetch()
@@ -106,11 +114,11 @@ def child_trace(a):
 
 
 def trace_times(rows, steps):
-    """Time of slct_kernel and cond_kernel per step from the kernel-trace rows of ONE job's process, grouped by kernel name.  A step
-    launches each kernel once; a clamped window launches both again inside the fetch, which belongs to the step and is counted in
+    """Time of slct_kernel, cond_kernel and the cs kernels per step from the kernel-trace rows of ONE job's process, grouped by kernel name.  A step
+    launches each kernel once; a clamped window launches them again inside the fetch, which belongs to the step and is counted in
     `launches`.  Fewer launches than steps means the trace is not the one expected: an error, not a missing figure."""
     res = {}
-    for key in ("slct_kernel", "cond_kernel"):
+    for key in ("slct_kernel", "cond_kernel", "cs_lbf_kernel", "cs_set_kernel", "cs_fold_kernel"):
         us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if key in r.get("Kernel_Name", "")]
         if len(us) < steps:
             raise SystemExit(f"slct_probe: the trace holds {len(us)} launches of {key} for {steps} steps")
