@@ -26,6 +26,10 @@ TRAITS_MORE_MAX = 63     # GAUSS_TRAITS_MORE_MAX
 TRAITS_MISS_MAX = 32     # GAUSS_TRAITS_MISS_MAX
 TRAITS_MISS_UNION_MAX = 128   # GAUSS_TRAITS_MISS_UNION_MAX
 ST_SLCT_SKIPPED = 8      # GAUSS_ST_SLCT_SKIPPED
+ST_SUSIE_NOCONV = 16     # GAUSS_ST_SUSIE_NOCONV
+ST_SUSIE_NOFIT = 32      # GAUSS_ST_SUSIE_NOFIT
+SUSIE_MAX_L = 32         # GAUSS_SUSIE_MAX_L
+SUSIE_MAX_SWEEPS = 1000  # GAUSS_SUSIE_MAX_SWEEPS
 CODE_ADDITIVE, CODE_DOMINANT, CODE_RECESSIVE = 1, 2, 4
 GRAM_F32 = 0
 GRAM_I8 = 1
@@ -44,6 +48,11 @@ class WindowDesc(C.Structure):
         ("out_z", _dp), ("out_info", _dp), ("out_status", _ip), ("out_b11", _dp), ("out_b21", _dp),
         ("kind", C.c_int), ("n_head_measured", C.c_int), ("n_pred_measured", C.c_int), ("eig_cutoff", C.c_double),
         ("out_r", _dp), ("out_num_eig", _ip), ("u_codings", C.c_int),
+        ("susie_L", C.c_int), ("susie_coverage", C.c_double), ("susie_prior_var", C.c_double), ("susie_tol", C.c_double),
+        ("susie_min_abs_corr", C.c_double), ("out_susie_pip", _dp), ("out_susie_set", _ip), ("out_susie_set_pip", _dp),
+        ("out_susie_V", _dp), ("out_susie_lse", _dp), ("out_susie_mass", _dp), ("out_susie_purity", _dp),
+        ("out_susie_size", _ip), ("out_susie_kept", _ip), ("out_susie_alpha", _dp), ("out_susie_mu", _dp), ("out_susie_sweeps", _dp),
+        ("susie_max_sweeps", C.c_int), ("susie_estimate_var", C.c_int), ("susie_measured_only", C.c_int),
         ("geno_format", C.c_int), ("rows_m", _ip), ("rows_u", _ip), ("pop_src_off", _ip),
         ("cs_coverage", C.c_double), ("cs_prior_var", C.c_double), ("out_cs_pip", _dp), ("out_cs_set", _ip), ("out_cs_set_pip", _dp),
         ("out_cs_size", _ip), ("out_cs_mass", _dp), ("out_cs_lse", _dp),

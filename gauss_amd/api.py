@@ -48,7 +48,7 @@ HOST_SYMBOLS = [
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
-    "gauss_host_dist_cs", "gauss_host_distmix_cs",
+    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie",
     "gauss_host_dist_traits", "gauss_host_distmix_traits", "gauss_host_dist_traits_miss", "gauss_host_distmix_traits_miss",
 ]
 
@@ -145,6 +145,9 @@ def load_host():
     h.gauss_host_distmix_cond.argtypes = h.gauss_host_distmix_slct.argtypes
     h.gauss_host_dist_cs.argtypes = h.gauss_host_dist_slct.argtypes[:-1] + [_dbl, _dbl, C.POINTER(_vp)]      # ..., coverage, prior_var, out
     h.gauss_host_distmix_cs.argtypes = h.gauss_host_distmix_slct.argtypes[:-1] + [_dbl, _dbl, C.POINTER(_vp)]
+    susie_tail = [C.c_int, _dbl, _dbl, _dbl, C.c_int, _dbl, C.c_int, C.c_int, C.POINTER(_vp)]      # L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only, out
+    h.gauss_host_dist_susie.argtypes = h.gauss_host_dist.argtypes[:-1] + susie_tail
+    h.gauss_host_distmix_susie.argtypes = h.gauss_host_distmix.argtypes[:-1] + susie_tail
     traits_tail = [_strs, C.c_int, C.POINTER(_vp)]                           # more_input_files, n_more, out
     h.gauss_host_dist_traits.argtypes = h.gauss_host_dist.argtypes[:-1] + traits_tail
     h.gauss_host_distmix_traits.argtypes = h.gauss_host_distmix.argtypes[:-1] + traits_tail
@@ -457,6 +460,51 @@ def distmix_cs(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, referen
     return _cond_frame(*_window_call("gauss_host_distmix_cs", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
                      (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
                      _slct_args(p_cutoff, collin, max_signals, cond_rsids) + _cs_args(coverage, prior_var)), sets=True)
+
+
+def _susie_args(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only):
+    f = lambda v: 0.0 if v is None else float(v)
+    return (0 if L is None else int(L), f(coverage), f(prior_var), f(min_abs_corr), 0 if max_sweeps is None else int(max_sweeps), f(tol),
+            -1 if estimate_prior_var is None else int(bool(estimate_prior_var)), int(bool(measured_only)))
+
+
+def _susie_frame(h, out):
+    named = _named(h, out)
+    df = _table(h, out)[0]                                 # (frees the table: nothing may fail between the two reads and this)
+    e = np.asarray(named["effects"], dtype=np.float64).reshape(-1, 7)
+    df.attrs["effects"] = dict(row=e[:, 0].astype(np.int64), V=e[:, 1].copy(), lse=e[:, 2].copy(), size=e[:, 3].astype(np.int64),
+                               mass=e[:, 4].copy(), purity=e[:, 5].copy(), kept=e[:, 6] != 0)
+    f = np.asarray(named["fit"], dtype=np.float64).reshape(-1)
+    df.attrs["fit"] = dict(sweeps=int(f[0]), delta=float(f[1]), converged=bool(f[2]))
+    return df
+
+
+def dist_susie(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
+               reference_pop_desc_file, af1_cutoff=None, L=None, coverage=None, prior_var=None, min_abs_corr=None, max_sweeps=None, tol=None,
+               estimate_prior_var=None, measured_only=False, ctx=None):
+    """Multi-causal fine-mapping of a dist() window (gauss_host_dist_susie): the "sum of single effects" model (SuSiE-RSS) fitted to the
+    measured z, with the imputed SNPs as candidates beside the measured ones, each with the variance an imputed SNP really has.  Unlike
+    dist_cs() it does not build on a stepwise selection: a measured SNP that tags two causal SNPs does not mislead it.
+    L (None: 10, at most 32) effects; coverage (None: 0.95); prior_var (None: 25.0, in z units); min_abs_corr (None: 0.5), the purity a
+    reported set needs; max_sweeps (None: 100, at most 1000); tol (None: 1e-4; negative: exactly max_sweeps sweeps); estimate_prior_var (None: True);
+    measured_only=True: plain SuSiE-RSS on the measured SNPs.  The frame has dist()'s rows (same bits in the shared columns), then the
+    measured SNPs of the wings, with wing, pip, cs (1-based effect of the reported set that holds the SNP, 0: none) and cs_pip appended.
+    frame.attrs["effects"] = dict(row, V, lse, size, mass, purity, kept) per effect; frame.attrs["fit"] = dict(sweeps, delta, converged).
+    Limits: the candidates are the measured SNPs of the extended window and the unmeasured SNPs of the prediction window; a window whose
+    B11 MakePosDef repairs is not fitted (a message says so); z units; L <= 32; residual variance fixed at 1; uniform prior."""
+    return _susie_frame(*_window_call("gauss_host_dist_susie", (chr, start_bp, end_bp, wing_size), study_pop,
+                        (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                        _susie_args(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only)))
+
+
+def distmix_susie(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
+                  reference_pop_desc_file, af1_cutoff=None, L=None, coverage=None, prior_var=None, min_abs_corr=None, max_sweeps=None, tol=None,
+                  estimate_prior_var=None, measured_only=False, ctx=None):
+    """Multi-causal fine-mapping of a distmix() window (gauss_host_distmix_susie), on the ancestry-weighted LD; columns as dist_susie
+    with af1mix."""
+    return _susie_frame(*_window_call("gauss_host_distmix_susie", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                        (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                        _susie_args(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only)))
 
 
 def slct_chi2(p):

@@ -35,6 +35,7 @@ HIP_UNITS = {
     "k_slct.hip": ["-ffp-contract=off"],        # signal selection: the recurrence as written, sums in ascending order
     "k_cond.hip": ["-ffp-contract=off"],        # imputed SNPs conditioned on the selection: the forward substitution as written, sums in ascending order
     "k_cs.hip": ["-ffp-contract=off"],          # credible sets of the selected signals: the downdate as written, sums in a fixed order
+    "k_susie.hip": ["-ffp-contract=off"],       # multi-causal fine-mapping: the fit's sums as written, in a fixed order
     "k_traits.hip": ["-ffp-contract=off"],      # further traits: MFMA chains in ascending k, the closing division as written
     "k_traits_miss.hip": ["-ffp-contract=off"], # traits that lack some measured SNPs: the downdate's recurrences as written, sums in ascending order
 }

@@ -30,6 +30,13 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.cs_coverage = d.cs_coverage; w.cs_prior_var = d.cs_prior_var;
     w.out.cs_pip = d.out_cs_pip; w.out.cs_set = d.out_cs_set; w.out.cs_set_pip = d.out_cs_set_pip;
     w.out.cs_size = d.out_cs_size; w.out.cs_mass = d.out_cs_mass; w.out.cs_lse = d.out_cs_lse;
+    w.susie_L = d.susie_L; w.susie_coverage = d.susie_coverage; w.susie_prior_var = d.susie_prior_var; w.susie_tol = d.susie_tol;
+    w.susie_max_sweeps = d.susie_max_sweeps; w.susie_min_abs_corr = d.susie_min_abs_corr;
+    w.susie_estimate_var = d.susie_estimate_var; w.susie_measured_only = d.susie_measured_only;
+    w.out.susie_pip = d.out_susie_pip; w.out.susie_set = d.out_susie_set; w.out.susie_set_pip = d.out_susie_set_pip;
+    w.out.susie_V = d.out_susie_V; w.out.susie_lse = d.out_susie_lse; w.out.susie_mass = d.out_susie_mass; w.out.susie_purity = d.out_susie_purity;
+    w.out.susie_size = d.out_susie_size; w.out.susie_kept = d.out_susie_kept;
+    w.out.susie_alpha = d.out_susie_alpha; w.out.susie_mu = d.out_susie_mu; w.out.susie_sweeps = d.out_susie_sweeps;
     return w;
 }
 extern "C" {

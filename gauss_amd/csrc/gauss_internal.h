@@ -139,6 +139,13 @@ struct Prob {
     GP(double) cs_lbf;                     // [slct_max][cs_tld(M + U)] scratch: log Bayes factors, then pip, of every candidate per signal
     GP(uint8_t) cs_mem;                    // [slct_max][cs_tld(M + U)] scratch: 1 where the candidate is in the signal's set
     GP(double) out_cs;                     // [cs_layout(M + U, K).count]
+    // multi-causal fine-mapping of the window (k_susie.hip); susie_L = 0: not asked
+    int susie_L, susie_max_sweeps;         // effects L <= SUSIE_L, sweeps over them at the most
+    int susie_estimate_var, susie_measured_only, susie_am;      // flags; am: the result section also holds alpha and mu
+    double susie_coverage, susie_prior_var, susie_tol, susie_min_abs_corr;
+    GP(double) susie_ws;                   // [susie_ws(M, U, Mld, L, !measured_only).count] scratch: W = B11^-1 B12, the fit's state (SusieWs below)
+    GP(uint8_t) susie_mem;                 // [L][cs_tld(M + U)] scratch: 1 where the candidate is in the effect's set
+    GP(double) out_susie;                  // [susie_layout(M + U, L, am).count]
     // further traits on the same window (k_traits.hip); traits_T = 0: not asked
     int traits_T;                          // T <= TRAITS_MAX further Z-score vectors
     GP(const double) traits_Z;             // [Mld][T16] their Z-scores, SNP-major, zero beyond M and T (T16 = T rounded up to 16)
@@ -163,6 +170,9 @@ inline void clear_riders(Prob& q)
     q.slct_forced = nullptr; q.slct_W = nullptr; q.out_slct = nullptr;
     q.cond_min_var_frac = 0.0; q.out_cond = nullptr;
     q.cs_coverage = q.cs_prior_var = 0.0; q.cs_lbf = nullptr; q.cs_mem = nullptr; q.out_cs = nullptr;
+    q.susie_L = q.susie_max_sweeps = q.susie_estimate_var = q.susie_measured_only = q.susie_am = 0;
+    q.susie_coverage = q.susie_prior_var = q.susie_tol = q.susie_min_abs_corr = 0.0;
+    q.susie_ws = nullptr; q.susie_mem = nullptr; q.out_susie = nullptr;
     q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr;
     q.miss_E = q.miss_nm = q.miss_n = 0; q.miss_tab = nullptr;
     q.miss_YE = q.miss_AE = q.miss_YU = q.miss_LD = q.out_traits_info = q.out_traits_miss = nullptr;
@@ -183,15 +193,41 @@ constexpr int COND_T = 128;            // threads of cond_kernel: one per unmeas
 constexpr int CS_T = 128;              // threads of cs_lbf_kernel and cs_fold_kernel: one per candidate of its block
 constexpr int CS_SET_T = 512;          // threads of cs_set_kernel
 constexpr int cs_tld(int T) { return (T + 15) & ~15; }      // row pitch of Prob::cs_lbf / cs_mem
+constexpr int SUSIE_L = 32;            // GAUSS_SUSIE_MAX_L: cs_set_row's workspace geometry, one row per effect
+constexpr int SUSIE_MAX_SWEEPS = 1000; // GAUSS_SUSIE_MAX_SWEEPS: a run queues max_sweeps x L x 2 launches up front
+constexpr int SUSIE_T = 256;           // threads of the fit's kernels
+constexpr int SUSIE_CH = 1024;         // unmeasured candidates whose mean effects sit in LDS at a time (susie_ser_v_kernel)
+constexpr int SUSIE_VR = 8;            // rows of v = b_meas + W b_unmeas a workgroup writes (two a wave)
+constexpr int SUSIE_RR = 8;            // rows of R b = [B v ; C v] a workgroup writes (two a wave)
+constexpr int SUSIE_P = 128;           // members of a set the purity looks at
+constexpr int SUSIE_PG = 32;           // workgroups that share the pairs of one set's purity
+constexpr int susie_uld(int U) { return (U + 63) & ~63; }   // row pitch of W and Y
+// Prob::susie_ws in doubles.  Y = X C^T and W = X^T Y = B11^-1 B12 [Mld][uld]; zhat, d, adm [tld] per candidate; alpha, mu, rb
+// (R b_l) and lbf [L][tld]; f [tld]; v [Mld]; V [2][SUSIE_L] by sweep parity; lse, lse_set, part [SUSIE_L][SUSIE_PG] (partial minima of
+// the purity), top [SUSIE_L][SUSIE_P] (candidate indices as ints: half the doubles), ntop [SUSIE_L]; ctl: done, sweeps, last
+// delta, delta by sweep parity [2], z1 holds a NaN.  state .. count is zeroed by susie_prep_kernel at the start of every run.
+struct SusieWs { size_t Y, W, zhat, d, adm, state, alpha, mu, rb, lbf, f, v, V, lse, lse_set, part, top, ntop, ctl, count; };
+enum { SUSIE_CTL_DONE = 0, SUSIE_CTL_SWEEPS, SUSIE_CTL_LAST, SUSIE_CTL_DELTA, SUSIE_CTL_ZNAN = SUSIE_CTL_DELTA + 2, SUSIE_CTL_N = 8 };
+// (w = false: a fit of the measured SNPs alone forms no W)
+constexpr SusieWs susie_ws(int M, int U, int Mld, int L, bool w)
+{
+    const size_t tld = (size_t)cs_tld(M + U), mu = w ? (size_t)Mld * susie_uld(U) : 0, lt = (size_t)L * tld;
+    const size_t zhat = 2 * mu, state = zhat + 3 * tld, f = state + 4 * lt, V = f + tld + (size_t)Mld, lse = V + 2 * SUSIE_L;
+    const size_t part = lse + 2 * SUSIE_L, top = part + (size_t)SUSIE_L * SUSIE_PG, ntop = top + (size_t)SUSIE_L * SUSIE_P / 2;
+    return {0, mu, zhat, zhat + tld, zhat + 2 * tld, state, state, state + lt, state + 2 * lt, state + 3 * lt, f, f + tld, V, lse,
+            lse + SUSIE_L, part, top, ntop, ntop + SUSIE_L, ntop + SUSIE_L + SUSIE_CTL_N};
+}
 
 // ---- the result block ------------------------------------------------------------------------------------------------
 // A window's doubles in the job's result block, in this order and nowhere else written down:
 //     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, traits_info [T][U], traits_miss [2][n_miss]]
 //     [, the selection] [, cond_z[U], cond_var[U]] [, cs: size[K], mass[K], lse[K], pip[M+U], set[M+U], set_pip[M+U]]
+//     [, susie: susie_layout]
 // Offsets in doubles from the window's Plan::res_off; a section nobody asked for takes nothing and its offset is that of the next.
 // traits_info and traits_miss exist when the window passed a mask (miss): n_miss = its set bits.  The conditional section
-// (cond; k_cond.hip) and behind it the credible sets (cs; k_cs.hip) are the last: every other offset is what it is without them.
-struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, count; };
+// (cond; k_cond.hip), behind it the credible sets (cs; k_cs.hip) and behind them the multi-causal fit (susie; k_susie.hip) are the
+// last: every other offset is what it is without them.
+struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, count; };
 // Inside the selection's section, from its start: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] (indices, n and the
 // skipped flag travel as exact doubles).  The host and slct_kernel both read it here.
 struct SlctLayout { size_t n, skipped, idx, zin, joint, zc, var, count; };
@@ -206,14 +242,25 @@ constexpr CsLayout cs_layout(int T, int K)
 {
     return {0, (size_t)K, 2 * (size_t)K, 3 * (size_t)K, 3 * (size_t)K + (size_t)T, 3 * (size_t)K + 2 * (size_t)T, 3 * (size_t)K + 3 * (size_t)T};
 }
+// Inside the multi-causal fit's section, from its start: V, lse, size, mass, purity, kept [L] per effect, fit [4] = sweeps run, the
+// last delta, 1 when the sweeps ran out before delta < tol, unused; pip, set, set_pip [T] per candidate (T = M + U, the measured
+// SNPs first); with am, alpha [L][T] and mu [L][T].  Sizes, set, kept and sweeps travel as exact doubles.
+struct SusieLayout { size_t V, lse, size, mass, purity, kept, fit, pip, set, set_pip, alpha, mu, count; };
+constexpr SusieLayout susie_layout(int T, int L, bool am)
+{
+    const size_t l = (size_t)L, t = (size_t)T, c = 6 * l + 4;
+    return {0, l, 2 * l, 3 * l, 4 * l, 5 * l, 6 * l, c, c + t, c + 2 * t, c + 3 * t, c + 3 * t + (am ? l * t : 0), c + 3 * t + (am ? 2 * l * t : 0)};
+}
 constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, bool miss = false, int n_miss = 0, bool cond = false,
-                               bool cs = false)
+                               bool cs = false, int susie_L = 0, bool susie_am = false)
 {
     const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_tinfo = o_traits + (size_t)T * U;
     const size_t o_tmiss = o_tinfo + (miss ? (size_t)T * U : 0), o_slct = o_tmiss + (miss ? 2 * (size_t)n_miss : 0);
     const size_t o_cond = o_slct + (K ? slct_layout(M, K).count : 0);
     const size_t o_cs = o_cond + (cond ? 2 * (size_t)U : 0);
-    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_cs + (cs ? cs_layout(M + U, K).count : 0)};
+    const size_t o_susie = o_cs + (cs ? cs_layout(M + U, K).count : 0);
+    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie,
+            o_susie + (susie_L ? susie_layout(M + U, susie_L, susie_am).count : 0)};
 }
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
@@ -330,6 +377,13 @@ void launch_cond(const Prob* d_probs, const int* d_condmap, int n, int max_U, hi
 // d_probs[0 .. n)); max_T = the most candidates (M + U) one of them has.  They run behind launch_cond's place: behind launch_slct and
 // behind the kernel that writes out_z / out_info
 void launch_cs(const Prob* d_probs, const int* d_csmap, int n, int max_T, hipStream_t s);
+// multi-causal fine-mapping (k_susie.hip) of the asking windows (d_susiemap; null: the windows d_probs[0 .. n)).  launch_susie_w:
+// W = X^T (X B12) of the windows that fit unmeasured candidates, two launches over (64-row block of X) x (64 unmeasured SNPs); it runs
+// where launch_traits_weights runs (B21 is complete there).  launch_susie: the state, then max_sweeps x max_L x 2 dependent launches
+// -- a window that has converged, has fewer effects or fewer sweeps leaves at once -- then the sets, their purity and the fold; it runs
+// behind launch_cs.  max_M / max_U / max_T / max_L / max_sweeps: the largest among the asking windows
+void launch_susie_w(const Prob* d_probs, const int* d_susiemap, int n, int max_nblk, int max_U, hipStream_t s);
+void launch_susie(const Prob* d_probs, const int* d_susiemap, int n, int max_M, int max_T, int max_L, int max_sweeps, hipStream_t s);
 // further traits (k_traits.hip).  launch_traits_weights: G = X^T (X Z) of the windows that asked, d_map = (window, 64-row block of X),
 // two launches (Y = X Z, then G = X^T Y); it runs where launch_loo runs.  launch_traits_impute: out_traits = B21 G / sqrt(out_info),
 // d_umap = (window, strip of 64 unmeasured SNPs); it runs behind the kernel that writes out_info

@@ -240,6 +240,9 @@ struct RiderOuts {
     double *cond_z = nullptr, *cond_var = nullptr;      // the imputed SNPs conditioned on the selection (gauss_window_desc.out_cond_*)
     double *cs_pip = nullptr, *cs_set_pip = nullptr, *cs_mass = nullptr, *cs_lse = nullptr;      // credible sets (gauss_window_desc.out_cs_*)
     int32_t *cs_set = nullptr, *cs_size = nullptr;
+    double *susie_pip = nullptr, *susie_set_pip = nullptr, *susie_V = nullptr, *susie_lse = nullptr, *susie_mass = nullptr;      // the multi-causal fit
+    double *susie_purity = nullptr, *susie_alpha = nullptr, *susie_mu = nullptr, *susie_sweeps = nullptr;                        // (gauss_window_desc.out_susie_*)
+    int32_t *susie_set = nullptr, *susie_size = nullptr, *susie_kept = nullptr;
     double* z_more = nullptr;
     double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
 };
@@ -280,15 +283,17 @@ struct Plan {
         std::vector<int> slct_forced;
         bool cond = false;                   // the imputed SNPs conditioned on the selection (k_cond.hip); needs slct_K
         bool cs = false;                     // credible sets of the selected signals (k_cs.hip); needs slct_K
+        int susie_L = 0;                     // multi-causal fine-mapping (k_susie.hip): effects; 0: not asked
+        bool susie_am = false;               // ... and its result section holds alpha and mu (out_susie_alpha / out_susie_mu ask)
         int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
         std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
         bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
         int miss_n = 0;                      // set mask bits
         std::vector<int> miss_tab;           // Prob::miss_tab (MissTab, gauss_internal.h); empty: no mask
         RiderOuts out;
-        bool needs_fused() const { return loo || traits_T > 0; }      // it reads the rows of L^-1 that only the fused solve forms
+        bool needs_fused() const { return loo || traits_T > 0 || susie_L > 0; }      // it reads the rows of L^-1 that only the fused solve forms
     } rd;
-    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs); }
+    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs, rd.susie_L, rd.susie_am); }
     size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
@@ -347,6 +352,9 @@ struct gauss_job {
     int cond_max_U = 0;                                    // ... and the most unmeasured SNPs one of them has
     int* d_csmap = nullptr;     int n_cs = 0;              // credible sets: the windows that asked
     int cs_max_T = 0;                                      // ... and the most candidates (M + U) one of them has
+    int* d_susiemap = nullptr;  int n_susie = 0;           // multi-causal fine-mapping: the windows that asked
+    int susie_max_M = 0, susie_max_U = 0, susie_max_T = 0; // ... the largest M, U (of those that fit unmeasured candidates) and M + U among them,
+    int susie_max_L = 0, susie_max_sweeps = 0, susie_max_nblk = 0;      // the most effects, sweeps and 64-row blocks of X
     int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
     int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
     int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some
@@ -467,6 +475,8 @@ struct WinSpec {
     double slct_chi2_stop = 0.0, slct_min_var_frac = 0.0;
     double cond_min_var_frac = 0.0;          // guard of the imputed SNPs conditioned on the selection (out.cond_z / out.cond_var ask)
     double cs_coverage = 0.0, cs_prior_var = 0.0;      // credible sets of the selected signals (an out.cs_* asks)
+    int susie_L = 0, susie_max_sweeps = 0, susie_estimate_var = 0, susie_measured_only = 0;      // multi-causal fine-mapping (gauss_window_desc.susie_*)
+    double susie_coverage = 0.0, susie_prior_var = 0.0, susie_tol = 0.0, susie_min_abs_corr = 0.0;
     const int32_t* slct_forced = nullptr;
     int n_slct_forced = 0;
     // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample

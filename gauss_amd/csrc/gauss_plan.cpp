@@ -120,6 +120,24 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         return fail(GAUSS_E_INVALID, "cs_coverage = %g: the coverage of a credible set lies in (0, 1]", w.cs_coverage);
     if (cs && !(w.cs_prior_var > 0.0 && std::isfinite(w.cs_prior_var)))
         return fail(GAUSS_E_INVALID, "cs_prior_var = %g: the prior variance of the causal SNP's non-centrality is positive and finite", w.cs_prior_var);
+    // multi-causal fine-mapping (k_susie.hip)
+    const bool susie = w.susie_L != 0;
+    if (susie && !imputes)
+        return fail(GAUSS_E_INVALID, "multi-causal fine-mapping (susie_L) is for imputation windows only (%s window)", not_imputing);
+    if (susie && (w.susie_L < 1 || w.susie_L > SUSIE_L))
+        return fail(GAUSS_E_INVALID, "susie_L = %d: multi-causal fine-mapping takes 1 .. %d effects", w.susie_L, SUSIE_L);
+    if (susie && !(w.susie_coverage > 0.0 && w.susie_coverage <= 1.0))
+        return fail(GAUSS_E_INVALID, "susie_coverage = %g: the coverage of a credible set lies in (0, 1]", w.susie_coverage);
+    if (susie && !(w.susie_prior_var > 0.0 && std::isfinite(w.susie_prior_var)))
+        return fail(GAUSS_E_INVALID, "susie_prior_var = %g: the prior variance of an effect is positive and finite", w.susie_prior_var);
+    if (susie && !(w.susie_tol >= 0.0 && std::isfinite(w.susie_tol)))
+        return fail(GAUSS_E_INVALID, "susie_tol = %g: the stopping tolerance is finite and not negative", w.susie_tol);
+    // (every run queues max_sweeps x L x 2 launches up front: the cap bounds what one window can put on the queue)
+    if (susie && (w.susie_max_sweeps < 1 || w.susie_max_sweeps > SUSIE_MAX_SWEEPS))
+        return fail(GAUSS_E_INVALID, "susie_max_sweeps = %d: the fit takes 1 .. %d sweeps", w.susie_max_sweeps, SUSIE_MAX_SWEEPS);
+    if (susie && !(w.susie_min_abs_corr >= 0.0 && w.susie_min_abs_corr <= 1.0))
+        return fail(GAUSS_E_INVALID, "susie_min_abs_corr = %g: the purity threshold lies in [0, 1]", w.susie_min_abs_corr);
+    // (an imputation window without unmeasured SNPs never gets here: gauss_job_create refuses it)
     // further traits (k_traits.hip)
     if (w.n_traits_more < 0 || w.n_traits_more > TRAITS_MAX)
         return fail(GAUSS_E_INVALID, "n_traits_more = %d: a window takes 0 .. %d further traits", w.n_traits_more, TRAITS_MAX);
@@ -393,6 +411,14 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
     rd.cs = cs;
     p.cs_coverage = cs ? w.cs_coverage : 0.0;
     p.cs_prior_var = cs ? w.cs_prior_var : 0.0;
+    if (susie) {
+        rd.susie_L = w.susie_L;
+        rd.susie_am = w.out.susie_alpha || w.out.susie_mu;
+        p.susie_L = w.susie_L; p.susie_max_sweeps = w.susie_max_sweeps; p.susie_am = rd.susie_am ? 1 : 0;
+        p.susie_estimate_var = w.susie_estimate_var ? 1 : 0; p.susie_measured_only = w.susie_measured_only ? 1 : 0;
+        p.susie_coverage = w.susie_coverage; p.susie_prior_var = w.susie_prior_var; p.susie_tol = w.susie_tol;
+        p.susie_min_abs_corr = w.susie_min_abs_corr;
+    }
     rd.traits_T = w.n_traits_more;
     if (w.n_traits_more > 0) {
         // SNP-major and padded to the kernels' tiles: row g = the T traits' Z-scores at measured SNP g
@@ -630,7 +656,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<ItemH> items;
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
     std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
-    std::vector<int> slctmap, condmap, csmap;
+    std::vector<int> slctmap, condmap, csmap, susiemap;
     std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
     job->max_nblk = 0;
     {
@@ -704,6 +730,12 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (rd.slct_K) slctmap.push_back(i);
         if (rd.cond) { condmap.push_back(i); job->cond_max_U = std::max(job->cond_max_U, p.U); }
         if (rd.cs) { csmap.push_back(i); job->cs_max_T = std::max(job->cs_max_T, p.M + p.U); }
+        if (rd.susie_L) {
+            susiemap.push_back(i);
+            job->susie_max_M = std::max(job->susie_max_M, p.M); job->susie_max_T = std::max(job->susie_max_T, p.M + p.U);
+            job->susie_max_L = std::max(job->susie_max_L, rd.susie_L); job->susie_max_sweeps = std::max(job->susie_max_sweeps, p.susie_max_sweeps);
+            if (!p.susie_measured_only) { job->susie_max_U = std::max(job->susie_max_U, p.U); job->susie_max_nblk = std::max(job->susie_max_nblk, p.nblk); }
+        }
         if (rd.traits_T) {
             for (int b = 0; b < p.nblk; b++) traitsmap.push_back(make_int2(i, b));
             for (int us = 0; us < (p.U + NB - 1) / NB; us++) traitsumap.push_back(make_int2(i, us));
@@ -919,6 +951,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     const size_t o_slctmap = slctmap.empty() ? 0 : put(blob, ta, slctmap);      // (a job in which nobody asks takes nothing)
     const size_t o_condmap = condmap.empty() ? 0 : put(blob, ta, condmap);
     const size_t o_csmap = csmap.empty() ? 0 : put(blob, ta, csmap);
+    const size_t o_susiemap = susiemap.empty() ? 0 : put(blob, ta, susiemap);
     const size_t o_traitsmap = traitsmap.empty() ? 0 : put(blob, ta, traitsmap);
     const size_t o_traitsumap = traitsumap.empty() ? 0 : put(blob, ta, traitsumap);
     const size_t o_missmap = missmap.empty() ? 0 : put(blob, ta, missmap);
@@ -938,6 +971,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n_slct = (int)slctmap.size();
     job->n_cond = (int)condmap.size();
     job->n_cs = (int)csmap.size();
+    job->n_susie = (int)susiemap.size();
     job->n_traits = (int)traitsmap.size();
     job->n_traits_u = (int)traitsumap.size();
     job->n_miss_blk = (int)missmap.size();
@@ -947,7 +981,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     // ---- workspace arena ----
     Arena wa;         // zeroed once per job: operand padding, B21 padding and the solve matrices rely on it
     Arena wslab;      // partial slabs: every entry a reader keeps is written by the Gram kernel first, so no zeroing
-    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct, cs_lbf, cs_mem, ty, tg, mye, mae, myu, mld; long long ldraw; };
+    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct, cs_lbf, cs_mem, susie_ws, susie_mem, ty, tg, mye, mae, myu, mld; long long ldraw; };
     std::vector<WsOff> wo(job->n);
     size_t res = 0;
     {
@@ -1007,6 +1041,11 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (pl.rd.cs) {                     // the candidates' log Bayes factors / pips per signal, and their membership bytes
             w.cs_lbf = wa.take((size_t)pl.rd.slct_K * cs_tld(p.M + p.U) * sizeof(double));
             w.cs_mem = wa.take((size_t)pl.rd.slct_K * cs_tld(p.M + p.U));
+        }
+        w.susie_ws = w.susie_mem = 0;
+        if (pl.rd.susie_L) {                // W, the fit's state and the sets' membership bytes
+            w.susie_ws = wa.take(susie_ws(p.M, p.U, p.Mld, pl.rd.susie_L, !p.susie_measured_only).count * sizeof(double));
+            w.susie_mem = wa.take((size_t)pl.rd.susie_L * cs_tld(p.M + p.U));
         }
         w.ty = w.tg = 0;
         if (pl.rd.traits_T) {               // Y = X Z and G = X^T Y of the further traits
@@ -1172,6 +1211,9 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.out_cs = pl.rd.cs ? out + lay.cs : nullptr;
         p.cs_lbf = pl.rd.cs ? (double*)(W + w.cs_lbf) : nullptr;
         p.cs_mem = pl.rd.cs ? (uint8_t*)(W + w.cs_mem) : nullptr;
+        p.out_susie = pl.rd.susie_L ? out + lay.susie : nullptr;
+        p.susie_ws = pl.rd.susie_L ? (double*)(W + w.susie_ws) : nullptr;
+        p.susie_mem = pl.rd.susie_L ? (uint8_t*)(W + w.susie_mem) : nullptr;
         p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;
         p.traits_Z = pl.rd.traits_T ? (const double*)(T + to[i].tz) : nullptr;
         p.traits_Y = pl.rd.traits_T ? (double*)(W + w.ty) : nullptr;
@@ -1320,6 +1362,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->d_slctmap = (int*)(job->d_tab + o_slctmap);
     job->d_condmap = (int*)(job->d_tab + o_condmap);
     job->d_csmap = (int*)(job->d_tab + o_csmap);
+    job->d_susiemap = (int*)(job->d_tab + o_susiemap);
     job->d_traitsmap = (int2*)(job->d_tab + o_traitsmap);
     job->d_traitsumap = (int2*)(job->d_tab + o_traitsumap);
     job->d_missmap = (int2*)(job->d_tab + o_missmap);

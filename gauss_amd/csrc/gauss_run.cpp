@@ -85,7 +85,8 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 }
 
 // The tail of a fused solve, in the one order its inputs allow:
-//     loo -> selection -> traits weights -> miss solve -> closing step -> traits impute -> miss apply -> conditional -> credible sets
+//     loo -> selection -> traits weights -> miss solve -> fine-mapping weights -> closing step -> traits impute -> miss apply
+//         -> conditional -> credible sets -> multi-causal fit
 //   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
 //     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
 //   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
@@ -95,7 +96,9 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 //   - the imputed SNPs conditioned on the selection (k_cond.hip): z and info of the closing step, the selection's W, indices and
 //     zin, and B21, which everything in front of it only reads;
 //   - the credible sets of the selected signals (k_cs.hip): what the conditional step reads, and the selection's joint z and B11's
-//     diagonal in A[0]; they write a workspace and a result section of their own.
+//     diagonal in A[0]; they write a workspace and a result section of their own;
+//   - the multi-causal fit (k_susie.hip): its weights W = X^T (X B12) read the rows of X like the traits weights, and B21, which is
+//     complete where the tail starts; the fit itself reads z and info of the closing step, B11 in A[0] and B21.
 // The closing step of a run is the product B21 [X | y] with its finish kernel.  A launch for which no window asked is skipped by its
 // launcher.  The clamp path (job_clamp_window) keeps the same order with its single-window map and the stand-alone solve as its
 // closing step; its selection runs in front of the re-factorisation.
@@ -105,11 +108,13 @@ static void queue_tail(gauss_job* job, hipStream_t st)
     launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
     launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
     launch_traits_miss_solve(job->d_probs, job->d_missmap, job->n_miss_blk, job->d_misstmap, job->n_miss_t, st);
+    launch_susie_w(job->d_probs, job->d_susiemap, job->n_susie, job->susie_max_nblk, job->susie_max_U, st);
     launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
     launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
     launch_traits_miss_apply(job->d_probs, job->d_missumap, job->n_miss_u, st);
     launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);
     launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
+    launch_susie(job->d_probs, job->d_susiemap, job->n_susie, job->susie_max_M, job->susie_max_T, job->susie_max_L, job->susie_max_sweeps, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -469,7 +474,8 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     // a window that rides on the rows of L^-1: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this factorisation
     // as they do in a run's (same L either way), and the stand-alone solve below is this tail's closing step (queue_tail): it
     // takes V as its scratch, only reads B21 and leaves the info the further traits are divided by
-    const bool loo = pl.rd.loo, traits = pl.rd.traits_T > 0, miss = pl.rd.miss, ride = pl.rd.needs_fused();
+    // (the multi-causal fit does not ride here: a repaired window is not fitted, job_fetch fills its section)
+    const bool loo = pl.rd.loo, traits = pl.rd.traits_T > 0, miss = pl.rd.miss, ride = loo || traits;
     for (int s = 0; s < p.nblk; s++) {
         // launch over all problems would redo the others; use a single-problem launch instead
         launch_factor_step(job->d_probs + i, 1, s, p.nblk, ride ? p.npi : 0, ride ? job->solve_split : 0, 0, st);
@@ -705,6 +711,17 @@ int job_fetch(gauss_job* job)
                     for (int c = 0; c < p.M + p.U; c++) res[lay.cs + cl.set + c] = -1.0;
                 }
             }
+            if (rd.susie_L && (clamped || (bits & GAUSS_ST_NONFINITE))) {
+                // not fitted: NaN, size 0, kept 0, set -1, no sweep.  A repaired B11 (MakePosDef) is no ground for the fit, and the
+                // clamp path's stand-alone solve forms no rows of the inverse
+                const SusieLayout ql = susie_layout(p.M + p.U, rd.susie_L, rd.susie_am);
+                double* const sq = res + lay.susie;
+                for (size_t u = 0; u < ql.count; u++) sq[u] = NAN;
+                for (int l = 0; l < rd.susie_L; l++) sq[ql.size + l] = sq[ql.kept + l] = 0.0;
+                for (int c = 0; c < p.M + p.U; c++) sq[ql.set + c] = -1.0;
+                sq[ql.fit] = sq[ql.fit + 2] = 0.0;
+                if (!(bits & GAUSS_ST_NONFINITE)) bits |= GAUSS_ST_SUSIE_NOFIT;
+            }
             auto copy_out = [](double* dst, const double* src, size_t n) { if (dst) memcpy(dst, src, sizeof(double) * n); };
             copy_out(pl.out_z, res + lay.z, p.U);
             copy_out(pl.out_info, res + lay.info, p.U);
@@ -743,6 +760,23 @@ int job_fetch(gauss_job* job)
                 copy_out(rd.out.cs_pip, cs + cl.pip, T);
                 if (rd.out.cs_set) for (int c = 0; c < T; c++) rd.out.cs_set[c] = (int32_t)cs[cl.set + c];
                 copy_out(rd.out.cs_set_pip, cs + cl.set_pip, T);
+            }
+            if (rd.susie_L) {                      // the multi-causal fit (k_susie.hip)
+                const int L = rd.susie_L, T = p.M + p.U;
+                const SusieLayout ql = susie_layout(T, L, rd.susie_am);
+                const double* const sq = res + lay.susie;
+                if (sq[ql.fit + 2] != 0.0) bits |= GAUSS_ST_SUSIE_NOCONV;
+                copy_out(rd.out.susie_V, sq + ql.V, L);
+                copy_out(rd.out.susie_lse, sq + ql.lse, L);
+                copy_out(rd.out.susie_mass, sq + ql.mass, L);
+                copy_out(rd.out.susie_purity, sq + ql.purity, L);
+                if (rd.out.susie_size) for (int l = 0; l < L; l++) rd.out.susie_size[l] = (int32_t)sq[ql.size + l];
+                if (rd.out.susie_kept) for (int l = 0; l < L; l++) rd.out.susie_kept[l] = (int32_t)sq[ql.kept + l];
+                copy_out(rd.out.susie_pip, sq + ql.pip, T);
+                if (rd.out.susie_set) for (int c = 0; c < T; c++) rd.out.susie_set[c] = (int32_t)sq[ql.set + c];
+                copy_out(rd.out.susie_set_pip, sq + ql.set_pip, T);
+                if (rd.susie_am) { copy_out(rd.out.susie_alpha, sq + ql.alpha, (size_t)L * T); copy_out(rd.out.susie_mu, sq + ql.mu, (size_t)L * T); }
+                copy_out(rd.out.susie_sweeps, sq + ql.fit, 2);
             }
             if (pl.out_b11 && (!exporting || clamped))
                 { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }

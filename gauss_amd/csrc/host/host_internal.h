@@ -548,6 +548,13 @@ int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vec
 int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
               int n_sel, const int32_t* idx, const double* pip, const int32_t* set, const double* set_pip,
               const int32_t* size, const double* mass, const double* lse);
+// dist_susie / distmix_susie: the call's own table `t` with the wings' measured SNPs appended (cond_output's rows) and the columns wing
+// pip cs cs_pip added -- cs = the 1-based effect of the kept set that holds the SNP, 0 for none -- the named matrices `effects` [L x 7]
+// (table row of the SNP of largest alpha from 0, V, lse, size, mass, purity, kept) and `fit` [1 x 3] (sweeps, delta, converged), and a
+// message when the sweeps ran out or the window was not fitted.  pip / set / set_pip / alpha [L][T] are indexed by candidate
+int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                 int L, double tol, const double* pip, const int32_t* set, const double* set_pip, const double* alpha, const double* V,
+                 const double* lse, const int32_t* size, const double* mass, const double* purity, const int32_t* kept, const double* sweeps);
 // dist_traits / distmix_traits: the Z-scores of one further trait at the n measured SNPs of a window.  SNP i is at(i) -- position and
 // alleles in the window's (the panel's) orientation -- and is looked up in the study `gw` (read from `path`, named in the messages)
 // by (chr, bp, a1, a2): the same allele order gives z, the swapped order -z (gauss.cpp:358-370); of several rows that match, the
@@ -629,6 +636,23 @@ struct CsRider : SlctRider {
         : SlctRider(p_cutoff_, collin_, max_signals_, cond_, n_cond_, true), coverage(coverage_), prior_var(prior_var_) {}
     std::vector<double> pip, set_pip, mass, lse;
     std::vector<int32_t> set, size;
+    int ask(gauss_window_desc& d, const WindowView& v) override;
+    int table(const WindowView& v, gauss_table** out) override;
+};
+// dist_susie / distmix_susie: the susie_* fields of gauss_window_desc; the table is the call's own with every measured SNP of the
+// extended window listed (susie_output).  Independent of the selection
+struct SusieRider : Rider {
+    int L, max_sweeps, estimate_prior_var, measured_only;              // the call's own arguments; <= 0 or NaN: the defaults (ask)
+    double coverage, prior_var, min_abs_corr, tol;
+    SusieRider(int L_, double coverage_, double prior_var_, double min_abs_corr_, int max_sweeps_, double tol_, int estimate_prior_var_,
+               int measured_only_)
+        : L(L_), max_sweeps(max_sweeps_), estimate_prior_var(estimate_prior_var_), measured_only(measured_only_), coverage(coverage_),
+          prior_var(prior_var_), min_abs_corr(min_abs_corr_), tol(tol_) {}
+    int n_eff = 0;
+    double tol_used = 0.0;
+    std::vector<double> pip, set_pip, alpha, V, lse, mass, purity, sweeps;
+    std::vector<int32_t> set, size, kept;
+    int check() override;
     int ask(gauss_window_desc& d, const WindowView& v) override;
     int table(const WindowView& v, gauss_table** out) override;
 };

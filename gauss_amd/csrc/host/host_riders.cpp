@@ -98,6 +98,47 @@ int CsRider::table(const WindowView& v, gauss_table** out)
     return 0;
 }
 
+// ---- susie ----
+int SusieRider::check()
+{
+    if (L > GAUSS_SUSIE_MAX_L) return herr("L = %d: the multi-causal fit takes at most %d effects", L, GAUSS_SUSIE_MAX_L);
+    return 0;
+}
+
+int SusieRider::ask(gauss_window_desc& d, const WindowView&)
+{
+    n_eff = L > 0 ? L : 10;
+    const size_t T = (size_t)std::max(d.n_measured + d.n_unmeasured, 1), K = (size_t)n_eff;
+    pip.assign(T, NAN); set_pip = pip; set.assign(T, -1); alpha.assign(K * T, NAN);
+    V.assign(K, NAN); lse = V; mass = V; purity = V; size.assign(K, 0); kept = size; sweeps.assign(2, NAN); sweeps[0] = 0.0;
+    tol_used = tol < 0 ? 0.0 : (tol > 0 ? tol : 1e-4);                 // negative: exactly max_sweeps sweeps; 0 or NaN: the default
+    d.susie_L = n_eff;
+    d.susie_coverage = coverage > 0 ? coverage : 0.95;                 // (a NaN compares false: the default)
+    d.susie_prior_var = prior_var > 0 ? prior_var : 25.0;              // a prior s.d. of 5 on an effect, in z units: this project's default, as for *_cs
+    d.susie_min_abs_corr = min_abs_corr > 0 ? min_abs_corr : 0.5;
+    d.susie_max_sweeps = max_sweeps > 0 ? max_sweeps : 100;
+    d.susie_tol = tol_used;
+    d.susie_estimate_var = estimate_prior_var < 0 ? 1 : (estimate_prior_var ? 1 : 0);      // negative: the default, on
+    d.susie_measured_only = measured_only > 0 ? 1 : 0;
+    d.out_susie_pip = pip.data(); d.out_susie_set = set.data(); d.out_susie_set_pip = set_pip.data(); d.out_susie_alpha = alpha.data();
+    d.out_susie_V = V.data(); d.out_susie_lse = lse.data(); d.out_susie_mass = mass.data(); d.out_susie_purity = purity.data();
+    d.out_susie_size = size.data(); d.out_susie_kept = kept.data(); d.out_susie_sweeps = sweeps.data();
+    return 0;
+}
+
+int SusieRider::table(const WindowView& v, gauss_table** out)
+{
+    if (v.plain(out)) return -1;
+    std::vector<SlctRow> rows;
+    for (const ViewSnp& s : v.measured) rows.push_back(SlctRow{s.id, s.af, s.z, s.wing});
+    if (susie_output(**out, rows, v.row_m, v.row_u, n_eff, tol_used, pip.data(), set.data(), set_pip.data(), alpha.data(), V.data(), lse.data(),
+                     size.data(), mass.data(), purity.data(), kept.data(), sweeps.data())) {
+        gauss_table_free(*out); *out = nullptr;
+        return -1;
+    }
+    return 0;
+}
+
 // ---- traits, traits_miss ----
 int TraitsRider::check()
 {

@@ -267,17 +267,18 @@ gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, 
 // row the statistics conditioned on the selected SNPs and order 0.  z_entry / z_joint of the n selected SNPs go to the named
 // matrix `signals` [n x 3]: table row (from 0), z_entry, z_joint, in order of entry.  Returns 0, or -1 with the message set when `t`
 // holds a column this function does not know how to fill for a wing row (`t` is then left as it came).
-int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
-                 int n_sel, const int32_t* idx, const double* zin, const double* joint, const double* zc, const double* var_left,
-                 const double* cond_z, const double* cond_var)
+// The measured SNPs the call's own table does not list (the wings': row_m < 0) appended to it in matrix order, so that every measured SNP
+// has a row: `at` = table row of measured SNP i, `nrow` = rows afterwards.  `room` further columns must still fit.  -1: message set
+static int append_wing_rows(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, size_t room, const char* who,
+                            std::vector<int32_t>& at, size_t& nrow)
 {
     static const char* const known[] = {"rsid", "chr", "bp", "a1", "a2", "af1ref", "af1mix", "z", "pval", "info", "type"};
     for (const Column& c : t.cols)
         if (std::none_of(std::begin(known), std::end(known), [&](const char* k) { return c.name == k; }))
-            return herr("cond_output: no value for column '%s' in the rows of the wings", c.name.c_str());
-    if (t.cols.size() + 5 > (size_t)gauss_table::MAX_COLS) return herr("cond_output: %zu columns leave no room for five more", t.cols.size());
-    size_t nrow = (size_t)t.nrow();
-    std::vector<int32_t> at(row_m);                                   // table row of measured SNP i, the appended ones included
+            return herr("%s: no value for column '%s' in the rows of the wings", who, c.name.c_str());
+    if (t.cols.size() + room > (size_t)gauss_table::MAX_COLS) return herr("%s: %zu columns leave no room for %zu more", who, t.cols.size(), room);
+    nrow = (size_t)t.nrow();
+    at = row_m;                                                       // table row of measured SNP i, the appended ones included
     for (size_t i = 0; i < rows.size(); i++) {
         if (at[i] >= 0) continue;
         at[i] = (int32_t)nrow++;
@@ -295,6 +296,16 @@ int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vec
             else c.d.push_back(r.af);                                 // af1ref | af1mix: the names were checked above
         }
     }
+    return 0;
+}
+
+int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                 int n_sel, const int32_t* idx, const double* zin, const double* joint, const double* zc, const double* var_left,
+                 const double* cond_z, const double* cond_var)
+{
+    std::vector<int32_t> at;
+    size_t nrow = 0;
+    if (append_wing_rows(t, rows, row_m, 5, "cond_output", at, nrow)) return -1;
     Column &wing = t.add("wing", GAUSS_COL_INT), &order = t.add("order", GAUSS_COL_INT), &zcond = t.add("z_cond", GAUSS_COL_DBL);
     Column &pval = t.add("pval_cond", GAUSS_COL_DBL), &vl = t.add("var_left", GAUSS_COL_DBL);
     wing.i.assign(nrow, 0); order.i.assign(nrow, 0);
@@ -349,6 +360,50 @@ int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vecto
         sets[2 * (size_t)n_sel + a] = mass[a]; sets[3 * (size_t)n_sel + a] = lse[a];
     }
     t.put_named("sets", n_sel, 4, std::move(sets));
+    return 0;
+}
+
+// dist_susie / distmix_susie: `t` is the call's own table.  The wings' measured SNPs are appended as cond_output appends them; adds
+// wing, pip, cs (1-based effect of the kept set that holds the SNP, 0: none) and cs_pip, the named matrices `effects` [L x 7] (table row
+// of the SNP of largest alpha, V, lse, size, mass, purity, kept) and `fit` [1 x 3] (sweeps, delta, converged), and a message when the
+// sweeps ran out or the window was not fitted
+int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                 int L, double tol, const double* pip, const int32_t* set, const double* set_pip, const double* alpha, const double* V,
+                 const double* lse, const int32_t* size, const double* mass, const double* purity, const int32_t* kept, const double* sweeps)
+{
+    std::vector<int32_t> at;
+    size_t nrow = 0;
+    if (append_wing_rows(t, rows, row_m, 4, "susie_output", at, nrow)) return -1;
+    const size_t M = rows.size(), T = M + row_u.size();
+    Column &wing = t.add("wing", GAUSS_COL_INT), &p = t.add("pip", GAUSS_COL_DBL), &cs = t.add("cs", GAUSS_COL_INT), &cp = t.add("cs_pip", GAUSS_COL_DBL);
+    wing.i.assign(nrow, 0); p.d.assign(nrow, NAN); cs.i.assign(nrow, 0); cp.d.assign(nrow, NAN);
+    std::vector<int32_t> row_of(T, -1);                               // table row of candidate c
+    for (size_t i = 0; i < M; i++) { row_of[i] = at[i]; wing.i[(size_t)at[i]] = rows[i].wing; }
+    for (size_t u = 0; u < row_u.size(); u++) row_of[M + u] = row_u[u];
+    for (size_t c = 0; c < T; c++) {
+        if (row_of[c] < 0) continue;
+        const size_t r = (size_t)row_of[c];
+        p.d[r] = pip[c]; cs.i[r] = set[c] + 1; cp.d[r] = set_pip[c];
+    }
+    const bool fitted = sweeps[0] > 0;
+    std::vector<double> eff((size_t)L * 7);
+    for (int l = 0; l < L; l++) {
+        int32_t lead = -1;
+        if (fitted) {
+            size_t best = 0;
+            for (size_t c = 1; c < T; c++) if (alpha[(size_t)l * T + c] > alpha[(size_t)l * T + best]) best = c;
+            lead = row_of[best];
+        }
+        const double vals[7] = {(double)lead, V[l], lse[l], (double)size[l], mass[l], purity[l], (double)kept[l]};
+        for (int k = 0; k < 7; k++) eff[(size_t)k * L + l] = vals[k];
+    }
+    t.put_named("effects", L, 7, std::move(eff));
+    // tol = 0 (the caller asked for exactly max_sweeps sweeps with a negative tol): delta < 0 never holds, so `converged` is 0, and
+    // running the sweeps out is what was asked for: no message
+    const bool converged = fitted && sweeps[1] < tol;
+    t.put_named("fit", 1, 3, std::vector<double>{sweeps[0], sweeps[1], converged ? 1.0 : 0.0});
+    if (!fitted) t.messages.push_back("susie: the window was not fitted (its B11 is not finite, or MakePosDef repaired it): pip, cs and cs_pip are empty");
+    else if (!converged && tol > 0) t.messages.push_back("susie: the sweeps ran out before the fit converged (max_sweeps); the values are those of the last sweep");
     return 0;
 }
 

@@ -31,12 +31,11 @@
 // No atomics, every sum in a fixed order: the bits do not depend on the run or on the launch form.  Compiled with
 // -ffp-contract=off like the other fp64 tails.
 #include "gauss_internal.h"
+#include "k_cs_common.h"      // the membership step of one row, shared with k_susie.hip
 
 namespace gauss {
 
 constexpr int CS_LP = SLCT_K + 1;            // row pitch of L and X in LDS
-constexpr int CS_LDS_T = 4096;               // a row of up to this many pips sits in LDS: 32 KB
-constexpr int CS_SET_NW = CS_SET_T / 64;
 static_assert(SLCT_K <= CS_T && SLCT_K <= 64, "one lane per selected SNP");
 
 // n and the indices are the selection's own; whatever a run that is being replaced may have left there, nothing is indexed outside
@@ -154,23 +153,6 @@ __global__ __launch_bounds__(CS_T) void cs_lbf_kernel(const Prob* __restrict__ p
     }
 }
 
-// the order of the max: a NaN is never better
-__device__ __forceinline__ double cs_max(double a, double b) { return b > a ? b : a; }
-
-// sum over the workgroup in a fixed order: the lanes of a wave by xor moves, then the waves ascending
-__device__ __forceinline__ double cs_block_sum(double x, double* s_red, int tid)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    __syncthreads();                                        // (s_red may still be read from the reduction before)
-    if ((tid & 63) == 0) s_red[tid >> 6] = x;
-    __syncthreads();
-    double t = s_red[0];
-#pragma unroll
-    for (int w = 1; w < CS_SET_NW; w++) t += s_red[w];
-    return t;
-}
-
 __global__ __launch_bounds__(CS_SET_T) void cs_set_kernel(const Prob* __restrict__ probs, const int* __restrict__ csmap)
 {
     __shared__ double s_row[CS_LDS_T], s_red[CS_SET_NW];
@@ -188,45 +170,8 @@ __global__ __launch_bounds__(CS_SET_T) void cs_set_kernel(const Prob* __restrict
     const size_t tld = (size_t)cs_tld(T);
     double* const g_row = pb.cs_lbf + (size_t)a * tld;
     uint8_t* const mem = pb.cs_mem + (size_t)a * tld;
-    const bool in_lds = T <= CS_LDS_T;
-    double* const row = in_lds ? s_row : g_row;
-    // the row's max (sel[a] is always a candidate: it is finite unless a NaN has come in), then lse
-    double mx = -__builtin_inf();
-    for (int i = tid; i < T; i += CS_SET_T) mx = cs_max(mx, g_row[i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = cs_max(mx, __shfl_xor(mx, off, 64));
-    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-    __syncthreads();
-    mx = s_red[0];
-#pragma unroll
-    for (int w = 1; w < CS_SET_NW; w++) mx = cs_max(mx, s_red[w]);
-    double sum = 0.0;
-    for (int i = tid; i < T; i += CS_SET_T) sum += exp(g_row[i] - mx);
-    sum = cs_block_sum(sum, s_red, tid);
-    const double lse = mx + log(sum);
-    // pip in place: a thread rewrites the entries it alone has read
-    for (int i = tid; i < T; i += CS_SET_T) {
-        const double p = exp(g_row[i] - lse);
-        g_row[i] = p;
-        if (in_lds) s_row[i] = p;
-    }
-    __syncthreads();                                        // (workgroup scope covers the global row too: this workgroup alone reads it)
-    // membership: the mass ranked ahead of i, j ascending; every lane reads the same row[j] at a time
-    const double rho = pb.cs_coverage;
-    double mass = 0.0, size = 0.0;
-    for (int i = tid; i < T; i += CS_SET_T) {
-        const double p = row[i];
-        double ahead = 0.0;
-        for (int j = 0; j < T; j++) {
-            const double q = row[j];
-            if (q > p || (q == p && j < i)) ahead += q;
-        }
-        const bool in = p > 0.0 && (ahead < rho || rho >= 1.0);      // (rho = 1: the rounded mass ahead may reach 1, the exact one cannot)
-        mem[i] = in ? 1 : 0;
-        if (in) { mass += p; size += 1.0; }
-    }
-    mass = cs_block_sum(mass, s_red, tid);
-    size = cs_block_sum(size, s_red, tid);
+    double size, mass, lse;
+    cs_set_row(g_row, mem, T, pb.cs_coverage, s_row, s_red, tid, size, mass, lse);
     if (tid == 0) { out[o.size + a] = size; out[o.mass + a] = mass; out[o.lse + a] = lse; }
 }
 

@@ -272,7 +272,8 @@ class _Win:
     """Keeps the numpy buffers of one window alive next to its C descriptor."""
 
     def __init__(self, desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig,
-                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None, z_more=None, miss_more=None):
+                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None, z_more=None, miss_more=None,
+                 susie=None):
         self.po, self.w = _pops(pop_off, pop_wgt)
         self.z1 = np.ascontiguousarray(z1, dtype=np.float64)
         if dev_ptrs is None:
@@ -348,6 +349,28 @@ class _Win:
                 desc.cs_coverage, desc.cs_prior_var = float(cs.get("coverage", 0.95)), float(cs.get("prior_var", 25.0))
                 desc.out_cs_pip, desc.out_cs_set, desc.out_cs_set_pip = s["cs_pip"].ctypes.data_as(_dp), s["cs_set"].ctypes.data_as(_ip), s["cs_set_pip"].ctypes.data_as(_dp)
                 desc.out_cs_size, desc.out_cs_mass, desc.out_cs_lse = s["cs_size"].ctypes.data_as(_ip), s["cs_mass"].ctypes.data_as(_dp), s["cs_lse"].ctypes.data_as(_dp)
+        # multi-causal fine-mapping (susie_* of gauss_window_desc): susie=dict(L=10, coverage=0.95, prior_var=25.0, tol=1e-4,
+        # max_sweeps=100, min_abs_corr=0.5, estimate_var=True, measured_only=False, want_alpha=False)
+        self.susie = None
+        if susie is not None:
+            L, T = int(susie.get("L", 10)), M + U
+            Lc = min(max(L, 0), _lib.SUSIE_MAX_L)
+            q = self.susie = dict(pip=np.full(T, np.nan), set=np.full(T, -1, dtype=np.int32), set_pip=np.full(T, np.nan),
+                                  V=np.full(Lc, np.nan), lse=np.full(Lc, np.nan), mass=np.full(Lc, np.nan), purity=np.full(Lc, np.nan),
+                                  size=np.zeros(Lc, dtype=np.int32), kept=np.zeros(Lc, dtype=np.int32), sweeps=np.full(2, np.nan))
+            desc.susie_L = L
+            desc.susie_coverage, desc.susie_prior_var = float(susie.get("coverage", 0.95)), float(susie.get("prior_var", 25.0))
+            desc.susie_tol, desc.susie_max_sweeps = float(susie.get("tol", 1e-4)), int(susie.get("max_sweeps", 100))
+            desc.susie_min_abs_corr = float(susie.get("min_abs_corr", 0.5))
+            desc.susie_estimate_var = 1 if susie.get("estimate_var", True) else 0
+            desc.susie_measured_only = 1 if susie.get("measured_only", False) else 0
+            for key in ("pip", "set_pip", "V", "lse", "mass", "purity", "sweeps"):
+                setattr(desc, "out_susie_" + key, q[key].ctypes.data_as(_dp))
+            for key in ("set", "size", "kept"):
+                setattr(desc, "out_susie_" + key, q[key].ctypes.data_as(_ip))
+            if susie.get("want_alpha"):
+                q["alpha"], q["mu"] = np.full((Lc, T), np.nan), np.full((Lc, T), np.nan)
+                desc.out_susie_alpha, desc.out_susie_mu = q["alpha"].ctypes.data_as(_dp), q["mu"].ctypes.data_as(_dp)
         # further traits on the same window (n_traits_more / z_more / out_z_more of gauss_window_desc): z_more [T, M] -> [T, U]
         self.z_more = self.out_z_more = None
         if z_more is not None:
@@ -432,11 +455,15 @@ class _Win:
                 out.update(cs_pip=s["cs_pip"], cs_set=s["cs_set"], cs_set_pip=s["cs_set_pip"], cs_size=s["cs_size"][:n].copy(),
                            cs_mass=s["cs_mass"][:n].copy(), cs_lse=s["cs_lse"][:n].copy(),
                            cs_raw=dict(size=s["cs_size"], mass=s["cs_mass"], lse=s["cs_lse"]))
+        if self.susie is not None:
+            q = self.susie
+            out.update({"susie_" + k: v for k, v in q.items() if k != "sweeps"})
+            out.update(susie_sweeps=int(q["sweeps"][0]) if np.isfinite(q["sweeps"][0]) else 0, susie_delta=float(q["sweeps"][1]))
         return out
 
 
 def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_eig=1e-5,
-                  want_mats=False, ctx=None, loo=False, slct=None, z_more=None, miss_more=None):
+                  want_mats=False, ctx=None, loo=False, slct=None, z_more=None, miss_more=None, susie=None):
     """run_dist (mode 0, dist.cpp:129-227) / run_distmix (mode 1, distmix.cpp:138-253).
     loo=True adds loo_z, loo_info, loo_t [M]: every measured SNP re-imputed from the other measured SNPs, and its
     standardised residual (include/gauss_hip.h, out_loo_*).
@@ -450,11 +477,16 @@ def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_e
     and the same factorisation (include/gauss_hip.h, n_traits_more); row t is what z would be with z1 = z_more[t].
     miss_more [T, M] (non-zero: further trait t has no score at measured SNP m; at most 32 per trait, 128 distinct per window) makes row t
     what the window returns for trait t alone with those SNPs unmeasured (include/gauss_hip.h, miss_more) and adds info_more [T, U], the
-    info per trait, and z_miss / info_miss [T, M]: the imputed Z-scores and the info of the SNPs a trait lacks, NaN elsewhere."""
+    info per trait, and z_miss / info_miss [T, M]: the imputed Z-scores and the info of the SNPs a trait lacks, NaN elsewhere.
+    susie=dict(L=10, coverage=0.95, prior_var=25.0, tol=1e-4, max_sweeps=100, min_abs_corr=0.5, estimate_var=True, measured_only=False)
+    adds the multi-causal fine-mapping of the window (include/gauss_hip.h, susie_*): susie_pip / susie_set / susie_set_pip [M + U] per
+    candidate, the measured SNPs first, susie_V / susie_lse / susie_size / susie_mass / susie_purity / susie_kept [L] per effect,
+    susie_sweeps and susie_delta; want_alpha=True in that dict adds susie_alpha / susie_mu [L, M + U].  Status bit 16: the sweeps ran
+    out; bit 32: MakePosDef repaired the window, which is then not fitted."""
     ctx = ctx or default_context()
     desc = WindowDesc()
     win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct, z_more=z_more,
-               miss_more=miss_more)
+               miss_more=miss_more, susie=susie)
     check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
     return win.result()
 
@@ -586,13 +618,14 @@ class Job:
     """A batch of windows sharing every launch (gauss_job_*)."""
 
     def __init__(self, windows, ctx=None, on_device=False, want_mats=False):
-        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more, miss_more])
+        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more, miss_more, susie])
         or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
         loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs).
         slct=dict(max=, chi2_stop=, collin=, forced=[, unmeasured=True][, cs=dict(coverage=, prior_var=)]) in a window's dict: its
         result carries the signal selection (and the imputed SNPs conditioned on it, and the signals' credible sets; impute_window).
         z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window).
-        miss_more=[T, M] beside it: the SNPs each further trait lacks; the result carries info_more, z_miss, info_miss (impute_window)."""
+        miss_more=[T, M] beside it: the SNPs each further trait lacks; the result carries info_more, z_miss, info_miss (impute_window).
+        susie=dict(L=, ...) in a window's dict: its result carries the multi-causal fine-mapping susie_* (impute_window)."""
         self.ctx = ctx or default_context()
         n = len(windows)
         self.descs = (WindowDesc * n)()
@@ -601,7 +634,8 @@ class Job:
             self.wins.append(_Win(self.descs[i], w["mode"], w.get("geno_m"), w.get("geno_u"),
                                   w["pop_off"], w.get("pop_wgt"), w["z1"], w.get("lam", 0.1),
                                   w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed"),
-                                  loo=bool(w.get("loo", False)), slct=w.get("slct"), z_more=w.get("z_more"), miss_more=w.get("miss_more")))
+                                  loo=bool(w.get("loo", False)), slct=w.get("slct"), z_more=w.get("z_more"), miss_more=w.get("miss_more"),
+                                  susie=w.get("susie")))
         h = C.c_void_p()
         check(self.ctx.lib.gauss_job_create(self.ctx.handle, self.descs, n, 1 if on_device else 0,
                                             C.byref(h)))

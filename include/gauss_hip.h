@@ -56,6 +56,8 @@ extern "C" {
 #define GAUSS_ST_NONFINITE  2  /* B11 not finite / not factorisable: outputs are NaN like the reference's */
 #define GAUSS_ST_NOCONV     4  /* gauss_pop_weights: the Jacobi eigen-clamp hit its sweep cap (outputs NaN, NONFINITE set too) */
 #define GAUSS_ST_SLCT_SKIPPED 8 /* signal selection: a forced SNP failed the collinearity guard and was left out */
+#define GAUSS_ST_SUSIE_NOCONV 16 /* multi-causal fit: susie_max_sweeps sweeps ran without delta < susie_tol (values of the last sweep) */
+#define GAUSS_ST_SUSIE_NOFIT  32 /* multi-causal fit: MakePosDef repaired B11 (GAUSS_ST_CLAMPED), the window is not fitted      */
 
 typedef struct gauss_ctx gauss_ctx;
 typedef struct gauss_job gauss_job;
@@ -98,6 +100,74 @@ typedef struct gauss_window_desc {
      * order additive, dominant (0/1/2 -> 0/1/1), recessive (0/1/2 -> 0/0/1); out_b21 is
      * [n_codings * U x M].  Codes outside 0..2 are left unchanged, as in the reference. */
     int u_codings;            /* bit mask of GAUSS_CODE_*                                          */
+    /* ---- multi-causal fine-mapping of the window (GAUSS_WIN_IMPUTE windows only) ----------------------------------
+     * The "sum of single effects" model (SuSiE; on summary statistics SuSiE-RSS, Zou et al. 2022) fitted to the measured z,
+     * with the unmeasured SNPs as candidates beside the measured ones, each with the variance an imputed SNP really has.
+     * Unlike the credible sets of the stepwise selection (out_cs_*) it does not condition on one SNP per signal: a measured
+     * SNP that tags two causal SNPs does not mislead it.  Notation: B = B11 [M x M] (lambda on the diagonal), C = B21 [U x M],
+     * z = z1, A = [B | C^T] [M x T], T = M + U; candidates are indexed as in out_cs_*: measured first, then unmeasured.
+     *   R = A^T B^-1 A [T x T, rank M];  zhat = A^T B^-1 z = [z ; m], m_u = out_z[u] sqrt(out_info[u]) (the conditional mean);
+     *   d_j = R_jj = B_jj (measured), out_info[u] (unmeasured)
+     * Model: z ~ N(A sum_l b_l, B), l = 1 .. L = susie_L; b_l has exactly one non-zero entry, at a candidate drawn uniformly from
+     * the admissible ones, with value ~ N(0, V_l).  Residual variance 1 (z units), fixed.
+     * Admissible: zhat_j finite, d_j finite and > 0; with susie_measured_only no unmeasured SNP; a non-finite value in z1 makes
+     * every unmeasured SNP inadmissible.  An inadmissible candidate has alpha = mu = 0 and enters no sum.
+     * Fit (IBSS, Gauss-Seidel over l, every sum in a fixed order): bbar_l = 0, V_l = omega = susie_prior_var, f = 0.  One sweep,
+     * for l = 1 .. L in order:
+     *   r      = zhat - (f - R bbar_l)
+     *   lbf_j  = ( r_j^2 V_l / (1 + V_l d_j) - log1p(V_l d_j) ) / 2                    (V_l = 0: lbf_j = 0)
+     *   lse_l  = log( (1 / n_adm) sum_j exp(lbf_j) ),   alpha_lj = exp(lbf_j - max) / sum_j exp(lbf_j - max)
+     *   s2_j   = V_l / (1 + V_l d_j),   mu_lj = s2_j r_j
+     *   bbar_l = alpha_l o mu_l;   f = (f - R bbar_l_old) + R bbar_l_new
+     *   susie_estimate_var:  V' = sum_j alpha_lj (mu_lj^2 + s2_j);  V' = 0 if log((1 / n_adm) sum_j exp(lbf_j(V'))) <= 0;
+     *                        V_l = V' from the next sweep on (susieR's "EM"); V_l = 0 is absorbing
+     * After each sweep delta = max_lj |alpha_lj - alpha_lj(previous sweep)|; the fit stops when delta < susie_tol or after
+     * susie_max_sweeps sweeps -- then GAUSS_ST_SUSIE_NOCONV is set and the values are those of the last sweep (susie_tol = 0
+     * runs exactly susie_max_sweeps sweeps).  Nothing T x T is formed: with W = B^-1 C^T = X^T (X C^T) (X = L^-1, the rows the
+     * solve holds), v = bbar_meas + W bbar_unmeas and R bbar = [B v ; C v]: two dependent matrix-vector products per (sweep, l).
+     * Sets and summaries, from the final alpha:
+     *   membership of set l: the rule of out_cs_set on alpha_l: alpha_lj > 0 and the mass ranked ahead (larger alpha; ties: the
+     *     smaller index) below rho = susie_coverage; rho = 1 takes every alpha_lj > 0
+     *   purity_l: the minimum, over the pairs of the min(size, 128) members of largest alpha (ties: the smaller index), of
+     *     |R_ij| / sqrt(d_i d_j), R_ij = B_ij, C_ui or c_u . W_v; one member: 1; no member: NaN.  (susieR subsamples at random;
+     *     this rule is deterministic on purpose.)
+     *   kept_l = V_l > 0 and purity_l >= susie_min_abs_corr and no kept set l' < l has the same members
+     *   per SNP: out_susie_pip = 1 - prod_{l: V_l > 0} (1 - alpha_lj);  out_susie_set = the kept l (0-based) of largest alpha_lj
+     *     among the kept sets that hold it (ties: the smaller l; -1: none);  out_susie_set_pip = that alpha_lj (0: none)
+     *   per effect: V_l (after the last sweep's update), lse_l, size, mass (of the members), purity, kept
+     *   per window: out_susie_sweeps = sweeps run, the last delta
+     * Not fitted: GAUSS_ST_NONFINITE windows return NaN, size 0, kept 0, set -1.  A window that MakePosDef repairs
+     * (GAUSS_ST_CLAMPED) is NOT fitted either -- the same NaN / 0 / -1 and GAUSS_ST_SUSIE_NOFIT; its other outputs keep their
+     * bits: the repaired path forms no rows of the inverse, and eigenvalues at 1e-5 are no ground for some hundred dependent
+     * products.  susie_L = 0: off (a zeroed block asks for nothing).  GAUSS_E_INVALID: QCAT / LD windows that ask; susie_L
+     * outside 1 .. GAUSS_SUSIE_MAX_L; susie_coverage outside (0, 1]; susie_prior_var <= 0; susie_tol < 0; susie_max_sweeps outside
+     * 1 .. GAUSS_SUSIE_MAX_SWEEPS (every run queues susie_max_sweeps x L x 2 launches up front: the cap bounds what one window puts
+     * on the queue); susie_min_abs_corr outside [0, 1]; any of them non-finite.  (A window without unmeasured SNPs is refused
+     * as it is without the fit, with susie_measured_only too.)  No admissible candidate at all (every z1
+     * non-finite): alpha = mu = 0, pip 0, lse NaN, sizes 0, purity NaN, nothing kept; no status bit.  Independent of the selection and of every other rider.  The
+     * kernels (k_susie.hip) are queued behind the credible sets: susie_max_sweeps x L x 2 launches up front, a converged window
+     * leaves its launches at once; fp64, no atomics.  (The block sits in front of the packed-rows block: every later field
+     * keeps its neighbours.) */
+    int      susie_L;             /* effects; 0 = off; at most GAUSS_SUSIE_MAX_L                              */
+    double   susie_coverage;      /* rho in (0, 1]                                                           */
+    double   susie_prior_var;     /* omega > 0: prior variance of an effect, in z units                      */
+    double   susie_tol;           /* >= 0: the fit stops when no alpha moved by this much in a sweep          */
+    double   susie_min_abs_corr;  /* in [0, 1]: purity a kept set needs                                       */
+    double*  out_susie_pip;       /* [M+U] measured first                          host pointer / NULL       */
+    int32_t* out_susie_set;       /* [M+U]                                                     optional      */
+    double*  out_susie_set_pip;   /* [M+U]                                                     optional      */
+    double*  out_susie_V;         /* [L]                                                       optional      */
+    double*  out_susie_lse;       /* [L]                                                       optional      */
+    double*  out_susie_mass;      /* [L]                                                       optional      */
+    double*  out_susie_purity;    /* [L]                                                       optional      */
+    int32_t* out_susie_size;      /* [L]                                                       optional      */
+    int32_t* out_susie_kept;      /* [L]                                                       optional      */
+    double*  out_susie_alpha;     /* [L][M+U]                                                  optional      */
+    double*  out_susie_mu;        /* [L][M+U]                                                  optional      */
+    double*  out_susie_sweeps;    /* [2] sweeps run, the last delta                            optional      */
+    int      susie_max_sweeps;    /* 1 .. GAUSS_SUSIE_MAX_SWEEPS                                             */
+    int      susie_estimate_var;  /* non-zero: V_l is re-estimated every sweep                               */
+    int      susie_measured_only; /* non-zero: only the measured SNPs are candidates                         */
     /* ---- packed panel rows -------------------------------------------------
      * geno_format = GAUSS_GENO_2BIT: a genotype row is a 2-bit stream (sample s of a population block at bits
      * 2*(s%4) of byte s/4, codes 0..2), each selected population's block starting on a 16-byte boundary and
@@ -259,6 +329,8 @@ typedef struct gauss_window_desc {
 } gauss_window_desc;
 
 #define GAUSS_SLCT_MAX 32
+#define GAUSS_SUSIE_MAX_L 32
+#define GAUSS_SUSIE_MAX_SWEEPS 1000
 #define GAUSS_TRAITS_MORE_MAX 63
 #define GAUSS_TRAITS_MISS_MAX 32        /* missing SNPs per further trait and window */
 #define GAUSS_TRAITS_MISS_UNION_MAX 128 /* distinct missing SNPs per window          */

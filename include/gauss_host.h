@@ -231,6 +231,38 @@ int gauss_host_distmix_cs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end
                           const char* reference_data_file, const char* reference_pop_desc_file,
                           double af1_cutoff, double p_cutoff, double collin, int max_signals,
                           const char* const* cond_rsids, int n_cond, double coverage, double prior_var, gauss_table** out);
+/* Multi-causal fine-mapping of the window: the "sum of single effects" model (SuSiE-RSS) fitted to the measured z with the imputed
+ * SNPs as candidates beside the measured ones -- unlike the credible sets above it does not condition on one selected SNP per signal,
+ * so a measured SNP that tags two causal SNPs does not mislead it.  Arguments, window, data layer, single job and refusals of
+ * gauss_host_dist / gauss_host_distmix; the job's window also sets the susie_* fields of gauss_window_desc (include/gauss_hip.h: the
+ * model, the fit, the sets, their purity) with
+ *   L                   effects; <= 0: 10; at most GAUSS_SUSIE_MAX_L
+ *   coverage            rho in (0, 1]; <= 0 or NaN: 0.95
+ *   prior_var           omega > 0, prior variance of an effect in z units; <= 0 or NaN: 25.0 (this project's documented default, as above)
+ *   min_abs_corr        purity a reported set needs; <= 0 or NaN: 0.5
+ *   max_sweeps          <= 0: 100; at most GAUSS_SUSIE_MAX_SWEEPS (the window refuses more)
+ *   tol                 the fit stops when no alpha moved by this much in a sweep; 0 or NaN: 1e-4; negative: exactly max_sweeps sweeps
+ *                       (`fit` then reports converged = 0 whatever delta is, and no message is added: running them out was asked for)
+ *   estimate_prior_var  0: the prior variance stays omega; otherwise (negative: the default) it is re-estimated every sweep
+ *   measured_only       > 0: only the measured SNPs are candidates (plain SuSiE-RSS on z and B11)
+ * Table: the call's own rows (same order, same bits in the shared columns), then the measured SNPs of the wings, so that every
+ * candidate has a row (gauss_host_dist_cond's row set, without its conditional columns).  Appended columns: wing, pip, cs (the 1-based
+ * effect of the kept set that holds the SNP; 0: none) and cs_pip.  Named matrices: `effects` [L x 7]: table row (from 0) of the SNP of
+ * largest alpha, V, lse, size, mass, purity, kept; `fit` [1 x 3]: sweeps, the last delta, converged.  A message is added when the
+ * sweeps ran out (GAUSS_ST_SUSIE_NOCONV) and when the window was not fitted (GAUSS_ST_SUSIE_NOFIT, GAUSS_ST_NONFINITE).
+ * Limits: the candidates are the measured SNPs of the extended window and the unmeasured SNPs of the prediction window; a window that
+ * MakePosDef repairs is not fitted; z units; L <= 32; the residual variance is fixed at 1; uniform prior. */
+int gauss_host_dist_susie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                          const char* study_pop, const char* input_file, const char* reference_index_file,
+                          const char* reference_data_file, const char* reference_pop_desc_file,
+                          double af1_cutoff, int L, double coverage, double prior_var, double min_abs_corr, int max_sweeps,
+                          double tol, int estimate_prior_var, int measured_only, gauss_table** out);
+int gauss_host_distmix_susie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                             const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                             const char* input_file, const char* reference_index_file,
+                             const char* reference_data_file, const char* reference_pop_desc_file,
+                             double af1_cutoff, int L, double coverage, double prior_var, double min_abs_corr, int max_sweeps,
+                             double tol, int estimate_prior_var, int measured_only, gauss_table** out);
 /* The chi^2 (1 df) threshold of a two-sided p-value: the smallest double chi2 with 2 pnorm(-sqrt(chi2)) < p in the library's own
  * normal tail, found by bisection on the bit pattern -- monotone in p, and exact to the last bit that changes the comparison.
  * p must be positive. */
