@@ -30,6 +30,7 @@ ST_SUSIE_NOCONV = 16     # GAUSS_ST_SUSIE_NOCONV
 ST_SUSIE_NOFIT = 32      # GAUSS_ST_SUSIE_NOFIT
 SUSIE_MAX_L = 32         # GAUSS_SUSIE_MAX_L
 SUSIE_MAX_SWEEPS = 1000  # GAUSS_SUSIE_MAX_SWEEPS
+SUSIE_TRAITS_MORE_MAX = 7  # GAUSS_SUSIE_TRAITS_MORE_MAX
 CODE_ADDITIVE, CODE_DOMINANT, CODE_RECESSIVE = 1, 2, 4
 GRAM_F32 = 0
 GRAM_I8 = 1
@@ -47,7 +48,14 @@ class WindowDesc(C.Structure):
         ("lambda_", C.c_double), ("min_abs_eig", C.c_double),
         ("out_z", _dp), ("out_info", _dp), ("out_status", _ip), ("out_b11", _dp), ("out_b21", _dp),
         ("kind", C.c_int), ("n_head_measured", C.c_int), ("n_pred_measured", C.c_int), ("eig_cutoff", C.c_double),
-        ("out_r", _dp), ("out_num_eig", _ip), ("u_codings", C.c_int),
+        ("out_r", _dp), ("out_num_eig", _ip),
+        ("coloc_traits_more", C.c_int), ("coloc_p1", C.c_double), ("coloc_p2", C.c_double), ("coloc_p12", C.c_double),
+        ("out_coloc_lbf", _dp), ("out_coloc_more_pip", _dp), ("out_coloc_more_set", _ip), ("out_coloc_more_set_pip", _dp),
+        ("out_coloc_more_V", _dp), ("out_coloc_more_lse", _dp), ("out_coloc_more_mass", _dp), ("out_coloc_more_purity", _dp),
+        ("out_coloc_more_size", _ip), ("out_coloc_more_kept", _ip), ("out_coloc_more_alpha", _dp), ("out_coloc_more_mu", _dp),
+        ("out_coloc_more_lbf", _dp), ("out_coloc_more_sweeps", _dp), ("out_coloc_more_status", _ip),
+        ("out_coloc_pp", _dp), ("out_coloc_hit", _ip), ("out_coloc_hit_pp", _dp), ("out_coloc_n", _ip),
+        ("u_codings", C.c_int),
         ("susie_L", C.c_int), ("susie_coverage", C.c_double), ("susie_prior_var", C.c_double), ("susie_tol", C.c_double),
         ("susie_min_abs_corr", C.c_double), ("out_susie_pip", _dp), ("out_susie_set", _ip), ("out_susie_set_pip", _dp),
         ("out_susie_V", _dp), ("out_susie_lse", _dp), ("out_susie_mass", _dp), ("out_susie_purity", _dp),

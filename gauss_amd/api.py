@@ -48,7 +48,7 @@ HOST_SYMBOLS = [
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
-    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie",
+    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
     "gauss_host_dist_traits", "gauss_host_distmix_traits", "gauss_host_dist_traits_miss", "gauss_host_distmix_traits_miss",
 ]
 
@@ -152,6 +152,9 @@ def load_host():
     h.gauss_host_dist_traits.argtypes = h.gauss_host_dist.argtypes[:-1] + traits_tail
     h.gauss_host_distmix_traits.argtypes = h.gauss_host_distmix.argtypes[:-1] + traits_tail
     h.gauss_host_dist_traits_miss.argtypes = h.gauss_host_dist_traits.argtypes
+    coloc_tail = traits_tail[:-1] + susie_tail[:-1] + [_dbl, _dbl, _dbl, C.POINTER(_vp)]      # the files, the fit's arguments, p1, p2, p12, out
+    h.gauss_host_dist_coloc.argtypes = h.gauss_host_dist.argtypes[:-1] + coloc_tail
+    h.gauss_host_distmix_coloc.argtypes = h.gauss_host_distmix.argtypes[:-1] + coloc_tail
     h.gauss_host_distmix_traits_miss.argtypes = h.gauss_host_distmix_traits.argtypes
     h.gauss_host_qcatmix.argtypes = h.gauss_host_distmix.argtypes
     h.gauss_prepared_qcat_counts.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -586,6 +589,72 @@ def distmix_traits(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_files, re
     first, more, n_more = _traits_files(input_files)
     return _traits_frame(*_window_call(name, (chr, start_bp, end_bp, wing_size), pop_wgt_df,
                        (first, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx, (more, n_more)))
+
+
+COLOC_COLUMNS = ("trait_a", "trait_b", "cs_a", "cs_b", "n", "H0", "H1", "H2", "H3", "H4", "hit_row", "hit_pp")
+
+
+def _coloc_frame(h, out):
+    """The *_traits frame with *_susie's columns for trait 1 and pip_t, cs_t, cs_pip_t per further trait; attrs: coloc (a DataFrame, one
+    row per pair of kept effects of two traits, hit_rsid resolved), effects and fit (lists, one entry per trait)."""
+    import pandas as pd
+    named = _named(h, out)
+    df = _table(h, out)[0]
+    z, pv = (np.asarray(named[k]).reshape(len(df), -1) for k in ("z_traits", "pval_traits"))
+    n_traits = z.shape[1]
+    at = list(df.columns).index("wing")                    # the *_traits columns stand in front of the fit's
+    for k in range(1, n_traits):
+        df.insert(at, f"z_{k + 1}", z[:, k])
+        df.insert(at + 1, f"pval_{k + 1}", pv[:, k])
+        at += 2
+    effects, fits = [], []
+    for t in range(1, n_traits + 1):
+        e = np.asarray(named[f"effects_{t}"], dtype=np.float64).reshape(-1, 7)
+        effects.append(dict(row=e[:, 0].astype(np.int64), V=e[:, 1].copy(), lse=e[:, 2].copy(), size=e[:, 3].astype(np.int64),
+                            mass=e[:, 4].copy(), purity=e[:, 5].copy(), kept=e[:, 6] != 0))
+        f = np.asarray(named[f"fit_{t}"], dtype=np.float64).reshape(-1)
+        fits.append(dict(sweeps=int(f[0]), delta=float(f[1]), converged=bool(f[2])))
+    c = np.asarray(named["coloc"], dtype=np.float64).reshape(-1, len(COLOC_COLUMNS))
+    co = pd.DataFrame({k: c[:, j] for j, k in enumerate(COLOC_COLUMNS)})
+    for k in ("trait_a", "trait_b", "cs_a", "cs_b", "n", "hit_row"):
+        co[k] = co[k].astype(np.int64)
+    rsid = df["rsid"].to_numpy()
+    co["hit_rsid"] = [rsid[r] if r >= 0 else None for r in co["hit_row"]]
+    df.attrs.update(coloc=co, effects=effects, fit=fits)
+    return df
+
+
+def _coloc_args(input_files, susie, p1, p2, p12):
+    first, more, n_more = _traits_files(input_files)
+    f = lambda v: 0.0 if v is None else float(v)
+    return first, (more, n_more) + _susie_args(*susie) + (f(p1), f(p2), f(p12))
+
+
+def dist_coloc(chr, start_bp, end_bp, wing_size, study_pop, input_files, reference_index_file, reference_data_file,
+               reference_pop_desc_file, af1_cutoff=None, L=None, coverage=None, prior_var=None, min_abs_corr=None, max_sweeps=None, tol=None,
+               estimate_prior_var=None, measured_only=False, p1=None, p2=None, p12=None, ctx=None):
+    """Do two traits share a causal SNP in this window, or do they have two different ones in LD?  (gauss_host_dist_coloc)
+    input_files: 2 .. 8 study files as for dist_traits (the first is trait 1 and defines the window; every measured SNP of the window
+    must be in each further file).  Every trait is fine-mapped as dist_susie does (its arguments; all traits in the same launches), then
+    every pair of reported effects of two traits is colocalised: coloc's bf_bf on the fit's Bayes factors with the priors p1, p2, p12
+    (None: 1e-4, 1e-4, 1e-5), the imputed SNPs among the candidates -- the shared SNP may be one that neither study measured.
+    The frame: dist_susie()'s rows; dist_traits()'s columns; wing, pip, cs, cs_pip for trait 1 (dist_susie's bits on the first file);
+    pip_t, cs_t, cs_pip_t for t = 2 .. T.  frame.attrs["coloc"]: a DataFrame, one row per pair of reported effects of two traits, with
+    trait_a, trait_b (1-based), cs_a, cs_b (the cs / cs_t numbering), n, H0 .. H4 (the posteriors: none, a only, b only, two different
+    SNPs, one shared), hit_row, hit_rsid and hit_pp (the most likely shared SNP and its share of H4); attrs["effects"] / attrs["fit"]:
+    lists with dist_susie's dicts, one per trait.  Limits: dist_susie's; eight traits; traits that lack measured SNPs are not fitted."""
+    first, tail = _coloc_args(input_files, (L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only), p1, p2, p12)
+    return _coloc_frame(*_window_call("gauss_host_dist_coloc", (chr, start_bp, end_bp, wing_size), study_pop,
+                        (first, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx, tail))
+
+
+def distmix_coloc(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_files, reference_index_file, reference_data_file,
+                  reference_pop_desc_file, af1_cutoff=None, L=None, coverage=None, prior_var=None, min_abs_corr=None, max_sweeps=None, tol=None,
+                  estimate_prior_var=None, measured_only=False, p1=None, p2=None, p12=None, ctx=None):
+    """dist_coloc on the ancestry-weighted LD of a distmix() window (gauss_host_distmix_coloc); columns as dist_coloc with af1mix."""
+    first, tail = _coloc_args(input_files, (L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only), p1, p2, p12)
+    return _coloc_frame(*_window_call("gauss_host_distmix_coloc", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                        (first, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx, tail))
 
 
 def _named(h, t):

@@ -36,6 +36,7 @@ HIP_UNITS = {
     "k_cond.hip": ["-ffp-contract=off"],        # imputed SNPs conditioned on the selection: the forward substitution as written, sums in ascending order
     "k_cs.hip": ["-ffp-contract=off"],          # credible sets of the selected signals: the downdate as written, sums in a fixed order
     "k_susie.hip": ["-ffp-contract=off"],       # multi-causal fine-mapping: the fit's sums as written, in a fixed order
+    "k_coloc.hip": ["-ffp-contract=off"],       # colocalisation of the fit's traits: the shifted sums as written, in a fixed order
     "k_traits.hip": ["-ffp-contract=off"],      # further traits: MFMA chains in ascending k, the closing division as written
     "k_traits_miss.hip": ["-ffp-contract=off"], # traits that lack some measured SNPs: the downdate's recurrences as written, sums in ascending order
 }
@@ -147,7 +148,7 @@ def build_hip(force=False, verbose=False):
     import json
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
-    hdrs = [os.path.join(CSRC, "gauss_internal.h"), os.path.join(CSRC, "gauss_job.h"), os.path.join(CSRC, "k_gram_common.h"), os.path.join(CSRC, "k_solve_common.h"), os.path.join(CSRC, "k_traits_common.h"), os.path.join(HERE, "..", "include", "gauss_hip.h")]
+    hdrs = [os.path.join(CSRC, "gauss_internal.h"), os.path.join(CSRC, "gauss_job.h"), os.path.join(CSRC, "k_gram_common.h"), os.path.join(CSRC, "k_solve_common.h"), os.path.join(CSRC, "k_traits_common.h"), os.path.join(CSRC, "k_cs_common.h"), os.path.join(CSRC, "k_susie_common.h"), os.path.join(HERE, "..", "include", "gauss_hip.h")]
     # an object is rebuilt when its recorded identity (source + headers + command line + compiler) differs -- not by mtime: a
     # flag change or a checkout that restores old timestamps must not link stale objects under a fresh source hash
     ids_path = os.path.join(OBJDIR, "unit_ids.json")

@@ -37,6 +37,14 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.out.susie_V = d.out_susie_V; w.out.susie_lse = d.out_susie_lse; w.out.susie_mass = d.out_susie_mass; w.out.susie_purity = d.out_susie_purity;
     w.out.susie_size = d.out_susie_size; w.out.susie_kept = d.out_susie_kept;
     w.out.susie_alpha = d.out_susie_alpha; w.out.susie_mu = d.out_susie_mu; w.out.susie_sweeps = d.out_susie_sweeps;
+    w.susie_traits_more = d.coloc_traits_more; w.coloc_p1 = d.coloc_p1; w.coloc_p2 = d.coloc_p2; w.coloc_p12 = d.coloc_p12;
+    w.out.susie_lbf = d.out_coloc_lbf;
+    w.out.more_pip = d.out_coloc_more_pip; w.out.more_set = d.out_coloc_more_set; w.out.more_set_pip = d.out_coloc_more_set_pip;
+    w.out.more_V = d.out_coloc_more_V; w.out.more_lse = d.out_coloc_more_lse; w.out.more_mass = d.out_coloc_more_mass;
+    w.out.more_purity = d.out_coloc_more_purity; w.out.more_size = d.out_coloc_more_size; w.out.more_kept = d.out_coloc_more_kept;
+    w.out.more_alpha = d.out_coloc_more_alpha; w.out.more_mu = d.out_coloc_more_mu; w.out.more_lbf = d.out_coloc_more_lbf;
+    w.out.more_sweeps = d.out_coloc_more_sweeps; w.out.more_status = d.out_coloc_more_status;
+    w.out.coloc_pp = d.out_coloc_pp; w.out.coloc_hit = d.out_coloc_hit; w.out.coloc_hit_pp = d.out_coloc_hit_pp; w.out.coloc_n = d.out_coloc_n;
     return w;
 }
 extern "C" {

@@ -143,9 +143,14 @@ struct Prob {
     int susie_L, susie_max_sweeps;         // effects L <= SUSIE_L, sweeps over them at the most
     int susie_estimate_var, susie_measured_only, susie_am;      // flags; am: the result section also holds alpha and mu
     double susie_coverage, susie_prior_var, susie_tol, susie_min_abs_corr;
-    GP(double) susie_ws;                   // [susie_ws(M, U, Mld, L, !measured_only).count] scratch: W = B11^-1 B12, the fit's state (SusieWs below)
-    GP(uint8_t) susie_mem;                 // [L][cs_tld(M + U)] scratch: 1 where the candidate is in the effect's set
+    GP(double) susie_ws;                   // [susie_ws(M, U, Mld, L, !measured_only).total(susie_k)] scratch: W = B11^-1 B12, the fit's state (SusieWs below)
+    GP(uint8_t) susie_mem;                 // [1 + susie_k][L][cs_tld(M + U)] scratch: 1 where the candidate is in the effect's set
     GP(double) out_susie;                  // [susie_layout(M + U, L, am).count]
+    // ... of further traits in the same fit, and the colocalisation of every pair of fitted traits (k_coloc.hip); susie_k = 0: trait 1 alone
+    int susie_k;                           // the first susie_k rows of traits_Z are fitted beside z1 (<= SUSIE_K); each has a state of its own in susie_ws
+    int susie_lbf, coloc;                  // flags; lbf: the section holds the final lbf rows of every fitted trait; coloc: the pairs are asked
+    double coloc_p1, coloc_p2, coloc_p12;  // prior probabilities that a SNP is causal for the first trait only, the second only, both
+    GP(double) out_susie_more;             // [susie_more_layout(M + U, L, am, lbf, susie_k, coloc).count]
     // further traits on the same window (k_traits.hip); traits_T = 0: not asked
     int traits_T;                          // T <= TRAITS_MAX further Z-score vectors
     GP(const double) traits_Z;             // [Mld][T16] their Z-scores, SNP-major, zero beyond M and T (T16 = T rounded up to 16)
@@ -173,6 +178,7 @@ inline void clear_riders(Prob& q)
     q.susie_L = q.susie_max_sweeps = q.susie_estimate_var = q.susie_measured_only = q.susie_am = 0;
     q.susie_coverage = q.susie_prior_var = q.susie_tol = q.susie_min_abs_corr = 0.0;
     q.susie_ws = nullptr; q.susie_mem = nullptr; q.out_susie = nullptr;
+    q.susie_k = q.susie_lbf = q.coloc = 0; q.coloc_p1 = q.coloc_p2 = q.coloc_p12 = 0.0; q.out_susie_more = nullptr;
     q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr;
     q.miss_E = q.miss_nm = q.miss_n = 0; q.miss_tab = nullptr;
     q.miss_YE = q.miss_AE = q.miss_YU = q.miss_LD = q.out_traits_info = q.out_traits_miss = nullptr;
@@ -201,12 +207,20 @@ constexpr int SUSIE_VR = 8;            // rows of v = b_meas + W b_unmeas a work
 constexpr int SUSIE_RR = 8;            // rows of R b = [B v ; C v] a workgroup writes (two a wave)
 constexpr int SUSIE_P = 128;           // members of a set the purity looks at
 constexpr int SUSIE_PG = 32;           // workgroups that share the pairs of one set's purity
+constexpr int SUSIE_K = 7;             // GAUSS_SUSIE_TRAITS_MORE_MAX: further traits in one fit; (SUSIE_K + 1) SUSIE_K / 2 = 28 pairs at the most
 constexpr int susie_uld(int U) { return (U + 63) & ~63; }   // row pitch of W and Y
-// Prob::susie_ws in doubles.  Y = X C^T and W = X^T Y = B11^-1 B12 [Mld][uld]; zhat, d, adm [tld] per candidate; alpha, mu, rb
-// (R b_l) and lbf [L][tld]; f [tld]; v [Mld]; V [2][SUSIE_L] by sweep parity; lse, lse_set, part [SUSIE_L][SUSIE_PG] (partial minima of
-// the purity), top [SUSIE_L][SUSIE_P] (candidate indices as ints: half the doubles), ntop [SUSIE_L]; ctl: done, sweeps, last
-// delta, delta by sweep parity [2], z1 holds a NaN.  state .. count is zeroed by susie_prep_kernel at the start of every run.
-struct SusieWs { size_t Y, W, zhat, d, adm, state, alpha, mu, rb, lbf, f, v, V, lse, lse_set, part, top, ntop, ctl, count; };
+// Prob::susie_ws in doubles.  Y = X C^T and W = X^T Y = B11^-1 B12 [Mld][uld], the window's; then one block per fitted trait (trait t
+// of 0 .. susie_k at t * trait doubles further on): zhat, d, adm [tld] per candidate; alpha, mu, rb (R b_l) and lbf [L][tld]; f [tld];
+// v [Mld]; V [2][SUSIE_L] by sweep parity; lse, lse_set, part [SUSIE_L][SUSIE_PG] (partial minima of the purity), top [SUSIE_L][SUSIE_P]
+// (candidate indices as ints: half the doubles), ntop [SUSIE_L]; ctl: done, sweeps, last delta, delta by sweep parity [2], the trait's
+// scores hold a NaN; keep [L][tld]: the final lbf rows, which susie_set_kernel turns into pips where they stand -- copied there only
+// where the lbf output or the colocalisation is asked.  [state, keep) is zeroed by susie_prep_kernel at the start of every run; keep
+// itself is not: susie_set_kernel rewrites all of it that anyone reads (l < L, i < T) before the fold and coloc_kernel read it.  (d and its part in adm are the same for every trait: each block has its own
+// copy, so that trait 0's offsets are those of a fit of one trait.)
+struct SusieWs {
+    size_t Y, W, zhat, d, adm, state, alpha, mu, rb, lbf, f, v, V, lse, lse_set, part, top, ntop, ctl, keep, count, trait;
+    constexpr size_t total(int k) const { return zhat + (size_t)(1 + k) * trait; }
+};
 enum { SUSIE_CTL_DONE = 0, SUSIE_CTL_SWEEPS, SUSIE_CTL_LAST, SUSIE_CTL_DELTA, SUSIE_CTL_ZNAN = SUSIE_CTL_DELTA + 2, SUSIE_CTL_N = 8 };
 // (w = false: a fit of the measured SNPs alone forms no W)
 constexpr SusieWs susie_ws(int M, int U, int Mld, int L, bool w)
@@ -214,20 +228,22 @@ constexpr SusieWs susie_ws(int M, int U, int Mld, int L, bool w)
     const size_t tld = (size_t)cs_tld(M + U), mu = w ? (size_t)Mld * susie_uld(U) : 0, lt = (size_t)L * tld;
     const size_t zhat = 2 * mu, state = zhat + 3 * tld, f = state + 4 * lt, V = f + tld + (size_t)Mld, lse = V + 2 * SUSIE_L;
     const size_t part = lse + 2 * SUSIE_L, top = part + (size_t)SUSIE_L * SUSIE_PG, ntop = top + (size_t)SUSIE_L * SUSIE_P / 2;
+    const size_t keep = ntop + SUSIE_L + SUSIE_CTL_N;
     return {0, mu, zhat, zhat + tld, zhat + 2 * tld, state, state, state + lt, state + 2 * lt, state + 3 * lt, f, f + tld, V, lse,
-            lse + SUSIE_L, part, top, ntop, ntop + SUSIE_L, ntop + SUSIE_L + SUSIE_CTL_N};
+            lse + SUSIE_L, part, top, ntop, ntop + SUSIE_L, keep, keep + lt, keep + lt - zhat};
 }
 
 // ---- the result block ------------------------------------------------------------------------------------------------
 // A window's doubles in the job's result block, in this order and nowhere else written down:
 //     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, traits_info [T][U], traits_miss [2][n_miss]]
 //     [, the selection] [, cond_z[U], cond_var[U]] [, cs: size[K], mass[K], lse[K], pip[M+U], set[M+U], set_pip[M+U]]
-//     [, susie: susie_layout]
+//     [, susie: susie_layout] [, susie_more: susie_more_layout]
 // Offsets in doubles from the window's Plan::res_off; a section nobody asked for takes nothing and its offset is that of the next.
 // traits_info and traits_miss exist when the window passed a mask (miss): n_miss = its set bits.  The conditional section
-// (cond; k_cond.hip), behind it the credible sets (cs; k_cs.hip) and behind them the multi-causal fit (susie; k_susie.hip) are the
-// last: every other offset is what it is without them.
-struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, count; };
+// (cond; k_cond.hip), behind it the credible sets (cs; k_cs.hip), behind them the multi-causal fit (susie; k_susie.hip) and what it holds beyond trait 1's
+// values (susie_more; the further traits' fits, the lbf rows, the colocalisation of k_coloc.hip) are the last: every other offset is
+// what it is without them.
+struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, susie_more, count; };
 // Inside the selection's section, from its start: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] (indices, n and the
 // skipped flag travel as exact doubles).  The host and slct_kernel both read it here.
 struct SlctLayout { size_t n, skipped, idx, zin, joint, zc, var, count; };
@@ -251,16 +267,29 @@ constexpr SusieLayout susie_layout(int T, int L, bool am)
     const size_t l = (size_t)L, t = (size_t)T, c = 6 * l + 4;
     return {0, l, 2 * l, 3 * l, 4 * l, 5 * l, 6 * l, c, c + t, c + 2 * t, c + 3 * t, c + 3 * t + (am ? l * t : 0), c + 3 * t + (am ? 2 * l * t : 0)};
 }
+// Behind the multi-causal fit's section, from its start: with lbf, trait 1's final lbf [L][T]; then one block per further fitted trait
+// (k of them, `one` doubles apart): its susie_layout and, with lbf, its lbf [L][T] at `tlbf` inside the block; with coloc, for the
+// pairs = (k + 1) k / 2 pairs of fitted traits in the order (0, 1), (0, 2), .., (k - 1, k): pp [pairs][L][L][5], hit [pairs][L][L] (an
+// exact double, -1: none), hit_pp [pairs][L][L], n [pairs].  A part nobody asked for takes nothing.
+struct SusieMoreLayout { size_t lbf, trait, one, tlbf, pp, hit, hit_pp, n, count; };
+constexpr SusieMoreLayout susie_more_layout(int T, int L, bool am, bool lbf, int k, bool coloc)
+{
+    const size_t lt = lbf ? (size_t)L * T : 0, fit = susie_layout(T, L, am).count, one = fit + lt;
+    const size_t pp = lt + (size_t)k * one, ll = (size_t)L * L, np = coloc ? (size_t)(k + 1) * k / 2 : 0;
+    return {0, lt, one, fit, pp, pp + 5 * np * ll, pp + 6 * np * ll, pp + 7 * np * ll, pp + 7 * np * ll + np};
+}
 constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, bool miss = false, int n_miss = 0, bool cond = false,
-                               bool cs = false, int susie_L = 0, bool susie_am = false)
+                               bool cs = false, int susie_L = 0, bool susie_am = false, bool susie_lbf = false, int susie_k = 0,
+                               bool coloc = false)
 {
     const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_tinfo = o_traits + (size_t)T * U;
     const size_t o_tmiss = o_tinfo + (miss ? (size_t)T * U : 0), o_slct = o_tmiss + (miss ? 2 * (size_t)n_miss : 0);
     const size_t o_cond = o_slct + (K ? slct_layout(M, K).count : 0);
     const size_t o_cs = o_cond + (cond ? 2 * (size_t)U : 0);
     const size_t o_susie = o_cs + (cs ? cs_layout(M + U, K).count : 0);
-    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie,
-            o_susie + (susie_L ? susie_layout(M + U, susie_L, susie_am).count : 0)};
+    const size_t o_more = o_susie + (susie_L ? susie_layout(M + U, susie_L, susie_am).count : 0);
+    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie, o_more,
+            o_more + (susie_L ? susie_more_layout(M + U, susie_L, susie_am, susie_lbf, susie_k, coloc).count : 0)};
 }
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
@@ -383,7 +412,11 @@ void launch_cs(const Prob* d_probs, const int* d_csmap, int n, int max_T, hipStr
 // -- a window that has converged, has fewer effects or fewer sweeps leaves at once -- then the sets, their purity and the fold; it runs
 // behind launch_cs.  max_M / max_U / max_T / max_L / max_sweeps: the largest among the asking windows
 void launch_susie_w(const Prob* d_probs, const int* d_susiemap, int n, int max_nblk, int max_U, hipStream_t s);
-void launch_susie(const Prob* d_probs, const int* d_susiemap, int n, int max_M, int max_T, int max_L, int max_sweeps, hipStream_t s);
+// max_k: the most further traits one of them fits -- the trait is a grid dimension of the fit's launches, never a launch of its own;
+// coloc: one of them asks for the colocalisation (k_coloc.hip), one launch behind susie_kept_kernel
+void launch_susie(const Prob* d_probs, const int* d_susiemap, int n, int max_M, int max_T, int max_L, int max_sweeps, int max_k, bool coloc,
+                  hipStream_t s);
+void launch_coloc(const Prob* d_probs, const int* d_susiemap, int n, int max_L, int max_k, hipStream_t s);
 // further traits (k_traits.hip).  launch_traits_weights: G = X^T (X Z) of the windows that asked, d_map = (window, 64-row block of X),
 // two launches (Y = X Z, then G = X^T Y); it runs where launch_loo runs.  launch_traits_impute: out_traits = B21 G / sqrt(out_info),
 // d_umap = (window, strip of 64 unmeasured SNPs); it runs behind the kernel that writes out_info

@@ -243,6 +243,13 @@ struct RiderOuts {
     double *susie_pip = nullptr, *susie_set_pip = nullptr, *susie_V = nullptr, *susie_lse = nullptr, *susie_mass = nullptr;      // the multi-causal fit
     double *susie_purity = nullptr, *susie_alpha = nullptr, *susie_mu = nullptr, *susie_sweeps = nullptr;                        // (gauss_window_desc.out_susie_*)
     int32_t *susie_set = nullptr, *susie_size = nullptr, *susie_kept = nullptr;
+    double* susie_lbf = nullptr;
+    // the further traits of the same fit (gauss_window_desc.out_coloc_more_*, a leading [k]) and the pairs (out_coloc_*)
+    double *more_pip = nullptr, *more_set_pip = nullptr, *more_V = nullptr, *more_lse = nullptr, *more_mass = nullptr, *more_purity = nullptr;
+    double *more_alpha = nullptr, *more_mu = nullptr, *more_lbf = nullptr, *more_sweeps = nullptr;
+    int32_t *more_set = nullptr, *more_size = nullptr, *more_kept = nullptr, *more_status = nullptr;
+    double *coloc_pp = nullptr, *coloc_hit_pp = nullptr;
+    int32_t *coloc_hit = nullptr, *coloc_n = nullptr;
     double* z_more = nullptr;
     double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
 };
@@ -285,6 +292,8 @@ struct Plan {
         bool cs = false;                     // credible sets of the selected signals (k_cs.hip); needs slct_K
         int susie_L = 0;                     // multi-causal fine-mapping (k_susie.hip): effects; 0: not asked
         bool susie_am = false;               // ... and its result section holds alpha and mu (out_susie_alpha / out_susie_mu ask)
+        int susie_k = 0;                     // ... further traits fitted beside z1 (gauss_window_desc.coloc_traits_more)
+        bool susie_lbf = false, coloc = false;      // ... the lbf rows are asked; the colocalisation of the traits' pairs is (k_coloc.hip)
         int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
         std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
         bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
@@ -293,7 +302,7 @@ struct Plan {
         RiderOuts out;
         bool needs_fused() const { return loo || traits_T > 0 || susie_L > 0; }      // it reads the rows of L^-1 that only the fused solve forms
     } rd;
-    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs, rd.susie_L, rd.susie_am); }
+    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs, rd.susie_L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc); }
     size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
@@ -355,6 +364,7 @@ struct gauss_job {
     int* d_susiemap = nullptr;  int n_susie = 0;           // multi-causal fine-mapping: the windows that asked
     int susie_max_M = 0, susie_max_U = 0, susie_max_T = 0; // ... the largest M, U (of those that fit unmeasured candidates) and M + U among them,
     int susie_max_L = 0, susie_max_sweeps = 0, susie_max_nblk = 0;      // the most effects, sweeps and 64-row blocks of X
+    int susie_max_k = 0;  bool susie_coloc = false;        // ... the most further traits in one fit; a window asks for the colocalisation
     int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
     int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
     int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some
@@ -477,6 +487,8 @@ struct WinSpec {
     double cs_coverage = 0.0, cs_prior_var = 0.0;      // credible sets of the selected signals (an out.cs_* asks)
     int susie_L = 0, susie_max_sweeps = 0, susie_estimate_var = 0, susie_measured_only = 0;      // multi-causal fine-mapping (gauss_window_desc.susie_*)
     double susie_coverage = 0.0, susie_prior_var = 0.0, susie_tol = 0.0, susie_min_abs_corr = 0.0;
+    int susie_traits_more = 0;               // further traits in the same fit; the colocalisation's priors (all zero: off)
+    double coloc_p1 = 0.0, coloc_p2 = 0.0, coloc_p12 = 0.0;
     const int32_t* slct_forced = nullptr;
     int n_slct_forced = 0;
     // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample

@@ -146,6 +146,32 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         if (!w.z_more || !w.out.z_more)
             return fail(GAUSS_E_INVALID, "n_traits_more = %d needs z_more and out_z_more (%s is NULL)", w.n_traits_more, !w.z_more ? "z_more" : "out_z_more");
     }
+    // every trait of the window in one fit, and the colocalisation of their signals (k_susie.hip, k_coloc.hip)
+    if (w.susie_traits_more < 0 || w.susie_traits_more > w.n_traits_more || w.susie_traits_more > SUSIE_K)
+        return fail(GAUSS_E_INVALID, "coloc_traits_more = %d: the fit takes 0 .. min(n_traits_more = %d, %d) further traits", w.susie_traits_more,
+                    w.n_traits_more, SUSIE_K);
+    if (w.susie_traits_more > 0 && !susie)
+        return fail(GAUSS_E_INVALID, "coloc_traits_more = %d fits further traits beside z1: it needs susie_L > 0", w.susie_traits_more);
+    if (w.susie_traits_more > 0 && w.miss_more)
+        return fail(GAUSS_E_INVALID, "coloc_traits_more = %d with miss_more: traits that lack measured SNPs are not fitted", w.susie_traits_more);
+    const bool more_out = w.out.more_pip || w.out.more_set || w.out.more_set_pip || w.out.more_V || w.out.more_lse || w.out.more_mass ||
+                          w.out.more_purity || w.out.more_size || w.out.more_kept || w.out.more_alpha || w.out.more_mu || w.out.more_lbf ||
+                          w.out.more_sweeps || w.out.more_status;
+    if (more_out && w.susie_traits_more <= 0)
+        return fail(GAUSS_E_INVALID, "out_coloc_more_* are the further traits' fits: they need coloc_traits_more > 0");
+    if (w.out.susie_lbf && !susie) return fail(GAUSS_E_INVALID, "out_coloc_lbf belongs to the multi-causal fit: it needs susie_L > 0");
+    const bool coloc = w.coloc_p1 != 0.0 || w.coloc_p2 != 0.0 || w.coloc_p12 != 0.0;
+    if (coloc) {
+        if (!(w.coloc_p1 > 0.0 && w.coloc_p1 < 1.0)) return fail(GAUSS_E_INVALID, "coloc_p1 = %g: a prior probability lies in (0, 1)", w.coloc_p1);
+        if (!(w.coloc_p2 > 0.0 && w.coloc_p2 < 1.0)) return fail(GAUSS_E_INVALID, "coloc_p2 = %g: a prior probability lies in (0, 1)", w.coloc_p2);
+        if (!(w.coloc_p12 > 0.0 && w.coloc_p12 < 1.0)) return fail(GAUSS_E_INVALID, "coloc_p12 = %g: a prior probability lies in (0, 1)", w.coloc_p12);
+        if (w.coloc_p12 > std::min(w.coloc_p1, w.coloc_p2))
+            return fail(GAUSS_E_INVALID, "coloc_p12 = %g exceeds min(coloc_p1, coloc_p2) = %g", w.coloc_p12, std::min(w.coloc_p1, w.coloc_p2));
+        if (!susie || w.susie_traits_more < 1)
+            return fail(GAUSS_E_INVALID, "coloc_p1 / coloc_p2 / coloc_p12 colocalise pairs of fitted traits: they need susie_L > 0 and coloc_traits_more >= 1");
+    }
+    if ((w.out.coloc_pp || w.out.coloc_hit || w.out.coloc_hit_pp || w.out.coloc_n) && !coloc)
+        return fail(GAUSS_E_INVALID, "out_coloc_* need coloc_p1, coloc_p2 and coloc_p12");
     // further traits that lack some measured SNPs (k_traits_miss.hip): the mask as index lists (MissTab)
     std::vector<int> miss_tab;
     int miss_n = 0, miss_nm = 0, miss_ne = 0;
@@ -428,6 +454,13 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
             for (int g = 0; g < w.M; g++)      // (a score the trait lacks is not read: an exact zero takes its place)
                 rd.traits_z[(size_t)g * T16 + t] = (w.miss_more && w.miss_more[(size_t)t * w.M + g]) ? 0.0 : w.z_more[(size_t)t * w.M + g];
         p.traits_T = w.n_traits_more;
+    }
+    if (susie) {
+        rd.susie_k = w.susie_traits_more;
+        rd.susie_lbf = w.out.susie_lbf || w.out.more_lbf;
+        rd.coloc = coloc;
+        p.susie_k = rd.susie_k; p.susie_lbf = rd.susie_lbf ? 1 : 0; p.coloc = coloc ? 1 : 0;
+        p.coloc_p1 = w.coloc_p1; p.coloc_p2 = w.coloc_p2; p.coloc_p12 = w.coloc_p12;
     }
     rd.miss = !miss_tab.empty();
     rd.miss_n = miss_n;
@@ -734,6 +767,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             susiemap.push_back(i);
             job->susie_max_M = std::max(job->susie_max_M, p.M); job->susie_max_T = std::max(job->susie_max_T, p.M + p.U);
             job->susie_max_L = std::max(job->susie_max_L, rd.susie_L); job->susie_max_sweeps = std::max(job->susie_max_sweeps, p.susie_max_sweeps);
+            job->susie_max_k = std::max(job->susie_max_k, rd.susie_k); job->susie_coloc = job->susie_coloc || rd.coloc;
             if (!p.susie_measured_only) { job->susie_max_U = std::max(job->susie_max_U, p.U); job->susie_max_nblk = std::max(job->susie_max_nblk, p.nblk); }
         }
         if (rd.traits_T) {
@@ -1044,8 +1078,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         }
         w.susie_ws = w.susie_mem = 0;
         if (pl.rd.susie_L) {                // W, the fit's state and the sets' membership bytes
-            w.susie_ws = wa.take(susie_ws(p.M, p.U, p.Mld, pl.rd.susie_L, !p.susie_measured_only).count * sizeof(double));
-            w.susie_mem = wa.take((size_t)pl.rd.susie_L * cs_tld(p.M + p.U));
+            w.susie_ws = wa.take(susie_ws(p.M, p.U, p.Mld, pl.rd.susie_L, !p.susie_measured_only).total(pl.rd.susie_k) * sizeof(double));
+            w.susie_mem = wa.take((size_t)(1 + pl.rd.susie_k) * pl.rd.susie_L * cs_tld(p.M + p.U));
         }
         w.ty = w.tg = 0;
         if (pl.rd.traits_T) {               // Y = X Z and G = X^T Y of the further traits
@@ -1212,6 +1246,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.cs_lbf = pl.rd.cs ? (double*)(W + w.cs_lbf) : nullptr;
         p.cs_mem = pl.rd.cs ? (uint8_t*)(W + w.cs_mem) : nullptr;
         p.out_susie = pl.rd.susie_L ? out + lay.susie : nullptr;
+        p.out_susie_more = pl.rd.susie_L && lay.count > lay.susie_more ? out + lay.susie_more : nullptr;
         p.susie_ws = pl.rd.susie_L ? (double*)(W + w.susie_ws) : nullptr;
         p.susie_mem = pl.rd.susie_L ? (uint8_t*)(W + w.susie_mem) : nullptr;
         p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;

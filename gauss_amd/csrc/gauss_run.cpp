@@ -86,7 +86,7 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 
 // The tail of a fused solve, in the one order its inputs allow:
 //     loo -> selection -> traits weights -> miss solve -> fine-mapping weights -> closing step -> traits impute -> miss apply
-//         -> conditional -> credible sets -> multi-causal fit
+//         -> conditional -> credible sets -> multi-causal fit (-> colocalisation of its traits, inside launch_susie)
 //   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
 //     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
 //   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
@@ -98,7 +98,8 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 //   - the credible sets of the selected signals (k_cs.hip): what the conditional step reads, and the selection's joint z and B11's
 //     diagonal in A[0]; they write a workspace and a result section of their own;
 //   - the multi-causal fit (k_susie.hip): its weights W = X^T (X B12) read the rows of X like the traits weights, and B21, which is
-//     complete where the tail starts; the fit itself reads z and info of the closing step, B11 in A[0] and B21.
+//     complete where the tail starts; the fit itself reads z and info of the closing step, B11 in A[0] and B21, and for its further
+//     traits the scores in traits_Z and the imputed Z-scores traits impute has left (such a window has no mask: miss apply leaves them).
 // The closing step of a run is the product B21 [X | y] with its finish kernel.  A launch for which no window asked is skipped by its
 // launcher.  The clamp path (job_clamp_window) keeps the same order with its single-window map and the stand-alone solve as its
 // closing step; its selection runs in front of the re-factorisation.
@@ -114,7 +115,8 @@ static void queue_tail(gauss_job* job, hipStream_t st)
     launch_traits_miss_apply(job->d_probs, job->d_missumap, job->n_miss_u, st);
     launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);
     launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
-    launch_susie(job->d_probs, job->d_susiemap, job->n_susie, job->susie_max_M, job->susie_max_T, job->susie_max_L, job->susie_max_sweeps, st);
+    launch_susie(job->d_probs, job->d_susiemap, job->n_susie, job->susie_max_M, job->susie_max_T, job->susie_max_L, job->susie_max_sweeps,
+                 job->susie_max_k, job->susie_coloc, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -720,6 +722,13 @@ int job_fetch(gauss_job* job)
                 for (int l = 0; l < rd.susie_L; l++) sq[ql.size + l] = sq[ql.kept + l] = 0.0;
                 for (int c = 0; c < p.M + p.U; c++) sq[ql.set + c] = -1.0;
                 sq[ql.fit] = sq[ql.fit + 2] = 0.0;
+                // ... and so is every further trait of the fit; every pair: NaN, hit -1, n 0
+                const SusieMoreLayout ml = susie_more_layout(p.M + p.U, rd.susie_L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc);
+                double* const mq = res + lay.susie_more;
+                for (size_t u = 0; u < ml.count; u++) mq[u] = NAN;
+                for (int t = 0; t < rd.susie_k; t++) memcpy(mq + ml.trait + (size_t)t * ml.one, sq, sizeof(double) * ql.count);
+                for (size_t u = ml.hit; u < ml.hit_pp; u++) mq[u] = -1.0;
+                for (size_t u = ml.n; u < ml.count; u++) mq[u] = 0.0;
                 if (!(bits & GAUSS_ST_NONFINITE)) bits |= GAUSS_ST_SUSIE_NOFIT;
             }
             auto copy_out = [](double* dst, const double* src, size_t n) { if (dst) memcpy(dst, src, sizeof(double) * n); };
@@ -777,6 +786,37 @@ int job_fetch(gauss_job* job)
                 copy_out(rd.out.susie_set_pip, sq + ql.set_pip, T);
                 if (rd.susie_am) { copy_out(rd.out.susie_alpha, sq + ql.alpha, (size_t)L * T); copy_out(rd.out.susie_mu, sq + ql.mu, (size_t)L * T); }
                 copy_out(rd.out.susie_sweeps, sq + ql.fit, 2);
+                // the lbf rows, the further traits of the same fit and the pairs (susie_more_layout)
+                const SusieMoreLayout ml = susie_more_layout(T, L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc);
+                const double* const mq = res + lay.susie_more;
+                const size_t lt = (size_t)L * T;
+                if (rd.susie_lbf) copy_out(rd.out.susie_lbf, mq + ml.lbf, lt);
+                for (int t = 0; t < rd.susie_k; t++) {
+                    const double* const tq = mq + ml.trait + (size_t)t * ml.one;
+                    const RiderOuts& o = rd.out;
+                    if (o.more_status)
+                        o.more_status[t] = (tq[ql.fit + 2] != 0.0 ? GAUSS_ST_SUSIE_NOCONV : 0) | (bits & (GAUSS_ST_SUSIE_NOFIT | GAUSS_ST_NONFINITE));
+                    if (o.more_V) copy_out(o.more_V + (size_t)t * L, tq + ql.V, L);
+                    if (o.more_lse) copy_out(o.more_lse + (size_t)t * L, tq + ql.lse, L);
+                    if (o.more_mass) copy_out(o.more_mass + (size_t)t * L, tq + ql.mass, L);
+                    if (o.more_purity) copy_out(o.more_purity + (size_t)t * L, tq + ql.purity, L);
+                    if (o.more_size) for (int l = 0; l < L; l++) o.more_size[(size_t)t * L + l] = (int32_t)tq[ql.size + l];
+                    if (o.more_kept) for (int l = 0; l < L; l++) o.more_kept[(size_t)t * L + l] = (int32_t)tq[ql.kept + l];
+                    if (o.more_pip) copy_out(o.more_pip + (size_t)t * T, tq + ql.pip, T);
+                    if (o.more_set) for (int c = 0; c < T; c++) o.more_set[(size_t)t * T + c] = (int32_t)tq[ql.set + c];
+                    if (o.more_set_pip) copy_out(o.more_set_pip + (size_t)t * T, tq + ql.set_pip, T);
+                    if (rd.susie_am && o.more_alpha) copy_out(o.more_alpha + t * lt, tq + ql.alpha, lt);
+                    if (rd.susie_am && o.more_mu) copy_out(o.more_mu + t * lt, tq + ql.mu, lt);
+                    if (rd.susie_lbf && o.more_lbf) copy_out(o.more_lbf + t * lt, tq + ml.tlbf, lt);
+                    if (o.more_sweeps) copy_out(o.more_sweeps + 2 * (size_t)t, tq + ql.fit, 2);
+                }
+                if (rd.coloc) {
+                    const size_t np = (size_t)(rd.susie_k + 1) * rd.susie_k / 2, ll = (size_t)L * L;
+                    copy_out(rd.out.coloc_pp, mq + ml.pp, 5 * np * ll);
+                    if (rd.out.coloc_hit) for (size_t e = 0; e < np * ll; e++) rd.out.coloc_hit[e] = (int32_t)mq[ml.hit + e];
+                    copy_out(rd.out.coloc_hit_pp, mq + ml.hit_pp, np * ll);
+                    if (rd.out.coloc_n) for (size_t e = 0; e < np; e++) rd.out.coloc_n[e] = (int32_t)mq[ml.n + e];
+                }
             }
             if (pl.out_b11 && (!exporting || clamped))
                 { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }

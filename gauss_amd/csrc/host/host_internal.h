@@ -555,6 +555,18 @@ int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vecto
 int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const double* pip, const int32_t* set, const double* set_pip, const double* alpha, const double* V,
                  const double* lse, const int32_t* size, const double* mass, const double* purity, const int32_t* kept, const double* sweeps);
+// dist_coloc / distmix_coloc: susie_output's rows and its columns wing pip cs cs_pip for trait 1, then pip_t cs_t cs_pip_t for every
+// further fitted trait t = 2 .. 1 + k; traits_output's named matrices over ALL rows (a wing's measured SNP shows its own study z); the
+// named matrices effects_t and fit_t (susie_output's `effects` and `fit`) for t = 1 .. 1 + k; and `coloc`, one row per pair of kept
+// effects of two traits: trait_a trait_b (1-based) cs_a cs_b (the 1-based effects, the cs / cs_t columns' numbering) n H0 H1 H2 H3 H4
+// hit_row (table row of the most likely shared SNP, from 0) hit_pp.  A message per trait whose sweeps ran out or that was not fitted
+struct SusieFit {                     // one trait's out_susie_* (first) or the further traits' out_coloc_more_* with a leading [k] (more)
+    const double *pip, *set_pip, *alpha, *V, *lse, *mass, *purity, *sweeps;
+    const int32_t *set, *size, *kept;
+};
+struct ColocMore { int k; SusieFit fit; const double* pp; const int32_t* hit; const double* hit_pp; const int32_t* n; };
+int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                 int L, double tol, const SusieFit& first, int n_more, const double* z_more, const double* out_z_more, const ColocMore& more);
 // dist_traits / distmix_traits: the Z-scores of one further trait at the n measured SNPs of a window.  SNP i is at(i) -- position and
 // alleles in the window's (the panel's) orientation -- and is looked up in the study `gw` (read from `path`, named in the messages)
 // by (chr, bp, a1, a2): the same allele order gives z, the swapped order -z (gauss.cpp:358-370); of several rows that match, the
@@ -661,6 +673,21 @@ struct TraitsRider : Rider {
     TraitsRider(const char* const* files_, int n_more_, bool miss_) : files(files_), n_more(n_more_), miss(miss_) {}
     std::vector<double> z, out_z, info, z_miss, info_miss;
     std::vector<uint8_t> mask;
+    int check() override;
+    int ask(gauss_window_desc& d, const WindowView& v) override;
+    int table(const WindowView& v, gauss_table** out) override;
+};
+// dist_coloc / distmix_coloc: TraitsRider's files and matching (no mask: a further file that lacks a measured SNP is refused) and
+// SusieRider's arguments in one window; every further trait is fitted beside trait 1 (coloc_traits_more = n_more) and every pair of
+// fitted traits is colocalised (coloc_p1 / coloc_p2 / coloc_p12; <= 0 or NaN: coloc's 1e-4, 1e-4, 1e-5).  The table is coloc_output's
+struct ColocRider : Rider {
+    TraitsRider traits;
+    SusieRider susie;
+    double p1, p2, p12;
+    ColocRider(const char* const* files_, int n_more_, const SusieRider& susie_, double p1_, double p2_, double p12_)
+        : traits(files_, n_more_, false), susie(susie_), p1(p1_), p2(p2_), p12(p12_) {}
+    std::vector<double> pip, set_pip, alpha, V, lse, mass, purity, sweeps, pp, hit_pp;      // the further traits [k][..], the pairs
+    std::vector<int32_t> set, size, kept, hit, n;
     int check() override;
     int ask(gauss_window_desc& d, const WindowView& v) override;
     int table(const WindowView& v, gauss_table** out) override;

@@ -179,3 +179,52 @@ int TraitsRider::table(const WindowView& v, gauss_table** out)
     traits_output(**out, n_more, v.row_m, v.row_u, z.data(), out_z.data(), n_more > 0 && miss ? &tm : nullptr);
     return 0;
 }
+
+// ---- coloc ----
+int ColocRider::check()
+{
+    if (traits.check() || susie.check()) return -1;
+    if (traits.n_more < 1) return herr("the colocalisation takes at least two study files (the first is trait 1)");
+    if (traits.n_more > GAUSS_SUSIE_TRAITS_MORE_MAX)
+        return herr("%d study files: at most %d traits are fitted in one window", 1 + traits.n_more, 1 + GAUSS_SUSIE_TRAITS_MORE_MAX);
+    return 0;
+}
+
+int ColocRider::ask(gauss_window_desc& d, const WindowView& v)
+{
+    if (traits.ask(d, v) || susie.ask(d, v)) return -1;
+    const size_t k = (size_t)traits.n_more, L = (size_t)susie.n_eff, T = (size_t)std::max(d.n_measured + d.n_unmeasured, 1);
+    const size_t np = (k + 1) * k / 2;
+    pip.assign(k * T, NAN); set_pip = pip; set.assign(k * T, -1); alpha.assign(k * L * T, NAN);
+    V.assign(k * L, NAN); lse = V; mass = V; purity = V; size.assign(k * L, 0); kept = size; sweeps.assign(2 * k, NAN);
+    for (size_t t = 0; t < k; t++) sweeps[2 * t] = 0.0;
+    pp.assign(5 * np * L * L, NAN); hit_pp.assign(np * L * L, NAN); hit.assign(np * L * L, -1); n.assign(np, 0);
+    d.coloc_traits_more = (int)k;
+    d.out_coloc_more_pip = pip.data(); d.out_coloc_more_set = set.data(); d.out_coloc_more_set_pip = set_pip.data();
+    d.out_coloc_more_alpha = alpha.data(); d.out_coloc_more_V = V.data(); d.out_coloc_more_lse = lse.data();
+    d.out_coloc_more_mass = mass.data(); d.out_coloc_more_purity = purity.data(); d.out_coloc_more_size = size.data();
+    d.out_coloc_more_kept = kept.data(); d.out_coloc_more_sweeps = sweeps.data();
+    d.coloc_p1 = p1 > 0 ? p1 : 1e-4;                                   // (a NaN compares false: coloc's defaults)
+    d.coloc_p2 = p2 > 0 ? p2 : 1e-4;
+    d.coloc_p12 = p12 > 0 ? p12 : 1e-5;
+    d.out_coloc_pp = pp.data(); d.out_coloc_hit = hit.data(); d.out_coloc_hit_pp = hit_pp.data(); d.out_coloc_n = n.data();
+    return 0;
+}
+
+int ColocRider::table(const WindowView& v, gauss_table** out)
+{
+    if (v.plain(out)) return -1;
+    std::vector<SlctRow> rows;
+    for (const ViewSnp& s : v.measured) rows.push_back(SlctRow{s.id, s.af, s.z, s.wing});
+    const SusieRider& s = susie;
+    const SusieFit first = {s.pip.data(), s.set_pip.data(), s.alpha.data(), s.V.data(), s.lse.data(), s.mass.data(), s.purity.data(),
+                            s.sweeps.data(), s.set.data(), s.size.data(), s.kept.data()};
+    const ColocMore more = {traits.n_more, {pip.data(), set_pip.data(), alpha.data(), V.data(), lse.data(), mass.data(), purity.data(),
+                                            sweeps.data(), set.data(), size.data(), kept.data()},
+                            pp.data(), hit.data(), hit_pp.data(), n.data()};
+    if (coloc_output(**out, rows, v.row_m, v.row_u, s.n_eff, s.tol_used, first, traits.n_more, traits.z.data(), traits.out_z.data(), more)) {
+        gauss_table_free(*out); *out = nullptr;
+        return -1;
+    }
+    return 0;
+}

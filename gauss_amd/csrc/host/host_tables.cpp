@@ -1,5 +1,6 @@
 // libgauss_host.so -- result tables (the reference's output lists: dist.cpp:91-124, qcat.cpp:94-131, prep_qcat.cpp:135-204),
 // the JEPEG k x k tail (gene.cpp:88-185, 317-550) and the table accessors of the C ABI (include/gauss_host.h).
+#include <array>
 #include "host_internal.h"
 
 thread_local std::string g_err;
@@ -367,19 +368,17 @@ int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vecto
 // wing, pip, cs (1-based effect of the kept set that holds the SNP, 0: none) and cs_pip, the named matrices `effects` [L x 7] (table row
 // of the SNP of largest alpha, V, lse, size, mass, purity, kept) and `fit` [1 x 3] (sweeps, delta, converged), and a message when the
 // sweeps ran out or the window was not fitted
-int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
-                 int L, double tol, const double* pip, const int32_t* set, const double* set_pip, const double* alpha, const double* V,
-                 const double* lse, const int32_t* size, const double* mass, const double* purity, const int32_t* kept, const double* sweeps)
+// One trait's fit in the table: the columns pip<cs> cs<cs> cs_pip<cs> by candidate (row_of[c]: the candidate's table row, -1: not listed),
+// the named matrices effects<nm> and fit<nm>, and a message (`who` names the trait) when the sweeps ran out or nothing was fitted
+static void susie_trait_output(gauss_table& t, size_t nrow, const std::vector<int32_t>& row_of, const std::string& cs_sfx, const std::string& nm_sfx,
+                               const std::string& who, int L, double tol, const double* pip, const int32_t* set, const double* set_pip,
+                               const double* alpha, const double* V, const double* lse, const int32_t* size, const double* mass,
+                               const double* purity, const int32_t* kept, const double* sweeps)
 {
-    std::vector<int32_t> at;
-    size_t nrow = 0;
-    if (append_wing_rows(t, rows, row_m, 4, "susie_output", at, nrow)) return -1;
-    const size_t M = rows.size(), T = M + row_u.size();
-    Column &wing = t.add("wing", GAUSS_COL_INT), &p = t.add("pip", GAUSS_COL_DBL), &cs = t.add("cs", GAUSS_COL_INT), &cp = t.add("cs_pip", GAUSS_COL_DBL);
-    wing.i.assign(nrow, 0); p.d.assign(nrow, NAN); cs.i.assign(nrow, 0); cp.d.assign(nrow, NAN);
-    std::vector<int32_t> row_of(T, -1);                               // table row of candidate c
-    for (size_t i = 0; i < M; i++) { row_of[i] = at[i]; wing.i[(size_t)at[i]] = rows[i].wing; }
-    for (size_t u = 0; u < row_u.size(); u++) row_of[M + u] = row_u[u];
+    const size_t T = row_of.size();
+    Column &p = t.add(("pip" + cs_sfx).c_str(), GAUSS_COL_DBL), &cs = t.add(("cs" + cs_sfx).c_str(), GAUSS_COL_INT),
+           &cp = t.add(("cs_pip" + cs_sfx).c_str(), GAUSS_COL_DBL);
+    p.d.assign(nrow, NAN); cs.i.assign(nrow, 0); cp.d.assign(nrow, NAN);
     for (size_t c = 0; c < T; c++) {
         if (row_of[c] < 0) continue;
         const size_t r = (size_t)row_of[c];
@@ -397,13 +396,79 @@ int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::ve
         const double vals[7] = {(double)lead, V[l], lse[l], (double)size[l], mass[l], purity[l], (double)kept[l]};
         for (int k = 0; k < 7; k++) eff[(size_t)k * L + l] = vals[k];
     }
-    t.put_named("effects", L, 7, std::move(eff));
+    t.put_named(("effects" + nm_sfx).c_str(), L, 7, std::move(eff));
     // tol = 0 (the caller asked for exactly max_sweeps sweeps with a negative tol): delta < 0 never holds, so `converged` is 0, and
     // running the sweeps out is what was asked for: no message
     const bool converged = fitted && sweeps[1] < tol;
-    t.put_named("fit", 1, 3, std::vector<double>{sweeps[0], sweeps[1], converged ? 1.0 : 0.0});
-    if (!fitted) t.messages.push_back("susie: the window was not fitted (its B11 is not finite, or MakePosDef repaired it): pip, cs and cs_pip are empty");
-    else if (!converged && tol > 0) t.messages.push_back("susie: the sweeps ran out before the fit converged (max_sweeps); the values are those of the last sweep");
+    t.put_named(("fit" + nm_sfx).c_str(), 1, 3, std::vector<double>{sweeps[0], sweeps[1], converged ? 1.0 : 0.0});
+    if (!fitted) t.messages.push_back(who + ": the window was not fitted (its B11 is not finite, or MakePosDef repaired it): pip, cs and cs_pip are empty");
+    else if (!converged && tol > 0) t.messages.push_back(who + ": the sweeps ran out before the fit converged (max_sweeps); the values are those of the last sweep");
+}
+
+// the wing column and the table row of every candidate, the measured SNPs (appended ones included) first
+static std::vector<int32_t> wing_column(gauss_table& t, size_t nrow, const std::vector<SlctRow>& rows, const std::vector<int32_t>& at,
+                                        const std::vector<int32_t>& row_u)
+{
+    const size_t M = rows.size();
+    Column& wing = t.add("wing", GAUSS_COL_INT);
+    wing.i.assign(nrow, 0);
+    std::vector<int32_t> row_of(M + row_u.size(), -1);
+    for (size_t i = 0; i < M; i++) { row_of[i] = at[i]; wing.i[(size_t)at[i]] = rows[i].wing; }
+    for (size_t u = 0; u < row_u.size(); u++) row_of[M + u] = row_u[u];
+    return row_of;
+}
+
+int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                 int L, double tol, const double* pip, const int32_t* set, const double* set_pip, const double* alpha, const double* V,
+                 const double* lse, const int32_t* size, const double* mass, const double* purity, const int32_t* kept, const double* sweeps)
+{
+    std::vector<int32_t> at;
+    size_t nrow = 0;
+    if (append_wing_rows(t, rows, row_m, 4, "susie_output", at, nrow)) return -1;
+    const std::vector<int32_t> row_of = wing_column(t, nrow, rows, at, row_u);
+    susie_trait_output(t, nrow, row_of, "", "", "susie", L, tol, pip, set, set_pip, alpha, V, lse, size, mass, purity, kept, sweeps);
+    return 0;
+}
+
+int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+                 int L, double tol, const SusieFit& first, int n_more, const double* z_more, const double* out_z_more, const ColocMore& more)
+{
+    std::vector<int32_t> at;
+    size_t nrow = 0;
+    if (append_wing_rows(t, rows, row_m, 4, "coloc_output", at, nrow)) return -1;
+    const int k = more.k;
+    t.widen(4 + 3 * (size_t)k);                                       // before the first add(): no reference into the table is held
+    const std::vector<int32_t> row_of = wing_column(t, nrow, rows, at, row_u);
+    const size_t Tn = row_of.size(), lt = (size_t)L * Tn;
+    susie_trait_output(t, nrow, row_of, "", "_1", "coloc, trait 1", L, tol, first.pip, first.set, first.set_pip, first.alpha, first.V, first.lse,
+                       first.size, first.mass, first.purity, first.kept, first.sweeps);
+    for (int q = 0; q < k; q++) {
+        const std::string n = std::to_string(q + 2);
+        const SusieFit& f = more.fit;
+        susie_trait_output(t, nrow, row_of, "_" + n, "_" + n, "coloc, trait " + n, L, tol, f.pip + q * Tn, f.set + q * Tn, f.set_pip + q * Tn,
+                           f.alpha + q * lt, f.V + (size_t)q * L, f.lse + (size_t)q * L, f.size + (size_t)q * L, f.mass + (size_t)q * L,
+                           f.purity + (size_t)q * L, f.kept + (size_t)q * L, f.sweeps + 2 * (size_t)q);
+    }
+    // the further traits' Z-scores on every row, the wings' measured SNPs included
+    traits_output(t, n_more, at, row_u, z_more, out_z_more);
+    // one row per pair of kept effects of two traits
+    std::vector<std::array<double, 12>> out;
+    size_t pair = 0;
+    for (int a = 0; a <= k; a++)
+        for (int b = a + 1; b <= k; b++, pair++)
+            for (int la = 0; la < L; la++)
+                for (int lb = 0; lb < L; lb++) {
+                    const size_t e = (pair * L + la) * L + lb;
+                    const int32_t hit = more.hit[e];
+                    if (hit < 0) continue;
+                    const double* pp = more.pp + 5 * e;
+                    out.push_back({(double)(a + 1), (double)(b + 1), (double)(la + 1), (double)(lb + 1), (double)more.n[pair], pp[0], pp[1], pp[2],
+                                   pp[3], pp[4], (double)((size_t)hit < Tn ? row_of[(size_t)hit] : -1), more.hit_pp[e]});
+                }
+    std::vector<double> cm(out.size() * 12);
+    for (size_t r = 0; r < out.size(); r++)
+        for (int c = 0; c < 12; c++) cm[(size_t)c * out.size() + r] = out[r][(size_t)c];
+    t.put_named("coloc", (int)out.size(), 12, std::move(cm));
     return 0;
 }
 

@@ -36,50 +36,25 @@
 //   susie_kept_kernel     one workgroup per window: purity, kept (V_l > 0, purity >= min_abs_corr, no kept l' < l with the same members),
 //                         the per-effect outputs, sweeps / delta / the no-convergence flag
 //   susie_fold_kernel     one thread per candidate: pip = 1 - prod_{V_l > 0} (1 - alpha_lj), set, set_pip over the kept sets
+//   coloc_kernel          (k_coloc.hip) behind susie_kept_kernel where a window asks: the pairs of kept effects of two fitted traits
+// Further traits (Prob::susie_k of the window's further Z-score vectors, k_traits.hip) are fitted in the same launches: the trait is
+// blockIdx.z of prep, ser_v, rb, set, rank, kept and fold, and rides with the effect in blockIdx.y of purity.  B, C, W and Y are the
+// window's; a trait reads its own scores (susie_trait, k_susie_common.h) and keeps its own state, done word included, so every trait
+// leaves the step launches at its own sweep.  Trait 0's pointers, sums and bits are those of a fit of one trait.
 // fp64, no atomics, every sum in a fixed order.  Compiled with -ffp-contract=off like the other fp64 tails.
 #include "k_traits_common.h"
-#include "k_cs_common.h"
+#include "k_susie_common.h"
 
 namespace gauss {
 
-constexpr int SUSIE_NW = SUSIE_T / 64;
 static_assert(SUSIE_VR == 2 * SUSIE_NW && SUSIE_RR == 2 * SUSIE_NW, "two rows a wave");
 static_assert(SUSIE_L <= SLCT_K, "cs_set_row's workspace geometry");
-
-__device__ __forceinline__ const Prob& susie_prob(const Prob* probs, const int* map, int y) { return probs[map ? map[y] : y]; }
-__device__ __forceinline__ SusieWs susie_ws_of(const Prob& pb) { return susie_ws(pb.M, pb.U, pb.Mld, pb.susie_L, !pb.susie_measured_only); }
 
 __device__ __forceinline__ double susie_lbf(double r, double d, double V)
 {
     if (V == 0.0) return 0.0;
     const double vd = V * d;
     return 0.5 * (r * r * V / (1.0 + vd) - log1p(vd));
-}
-
-// max and sum over the workgroup (SUSIE_T threads) in a fixed order: lanes by xor moves, then the waves ascending
-__device__ __forceinline__ double susie_block_max(double x, double* s_red, int tid)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = cs_max(x, __shfl_xor(x, off, 64));
-    __syncthreads();
-    if ((tid & 63) == 0) s_red[tid >> 6] = x;
-    __syncthreads();
-    double t = s_red[0];
-#pragma unroll
-    for (int w = 1; w < SUSIE_NW; w++) t = cs_max(t, s_red[w]);
-    return t;
-}
-__device__ __forceinline__ double susie_block_sum(double x, double* s_red, int tid)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) s_red[tid >> 6] = x;
-    __syncthreads();
-    double t = s_red[0];
-#pragma unroll
-    for (int w = 1; w < SUSIE_NW; w++) t += s_red[w];
-    return t;
 }
 
 // ---- W = X^T (X C^T) ----
@@ -140,14 +115,16 @@ __global__ __launch_bounds__(SUSIE_T) void susie_prep_kernel(const Prob* __restr
     const Prob& pb = susie_prob(probs, map, blockIdx.y);
     const int tid = threadIdx.x;
     const int M = pb.M, U = pb.U, T = M + U, ld = pb.Mld;
+    if ((int)blockIdx.z > pb.susie_k) return;
     const SusieWs o = susie_ws_of(pb);
-    const auto ws = pb.susie_ws;
+    const SusieTrait tr = susie_trait(pb, o, blockIdx.z);
+    const auto ws = tr.st;
     const size_t stride = (size_t)gridDim.x * SUSIE_T, first = (size_t)blockIdx.x * SUSIE_T + tid;
-    // a non-finite z1 anywhere: no unmeasured SNP is admissible (every workgroup looks for itself)
+    // a non-finite score of the trait anywhere: no unmeasured SNP is admissible (every workgroup looks for itself)
     double bad = 0.0;
-    for (int i = tid; i < M; i += SUSIE_T) bad += isfinite(pb.z1[i]) ? 0.0 : 1.0;
+    for (int i = tid; i < M; i += SUSIE_T) bad += isfinite(tr.z[(size_t)i * tr.zs]) ? 0.0 : 1.0;
     bad = susie_block_sum(bad, s_red, tid);
-    for (size_t e = o.state + first; e < o.count; e += stride) {
+    for (size_t e = o.state + first; e < o.keep; e += stride) {
         double x = 0.0;
         if (e >= o.V && e < o.V + 2 * SUSIE_L) x = pb.susie_prior_var;
         if (e == o.ctl + SUSIE_CTL_ZNAN) x = bad;
@@ -157,10 +134,10 @@ __global__ __launch_bounds__(SUSIE_T) void susie_prep_kernel(const Prob* __restr
         double zh, d;
         bool adm;
         if (j < (size_t)M) {
-            zh = pb.z1[j]; d = pb.A[j * ld + j];
+            zh = tr.z[j * tr.zs]; d = pb.A[j * ld + j];
             adm = true;
         } else {
-            const double zu = pb.out_z[j - M], info = pb.out_info[j - M];
+            const double zu = tr.zu[j - M], info = pb.out_info[j - M];
             zh = zu * sqrt(info); d = info;
             adm = !pb.susie_measured_only && bad == 0.0;
         }
@@ -176,9 +153,9 @@ __global__ __launch_bounds__(SUSIE_T) void susie_ser_v_kernel(const Prob* __rest
     const Prob& pb = susie_prob(probs, map, blockIdx.y);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = pb.M, U = pb.U, T = M + U, L = pb.susie_L;
-    if (l >= L || sweep >= pb.susie_max_sweeps || (int)blockIdx.x * SUSIE_VR >= M) return;
+    if (l >= L || sweep >= pb.susie_max_sweeps || (int)blockIdx.x * SUSIE_VR >= M || (int)blockIdx.z > pb.susie_k) return;
     const SusieWs o = susie_ws_of(pb);
-    const auto ws = pb.susie_ws;
+    const auto ws = pb.susie_ws + (size_t)blockIdx.z * o.trait;      // the trait's state
     const auto ctl = ws + o.ctl;
     if (ctl[SUSIE_CTL_DONE] != 0.0) return;
     if (l == 0 && sweep > 0) {
@@ -216,7 +193,7 @@ __global__ __launch_bounds__(SUSIE_T) void susie_ser_v_kernel(const Prob* __rest
     double acc0 = 0.0, acc1 = 0.0;
     if (!pb.susie_measured_only && U > 0) {
         const int uld = susie_uld(U);
-        const auto W0 = ws + o.W + (size_t)min(i0, M - 1) * uld, W1 = ws + o.W + (size_t)min(i0 + 1, M - 1) * uld;
+        const auto W0 = pb.susie_ws + o.W + (size_t)min(i0, M - 1) * uld, W1 = pb.susie_ws + o.W + (size_t)min(i0 + 1, M - 1) * uld;
         for (int c0 = 0; c0 < U; c0 += SUSIE_CH) {
             const int n = min(SUSIE_CH, U - c0);
             __syncthreads();                                // (the chunk before has been read)
@@ -282,9 +259,9 @@ __global__ __launch_bounds__(SUSIE_T) void susie_rb_kernel(const Prob* __restric
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = pb.M, T = M + pb.U, L = pb.susie_L, ld = pb.Mld;
     const int rows = pb.susie_measured_only ? M : T;        // (an inadmissible candidate's row is never read)
-    if (l >= L || sweep >= pb.susie_max_sweeps || (int)blockIdx.x * SUSIE_RR >= rows) return;
+    if (l >= L || sweep >= pb.susie_max_sweeps || (int)blockIdx.x * SUSIE_RR >= rows || (int)blockIdx.z > pb.susie_k) return;
     const SusieWs o = susie_ws_of(pb);
-    const auto ws = pb.susie_ws;
+    const auto ws = pb.susie_ws + (size_t)blockIdx.z * o.trait;      // the trait's state
     if (ws[o.ctl + SUSIE_CTL_DONE] != 0.0) return;
     const auto v = ws + o.v, f = ws + o.f, rb = ws + o.rb + (size_t)l * cs_tld(T);
     const int j0 = blockIdx.x * SUSIE_RR + 2 * wave;
@@ -307,9 +284,8 @@ __global__ __launch_bounds__(SUSIE_T) void susie_rb_kernel(const Prob* __restric
 
 // ---- sets ----
 // the sweeps the fit ran: what the step that saw it converge wrote down, else all of them
-__device__ __forceinline__ int susie_sweeps_of(const Prob& pb, const SusieWs& o)
+__device__ __forceinline__ int susie_sweeps_of(const Prob& pb, GP(const double) ctl)
 {
-    const auto ctl = pb.susie_ws + o.ctl;
     const double s = ctl[SUSIE_CTL_SWEEPS];
     const int n = ctl[SUSIE_CTL_DONE] != 0.0 && s >= 0.0 && s <= (double)pb.susie_max_sweeps ? (int)s : pb.susie_max_sweeps;
     return __builtin_amdgcn_readfirstlane(n);
@@ -321,17 +297,22 @@ __global__ __launch_bounds__(CS_SET_T) void susie_set_kernel(const Prob* __restr
     const Prob& pb = susie_prob(probs, map, blockIdx.y);
     const int tid = threadIdx.x, l = blockIdx.x;
     const int T = pb.M + pb.U, L = pb.susie_L;
-    if (l >= L) return;
+    if (l >= L || (int)blockIdx.z > pb.susie_k) return;
     const SusieWs o = susie_ws_of(pb);
+    const SusieTrait tr = susie_trait(pb, o, blockIdx.z);
     const size_t tld = (size_t)cs_tld(T);
-    double* const g_row = pb.susie_ws + o.lbf + (size_t)l * tld;
-    uint8_t* const mem = pb.susie_mem + (size_t)l * tld;
+    double* const g_row = tr.st + o.lbf + (size_t)l * tld;
+    uint8_t* const mem = tr.mem + (size_t)l * tld;
+    // the row becomes pips where it stands: where the lbf output or the colocalisation is asked, the Bayes factors themselves are kept
+    // (a thread copies the entries that it alone reads first below)
+    if (pb.susie_lbf || pb.coloc)
+        for (int i = tid; i < T; i += CS_SET_T) tr.st[o.keep + (size_t)l * tld + i] = g_row[i];
     double size, mass, lse;
     cs_set_row(g_row, mem, T, pb.susie_coverage, s_row, s_red, tid, size, mass, lse);
     if (tid == 0) {
         const SusieLayout q = susie_layout(T, L, pb.susie_am != 0);
-        pb.out_susie[q.size + l] = size; pb.out_susie[q.mass + l] = mass;
-        pb.susie_ws[o.lse_set + l] = lse;
+        tr.out[q.size + l] = size; tr.out[q.mass + l] = mass;
+        tr.st[o.lse_set + l] = lse;
     }
 }
 
@@ -340,12 +321,13 @@ __global__ __launch_bounds__(SUSIE_T) void susie_rank_kernel(const Prob* __restr
     const Prob& pb = susie_prob(probs, map, blockIdx.y);
     const int tid = threadIdx.x, l = blockIdx.x;
     const int T = pb.M + pb.U, L = pb.susie_L;
-    if (l >= L) return;
+    if (l >= L || (int)blockIdx.z > pb.susie_k) return;
     const SusieWs o = susie_ws_of(pb);
+    const SusieTrait tr = susie_trait(pb, o, blockIdx.z);
     const size_t tld = (size_t)cs_tld(T);
-    const auto row = pb.susie_ws + o.lbf + (size_t)l * tld;      // pips by now (cs_set_row)
-    const auto mem = pb.susie_mem + (size_t)l * tld;
-    const auto top = (GP(int))(pb.susie_ws + o.top) + l * SUSIE_P;
+    const auto row = tr.st + o.lbf + (size_t)l * tld;      // pips by now (cs_set_row)
+    const auto mem = tr.mem + (size_t)l * tld;
+    const auto top = (GP(int))(tr.st + o.top) + l * SUSIE_P;
     // the members are a prefix of the order (pip descending, index ascending): a member's place in it is its rank among all candidates
     for (int i = tid; i < T; i += SUSIE_T) {
         if (!mem[i]) continue;
@@ -359,22 +341,22 @@ __global__ __launch_bounds__(SUSIE_T) void susie_rank_kernel(const Prob* __restr
     }
     if (tid == 0) {
         const SusieLayout q = susie_layout(T, L, pb.susie_am != 0);
-        const double size = pb.out_susie[q.size + l];
-        pb.susie_ws[o.ntop + l] = size >= 0.0 && size < (double)SUSIE_P ? size : (double)SUSIE_P;
+        const double size = tr.out[q.size + l];
+        tr.st[o.ntop + l] = size >= 0.0 && size < (double)SUSIE_P ? size : (double)SUSIE_P;
     }
 }
 
-__global__ __launch_bounds__(SUSIE_T) void susie_purity_kernel(const Prob* __restrict__ probs, const int* __restrict__ map)
+__global__ __launch_bounds__(SUSIE_T) void susie_purity_kernel(const Prob* __restrict__ probs, const int* __restrict__ map, int max_L)
 {
     __shared__ double s_min[SUSIE_NW];
     __shared__ int s_top[SUSIE_P];
     const Prob& pb = susie_prob(probs, map, blockIdx.z);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = blockIdx.x, l = blockIdx.y;
+    const int g = blockIdx.x, l = blockIdx.y % max_L, t = blockIdx.y / max_L;      // (effect, trait) of the job's most effects
     const int M = pb.M, U = pb.U, T = M + U, L = pb.susie_L, ld = pb.Mld;
-    if (l >= L) return;
+    if (l >= L || t > pb.susie_k) return;
     const SusieWs o = susie_ws_of(pb);
-    const auto ws = pb.susie_ws;
+    const auto ws = pb.susie_ws + (size_t)t * o.trait;      // the trait's state
     const double np = ws[o.ntop + l];
     const int P = __builtin_amdgcn_readfirstlane(np >= 0.0 && np <= (double)SUSIE_P ? (int)np : 0);
     const auto top = (GP(const int))(ws + o.top) + l * SUSIE_P;
@@ -397,7 +379,7 @@ __global__ __launch_bounds__(SUSIE_T) void susie_purity_kernel(const Prob* __res
             else {
                 // c_u . W_v over the measured SNPs, a lane the rows lane, + 64, ...
                 const auto cu = pb.B21 + (size_t)(ca - M) * ld;
-                const auto wv = ws + o.W + (cb - M);
+                const auto wv = pb.susie_ws + o.W + (cb - M);
                 double acc = 0.0;
                 for (int m = lane; m < M; m += 64) acc += cu[m] * wv[(size_t)m * uld];
 #pragma unroll
@@ -424,12 +406,14 @@ __global__ __launch_bounds__(SUSIE_T) void susie_kept_kernel(const Prob* __restr
     const Prob& pb = susie_prob(probs, map, blockIdx.x);
     const int tid = threadIdx.x;
     const int T = pb.M + pb.U, L = pb.susie_L;
+    if ((int)blockIdx.z > pb.susie_k) return;
     const SusieWs o = susie_ws_of(pb);
     const SusieLayout q = susie_layout(T, L, pb.susie_am != 0);
-    const auto ws = pb.susie_ws;
-    const auto out = pb.out_susie;
+    const SusieTrait tr = susie_trait(pb, o, blockIdx.z);
+    const auto ws = tr.st;
+    const auto out = tr.out;
     const size_t tld = (size_t)cs_tld(T);
-    const int sweeps = susie_sweeps_of(pb, o);
+    const int sweeps = susie_sweeps_of(pb, ws + o.ctl);
     const auto Vfin = ws + o.V + (size_t)(sweeps & 1) * SUSIE_L;      // what the last sweep's update left
     for (int l = 0; l < L; l++) {
         const double np = ws[o.ntop + l];
@@ -441,7 +425,7 @@ __global__ __launch_bounds__(SUSIE_T) void susie_kept_kernel(const Prob* __restr
         for (int k = 0; k < l && kept; k++) {
             if (!s_kept[k] || out[q.size + k] != out[q.size + l]) continue;      // (s_kept[k]: written behind a barrier of iteration k)
             double diff = 0.0;
-            for (int i = tid; i < T; i += SUSIE_T) diff += pb.susie_mem[(size_t)k * tld + i] != pb.susie_mem[(size_t)l * tld + i] ? 1.0 : 0.0;
+            for (int i = tid; i < T; i += SUSIE_T) diff += tr.mem[(size_t)k * tld + i] != tr.mem[(size_t)l * tld + i] ? 1.0 : 0.0;
             diff = susie_block_sum(diff, s_red, tid);
             if (diff == 0.0) kept = false;
         }
@@ -467,19 +451,21 @@ __global__ __launch_bounds__(SUSIE_T) void susie_fold_kernel(const Prob* __restr
     const Prob& pb = susie_prob(probs, map, blockIdx.y);
     const int T = pb.M + pb.U, L = pb.susie_L;
     const int c = blockIdx.x * SUSIE_T + threadIdx.x;
-    if (c >= T) return;
+    if (c >= T || (int)blockIdx.z > pb.susie_k) return;
     const SusieWs o = susie_ws_of(pb);
     const SusieLayout q = susie_layout(T, L, pb.susie_am != 0);
-    const auto ws = pb.susie_ws;
-    const auto out = pb.out_susie;
+    const SusieTrait tr = susie_trait(pb, o, blockIdx.z);
+    const auto ws = tr.st;
+    const auto out = tr.out;
     const size_t tld = (size_t)cs_tld(T);
     double keep = 1.0, best = 0.0;
     int set = -1;
     for (int l = 0; l < L; l++) {
         const double a = ws[o.alpha + (size_t)l * tld + c];
         if (out[q.V + l] > 0.0) keep *= 1.0 - a;
-        if (out[q.kept + l] != 0.0 && pb.susie_mem[(size_t)l * tld + c] && (set < 0 || a > best)) { set = l; best = a; }
+        if (out[q.kept + l] != 0.0 && tr.mem[(size_t)l * tld + c] && (set < 0 || a > best)) { set = l; best = a; }
         if (pb.susie_am) { out[q.alpha + (size_t)l * T + c] = a; out[q.mu + (size_t)l * T + c] = ws[o.mu + (size_t)l * tld + c]; }
+        if (pb.susie_lbf) tr.out_lbf[(size_t)l * T + c] = ws[o.keep + (size_t)l * tld + c];
     }
     out[q.pip + c] = 1.0 - keep;
     out[q.set + c] = (double)set;
@@ -494,21 +480,24 @@ void launch_susie_w(const Prob* d_probs, const int* d_susiemap, int n, int max_n
     hipLaunchKernelGGL(susie_w_kernel, grid, dim3(256), 0, s, d_probs, d_susiemap, 1);
 }
 
-void launch_susie(const Prob* d_probs, const int* d_susiemap, int n, int max_M, int max_T, int max_L, int max_sweeps, hipStream_t s)
+void launch_susie(const Prob* d_probs, const int* d_susiemap, int n, int max_M, int max_T, int max_L, int max_sweeps, int max_k, bool coloc,
+                  hipStream_t s)
 {
     if (n <= 0 || max_T <= 0) return;
-    hipLaunchKernelGGL(susie_prep_kernel, dim3(64, n), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
-    const dim3 gv((max_M + SUSIE_VR - 1) / SUSIE_VR, n), gr((max_T + SUSIE_RR - 1) / SUSIE_RR, n);
+    const unsigned nt = 1 + max_k;                          // fitted traits: a grid dimension of every launch, never a launch
+    hipLaunchKernelGGL(susie_prep_kernel, dim3(64, n, nt), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
+    const dim3 gv((max_M + SUSIE_VR - 1) / SUSIE_VR, n, nt), gr((max_T + SUSIE_RR - 1) / SUSIE_RR, n, nt);
     for (int sweep = 0; sweep < max_sweeps; sweep++)
         for (int l = 0; l < max_L; l++) {
             hipLaunchKernelGGL(susie_ser_v_kernel, gv, dim3(SUSIE_T), 0, s, d_probs, d_susiemap, sweep, l);
             hipLaunchKernelGGL(susie_rb_kernel, gr, dim3(SUSIE_T), 0, s, d_probs, d_susiemap, sweep, l);
         }
-    hipLaunchKernelGGL(susie_set_kernel, dim3(max_L, n), dim3(CS_SET_T), 0, s, d_probs, d_susiemap);
-    hipLaunchKernelGGL(susie_rank_kernel, dim3(max_L, n), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
-    hipLaunchKernelGGL(susie_purity_kernel, dim3(SUSIE_PG, max_L, n), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
-    hipLaunchKernelGGL(susie_kept_kernel, dim3(n), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
-    hipLaunchKernelGGL(susie_fold_kernel, dim3((max_T + SUSIE_T - 1) / SUSIE_T, n), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
+    hipLaunchKernelGGL(susie_set_kernel, dim3(max_L, n, nt), dim3(CS_SET_T), 0, s, d_probs, d_susiemap);
+    hipLaunchKernelGGL(susie_rank_kernel, dim3(max_L, n, nt), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
+    hipLaunchKernelGGL(susie_purity_kernel, dim3(SUSIE_PG, max_L * nt, n), dim3(SUSIE_T), 0, s, d_probs, d_susiemap, max_L);
+    hipLaunchKernelGGL(susie_kept_kernel, dim3(n, 1, nt), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
+    if (coloc) launch_coloc(d_probs, d_susiemap, n, max_L, max_k, s);
+    hipLaunchKernelGGL(susie_fold_kernel, dim3((max_T + SUSIE_T - 1) / SUSIE_T, n, nt), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
 }
 
 }  // namespace gauss

@@ -371,6 +371,36 @@ class _Win:
             if susie.get("want_alpha"):
                 q["alpha"], q["mu"] = np.full((Lc, T), np.nan), np.full((Lc, T), np.nan)
                 desc.out_susie_alpha, desc.out_susie_mu = q["alpha"].ctypes.data_as(_dp), q["mu"].ctypes.data_as(_dp)
+            if susie.get("want_lbf"):
+                q["lbf"] = np.full((Lc, T), np.nan)
+                desc.out_coloc_lbf = q["lbf"].ctypes.data_as(_dp)
+            # traits=k: the first k rows of z_more are fitted as well (coloc_traits_more / out_coloc_more_* of gauss_window_desc);
+            # coloc=dict(p1=1e-4, p2=1e-4, p12=1e-5): the colocalisation of every pair of fitted traits (coloc_* / out_coloc_*)
+            self.susie_more = self.coloc = None
+            k = int(susie.get("traits", 0))
+            kc = min(max(k, 0), _lib.SUSIE_TRAITS_MORE_MAX)
+            desc.coloc_traits_more = k
+            if kc:
+                m = self.susie_more = dict(pip=np.full((kc, T), np.nan), set=np.full((kc, T), -1, dtype=np.int32), set_pip=np.full((kc, T), np.nan),
+                                           V=np.full((kc, Lc), np.nan), lse=np.full((kc, Lc), np.nan), mass=np.full((kc, Lc), np.nan),
+                                           purity=np.full((kc, Lc), np.nan), size=np.zeros((kc, Lc), dtype=np.int32),
+                                           kept=np.zeros((kc, Lc), dtype=np.int32), sweeps=np.full((kc, 2), np.nan),
+                                           status=np.zeros(kc, dtype=np.int32))
+                if susie.get("want_alpha"):
+                    m["alpha"], m["mu"] = np.full((kc, Lc, T), np.nan), np.full((kc, Lc, T), np.nan)
+                if susie.get("want_lbf"):
+                    m["lbf"] = np.full((kc, Lc, T), np.nan)
+                for key, a in m.items():
+                    setattr(desc, "out_coloc_more_" + key, a.ctypes.data_as(_ip if a.dtype == np.int32 else _dp))
+            if susie.get("coloc") is not None:
+                co = susie["coloc"]
+                n_pairs = (kc + 1) * kc // 2
+                c = self.coloc = dict(pp=np.full((n_pairs, Lc, Lc, 5), np.nan), hit=np.full((n_pairs, Lc, Lc), -1, dtype=np.int32),
+                                      hit_pp=np.full((n_pairs, Lc, Lc), np.nan), n=np.zeros(n_pairs, dtype=np.int32))
+                desc.coloc_p1, desc.coloc_p2, desc.coloc_p12 = float(co.get("p1", 1e-4)), float(co.get("p2", 1e-4)), float(co.get("p12", 1e-5))
+                if n_pairs:
+                    for key, a in c.items():
+                        setattr(desc, "out_coloc_" + key, a.ctypes.data_as(_ip if a.dtype == np.int32 else _dp))
         # further traits on the same window (n_traits_more / z_more / out_z_more of gauss_window_desc): z_more [T, M] -> [T, U]
         self.z_more = self.out_z_more = None
         if z_more is not None:
@@ -459,6 +489,13 @@ class _Win:
             q = self.susie
             out.update({"susie_" + k: v for k, v in q.items() if k != "sweeps"})
             out.update(susie_sweeps=int(q["sweeps"][0]) if np.isfinite(q["sweeps"][0]) else 0, susie_delta=float(q["sweeps"][1]))
+            if self.susie_more is not None:
+                m = self.susie_more
+                out.update({"susie_more_" + k: v for k, v in m.items() if k != "sweeps"})
+                out.update(susie_more_sweeps=np.where(np.isfinite(m["sweeps"][:, 0]), m["sweeps"][:, 0], 0).astype(np.int64),
+                           susie_more_delta=m["sweeps"][:, 1].copy())
+            if self.coloc is not None:
+                out.update({"coloc_" + k: v for k, v in self.coloc.items()})
         return out
 
 
@@ -481,8 +518,14 @@ def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_e
     susie=dict(L=10, coverage=0.95, prior_var=25.0, tol=1e-4, max_sweeps=100, min_abs_corr=0.5, estimate_var=True, measured_only=False)
     adds the multi-causal fine-mapping of the window (include/gauss_hip.h, susie_*): susie_pip / susie_set / susie_set_pip [M + U] per
     candidate, the measured SNPs first, susie_V / susie_lse / susie_size / susie_mass / susie_purity / susie_kept [L] per effect,
-    susie_sweeps and susie_delta; want_alpha=True in that dict adds susie_alpha / susie_mu [L, M + U].  Status bit 16: the sweeps ran
-    out; bit 32: MakePosDef repaired the window, which is then not fitted."""
+    susie_sweeps and susie_delta; want_alpha=True in that dict adds susie_alpha / susie_mu [L, M + U], want_lbf=True susie_lbf.  Status
+    bit 16: the sweeps ran out; bit 32: MakePosDef repaired the window, which is then not fitted.
+    traits=k in that dict (k <= 7, with z_more of at least k rows and no miss_more) fits the first k rows of z_more in the same launches
+    (include/gauss_hip.h, coloc_traits_more): susie_more_* are the susie_* of the further traits with a leading [k], susie_more_status [k]
+    their bits 16 / 32.  coloc=dict(p1=1e-4, p2=1e-4, p12=1e-5) beside it colocalises every pair of fitted traits (coloc_*): coloc_pp
+    [pairs, L, L, 5] = the posteriors of H0 .. H4 for effect la of the pair's first trait and lb of its second (NaN unless both are
+    kept), coloc_hit / coloc_hit_pp [pairs, L, L] the most likely shared candidate (measured first; -1: none) and its share of H4,
+    coloc_n [pairs]; pairs in the order (0, 1), (0, 2), .., (k - 1, k), trait 0 being z1."""
     ctx = ctx or default_context()
     desc = WindowDesc()
     win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct, z_more=z_more,
@@ -625,7 +668,8 @@ class Job:
         result carries the signal selection (and the imputed SNPs conditioned on it, and the signals' credible sets; impute_window).
         z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window).
         miss_more=[T, M] beside it: the SNPs each further trait lacks; the result carries info_more, z_miss, info_miss (impute_window).
-        susie=dict(L=, ...) in a window's dict: its result carries the multi-causal fine-mapping susie_* (impute_window)."""
+        susie=dict(L=, ...[, traits=k][, coloc=dict(p1=, p2=, p12=)]) in a window's dict: its result carries the multi-causal fine-mapping
+        susie_*, of the first k rows of z_more too (susie_more_*), and the colocalisation of their pairs coloc_* (impute_window)."""
         self.ctx = ctx or default_context()
         n = len(windows)
         self.descs = (WindowDesc * n)()

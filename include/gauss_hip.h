@@ -92,6 +92,57 @@ typedef struct gauss_window_desc {
     double eig_cutoff;        /* CountPC cutoff: Arguments::eig_cutoff = 0.01 (gauss.cpp:22)       */
     double* out_r;            /* [n_pred_measured + U] correlations, measured first   host pointer */
     int32_t* out_num_eig;     /* [1] CountPC(B11, eig_cutoff)                          host pointer */
+    /* ---- every trait of the window in one fit, and the colocalisation of their signals (needs susie_L > 0) ---------
+     * coloc_traits_more = k fits the first k rows of z_more as well as z1, with the window's susie_* arguments: 1 + k traits, at
+     * most 1 + GAUSS_SUSIE_TRAITS_MORE_MAX.  For further trait t (row t - 1 of z_more) the definition above applies word for word
+     * with z = z_more[t - 1] and m = out_z_more[t - 1] o sqrt(out_info); a non-finite value in z_more[t - 1] makes that trait's
+     * unmeasured SNPs inadmissible.  B, C, W and d are the window's, formed once; each trait keeps its own state and stops at its
+     * own sweep; the traits share every launch (the same susie_max_sweeps x L x 2 step launches).  Trait 1's out_susie_* keep the
+     * bits of a window without coloc_traits_more, and a further trait's bits depend on its own row of z_more only: not on k, not
+     * on the other rows, not on its place among them.  out_coloc_more_* are the further traits' out_susie_* with a leading [k]
+     * dimension, every one optional; out_coloc_more_status [k] carries GAUSS_ST_SUSIE_NOCONV (and GAUSS_ST_SUSIE_NOFIT) per
+     * trait, the window's own status word keeps meaning trait 1.  out_coloc_lbf / out_coloc_more_lbf: the log Bayes factors of
+     * the last sweep's update of every effect, -inf at an inadmissible candidate.
+     * Colocalisation (coloc's bf_bf, Wallace 2021, on the fit's per-effect Bayes factors; coloc_p1 = coloc_p2 = coloc_p12 = 0:
+     * off): for fitted traits a < b, a kept effect la of a and a kept effect lb of b, with l1 = lbf row la of a, l2 = lbf row lb of
+     * b, J = the candidates admissible in both fits, n = |J|:
+     *   S1 = sum_J e^l1_j,  S2 = sum_J e^l2_j,  S12 = sum_J e^(l1_j + l2_j)
+     *   lH0 = 0,  lH1 = log p1 + log S1,  lH2 = log p2 + log S2,  lH3 = log p1 + log p2 + log max(S1 S2 - S12, 0),
+     *   lH4 = log p12 + log S12;   out_coloc_pp = softmax(lH) [5]: no causal SNP, one for a only, one for b only, two different
+     *   ones, one shared;   out_coloc_hit = argmax_J (l1_j + l2_j) (ties: the smaller index), a candidate index, measured first --
+     *   an imputed SNP can be the shared causal SNP of two traits that neither study measured;  out_coloc_hit_pp = e^(l1_hit +
+     *   l2_hit) / S12.  Sums are shifted by their maxima and S1 S2 - S12 is formed in logs: with n = 1 PP.H3 is an exact 0.
+     * Pairs are in the order (0, 1), (0, 2), .., (k - 1, k), trait 0 being z1.  A pair of effects that are not both kept gives
+     * NaN / -1, and so does every pair when a fit was not made (GAUSS_ST_SUSIE_NOFIT, GAUSS_ST_NONFINITE) or n = 0.
+     * GAUSS_E_INVALID: coloc_traits_more < 0, > n_traits_more or > GAUSS_SUSIE_TRAITS_MORE_MAX; coloc_traits_more > 0 with
+     * susie_L = 0 or with miss_more (traits that lack measured SNPs are not fitted); a coloc parameter that is not finite, not in
+     * (0, 1), or coloc_p12 > min(coloc_p1, coloc_p2); coloc parameters with fewer than two fitted traits; an out_coloc_more_* or
+     * out_coloc_* pointer without what it belongs to.  Kernels: k_susie.hip (the trait is a grid dimension), k_coloc.hip (one
+     * launch behind the fit).  (The block sits in front of u_codings: every later field keeps its neighbours, and every field of it
+     * is named coloc_* / out_coloc_*: the traits are fitted for the sake of their pairs.) */
+    int      coloc_traits_more;        /* k: rows of z_more fitted beside z1; 0 = trait 1 alone                             */
+    double   coloc_p1;                 /* prior probability that a SNP is causal for the first trait of a pair only          */
+    double   coloc_p2;                 /* ... for the second only                                                             */
+    double   coloc_p12;                /* ... for both; <= min(coloc_p1, coloc_p2)                                            */
+    double*  out_coloc_lbf;            /* [L][M+U] trait 1                                           optional              */
+    double*  out_coloc_more_pip;       /* [k][M+U]                                                   optional              */
+    int32_t* out_coloc_more_set;       /* [k][M+U]                                                   optional              */
+    double*  out_coloc_more_set_pip;   /* [k][M+U]                                                   optional              */
+    double*  out_coloc_more_V;         /* [k][L]                                                     optional              */
+    double*  out_coloc_more_lse;       /* [k][L]                                                     optional              */
+    double*  out_coloc_more_mass;      /* [k][L]                                                     optional              */
+    double*  out_coloc_more_purity;    /* [k][L]                                                     optional              */
+    int32_t* out_coloc_more_size;      /* [k][L]                                                     optional              */
+    int32_t* out_coloc_more_kept;      /* [k][L]                                                     optional              */
+    double*  out_coloc_more_alpha;     /* [k][L][M+U]                                                optional              */
+    double*  out_coloc_more_mu;        /* [k][L][M+U]                                                optional              */
+    double*  out_coloc_more_lbf;       /* [k][L][M+U]                                                optional              */
+    double*  out_coloc_more_sweeps;    /* [k][2] sweeps run, the last delta                          optional              */
+    int32_t* out_coloc_more_status;    /* [k] GAUSS_ST_SUSIE_NOCONV / GAUSS_ST_SUSIE_NOFIT           optional              */
+    double*  out_coloc_pp;             /* [pairs][L][L][5], pairs = (k + 1) k / 2                    optional              */
+    int32_t* out_coloc_hit;            /* [pairs][L][L] candidate index, -1: none                    optional              */
+    double*  out_coloc_hit_pp;         /* [pairs][L][L]                                              optional              */
+    int32_t* out_coloc_n;              /* [pairs] candidates admissible in both fits                 optional              */
     /* ---- raw LD export (prep_qcat prep_qcat.cpp:104-132, prep_recessive_impute prep_qcatmix.cpp:136-221) ----
      * kind = GAUSS_WIN_LD stops after the LD step: out_b11 = B11 (diagonal 1 + lambda; pass lambda = 0 for
      * the reference's 1.0) and out_b21 = the LD of the geno_u rows against the measured rows; no z1 needed.
@@ -331,6 +382,7 @@ typedef struct gauss_window_desc {
 #define GAUSS_SLCT_MAX 32
 #define GAUSS_SUSIE_MAX_L 32
 #define GAUSS_SUSIE_MAX_SWEEPS 1000
+#define GAUSS_SUSIE_TRAITS_MORE_MAX 7   /* further traits in one fit: eight traits, 28 pairs at the most */
 #define GAUSS_TRAITS_MORE_MAX 63
 #define GAUSS_TRAITS_MISS_MAX 32        /* missing SNPs per further trait and window */
 #define GAUSS_TRAITS_MISS_UNION_MAX 128 /* distinct missing SNPs per window          */

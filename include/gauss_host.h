@@ -263,6 +263,32 @@ int gauss_host_distmix_susie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t 
                              const char* reference_data_file, const char* reference_pop_desc_file,
                              double af1_cutoff, int L, double coverage, double prior_var, double min_abs_corr, int max_sweeps,
                              double tol, int estimate_prior_var, int measured_only, gauss_table** out);
+/* Every trait of the window in one multi-causal fit, and the colocalisation of their signals: do two traits share a causal SNP in
+ * this locus, or do they have two different ones in LD?  The arguments of gauss_host_dist_traits / _distmix_traits with 1 .. 7 further
+ * study files (input_file is trait 1 and defines the window; a further file that lacks a measured SNP of the window is refused, as
+ * there), the arguments of gauss_host_dist_susie / _distmix_susie, and coloc's priors p1, p2, p12 (<= 0 or NaN: 1e-4, 1e-4, 1e-5; they
+ * must lie in (0, 1) with p12 <= min(p1, p2)).  The window sets coloc_traits_more = n_more and the coloc_* fields of gauss_window_desc
+ * (include/gauss_hip.h: the definition): all traits are fitted in the same launches, every pair of kept effects of two traits is
+ * colocalised, the imputed SNPs among the candidates.
+ * The table: the rows of *_susie (the call's own, then the wings' measured SNPs); its columns wing pip cs cs_pip for trait 1 with the
+ * same bits as *_susie on the first file; pip_t cs_t cs_pip_t for t = 2 .. 1 + n_more.  Named matrices: z_traits and pval_traits
+ * (as *_traits, on every row); effects_t [L x 7] and fit_t [1 x 3] (the `effects` and `fit` of *_susie) for t = 1 .. 1 + n_more;
+ * coloc, one row per pair of kept effects of two traits: trait_a trait_b (1-based) cs_a cs_b (1-based effects) n H0 H1 H2 H3 H4
+ * hit_row (the table row, from 0, of the most likely shared SNP) hit_pp.  A message per trait whose sweeps ran out or that was not
+ * fitted.  Limits: those of *_susie; eight traits; traits that lack measured SNPs are not fitted. */
+int gauss_host_dist_coloc(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                          const char* study_pop, const char* input_file, const char* reference_index_file,
+                          const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,
+                          const char* const* more_input_files, int n_more, int L, double coverage, double prior_var,
+                          double min_abs_corr, int max_sweeps, double tol, int estimate_prior_var, int measured_only,
+                          double p1, double p2, double p12, gauss_table** out);
+int gauss_host_distmix_coloc(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                             const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                             const char* input_file, const char* reference_index_file,
+                             const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,
+                             const char* const* more_input_files, int n_more, int L, double coverage, double prior_var,
+                             double min_abs_corr, int max_sweeps, double tol, int estimate_prior_var, int measured_only,
+                             double p1, double p2, double p12, gauss_table** out);
 /* The chi^2 (1 df) threshold of a two-sided p-value: the smallest double chi2 with 2 pnorm(-sqrt(chi2)) < p in the library's own
  * normal tail, found by bisection on the bit pattern -- monotone in p, and exact to the last bit that changes the comparison.
  * p must be positive. */

@@ -125,8 +125,9 @@ def trace_times(rows, steps):
     return res
 
 
-def _child(args, limit, prefix=()):
-    cmd = list(prefix) + [sys.executable, os.path.abspath(__file__)] + args
+def _child(args, limit, prefix=(), script=None):
+    """script: the probe whose child this is (tools/coloc_probe.py starts its own through here)"""
+    cmd = list(prefix) + [sys.executable, os.path.abspath(script or __file__)] + args
     # a session of its own: under the profiler the process that holds the GPU is a grandchild, and the time limit ends the whole group
     pr = subprocess.Popen(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, start_new_session=True)
     try:
