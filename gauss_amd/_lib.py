@@ -31,6 +31,7 @@ ST_SUSIE_NOFIT = 32      # GAUSS_ST_SUSIE_NOFIT
 SUSIE_MAX_L = 32         # GAUSS_SUSIE_MAX_L
 SUSIE_MAX_SWEEPS = 1000  # GAUSS_SUSIE_MAX_SWEEPS
 SUSIE_TRAITS_MORE_MAX = 7  # GAUSS_SUSIE_TRAITS_MORE_MAX
+XS_MAX = 4               # GAUSS_XS_MAX
 CODE_ADDITIVE, CODE_DOMINANT, CODE_RECESSIVE = 1, 2, 4
 GRAM_F32 = 0
 GRAM_I8 = 1
@@ -47,6 +48,7 @@ class WindowDesc(C.Structure):
         ("geno_m", _u8p), ("geno_u", _u8p), ("ld", C.c_int64), ("z1", _dp),
         ("lambda_", C.c_double), ("min_abs_eig", C.c_double),
         ("out_z", _dp), ("out_info", _dp), ("out_status", _ip), ("out_b11", _dp), ("out_b21", _dp),
+        ("xs_group", C.c_int), ("xs_from_lead", _ip), ("out_xs_V", _dp), ("out_xs_purity", _dp), ("out_xs_mu", _dp), ("out_xs_n", _ip),
         ("kind", C.c_int), ("n_head_measured", C.c_int), ("n_pred_measured", C.c_int), ("eig_cutoff", C.c_double),
         ("out_r", _dp), ("out_num_eig", _ip),
         ("coloc_traits_more", C.c_int), ("coloc_p1", C.c_double), ("coloc_p2", C.c_double), ("coloc_p12", C.c_double),

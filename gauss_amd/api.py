@@ -48,7 +48,7 @@ HOST_SYMBOLS = [
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
-    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
+    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_xsusie", "gauss_host_distmix_xsusie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
     "gauss_host_dist_traits", "gauss_host_distmix_traits", "gauss_host_dist_traits_miss", "gauss_host_distmix_traits_miss",
 ]
 
@@ -148,6 +148,9 @@ def load_host():
     susie_tail = [C.c_int, _dbl, _dbl, _dbl, C.c_int, _dbl, C.c_int, C.c_int, C.POINTER(_vp)]      # L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only, out
     h.gauss_host_dist_susie.argtypes = h.gauss_host_dist.argtypes[:-1] + susie_tail
     h.gauss_host_distmix_susie.argtypes = h.gauss_host_distmix.argtypes[:-1] + susie_tail
+    files_tail = [C.c_char_p, C.c_char_p, C.c_char_p, _dbl]                  # index, data, description, af1_cutoff
+    h.gauss_host_dist_xsusie.argtypes = h.gauss_host_dist.argtypes[:5] + [_strs, _strs, C.c_int] + files_tail + susie_tail
+    h.gauss_host_distmix_xsusie.argtypes = h.gauss_host_distmix.argtypes[:8] + [_strs, C.c_int] + files_tail + susie_tail
     traits_tail = [_strs, C.c_int, C.POINTER(_vp)]                           # more_input_files, n_more, out
     h.gauss_host_dist_traits.argtypes = h.gauss_host_dist.argtypes[:-1] + traits_tail
     h.gauss_host_distmix_traits.argtypes = h.gauss_host_distmix.argtypes[:-1] + traits_tail
@@ -508,6 +511,62 @@ def distmix_susie(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, refe
     return _susie_frame(*_window_call("gauss_host_distmix_susie", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
                         (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
                         _susie_args(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only)))
+
+
+def _xsusie_frame(h, out, K):
+    named = _named(h, out)
+    df = _table(h, out)[0]                                 # (frees the table: nothing may fail between the two reads and this)
+    e = np.asarray(named["effects"], dtype=np.float64).reshape(-1, 2 * K + 5)
+    df.attrs["effects"] = dict(row=e[:, 0].astype(np.int64), V=e[:, 1:1 + K].T.copy(), purity=e[:, 1 + K:1 + 2 * K].T.copy(), lse=e[:, 1 + 2 * K].copy(),
+                               size=e[:, 2 + 2 * K].astype(np.int64), mass=e[:, 3 + 2 * K].copy(), kept=e[:, 4 + 2 * K] != 0)
+    f = np.asarray(named["fit"], dtype=np.float64).reshape(-1)
+    df.attrs["fit"] = dict(sweeps=int(f[0]), delta=float(f[1]), converged=bool(f[2]))
+    return df
+
+
+def dist_xsusie(chr, start_bp, end_bp, wing_size, study_pops, input_files, reference_index_file, reference_data_file,
+                reference_pop_desc_file, af1_cutoff=None, L=None, coverage=None, prior_var=None, min_abs_corr=None, max_sweeps=None, tol=None,
+                estimate_prior_var=None, measured_only=False, ctx=None):
+    """Joint fine-mapping of one trait across 2 .. 4 studies of different populations (gauss_host_dist_xsusie): one shared causal SNP
+    per effect, each study's own LD (study_pops[k]) and effect size -- a tag SNP one ancestry cannot tell from the causal SNP is often
+    only loosely linked to it in another.  input_files[k] is study k's GWAS; study 1 leads.  The frame is dist_susie()'s of study 1 with
+    the joint pip, cs, cs_pip and a column joint (1: the SNP is a candidate of every study) appended; frame.attrs["effects"] =
+    dict(row, V [K, L], purity [K, L], lse, size, mass, kept), frame.attrs["fit"] as dist_susie.  The fit's arguments are dist_susie's.
+    Limits: the candidates are an intersection over the studies; residual variance 1; uniform prior; a set is reported when it is pure
+    in at least one study; a group in which MakePosDef repairs any study's window is not fitted (a message says which)."""
+    h = load_host()
+    K = len(input_files)
+    if len(study_pops) != K:
+        raise ValueError("one study population per input file")
+    out = _vp()
+    pops, files = (C.c_char_p * K)(*[_enc(p) for p in study_pops]), (C.c_char_p * K)(*[_enc(f) for f in input_files])
+    _hcheck(h.gauss_host_dist_xsusie(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), pops, files, K, _enc(reference_index_file),
+                                     _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
+                                     *_susie_args(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only), C.byref(out)))
+    return _xsusie_frame(h, out, K)
+
+
+def distmix_xsusie(chr, start_bp, end_bp, wing_size, pop_wgt_dfs, input_files, reference_index_file, reference_data_file,
+                   reference_pop_desc_file, af1_cutoff=None, L=None, coverage=None, prior_var=None, min_abs_corr=None, max_sweeps=None, tol=None,
+                   estimate_prior_var=None, measured_only=False, ctx=None):
+    """Joint fine-mapping of one trait across 2 .. 4 studies of different ancestry mixes (gauss_host_distmix_xsusie): pop_wgt_dfs[k] is
+    study k's weights as distmix() takes them, over the same population names in the same order; the rest as dist_xsusie with af1mix."""
+    h = load_host()
+    K = len(input_files)
+    if len(pop_wgt_dfs) != K:
+        raise ValueError("one set of ancestry weights per input file")
+    parts = [_pop_wgt(p) for p in pop_wgt_dfs]
+    names, n = parts[0][0], parts[0][2]
+    if any(list(p[0]) != list(names) or p[2] != n for p in parts[1:]):
+        raise ValueError("the studies' weights must name the same populations in the same order")
+    w = np.ascontiguousarray(np.stack([np.asarray(p[1], dtype=np.float64) for p in parts]))
+    out = _vp()
+    files = (C.c_char_p * K)(*[_enc(f) for f in input_files])
+    _hcheck(h.gauss_host_distmix_xsusie(_ctx(ctx), int(chr), int(start_bp), int(end_bp), int(wing_size), names, w.ctypes.data_as(_dp), n, files, K,
+                                        _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
+                                        *_susie_args(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only),
+                                        C.byref(out)))
+    return _xsusie_frame(h, out, K)
 
 
 def slct_chi2(p):

@@ -45,6 +45,8 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.out.more_alpha = d.out_coloc_more_alpha; w.out.more_mu = d.out_coloc_more_mu; w.out.more_lbf = d.out_coloc_more_lbf;
     w.out.more_sweeps = d.out_coloc_more_sweeps; w.out.more_status = d.out_coloc_more_status;
     w.out.coloc_pp = d.out_coloc_pp; w.out.coloc_hit = d.out_coloc_hit; w.out.coloc_hit_pp = d.out_coloc_hit_pp; w.out.coloc_n = d.out_coloc_n;
+    w.xs_group = d.xs_group; w.xs_from_lead = d.xs_from_lead;
+    w.out.xs_V = d.out_xs_V; w.out.xs_purity = d.out_xs_purity; w.out.xs_mu = d.out_xs_mu; w.out.xs_n = d.out_xs_n;
     return w;
 }
 extern "C" {
@@ -198,6 +200,8 @@ int gauss_job_stats(gauss_job* job, double* out4)
 int gauss_impute_window(gauss_ctx* ctx, const gauss_window_desc* win)
 {
     if (!ctx || !win) return fail(GAUSS_E_INVALID, "bad arguments to gauss_impute_window");
+    if (win->xs_group != 0)
+        return fail(GAUSS_E_INVALID, "xs_group = %d: a group of the joint fit across studies is two or more windows of one job (gauss_job_create)", win->xs_group);
     // Streamed form (default): upload and compute overlap (job_run_streamed).  It covers the windows the drivers make --
     // contiguous host matrices, additive coding, something to solve; the clamp path re-reads the job's buffers and works
     // on either form.  GAUSS_STREAM_WINDOW=0 (or GAUSS_FUSED_SOLVE=0): upload everything, then run.

@@ -151,6 +151,13 @@ struct Prob {
     int susie_lbf, coloc;                  // flags; lbf: the section holds the final lbf rows of every fitted trait; coloc: the pairs are asked
     double coloc_p1, coloc_p2, coloc_p12;  // prior probabilities that a SNP is causal for the first trait only, the second only, both
     GP(double) out_susie_more;             // [susie_more_layout(M + U, L, am, lbf, susie_k, coloc).count]
+    // joint fine-mapping across the windows of a group, one study each (k_xsusie.hip); xs_n = 0: the window is in no group
+    int xs_n, xs_pos;                      // studies K of the group (2 .. XS_MAX) and this window's place among them (0: the leader)
+    int xs_peer[4];                        // the group's windows in job order, as indices into the job's descriptors ([0]: the leader)
+    int xs_mu;                             // flag, on the leader: the section holds every study's mu
+    GP(const int) xs_from_lead;            // [T_lead] leader candidate -> this window's candidate, -1: not one; null: the same index (the leader; a peer of equal M and U)
+    GP(const int) xs_to_lead;              // [M + U] this window's candidate -> leader candidate, -1: none; null with xs_from_lead
+    GP(double) out_xs;                     // the leader's: [xs_layout(K, L, T_lead, xs_mu).count]
     // further traits on the same window (k_traits.hip); traits_T = 0: not asked
     int traits_T;                          // T <= TRAITS_MAX further Z-score vectors
     GP(const double) traits_Z;             // [Mld][T16] their Z-scores, SNP-major, zero beyond M and T (T16 = T rounded up to 16)
@@ -179,6 +186,8 @@ inline void clear_riders(Prob& q)
     q.susie_coverage = q.susie_prior_var = q.susie_tol = q.susie_min_abs_corr = 0.0;
     q.susie_ws = nullptr; q.susie_mem = nullptr; q.out_susie = nullptr;
     q.susie_k = q.susie_lbf = q.coloc = 0; q.coloc_p1 = q.coloc_p2 = q.coloc_p12 = 0.0; q.out_susie_more = nullptr;
+    q.xs_n = q.xs_pos = q.xs_mu = 0; q.xs_peer[0] = q.xs_peer[1] = q.xs_peer[2] = q.xs_peer[3] = 0;
+    q.xs_from_lead = q.xs_to_lead = nullptr; q.out_xs = nullptr;
     q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr;
     q.miss_E = q.miss_nm = q.miss_n = 0; q.miss_tab = nullptr;
     q.miss_YE = q.miss_AE = q.miss_YU = q.miss_LD = q.out_traits_info = q.out_traits_miss = nullptr;
@@ -208,6 +217,7 @@ constexpr int SUSIE_RR = 8;            // rows of R b = [B v ; C v] a workgroup 
 constexpr int SUSIE_P = 128;           // members of a set the purity looks at
 constexpr int SUSIE_PG = 32;           // workgroups that share the pairs of one set's purity
 constexpr int SUSIE_K = 7;             // GAUSS_SUSIE_TRAITS_MORE_MAX: further traits in one fit; (SUSIE_K + 1) SUSIE_K / 2 = 28 pairs at the most
+constexpr int XS_MAX = 4;              // GAUSS_XS_MAX: studies (windows) in one group of the joint fit (k_xsusie.hip)
 constexpr int susie_uld(int U) { return (U + 63) & ~63; }   // row pitch of W and Y
 // Prob::susie_ws in doubles.  Y = X C^T and W = X^T Y = B11^-1 B12 [Mld][uld], the window's; then one block per fitted trait (trait t
 // of 0 .. susie_k at t * trait doubles further on): zhat, d, adm [tld] per candidate; alpha, mu, rb (R b_l) and lbf [L][tld]; f [tld];
@@ -237,13 +247,13 @@ constexpr SusieWs susie_ws(int M, int U, int Mld, int L, bool w)
 // A window's doubles in the job's result block, in this order and nowhere else written down:
 //     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, traits_info [T][U], traits_miss [2][n_miss]]
 //     [, the selection] [, cond_z[U], cond_var[U]] [, cs: size[K], mass[K], lse[K], pip[M+U], set[M+U], set_pip[M+U]]
-//     [, susie: susie_layout] [, susie_more: susie_more_layout]
+//     [, susie: susie_layout] [, susie_more: susie_more_layout] [, xs: xs_layout]
 // Offsets in doubles from the window's Plan::res_off; a section nobody asked for takes nothing and its offset is that of the next.
 // traits_info and traits_miss exist when the window passed a mask (miss): n_miss = its set bits.  The conditional section
 // (cond; k_cond.hip), behind it the credible sets (cs; k_cs.hip), behind them the multi-causal fit (susie; k_susie.hip) and what it holds beyond trait 1's
 // values (susie_more; the further traits' fits, the lbf rows, the colocalisation of k_coloc.hip) are the last: every other offset is
-// what it is without them.
-struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, susie_more, count; };
+// what it is without them.  The leader of a group of the joint fit across studies (xs; k_xsusie.hip) has one more section behind them.
+struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, susie_more, xs, count; };
 // Inside the selection's section, from its start: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] (indices, n and the
 // skipped flag travel as exact doubles).  The host and slct_kernel both read it here.
 struct SlctLayout { size_t n, skipped, idx, zin, joint, zc, var, count; };
@@ -278,9 +288,18 @@ constexpr SusieMoreLayout susie_more_layout(int T, int L, bool am, bool lbf, int
     const size_t pp = lt + (size_t)k * one, ll = (size_t)L * L, np = coloc ? (size_t)(k + 1) * k / 2 : 0;
     return {0, lt, one, fit, pp, pp + 5 * np * ll, pp + 6 * np * ll, pp + 7 * np * ll, pp + 7 * np * ll + np};
 }
+// The leader's section of the joint fit across the K studies of a group, from its start: V [K][L] and purity [K][L] per study and
+// effect, n = the joint admissible candidates (an exact double); with mu, every study's mu [K][L][T] in the leader's candidate order
+// (T = the leader's M + U).  The joint pip / set / alpha / lse / sizes are the leader's susie_layout.
+struct XsLayout { size_t V, purity, n, mu, count; };
+constexpr XsLayout xs_layout(int K, int L, int T, bool mu)
+{
+    const size_t kl = (size_t)K * L;
+    return {0, kl, 2 * kl, 2 * kl + 1, 2 * kl + 1 + (mu ? kl * T : 0)};
+}
 constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, bool miss = false, int n_miss = 0, bool cond = false,
                                bool cs = false, int susie_L = 0, bool susie_am = false, bool susie_lbf = false, int susie_k = 0,
-                               bool coloc = false)
+                               bool coloc = false, int xs_K = 0, bool xs_mu = false)
 {
     const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_tinfo = o_traits + (size_t)T * U;
     const size_t o_tmiss = o_tinfo + (miss ? (size_t)T * U : 0), o_slct = o_tmiss + (miss ? 2 * (size_t)n_miss : 0);
@@ -288,8 +307,9 @@ constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, 
     const size_t o_cs = o_cond + (cond ? 2 * (size_t)U : 0);
     const size_t o_susie = o_cs + (cs ? cs_layout(M + U, K).count : 0);
     const size_t o_more = o_susie + (susie_L ? susie_layout(M + U, susie_L, susie_am).count : 0);
-    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie, o_more,
-            o_more + (susie_L ? susie_more_layout(M + U, susie_L, susie_am, susie_lbf, susie_k, coloc).count : 0)};
+    const size_t o_xs = o_more + (susie_L ? susie_more_layout(M + U, susie_L, susie_am, susie_lbf, susie_k, coloc).count : 0);
+    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie, o_more, o_xs,
+            o_xs + (xs_K ? xs_layout(xs_K, susie_L, M + U, xs_mu).count : 0)};
 }
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
@@ -417,6 +437,19 @@ void launch_susie_w(const Prob* d_probs, const int* d_susiemap, int n, int max_n
 void launch_susie(const Prob* d_probs, const int* d_susiemap, int n, int max_M, int max_T, int max_L, int max_sweeps, int max_k, bool coloc,
                   hipStream_t s);
 void launch_coloc(const Prob* d_probs, const int* d_susiemap, int n, int max_L, int max_k, hipStream_t s);
+// single launches of the fit's kernels (k_susie.hip) over the windows of a map, for the joint fit across studies to reuse them as they
+// are: the state; R bbar_l and f of one (sweep, l); the sets' membership and their top members; the fold into pip / set / set_pip
+void launch_susie_prep(const Prob* d_probs, const int* d_map, int n, hipStream_t s);
+void launch_susie_rb(const Prob* d_probs, const int* d_map, int n, int max_T, int sweep, int l, hipStream_t s);
+void launch_susie_sets(const Prob* d_probs, const int* d_map, int n, int max_L, hipStream_t s);
+void launch_susie_fold(const Prob* d_probs, const int* d_map, int n, int max_T, hipStream_t s);
+// joint fine-mapping across the studies of a group (k_xsusie.hip).  d_xsmap: the n windows that are members of a group; d_xsleadmap:
+// the n_lead leaders among them.  Queued where launch_susie is (their W by launch_susie_w over d_xsmap where the ungrouped W is
+// formed): the members' state, max_sweeps x max_L x 2 step launches (xsusie_ser_v_kernel over the members, susie_rb_kernel over the
+// members), then the leaders' sets, every member's purity of the leader's top members, the leaders' kept / outputs and fold.
+// max_M / max_T / max_L / max_sweeps: the largest among the members
+void launch_xsusie(const Prob* d_probs, const int* d_xsmap, int n, const int* d_xsleadmap, int n_lead, int max_M, int max_T, int max_L,
+                   int max_sweeps, hipStream_t s);
 // further traits (k_traits.hip).  launch_traits_weights: G = X^T (X Z) of the windows that asked, d_map = (window, 64-row block of X),
 // two launches (Y = X Z, then G = X^T Y); it runs where launch_loo runs.  launch_traits_impute: out_traits = B21 G / sqrt(out_info),
 // d_umap = (window, strip of 64 unmeasured SNPs); it runs behind the kernel that writes out_info

@@ -250,6 +250,8 @@ struct RiderOuts {
     int32_t *more_set = nullptr, *more_size = nullptr, *more_kept = nullptr, *more_status = nullptr;
     double *coloc_pp = nullptr, *coloc_hit_pp = nullptr;
     int32_t *coloc_hit = nullptr, *coloc_n = nullptr;
+    double *xs_V = nullptr, *xs_purity = nullptr, *xs_mu = nullptr;      // the joint fit across studies, on a group's leader (gauss_window_desc.out_xs_*)
+    int32_t* xs_n = nullptr;
     double* z_more = nullptr;
     double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
 };
@@ -294,6 +296,10 @@ struct Plan {
         bool susie_am = false;               // ... and its result section holds alpha and mu (out_susie_alpha / out_susie_mu ask)
         int susie_k = 0;                     // ... further traits fitted beside z1 (gauss_window_desc.coloc_traits_more)
         bool susie_lbf = false, coloc = false;      // ... the lbf rows are asked; the colocalisation of the traits' pairs is (k_coloc.hip)
+        int xs_group = 0;                    // joint fit across studies (k_xsusie.hip): the group's id; 0: the window is in no group
+        int xs_K = 0, xs_pos = 0, xs_lead = 0;      // ... the group's windows, this one's place among them (0: the leader), the leader's index in the job
+        bool xs_mu = false;                  // ... the leader's section holds every study's mu (out_xs_mu asks)
+        std::vector<int> xs_from_lead, xs_to_lead;  // ... Prob::xs_from_lead / xs_to_lead; empty: the same index
         int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
         std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
         bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
@@ -302,7 +308,9 @@ struct Plan {
         RiderOuts out;
         bool needs_fused() const { return loo || traits_T > 0 || susie_L > 0; }      // it reads the rows of L^-1 that only the fused solve forms
     } rd;
-    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs, rd.susie_L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc); }
+    // (a peer of a group keeps its fit's state in the workspace and returns none of it: the joint fit's sections are the leader's)
+    bool xs_peer() const { return rd.xs_group != 0 && rd.xs_pos > 0; }
+    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs, xs_peer() ? 0 : rd.susie_L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc, rd.xs_group && rd.xs_pos == 0 ? rd.xs_K : 0, rd.xs_mu); }
     size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
@@ -365,6 +373,9 @@ struct gauss_job {
     int susie_max_M = 0, susie_max_U = 0, susie_max_T = 0; // ... the largest M, U (of those that fit unmeasured candidates) and M + U among them,
     int susie_max_L = 0, susie_max_sweeps = 0, susie_max_nblk = 0;      // the most effects, sweeps and 64-row blocks of X
     int susie_max_k = 0;  bool susie_coloc = false;        // ... the most further traits in one fit; a window asks for the colocalisation
+    int* d_xsmap = nullptr;     int n_xs = 0;              // joint fit across studies: the windows that are members of a group (they are not in d_susiemap)
+    int* d_xsleadmap = nullptr; int n_xs_lead = 0;         // ... the leaders among them
+    int xs_max_M = 0, xs_max_U = 0, xs_max_T = 0, xs_max_L = 0, xs_max_sweeps = 0, xs_max_nblk = 0;      // ... as susie_max_*, over the members
     int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
     int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
     int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some
@@ -489,6 +500,8 @@ struct WinSpec {
     double susie_coverage = 0.0, susie_prior_var = 0.0, susie_tol = 0.0, susie_min_abs_corr = 0.0;
     int susie_traits_more = 0;               // further traits in the same fit; the colocalisation's priors (all zero: off)
     double coloc_p1 = 0.0, coloc_p2 = 0.0, coloc_p12 = 0.0;
+    int xs_group = 0;                        // joint fit across studies (gauss_window_desc.xs_group / xs_from_lead); 0: off
+    const int32_t* xs_from_lead = nullptr;   // [T_lead] or NULL
     const int32_t* slct_forced = nullptr;
     int n_slct_forced = 0;
     // resampled window (gauss_ld_resampled_rows, simulateLD): pooled LD-only over n_cols samples, of which draw k is sample

@@ -172,6 +172,14 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
     }
     if ((w.out.coloc_pp || w.out.coloc_hit || w.out.coloc_hit_pp || w.out.coloc_n) && !coloc)
         return fail(GAUSS_E_INVALID, "out_coloc_* need coloc_p1, coloc_p2 and coloc_p12");
+    // joint fine-mapping across studies (k_xsusie.hip): what one window can be asked alone; the group itself is job_build's
+    if (w.xs_group < 0) return fail(GAUSS_E_INVALID, "xs_group = %d: a group id is positive (0: off)", w.xs_group);
+    if (w.xs_group > 0 && !susie) return fail(GAUSS_E_INVALID, "xs_group = %d joins the window's multi-causal fit to a group: it needs susie_L > 0", w.xs_group);
+    if (w.xs_group > 0 && w.susie_traits_more > 0)
+        return fail(GAUSS_E_INVALID, "coloc_traits_more = %d in a group (xs_group = %d): a group fits one trait per study", w.susie_traits_more, w.xs_group);
+    if (w.xs_from_lead && w.xs_group <= 0) return fail(GAUSS_E_INVALID, "xs_from_lead maps a group leader's candidates: it needs xs_group > 0");
+    if ((w.out.xs_V || w.out.xs_purity || w.out.xs_mu || w.out.xs_n) && w.xs_group <= 0)
+        return fail(GAUSS_E_INVALID, "out_xs_* are a group leader's outputs: they need xs_group > 0");
     // further traits that lack some measured SNPs (k_traits_miss.hip): the mask as index lists (MissTab)
     std::vector<int> miss_tab;
     int miss_n = 0, miss_nm = 0, miss_ne = 0;
@@ -462,6 +470,7 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         p.susie_k = rd.susie_k; p.susie_lbf = rd.susie_lbf ? 1 : 0; p.coloc = coloc ? 1 : 0;
         p.coloc_p1 = w.coloc_p1; p.coloc_p2 = w.coloc_p2; p.coloc_p12 = w.coloc_p12;
     }
+    rd.xs_group = w.xs_group;
     rd.miss = !miss_tab.empty();
     rd.miss_n = miss_n;
     rd.miss_tab.swap(miss_tab);
@@ -484,6 +493,64 @@ static size_t put(std::vector<char>& blob, Arena& a, const std::vector<T>& v)
     if (!v.empty()) memcpy(blob.data() + o, v.data(), v.size() * sizeof(T));
     return o;
 }
+// The groups of the joint fit across studies (gauss_window_desc.xs_group; k_xsusie.hip): the windows of equal id in job order, the
+// first its leader.  Checks what only the group can be asked (its size, equal susie_* arguments, who may carry outputs, the maps)
+// and leaves every member's place, peers and validated maps in its plan.  No kernel checks a map again.
+static int plan_xs_groups(const std::vector<WinSpec>& specs, std::vector<Plan>& plans)
+{
+    std::map<int, std::vector<int>> groups;
+    for (size_t i = 0; i < specs.size(); i++)
+        if (specs[i].xs_group > 0) groups[specs[i].xs_group].push_back((int)i);
+    for (const auto& kv : groups) {
+        const std::vector<int>& mem = kv.second;
+        const int id = kv.first, K = (int)mem.size(), lead = mem[0];
+        if (K < 2 || K > XS_MAX)
+            return fail(GAUSS_E_INVALID, "xs_group = %d has %d window%s: a group is 2 .. %d windows of one job", id, K, K == 1 ? "" : "s", XS_MAX);
+        const WinSpec& a = specs[(size_t)lead];
+        const int TL = a.M + a.U;
+        if (a.xs_from_lead) return fail(GAUSS_E_INVALID, "window %d: xs_from_lead on the leader of xs_group = %d (the first window of a group has no map)", lead, id);
+        for (int k = 0; k < K; k++) {
+            const int i = mem[(size_t)k];
+            const WinSpec& w = specs[(size_t)i];
+            Plan::Riders& rd = plans[(size_t)i].rd;
+            Prob& p = plans[(size_t)i].p;
+            const char* differs = w.susie_L != a.susie_L ? "susie_L" : w.susie_coverage != a.susie_coverage ? "susie_coverage" :
+                w.susie_prior_var != a.susie_prior_var ? "susie_prior_var" : w.susie_tol != a.susie_tol ? "susie_tol" :
+                w.susie_min_abs_corr != a.susie_min_abs_corr ? "susie_min_abs_corr" : w.susie_max_sweeps != a.susie_max_sweeps ? "susie_max_sweeps" :
+                (w.susie_estimate_var != 0) != (a.susie_estimate_var != 0) ? "susie_estimate_var" :
+                (w.susie_measured_only != 0) != (a.susie_measured_only != 0) ? "susie_measured_only" : nullptr;
+            if (differs) return fail(GAUSS_E_INVALID, "window %d: %s differs from the leader's (window %d): the windows of xs_group = %d share their susie_* arguments", i, differs, lead, id);
+            const RiderOuts& o = w.out;
+            if (k > 0 && (o.susie_pip || o.susie_set || o.susie_set_pip || o.susie_V || o.susie_lse || o.susie_mass || o.susie_purity || o.susie_size ||
+                          o.susie_kept || o.susie_alpha || o.susie_mu || o.susie_sweeps || o.susie_lbf))
+                return fail(GAUSS_E_INVALID, "window %d: out_susie_* on a peer of xs_group = %d: the joint fit is returned on the leader (window %d)", i, id, lead);
+            if (k > 0 && (o.xs_V || o.xs_purity || o.xs_mu || o.xs_n))
+                return fail(GAUSS_E_INVALID, "window %d: out_xs_* on a peer of xs_group = %d: they are the leader's (window %d)", i, id, lead);
+            const int T = w.M + w.U;
+            if (k > 0 && !w.xs_from_lead && (w.M != a.M || w.U != a.U))
+                return fail(GAUSS_E_INVALID, "window %d: xs_from_lead is NULL (the same index) but n_measured / n_unmeasured = %d / %d differ from the leader's %d / %d",
+                            i, w.M, w.U, a.M, a.U);
+            if (w.xs_from_lead) {
+                rd.xs_from_lead.assign(w.xs_from_lead, w.xs_from_lead + TL);
+                rd.xs_to_lead.assign((size_t)T, -1);
+                for (int j = 0; j < TL; j++) {
+                    const int c = rd.xs_from_lead[(size_t)j];
+                    if (c < -1 || c >= T)
+                        return fail(GAUSS_E_INVALID, "window %d: xs_from_lead[%d] = %d is neither -1 nor a candidate of the window (0 .. %d)", i, j, c, T - 1);
+                    if (c >= 0 && rd.xs_to_lead[(size_t)c] >= 0)
+                        return fail(GAUSS_E_INVALID, "window %d: xs_from_lead[%d] = xs_from_lead[%d] = %d: two leader candidates cannot be one SNP", i,
+                                    rd.xs_to_lead[(size_t)c], j, c);
+                    if (c >= 0) rd.xs_to_lead[(size_t)c] = j;
+                }
+            }
+            rd.xs_K = K; rd.xs_pos = k; rd.xs_lead = lead; rd.xs_mu = k == 0 && o.xs_mu != nullptr;
+            p.xs_n = K; p.xs_pos = k; p.xs_mu = rd.xs_mu ? 1 : 0;
+            for (int s = 0; s < XS_MAX; s++) p.xs_peer[s] = mem[(size_t)std::min(s, K - 1)];
+        }
+    }
+    return GAUSS_OK;
+}
+
 // streamed: one window on contiguous host matrices whose upload is left to job_run_streamed (chunk by chunk on the
 // copy stream, overlapped with the pack / Gram launches of the rows that have landed)
 int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, gauss_job** out, const StreamSetup* stream)
@@ -507,6 +574,10 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (rc) return rc;
         job->plans[i].p.gram_i8 = job->gram_i8;
         if (!job->plans[i].draw_col.empty()) job->resample_lds = resample_pack_lds_bytes(job->plans[i].p.row_src_bytes);
+    }
+    {
+        const int rc = plan_xs_groups(specs, job->plans);
+        if (rc) return rc;
     }
     // Matrix exports (gauss_job.h): which matrices the caller wants back, and where each lands in the pinned mirror
     size_t exp_doubles = 0;
@@ -653,7 +724,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<char>& blob = job->h_tab;
     blob.reserve((size_t)n_prob * ((size_t)320 << 10) + ((size_t)64 << 10));      // (~0.3 MB a window: grown in place, not copied over and over)
     const auto tb2 = std::chrono::steady_clock::now();
-    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch, dc, sf, tz, mt; };
+    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch, dc, sf, tz, mt, xf, xt; };
     std::vector<TabOff> to((size_t)n_prob);
     for (int i = 0; i < n_prob; i++) {
         Plan& pl = plan_of(i);
@@ -683,13 +754,15 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         to[i].sf = pl.rd.slct_forced.empty() ? 0 : put(blob, ta, pl.rd.slct_forced);
         to[i].tz = pl.rd.traits_z.empty() ? 0 : put(blob, ta, pl.rd.traits_z);
         to[i].mt = pl.rd.miss_tab.empty() ? 0 : put(blob, ta, pl.rd.miss_tab);
+        to[i].xf = pl.rd.xs_from_lead.empty() ? 0 : put(blob, ta, pl.rd.xs_from_lead);
+        to[i].xt = pl.rd.xs_to_lead.empty() ? 0 : put(blob, ta, pl.rd.xs_to_lead);
     }
     // work lists
     struct ItemH { int prob, pair, group, len, b11, ord = 0; };     // b11: an item of B11 (job-wide pairs, or a window's own measured x measured pairs); ord: launch-order key (below)
     std::vector<ItemH> items;
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
     std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
-    std::vector<int> slctmap, condmap, csmap, susiemap;
+    std::vector<int> slctmap, condmap, csmap, susiemap, xsmap, xsleadmap;
     std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
     job->max_nblk = 0;
     {
@@ -763,7 +836,13 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (rd.slct_K) slctmap.push_back(i);
         if (rd.cond) { condmap.push_back(i); job->cond_max_U = std::max(job->cond_max_U, p.U); }
         if (rd.cs) { csmap.push_back(i); job->cs_max_T = std::max(job->cs_max_T, p.M + p.U); }
-        if (rd.susie_L) {
+        if (rd.susie_L && rd.xs_group) {       // a member of a group of the joint fit across studies: launches and map of its own
+            xsmap.push_back(i);
+            if (rd.xs_pos == 0) xsleadmap.push_back(i);
+            job->xs_max_M = std::max(job->xs_max_M, p.M); job->xs_max_T = std::max(job->xs_max_T, p.M + p.U);
+            job->xs_max_L = std::max(job->xs_max_L, rd.susie_L); job->xs_max_sweeps = std::max(job->xs_max_sweeps, p.susie_max_sweeps);
+            if (!p.susie_measured_only) { job->xs_max_U = std::max(job->xs_max_U, p.U); job->xs_max_nblk = std::max(job->xs_max_nblk, p.nblk); }
+        } else if (rd.susie_L) {
             susiemap.push_back(i);
             job->susie_max_M = std::max(job->susie_max_M, p.M); job->susie_max_T = std::max(job->susie_max_T, p.M + p.U);
             job->susie_max_L = std::max(job->susie_max_L, rd.susie_L); job->susie_max_sweeps = std::max(job->susie_max_sweeps, p.susie_max_sweeps);
@@ -986,6 +1065,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     const size_t o_condmap = condmap.empty() ? 0 : put(blob, ta, condmap);
     const size_t o_csmap = csmap.empty() ? 0 : put(blob, ta, csmap);
     const size_t o_susiemap = susiemap.empty() ? 0 : put(blob, ta, susiemap);
+    const size_t o_xsmap = xsmap.empty() ? 0 : put(blob, ta, xsmap);
+    const size_t o_xsleadmap = xsleadmap.empty() ? 0 : put(blob, ta, xsleadmap);
     const size_t o_traitsmap = traitsmap.empty() ? 0 : put(blob, ta, traitsmap);
     const size_t o_traitsumap = traitsumap.empty() ? 0 : put(blob, ta, traitsumap);
     const size_t o_missmap = missmap.empty() ? 0 : put(blob, ta, missmap);
@@ -1006,6 +1087,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n_cond = (int)condmap.size();
     job->n_cs = (int)csmap.size();
     job->n_susie = (int)susiemap.size();
+    job->n_xs = (int)xsmap.size();
+    job->n_xs_lead = (int)xsleadmap.size();
     job->n_traits = (int)traitsmap.size();
     job->n_traits_u = (int)traitsumap.size();
     job->n_miss_blk = (int)missmap.size();
@@ -1245,10 +1328,13 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.out_cs = pl.rd.cs ? out + lay.cs : nullptr;
         p.cs_lbf = pl.rd.cs ? (double*)(W + w.cs_lbf) : nullptr;
         p.cs_mem = pl.rd.cs ? (uint8_t*)(W + w.cs_mem) : nullptr;
-        p.out_susie = pl.rd.susie_L ? out + lay.susie : nullptr;
-        p.out_susie_more = pl.rd.susie_L && lay.count > lay.susie_more ? out + lay.susie_more : nullptr;
+        p.out_susie = pl.rd.susie_L && !pl.xs_peer() ? out + lay.susie : nullptr;
+        p.out_susie_more = pl.rd.susie_L && lay.xs > lay.susie_more ? out + lay.susie_more : nullptr;
         p.susie_ws = pl.rd.susie_L ? (double*)(W + w.susie_ws) : nullptr;
         p.susie_mem = pl.rd.susie_L ? (uint8_t*)(W + w.susie_mem) : nullptr;
+        p.out_xs = lay.count > lay.xs ? out + lay.xs : nullptr;
+        p.xs_from_lead = pl.rd.xs_from_lead.empty() ? nullptr : (const int*)(T + to[i].xf);
+        p.xs_to_lead = pl.rd.xs_to_lead.empty() ? nullptr : (const int*)(T + to[i].xt);
         p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;
         p.traits_Z = pl.rd.traits_T ? (const double*)(T + to[i].tz) : nullptr;
         p.traits_Y = pl.rd.traits_T ? (double*)(W + w.ty) : nullptr;
@@ -1398,6 +1484,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->d_condmap = (int*)(job->d_tab + o_condmap);
     job->d_csmap = (int*)(job->d_tab + o_csmap);
     job->d_susiemap = (int*)(job->d_tab + o_susiemap);
+    job->d_xsmap = (int*)(job->d_tab + o_xsmap);
+    job->d_xsleadmap = (int*)(job->d_tab + o_xsleadmap);
     job->d_traitsmap = (int2*)(job->d_tab + o_traitsmap);
     job->d_traitsumap = (int2*)(job->d_tab + o_traitsumap);
     job->d_missmap = (int2*)(job->d_tab + o_missmap);

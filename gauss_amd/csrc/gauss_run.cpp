@@ -87,6 +87,7 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 // The tail of a fused solve, in the one order its inputs allow:
 //     loo -> selection -> traits weights -> miss solve -> fine-mapping weights -> closing step -> traits impute -> miss apply
 //         -> conditional -> credible sets -> multi-causal fit (-> colocalisation of its traits, inside launch_susie)
+//         -> joint fit across the studies of a group (k_xsusie.hip: its members' W beside the ungrouped windows', its fit last)
 //   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
 //     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
 //   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
@@ -110,6 +111,7 @@ static void queue_tail(gauss_job* job, hipStream_t st)
     launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
     launch_traits_miss_solve(job->d_probs, job->d_missmap, job->n_miss_blk, job->d_misstmap, job->n_miss_t, st);
     launch_susie_w(job->d_probs, job->d_susiemap, job->n_susie, job->susie_max_nblk, job->susie_max_U, st);
+    launch_susie_w(job->d_probs, job->d_xsmap, job->n_xs, job->xs_max_nblk, job->xs_max_U, st);
     launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
     launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
     launch_traits_miss_apply(job->d_probs, job->d_missumap, job->n_miss_u, st);
@@ -117,6 +119,8 @@ static void queue_tail(gauss_job* job, hipStream_t st)
     launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
     launch_susie(job->d_probs, job->d_susiemap, job->n_susie, job->susie_max_M, job->susie_max_T, job->susie_max_L, job->susie_max_sweeps,
                  job->susie_max_k, job->susie_coloc, st);
+    launch_xsusie(job->d_probs, job->d_xsmap, job->n_xs, job->d_xsleadmap, job->n_xs_lead, job->xs_max_M, job->xs_max_T, job->xs_max_L,
+                  job->xs_max_sweeps, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -687,6 +691,14 @@ int job_fetch(gauss_job* job)
                 { int rc2 = fetch_matrix(pl.out_b21, p.B21, p.U, p.M, p.Mld); if (rc2) return rc2; }
             continue;
         }
+        // a group of the joint fit across studies (k_xsusie.hip) in which ANY window is repaired is not fitted: what the status words
+        // say of every member is known before the first of them is repaired
+        bool xs_nofit = false;
+        if (pl.rd.xs_group)
+            for (int s = 0; s < pl.rd.xs_K; s++) {
+                const int m = p.xs_peer[s];
+                xs_nofit = xs_nofit || (job->plans[m].p.npanel > 0 && (job->h_status[4 * m + 0] || job->h_status[4 * m + 1]));
+            }
         bool clamped = false;
         if (p.npanel > 0 && (job->h_status[4 * i + 0] || job->h_status[4 * i + 1])) {
             int rc = job_clamp_window(job, i, &bits);
@@ -713,7 +725,8 @@ int job_fetch(gauss_job* job)
                     for (int c = 0; c < p.M + p.U; c++) res[lay.cs + cl.set + c] = -1.0;
                 }
             }
-            if (rd.susie_L && (clamped || (bits & GAUSS_ST_NONFINITE))) {
+            if (pl.xs_peer() && (clamped || xs_nofit) && !(bits & GAUSS_ST_NONFINITE)) bits |= GAUSS_ST_SUSIE_NOFIT;
+            if (rd.susie_L && !pl.xs_peer() && (clamped || xs_nofit || (bits & GAUSS_ST_NONFINITE))) {
                 // not fitted: NaN, size 0, kept 0, set -1, no sweep.  A repaired B11 (MakePosDef) is no ground for the fit, and the
                 // clamp path's stand-alone solve forms no rows of the inverse
                 const SusieLayout ql = susie_layout(p.M + p.U, rd.susie_L, rd.susie_am);
@@ -729,6 +742,11 @@ int job_fetch(gauss_job* job)
                 for (int t = 0; t < rd.susie_k; t++) memcpy(mq + ml.trait + (size_t)t * ml.one, sq, sizeof(double) * ql.count);
                 for (size_t u = ml.hit; u < ml.hit_pp; u++) mq[u] = -1.0;
                 for (size_t u = ml.n; u < ml.count; u++) mq[u] = 0.0;
+                if (lay.count > lay.xs) {          // a group's leader: every study's V, purity and mu NaN, no joint candidate
+                    const XsLayout xl = xs_layout(rd.xs_K, rd.susie_L, p.M + p.U, rd.xs_mu);
+                    for (size_t u = 0; u < xl.count; u++) res[lay.xs + u] = NAN;
+                    res[lay.xs + xl.n] = 0.0;
+                }
                 if (!(bits & GAUSS_ST_NONFINITE)) bits |= GAUSS_ST_SUSIE_NOFIT;
             }
             auto copy_out = [](double* dst, const double* src, size_t n) { if (dst) memcpy(dst, src, sizeof(double) * n); };
@@ -770,7 +788,7 @@ int job_fetch(gauss_job* job)
                 if (rd.out.cs_set) for (int c = 0; c < T; c++) rd.out.cs_set[c] = (int32_t)cs[cl.set + c];
                 copy_out(rd.out.cs_set_pip, cs + cl.set_pip, T);
             }
-            if (rd.susie_L) {                      // the multi-causal fit (k_susie.hip)
+            if (rd.susie_L && !pl.xs_peer()) {     // the multi-causal fit (k_susie.hip); for a group's leader the joint fit (k_xsusie.hip)
                 const int L = rd.susie_L, T = p.M + p.U;
                 const SusieLayout ql = susie_layout(T, L, rd.susie_am);
                 const double* const sq = res + lay.susie;
@@ -809,6 +827,14 @@ int job_fetch(gauss_job* job)
                     if (rd.susie_am && o.more_mu) copy_out(o.more_mu + t * lt, tq + ql.mu, lt);
                     if (rd.susie_lbf && o.more_lbf) copy_out(o.more_lbf + t * lt, tq + ml.tlbf, lt);
                     if (o.more_sweeps) copy_out(o.more_sweeps + 2 * (size_t)t, tq + ql.fit, 2);
+                }
+                if (lay.count > lay.xs) {          // a group's leader: what the joint fit holds per study (k_xsusie.hip)
+                    const XsLayout xl = xs_layout(rd.xs_K, L, T, rd.xs_mu);
+                    const double* const xq = res + lay.xs;
+                    copy_out(rd.out.xs_V, xq + xl.V, (size_t)rd.xs_K * L);
+                    copy_out(rd.out.xs_purity, xq + xl.purity, (size_t)rd.xs_K * L);
+                    if (rd.xs_mu) copy_out(rd.out.xs_mu, xq + xl.mu, (size_t)rd.xs_K * lt);
+                    if (rd.out.xs_n) *rd.out.xs_n = (int32_t)xq[xl.n];
                 }
                 if (rd.coloc) {
                     const size_t np = (size_t)(rd.susie_k + 1) * rd.susie_k / 2, ll = (size_t)L * L;

@@ -475,6 +475,124 @@ int gauss_host_distmix_susie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t 
                                     reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
+// dist_xsusie / distmix_xsusie: K studies of one trait on one panel, fitted jointly (gauss_window_desc.xs_group).  Every study's window
+// is built exactly as its own dist() / distmix() call builds it (run_impute), the maps come from the panel SNP each candidate is
+// (xs_build_map), and the K windows run as one job.  The table is study 1's *_susie table with the joint values (xsusie_output).
+struct XsStudy {
+    OneWindow ow;                        // (points into itself: built in place, never moved)
+    std::unique_ptr<gauss_prepared> prep;
+    WindowView v;
+    std::vector<int64_t> key;            // the panel SNP of every candidate, measured first
+    std::vector<int32_t> from_lead;
+    int32_t status = 0;
+};
+static int run_xsusie(gauss_ctx* ctx, const std::vector<CallArgs>& calls, SusieRider& r, gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    const int K = (int)calls.size();
+    if (K < 2 || K > GAUSS_XS_MAX) return herr("n_studies = %d: the joint fit takes 2 .. %d studies", K, GAUSS_XS_MAX);
+    for (const CallArgs& c : calls) if (files_ok({c.input, c.index, c.data, c.desc})) return -1;
+    if (r.check()) return -1;
+    const CallArgs& c0 = calls[0];
+    std::string panel_path;
+    std::shared_ptr<PackedPanel> pk;
+    if (open_panel(c0.index, c0.data, c0.desc, panel_path, pk)) return -1;
+    std::vector<std::unique_ptr<XsStudy>> st;
+    std::vector<gauss_window_desc> d((size_t)K);
+    std::map<std::string, int64_t> snp_no;                                  // chr:bp:rsid -> one number per panel SNP
+    auto key_of = [&](const SnpIdent& id) {
+        const std::string s = std::to_string(id.chr) + ":" + std::to_string(id.bp) + ":" + (id.rsid ? id.rsid : "");
+        return snp_no.emplace(s, (int64_t)snp_no.size()).first->second;
+    };
+    int lean0 = 0;
+    for (int k = 0; k < K; k++) {
+        const CallArgs& c = calls[(size_t)k];
+        st.emplace_back(new XsStudy());
+        XsStudy& s = *st.back();
+        const int lean = one_window_build(s.ow, c, panel_path, pk);         // (0: a lean window; 1: the literal path)
+        if (lean < 0) return -1;
+        if (k == 0) lean0 = lean;
+        else if (lean != lean0) return herr("study %d cannot be built the way study 1 is", k + 1);
+        if (lean) {
+            gauss_prepared* p = nullptr;
+            if (prepare_opened(c, nullptr, panel_path, pk, false, &p)) return -1;
+            s.prep.reset(p);
+        }
+        if (lean ? gauss_prepared_window_desc(s.prep.get(), &d[(size_t)k]) : lean_window_desc(s.ow.w, &d[(size_t)k])) return -1;
+        s.v = lean ? view_of_prepared(*s.prep, c) : view_of_lean(s.ow, *pk, c);
+        XsStudy* sp = &s;
+        const bool is_lean = !lean;
+        s.v.plain = [sp, is_lean](gauss_table** t) { if (!is_lean) return gauss_prepared_finish(sp->prep.get(), t); *t = lean_window_finish(sp->ow.w); return 0; };
+        for (const ViewSnp& m : s.v.measured) s.key.push_back(key_of(m.id));
+        if (lean) for (const Snp* u : s.prep->unmeasured) s.key.push_back(key_of(ident_of(*u)));
+        else for (int32_t vi : s.ow.w.unmeasured) s.key.push_back(key_of(ident_of(*pk, s.ow.w.v[(size_t)vi])));
+        d[(size_t)k].out_status = &s.status;
+    }
+    // the leader asks for the fit; the peers take its arguments and their maps
+    if (r.ask(d[0], st[0]->v)) return -1;
+    const size_t TL = st[0]->key.size(), L = (size_t)r.n_eff;
+    std::vector<double> xs_V((size_t)K * L, NAN), xs_purity((size_t)K * L, NAN);
+    std::vector<uint8_t> joint(TL, 1);
+    d[0].xs_group = 1; d[0].out_xs_V = xs_V.data(); d[0].out_xs_purity = xs_purity.data();
+    for (int k = 1; k < K; k++) {
+        XsStudy& s = *st[(size_t)k];
+        gauss_window_desc& q = d[(size_t)k];
+        q.susie_L = d[0].susie_L; q.susie_coverage = d[0].susie_coverage; q.susie_prior_var = d[0].susie_prior_var; q.susie_tol = d[0].susie_tol;
+        q.susie_min_abs_corr = d[0].susie_min_abs_corr; q.susie_max_sweeps = d[0].susie_max_sweeps;
+        q.susie_estimate_var = d[0].susie_estimate_var; q.susie_measured_only = d[0].susie_measured_only;
+        s.from_lead.assign(TL, -1);
+        if (xs_build_map(st[0]->key.data(), TL, s.key.data(), s.key.size(), s.from_lead.data()) < 0) return -1;
+        for (size_t j = 0; j < TL; j++) if (s.from_lead[j] < 0) joint[j] = 0;
+        q.xs_group = 1; q.xs_from_lead = s.from_lead.data();
+    }
+    int on_device = 0;
+    if (!lean0)
+        for (int k = 0; k < K; k++) { panel_rows(ctx, panel_path, *pk, &d[(size_t)k].geno_m, &on_device); d[(size_t)k].geno_u = d[(size_t)k].geno_m; }
+    gauss_job* job = nullptr;
+    int rc = gauss_job_create(ctx, d.data(), K, on_device, &job);
+    if (rc == 0) rc = gauss_job_run(job);
+    if (rc == 0) rc = gauss_job_fetch(job);
+    if (job) gauss_job_destroy(job);
+    if (rc) return herr("%s", gauss_last_error());
+    if (r.table(st[0]->v, out)) return -1;
+    std::vector<int32_t> status;
+    for (const auto& s : st) status.push_back(s->status);
+    if (xsusie_output(**out, st[0]->v.row_m, st[0]->v.row_u, joint.data(), K, (int)L, xs_V.data(), xs_purity.data(), status.data())) {
+        gauss_table_free(*out); *out = nullptr;
+        return -1;
+    }
+    return 0;
+}
+
+int gauss_host_dist_xsusie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* const* study_pops,
+                           const char* const* input_files, int n_studies, const char* reference_index_file, const char* reference_data_file,
+                           const char* reference_pop_desc_file, double af1_cutoff, int L, double coverage, double prior_var,
+                           double min_abs_corr, int max_sweeps, double tol, int estimate_prior_var, int measured_only, gauss_table** out)
+{
+    if (!study_pops || !input_files) return herr("bad arguments");
+    SusieRider r(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only);
+    std::vector<CallArgs> calls;
+    for (int k = 0; k < n_studies; k++)
+        calls.push_back(call_pop(GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pops[k], input_files[k], reference_index_file,
+                                 reference_data_file, reference_pop_desc_file, af1_cutoff));
+    return run_xsusie(ctx, calls, r, out);
+}
+
+int gauss_host_distmix_xsusie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* const* pop_names,
+                              const double* pop_wgts, int n_pop_wgt, const char* const* input_files, int n_studies,
+                              const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                              double af1_cutoff, int L, double coverage, double prior_var, double min_abs_corr, int max_sweeps, double tol,
+                              int estimate_prior_var, int measured_only, gauss_table** out)
+{
+    if (!pop_names || !pop_wgts || !input_files || n_pop_wgt < 1) return herr("bad arguments");
+    SusieRider r(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only);
+    std::vector<CallArgs> calls;
+    for (int k = 0; k < n_studies; k++)                                    // pop_wgts [n_studies][n_pop_wgt]: study k's weights of the same names
+        calls.push_back(call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts + (size_t)k * n_pop_wgt, n_pop_wgt,
+                                 input_files[k], reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff));
+    return run_xsusie(ctx, calls, r, out);
+}
+
 int gauss_host_dist_coloc(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
                           const char* input_file, const char* reference_index_file, const char* reference_data_file,
                           const char* reference_pop_desc_file, double af1_cutoff, const char* const* more_input_files, int n_more, int L,

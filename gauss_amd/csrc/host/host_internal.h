@@ -555,6 +555,18 @@ int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vecto
 int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const double* pip, const int32_t* set, const double* set_pip, const double* alpha, const double* V,
                  const double* lse, const int32_t* size, const double* mass, const double* purity, const int32_t* kept, const double* sweeps);
+// dist_xsusie / distmix_xsusie, the joint fit across studies.  xs_build_map: plain arrays in, plain array out -- key_lead [n_lead] and
+// key_peer [n_peer] name the panel SNP every candidate of the leader and of a peer is (any 64-bit key that is equal for the same SNP);
+// from_lead [n_lead] gets the peer's candidate index of leader candidate j, -1 where the peer has no such SNP (gauss_window_desc.
+// xs_from_lead).  Returns the number of shared candidates, or -1 (herr) when a study names one SNP twice.
+int xs_build_map(const int64_t* key_lead, size_t n_lead, const int64_t* key_peer, size_t n_peer, int32_t* from_lead);
+// ... and the table: `t` is study 1's susie_output table (the joint pip / cs / cs_pip in its rows); adds the column `joint` (1: the SNP
+// is a candidate of every study; joint [M + U] by leader candidate, row_m / row_u as susie_output takes them), replaces the named
+// matrix `effects` by [L x (2 K + 5)]: table row of the SNP of largest alpha, V_1 .. V_K, purity_1 .. purity_K, lse, size, mass, kept
+// (xs_V / xs_purity [K][L]; the others are columns of susie_output's `effects`), and says which study kept the group from being
+// fitted (status [K]: the windows' GAUSS_ST_* bits)
+int xsusie_output(gauss_table& t, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u, const uint8_t* joint, int K, int L,
+                  const double* xs_V, const double* xs_purity, const int32_t* status);
 // dist_coloc / distmix_coloc: susie_output's rows and its columns wing pip cs cs_pip for trait 1, then pip_t cs_t cs_pip_t for every
 // further fitted trait t = 2 .. 1 + k; traits_output's named matrices over ALL rows (a wing's measured SNP shows its own study z); the
 // named matrices effects_t and fit_t (susie_output's `effects` and `fit`) for t = 1 .. 1 + k; and `coloc`, one row per pair of kept

@@ -430,6 +430,54 @@ int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::ve
     return 0;
 }
 
+int xs_build_map(const int64_t* key_lead, size_t n_lead, const int64_t* key_peer, size_t n_peer, int32_t* from_lead)
+{
+    std::map<int64_t, int32_t> at;
+    for (size_t c = 0; c < n_peer; c++)
+        if (!at.emplace(key_peer[c], (int32_t)c).second)
+            return herr("xs_build_map: candidates %d and %zu of a study are the same panel SNP", (int)at[key_peer[c]], c);
+    std::map<int64_t, int32_t> seen;
+    int shared = 0;
+    for (size_t j = 0; j < n_lead; j++) {
+        if (!seen.emplace(key_lead[j], (int32_t)j).second)
+            return herr("xs_build_map: candidates %d and %zu of the first study are the same panel SNP", (int)seen[key_lead[j]], j);
+        const auto it = at.find(key_lead[j]);
+        from_lead[j] = it == at.end() ? -1 : it->second;
+        shared += it == at.end() ? 0 : 1;
+    }
+    return shared;
+}
+
+int xsusie_output(gauss_table& t, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u, const uint8_t* joint, int K, int L,
+                  const double* xs_V, const double* xs_purity, const int32_t* status)
+{
+    size_t wings = 0;
+    for (int32_t r : row_m) wings += r < 0 ? 1 : 0;
+    const size_t nrow = (size_t)t.nrow(), M = row_m.size();
+    NamedMat* eff = nullptr;
+    for (NamedMat& m : t.named) if (m.name == "effects") eff = &m;
+    if (nrow < wings || !eff || eff->nrow != L || eff->ncol != 7) return herr("xsusie_output: the table is not susie_output's of the same window");
+    Column& jc = t.add("joint", GAUSS_COL_INT);
+    jc.i.assign(nrow, 0);
+    int32_t next = (int32_t)(nrow - wings);                            // susie_output's rows: the wings' SNPs follow the call's own
+    for (size_t i = 0; i < M; i++) jc.i[(size_t)(row_m[i] >= 0 ? row_m[i] : next++)] = joint[i] ? 1 : 0;
+    for (size_t u = 0; u < row_u.size(); u++) if (row_u[u] >= 0) jc.i[(size_t)row_u[u]] = joint[M + u] ? 1 : 0;
+    const size_t l = (size_t)L, nc = 2 * (size_t)K + 5;
+    std::vector<double> e(l * nc), old(eff->d);                       // old, column-major: row, V, lse, size, mass, purity, kept
+    for (size_t a = 0; a < l; a++) {
+        e[a] = old[a];
+        for (int k = 0; k < K; k++) { e[(1 + (size_t)k) * l + a] = xs_V[(size_t)k * l + a]; e[(1 + (size_t)K + k) * l + a] = xs_purity[(size_t)k * l + a]; }
+        e[(2 * (size_t)K + 1) * l + a] = old[2 * l + a]; e[(2 * (size_t)K + 2) * l + a] = old[3 * l + a];
+        e[(2 * (size_t)K + 3) * l + a] = old[4 * l + a]; e[(2 * (size_t)K + 4) * l + a] = old[6 * l + a];
+    }
+    eff->ncol = (int)nc; eff->d = std::move(e);
+    for (int k = 0; k < K; k++)
+        if (status[k] & (GAUSS_ST_CLAMPED | GAUSS_ST_NONFINITE))
+            t.messages.push_back("xsusie: the group was not fitted: the B11 of study " + std::to_string(k + 1) +
+                                 (status[k] & GAUSS_ST_NONFINITE ? " is not finite" : " was repaired by MakePosDef"));
+    return 0;
+}
+
 int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const SusieFit& first, int n_more, const double* z_more, const double* out_z_more, const ColocMore& more)
 {

@@ -50,13 +50,6 @@ namespace gauss {
 static_assert(SUSIE_VR == 2 * SUSIE_NW && SUSIE_RR == 2 * SUSIE_NW, "two rows a wave");
 static_assert(SUSIE_L <= SLCT_K, "cs_set_row's workspace geometry");
 
-__device__ __forceinline__ double susie_lbf(double r, double d, double V)
-{
-    if (V == 0.0) return 0.0;
-    const double vd = V * d;
-    return 0.5 * (r * r * V / (1.0 + vd) - log1p(vd));
-}
-
 // ---- W = X^T (X C^T) ----
 __global__ __launch_bounds__(256) void susie_w_kernel(const Prob* __restrict__ probs, const int* __restrict__ map, int pass)
 {
@@ -283,14 +276,6 @@ __global__ __launch_bounds__(SUSIE_T) void susie_rb_kernel(const Prob* __restric
 }
 
 // ---- sets ----
-// the sweeps the fit ran: what the step that saw it converge wrote down, else all of them
-__device__ __forceinline__ int susie_sweeps_of(const Prob& pb, GP(const double) ctl)
-{
-    const double s = ctl[SUSIE_CTL_SWEEPS];
-    const int n = ctl[SUSIE_CTL_DONE] != 0.0 && s >= 0.0 && s <= (double)pb.susie_max_sweeps ? (int)s : pb.susie_max_sweeps;
-    return __builtin_amdgcn_readfirstlane(n);
-}
-
 __global__ __launch_bounds__(CS_SET_T) void susie_set_kernel(const Prob* __restrict__ probs, const int* __restrict__ map)
 {
     __shared__ double s_row[CS_LDS_T], s_red[CS_SET_NW];
@@ -498,6 +483,29 @@ void launch_susie(const Prob* d_probs, const int* d_susiemap, int n, int max_M, 
     hipLaunchKernelGGL(susie_kept_kernel, dim3(n, 1, nt), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
     if (coloc) launch_coloc(d_probs, d_susiemap, n, max_L, max_k, s);
     hipLaunchKernelGGL(susie_fold_kernel, dim3((max_T + SUSIE_T - 1) / SUSIE_T, n, nt), dim3(SUSIE_T), 0, s, d_probs, d_susiemap);
+}
+
+// Single launches of the kernels above over the windows of a map, trait 0 only: the joint fit across studies (k_xsusie.hip) runs the
+// state, R bbar_l, the sets' membership and the fold as they are, around a single-effect update of its own.
+void launch_susie_prep(const Prob* d_probs, const int* d_map, int n, hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(susie_prep_kernel, dim3(64, n, 1), dim3(SUSIE_T), 0, s, d_probs, d_map);
+}
+void launch_susie_rb(const Prob* d_probs, const int* d_map, int n, int max_T, int sweep, int l, hipStream_t s)
+{
+    if (n > 0 && max_T > 0)
+        hipLaunchKernelGGL(susie_rb_kernel, dim3((max_T + SUSIE_RR - 1) / SUSIE_RR, n, 1), dim3(SUSIE_T), 0, s, d_probs, d_map, sweep, l);
+}
+void launch_susie_sets(const Prob* d_probs, const int* d_map, int n, int max_L, hipStream_t s)
+{
+    if (n <= 0 || max_L <= 0) return;
+    hipLaunchKernelGGL(susie_set_kernel, dim3(max_L, n, 1), dim3(CS_SET_T), 0, s, d_probs, d_map);
+    hipLaunchKernelGGL(susie_rank_kernel, dim3(max_L, n, 1), dim3(SUSIE_T), 0, s, d_probs, d_map);
+}
+void launch_susie_fold(const Prob* d_probs, const int* d_map, int n, int max_T, hipStream_t s)
+{
+    if (n > 0 && max_T > 0)
+        hipLaunchKernelGGL(susie_fold_kernel, dim3((max_T + SUSIE_T - 1) / SUSIE_T, n, 1), dim3(SUSIE_T), 0, s, d_probs, d_map);
 }
 
 }  // namespace gauss

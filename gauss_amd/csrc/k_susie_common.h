@@ -33,6 +33,22 @@ __device__ __forceinline__ SusieTrait susie_trait(const Prob& pb, const SusieWs&
             pb.susie_mem + (size_t)t * L * cs_tld(T), blk, blk + m.tlbf};
 }
 
+// log Bayes factor of a single effect of prior variance V at a candidate of residual score r and variance d
+__device__ __forceinline__ double susie_lbf(double r, double d, double V)
+{
+    if (V == 0.0) return 0.0;
+    const double vd = V * d;
+    return 0.5 * (r * r * V / (1.0 + vd) - log1p(vd));
+}
+
+// the sweeps the fit ran: what the step that saw it converge wrote down, else all of them
+__device__ __forceinline__ int susie_sweeps_of(const Prob& pb, GP(const double) ctl)
+{
+    const double s = ctl[SUSIE_CTL_SWEEPS];
+    const int n = ctl[SUSIE_CTL_DONE] != 0.0 && s >= 0.0 && s <= (double)pb.susie_max_sweeps ? (int)s : pb.susie_max_sweeps;
+    return __builtin_amdgcn_readfirstlane(n);
+}
+
 // max and sum over the workgroup (SUSIE_T threads) in a fixed order: lanes by xor moves, then the waves ascending
 __device__ __forceinline__ double susie_block_max(double x, double* s_red, int tid)
 {

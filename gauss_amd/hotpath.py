@@ -351,10 +351,39 @@ class _Win:
                 desc.out_cs_size, desc.out_cs_mass, desc.out_cs_lse = s["cs_size"].ctypes.data_as(_ip), s["cs_mass"].ctypes.data_as(_dp), s["cs_lse"].ctypes.data_as(_dp)
         # multi-causal fine-mapping (susie_* of gauss_window_desc): susie=dict(L=10, coverage=0.95, prior_var=25.0, tol=1e-4,
         # max_sweeps=100, min_abs_corr=0.5, estimate_var=True, measured_only=False, want_alpha=False)
-        self.susie = None
-        if susie is not None:
+        # group=g (> 0) in that dict joins the window to group g of its job, the joint fit across studies (xs_* of gauss_window_desc):
+        # the job's first window of a group is its leader and carries the joint susie_* and xs_V / xs_purity [K, L] / xs_n (K, the
+        # group's windows, is filled in by Job; want_mu=True adds xs_mu [K, L, T]); a later one is a peer, passes from_lead=[T_lead]
+        # (leader candidate -> its own, -1: absent; None: the same index) and returns no susie_*
+        self.susie = self.xs = None
+        self.xs_role = None if susie is None or not susie.get("group") else susie.get("_role", "leader")
+        if susie is not None and self.xs_role == "peer":
+            self.susie_more = self.coloc = None
+            desc.susie_L = int(susie.get("L", 10))
+            desc.susie_coverage, desc.susie_prior_var = float(susie.get("coverage", 0.95)), float(susie.get("prior_var", 25.0))
+            desc.susie_tol, desc.susie_max_sweeps = float(susie.get("tol", 1e-4)), int(susie.get("max_sweeps", 100))
+            desc.susie_min_abs_corr = float(susie.get("min_abs_corr", 0.5))
+            desc.susie_estimate_var = 1 if susie.get("estimate_var", True) else 0
+            desc.susie_measured_only = 1 if susie.get("measured_only", False) else 0
+            desc.coloc_traits_more = int(susie.get("traits", 0))
+            desc.xs_group = int(susie["group"])
+            if susie.get("from_lead") is not None:
+                self.xs_map = np.ascontiguousarray(susie["from_lead"], dtype=np.int32)
+                desc.xs_from_lead = self.xs_map.ctypes.data_as(_ip)
+        elif susie is not None:
             L, T = int(susie.get("L", 10)), M + U
             Lc = min(max(L, 0), _lib.SUSIE_MAX_L)
+            if self.xs_role == "leader":
+                Kc = min(max(int(susie.get("_K", 2)), 1), _lib.XS_MAX)
+                desc.xs_group = int(susie["group"])
+                x = self.xs = dict(V=np.full((Kc, Lc), np.nan), purity=np.full((Kc, Lc), np.nan), n=np.zeros(1, dtype=np.int32))
+                if susie.get("want_mu"):
+                    x["mu"] = np.full((Kc, Lc, T), np.nan)
+                for key, a in x.items():
+                    setattr(desc, "out_xs_" + key, a.ctypes.data_as(_ip if a.dtype == np.int32 else _dp))
+                if susie.get("from_lead") is not None:      # (refused by the library: a leader has no map)
+                    self.xs_map = np.ascontiguousarray(susie["from_lead"], dtype=np.int32)
+                    desc.xs_from_lead = self.xs_map.ctypes.data_as(_ip)
             q = self.susie = dict(pip=np.full(T, np.nan), set=np.full(T, -1, dtype=np.int32), set_pip=np.full(T, np.nan),
                                   V=np.full(Lc, np.nan), lse=np.full(Lc, np.nan), mass=np.full(Lc, np.nan), purity=np.full(Lc, np.nan),
                                   size=np.zeros(Lc, dtype=np.int32), kept=np.zeros(Lc, dtype=np.int32), sweeps=np.full(2, np.nan))
@@ -496,6 +525,9 @@ class _Win:
                            susie_more_delta=m["sweeps"][:, 1].copy())
             if self.coloc is not None:
                 out.update({"coloc_" + k: v for k, v in self.coloc.items()})
+            if self.xs is not None:
+                out.update({"xs_" + k: v for k, v in self.xs.items() if k != "n"})
+                out["xs_n"] = int(self.xs["n"][0])
         return out
 
 
@@ -669,9 +701,25 @@ class Job:
         z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window).
         miss_more=[T, M] beside it: the SNPs each further trait lacks; the result carries info_more, z_miss, info_miss (impute_window).
         susie=dict(L=, ...[, traits=k][, coloc=dict(p1=, p2=, p12=)]) in a window's dict: its result carries the multi-causal fine-mapping
-        susie_*, of the first k rows of z_more too (susie_more_*), and the colocalisation of their pairs coloc_* (impute_window)."""
+        susie_*, of the first k rows of z_more too (susie_more_*), and the colocalisation of their pairs coloc_* (impute_window).
+        susie=dict(L=, ..., group=g[, from_lead=idx]) in two to four windows' dicts: one joint fit across those studies
+        (include/gauss_hip.h, xs_group); the first of them is the leader, whose result carries the joint susie_* in its candidate
+        order and xs_V / xs_purity [K, L], xs_n (want_mu=True: xs_mu [K, L, T]); the others pass their map and return z / info."""
         self.ctx = ctx or default_context()
         n = len(windows)
+        # who leads each group, and how many windows it has: the leader's buffers are sized by it
+        seen = {}
+        for w in windows:
+            g = (w.get("susie") or {}).get("group")
+            if g:
+                seen[g] = seen.get(g, 0) + 1
+        first = set()
+        windows = [dict(w) for w in windows]
+        for w in windows:
+            g = (w.get("susie") or {}).get("group")
+            if g:
+                w["susie"] = dict(w["susie"], _role="peer" if g in first else "leader", _K=seen[g])
+                first.add(g)
         self.descs = (WindowDesc * n)()
         self.wins = []
         for i, w in enumerate(windows):
@@ -728,3 +776,44 @@ class Job:
             self.close()
         except Exception:
             pass
+
+
+def xs_maps(ids_lead, ids_peer):
+    """Leader candidate -> peer candidate for the joint fit across studies: ids_* are the integer SNP ids of a study's candidates in
+    its own order (measured first, then unmeasured), each id at most once; -1 where the peer does not have the leader's SNP."""
+    ids_lead, ids_peer = np.asarray(ids_lead, dtype=np.int64), np.asarray(ids_peer, dtype=np.int64)
+    if len(np.unique(ids_peer)) != len(ids_peer) or len(np.unique(ids_lead)) != len(ids_lead):
+        raise ValueError("a study names a SNP id twice")
+    order = np.argsort(ids_peer, kind="stable")
+    pos = np.searchsorted(ids_peer[order], ids_lead)
+    pos = np.minimum(pos, len(ids_peer) - 1)
+    hit = ids_peer[order][pos] == ids_lead
+    return np.where(hit, order[pos], -1).astype(np.int32)
+
+
+def fine_map_studies(studies, susie=None, ctx=None, want_mats=False):
+    """One joint fit across 2 .. 4 studies of one trait (include/gauss_hip.h, xs_group): every study is a dict of a window's arguments
+    (mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig]) plus ids_m / ids_u, the integer SNP ids of its measured and
+    unmeasured SNPs.  The first study leads.  Builds the maps from the ids, runs one job and returns the leader's result -- the joint
+    susie_* in the leader's candidate order, xs_V / xs_purity [K, L], xs_n -- with ids (the leader's candidates' ids), joint (True
+    where the SNP is a candidate of every study) and peers (the other windows' results)."""
+    if not 2 <= len(studies) <= _lib.XS_MAX:
+        raise ValueError(f"fine_map_studies takes 2 .. {_lib.XS_MAX} studies, got {len(studies)}")
+    ids = [np.concatenate([np.asarray(s["ids_m"], dtype=np.int64), np.asarray(s["ids_u"], dtype=np.int64)]) for s in studies]
+    wins, joint = [], np.ones(len(ids[0]), dtype=bool)
+    for k, s in enumerate(studies):
+        w = {key: v for key, v in s.items() if key not in ("ids_m", "ids_u")}
+        q = dict(susie or {}, group=1)
+        if k:
+            q["from_lead"] = xs_maps(ids[0], ids[k])
+            joint &= q["from_lead"] >= 0
+        w["susie"] = q
+        wins.append(w)
+    job = Job(wins, ctx=ctx, want_mats=want_mats)
+    try:
+        job.run()
+        res = job.fetch()
+    finally:
+        job.close()
+    out = dict(res[0], ids=ids[0], joint=joint, peers=res[1:])
+    return out

@@ -82,6 +82,50 @@ typedef struct gauss_window_desc {
     int32_t* out_status;      /* [1] GAUSS_ST_* bits                           host pointer        */
     double* out_b11;          /* optional [M x M] B11 incl. lambda (symmetric)  host pointer / NULL */
     double* out_b21;          /* optional [U x M] row-major                     host pointer / NULL */
+    /* ---- joint fine-mapping across studies: one fit over 2 .. GAUSS_XS_MAX windows of one job (needs susie_L > 0) ----
+     * The windows of a job that carry the same xs_group > 0 form a GROUP: one study each (its own populations or weights, its
+     * own measured SNPs and scores), fitted together under the assumption that effect l sits at the SAME SNP in every study,
+     * with its own size in each (the cross-population "sum of single effects" model, SuSiEx / MESuSiE).  Studies k = 1 .. K in
+     * job order; study 1 is the LEADER.  Study k has the per-window quantities of susie_* unchanged, in its own candidate
+     * order (measured first): B_k, C_k, z_k, W_k = B_k^-1 C_k^T, zhat_k, d_k and adm_k.
+     * Candidates: the joint candidates are the leader's candidates that are candidates of every study (a SNP may be measured in
+     * one study and imputed in another).  xs_from_lead of study k maps leader candidate j to study k's candidate index, -1 for
+     * absent; the leader's is NULL; NULL on a peer means the same index and needs equal n_measured and n_unmeasured.  Joint
+     * admissible: every map entry >= 0 and adm_k true in every study (each study's own rules: a non-finite z_k makes that
+     * study's unmeasured SNPs inadmissible; susie_measured_only applies).
+     * Fit (IBSS, Gauss-Seidel over l; every sum in a fixed order: candidates in LEADER order, studies ascending):
+     * V_lk = omega, bbar_lk = 0, f_k = 0.  One step (sweep, l):
+     *   r_k     = zhat_k - (f_k - R_k bbar_lk)                                    per study, own order
+     *   lbf_j   = sum_k ( r_kj^2 V_lk / (1 + V_lk d_kj) - log1p(V_lk d_kj) ) / 2  joint candidates (every V_lk = 0: lbf_j = 0)
+     *   alpha_l = softmax over the admissible joint candidates;  lse_l = max + log(sum / n_adm)
+     *   mu_lkj  = V_lk / (1 + V_lk d_kj) r_kj;  bbar_lk = alpha_l o mu_lk;  f_k and R_k bbar_lk as in susie_*
+     *   susie_estimate_var:  V'_k = sum_j alpha_lj (mu_lkj^2 + s2_kj);  if lse(V'_1 .. V'_K) <= 0 every V_lk = 0 (joint,
+     *                        absorbing), else V_lk = V'_k from the next sweep on
+     * delta, the stop rule, GAUSS_ST_SUSIE_NOCONV, susie_tol = 0 and susie_max_sweeps are those of susie_*.
+     * Sets: membership is that of susie_* on the joint lbf row in leader order.  purity_lk is the deterministic purity of susie_*
+     * of the leader's <= 128 top members, evaluated in study k's LD through its map.  A set is kept when V_lk > 0 for some k,
+     * max_k purity_lk >= susie_min_abs_corr and no kept earlier set has the same members.  (The maximum is this project's
+     * decision: a set is pure if it is tight in at least one ancestry.)  pip, set and set_pip are those of susie_*, from the
+     * shared alpha.
+     * Outputs: the LEADER's out_susie_* carry the joint pip / set / set_pip / lse / mass / size / kept / alpha / sweeps in leader
+     * order; its out_susie_V holds study 1's V, out_susie_purity the maximum, out_susie_mu study 1's mu.  out_xs_* on the leader
+     * only.  A peer returns its own z / info (and whatever else it asks for) as it would alone.
+     * Limits: the candidates are an intersection; residual variance is 1; the prior over the candidates is uniform; K <=
+     * GAUSS_XS_MAX and L <= GAUSS_SUSIE_MAX_L.  A group in which ANY window is repaired by MakePosDef (GAUSS_ST_CLAMPED) or is
+     * GAUSS_ST_NONFINITE is not fitted: the leader's sections get NaN / 0 / -1 and every member GAUSS_ST_SUSIE_NOFIT (a
+     * NONFINITE member keeps that bit instead); every member's other outputs keep their bits.
+     * GAUSS_E_INVALID: a group of one or of more than GAUSS_XS_MAX windows; members that differ in a susie_* argument; a peer
+     * with out_susie_* / out_coloc_lbf or out_xs_* pointers; coloc_traits_more > 0 in a group; xs_from_lead with an entry
+     * outside -1 .. M + U - 1 or one target named twice; a NULL xs_from_lead on a peer whose n_measured / n_unmeasured differ
+     * from the leader's; xs_from_lead on a leader or without xs_group; xs_group < 0 or without susie_L; xs_group in
+     * gauss_impute_window (a group needs a job).  Kernels: k_xsusie.hip; a job without a group launches what it launched before.
+     * (The block sits in front of the QCAT block.) */
+    int xs_group;                  /* 0 = off; equal positive ids in one job form a group, the first window is its leader */
+    const int32_t* xs_from_lead;   /* [M_lead + U_lead] leader candidate -> this window's candidate, -1 = absent; NULL = the same index   host pointer */
+    double*  out_xs_V;             /* [K][L] every study's V                                  leader, optional */
+    double*  out_xs_purity;        /* [K][L] every study's purity                             leader, optional */
+    double*  out_xs_mu;            /* [K][L][M_lead + U_lead] every study's mu, leader order  leader, optional */
+    int32_t* out_xs_n;             /* [1] joint admissible candidates                         leader, optional */
     /* ---- QCAT / QCATMIX windows (run_qcat qcat.cpp:134-262, run_qcatmix qcatmix.cpp:145-286) ----
      * kind = GAUSS_WIN_QCAT tests, for the n_pred_measured measured SNPs of the prediction window
      * (rows n_head_measured .. of geno_m) and then the U unmeasured ones, the Pearson correlation
@@ -381,6 +425,7 @@ typedef struct gauss_window_desc {
 
 #define GAUSS_SLCT_MAX 32
 #define GAUSS_SUSIE_MAX_L 32
+#define GAUSS_XS_MAX 4
 #define GAUSS_SUSIE_MAX_SWEEPS 1000
 #define GAUSS_SUSIE_TRAITS_MORE_MAX 7   /* further traits in one fit: eight traits, 28 pairs at the most */
 #define GAUSS_TRAITS_MORE_MAX 63

@@ -263,6 +263,27 @@ int gauss_host_distmix_susie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t 
                              const char* reference_data_file, const char* reference_pop_desc_file,
                              double af1_cutoff, int L, double coverage, double prior_var, double min_abs_corr, int max_sweeps,
                              double tol, int estimate_prior_var, int measured_only, gauss_table** out);
+/* Joint fine-mapping across studies (gauss_hip.h, xs_group): n_studies = 2 .. GAUSS_XS_MAX GWAS of ONE trait, each with its own study
+ * population (dist_xsusie: study_pops [n_studies]) or its own ancestry weights over the same population names (distmix_xsusie:
+ * pop_wgts [n_studies][n_pop_wgt], row k study k's) and its own file (input_files [n_studies]), on one panel.  Every study's window
+ * is built exactly as its own dist() / distmix() call builds it; a SNP may be measured in one study and imputed in another; the
+ * candidates are those of study 1 that every study has (the panel SNP decides: alleles are already oriented to the panel).  One job
+ * of n_studies windows.  The table is study 1's *_susie table -- its rows, then the measured SNPs of its wings; wing pip cs cs_pip
+ * from the joint fit -- with `joint` appended (1: the SNP is a candidate of every study), the named matrices `effects`
+ * [L x (2 n_studies + 5)] (table row of the SNP of largest alpha, V_1 .. V_K, purity_1 .. purity_K, lse, size, mass, kept) and `fit`
+ * [1 x 3], and a message when the sweeps ran out or when the group was not fitted (MakePosDef repaired some study's B11).  A set is
+ * reported when it is pure in at least one study.  The fit's arguments are those of *_susie. */
+int gauss_host_dist_xsusie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                           const char* const* study_pops, const char* const* input_files, int n_studies,
+                           const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                           double af1_cutoff, int L, double coverage, double prior_var, double min_abs_corr, int max_sweeps,
+                           double tol, int estimate_prior_var, int measured_only, gauss_table** out);
+int gauss_host_distmix_xsusie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                              const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                              const char* const* input_files, int n_studies,
+                              const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                              double af1_cutoff, int L, double coverage, double prior_var, double min_abs_corr, int max_sweeps,
+                              double tol, int estimate_prior_var, int measured_only, gauss_table** out);
 /* Every trait of the window in one multi-causal fit, and the colocalisation of their signals: do two traits share a causal SNP in
  * this locus, or do they have two different ones in LD?  The arguments of gauss_host_dist_traits / _distmix_traits with 1 .. 7 further
  * study files (input_file is trait 1 and defines the window; a further file that lacks a measured SNP of the window is refused, as
