@@ -32,6 +32,8 @@ SUSIE_MAX_L = 32         # GAUSS_SUSIE_MAX_L
 SUSIE_MAX_SWEEPS = 1000  # GAUSS_SUSIE_MAX_SWEEPS
 SUSIE_TRAITS_MORE_MAX = 7  # GAUSS_SUSIE_TRAITS_MORE_MAX
 XS_MAX = 4               # GAUSS_XS_MAX
+ST_PRS_NOCONV = 64       # GAUSS_ST_PRS_NOCONV
+PRS_MAX_S, PRS_MAX_LAM, PRS_MAX_SWEEPS, PRS_MAX_M = 8, 32, 1000, 4096      # GAUSS_PRS_MAX_*
 CODE_ADDITIVE, CODE_DOMINANT, CODE_RECESSIVE = 1, 2, 4
 GRAM_F32 = 0
 GRAM_I8 = 1
@@ -47,6 +49,9 @@ class WindowDesc(C.Structure):
         ("n_measured", C.c_int), ("n_unmeasured", C.c_int),
         ("geno_m", _u8p), ("geno_u", _u8p), ("ld", C.c_int64), ("z1", _dp),
         ("lambda_", C.c_double), ("min_abs_eig", C.c_double),
+        ("prs_n_s", C.c_int), ("prs_n_lam", C.c_int), ("prs_s", _dp), ("prs_lam", _dp), ("prs_n", C.c_double), ("prs_tol", C.c_double),
+        ("prs_max_sweeps", C.c_int), ("out_prs_beta", _dp), ("out_prs_nnz", _ip), ("out_prs_sweeps", _ip), ("out_prs_delta", _dp),
+        ("out_prs_br", _dp), ("out_prs_bg", _dp), ("out_prs_kkt", _dp),
         ("out_z", _dp), ("out_info", _dp), ("out_status", _ip), ("out_b11", _dp), ("out_b21", _dp),
         ("xs_group", C.c_int), ("xs_from_lead", _ip), ("out_xs_V", _dp), ("out_xs_purity", _dp), ("out_xs_mu", _dp), ("out_xs_n", _ip),
         ("kind", C.c_int), ("n_head_measured", C.c_int), ("n_pred_measured", C.c_int), ("eig_cutoff", C.c_double),

@@ -48,7 +48,7 @@ HOST_SYMBOLS = [
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
-    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_xsusie", "gauss_host_distmix_xsusie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
+    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_prs", "gauss_host_distmix_prs", "gauss_host_dist_xsusie", "gauss_host_distmix_xsusie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
     "gauss_host_dist_traits", "gauss_host_distmix_traits", "gauss_host_dist_traits_miss", "gauss_host_distmix_traits_miss",
 ]
 
@@ -148,6 +148,9 @@ def load_host():
     susie_tail = [C.c_int, _dbl, _dbl, _dbl, C.c_int, _dbl, C.c_int, C.c_int, C.POINTER(_vp)]      # L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only, out
     h.gauss_host_dist_susie.argtypes = h.gauss_host_dist.argtypes[:-1] + susie_tail
     h.gauss_host_distmix_susie.argtypes = h.gauss_host_distmix.argtypes[:-1] + susie_tail
+    prs_tail = [_dbl, C.POINTER(_dbl), C.c_int, C.POINTER(_dbl), C.c_int, _dbl, C.c_int, C.POINTER(_vp)]      # n, s, n_s, lam, n_lam, tol, max_sweeps, out
+    h.gauss_host_dist_prs.argtypes = h.gauss_host_dist.argtypes[:-1] + prs_tail
+    h.gauss_host_distmix_prs.argtypes = h.gauss_host_distmix.argtypes[:-1] + prs_tail
     files_tail = [C.c_char_p, C.c_char_p, C.c_char_p, _dbl]                  # index, data, description, af1_cutoff
     h.gauss_host_dist_xsusie.argtypes = h.gauss_host_dist.argtypes[:5] + [_strs, _strs, C.c_int] + files_tail + susie_tail
     h.gauss_host_distmix_xsusie.argtypes = h.gauss_host_distmix.argtypes[:8] + [_strs, C.c_int] + files_tail + susie_tail
@@ -567,6 +570,57 @@ def distmix_xsusie(chr, start_bp, end_bp, wing_size, pop_wgt_dfs, input_files, r
                                         *_susie_args(L, coverage, prior_var, min_abs_corr, max_sweeps, tol, estimate_prior_var, measured_only),
                                         C.byref(out)))
     return _xsusie_frame(h, out, K)
+
+
+def _prs_args(n, s, lam, tol, max_sweeps):
+    """(the call's trailing arguments, the arrays they point into: keep them alive over the call)"""
+    sa = None if s is None else np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+    la = None if lam is None else np.ascontiguousarray(lam, dtype=np.float64).reshape(-1)
+    if (sa is not None and len(sa) == 0) or (la is not None and len(la) == 0):
+        raise ValueError("s and lam are None (lassosum's grid) or lists of at least one value")
+    p = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(_dbl))
+    return (float(n), p(sa), 0 if sa is None else len(sa), p(la), 0 if la is None else len(la), 0.0 if tol is None else float(tol),
+            0 if max_sweeps is None else int(max_sweeps)), (sa, la)
+
+
+def _prs_frame(h, out, per_allele):
+    named = _named(h, out)
+    df = _table(h, out)[0]                                 # (frees the table: nothing may fail between the two reads and this)
+    g = np.asarray(named["grid"], dtype=np.float64).reshape(-1, 9)
+    beta = np.asarray(named["beta"], dtype=np.float64).reshape(g.shape[0], -1)
+    if per_allele:
+        af = df["af1mix" if "af1mix" in df else "af1ref"].to_numpy()
+        beta = beta / np.sqrt(2.0 * af * (1.0 - af))[None, :]
+    df.attrs["beta"] = beta
+    df.attrs["grid"] = dict(s=g[:, 0].copy(), lam=g[:, 1].copy(), nnz=g[:, 2].astype(np.int64), sweeps=g[:, 3].astype(np.int64), delta=g[:, 4].copy(),
+                            br=g[:, 5].copy(), bg=g[:, 6].copy(), kkt=g[:, 7].copy(), converged=g[:, 8] != 0)
+    return df
+
+
+def dist_prs(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
+             reference_pop_desc_file, n, af1_cutoff=None, s=None, lam=None, tol=None, max_sweeps=None, per_allele=False, ctx=None):
+    """Polygenic score weights of a dist() window (gauss_host_dist_prs): lassosum's elastic net on summary statistics, fitted by
+    coordinate descent on the window's own LD over a grid of shrinkage values s and a path of penalties lam (lam = 0: ridge regression,
+    LDpred-inf's estimator).  n: the study's sample size.  s (None: 0.2, 0.5, 0.9, 1; at most 8 values in (0, 1]); lam (None: 20 values
+    log-spaced from 0.1 down to 0.001; at most 32, taken in the order given, each from the solution of the one before); tol (None: 1e-4);
+    max_sweeps (None: 100, at most 1000).  The frame has one row per measured SNP of the extended window: rsid chr bp a1 a2 af1ref z r
+    wing.  frame.attrs["beta"] [n_s n_lam, rows]: the weights of grid cell i_s n_lam + i_lam; frame.attrs["grid"] = dict(s, lam, nnz,
+    sweeps, delta, br, bg, kkt, converged) per cell; the in-sample predicted R^2 of a cell is br^2 / bg.  per_allele=True divides the
+    weights by sqrt(2 af (1 - af)).
+    Limits: weights for measured SNPs only (an imputed SNP adds no information to a score); standardised-genotype units unless
+    per_allele; one trait; the tuning value is the caller's choice (pseudovalidation needs genotypes of the target cohort)."""
+    extra, keep = _prs_args(n, s, lam, tol, max_sweeps)
+    return _prs_frame(*_window_call("gauss_host_dist_prs", (chr, start_bp, end_bp, wing_size), study_pop,
+                      (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx, extra), per_allele)
+
+
+def distmix_prs(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
+                reference_pop_desc_file, n, af1_cutoff=None, s=None, lam=None, tol=None, max_sweeps=None, per_allele=False, ctx=None):
+    """Polygenic score weights of a distmix() window (gauss_host_distmix_prs), on the ancestry-weighted LD: the LD reference a
+    mixed-ancestry cohort otherwise lacks.  Columns as dist_prs with af1mix."""
+    extra, keep = _prs_args(n, s, lam, tol, max_sweeps)
+    return _prs_frame(*_window_call("gauss_host_distmix_prs", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                      (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx, extra), per_allele)
 
 
 def slct_chi2(p):

@@ -46,6 +46,10 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.out.more_sweeps = d.out_coloc_more_sweeps; w.out.more_status = d.out_coloc_more_status;
     w.out.coloc_pp = d.out_coloc_pp; w.out.coloc_hit = d.out_coloc_hit; w.out.coloc_hit_pp = d.out_coloc_hit_pp; w.out.coloc_n = d.out_coloc_n;
     w.xs_group = d.xs_group; w.xs_from_lead = d.xs_from_lead;
+    w.prs_n_s = d.prs_n_s; w.prs_n_lam = d.prs_n_lam; w.prs_s = d.prs_s; w.prs_lam = d.prs_lam; w.prs_n = d.prs_n; w.prs_tol = d.prs_tol;
+    w.prs_max_sweeps = d.prs_max_sweeps;
+    w.out.prs_beta = d.out_prs_beta; w.out.prs_nnz = d.out_prs_nnz; w.out.prs_sweeps = d.out_prs_sweeps; w.out.prs_delta = d.out_prs_delta;
+    w.out.prs_br = d.out_prs_br; w.out.prs_bg = d.out_prs_bg; w.out.prs_kkt = d.out_prs_kkt;
     w.out.xs_V = d.out_xs_V; w.out.xs_purity = d.out_xs_purity; w.out.xs_mu = d.out_xs_mu; w.out.xs_n = d.out_xs_n;
     return w;
 }

@@ -158,6 +158,11 @@ struct Prob {
     GP(const int) xs_from_lead;            // [T_lead] leader candidate -> this window's candidate, -1: not one; null: the same index (the leader; a peer of equal M and U)
     GP(const int) xs_to_lead;              // [M + U] this window's candidate -> leader candidate, -1: none; null with xs_from_lead
     GP(double) out_xs;                     // the leader's: [xs_layout(K, L, T_lead, xs_mu).count]
+    // polygenic score weights of the window (k_prs.hip); prs_n_s = 0: not asked
+    int prs_n_s, prs_n_lam, prs_max_sweeps;      // chains (<= PRS_S), penalties on each chain's path (<= PRS_LAM), sweeps per (s, lam) at the most
+    double prs_n, prs_tol;                 // the study's sample size; a lam is left when delta < prs_tol * r_max
+    double prs_s[8], prs_lam[32];          // [PRS_S], [PRS_LAM] the grid
+    GP(double) out_prs;                    // [prs_layout(M, n_s, n_lam).count]
     // further traits on the same window (k_traits.hip); traits_T = 0: not asked
     int traits_T;                          // T <= TRAITS_MAX further Z-score vectors
     GP(const double) traits_Z;             // [Mld][T16] their Z-scores, SNP-major, zero beyond M and T (T16 = T rounded up to 16)
@@ -188,6 +193,7 @@ inline void clear_riders(Prob& q)
     q.susie_k = q.susie_lbf = q.coloc = 0; q.coloc_p1 = q.coloc_p2 = q.coloc_p12 = 0.0; q.out_susie_more = nullptr;
     q.xs_n = q.xs_pos = q.xs_mu = 0; q.xs_peer[0] = q.xs_peer[1] = q.xs_peer[2] = q.xs_peer[3] = 0;
     q.xs_from_lead = q.xs_to_lead = nullptr; q.out_xs = nullptr;
+    q.prs_n_s = q.prs_n_lam = q.prs_max_sweeps = 0; q.prs_n = q.prs_tol = 0.0; q.out_prs = nullptr;
     q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr;
     q.miss_E = q.miss_nm = q.miss_n = 0; q.miss_tab = nullptr;
     q.miss_YE = q.miss_AE = q.miss_YU = q.miss_LD = q.out_traits_info = q.out_traits_miss = nullptr;
@@ -218,6 +224,11 @@ constexpr int SUSIE_P = 128;           // members of a set the purity looks at
 constexpr int SUSIE_PG = 32;           // workgroups that share the pairs of one set's purity
 constexpr int SUSIE_K = 7;             // GAUSS_SUSIE_TRAITS_MORE_MAX: further traits in one fit; (SUSIE_K + 1) SUSIE_K / 2 = 28 pairs at the most
 constexpr int XS_MAX = 4;              // GAUSS_XS_MAX: studies (windows) in one group of the joint fit (k_xsusie.hip)
+constexpr int PRS_S = 8;               // GAUSS_PRS_MAX_S: chains of a window (Prob::prs_s)
+constexpr int PRS_LAM = 32;            // GAUSS_PRS_MAX_LAM: penalties on a chain's path (Prob::prs_lam)
+constexpr int PRS_MAX_SWEEPS = 1000;   // GAUSS_PRS_MAX_SWEEPS: with it every loop of prs_kernel is bounded
+constexpr int PRS_M_MAX = 4096;        // GAUSS_PRS_MAX_M: beta, g, r and diag(B) of a chain in LDS: 4 M doubles, 128 KB of gfx950's 160
+constexpr int PRS_T = 256;             // threads of prs_kernel: one workgroup per chain
 constexpr int susie_uld(int U) { return (U + 63) & ~63; }   // row pitch of W and Y
 // Prob::susie_ws in doubles.  Y = X C^T and W = X^T Y = B11^-1 B12 [Mld][uld], the window's; then one block per fitted trait (trait t
 // of 0 .. susie_k at t * trait doubles further on): zhat, d, adm [tld] per candidate; alpha, mu, rb (R b_l) and lbf [L][tld]; f [tld];
@@ -247,13 +258,14 @@ constexpr SusieWs susie_ws(int M, int U, int Mld, int L, bool w)
 // A window's doubles in the job's result block, in this order and nowhere else written down:
 //     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, traits_info [T][U], traits_miss [2][n_miss]]
 //     [, the selection] [, cond_z[U], cond_var[U]] [, cs: size[K], mass[K], lse[K], pip[M+U], set[M+U], set_pip[M+U]]
-//     [, susie: susie_layout] [, susie_more: susie_more_layout] [, xs: xs_layout]
+//     [, susie: susie_layout] [, susie_more: susie_more_layout] [, xs: xs_layout] [, prs: prs_layout]
 // Offsets in doubles from the window's Plan::res_off; a section nobody asked for takes nothing and its offset is that of the next.
 // traits_info and traits_miss exist when the window passed a mask (miss): n_miss = its set bits.  The conditional section
 // (cond; k_cond.hip), behind it the credible sets (cs; k_cs.hip), behind them the multi-causal fit (susie; k_susie.hip) and what it holds beyond trait 1's
 // values (susie_more; the further traits' fits, the lbf rows, the colocalisation of k_coloc.hip) are the last: every other offset is
 // what it is without them.  The leader of a group of the joint fit across studies (xs; k_xsusie.hip) has one more section behind them.
-struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, susie_more, xs, count; };
+// The polygenic score weights (prs; k_prs.hip) come behind all of them.
+struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, susie_more, xs, prs, count; };
 // Inside the selection's section, from its start: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] (indices, n and the
 // skipped flag travel as exact doubles).  The host and slct_kernel both read it here.
 struct SlctLayout { size_t n, skipped, idx, zin, joint, zc, var, count; };
@@ -297,9 +309,19 @@ constexpr XsLayout xs_layout(int K, int L, int T, bool mu)
     const size_t kl = (size_t)K * L;
     return {0, kl, 2 * kl, 2 * kl + 1, 2 * kl + 1 + (mu ? kl * T : 0)};
 }
+// Inside the polygenic score's section, from its start: cell [n_s * n_lam][PRS_CELL] = nnz, sweeps, delta, br, bg, kkt, 1 when the
+// sweeps ran out, unused, per grid cell c = i_s * n_lam + i_lam; then beta [n_s * n_lam][M].  nnz, sweeps and the flag travel as
+// exact doubles.  prs_kernel and the host both read it here.
+enum { PRS_NNZ = 0, PRS_SWEEPS, PRS_DELTA, PRS_BR, PRS_BG, PRS_KKT, PRS_NOCONV, PRS_CELL = 8 };
+struct PrsLayout { size_t cell, beta, count; };
+constexpr PrsLayout prs_layout(int M, int n_s, int n_lam)
+{
+    const size_t c = (size_t)n_s * n_lam;
+    return {0, c * PRS_CELL, c * PRS_CELL + c * (size_t)M};
+}
 constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, bool miss = false, int n_miss = 0, bool cond = false,
                                bool cs = false, int susie_L = 0, bool susie_am = false, bool susie_lbf = false, int susie_k = 0,
-                               bool coloc = false, int xs_K = 0, bool xs_mu = false)
+                               bool coloc = false, int xs_K = 0, bool xs_mu = false, int prs_n_s = 0, int prs_n_lam = 0)
 {
     const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_tinfo = o_traits + (size_t)T * U;
     const size_t o_tmiss = o_tinfo + (miss ? (size_t)T * U : 0), o_slct = o_tmiss + (miss ? 2 * (size_t)n_miss : 0);
@@ -308,8 +330,9 @@ constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, 
     const size_t o_susie = o_cs + (cs ? cs_layout(M + U, K).count : 0);
     const size_t o_more = o_susie + (susie_L ? susie_layout(M + U, susie_L, susie_am).count : 0);
     const size_t o_xs = o_more + (susie_L ? susie_more_layout(M + U, susie_L, susie_am, susie_lbf, susie_k, coloc).count : 0);
-    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie, o_more, o_xs,
-            o_xs + (xs_K ? xs_layout(xs_K, susie_L, M + U, xs_mu).count : 0)};
+    const size_t o_prs = o_xs + (xs_K ? xs_layout(xs_K, susie_L, M + U, xs_mu).count : 0);
+    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie, o_more, o_xs, o_prs,
+            o_prs + (prs_n_s ? prs_layout(M, prs_n_s, prs_n_lam).count : 0)};
 }
 
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
@@ -426,6 +449,10 @@ void launch_cond(const Prob* d_probs, const int* d_condmap, int n, int max_U, hi
 // d_probs[0 .. n)); max_T = the most candidates (M + U) one of them has.  They run behind launch_cond's place: behind launch_slct and
 // behind the kernel that writes out_z / out_info
 void launch_cs(const Prob* d_probs, const int* d_csmap, int n, int max_T, hipStream_t s);
+// polygenic score weights (k_prs.hip) of the asking windows (d_prsmap; null: the windows d_probs[0 .. n)): one workgroup per (chain,
+// window), max_s = the most chains, max_M = the most measured SNPs one of them has (the launch's LDS).  B11 in A[0] and z1 are all it
+// reads: it needs no fused solve, and runs at the end of the tail, where nothing waits for it
+void launch_prs(const Prob* d_probs, const int* d_prsmap, int n, int max_s, int max_M, hipStream_t s);
 // multi-causal fine-mapping (k_susie.hip) of the asking windows (d_susiemap; null: the windows d_probs[0 .. n)).  launch_susie_w:
 // W = X^T (X B12) of the windows that fit unmeasured candidates, two launches over (64-row block of X) x (64 unmeasured SNPs); it runs
 // where launch_traits_weights runs (B21 is complete there).  launch_susie: the state, then max_sweeps x max_L x 2 dependent launches

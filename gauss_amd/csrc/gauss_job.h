@@ -252,6 +252,8 @@ struct RiderOuts {
     int32_t *coloc_hit = nullptr, *coloc_n = nullptr;
     double *xs_V = nullptr, *xs_purity = nullptr, *xs_mu = nullptr;      // the joint fit across studies, on a group's leader (gauss_window_desc.out_xs_*)
     int32_t* xs_n = nullptr;
+    double *prs_beta = nullptr, *prs_delta = nullptr, *prs_br = nullptr, *prs_bg = nullptr, *prs_kkt = nullptr;      // polygenic score weights
+    int32_t *prs_nnz = nullptr, *prs_sweeps = nullptr;                                                               // (gauss_window_desc.out_prs_*)
     double* z_more = nullptr;
     double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
 };
@@ -300,6 +302,7 @@ struct Plan {
         int xs_K = 0, xs_pos = 0, xs_lead = 0;      // ... the group's windows, this one's place among them (0: the leader), the leader's index in the job
         bool xs_mu = false;                  // ... the leader's section holds every study's mu (out_xs_mu asks)
         std::vector<int> xs_from_lead, xs_to_lead;  // ... Prob::xs_from_lead / xs_to_lead; empty: the same index
+        int prs_n_s = 0, prs_n_lam = 0;      // polygenic score weights (k_prs.hip): the grid; 0: not asked
         int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
         std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
         bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
@@ -310,7 +313,7 @@ struct Plan {
     } rd;
     // (a peer of a group keeps its fit's state in the workspace and returns none of it: the joint fit's sections are the leader's)
     bool xs_peer() const { return rd.xs_group != 0 && rd.xs_pos > 0; }
-    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs, xs_peer() ? 0 : rd.susie_L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc, rd.xs_group && rd.xs_pos == 0 ? rd.xs_K : 0, rd.xs_mu); }
+    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs, xs_peer() ? 0 : rd.susie_L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc, rd.xs_group && rd.xs_pos == 0 ? rd.xs_K : 0, rd.xs_mu, rd.prs_n_s, rd.prs_n_lam); }
     size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
@@ -368,6 +371,8 @@ struct gauss_job {
     int* d_condmap = nullptr;   int n_cond = 0;            // imputed SNPs conditioned on the selection: the windows that asked
     int cond_max_U = 0;                                    // ... and the most unmeasured SNPs one of them has
     int* d_csmap = nullptr;     int n_cs = 0;              // credible sets: the windows that asked
+    int* d_prsmap = nullptr;    int n_prs = 0;             // polygenic score weights: the windows that asked
+    int prs_max_s = 0, prs_max_M = 0;                      // ... the most chains and the most measured SNPs one of them has
     int cs_max_T = 0;                                      // ... and the most candidates (M + U) one of them has
     int* d_susiemap = nullptr;  int n_susie = 0;           // multi-causal fine-mapping: the windows that asked
     int susie_max_M = 0, susie_max_U = 0, susie_max_T = 0; // ... the largest M, U (of those that fit unmeasured candidates) and M + U among them,
@@ -501,6 +506,9 @@ struct WinSpec {
     int susie_traits_more = 0;               // further traits in the same fit; the colocalisation's priors (all zero: off)
     double coloc_p1 = 0.0, coloc_p2 = 0.0, coloc_p12 = 0.0;
     int xs_group = 0;                        // joint fit across studies (gauss_window_desc.xs_group / xs_from_lead); 0: off
+    int prs_n_s = 0, prs_n_lam = 0, prs_max_sweeps = 0;      // polygenic score weights (gauss_window_desc.prs_*); prs_n_s = 0: off
+    const double *prs_s = nullptr, *prs_lam = nullptr;
+    double prs_n = 0.0, prs_tol = 0.0;
     const int32_t* xs_from_lead = nullptr;   // [T_lead] or NULL
     const int32_t* slct_forced = nullptr;
     int n_slct_forced = 0;

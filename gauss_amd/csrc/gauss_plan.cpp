@@ -120,6 +120,29 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         return fail(GAUSS_E_INVALID, "cs_coverage = %g: the coverage of a credible set lies in (0, 1]", w.cs_coverage);
     if (cs && !(w.cs_prior_var > 0.0 && std::isfinite(w.cs_prior_var)))
         return fail(GAUSS_E_INVALID, "cs_prior_var = %g: the prior variance of the causal SNP's non-centrality is positive and finite", w.cs_prior_var);
+    // polygenic score weights (k_prs.hip)
+    const bool prs = w.prs_n_s != 0;
+    if (prs && !imputes)
+        return fail(GAUSS_E_INVALID, "polygenic score weights (prs_n_s) are for imputation windows only (%s window)", not_imputing);
+    if (prs && (w.prs_n_s < 1 || w.prs_n_s > PRS_S || !w.prs_s))
+        return fail(GAUSS_E_INVALID, "prs_n_s = %d: the score takes 1 .. %d shrinkage values, with their list (prs_s)", w.prs_n_s, PRS_S);
+    if (prs && (w.prs_n_lam < 1 || w.prs_n_lam > PRS_LAM || !w.prs_lam))
+        return fail(GAUSS_E_INVALID, "prs_n_lam = %d: the score takes 1 .. %d penalties, with their list (prs_lam)", w.prs_n_lam, PRS_LAM);
+    for (int a = 0; prs && a < w.prs_n_s; a++)
+        if (!(w.prs_s[a] > 0.0 && w.prs_s[a] <= 1.0))
+            return fail(GAUSS_E_INVALID, "prs_s[%d] = %g: a shrinkage value lies in (0, 1]", a, w.prs_s[a]);
+    for (int a = 0; prs && a < w.prs_n_lam; a++)
+        if (!(w.prs_lam[a] >= 0.0 && std::isfinite(w.prs_lam[a])))
+            return fail(GAUSS_E_INVALID, "prs_lam[%d] = %g: a penalty is finite and not negative", a, w.prs_lam[a]);
+    if (prs && !(w.prs_n > 2.0 && std::isfinite(w.prs_n)))
+        return fail(GAUSS_E_INVALID, "prs_n = %g: the study's sample size is finite and above 2", w.prs_n);
+    if (prs && !(w.prs_tol >= 0.0 && std::isfinite(w.prs_tol)))
+        return fail(GAUSS_E_INVALID, "prs_tol = %g: the stopping tolerance is finite and not negative", w.prs_tol);
+    // (the cap bounds what one window can keep a workgroup busy for: n_lam x max_sweeps sweeps per chain at the most)
+    if (prs && (w.prs_max_sweeps < 1 || w.prs_max_sweeps > PRS_MAX_SWEEPS))
+        return fail(GAUSS_E_INVALID, "prs_max_sweeps = %d: a penalty takes 1 .. %d sweeps", w.prs_max_sweeps, PRS_MAX_SWEEPS);
+    if (prs && w.M > PRS_M_MAX)
+        return fail(GAUSS_E_INVALID, "n_measured = %d: the score (prs_n_s) takes windows of at most %d measured SNPs", w.M, PRS_M_MAX);
     // multi-causal fine-mapping (k_susie.hip)
     const bool susie = w.susie_L != 0;
     if (susie && !imputes)
@@ -443,6 +466,12 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
     rd.cond = cond;
     p.cond_min_var_frac = cond || cs ? w.cond_min_var_frac : 0.0;
     rd.cs = cs;
+    if (prs) {
+        rd.prs_n_s = w.prs_n_s; rd.prs_n_lam = w.prs_n_lam;
+        p.prs_n_s = w.prs_n_s; p.prs_n_lam = w.prs_n_lam; p.prs_max_sweeps = w.prs_max_sweeps; p.prs_n = w.prs_n; p.prs_tol = w.prs_tol;
+        for (int a = 0; a < PRS_S; a++) p.prs_s[a] = a < w.prs_n_s ? w.prs_s[a] : 0.0;
+        for (int a = 0; a < PRS_LAM; a++) p.prs_lam[a] = a < w.prs_n_lam ? w.prs_lam[a] : 0.0;
+    }
     p.cs_coverage = cs ? w.cs_coverage : 0.0;
     p.cs_prior_var = cs ? w.cs_prior_var : 0.0;
     if (susie) {
@@ -762,7 +791,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     std::vector<ItemH> items;
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
     std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
-    std::vector<int> slctmap, condmap, csmap, susiemap, xsmap, xsleadmap;
+    std::vector<int> slctmap, condmap, csmap, susiemap, xsmap, xsleadmap, prsmap;
     std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
     job->max_nblk = 0;
     {
@@ -836,6 +865,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (rd.slct_K) slctmap.push_back(i);
         if (rd.cond) { condmap.push_back(i); job->cond_max_U = std::max(job->cond_max_U, p.U); }
         if (rd.cs) { csmap.push_back(i); job->cs_max_T = std::max(job->cs_max_T, p.M + p.U); }
+        if (rd.prs_n_s) { prsmap.push_back(i); job->prs_max_s = std::max(job->prs_max_s, rd.prs_n_s); job->prs_max_M = std::max(job->prs_max_M, p.M); }
         if (rd.susie_L && rd.xs_group) {       // a member of a group of the joint fit across studies: launches and map of its own
             xsmap.push_back(i);
             if (rd.xs_pos == 0) xsleadmap.push_back(i);
@@ -1064,6 +1094,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     const size_t o_slctmap = slctmap.empty() ? 0 : put(blob, ta, slctmap);      // (a job in which nobody asks takes nothing)
     const size_t o_condmap = condmap.empty() ? 0 : put(blob, ta, condmap);
     const size_t o_csmap = csmap.empty() ? 0 : put(blob, ta, csmap);
+    const size_t o_prsmap = prsmap.empty() ? 0 : put(blob, ta, prsmap);
     const size_t o_susiemap = susiemap.empty() ? 0 : put(blob, ta, susiemap);
     const size_t o_xsmap = xsmap.empty() ? 0 : put(blob, ta, xsmap);
     const size_t o_xsleadmap = xsleadmap.empty() ? 0 : put(blob, ta, xsleadmap);
@@ -1086,6 +1117,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->n_slct = (int)slctmap.size();
     job->n_cond = (int)condmap.size();
     job->n_cs = (int)csmap.size();
+    job->n_prs = (int)prsmap.size();
     job->n_susie = (int)susiemap.size();
     job->n_xs = (int)xsmap.size();
     job->n_xs_lead = (int)xsleadmap.size();
@@ -1332,7 +1364,8 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         p.out_susie_more = pl.rd.susie_L && lay.xs > lay.susie_more ? out + lay.susie_more : nullptr;
         p.susie_ws = pl.rd.susie_L ? (double*)(W + w.susie_ws) : nullptr;
         p.susie_mem = pl.rd.susie_L ? (uint8_t*)(W + w.susie_mem) : nullptr;
-        p.out_xs = lay.count > lay.xs ? out + lay.xs : nullptr;
+        p.out_xs = lay.prs > lay.xs ? out + lay.xs : nullptr;
+        p.out_prs = pl.rd.prs_n_s ? out + lay.prs : nullptr;
         p.xs_from_lead = pl.rd.xs_from_lead.empty() ? nullptr : (const int*)(T + to[i].xf);
         p.xs_to_lead = pl.rd.xs_to_lead.empty() ? nullptr : (const int*)(T + to[i].xt);
         p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;
@@ -1483,6 +1516,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->d_slctmap = (int*)(job->d_tab + o_slctmap);
     job->d_condmap = (int*)(job->d_tab + o_condmap);
     job->d_csmap = (int*)(job->d_tab + o_csmap);
+    job->d_prsmap = (int*)(job->d_tab + o_prsmap);
     job->d_susiemap = (int*)(job->d_tab + o_susiemap);
     job->d_xsmap = (int*)(job->d_tab + o_xsmap);
     job->d_xsleadmap = (int*)(job->d_tab + o_xsleadmap);

@@ -88,6 +88,7 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 //     loo -> selection -> traits weights -> miss solve -> fine-mapping weights -> closing step -> traits impute -> miss apply
 //         -> conditional -> credible sets -> multi-causal fit (-> colocalisation of its traits, inside launch_susie)
 //         -> joint fit across the studies of a group (k_xsusie.hip: its members' W beside the ungrouped windows', its fit last)
+//         -> polygenic score weights
 //   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
 //     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
 //   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
@@ -101,6 +102,8 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 //   - the multi-causal fit (k_susie.hip): its weights W = X^T (X B12) read the rows of X like the traits weights, and B21, which is
 //     complete where the tail starts; the fit itself reads z and info of the closing step, B11 in A[0] and B21, and for its further
 //     traits the scores in traits_Z and the imputed Z-scores traits impute has left (such a window has no mask: miss apply leaves them).
+//   - the polygenic score weights (k_prs.hip): B11 in A[0] and z1, like the selection; a chain is some hundred dependent sweeps that
+//     nothing else reads, so it is queued last: everything the caller may be waiting for is in front of it.
 // The closing step of a run is the product B21 [X | y] with its finish kernel.  A launch for which no window asked is skipped by its
 // launcher.  The clamp path (job_clamp_window) keeps the same order with its single-window map and the stand-alone solve as its
 // closing step; its selection runs in front of the re-factorisation.
@@ -121,6 +124,7 @@ static void queue_tail(gauss_job* job, hipStream_t st)
                  job->susie_max_k, job->susie_coloc, st);
     launch_xsusie(job->d_probs, job->d_xsmap, job->n_xs, job->d_xsleadmap, job->n_xs_lead, job->xs_max_M, job->xs_max_T, job->xs_max_L,
                   job->xs_max_sweeps, st);
+    launch_prs(job->d_probs, job->d_prsmap, job->n_prs, job->prs_max_s, job->prs_max_M, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -267,6 +271,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
             launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
             launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);      // z, info, the selection and B21: no fused solve either
             launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
+            launch_prs(job->d_probs, job->d_prsmap, job->n_prs, job->prs_max_s, job->prs_max_M, st);      // B11 and z1 again
         }
         prof_end(job, st);
     }
@@ -477,6 +482,7 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     if (pl.out_b11) HIPCHK(hipMemcpyAsync(pl.d_b11_copy, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(p.A + 4 * n * n, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));   // W0 = clamped B11
     if (pl.rd.slct_K) launch_slct(job->d_probs + i, nullptr, 1, st);      // signal selection again, on the REPAIRED B11 in A[0]
+    if (pl.rd.prs_n_s) launch_prs(job->d_probs + i, nullptr, 1, p.prs_n_s, p.M, st);      // ... and the score weights, on the same matrix
     // a window that rides on the rows of L^-1: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this factorisation
     // as they do in a run's (same L either way), and the stand-alone solve below is this tail's closing step (queue_tail): it
     // takes V as its scratch, only reads B21 and leaves the info the further traits are divided by
@@ -719,6 +725,13 @@ int job_fetch(gauss_job* job)
                     sel[sl.n] = sel[sl.skipped] = 0.0;
                     for (int a = 0; a < rd.slct_K; a++) sel[sl.idx + a] = -1.0;
                 }
+                if (rd.prs_n_s) {                  // no fit: nnz 0, no sweep, no flag
+                    const PrsLayout ql = prs_layout(p.M, rd.prs_n_s, rd.prs_n_lam);
+                    for (int c = 0; c < rd.prs_n_s * rd.prs_n_lam; c++) {
+                        double* const cell = res + lay.prs + ql.cell + (size_t)c * PRS_CELL;
+                        cell[PRS_NNZ] = cell[PRS_SWEEPS] = cell[PRS_NOCONV] = 0.0;
+                    }
+                }
                 if (rd.cs) {                       // no sets: size 0, set -1
                     const CsLayout cl = cs_layout(p.M + p.U, rd.slct_K);
                     for (int a = 0; a < rd.slct_K; a++) res[lay.cs + cl.size + a] = 0.0;
@@ -742,7 +755,7 @@ int job_fetch(gauss_job* job)
                 for (int t = 0; t < rd.susie_k; t++) memcpy(mq + ml.trait + (size_t)t * ml.one, sq, sizeof(double) * ql.count);
                 for (size_t u = ml.hit; u < ml.hit_pp; u++) mq[u] = -1.0;
                 for (size_t u = ml.n; u < ml.count; u++) mq[u] = 0.0;
-                if (lay.count > lay.xs) {          // a group's leader: every study's V, purity and mu NaN, no joint candidate
+                if (lay.prs > lay.xs) {          // a group's leader: every study's V, purity and mu NaN, no joint candidate
                     const XsLayout xl = xs_layout(rd.xs_K, rd.susie_L, p.M + p.U, rd.xs_mu);
                     for (size_t u = 0; u < xl.count; u++) res[lay.xs + u] = NAN;
                     res[lay.xs + xl.n] = 0.0;
@@ -788,6 +801,22 @@ int job_fetch(gauss_job* job)
                 if (rd.out.cs_set) for (int c = 0; c < T; c++) rd.out.cs_set[c] = (int32_t)cs[cl.set + c];
                 copy_out(rd.out.cs_set_pip, cs + cl.set_pip, T);
             }
+            if (rd.prs_n_s) {                      // polygenic score weights (k_prs.hip)
+                const int nc = rd.prs_n_s * rd.prs_n_lam;
+                const PrsLayout ql = prs_layout(p.M, rd.prs_n_s, rd.prs_n_lam);
+                const double* const pq = res + lay.prs;
+                for (int c = 0; c < nc; c++) {
+                    const double* const cell = pq + ql.cell + (size_t)c * PRS_CELL;
+                    if (cell[PRS_NOCONV] != 0.0) bits |= GAUSS_ST_PRS_NOCONV;
+                    if (rd.out.prs_nnz) rd.out.prs_nnz[c] = (int32_t)cell[PRS_NNZ];
+                    if (rd.out.prs_sweeps) rd.out.prs_sweeps[c] = (int32_t)cell[PRS_SWEEPS];
+                    if (rd.out.prs_delta) rd.out.prs_delta[c] = cell[PRS_DELTA];
+                    if (rd.out.prs_br) rd.out.prs_br[c] = cell[PRS_BR];
+                    if (rd.out.prs_bg) rd.out.prs_bg[c] = cell[PRS_BG];
+                    if (rd.out.prs_kkt) rd.out.prs_kkt[c] = cell[PRS_KKT];
+                }
+                copy_out(rd.out.prs_beta, pq + ql.beta, (size_t)nc * p.M);
+            }
             if (rd.susie_L && !pl.xs_peer()) {     // the multi-causal fit (k_susie.hip); for a group's leader the joint fit (k_xsusie.hip)
                 const int L = rd.susie_L, T = p.M + p.U;
                 const SusieLayout ql = susie_layout(T, L, rd.susie_am);
@@ -828,7 +857,7 @@ int job_fetch(gauss_job* job)
                     if (rd.susie_lbf && o.more_lbf) copy_out(o.more_lbf + t * lt, tq + ml.tlbf, lt);
                     if (o.more_sweeps) copy_out(o.more_sweeps + 2 * (size_t)t, tq + ql.fit, 2);
                 }
-                if (lay.count > lay.xs) {          // a group's leader: what the joint fit holds per study (k_xsusie.hip)
+                if (lay.prs > lay.xs) {          // a group's leader: what the joint fit holds per study (k_xsusie.hip)
                     const XsLayout xl = xs_layout(rd.xs_K, L, T, rd.xs_mu);
                     const double* const xq = res + lay.xs;
                     copy_out(rd.out.xs_V, xq + xl.V, (size_t)rd.xs_K * L);

@@ -618,6 +618,27 @@ int gauss_host_distmix_coloc(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t 
                                     reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
 }
 
+int gauss_host_dist_prs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                        const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                        const char* reference_pop_desc_file, double af1_cutoff, double n, const double* s, int n_s, const double* lam,
+                        int n_lam, double tol, int max_sweeps, gauss_table** out)
+{
+    PrsRider r(n, s, n_s, lam, n_lam, tol, max_sweeps);
+    return run_impute(ctx, call_pop(GAUSS_KIND_DIST, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
+}
+
+int gauss_host_distmix_prs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                           const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                           const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                           double af1_cutoff, double n, const double* s, int n_s, const double* lam, int n_lam, double tol, int max_sweeps,
+                           gauss_table** out)
+{
+    PrsRider r(n, s, n_s, lam, n_lam, tol, max_sweeps);
+    return run_impute(ctx, call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                    reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
+}
+
 int gauss_host_dist_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
                            const char* input_file, const char* reference_index_file, const char* reference_data_file,
                            const char* reference_pop_desc_file, double af1_cutoff, const char* const* more_input_files, int n_more,

@@ -579,6 +579,13 @@ struct SusieFit {                     // one trait's out_susie_* (first) or the 
 struct ColocMore { int k; SusieFit fit; const double* pp; const int32_t* hit; const double* hit_pp; const int32_t* n; };
 int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const SusieFit& first, int n_more, const double* z_more, const double* out_z_more, const ColocMore& more);
+// dist_prs / distmix_prs: a table of its own, one row per measured SNP of the extended window: rsid chr bp a1 a2 af1ref|af1mix z r wing
+// (r = z / sqrt(n - 2 + z^2), 0 where z is not finite: such a SNP is frozen at weight 0), the named matrices `beta` [n_s n_lam x rows],
+// grid cell i_s n_lam + i_lam, and `grid` [n_s n_lam x 9]: s, lam, nnz, sweeps, delta, br, bg, kkt, converged; a message when a cell
+// ran its sweeps out and when the window was not fitted.  beta [n_s][n_lam][rows]
+gauss_table* prs_output(bool mix, const std::vector<SlctRow>& rows, double n, double tol, const std::vector<double>& s,
+                        const std::vector<double>& lam, const double* beta, const int32_t* nnz, const int32_t* sweeps, const double* delta,
+                        const double* br, const double* bg, const double* kkt);
 // dist_traits / distmix_traits: the Z-scores of one further trait at the n measured SNPs of a window.  SNP i is at(i) -- position and
 // alleles in the window's (the panel's) orientation -- and is looked up in the study `gw` (read from `path`, named in the messages)
 // by (chr, bp, a1, a2): the same allele order gives z, the swapped order -z (gauss.cpp:358-370); of several rows that match, the
@@ -676,6 +683,20 @@ struct SusieRider : Rider {
     double tol_used = 0.0;
     std::vector<double> pip, set_pip, alpha, V, lse, mass, purity, sweeps;
     std::vector<int32_t> set, size, kept;
+    int check() override;
+    int ask(gauss_window_desc& d, const WindowView& v) override;
+    int table(const WindowView& v, gauss_table** out) override;
+};
+// dist_prs / distmix_prs: the prs_* fields of gauss_window_desc; the table lists every measured SNP of the extended window with its
+// weights over the grid (prs_output).  Independent of the selection
+struct PrsRider : Rider {
+    double n, tol; int max_sweeps;                                     // the call's own arguments; tol 0 or NaN, max_sweeps <= 0: the defaults (ask)
+    std::vector<double> s, lam;                                        // the grid; an empty list: lassosum's (the constructor)
+    int n_s_arg, n_lam_arg;
+    PrsRider(double n_, const double* s_, int n_s, const double* lam_, int n_lam, double tol_, int max_sweeps_);
+    double tol_used = 0.0;
+    std::vector<double> beta, delta, br, bg, kkt;
+    std::vector<int32_t> nnz, sweeps;
     int check() override;
     int ask(gauss_window_desc& d, const WindowView& v) override;
     int table(const WindowView& v, gauss_table** out) override;

@@ -139,6 +139,46 @@ int SusieRider::table(const WindowView& v, gauss_table** out)
     return 0;
 }
 
+// ---- prs ----
+// lassosum's grid: s = 0.2, 0.5, 0.9, 1 and 20 penalties log-spaced from 0.1 down to 0.001
+PrsRider::PrsRider(double n_, const double* s_, int n_s, const double* lam_, int n_lam, double tol_, int max_sweeps_)
+    : n(n_), tol(tol_), max_sweeps(max_sweeps_), n_s_arg(n_s), n_lam_arg(n_lam)
+{
+    if (s_ && n_s > 0) s.assign(s_, s_ + n_s);
+    else s = {0.2, 0.5, 0.9, 1.0};
+    if (lam_ && n_lam > 0) lam.assign(lam_, lam_ + n_lam);
+    else
+        for (int k = 0; k < 20; k++) lam.push_back(exp(log(0.1) + (log(0.001) - log(0.1)) * k / 19.0));
+}
+
+int PrsRider::check()
+{
+    if (n_s_arg > GAUSS_PRS_MAX_S) return herr("%d shrinkage values: the score takes at most %d", n_s_arg, GAUSS_PRS_MAX_S);
+    if (n_lam_arg > GAUSS_PRS_MAX_LAM) return herr("%d penalties: the score takes at most %d", n_lam_arg, GAUSS_PRS_MAX_LAM);
+    return 0;
+}
+
+int PrsRider::ask(gauss_window_desc& d, const WindowView&)
+{
+    const size_t M = (size_t)std::max(d.n_measured, 1), nc = s.size() * lam.size();
+    beta.assign(nc * M, NAN); delta.assign(nc, NAN); br = delta; bg = delta; kkt = delta;
+    nnz.assign(nc, 0); sweeps = nnz;
+    tol_used = tol != 0 && tol == tol ? tol : 1e-4;                    // 0 or NaN: the default; a negative one is the window's to refuse
+    d.prs_n_s = (int)s.size(); d.prs_n_lam = (int)lam.size(); d.prs_s = s.data(); d.prs_lam = lam.data();
+    d.prs_n = n; d.prs_tol = tol_used; d.prs_max_sweeps = max_sweeps > 0 ? max_sweeps : 100;
+    d.out_prs_beta = beta.data(); d.out_prs_nnz = nnz.data(); d.out_prs_sweeps = sweeps.data(); d.out_prs_delta = delta.data();
+    d.out_prs_br = br.data(); d.out_prs_bg = bg.data(); d.out_prs_kkt = kkt.data();
+    return 0;
+}
+
+int PrsRider::table(const WindowView& v, gauss_table** out)
+{
+    std::vector<SlctRow> rows;
+    for (const ViewSnp& q : v.measured) rows.push_back(SlctRow{q.id, q.af, q.z, q.wing});
+    *out = prs_output(v.mix, rows, n, tol_used, s, lam, beta.data(), nnz.data(), sweeps.data(), delta.data(), br.data(), bg.data(), kkt.data());
+    return 0;
+}
+
 // ---- traits, traits_miss ----
 int TraitsRider::check()
 {

@@ -520,6 +520,41 @@ int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::ve
     return 0;
 }
 
+// dist_prs / distmix_prs: one row per measured SNP of the extended window; `beta` [n_s n_lam x rows] and `grid` [n_s n_lam x 9] as named
+// matrices (host_internal.h).  converged = delta < tol r_max (or r_max = 0), the kernel's own rule on the same r
+gauss_table* prs_output(bool mix, const std::vector<SlctRow>& rows, double n, double tol, const std::vector<double>& s,
+                        const std::vector<double>& lam, const double* beta, const int32_t* nnz, const int32_t* sweeps, const double* delta,
+                        const double* br, const double* bg, const double* kkt)
+{
+    gauss_table* t = new gauss_table();
+    add_ident_columns(*t, rows.size(), [&](size_t i) { return rows[i].id; });
+    Column &af = t->add(mix ? "af1mix" : "af1ref", GAUSS_COL_DBL), &z = t->add("z", GAUSS_COL_DBL), &r = t->add("r", GAUSS_COL_DBL);
+    Column& wing = t->add("wing", GAUSS_COL_INT);
+    const size_t M = rows.size(), nl = lam.size(), nc = s.size() * nl;
+    double rmax = 0.0;
+    for (size_t i = 0; i < M; i++) {
+        const double zi = rows[i].z;
+        const double ri = std::isfinite(zi) ? zi / sqrt(n - 2.0 + zi * zi) : 0.0;
+        af.d.push_back(rows[i].af); z.d.push_back(zi); r.d.push_back(ri); wing.i.push_back(rows[i].wing);
+        rmax = std::max(rmax, fabs(ri));
+    }
+    std::vector<double> b(nc * M), g(nc * 9);
+    bool ran_out = false, fitted = true;
+    for (size_t c = 0; c < nc; c++) {
+        for (size_t i = 0; i < M; i++) b[i * nc + c] = beta[c * M + i];
+        const bool conv = sweeps[c] > 0 && (delta[c] < tol * rmax || rmax == 0.0);
+        fitted = fitted && sweeps[c] > 0;
+        ran_out = ran_out || (sweeps[c] > 0 && !conv);
+        const double vals[9] = {s[c / nl], lam[c % nl], (double)nnz[c], (double)sweeps[c], delta[c], br[c], bg[c], kkt[c], conv ? 1.0 : 0.0};
+        for (int k = 0; k < 9; k++) g[(size_t)k * nc + c] = vals[k];
+    }
+    t->put_named("beta", (int)nc, (int)M, std::move(b));
+    t->put_named("grid", (int)nc, 9, std::move(g));
+    if (!fitted) t->messages.push_back("prs: the window was not fitted (its B11 is not finite): the weights are empty");
+    else if (ran_out) t->messages.push_back("prs: some (s, lam) ran its sweeps out before it converged (max_sweeps); its weights are those of the last sweep");
+    return t;
+}
+
 int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out,
                  uint8_t* miss_out, size_t* n_missing)
 {

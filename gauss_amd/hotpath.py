@@ -268,12 +268,17 @@ def gene_ld_batch_rows(store, rows, pop_off, gene_off, pop_wgt=None, mode=MODE_P
     return blocks
 
 
+# lassosum's grid: the default of prs=dict(...)
+PRS_S = (0.2, 0.5, 0.9, 1.0)
+PRS_LAM = tuple(float(v) for v in np.exp(np.linspace(np.log(0.1), np.log(0.001), 20)))
+
+
 class _Win:
     """Keeps the numpy buffers of one window alive next to its C descriptor."""
 
     def __init__(self, desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig,
                  want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None, z_more=None, miss_more=None,
-                 susie=None):
+                 susie=None, prs=None):
         self.po, self.w = _pops(pop_off, pop_wgt)
         self.z1 = np.ascontiguousarray(z1, dtype=np.float64)
         if dev_ptrs is None:
@@ -452,6 +457,25 @@ class _Win:
             desc.miss_more = mask.ctypes.data
             desc.out_info_more = self.miss["info_more"].ctypes.data_as(_dp)
             desc.out_z_miss, desc.out_info_miss = self.miss["z"].ctypes.data_as(_dp), self.miss["info"].ctypes.data_as(_dp)
+        # polygenic score weights (prs_* of gauss_window_desc): prs=dict(n=, s=PRS_S, lam=PRS_LAM, tol=1e-4, max_sweeps=100)
+        self.prs = None
+        if prs is not None:
+            s = np.ascontiguousarray(PRS_S if prs.get("s") is None else prs["s"], dtype=np.float64).reshape(-1)
+            lm = np.ascontiguousarray(PRS_LAM if prs.get("lam") is None else prs["lam"], dtype=np.float64).reshape(-1)
+            if len(s) == 0:                                 # (prs_n_s = 0 is the descriptor's "off": the library could not refuse it)
+                raise ValueError("prs_n_s = 0: the score takes 1 .. %d shrinkage values" % _lib.PRS_MAX_S)
+            ns, nl = min(len(s), _lib.PRS_MAX_S), min(len(lm), _lib.PRS_MAX_LAM)      # (the library refuses a longer list: only the buffers are capped)
+            q = self.prs = dict(beta=np.full((ns, nl, M), np.nan), nnz=np.zeros((ns, nl), dtype=np.int32), sweeps=np.zeros((ns, nl), dtype=np.int32),
+                                delta=np.full((ns, nl), np.nan), br=np.full((ns, nl), np.nan), bg=np.full((ns, nl), np.nan),
+                                kkt=np.full((ns, nl), np.nan))
+            self._prs_grid = (s, lm)
+            desc.prs_n_s, desc.prs_n_lam = len(s), len(lm)
+            desc.prs_s, desc.prs_lam = _lib.ptr(s if len(s) else None, _dp), _lib.ptr(lm if len(lm) else None, _dp)
+            desc.prs_n, desc.prs_tol, desc.prs_max_sweeps = float(prs.get("n", 0.0)), float(prs.get("tol", 1e-4)), int(prs.get("max_sweeps", 100))
+            for key in ("beta", "delta", "br", "bg", "kkt"):
+                setattr(desc, "out_prs_" + key, q[key].ctypes.data_as(_dp))
+            for key in ("nnz", "sweeps"):
+                setattr(desc, "out_prs_" + key, q[key].ctypes.data_as(_ip))
         if packed is not None:
             # packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=): rows taken from a row store (dev_ptrs or
             # geno_m/geno_u give its base pointer and stride), optionally 2-bit packed (include/gauss_hip.h)
@@ -528,11 +552,13 @@ class _Win:
             if self.xs is not None:
                 out.update({"xs_" + k: v for k, v in self.xs.items() if k != "n"})
                 out["xs_n"] = int(self.xs["n"][0])
+        if self.prs is not None:
+            out.update({"prs_" + k: v for k, v in self.prs.items()})
         return out
 
 
 def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_eig=1e-5,
-                  want_mats=False, ctx=None, loo=False, slct=None, z_more=None, miss_more=None, susie=None):
+                  want_mats=False, ctx=None, loo=False, slct=None, z_more=None, miss_more=None, susie=None, prs=None):
     """run_dist (mode 0, dist.cpp:129-227) / run_distmix (mode 1, distmix.cpp:138-253).
     loo=True adds loo_z, loo_info, loo_t [M]: every measured SNP re-imputed from the other measured SNPs, and its
     standardised residual (include/gauss_hip.h, out_loo_*).
@@ -557,11 +583,15 @@ def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_e
     their bits 16 / 32.  coloc=dict(p1=1e-4, p2=1e-4, p12=1e-5) beside it colocalises every pair of fitted traits (coloc_*): coloc_pp
     [pairs, L, L, 5] = the posteriors of H0 .. H4 for effect la of the pair's first trait and lb of its second (NaN unless both are
     kept), coloc_hit / coloc_hit_pp [pairs, L, L] the most likely shared candidate (measured first; -1: none) and its share of H4,
-    coloc_n [pairs]; pairs in the order (0, 1), (0, 2), .., (k - 1, k), trait 0 being z1."""
+    coloc_n [pairs]; pairs in the order (0, 1), (0, 2), .., (k - 1, k), trait 0 being z1.
+    prs=dict(n=study sample size, s=[...], lam=[...], tol=1e-4, max_sweeps=100) adds the polygenic score weights of the measured SNPs
+    (include/gauss_hip.h, prs_*): lassosum's elastic net on the window's own LD, one warm-started chain over lam per s (defaults: PRS_S,
+    PRS_LAM, lassosum's grid).  prs_beta [n_s, n_lam, M], prs_nnz / prs_sweeps / prs_delta / prs_br / prs_bg / prs_kkt [n_s, n_lam]; the
+    in-sample predicted R^2 of a cell is prs_br^2 / prs_bg.  Status bit 64: some cell ran its sweeps out."""
     ctx = ctx or default_context()
     desc = WindowDesc()
     win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct, z_more=z_more,
-               miss_more=miss_more, susie=susie)
+               miss_more=miss_more, susie=susie, prs=prs)
     check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
     return win.result()
 
@@ -693,7 +723,7 @@ class Job:
     """A batch of windows sharing every launch (gauss_job_*)."""
 
     def __init__(self, windows, ctx=None, on_device=False, want_mats=False):
-        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more, miss_more, susie])
+        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more, miss_more, susie, prs])
         or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
         loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs).
         slct=dict(max=, chi2_stop=, collin=, forced=[, unmeasured=True][, cs=dict(coverage=, prior_var=)]) in a window's dict: its
@@ -727,7 +757,7 @@ class Job:
                                   w["pop_off"], w.get("pop_wgt"), w["z1"], w.get("lam", 0.1),
                                   w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed"),
                                   loo=bool(w.get("loo", False)), slct=w.get("slct"), z_more=w.get("z_more"), miss_more=w.get("miss_more"),
-                                  susie=w.get("susie")))
+                                  susie=w.get("susie"), prs=w.get("prs")))
         h = C.c_void_p()
         check(self.ctx.lib.gauss_job_create(self.ctx.handle, self.descs, n, 1 if on_device else 0,
                                             C.byref(h)))

@@ -58,6 +58,7 @@ extern "C" {
 #define GAUSS_ST_SLCT_SKIPPED 8 /* signal selection: a forced SNP failed the collinearity guard and was left out */
 #define GAUSS_ST_SUSIE_NOCONV 16 /* multi-causal fit: susie_max_sweeps sweeps ran without delta < susie_tol (values of the last sweep) */
 #define GAUSS_ST_SUSIE_NOFIT  32 /* multi-causal fit: MakePosDef repaired B11 (GAUSS_ST_CLAMPED), the window is not fitted      */
+#define GAUSS_ST_PRS_NOCONV  64 /* polygenic score weights: a (s, lam) ran prs_max_sweeps sweeps without delta < prs_tol r_max (last sweep's values) */
 
 typedef struct gauss_ctx gauss_ctx;
 typedef struct gauss_job gauss_job;
@@ -77,6 +78,54 @@ typedef struct gauss_window_desc {
     const double* z1;         /* [M] measured z-scores (host pointer, always)                      */
     double lambda;            /* ridge added to diag(B11): Arguments::lambda = 0.1 (gauss.cpp:20)  */
     double min_abs_eig;       /* MakePosDef floor: 1e-5 (gauss.cpp:21)                             */
+    /* ---- polygenic score weights of the window (GAUSS_WIN_IMPUTE windows only) ------------------------------------
+     * lassosum's model (Mak et al. 2017): elastic-net-penalised regression on summary statistics, solved by cyclic coordinate
+     * descent on the window's own LD, over a grid of shrinkage values s and a path of penalties lam.  lam = 0 is ridge
+     * regression (LDpred-inf's estimator).  Notation: B = B11 [M x M] as the job holds it -- lambda on the diagonal, pooled or
+     * weighted as `mode` says, MakePosDef's repair included (the matrix the selection runs on); z = z1.
+     *   r_j = z_j / sqrt(n - 2 + z_j^2)  (lassosum's p2cor; n = prs_n, the study's sample size);  r_max = max |r_j|
+     *   a measured SNP whose z_j is not finite is FROZEN: r_j = 0, beta_j = 0, never updated
+     * For s in (0, 1] and lam >= 0 the fit minimises
+     *   f(beta) = beta' ((1 - s) B + s I) beta - 2 beta' r + 2 lam |beta|_1
+     * One CHAIN per s = prs_s[i_s]: it starts from beta = 0, g = 0 (g stands for B beta) and takes prs_lam[0 .. n_lam) in the
+     * caller's order, each from the solution of the one before it (a warm start).  One sweep at (s, lam), for j = 0 .. M - 1 in
+     * order, frozen j skipped, den_j = (1 - s) B_jj + s:
+     *   u  = r_j - (1 - s) (g_j - B_jj beta_j)
+     *   b' = sign(u) (|u| - lam) / den_j  if |u| > lam, else 0
+     *   D  = b' - beta_j;  if D != 0:  g_i += D * B_ji for every i (one multiply, one add, not contracted),  beta_j = b'
+     * delta = max |D| over the sweep.  The chain leaves this lam when delta < prs_tol * r_max, or after prs_max_sweeps sweeps:
+     * then GAUSS_ST_PRS_NOCONV is set and the values are those of the last sweep.  r_max = 0 (every z frozen, or zero): one
+     * sweep, beta = 0, no status bit.  The algorithm has no reductions: every g_i is a fixed sequence of scalar updates, the
+     * result does not depend on how the i are spread over lanes.
+     * Per (s, lam), grid cell c = i_s * n_lam + i_lam:  beta [M];  nnz = #{beta_j != 0};  the sweeps run;  the last delta;
+     *   br = beta' r and bg = beta' g, both summed in index order (the caller's in-sample predicted R^2 is br^2 / bg);
+     *   kkt = the largest KKT residual of the stored beta, from g: with q_j = r_j - (1 - s) g_j - s beta_j,
+     *         |q_j - lam sign(beta_j)| where beta_j != 0, max(0, |q_j| - lam) where it is 0 (frozen j skipped).
+     * GAUSS_ST_NONFINITE windows return NaN, nnz 0, sweeps 0.  prs_n_s = 0: off (a zeroed block asks for nothing).
+     * GAUSS_E_INVALID: QCAT / LD windows that ask; prs_n_s outside 1 .. GAUSS_PRS_MAX_S; prs_n_lam outside 1 ..
+     * GAUSS_PRS_MAX_LAM; an s outside (0, 1]; a lam negative or not finite; prs_n <= 2 or not finite; prs_tol < 0 or not
+     * finite; prs_max_sweeps outside 1 .. GAUSS_PRS_MAX_SWEEPS (the cap bounds what one window can keep a workgroup busy for:
+     * with the caps every loop of the kernel is bounded); n_measured above GAUSS_PRS_MAX_M (beta, g, r and diag(B) of a chain
+     * live in LDS).  The kernel (k_prs.hip) runs at the end of the job's tail, one workgroup per chain; fp64, not contracted,
+     * no atomics.  Independent of every other rider.
+     * Limits: weights for the measured SNPs of the extended window only (an imputed SNP adds no information to a score);
+     * standardised-genotype units; one trait; the tuning value (s, lam) is the caller's choice -- pseudovalidation needs
+     * genotypes of the target cohort.  (The block sits between the window's inputs and its outputs: every later field keeps its
+     * neighbours.) */
+    int      prs_n_s;          /* shrinkage values; 0 = off; at most GAUSS_PRS_MAX_S                           */
+    int      prs_n_lam;        /* penalties of the path; 1 .. GAUSS_PRS_MAX_LAM                                */
+    const double* prs_s;       /* [prs_n_s] each in (0, 1]                                     host pointer    */
+    const double* prs_lam;     /* [prs_n_lam] each finite and >= 0, in the order the chain takes host pointer  */
+    double   prs_n;            /* the study's sample size, finite and > 2                                      */
+    double   prs_tol;          /* >= 0: a lam is left when delta < prs_tol * r_max                             */
+    int      prs_max_sweeps;   /* 1 .. GAUSS_PRS_MAX_SWEEPS                                                    */
+    double*  out_prs_beta;     /* [n_s][n_lam][M]                                host pointer / NULL, optional */
+    int32_t* out_prs_nnz;      /* [n_s][n_lam]                                                 optional        */
+    int32_t* out_prs_sweeps;   /* [n_s][n_lam]                                                 optional        */
+    double*  out_prs_delta;    /* [n_s][n_lam]                                                 optional        */
+    double*  out_prs_br;       /* [n_s][n_lam]                                                 optional        */
+    double*  out_prs_bg;       /* [n_s][n_lam]                                                 optional        */
+    double*  out_prs_kkt;      /* [n_s][n_lam]                                                 optional        */
     double* out_z;            /* [U] imputed z / sqrt(info)    (dist.cpp:200)  host pointer        */
     double* out_info;         /* [U] info = |b21 B11^-1 b12|   (dist.cpp:198)  host pointer        */
     int32_t* out_status;      /* [1] GAUSS_ST_* bits                           host pointer        */
@@ -424,6 +473,10 @@ typedef struct gauss_window_desc {
 } gauss_window_desc;
 
 #define GAUSS_SLCT_MAX 32
+#define GAUSS_PRS_MAX_S 8
+#define GAUSS_PRS_MAX_LAM 32
+#define GAUSS_PRS_MAX_SWEEPS 1000
+#define GAUSS_PRS_MAX_M 4096
 #define GAUSS_SUSIE_MAX_L 32
 #define GAUSS_XS_MAX 4
 #define GAUSS_SUSIE_MAX_SWEEPS 1000

@@ -310,6 +310,35 @@ int gauss_host_distmix_coloc(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t 
                              const char* const* more_input_files, int n_more, int L, double coverage, double prior_var,
                              double min_abs_corr, int max_sweeps, double tol, int estimate_prior_var, int measured_only,
                              double p1, double p2, double p12, gauss_table** out);
+/* Polygenic score weights of the window: lassosum's elastic net on summary statistics (Mak et al. 2017), fitted by coordinate descent on
+ * the window's own LD -- the ancestry-weighted B11 of distmix, the pooled one of dist -- over a grid of shrinkage values s and a path of
+ * penalties lam; lam = 0 is ridge regression (LDpred-inf's estimator).  Arguments, window, data layer, single job and refusals of
+ * gauss_host_dist / gauss_host_distmix; the job's window also sets the prs_* fields of gauss_window_desc (include/gauss_hip.h: the
+ * model, the sweep, the stopping rule, the outputs) with
+ *   n           the study's sample size, finite and > 2 (z becomes the correlation r = z / sqrt(n - 2 + z^2))
+ *   s, n_s      shrinkage values in (0, 1]; NULL or n_s <= 0: 0.2, 0.5, 0.9, 1; at most GAUSS_PRS_MAX_S
+ *   lam, n_lam  penalties >= 0 in the order each chain takes them; NULL or n_lam <= 0: 20 values log-spaced from 0.1 down to 0.001
+ *               (lassosum's grid); at most GAUSS_PRS_MAX_LAM
+ *   tol         a penalty is left when no weight moved by tol r_max in a sweep; 0 or NaN: 1e-4
+ *   max_sweeps  <= 0: 100; at most GAUSS_PRS_MAX_SWEEPS (the window refuses more)
+ * Table: one row per measured SNP of the extended window (the wings included), in matrix order: rsid chr bp a1 a2 af1ref|af1mix z r
+ * wing.  Named matrices: `beta` [n_s n_lam x rows], the weights of grid cell i_s n_lam + i_lam; `grid` [n_s n_lam x 9]: s, lam, nnz,
+ * sweeps, delta, br, bg, kkt, converged (the in-sample predicted R^2 of a cell is br^2 / bg).  A message is added when a cell ran its
+ * sweeps out (GAUSS_ST_PRS_NOCONV) and when the window was not fitted (GAUSS_ST_NONFINITE).
+ * Limits: weights for the measured SNPs of the extended window only -- an imputed SNP adds no information to a score; standardised-
+ * genotype units (divide by sqrt(2 af (1 - af)) for per-allele weights); one trait; the tuning value (s, lam) is the caller's choice:
+ * pseudovalidation needs genotypes of the target cohort. */
+int gauss_host_dist_prs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                        const char* study_pop, const char* input_file, const char* reference_index_file,
+                        const char* reference_data_file, const char* reference_pop_desc_file,
+                        double af1_cutoff, double n, const double* s, int n_s, const double* lam, int n_lam, double tol, int max_sweeps,
+                        gauss_table** out);
+int gauss_host_distmix_prs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                           const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                           const char* input_file, const char* reference_index_file,
+                           const char* reference_data_file, const char* reference_pop_desc_file,
+                           double af1_cutoff, double n, const double* s, int n_s, const double* lam, int n_lam, double tol, int max_sweeps,
+                           gauss_table** out);
 /* The chi^2 (1 df) threshold of a two-sided p-value: the smallest double chi2 with 2 pnorm(-sqrt(chi2)) < p in the library's own
  * normal tail, found by bisection on the bit pattern -- monotone in p, and exact to the last bit that changes the comparison.
  * p must be positive. */
