@@ -249,6 +249,8 @@ int gauss_hip_init(int device, gauss_ctx** out_ctx)
     c->gram_i8 = (e && (strcmp(e, "i8") == 0 || strcmp(e, "int8") == 0)) ? 1 : 0;
     // GAUSS_GRAM_PACKED=0: the f32 Gram kernel multiplies every item one A row per lane (the form before the packed one; same bits)
     c->gram_packed = env_int("GAUSS_GRAM_PACKED", 1) != 0 ? 1 : 0;
+    // GAUSS_GRAM_PKF=7: the packed items split their accumulators every 7 chunks whatever the codes (the interval before; same bits)
+    c->gram_pkf_geno = env_int("GAUSS_GRAM_PKF", 15) != 7 ? 1 : 0;
     const char* one = getenv("GAUSS_SIDE_STREAM");
     c->main_cls = (one && atoi(one) == 0) ? STREAM_NORMAL : STREAM_HIGH;
     int rc = ctx_stream_create(c, &c->stream, c->main_cls);

@@ -404,14 +404,21 @@ struct DeviceOnce {
 };
 
 // ---- launchers (host functions defined in the .hip files) ----
-void launch_pack_stats(const Prob* d_probs, const int2* d_rowmap, int n_rows, hipStream_t s);
+// d_code3 (may be null): a workgroup that meets a code 3 in a row of a 2-bit source raises the word to `pack_stamp` (it only
+// grows: the caller numbers its pack launches upwards from 1).  launch_gram compares the word with the stamp of the pack launch
+// that wrote ITS operands: below it, no row of this run holds a 3 (k_gram.hip: PK_F_GENO)
+void launch_pack_stats(const Prob* d_probs, const int2* d_rowmap, int n_rows, hipStream_t s, unsigned long long* d_code3 = nullptr,
+                       unsigned long long pack_stamp = 0);
 // resampled windows (k_simld.hip): the pack stage of a job whose window has Prob::draw_col.  lds_bytes: from
 // resample_pack_lds_bytes (0: the source row is too long to stage in LDS and is read from global memory)
 constexpr int SIMLD_LDS_MAX = 60 << 10;
 int resample_pack_lds_bytes(long long row_src_bytes);
 void launch_resample_pack(const Prob* d_probs, const int2* d_rowmap, int n_rows, int lds_bytes, hipStream_t s);
 // d_b11_done (may be null): items with flag bit 4 count themselves off there when their slabs are out (k_gram.hip)
-void launch_gram(const Item* d_items, int n_items, int dtype_i8, hipStream_t s, unsigned long long* d_b11_done = nullptr);
+// d_code3 / pack_stamp: as given to the launch_pack_stats of the same run; null: the packed items split at the interval that any
+// 2-bit code admits
+void launch_gram(const Item* d_items, int n_items, int dtype_i8, hipStream_t s, unsigned long long* d_b11_done = nullptr,
+                 const unsigned long long* d_code3 = nullptr, unsigned long long pack_stamp = 0);
 // one wave that returns when *d_count >= target (bounded; on timeout d_status[0 .. n_status) = 1)
 // bound_us: give-up bound in microseconds (at least two seconds are always granted)
 void launch_wait_count(const unsigned long long* d_count, unsigned long long target, int* d_status, int n_status, hipStream_t s,

@@ -165,6 +165,7 @@ struct gauss_ctx {
     std::map<const void*, std::shared_ptr<StoreUpload>> uploads;      // by device pointer (guarded by mu); shared: a waiter keeps its entry alive
     int gram_i8 = 0;
     int gram_packed = 1;                     // f32 Gram items with 16-bit slabs pack two A rows per lane (k_gram.hip); GAUSS_GRAM_PACKED=0: off
+    int gram_pkf_geno = 1;                   // packed items of a run without a code 3 split every 15 chunks, not 7; GAUSS_GRAM_PKF=7: off
     std::map<const void*, size_t> stores;    // row stores made by gauss_store_upload: base pointer -> bytes
     std::mutex mu;
     BlockCache dev_cache, pin_cache;
@@ -206,9 +207,11 @@ void ctx_pin_release(gauss_ctx* c, void* p);
 bool trace_on(const char* what);
 
 // A packed f32 Gram item's time per sample over an unpacked one's (k_gram.hip: half the MFMAs, plus the A-side combine and the
-// sub-flushes).  The K-loop model says 0.54-0.57 plus ~3 % of sub-flushes; measured on the 36-window job: Gram launch
-// 36.39 -> 20.37 ms = 0.56.  The planner's estimates rest on it (gauss_plan.cpp: t_b21, wait_bound_us).
-constexpr double GRAM_PACKED_COST = 0.58;
+// sub-flushes).  The K-loop model says 0.54-0.57 plus ~2 % of sub-flushes; measured on the 36-window job: Gram launch
+// 36.38 -> 20.17 ms = 0.554 with a sub-flush every 15 chunks (genotype codes 0..2), 20.34 ms = 0.559 every 7 (a run with a
+// code 3).  The constant keeps the 0.02 above the measured ratio that it had before (0.56 measured, 0.58).  The planner's
+// estimates rest on it (gauss_plan.cpp: t_b21, wait_bound_us).
+constexpr double GRAM_PACKED_COST = 0.57;
 static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Plan thresholds (measured on MI355X).  Both sides of each are ordinary production forms that a job
@@ -401,6 +404,12 @@ struct gauss_job {
     int max_pop = 1;
     int gram_i8 = 0;
     int gram_packed = 0;                                   // 1: the items of windows with 16-bit slabs carry Item::flags bit 2
+    // Sub-flush interval of the packed items by the codes of THIS run (k_gram.hip: PK_F / PK_F_GENO): every pack launch of the job
+    // gets the next stamp, a pack workgroup that meets a code 3 raises *d_code3 to it, and the Gram launches of the run take the
+    // long interval only while the word is below their run's stamp.  The word only grows and is never cleared: a run can neither
+    // inherit the verdict of an earlier run (its stamp is higher) nor be harmed by a later one (which can only shorten the interval).
+    unsigned long long* d_code3 = nullptr;                 // null: GAUSS_GRAM_PKF=7, the short interval always
+    unsigned long long pack_stamp = 0;                     // pack launches queued so far
     int resample_lds = -1;                                 // >= 0: the window is resampled (k_simld.hip) and its pack stage is
                                                            // resample_pack with this much dynamic LDS
     int* d_status = nullptr;                               // [n][4] + 4 job-wide ints

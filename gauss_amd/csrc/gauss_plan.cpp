@@ -346,6 +346,8 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
     if (w.rows_m) pl.rows_m.assign(w.rows_m, w.rows_m + w.M);
     if (w.rows_u && w.U > 0) pl.rows_u.assign(w.rows_u, w.rows_u + w.U);
     p.Kp = pl.pop_pk_off[P];
+    // the Gram kernel addresses a lane's place inside an operand tile (TILE rows) with a 32-bit offset (k_gram.hip: run_item)
+    if ((long long)TILE * p.Kp > INT32_MAX) return fail(GAUSS_E_RANGE, "%d packed samples per row: a tile of %d rows exceeds 2^31 bytes", p.Kp, TILE);
     // 16-bit partial slabs: 2-bit sources carry codes 0..3 (recoding only lowers them), so a segment of at most 7168
     // samples sums to <= 9 * 7168 < 2^16; the fast epilogue reads them (windows with LDS-resident population tables);
     // LD-only calls and gene batches keep f32 / int32 slabs
@@ -1230,6 +1232,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     }
     const size_t o_status = wa.take(sizeof(int) * (4 * job->n + 4));    // [n][4], then 4 job-wide ints ([4 n]: the chain queue timed out)
     const size_t o_count = wa.take(128);                                 // counters of the merged Gram launch, a cache line each: [0] B11's items, [8] the early windows' B21 items (zeroed once; they only grow)
+    const size_t o_code3 = wa.take(64);                                  // stamp of the latest pack launch that met a code 3 (gauss_job::d_code3; zeroed once, only grows)
     const size_t o_results = wa.take(sizeof(double) * std::max<size_t>(res, 1));
     job->n_results = res;
     const size_t slab_base = rup(wa.off, 4096);
@@ -1305,6 +1308,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
 
     job->d_status = (int*)(job->d_ws + o_status);
     job->d_b11_done = (unsigned long long*)(job->d_ws + o_count);
+    job->d_code3 = ctx->gram_pkf_geno ? (unsigned long long*)(job->d_ws + o_code3) : nullptr;
     job->d_results = (double*)(job->d_ws + o_results);
     std::deque<std::vector<uint8_t>> stage;      // host gather buffers, alive until the copies have drained
     for (int i = 0; i < job->n; i++) {

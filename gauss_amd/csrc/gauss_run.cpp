@@ -154,8 +154,12 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
     const bool fused = env_int("GAUSS_FUSED_SOLVE", 1) != 0 || job->needs_fused();           // read per run: the tests drive both forms
     hipStream_t side = (solve && fused && job->n_panels > 0 && job->n_tiles > job->n_tiles_b11) ? ctx->side : nullptr;
     prof_begin(job, 1, st);
+    // the packed Gram items' sub-flush interval follows the codes this pack launch meets (gauss_job.h: d_code3); operands that
+    // another kernel writes get the interval that any 2-bit code admits
+    const unsigned long long* code3 = job->resample_lds >= 0 ? nullptr : job->d_code3;
+    const unsigned long long stamp = ++job->pack_stamp;
     if (job->resample_lds >= 0) launch_resample_pack(job->d_probs, job->d_rowmap, job->n_rows, job->resample_lds, st);
-    else launch_pack_stats(job->d_probs, job->d_rowmap, job->n_rows, st);
+    else launch_pack_stats(job->d_probs, job->d_rowmap, job->n_rows, st, job->d_code3, stamp);
     // the certificate needs the row tables only and is read by B11's epilogue tiles and the chain: in a merged launch it
     // moves to the head of the chain queue, beside the Gram kernel's start (23 us off the main queue's critical path)
     const bool cert_on_chain = solve && job->chain_aside && merged;
@@ -176,7 +180,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
             // and then waits for the count of this run: the counter only grows, run r is complete at (r + 1) x n_items_b11.
             HIPCHK(hipEventRecord(ev.gram, st));
             prof_begin(job, 0, st, 1);
-            launch_gram(job->d_items, job->n_items, job->gram_i8, st, job->d_b11_done);
+            launch_gram(job->d_items, job->n_items, job->gram_i8, st, job->d_b11_done, code3, stamp);
             job->merged_runs++;                            // counted per LAUNCH, not per completed call: a later error must not shift the target
             prof_end(job, st);
             HIPCHK(hipStreamWaitEvent(ch, ev.gram, 0));
@@ -185,9 +189,9 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         } else {
             // two launches joined by an event: B11's items, then B21's (no kernel waits for another queue's progress)
             prof_begin(job, 0, st, 2);
-            launch_gram(job->d_items, job->n_items_b11, job->gram_i8, st);
+            launch_gram(job->d_items, job->n_items_b11, job->gram_i8, st, nullptr, code3, stamp);
             HIPCHK(hipEventRecord(ev.gram, st));
-            launch_gram(job->d_items + job->n_items_b11, job->n_items - job->n_items_b11, job->gram_i8, st);
+            launch_gram(job->d_items + job->n_items_b11, job->n_items - job->n_items_b11, job->gram_i8, st, nullptr, code3, stamp);
             prof_end(job, st);
             HIPCHK(hipStreamWaitEvent(ch, ev.gram, 0));
         }
@@ -234,7 +238,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         return job_queue_results(job, par, st);
     }
     prof_begin(job, 0, st, 1);
-    launch_gram(job->d_items, job->n_items, job->gram_i8, st);
+    launch_gram(job->d_items, job->n_items, job->gram_i8, st, nullptr, code3, stamp);
     prof_end(job, st);
     if (side) {
         HIPCHK(hipEventRecord(ev.gram, st));
@@ -409,6 +413,9 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
     // what job_build queued on the main stream (zeroing, tables) comes before anything on the other queues
     HIPCHK(hipEventRecord(ev.pack, st));
     HIPCHK(hipStreamWaitEvent(ax, ev.pack, 0));
+    // one stamp for the run's pack launches: chunk g's Gram launch follows the packing of all its rows (chunks 0 and g), and a 3
+    // that a later chunk's pack meets meanwhile can only shorten its interval
+    const unsigned long long stamp = ++job->pack_stamp;
     for (size_t g = 0; g < ng; g++) {
         const gauss_job::StreamGroup& sg = job->sgroups[g];
         {
@@ -422,13 +429,13 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
         // launch (measured: 2.86 ms per call against 3.07 with pack in front of the Gram launch on the main stream)
         hipStream_t ps = ax;
         HIPCHK(hipStreamWaitEvent(ps, su.ev[g], 0));
-        launch_pack_stats(job->d_probs, job->d_rowmap + sg.row0, sg.n_rows, ps);
+        launch_pack_stats(job->d_probs, job->d_rowmap + sg.row0, sg.n_rows, ps, job->d_code3, stamp);
         if (g == 0) launch_shift_cert(job->d_probs, job->n, ps);
         if (ps != st) {
             HIPCHK(hipEventRecord(job->sevp[g], ps));
             HIPCHK(hipStreamWaitEvent(st, job->sevp[g], 0));
         }
-        launch_gram(job->d_items + sg.item0, sg.n_items, job->gram_i8, st);
+        launch_gram(job->d_items + sg.item0, sg.n_items, job->gram_i8, st, nullptr, job->d_code3, stamp);
         if (g == 0) {
             if (ch != st) {
                 HIPCHK(hipEventRecord(ev.gram, st));

@@ -16,7 +16,7 @@
 // Work item = (tile pair, run of K segments).  Workgroup = 256 threads = 4 waves, each wave owns a
 // 64 x 64 sub-tile = 2 x 2 MFMA tiles of 32 x 32 (four independent accumulators keep the MFMA pipe
 // issuing back to back).  K is walked in chunks of KC = 64 bytes staged by LDS-DMA
-// (global_load_lds_dwordx4) into a ring of NS chunk images (NS = 2: one chunk in flight while the previous
+// (buffer_load_dwordx4 ... lds) into a ring of NS chunk images (NS = 2: one chunk in flight while the previous
 // one is multiplied; the ring depth is a template parameter, deeper rings brought nothing).
 //
 // LDS image: [128 rows][64 bytes] per operand, unpadded; the bank conflicts of the ds_read_b128 fragment
@@ -103,6 +103,12 @@ constexpr int PK_SHIFT = 12;                                        // row r' ri
 constexpr int PK_CODE_MAX = 3;                                      // 2-bit sources (gauss_plan.cpp: Prob::slab16)
 constexpr int PK_F = ((1 << PK_SHIFT) - 1) / (PK_CODE_MAX * PK_CODE_MAX * KC);      // chunks between two sub-flushes
 static_assert(PK_F == 7 && PK_CODE_MAX * PK_CODE_MAX * KC * PK_F < (1 << PK_SHIFT), "a row's sum between two sub-flushes must stay below 2^PK_SHIFT");
+// Genotype panels hold 0, 1, 2: the pack kernel reports whether ANY 2-bit row of this run held a 3 (launch_gram: d_code3), and a
+// run without one splits every PK_F_GENO = 15 chunks = 960 samples instead: 4 * 960 = 3840.  Same sums, same bits: every partial
+// sum is an exact integer either way.
+constexpr int PK_CODE_GENO = 2;
+constexpr int PK_F_GENO = ((1 << PK_SHIFT) - 1) / (PK_CODE_GENO * PK_CODE_GENO * KC);      // the same bound for codes <= 2
+static_assert(PK_F_GENO == 15 && PK_CODE_GENO * PK_CODE_GENO * KC * PK_F_GENO < (1 << PK_SHIFT), "a row's sum between two sub-flushes must stay below 2^PK_SHIFT");
 static_assert(2 * PK_SHIFT <= 24, "both rows' sums together must stay an exact f32 integer");
 
 // fa0 + 2^PK_SHIFT fa1: one plain v_fma_f32 per element.  Written as C, not as inline asm: the compiler must see the consumer
@@ -359,7 +365,7 @@ __device__ __forceinline__ void wait_dma_barrier_dyn(int groups_newer)
 // PK (f32 only, items with 16-bit slabs): two A rows per lane (chunk_mfma_packed / chunk_mfma_edge_packed): half the accumulators,
 // the other half of the registers holds the segment's running sums.
 template <int NA, int NB, typename ACC, int NS, bool SK10 = false, int NC = 0, bool PK = false>
-__device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, int wc)
+__device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, int wc, int pkf)
 {
     const int Kp = it.Kp;
     const auto Ag = it.a;
@@ -368,7 +374,7 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
     const int lane = tid & 63;
     const int li = lane & 31, lh = lane >> 5;
 
-    // Staging by LDS-DMA (global_load_lds_dwordx4: 64 lanes x 16 bytes land contiguously in LDS, no
+    // Staging by LDS-DMA (buffer_load_dwordx4 ... lds: 64 lanes x 16 bytes land contiguously in LDS, no
     // VGPR round trip, no ds_write).  One wave-instruction carries 16 rows x 64 bytes of a tile chunk;
     // each wave issues two per operand.  The image has unpadded 64-byte rows; bank conflicts of the
     // ds_read_b128 fragment reads are avoided by an XOR swizzle applied to the SOURCE address here and
@@ -376,11 +382,16 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int srow = lane >> 2;                                   // row inside the 16-row group
     const int spiece = (lane & 3) ^ ((lane >> 4) & 3);            // swizzled source piece
-    size_t gsrc[2];
+    // The request is the buffer form: one descriptor per operand tile (scalar registers; range = the tile's 128 rows), the lane's
+    // place inside the tile as a 32-bit offset that never changes, the K position -- all that moves -- as the scalar offset.  No
+    // 64-bit vector address is formed per request.  (128 Kp < 2^31: gauss_plan.cpp bounds Kp.)
+    uint32_t gsrc[2];
 #pragma unroll
-    for (int j = 0; j < 2; j++) gsrc[j] = (size_t)(16 * (wave * 2 + j) + srow) * Kp + 16 * spiece;
+    for (int j = 0; j < 2; j++) gsrc[j] = (uint32_t)(16 * (wave * 2 + j) + srow) * (uint32_t)Kp + 16u * (uint32_t)spiece;
     typedef __attribute__((address_space(3))) uint8_t* lds_ptr;
-    typedef __attribute__((address_space(1))) const uint8_t* glb_ptr;
+    constexpr int RSRC_RAW = 0x00020000;                          // descriptor word 3 of a raw (unstrided, byte-addressed) buffer on gfx9
+    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)Ag, 0, TILE * Kp, RSRC_RAW);
+    const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void*)Bg, 0, TILE * Kp, RSRC_RAW);
 
     ACC acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};           // (PK: acc00 / acc01 are the two packed accumulators)
     uint32_t run0[16], run1[16];                                      // PK: the segment's sums, rows r / r + 32 in the low / high half
@@ -404,8 +415,8 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
     {                                                                                                            \
         _Pragma("unroll") for (int j = 0; j < 2; j++) {                                                        \
             const int t = wave * 2 + j;                                                                          \
-            __builtin_amdgcn_global_load_lds((glb_ptr)Ag + gsrc[j] + (KOFF), (lds_ptr)(lds + (BUF) * 2 * LTILE + t * 1024), 16, 0, 0);          \
-            __builtin_amdgcn_global_load_lds((glb_ptr)Bg + gsrc[j] + (KOFF), (lds_ptr)(lds + (BUF) * 2 * LTILE + LTILE + t * 1024), 16, 0, 0);  \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_ptr)(lds + (BUF) * 2 * LTILE + t * 1024), 16, (int)gsrc[j], (KOFF), 0, 0);          \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_ptr)(lds + (BUF) * 2 * LTILE + LTILE + t * 1024), 16, (int)gsrc[j], (KOFF), 0, 0);  \
         }                                                                                                        \
     }
     // ring of NS chunk images: up to NS - 1 chunks are in flight beyond the one being multiplied
@@ -476,8 +487,9 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
             if constexpr (PK) {
                 if (NA > 0 && NB > 0) chunk_mfma_packed<NA, (NB > 0 ? NB : 1)>(la, lb, aoff, boff, acc00, acc01, nl);
                 if (BE) chunk_mfma_edge_packed<(NA > 0 ? NA : 1), NCE>(la, lb, eoffa, eoffb, acce);
-                // every PK_F chunks and at the segment's end the accumulators go to the running sums
-                if (++since == PK_F || k + KC >= kend) {
+                // every pkf chunks (PK_F, or PK_F_GENO in a run whose codes stay below 3) and at the segment's end the
+                // accumulators go to the running sums
+                if (++since == pkf || k + KC >= kend) {
                     since = 0;
                     if (NA > 0 && NB > 0) {
 #pragma unroll
@@ -562,7 +574,7 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
 // 104 registers at most: four workgroups per CU then leave 96 per lane for the small-footprint kernels that run beside this one
 // (k_solve_lite.hip); the common paths need 104, the 16-column edge path would take 107 if left alone.
 template <typename ACC, int NS>
-__device__ __forceinline__ void gram_item(const Item& it, uint8_t* lds)
+__device__ __forceinline__ void gram_item(const Item& it, uint8_t* lds, int pkf)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 1, wc = wave & 1;
@@ -585,24 +597,24 @@ __device__ __forceinline__ void gram_item(const Item& it, uint8_t* lds)
     // f32 path, items with flag bit 2 (16-bit slabs, codes <= 3; the planner sets it unless GAUSS_GRAM_PACKED=0): two A rows per lane
     if constexpr (std::is_same<ACC, f32x16>::value) {
         if (it.flags & 4) {
-            if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3, true>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 3, true>(it, lds, wr, wc); }
-            else if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1, true>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 1, true>(it, lds, wr, wc); }
-            else if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, wr, wc);
-            else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS, false, 0, true>(it, lds, wr, wc);       // (a diagonal wave too: its mirrored block costs no MFMA here)
-            else if (na == 2) run_item<2, 1, ACC, NS, false, 0, true>(it, lds, wr, wc);
-            else if (nb == 2) run_item<1, 2, ACC, NS, false, 0, true>(it, lds, wr, wc);
-            else run_item<1, 1, ACC, NS, false, 0, true>(it, lds, wr, wc);
+            if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3, true>(it, lds, wr, wc, pkf); else run_item<1, 0, ACC, NS, false, 3, true>(it, lds, wr, wc, pkf); }
+            else if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1, true>(it, lds, wr, wc, pkf); else run_item<1, 0, ACC, NS, false, 1, true>(it, lds, wr, wc, pkf); }
+            else if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, wr, wc, pkf);
+            else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS, false, 0, true>(it, lds, wr, wc, pkf);       // (a diagonal wave too: its mirrored block costs no MFMA here)
+            else if (na == 2) run_item<2, 1, ACC, NS, false, 0, true>(it, lds, wr, wc, pkf);
+            else if (nb == 2) run_item<1, 2, ACC, NS, false, 0, true>(it, lds, wr, wc, pkf);
+            else run_item<1, 1, ACC, NS, false, 0, true>(it, lds, wr, wc, pkf);
             return;
         }
     }
-    if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 3>(it, lds, wr, wc); return; }
-    if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1>(it, lds, wr, wc); else run_item<1, 0, ACC, NS, false, 1>(it, lds, wr, wc); return; }
-    if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, wr, wc);
-    else if (na == 2 && nb == 2 && diag && wr == wc) run_item<2, 2, ACC, NS, true>(it, lds, wr, wc);
-    else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS>(it, lds, wr, wc);
-    else if (na == 2) run_item<2, 1, ACC, NS>(it, lds, wr, wc);
-    else if (nb == 2) run_item<1, 2, ACC, NS>(it, lds, wr, wc);
-    else run_item<1, 1, ACC, NS>(it, lds, wr, wc);
+    if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3>(it, lds, wr, wc, pkf); else run_item<1, 0, ACC, NS, false, 3>(it, lds, wr, wc, pkf); return; }
+    if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1>(it, lds, wr, wc, pkf); else run_item<1, 0, ACC, NS, false, 1>(it, lds, wr, wc, pkf); return; }
+    if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, wr, wc, pkf);
+    else if (na == 2 && nb == 2 && diag && wr == wc) run_item<2, 2, ACC, NS, true>(it, lds, wr, wc, pkf);
+    else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS>(it, lds, wr, wc, pkf);
+    else if (na == 2) run_item<2, 1, ACC, NS>(it, lds, wr, wc, pkf);
+    else if (nb == 2) run_item<1, 2, ACC, NS>(it, lds, wr, wc, pkf);
+    else run_item<1, 1, ACC, NS>(it, lds, wr, wc, pkf);
 }
 
 // 104 registers at most: four workgroups per CU then leave 96 per lane for the small-footprint kernels that run beside this one
@@ -618,13 +630,21 @@ __device__ __forceinline__ void gram_item(const Item& it, uint8_t* lds)
 // started by wait_count_kernel below.
 template <typename ACC, int NS, int OCC>
 __global__ __launch_bounds__(256, OCC) __attribute__((amdgpu_num_vgpr(52))) void gram_kernel(const Item* __restrict__ items,
-                                                                                             unsigned long long* __restrict__ b11_done)
+                                                                                             unsigned long long* __restrict__ b11_done,
+                                                                                             const unsigned long long* __restrict__ code3,
+                                                                                             unsigned long long pack_stamp)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[NS * 2 * LTILE];
 
     const Item& it = items[blockIdx.x];
     const int counted = it.flags & 48;                                // scalar: read before the K loop's memory clobbers
-    gram_item<ACC, NS>(it, lds);
+    // `code3` (may be null): the stamp of the latest pack launch of this job that met a code 3 in a 2-bit row (pack_stats_kernel;
+    // it only grows).  Below this run's own stamp: this run's operands hold 0, 1, 2 and the packed items split every PK_F_GENO
+    // chunks.  At or above it -- this run's pack met a 3, or a later run's did while this launch was under way -- or no word
+    // at all (the operands were not written by pack_stats_kernel in this run): PK_F.
+    int pkf = PK_F;
+    if (code3 && uniform_load<unsigned long long>((GP(const unsigned long long))code3, 0) < pack_stamp) pkf = PK_F_GENO;
+    gram_item<ACC, NS>(it, lds, pkf);
     if (counted && b11_done) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this wave's slab stores have reached the L2
         __syncthreads();
@@ -688,7 +708,8 @@ void launch_wait_count(const unsigned long long* d_count, unsigned long long tar
     hipLaunchKernelGGL(wait_count_kernel, dim3(1), dim3(64), 0, s, d_count, target, ticks, d_status, n_status);
 }
 
-void launch_gram(const Item* d_items, int n_items, int dtype_i8, hipStream_t s, unsigned long long* d_b11_done)
+void launch_gram(const Item* d_items, int n_items, int dtype_i8, hipStream_t s, unsigned long long* d_b11_done,
+                 const unsigned long long* d_code3, unsigned long long pack_stamp)
 {
     if (n_items <= 0) return;
     // two chunk images (32 KB), four workgroups per CU for both paths.  Deeper rings were measured for the int8
@@ -698,8 +719,8 @@ void launch_gram(const Item* d_items, int n_items, int dtype_i8, hipStream_t s, 
 #define GAUSS_I8_NS 2
 #define GAUSS_I8_OCC 4
 #endif
-    if (dtype_i8) hipLaunchKernelGGL((gram_kernel<i32x16, GAUSS_I8_NS, GAUSS_I8_OCC>), dim3(n_items), dim3(256), 0, s, d_items, d_b11_done);
-    else hipLaunchKernelGGL((gram_kernel<f32x16, 2, 4>), dim3(n_items), dim3(256), 0, s, d_items, d_b11_done);
+    if (dtype_i8) hipLaunchKernelGGL((gram_kernel<i32x16, GAUSS_I8_NS, GAUSS_I8_OCC>), dim3(n_items), dim3(256), 0, s, d_items, d_b11_done, d_code3, pack_stamp);
+    else hipLaunchKernelGGL((gram_kernel<f32x16, 2, 4>), dim3(n_items), dim3(256), 0, s, d_items, d_b11_done, d_code3, pack_stamp);
 }
 
 }  // namespace gauss

@@ -26,9 +26,11 @@ struct __attribute__((packed)) U32u { uint32_t v; };
 // kernel reaches 4.6 TB/s on a 1 : 1 stream and its 1 : 4 expanding copy 3.9 (tools/hbm_write_probe.py: fill_ alone 6.5): the
 // kernel sits at what a write-heavy mixed stream gets out of this memory system.)
 __global__ __launch_bounds__(256) void pack_stats_kernel(const Prob* __restrict__ probs,
-                                                         const int2* __restrict__ rowmap)
+                                                         const int2* __restrict__ rowmap,
+                                                         unsigned long long* __restrict__ code3, unsigned long long pack_stamp)
 {
     __shared__ int s_sx[64];
+    __shared__ int s_code3;         // a code 3 in this row (2-bit sources): the Gram kernel's packed items split sooner (k_gram.hip: PK_F)
     __shared__ int s_sxx[64];
     // word -> source block tables staged in LDS: looked up once per 16 samples, and a chain of dependent global
     // loads (word table -> offsets -> data) would set the pace of the whole kernel
@@ -59,6 +61,10 @@ __global__ __launch_bounds__(256) void pack_stats_kernel(const Prob* __restrict_
     uint4* dst = reinterpret_cast<uint4*>((um ? pb.packed_u : pb.packed) + (size_t)prow * pb.Kp);
 
     if (threadIdx.x < 64) { s_sx[threadIdx.x] = 0; s_sxx[threadIdx.x] = 0; }
+    if (threadIdx.x == 0) s_code3 = 0;
+    // the 2-bit fields that hold a 3, over this lane's words.  (Recoding maps 0..2 only -- finish_word keeps a 3 -- so the final
+    // code is 3 exactly where the source's is.)
+    uint32_t threes = 0;
     const int nwords = pb.Kp >> 4;                 // a multiple of 4 (Kp is a multiple of 64)
     const bool fmt2 = pb.geno_fmt != 0;
     const int n_tab = fmt2 ? pb.n_run : pb.P;      // source blocks ("runs"): populations, or 2-bit blocks
@@ -159,6 +165,7 @@ __global__ __launch_bounds__(256) void pack_stats_kernel(const Prob* __restrict_
                 pp[j] = (pb.P == 1) ? 0 : run;
                 const int o = (ww[j] << 4) - s_pk[run];
                 bits[j] = lv[j] ? *reinterpret_cast<const uint32_t*>(src + s_src[run] + (o >> 2)) : 0u;
+                threes |= bits[j] & (bits[j] >> 1) & 0x55555555u;
             }
 #pragma unroll
             for (int j = 0; j < PB; j++) {
@@ -183,6 +190,7 @@ __global__ __launch_bounds__(256) void pack_stats_kernel(const Prob* __restrict_
             uint32_t v[4] = {0u, 0u, 0u, 0u};
             if (fmt2) {
                 const uint32_t bits = live ? *reinterpret_cast<const uint32_t*>(src + s_src[run] + (o >> 2)) : 0u;
+                threes |= bits & (bits >> 1) & 0x55555555u;
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     uint32_t b = (bits >> (8 * q)) & 0xFFu;
@@ -204,7 +212,10 @@ __global__ __launch_bounds__(256) void pack_stats_kernel(const Prob* __restrict_
             finish_word(w, live, p, v);
         }
     }
+    if (threes) s_code3 = 1;
     __syncthreads();
+    // one atomic a row, and none at all on genotype data (0, 1, 2)
+    if (threadIdx.x == 0 && s_code3 && code3) __hip_atomic_fetch_max(code3, pack_stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int P = pb.P;
     if (threadIdx.x < P) {
         (um ? pb.sx_u : pb.sx)[(size_t)prow * P + threadIdx.x] = s_sx[threadIdx.x];
@@ -258,9 +269,10 @@ __global__ __launch_bounds__(256) void pack_stats_kernel(const Prob* __restrict_
     }
 }
 
-void launch_pack_stats(const Prob* d_probs, const int2* d_rowmap, int n_rows, hipStream_t s)
+void launch_pack_stats(const Prob* d_probs, const int2* d_rowmap, int n_rows, hipStream_t s, unsigned long long* d_code3,
+                       unsigned long long pack_stamp)
 {
-    if (n_rows > 0) hipLaunchKernelGGL(pack_stats_kernel, dim3(n_rows), dim3(256), 0, s, d_probs, d_rowmap);
+    if (n_rows > 0) hipLaunchKernelGGL(pack_stats_kernel, dim3(n_rows), dim3(256), 0, s, d_probs, d_rowmap, d_code3, pack_stamp);
 }
 
 // ------------------------------------------------------------------------------------------
