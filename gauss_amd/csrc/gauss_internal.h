@@ -356,7 +356,8 @@ struct Item {
     int flags;               // bit 0: ti == tj (diagonal tile); bit 1: slabs are uint16 pairs (Prob::slab16); bit 2 (f32 path, only with bit 1: codes <= 3): the
                              // kernel packs two A rows per lane (k_gram.hip: chunk_mfma_packed); bit 4: a B11 item of a
                              // job built for a merged launch: counts itself off in the launch's `b11_done[0]` when one is passed
-                             // (k_gram.hip); bit 5: a B21 item of an "early" window, counted in `b11_done[8]`
+                             // (k_gram.hip); bit 5: a B21 item of an "early" window, counted in `b11_done[8]`; bits 6-7: how the four waves share
+                             // the tile (k_gram_common.h: LAYOUT_*; 0 = a 64 x 64 quadrant each)
 };
 static_assert(sizeof(Item) == 64, "work items are fetched as one 64-byte descriptor");
 

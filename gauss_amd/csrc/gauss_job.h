@@ -404,6 +404,7 @@ struct gauss_job {
     int max_pop = 1;
     int gram_i8 = 0;
     int gram_packed = 0;                                   // 1: the items of windows with 16-bit slabs carry Item::flags bit 2
+    int gram_narrow = 0;                                   // 1: f32 items of half-empty tiles carry a narrow layout in Item::flags bits 6-7 (k_gram_common.h)
     // Sub-flush interval of the packed items by the codes of THIS run (k_gram.hip: PK_F / PK_F_GENO): every pack launch of the job
     // gets the next stamp, a pack workgroup that meets a code 3 raises *d_code3 to it, and the Gram launches of the run take the
     // long interval only while the word is below their run's stamp.  The word only grows and is never cleared: a run can neither

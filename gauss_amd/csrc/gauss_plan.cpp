@@ -5,6 +5,7 @@
 // filled by work items of many windows at once (the per-window matrices are too small to fill
 // 256 CUs on their own) and the latency-bound factor steps are amortised over the batch.
 #include "gauss_job.h"
+#include "k_gram_common.h"
 
 // K segment length: short segments give a single window enough work items to fill 256 CUs;
 // a batch of windows has plenty of items already, and longer segments mean fewer partial slabs
@@ -596,6 +597,11 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->on_device = on_device;
     job->gram_i8 = ctx->gram_i8;
     job->gram_packed = (ctx->gram_packed && !ctx->gram_i8) ? 1 : 0;
+    // Narrow layouts for the f32 kernel's half-empty tiles (k_gram_common.h: tile_layout); the int8 kernel keeps the quadrants (it is
+    // bound by operand delivery, not by a wave's MFMA issue).  GAUSS_GRAM_ROTATE=0 restores the quadrant roles for every item (the
+    // switch was named for a rotation of the roles, which the placement probe ruled out: tools/wave_simd_probe.py);
+    // GAUSS_GRAM_NARROW=0 does the same.  Read per job: the tests build both forms in one process.
+    job->gram_narrow = (!ctx->gram_i8 && env_int("GAUSS_GRAM_ROTATE", 1) != 0 && env_int("GAUSS_GRAM_NARROW", 1) != 0) ? 1 : 0;
     job->plans.resize(job->n);
     for (const WinSpec& w : specs)
         if (w.draw_pop && (specs.size() != 1 || streamed)) return fail(GAUSS_E_INVALID, "a resampled window is a job of its own");
@@ -915,17 +921,21 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             const int left = (t < mt) ? p.M - t * TILE : p.U - (t - mt) * TILE;
             return left > TILE ? TILE : left;
         };
-        auto halves = [](int r, int w) { const int n = (r - w * 64 + 31) / 32; return n < 0 ? 0 : (n > 2 ? 2 : n); };
         for (ItemH& h : items) {
             h.ord = h.len;
             if (job->gram_i8) continue;          // (the int8 kernel is bound by operand delivery: it keeps items of one K range together -- 5.40 against 5.53 ms)
             const Plan& pl = plan_of(h.prob);
-            const int ra = live_rows(pl, pl.pair_ti[h.pair]), rb = live_rows(pl, pl.pair_tj[h.pair]);
+            const int ti = pl.pair_ti[h.pair], tj = pl.pair_tj[h.pair];
+            const int ra = live_rows(pl, ti), rb = live_rows(pl, tj);
             // (packed items, k_gram.hip: a wave with any live A half issues one MFMA per live B half -- 2 at most, half a full unpacked wave)
             const bool packed = job->gram_packed && pl.p.slab16;
+            // the waves' blocks by the item's layout (k_gram_common.h): a narrow layout halves the fullest wave's blocks, and the key follows
+            const int layout = job->gram_narrow ? tile_layout(ra, rb, packed) : LAYOUT_QUAD;
             int mx = 0;
-            for (int wr = 0; wr < 2; wr++)
-                for (int wc = 0; wc < 2; wc++) mx = std::max(mx, (packed ? std::min(halves(ra, wr), 1) : halves(ra, wr)) * halves(rb, wc));
+            for (int w = 0; w < 4; w++) {
+                const WaveWork ww = wave_work(ra, rb, ti == tj, packed, false, w, layout);
+                mx = std::max(mx, (packed ? std::min(ww.na, 1) : ww.na) * ww.nb);
+            }
             h.ord = std::max(KC, (h.len * std::max(mx, 1) / 4 + KC - 1) / KC * KC);
         }
     }
@@ -1482,9 +1492,50 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         it.chunk_live = (const uint32_t*)(job->d_tab + to[h.prob].ch);
         it.Kp = p.Kp; it.k0 = pl.seg_k0[gr.first]; it.nseg = gr.second - gr.first;
         it.rows_a = rows(ti); it.rows_b = rows(tj); it.flags = (ti == tj ? 1 : 0) | (p.slab16 ? 2 : 0) | (p.slab16 && job->gram_packed ? 4 : 0);
+        if (job->gram_narrow) it.flags |= tile_layout(it.rows_a, it.rows_b, (it.flags & 4) != 0) << LAYOUT_SHIFT;
         if (job->merged && (int)n < job->n_items_b11) it.flags |= 16;         // counts itself off in b11_done[0]
         else if (job->merged && (int)n < job->n_items_b11 + job->n_items_b21_early) it.flags |= 32;      // ... in b11_done[8] (the early windows' B21 items)
         memcpy(blob.data() + o_items + sizeof(Item) * n, &it, sizeof(Item));
+    }
+    // GAUSS_PLAN_FILL=1: how unequal the four waves of the job's items are.  Per item, the waves' MFMA issue per K step as shares of
+    // a full wave's (k_gram_common.h: wave_load); the waves meet at a barrier every chunk, so an item runs at the pace of its
+    // fullest wave.  Printed per class (B11's items, B21's), in K samples x full waves: the issue of the fullest wave (`max`: the
+    // item's time while its fullest wave has its SIMD's matrix pipe to itself), the mean of the four (`mean`: its time if every
+    // SIMD of the CU saw an equal share), for the quadrant roles and for the layouts this job's items carry.
+    if (env_int("GAUSS_PLAN_FILL", 0) != 0 && !job->gram_i8) {
+        double mx[2][2] = {{0, 0}, {0, 0}}, mean[2][2] = {{0, 0}, {0, 0}}, full[2] = {0, 0};
+        long n_narrow[2] = {0, 0}, n_uneven[2] = {0, 0}, n_cls[2] = {0, 0};
+        for (size_t n = 0; n < items.size(); n++) {
+            const ItemH& h = items[n];
+            const Plan& pl = plan_of(h.prob);
+            const int ti = pl.pair_ti[h.pair], tj = pl.pair_tj[h.pair];
+            const int mt = pl.p.Mp / TILE;
+            auto rows = [&](int t) {
+                if (!pl.tile_live.empty()) return pl.tile_live[(size_t)t];
+                int left = (t < mt) ? pl.p.M - t * TILE : pl.p.U - (t - mt) * TILE; return left > TILE ? TILE : left;
+            };
+            const int ra = rows(ti), rb = rows(tj), c = h.b11 ? 0 : 1;
+            const bool packed = job->gram_packed && pl.p.slab16;
+            n_cls[c]++;
+            full[c] += h.len;
+            for (int f = 0; f < 2; f++) {
+                const int layout = (f && job->gram_narrow) ? tile_layout(ra, rb, packed) : LAYOUT_QUAD;
+                double m = 0, s = 0;
+                for (int w = 0; w < 4; w++) {
+                    const double l = wave_load(wave_work(ra, rb, ti == tj, packed, true, w, layout), packed);
+                    m = std::max(m, l); s += l;
+                }
+                mx[f][c] += h.len * m; mean[f][c] += h.len * s / 4;
+                if (f && layout != LAYOUT_QUAD) n_narrow[c]++;
+                if (!f && m * 4 > s + 1e-9) n_uneven[c]++;
+            }
+        }
+        for (int c = 0; c < 2; c++) {
+            if (!n_cls[c]) continue;
+            fprintf(stderr, "[fill] %s: %ld items (%ld with unequal waves, %ld narrow), K x tiles %.4e; quadrant roles: max %.4e mean %.4e mean/max %.4f; "
+                            "this job's layouts: max %.4e mean %.4e mean/max %.4f\n", c ? "B21" : "B11", n_cls[c], n_uneven[c], n_narrow[c], full[c],
+                    mx[0][c], mean[0][c], mean[0][c] / mx[0][c], mx[1][c], mean[1][c], mean[1][c] / mx[1][c]);
+        }
     }
     for (size_t x = 0; x < job->exports.size(); x++) {
         const gauss_job::Export& ex = job->exports[x];

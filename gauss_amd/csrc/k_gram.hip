@@ -15,8 +15,9 @@
 //
 // Work item = (tile pair, run of K segments).  Workgroup = 256 threads = 4 waves, each wave owns a
 // 64 x 64 sub-tile = 2 x 2 MFMA tiles of 32 x 32 (four independent accumulators keep the MFMA pipe
-// issuing back to back).  K is walked in chunks of KC = 64 bytes staged by LDS-DMA
-// (buffer_load_dwordx4 ... lds) into a ring of NS chunk images (NS = 2: one chunk in flight while the previous
+// issuing back to back; a tile whose second half of rows or columns is empty is cut into four narrower
+// blocks instead, so that no wave idles at the chunk barrier: k_gram_common.h, wave_role).  K is walked
+// in chunks of KC = 64 bytes staged by LDS-DMA (buffer_load_dwordx4 ... lds) into a ring of NS chunk images (NS = 2: one chunk in flight while the previous
 // one is multiplied; the ring depth is a template parameter, deeper rings brought nothing).
 //
 // LDS image: [128 rows][64 bytes] per operand, unpadded; the bank conflicts of the ds_read_b128 fragment
@@ -93,7 +94,7 @@ __device__ __forceinline__ void chunk_mfma(const uint8_t* __restrict__ la, const
 }
 
 // ---- two A rows per lane (f32 path, items with Item::flags bit 2: 16-bit slabs, codes <= 3) ---------------------------
-// The A operand of one MFMA is  a_r + 4096 a_r'  for the lane's two rows r = wr * 64 + li and r' = r + 32, so accumulator
+// The A operand of one MFMA is  a_r + 4096 a_r'  for the lane's two rows r = r0 + li (r0: the wave's first row) and r' = r + 32, so accumulator
 // register (row r, column c) carries  S_rc + 4096 S_r'c : ONE 32 x 32 MFMA yields a 64 x 32 block of sums and a wave issues
 // NB of them per K step instead of NA x NB.  Exact while both sums stay below 4096 (the whole is then an integer below
 // 2^24 and every partial sum of the fmaf chain is one too): a product of two codes is at most PK_CODE_MAX^2 = 9, a chunk
@@ -254,8 +255,8 @@ __device__ __forceinline__ void chunk_mfma_edge(const uint8_t* __restrict__ la, 
     }
 }
 
-// the edge accumulators of a segment to its slab: rows erow0 + 16 ga + reg (erow0 = wr * 64 + 4 (lane / 16)), columns
-// ecol0 + 16 nc (ecol0 = wc * 64 + lane % 16)
+// the edge accumulators of a segment to its slab: rows erow0 + 16 ga + reg (erow0 = r0 + 4 (lane / 16)), columns
+// ecol0 + 16 nc (ecol0 = c0 + lane % 16)
 template <int NA, int NC, typename OUT>
 __device__ __forceinline__ void flush_edge(OUT out, bool slab16, int erow0, int ecol0, const f32x4 (&acce)[4][NC])
 {
@@ -365,7 +366,7 @@ __device__ __forceinline__ void wait_dma_barrier_dyn(int groups_newer)
 // PK (f32 only, items with 16-bit slabs): two A rows per lane (chunk_mfma_packed / chunk_mfma_edge_packed): half the accumulators,
 // the other half of the registers holds the segment's running sums.
 template <int NA, int NB, typename ACC, int NS, bool SK10 = false, int NC = 0, bool PK = false>
-__device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, int wc, int pkf)
+__device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int r0, int c0, int pkf)
 {
     const int Kp = it.Kp;
     const auto Ag = it.a;
@@ -408,8 +409,8 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
     const auto live_tab = it.chunk_live;
     const int klast = uniform_load<int>(seg_k1, nseg - 1);
     auto out = it.slab;
-    const int obase = (wr * 64 + 4 * lh) * TILE + wc * 64 + li;
-    const int obase16 = (wr * 32 + 2 * lh) * TILE + wc * 64 + li;         // row pair (wr * 64 + 4 lh) / 2
+    const int obase = (r0 + 4 * lh) * TILE + c0 + li;
+    const int obase16 = (r0 / 2 + 2 * lh) * TILE + c0 + li;               // row pair (r0 + 4 lh) / 2
 
 #define GAUSS_STAGE(BUF, KOFF)                                                                                   \
     {                                                                                                            \
@@ -429,13 +430,13 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
     wait_dma_barrier_dyn<NS>(ahead - 1);                          // the first chunk has landed (all waves)
     ahead--;
 
-    // fragment read offsets: logical piece 2g + lh of rows wr*64 + li (+32 has the same swizzle)
+    // fragment read offsets: logical piece 2g + lh of rows r0 + li (+32 has the same swizzle; r0, c0: multiples of 32)
     const int sw = (li >> 2) & 3;
     int aoff[2], boff[2];
 #pragma unroll
     for (int g = 0; g < 2; g++) {
-        aoff[g] = (wr * 64 + li) * LROW + 16 * ((2 * g + lh) ^ sw);
-        boff[g] = (wc * 64 + li) * LROW + 16 * ((2 * g + lh) ^ sw);
+        aoff[g] = (r0 + li) * LROW + 16 * ((2 * g + lh) ^ sw);
+        boff[g] = (c0 + li) * LROW + 16 * ((2 * g + lh) ^ sw);
     }
 
     // 16-column edge: fragment offsets in the (row lane % 16, piece lane / 16) layout, and where its results go
@@ -454,10 +455,10 @@ __device__ __forceinline__ void run_item(const Item& it, uint8_t* lds, int wr, i
 #pragma unroll
                 for (int r = 0; r < 4; r++) if (PK) rune[ga & 1][nc][r] = 0;
             }
-        eoffa = (wr * 64 + r16) * LROW + 16 * (q16 ^ sw16);
-        eoffb = (wc * 64 + r16) * LROW + 16 * (q16 ^ sw16);
-        erow0 = wr * 64 + 4 * q16;
-        ecol0 = wc * 64 + r16;
+        eoffa = (r0 + r16) * LROW + 16 * (q16 ^ sw16);
+        eoffb = (c0 + r16) * LROW + 16 * (q16 ^ sw16);
+        erow0 = r0 + 4 * q16;
+        ecol0 = c0 + r16;
     }
 
     int k = k0;
@@ -577,44 +578,39 @@ template <typename ACC, int NS>
 __device__ __forceinline__ void gram_item(const Item& it, uint8_t* lds, int pkf)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
-
-    // live 32-row halves of this wave's A rows / B rows (wave-uniform)
-    int na = (it.rows_a - wr * 64 + 31) / 32;
-    int nb = (it.rows_b - wc * 64 + 31) / 32;
-    na = na < 0 ? 0 : (na > 2 ? 2 : na);
-    nb = nb < 0 ? 0 : (nb > 2 ? 2 : nb);
-    // diagonal tile: the lower-left 64 x 64 quadrant mirrors the upper-right one and is never read
+    // The wave's block of the tile by the item's layout (k_gram_common.h: the quadrant (wave >> 1, wave & 1), or a narrower block
+    // of a tile whose second half is empty), and what is live of it (wave-uniform): 32-row halves of A / of B; a diagonal tile's
+    // block below the diagonal mirrors one above it and is never read; f32 path: a last half of at most 16 live B rows goes to the
+    // 16-column edge routine (GAUSS_GRAM_EDGE16 compiled in).  Staging (run_item) keeps the physical wave index: which 16-row
+    // groups a wave requests does not depend on its block.
+    constexpr bool F32 = std::is_same<ACC, f32x16>::value;
+    const int layout = (it.flags >> LAYOUT_SHIFT) & 3;
+    const WaveRole ro = wave_role(wave, layout);
+    const int r0 = ro.r0, c0 = ro.c0;
     const bool diag = (it.flags & 1) != 0;
-    if (diag && wr == 1 && wc == 0) na = 0;
-    // f32 path: a last half of at most 16 live B rows goes to the 16-column edge routine (GAUSS_GRAM_EDGE16 compiled in)
-    int nc = 0;
-    if (std::is_same<ACC, f32x16>::value && GAUSS_GRAM_EDGE16 && na > 0) {
-        int nb16 = (it.rows_b - wc * 64 + 15) / 16;
-        nb16 = nb16 < 0 ? 0 : (nb16 > 4 ? 4 : nb16);
-        if (nb16 & 1) nc = nb16;
-    }
+    const WaveWork ww = wave_work(it.rows_a, it.rows_b, diag, F32 && (it.flags & 4) != 0, F32 && GAUSS_GRAM_EDGE16, wave, layout);
+    const int na = ww.na, nb = ww.nb, nc = ww.nc;
     // f32 path, items with flag bit 2 (16-bit slabs, codes <= 3; the planner sets it unless GAUSS_GRAM_PACKED=0): two A rows per lane
     if constexpr (std::is_same<ACC, f32x16>::value) {
         if (it.flags & 4) {
-            if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3, true>(it, lds, wr, wc, pkf); else run_item<1, 0, ACC, NS, false, 3, true>(it, lds, wr, wc, pkf); }
-            else if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1, true>(it, lds, wr, wc, pkf); else run_item<1, 0, ACC, NS, false, 1, true>(it, lds, wr, wc, pkf); }
-            else if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, wr, wc, pkf);
-            else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS, false, 0, true>(it, lds, wr, wc, pkf);       // (a diagonal wave too: its mirrored block costs no MFMA here)
-            else if (na == 2) run_item<2, 1, ACC, NS, false, 0, true>(it, lds, wr, wc, pkf);
-            else if (nb == 2) run_item<1, 2, ACC, NS, false, 0, true>(it, lds, wr, wc, pkf);
-            else run_item<1, 1, ACC, NS, false, 0, true>(it, lds, wr, wc, pkf);
+            if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3, true>(it, lds, r0, c0, pkf); else run_item<1, 0, ACC, NS, false, 3, true>(it, lds, r0, c0, pkf); }
+            else if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1, true>(it, lds, r0, c0, pkf); else run_item<1, 0, ACC, NS, false, 1, true>(it, lds, r0, c0, pkf); }
+            else if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, r0, c0, pkf);
+            else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS, false, 0, true>(it, lds, r0, c0, pkf);       // (a diagonal wave too: its mirrored block costs no MFMA here)
+            else if (na == 2) run_item<2, 1, ACC, NS, false, 0, true>(it, lds, r0, c0, pkf);
+            else if (nb == 2) run_item<1, 2, ACC, NS, false, 0, true>(it, lds, r0, c0, pkf);
+            else run_item<1, 1, ACC, NS, false, 0, true>(it, lds, r0, c0, pkf);
             return;
         }
     }
-    if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3>(it, lds, wr, wc, pkf); else run_item<1, 0, ACC, NS, false, 3>(it, lds, wr, wc, pkf); return; }
-    if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1>(it, lds, wr, wc, pkf); else run_item<1, 0, ACC, NS, false, 1>(it, lds, wr, wc, pkf); return; }
-    if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, wr, wc, pkf);
-    else if (na == 2 && nb == 2 && diag && wr == wc) run_item<2, 2, ACC, NS, true>(it, lds, wr, wc, pkf);
-    else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS>(it, lds, wr, wc, pkf);
-    else if (na == 2) run_item<2, 1, ACC, NS>(it, lds, wr, wc, pkf);
-    else if (nb == 2) run_item<1, 2, ACC, NS>(it, lds, wr, wc, pkf);
-    else run_item<1, 1, ACC, NS>(it, lds, wr, wc, pkf);
+    if (nc == 3) { if (na == 2) run_item<2, 0, ACC, NS, false, 3>(it, lds, r0, c0, pkf); else run_item<1, 0, ACC, NS, false, 3>(it, lds, r0, c0, pkf); return; }
+    if (nc == 1) { if (na == 2) run_item<2, 0, ACC, NS, false, 1>(it, lds, r0, c0, pkf); else run_item<1, 0, ACC, NS, false, 1>(it, lds, r0, c0, pkf); return; }
+    if (na == 0 || nb == 0) run_item<0, 0, ACC, NS>(it, lds, r0, c0, pkf);
+    else if (ww.sk10) run_item<2, 2, ACC, NS, true>(it, lds, r0, c0, pkf);
+    else if (na == 2 && nb == 2) run_item<2, 2, ACC, NS>(it, lds, r0, c0, pkf);
+    else if (na == 2) run_item<2, 1, ACC, NS>(it, lds, r0, c0, pkf);
+    else if (nb == 2) run_item<1, 2, ACC, NS>(it, lds, r0, c0, pkf);
+    else run_item<1, 1, ACC, NS>(it, lds, r0, c0, pkf);
 }
 
 // 104 registers at most: four workgroups per CU then leave 96 per lane for the small-footprint kernels that run beside this one
