@@ -325,6 +325,18 @@ struct Plan {
     size_t res_off = 0;                      // offset (in doubles) of this problem's z in the result block
 };
 
+// The largest dimensions among the windows of one fitting launch (k_susie.hip, k_xsusie.hip): M, U (of those that fit unmeasured
+// candidates) and M + U, the most effects, sweeps and 64-row blocks of X
+struct FitDims {
+    int M = 0, U = 0, T = 0, L = 0, sweeps = 0, nblk = 0;
+    void grow(const Prob& p, const Plan::Riders& rd)
+    {
+        M = std::max(M, p.M); T = std::max(T, p.M + p.U);
+        L = std::max(L, rd.susie_L); sweeps = std::max(sweeps, p.susie_max_sweeps);
+        if (!p.susie_measured_only) { U = std::max(U, p.U); nblk = std::max(nblk, p.nblk); }
+    }
+};
+
 struct ProfSlot { hipEvent_t a, b; int kernel; unsigned run; int launches = 1; };      // run: gauss_job::run_seq of the run that recorded it;
                                                                                         // launches: kernel launches the slot spans
 
@@ -378,12 +390,11 @@ struct gauss_job {
     int prs_max_s = 0, prs_max_M = 0;                      // ... the most chains and the most measured SNPs one of them has
     int cs_max_T = 0;                                      // ... and the most candidates (M + U) one of them has
     int* d_susiemap = nullptr;  int n_susie = 0;           // multi-causal fine-mapping: the windows that asked
-    int susie_max_M = 0, susie_max_U = 0, susie_max_T = 0; // ... the largest M, U (of those that fit unmeasured candidates) and M + U among them,
-    int susie_max_L = 0, susie_max_sweeps = 0, susie_max_nblk = 0;      // the most effects, sweeps and 64-row blocks of X
+    FitDims susie_dims;                                    // ... their largest dimensions
     int susie_max_k = 0;  bool susie_coloc = false;        // ... the most further traits in one fit; a window asks for the colocalisation
     int* d_xsmap = nullptr;     int n_xs = 0;              // joint fit across studies: the windows that are members of a group (they are not in d_susiemap)
     int* d_xsleadmap = nullptr; int n_xs_lead = 0;         // ... the leaders among them
-    int xs_max_M = 0, xs_max_U = 0, xs_max_T = 0, xs_max_L = 0, xs_max_sweeps = 0, xs_max_nblk = 0;      // ... as susie_max_*, over the members
+    FitDims xs_dims;                                       // ... as susie_dims, over the members
     int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
     int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
     int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some

@@ -583,15 +583,90 @@ static int plan_xs_groups(const std::vector<WinSpec>& specs, std::vector<Plan>& 
     return GAUSS_OK;
 }
 
-// streamed: one window on contiguous host matrices whose upload is left to job_run_streamed (chunk by chunk on the
-// copy stream, overlapped with the pack / Gram launches of the rows that have landed)
-int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, gauss_job** out, const StreamSetup* stream)
+// ---- job_build: the planned windows of a batch -> tables, work lists, workspace and device descriptors ----
+
+// live rows of row tile t of a plan (the job-wide rows keep a table: their clusters end in padding rows)
+static inline int live_rows(const Plan& pl, int t)
 {
-    const bool streamed = stream != nullptr;
-    const auto tb0 = std::chrono::steady_clock::now();
-    gauss_job* job = new gauss_job();
-    // every early return below (bad arguments, a failed HIP call) releases the job and what it owns
-    std::unique_ptr<gauss_job, void (*)(gauss_job*)> guard(job, job_free);
+    const Prob& p = pl.p;
+    const int mt = p.Mp / TILE;
+    if (!pl.tile_live.empty()) return pl.tile_live[(size_t)t];
+    const int left = (t < mt) ? p.M - t * TILE : p.U - (t - mt) * TILE;
+    return left > TILE ? TILE : left;
+}
+// f(ti, tj) for every job-wide tile pair ti <= tj that `rows` measured rows from job-wide row `row0` on lie in
+template <typename F>
+static void for_tile_pairs(size_t row0, size_t rows, F f)
+{
+    const int lo = (int)(row0 / TILE), hi = (int)((row0 + rows - 1) / TILE);
+    for (int ti = lo; ti <= hi; ti++)
+        for (int tj = ti; tj <= hi; tj++) f(ti, tj);
+}
+struct ItemH { int prob, pair, group, len, b11, ord = 0; };     // b11: an item of B11 (job-wide pairs, or a window's own measured x measured pairs); ord: launch-order key (item_keys)
+
+// What job_build's steps share.  Name once, bind later: the device bases are known only after the allocations, so a table,
+// a map or a workspace block is named ONCE, where it is placed -- tab() copies a host vector into the table image, ws() and
+// slab() take a block of the zeroed workspace or of the slab arena -- and each call records (the pointer field, the offset,
+// the base); relocate() writes base + offset into every recorded field.  The fields live in job->plans (sized before the first
+// call), in *job->gplan and in the job itself: none of them moves while the job is built.
+struct JobBuild {
+    gauss_ctx* ctx;
+    const std::vector<WinSpec>& specs;
+    int on_device;
+    const StreamSetup* stream;
+    gauss_job* job;
+    bool streamed() const { return stream != nullptr; }
+    bool shm() const { return job->gplan != nullptr; }
+    int n_prob() const { return job->n + (shm() ? 1 : 0); }      // descriptors on the device: the windows, then the job-wide rows
+    Plan& plan_of(int i) const { return i < job->n ? job->plans[i] : *job->gplan; }
+    size_t exp_doubles = 0;                                // doubles of the pinned export mirror
+    std::vector<ItemH> items;
+    std::vector<uint8_t> item_class;                       // launch class of items[n]: 0 B11 (or everything), 1 early B21, 2 late B21
+    std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
+    std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
+    std::vector<int> slctmap, condmap, csmap, susiemap, xsmap, xsleadmap, prsmap;
+    std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
+    std::vector<const uint32_t*> chunk_live;               // per descriptor: its Plan::chunk_live on the device (Item::chunk_live)
+    Arena ta;         // table image (job->h_tab)
+    Arena wa;         // zeroed once per job: operand padding, B21 padding and the solve matrices rely on it
+    Arena wslab;      // partial slabs: every entry a reader keeps is written by the Gram kernel first, so no zeroing
+    size_t o_items = 0, o_probs = 0, o_exports = 0, slab_base = 0, res = 0;
+    size_t pin_tab = 0, pin_res = 0, pin_st = 0;
+    std::deque<std::vector<uint8_t>> stage;                // host gather buffers, alive until the copies have drained
+
+    enum Base { TAB, WS, SLAB };
+    struct Reloc { void* field; size_t off; Base base; };
+    std::vector<Reloc> rel;
+    template <typename P> size_t at(P*& field, size_t off, Base base, bool bound = true)
+    { field = nullptr; if (bound) rel.push_back(Reloc{(void*)&field, off, base}); return off; }
+    // a host vector in the table image (an empty one still takes its 256 bytes); !bound: placed all the same, the field stays null
+    template <typename P, typename V> void tab(P*& field, const std::vector<V>& v, bool bound = true)
+    {
+        static_assert(sizeof(P) == sizeof(V), "the field points to the vector's elements");
+        at(field, put(job->h_tab, ta, v), TAB, bound);
+    }
+    // a work list and its count (a list that nobody asked for takes nothing and points to the image's start)
+    template <typename P, typename V> void tab(P*& field, int& count, const std::vector<V>& v, bool if_any = false)
+    { count = (int)v.size(); if (if_any && v.empty()) at(field, 0, TAB); else tab(field, v); }
+    template <typename P> size_t tab_block(P*& field, size_t bytes) { return at(field, ta.take(bytes), TAB); }      // written later, at the offset returned
+    template <typename P> void ws(P*& field, size_t bytes, bool bound = true) { at(field, wa.take(bytes), WS, bound); }
+    template <typename P> void slab(P*& field, size_t bytes) { at(field, wslab.take(bytes), SLAB); }
+    void relocate()
+    {
+        char* const base[3] = {job->d_tab, job->d_ws, job->d_ws + slab_base};
+        for (const Reloc& r : rel) { char* const addr = base[r.base] + r.off; memcpy(r.field, &addr, sizeof(addr)); }
+    }
+    // the steps, in job_build's order; each returns a status
+    int plan_windows(), plan_exports(), share_measured(), check_row_lists(), place_all_tables(), work_lists(), order_items(), place_lists();
+    int layout_workspace(), allocate(), events_and_zeroing(), bind(), upload_host_rows(), write_items(), fill_report(), export_descriptors();
+    int upload_tables();
+    // ... and their parts
+    void place_tables(Plan& pl, const uint32_t*& d_chunk_live, bool window), layout_window(Plan& pl);
+    void item_keys(), sort_items(), launch_classes(), stream_groups(), xcd_interleave();
+    int upload_rows(const Plan& pl, const uint8_t* dst_rows, const uint8_t* src, const std::vector<int32_t>& rows, int nrows);
+};
+int JobBuild::plan_windows()
+{
     job->ctx = ctx;
     job->n = (int)specs.size();
     job->on_device = on_device;
@@ -604,7 +679,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
     job->gram_narrow = (!ctx->gram_i8 && env_int("GAUSS_GRAM_ROTATE", 1) != 0 && env_int("GAUSS_GRAM_NARROW", 1) != 0) ? 1 : 0;
     job->plans.resize(job->n);
     for (const WinSpec& w : specs)
-        if (w.draw_pop && (specs.size() != 1 || streamed)) return fail(GAUSS_E_INVALID, "a resampled window is a job of its own");
+        if (w.draw_pop && (specs.size() != 1 || streamed())) return fail(GAUSS_E_INVALID, "a resampled window is a job of its own");
     const int seg_max = seg_max_for(specs);
     for (int i = 0; i < job->n; i++) {
         int rc = plan_problem(specs[i], job->plans[i], seg_max, group_target_for(specs.size()));
@@ -612,122 +687,115 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         job->plans[i].p.gram_i8 = job->gram_i8;
         if (!job->plans[i].draw_col.empty()) job->resample_lds = resample_pack_lds_bytes(job->plans[i].p.row_src_bytes);
     }
-    {
-        const int rc = plan_xs_groups(specs, job->plans);
-        if (rc) return rc;
+    return plan_xs_groups(specs, job->plans);
+}
+// Matrix exports (gauss_job.h): which matrices the caller wants back, and where each lands in the pinned mirror
+int JobBuild::plan_exports()
+{
+    if (streamed()) return GAUSS_OK;
+    for (int i = 0; i < job->n; i++) {
+        const Plan& pl = job->plans[i];
+        const Prob& p = pl.p;
+        const bool has = p.kind == GAUSS_WIN_LD || p.npanel > 0;          // (the windows gauss_job_fetch exports matrices for)
+        if (!has) continue;
+        if (pl.out_b11) { job->exports.push_back(gauss_job::Export{i, 0, exp_doubles, p.M, p.M, p.Mld, pl.out_b11}); exp_doubles += (size_t)p.M * p.M; }
+        if (pl.out_b21 && p.U > 0) { job->exports.push_back(gauss_job::Export{i, 1, exp_doubles, p.U, p.M, p.Mld, pl.out_b21}); exp_doubles += (size_t)p.U * p.M; }
+        exp_doubles = rup(exp_doubles, 32);                                // every window's block starts on a 256-byte boundary
     }
-    // Matrix exports (gauss_job.h): which matrices the caller wants back, and where each lands in the pinned mirror
-    size_t exp_doubles = 0;
-    if (!streamed) {
-        for (int i = 0; i < job->n; i++) {
-            const Plan& pl = job->plans[i];
-            const Prob& p = pl.p;
-            const bool has = p.kind == GAUSS_WIN_LD || p.npanel > 0;          // (the windows gauss_job_fetch exports matrices for)
-            if (!has) continue;
-            if (pl.out_b11) { job->exports.push_back(gauss_job::Export{i, 0, exp_doubles, p.M, p.M, p.Mld, pl.out_b11}); exp_doubles += (size_t)p.M * p.M; }
-            if (pl.out_b21 && p.U > 0) { job->exports.push_back(gauss_job::Export{i, 1, exp_doubles, p.U, p.M, p.Mld, pl.out_b21}); exp_doubles += (size_t)p.U * p.M; }
-            exp_doubles = rup(exp_doubles, 32);                                // every window's block starts on a 256-byte boundary
-        }
-        if (exp_doubles * sizeof(double) > ((size_t)256 << 20)) { job->exports.clear(); exp_doubles = 0; }      // pinned budget: per matrix instead
-    }
-    const auto tb1 = std::chrono::steady_clock::now();
-    // Shared measured rows: every window reads its measured SNPs from the same resident store under the same populations.
-    // The job keeps ONE list of measured rows, made of CLUSTERS: a window whose rows continue a run of the current cluster
-    // (the next window of a chromosome: half its measured SNPs are the previous window's) joins it at that offset -- when
-    // that costs no more B11 tile pairs than tiles of its own would -- and every other window starts a new cluster on a
-    // tile boundary (padding rows in between: never packed, all zero), where it costs exactly what its own tiles would.
-    // So sharing can only save work: the scattered windows of a multi-GPU share keep their own tiles, two neighbours that
-    // landed on the same rank share theirs (round 3 had one all-or-nothing list whose tiles started where the LIST started:
-    // a share's scattered windows paid an extra row tile each and sharing was switched off for them).
-    if (on_device && !streamed && job->n >= 2 && env_int("GAUSS_SHARE_MEASURED", 1) != 0) {
-        const Plan& a = job->plans[0];
-        bool ok = true;
-        std::vector<int32_t> gl;
-        std::vector<int> g0((size_t)job->n, 0);
-        std::set<std::pair<int, int>> have;                     // job-wide B11 tile pairs so far
-        size_t cl0 = 0, own_pairs = 0;                          // start of the current cluster in gl
-        for (int i = 0; i < job->n && ok; i++) {
-            const Plan& b = job->plans[i];
-            ok = !b.rows_m.empty() && !b.p.ld_only && !b.p.n_gene && b.p.P <= 32 && b.h_geno_m == a.h_geno_m && b.user_ld == a.user_ld &&
-                 b.p.mode == a.p.mode && b.p.P == a.p.P && b.p.geno_fmt == a.p.geno_fmt && b.p.slab16 == a.p.slab16 && b.p.Kp == a.p.Kp &&
-                 b.pop_raw_off == a.pop_raw_off && b.pop_pk_off == a.pop_pk_off && b.pop_w == a.pop_w && b.seg_k0 == a.seg_k0 &&
-                 b.seg_k1 == a.seg_k1 && b.seg_pop == a.seg_pop && b.run_src == a.run_src && b.run_pk_off == a.run_pk_off &&
-                 b.groups == a.groups;
-            if (!ok) break;
-            const size_t M = b.rows_m.size(), mt = (M + TILE - 1) / TILE;
-            own_pairs += mt * (mt + 1) / 2;
-            // does the window continue a run of the current cluster?  (the cluster is ascending where that matters: a window
-            // only joins through a binary search for its first row and an element-wise comparison of the overlap)
-            size_t pos = gl.size();
-            bool join = false;
-            if (gl.size() > cl0 && std::is_sorted(gl.begin() + (ptrdiff_t)cl0, gl.end())) {
-                const int32_t first = b.rows_m[0];
-                const size_t p0 = (size_t)(std::lower_bound(gl.begin() + (ptrdiff_t)cl0, gl.end(), first) - gl.begin());
-                if (p0 < gl.size() && gl[p0] == first) {
-                    join = true;
-                    for (size_t k = 0; k < M && join; k++) {
-                        if (k > 0 && b.rows_m[k] <= b.rows_m[k - 1]) join = false;
-                        else if (p0 + k < gl.size() && gl[p0 + k] != b.rows_m[k]) join = false;
-                    }
-                    if (join) {
-                        // tile pairs the window would ADD as part of the cluster, against tiles of its own
-                        const int lo = (int)(p0 / TILE), hi = (int)((p0 + M - 1) / TILE);
-                        size_t add = 0;
-                        for (int ti = lo; ti <= hi; ti++)
-                            for (int tj = ti; tj <= hi; tj++) add += have.count(std::make_pair(ti, tj)) ? 0 : 1;
-                        join = add <= mt * (mt + 1) / 2;
-                        pos = p0;
-                    }
+    if (exp_doubles * sizeof(double) > ((size_t)256 << 20)) { job->exports.clear(); exp_doubles = 0; }      // pinned budget: per matrix instead
+    return GAUSS_OK;
+}
+// Shared measured rows: every window reads its measured SNPs from the same resident store under the same populations.
+// The job keeps ONE list of measured rows, made of CLUSTERS: a window whose rows continue a run of the current cluster
+// (the next window of a chromosome: half its measured SNPs are the previous window's) joins it at that offset -- when
+// that costs no more B11 tile pairs than tiles of its own would -- and every other window starts a new cluster on a
+// tile boundary (padding rows in between: never packed, all zero), where it costs exactly what its own tiles would.
+// So sharing can only save work: the scattered windows of a multi-GPU share keep their own tiles, two neighbours that
+// landed on the same rank share theirs (round 3 had one all-or-nothing list whose tiles started where the LIST started:
+// a share's scattered windows paid an extra row tile each and sharing was switched off for them).
+int JobBuild::share_measured()
+{
+    if (!(on_device && !streamed() && job->n >= 2 && env_int("GAUSS_SHARE_MEASURED", 1) != 0)) return GAUSS_OK;
+    const Plan& a = job->plans[0];
+    bool ok = true;
+    std::vector<int32_t> gl;
+    std::vector<int> g0((size_t)job->n, 0);
+    std::set<std::pair<int, int>> have;                     // job-wide B11 tile pairs so far
+    size_t cl0 = 0, own_pairs = 0;                          // start of the current cluster in gl
+    for (int i = 0; i < job->n && ok; i++) {
+        const Plan& b = job->plans[i];
+        ok = !b.rows_m.empty() && !b.p.ld_only && !b.p.n_gene && b.p.P <= 32 && b.h_geno_m == a.h_geno_m && b.user_ld == a.user_ld &&
+             b.p.mode == a.p.mode && b.p.P == a.p.P && b.p.geno_fmt == a.p.geno_fmt && b.p.slab16 == a.p.slab16 && b.p.Kp == a.p.Kp &&
+             b.pop_raw_off == a.pop_raw_off && b.pop_pk_off == a.pop_pk_off && b.pop_w == a.pop_w && b.seg_k0 == a.seg_k0 &&
+             b.seg_k1 == a.seg_k1 && b.seg_pop == a.seg_pop && b.run_src == a.run_src && b.run_pk_off == a.run_pk_off &&
+             b.groups == a.groups;
+        if (!ok) break;
+        const size_t M = b.rows_m.size(), mt = (M + TILE - 1) / TILE;
+        own_pairs += mt * (mt + 1) / 2;
+        // does the window continue a run of the current cluster?  (the cluster is ascending where that matters: a window
+        // only joins through a binary search for its first row and an element-wise comparison of the overlap)
+        size_t pos = gl.size();
+        bool join = false;
+        if (gl.size() > cl0 && std::is_sorted(gl.begin() + (ptrdiff_t)cl0, gl.end())) {
+            const int32_t first = b.rows_m[0];
+            const size_t p0 = (size_t)(std::lower_bound(gl.begin() + (ptrdiff_t)cl0, gl.end(), first) - gl.begin());
+            if (p0 < gl.size() && gl[p0] == first) {
+                join = true;
+                for (size_t k = 0; k < M && join; k++) {
+                    if (k > 0 && b.rows_m[k] <= b.rows_m[k - 1]) join = false;
+                    else if (p0 + k < gl.size() && gl[p0 + k] != b.rows_m[k]) join = false;
+                }
+                if (join) {
+                    // tile pairs the window would ADD as part of the cluster, against tiles of its own
+                    size_t add = 0;
+                    for_tile_pairs(p0, M, [&](int ti, int tj) { add += have.count(std::make_pair(ti, tj)) ? 0 : 1; });
+                    join = add <= mt * (mt + 1) / 2;
+                    pos = p0;
                 }
             }
-            if (!join) {
-                gl.resize(rup(gl.size(), TILE), -1);               // a new cluster on a tile boundary (padding rows: never packed)
-                cl0 = pos = gl.size();
-            }
-            g0[(size_t)i] = (int)pos;
-            for (size_t k = 0; k < M; k++)
-                if (pos + k >= gl.size()) gl.push_back(b.rows_m[k]);
-            const int lo = (int)(pos / TILE), hi = (int)((pos + M - 1) / TILE);
-            for (int ti = lo; ti <= hi; ti++)
-                for (int tj = ti; tj <= hi; tj++) have.insert(std::make_pair(ti, tj));
         }
-        // worth the extra descriptor only if something IS shared (GAUSS_SHARE_MEASURED=2: always, for the tests)
-        if (ok && (long long)gl.size() < (1 << 24) && (have.size() < own_pairs || env_int("GAUSS_SHARE_MEASURED", 1) == 2)) {
-            job->gplan.reset(new Plan(a));
-            job->g0 = g0;
-            Plan& g = *job->gplan;
-            g.rows_m = gl;
-            g.rows_u.clear(); g.z1.clear(); g.gene_off.clear(); g.gene_out_off.clear();
-            Prob& q = g.p;
-            q.M = (int)gl.size(); q.U = 0; q.U_raw = 1; q.n_rhs = 0;
-            q.Mp = (int)rup((size_t)q.M, TILE); q.Up = 0; q.Sp = q.Mp; q.nT = q.Mp / TILE;
-            q.Mld = 0; q.nblk = 0; q.npanel = 0; q.npi = 0; q.kind = 0; q.ld_only = 0; q.n_head = q.n_predm = 0;
-            g.U_user = 0; g.h_geno_u = nullptr; g.rd = Plan::Riders(); clear_riders(q);
-            // job-wide B11 pairs: the tile pairs some window lies in
-            g.pair_ti.clear(); g.pair_tj.clear(); g.pair_lut.assign((size_t)q.nT * q.nT, -1);
-            for (int i = 0; i < job->n; i++) {
-                const int lo = g0[(size_t)i] / TILE, hi = (g0[(size_t)i] + job->plans[i].p.M - 1) / TILE;
-                for (int ti = lo; ti <= hi; ti++)
-                    for (int tj = ti; tj <= hi; tj++)
-                        if (g.pair_lut[(size_t)ti * q.nT + tj] < 0) {
-                            g.pair_lut[(size_t)ti * q.nT + tj] = g.pair_lut[(size_t)tj * q.nT + ti] = (int)g.pair_ti.size();
-                            g.pair_ti.push_back(ti); g.pair_tj.push_back(tj);
-                        }
-            }
-            q.npair = (int)g.pair_ti.size();
-            // live rows per job-wide row tile: up to the last real row in it (a cluster's last tile ends in padding rows, whose
-            // dead 32-row halves the Gram kernel skips exactly as it does in a window's own last tile)
-            g.tile_live.assign((size_t)q.nT, 0);
-            for (size_t r = 0; r < gl.size(); r++)
-                if (gl[r] >= 0) g.tile_live[r / TILE] = (int)(r % TILE) + 1;
+        if (!join) {
+            gl.resize(rup(gl.size(), TILE), -1);               // a new cluster on a tile boundary (padding rows: never packed)
+            cl0 = pos = gl.size();
         }
+        g0[(size_t)i] = (int)pos;
+        for (size_t k = 0; k < M; k++)
+            if (pos + k >= gl.size()) gl.push_back(b.rows_m[k]);
+        for_tile_pairs(pos, M, [&](int ti, int tj) { have.insert(std::make_pair(ti, tj)); });
     }
-    const bool shm = job->gplan != nullptr;
-    const int n_prob = job->n + (shm ? 1 : 0);             // descriptors on the device: the windows, then the job-wide rows
-    auto plan_of = [&](int i) -> Plan& { return i < job->n ? job->plans[i] : *job->gplan; };
-
-    // Row lists are resolved by the pack kernel: an index beyond the store would be an out-of-bounds read on the
-    // GPU.  Host stores cannot be checked (only a pointer is known), stores made by gauss_store_upload can.
+    // worth the extra descriptor only if something IS shared (GAUSS_SHARE_MEASURED=2: always, for the tests)
+    if (!(ok && (long long)gl.size() < (1 << 24) && (have.size() < own_pairs || env_int("GAUSS_SHARE_MEASURED", 1) == 2))) return GAUSS_OK;
+    job->gplan.reset(new Plan(a));
+    job->g0 = g0;
+    Plan& g = *job->gplan;
+    g.rows_m = gl;
+    g.rows_u.clear(); g.z1.clear(); g.gene_off.clear(); g.gene_out_off.clear();
+    Prob& q = g.p;
+    q.M = (int)gl.size(); q.U = 0; q.U_raw = 1; q.n_rhs = 0;
+    q.Mp = (int)rup((size_t)q.M, TILE); q.Up = 0; q.Sp = q.Mp; q.nT = q.Mp / TILE;
+    q.Mld = 0; q.nblk = 0; q.npanel = 0; q.npi = 0; q.kind = 0; q.ld_only = 0; q.n_head = q.n_predm = 0;
+    g.U_user = 0; g.h_geno_u = nullptr; g.rd = Plan::Riders(); clear_riders(q);
+    // job-wide B11 pairs: the tile pairs some window lies in
+    g.pair_ti.clear(); g.pair_tj.clear(); g.pair_lut.assign((size_t)q.nT * q.nT, -1);
+    for (int i = 0; i < job->n; i++)
+        for_tile_pairs((size_t)g0[(size_t)i], (size_t)job->plans[i].p.M, [&](int ti, int tj) {
+            if (g.pair_lut[(size_t)ti * q.nT + tj] < 0) {
+                g.pair_lut[(size_t)ti * q.nT + tj] = g.pair_lut[(size_t)tj * q.nT + ti] = (int)g.pair_ti.size();
+                g.pair_ti.push_back(ti); g.pair_tj.push_back(tj);
+            }
+        });
+    q.npair = (int)g.pair_ti.size();
+    // live rows per job-wide row tile: up to the last real row in it (a cluster's last tile ends in padding rows, whose
+    // dead 32-row halves the Gram kernel skips exactly as it does in a window's own last tile)
+    g.tile_live.assign((size_t)q.nT, 0);
+    for (size_t r = 0; r < gl.size(); r++)
+        if (gl[r] >= 0) g.tile_live[r / TILE] = (int)(r % TILE) + 1;
+    return GAUSS_OK;
+}
+// Row lists are resolved by the pack kernel: an index beyond the store would be an out-of-bounds read on the
+// GPU.  Host stores cannot be checked (only a pointer is known), stores made by gauss_store_upload can.
+int JobBuild::check_row_lists()
+{
     std::map<const void*, size_t> stores;
     { std::lock_guard<std::mutex> lock(ctx->mu); stores = ctx->stores; }
     for (int i = 0; i < job->n; i++) {
@@ -754,53 +822,42 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
             }
         }
     }
-    HIPCHK(hipSetDevice(ctx->device));
-
-    // ---- table arena (host mirrored) ----
-    Arena ta;
-    std::vector<char>& blob = job->h_tab;
-    blob.reserve((size_t)n_prob * ((size_t)320 << 10) + ((size_t)64 << 10));      // (~0.3 MB a window: grown in place, not copied over and over)
-    const auto tb2 = std::chrono::steady_clock::now();
-    struct TabOff { size_t raw_off, pk_off, w, wf, md, seg_pop, k0, k1, seg0, ti, tj, lut, wp, z1, goff, gout, wr, rpk, rsrc, rm, ru, ch, dc, sf, tz, mt, xf, xt; };
-    std::vector<TabOff> to((size_t)n_prob);
-    for (int i = 0; i < n_prob; i++) {
-        Plan& pl = plan_of(i);
-        to[i].raw_off = put(blob, ta, pl.pop_raw_off);
-        to[i].pk_off = put(blob, ta, pl.pop_pk_off);
-        to[i].w = put(blob, ta, pl.pop_w);
-        to[i].wf = put(blob, ta, pl.pop_wf);
-        to[i].md = put(blob, ta, pl.pop_md);
-        to[i].seg_pop = put(blob, ta, pl.seg_pop);
-        to[i].k0 = put(blob, ta, pl.seg_k0);
-        to[i].k1 = put(blob, ta, pl.seg_k1);
-        to[i].seg0 = put(blob, ta, pl.pop_seg0);
-        to[i].ti = put(blob, ta, pl.pair_ti);
-        to[i].tj = put(blob, ta, pl.pair_tj);
-        to[i].lut = put(blob, ta, pl.pair_lut);
-        to[i].wp = put(blob, ta, pl.word_pop);
-        to[i].z1 = put(blob, ta, pl.z1);
-        to[i].goff = put(blob, ta, pl.gene_off);
-        to[i].gout = put(blob, ta, pl.gene_out_off);
-        to[i].wr = put(blob, ta, pl.word_run);
-        to[i].rpk = put(blob, ta, pl.run_pk_off);
-        to[i].rsrc = put(blob, ta, pl.run_src);
-        to[i].rm = put(blob, ta, pl.rows_m);
-        to[i].ru = put(blob, ta, pl.rows_u);
-        to[i].ch = put(blob, ta, pl.chunk_live);
-        to[i].dc = put(blob, ta, pl.draw_col);
-        to[i].sf = pl.rd.slct_forced.empty() ? 0 : put(blob, ta, pl.rd.slct_forced);
-        to[i].tz = pl.rd.traits_z.empty() ? 0 : put(blob, ta, pl.rd.traits_z);
-        to[i].mt = pl.rd.miss_tab.empty() ? 0 : put(blob, ta, pl.rd.miss_tab);
-        to[i].xf = pl.rd.xs_from_lead.empty() ? 0 : put(blob, ta, pl.rd.xs_from_lead);
-        to[i].xt = pl.rd.xs_to_lead.empty() ? 0 : put(blob, ta, pl.rd.xs_to_lead);
-    }
-    // work lists
-    struct ItemH { int prob, pair, group, len, b11, ord = 0; };     // b11: an item of B11 (job-wide pairs, or a window's own measured x measured pairs); ord: launch-order key (below)
-    std::vector<ItemH> items;
-    std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
-    std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
-    std::vector<int> slctmap, condmap, csmap, susiemap, xsmap, xsleadmap, prsmap;
-    std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
+    return GAUSS_OK;
+}
+// The tables of one descriptor -- a window's, or the job-wide measured rows' -- in the order of the image.  Every list of the
+// plan is placed, asked or not (the image does not depend on who reads it); the riders' lists only where they exist.
+void JobBuild::place_tables(Plan& pl, const uint32_t*& d_chunk_live, bool window)
+{
+    Prob& p = pl.p;
+    tab(p.pop_raw_off, pl.pop_raw_off); tab(p.pop_pk_off, pl.pop_pk_off);
+    tab(p.pop_w, pl.pop_w); tab(p.pop_wf, pl.pop_wf); tab(p.pop_md, pl.pop_md);
+    tab(p.seg_pop, pl.seg_pop); tab(p.seg_k0, pl.seg_k0); tab(p.seg_k1, pl.seg_k1); tab(p.pop_seg0, pl.pop_seg0);
+    tab(p.pair_ti, pl.pair_ti); tab(p.pair_tj, pl.pair_tj); tab(p.pair_lut, pl.pair_lut);
+    tab(p.word_pop, pl.word_pop);
+    tab(p.z1, pl.z1, window);      // (the job-wide rows have no Z-scores)
+    tab(p.gene_off, pl.gene_off, p.n_gene != 0); tab(p.gene_out_off, pl.gene_out_off, p.n_gene != 0);
+    tab(p.word_run, pl.word_run); tab(p.run_pk_off, pl.run_pk_off); tab(p.run_src, pl.run_src);
+    // row lists are resolved on the device only for a resident store; host rows are gathered while staging
+    tab(p.rows_m, pl.rows_m, on_device && !pl.rows_m.empty()); tab(p.rows_u, pl.rows_u, on_device && !pl.rows_u.empty());
+    tab(d_chunk_live, pl.chunk_live);
+    tab(p.draw_col, pl.draw_col, !pl.draw_col.empty());
+    if (!pl.rd.slct_forced.empty()) tab(p.slct_forced, pl.rd.slct_forced);
+    if (!pl.rd.traits_z.empty()) tab(p.traits_Z, pl.rd.traits_z, pl.rd.traits_T != 0);
+    if (!pl.rd.miss_tab.empty()) tab(p.miss_tab, pl.rd.miss_tab, pl.rd.miss);
+    if (!pl.rd.xs_from_lead.empty()) tab(p.xs_from_lead, pl.rd.xs_from_lead);
+    if (!pl.rd.xs_to_lead.empty()) tab(p.xs_to_lead, pl.rd.xs_to_lead);
+}
+// ---- table arena (host mirrored) ----
+int JobBuild::place_all_tables()
+{
+    rel.reserve((size_t)n_prob() * 64 + 64);
+    chunk_live.assign((size_t)n_prob(), nullptr);
+    for (int i = 0; i < n_prob(); i++) place_tables(plan_of(i), chunk_live[(size_t)i], i < job->n);
+    return GAUSS_OK;
+}
+// The work items of the Gram launch and the work lists of every other launch, in window order; the riders' largest dimensions
+int JobBuild::work_lists()
+{
     job->max_nblk = 0;
     {
         // tiles of the closing product at 128 right-hand sides each: a small job (an 8-rank share: ~570) cannot fill the
@@ -813,7 +870,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         job->gemm_ut = t128 < (size_t)GEMM_SMALL_TILES ? 64 : 128;
     }
     job->win_tiles.assign((size_t)job->n, std::vector<int2>());
-    if (shm) {
+    if (shm()) {
         // the job-wide measured rows are packed once, and B11's job-wide tile pairs multiplied once
         const Plan& g = *job->gplan;
         for (int pr = 0; pr < g.p.npair; pr++)
@@ -834,7 +891,7 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         const int mt_i = p.Mp / TILE;
         for (int pr = 0; pr < p.npair; pr++) {
             const int b11 = job->plans[i].pair_ti[pr] < mt_i ? 1 : 0;
-            if (shm && b11) continue;                                    // a B11 pair: done on the job-wide tiles
+            if (shm() && b11) continue;                                    // a B11 pair: done on the job-wide tiles
             if (fine_every > 0 && ++pair_no % fine_every == 0 && job->plans[i].groups.size() < job->plans[i].fine.size()) {
                 for (size_t g = 0; g < job->plans[i].fine.size(); g++) {
                     const std::pair<int, int>& gr = job->plans[i].fine[g];
@@ -847,21 +904,19 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
                 items.push_back(ItemH{i, pr, (int)g, job->plans[i].seg_k1[gr.second - 1] - job->plans[i].seg_k0[gr.first], b11});
             }
         }
-        for (int r = shm ? p.M : 0; r < p.M + p.U; r++) rowmap.push_back(make_int2(i, r));
-        if (shm) {
+        for (int r = shm() ? p.M : 0; r < p.M + p.U; r++) rowmap.push_back(make_int2(i, r));
+        if (shm()) {
             // this window's view of the job-wide B11 pairs it lies in
             const Plan& g = *job->gplan;
-            const int lo = job->g0[(size_t)i] / TILE, hi = (job->g0[(size_t)i] + p.M - 1) / TILE;
-            for (int ti = lo; ti <= hi; ti++)
-                for (int tj = ti; tj <= hi; tj++) {
-                    const int2 e = make_int2(i, g.pair_lut[(size_t)ti * g.p.nT + tj] | TILE_GB11);
-                    tilemap.push_back(e); job->win_tiles[(size_t)i].push_back(e);
-                }
+            for_tile_pairs((size_t)job->g0[(size_t)i], (size_t)p.M, [&](int ti, int tj) {
+                const int2 e = make_int2(i, g.pair_lut[(size_t)ti * g.p.nT + tj] | TILE_GB11);
+                tilemap.push_back(e); job->win_tiles[(size_t)i].push_back(e);
+            });
         }
         if (!p.n_gene)
             for (int pr = 0; pr < p.npair; pr++) {
                 const bool b21 = !p.ld_only && job->plans[i].pair_ti[pr] >= p.Mp / TILE;      // a tile of U rows x M columns
-                if (shm && !b21) continue;
+                if (shm() && !b21) continue;
                 (b21 ? tilemap_b21 : tilemap).push_back(make_int2(i, pr));
                 job->win_tiles[(size_t)i].push_back(make_int2(i, pr));
             }
@@ -877,15 +932,11 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         if (rd.susie_L && rd.xs_group) {       // a member of a group of the joint fit across studies: launches and map of its own
             xsmap.push_back(i);
             if (rd.xs_pos == 0) xsleadmap.push_back(i);
-            job->xs_max_M = std::max(job->xs_max_M, p.M); job->xs_max_T = std::max(job->xs_max_T, p.M + p.U);
-            job->xs_max_L = std::max(job->xs_max_L, rd.susie_L); job->xs_max_sweeps = std::max(job->xs_max_sweeps, p.susie_max_sweeps);
-            if (!p.susie_measured_only) { job->xs_max_U = std::max(job->xs_max_U, p.U); job->xs_max_nblk = std::max(job->xs_max_nblk, p.nblk); }
+            job->xs_dims.grow(p, rd);
         } else if (rd.susie_L) {
             susiemap.push_back(i);
-            job->susie_max_M = std::max(job->susie_max_M, p.M); job->susie_max_T = std::max(job->susie_max_T, p.M + p.U);
-            job->susie_max_L = std::max(job->susie_max_L, rd.susie_L); job->susie_max_sweeps = std::max(job->susie_max_sweeps, p.susie_max_sweeps);
+            job->susie_dims.grow(p, rd);
             job->susie_max_k = std::max(job->susie_max_k, rd.susie_k); job->susie_coloc = job->susie_coloc || rd.coloc;
-            if (!p.susie_measured_only) { job->susie_max_U = std::max(job->susie_max_U, p.U); job->susie_max_nblk = std::max(job->susie_max_nblk, p.nblk); }
         }
         if (rd.traits_T) {
             for (int b = 0; b < p.nblk; b++) traitsmap.push_back(make_int2(i, b));
@@ -904,247 +955,301 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         }
         if (p.mode != 0) job->max_pop = std::max(job->max_pop, p.P);
     }
-    // The launch order: longest segments first (the tail of the launch is then made of short items), inside up to three classes --
-    // B11's items, the early windows' B21 items, the late windows' (below).  One stable counting pass over (class, length): lengths
-    // are whole K chunks and a job has a handful of distinct ones (three stable sorts through the plans' tables were 0.3 ms of the
-    // 0.53 ms a three-window job took to plan; a rank of eight waits for exactly that before its GPU starts).
-    // The order key: the item's K length scaled by how much of the tile its slowest wave multiplies (a wave issues na x nb 32 x 32
-    // blocks per K step, 4 at most; the waves of a workgroup meet at a barrier every chunk, so the fullest wave sets the item's
-    // pace): full tiles start first, edge tiles (a window's last 17 rows are a quarter of a tile's work) end the launch.  Measured:
-    // one 529-SNP window (1.3 rounds of the chip's workgroup slots) Gram 115 -> 109 us; the 36-window job 36.62 -> 36.52 ms; an
-    // 8-rank share unchanged.  The order changes no bit (items are independent).
-    {
-        auto live_rows = [&](const Plan& pl, int t) {
-            const Prob& p = pl.p;
-            const int mt = p.Mp / TILE;
-            if (!pl.tile_live.empty()) return pl.tile_live[(size_t)t];
-            const int left = (t < mt) ? p.M - t * TILE : p.U - (t - mt) * TILE;
-            return left > TILE ? TILE : left;
-        };
-        for (ItemH& h : items) {
-            h.ord = h.len;
-            if (job->gram_i8) continue;          // (the int8 kernel is bound by operand delivery: it keeps items of one K range together -- 5.40 against 5.53 ms)
-            const Plan& pl = plan_of(h.prob);
-            const int ti = pl.pair_ti[h.pair], tj = pl.pair_tj[h.pair];
-            const int ra = live_rows(pl, ti), rb = live_rows(pl, tj);
-            // (packed items, k_gram.hip: a wave with any live A half issues one MFMA per live B half -- 2 at most, half a full unpacked wave)
-            const bool packed = job->gram_packed && pl.p.slab16;
-            // the waves' blocks by the item's layout (k_gram_common.h): a narrow layout halves the fullest wave's blocks, and the key follows
-            const int layout = job->gram_narrow ? tile_layout(ra, rb, packed) : LAYOUT_QUAD;
-            int mx = 0;
-            for (int w = 0; w < 4; w++) {
-                const WaveWork ww = wave_work(ra, rb, ti == tj, packed, false, w, layout);
-                mx = std::max(mx, (packed ? std::min(ww.na, 1) : ww.na) * ww.nb);
-            }
-            h.ord = std::max(KC, (h.len * std::max(mx, 1) / 4 + KC - 1) / KC * KC);
+    return GAUSS_OK;
+}
+// The order key: the item's K length scaled by how much of the tile its slowest wave multiplies (a wave issues na x nb 32 x 32
+// blocks per K step, 4 at most; the waves of a workgroup meet at a barrier every chunk, so the fullest wave sets the item's
+// pace): full tiles start first, edge tiles (a window's last 17 rows are a quarter of a tile's work) end the launch.  Measured:
+// one 529-SNP window (1.3 rounds of the chip's workgroup slots) Gram 115 -> 109 us; the 36-window job 36.62 -> 36.52 ms; an
+// 8-rank share unchanged.  The order changes no bit (items are independent).
+void JobBuild::item_keys()
+{
+    gauss_job* const job = this->job;
+    std::vector<ItemH> items(std::move(this->items));      // (the steps of order_items work on locals, as the loops did inside one function: through `this` every store reloads them)
+    for (ItemH& h : items) {
+        h.ord = h.len;
+        if (job->gram_i8) continue;          // (the int8 kernel is bound by operand delivery: it keeps items of one K range together -- 5.40 against 5.53 ms)
+        const Plan& pl = plan_of(h.prob);
+        const int ti = pl.pair_ti[h.pair], tj = pl.pair_tj[h.pair];
+        const int ra = live_rows(pl, ti), rb = live_rows(pl, tj);
+        // (packed items, k_gram.hip: a wave with any live A half issues one MFMA per live B half -- 2 at most, half a full unpacked wave)
+        const bool packed = job->gram_packed && pl.p.slab16;
+        // the waves' blocks by the item's layout (k_gram_common.h): a narrow layout halves the fullest wave's blocks, and the key follows
+        const int layout = job->gram_narrow ? tile_layout(ra, rb, packed) : LAYOUT_QUAD;
+        int mx = 0;
+        for (int w = 0; w < 4; w++) {
+            const WaveWork ww = wave_work(ra, rb, ti == tj, packed, false, w, layout);
+            mx = std::max(mx, (packed ? std::min(ww.na, 1) : ww.na) * ww.nb);
         }
+        h.ord = std::max(KC, (h.len * std::max(mx, 1) / 4 + KC - 1) / KC * KC);
     }
+    items.swap(this->items);
+}
+// The launch order: longest segments first (the tail of the launch is then made of short items), inside up to three classes --
+// B11's items, the early windows' B21 items, the late windows' (launch_classes).  One stable counting pass over (class, length): lengths
+// are whole K chunks and a job has a handful of distinct ones (three stable sorts through the plans' tables were 0.3 ms of the
+// 0.53 ms a three-window job took to plan; a rank of eight waits for exactly that before its GPU starts).
+void JobBuild::sort_items()
+{
+    std::vector<ItemH> items(std::move(this->items));
+    std::vector<uint8_t> item_class(std::move(this->item_class));
+    int L = 0;
+    bool whole = true;
+    for (const ItemH& h : items) { L = std::max(L, h.ord / KC); whole = whole && h.ord % KC == 0 && h.ord >= 0; }
+    if (!whole || (size_t)L > 4 * items.size() + 1024) {            // (never on a plan of this file: lengths are multiples of KC)
+        std::vector<size_t> idx(items.size());
+        for (size_t n = 0; n < idx.size(); n++) idx[n] = n;
+        std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) {
+            return item_class[a] != item_class[b] ? item_class[a] < item_class[b] : items[a].ord > items[b].ord; });
+        std::vector<ItemH> out(items.size());
+        for (size_t n = 0; n < idx.size(); n++) out[n] = items[idx[n]];
+        this->items.swap(out); this->item_class.swap(item_class);
+        return;
+    }
+    const size_t nb = (size_t)3 * (size_t)(L + 1);
+    std::vector<uint32_t> start(nb + 1, 0u);
+    auto bucket = [&](size_t n) { return (size_t)item_class[n] * (size_t)(L + 1) + (size_t)(L - items[n].ord / KC); };
+    for (size_t n = 0; n < items.size(); n++) start[bucket(n) + 1]++;
+    for (size_t b = 0; b < nb; b++) start[b + 1] += start[b];
+    std::vector<ItemH> out(items.size());
+    for (size_t n = 0; n < items.size(); n++) out[start[bucket(n)]++] = items[n];
+    this->items.swap(out); this->item_class.swap(item_class);
+}
+// Which launches the job's Gram items make, and the class of every item in them
+void JobBuild::launch_classes()
+{
+    gauss_job* const job = this->job;
+    std::vector<ItemH> items(std::move(this->items));
     auto is_b11 = [&](const ItemH& h) { return h.b11 != 0; };
     std::vector<uint8_t> item_class(items.size(), 0);
-    auto order_items = [&]() {
-        int L = 0;
-        bool whole = true;
-        for (const ItemH& h : items) { L = std::max(L, h.ord / KC); whole = whole && h.ord % KC == 0 && h.ord >= 0; }
-        if (!whole || (size_t)L > 4 * items.size() + 1024) {            // (never on a plan of this file: lengths are multiples of KC)
-            std::vector<size_t> idx(items.size());
-            for (size_t n = 0; n < idx.size(); n++) idx[n] = n;
-            std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) {
-                return item_class[a] != item_class[b] ? item_class[a] < item_class[b] : items[a].ord > items[b].ord; });
-            std::vector<ItemH> out(items.size());
-            for (size_t n = 0; n < idx.size(); n++) out[n] = items[idx[n]];
-            items.swap(out);
-            return;
-        }
-        const size_t nb = (size_t)3 * (size_t)(L + 1);
-        std::vector<uint32_t> start(nb + 1, 0u);
-        auto bucket = [&](size_t n) { return (size_t)item_class[n] * (size_t)(L + 1) + (size_t)(L - items[n].ord / KC); };
-        for (size_t n = 0; n < items.size(); n++) start[bucket(n) + 1]++;
-        for (size_t b = 0; b < nb; b++) start[b + 1] += start[b];
-        std::vector<ItemH> out(items.size());
-        for (size_t n = 0; n < items.size(); n++) out[start[bucket(n)]++] = items[n];
-        items.swap(out);
-    };
+    std::vector<char> late_window;
+    // Chain beside the Gram kernel (k_solve_lite.hip): B11's items become a launch of their own, B11's epilogue tiles and
+    // the factorisation chain follow it on the chain queue, and the chain's latency hides under the Gram launch of
+    // B21's items.  Worth it when that launch is long enough to cover B11's small-footprint epilogue tiles (~0.5 ms) and
+    // the chain, which runs ~3 x slower beside the Gram kernel than alone (~100 us per block step: two launches);
+    // GAUSS_CHAIN_ASIDE = 0 never, 2 always (tests), 1 (default) by this estimate.
+    const int mode = env_int("GAUSS_CHAIN_ASIDE", 1);
+    bool genes = false;
+    double b21_len = 0.0;
+    // an item's K length in the time units of the unpacked f32 kernel (the 120e12 below): a packed item (k_gram.hip) issues half
+    // the MFMAs and pays the A-side combine and the sub-flushes on top -- GRAM_PACKED_COST of the unpacked time per sample
+    auto cost_len = [&](const ItemH& h) { return (double)h.len * ((job->gram_packed && plan_of(h.prob).p.slab16) ? GRAM_PACKED_COST : 1.0); };
+    for (const ItemH& h : items) if (!is_b11(h)) b21_len += cost_len(h);
+    for (int i = 0; i < job->n; i++) genes = genes || job->plans[i].p.n_gene > 0;
+    // (the int8 Gram kernel is ~8 x faster: an 8-rank share's B21 launch, 0.5 ms, no longer covers its chain)
+    const double t_b21 = b21_len * 2.0 * TILE * TILE / (job->gram_i8 ? 960e12 : 120e12), t_chain = 0.5e-3 + 100e-6 * job->max_nblk;
     {
-        // Chain beside the Gram kernel (k_solve_lite.hip): B11's items become a launch of their own, B11's epilogue tiles and
-        // the factorisation chain follow it on the chain queue, and the chain's latency hides under the Gram launch of
-        // B21's items.  Worth it when that launch is long enough to cover B11's small-footprint epilogue tiles (~0.5 ms) and
-        // the chain, which runs ~3 x slower beside the Gram kernel than alone (~100 us per block step: two launches);
-        // GAUSS_CHAIN_ASIDE = 0 never, 2 always (tests), 1 (default) by this estimate.
-        const int mode = env_int("GAUSS_CHAIN_ASIDE", 1);
-        bool genes = false;
-        double b21_len = 0.0;
-        // an item's K length in the time units of the unpacked f32 kernel (the 120e12 below): a packed item (k_gram.hip) issues half
-        // the MFMAs and pays the A-side combine and the sub-flushes on top -- GRAM_PACKED_COST of the unpacked time per sample
-        auto cost_len = [&](const ItemH& h) { return (double)h.len * ((job->gram_packed && plan_of(h.prob).p.slab16) ? GRAM_PACKED_COST : 1.0); };
-        for (const ItemH& h : items) if (!is_b11(h)) b21_len += cost_len(h);
-        for (int i = 0; i < job->n; i++) genes = genes || job->plans[i].p.n_gene > 0;
-        // (the int8 Gram kernel is ~8 x faster: an 8-rank share's B21 launch, 0.5 ms, no longer covers its chain)
-        const double t_b21 = b21_len * 2.0 * TILE * TILE / (job->gram_i8 ? 960e12 : 120e12), t_chain = 0.5e-3 + 100e-6 * job->max_nblk;
-        {
-            double all_len = 0.0;
-            for (const ItemH& h : items) all_len += cost_len(h);
-            job->wait_bound_us = 50.0 * 1e6 * all_len * 2.0 * TILE * TILE / (job->gram_i8 ? 960e12 : 120e12);      // a whole-genome job must not trip a fixed bound
-        }
-        job->chain_aside = !streamed && mode != 0 && !panelmap.empty() && !tilemap_b21.empty() && !genes && job->ctx->chain &&
-                           job->ctx->side && (mode == 2 || t_b21 >= 1.2 * t_chain);
-        if (job->chain_aside)
-            for (size_t n = 0; n < items.size(); n++) {
-                item_class[n] = is_b11(items[n]) ? 0 : 1;
-                job->n_items_b11 += is_b11(items[n]) ? 1 : 0;
-            }
-        // Merged launch (round 4): B11's items and B21's items are ONE launch, B11's first; they count themselves off and the
-        // chain queue starts when the count is complete (k_gram.hip: wait_count_kernel) -- the chip is never drained between
-        // the two halves (two launches: 37.1 ms, one: 36.6 on the 36-window job).  GAUSS_CHAIN_MERGED=0: two launches + event.
-        // (f32 only: the int8 Gram kernel is operand-delivery bound and the chain's memory traffic beside ALL of it costs more than
-        // the second launch's start-up -- measured 8.70 ms per step merged against 8.35 ms as two launches; =2 forces it for both)
-        {
-            const int mm = env_int("GAUSS_CHAIN_MERGED", 1);
-            job->merged = job->chain_aside && mm != 0 && (!job->gram_i8 || mm == 2);
-            // =2 (tests): merged whatever the queue registry says -- job_queue_run otherwise takes the two-launch form for a run
-            // whose context cannot be sure of a hardware queue per stream (gauss_ctx.cpp)
-            job->force_merged = job->merged && mm == 2;
-        }
-        // Early epilogue: the smallest windows of the job that together hold about a third of B21's Gram work are "late" -- their
-        // items end the launch -- and every other window is "early" (GAUSS_EPI_EARLY=0: off.  Measured by the late share,
-        // 36-window step / slowest 8-rank share: off 40.04 / 5.45 ms; 6 % 39.89 / 5.51; 12 % 39.76 / 5.51; 25 % 39.75 / 5.45; 35 %
-        // 39.67 / 5.40; 50 % 39.64 / 5.47 -- a late part that is too small opens the gate only when the launch is all but over and
-        // the two epilogue launches cost their event hops).  One window: nothing to split.
-        late_window.assign((size_t)job->n + 1, 0);
-        if (job->merged && job->n >= 2 && job->ctx->side && env_int("GAUSS_EPI_EARLY", 1) != 0) {
-            std::vector<double> w21((size_t)job->n, 0.0);
-            double tot = 0;
-            for (const ItemH& h : items) if (!is_b11(h)) { w21[(size_t)h.prob] += h.len; tot += h.len; }
-            const double want = tot * 0.35;
-            double acc = 0;
-            int n_late = 0;
-            // (the windows with the least B21 work: a share of four windows gives up its smallest one, not whichever comes last)
-            std::vector<int> by_work((size_t)job->n);
-            for (int i = 0; i < job->n; i++) by_work[(size_t)i] = i;
-            std::stable_sort(by_work.begin(), by_work.end(), [&](int a, int b) { return w21[(size_t)a] < w21[(size_t)b]; });
-            for (int k = 0; k + 1 < job->n && acc < want; k++) { late_window[(size_t)by_work[(size_t)k]] = 1; acc += w21[(size_t)by_work[(size_t)k]]; n_late++; }
-            if (n_late > 0 && acc < tot) {
-                for (size_t n = 0; n < items.size(); n++) {
-                    if (is_b11(items[n])) continue;
-                    if (late_window[(size_t)items[n].prob]) item_class[n] = 2;
-                    else job->n_items_b21_early++;
-                }
-            } else late_window.assign((size_t)job->n + 1, 0);
-        }
-        order_items();
+        double all_len = 0.0;
+        for (const ItemH& h : items) all_len += cost_len(h);
+        job->wait_bound_us = 50.0 * 1e6 * all_len * 2.0 * TILE * TILE / (job->gram_i8 ? 960e12 : 120e12);      // a whole-genome job must not trip a fixed bound
     }
-    std::vector<int> sgroup_of_item;
-    if (streamed) {
-        // streamed window: B11's items (measured rows only) first, then B21's items by chunk of `ct` unmeasured row
-        // tiles; each group is one Gram launch that starts as soon as its rows have landed
-        const Plan& pl0 = job->plans[0];
-        const int mt = pl0.p.Mp / TILE;
-        const std::vector<int>& tile_group = stream->tile_group;
-        const std::vector<int>& first_tile = stream->first_tile;
-        const int ngrp = (int)first_tile.size() - 1;
-        auto grp = [&](const ItemH& h) { const int ti = pl0.pair_ti[h.pair]; return ti < mt ? 0 : tile_group[(size_t)(ti - mt)]; };
-        std::stable_sort(items.begin(), items.end(), [&](const ItemH& a, const ItemH& b) { return grp(a) < grp(b); });
-        job->sgroups.assign((size_t)ngrp, gauss_job::StreamGroup{0, 0, 0, 0, 0, 0});
+    job->chain_aside = !streamed() && mode != 0 && !panelmap.empty() && !tilemap_b21.empty() && !genes && job->ctx->chain &&
+                       job->ctx->side && (mode == 2 || t_b21 >= 1.2 * t_chain);
+    if (job->chain_aside)
         for (size_t n = 0; n < items.size(); n++) {
-            gauss_job::StreamGroup& g = job->sgroups[(size_t)grp(items[n])];
-            if (g.n_items == 0) g.item0 = (int)n;
-            g.n_items++;
+            item_class[n] = is_b11(items[n]) ? 0 : 1;
+            job->n_items_b11 += is_b11(items[n]) ? 1 : 0;
         }
-        job->sgroups[0].row0 = 0; job->sgroups[0].n_rows = pl0.p.M;
-        for (int g = 1; g < ngrp; g++) {
-            const int u0 = first_tile[(size_t)g] * TILE, u1 = std::min(pl0.p.U, first_tile[(size_t)g + 1] * TILE);
-            job->sgroups[g].row0 = pl0.p.M + u0; job->sgroups[g].n_rows = std::max(0, u1 - u0);
-            // B21's epilogue tiles are listed in pair order (row tile, then column tile): a chunk's tiles are contiguous
-            job->sgroups[g].tile0 = first_tile[(size_t)g] * mt;
-            job->sgroups[g].n_tiles = (first_tile[(size_t)g + 1] - first_tile[(size_t)g]) * mt;
-        }
-    }
-    // XCD-aware launch order.  Workgroup b runs on XCD b % 8 (each XCD has its own 4 MiB L2).  Neighbours in
-    // the sorted list share operand tiles (same window, same K range, adjacent tile pairs), so the list is
-    // cut into super-blocks of xcd_block items and super-block j is queued on XCD j % 8: the items that are
-    // resident together on one XCD then read the same tiles at about the same K position.  Measured on the
-    // bench workload (rocprofv3 FETCH_SIZE): 22.0 GB -> 16.0 GB per launch at 36, same kernel time; larger
-    // blocks start to cost time (load balance).
+    // Merged launch (round 4): B11's items and B21's items are ONE launch, B11's first; they count themselves off and the
+    // chain queue starts when the count is complete (k_gram.hip: wait_count_kernel) -- the chip is never drained between
+    // the two halves (two launches: 37.1 ms, one: 36.6 on the 36-window job).  GAUSS_CHAIN_MERGED=0: two launches + event.
+    // (f32 only: the int8 Gram kernel is operand-delivery bound and the chain's memory traffic beside ALL of it costs more than
+    // the second launch's start-up -- measured 8.70 ms per step merged against 8.35 ms as two launches; =2 forces it for both)
     {
-        // Small jobs (the 4-5 windows an 8-rank run leaves per GPU, ~7 000 items) take blocks of 8: a block of 36 is
-        // 4 % of an XCD's share there, and the XCD that gets one more than the others finishes last (Gram kernel of
-        // the 8-rank shares 5.10 -> 5.03 ms; 36 windows: 38.5 ms either way, but 36 reads 27 % less from the fabric).
-        const int xcd_block = items.size() >= 20000 ? 36 : 8;
-        // (a job whose B11 items are a launch of their own interleaves each launch's list by itself)
-        auto interleave = [&](size_t i0, size_t i1) {
-            if (xcd_block <= 0 || i1 - i0 <= (size_t)8 * xcd_block) return;
-            std::vector<std::vector<ItemH>> q(8);
-            for (size_t i = i0; i < i1; i++) q[((i - i0) / xcd_block) % 8].push_back(items[i]);
-            size_t pos[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n = i0;
-            while (n < i1)
-                for (int x = 0; x < 8; x++)
-                    if (pos[x] < q[x].size()) items[n++] = q[x][pos[x]++];
-        };
-        if (!streamed) {
-            interleave(0, (size_t)job->n_items_b11);
-            if (job->n_items_b21_early > 0) {
-                interleave((size_t)job->n_items_b11, (size_t)(job->n_items_b11 + job->n_items_b21_early));
-                interleave((size_t)(job->n_items_b11 + job->n_items_b21_early), items.size());
-            } else interleave((size_t)job->n_items_b11, items.size());
-        }
+        const int mm = env_int("GAUSS_CHAIN_MERGED", 1);
+        job->merged = job->chain_aside && mm != 0 && (!job->gram_i8 || mm == 2);
+        // =2 (tests): merged whatever the queue registry says -- job_queue_run otherwise takes the two-launch form for a run
+        // whose context cannot be sure of a hardware queue per stream (gauss_ctx.cpp)
+        job->force_merged = job->merged && mm == 2;
     }
-    const size_t o_items = ta.take(sizeof(Item) * std::max<size_t>(items.size(), 1));
-    const size_t o_rowmap = put(blob, ta, rowmap);
+    // Early epilogue: the smallest windows of the job that together hold about a third of B21's Gram work are "late" -- their
+    // items end the launch -- and every other window is "early" (GAUSS_EPI_EARLY=0: off.  Measured by the late share,
+    // 36-window step / slowest 8-rank share: off 40.04 / 5.45 ms; 6 % 39.89 / 5.51; 12 % 39.76 / 5.51; 25 % 39.75 / 5.45; 35 %
+    // 39.67 / 5.40; 50 % 39.64 / 5.47 -- a late part that is too small opens the gate only when the launch is all but over and
+    // the two epilogue launches cost their event hops).  One window: nothing to split.
+    late_window.assign((size_t)job->n + 1, 0);
+    if (job->merged && job->n >= 2 && job->ctx->side && env_int("GAUSS_EPI_EARLY", 1) != 0) {
+        std::vector<double> w21((size_t)job->n, 0.0);
+        double tot = 0;
+        for (const ItemH& h : items) if (!is_b11(h)) { w21[(size_t)h.prob] += h.len; tot += h.len; }
+        const double want = tot * 0.35;
+        double acc = 0;
+        int n_late = 0;
+        // (the windows with the least B21 work: a share of four windows gives up its smallest one, not whichever comes last)
+        std::vector<int> by_work((size_t)job->n);
+        for (int i = 0; i < job->n; i++) by_work[(size_t)i] = i;
+        std::stable_sort(by_work.begin(), by_work.end(), [&](int a, int b) { return w21[(size_t)a] < w21[(size_t)b]; });
+        for (int k = 0; k + 1 < job->n && acc < want; k++) { late_window[(size_t)by_work[(size_t)k]] = 1; acc += w21[(size_t)by_work[(size_t)k]]; n_late++; }
+        if (n_late > 0 && acc < tot) {
+            for (size_t n = 0; n < items.size(); n++) {
+                if (is_b11(items[n])) continue;
+                if (late_window[(size_t)items[n].prob]) item_class[n] = 2;
+                else job->n_items_b21_early++;
+            }
+        } else late_window.assign((size_t)job->n + 1, 0);
+    }
+    items.swap(this->items); item_class.swap(this->item_class); late_window.swap(this->late_window);
+}
+// streamed window: B11's items (measured rows only) first, then B21's items by chunk of `ct` unmeasured row
+// tiles; each group is one Gram launch that starts as soon as its rows have landed
+void JobBuild::stream_groups()
+{
+    const Plan& pl0 = job->plans[0];
+    const int mt = pl0.p.Mp / TILE;
+    const std::vector<int>& tile_group = stream->tile_group;
+    const std::vector<int>& first_tile = stream->first_tile;
+    const int ngrp = (int)first_tile.size() - 1;
+    auto grp = [&](const ItemH& h) { const int ti = pl0.pair_ti[h.pair]; return ti < mt ? 0 : tile_group[(size_t)(ti - mt)]; };
+    std::stable_sort(items.begin(), items.end(), [&](const ItemH& a, const ItemH& b) { return grp(a) < grp(b); });
+    job->sgroups.assign((size_t)ngrp, gauss_job::StreamGroup{0, 0, 0, 0, 0, 0});
+    for (size_t n = 0; n < items.size(); n++) {
+        gauss_job::StreamGroup& g = job->sgroups[(size_t)grp(items[n])];
+        if (g.n_items == 0) g.item0 = (int)n;
+        g.n_items++;
+    }
+    job->sgroups[0].row0 = 0; job->sgroups[0].n_rows = pl0.p.M;
+    for (int g = 1; g < ngrp; g++) {
+        const int u0 = first_tile[(size_t)g] * TILE, u1 = std::min(pl0.p.U, first_tile[(size_t)g + 1] * TILE);
+        job->sgroups[g].row0 = pl0.p.M + u0; job->sgroups[g].n_rows = std::max(0, u1 - u0);
+        // B21's epilogue tiles are listed in pair order (row tile, then column tile): a chunk's tiles are contiguous
+        job->sgroups[g].tile0 = first_tile[(size_t)g] * mt;
+        job->sgroups[g].n_tiles = (first_tile[(size_t)g + 1] - first_tile[(size_t)g]) * mt;
+    }
+}
+// XCD-aware launch order.  Workgroup b runs on XCD b % 8 (each XCD has its own 4 MiB L2).  Neighbours in
+// the sorted list share operand tiles (same window, same K range, adjacent tile pairs), so the list is
+// cut into super-blocks of xcd_block items and super-block j is queued on XCD j % 8: the items that are
+// resident together on one XCD then read the same tiles at about the same K position.  Measured on the
+// bench workload (rocprofv3 FETCH_SIZE): 22.0 GB -> 16.0 GB per launch at 36, same kernel time; larger
+// blocks start to cost time (load balance).
+void JobBuild::xcd_interleave()
+{
+    gauss_job* const job = this->job;
+    std::vector<ItemH> items(std::move(this->items));
+    // Small jobs (the 4-5 windows an 8-rank run leaves per GPU, ~7 000 items) take blocks of 8: a block of 36 is
+    // 4 % of an XCD's share there, and the XCD that gets one more than the others finishes last (Gram kernel of
+    // the 8-rank shares 5.10 -> 5.03 ms; 36 windows: 38.5 ms either way, but 36 reads 27 % less from the fabric).
+    const int xcd_block = items.size() >= 20000 ? 36 : 8;
+    // (a job whose B11 items are a launch of their own interleaves each launch's list by itself)
+    auto interleave = [&](size_t i0, size_t i1) {
+        if (xcd_block <= 0 || i1 - i0 <= (size_t)8 * xcd_block) return;
+        std::vector<std::vector<ItemH>> q(8);
+        for (size_t i = i0; i < i1; i++) q[((i - i0) / xcd_block) % 8].push_back(items[i]);
+        size_t pos[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n = i0;
+        while (n < i1)
+            for (int x = 0; x < 8; x++)
+                if (pos[x] < q[x].size()) items[n++] = q[x][pos[x]++];
+    };
+    interleave(0, (size_t)job->n_items_b11);
+    if (job->n_items_b21_early > 0) {
+        interleave((size_t)job->n_items_b11, (size_t)(job->n_items_b11 + job->n_items_b21_early));
+        interleave((size_t)(job->n_items_b11 + job->n_items_b21_early), items.size());
+    } else interleave((size_t)job->n_items_b11, items.size());
+    items.swap(this->items);
+}
+int JobBuild::order_items()
+{
+    item_keys();
+    launch_classes();
+    sort_items();
+    if (streamed()) stream_groups();
+    else xcd_interleave();
+    return GAUSS_OK;
+}
+// The work items' block and every work list in the table image, behind the descriptors' tables
+int JobBuild::place_lists()
+{
+    o_items = tab_block(job->d_items, sizeof(Item) * std::max<size_t>(items.size(), 1));
+    job->n_items = (int)items.size();
+    tab(job->d_rowmap, job->n_rows, rowmap);
     job->n_tiles_b11 = (int)tilemap.size();
     if (job->n_items_b21_early > 0) {
         std::stable_partition(tilemap_b21.begin(), tilemap_b21.end(), [&](const int2& a) { return !late_window[(size_t)a.x]; });
         for (const int2& t : tilemap_b21) job->n_tiles_b21_early += late_window[(size_t)t.x] ? 0 : 1;
     }
     tilemap.insert(tilemap.end(), tilemap_b21.begin(), tilemap_b21.end());
-    const size_t o_tilemap = put(blob, ta, tilemap);
+    tab(job->d_tilemap, job->n_tiles, tilemap);
     // the product's tiles with the longest K loop (highest k block) first
-    std::stable_sort(gemmmap.begin(), gemmmap.end(), [](const int2& a, const int2& b) { return (a.y & 255) > (b.y & 255); });
-    const size_t o_panelmap = put(blob, ta, panelmap);
-    const size_t o_dpanelmap = put(blob, ta, dpanelmap);
-    const size_t o_gemmmap = put(blob, ta, gemmmap);
-    const size_t o_finmap = put(blob, ta, finmap);
-    const size_t o_loomap = put(blob, ta, loomap);
-    const size_t o_slctmap = slctmap.empty() ? 0 : put(blob, ta, slctmap);      // (a job in which nobody asks takes nothing)
-    const size_t o_condmap = condmap.empty() ? 0 : put(blob, ta, condmap);
-    const size_t o_csmap = csmap.empty() ? 0 : put(blob, ta, csmap);
-    const size_t o_prsmap = prsmap.empty() ? 0 : put(blob, ta, prsmap);
-    const size_t o_susiemap = susiemap.empty() ? 0 : put(blob, ta, susiemap);
-    const size_t o_xsmap = xsmap.empty() ? 0 : put(blob, ta, xsmap);
-    const size_t o_xsleadmap = xsleadmap.empty() ? 0 : put(blob, ta, xsleadmap);
-    const size_t o_traitsmap = traitsmap.empty() ? 0 : put(blob, ta, traitsmap);
-    const size_t o_traitsumap = traitsumap.empty() ? 0 : put(blob, ta, traitsumap);
-    const size_t o_missmap = missmap.empty() ? 0 : put(blob, ta, missmap);
-    const size_t o_misstmap = misstmap.empty() ? 0 : put(blob, ta, misstmap);
-    const size_t o_missumap = missumap.empty() ? 0 : put(blob, ta, missumap);
-    const size_t o_probs = ta.take(sizeof(Prob) * (size_t)n_prob);
-    const size_t o_exports = ta.take(sizeof(ExportD) * std::max<size_t>(job->exports.size(), 1));
-    blob.resize(ta.off);
-    job->n_items = (int)items.size();
-    job->n_rows = (int)rowmap.size();
-    job->n_tiles = (int)tilemap.size();
-    job->n_panels = (int)panelmap.size();
-    job->n_dpanels = (int)dpanelmap.size();
-    job->n_gemm = (int)gemmmap.size();
-    job->n_fin = (int)finmap.size();
-    job->n_loo = (int)loomap.size();
-    job->n_slct = (int)slctmap.size();
-    job->n_cond = (int)condmap.size();
-    job->n_cs = (int)csmap.size();
-    job->n_prs = (int)prsmap.size();
-    job->n_susie = (int)susiemap.size();
-    job->n_xs = (int)xsmap.size();
-    job->n_xs_lead = (int)xsleadmap.size();
-    job->n_traits = (int)traitsmap.size();
-    job->n_traits_u = (int)traitsumap.size();
-    job->n_miss_blk = (int)missmap.size();
-    job->n_miss_t = (int)misstmap.size();
-    job->n_miss_u = (int)missumap.size();
-
-    // ---- workspace arena ----
-    Arena wa;         // zeroed once per job: operand padding, B21 padding and the solve matrices rely on it
-    Arena wslab;      // partial slabs: every entry a reader keeps is written by the Gram kernel first, so no zeroing
-    struct WsOff { size_t raw_m, raw_u, packed, sx, sxx, slab, sd, wm, mu, wmu, A, Linv, B21, V, ld, b11c, gsum, part, slct, cs_lbf, cs_mem, susie_ws, susie_mem, ty, tg, mye, mae, myu, mld; long long ldraw; };
-    std::vector<WsOff> wo(job->n);
-    size_t res = 0;
+    std::stable_sort(gemmmap.begin(), gemmmap.end(), [](const int2& x, const int2& y) { return (x.y & 255) > (y.y & 255); });
+    tab(job->d_panelmap, job->n_panels, panelmap); tab(job->d_dpanelmap, job->n_dpanels, dpanelmap);
+    tab(job->d_gemmmap, job->n_gemm, gemmmap); tab(job->d_finmap, job->n_fin, finmap);
+    tab(job->d_loomap, job->n_loo, loomap);
+    const bool if_any = true;                              // (a job in which nobody asks takes nothing)
+    tab(job->d_slctmap, job->n_slct, slctmap, if_any); tab(job->d_condmap, job->n_cond, condmap, if_any);
+    tab(job->d_csmap, job->n_cs, csmap, if_any); tab(job->d_prsmap, job->n_prs, prsmap, if_any);
+    tab(job->d_susiemap, job->n_susie, susiemap, if_any);
+    tab(job->d_xsmap, job->n_xs, xsmap, if_any); tab(job->d_xsleadmap, job->n_xs_lead, xsleadmap, if_any);
+    tab(job->d_traitsmap, job->n_traits, traitsmap, if_any); tab(job->d_traitsumap, job->n_traits_u, traitsumap, if_any);
+    tab(job->d_missmap, job->n_miss_blk, missmap, if_any); tab(job->d_misstmap, job->n_miss_t, misstmap, if_any);
+    tab(job->d_missumap, job->n_miss_u, missumap, if_any);
+    o_probs = tab_block(job->d_probs, sizeof(Prob) * (size_t)n_prob());
+    o_exports = tab_block(job->d_exports, sizeof(ExportD) * std::max<size_t>(job->exports.size(), 1));
+    job->h_tab.resize(ta.off);
+    return GAUSS_OK;
+}
+// ---- workspace arena ----
+// One window's blocks.  A rider registers its blocks here, under the `if` that says it was asked: a field that is not
+// registered stays null.
+void JobBuild::layout_window(Plan& pl)
+{
+    Prob& p = pl.p;
+    const Plan::Riders& rd = pl.rd;
+    if (streamed()) {
+        p.ld_raw = stream->ldraw; p.raw_m = stream->d_m; p.raw_u = stream->d_u;      // the rows land in the context's landing buffer
+    } else if (!on_device) {
+        // contiguous host matrices whose stride is close to the row length keep their stride on the device:
+        // the upload is then ONE linear copy (a pitched copy of 3 000 rows runs at a fraction of that rate)
+        const bool linear = pl.rows_m.empty() && pl.rows_u.empty() && (size_t)pl.user_ld <= pl.row_bytes + pl.row_bytes / 8 + 64;
+        p.ld_raw = linear ? pl.user_ld : (long long)rup(pl.row_bytes, 16);
+        ws(p.raw_m, (size_t)p.M * p.ld_raw + 64);
+        ws(p.raw_u, (size_t)std::max(pl.U_user, 1) * p.ld_raw + 64);
+    } else {
+        p.ld_raw = pl.user_ld; p.raw_m = pl.h_geno_m; p.raw_u = pl.h_geno_u;
+    }
+    ws(p.packed, (size_t)p.Sp * p.Kp);
+    ws(p.sx, (size_t)p.Sp * p.P * sizeof(int)); ws(p.sxx, (size_t)p.Sp * p.P * sizeof(int));
+    slab(p.slab, (size_t)p.npair * p.nseg * TILE * TILE * (p.slab16 ? sizeof(uint16_t) : sizeof(float)));
+    ws(p.rt_sd, (size_t)p.Sp * sizeof(double)); ws(p.rt_wm, (size_t)p.Sp * sizeof(double));
+    ws(p.rt_mu, (size_t)p.Sp * p.P * sizeof(double)); ws(p.rt_wmu, (size_t)p.Sp * p.P * sizeof(double));
+    if (!p.ld_only) {
+        // the LD epilogue writes B11 (and its shifted twin) and B21 for every window that is not a plain
+        // gauss_ld / gene batch; the factor and solve scratch only exists when there is something to solve
+        ws(p.A, (size_t)(p.npanel > 0 ? 5 : 2) * p.Mld * p.Mld * sizeof(double));   // A0 A1 [L0 L1 W0]
+        ws(p.B21, (size_t)std::max(p.U, 1) * p.Mld * sizeof(double));
+    }
+    if (p.npanel > 0) {
+        ws(p.Linv, (size_t)2 * p.nblk * NB * NB * sizeof(double));
+        ws(p.V, (size_t)std::max(p.npanel, p.npi) * p.Mld * NR * sizeof(double));
+        ws(p.Gsum, (size_t)((p.Mld + 127) / 128) * p.Up128 * 3 * sizeof(double));
+        ws(p.Part, (size_t)2 * p.npi * 4 * NB * NR * sizeof(double));      // double buffered by row parity
+        ws(pl.d_b11_copy, (size_t)p.Mld * p.Mld * sizeof(double));
+    }
+    if (rd.slct_K) ws(p.slct_W, (size_t)SLCT_K * p.Mld * sizeof(double));      // the selected columns of the partial factor
+    if (rd.cs) {                        // the candidates' log Bayes factors / pips per signal, and their membership bytes
+        ws(p.cs_lbf, (size_t)rd.slct_K * cs_tld(p.M + p.U) * sizeof(double));
+        ws(p.cs_mem, (size_t)rd.slct_K * cs_tld(p.M + p.U));
+    }
+    if (rd.susie_L) {                   // W, the fit's state and the sets' membership bytes
+        ws(p.susie_ws, susie_ws(p.M, p.U, p.Mld, rd.susie_L, !p.susie_measured_only).total(rd.susie_k) * sizeof(double));
+        ws(p.susie_mem, (size_t)(1 + rd.susie_k) * rd.susie_L * cs_tld(p.M + p.U));
+    }
+    if (rd.traits_T) {                  // Y = X Z and G = X^T Y of the further traits
+        ws(p.traits_Y, (size_t)p.Mld * traits_t16(rd.traits_T) * sizeof(double));
+        ws(p.traits_G, (size_t)p.Mld * traits_t16(rd.traits_T) * sizeof(double));
+    }
+    if (rd.miss && p.miss_nm) {         // the columns of X and of B11^-1 of the missing SNPs, B21 times them, every trait's L_D and c
+        const size_t E16 = (size_t)traits_t16(p.miss_E);
+        ws(p.miss_YE, (size_t)p.Mld * E16 * sizeof(double));
+        ws(p.miss_AE, (size_t)p.Mld * E16 * sizeof(double));
+        ws(p.miss_YU, E16 * (size_t)p.U * sizeof(double));
+        ws(p.miss_LD, (size_t)p.miss_nm * MISS_LD * sizeof(double));
+    }
+    ws(p.out_ld, std::max<size_t>(pl.out_ld_count, 1) * sizeof(double));
+    pl.res_off = res;
+    res += pl.res_count();
+}
+int JobBuild::layout_workspace()
+{
     {
         // The early products of a row of the inverse (k_solve.hip, ride_pre) are a chain of dependent tile products:
         // rows with at least `solve_split` of them give one workgroup to each of their SOLVE_SPLIT classes, shorter rows
@@ -1160,107 +1265,39 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         job->own_panel = (n_solve > 0 && n_solve <= OWN_PANEL_MAX_WINDOWS) ? 1 : 0;
         job->solve_split = job->n_panels > 0 ? SOLVE_SPLIT_MIN : 0;
     }
-    for (int i = 0; i < job->n; i++) {
-        Plan& pl = job->plans[i];
-        Prob& p = pl.p;
-        WsOff& w = wo[i];
-        if (streamed) {
-            w.ldraw = stream->ldraw;                               // the rows land in the context's landing buffer
-        } else if (!on_device) {
-            // contiguous host matrices whose stride is close to the row length keep their stride on the device:
-            // the upload is then ONE linear copy (a pitched copy of 3 000 rows runs at a fraction of that rate)
-            const bool linear = pl.rows_m.empty() && pl.rows_u.empty() && (size_t)pl.user_ld <= pl.row_bytes + pl.row_bytes / 8 + 64;
-            w.ldraw = linear ? pl.user_ld : (long long)rup(pl.row_bytes, 16);
-            w.raw_m = wa.take((size_t)p.M * w.ldraw + 64);
-            w.raw_u = wa.take((size_t)std::max(pl.U_user, 1) * w.ldraw + 64);
-        } else {
-            w.ldraw = pl.user_ld;
-        }
-        w.packed = wa.take((size_t)p.Sp * p.Kp);
-        w.sx = wa.take((size_t)p.Sp * p.P * sizeof(int));
-        w.sxx = wa.take((size_t)p.Sp * p.P * sizeof(int));
-        w.slab = wslab.take((size_t)p.npair * p.nseg * TILE * TILE * (p.slab16 ? sizeof(uint16_t) : sizeof(float)));
-        w.sd = wa.take((size_t)p.Sp * sizeof(double));
-        w.wm = wa.take((size_t)p.Sp * sizeof(double));
-        w.mu = wa.take((size_t)p.Sp * p.P * sizeof(double));
-        w.wmu = wa.take((size_t)p.Sp * p.P * sizeof(double));
-        if (!p.ld_only) {
-            // the LD epilogue writes B11 (and its shifted twin) and B21 for every window that is not a plain
-            // gauss_ld / gene batch; the factor and solve scratch only exists when there is something to solve
-            w.A = wa.take((size_t)(p.npanel > 0 ? 5 : 2) * p.Mld * p.Mld * sizeof(double));   // A0 A1 [L0 L1 W0]
-            w.B21 = wa.take((size_t)std::max(p.U, 1) * p.Mld * sizeof(double));
-        }
-        if (p.npanel > 0) {
-            w.Linv = wa.take((size_t)2 * p.nblk * NB * NB * sizeof(double));
-            w.V = wa.take((size_t)std::max(p.npanel, p.npi) * p.Mld * NR * sizeof(double));
-            w.gsum = wa.take((size_t)((p.Mld + 127) / 128) * p.Up128 * 3 * sizeof(double));
-            w.part = wa.take((size_t)2 * p.npi * 4 * NB * NR * sizeof(double));      // double buffered by row parity
-            w.b11c = wa.take((size_t)p.Mld * p.Mld * sizeof(double));
-        }
-        w.slct = pl.rd.slct_K ? wa.take((size_t)SLCT_K * p.Mld * sizeof(double)) : 0;      // the selected columns of the partial factor
-        w.cs_lbf = w.cs_mem = 0;
-        if (pl.rd.cs) {                     // the candidates' log Bayes factors / pips per signal, and their membership bytes
-            w.cs_lbf = wa.take((size_t)pl.rd.slct_K * cs_tld(p.M + p.U) * sizeof(double));
-            w.cs_mem = wa.take((size_t)pl.rd.slct_K * cs_tld(p.M + p.U));
-        }
-        w.susie_ws = w.susie_mem = 0;
-        if (pl.rd.susie_L) {                // W, the fit's state and the sets' membership bytes
-            w.susie_ws = wa.take(susie_ws(p.M, p.U, p.Mld, pl.rd.susie_L, !p.susie_measured_only).total(pl.rd.susie_k) * sizeof(double));
-            w.susie_mem = wa.take((size_t)(1 + pl.rd.susie_k) * pl.rd.susie_L * cs_tld(p.M + p.U));
-        }
-        w.ty = w.tg = 0;
-        if (pl.rd.traits_T) {               // Y = X Z and G = X^T Y of the further traits
-            w.ty = wa.take((size_t)p.Mld * traits_t16(pl.rd.traits_T) * sizeof(double));
-            w.tg = wa.take((size_t)p.Mld * traits_t16(pl.rd.traits_T) * sizeof(double));
-        }
-        w.mye = w.mae = w.myu = w.mld = 0;
-        if (pl.rd.miss && p.miss_nm) {      // the columns of X and of B11^-1 of the missing SNPs, B21 times them, every trait's L_D and c
-            const size_t E16 = (size_t)traits_t16(p.miss_E);
-            w.mye = wa.take((size_t)p.Mld * E16 * sizeof(double));
-            w.mae = wa.take((size_t)p.Mld * E16 * sizeof(double));
-            w.myu = wa.take(E16 * (size_t)p.U * sizeof(double));
-            w.mld = wa.take((size_t)p.miss_nm * MISS_LD * sizeof(double));
-        }
-        w.ld = wa.take(std::max<size_t>(pl.out_ld_count, 1) * sizeof(double));
-        pl.res_off = res;
-        res += pl.res_count();
-    }
+    for (int i = 0; i < job->n; i++) layout_window(job->plans[i]);
     // job-wide measured rows (shared measured rows): one more tile of rows than Mp, because a window's last row tile
     // starts wherever the window starts and may reach past the chromosome's last measured SNP (zero rows there)
-    struct GOff { size_t packed, sx, sxx, sd, wm, mu, wmu, slab; } go = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (shm) {
-        const Prob& q = job->gplan->p;
+    if (shm()) {
+        Prob& q = job->gplan->p;
         const size_t rows = (size_t)q.Mp + TILE;
-        go.packed = wa.take(rows * q.Kp);
-        go.sx = wa.take(rows * q.P * sizeof(int));
-        go.sxx = wa.take(rows * q.P * sizeof(int));
-        go.sd = wa.take(rows * sizeof(double));
-        go.wm = wa.take(rows * sizeof(double));
-        go.mu = wa.take(rows * q.P * sizeof(double));
-        go.wmu = wa.take(rows * q.P * sizeof(double));
-        go.slab = wslab.take((size_t)q.npair * q.nseg * TILE * TILE * (q.slab16 ? sizeof(uint16_t) : sizeof(float)));
+        ws(q.packed, rows * q.Kp);
+        ws(q.sx, rows * q.P * sizeof(int)); ws(q.sxx, rows * q.P * sizeof(int));
+        ws(q.rt_sd, rows * sizeof(double)); ws(q.rt_wm, rows * sizeof(double));
+        ws(q.rt_mu, rows * q.P * sizeof(double)); ws(q.rt_wmu, rows * q.P * sizeof(double));
+        slab(q.slab, (size_t)q.npair * q.nseg * TILE * TILE * (q.slab16 ? sizeof(uint16_t) : sizeof(float)));
     }
-    const size_t o_status = wa.take(sizeof(int) * (4 * job->n + 4));    // [n][4], then 4 job-wide ints ([4 n]: the chain queue timed out)
-    const size_t o_count = wa.take(128);                                 // counters of the merged Gram launch, a cache line each: [0] B11's items, [8] the early windows' B21 items (zeroed once; they only grow)
-    const size_t o_code3 = wa.take(64);                                  // stamp of the latest pack launch that met a code 3 (gauss_job::d_code3; zeroed once, only grows)
-    const size_t o_results = wa.take(sizeof(double) * std::max<size_t>(res, 1));
+    ws(job->d_status, sizeof(int) * (4 * job->n + 4));     // [n][4], then 4 job-wide ints ([4 n]: the chain queue timed out)
+    ws(job->d_b11_done, 128);                                // counters of the merged Gram launch, a cache line each: [0] B11's items, [8] the early windows' B21 items (zeroed once; they only grow)
+    ws(job->d_code3, 64, ctx->gram_pkf_geno != 0);         // stamp of the latest pack launch that met a code 3 (gauss_job::d_code3; zeroed once, only grows)
+    ws(job->d_results, sizeof(double) * std::max<size_t>(res, 1));
     job->n_results = res;
-    const size_t slab_base = rup(wa.off, 4096);
-    for (WsOff& w : wo) w.slab += slab_base;
-    go.slab += slab_base;
+    slab_base = rup(wa.off, 4096);
     job->ws_bytes = slab_base + wslab.off;
-    job->tab_bytes = rup(blob.size(), 16);                               // (copied in 16-byte words, below)
-
-    const bool job_trace = trace_on("job");
-    const auto tj0 = std::chrono::steady_clock::now();
+    job->tab_bytes = rup(job->h_tab.size(), 16);                               // (copied in 16-byte words: upload_tables)
+    return GAUSS_OK;
+}
+// The three allocations, the result mirrors and the export chunks
+int JobBuild::allocate()
+{
     hipError_t e = ctx_dev_alloc(ctx, job->ws_bytes, (void**)&job->d_ws);
     if (e != hipSuccess) { job->d_ws = nullptr; return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes workspace) failed: %s", wa.off, hipGetErrorString(e)); }
     e = ctx_dev_alloc(ctx, job->tab_bytes, (void**)&job->d_tab);
-    if (e != hipSuccess) { job->d_tab = nullptr; return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes tables) failed", blob.size()); }
+    if (e != hipSuccess) { job->d_tab = nullptr; return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes tables) failed", job->h_tab.size()); }
     // one pinned block for the table image and the result mirrors: the table upload is then a true asynchronous
     // DMA and a job over resident rows is created without waiting for the stream (another job may be running on it)
-    const size_t pin_tab = rup(job->tab_bytes, 256), pin_res = rup(sizeof(double) * std::max<size_t>(res, 1), 256);
-    const size_t pin_st = rup(sizeof(int) * (4 * job->n + 4), 256);
+    pin_tab = rup(job->tab_bytes, 256); pin_res = rup(sizeof(double) * std::max<size_t>(res, 1), 256);
+    pin_st = rup(sizeof(int) * (4 * job->n + 4), 256);
     const size_t pin_exp = rup(sizeof(double) * exp_doubles, 256);
     e = ctx_pin_alloc(ctx, pin_tab + 2 * (pin_res + pin_st) + pin_exp, (void**)&job->h_pin);
     if (e != hipSuccess) { job->h_pin = nullptr; return fail(GAUSS_E_NOMEM, "hipHostMalloc(%zu bytes) failed", pin_tab + 2 * pin_res); }
@@ -1286,7 +1323,10 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         job->exp_ev.assign(job->exp_chunks.size(), nullptr);
         for (hipEvent_t& ev : job->exp_ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    const auto tj1 = std::chrono::steady_clock::now();
+    return GAUSS_OK;
+}
+int JobBuild::events_and_zeroing()
+{
     HIPCHK(hipEventCreate(&job->begin));
     for (int k = 0; k < 2; k++)
         for (hipEvent_t* e : {&job->rev[k].gram, &job->rev[k].side, &job->rev[k].pack, &job->rev[k].rows, &job->rev[k].epi})
@@ -1311,165 +1351,104 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         HIPCHK(hipEventRecord(job->zeroed, zs));
         HIPCHK(hipStreamWaitEvent(st, job->zeroed, 0));
     }
-    if (streamed) {
+    if (streamed()) {
         job->sevp.resize(job->sgroups.size(), nullptr);
         for (hipEvent_t& e : job->sevp) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-
-    job->d_status = (int*)(job->d_ws + o_status);
-    job->d_b11_done = (unsigned long long*)(job->d_ws + o_count);
-    job->d_code3 = ctx->gram_pkf_geno ? (unsigned long long*)(job->d_ws + o_code3) : nullptr;
-    job->d_results = (double*)(job->d_ws + o_results);
-    std::deque<std::vector<uint8_t>> stage;      // host gather buffers, alive until the copies have drained
+    return GAUSS_OK;
+}
+// Every recorded pointer, then what is derived from them, then the descriptors into the table image
+int JobBuild::bind()
+{
+    relocate();
+    std::vector<char>& blob = job->h_tab;
+    if (shm()) {
+        // descriptor n: the job-wide measured rows (pack_stats / row_stats work on it; nothing else is launched for it)
+        Plan& g = *job->gplan;
+        Prob& q = g.p;
+        q.ld_raw = g.user_ld;
+        q.raw_m = g.h_geno_m; q.raw_u = nullptr;
+        q.packed_u = q.packed; q.sx_u = q.sx; q.sxx_u = q.sxx;
+        q.rt_sd_u = q.rt_sd; q.rt_wm_u = q.rt_wm; q.rt_mu_u = q.rt_mu; q.rt_wmu_u = q.rt_wmu;
+        q.slab_g = q.slab; q.gpair_ti = q.pair_ti; q.gpair_tj = q.pair_tj; q.g0 = 0; q.n_gpair = q.npair;
+        q.status = job->d_status;      // never written for this descriptor
+        memcpy(blob.data() + o_probs + sizeof(Prob) * (size_t)job->n, &q, sizeof(Prob));
+    }
     for (int i = 0; i < job->n; i++) {
         Plan& pl = job->plans[i];
         Prob& p = pl.p;
-        const WsOff& w = wo[i];
-        char* T = job->d_tab;
-        char* W = job->d_ws;
-        p.ld_raw = w.ldraw;
-        if (streamed) { p.raw_m = stream->d_m; p.raw_u = stream->d_u; }
-        else if (on_device) { p.raw_m = pl.h_geno_m; p.raw_u = pl.h_geno_u; }
-        else { p.raw_m = (const uint8_t*)(W + w.raw_m); p.raw_u = (const uint8_t*)(W + w.raw_u); }
-        p.packed = (uint8_t*)(W + w.packed);
-        p.sx = (int*)(W + w.sx); p.sxx = (int*)(W + w.sxx);
-        p.pop_raw_off = (const int*)(T + to[i].raw_off);
-        p.pop_pk_off = (const int*)(T + to[i].pk_off);
-        p.pop_w = (const double*)(T + to[i].w);
-        p.pop_wf = (const double*)(T + to[i].wf);
-        p.pop_md = (const double*)(T + to[i].md);
-        p.seg_pop = (const int*)(T + to[i].seg_pop);
-        p.seg_k0 = (const int*)(T + to[i].k0);
-        p.seg_k1 = (const int*)(T + to[i].k1);
-        p.pop_seg0 = (const int*)(T + to[i].seg0);
-        p.pair_ti = (const int*)(T + to[i].ti);
-        p.pair_tj = (const int*)(T + to[i].tj);
-        p.pair_lut = (const int*)(T + to[i].lut);
-        p.word_pop = (const uint8_t*)(T + to[i].wp);
-        p.word_run = (const uint8_t*)(T + to[i].wr);
-        // row lists are resolved on the device only for a resident store; host rows are gathered while staging
-        p.rows_m = (on_device && !pl.rows_m.empty()) ? (const int*)(T + to[i].rm) : nullptr;
-        p.rows_u = (on_device && !pl.rows_u.empty()) ? (const int*)(T + to[i].ru) : nullptr;
-        p.run_pk_off = (const int*)(T + to[i].rpk);
-        p.run_src = (const int*)(T + to[i].rsrc);
-        p.slab = (float*)(W + w.slab);
-        p.rt_sd = (double*)(W + w.sd); p.rt_wm = (double*)(W + w.wm);
-        p.rt_mu = (double*)(W + w.mu); p.rt_wmu = (double*)(W + w.wmu);
-        p.z1 = (const double*)(T + to[i].z1);
-        if (!p.ld_only) { p.A = (double*)(W + w.A); p.B21 = (double*)(W + w.B21); }
-        if (p.npanel > 0) {
-            p.Linv = (double*)(W + w.Linv); p.V = (double*)(W + w.V); p.Gsum = (double*)(W + w.gsum);
-            p.Part = (double*)(W + w.part);
-            pl.d_b11_copy = (double*)(W + w.b11c);
-        }
         const ResLayout lay = pl.layout();
         double* const out = job->d_results + pl.res_off;
-        p.out_z = out + lay.z;
-        p.out_info = out + lay.info;
+        p.out_z = out + lay.z; p.out_info = out + lay.info;
         p.out_loo = pl.rd.loo ? out + lay.loo : nullptr;
         p.out_slct = pl.rd.slct_K ? out + lay.slct : nullptr;
-        p.slct_W = pl.rd.slct_K ? (double*)(W + w.slct) : nullptr;
-        p.slct_forced = pl.rd.slct_forced.empty() ? nullptr : (const int*)(T + to[i].sf);
         p.out_cond = pl.rd.cond ? out + lay.cond : nullptr;
         p.out_cs = pl.rd.cs ? out + lay.cs : nullptr;
-        p.cs_lbf = pl.rd.cs ? (double*)(W + w.cs_lbf) : nullptr;
-        p.cs_mem = pl.rd.cs ? (uint8_t*)(W + w.cs_mem) : nullptr;
         p.out_susie = pl.rd.susie_L && !pl.xs_peer() ? out + lay.susie : nullptr;
         p.out_susie_more = pl.rd.susie_L && lay.xs > lay.susie_more ? out + lay.susie_more : nullptr;
-        p.susie_ws = pl.rd.susie_L ? (double*)(W + w.susie_ws) : nullptr;
-        p.susie_mem = pl.rd.susie_L ? (uint8_t*)(W + w.susie_mem) : nullptr;
         p.out_xs = lay.prs > lay.xs ? out + lay.xs : nullptr;
         p.out_prs = pl.rd.prs_n_s ? out + lay.prs : nullptr;
-        p.xs_from_lead = pl.rd.xs_from_lead.empty() ? nullptr : (const int*)(T + to[i].xf);
-        p.xs_to_lead = pl.rd.xs_to_lead.empty() ? nullptr : (const int*)(T + to[i].xt);
         p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;
-        p.traits_Z = pl.rd.traits_T ? (const double*)(T + to[i].tz) : nullptr;
-        p.traits_Y = pl.rd.traits_T ? (double*)(W + w.ty) : nullptr;
-        p.traits_G = pl.rd.traits_T ? (double*)(W + w.tg) : nullptr;
-        p.miss_tab = pl.rd.miss ? (const int*)(T + to[i].mt) : nullptr;
-        const bool miss_ws = pl.rd.miss && p.miss_nm;
-        p.miss_YE = miss_ws ? (double*)(W + w.mye) : nullptr;
-        p.miss_AE = miss_ws ? (double*)(W + w.mae) : nullptr;
-        p.miss_YU = miss_ws ? (double*)(W + w.myu) : nullptr;
-        p.miss_LD = miss_ws ? (double*)(W + w.mld) : nullptr;
-        p.out_traits_info = pl.rd.miss ? out + lay.traits_info : nullptr;
-        p.out_traits_miss = pl.rd.miss ? out + lay.traits_miss : nullptr;
+        p.out_traits_info = pl.rd.miss ? out + lay.traits_info : nullptr; p.out_traits_miss = pl.rd.miss ? out + lay.traits_miss : nullptr;
         p.status = job->d_status + 4 * i;
-        p.out_ld = (double*)(W + w.ld);
-        p.gene_off = p.n_gene ? (const int*)(T + to[i].goff) : nullptr;
-        p.gene_out_off = p.n_gene ? (long long*)(T + to[i].gout) : nullptr;
-        p.draw_col = pl.draw_col.empty() ? nullptr : (const int*)(T + to[i].dc);
         // the unmeasured part of every row array follows the measured part ...
         p.packed_u = p.packed + (size_t)p.Mp * p.Kp;
         p.sx_u = p.sx + (size_t)p.Mp * p.P; p.sxx_u = p.sxx + (size_t)p.Mp * p.P;
         p.rt_sd_u = p.rt_sd + p.Mp; p.rt_wm_u = p.rt_wm + p.Mp;
         p.rt_mu_u = p.rt_mu + (size_t)p.Mp * p.P; p.rt_wmu_u = p.rt_wmu + (size_t)p.Mp * p.P;
         p.g0 = 0; p.n_gpair = 0; p.gpair_ti = p.pair_ti; p.gpair_tj = p.pair_tj; p.slab_g = p.slab;
-        if (shm) {
+        if (shm()) {
             // ... unless the measured rows are the job-wide ones: this window's run starts at g0
             const Prob& q = job->gplan->p;
             const size_t g0 = (size_t)job->g0[(size_t)i];
             p.g0 = (int)g0; p.n_gpair = q.npair;
-            p.packed = (uint8_t*)(W + go.packed) + g0 * q.Kp;
-            p.sx = (int*)(W + go.sx) + g0 * q.P; p.sxx = (int*)(W + go.sxx) + g0 * q.P;
-            p.rt_sd = (double*)(W + go.sd) + g0; p.rt_wm = (double*)(W + go.wm) + g0;
-            p.rt_mu = (double*)(W + go.mu) + g0 * q.P; p.rt_wmu = (double*)(W + go.wmu) + g0 * q.P;
-            p.gpair_ti = (const int*)(T + to[(size_t)job->n].ti); p.gpair_tj = (const int*)(T + to[(size_t)job->n].tj);
-            p.slab_g = (float*)(W + go.slab);
+            p.packed = q.packed + g0 * q.Kp;
+            p.sx = q.sx + g0 * q.P; p.sxx = q.sxx + g0 * q.P;
+            p.rt_sd = q.rt_sd + g0; p.rt_wm = q.rt_wm + g0;
+            p.rt_mu = q.rt_mu + g0 * q.P; p.rt_wmu = q.rt_wmu + g0 * q.P;
+            p.gpair_ti = q.pair_ti; p.gpair_tj = q.pair_tj;
+            p.slab_g = q.slab;
         }
         memcpy(blob.data() + o_probs + sizeof(Prob) * i, &p, sizeof(Prob));
-        if (!on_device && !streamed) {
-            auto upload = [&](size_t dst_off, const uint8_t* src, const std::vector<int32_t>& rows, int nrows) -> int {
-                if (nrows <= 0) return GAUSS_OK;
-                if (rows.empty()) {
-                    if (w.ldraw == pl.user_ld)      // same stride: one linear copy (the last row stops at its data)
-                        HIPCHK(hipMemcpyAsync(W + dst_off, src, (size_t)(nrows - 1) * pl.user_ld + pl.row_bytes,
-                                              hipMemcpyHostToDevice, st));
-                    else
-                        HIPCHK(hipMemcpy2DAsync(W + dst_off, (size_t)w.ldraw, src, (size_t)pl.user_ld, pl.row_bytes,
-                                                (size_t)nrows, hipMemcpyHostToDevice, st));
-                    return GAUSS_OK;
-                }
-                stage.emplace_back((size_t)nrows * w.ldraw);               // gather the listed store rows
-                std::vector<uint8_t>& buf = stage.back();
-                for (int r = 0; r < nrows; r++)
-                    memcpy(buf.data() + (size_t)r * w.ldraw, src + (size_t)rows[r] * pl.user_ld, pl.row_bytes);
-                HIPCHK(hipMemcpyAsync(W + dst_off, buf.data(), buf.size(), hipMemcpyHostToDevice, st));
-                return GAUSS_OK;
-            };
-            int rc = upload(w.raw_m, pl.h_geno_m, pl.rows_m, p.M);
-            if (!rc) rc = upload(w.raw_u, pl.h_geno_u, pl.rows_u, pl.U_user);
-            if (rc) return rc;
-        }
     }
-    if (shm) {
-        // descriptor n: the job-wide measured rows (pack_stats / row_stats work on it; nothing else is launched for it)
-        Plan& g = *job->gplan;
-        Prob& q = g.p;
-        const size_t n = (size_t)job->n;
-        char* T = job->d_tab;
-        char* W = job->d_ws;
-        q.ld_raw = g.user_ld;
-        q.raw_m = g.h_geno_m; q.raw_u = nullptr;
-        q.packed = (uint8_t*)(W + go.packed); q.packed_u = q.packed;
-        q.sx = (int*)(W + go.sx); q.sxx = (int*)(W + go.sxx); q.sx_u = q.sx; q.sxx_u = q.sxx;
-        q.rt_sd = (double*)(W + go.sd); q.rt_wm = (double*)(W + go.wm); q.rt_sd_u = q.rt_sd; q.rt_wm_u = q.rt_wm;
-        q.rt_mu = (double*)(W + go.mu); q.rt_wmu = (double*)(W + go.wmu); q.rt_mu_u = q.rt_mu; q.rt_wmu_u = q.rt_wmu;
-        q.pop_raw_off = (const int*)(T + to[n].raw_off); q.pop_pk_off = (const int*)(T + to[n].pk_off);
-        q.pop_w = (const double*)(T + to[n].w); q.pop_wf = (const double*)(T + to[n].wf); q.pop_md = (const double*)(T + to[n].md);
-        q.seg_pop = (const int*)(T + to[n].seg_pop); q.seg_k0 = (const int*)(T + to[n].k0); q.seg_k1 = (const int*)(T + to[n].k1);
-        q.pop_seg0 = (const int*)(T + to[n].seg0);
-        q.pair_ti = (const int*)(T + to[n].ti); q.pair_tj = (const int*)(T + to[n].tj); q.pair_lut = (const int*)(T + to[n].lut);
-        q.word_pop = (const uint8_t*)(T + to[n].wp); q.word_run = (const uint8_t*)(T + to[n].wr);
-        q.rows_m = (const int*)(T + to[n].rm); q.rows_u = nullptr;
-        q.run_pk_off = (const int*)(T + to[n].rpk); q.run_src = (const int*)(T + to[n].rsrc);
-        q.slab = (float*)(W + go.slab); q.slab_g = q.slab; q.gpair_ti = q.pair_ti; q.gpair_tj = q.pair_tj; q.g0 = 0; q.n_gpair = q.npair;
-        q.z1 = nullptr; q.A = nullptr; q.B21 = nullptr; q.Linv = nullptr; q.V = nullptr; q.Gsum = nullptr; q.Part = nullptr;
-        q.out_z = q.out_info = nullptr; clear_riders(q); q.out_ld = nullptr; q.status = job->d_status;      // never written for this descriptor
-        q.gene_off = nullptr; q.gene_out_off = nullptr; q.n_gene = 0;
-        memcpy(blob.data() + o_probs + sizeof(Prob) * n, &q, sizeof(Prob));
+    return GAUSS_OK;
+}
+// Rows of a host matrix into a window's raw block: one copy, or the listed store rows gathered first
+int JobBuild::upload_rows(const Plan& pl, const uint8_t* dst_rows, const uint8_t* src, const std::vector<int32_t>& rows, int nrows)
+{
+    void* const dst = (void*)dst_rows;
+    const long long ldraw = pl.p.ld_raw;
+    hipStream_t st = ctx->stream;
+    if (nrows <= 0) return GAUSS_OK;
+    if (rows.empty()) {
+        if (ldraw == pl.user_ld)      // same stride: one linear copy (the last row stops at its data)
+            HIPCHK(hipMemcpyAsync(dst, src, (size_t)(nrows - 1) * pl.user_ld + pl.row_bytes,
+                                  hipMemcpyHostToDevice, st));
+        else
+            HIPCHK(hipMemcpy2DAsync(dst, (size_t)ldraw, src, (size_t)pl.user_ld, pl.row_bytes,
+                                    (size_t)nrows, hipMemcpyHostToDevice, st));
+        return GAUSS_OK;
     }
-    // device work items: every pointer is resolved here so the kernel starts loading operands at once
+    stage.emplace_back((size_t)nrows * ldraw);               // gather the listed store rows
+    std::vector<uint8_t>& buf = stage.back();
+    for (int r = 0; r < nrows; r++)
+        memcpy(buf.data() + (size_t)r * ldraw, src + (size_t)rows[r] * pl.user_ld, pl.row_bytes);
+    HIPCHK(hipMemcpyAsync(dst, buf.data(), buf.size(), hipMemcpyHostToDevice, st));
+    return GAUSS_OK;
+}
+int JobBuild::upload_host_rows()
+{
+    if (on_device || streamed()) return GAUSS_OK;
+    for (const Plan& pl : job->plans) {
+        int rc = upload_rows(pl, pl.p.raw_m, pl.h_geno_m, pl.rows_m, pl.p.M);
+        if (!rc) rc = upload_rows(pl, pl.p.raw_u, pl.h_geno_u, pl.rows_u, pl.U_user);
+        if (rc) return rc;
+    }
+    return GAUSS_OK;
+}
+// device work items: every pointer is resolved here so the kernel starts loading operands at once
+int JobBuild::write_items()
+{
     for (size_t n = 0; n < items.size(); n++) {
         const ItemH& h = items[n];
         const Plan& pl = plan_of(h.prob);
@@ -1477,10 +1456,6 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         const std::pair<int, int>& gr = h.group >= 0 ? pl.groups[h.group] : pl.fine[(size_t)(-1 - h.group)];
         const int ti = pl.pair_ti[h.pair], tj = pl.pair_tj[h.pair];
         const int mt = p.Mp / TILE;
-        auto rows = [&](int t) {
-            if (!pl.tile_live.empty()) return pl.tile_live[(size_t)t];
-            int left = (t < mt) ? p.M - t * TILE : p.U - (t - mt) * TILE; return left > TILE ? TILE : left;
-        };
         // a row tile of the measured part (for a window that shares its measured rows: inside the job-wide array, from
         // wherever the window starts) or of the unmeasured part
         auto tile_rows = [&](int t) { return t < mt ? p.packed + (size_t)t * TILE * p.Kp : p.packed_u + (size_t)(t - mt) * TILE * p.Kp; };
@@ -1489,54 +1464,55 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         it.b = tile_rows(tj);
         it.slab = p.slab + ((size_t)h.pair * p.nseg + gr.first) * (p.slab16 ? TILE * TILE / 2 : TILE * TILE);
         it.seg_k1 = p.seg_k1 + gr.first;
-        it.chunk_live = (const uint32_t*)(job->d_tab + to[h.prob].ch);
+        it.chunk_live = chunk_live[(size_t)h.prob];
         it.Kp = p.Kp; it.k0 = pl.seg_k0[gr.first]; it.nseg = gr.second - gr.first;
-        it.rows_a = rows(ti); it.rows_b = rows(tj); it.flags = (ti == tj ? 1 : 0) | (p.slab16 ? 2 : 0) | (p.slab16 && job->gram_packed ? 4 : 0);
+        it.rows_a = live_rows(pl, ti); it.rows_b = live_rows(pl, tj); it.flags = (ti == tj ? 1 : 0) | (p.slab16 ? 2 : 0) | (p.slab16 && job->gram_packed ? 4 : 0);
         if (job->gram_narrow) it.flags |= tile_layout(it.rows_a, it.rows_b, (it.flags & 4) != 0) << LAYOUT_SHIFT;
         if (job->merged && (int)n < job->n_items_b11) it.flags |= 16;         // counts itself off in b11_done[0]
         else if (job->merged && (int)n < job->n_items_b11 + job->n_items_b21_early) it.flags |= 32;      // ... in b11_done[8] (the early windows' B21 items)
-        memcpy(blob.data() + o_items + sizeof(Item) * n, &it, sizeof(Item));
+        memcpy(job->h_tab.data() + o_items + sizeof(Item) * n, &it, sizeof(Item));
     }
-    // GAUSS_PLAN_FILL=1: how unequal the four waves of the job's items are.  Per item, the waves' MFMA issue per K step as shares of
-    // a full wave's (k_gram_common.h: wave_load); the waves meet at a barrier every chunk, so an item runs at the pace of its
-    // fullest wave.  Printed per class (B11's items, B21's), in K samples x full waves: the issue of the fullest wave (`max`: the
-    // item's time while its fullest wave has its SIMD's matrix pipe to itself), the mean of the four (`mean`: its time if every
-    // SIMD of the CU saw an equal share), for the quadrant roles and for the layouts this job's items carry.
-    if (env_int("GAUSS_PLAN_FILL", 0) != 0 && !job->gram_i8) {
-        double mx[2][2] = {{0, 0}, {0, 0}}, mean[2][2] = {{0, 0}, {0, 0}}, full[2] = {0, 0};
-        long n_narrow[2] = {0, 0}, n_uneven[2] = {0, 0}, n_cls[2] = {0, 0};
-        for (size_t n = 0; n < items.size(); n++) {
-            const ItemH& h = items[n];
-            const Plan& pl = plan_of(h.prob);
-            const int ti = pl.pair_ti[h.pair], tj = pl.pair_tj[h.pair];
-            const int mt = pl.p.Mp / TILE;
-            auto rows = [&](int t) {
-                if (!pl.tile_live.empty()) return pl.tile_live[(size_t)t];
-                int left = (t < mt) ? pl.p.M - t * TILE : pl.p.U - (t - mt) * TILE; return left > TILE ? TILE : left;
-            };
-            const int ra = rows(ti), rb = rows(tj), c = h.b11 ? 0 : 1;
-            const bool packed = job->gram_packed && pl.p.slab16;
-            n_cls[c]++;
-            full[c] += h.len;
-            for (int f = 0; f < 2; f++) {
-                const int layout = (f && job->gram_narrow) ? tile_layout(ra, rb, packed) : LAYOUT_QUAD;
-                double m = 0, s = 0;
-                for (int w = 0; w < 4; w++) {
-                    const double l = wave_load(wave_work(ra, rb, ti == tj, packed, true, w, layout), packed);
-                    m = std::max(m, l); s += l;
-                }
-                mx[f][c] += h.len * m; mean[f][c] += h.len * s / 4;
-                if (f && layout != LAYOUT_QUAD) n_narrow[c]++;
-                if (!f && m * 4 > s + 1e-9) n_uneven[c]++;
+    return GAUSS_OK;
+}
+// GAUSS_PLAN_FILL=1: how unequal the four waves of the job's items are.  Per item, the waves' MFMA issue per K step as shares of
+// a full wave's (k_gram_common.h: wave_load); the waves meet at a barrier every chunk, so an item runs at the pace of its
+// fullest wave.  Printed per class (B11's items, B21's), in K samples x full waves: the issue of the fullest wave (`max`: the
+// item's time while its fullest wave has its SIMD's matrix pipe to itself), the mean of the four (`mean`: its time if every
+// SIMD of the CU saw an equal share), for the quadrant roles and for the layouts this job's items carry.
+int JobBuild::fill_report()
+{
+    if (!(env_int("GAUSS_PLAN_FILL", 0) != 0 && !job->gram_i8)) return GAUSS_OK;
+    double mx[2][2] = {{0, 0}, {0, 0}}, mean[2][2] = {{0, 0}, {0, 0}}, full[2] = {0, 0};
+    long n_narrow[2] = {0, 0}, n_uneven[2] = {0, 0}, n_cls[2] = {0, 0};
+    for (const ItemH& h : items) {
+        const Plan& pl = plan_of(h.prob);
+        const int ti = pl.pair_ti[h.pair], tj = pl.pair_tj[h.pair];
+        const int ra = live_rows(pl, ti), rb = live_rows(pl, tj), c = h.b11 ? 0 : 1;
+        const bool packed = job->gram_packed && pl.p.slab16;
+        n_cls[c]++;
+        full[c] += h.len;
+        for (int f = 0; f < 2; f++) {
+            const int layout = (f && job->gram_narrow) ? tile_layout(ra, rb, packed) : LAYOUT_QUAD;
+            double m = 0, s = 0;
+            for (int w = 0; w < 4; w++) {
+                const double l = wave_load(wave_work(ra, rb, ti == tj, packed, true, w, layout), packed);
+                m = std::max(m, l); s += l;
             }
-        }
-        for (int c = 0; c < 2; c++) {
-            if (!n_cls[c]) continue;
-            fprintf(stderr, "[fill] %s: %ld items (%ld with unequal waves, %ld narrow), K x tiles %.4e; quadrant roles: max %.4e mean %.4e mean/max %.4f; "
-                            "this job's layouts: max %.4e mean %.4e mean/max %.4f\n", c ? "B21" : "B11", n_cls[c], n_uneven[c], n_narrow[c], full[c],
-                    mx[0][c], mean[0][c], mean[0][c] / mx[0][c], mx[1][c], mean[1][c], mean[1][c] / mx[1][c]);
+            mx[f][c] += h.len * m; mean[f][c] += h.len * s / 4;
+            if (f && layout != LAYOUT_QUAD) n_narrow[c]++;
+            if (!f && m * 4 > s + 1e-9) n_uneven[c]++;
         }
     }
+    for (int c = 0; c < 2; c++) {
+        if (!n_cls[c]) continue;
+        fprintf(stderr, "[fill] %s: %ld items (%ld with unequal waves, %ld narrow), K x tiles %.4e; quadrant roles: max %.4e mean %.4e mean/max %.4f; "
+                        "this job's layouts: max %.4e mean %.4e mean/max %.4f\n", c ? "B21" : "B11", n_cls[c], n_uneven[c], n_narrow[c], full[c],
+                mx[0][c], mean[0][c], mean[0][c] / mx[0][c], mx[1][c], mean[1][c], mean[1][c] / mx[1][c]);
+    }
+    return GAUSS_OK;
+}
+int JobBuild::export_descriptors()
+{
     for (size_t x = 0; x < job->exports.size(); x++) {
         const gauss_job::Export& ex = job->exports[x];
         const Plan& pl = job->plans[(size_t)ex.plan];
@@ -1544,44 +1520,53 @@ int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, 
         d.src = ex.which ? pl.p.B21 : (pl.p.kind == GAUSS_WIN_LD ? pl.p.A : pl.d_b11_copy);
         d.dst = job->h_export + ex.off;
         d.rows = ex.rows; d.width = ex.width; d.pitch = ex.pitch; d.pad_ = 0;
-        memcpy(blob.data() + o_exports + sizeof(ExportD) * x, &d, sizeof(ExportD));
+        memcpy(job->h_tab.data() + o_exports + sizeof(ExportD) * x, &d, sizeof(ExportD));
     }
-    const auto tj2 = std::chrono::steady_clock::now();
-    memcpy(job->h_pin, blob.data(), blob.size());
+    return GAUSS_OK;
+}
+int JobBuild::upload_tables()
+{
+    memcpy(job->h_pin, job->h_tab.data(), job->h_tab.size());
     // The table image crosses PCIe by kernel, not by hipMemcpyAsync: while a background upload keeps the DMA engines busy
     // (gauss_store_upload_async: a chromosome's first call) the runtime made the CALLER wait for an engine -- one job creation in
     // five stalled for 11-16 ms on these few MB (GAUSS_JOB_TRACE=1, round 4), the GPU idle meanwhile.
-    launch_h2d_copy(job->d_tab, job->h_pin, job->tab_bytes, st);
+    launch_h2d_copy(job->d_tab, job->h_pin, job->tab_bytes, ctx->stream);
     HIPCHK(hipGetLastError());
+    return GAUSS_OK;
+}
+// streamed: one window on contiguous host matrices whose upload is left to job_run_streamed (chunk by chunk on the
+// copy stream, overlapped with the pack / Gram launches of the rows that have landed)
+int job_build(gauss_ctx* ctx, const std::vector<WinSpec>& specs, int on_device, gauss_job** out, const StreamSetup* stream)
+{
+    typedef std::chrono::steady_clock clk;
+    const auto tb0 = clk::now();
+    gauss_job* job = new gauss_job();
+    // every early return below (bad arguments, a failed HIP call) releases the job and what it owns
+    std::unique_ptr<gauss_job, void (*)(gauss_job*)> guard(job, job_free);
+    JobBuild b{ctx, specs, on_device, stream, job};
+    int rc;
+    if ((rc = b.plan_windows()) || (rc = b.plan_exports())) return rc;
+    const auto tb1 = clk::now();
+    if ((rc = b.share_measured()) || (rc = b.check_row_lists())) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    job->h_tab.reserve((size_t)b.n_prob() * ((size_t)320 << 10) + ((size_t)64 << 10));      // (~0.3 MB a window: grown in place, not copied over and over)
+    const auto tb2 = clk::now();
+    if ((rc = b.place_all_tables()) || (rc = b.work_lists()) || (rc = b.order_items()) || (rc = b.place_lists()) || (rc = b.layout_workspace())) return rc;
+    const bool job_trace = trace_on("job");
+    const auto tj0 = clk::now();
+    if ((rc = b.allocate())) return rc;
+    const auto tj1 = clk::now();
+    if ((rc = b.events_and_zeroing()) || (rc = b.bind()) || (rc = b.upload_host_rows()) || (rc = b.write_items()) || (rc = b.fill_report()) ||
+        (rc = b.export_descriptors())) return rc;
+    const auto tj2 = clk::now();
+    if ((rc = b.upload_tables())) return rc;
     if (job_trace) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        auto ms = [](clk::time_point t0, clk::time_point t1) { return std::chrono::duration<double, std::milli>(t1 - t0).count(); };
         fprintf(stderr, "[job] %d windows: plan %.2f ms (the windows' plans %.2f, shared rows + row checks %.2f, tables + work items %.2f), allocations %.2f ms (workspace %.1f MB, tables %.2f MB, pinned %.2f MB), events + zeroing + tables %.2f ms, table copy queued in %.2f ms\n",
-                job->n, ms(tb0, tj0), ms(tb0, tb1), ms(tb1, tb2), ms(tb2, tj0), ms(tj0, tj1), job->ws_bytes / 1e6, job->tab_bytes / 1e6, (pin_tab + 2 * (pin_res + pin_st)) / 1e6, ms(tj1, tj2),
-                ms(tj2, std::chrono::steady_clock::now()));
+                job->n, ms(tb0, tj0), ms(tb0, tb1), ms(tb1, tb2), ms(tb2, tj0), ms(tj0, tj1), job->ws_bytes / 1e6, job->tab_bytes / 1e6, (b.pin_tab + 2 * (b.pin_res + b.pin_st)) / 1e6, ms(tj1, tj2),
+                ms(tj2, clk::now()));
     }
-    job->d_probs = (Prob*)(job->d_tab + o_probs);
-    job->d_items = (Item*)(job->d_tab + o_items);
-    job->d_rowmap = (int2*)(job->d_tab + o_rowmap);
-    job->d_tilemap = (int2*)(job->d_tab + o_tilemap);
-    job->d_panelmap = (int2*)(job->d_tab + o_panelmap);
-    job->d_dpanelmap = (int2*)(job->d_tab + o_dpanelmap);
-    job->d_gemmmap = (int2*)(job->d_tab + o_gemmmap);
-    job->d_finmap = (int2*)(job->d_tab + o_finmap);
-    job->d_loomap = (int2*)(job->d_tab + o_loomap);
-    job->d_slctmap = (int*)(job->d_tab + o_slctmap);
-    job->d_condmap = (int*)(job->d_tab + o_condmap);
-    job->d_csmap = (int*)(job->d_tab + o_csmap);
-    job->d_prsmap = (int*)(job->d_tab + o_prsmap);
-    job->d_susiemap = (int*)(job->d_tab + o_susiemap);
-    job->d_xsmap = (int*)(job->d_tab + o_xsmap);
-    job->d_xsleadmap = (int*)(job->d_tab + o_xsleadmap);
-    job->d_traitsmap = (int2*)(job->d_tab + o_traitsmap);
-    job->d_traitsumap = (int2*)(job->d_tab + o_traitsumap);
-    job->d_missmap = (int2*)(job->d_tab + o_missmap);
-    job->d_misstmap = (int2*)(job->d_tab + o_misstmap);
-    job->d_missumap = (int2*)(job->d_tab + o_missumap);
-    job->d_exports = (ExportD*)(job->d_tab + o_exports);
-    if (!on_device && !streamed) HIPCHK(hipStreamSynchronize(st));   // uploads from pageable user memory are complete
+    if (!on_device && !stream) HIPCHK(hipStreamSynchronize(ctx->stream));   // uploads from pageable user memory are complete
     std::vector<char>().swap(job->h_tab);
     { std::lock_guard<std::mutex> lock(ctx->mu); ctx->jobs.insert(job); }
     *out = guard.release();

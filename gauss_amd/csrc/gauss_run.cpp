@@ -113,17 +113,17 @@ static void queue_tail(gauss_job* job, hipStream_t st)
     launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
     launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
     launch_traits_miss_solve(job->d_probs, job->d_missmap, job->n_miss_blk, job->d_misstmap, job->n_miss_t, st);
-    launch_susie_w(job->d_probs, job->d_susiemap, job->n_susie, job->susie_max_nblk, job->susie_max_U, st);
-    launch_susie_w(job->d_probs, job->d_xsmap, job->n_xs, job->xs_max_nblk, job->xs_max_U, st);
+    launch_susie_w(job->d_probs, job->d_susiemap, job->n_susie, job->susie_dims.nblk, job->susie_dims.U, st);
+    launch_susie_w(job->d_probs, job->d_xsmap, job->n_xs, job->xs_dims.nblk, job->xs_dims.U, st);
     launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
     launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
     launch_traits_miss_apply(job->d_probs, job->d_missumap, job->n_miss_u, st);
     launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);
     launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
-    launch_susie(job->d_probs, job->d_susiemap, job->n_susie, job->susie_max_M, job->susie_max_T, job->susie_max_L, job->susie_max_sweeps,
+    launch_susie(job->d_probs, job->d_susiemap, job->n_susie, job->susie_dims.M, job->susie_dims.T, job->susie_dims.L, job->susie_dims.sweeps,
                  job->susie_max_k, job->susie_coloc, st);
-    launch_xsusie(job->d_probs, job->d_xsmap, job->n_xs, job->d_xsleadmap, job->n_xs_lead, job->xs_max_M, job->xs_max_T, job->xs_max_L,
-                  job->xs_max_sweeps, st);
+    launch_xsusie(job->d_probs, job->d_xsmap, job->n_xs, job->d_xsleadmap, job->n_xs_lead, job->xs_dims.M, job->xs_dims.T, job->xs_dims.L,
+                  job->xs_dims.sweeps, st);
     launch_prs(job->d_probs, job->d_prsmap, job->n_prs, job->prs_max_s, job->prs_max_M, st);
 }
 
