@@ -150,7 +150,7 @@ def build_hip(force=False, verbose=False):
     import json
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
-    hdrs = [os.path.join(CSRC, "gauss_internal.h"), os.path.join(CSRC, "gauss_job.h"), os.path.join(CSRC, "k_gram_common.h"), os.path.join(CSRC, "k_solve_common.h"), os.path.join(CSRC, "k_traits_common.h"), os.path.join(CSRC, "k_cs_common.h"), os.path.join(CSRC, "k_susie_common.h"), os.path.join(HERE, "..", "include", "gauss_hip.h")]
+    hdrs = [os.path.join(CSRC, "gauss_internal.h"), os.path.join(CSRC, "gauss_job.h"), os.path.join(CSRC, "gauss_deliver.h"), os.path.join(CSRC, "k_gram_common.h"), os.path.join(CSRC, "k_solve_common.h"), os.path.join(CSRC, "k_traits_common.h"), os.path.join(CSRC, "k_cs_common.h"), os.path.join(CSRC, "k_susie_common.h"), os.path.join(HERE, "..", "include", "gauss_hip.h")]
     # an object is rebuilt when its recorded identity (source + headers + command line + compiler) differs -- not by mtime: a
     # flag change or a checkout that restores old timestamps must not link stale objects under a fresh source hash
     ids_path = os.path.join(OBJDIR, "unit_ids.json")

@@ -1,11 +1,14 @@
 // Internal declarations shared by the HIP translation units of libgauss_hip.so.
 #pragma once
+#ifndef GAUSS_LAYOUTS_ONLY      // defined: the result block's layouts alone, for a host program without HIP (gauss_deliver.h)
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 #include <atomic>
 #include <mutex>
 
 namespace gauss {
+#ifndef GAUSS_LAYOUTS_ONLY
 
 constexpr int TILE = 128;      // Gram output tile edge per workgroup (4 waves x 64x64)
 constexpr int KC = 64;         // packed K chunk in bytes (= samples); pops are padded to it
@@ -254,6 +257,7 @@ constexpr SusieWs susie_ws(int M, int U, int Mld, int L, bool w)
             lse + SUSIE_L, part, top, ntop, ntop + SUSIE_L, keep, keep + lt, keep + lt - zhat};
 }
 
+#endif
 // ---- the result block ------------------------------------------------------------------------------------------------
 // A window's doubles in the job's result block, in this order and nowhere else written down:
 //     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, traits_info [T][U], traits_miss [2][n_miss]]
@@ -335,6 +339,7 @@ constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, 
             o_prs + (prs_n_s ? prs_layout(M, prs_n_s, prs_n_lam).count : 0)};
 }
 
+#ifndef GAUSS_LAYOUTS_ONLY
 // One unit of Gram work: a 128 x 128 tile pair times a run of consecutive K segments.  The kernel
 // streams the whole run without draining its load pipeline and flushes the accumulators into one
 // partial slab per segment.  Self-contained (64 bytes, fetched with scalar loads): no pointer
@@ -518,4 +523,5 @@ void launch_synth(uint8_t* d_out, int n_snp, long long ld, const int* d_pop_off,
                   int n_samples, const float* d_thr, const float* d_rho, uint64_t seed,
                   hipStream_t s);
 
+#endif
 }  // namespace gauss

@@ -10,6 +10,7 @@
 #pragma GCC visibility push(default)
 #include "../../include/gauss_hip.h"
 #pragma GCC visibility pop
+#include "gauss_deliver.h"      // RiderOuts, Riders and the delivery of a window's result sections (no HIP; behind the ABI header, for its visibility)
 
 #include <algorithm>
 #include <atomic>
@@ -235,31 +236,6 @@ struct DevBuf {
     hipError_t alloc(gauss_ctx* c, size_t bytes) { return ctx_malloc_retry(c, &p, bytes ? bytes : 1); }
     template <typename T> T* as() const { return (T*)p; }
 };
-// Where a window's riders put their results (out_loo_* / out_slct_* / out_z_more of gauss_window_desc); every pointer is optional
-struct RiderOuts {
-    double *loo_z = nullptr, *loo_info = nullptr, *loo_t = nullptr;
-    int32_t *slct_n = nullptr, *slct_idx = nullptr;
-    double *slct_zin = nullptr, *slct_joint = nullptr, *slct_zc = nullptr, *slct_var = nullptr;
-    double *cond_z = nullptr, *cond_var = nullptr;      // the imputed SNPs conditioned on the selection (gauss_window_desc.out_cond_*)
-    double *cs_pip = nullptr, *cs_set_pip = nullptr, *cs_mass = nullptr, *cs_lse = nullptr;      // credible sets (gauss_window_desc.out_cs_*)
-    int32_t *cs_set = nullptr, *cs_size = nullptr;
-    double *susie_pip = nullptr, *susie_set_pip = nullptr, *susie_V = nullptr, *susie_lse = nullptr, *susie_mass = nullptr;      // the multi-causal fit
-    double *susie_purity = nullptr, *susie_alpha = nullptr, *susie_mu = nullptr, *susie_sweeps = nullptr;                        // (gauss_window_desc.out_susie_*)
-    int32_t *susie_set = nullptr, *susie_size = nullptr, *susie_kept = nullptr;
-    double* susie_lbf = nullptr;
-    // the further traits of the same fit (gauss_window_desc.out_coloc_more_*, a leading [k]) and the pairs (out_coloc_*)
-    double *more_pip = nullptr, *more_set_pip = nullptr, *more_V = nullptr, *more_lse = nullptr, *more_mass = nullptr, *more_purity = nullptr;
-    double *more_alpha = nullptr, *more_mu = nullptr, *more_lbf = nullptr, *more_sweeps = nullptr;
-    int32_t *more_set = nullptr, *more_size = nullptr, *more_kept = nullptr, *more_status = nullptr;
-    double *coloc_pp = nullptr, *coloc_hit_pp = nullptr;
-    int32_t *coloc_hit = nullptr, *coloc_n = nullptr;
-    double *xs_V = nullptr, *xs_purity = nullptr, *xs_mu = nullptr;      // the joint fit across studies, on a group's leader (gauss_window_desc.out_xs_*)
-    int32_t* xs_n = nullptr;
-    double *prs_beta = nullptr, *prs_delta = nullptr, *prs_br = nullptr, *prs_bg = nullptr, *prs_kkt = nullptr;      // polygenic score weights
-    int32_t *prs_nnz = nullptr, *prs_sweeps = nullptr;                                                               // (gauss_window_desc.out_prs_*)
-    double* z_more = nullptr;
-    double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
-};
 // Host-side plan of one problem
 struct Plan {
     Prob p;                                  // device descriptor (pointers filled at layout time)
@@ -289,34 +265,8 @@ struct Plan {
     double* out_b21 = nullptr;
     double* out_r = nullptr;
     int32_t* out_num_eig = nullptr;
-    // What rides on an imputation window's solve (the sections of the result block: res_layout, gauss_internal.h).  A derived
-    // descriptor clears it with one assignment.
-    struct Riders {
-        bool loo = false;                    // leave-one-out values of the measured SNPs (k_loo.hip)
-        int slct_K = 0;                      // signal selection (k_slct.hip); 0: not asked
-        std::vector<int> slct_forced;
-        bool cond = false;                   // the imputed SNPs conditioned on the selection (k_cond.hip); needs slct_K
-        bool cs = false;                     // credible sets of the selected signals (k_cs.hip); needs slct_K
-        int susie_L = 0;                     // multi-causal fine-mapping (k_susie.hip): effects; 0: not asked
-        bool susie_am = false;               // ... and its result section holds alpha and mu (out_susie_alpha / out_susie_mu ask)
-        int susie_k = 0;                     // ... further traits fitted beside z1 (gauss_window_desc.coloc_traits_more)
-        bool susie_lbf = false, coloc = false;      // ... the lbf rows are asked; the colocalisation of the traits' pairs is (k_coloc.hip)
-        int xs_group = 0;                    // joint fit across studies (k_xsusie.hip): the group's id; 0: the window is in no group
-        int xs_K = 0, xs_pos = 0, xs_lead = 0;      // ... the group's windows, this one's place among them (0: the leader), the leader's index in the job
-        bool xs_mu = false;                  // ... the leader's section holds every study's mu (out_xs_mu asks)
-        std::vector<int> xs_from_lead, xs_to_lead;  // ... Prob::xs_from_lead / xs_to_lead; empty: the same index
-        int prs_n_s = 0, prs_n_lam = 0;      // polygenic score weights (k_prs.hip): the grid; 0: not asked
-        int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
-        std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
-        bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
-        int miss_n = 0;                      // set mask bits
-        std::vector<int> miss_tab;           // Prob::miss_tab (MissTab, gauss_internal.h); empty: no mask
-        RiderOuts out;
-        bool needs_fused() const { return loo || traits_T > 0 || susie_L > 0; }      // it reads the rows of L^-1 that only the fused solve forms
-    } rd;
-    // (a peer of a group keeps its fit's state in the workspace and returns none of it: the joint fit's sections are the leader's)
-    bool xs_peer() const { return rd.xs_group != 0 && rd.xs_pos > 0; }
-    ResLayout layout() const { return res_layout(p.n_rhs, p.M, p.U, rd.loo, rd.traits_T, rd.slct_K, rd.miss, rd.miss_n, rd.cond, rd.cs, xs_peer() ? 0 : rd.susie_L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc, rd.xs_group && rd.xs_pos == 0 ? rd.xs_K : 0, rd.xs_mu, rd.prs_n_s, rd.prs_n_lam); }
+    Riders rd;                               // what rides on an imputation window's solve (gauss_deliver.h)
+    ResLayout layout() const { return rd.layout(p.n_rhs, p.M, p.U); }
     size_t res_count() const { return layout().count; }      // doubles of this window in the result block
     double* out_ld_user = nullptr;           // ld_only / gene outputs
     int U_user = 0;                          // geno_u rows as passed by the caller (before codings)
@@ -329,12 +279,39 @@ struct Plan {
 // candidates) and M + U, the most effects, sweeps and 64-row blocks of X
 struct FitDims {
     int M = 0, U = 0, T = 0, L = 0, sweeps = 0, nblk = 0;
-    void grow(const Prob& p, const Plan::Riders& rd)
+    void grow(const Prob& p, const Riders& rd)
     {
         M = std::max(M, p.M); T = std::max(T, p.M + p.U);
         L = std::max(L, rd.susie_L); sweeps = std::max(sweeps, p.susie_max_sweeps);
         if (!p.susie_measured_only) { U = std::max(U, p.U); nblk = std::max(nblk, p.nblk); }
     }
+};
+
+// What the tail of a solve launches over (queue_tail, gauss_run.cpp): the riders' maps with their counts and largest dimensions, and
+// the closing product's.  job_build fills the job's; the clamp path makes one for its single window.
+struct TailMaps {
+    int2* d_gemmmap = nullptr;  int n_gemm = 0;            // (window, rhs panel of gemm_ut << 8 | k block of 128), longest first
+    int gemm_ut = 128;                                     // right-hand sides per tile of the product: 128, small jobs 64
+    int2* d_finmap = nullptr;   int n_fin = 0;             // (window, chunk of 256 right-hand sides)
+    int* d_slctmap = nullptr;   int n_slct = 0;            // signal selection: the windows that asked
+    int* d_condmap = nullptr;   int n_cond = 0;            // imputed SNPs conditioned on the selection: the windows that asked
+    int cond_max_U = 0;                                    // ... and the most unmeasured SNPs one of them has
+    int* d_csmap = nullptr;     int n_cs = 0;              // credible sets: the windows that asked
+    int* d_prsmap = nullptr;    int n_prs = 0;             // polygenic score weights: the windows that asked
+    int prs_max_s = 0, prs_max_M = 0;                      // ... the most chains and the most measured SNPs one of them has
+    int cs_max_T = 0;                                      // ... and the most candidates (M + U) one of them has
+    int* d_susiemap = nullptr;  int n_susie = 0;           // multi-causal fine-mapping: the windows that asked
+    FitDims susie_dims;                                    // ... their largest dimensions
+    int susie_max_k = 0;  bool susie_coloc = false;        // ... the most further traits in one fit; a window asks for the colocalisation
+    int* d_xsmap = nullptr;     int n_xs = 0;              // joint fit across studies: the windows that are members of a group (they are not in d_susiemap)
+    int* d_xsleadmap = nullptr; int n_xs_lead = 0;         // ... the leaders among them
+    FitDims xs_dims;                                       // ... as susie_dims, over the members
+    int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
+    int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
+    int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some
+    int2* d_misstmap = nullptr; int n_miss_t = 0;          // missing SNPs: (window, k-th trait that lacks some)
+    int2* d_missumap = nullptr; int n_miss_u = 0;          // missing SNPs: (window, strip of 64 unmeasured SNPs) of the windows that passed a mask
+    int2* d_loomap = nullptr;   int n_loo = 0;             // leave-one-out: (window, 64-column panel of X) of the windows that asked
 };
 
 struct ProfSlot { hipEvent_t a, b; int kernel; unsigned run; int launches = 1; };      // run: gauss_job::run_seq of the run that recorded it;
@@ -379,28 +356,7 @@ struct gauss_job {
     bool chain_aside = false;                              // the factorisation chain runs beside the Gram launch of B21's items (job_run)
     int2* d_panelmap = nullptr; int n_panels = 0;          // fused path: (window, panel of [I | z1])
     int2* d_dpanelmap = nullptr; int n_dpanels = 0;        // stand-alone solve: (window, panel of right-hand sides)
-    int2* d_gemmmap = nullptr;  int n_gemm = 0;            // (window, rhs panel of gemm_ut << 8 | k block of 128), longest first
-    int gemm_ut = 128;                                     // right-hand sides per tile of the product: 128, small jobs 64
-    int2* d_finmap = nullptr;   int n_fin = 0;             // (window, chunk of 256 right-hand sides)
-    int* d_slctmap = nullptr;   int n_slct = 0;            // signal selection: the windows that asked
-    int* d_condmap = nullptr;   int n_cond = 0;            // imputed SNPs conditioned on the selection: the windows that asked
-    int cond_max_U = 0;                                    // ... and the most unmeasured SNPs one of them has
-    int* d_csmap = nullptr;     int n_cs = 0;              // credible sets: the windows that asked
-    int* d_prsmap = nullptr;    int n_prs = 0;             // polygenic score weights: the windows that asked
-    int prs_max_s = 0, prs_max_M = 0;                      // ... the most chains and the most measured SNPs one of them has
-    int cs_max_T = 0;                                      // ... and the most candidates (M + U) one of them has
-    int* d_susiemap = nullptr;  int n_susie = 0;           // multi-causal fine-mapping: the windows that asked
-    FitDims susie_dims;                                    // ... their largest dimensions
-    int susie_max_k = 0;  bool susie_coloc = false;        // ... the most further traits in one fit; a window asks for the colocalisation
-    int* d_xsmap = nullptr;     int n_xs = 0;              // joint fit across studies: the windows that are members of a group (they are not in d_susiemap)
-    int* d_xsleadmap = nullptr; int n_xs_lead = 0;         // ... the leaders among them
-    FitDims xs_dims;                                       // ... as susie_dims, over the members
-    int2* d_traitsmap = nullptr;  int n_traits = 0;        // further traits: (window, 64-row block of X) of the windows that asked
-    int2* d_traitsumap = nullptr; int n_traits_u = 0;      // further traits: (window, strip of 64 unmeasured SNPs) of the windows that asked
-    int2* d_missmap = nullptr;  int n_miss_blk = 0;        // missing SNPs: (window, 64-row block of X) of the windows whose traits lack some
-    int2* d_misstmap = nullptr; int n_miss_t = 0;          // missing SNPs: (window, k-th trait that lacks some)
-    int2* d_missumap = nullptr; int n_miss_u = 0;          // missing SNPs: (window, strip of 64 unmeasured SNPs) of the windows that passed a mask
-    int2* d_loomap = nullptr;   int n_loo = 0;             // leave-one-out: (window, 64-column panel of X) of the windows that asked
+    TailMaps tail;                                         // what the tail of a solve launches over (queue_tail)
     bool needs_fused() const                               // some window rides on the rows of L^-1
     { return std::any_of(plans.begin(), plans.end(), [](const Plan& pl) { return pl.rd.needs_fused(); }); }
     int max_nblk = 0;

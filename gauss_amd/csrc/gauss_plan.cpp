@@ -456,8 +456,8 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
     if (w.z1) pl.z1.assign(w.z1, w.z1 + w.M);
     pl.h_geno_m = w.geno_m; pl.h_geno_u = w.geno_u; pl.user_ld = w.ld;
     pl.out_b11 = w.out_b11; pl.out_b21 = w.out_b21;
-    Plan::Riders& rd = pl.rd;
-    rd = Plan::Riders();
+    Riders& rd = pl.rd;
+    rd = Riders();
     rd.out = w.out;
     rd.loo = loo;
     rd.slct_K = w.slct_max;
@@ -544,7 +544,7 @@ static int plan_xs_groups(const std::vector<WinSpec>& specs, std::vector<Plan>& 
         for (int k = 0; k < K; k++) {
             const int i = mem[(size_t)k];
             const WinSpec& w = specs[(size_t)i];
-            Plan::Riders& rd = plans[(size_t)i].rd;
+            Riders& rd = plans[(size_t)i].rd;
             Prob& p = plans[(size_t)i].p;
             const char* differs = w.susie_L != a.susie_L ? "susie_L" : w.susie_coverage != a.susie_coverage ? "susie_coverage" :
                 w.susie_prior_var != a.susie_prior_var ? "susie_prior_var" : w.susie_tol != a.susie_tol ? "susie_tol" :
@@ -774,7 +774,7 @@ int JobBuild::share_measured()
     q.M = (int)gl.size(); q.U = 0; q.U_raw = 1; q.n_rhs = 0;
     q.Mp = (int)rup((size_t)q.M, TILE); q.Up = 0; q.Sp = q.Mp; q.nT = q.Mp / TILE;
     q.Mld = 0; q.nblk = 0; q.npanel = 0; q.npi = 0; q.kind = 0; q.ld_only = 0; q.n_head = q.n_predm = 0;
-    g.U_user = 0; g.h_geno_u = nullptr; g.rd = Plan::Riders(); clear_riders(q);
+    g.U_user = 0; g.h_geno_u = nullptr; g.rd = Riders(); clear_riders(q);
     // job-wide B11 pairs: the tile pairs some window lies in
     g.pair_ti.clear(); g.pair_tj.clear(); g.pair_lut.assign((size_t)q.nT * q.nT, -1);
     for (int i = 0; i < job->n; i++)
@@ -867,7 +867,7 @@ int JobBuild::work_lists()
             const Prob& p = job->plans[i].p;
             if (p.npanel > 0) t128 += (size_t)(p.Up128 / 128) * ((p.Mld + 127) / 128);
         }
-        job->gemm_ut = t128 < (size_t)GEMM_SMALL_TILES ? 64 : 128;
+        job->tail.gemm_ut = t128 < (size_t)GEMM_SMALL_TILES ? 64 : 128;
     }
     job->win_tiles.assign((size_t)job->n, std::vector<int2>());
     if (shm()) {
@@ -922,21 +922,21 @@ int JobBuild::work_lists()
             }
         for (int pn = 0; pn < p.npi; pn++) panelmap.push_back(make_int2(i, pn));
         for (int pn = 0; pn < p.npanel; pn++) dpanelmap.push_back(make_int2(i, pn));
-        const Plan::Riders& rd = job->plans[i].rd;
+        const Riders& rd = job->plans[i].rd;
         if (rd.loo)
             for (int pn = 0; pn < (p.M + NR - 1) / NR; pn++) loomap.push_back(make_int2(i, pn));      // the panels that hold columns of X
         if (rd.slct_K) slctmap.push_back(i);
-        if (rd.cond) { condmap.push_back(i); job->cond_max_U = std::max(job->cond_max_U, p.U); }
-        if (rd.cs) { csmap.push_back(i); job->cs_max_T = std::max(job->cs_max_T, p.M + p.U); }
-        if (rd.prs_n_s) { prsmap.push_back(i); job->prs_max_s = std::max(job->prs_max_s, rd.prs_n_s); job->prs_max_M = std::max(job->prs_max_M, p.M); }
+        if (rd.cond) { condmap.push_back(i); job->tail.cond_max_U = std::max(job->tail.cond_max_U, p.U); }
+        if (rd.cs) { csmap.push_back(i); job->tail.cs_max_T = std::max(job->tail.cs_max_T, p.M + p.U); }
+        if (rd.prs_n_s) { prsmap.push_back(i); job->tail.prs_max_s = std::max(job->tail.prs_max_s, rd.prs_n_s); job->tail.prs_max_M = std::max(job->tail.prs_max_M, p.M); }
         if (rd.susie_L && rd.xs_group) {       // a member of a group of the joint fit across studies: launches and map of its own
             xsmap.push_back(i);
             if (rd.xs_pos == 0) xsleadmap.push_back(i);
-            job->xs_dims.grow(p, rd);
+            job->tail.xs_dims.grow(p, rd);
         } else if (rd.susie_L) {
             susiemap.push_back(i);
-            job->susie_dims.grow(p, rd);
-            job->susie_max_k = std::max(job->susie_max_k, rd.susie_k); job->susie_coloc = job->susie_coloc || rd.coloc;
+            job->tail.susie_dims.grow(p, rd);
+            job->tail.susie_max_k = std::max(job->tail.susie_max_k, rd.susie_k); job->tail.susie_coloc = job->tail.susie_coloc || rd.coloc;
         }
         if (rd.traits_T) {
             for (int b = 0; b < p.nblk; b++) traitsmap.push_back(make_int2(i, b));
@@ -949,7 +949,7 @@ int JobBuild::work_lists()
         }
         if (p.npanel > 0) {
             job->max_nblk = std::max(job->max_nblk, p.nblk); job->max_npanel = std::max(job->max_npanel, p.npi);
-            for (int up = 0; up < p.Up128 / job->gemm_ut; up++)
+            for (int up = 0; up < p.Up128 / job->tail.gemm_ut; up++)
                 for (int kb = 0; kb < (p.Mld + 127) / 128; kb++) gemmmap.push_back(make_int2(i, (up << 8) | kb));
             for (int c = 0; c < (p.n_rhs + 255) / 256; c++) finmap.push_back(make_int2(i, c));
         }
@@ -1172,16 +1172,16 @@ int JobBuild::place_lists()
     // the product's tiles with the longest K loop (highest k block) first
     std::stable_sort(gemmmap.begin(), gemmmap.end(), [](const int2& x, const int2& y) { return (x.y & 255) > (y.y & 255); });
     tab(job->d_panelmap, job->n_panels, panelmap); tab(job->d_dpanelmap, job->n_dpanels, dpanelmap);
-    tab(job->d_gemmmap, job->n_gemm, gemmmap); tab(job->d_finmap, job->n_fin, finmap);
-    tab(job->d_loomap, job->n_loo, loomap);
+    tab(job->tail.d_gemmmap, job->tail.n_gemm, gemmmap); tab(job->tail.d_finmap, job->tail.n_fin, finmap);
+    tab(job->tail.d_loomap, job->tail.n_loo, loomap);
     const bool if_any = true;                              // (a job in which nobody asks takes nothing)
-    tab(job->d_slctmap, job->n_slct, slctmap, if_any); tab(job->d_condmap, job->n_cond, condmap, if_any);
-    tab(job->d_csmap, job->n_cs, csmap, if_any); tab(job->d_prsmap, job->n_prs, prsmap, if_any);
-    tab(job->d_susiemap, job->n_susie, susiemap, if_any);
-    tab(job->d_xsmap, job->n_xs, xsmap, if_any); tab(job->d_xsleadmap, job->n_xs_lead, xsleadmap, if_any);
-    tab(job->d_traitsmap, job->n_traits, traitsmap, if_any); tab(job->d_traitsumap, job->n_traits_u, traitsumap, if_any);
-    tab(job->d_missmap, job->n_miss_blk, missmap, if_any); tab(job->d_misstmap, job->n_miss_t, misstmap, if_any);
-    tab(job->d_missumap, job->n_miss_u, missumap, if_any);
+    tab(job->tail.d_slctmap, job->tail.n_slct, slctmap, if_any); tab(job->tail.d_condmap, job->tail.n_cond, condmap, if_any);
+    tab(job->tail.d_csmap, job->tail.n_cs, csmap, if_any); tab(job->tail.d_prsmap, job->tail.n_prs, prsmap, if_any);
+    tab(job->tail.d_susiemap, job->tail.n_susie, susiemap, if_any);
+    tab(job->tail.d_xsmap, job->tail.n_xs, xsmap, if_any); tab(job->tail.d_xsleadmap, job->tail.n_xs_lead, xsleadmap, if_any);
+    tab(job->tail.d_traitsmap, job->tail.n_traits, traitsmap, if_any); tab(job->tail.d_traitsumap, job->tail.n_traits_u, traitsumap, if_any);
+    tab(job->tail.d_missmap, job->tail.n_miss_blk, missmap, if_any); tab(job->tail.d_misstmap, job->tail.n_miss_t, misstmap, if_any);
+    tab(job->tail.d_missumap, job->tail.n_miss_u, missumap, if_any);
     o_probs = tab_block(job->d_probs, sizeof(Prob) * (size_t)n_prob());
     o_exports = tab_block(job->d_exports, sizeof(ExportD) * std::max<size_t>(job->exports.size(), 1));
     job->h_tab.resize(ta.off);
@@ -1193,7 +1193,7 @@ int JobBuild::place_lists()
 void JobBuild::layout_window(Plan& pl)
 {
     Prob& p = pl.p;
-    const Plan::Riders& rd = pl.rd;
+    const Riders& rd = pl.rd;
     if (streamed()) {
         p.ld_raw = stream->ldraw; p.raw_m = stream->d_m; p.raw_u = stream->d_u;      // the rows land in the context's landing buffer
     } else if (!on_device) {
@@ -1384,7 +1384,7 @@ int JobBuild::bind()
         p.out_slct = pl.rd.slct_K ? out + lay.slct : nullptr;
         p.out_cond = pl.rd.cond ? out + lay.cond : nullptr;
         p.out_cs = pl.rd.cs ? out + lay.cs : nullptr;
-        p.out_susie = pl.rd.susie_L && !pl.xs_peer() ? out + lay.susie : nullptr;
+        p.out_susie = pl.rd.susie_L && !pl.rd.xs_peer() ? out + lay.susie : nullptr;
         p.out_susie_more = pl.rd.susie_L && lay.xs > lay.susie_more ? out + lay.susie_more : nullptr;
         p.out_xs = lay.prs > lay.xs ? out + lay.xs : nullptr;
         p.out_prs = pl.rd.prs_n_s ? out + lay.prs : nullptr;

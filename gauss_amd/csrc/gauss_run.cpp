@@ -21,25 +21,40 @@ static void prof_end(gauss_job* job, hipStream_t st)
     if (!job->prof) return;
     hipEventRecord(job->slots.back().b, st);
 }
-// Collects the stage timers of the runs before `run_end` (default: all).  gauss_job_fetch passes the run it has just
-// fetched: with two runs in flight the later run's events are still pending, and waiting for them here would make
-// the fetch of run k block until run k + 1 has finished -- the host's share of a step would no longer overlap GPU work.
-void prof_collect(gauss_job* job, unsigned run_end)
+// Retires the slots of the runs that `gone` names: their times go to the stage timers (collect), or nowhere
+template <class Gone> static void prof_retire(gauss_job* job, bool collect, Gone gone)
 {
     std::vector<ProfSlot> keep;
     for (ProfSlot& s : job->slots) {
-        if (run_end != ~0u && (int)(s.run - run_end) >= 0) { keep.push_back(s); continue; }
-        hipEventSynchronize(s.b);
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s.a, s.b);
-        job->prof_ms[s.kernel] += ms;
-        job->prof_n[s.kernel] += s.launches;
+        if (!gone(s.run)) { keep.push_back(s); continue; }
+        if (collect) {
+            hipEventSynchronize(s.b);
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, s.a, s.b);
+            job->prof_ms[s.kernel] += ms;
+            job->prof_n[s.kernel] += s.launches;
+        }
         hipEventDestroy(s.a);
         hipEventDestroy(s.b);
     }
     job->slots.swap(keep);
 }
+// Collects the stage timers of the runs before `run_end` (default: all).  gauss_job_fetch passes the run it has just
+// fetched: with two runs in flight the later run's events are still pending, and waiting for them here would make
+// the fetch of run k block until run k + 1 has finished -- the host's share of a step would no longer overlap GPU work.
+void prof_collect(gauss_job* job, unsigned run_end) { prof_retire(job, true, [&](unsigned run) { return run_end == ~0u || (int)(run - run_end) < 0; }); }
 
+static size_t status_bytes(const gauss_job* job) { return sizeof(int) * (4 * (size_t)job->n + 4); }      // d_status: [n][4] + 4 job-wide ints
+// B11 of window i, or its shifted copy, has no Cholesky factor (status words 0 and 1 of the run being fetched): MakePosDef would have modified it
+static bool needs_repair(const gauss_job* job, int i) { return job->h_status[4 * i + 0] || job->h_status[4 * i + 1]; }
+// B11 as the epilogue left it, kept for every solved window that exports it (a repair rewrites A[0])
+static int copy_b11_out(gauss_job* job, hipStream_t st)
+{
+    for (const Plan& pl : job->plans)
+        if (pl.out_b11 && pl.p.npanel > 0)
+            HIPCHK(hipMemcpyAsync(pl.d_b11_copy, pl.p.A, sizeof(double) * pl.p.Mld * pl.p.Mld, hipMemcpyDeviceToDevice, st));
+    return GAUSS_OK;
+}
 
 // ------------------------------------------------------------------------------------------
 // the result mirrors travel with the run, so that gauss_job_fetch waits for THIS job only (an event), not for
@@ -76,7 +91,7 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
     // matrix exports first, chunk by chunk: gauss_job_fetch starts copying chunk c out while the later chunks still cross the link
     { const int rc = queue_exports(job, 0, job->exp_chunks.size(), st); if (rc) return rc; }
     if (job->n_results) launch_h2d_copy(job->h_res2[par], job->d_results, rup(sizeof(double) * job->n_results, 16), st);
-    launch_h2d_copy(job->h_st2[par], job->d_status, sizeof(int) * (4 * job->n + 4), st);
+    launch_h2d_copy(job->h_st2[par], job->d_status, status_bytes(job), st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(job->done2[par], st));
     if (job_trace) fprintf(stderr, "[job] run: result copies queued in %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
@@ -84,14 +99,15 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
     return GAUSS_OK;
 }
 
-// The tail of a fused solve, in the one order its inputs allow:
+// The tail of a solve, in the one order its inputs allow:
 //     loo -> selection -> traits weights -> miss solve -> fine-mapping weights -> closing step -> traits impute -> miss apply
 //         -> conditional -> credible sets -> multi-causal fit (-> colocalisation of its traits, inside launch_susie)
 //         -> joint fit across the studies of a group (k_xsusie.hip: its members' W beside the ungrouped windows', its fit last)
 //         -> polygenic score weights
 //   - loo and the traits weights read the complete [X | y] = L^-1 [I | z1] in V: they follow solve_last (and the join with the
 //     chain queue) and precede a closing step that takes V as scratch (the clamp path's stand-alone solve);
-//   - the selection reads B11 in A[0], which the factorisation leaves untouched, and z1;
+//   - the selection reads B11 in A[0], which the factorisation leaves untouched (k_solve.hip: factor_init_kernel and factor_update_kernel
+//     work in W0 = A + 4 Mld^2 and the shifted A[1] and write L into A[2], A[3] and Linv; the riding rows write V), and z1;
 //   - traits impute divides B21 G by the info the closing step's finish kernel has just written;
 //   - traits that lack some measured SNPs (k_traits_miss.hip): the solve reads [X | y] like the traits weights, and their G; the
 //     apply step takes the raw means traits impute has left for such traits, and the info;
@@ -104,27 +120,28 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 //     traits the scores in traits_Z and the imputed Z-scores traits impute has left (such a window has no mask: miss apply leaves them).
 //   - the polygenic score weights (k_prs.hip): B11 in A[0] and z1, like the selection; a chain is some hundred dependent sweeps that
 //     nothing else reads, so it is queued last: everything the caller may be waiting for is in front of it.
-// The closing step of a run is the product B21 [X | y] with its finish kernel.  A launch for which no window asked is skipped by its
-// launcher.  The clamp path (job_clamp_window) keeps the same order with its single-window map and the stand-alone solve as its
-// closing step; its selection runs in front of the re-factorisation.
-static void queue_tail(gauss_job* job, hipStream_t st)
+// The closing step is the product B21 [X | y] with its finish kernel, or -- d_solvemap: (window, panel of right-hand sides) -- the
+// stand-alone solve, which takes V as its scratch and only reads B21.  A launch for which no window asked is skipped by its launcher
+// (each returns at n <= 0).  Every tail is queued here: a run's over the job's maps; under GAUSS_FUSED_SOLVE=0 with the stand-alone
+// solve (nothing in such a job rides on the rows of L^-1: selection -> solve -> conditional -> credible sets -> score weights are
+// left); the clamp path's (job_clamp_window) over the maps of its single window, behind its re-factorisation.
+static void queue_tail(const Prob* probs, const TailMaps& m, const int2* d_solvemap, int n_solve, hipStream_t st)
 {
-    launch_loo(job->d_probs, job->d_loomap, job->n_loo, st);
-    launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);
-    launch_traits_weights(job->d_probs, job->d_traitsmap, job->n_traits, st);
-    launch_traits_miss_solve(job->d_probs, job->d_missmap, job->n_miss_blk, job->d_misstmap, job->n_miss_t, st);
-    launch_susie_w(job->d_probs, job->d_susiemap, job->n_susie, job->susie_dims.nblk, job->susie_dims.U, st);
-    launch_susie_w(job->d_probs, job->d_xsmap, job->n_xs, job->xs_dims.nblk, job->xs_dims.U, st);
-    launch_impute_gemm(job->d_probs, job->d_gemmmap, job->n_gemm, job->gemm_ut, job->d_finmap, job->n_fin, st);
-    launch_traits_impute(job->d_probs, job->d_traitsumap, job->n_traits_u, st);
-    launch_traits_miss_apply(job->d_probs, job->d_missumap, job->n_miss_u, st);
-    launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);
-    launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
-    launch_susie(job->d_probs, job->d_susiemap, job->n_susie, job->susie_dims.M, job->susie_dims.T, job->susie_dims.L, job->susie_dims.sweeps,
-                 job->susie_max_k, job->susie_coloc, st);
-    launch_xsusie(job->d_probs, job->d_xsmap, job->n_xs, job->d_xsleadmap, job->n_xs_lead, job->xs_dims.M, job->xs_dims.T, job->xs_dims.L,
-                  job->xs_dims.sweeps, st);
-    launch_prs(job->d_probs, job->d_prsmap, job->n_prs, job->prs_max_s, job->prs_max_M, st);
+    launch_loo(probs, m.d_loomap, m.n_loo, st);
+    launch_slct(probs, m.d_slctmap, m.n_slct, st);
+    launch_traits_weights(probs, m.d_traitsmap, m.n_traits, st);
+    launch_traits_miss_solve(probs, m.d_missmap, m.n_miss_blk, m.d_misstmap, m.n_miss_t, st);
+    launch_susie_w(probs, m.d_susiemap, m.n_susie, m.susie_dims.nblk, m.susie_dims.U, st);
+    launch_susie_w(probs, m.d_xsmap, m.n_xs, m.xs_dims.nblk, m.xs_dims.U, st);
+    if (d_solvemap) launch_solve(probs, d_solvemap, n_solve, st);
+    else launch_impute_gemm(probs, m.d_gemmmap, m.n_gemm, m.gemm_ut, m.d_finmap, m.n_fin, st);
+    launch_traits_impute(probs, m.d_traitsumap, m.n_traits_u, st);
+    launch_traits_miss_apply(probs, m.d_missumap, m.n_miss_u, st);
+    launch_cond(probs, m.d_condmap, m.n_cond, m.cond_max_U, st);
+    launch_cs(probs, m.d_csmap, m.n_cs, m.cs_max_T, st);
+    launch_susie(probs, m.d_susiemap, m.n_susie, m.susie_dims.M, m.susie_dims.T, m.susie_dims.L, m.susie_dims.sweeps, m.susie_max_k, m.susie_coloc, st);
+    launch_xsusie(probs, m.d_xsmap, m.n_xs, m.d_xsleadmap, m.n_xs_lead, m.xs_dims.M, m.xs_dims.T, m.xs_dims.L, m.xs_dims.sweeps, st);
+    launch_prs(probs, m.d_prsmap, m.n_prs, m.prs_max_s, m.prs_max_M, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -145,7 +162,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
     if (job->merged && solve) { (merged ? ctx->n_runs_merged : ctx->n_runs_demoted)++; (merged ? job->n_merged : job->n_demoted)++; }
     const auto t_run0 = std::chrono::steady_clock::now();
     HIPCHK(hipEventRecord(job->begin, st));
-    HIPCHK(hipMemsetAsync(job->d_status, 0, sizeof(int) * (4 * job->n + 4), st));
+    HIPCHK(hipMemsetAsync(job->d_status, 0, status_bytes(job), st));
     if (trace_on("job")) fprintf(stderr, "[job] run (%s): begin mark + status zeroing queued in %.2f ms\n", merged ? "merged" : (job->chain_aside ? "two launches" : "one queue"),
                                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_run0).count());
     // fused tail: the factorisation chain needs B11 only and the closing product is the first reader of B21, so B21's
@@ -198,11 +215,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         prof_begin(job, 2, ch);
         launch_epilogue_b11_lite(job->d_probs, job->d_tilemap, job->n_tiles_b11, job->gram_i8, ch);
         prof_end(job, ch);
-        for (int i = 0; i < job->n; i++) {
-            Plan& pl = job->plans[i];
-            if (pl.out_b11 && pl.p.npanel > 0)
-                HIPCHK(hipMemcpyAsync(pl.d_b11_copy, pl.p.A, sizeof(double) * pl.p.Mld * pl.p.Mld, hipMemcpyDeviceToDevice, ch));
-        }
+        { const int rc = copy_b11_out(job, ch); if (rc) return rc; }
         prof_begin(job, 3, ch);
         for (int s = 0; s < job->max_nblk; s++)
             launch_factor_step_lite(job->d_probs, job->n, s, job->max_nblk, job->max_npanel, job->solve_split, ch);
@@ -233,7 +246,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         }
         HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
         prof_begin(job, 4, st);
-        queue_tail(job, st);               // the chain has been joined: [X | y] is complete
+        queue_tail(job->d_probs, job->tail, nullptr, 0, st);               // the chain has been joined: [X | y] is complete
         prof_end(job, st);
         return job_queue_results(job, par, st);
     }
@@ -252,11 +265,7 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         if (job->plans[i].p.n_gene) launch_gene_epilogue(job->d_probs, i, job->plans[i].p.n_gene, st);
     prof_end(job, st);
     if (solve && job->n_panels > 0) {
-        for (int i = 0; i < job->n; i++) {
-            Plan& pl = job->plans[i];
-            if (pl.out_b11 && pl.p.npanel > 0)
-                HIPCHK(hipMemcpyAsync(pl.d_b11_copy, pl.p.A, sizeof(double) * pl.p.Mld * pl.p.Mld, hipMemcpyDeviceToDevice, st));
-        }
+        { const int rc = copy_b11_out(job, st); if (rc) return rc; }
         // fused (default): the rows of [X | y] = L^-1 [I | z1] ride in the factorisation's update launches and the
         // closing product forms z / info (k_solve.hip); the stage timers read "factor" = factorisation + riding rows,
         // "solve" = closing row + product + finish
@@ -269,14 +278,8 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         if (fused) {
             launch_solve_last(job->d_probs, job->d_panelmap, job->n_panels, job->max_nblk, job->solve_split, st);
             if (side) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
-            queue_tail(job, st);
-        } else {
-            launch_slct(job->d_probs, job->d_slctmap, job->n_slct, st);      // B11 and z1 are all it reads: it needs no fused solve
-            launch_solve(job->d_probs, job->d_dpanelmap, job->n_dpanels, st);
-            launch_cond(job->d_probs, job->d_condmap, job->n_cond, job->cond_max_U, st);      // z, info, the selection and B21: no fused solve either
-            launch_cs(job->d_probs, job->d_csmap, job->n_cs, job->cs_max_T, st);
-            launch_prs(job->d_probs, job->d_prsmap, job->n_prs, job->prs_max_s, job->prs_max_M, st);      // B11 and z1 again
         }
+        queue_tail(job->d_probs, job->tail, fused ? nullptr : job->d_dpanelmap, job->n_dpanels, st);
         prof_end(job, st);
     }
     return job_queue_results(job, par, st);
@@ -403,13 +406,11 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t ax = ctx->aux;
     hipStream_t ch = ctx->chain;
-    Plan& pl = job->plans[0];
-    const Prob& p = pl.p;
     const size_t ng = job->sgroups.size();
     const gauss_job::RunEvents& ev = job->rev[job->run_seq & 1u];
     job->queue_touched = true;
     HIPCHK(hipEventRecord(job->begin, st));
-    HIPCHK(hipMemsetAsync(job->d_status, 0, sizeof(int) * (4 * job->n + 4), st));
+    HIPCHK(hipMemsetAsync(job->d_status, 0, status_bytes(job), st));
     // what job_build queued on the main stream (zeroing, tables) comes before anything on the other queues
     HIPCHK(hipEventRecord(ev.pack, st));
     HIPCHK(hipStreamWaitEvent(ax, ev.pack, 0));
@@ -442,8 +443,7 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
                 HIPCHK(hipStreamWaitEvent(ch, ev.gram, 0));
             }
             launch_epilogue(job->d_probs, job->d_tilemap, job->n_tiles_b11, job->max_pop, job->gram_i8, ch);
-            if (pl.out_b11)
-                HIPCHK(hipMemcpyAsync(pl.d_b11_copy, p.A, sizeof(double) * p.Mld * p.Mld, hipMemcpyDeviceToDevice, ch));
+            { const int rc = copy_b11_out(job, ch); if (rc) return rc; }
             for (int s = 0; s < job->max_nblk; s++)
                 launch_factor_step(job->d_probs, job->n, s, job->max_nblk, job->max_npanel, job->solve_split, job->own_panel, ch);
             launch_solve_last(job->d_probs, job->d_panelmap, job->n_panels, job->max_nblk, job->solve_split, ch);
@@ -452,7 +452,7 @@ int job_run_streamed(gauss_job* job, StreamSetup& su)
     }
     launch_epilogue(job->d_probs, job->d_tilemap + job->n_tiles_b11, job->n_tiles - job->n_tiles_b11, job->max_pop, job->gram_i8, st);
     if (ch != st) HIPCHK(hipStreamWaitEvent(st, ev.side, 0));
-    queue_tail(job, st);
+    queue_tail(job->d_probs, job->tail, nullptr, 0, st);
     const int rc = job_queue_results(job, (int)(job->run_seq & 1u), st);
     if (rc) return rc;
     job->run_seq++;
@@ -468,10 +468,9 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     hipStream_t st = job->ctx->stream;
     Plan& pl = job->plans[i];
     Prob& p = pl.p;
-    // Re-run the epilogue for this problem only to restore A[0] (the factorisation overwrote it)
-    std::vector<int2> tm;
-    tm = job->win_tiles[(size_t)i];                   // this window's epilogue tiles (job-wide B11 pairs included)
-    DevBuf d_tm, d_work, d_pm, d_lm;
+    // Re-run the epilogue for this problem only: B11 afresh in A[0], its shifted twin and the working copy
+    const std::vector<int2>& tm = job->win_tiles[(size_t)i];      // this window's epilogue tiles (job-wide B11 pairs included)
+    DevBuf d_tm, d_work, d_wm;
     HIPCHK(d_tm.alloc(job->ctx, sizeof(int2) * tm.size()));
     HIPCHK(hipMemcpyAsync(d_tm.p, tm.data(), sizeof(int2) * tm.size(), hipMemcpyHostToDevice, st));
     launch_epilogue(job->d_probs, d_tm.as<int2>(), (int)tm.size(), job->max_pop, job->gram_i8, st);
@@ -481,44 +480,36 @@ static int job_clamp_window(gauss_job* job, int i, int* status_bits)
     HIPCHK(hipMemsetAsync(p.status, 0, sizeof(int) * 4, st));
     launch_jacobi_clamp(job->d_probs, i, p, d_work.as<double>(), true, st);
     HIPCHK(hipGetLastError());
-    // refactor (both matrices are factored again; only matrix 0 is used) and solve this window
-    std::vector<int2> pm;
-    for (int pn = 0; pn < p.npanel; pn++) pm.push_back(make_int2(i, pn));
-    HIPCHK(d_pm.alloc(job->ctx, sizeof(int2) * pm.size()));
-    HIPCHK(hipMemcpyAsync(d_pm.p, pm.data(), sizeof(int2) * pm.size(), hipMemcpyHostToDevice, st));
+    // (a window that rides on the rows of L^-1: those of the REPAIRED matrix ride in this factorisation as they do in a run's)
+    const Riders& rd = pl.rd;
+    const bool traits = rd.traits_T > 0, ride = rd.loo || traits;
+    const int n_us = (p.U + NB - 1) / NB;                    // strips of unmeasured SNPs of the further traits' product
+    // (window, 0 .. n): read as right-hand side panels by the solve, as panels of [I | z1] by solve_last / loo, as blocks of X, as strips
+    // of unmeasured SNPs and as the traits that lack some SNPs by the traits kernels; its first int is the one-entry window list of the
+    // launchers that take one.  (`wm` is pageable and lives until the function's last synchronise.)
+    std::vector<int2> wm;
+    for (int k = 0; k < std::max(std::max(p.npanel, ride ? p.npi : 0), std::max(traits || rd.miss ? n_us : 0, rd.miss ? p.miss_nm : 0)); k++) wm.push_back(make_int2(i, k));
+    HIPCHK(d_wm.alloc(job->ctx, sizeof(int2) * wm.size()));
+    HIPCHK(hipMemcpyAsync(d_wm.p, wm.data(), sizeof(int2) * wm.size(), hipMemcpyHostToDevice, st));
     if (pl.out_b11) HIPCHK(hipMemcpyAsync(pl.d_b11_copy, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(p.A + 4 * n * n, p.A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));   // W0 = clamped B11
-    if (pl.rd.slct_K) launch_slct(job->d_probs + i, nullptr, 1, st);      // signal selection again, on the REPAIRED B11 in A[0]
-    if (pl.rd.prs_n_s) launch_prs(job->d_probs + i, nullptr, 1, p.prs_n_s, p.M, st);      // ... and the score weights, on the same matrix
-    // a window that rides on the rows of L^-1: the rows of [X | y] = L^-1 [I | z1] of the REPAIRED matrix ride in this factorisation
-    // as they do in a run's (same L either way), and the stand-alone solve below is this tail's closing step (queue_tail): it
-    // takes V as its scratch, only reads B21 and leaves the info the further traits are divided by
-    // (the multi-causal fit does not ride here: a repaired window is not fitted, job_fetch fills its section)
-    const bool loo = pl.rd.loo, traits = pl.rd.traits_T > 0, miss = pl.rd.miss, ride = loo || traits;
-    for (int s = 0; s < p.nblk; s++) {
-        // launch over all problems would redo the others; use a single-problem launch instead
+    // refactor (both matrices are factored again; only matrix 0 is used): a launch over all problems would redo the others
+    for (int s = 0; s < p.nblk; s++)
         launch_factor_step(job->d_probs + i, 1, s, p.nblk, ride ? p.npi : 0, ride ? job->solve_split : 0, 0, st);
-    }
-    const int n_us = (p.U + NB - 1) / NB;                    // strips of unmeasured SNPs of the further traits' product
-    if (ride) {
-        // (window, 0 .. n): read as panels by solve_last / loo, as blocks of X, as strips of unmeasured SNPs and as the traits that
-        // lack some SNPs by the traits kernels
-        std::vector<int2> lm;
-        for (int pn = 0; pn < std::max(std::max(p.npi, traits ? n_us : 0), miss ? p.miss_nm : 0); pn++) lm.push_back(make_int2(i, pn));
-        const int n_x = (p.M + NR - 1) / NR;                 // the panels that hold columns of X come first
-        HIPCHK(d_lm.alloc(job->ctx, sizeof(int2) * lm.size()));
-        HIPCHK(hipMemcpyAsync(d_lm.p, lm.data(), sizeof(int2) * lm.size(), hipMemcpyHostToDevice, st));
-        launch_solve_last(job->d_probs, d_lm.as<int2>(), p.npi, p.nblk, job->solve_split, st);
-        if (loo) launch_loo(job->d_probs, d_lm.as<int2>(), n_x, st);
-        if (traits) launch_traits_weights(job->d_probs, d_lm.as<int2>(), p.nblk, st);
-        if (miss) launch_traits_miss_solve(job->d_probs, d_lm.as<int2>(), p.miss_nm ? p.nblk : 0, d_lm.as<int2>(), p.miss_nm, st);
-        HIPCHK(hipStreamSynchronize(st));                    // (`lm` is pageable: the copy has read it)
-    }
-    launch_solve(job->d_probs, d_pm.as<int2>(), (int)pm.size(), st);
-    if (traits) launch_traits_impute(job->d_probs, d_lm.as<int2>(), n_us, st);
-    if (miss) launch_traits_miss_apply(job->d_probs, d_lm.as<int2>(), n_us, st);
-    if (pl.rd.cond) launch_cond(job->d_probs + i, nullptr, 1, p.U, st);      // W, indices and zin are those of the repaired B11 (the selection above)
-    if (pl.rd.cs) launch_cs(job->d_probs + i, nullptr, 1, p.M + p.U, st);
+    if (ride) launch_solve_last(job->d_probs, d_wm.as<int2>(), p.npi, p.nblk, job->solve_split, st);
+    // the tail of this window alone, on the REPAIRED B11 in A[0].  The multi-causal fit does not ride here: a repaired window is not
+    // fitted (deliver_window fills its sections)
+    TailMaps m;
+    int2* const w2 = d_wm.as<int2>();
+    int* const w1 = d_wm.as<int>();                      // {i}
+    if (rd.loo) { m.d_loomap = w2; m.n_loo = (p.M + NR - 1) / NR; }      // the panels that hold columns of X come first
+    if (rd.slct_K) { m.d_slctmap = w1; m.n_slct = 1; }
+    if (traits) { m.d_traitsmap = m.d_traitsumap = w2; m.n_traits = p.nblk; m.n_traits_u = n_us; }
+    if (rd.miss) { m.d_missmap = m.d_misstmap = m.d_missumap = w2; m.n_miss_blk = p.miss_nm ? p.nblk : 0; m.n_miss_t = p.miss_nm; m.n_miss_u = n_us; }
+    if (rd.cond) { m.d_condmap = w1; m.n_cond = 1; m.cond_max_U = p.U; }
+    if (rd.cs) { m.d_csmap = w1; m.n_cs = 1; m.cs_max_T = p.M + p.U; }
+    if (rd.prs_n_s) { m.d_prsmap = w1; m.n_prs = 1; m.prs_max_s = p.prs_n_s; m.prs_max_M = p.M; }
+    queue_tail(job->d_probs, m, w2, p.npanel, st);
     HIPCHK(hipGetLastError());
     int h_status[4];
     HIPCHK(hipMemcpyAsync(h_status, p.status, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
@@ -605,298 +596,144 @@ static int export_fetch_all(gauss_job* job)
     return GAUSS_OK;
 }
 
-int job_fetch(gauss_job* job)
+// The run of parity `par` has finished.  The exported matrices leave the pinned mirror chunk by chunk while the rest of the run is still
+// on the queue (with a later run of the job in flight that run rewrites the mirror with the same values: it is left to finish first, as
+// for any device read)
+static int fetch_wait(gauss_job* job, int par)
 {
-    if (!job->ran || job->fetch_seq == job->run_seq) return fail(GAUSS_E_INVALID, "gauss_job_fetch: no run of this job is waiting to be fetched");
-    hipStream_t st = job->ctx->stream;
-    HIPCHK(hipSetDevice(job->ctx->device));
-    const int par = (int)(job->fetch_seq & 1u);
-    job->h_results = job->h_res2[par];
-    job->h_status = job->h_st2[par];
-    // the exported matrices leave the pinned mirror chunk by chunk while the rest of the run is still on the queue (with a later run
-    // of the job in flight that run rewrites the mirror with the same values: it is left to finish first, as for any device read)
-    const bool exporting = !job->exports.empty();
-    if (exporting) {
+    if (!job->exports.empty()) {
         if (job->run_seq - job->fetch_seq > 1u) HIPCHK(hipEventSynchronize(job->done));
         const int rc = export_fetch_all(job);
         if (rc) return rc;
     }
     HIPCHK(hipEventSynchronize(job->done2[par]));
-    bool rerun = false;
-    if (job->h_status[4 * job->n] != 0) {
-        rerun = true;
-        // A waiting kernel of the merged launch gave up (k_gram.hip: wait_count_kernel raises this job-wide flag after its
-        // bound): what the chain computed from then on is not valid.  The run is queued once more in the two-launch form,
-        // which has no kernel that waits for another queue, into the same mirrors -- the job's inputs do not change between
-        // runs -- after everything of this job has left the queues (a later run of the job that is in flight included: its
-        // results sit in the other parity's mirrors and stay valid).
-        gauss_ctx* ctx = job->ctx;
-        ctx->n_merged_giveups++;
-        job->n_giveups++;
-        for (hipStream_t q : {ctx->stream, ctx->chain, ctx->side}) if (q) HIPCHK(hipStreamSynchronize(q));
-        // the stage timers of the run being replaced are void (its chain ran on nothing): dropped, so that the re-run's timers do not
-        // add to them; and the run number the timers are recorded under goes back to the newest queued run afterwards (a later run of
-        // the job may be in flight: its slots keep their number)
-        {
-            std::vector<ProfSlot> keep;
-            for (ProfSlot& ps : job->slots) {
-                if (ps.run == job->fetch_seq) { hipEventDestroy(ps.a); hipEventDestroy(ps.b); }
-                else keep.push_back(ps);
-            }
-            job->slots.swap(keep);
-        }
-        const unsigned prof_run_was = job->prof_run;
-        job->prof_run = job->fetch_seq;
-        int rc = job_queue_run(job, job->ran_solve, par, false);
-        job->prof_run = prof_run_was;
-        if (!rc && hipEventSynchronize(job->done2[par]) != hipSuccess) rc = fail(GAUSS_E_DEVICE, "waiting for the re-run failed");
-        if (rc || job->h_status[4 * job->n] != 0) {
-            ctx->n_rerun_failed++;
-            job->n_rerun_failed++;
-            job->fetch_seq++;
-            const std::string why = rc ? g_err : std::string("its failure flag is set again");
-            return fail(GAUSS_E_DEVICE, "the chain queue gave up waiting for B11's tile pairs of this run (merged Gram launch) and the re-run in the two-launch form failed: %s", why.c_str());
-        }
-        if (job->run_seq - job->fetch_seq > 1u) job->done = job->done2[par ^ 1];      // (the later run's event stays the newest: it was synchronised above)
+    return GAUSS_OK;
+}
+
+// A waiting kernel of the merged launch gave up (k_gram.hip: wait_count_kernel raises the job-wide flag after its
+// bound): what the chain computed from then on is not valid.  The run is queued once more in the two-launch form,
+// which has no kernel that waits for another queue, into the same mirrors -- the job's inputs do not change between
+// runs -- after everything of this job has left the queues (a later run of the job that is in flight included: its
+// results sit in the other parity's mirrors and stay valid).
+static int fetch_rerun(gauss_job* job, int par)
+{
+    gauss_ctx* ctx = job->ctx;
+    ctx->n_merged_giveups++;
+    job->n_giveups++;
+    for (hipStream_t q : {ctx->stream, ctx->chain, ctx->side}) if (q) HIPCHK(hipStreamSynchronize(q));
+    // the stage timers of the run being replaced are void (its chain ran on nothing): dropped, so that the re-run's timers do not
+    // add to them; and the run number the timers are recorded under goes back to the newest queued run afterwards (a later run of
+    // the job may be in flight: its slots keep their number)
+    prof_retire(job, false, [&](unsigned run) { return run == job->fetch_seq; });
+    const unsigned prof_run_was = job->prof_run;
+    job->prof_run = job->fetch_seq;
+    int rc = job_queue_run(job, job->ran_solve, par, false);
+    job->prof_run = prof_run_was;
+    if (!rc && hipEventSynchronize(job->done2[par]) != hipSuccess) rc = fail(GAUSS_E_DEVICE, "waiting for the re-run failed");
+    if (rc || job->h_status[4 * job->n] != 0) {
+        ctx->n_rerun_failed++;
+        job->n_rerun_failed++;
+        job->fetch_seq++;
+        const std::string why = rc ? g_err : std::string("its failure flag is set again");
+        return fail(GAUSS_E_DEVICE, "the chain queue gave up waiting for B11's tile pairs of this run (merged Gram launch) and the re-run in the two-launch form failed: %s", why.c_str());
     }
-    if (rerun && exporting) { const int rc = export_fetch_all(job); if (rc) return rc; }      // what the failed merged run exported is void
-    // With a later run of the job already queued, anything that reads the job's DEVICE buffers (matrix exports, the
-    // clamp path, the eigenvalue count) first lets that run finish: the job's inputs do not change between runs, so
-    // what it leaves on the device is what the fetched run left.
-    if (job->run_seq - job->fetch_seq > 1u) {
-        bool device_reads = false;
-        for (int i = 0; i < job->n && !device_reads; i++) {
-            const Plan& pl = job->plans[i];
-            device_reads = pl.out_b11 || pl.out_b21 || (pl.out_ld_user && pl.out_ld_count) ||
-                           job->h_status[4 * i + 0] || job->h_status[4 * i + 1];
-        }
-        if (device_reads) HIPCHK(hipEventSynchronize(job->done));
+    if (job->run_seq - job->fetch_seq > 1u) job->done = job->done2[par ^ 1];      // (the later run's event stays the newest: it was synchronised above)
+    return job->exports.empty() ? GAUSS_OK : export_fetch_all(job);      // what the failed merged run exported is void
+}
+
+// With a later run of the job already queued, anything that reads the job's DEVICE buffers (matrix exports, the
+// clamp path, the eigenvalue count) first lets that run finish: the job's inputs do not change between runs, so
+// what it leaves on the device is what the fetched run left.
+static int fetch_barrier(gauss_job* job)
+{
+    if (job->run_seq - job->fetch_seq <= 1u) return GAUSS_OK;
+    bool device_reads = false;
+    for (int i = 0; i < job->n && !device_reads; i++) {
+        const Plan& pl = job->plans[i];
+        device_reads = pl.out_b11 || pl.out_b21 || (pl.out_ld_user && pl.out_ld_count) || needs_repair(job, i);
     }
-    job->fetch_seq++;
-    for (int i = 0; i < job->n; i++) {
-        Plan& pl = job->plans[i];
-        const Prob& p = pl.p;
-        int bits = 0;
-        if (p.kind == GAUSS_WIN_LD) {
-            // raw LD export: B11 sits unfactored in A[0] (diagonal 1 + lambda), B21 in its buffer
-            if (pl.out_b11 && !exporting)
-                { int rc2 = fetch_matrix(pl.out_b11, p.A, p.M, p.M, p.Mld); if (rc2) return rc2; }
-            if (pl.out_b21 && p.U > 0 && !exporting)
-                { int rc2 = fetch_matrix(pl.out_b21, p.B21, p.U, p.M, p.Mld); if (rc2) return rc2; }
-            if (pl.out_status) *pl.out_status = 0;
-            continue;
-        }
-        if (p.kind == GAUSS_WIN_QCAT) {
-            // QCAT never repairs B11 (MakePosDef is commented out, qcat.cpp:206); CountPC only counts
-            int num_eig = p.M;
-            if (job->h_status[4 * i + 0]) bits = GAUSS_ST_NONFINITE;          // B11 has no Cholesky factor
-            // (no factor: B11 is indefinite -- weights summing far above 1 -- or not finite.  The reference still counts: CountPC runs
-            // before the factorisation, qcat.cpp:203, and an eigenvalue below the cutoff, negative ones included, is not counted)
-            if (job->h_status[4 * i + 0] || job->h_status[4 * i + 1]) { int rc = job_count_small_eigs(job, i, &num_eig); if (rc) return rc; }
-            if (bits & GAUSS_ST_NONFINITE)
-                for (int u = 0; u < 2 * p.n_rhs; u++) job->h_results[pl.res_off + u] = NAN;
-            if (pl.out_r) memcpy(pl.out_r, job->h_results + pl.res_off, sizeof(double) * p.n_rhs);
-            if (pl.out_num_eig) *pl.out_num_eig = num_eig;
-            if (pl.out_status) *pl.out_status = bits;
-            if (pl.out_b11 && !exporting)
-                { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }
-            if (pl.out_b21 && p.U > 0 && !exporting)
-                { int rc2 = fetch_matrix(pl.out_b21, p.B21, p.U, p.M, p.Mld); if (rc2) return rc2; }
-            continue;
-        }
+    if (device_reads) HIPCHK(hipEventSynchronize(job->done));
+    return GAUSS_OK;
+}
+
+// B11 (from `d_b11`) and B21 of a window that asked for them and whose job has no export mirror
+static int fetch_mats(const gauss_job* job, const Plan& pl, const double* d_b11, bool b11_again = false)
+{
+    const Prob& p = pl.p;
+    const bool exporting = !job->exports.empty();
+    int rc = GAUSS_OK;
+    if (pl.out_b11 && (!exporting || b11_again)) rc = fetch_matrix(pl.out_b11, d_b11, p.M, p.M, p.Mld);
+    if (!rc && pl.out_b21 && p.U > 0 && !exporting) rc = fetch_matrix(pl.out_b21, p.B21, p.U, p.M, p.Mld);
+    return rc;
+}
+
+// raw LD export: B11 sits unfactored in A[0] (diagonal 1 + lambda), B21 in its buffer
+static int deliver_ld(gauss_job* job, int i) { return fetch_mats(job, job->plans[i], job->plans[i].p.A); }
+
+// QCAT never repairs B11 (MakePosDef is commented out, qcat.cpp:206); CountPC only counts
+static int deliver_qcat(gauss_job* job, int i, int* bits)
+{
+    const Plan& pl = job->plans[i];
+    const Prob& p = pl.p;
+    int num_eig = p.M;
+    *bits = job->h_status[4 * i + 0] ? GAUSS_ST_NONFINITE : 0;          // B11 has no Cholesky factor
+    // (no factor: B11 is indefinite -- weights summing far above 1 -- or not finite.  The reference still counts: CountPC runs
+    // before the factorisation, qcat.cpp:203, and an eigenvalue below the cutoff, negative ones included, is not counted)
+    if (needs_repair(job, i)) { int rc = job_count_small_eigs(job, i, &num_eig); if (rc) return rc; }
+    if (*bits & GAUSS_ST_NONFINITE)
+        for (int u = 0; u < 2 * p.n_rhs; u++) job->h_results[pl.res_off + u] = NAN;
+    if (pl.out_r) memcpy(pl.out_r, job->h_results + pl.res_off, sizeof(double) * p.n_rhs);
+    if (pl.out_num_eig) *pl.out_num_eig = num_eig;
+    return fetch_mats(job, pl, pl.d_b11_copy);
+}
+
+// An imputation window: repaired if its B11 needs it, then its sections of the result block (gauss_deliver.h), then its matrices
+static int deliver_impute(gauss_job* job, int i, int* bits)
+{
+    const Plan& pl = job->plans[i];
+    const Prob& p = pl.p;
+    if (p.npanel > 0) {
         // a group of the joint fit across studies (k_xsusie.hip) in which ANY window is repaired is not fitted: what the status words
         // say of every member is known before the first of them is repaired
-        bool xs_nofit = false;
+        const bool clamped = needs_repair(job, i);
+        bool repaired = clamped;
         if (pl.rd.xs_group)
-            for (int s = 0; s < pl.rd.xs_K; s++) {
-                const int m = p.xs_peer[s];
-                xs_nofit = xs_nofit || (job->plans[m].p.npanel > 0 && (job->h_status[4 * m + 0] || job->h_status[4 * m + 1]));
-            }
-        bool clamped = false;
-        if (p.npanel > 0 && (job->h_status[4 * i + 0] || job->h_status[4 * i + 1])) {
-            int rc = job_clamp_window(job, i, &bits);
-            if (rc) return rc;
-            clamped = true;                    // B11's exported copy predates the clamp: fetched again below
-        }
-        if (p.npanel > 0) {
-            // the window's sections of the result block (res_layout, gauss_internal.h)
-            const Plan::Riders& rd = pl.rd;
-            const ResLayout lay = pl.layout();
-            const SlctLayout sl = slct_layout(p.M, rd.slct_K);
-            double* const res = job->h_results + pl.res_off;
-            double* const sel = res + lay.slct;
-            if (bits & GAUSS_ST_NONFINITE) {
-                // the reference's eigen-solver / LU propagate non-finite values to every output
-                for (size_t u = 0; u < lay.count; u++) res[u] = NAN;
-                if (rd.slct_K) {                   // nothing selected: n = 0, no skipped SNP, indices -1
-                    sel[sl.n] = sel[sl.skipped] = 0.0;
-                    for (int a = 0; a < rd.slct_K; a++) sel[sl.idx + a] = -1.0;
-                }
-                if (rd.prs_n_s) {                  // no fit: nnz 0, no sweep, no flag
-                    const PrsLayout ql = prs_layout(p.M, rd.prs_n_s, rd.prs_n_lam);
-                    for (int c = 0; c < rd.prs_n_s * rd.prs_n_lam; c++) {
-                        double* const cell = res + lay.prs + ql.cell + (size_t)c * PRS_CELL;
-                        cell[PRS_NNZ] = cell[PRS_SWEEPS] = cell[PRS_NOCONV] = 0.0;
-                    }
-                }
-                if (rd.cs) {                       // no sets: size 0, set -1
-                    const CsLayout cl = cs_layout(p.M + p.U, rd.slct_K);
-                    for (int a = 0; a < rd.slct_K; a++) res[lay.cs + cl.size + a] = 0.0;
-                    for (int c = 0; c < p.M + p.U; c++) res[lay.cs + cl.set + c] = -1.0;
-                }
-            }
-            if (pl.xs_peer() && (clamped || xs_nofit) && !(bits & GAUSS_ST_NONFINITE)) bits |= GAUSS_ST_SUSIE_NOFIT;
-            if (rd.susie_L && !pl.xs_peer() && (clamped || xs_nofit || (bits & GAUSS_ST_NONFINITE))) {
-                // not fitted: NaN, size 0, kept 0, set -1, no sweep.  A repaired B11 (MakePosDef) is no ground for the fit, and the
-                // clamp path's stand-alone solve forms no rows of the inverse
-                const SusieLayout ql = susie_layout(p.M + p.U, rd.susie_L, rd.susie_am);
-                double* const sq = res + lay.susie;
-                for (size_t u = 0; u < ql.count; u++) sq[u] = NAN;
-                for (int l = 0; l < rd.susie_L; l++) sq[ql.size + l] = sq[ql.kept + l] = 0.0;
-                for (int c = 0; c < p.M + p.U; c++) sq[ql.set + c] = -1.0;
-                sq[ql.fit] = sq[ql.fit + 2] = 0.0;
-                // ... and so is every further trait of the fit; every pair: NaN, hit -1, n 0
-                const SusieMoreLayout ml = susie_more_layout(p.M + p.U, rd.susie_L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc);
-                double* const mq = res + lay.susie_more;
-                for (size_t u = 0; u < ml.count; u++) mq[u] = NAN;
-                for (int t = 0; t < rd.susie_k; t++) memcpy(mq + ml.trait + (size_t)t * ml.one, sq, sizeof(double) * ql.count);
-                for (size_t u = ml.hit; u < ml.hit_pp; u++) mq[u] = -1.0;
-                for (size_t u = ml.n; u < ml.count; u++) mq[u] = 0.0;
-                if (lay.prs > lay.xs) {          // a group's leader: every study's V, purity and mu NaN, no joint candidate
-                    const XsLayout xl = xs_layout(rd.xs_K, rd.susie_L, p.M + p.U, rd.xs_mu);
-                    for (size_t u = 0; u < xl.count; u++) res[lay.xs + u] = NAN;
-                    res[lay.xs + xl.n] = 0.0;
-                }
-                if (!(bits & GAUSS_ST_NONFINITE)) bits |= GAUSS_ST_SUSIE_NOFIT;
-            }
-            auto copy_out = [](double* dst, const double* src, size_t n) { if (dst) memcpy(dst, src, sizeof(double) * n); };
-            copy_out(pl.out_z, res + lay.z, p.U);
-            copy_out(pl.out_info, res + lay.info, p.U);
-            if (rd.loo) {                          // leave-one-out values of the measured SNPs (k_loo.hip)
-                copy_out(rd.out.loo_z, res + lay.loo, p.M);
-                copy_out(rd.out.loo_info, res + lay.loo + p.M, p.M);
-                copy_out(rd.out.loo_t, res + lay.loo + 2 * (size_t)p.M, p.M);
-            }
-            if (rd.traits_T) copy_out(rd.out.z_more, res + lay.traits, (size_t)rd.traits_T * p.U);      // the further traits (k_traits.hip)
-            if (rd.miss) {                         // ... that lack some measured SNPs (k_traits_miss.hip)
-                copy_out(rd.out.info_more, res + lay.traits_info, (size_t)rd.traits_T * p.U);
-                copy_out(rd.out.z_miss, res + lay.traits_miss, (size_t)rd.miss_n);
-                copy_out(rd.out.info_miss, res + lay.traits_miss + rd.miss_n, (size_t)rd.miss_n);
-            }
-            if (rd.slct_K) {                       // signal selection (k_slct.hip)
-                const int K = rd.slct_K;
-                if (rd.out.slct_n) *rd.out.slct_n = (int32_t)sel[sl.n];
-                if (sel[sl.skipped] != 0.0) bits |= GAUSS_ST_SLCT_SKIPPED;
-                if (rd.out.slct_idx) for (int a = 0; a < K; a++) rd.out.slct_idx[a] = (int32_t)sel[sl.idx + a];
-                copy_out(rd.out.slct_zin, sel + sl.zin, K);
-                copy_out(rd.out.slct_joint, sel + sl.joint, K);
-                copy_out(rd.out.slct_zc, sel + sl.zc, p.M);
-                copy_out(rd.out.slct_var, sel + sl.var, p.M);
-            }
-            if (rd.cond) {                         // the imputed SNPs conditioned on the selection (k_cond.hip)
-                copy_out(rd.out.cond_z, res + lay.cond, p.U);
-                copy_out(rd.out.cond_var, res + lay.cond + p.U, p.U);
-            }
-            if (rd.cs) {                           // credible sets of the selected signals (k_cs.hip)
-                const int K = rd.slct_K, T = p.M + p.U;
-                const CsLayout cl = cs_layout(T, K);
-                const double* const cs = res + lay.cs;
-                if (rd.out.cs_size) for (int a = 0; a < K; a++) rd.out.cs_size[a] = (int32_t)cs[cl.size + a];
-                copy_out(rd.out.cs_mass, cs + cl.mass, K);
-                copy_out(rd.out.cs_lse, cs + cl.lse, K);
-                copy_out(rd.out.cs_pip, cs + cl.pip, T);
-                if (rd.out.cs_set) for (int c = 0; c < T; c++) rd.out.cs_set[c] = (int32_t)cs[cl.set + c];
-                copy_out(rd.out.cs_set_pip, cs + cl.set_pip, T);
-            }
-            if (rd.prs_n_s) {                      // polygenic score weights (k_prs.hip)
-                const int nc = rd.prs_n_s * rd.prs_n_lam;
-                const PrsLayout ql = prs_layout(p.M, rd.prs_n_s, rd.prs_n_lam);
-                const double* const pq = res + lay.prs;
-                for (int c = 0; c < nc; c++) {
-                    const double* const cell = pq + ql.cell + (size_t)c * PRS_CELL;
-                    if (cell[PRS_NOCONV] != 0.0) bits |= GAUSS_ST_PRS_NOCONV;
-                    if (rd.out.prs_nnz) rd.out.prs_nnz[c] = (int32_t)cell[PRS_NNZ];
-                    if (rd.out.prs_sweeps) rd.out.prs_sweeps[c] = (int32_t)cell[PRS_SWEEPS];
-                    if (rd.out.prs_delta) rd.out.prs_delta[c] = cell[PRS_DELTA];
-                    if (rd.out.prs_br) rd.out.prs_br[c] = cell[PRS_BR];
-                    if (rd.out.prs_bg) rd.out.prs_bg[c] = cell[PRS_BG];
-                    if (rd.out.prs_kkt) rd.out.prs_kkt[c] = cell[PRS_KKT];
-                }
-                copy_out(rd.out.prs_beta, pq + ql.beta, (size_t)nc * p.M);
-            }
-            if (rd.susie_L && !pl.xs_peer()) {     // the multi-causal fit (k_susie.hip); for a group's leader the joint fit (k_xsusie.hip)
-                const int L = rd.susie_L, T = p.M + p.U;
-                const SusieLayout ql = susie_layout(T, L, rd.susie_am);
-                const double* const sq = res + lay.susie;
-                if (sq[ql.fit + 2] != 0.0) bits |= GAUSS_ST_SUSIE_NOCONV;
-                copy_out(rd.out.susie_V, sq + ql.V, L);
-                copy_out(rd.out.susie_lse, sq + ql.lse, L);
-                copy_out(rd.out.susie_mass, sq + ql.mass, L);
-                copy_out(rd.out.susie_purity, sq + ql.purity, L);
-                if (rd.out.susie_size) for (int l = 0; l < L; l++) rd.out.susie_size[l] = (int32_t)sq[ql.size + l];
-                if (rd.out.susie_kept) for (int l = 0; l < L; l++) rd.out.susie_kept[l] = (int32_t)sq[ql.kept + l];
-                copy_out(rd.out.susie_pip, sq + ql.pip, T);
-                if (rd.out.susie_set) for (int c = 0; c < T; c++) rd.out.susie_set[c] = (int32_t)sq[ql.set + c];
-                copy_out(rd.out.susie_set_pip, sq + ql.set_pip, T);
-                if (rd.susie_am) { copy_out(rd.out.susie_alpha, sq + ql.alpha, (size_t)L * T); copy_out(rd.out.susie_mu, sq + ql.mu, (size_t)L * T); }
-                copy_out(rd.out.susie_sweeps, sq + ql.fit, 2);
-                // the lbf rows, the further traits of the same fit and the pairs (susie_more_layout)
-                const SusieMoreLayout ml = susie_more_layout(T, L, rd.susie_am, rd.susie_lbf, rd.susie_k, rd.coloc);
-                const double* const mq = res + lay.susie_more;
-                const size_t lt = (size_t)L * T;
-                if (rd.susie_lbf) copy_out(rd.out.susie_lbf, mq + ml.lbf, lt);
-                for (int t = 0; t < rd.susie_k; t++) {
-                    const double* const tq = mq + ml.trait + (size_t)t * ml.one;
-                    const RiderOuts& o = rd.out;
-                    if (o.more_status)
-                        o.more_status[t] = (tq[ql.fit + 2] != 0.0 ? GAUSS_ST_SUSIE_NOCONV : 0) | (bits & (GAUSS_ST_SUSIE_NOFIT | GAUSS_ST_NONFINITE));
-                    if (o.more_V) copy_out(o.more_V + (size_t)t * L, tq + ql.V, L);
-                    if (o.more_lse) copy_out(o.more_lse + (size_t)t * L, tq + ql.lse, L);
-                    if (o.more_mass) copy_out(o.more_mass + (size_t)t * L, tq + ql.mass, L);
-                    if (o.more_purity) copy_out(o.more_purity + (size_t)t * L, tq + ql.purity, L);
-                    if (o.more_size) for (int l = 0; l < L; l++) o.more_size[(size_t)t * L + l] = (int32_t)tq[ql.size + l];
-                    if (o.more_kept) for (int l = 0; l < L; l++) o.more_kept[(size_t)t * L + l] = (int32_t)tq[ql.kept + l];
-                    if (o.more_pip) copy_out(o.more_pip + (size_t)t * T, tq + ql.pip, T);
-                    if (o.more_set) for (int c = 0; c < T; c++) o.more_set[(size_t)t * T + c] = (int32_t)tq[ql.set + c];
-                    if (o.more_set_pip) copy_out(o.more_set_pip + (size_t)t * T, tq + ql.set_pip, T);
-                    if (rd.susie_am && o.more_alpha) copy_out(o.more_alpha + t * lt, tq + ql.alpha, lt);
-                    if (rd.susie_am && o.more_mu) copy_out(o.more_mu + t * lt, tq + ql.mu, lt);
-                    if (rd.susie_lbf && o.more_lbf) copy_out(o.more_lbf + t * lt, tq + ml.tlbf, lt);
-                    if (o.more_sweeps) copy_out(o.more_sweeps + 2 * (size_t)t, tq + ql.fit, 2);
-                }
-                if (lay.prs > lay.xs) {          // a group's leader: what the joint fit holds per study (k_xsusie.hip)
-                    const XsLayout xl = xs_layout(rd.xs_K, L, T, rd.xs_mu);
-                    const double* const xq = res + lay.xs;
-                    copy_out(rd.out.xs_V, xq + xl.V, (size_t)rd.xs_K * L);
-                    copy_out(rd.out.xs_purity, xq + xl.purity, (size_t)rd.xs_K * L);
-                    if (rd.xs_mu) copy_out(rd.out.xs_mu, xq + xl.mu, (size_t)rd.xs_K * lt);
-                    if (rd.out.xs_n) *rd.out.xs_n = (int32_t)xq[xl.n];
-                }
-                if (rd.coloc) {
-                    const size_t np = (size_t)(rd.susie_k + 1) * rd.susie_k / 2, ll = (size_t)L * L;
-                    copy_out(rd.out.coloc_pp, mq + ml.pp, 5 * np * ll);
-                    if (rd.out.coloc_hit) for (size_t e = 0; e < np * ll; e++) rd.out.coloc_hit[e] = (int32_t)mq[ml.hit + e];
-                    copy_out(rd.out.coloc_hit_pp, mq + ml.hit_pp, np * ll);
-                    if (rd.out.coloc_n) for (size_t e = 0; e < np; e++) rd.out.coloc_n[e] = (int32_t)mq[ml.n + e];
-                }
-            }
-            if (pl.out_b11 && (!exporting || clamped))
-                { int rc2 = fetch_matrix(pl.out_b11, pl.d_b11_copy, p.M, p.M, p.Mld); if (rc2) return rc2; }
-            if (pl.out_b21 && p.U > 0 && !exporting)
-                { int rc2 = fetch_matrix(pl.out_b21, p.B21, p.U, p.M, p.Mld); if (rc2) return rc2; }
-        }
+            for (int s = 0; s < pl.rd.xs_K; s++) repaired = repaired || (job->plans[p.xs_peer[s]].p.npanel > 0 && needs_repair(job, p.xs_peer[s]));
+        if (clamped) { int rc = job_clamp_window(job, i, bits); if (rc) return rc; }
+        *bits = deliver_window(job->h_results + pl.res_off, p.M, p.U, pl.rd, pl.out_z, pl.out_info, *bits, repaired);
+        int rc = fetch_mats(job, pl, pl.d_b11_copy, clamped);      // (B11's exported copy predates the clamp: fetched again)
+        if (rc) return rc;
+    }
+    if (pl.out_ld_user && pl.out_ld_count)
+        HIPCHK(hipMemcpy(pl.out_ld_user, p.out_ld, sizeof(double) * pl.out_ld_count, hipMemcpyDeviceToHost));
+    return GAUSS_OK;
+}
+
+int job_fetch(gauss_job* job)
+{
+    if (!job->ran || job->fetch_seq == job->run_seq) return fail(GAUSS_E_INVALID, "gauss_job_fetch: no run of this job is waiting to be fetched");
+    HIPCHK(hipSetDevice(job->ctx->device));
+    const int par = (int)(job->fetch_seq & 1u);
+    job->h_results = job->h_res2[par];
+    job->h_status = job->h_st2[par];
+    int rc = fetch_wait(job, par);
+    if (!rc && job->h_status[4 * job->n] != 0) rc = fetch_rerun(job, par);
+    if (!rc) rc = fetch_barrier(job);
+    if (rc) return rc;
+    job->fetch_seq++;
+    for (int i = 0; i < job->n; i++) {
+        const Plan& pl = job->plans[i];
+        int bits = 0;
+        rc = pl.p.kind == GAUSS_WIN_LD ? deliver_ld(job, i) : pl.p.kind == GAUSS_WIN_QCAT ? deliver_qcat(job, i, &bits) : deliver_impute(job, i, &bits);
+        if (rc) return rc;
         if (pl.out_status) *pl.out_status = bits;
-        if (pl.out_ld_user && pl.out_ld_count)
-            HIPCHK(hipMemcpy(pl.out_ld_user, p.out_ld, sizeof(double) * pl.out_ld_count, hipMemcpyDeviceToHost));
     }
     if (job->prof) prof_collect(job, job->fetch_seq);      // the slots of the run just fetched (fetch_seq already counts it)
     if (job->fetch_seq == job->run_seq) job->queue_touched = false;      // every run has delivered: nothing of this job is left on a queue
     return GAUSS_OK;
 }
 
-// Everything a job holds on its context: waits for its queued runs, then gives the blocks back and destroys the events.
-// Called by job_free, and by gauss_hip_destroy for the jobs that outlive their context (the context is still whole then).
-void job_release(gauss_job* job)
+void job_release(gauss_job* job)      // (gauss_job.h)
 {
     gauss_ctx* ctx = job->ctx;
     if (!ctx) return;
@@ -912,8 +749,7 @@ void job_release(gauss_job* job)
         if (!job->sgroups.empty() && ctx->aux) (void)hipStreamSynchronize(ctx->aux);
         job->queue_touched = false;
     }
-    for (ProfSlot& s : job->slots) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
-    job->slots.clear();
+    prof_retire(job, false, [](unsigned) { return true; });
     ctx_dev_release(ctx, job->d_ws);
     ctx_dev_release(ctx, job->d_tab);
     ctx_pin_release(ctx, job->h_pin);
