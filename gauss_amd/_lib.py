@@ -34,6 +34,7 @@ SUSIE_TRAITS_MORE_MAX = 7  # GAUSS_SUSIE_TRAITS_MORE_MAX
 XS_MAX = 4               # GAUSS_XS_MAX
 ST_PRS_NOCONV = 64       # GAUSS_ST_PRS_NOCONV
 PRS_MAX_S, PRS_MAX_LAM, PRS_MAX_SWEEPS, PRS_MAX_M = 8, 32, 1000, 4096      # GAUSS_PRS_MAX_*
+LDS_MAX_ANNOT, LDS_CHUNK = 32, 64      # GAUSS_LDS_MAX_ANNOT, GAUSS_LDS_CHUNK
 CODE_ADDITIVE, CODE_DOMINANT, CODE_RECESSIVE = 1, 2, 4
 GRAM_F32 = 0
 GRAM_I8 = 1
@@ -52,7 +53,10 @@ class WindowDesc(C.Structure):
         ("prs_n_s", C.c_int), ("prs_n_lam", C.c_int), ("prs_s", _dp), ("prs_lam", _dp), ("prs_n", C.c_double), ("prs_tol", C.c_double),
         ("prs_max_sweeps", C.c_int), ("out_prs_beta", _dp), ("out_prs_nnz", _ip), ("out_prs_sweeps", _ip), ("out_prs_delta", _dp),
         ("out_prs_br", _dp), ("out_prs_bg", _dp), ("out_prs_kkt", _dp),
-        ("out_z", _dp), ("out_info", _dp), ("out_status", _ip), ("out_b11", _dp), ("out_b21", _dp),
+        ("out_z", _dp), ("out_info", _dp), ("out_status", _ip),
+        ("lds_on", C.c_int), ("lds_n_annot", C.c_int), ("lds_radius", C.c_int64), ("lds_bp_m", _ip), ("lds_bp_u", _ip), ("lds_n", C.c_double),
+        ("lds_annot", _dp), ("out_lds_raw", _dp), ("out_lds_l2", _dp), ("out_lds_mass", _dp),
+        ("out_b11", _dp), ("out_b21", _dp),
         ("xs_group", C.c_int), ("xs_from_lead", _ip), ("out_xs_V", _dp), ("out_xs_purity", _dp), ("out_xs_mu", _dp), ("out_xs_n", _ip),
         ("kind", C.c_int), ("n_head_measured", C.c_int), ("n_pred_measured", C.c_int), ("eig_cutoff", C.c_double),
         ("out_r", _dp), ("out_num_eig", _ip),

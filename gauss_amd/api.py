@@ -48,7 +48,7 @@ HOST_SYMBOLS = [
     "gauss_host_simulateLD", "gauss_host_simulate_draws",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
-    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_prs", "gauss_host_distmix_prs", "gauss_host_dist_xsusie", "gauss_host_distmix_xsusie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
+    "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_prs", "gauss_host_distmix_prs", "gauss_host_dist_ldscore", "gauss_host_distmix_ldscore", "gauss_host_dist_xsusie", "gauss_host_distmix_xsusie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
     "gauss_host_dist_traits", "gauss_host_distmix_traits", "gauss_host_dist_traits_miss", "gauss_host_distmix_traits_miss",
 ]
 
@@ -151,6 +151,8 @@ def load_host():
     prs_tail = [_dbl, C.POINTER(_dbl), C.c_int, C.POINTER(_dbl), C.c_int, _dbl, C.c_int, C.POINTER(_vp)]      # n, s, n_s, lam, n_lam, tol, max_sweeps, out
     h.gauss_host_dist_prs.argtypes = h.gauss_host_dist.argtypes[:-1] + prs_tail
     h.gauss_host_distmix_prs.argtypes = h.gauss_host_distmix.argtypes[:-1] + prs_tail
+    h.gauss_host_dist_ldscore.argtypes = h.gauss_host_dist.argtypes[:-1] + [_dbl, C.POINTER(_vp)]      # n, out
+    h.gauss_host_distmix_ldscore.argtypes = h.gauss_host_distmix.argtypes[:-1] + [_dbl, C.POINTER(_vp)]
     files_tail = [C.c_char_p, C.c_char_p, C.c_char_p, _dbl]                  # index, data, description, af1_cutoff
     h.gauss_host_dist_xsusie.argtypes = h.gauss_host_dist.argtypes[:5] + [_strs, _strs, C.c_int] + files_tail + susie_tail
     h.gauss_host_distmix_xsusie.argtypes = h.gauss_host_distmix.argtypes[:8] + [_strs, C.c_int] + files_tail + susie_tail
@@ -621,6 +623,40 @@ def distmix_prs(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, refere
     extra, keep = _prs_args(n, s, lam, tol, max_sweeps)
     return _prs_frame(*_window_call("gauss_host_distmix_prs", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
                       (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx, extra), per_allele)
+
+
+def _ldscore_frame(h, out):
+    named = _named(h, out)
+    df = _table(h, out)[0]                                 # (frees the table: nothing may fail between the two reads and this)
+    a = np.asarray(named["ldscore"], dtype=np.float64).reshape(-1)
+    df.attrs.update(n_eff=float(a[0]), M=int(a[1]), M_5_50=int(a[2]), radius=int(a[3]))
+    return df
+
+
+def dist_ldscore(chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file, reference_data_file,
+                 reference_pop_desc_file, af1_cutoff=None, n=None, ctx=None):
+    """LD scores of a dist() window (gauss_host_dist_ldscore): l2_raw = sum r^2 over the panel SNPs within wing_size bp of each SNP, on
+    the pooled LD of the selected populations, reduced on the GPU -- the matrices never come back.  The SNPs scored are those of
+    input_file (its z column is ignored) that the panel has inside [start_bp, end_bp]; the sum runs over EVERY panel SNP of the extended
+    window that passes af1_cutoff, the wings' study SNPs included.  One row per scored SNP: rsid chr bp a1 a2 af1ref l2 l2_raw n_band;
+    l2 = l2_raw (1 + 1 / (n - 2)) - n_band / (n - 2) is ldsc's bias-adjusted score, n (None: the selected populations' sample count)
+    the sample size in it.  frame.attrs: n_eff, M (panel SNPs of the window, scored ones included), M_5_50 (those with minor allele
+    frequency above 0.05), radius.  Limits: one window per call; a bp radius, no cM; no stratified scores from files
+    (hotpath.ld_window(ldscore=dict(annot=...)) has them)."""
+    return _ldscore_frame(*_window_call("gauss_host_dist_ldscore", (chr, start_bp, end_bp, wing_size), study_pop,
+                          (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                          (0.0 if n is None else float(n),)))
+
+
+def distmix_ldscore(chr, start_bp, end_bp, wing_size, pop_wgt_df, input_file, reference_index_file, reference_data_file,
+                    reference_pop_desc_file, af1_cutoff=None, n=None, ctx=None):
+    """LD scores of a distmix() window (gauss_host_distmix_ldscore) on the ancestry-weighted LD: the LD scores a mixed-ancestry cohort
+    has no file to download for.  Columns as dist_ldscore with af1mix.  n (None): Kish's effective size of the weighted panel,
+    (sum w_p)^2 / sum (w_p^2 / n_p) over the populations of non-zero weight, the weights as passed -- a convention of this project,
+    stated in frame.attrs["n_eff"], not a measurement."""
+    return _ldscore_frame(*_window_call("gauss_host_distmix_ldscore", (chr, start_bp, end_bp, wing_size), pop_wgt_df,
+                          (input_file, reference_index_file, reference_data_file, reference_pop_desc_file), af1_cutoff, ctx,
+                          (0.0 if n is None else float(n),)))
 
 
 def slct_chi2(p):

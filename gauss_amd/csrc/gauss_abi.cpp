@@ -1,6 +1,9 @@
 // libgauss_hip.so -- the C ABI of include/gauss_hip.h: jobs, the blocking window call, the LD entry points.
 #include "gauss_job.h"
 
+// the kernels' constants that include/gauss_hip.h states to the caller (gauss_internal.h does not see that header)
+static_assert(gauss::LDS_C == GAUSS_LDS_MAX_ANNOT && gauss::LDS_CHUNK == GAUSS_LDS_CHUNK, "LD scores: gauss_internal.h and include/gauss_hip.h disagree");
+
 // entry points that need the job's context
 #define JOB_ALIVE(job)                                                                                          \
     do {                                                                                                        \
@@ -50,6 +53,9 @@ static WinSpec spec_from_desc(const gauss_window_desc& d)
     w.prs_max_sweeps = d.prs_max_sweeps;
     w.out.prs_beta = d.out_prs_beta; w.out.prs_nnz = d.out_prs_nnz; w.out.prs_sweeps = d.out_prs_sweeps; w.out.prs_delta = d.out_prs_delta;
     w.out.prs_br = d.out_prs_br; w.out.prs_bg = d.out_prs_bg; w.out.prs_kkt = d.out_prs_kkt;
+    w.lds_on = d.lds_on; w.lds_n_annot = d.lds_n_annot; w.lds_radius = d.lds_radius; w.lds_bp_m = d.lds_bp_m; w.lds_bp_u = d.lds_bp_u;
+    w.lds_n = d.lds_n; w.lds_annot = d.lds_annot;
+    w.out.lds_raw = d.out_lds_raw; w.out.lds_l2 = d.out_lds_l2; w.out.lds_mass = d.out_lds_mass;
     w.out.xs_V = d.out_xs_V; w.out.xs_purity = d.out_xs_purity; w.out.xs_mu = d.out_xs_mu; w.out.xs_n = d.out_xs_n;
     return w;
 }

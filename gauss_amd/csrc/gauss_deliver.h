@@ -32,6 +32,7 @@ struct RiderOuts {
     int32_t* xs_n = nullptr;
     double *prs_beta = nullptr, *prs_delta = nullptr, *prs_br = nullptr, *prs_bg = nullptr, *prs_kkt = nullptr;      // polygenic score weights
     int32_t *prs_nnz = nullptr, *prs_sweeps = nullptr;                                                               // (gauss_window_desc.out_prs_*)
+    double *lds_raw = nullptr, *lds_l2 = nullptr, *lds_mass = nullptr;      // LD scores of an LD window (gauss_window_desc.out_lds_*)
     double* z_more = nullptr;
     double *info_more = nullptr, *z_miss = nullptr, *info_miss = nullptr;      // (with a mask: gauss_window_desc.miss_more)
 };
@@ -53,6 +54,10 @@ struct Riders {
     bool xs_mu = false;                  // ... the leader's section holds every study's mu (out_xs_mu asks)
     std::vector<int> xs_from_lead, xs_to_lead;  // ... Prob::xs_from_lead / xs_to_lead; empty: the same index
     int prs_n_s = 0, prs_n_lam = 0;      // polygenic score weights (k_prs.hip): the grid; 0: not asked
+    bool lds = false;                    // LD scores of an LD window's measured SNPs (k_ldscore.hip)
+    int lds_C = 0;                       // ... their annotation categories beside the plain score
+    std::vector<int> lds_bp;             // ... Prob::lds_bp
+    std::vector<double> lds_annot;       // ... Prob::lds_annot; empty: C = 0
     int traits_T = 0;                    // further traits (k_traits.hip); 0: not asked
     std::vector<double> traits_z;        // [Mld][T16]: the further traits' Z-scores, SNP-major, zero padded (the kernels' B operand)
     bool miss = false;                   // the traits came with a mask of missing SNPs (k_traits_miss.hip)
@@ -62,7 +67,7 @@ struct Riders {
     bool needs_fused() const { return loo || traits_T > 0 || susie_L > 0; }      // it reads the rows of L^-1 that only the fused solve forms
     // (a peer of a group keeps its fit's state in the workspace and returns none of it: the joint fit's sections are the leader's)
     bool xs_peer() const { return xs_group != 0 && xs_pos > 0; }
-    ResLayout layout(int n_rhs, int M, int U) const { return res_layout(n_rhs, M, U, loo, traits_T, slct_K, miss, miss_n, cond, cs, xs_peer() ? 0 : susie_L, susie_am, susie_lbf, susie_k, coloc, xs_group && xs_pos == 0 ? xs_K : 0, xs_mu, prs_n_s, prs_n_lam); }
+    ResLayout layout(int n_rhs, int M, int U) const { return res_layout(n_rhs, M, U, loo, traits_T, slct_K, miss, miss_n, cond, cs, xs_peer() ? 0 : susie_L, susie_am, susie_lbf, susie_k, coloc, xs_group && xs_pos == 0 ? xs_K : 0, xs_mu, prs_n_s, prs_n_lam, lds, lds_C); }
 };
 
 // One field of a section: n values from res[off] on, `stride` doubles apart (1 but for the words of the prs cells).
@@ -96,7 +101,7 @@ inline void fit_fields(Fields& F, size_t at, size_t lbf, const Riders& rd, size_
     if (rd.susie_lbf) F.dbl(lbf, lt, to(o.lbf, lt));
 }
 
-// One imputation window's block (n_rhs = U), field by field, section by section (res_layout and the sub-layouts of gauss_internal.h):
+// One window's block (n_rhs = U: an imputation window's, or an LD window's with its LD scores), field by field, section by section (res_layout and the sub-layouts of gauss_internal.h):
 // every double of the block belongs to exactly one field.
 inline std::vector<Field> result_fields(int M, int U, const Riders& rd, const ResLayout& lay, double* out_z, double* out_info)
 {
@@ -156,6 +161,11 @@ inline std::vector<Field> result_fields(int M, int U, const Riders& rd, const Re
         F.dbl(at + PRS_BG, nc, o.prs_bg, NAN, PRS_CELL); F.dbl(at + PRS_KKT, nc, o.prs_kkt, NAN, PRS_CELL);
         F.flag(at + PRS_NOCONV, nc, GAUSS_ST_PRS_NOCONV, nullptr, PRS_CELL); F.dbl(at + PRS_NOCONV + 1, nc, nullptr, NAN, PRS_CELL);
         F.dbl(lay.prs + ql.beta, nc * m, o.prs_beta);
+    }
+    if (rd.lds) {                          // LD scores of an LD window's measured SNPs (k_ldscore.hip)
+        const LdsLayout ll = lds_layout(M, rd.lds_C);
+        const size_t n = (size_t)(1 + rd.lds_C) * m;
+        F.dbl(lay.lds + ll.raw, n, o.lds_raw); F.dbl(lay.lds + ll.l2, n, o.lds_l2); F.dbl(lay.lds + ll.mass, n, o.lds_mass);
     }
     return F.f;
 }

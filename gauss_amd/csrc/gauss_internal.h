@@ -166,6 +166,14 @@ struct Prob {
     double prs_n, prs_tol;                 // the study's sample size; a lam is left when delta < prs_tol * r_max
     double prs_s[8], prs_lam[32];          // [PRS_S], [PRS_LAM] the grid
     GP(double) out_prs;                    // [prs_layout(M, n_s, n_lam).count]
+    // LD scores of the measured SNPs of an LD window (k_ldscore.hip); lds_on = 0: not asked
+    int lds_on, lds_C;                     // categories C <= LDS_C beside the plain score
+    long long lds_radius;                  // bp, >= 0 (capped at 2^32 by the planner: positions are 32-bit)
+    double lds_n;                          // the sample size of the bias adjustment
+    GP(const int) lds_bp;                  // [M + U] positions, the measured rows first
+    GP(const double) lds_annot;            // [C][M + U] weights; null: C = 0
+    GP(double) lds_part;                   // [1 + C][lds_chunks(M, U)][2][Mld] scratch: every chunk's partial raw, then mass, per target
+    GP(double) out_lds;                    // [lds_layout(M, C).count]
     // further traits on the same window (k_traits.hip); traits_T = 0: not asked
     int traits_T;                          // T <= TRAITS_MAX further Z-score vectors
     GP(const double) traits_Z;             // [Mld][T16] their Z-scores, SNP-major, zero beyond M and T (T16 = T rounded up to 16)
@@ -197,6 +205,7 @@ inline void clear_riders(Prob& q)
     q.xs_n = q.xs_pos = q.xs_mu = 0; q.xs_peer[0] = q.xs_peer[1] = q.xs_peer[2] = q.xs_peer[3] = 0;
     q.xs_from_lead = q.xs_to_lead = nullptr; q.out_xs = nullptr;
     q.prs_n_s = q.prs_n_lam = q.prs_max_sweeps = 0; q.prs_n = q.prs_tol = 0.0; q.out_prs = nullptr;
+    q.lds_on = q.lds_C = 0; q.lds_radius = 0; q.lds_n = 0.0; q.lds_bp = nullptr; q.lds_annot = nullptr; q.lds_part = q.out_lds = nullptr;
     q.traits_T = 0; q.traits_Z = nullptr; q.traits_Y = q.traits_G = q.out_traits = nullptr;
     q.miss_E = q.miss_nm = q.miss_n = 0; q.miss_tab = nullptr;
     q.miss_YE = q.miss_AE = q.miss_YU = q.miss_LD = q.out_traits_info = q.out_traits_miss = nullptr;
@@ -232,6 +241,11 @@ constexpr int PRS_LAM = 32;            // GAUSS_PRS_MAX_LAM: penalties on a chai
 constexpr int PRS_MAX_SWEEPS = 1000;   // GAUSS_PRS_MAX_SWEEPS: with it every loop of prs_kernel is bounded
 constexpr int PRS_M_MAX = 4096;        // GAUSS_PRS_MAX_M: beta, g, r and diag(B) of a chain in LDS: 4 M doubles, 128 KB of gfx950's 160
 constexpr int PRS_T = 256;             // threads of prs_kernel: one workgroup per chain
+constexpr int LDS_C = 32;              // GAUSS_LDS_MAX_ANNOT: annotation categories of a window's LD scores
+constexpr int LDS_CHUNK = 64;          // GAUSS_LDS_CHUNK: rows of a chunk of ldscore_kernel's summation order
+constexpr int LDS_COLS = 64;           // targets of a workgroup of ldscore_kernel: one per lane of its wave
+constexpr int LDS_MAX_CHUNKS = 65535;  // chunks of a window: they are the y extent of ldscore_kernel's grid (the planner refuses more: 4.19 M rows)
+constexpr int lds_chunks(int M, int U) { return (M + LDS_CHUNK - 1) / LDS_CHUNK + (U + LDS_CHUNK - 1) / LDS_CHUNK; }      // measured rows' chunks, then the others'
 constexpr int susie_uld(int U) { return (U + 63) & ~63; }   // row pitch of W and Y
 // Prob::susie_ws in doubles.  Y = X C^T and W = X^T Y = B11^-1 B12 [Mld][uld], the window's; then one block per fitted trait (trait t
 // of 0 .. susie_k at t * trait doubles further on): zhat, d, adm [tld] per candidate; alpha, mu, rb (R b_l) and lbf [L][tld]; f [tld];
@@ -262,14 +276,15 @@ constexpr SusieWs susie_ws(int M, int U, int Mld, int L, bool w)
 // A window's doubles in the job's result block, in this order and nowhere else written down:
 //     z[n_rhs], info[n_rhs] [, loo_z[M], loo_info[M], loo_t[M]] [, traits [T][U]] [, traits_info [T][U], traits_miss [2][n_miss]]
 //     [, the selection] [, cond_z[U], cond_var[U]] [, cs: size[K], mass[K], lse[K], pip[M+U], set[M+U], set_pip[M+U]]
-//     [, susie: susie_layout] [, susie_more: susie_more_layout] [, xs: xs_layout] [, prs: prs_layout]
+//     [, susie: susie_layout] [, susie_more: susie_more_layout] [, xs: xs_layout] [, prs: prs_layout] [, lds: lds_layout]
 // Offsets in doubles from the window's Plan::res_off; a section nobody asked for takes nothing and its offset is that of the next.
 // traits_info and traits_miss exist when the window passed a mask (miss): n_miss = its set bits.  The conditional section
 // (cond; k_cond.hip), behind it the credible sets (cs; k_cs.hip), behind them the multi-causal fit (susie; k_susie.hip) and what it holds beyond trait 1's
 // values (susie_more; the further traits' fits, the lbf rows, the colocalisation of k_coloc.hip) are the last: every other offset is
 // what it is without them.  The leader of a group of the joint fit across studies (xs; k_xsusie.hip) has one more section behind them.
-// The polygenic score weights (prs; k_prs.hip) come behind all of them.
-struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, susie_more, xs, prs, count; };
+// The polygenic score weights (prs; k_prs.hip) come behind all of them, and behind them the LD scores of an LD window (lds;
+// k_ldscore.hip), which has none of the others.
+struct ResLayout { size_t z, info, loo, traits, traits_info, traits_miss, slct, cond, cs, susie, susie_more, xs, prs, lds, count; };
 // Inside the selection's section, from its start: n, skipped, idx[K], zin[K], joint[K], zc[M], var_left[M] (indices, n and the
 // skipped flag travel as exact doubles).  The host and slct_kernel both read it here.
 struct SlctLayout { size_t n, skipped, idx, zin, joint, zc, var, count; };
@@ -323,9 +338,18 @@ constexpr PrsLayout prs_layout(int M, int n_s, int n_lam)
     const size_t c = (size_t)n_s * n_lam;
     return {0, c * PRS_CELL, c * PRS_CELL + c * (size_t)M};
 }
+// Inside the LD scores' section, from its start: raw, l2, mass, each [1 + C][M] (category 0 is the plain score).  ldscore_finish_kernel
+// and the host both read it here.
+struct LdsLayout { size_t raw, l2, mass, count; };
+constexpr LdsLayout lds_layout(int M, int C)
+{
+    const size_t n = (size_t)(1 + C) * M;
+    return {0, n, 2 * n, 3 * n};
+}
 constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, bool miss = false, int n_miss = 0, bool cond = false,
                                bool cs = false, int susie_L = 0, bool susie_am = false, bool susie_lbf = false, int susie_k = 0,
-                               bool coloc = false, int xs_K = 0, bool xs_mu = false, int prs_n_s = 0, int prs_n_lam = 0)
+                               bool coloc = false, int xs_K = 0, bool xs_mu = false, int prs_n_s = 0, int prs_n_lam = 0, bool lds = false,
+                               int lds_C = 0)
 {
     const size_t o_loo = 2 * (size_t)n_rhs, o_traits = o_loo + (loo ? 3 * (size_t)M : 0), o_tinfo = o_traits + (size_t)T * U;
     const size_t o_tmiss = o_tinfo + (miss ? (size_t)T * U : 0), o_slct = o_tmiss + (miss ? 2 * (size_t)n_miss : 0);
@@ -335,8 +359,9 @@ constexpr ResLayout res_layout(int n_rhs, int M, int U, bool loo, int T, int K, 
     const size_t o_more = o_susie + (susie_L ? susie_layout(M + U, susie_L, susie_am).count : 0);
     const size_t o_xs = o_more + (susie_L ? susie_more_layout(M + U, susie_L, susie_am, susie_lbf, susie_k, coloc).count : 0);
     const size_t o_prs = o_xs + (xs_K ? xs_layout(xs_K, susie_L, M + U, xs_mu).count : 0);
-    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie, o_more, o_xs, o_prs,
-            o_prs + (prs_n_s ? prs_layout(M, prs_n_s, prs_n_lam).count : 0)};
+    const size_t o_lds = o_prs + (prs_n_s ? prs_layout(M, prs_n_s, prs_n_lam).count : 0);
+    return {0, (size_t)n_rhs, o_loo, o_traits, o_tinfo, o_tmiss, o_slct, o_cond, o_cs, o_susie, o_more, o_xs, o_prs, o_lds,
+            o_lds + (lds ? lds_layout(M, lds_C).count : 0)};
 }
 
 #ifndef GAUSS_LAYOUTS_ONLY
@@ -466,6 +491,10 @@ void launch_cs(const Prob* d_probs, const int* d_csmap, int n, int max_T, hipStr
 // window), max_s = the most chains, max_M = the most measured SNPs one of them has (the launch's LDS).  B11 in A[0] and z1 are all it
 // reads: it needs no fused solve, and runs at the end of the tail, where nothing waits for it
 void launch_prs(const Prob* d_probs, const int* d_prsmap, int n, int max_s, int max_M, hipStream_t s);
+// LD scores (k_ldscore.hip) of the asking LD windows (d_ldsmap): one wave per (LDS_COLS targets, chunk of LDS_CHUNK rows, category,
+// window) parks its partial sums, then a finish launch adds every target's chunks in ascending order and forms l2.  max_M / max_chunks /
+// max_C: the largest among the asking windows.  It reads B11 in A[0] and B21 as the LD epilogue left them: queued last, behind the tail
+void launch_ldscore(const Prob* d_probs, const int* d_ldsmap, int n, int max_M, int max_chunks, int max_C, hipStream_t s);
 // multi-causal fine-mapping (k_susie.hip) of the asking windows (d_susiemap; null: the windows d_probs[0 .. n)).  launch_susie_w:
 // W = X^T (X B12) of the windows that fit unmeasured candidates, two launches over (64-row block of X) x (64 unmeasured SNPs); it runs
 // where launch_traits_weights runs (B21 is complete there).  launch_susie: the state, then max_sweeps x max_L x 2 dependent launches

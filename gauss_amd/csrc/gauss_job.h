@@ -300,6 +300,8 @@ struct TailMaps {
     int* d_prsmap = nullptr;    int n_prs = 0;             // polygenic score weights: the windows that asked
     int prs_max_s = 0, prs_max_M = 0;                      // ... the most chains and the most measured SNPs one of them has
     int cs_max_T = 0;                                      // ... and the most candidates (M + U) one of them has
+    int* d_ldsmap = nullptr;    int n_lds = 0;             // LD scores: the LD windows that asked
+    int lds_max_M = 0, lds_max_chunks = 0, lds_max_C = 0;  // ... the most targets, row chunks and categories one of them has
     int* d_susiemap = nullptr;  int n_susie = 0;           // multi-causal fine-mapping: the windows that asked
     FitDims susie_dims;                                    // ... their largest dimensions
     int susie_max_k = 0;  bool susie_coloc = false;        // ... the most further traits in one fit; a window asks for the colocalisation
@@ -486,6 +488,11 @@ struct WinSpec {
     int prs_n_s = 0, prs_n_lam = 0, prs_max_sweeps = 0;      // polygenic score weights (gauss_window_desc.prs_*); prs_n_s = 0: off
     const double *prs_s = nullptr, *prs_lam = nullptr;
     double prs_n = 0.0, prs_tol = 0.0;
+    int lds_on = 0, lds_n_annot = 0;         // LD scores of an LD window (gauss_window_desc.lds_*); lds_on = 0: off
+    long long lds_radius = 0;
+    const int32_t *lds_bp_m = nullptr, *lds_bp_u = nullptr;
+    double lds_n = 0.0;
+    const double* lds_annot = nullptr;
     const int32_t* xs_from_lead = nullptr;   // [T_lead] or NULL
     const int32_t* slct_forced = nullptr;
     int n_slct_forced = 0;

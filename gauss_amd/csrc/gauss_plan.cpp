@@ -144,6 +144,36 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         return fail(GAUSS_E_INVALID, "prs_max_sweeps = %d: a penalty takes 1 .. %d sweeps", w.prs_max_sweeps, PRS_MAX_SWEEPS);
     if (prs && w.M > PRS_M_MAX)
         return fail(GAUSS_E_INVALID, "n_measured = %d: the score (prs_n_s) takes windows of at most %d measured SNPs", w.M, PRS_M_MAX);
+    // LD scores of the measured SNPs (k_ldscore.hip): the one rider of an LD window
+    const bool lds = w.lds_on != 0;
+    if (lds && (w.ld_only || w.kind != GAUSS_WIN_LD))
+        return fail(GAUSS_E_INVALID, "LD scores (lds_on) are for LD windows only (%s window)", w.kind == GAUSS_WIN_QCAT ? "QCAT" : "imputation");
+    if (lds && w.lambda != 0.0)
+        return fail(GAUSS_E_INVALID, "lambda = %g: LD scores (lds_on) take correlations, a window with lambda = 0", w.lambda);
+    if (lds && (w.u_codings & ~GAUSS_CODE_ADDITIVE))
+        return fail(GAUSS_E_INVALID, "u_codings = %d: LD scores (lds_on) take the additive coding only", w.u_codings);
+    if (lds && (!w.lds_bp_m || (w.U > 0 && !w.lds_bp_u)))
+        return fail(GAUSS_E_INVALID, "LD scores (lds_on) need the positions of the window's rows: %s is NULL", !w.lds_bp_m ? "lds_bp_m" : "lds_bp_u");
+    for (int a = 1; lds && a < w.M; a++)
+        if (w.lds_bp_m[a] < w.lds_bp_m[a - 1])
+            return fail(GAUSS_E_INVALID, "lds_bp_m[%d] = %d < lds_bp_m[%d] = %d: the positions do not decrease", a, (int)w.lds_bp_m[a], a - 1, (int)w.lds_bp_m[a - 1]);
+    for (int a = 1; lds && a < w.U; a++)
+        if (w.lds_bp_u[a] < w.lds_bp_u[a - 1])
+            return fail(GAUSS_E_INVALID, "lds_bp_u[%d] = %d < lds_bp_u[%d] = %d: the positions do not decrease", a, (int)w.lds_bp_u[a], a - 1, (int)w.lds_bp_u[a - 1]);
+    if (lds && !(w.lds_n > 2.0 && std::isfinite(w.lds_n)))
+        return fail(GAUSS_E_INVALID, "lds_n = %g: the sample size of the bias adjustment is finite and above 2", w.lds_n);
+    if (lds && w.lds_radius < 0)
+        return fail(GAUSS_E_INVALID, "lds_radius = %lld: the radius of an LD score is not negative", w.lds_radius);
+    if (lds && (w.lds_n_annot < 0 || w.lds_n_annot > LDS_C))
+        return fail(GAUSS_E_INVALID, "lds_n_annot = %d: LD scores take 0 .. %d annotation categories", w.lds_n_annot, LDS_C);
+    if (lds && lds_chunks(w.M, w.U) > LDS_MAX_CHUNKS)
+        return fail(GAUSS_E_INVALID, "LD scores (lds_on): %d + %d rows make %d chunks of %d; a window takes at most %d (shorten it)", w.M, w.U,
+                    lds_chunks(w.M, w.U), LDS_CHUNK, LDS_MAX_CHUNKS);
+    if (lds && w.lds_n_annot > 0 && !w.lds_annot)
+        return fail(GAUSS_E_INVALID, "lds_n_annot = %d: the categories' weights (lds_annot) are NULL", w.lds_n_annot);
+    for (size_t a = 0; lds && a < (size_t)w.lds_n_annot * (size_t)(w.M + w.U); a++)
+        if (!std::isfinite(w.lds_annot[a]))
+            return fail(GAUSS_E_INVALID, "lds_annot[%d][%d] = %g: an annotation weight is finite", (int)(a / (size_t)(w.M + w.U)), (int)(a % (size_t)(w.M + w.U)), w.lds_annot[a]);
     // multi-causal fine-mapping (k_susie.hip)
     const bool susie = w.susie_L != 0;
     if (susie && !imputes)
@@ -475,6 +505,15 @@ int plan_problem(const WinSpec& w, Plan& pl, int seg_max, int group_target)
         for (int a = 0; a < PRS_S; a++) p.prs_s[a] = a < w.prs_n_s ? w.prs_s[a] : 0.0;
         for (int a = 0; a < PRS_LAM; a++) p.prs_lam[a] = a < w.prs_n_lam ? w.prs_lam[a] : 0.0;
     }
+    if (lds) {
+        // positions and weights in the concatenated row space, the measured rows first; any radius from 2^32 on holds every 32-bit position
+        rd.lds = true; rd.lds_C = w.lds_n_annot;
+        rd.lds_bp.assign(w.lds_bp_m, w.lds_bp_m + w.M);
+        if (w.U > 0) rd.lds_bp.insert(rd.lds_bp.end(), w.lds_bp_u, w.lds_bp_u + w.U);
+        if (w.lds_n_annot > 0) rd.lds_annot.assign(w.lds_annot, w.lds_annot + (size_t)w.lds_n_annot * (size_t)(w.M + w.U));
+        p.lds_on = 1; p.lds_C = w.lds_n_annot; p.lds_n = w.lds_n;
+        p.lds_radius = std::min<long long>(w.lds_radius, 1LL << 32);
+    }
     p.cs_coverage = cs ? w.cs_coverage : 0.0;
     p.cs_prior_var = cs ? w.cs_prior_var : 0.0;
     if (susie) {
@@ -624,7 +663,7 @@ struct JobBuild {
     std::vector<uint8_t> item_class;                       // launch class of items[n]: 0 B11 (or everything), 1 early B21, 2 late B21
     std::vector<char> late_window;                         // early epilogue: windows whose B21 items end the merged launch
     std::vector<int2> rowmap, tilemap, tilemap_b21, panelmap, dpanelmap, gemmmap, finmap, loomap;
-    std::vector<int> slctmap, condmap, csmap, susiemap, xsmap, xsleadmap, prsmap;
+    std::vector<int> slctmap, condmap, csmap, susiemap, xsmap, xsleadmap, prsmap, ldsmap;
     std::vector<int2> traitsmap, traitsumap, missmap, misstmap, missumap;
     std::vector<const uint32_t*> chunk_live;               // per descriptor: its Plan::chunk_live on the device (Item::chunk_live)
     Arena ta;         // table image (job->h_tab)
@@ -846,6 +885,8 @@ void JobBuild::place_tables(Plan& pl, const uint32_t*& d_chunk_live, bool window
     if (!pl.rd.miss_tab.empty()) tab(p.miss_tab, pl.rd.miss_tab, pl.rd.miss);
     if (!pl.rd.xs_from_lead.empty()) tab(p.xs_from_lead, pl.rd.xs_from_lead);
     if (!pl.rd.xs_to_lead.empty()) tab(p.xs_to_lead, pl.rd.xs_to_lead);
+    if (pl.rd.lds) tab(p.lds_bp, pl.rd.lds_bp);
+    if (!pl.rd.lds_annot.empty()) tab(p.lds_annot, pl.rd.lds_annot);
 }
 // ---- table arena (host mirrored) ----
 int JobBuild::place_all_tables()
@@ -929,6 +970,11 @@ int JobBuild::work_lists()
         if (rd.cond) { condmap.push_back(i); job->tail.cond_max_U = std::max(job->tail.cond_max_U, p.U); }
         if (rd.cs) { csmap.push_back(i); job->tail.cs_max_T = std::max(job->tail.cs_max_T, p.M + p.U); }
         if (rd.prs_n_s) { prsmap.push_back(i); job->tail.prs_max_s = std::max(job->tail.prs_max_s, rd.prs_n_s); job->tail.prs_max_M = std::max(job->tail.prs_max_M, p.M); }
+        if (rd.lds) {
+            ldsmap.push_back(i);
+            job->tail.lds_max_M = std::max(job->tail.lds_max_M, p.M); job->tail.lds_max_C = std::max(job->tail.lds_max_C, rd.lds_C);
+            job->tail.lds_max_chunks = std::max(job->tail.lds_max_chunks, lds_chunks(p.M, p.U));
+        }
         if (rd.susie_L && rd.xs_group) {       // a member of a group of the joint fit across studies: launches and map of its own
             xsmap.push_back(i);
             if (rd.xs_pos == 0) xsleadmap.push_back(i);
@@ -1182,6 +1228,7 @@ int JobBuild::place_lists()
     tab(job->tail.d_traitsmap, job->tail.n_traits, traitsmap, if_any); tab(job->tail.d_traitsumap, job->tail.n_traits_u, traitsumap, if_any);
     tab(job->tail.d_missmap, job->tail.n_miss_blk, missmap, if_any); tab(job->tail.d_misstmap, job->tail.n_miss_t, misstmap, if_any);
     tab(job->tail.d_missumap, job->tail.n_miss_u, missumap, if_any);
+    tab(job->tail.d_ldsmap, job->tail.n_lds, ldsmap, if_any);
     o_probs = tab_block(job->d_probs, sizeof(Prob) * (size_t)n_prob());
     o_exports = tab_block(job->d_exports, sizeof(ExportD) * std::max<size_t>(job->exports.size(), 1));
     job->h_tab.resize(ta.off);
@@ -1244,6 +1291,8 @@ void JobBuild::layout_window(Plan& pl)
         ws(p.miss_YU, E16 * (size_t)p.U * sizeof(double));
         ws(p.miss_LD, (size_t)p.miss_nm * MISS_LD * sizeof(double));
     }
+    if (rd.lds)                         // every chunk's partial raw and mass, per category and target
+        ws(p.lds_part, (size_t)(1 + rd.lds_C) * lds_chunks(p.M, p.U) * 2 * p.Mld * sizeof(double));
     ws(p.out_ld, std::max<size_t>(pl.out_ld_count, 1) * sizeof(double));
     pl.res_off = res;
     res += pl.res_count();
@@ -1388,6 +1437,7 @@ int JobBuild::bind()
         p.out_susie_more = pl.rd.susie_L && lay.xs > lay.susie_more ? out + lay.susie_more : nullptr;
         p.out_xs = lay.prs > lay.xs ? out + lay.xs : nullptr;
         p.out_prs = pl.rd.prs_n_s ? out + lay.prs : nullptr;
+        p.out_lds = pl.rd.lds ? out + lay.lds : nullptr;
         p.out_traits = pl.rd.traits_T ? out + lay.traits : nullptr;
         p.out_traits_info = pl.rd.miss ? out + lay.traits_info : nullptr; p.out_traits_miss = pl.rd.miss ? out + lay.traits_miss : nullptr;
         p.status = job->d_status + 4 * i;

@@ -119,7 +119,9 @@ static int job_queue_results(gauss_job* job, int par, hipStream_t st)
 //     complete where the tail starts; the fit itself reads z and info of the closing step, B11 in A[0] and B21, and for its further
 //     traits the scores in traits_Z and the imputed Z-scores traits impute has left (such a window has no mask: miss apply leaves them).
 //   - the polygenic score weights (k_prs.hip): B11 in A[0] and z1, like the selection; a chain is some hundred dependent sweeps that
-//     nothing else reads, so it is queued last: everything the caller may be waiting for is in front of it.
+//     nothing else reads, so it is queued behind everything the caller may be waiting for;
+//   - the LD scores of the LD windows that ask (k_ldscore.hip): B11 in A[0] and B21 as the LD epilogue left them -- an LD window has
+//     no solve, nothing of the tail touches its matrices.  A run without a solve has no tail: it queues this launch alone.
 // The closing step is the product B21 [X | y] with its finish kernel, or -- d_solvemap: (window, panel of right-hand sides) -- the
 // stand-alone solve, which takes V as its scratch and only reads B21.  A launch for which no window asked is skipped by its launcher
 // (each returns at n <= 0).  Every tail is queued here: a run's over the job's maps; under GAUSS_FUSED_SOLVE=0 with the stand-alone
@@ -142,6 +144,7 @@ static void queue_tail(const Prob* probs, const TailMaps& m, const int2* d_solve
     launch_susie(probs, m.d_susiemap, m.n_susie, m.susie_dims.M, m.susie_dims.T, m.susie_dims.L, m.susie_dims.sweeps, m.susie_max_k, m.susie_coloc, st);
     launch_xsusie(probs, m.d_xsmap, m.n_xs, m.d_xsleadmap, m.n_xs_lead, m.xs_dims.M, m.xs_dims.T, m.xs_dims.L, m.xs_dims.sweeps, st);
     launch_prs(probs, m.d_prsmap, m.n_prs, m.prs_max_s, m.prs_max_M, st);
+    launch_ldscore(probs, m.d_ldsmap, m.n_lds, m.lds_max_M, m.lds_max_chunks, m.lds_max_C, st);
 }
 
 // One pass of the job on the context's queues, with the cross-queue events and the result mirrors of parity `par`.
@@ -281,6 +284,10 @@ static int job_queue_run(gauss_job* job, bool solve, int par, bool allow_merged)
         }
         queue_tail(job->d_probs, job->tail, fused ? nullptr : job->d_dpanelmap, job->n_dpanels, st);
         prof_end(job, st);
+    } else {
+        // no solve, no tail (`side` is null: every epilogue tile ran on this queue): the LD scores of the LD windows that ask
+        const TailMaps& m = job->tail;
+        launch_ldscore(job->d_probs, m.d_ldsmap, m.n_lds, m.lds_max_M, m.lds_max_chunks, m.lds_max_C, st);
     }
     return job_queue_results(job, par, st);
 }
@@ -667,8 +674,14 @@ static int fetch_mats(const gauss_job* job, const Plan& pl, const double* d_b11,
     return rc;
 }
 
-// raw LD export: B11 sits unfactored in A[0] (diagonal 1 + lambda), B21 in its buffer
-static int deliver_ld(gauss_job* job, int i) { return fetch_mats(job, job->plans[i], job->plans[i].p.A); }
+// raw LD export: B11 sits unfactored in A[0] (diagonal 1 + lambda), B21 in its buffer; a window that asked for its LD scores has that
+// one section in the result block (gauss_deliver.h)
+static int deliver_ld(gauss_job* job, int i, int* bits)
+{
+    const Plan& pl = job->plans[i];
+    if (pl.rd.lds) *bits = deliver_window(job->h_results + pl.res_off, pl.p.M, pl.p.U, pl.rd, nullptr, nullptr, *bits, false);
+    return fetch_mats(job, pl, pl.p.A);
+}
 
 // QCAT never repairs B11 (MakePosDef is commented out, qcat.cpp:206); CountPC only counts
 static int deliver_qcat(gauss_job* job, int i, int* bits)
@@ -724,7 +737,7 @@ int job_fetch(gauss_job* job)
     for (int i = 0; i < job->n; i++) {
         const Plan& pl = job->plans[i];
         int bits = 0;
-        rc = pl.p.kind == GAUSS_WIN_LD ? deliver_ld(job, i) : pl.p.kind == GAUSS_WIN_QCAT ? deliver_qcat(job, i, &bits) : deliver_impute(job, i, &bits);
+        rc = pl.p.kind == GAUSS_WIN_LD ? deliver_ld(job, i, &bits) : pl.p.kind == GAUSS_WIN_QCAT ? deliver_qcat(job, i, &bits) : deliver_impute(job, i, &bits);
         if (rc) return rc;
         if (pl.out_status) *pl.out_status = bits;
     }

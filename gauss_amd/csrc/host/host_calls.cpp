@@ -80,7 +80,7 @@ static int prepare_opened(const CallArgs& c, const char* annotation_file, const 
     a.drop_wing_unmeasured = pk && (kind == GAUSS_KIND_DIST || kind == GAUSS_KIND_DISTMIX);
     a.af1_cutoff = std::isnan(c.af1_cutoff) ? (kind == GAUSS_KIND_QCAT ? 0.05 : 0.01) : c.af1_cutoff;   // dist.cpp:53-57, qcat.cpp:53-57
     const bool mix = (kind == GAUSS_KIND_COMPUTELD || kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_JEPEGMIX ||
-                      kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_PREP_RECESSIVE);
+                      kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_PREP_RECESSIVE || kind == GAUSS_KIND_LDSCOREMIX);
     if (mix) {
         if (!c.pop_names || !c.pop_wgts || c.n_pop_wgt < 1) return herr("pop_wgt_df is empty");
         set_pop_wgt_map(a, c.pop_names, c.pop_wgts, c.n_pop_wgt);
@@ -637,6 +637,90 @@ int gauss_host_distmix_prs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t en
     PrsRider r(n, s, n_s, lam, n_lam, tol, max_sweeps);
     return run_impute(ctx, call_mix(GAUSS_KIND_DISTMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
                                     reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), &r, out);
+}
+
+// dist_ldscore / distmix_ldscore: ONE window of a kind of its own -- the targets are the study's SNPs inside [start_bp, end_bp], the
+// reference rows every other panel SNP of the extended window (lean_window_build / prepare make the partition) -- run as an LD window
+// that asks for its LD scores and for no matrix: M numbers come back (include/gauss_host.h)
+static int run_ldscore(gauss_ctx* ctx, const CallArgs& c, double n_arg, gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    if (files_ok({c.input, c.index, c.data, c.desc})) return -1;
+    std::string panel_path;
+    std::shared_ptr<PackedPanel> pk;
+    if (open_panel(c.index, c.data, c.desc, panel_path, pk)) return -1;
+    const bool mix = c.kind == GAUSS_KIND_LDSCOREMIX;
+    OneWindow ow;
+    std::unique_ptr<gauss_prepared> prep;
+    const int lean = one_window_build(ow, c, panel_path, pk);
+    if (lean < 0) return -1;
+    if (lean) {
+        gauss_prepared* p = nullptr;
+        if (prepare_opened(c, nullptr, panel_path, pk, false, &p)) return -1;
+        prep.reset(p);
+    }
+    std::vector<LdsRow> rows;
+    std::vector<int32_t> bp_m, bp_u;
+    int64_t n_ref = 0, n_ref_5_50 = 0;
+    auto count = [&](double af) { n_ref++; if (std::min(af, 1.0 - af) > 0.05) n_ref_5_50++; };
+    gauss_window_desc d;
+    memset(&d, 0, sizeof(d));
+    d.kind = GAUSS_WIN_LD;
+    d.mode = mix ? GAUSS_MODE_WEIGHTED : GAUSS_MODE_POOLED;
+    d.lambda = 0.0; d.u_codings = GAUSS_CODE_ADDITIVE;
+    if (!lean) {
+        const LeanWindow& w = ow.w;
+        const ChromSetup& cs = ow.cs;
+        for (int32_t vi : w.measured) { const LeanSnp& sn = w.v[(size_t)vi]; rows.push_back(LdsRow{ident_of(*pk, sn), sn.af}); bp_m.push_back((int32_t)sn.bp); count(sn.af); }
+        for (int32_t vi : w.unmeasured) { const LeanSnp& sn = w.v[(size_t)vi]; bp_u.push_back((int32_t)sn.bp); count(sn.af); }
+        d.n_pop = (int)cs.pop_off.size() - 1;
+        d.pop_off = cs.pop_off.data(); d.pop_wgt = cs.pop_wgt.data();
+        d.geno_format = GAUSS_GENO_2BIT;
+        d.ld = pk->row_bytes();
+        d.rows_m = w.store_rows_m.data(); d.rows_u = w.store_rows_u.data();
+        d.pop_src_off = cs.pop_src_off.data();
+    } else {
+        gauss_prepared& p = *prep;
+        for (const Snp* s : p.measured) { const double af = mix ? s->af1mix : s->af1ref; rows.push_back(LdsRow{ident_of(*s), af}); bp_m.push_back((int32_t)s->bp); count(af); }
+        for (const Snp* s : p.unmeasured) { bp_u.push_back((int32_t)s->bp); count(mix ? s->af1mix : s->af1ref); }
+        d.n_pop = (int)p.pop_off.size() - 1;
+        d.pop_off = p.pop_off.data(); d.pop_wgt = p.pop_wgt.data();
+        set_geno(&p, &d);
+    }
+    const size_t M = rows.size(), U = bp_u.size();
+    if (M == 0)
+        return herr("LD scores: no SNP of '%s' is in the panel between %lld and %lld on chromosome %d: the window has no SNP to score", c.input,
+                    (long long)c.start_bp, (long long)c.end_bp, c.chr);
+    if (M > GAUSS_HOST_LDSCORE_MAX_TARGETS || M + U > GAUSS_HOST_LDSCORE_MAX_ROWS)
+        return herr("LD scores: the window has %zu SNPs to score and %zu panel SNPs in all; one call takes at most %d and %d: shorten the window",
+                    M, M + U, GAUSS_HOST_LDSCORE_MAX_TARGETS, GAUSS_HOST_LDSCORE_MAX_ROWS);
+    d.n_measured = (int)M; d.n_unmeasured = (int)U;
+    const double n_eff = n_arg > 0.0 ? n_arg : mix ? kish_n_eff(d.pop_wgt, d.pop_off, d.n_pop) : (double)d.pop_off[d.n_pop];
+    std::vector<double> raw(M), l2(M), mass(M);
+    d.lds_on = 1; d.lds_n_annot = 0; d.lds_radius = c.wing; d.lds_n = n_eff;
+    d.lds_bp_m = bp_m.data(); d.lds_bp_u = U ? bp_u.data() : nullptr;
+    d.out_lds_raw = raw.data(); d.out_lds_l2 = l2.data(); d.out_lds_mass = mass.data();
+    // (out_b11 = out_b21 = NULL: the matrices stay on the device; out_status = NULL: an LD window raises no status bit)
+    if (run_window(ctx, d, panel_path, lean ? nullptr : pk.get())) return -1;
+    *out = ldscore_output(mix, rows, l2.data(), raw.data(), mass.data(), n_eff, n_ref, n_ref_5_50, c.wing);
+    return 0;
+}
+
+int gauss_host_dist_ldscore(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,
+                            const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                            const char* reference_pop_desc_file, double af1_cutoff, double n, gauss_table** out)
+{
+    return run_ldscore(ctx, call_pop(GAUSS_KIND_LDSCORE, chr, start_bp, end_bp, wing_size, study_pop, input_file, reference_index_file,
+                                     reference_data_file, reference_pop_desc_file, af1_cutoff), n, out);
+}
+
+int gauss_host_distmix_ldscore(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                               const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input_file,
+                               const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                               double af1_cutoff, double n, gauss_table** out)
+{
+    return run_ldscore(ctx, call_mix(GAUSS_KIND_LDSCOREMIX, chr, start_bp, end_bp, wing_size, pop_names, pop_wgts, n_pop_wgt, input_file,
+                                     reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff), n, out);
 }
 
 int gauss_host_dist_traits(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size, const char* study_pop,

@@ -223,7 +223,8 @@ int chrom_setup(ChromSetup& cs, int kind, int chr, int64_t wing_size, const char
                        const std::shared_ptr<const GwasCache>& gw)
 {
     cs.kind = kind;
-    cs.mix = (kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_COMPUTELD);
+    cs.mix = (kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_COMPUTELD || kind == GAUSS_KIND_LDSCOREMIX);
+    cs.lds = (kind == GAUSS_KIND_LDSCORE || kind == GAUSS_KIND_LDSCOREMIX);
     cs.measured_only = (kind == GAUSS_KIND_COMPUTELD);
     cs.qcat = (kind == GAUSS_KIND_QCAT || kind == GAUSS_KIND_QCATMIX);
     Args& a = cs.a;
@@ -273,7 +274,8 @@ int lean_window_build(LeanWindow& w, const ChromSetup& cs, long long start_bp, l
     const double cutoff = a.af1_cutoff;
     // MakeSnpVec / MakeSnpVecMix on the panel's tabulated counts and frequencies (MakeSnpVecPacked above), then the list
     auto keep = [&](int64_t row, long long bp, int type, double z, double info) {
-        if (type == 0 && (cs.measured_only || bp < start_bp || bp > end_bp)) return;       // a wing's unmeasured SNP (computeLD: any): nothing reads it
+        // a wing's unmeasured SNP (computeLD: any): nothing reads it -- but for the LD scores, whose reference rows are every panel SNP
+        if (type == 0 && !cs.lds && (cs.measured_only || bp < start_bp || bp > end_bp)) return;
         double af = 0;
         if (!cs.mix) {
             double allele_counter = 0;                                  // gauss.cpp:574-591 (integer-valued sums)
@@ -339,6 +341,13 @@ int lean_window_build(LeanWindow& w, const ChromSetup& cs, long long start_bp, l
     // the partition: dist.cpp:132-140, qcat.cpp:140-152
     for (size_t r = 0; r < w.v.size(); r++) {
         const LeanSnp& sn = w.v[r];
+        if (cs.lds) {
+            // LD scores: the targets are the study's SNPs inside [start_bp, end_bp]; every other panel SNP of the extended window -- a
+            // wing's SNP that the study measured too -- is a reference row
+            if (sn.type == 1 && sn.bp >= start_bp && sn.bp <= end_bp) { w.measured.push_back((int32_t)r); w.store_rows_m.push_back((int32_t)sn.row); w.z1.push_back(sn.z); w.n_predm++; }
+            else if (sn.type == 0 || sn.type == 1) { w.unmeasured.push_back((int32_t)r); w.store_rows_u.push_back((int32_t)sn.row); }
+            continue;
+        }
         if (sn.type == 0) { w.unmeasured.push_back((int32_t)r); w.store_rows_u.push_back((int32_t)sn.row); }   // (inside the prediction window: keep())
         else if (sn.type == 1) {
             w.measured.push_back((int32_t)r); w.store_rows_m.push_back((int32_t)sn.row); w.z1.push_back(sn.z);

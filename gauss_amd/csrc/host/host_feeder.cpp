@@ -874,7 +874,7 @@ void build_snp_table(gauss_prepared& p)
     gauss_table& t = p.snps;
     t.cols.clear();
     const bool mix = (p.kind == GAUSS_KIND_COMPUTELD || p.kind == GAUSS_KIND_DISTMIX || p.kind == GAUSS_KIND_JEPEGMIX ||
-                      p.kind == GAUSS_KIND_QCATMIX || p.kind == GAUSS_KIND_PREP_RECESSIVE);
+                      p.kind == GAUSS_KIND_QCATMIX || p.kind == GAUSS_KIND_PREP_RECESSIVE || p.kind == GAUSS_KIND_LDSCOREMIX);
     Column& rsid = t.add("rsid", GAUSS_COL_STR);
     for (Snp* s : p.snp_vec) rsid.s.push_back(s->rsid);
     Column& chr = t.add("chr", GAUSS_COL_INT);
@@ -905,7 +905,7 @@ int prepare(gauss_prepared& p)
     Args& a = p.args;
     const int kind = p.kind;
     const bool mix = (kind == GAUSS_KIND_COMPUTELD || kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_JEPEGMIX ||
-                      kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_PREP_RECESSIVE);
+                      kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_PREP_RECESSIVE || kind == GAUSS_KIND_LDSCOREMIX);
     const bool gene = (kind == GAUSS_KIND_JEPEG || kind == GAUSS_KIND_JEPEGMIX);
     const bool qcat = (kind == GAUSS_KIND_QCAT || kind == GAUSS_KIND_QCATMIX);
     const bool prep = (kind == GAUSS_KIND_PREP_QCAT || kind == GAUSS_KIND_PREP_RECESSIVE);
@@ -962,6 +962,14 @@ int prepare(gauss_prepared& p)
                 if (s->bp < a.start_bp) p.n_head++;
                 else if (s->bp <= a.end_bp) p.n_predm++;
             }
+        }
+    } else if (kind == GAUSS_KIND_LDSCORE || kind == GAUSS_KIND_LDSCOREMIX) {
+        // LD scores: the targets are the study's SNPs inside [start_bp, end_bp]; every other panel SNP of the extended window -- a
+        // wing's SNP that the study measured too -- is a reference row (host_chrom.cpp: lean_window_build makes the same partition)
+        for (size_t r = 0; r < p.snp_vec.size(); r++) {
+            Snp* s = p.snp_vec[r];
+            if (s->type == 1 && s->bp >= a.start_bp && s->bp <= a.end_bp) { p.measured.push_back(s); p.measured_rows.push_back((int32_t)r); p.n_predm++; }
+            else if (s->type == 0 || s->type == 1) { p.unmeasured.push_back(s); p.unmeasured_rows.push_back((int32_t)r); }
         }
     } else if (kind == GAUSS_KIND_COMPUTELD) {
         for (size_t r = 0; r < p.snp_vec.size(); r++)          // computeLD.cpp:80-86

@@ -417,6 +417,7 @@ struct ChromSetup {                     // what prepare() derives from a call's 
     int kind = 0;
     bool mix = false, qcat = false;
     bool measured_only = false;         // computeLD: unmeasured SNPs are never read (computeLD.cpp:80-86) -- not entered at all
+    bool lds = false;                   // LD scores: every panel SNP of the extended window is entered; the targets are the study's SNPs inside it
     Args a;                             // population table, flags, weights, cutoffs (start_bp / end_bp are the windows', not set here)
     std::vector<int> sel;               // the selected populations, panel order
     std::vector<int32_t> pop_off, pop_src_off;
@@ -579,6 +580,13 @@ struct SusieFit {                     // one trait's out_susie_* (first) or the 
 struct ColocMore { int k; SusieFit fit; const double* pp; const int32_t* hit; const double* hit_pp; const int32_t* n; };
 int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const SusieFit& first, int n_more, const double* z_more, const double* out_z_more, const ColocMore& more);
+// dist_ldscore / distmix_ldscore: a table of its own, one row per target: rsid chr bp a1 a2 af1ref|af1mix l2 l2_raw n_band, and the named
+// matrix `ldscore` [1 x 4]: n_eff, M (reference rows of the window, targets included), M_5_50 (those with min(af, 1 - af) > 0.05), radius
+struct LdsRow { SnpIdent id; double af; };
+gauss_table* ldscore_output(bool mix, const std::vector<LdsRow>& rows, const double* l2, const double* raw, const double* mass, double n_eff,
+                            int64_t n_ref, int64_t n_ref_5_50, int64_t radius);
+// Kish's effective size of a weighted panel: (sum w_p)^2 / sum (w_p^2 / n_p) over the populations of non-zero weight; sizes [P]
+double kish_n_eff(const double* w, const int32_t* pop_off, int P);
 // dist_prs / distmix_prs: a table of its own, one row per measured SNP of the extended window: rsid chr bp a1 a2 af1ref|af1mix z r wing
 // (r = z / sqrt(n - 2 + z^2), 0 where z is not finite: such a SNP is frozen at weight 0), the named matrices `beta` [n_s n_lam x rows],
 // grid cell i_s n_lam + i_lam, and `grid` [n_s n_lam x 9]: s, lam, nnz, sweeps, delta, br, bg, kkt, converged; a message when a cell

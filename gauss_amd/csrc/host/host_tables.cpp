@@ -555,6 +555,36 @@ gauss_table* prs_output(bool mix, const std::vector<SlctRow>& rows, double n, do
     return t;
 }
 
+// dist_ldscore / distmix_ldscore: one row per target (host_internal.h); n_band travels as the exact double the device summed
+gauss_table* ldscore_output(bool mix, const std::vector<LdsRow>& rows, const double* l2, const double* raw, const double* mass, double n_eff,
+                            int64_t n_ref, int64_t n_ref_5_50, int64_t radius)
+{
+    gauss_table* t = new gauss_table();
+    add_ident_columns(*t, rows.size(), [&](size_t i) { return rows[i].id; });
+    Column &af = t->add(mix ? "af1mix" : "af1ref", GAUSS_COL_DBL), &c_l2 = t->add("l2", GAUSS_COL_DBL), &c_raw = t->add("l2_raw", GAUSS_COL_DBL);
+    Column& band = t->add("n_band", GAUSS_COL_INT);
+    bool nan = false;
+    for (size_t i = 0; i < rows.size(); i++) {
+        af.d.push_back(rows[i].af); c_l2.d.push_back(l2[i]); c_raw.d.push_back(raw[i]);
+        band.i.push_back(mass[i] >= 0.0 && mass[i] <= (double)INT32_MAX ? (int)mass[i] : -1);      // (a count of rows; -1: not one, NaN included)
+        nan = nan || raw[i] != raw[i];
+    }
+    t->put_named("ldscore", 1, 4, std::vector<double>{n_eff, (double)n_ref, (double)n_ref_5_50, (double)radius});
+    if (nan) t->messages.push_back("ldscore: some scores are NaN: a panel SNP inside their band has no variance in the selected populations");
+    return t;
+}
+
+double kish_n_eff(const double* w, const int32_t* pop_off, int P)
+{
+    double sw = 0.0, sq = 0.0;
+    for (int p = 0; p < P; p++) {
+        if (w[p] == 0.0) continue;
+        sw += w[p];
+        sq += w[p] * w[p] / (double)(pop_off[p + 1] - pop_off[p]);
+    }
+    return sw * sw / sq;
+}
+
 int traits_match(const GwasCache& gw, const char* path, size_t n, const std::function<SnpIdent(size_t)>& at, double* z_out,
                  uint8_t* miss_out, size_t* n_missing)
 {

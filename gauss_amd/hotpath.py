@@ -278,7 +278,7 @@ class _Win:
 
     def __init__(self, desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig,
                  want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None, z_more=None, miss_more=None,
-                 susie=None, prs=None):
+                 susie=None, prs=None, ldscore=None, want_matrices=True):
         self.po, self.w = _pops(pop_off, pop_wgt)
         self.z1 = np.ascontiguousarray(z1, dtype=np.float64)
         if dev_ptrs is None:
@@ -294,11 +294,15 @@ class _Win:
             M = len(packed["rows_m"])                       # matrices are row lists into a store
             U = len(packed["rows_u"]) if packed.get("rows_u") is not None else 0
         self.M, self.U = M, U
+        if ldscore is not None and ld_codings is None:
+            ld_codings = _lib.CODE_ADDITIVE                 # LD scores ride on an LD window
         self.ld_codings = ld_codings
+        if not want_matrices and ldscore is None:           # (such a window would run and return nothing)
+            raise ValueError("want_matrices=False is for an LD window that asks for its LD scores (ldscore=dict(...))")
         if ld_codings is not None:
             ncode = max(1, bin(int(ld_codings)).count("1"))
-            want_mats = True
-            self.b21_ld = np.zeros((ncode * U, M))
+            want_mats = bool(want_matrices)                 # (False: out_b11 = out_b21 = NULL, nothing of the matrices comes back)
+            self.b21_ld = np.zeros((ncode * U, M)) if want_mats else None
         self.z = np.zeros(U)
         self.info = np.zeros(U)
         self.status = np.zeros(1, dtype=np.int32)
@@ -476,6 +480,24 @@ class _Win:
                 setattr(desc, "out_prs_" + key, q[key].ctypes.data_as(_dp))
             for key in ("nnz", "sweeps"):
                 setattr(desc, "out_prs_" + key, q[key].ctypes.data_as(_ip))
+        # LD scores of an LD window's measured SNPs (lds_* of gauss_window_desc): ldscore=dict(radius=, bp_m=, bp_u=, n=, annot=None);
+        # annot [C, M + U]: the weights of C annotation categories, the measured rows first
+        self.lds = None
+        if ldscore is not None:
+            q = ldscore
+            bm = np.ascontiguousarray(q["bp_m"], dtype=np.int32).reshape(-1) if q.get("bp_m") is not None else None
+            bu = np.ascontiguousarray(q["bp_u"], dtype=np.int32).reshape(-1) if q.get("bp_u") is not None else None
+            an = np.ascontiguousarray(q["annot"], dtype=np.float64) if q.get("annot") is not None else None
+            nc = 0 if an is None else (an.shape[0] if an.ndim == 2 else 1)
+            Cc = min(max(nc, 0), _lib.LDS_MAX_ANNOT)        # (the library refuses a count outside 0 .. 32: only the buffers are capped)
+            self._lds_in = (bm, bu, an)
+            self.lds = dict(raw=np.full((1 + Cc, M), np.nan), l2=np.full((1 + Cc, M), np.nan), mass=np.full((1 + Cc, M), np.nan))
+            desc.lds_on, desc.lds_n_annot, desc.lds_radius, desc.lds_n = 1, nc, int(q.get("radius", 0)), float(q.get("n", 0.0))
+            desc.lds_bp_m = _lib.ptr(bm if bm is not None and len(bm) else None, _ip)
+            desc.lds_bp_u = _lib.ptr(bu if bu is not None and len(bu) else None, _ip)
+            desc.lds_annot = _lib.ptr(an if an is not None and an.size else None, _dp)
+            for key in ("raw", "l2", "mass"):
+                setattr(desc, "out_lds_" + key, self.lds[key].ctypes.data_as(_dp))
         if packed is not None:
             # packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=): rows taken from a row store (dev_ptrs or
             # geno_m/geno_u give its base pointer and stride), optionally 2-bit packed (include/gauss_hip.h)
@@ -507,7 +529,10 @@ class _Win:
 
     def result(self):
         if self.ld_codings is not None:
-            return dict(b11=self.b11, b21=self.b21_ld, status=int(self.status[0]))
+            out = dict(b11=self.b11, b21=self.b21_ld, status=int(self.status[0]))
+            if self.lds is not None:
+                out.update({"lds_" + k: v for k, v in self.lds.items()})
+            return out
         if self.qcat is not None:
             out = dict(r=self.r, num_eig=int(self.num_eig[0]), status=int(self.status[0]))
             if self.b11 is not None:
@@ -609,14 +634,19 @@ def qcat_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, n_head, n_pred, lam=
     return win.result()
 
 
-def ld_window(mode, geno_m, geno_u, pop_off, pop_wgt, lam=0.0, codings=_lib.CODE_ADDITIVE, ctx=None):
+def ld_window(mode, geno_m, geno_u, pop_off, pop_wgt, lam=0.0, codings=_lib.CODE_ADDITIVE, ctx=None, ldscore=None, want_matrices=True):
     """Raw LD export (prep_qcat.cpp:104-132, prep_qcatmix.cpp:136-221): B11 among the measured rows
     (diagonal 1 + lam) and B21 of the geno_u rows against them, one block of rows per coding in
-    `codings` (additive, dominant, recessive)."""
+    `codings` (additive, dominant, recessive).
+    ldscore=dict(radius=bp, bp_m=[M], bp_u=[U], n=sample size, annot=None or [C, M + U]) adds the LD scores of the measured SNPs
+    (include/gauss_hip.h, lds_*), reduced on the device: lds_raw / lds_l2 / lds_mass [1 + C, M], row 0 the plain score, row 1 + c
+    the score stratified by category c.  want_matrices=False passes out_b11 = out_b21 = NULL: b11 / b21 are None and nothing of
+    the matrices comes back; without ldscore it is refused (the window would return nothing)."""
     ctx = ctx or default_context()
     desc = WindowDesc()
     M = len(geno_m)
-    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, np.zeros(M), lam, 1e-5, True, ld_codings=codings)
+    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, np.zeros(M), lam, 1e-5, True, ld_codings=codings, ldscore=ldscore,
+               want_matrices=want_matrices)
     check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
     return win.result()
 
@@ -734,7 +764,9 @@ class Job:
         susie_*, of the first k rows of z_more too (susie_more_*), and the colocalisation of their pairs coloc_* (impute_window).
         susie=dict(L=, ..., group=g[, from_lead=idx]) in two to four windows' dicts: one joint fit across those studies
         (include/gauss_hip.h, xs_group); the first of them is the leader, whose result carries the joint susie_* in its candidate
-        order and xs_V / xs_purity [K, L], xs_n (want_mu=True: xs_mu [K, L, T]); the others pass their map and return z / info."""
+        order and xs_V / xs_purity [K, L], xs_n (want_mu=True: xs_mu [K, L, T]); the others pass their map and return z / info.
+        ldscore=dict(radius=, bp_m=, bp_u=, n=, annot=None) in a window's dict makes it an LD window (as ld_codings= does) whose result
+        carries lds_raw / lds_l2 / lds_mass [1 + C, M] (ld_window); want_matrices=False beside it (and only beside it): no b11 / b21 come back."""
         self.ctx = ctx or default_context()
         n = len(windows)
         # who leads each group, and how many windows it has: the leader's buffers are sized by it
@@ -757,7 +789,8 @@ class Job:
                                   w["pop_off"], w.get("pop_wgt"), w["z1"], w.get("lam", 0.1),
                                   w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed"),
                                   loo=bool(w.get("loo", False)), slct=w.get("slct"), z_more=w.get("z_more"), miss_more=w.get("miss_more"),
-                                  susie=w.get("susie"), prs=w.get("prs")))
+                                  susie=w.get("susie"), prs=w.get("prs"), ldscore=w.get("ldscore"),
+                                  want_matrices=w.get("want_matrices", True)))
         h = C.c_void_p()
         check(self.ctx.lib.gauss_job_create(self.ctx.handle, self.descs, n, 1 if on_device else 0,
                                             C.byref(h)))

@@ -129,6 +129,39 @@ typedef struct gauss_window_desc {
     double* out_z;            /* [U] imputed z / sqrt(info)    (dist.cpp:200)  host pointer        */
     double* out_info;         /* [U] info = |b21 B11^-1 b12|   (dist.cpp:198)  host pointer        */
     int32_t* out_status;      /* [1] GAUSS_ST_* bits                           host pointer        */
+    /* ---- LD scores of the window's measured SNPs (GAUSS_WIN_LD windows only) --------------------------------------
+     * l_j = sum_k r_jk^2 over the window's SNPs within lds_radius bp of SNP j: the input of LD-score regression, reduced on the
+     * device from the B11 / B21 the LD step leaves in HBM -- one number per SNP comes back, not the matrix (an asking window may
+     * pass out_b11 = out_b21 = NULL: then nothing of the matrices is exported).  The SNP being scored is a TARGET: the M measured
+     * rows are the targets, the U geno_u rows are the other reference SNPs.  Rows k = 0 .. M - 1 of the concatenated row space
+     * are the measured rows (r_kj from B11), rows M .. M + U - 1 the geno_u rows (from B21); bp(k) = lds_bp_m[k] or
+     * lds_bp_u[k - M].  Row k CONTRIBUTES to target j iff |bp(k) - lds_bp_m[j]| <= lds_radius.  With a_0(k) = 1 and a_c(k) =
+     * lds_annot[c - 1][k] for the categories c = 1 .. C = lds_n_annot, over the contributing rows:
+     *   raw[c][j]  = sum_k a_c(k) r_kj^2         mass[c][j] = sum_k a_c(k)         (mass[0][j]: the number of contributing rows)
+     *   l2[c][j]   = raw (1 + 1 / (n - 2)) - mass / (n - 2),  n = lds_n: ldsc's r^2 - (1 - r^2) / (n - 2) summed, formed on the
+     *                device in fp64 from the two totals in exactly that expression
+     * The self term is in (it is 1: lambda must be 0).  A row outside the band is NOT READ into the sum (a select, not a product
+     * with 0): a non-finite r outside a target's band does not reach that target.  Inside the band the arithmetic is plain: a NaN
+     * r gives NaN, under a zero weight too.  Order of summation (fixed): rows are cut into chunks of
+     * GAUSS_LDS_CHUNK, first the measured rows from row 0, then the geno_u rows from row M (a chunk never holds rows of both); a
+     * chunk's partial starts at 0 and takes its contributing rows in ascending order, t = r r, then raw += a t, mass += a; the
+     * totals start at 0 and take the chunks' partials in ascending order.  Not contracted, no atomics (k_ldscore.hip).
+     * An LD window raises no status bit, with or without its scores (out_status is 0): a non-finite r shows as NaN in exactly the
+     * targets whose band holds it.  lds_on = 0: off (a zeroed block asks for nothing).  GAUSS_E_INVALID: an asking
+     * window that is not GAUSS_WIN_LD; lambda != 0; u_codings other than additive; lds_bp_m NULL, lds_bp_u NULL with U > 0, a
+     * decreasing list; lds_n not finite or <= 2; lds_radius < 0; lds_n_annot outside 0 .. GAUSS_LDS_MAX_ANNOT; lds_annot NULL
+     * with C > 0; a weight that is not finite; more than 65 535 chunks (4.19 M rows).  Limits: a bp radius only (no cM); the targets are the measured rows.  (The block
+     * sits in front of the two matrices it stands in for: every other field keeps its neighbours.) */
+    int      lds_on;           /* 0 = off, 1 = on                                                                 */
+    int      lds_n_annot;      /* C: annotation categories beside the plain score, 0 .. GAUSS_LDS_MAX_ANNOT       */
+    int64_t  lds_radius;       /* >= 0, in bp                                                                     */
+    const int32_t* lds_bp_m;   /* [M] positions of the measured rows, non-decreasing             host pointer     */
+    const int32_t* lds_bp_u;   /* [U] positions of the geno_u rows, non-decreasing; NULL only when U = 0          */
+    double   lds_n;            /* the sample size of the bias adjustment, finite and > 2                          */
+    const double* lds_annot;   /* [C][M + U] weights, measured rows first; NULL iff C = 0        host pointer     */
+    double*  out_lds_raw;      /* [1 + C][M]                                    host pointer / NULL, optional     */
+    double*  out_lds_l2;       /* [1 + C][M]                                                   optional           */
+    double*  out_lds_mass;     /* [1 + C][M]                                                   optional           */
     double* out_b11;          /* optional [M x M] B11 incl. lambda (symmetric)  host pointer / NULL */
     double* out_b21;          /* optional [U x M] row-major                     host pointer / NULL */
     /* ---- joint fine-mapping across studies: one fit over 2 .. GAUSS_XS_MAX windows of one job (needs susie_L > 0) ----
@@ -477,6 +510,8 @@ typedef struct gauss_window_desc {
 #define GAUSS_PRS_MAX_LAM 32
 #define GAUSS_PRS_MAX_SWEEPS 1000
 #define GAUSS_PRS_MAX_M 4096
+#define GAUSS_LDS_MAX_ANNOT 32          /* annotation categories of a window's LD scores */
+#define GAUSS_LDS_CHUNK 64              /* rows of a chunk of the LD scores' summation order */
 #define GAUSS_SUSIE_MAX_L 32
 #define GAUSS_XS_MAX 4
 #define GAUSS_SUSIE_MAX_SWEEPS 1000

@@ -61,6 +61,8 @@ typedef struct gauss_prepared gauss_prepared; /* one window/gene set after the h
 #define GAUSS_KIND_PREP_RECESSIVE 8
 #define GAUSS_KIND_AFMIX     9
 #define GAUSS_KIND_CPW2      10
+#define GAUSS_KIND_LDSCORE    11   /* gauss_host_dist_ldscore's window (pooled LD) */
+#define GAUSS_KIND_LDSCOREMIX 12   /* gauss_host_distmix_ldscore's window (weighted LD) */
 
 const char* gauss_host_last_error(void);
 
@@ -339,6 +341,41 @@ int gauss_host_distmix_prs(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t en
                            const char* reference_data_file, const char* reference_pop_desc_file,
                            double af1_cutoff, double n, const double* s, int n_s, const double* lam, int n_lam, double tol, int max_sweeps,
                            gauss_table** out);
+/* LD scores of the window: l_j = sum_k r_jk^2 over the panel SNPs within wing_size bp of SNP j, on the ancestry-weighted LD of distmix or
+ * the pooled LD of dist -- the input of LD-score regression for a cohort that has no matching LD-score file to download.  Arguments of
+ * gauss_host_dist / gauss_host_distmix, and their population selection, allele orientation and af1_cutoff; ONE window per call.
+ * The window is a kind of its own (GAUSS_KIND_LDSCORE / GAUSS_KIND_LDSCOREMIX, in both data layers):
+ *   targets         the SNPs that are in both the study file and the panel with bp in [start_bp, end_bp]: the study file is the list of
+ *                   SNPs to score (ldsc's --print-snps); its z column is read and ignored
+ *   reference rows  EVERY other panel SNP of [start_bp - wing_size, end_bp + wing_size] that passes the af1 cutoff -- the panel SNPs
+ *                   the study measured in the wings included (dist()'s unmeasured rows stop at the prediction window; these do not)
+ * The job's one window is a GAUSS_WIN_LD window with the lds_* fields of gauss_window_desc (include/gauss_hip.h: the band, the order
+ * of summation, the bias adjustment) and out_b11 = out_b21 = NULL: the scores are reduced on the device, the matrices never come back.
+ * lds_radius = wing_size, so every target sees its whole neighbourhood.
+ *   n   the sample size of the bias adjustment; <= 0 or NaN: dist -- the selected populations' sample count N; distmix -- Kish's
+ *       effective size (sum w_p)^2 / sum (w_p^2 / n_p) over the populations of non-zero weight, the weights un-normalised as passed.
+ *       Kish's size is this project's convention for a weighted panel, not a measurement
+ * Table: one row per target: rsid chr bp a1 a2 af1ref|af1mix l2 l2_raw n_band (l2_raw = sum r^2, n_band = the rows in the band, l2 =
+ * l2_raw (1 + 1 / (n - 2)) - n_band / (n - 2)).  Named matrix `ldscore` [1 x 4]: n_eff, M (the window's reference rows, targets
+ * included), M_5_50 (those with min(af, 1 - af) > 0.05), radius.
+ * Refused with a message: a window with no target; a window of more than GAUSS_HOST_LDSCORE_MAX_TARGETS targets or
+ * GAUSS_HOST_LDSCORE_MAX_ROWS rows (shorten it).  The two numbers are a budget this call sets for its one job, not a limit of the
+ * kernels: at both of them the window's fp64 matrices are B11 [8 192][8 192] = 0.5 GiB and B21 [122 880][8 192] = 7.5 GiB, the
+ * parked chunk partials 2 048 chunks x 2 x 8 192 doubles = 0.25 GiB -- 8.25 GiB of workspace, which a card that also holds the
+ * panel's rows gives without question; 6 times chr22's largest window in targets, 35 times in rows.  A window beyond them is a
+ * mistyped one far more often than a wanted one, and it is refused on the host before anything is allocated.  Limits: one window per call; a bp radius only, no cM; scores for the study's SNPs
+ * that the panel has; no stratified scores from files (gauss_window_desc.lds_annot through a job). */
+#define GAUSS_HOST_LDSCORE_MAX_TARGETS 8192
+#define GAUSS_HOST_LDSCORE_MAX_ROWS 131072
+int gauss_host_dist_ldscore(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                            const char* study_pop, const char* input_file, const char* reference_index_file,
+                            const char* reference_data_file, const char* reference_pop_desc_file,
+                            double af1_cutoff, double n, gauss_table** out);
+int gauss_host_distmix_ldscore(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, int64_t wing_size,
+                               const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                               const char* input_file, const char* reference_index_file,
+                               const char* reference_data_file, const char* reference_pop_desc_file,
+                               double af1_cutoff, double n, gauss_table** out);
 /* The chi^2 (1 df) threshold of a two-sided p-value: the smallest double chi2 with 2 pnorm(-sqrt(chi2)) < p in the library's own
  * normal tail, found by bisection on the bit pattern -- monotone in p, and exact to the last bit that changes the comparison.
  * p must be positive. */
