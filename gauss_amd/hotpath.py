@@ -273,187 +273,205 @@ PRS_S = (0.2, 0.5, 0.9, 1.0)
 PRS_LAM = tuple(float(v) for v in np.exp(np.linspace(np.log(0.1), np.log(0.001), 20)))
 
 
-class _Win:
-    """Keeps the numpy buffers of one window alive next to its C descriptor."""
+_F, _I, _NAN = np.float64, np.int32, np.nan
+# The riders' output buffers: key -> (dtype, shape, fill of what is not fitted).  A shape names sizes of the window (_Win.sz): M, U,
+# T = M + U; k: slct's max; L: susie's effects, t: the further traits fitted, p: their pairs, K: the group's studies; s, l: the prs
+# grid; c: 1 + the annotation categories -- each as capped by its rider.  _Win._alloc() makes a table's buffers and binds each to
+# out_<prefix>_<key> (_field()); result() returns them as <prefix>_<key>
+_OUT = dict(
+    slct=dict(n=(_I, "1", 0), idx=(_I, "k", -1), zin=(_F, "k", _NAN), joint=(_F, "k", _NAN), zc=(_F, "M", _NAN), var=(_F, "M", _NAN)),
+    cond=dict(z=(_F, "U", _NAN), var=(_F, "U", _NAN)),
+    cs=dict(pip=(_F, "T", _NAN), set=(_I, "T", -1), set_pip=(_F, "T", _NAN), size=(_I, "k", 0), mass=(_F, "k", _NAN), lse=(_F, "k", _NAN)),
+    susie=dict(pip=(_F, "T", _NAN), set=(_I, "T", -1), set_pip=(_F, "T", _NAN), V=(_F, "L", _NAN), lse=(_F, "L", _NAN), mass=(_F, "L", _NAN),
+               purity=(_F, "L", _NAN), size=(_I, "L", 0), kept=(_I, "L", 0), sweeps=(_F, "2", _NAN),
+               alpha=(_F, "L T", _NAN), mu=(_F, "L T", _NAN), lbf=(_F, "L T", _NAN)),                  # (want_alpha, want_lbf)
+    coloc=dict(pp=(_F, "p L L 5", _NAN), hit=(_I, "p L L", -1), hit_pp=(_F, "p L L", _NAN), n=(_I, "p", 0)),
+    xs=dict(V=(_F, "K L", _NAN), purity=(_F, "K L", _NAN), n=(_I, "1", 0), mu=(_F, "K L T", _NAN)),     # (mu: want_mu)
+    prs=dict(beta=(_F, "s l M", _NAN), nnz=(_I, "s l", 0), sweeps=(_I, "s l", 0), delta=(_F, "s l", _NAN), br=(_F, "s l", _NAN),
+             bg=(_F, "s l", _NAN), kkt=(_F, "s l", _NAN)),
+    lds=dict(raw=(_F, "c M", _NAN), l2=(_F, "c M", _NAN), mass=(_F, "c M", _NAN)),
+)
+# the further traits' fits: susie's buffers with a leading [t], and their status bits
+_OUT["susie_more"] = dict({key: (dtype, "t " + shape, fill) for key, (dtype, shape, fill) in _OUT["susie"].items()}, status=(_I, "t", 0))
 
-    def __init__(self, desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig,
-                 want_mats, dev_ptrs=None, qcat=None, ld_codings=None, packed=None, loo=False, slct=None, z_more=None, miss_more=None,
-                 susie=None, prs=None, ldscore=None, want_matrices=True):
-        self.po, self.w = _pops(pop_off, pop_wgt)
-        self.z1 = np.ascontiguousarray(z1, dtype=np.float64)
-        if dev_ptrs is None:
+
+def _field(prefix, key):
+    """The descriptor's name of a buffer: out_<prefix>_<key>, but the further traits' fits and the lbf belong to coloc_* there."""
+    if prefix == "susie_more":
+        return "out_coloc_more_" + key
+    return "out_coloc_lbf" if (prefix, key) == ("susie", "lbf") else f"out_{prefix}_{key}"
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _xs_roles(windows):
+    """Per window of a job: None, or (role, K) of a window whose susie dict names a group -- the job's first window of a group is
+    its "leader", a later one a "peer"; K is the number of the group's windows (the leader's buffers are sized by it)."""
+    groups = [(w.get("susie") or {}).get("group") for w in windows]
+    size = {}
+    for g in groups:
+        if g:
+            size[g] = size.get(g, 0) + 1
+    roles, led = [], set()
+    for g in groups:
+        roles.append(("peer" if g in led else "leader", size[g]) if g else None)
+        led.add(g)
+    return roles
+
+
+class _Win:
+    """Fills the C descriptor of one window and keeps the numpy buffers behind its pointers alive.  `window` is the dict Job
+    documents (unknown keys are ignored); xs is the window's (role, K) in a group across studies (_xs_roles)."""
+
+    def __init__(self, desc, window, want_mats=False, xs=None):
+        w = window
+        self.po, self.w = _pops(w["pop_off"], w.get("pop_wgt"))
+        self.z1 = np.ascontiguousarray(w["z1"], dtype=np.float64)
+        lam, ldscore = w.get("lam", 0.1), w.get("ldscore")
+        M, U = self._geno(desc, w.get("geno_m"), w.get("geno_u"), w.get("dev"), w.get("packed"))
+        self.sz = dict(M=M, U=U, T=M + U)
+        self.ld_codings = w.get("ld_codings")
+        if ldscore is not None and self.ld_codings is None:
+            self.ld_codings = _lib.CODE_ADDITIVE            # LD scores ride on an LD window
+        if not w.get("want_matrices", True) and ldscore is None:        # (such a window would run and return nothing)
+            raise ValueError("want_matrices=False is for an LD window that asks for its LD scores (ldscore=dict(...))")
+        ncode = 1
+        if self.ld_codings is not None:                     # B21 has one block of rows per coding
+            ncode = max(1, bin(int(self.ld_codings)).count("1"))
+            want_mats = bool(w.get("want_matrices", True))  # (False: out_b11 = out_b21 = NULL, nothing of the matrices comes back)
+        self.z, self.info, self.status = np.zeros(U), np.zeros(U), np.zeros(1, dtype=np.int32)
+        self.b11 = np.zeros((M, M)) if want_mats else None
+        self.b21 = np.zeros((ncode * U, M)) if want_mats else None
+        desc.mode = int(w["mode"])
+        desc.n_pop = len(self.po) - 1
+        desc.pop_off, desc.pop_wgt = self.po.ctypes.data_as(_ip), _lib.ptr(self.w, _dp)
+        desc.z1 = self.z1.ctypes.data_as(_dp)
+        desc.lambda_, desc.min_abs_eig = float(lam), float(w.get("min_abs_eig", 1e-5))
+        desc.out_z, desc.out_info, desc.out_status = self.z.ctypes.data_as(_dp), self.info.ctypes.data_as(_dp), self.status.ctypes.data_as(_ip)
+        desc.out_b11, desc.out_b21 = _lib.ptr(self.b11, _dp), _lib.ptr(self.b21, _dp)
+        self.out = {}                                       # prefix -> key -> buffer of the riders asked for (_OUT)
+        self.traits = self.miss = self.qcat = None
+        if w.get("loo"):
+            self._loo(desc)
+        if w.get("slct") is not None:
+            self._slct(desc, w["slct"], lam)
+        if w.get("susie") is not None:
+            self._susie(desc, w["susie"], xs)
+        if w.get("z_more") is not None or w.get("miss_more") is not None:
+            self._traits(desc, w.get("z_more"), w.get("miss_more"))
+        if w.get("prs") is not None:
+            self._prs(desc, w["prs"])
+        if ldscore is not None:
+            self._ldscore(desc, ldscore)
+        if self.ld_codings is not None:                     # an LD window has no Z-scores, in or out
+            desc.kind, desc.u_codings = _lib.WIN_LD, int(self.ld_codings)
+            desc.z1 = desc.out_z = desc.out_info = None
+        if w.get("qcat") is not None:
+            self._qcat(desc, *w["qcat"])
+
+    def _geno(self, desc, geno_m, geno_u, dev, packed):
+        """The genotype rows: host matrices, or dev=(ptr_m, ptr_u, M, U, ld); packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=)
+        makes either the base and stride of a row store whose rows the window names.  Returns M, U."""
+        if dev is None:
             self.gm = _lib.as_u8(geno_m)
             self.gu = _lib.as_u8(geno_u) if geno_u is not None and len(geno_u) else np.zeros((0, 1), np.uint8)
             M, U = self.gm.shape[0], self.gu.shape[0]
-            pm, pu, ld = self.gm.ctypes.data, self.gu.ctypes.data, self.gm.strides[0]
-            if U and self.gu.strides[0] != ld:
+            desc.geno_m, desc.geno_u, desc.ld = self.gm.ctypes.data, self.gu.ctypes.data, self.gm.strides[0]
+            if U and self.gu.strides[0] != desc.ld:
                 raise ValueError("geno_m and geno_u must share a row stride")
         else:
-            pm, pu, M, U, ld = dev_ptrs
-        if packed is not None and packed.get("rows_m") is not None:
-            M = len(packed["rows_m"])                       # matrices are row lists into a store
-            U = len(packed["rows_u"]) if packed.get("rows_u") is not None else 0
-        self.M, self.U = M, U
-        if ldscore is not None and ld_codings is None:
-            ld_codings = _lib.CODE_ADDITIVE                 # LD scores ride on an LD window
-        self.ld_codings = ld_codings
-        if not want_matrices and ldscore is None:           # (such a window would run and return nothing)
-            raise ValueError("want_matrices=False is for an LD window that asks for its LD scores (ldscore=dict(...))")
-        if ld_codings is not None:
-            ncode = max(1, bin(int(ld_codings)).count("1"))
-            want_mats = bool(want_matrices)                 # (False: out_b11 = out_b21 = NULL, nothing of the matrices comes back)
-            self.b21_ld = np.zeros((ncode * U, M)) if want_mats else None
-        self.z = np.zeros(U)
-        self.info = np.zeros(U)
-        self.status = np.zeros(1, dtype=np.int32)
-        self.b11 = np.zeros((M, M)) if want_mats else None
-        self.b21 = np.zeros((U, M)) if want_mats else None
-        desc.mode = int(mode)
-        desc.n_pop = len(self.po) - 1
-        desc.pop_off = self.po.ctypes.data_as(_ip)
-        desc.pop_wgt = _lib.ptr(self.w, _dp)
+            desc.geno_m, desc.geno_u, M, U, desc.ld = dev
+        if packed is not None:
+            desc.geno_format = int(packed.get("fmt", _lib.GENO_U8))
+            self.rows = {key: _i32(packed[key]) for key in ("rows_m", "rows_u", "pop_src_off") if packed.get(key) is not None}
+            for key, a in self.rows.items():
+                setattr(desc, key, a.ctypes.data_as(_ip))
+            if "rows_m" in self.rows:                       # the matrices are row lists into the store
+                M, U = len(self.rows["rows_m"]), len(self.rows.get("rows_u", ()))
         desc.n_measured, desc.n_unmeasured = M, U
-        desc.geno_m, desc.geno_u, desc.ld = pm, pu, ld
-        desc.z1 = self.z1.ctypes.data_as(_dp)
-        desc.lambda_, desc.min_abs_eig = float(lam), float(min_abs_eig)
-        desc.out_z = self.z.ctypes.data_as(_dp)
-        desc.out_info = self.info.ctypes.data_as(_dp)
-        desc.out_status = self.status.ctypes.data_as(_ip)
-        desc.out_b11 = _lib.ptr(self.b11, _dp)
-        desc.out_b21 = _lib.ptr(self.b21, _dp)
-        # leave-one-out re-imputation of the measured SNPs (out_loo_* of gauss_window_desc): [3, M] z, info, t
-        self.loo = np.zeros((3, M)) if loo else None
-        if loo:
-            desc.out_loo_z, desc.out_loo_info, desc.out_loo_t = (self.loo[k].ctypes.data_as(_dp) for k in range(3))
-        # stepwise conditional signal selection (slct_* of gauss_window_desc): slct=dict(max=, chi2_stop=, collin=, forced=)
-        self.slct = None
-        if slct is not None:
-            K = int(slct.get("max", _lib.SLCT_MAX))
-            self.slct = dict(n=np.zeros(1, dtype=np.int32), idx=np.full(max(K, 0), -1, dtype=np.int32), zin=np.full(max(K, 0), np.nan),
-                             joint=np.full(max(K, 0), np.nan), zc=np.full(M, np.nan), var=np.full(M, np.nan),
-                             forced=np.ascontiguousarray(slct.get("forced", ()), dtype=np.int32))
-            s = self.slct
-            desc.slct_max = K
-            desc.slct_chi2_stop = float(slct.get("chi2_stop", 0.0))
-            # "un-ridged r^2 >= collin" (include/gauss_hip.h); min_var_frac= passes the guard as it is
-            desc.slct_min_var_frac = float(slct["min_var_frac"]) if "min_var_frac" in slct else 1.0 - float(slct.get("collin", 0.9)) / (1.0 + float(lam)) ** 2
-            desc.slct_forced, desc.n_slct_forced = _lib.ptr(s["forced"] if len(s["forced"]) else None, _ip), len(s["forced"])
-            desc.out_slct_n, desc.out_slct_idx = s["n"].ctypes.data_as(_ip), s["idx"].ctypes.data_as(_ip)
-            desc.out_slct_zin, desc.out_slct_joint = s["zin"].ctypes.data_as(_dp), s["joint"].ctypes.data_as(_dp)
-            desc.out_slct_zc, desc.out_slct_var = s["zc"].ctypes.data_as(_dp), s["var"].ctypes.data_as(_dp)
-            # unmeasured=True: the imputed SNPs conditioned on the selection (cond_min_var_frac / out_cond_* of gauss_window_desc).  The
-            # ridge does not cap what the signals explain of an imputed SNP: "r^2 >= collin" is 1 - collin here, without (1 + lambda)^2
-            if slct.get("unmeasured"):
-                s["cond_z"], s["cond_var"] = np.full(U, np.nan), np.full(U, np.nan)
-                desc.cond_min_var_frac = float(slct["min_var_frac_u"]) if "min_var_frac_u" in slct else 1.0 - float(slct.get("collin", 0.9))
-                desc.out_cond_z, desc.out_cond_var = s["cond_z"].ctypes.data_as(_dp), s["cond_var"].ctypes.data_as(_dp)
-            # cs=dict(coverage=0.95, prior_var=25.0): a credible set for each selected signal (cs_* of gauss_window_desc).  The unmeasured
-            # candidates' guard is cond_min_var_frac, whether or not unmeasured=True asks for the conditional columns
-            if slct.get("cs") is not None:
-                cs = slct["cs"]
-                T, Kc = M + U, max(K, 0)
-                s.update(cs_pip=np.full(T, np.nan), cs_set=np.full(T, -1, dtype=np.int32), cs_set_pip=np.full(T, np.nan),
-                         cs_size=np.zeros(Kc, dtype=np.int32), cs_mass=np.full(Kc, np.nan), cs_lse=np.full(Kc, np.nan))
-                desc.cond_min_var_frac = float(slct["min_var_frac_u"]) if "min_var_frac_u" in slct else 1.0 - float(slct.get("collin", 0.9))
-                desc.cs_coverage, desc.cs_prior_var = float(cs.get("coverage", 0.95)), float(cs.get("prior_var", 25.0))
-                desc.out_cs_pip, desc.out_cs_set, desc.out_cs_set_pip = s["cs_pip"].ctypes.data_as(_dp), s["cs_set"].ctypes.data_as(_ip), s["cs_set_pip"].ctypes.data_as(_dp)
-                desc.out_cs_size, desc.out_cs_mass, desc.out_cs_lse = s["cs_size"].ctypes.data_as(_ip), s["cs_mass"].ctypes.data_as(_dp), s["cs_lse"].ctypes.data_as(_dp)
-        # multi-causal fine-mapping (susie_* of gauss_window_desc): susie=dict(L=10, coverage=0.95, prior_var=25.0, tol=1e-4,
-        # max_sweeps=100, min_abs_corr=0.5, estimate_var=True, measured_only=False, want_alpha=False)
-        # group=g (> 0) in that dict joins the window to group g of its job, the joint fit across studies (xs_* of gauss_window_desc):
-        # the job's first window of a group is its leader and carries the joint susie_* and xs_V / xs_purity [K, L] / xs_n (K, the
-        # group's windows, is filled in by Job; want_mu=True adds xs_mu [K, L, T]); a later one is a peer, passes from_lead=[T_lead]
-        # (leader candidate -> its own, -1: absent; None: the same index) and returns no susie_*
-        self.susie = self.xs = None
-        self.xs_role = None if susie is None or not susie.get("group") else susie.get("_role", "leader")
-        if susie is not None and self.xs_role == "peer":
-            self.susie_more = self.coloc = None
-            desc.susie_L = int(susie.get("L", 10))
-            desc.susie_coverage, desc.susie_prior_var = float(susie.get("coverage", 0.95)), float(susie.get("prior_var", 25.0))
-            desc.susie_tol, desc.susie_max_sweeps = float(susie.get("tol", 1e-4)), int(susie.get("max_sweeps", 100))
-            desc.susie_min_abs_corr = float(susie.get("min_abs_corr", 0.5))
-            desc.susie_estimate_var = 1 if susie.get("estimate_var", True) else 0
-            desc.susie_measured_only = 1 if susie.get("measured_only", False) else 0
-            desc.coloc_traits_more = int(susie.get("traits", 0))
+        return M, U
+
+    def _alloc(self, desc, prefix, skip=(), bind=True):
+        """The buffers of _OUT[prefix] but `skip`, each bound to its descriptor field with the pointer type of its dtype."""
+        bufs = self.out[prefix] = {}
+        for key, (dtype, shape, fill) in _OUT[prefix].items():
+            if key not in skip:
+                a = bufs[key] = np.full([int(c) if c.isdigit() else self.sz[c] for c in shape.split()], fill, dtype)
+                if bind:
+                    setattr(desc, _field(prefix, key), a.ctypes.data_as(_ip if dtype is _I else _dp))
+        return bufs
+
+    def _loo(self, desc):
+        """loo=True: out_loo_* are the rows of one [3, M] block."""
+        blk = np.zeros((3, self.sz["M"]))
+        self.out["loo"] = dict(z=blk[0], info=blk[1], t=blk[2])
+        desc.out_loo_z, desc.out_loo_info, desc.out_loo_t = (blk[k].ctypes.data_as(_dp) for k in range(3))
+
+    def _slct(self, desc, slct, lam):
+        """slct=dict(...): slct_*, with unmeasured=True out_cond_*, with cs=dict(...) cs_*; either reads cond_min_var_frac."""
+        K, collin = int(slct.get("max", _lib.SLCT_MAX)), float(slct.get("collin", 0.9))
+        self.sz["k"] = max(K, 0)
+        forced = self.forced = np.ascontiguousarray(slct.get("forced", ()), dtype=np.int32)
+        desc.slct_max, desc.slct_chi2_stop = K, float(slct.get("chi2_stop", 0.0))
+        desc.slct_min_var_frac = float(slct["min_var_frac"]) if "min_var_frac" in slct else 1.0 - collin / (1.0 + float(lam)) ** 2
+        desc.slct_forced, desc.n_slct_forced = _lib.ptr(forced if len(forced) else None, _ip), len(forced)
+        self._alloc(desc, "slct")
+        cs = slct.get("cs")
+        if slct.get("unmeasured") or cs is not None:
+            desc.cond_min_var_frac = float(slct["min_var_frac_u"]) if "min_var_frac_u" in slct else 1.0 - collin
+        if slct.get("unmeasured"):
+            self._alloc(desc, "cond")
+        if cs is not None:
+            desc.cs_coverage, desc.cs_prior_var = float(cs.get("coverage", 0.95)), float(cs.get("prior_var", 25.0))
+            self._alloc(desc, "cs")
+
+    def _susie(self, desc, susie, xs):
+        """susie=dict(...): susie_*, with traits=k coloc_traits_more / out_coloc_more_*, with coloc=dict(...) coloc_*; in a group
+        xs_*: a leader (a grouped window nobody gave a role leads a group of 2) also fills out_xs_*, a peer has no buffers."""
+        role, K = (xs or ("leader", 2)) if susie.get("group") else (None, 0)
+        L, k = int(susie.get("L", 10)), int(susie.get("traits", 0))
+        desc.susie_L, desc.coloc_traits_more = L, k         # (uncapped: the library does the refusing, only the buffers are capped)
+        desc.susie_coverage, desc.susie_prior_var = float(susie.get("coverage", 0.95)), float(susie.get("prior_var", 25.0))
+        desc.susie_tol, desc.susie_max_sweeps = float(susie.get("tol", 1e-4)), int(susie.get("max_sweeps", 100))
+        desc.susie_min_abs_corr = float(susie.get("min_abs_corr", 0.5))
+        desc.susie_estimate_var = 1 if susie.get("estimate_var", True) else 0
+        desc.susie_measured_only = 1 if susie.get("measured_only", False) else 0
+        if role:
             desc.xs_group = int(susie["group"])
-            if susie.get("from_lead") is not None:
-                self.xs_map = np.ascontiguousarray(susie["from_lead"], dtype=np.int32)
+            if susie.get("from_lead") is not None:          # (from a leader it is refused by the library: a leader has no map)
+                self.xs_map = _i32(susie["from_lead"])
                 desc.xs_from_lead = self.xs_map.ctypes.data_as(_ip)
-        elif susie is not None:
-            L, T = int(susie.get("L", 10)), M + U
-            Lc = min(max(L, 0), _lib.SUSIE_MAX_L)
-            if self.xs_role == "leader":
-                Kc = min(max(int(susie.get("_K", 2)), 1), _lib.XS_MAX)
-                desc.xs_group = int(susie["group"])
-                x = self.xs = dict(V=np.full((Kc, Lc), np.nan), purity=np.full((Kc, Lc), np.nan), n=np.zeros(1, dtype=np.int32))
-                if susie.get("want_mu"):
-                    x["mu"] = np.full((Kc, Lc, T), np.nan)
-                for key, a in x.items():
-                    setattr(desc, "out_xs_" + key, a.ctypes.data_as(_ip if a.dtype == np.int32 else _dp))
-                if susie.get("from_lead") is not None:      # (refused by the library: a leader has no map)
-                    self.xs_map = np.ascontiguousarray(susie["from_lead"], dtype=np.int32)
-                    desc.xs_from_lead = self.xs_map.ctypes.data_as(_ip)
-            q = self.susie = dict(pip=np.full(T, np.nan), set=np.full(T, -1, dtype=np.int32), set_pip=np.full(T, np.nan),
-                                  V=np.full(Lc, np.nan), lse=np.full(Lc, np.nan), mass=np.full(Lc, np.nan), purity=np.full(Lc, np.nan),
-                                  size=np.zeros(Lc, dtype=np.int32), kept=np.zeros(Lc, dtype=np.int32), sweeps=np.full(2, np.nan))
-            desc.susie_L = L
-            desc.susie_coverage, desc.susie_prior_var = float(susie.get("coverage", 0.95)), float(susie.get("prior_var", 25.0))
-            desc.susie_tol, desc.susie_max_sweeps = float(susie.get("tol", 1e-4)), int(susie.get("max_sweeps", 100))
-            desc.susie_min_abs_corr = float(susie.get("min_abs_corr", 0.5))
-            desc.susie_estimate_var = 1 if susie.get("estimate_var", True) else 0
-            desc.susie_measured_only = 1 if susie.get("measured_only", False) else 0
-            for key in ("pip", "set_pip", "V", "lse", "mass", "purity", "sweeps"):
-                setattr(desc, "out_susie_" + key, q[key].ctypes.data_as(_dp))
-            for key in ("set", "size", "kept"):
-                setattr(desc, "out_susie_" + key, q[key].ctypes.data_as(_ip))
-            if susie.get("want_alpha"):
-                q["alpha"], q["mu"] = np.full((Lc, T), np.nan), np.full((Lc, T), np.nan)
-                desc.out_susie_alpha, desc.out_susie_mu = q["alpha"].ctypes.data_as(_dp), q["mu"].ctypes.data_as(_dp)
-            if susie.get("want_lbf"):
-                q["lbf"] = np.full((Lc, T), np.nan)
-                desc.out_coloc_lbf = q["lbf"].ctypes.data_as(_dp)
-            # traits=k: the first k rows of z_more are fitted as well (coloc_traits_more / out_coloc_more_* of gauss_window_desc);
-            # coloc=dict(p1=1e-4, p2=1e-4, p12=1e-5): the colocalisation of every pair of fitted traits (coloc_* / out_coloc_*)
-            self.susie_more = self.coloc = None
-            k = int(susie.get("traits", 0))
-            kc = min(max(k, 0), _lib.SUSIE_TRAITS_MORE_MAX)
-            desc.coloc_traits_more = k
-            if kc:
-                m = self.susie_more = dict(pip=np.full((kc, T), np.nan), set=np.full((kc, T), -1, dtype=np.int32), set_pip=np.full((kc, T), np.nan),
-                                           V=np.full((kc, Lc), np.nan), lse=np.full((kc, Lc), np.nan), mass=np.full((kc, Lc), np.nan),
-                                           purity=np.full((kc, Lc), np.nan), size=np.zeros((kc, Lc), dtype=np.int32),
-                                           kept=np.zeros((kc, Lc), dtype=np.int32), sweeps=np.full((kc, 2), np.nan),
-                                           status=np.zeros(kc, dtype=np.int32))
-                if susie.get("want_alpha"):
-                    m["alpha"], m["mu"] = np.full((kc, Lc, T), np.nan), np.full((kc, Lc, T), np.nan)
-                if susie.get("want_lbf"):
-                    m["lbf"] = np.full((kc, Lc, T), np.nan)
-                for key, a in m.items():
-                    setattr(desc, "out_coloc_more_" + key, a.ctypes.data_as(_ip if a.dtype == np.int32 else _dp))
-            if susie.get("coloc") is not None:
-                co = susie["coloc"]
-                n_pairs = (kc + 1) * kc // 2
-                c = self.coloc = dict(pp=np.full((n_pairs, Lc, Lc, 5), np.nan), hit=np.full((n_pairs, Lc, Lc), -1, dtype=np.int32),
-                                      hit_pp=np.full((n_pairs, Lc, Lc), np.nan), n=np.zeros(n_pairs, dtype=np.int32))
-                desc.coloc_p1, desc.coloc_p2, desc.coloc_p12 = float(co.get("p1", 1e-4)), float(co.get("p2", 1e-4)), float(co.get("p12", 1e-5))
-                if n_pairs:
-                    for key, a in c.items():
-                        setattr(desc, "out_coloc_" + key, a.ctypes.data_as(_ip if a.dtype == np.int32 else _dp))
-        # further traits on the same window (n_traits_more / z_more / out_z_more of gauss_window_desc): z_more [T, M] -> [T, U]
-        self.z_more = self.out_z_more = None
+        if role == "peer":
+            return
+        t = min(max(k, 0), _lib.SUSIE_TRAITS_MORE_MAX)
+        self.sz.update(L=min(max(L, 0), _lib.SUSIE_MAX_L), t=t, p=(t + 1) * t // 2, K=min(max(int(K), 1), _lib.XS_MAX))
+        skip = [key for key, want in (("alpha", "want_alpha"), ("mu", "want_alpha"), ("lbf", "want_lbf")) if not susie.get(want)]
+        self._alloc(desc, "susie", skip)
+        if t:
+            self._alloc(desc, "susie_more", skip)
+        if susie.get("coloc") is not None:
+            co = susie["coloc"]
+            desc.coloc_p1, desc.coloc_p2, desc.coloc_p12 = float(co.get("p1", 1e-4)), float(co.get("p2", 1e-4)), float(co.get("p12", 1e-5))
+            self._alloc(desc, "coloc", bind=self.sz["p"] > 0)
+        if role == "leader":
+            self._alloc(desc, "xs", () if susie.get("want_mu") else ("mu",))
+
+    def _traits(self, desc, z_more, miss_more):
+        """z_more [T, M]: n_traits_more / z_more / out_z_more [T, U]; miss_more [T, M] beside it: miss_more / out_info_more [T, U] and
+        the compact out_z_miss / out_info_miss, one entry per set mask bit."""
+        M, U, T = self.sz["M"], self.sz["U"], 0
         if z_more is not None:
-            self.z_more = np.ascontiguousarray(z_more, dtype=np.float64)
-            if self.z_more.ndim != 2 or self.z_more.shape[1] != M:
-                raise ValueError(f"z_more must be [T, {M}] (one row per further trait), got {self.z_more.shape}")
-            T = self.z_more.shape[0]
-            self.out_z_more = np.zeros((T, U))
+            zm = np.ascontiguousarray(z_more, dtype=np.float64)
+            if zm.ndim != 2 or zm.shape[1] != M:
+                raise ValueError(f"z_more must be [T, {M}] (one row per further trait), got {zm.shape}")
+            T = zm.shape[0]
+            self.traits = dict(z_more=zm, out=np.zeros((T, U)))
             desc.n_traits_more = T
-            desc.z_more, desc.out_z_more = _lib.ptr(self.z_more if T else None, _dp), _lib.ptr(self.out_z_more if T else None, _dp)
-        # ... that lack some of the measured SNPs (miss_more / out_info_more / out_z_miss / out_info_miss): mask [T, M], non-zero = no score
-        self.miss = None
+            desc.z_more, desc.out_z_more = _lib.ptr(zm if T else None, _dp), _lib.ptr(self.traits["out"] if T else None, _dp)
         if miss_more is not None:
             mask = np.ascontiguousarray(np.asarray(miss_more) != 0, dtype=np.uint8)
-            T = 0 if self.z_more is None else self.z_more.shape[0]
             if T == 0 or mask.shape != (T, M):
                 raise ValueError(f"miss_more must be [{T}, {M}] like z_more, got {mask.shape}")
             n = int(mask.sum())
@@ -461,90 +479,81 @@ class _Win:
             desc.miss_more = mask.ctypes.data
             desc.out_info_more = self.miss["info_more"].ctypes.data_as(_dp)
             desc.out_z_miss, desc.out_info_miss = self.miss["z"].ctypes.data_as(_dp), self.miss["info"].ctypes.data_as(_dp)
-        # polygenic score weights (prs_* of gauss_window_desc): prs=dict(n=, s=PRS_S, lam=PRS_LAM, tol=1e-4, max_sweeps=100)
-        self.prs = None
-        if prs is not None:
-            s = np.ascontiguousarray(PRS_S if prs.get("s") is None else prs["s"], dtype=np.float64).reshape(-1)
-            lm = np.ascontiguousarray(PRS_LAM if prs.get("lam") is None else prs["lam"], dtype=np.float64).reshape(-1)
-            if len(s) == 0:                                 # (prs_n_s = 0 is the descriptor's "off": the library could not refuse it)
-                raise ValueError("prs_n_s = 0: the score takes 1 .. %d shrinkage values" % _lib.PRS_MAX_S)
-            ns, nl = min(len(s), _lib.PRS_MAX_S), min(len(lm), _lib.PRS_MAX_LAM)      # (the library refuses a longer list: only the buffers are capped)
-            q = self.prs = dict(beta=np.full((ns, nl, M), np.nan), nnz=np.zeros((ns, nl), dtype=np.int32), sweeps=np.zeros((ns, nl), dtype=np.int32),
-                                delta=np.full((ns, nl), np.nan), br=np.full((ns, nl), np.nan), bg=np.full((ns, nl), np.nan),
-                                kkt=np.full((ns, nl), np.nan))
-            self._prs_grid = (s, lm)
-            desc.prs_n_s, desc.prs_n_lam = len(s), len(lm)
-            desc.prs_s, desc.prs_lam = _lib.ptr(s if len(s) else None, _dp), _lib.ptr(lm if len(lm) else None, _dp)
-            desc.prs_n, desc.prs_tol, desc.prs_max_sweeps = float(prs.get("n", 0.0)), float(prs.get("tol", 1e-4)), int(prs.get("max_sweeps", 100))
-            for key in ("beta", "delta", "br", "bg", "kkt"):
-                setattr(desc, "out_prs_" + key, q[key].ctypes.data_as(_dp))
-            for key in ("nnz", "sweeps"):
-                setattr(desc, "out_prs_" + key, q[key].ctypes.data_as(_ip))
-        # LD scores of an LD window's measured SNPs (lds_* of gauss_window_desc): ldscore=dict(radius=, bp_m=, bp_u=, n=, annot=None);
-        # annot [C, M + U]: the weights of C annotation categories, the measured rows first
-        self.lds = None
-        if ldscore is not None:
-            q = ldscore
-            bm = np.ascontiguousarray(q["bp_m"], dtype=np.int32).reshape(-1) if q.get("bp_m") is not None else None
-            bu = np.ascontiguousarray(q["bp_u"], dtype=np.int32).reshape(-1) if q.get("bp_u") is not None else None
-            an = np.ascontiguousarray(q["annot"], dtype=np.float64) if q.get("annot") is not None else None
-            nc = 0 if an is None else (an.shape[0] if an.ndim == 2 else 1)
-            Cc = min(max(nc, 0), _lib.LDS_MAX_ANNOT)        # (the library refuses a count outside 0 .. 32: only the buffers are capped)
-            self._lds_in = (bm, bu, an)
-            self.lds = dict(raw=np.full((1 + Cc, M), np.nan), l2=np.full((1 + Cc, M), np.nan), mass=np.full((1 + Cc, M), np.nan))
-            desc.lds_on, desc.lds_n_annot, desc.lds_radius, desc.lds_n = 1, nc, int(q.get("radius", 0)), float(q.get("n", 0.0))
-            desc.lds_bp_m = _lib.ptr(bm if bm is not None and len(bm) else None, _ip)
-            desc.lds_bp_u = _lib.ptr(bu if bu is not None and len(bu) else None, _ip)
-            desc.lds_annot = _lib.ptr(an if an is not None and an.size else None, _dp)
-            for key in ("raw", "l2", "mass"):
-                setattr(desc, "out_lds_" + key, self.lds[key].ctypes.data_as(_dp))
-        if packed is not None:
-            # packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=): rows taken from a row store (dev_ptrs or
-            # geno_m/geno_u give its base pointer and stride), optionally 2-bit packed (include/gauss_hip.h)
-            desc.geno_format = int(packed.get("fmt", _lib.GENO_U8))
-            self._rows = []
-            for key in ("rows_m", "rows_u", "pop_src_off"):
-                a = packed.get(key)
-                if a is not None:
-                    a = np.ascontiguousarray(a, dtype=np.int32)
-                    self._rows.append(a)
-                    setattr(desc, key, a.ctypes.data_as(_ip))
-        if ld_codings is not None:
-            desc.kind = _lib.WIN_LD
-            desc.u_codings = int(ld_codings)
-            desc.out_b21 = _lib.ptr(self.b21_ld, _dp)
-            desc.out_z = desc.out_info = None
-            desc.z1 = None
-        self.qcat = qcat
-        if qcat is not None:
-            n_head, n_pred, eig_cutoff = qcat
-            self.r = np.zeros(n_pred + U)
-            self.num_eig = np.zeros(1, dtype=np.int32)
-            desc.kind = _lib.WIN_QCAT
-            desc.n_head_measured, desc.n_pred_measured = int(n_head), int(n_pred)
-            desc.eig_cutoff = float(eig_cutoff)
-            desc.out_r = self.r.ctypes.data_as(_dp)
-            desc.out_num_eig = self.num_eig.ctypes.data_as(_ip)
-            desc.out_z = desc.out_info = None
+
+    def _prs(self, desc, prs):
+        """prs=dict(...): prs_*; the whole grid goes into the descriptor, the buffers hold what the library accepts at the most."""
+        s = np.ascontiguousarray(PRS_S if prs.get("s") is None else prs["s"], dtype=np.float64).reshape(-1)
+        lm = np.ascontiguousarray(PRS_LAM if prs.get("lam") is None else prs["lam"], dtype=np.float64).reshape(-1)
+        if len(s) == 0:                                     # (prs_n_s = 0 is the descriptor's "off": the library could not refuse it)
+            raise ValueError("prs_n_s = 0: the score takes 1 .. %d shrinkage values" % _lib.PRS_MAX_S)
+        self.prs_grid = (s, lm)
+        self.sz.update(s=min(len(s), _lib.PRS_MAX_S), l=min(len(lm), _lib.PRS_MAX_LAM))
+        desc.prs_n_s, desc.prs_n_lam = len(s), len(lm)
+        desc.prs_s, desc.prs_lam = _lib.ptr(s if len(s) else None, _dp), _lib.ptr(lm if len(lm) else None, _dp)
+        desc.prs_n, desc.prs_tol, desc.prs_max_sweeps = float(prs.get("n", 0.0)), float(prs.get("tol", 1e-4)), int(prs.get("max_sweeps", 100))
+        self._alloc(desc, "prs")
+
+    def _ldscore(self, desc, q):
+        """ldscore=dict(...): lds_*; a count of categories outside 0 .. LDS_MAX_ANNOT is the library's to refuse."""
+        bm, bu = (None if q.get(key) is None else _i32(q[key]).reshape(-1) for key in ("bp_m", "bp_u"))
+        an = np.ascontiguousarray(q["annot"], dtype=np.float64) if q.get("annot") is not None else None
+        nc = 0 if an is None else (an.shape[0] if an.ndim == 2 else 1)
+        self.lds_in = (bm, bu, an)
+        self.sz["c"] = 1 + min(max(nc, 0), _lib.LDS_MAX_ANNOT)
+        desc.lds_on, desc.lds_n_annot, desc.lds_radius, desc.lds_n = 1, nc, int(q.get("radius", 0)), float(q.get("n", 0.0))
+        desc.lds_bp_m = _lib.ptr(bm if bm is not None and len(bm) else None, _ip)
+        desc.lds_bp_u = _lib.ptr(bu if bu is not None and len(bu) else None, _ip)
+        desc.lds_annot = _lib.ptr(an if an is not None and an.size else None, _dp)
+        self._alloc(desc, "lds")
+
+    def _qcat(self, desc, n_head, n_pred, eig_cutoff):
+        """qcat=(n_head, n_pred, eig_cutoff): a QCAT window returns r and num_eig, no Z-scores."""
+        self.qcat = (n_head, n_pred, eig_cutoff)
+        self.r, self.num_eig = np.zeros(n_pred + self.sz["U"]), np.zeros(1, dtype=np.int32)
+        desc.kind = _lib.WIN_QCAT
+        desc.n_head_measured, desc.n_pred_measured, desc.eig_cutoff = int(n_head), int(n_pred), float(eig_cutoff)
+        desc.out_r, desc.out_num_eig = self.r.ctypes.data_as(_dp), self.num_eig.ctypes.data_as(_ip)
+        desc.out_z = desc.out_info = None
 
     def result(self):
+        st = int(self.status[0])
         if self.ld_codings is not None:
-            out = dict(b11=self.b11, b21=self.b21_ld, status=int(self.status[0]))
-            if self.lds is not None:
-                out.update({"lds_" + k: v for k, v in self.lds.items()})
+            out = dict(b11=self.b11, b21=self.b21, status=st)
+            out.update(("lds_" + key, a) for key, a in self.out.get("lds", {}).items())
             return out
-        if self.qcat is not None:
-            out = dict(r=self.r, num_eig=int(self.num_eig[0]), status=int(self.status[0]))
-            if self.b11 is not None:
-                out["b11"], out["b21"] = self.b11, self.b21
-            return out
-        out = dict(z=self.z, info=self.info, status=int(self.status[0]))
+        out = dict(z=self.z, info=self.info, status=st) if self.qcat is None else dict(r=self.r, num_eig=int(self.num_eig[0]), status=st)
         if self.b11 is not None:
             out["b11"], out["b21"] = self.b11, self.b21
-        if self.loo is not None:
-            out["loo_z"], out["loo_info"], out["loo_t"] = self.loo[0], self.loo[1], self.loo[2]
-        if self.out_z_more is not None:
-            out["z_more"] = self.out_z_more
+        if self.qcat is None:
+            if self.out:
+                self._riders(out)
+            if self.traits is not None:
+                self._traits_result(out)
+        return out
+
+    def _riders(self, out):
+        """Every buffer as <prefix>_<key>, then what is not the buffer as it stands."""
+        for prefix, bufs in self.out.items():
+            for key, a in bufs.items():
+                out[f"{prefix}_{key}"] = a
+        if "slct" in self.out:                              # per signal: cut to the n found (copies), the buffers under *_raw
+            n = out["slct_n"] = int(self.out["slct"]["n"][0])
+            for prefix, keys in (("slct", ("idx", "zin", "joint")), ("cs", ("size", "mass", "lse"))):
+                bufs = self.out.get(prefix)
+                if bufs is not None:
+                    out[prefix + "_raw"] = {key: bufs[key] for key in keys}
+                    out.update((f"{prefix}_{key}", bufs[key][:n].copy()) for key in keys)
+        if "susie" in self.out:                             # sweeps = [sweeps run (NaN: not fitted), last change]
+            sw = self.out["susie"]["sweeps"]
+            out.update(susie_sweeps=int(sw[0]) if np.isfinite(sw[0]) else 0, susie_delta=float(sw[1]))
+            if "susie_more" in self.out:
+                sw = self.out["susie_more"]["sweeps"]
+                out.update(susie_more_sweeps=np.where(np.isfinite(sw[:, 0]), sw[:, 0], 0).astype(np.int64), susie_more_delta=sw[:, 1].copy())
+            if "xs" in self.out:
+                out["xs_n"] = int(self.out["xs"]["n"][0])
+
+    def _traits_result(self, out):
+        out["z_more"] = self.traits["out"]
         if self.miss is not None:
             # the compact arrays hold one entry per set mask bit in mask order: scattered here, NaN where nothing is missing
             m = self.miss
@@ -553,33 +562,15 @@ class _Win:
             out["info_more"] = m["info_more"]
             out["z_miss"], out["info_miss"] = np.full(at.shape, np.nan), np.full(at.shape, np.nan)
             out["z_miss"][at], out["info_miss"][at] = m["z"][:n], m["info"][:n]
-        if self.slct is not None:
-            s, n = self.slct, int(self.slct["n"][0])
-            out.update(slct_n=n, slct_idx=s["idx"][:n].copy(), slct_zin=s["zin"][:n].copy(), slct_joint=s["joint"][:n].copy(),
-                       slct_zc=s["zc"], slct_var=s["var"], slct_raw=dict(idx=s["idx"], zin=s["zin"], joint=s["joint"]))
-            if "cond_z" in s:
-                out.update(cond_z=s["cond_z"], cond_var=s["cond_var"])
-            if "cs_pip" in s:
-                out.update(cs_pip=s["cs_pip"], cs_set=s["cs_set"], cs_set_pip=s["cs_set_pip"], cs_size=s["cs_size"][:n].copy(),
-                           cs_mass=s["cs_mass"][:n].copy(), cs_lse=s["cs_lse"][:n].copy(),
-                           cs_raw=dict(size=s["cs_size"], mass=s["cs_mass"], lse=s["cs_lse"]))
-        if self.susie is not None:
-            q = self.susie
-            out.update({"susie_" + k: v for k, v in q.items() if k != "sweeps"})
-            out.update(susie_sweeps=int(q["sweeps"][0]) if np.isfinite(q["sweeps"][0]) else 0, susie_delta=float(q["sweeps"][1]))
-            if self.susie_more is not None:
-                m = self.susie_more
-                out.update({"susie_more_" + k: v for k, v in m.items() if k != "sweeps"})
-                out.update(susie_more_sweeps=np.where(np.isfinite(m["sweeps"][:, 0]), m["sweeps"][:, 0], 0).astype(np.int64),
-                           susie_more_delta=m["sweeps"][:, 1].copy())
-            if self.coloc is not None:
-                out.update({"coloc_" + k: v for k, v in self.coloc.items()})
-            if self.xs is not None:
-                out.update({"xs_" + k: v for k, v in self.xs.items() if k != "n"})
-                out["xs_n"] = int(self.xs["n"][0])
-        if self.prs is not None:
-            out.update({"prs_" + k: v for k, v in self.prs.items()})
-        return out
+
+
+def _one_window(ctx, window, want_mats=False):
+    """One window on its own: descriptor, buffers, gauss_impute_window, result()."""
+    ctx = ctx or default_context()
+    desc = WindowDesc()
+    win = _Win(desc, window, want_mats)
+    check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
+    return win.result()
 
 
 def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_eig=1e-5,
@@ -589,10 +580,13 @@ def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_e
     standardised residual (include/gauss_hip.h, out_loo_*).
     slct=dict(max=K, chi2_stop=, collin=0.9, forced=[...]) adds the stepwise conditional signal selection among the measured SNPs
     (include/gauss_hip.h, slct_*): slct_n, slct_idx / slct_zin / slct_joint [n] in order of entry, slct_zc / slct_var [M]; status bit
-    8 when a forced SNP failed the collinearity guard.  unmeasured=True in that dict (with min_var_frac_u= to pass their guard as it
-    is) adds cond_z / cond_var [U]: the imputed SNPs conditioned on the selected ones (include/gauss_hip.h, out_cond_*).
+    8 when a forced SNP failed the collinearity guard.  The guard is "un-ridged r^2 >= collin"; min_var_frac= passes it as it is.
+    unmeasured=True in that dict (with min_var_frac_u= to pass their guard as it
+    is) adds cond_z / cond_var [U]: the imputed SNPs conditioned on the selected ones (include/gauss_hip.h, out_cond_*).  The ridge
+    does not cap what the signals explain of an imputed SNP: their "r^2 >= collin" is 1 - collin, without (1 + lambda)^2.
     cs=dict(coverage=0.95, prior_var=25.0) in that dict adds a credible set for each selected signal (include/gauss_hip.h, out_cs_*):
-    cs_pip / cs_set / cs_set_pip [M + U] per candidate, the measured SNPs first, and cs_size / cs_mass / cs_lse [n] per signal.
+    cs_pip / cs_set / cs_set_pip [M + U] per candidate, the measured SNPs first, and cs_size / cs_mass / cs_lse [n] per signal.  The
+    unmeasured candidates' guard is that of unmeasured=True, whether or not it asks for the conditional columns.
     z_more [T, M] (T <= 63) adds z_more [T, U]: the Z-scores of T further traits measured at the same SNPs, imputed from the same LD
     and the same factorisation (include/gauss_hip.h, n_traits_more); row t is what z would be with z1 = z_more[t].
     miss_more [T, M] (non-zero: further trait t has no score at measured SNP m; at most 32 per trait, 128 distinct per window) makes row t
@@ -613,12 +607,9 @@ def impute_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam=0.1, min_abs_e
     (include/gauss_hip.h, prs_*): lassosum's elastic net on the window's own LD, one warm-started chain over lam per s (defaults: PRS_S,
     PRS_LAM, lassosum's grid).  prs_beta [n_s, n_lam, M], prs_nnz / prs_sweeps / prs_delta / prs_br / prs_bg / prs_kkt [n_s, n_lam]; the
     in-sample predicted R^2 of a cell is prs_br^2 / prs_bg.  Status bit 64: some cell ran its sweeps out."""
-    ctx = ctx or default_context()
-    desc = WindowDesc()
-    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, min_abs_eig, want_mats, loo=loo, slct=slct, z_more=z_more,
-               miss_more=miss_more, susie=susie, prs=prs)
-    check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
-    return win.result()
+    return _one_window(ctx, dict(mode=mode, geno_m=geno_m, geno_u=geno_u, pop_off=pop_off, pop_wgt=pop_wgt, z1=z1, lam=lam,
+                                 min_abs_eig=min_abs_eig, loo=loo, slct=slct, z_more=z_more, miss_more=miss_more, susie=susie, prs=prs),
+                       want_mats)
 
 
 def qcat_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, n_head, n_pred, lam=0.1, eig_cutoff=0.01,
@@ -626,12 +617,8 @@ def qcat_window(mode, geno_m, geno_u, pop_off, pop_wgt, z1, n_head, n_pred, lam=
     """run_qcat (mode 0, qcat.cpp:134-262) / run_qcatmix (mode 1, qcatmix.cpp): correlation r between the
     whitened measured Z-scores and the whitened LD column of every tested SNP -- first the n_pred measured
     SNPs that follow the n_head left-wing ones, then the unmeasured SNPs -- plus CountPC's num_eig."""
-    ctx = ctx or default_context()
-    desc = WindowDesc()
-    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, z1, lam, 1e-5, want_mats,
-               qcat=(n_head, n_pred, eig_cutoff))
-    check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
-    return win.result()
+    return _one_window(ctx, dict(mode=mode, geno_m=geno_m, geno_u=geno_u, pop_off=pop_off, pop_wgt=pop_wgt, z1=z1, lam=lam,
+                                 qcat=(n_head, n_pred, eig_cutoff)), want_mats)
 
 
 def ld_window(mode, geno_m, geno_u, pop_off, pop_wgt, lam=0.0, codings=_lib.CODE_ADDITIVE, ctx=None, ldscore=None, want_matrices=True):
@@ -640,15 +627,11 @@ def ld_window(mode, geno_m, geno_u, pop_off, pop_wgt, lam=0.0, codings=_lib.CODE
     `codings` (additive, dominant, recessive).
     ldscore=dict(radius=bp, bp_m=[M], bp_u=[U], n=sample size, annot=None or [C, M + U]) adds the LD scores of the measured SNPs
     (include/gauss_hip.h, lds_*), reduced on the device: lds_raw / lds_l2 / lds_mass [1 + C, M], row 0 the plain score, row 1 + c
-    the score stratified by category c.  want_matrices=False passes out_b11 = out_b21 = NULL: b11 / b21 are None and nothing of
+    the score stratified by category c; annot holds the weights of the C annotation categories, the measured SNPs' columns first.
+    want_matrices=False passes out_b11 = out_b21 = NULL: b11 / b21 are None and nothing of
     the matrices comes back; without ldscore it is refused (the window would return nothing)."""
-    ctx = ctx or default_context()
-    desc = WindowDesc()
-    M = len(geno_m)
-    win = _Win(desc, mode, geno_m, geno_u, pop_off, pop_wgt, np.zeros(M), lam, 1e-5, True, ld_codings=codings, ldscore=ldscore,
-               want_matrices=want_matrices)
-    check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))
-    return win.result()
+    return _one_window(ctx, dict(mode=mode, geno_m=geno_m, geno_u=geno_u, pop_off=pop_off, pop_wgt=pop_wgt, z1=np.zeros(len(geno_m)),
+                                 lam=lam, ld_codings=codings, ldscore=ldscore, want_matrices=want_matrices), True)
 
 
 class PinnedArray:
@@ -753,44 +736,24 @@ class Job:
     """A batch of windows sharing every launch (gauss_job_*)."""
 
     def __init__(self, windows, ctx=None, on_device=False, want_mats=False):
-        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig, loo, slct, z_more, miss_more, susie, prs])
-        or, with on_device=True, dicts carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.
-        loo=True in a window's dict: its result carries loo_z, loo_info, loo_t (leave-one-out values of its measured SNPs).
-        slct=dict(max=, chi2_stop=, collin=, forced=[, unmeasured=True][, cs=dict(coverage=, prior_var=)]) in a window's dict: its
-        result carries the signal selection (and the imputed SNPs conditioned on it, and the signals' credible sets; impute_window).
-        z_more=[T, M] in a window's dict: its result carries z_more [T, U], the further traits' imputed Z-scores (impute_window).
-        miss_more=[T, M] beside it: the SNPs each further trait lacks; the result carries info_more, z_miss, info_miss (impute_window).
-        susie=dict(L=, ...[, traits=k][, coloc=dict(p1=, p2=, p12=)]) in a window's dict: its result carries the multi-causal fine-mapping
-        susie_*, of the first k rows of z_more too (susie_more_*), and the colocalisation of their pairs coloc_* (impute_window).
-        susie=dict(L=, ..., group=g[, from_lead=idx]) in two to four windows' dicts: one joint fit across those studies
-        (include/gauss_hip.h, xs_group); the first of them is the leader, whose result carries the joint susie_* in its candidate
-        order and xs_V / xs_purity [K, L], xs_n (want_mu=True: xs_mu [K, L, T]); the others pass their map and return z / info.
-        ldscore=dict(radius=, bp_m=, bp_u=, n=, annot=None) in a window's dict makes it an LD window (as ld_codings= does) whose result
-        carries lds_raw / lds_l2 / lds_mass [1 + C, M] (ld_window); want_matrices=False beside it (and only beside it): no b11 / b21 come back."""
+        """windows: list of dicts(mode, geno_m, geno_u, pop_off, pop_wgt, z1[, lam, min_abs_eig]) or, with on_device=True, dicts
+        carrying dev=(ptr_m, ptr_u, M, U, ld) instead of arrays.  Further keys of a window's dict:
+        loo, slct, z_more, miss_more, susie, prs: the riders of impute_window, with the same meaning and the same result keys.
+        qcat=(n_head, n_pred, eig_cutoff): a QCAT window (qcat_window).
+        ld_codings=mask: an LD window; ldscore=dict(...) makes a window one too and adds its LD scores; want_matrices=False beside
+        ldscore (and only beside it): no b11 / b21 come back (ld_window).
+        packed=dict(fmt=GENO_*, rows_m=, rows_u=, pop_src_off=): the rows are taken from a row store, optionally 2-bit packed
+        (include/gauss_hip.h); dev or geno_m / geno_u give its base pointer and stride.
+        susie=dict(L=, ..., group=g[, from_lead=idx]) (g > 0) in two to four windows' dicts: one joint fit across those studies
+        (include/gauss_hip.h, xs_group).  The job's first window of a group is its leader: its result carries the joint susie_* in its
+        candidate order and xs_V / xs_purity [K, L], xs_n, K being the group's windows (want_mu=True: xs_mu [K, L, T]).  A later one is
+        a peer: it passes from_lead=[T_lead] (leader candidate -> its own, -1: absent; None: the same index) and returns z / info
+        and no susie_*."""
         self.ctx = ctx or default_context()
         n = len(windows)
-        # who leads each group, and how many windows it has: the leader's buffers are sized by it
-        seen = {}
-        for w in windows:
-            g = (w.get("susie") or {}).get("group")
-            if g:
-                seen[g] = seen.get(g, 0) + 1
-        first = set()
-        windows = [dict(w) for w in windows]
-        for w in windows:
-            g = (w.get("susie") or {}).get("group")
-            if g:
-                w["susie"] = dict(w["susie"], _role="peer" if g in first else "leader", _K=seen[g])
-                first.add(g)
+        roles = _xs_roles(windows)
         self.descs = (WindowDesc * n)()
-        self.wins = []
-        for i, w in enumerate(windows):
-            self.wins.append(_Win(self.descs[i], w["mode"], w.get("geno_m"), w.get("geno_u"),
-                                  w["pop_off"], w.get("pop_wgt"), w["z1"], w.get("lam", 0.1),
-                                  w.get("min_abs_eig", 1e-5), want_mats, w.get("dev"), w.get("qcat"), w.get("ld_codings"), w.get("packed"),
-                                  loo=bool(w.get("loo", False)), slct=w.get("slct"), z_more=w.get("z_more"), miss_more=w.get("miss_more"),
-                                  susie=w.get("susie"), prs=w.get("prs"), ldscore=w.get("ldscore"),
-                                  want_matrices=w.get("want_matrices", True)))
+        self.wins = [_Win(self.descs[i], w, want_mats, roles[i]) for i, w in enumerate(windows)]
         h = C.c_void_p()
         check(self.ctx.lib.gauss_job_create(self.ctx.handle, self.descs, n, 1 if on_device else 0,
                                             C.byref(h)))

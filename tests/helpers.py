@@ -29,6 +29,31 @@ def split_window(panel, n_measured, seed=3):
     return np.ascontiguousarray(panel["G"][m]), np.ascontiguousarray(panel["G"][u]), z1
 
 
+def desc_layout(fields, macros=()):
+    """What the C compiler makes of include/gauss_hip.h: (sizeof(gauss_window_desc), [offsetof of each of `fields`], [the integer value
+    of each of `macros`]), read from a small program built with g++ -std=c++17 -I include.  Skips the test when g++ is missing."""
+    import os
+    import shutil
+    import subprocess
+    import tempfile
+
+    import pytest
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with tempfile.TemporaryDirectory() as tmp:
+        src, exe = os.path.join(tmp, "sz.cpp"), os.path.join(tmp, "sz")
+        with open(src, "w") as fh:
+            fh.write('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
+                     'int main() { std::printf("%zu", sizeof(gauss_window_desc));\n'
+                     + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in fields)
+                     + "".join(f'std::printf(" %lld", (long long)({m}));\n' for m in macros) + '}\n')
+        subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(root, "include"), src, "-o", exe])
+        size, *rest = (int(x) for x in subprocess.check_output([exe]).split())
+    return size, rest[:len(fields)], rest[len(fields):]
+
+
 def relerr(a, b, floor=1e-300):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor))) if a.size else 0.0

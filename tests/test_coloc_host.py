@@ -11,13 +11,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import desc_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MORE = ["pip", "set", "set_pip", "V", "lse", "mass", "purity", "size", "kept", "alpha", "mu", "lbf", "sweeps", "status"]
 COLOC_FIELDS = ["coloc_traits_more", "coloc_p1", "coloc_p2", "coloc_p12", "out_coloc_lbf"] + ["out_coloc_more_" + k for k in MORE] + \
                ["out_coloc_pp", "out_coloc_hit", "out_coloc_hit_pp", "out_coloc_n"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("coloc_traits_more")
@@ -25,14 +27,8 @@ def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_
     assert [n for n in names if "coloc_" in n] == COLOC_FIELDS
     gxx = shutil.which("g++")
     assert gxx is not None, "g++ is needed to check the descriptor against the header"
-    src = tmp_path / "sz.cpp"
     fields = ["out_num_eig"] + COLOC_FIELDS + ["u_codings", "susie_L"]
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu %d", sizeof(gauss_window_desc), GAUSS_SUSIE_TRAITS_MORE_MAX);\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in fields) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, cap, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, (cap,) = desc_layout(fields, ["GAUSS_SUSIE_TRAITS_MORE_MAX"])
     assert ctypes.sizeof(_lib.WindowDesc) == size and cap == _lib.SUSIE_TRAITS_MORE_MAX == 7
     assert [getattr(_lib.WindowDesc, n).offset for n in fields] == offs
     # an int with its padding, then 3 + 1 + 14 + 4 eight-byte fields, then u_codings and susie_L in one word
@@ -58,8 +54,8 @@ def test_integration_snippet_compiles_against_the_header():
 def test_hotpath_sets_the_fields():
     from gauss_amd import _lib, hotpath
     gm, gu = np.zeros((5, 8), dtype=np.uint8), np.zeros((3, 8), dtype=np.uint8)
-    mk = lambda susie, z_more=None: (lambda d: (d, hotpath._Win(d, 0, gm, gu, [0, 8], None, np.zeros(5), 0.1, 1e-5, False, z_more=z_more,
-                                                               susie=susie)))(_lib.WindowDesc())
+    mk = lambda susie, z_more=None: (lambda d: (d, hotpath._Win(d, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(5), lam=0.1, z_more=z_more,
+                                                                    susie=susie))))(_lib.WindowDesc())
     d, w = mk(dict())                                  # the fit of trait 1 alone asks for nothing new
     assert d.coloc_traits_more == 0 and d.coloc_p12 == 0.0 and not any(getattr(d, n) for n in COLOC_FIELDS if n.startswith("out_"))
     assert "susie_more_pip" not in w.result() and "coloc_pp" not in w.result() and "susie_lbf" not in w.result()
@@ -75,7 +71,7 @@ def test_hotpath_sets_the_fields():
     d, w = mk(dict(traits=1, coloc=dict(p1=1e-3, p2=2e-3, p12=5e-4)), np.zeros((1, 5)))
     assert (d.coloc_p1, d.coloc_p2, d.coloc_p12) == (1e-3, 2e-3, 5e-4) and not d.out_coloc_lbf and not d.out_coloc_more_alpha
     d, w = mk(dict(traits=9), np.zeros((9, 5)))        # the library refuses; the buffers stay at the cap
-    assert d.coloc_traits_more == 9 and w.susie_more["pip"].shape == (_lib.SUSIE_TRAITS_MORE_MAX, 8)
+    assert d.coloc_traits_more == 9 and w.result()["susie_more_pip"].shape == (_lib.SUSIE_TRAITS_MORE_MAX, 8)
 
 
 def test_the_reference_s_pairs_are_in_the_documented_order():

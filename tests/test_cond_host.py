@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from cond_ref import cond_by_augmented, cond_by_definition, cond_by_residual, window_mats
-from helpers import small_panel, split_window
+from helpers import desc_layout, small_panel, split_window
 from slct_ref import min_var_frac, planted_z, slct_by_definition
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,23 +116,14 @@ def test_unmeasured_twin_of_an_isolated_selected_snp_has_nothing_left():
 COND_FIELDS = ["cond_min_var_frac", "out_cond_z", "out_cond_var"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("out_slct_var")
     assert names[at + 1: at + 4] == COND_FIELDS and names[at + 4] == "miss_more"
     assert [n for n in names if "cond" in n] == COND_FIELDS and not any("slct" in n for n in COND_FIELDS)
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
     fields = ["out_slct_var"] + COND_FIELDS + ["miss_more"]
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu", sizeof(gauss_window_desc));\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in fields) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, _ = desc_layout(fields)
     assert ctypes.sizeof(_lib.WindowDesc) == size
     assert [getattr(_lib.WindowDesc, n).offset for n in fields] == offs
     assert offs == sorted(offs) and offs[4] - offs[1] == 24          # three 8-byte fields, nothing between them and miss_more
@@ -168,7 +159,7 @@ def test_integration_snippet_compiles_against_the_header():
 def test_hotpath_sets_the_fields_and_the_guard_without_the_ridge_correction():
     from gauss_amd import _lib, hotpath
     gm, gu = np.zeros((5, 8), dtype=np.uint8), np.zeros((3, 8), dtype=np.uint8)
-    mk = lambda slct: (lambda d: (d, hotpath._Win(d, 0, gm, gu, [0, 8], None, np.zeros(5), 0.1, 1e-5, False, slct=slct)))(_lib.WindowDesc())
+    mk = lambda slct: (lambda d: (d, hotpath._Win(d, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(5), lam=0.1, slct=slct))))(_lib.WindowDesc())
     d, w = mk(dict(max=4, chi2_stop=3.0, unmeasured=True))
     assert d.slct_max == 4 and d.out_cond_z and d.out_cond_var and abs(d.cond_min_var_frac - 0.1) < 1e-15
     assert abs(d.slct_min_var_frac - (1 - 0.9 / 1.21)) < 1e-15

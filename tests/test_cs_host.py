@@ -10,27 +10,20 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import desc_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS_FIELDS = ["cs_coverage", "cs_prior_var", "out_cs_pip", "out_cs_set", "out_cs_set_pip", "out_cs_size", "out_cs_mass", "out_cs_lse"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("cs_coverage")
     assert names[at: at + 8] == CS_FIELDS and names[at + 8] == "slct_max" and names[at - 1] == "pop_src_off"
     assert [n for n in names if "cs_" in n] == CS_FIELDS and names[-3:] == ["out_loo_z", "out_loo_info", "out_loo_t"]
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
     fields = ["pop_src_off"] + CS_FIELDS + ["slct_max"]
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu", sizeof(gauss_window_desc));\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in fields) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, _ = desc_layout(fields)
     assert ctypes.sizeof(_lib.WindowDesc) == size
     assert [getattr(_lib.WindowDesc, n).offset for n in fields] == offs
     assert offs == sorted(offs) and offs[-1] - offs[1] == 64          # eight 8-byte fields, nothing between them and slct_max
@@ -67,7 +60,7 @@ def test_integration_snippet_compiles_against_the_header():
 def test_hotpath_sets_the_fields_and_both_guards():
     from gauss_amd import _lib, hotpath
     gm, gu = np.zeros((5, 8), dtype=np.uint8), np.zeros((3, 8), dtype=np.uint8)
-    mk = lambda slct: (lambda d: (d, hotpath._Win(d, 0, gm, gu, [0, 8], None, np.zeros(5), 0.1, 1e-5, False, slct=slct)))(_lib.WindowDesc())
+    mk = lambda slct: (lambda d: (d, hotpath._Win(d, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(5), lam=0.1, slct=slct))))(_lib.WindowDesc())
     d, w = mk(dict(max=4, chi2_stop=3.0, cs=dict()))
     assert d.slct_max == 4 and d.cs_coverage == 0.95 and d.cs_prior_var == 25.0
     assert all((d.out_cs_pip, d.out_cs_set, d.out_cs_set_pip, d.out_cs_size, d.out_cs_mass, d.out_cs_lse))

@@ -249,7 +249,7 @@ def _refused(ctx, text, mode=0, lam=0.0, codings=1, kind=None, n_annot=None, **c
     q = dict(radius=1000, bp_m=p["bp"][mi], bp_u=p["bp"][ui], n=200.0, annot=None)
     q.update(change)
     desc = hotpath.WindowDesc()
-    win = hotpath._Win(desc, mode, gm, gu, p["off"], None, np.zeros(20), lam, 1e-5, True, ld_codings=codings, ldscore=q)
+    win = hotpath._Win(desc, dict(mode=mode, geno_m=gm, geno_u=gu, pop_off=p["off"], z1=np.zeros(20), lam=lam, ld_codings=codings, ldscore=q), True)
     if n_annot is not None:                            # a count that disagrees with the weights passed
         desc.lds_n_annot = n_annot
     if kind is not None:                               # an imputation window that asks
@@ -292,12 +292,12 @@ def test_more_chunks_than_a_grid_holds_are_refused(ctx):
     U = 65534 * CHUNK + 1
     gm, gu = np.array([[0, 1, 2, 1, 0, 2, 1, 1]], dtype=np.uint8), np.ones((U, 8), dtype=np.uint8)
     desc = hotpath.WindowDesc()
-    win = hotpath._Win(desc, 0, gm, gu, [0, 8], None, np.zeros(1), 0.0, 1e-5, True,
-                       ldscore=dict(radius=10, bp_m=[5], bp_u=np.arange(U, dtype=np.int32), n=8.0), want_matrices=False)
+    win = hotpath._Win(desc, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(1), lam=0.0,
+                                  ldscore=dict(radius=10, bp_m=[5], bp_u=np.arange(U, dtype=np.int32), n=8.0), want_matrices=False), True)
     rc = ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc))
     msg = ctx.lib.gauss_last_error().decode()
     assert rc == -1 and "1 + 4194177 rows make 65536 chunks of 64; a window takes at most 65535" in msg, (rc, msg)
-    assert win.lds is not None and np.all(np.isnan(win.lds["raw"]))
+    assert "lds_raw" in win.result() and np.all(np.isnan(win.result()["lds_raw"]))
 
 
 def test_a_job_in_which_nobody_asks_keeps_its_bits(ctx):

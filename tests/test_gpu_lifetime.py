@@ -208,7 +208,7 @@ def test_streamed_window_call_strided_rows_and_error_paths(ctx, monkeypatch):
     def call(stream, a=gm, b=gu, ld=None, mode=1):
         monkeypatch.setenv("GAUSS_STREAM_WINDOW", "1" if stream else "0")
         desc = _lib.WindowDesc()
-        win = hotpath._Win(desc, mode, gm, gu, off, w, z1, 0.1, 1e-5, False)
+        win = hotpath._Win(desc, dict(mode=mode, geno_m=gm, geno_u=gu, pop_off=off, pop_wgt=w, z1=z1, lam=0.1))
         if ld is not None:
             desc.geno_m, desc.geno_u, desc.ld = a.ctypes.data, b.ctypes.data, ld
         _lib.check(ctx.lib.gauss_impute_window(ctx.handle, C.byref(desc)))

@@ -428,7 +428,7 @@ def test_refusals(ctx):
     # the descriptor itself: a negative count, and a count without its arrays
     for field, value, msg in (("n_traits_more", -1, "0 .. 63 further traits"), ("z_more", None, "z_more is NULL"), ("out_z_more", None, "out_z_more is NULL")):
         desc = hotpath.WindowDesc()
-        win = hotpath._Win(desc, 0, gm, gu, p["off"], None, z1, 0.1, 1e-5, False, z_more=Z)
+        win = hotpath._Win(desc, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=p["off"], z1=z1, lam=0.1, z_more=Z))
         setattr(desc, field, value)
         with pytest.raises(Exception, match=msg):
             hotpath.check(ctx.lib.gauss_impute_window(ctx.handle, hotpath.C.byref(desc)))

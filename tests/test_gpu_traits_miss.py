@@ -469,7 +469,7 @@ def test_refusals(ctx):
     for field, msg in (("out_info_more", "out_info_more is NULL"), ("out_z_miss", "out_z_miss is NULL"), ("out_info_miss", "out_info_miss is NULL"),
                        ("n_traits_more", "needs n_traits_more > 0")):
         desc = hotpath.WindowDesc()
-        win = hotpath._Win(desc, 0, gm, gu, p["off"], None, z1, 0.1, 1e-5, False, z_more=Z, miss_more=ok)
+        win = hotpath._Win(desc, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=p["off"], z1=z1, lam=0.1, z_more=Z, miss_more=ok))
         setattr(desc, field, 0 if field == "n_traits_more" else None)
         with pytest.raises(Exception, match=msg):
             hotpath.check(ctx.lib.gauss_impute_window(ctx.handle, hotpath.C.byref(desc)))

@@ -13,27 +13,20 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import desc_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LDS_FIELDS = ["lds_on", "lds_n_annot", "lds_radius", "lds_bp_m", "lds_bp_u", "lds_n", "lds_annot", "out_lds_raw", "out_lds_l2", "out_lds_mass"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("lds_on")
     assert names[at: at + 10] == LDS_FIELDS and names[at - 1] == "out_status" and names[at + 10] == "out_b11"      # in front of the matrices
     assert [n for n in names if "lds_" in n] == LDS_FIELDS and names[-3:] == ["out_loo_z", "out_loo_info", "out_loo_t"]
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
     fields = ["out_status"] + LDS_FIELDS + ["out_b11"]
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu", sizeof(gauss_window_desc));\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in fields) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, _ = desc_layout(fields)
     assert ctypes.sizeof(_lib.WindowDesc) == size
     assert [getattr(_lib.WindowDesc, n).offset for n in fields] == offs
     # lds_on and lds_n_annot share a word: 1 + 1 + 8 words from out_status to out_b11
@@ -69,7 +62,7 @@ def test_host_header_declares_and_api_binds_the_calls():
 def test_hotpath_sets_the_fields():
     from gauss_amd import _lib, hotpath
     gm, gu = np.zeros((5, 8), dtype=np.uint8), np.zeros((3, 8), dtype=np.uint8)
-    mk = lambda q, **kw: (lambda d: (d, hotpath._Win(d, 0, gm, gu, [0, 8], None, np.zeros(5), 0.0, 1e-5, False, ldscore=q, **kw)))(_lib.WindowDesc())
+    mk = lambda q, **kw: (lambda d: (d, hotpath._Win(d, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(5), lam=0.0, ldscore=q, **kw))))(_lib.WindowDesc())
     bm, bu = [1, 2, 3, 5, 8], [2, 4, 9]
     d, w = mk(dict(radius=3, bp_m=bm, bp_u=bu, n=100))
     assert (d.kind, d.u_codings, d.lds_on, d.lds_n_annot, d.lds_radius, d.lds_n) == (_lib.WIN_LD, 1, 1, 0, 3, 100.0)
@@ -92,7 +85,7 @@ def test_no_matrices_is_for_a_window_that_asks():
     from gauss_amd import _lib, hotpath
     gm, gu = np.zeros((5, 8), dtype=np.uint8), np.zeros((3, 8), dtype=np.uint8)
     with pytest.raises(ValueError, match="want_matrices=False is for an LD window that asks"):
-        hotpath._Win(_lib.WindowDesc(), 0, gm, gu, [0, 8], None, np.zeros(5), 0.0, 1e-5, True, ld_codings=1, want_matrices=False)
+        hotpath._Win(_lib.WindowDesc(), dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(5), lam=0.0, ld_codings=1, want_matrices=False), True)
     with pytest.raises(ValueError, match="want_matrices=False is for an LD window that asks"):
         hotpath.ld_window(0, gm, gu, [0, 8], None, ctx=object(), want_matrices=False)
 

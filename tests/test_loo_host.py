@@ -3,14 +3,12 @@ plumbing a GPU-less machine can check -- the C ABI's window descriptor and its c
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle
-from helpers import relerr, small_panel, split_window
+from helpers import desc_layout, relerr, small_panel, split_window
 from loo_ref import loo_by_deletion, loo_closed_form, window_b11
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,20 +68,11 @@ def test_host_header_declares_and_api_binds_the_two_calls():
     assert h.gauss_host_distmix_loo.argtypes == h.gauss_host_distmix.argtypes
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     assert names[-3:] == ["out_loo_z", "out_loo_info", "out_loo_t"]
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu %zu %zu\\n", sizeof(gauss_window_desc), offsetof(gauss_window_desc, out_loo_z),'
-                   ' offsetof(gauss_window_desc, out_loo_t)); }\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, off_z, off_t = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, (off_z, off_t), _ = desc_layout(["out_loo_z", "out_loo_t"])
     assert ctypes.sizeof(_lib.WindowDesc) == size
     assert _lib.WindowDesc.out_loo_z.offset == off_z and _lib.WindowDesc.out_loo_t.offset == off_t
 

@@ -10,28 +10,21 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import desc_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRS_FIELDS = ["prs_n_s", "prs_n_lam", "prs_s", "prs_lam", "prs_n", "prs_tol", "prs_max_sweeps", "out_prs_beta", "out_prs_nnz",
               "out_prs_sweeps", "out_prs_delta", "out_prs_br", "out_prs_bg", "out_prs_kkt"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("prs_n_s")
     assert names[at: at + 14] == PRS_FIELDS and names[at + 14] == "out_z" and names[at - 1] == "min_abs_eig"      # between the window's inputs and its outputs
     assert [n for n in names if "prs_" in n] == PRS_FIELDS and names[-3:] == ["out_loo_z", "out_loo_info", "out_loo_t"]
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
     fields = ["min_abs_eig"] + PRS_FIELDS + ["out_z"]
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu", sizeof(gauss_window_desc));\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in fields) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, _ = desc_layout(fields)
     assert ctypes.sizeof(_lib.WindowDesc) == size
     assert [getattr(_lib.WindowDesc, n).offset for n in fields] == offs
     # n_s and n_lam share a word; max_sweeps has one of its own: 1 + 1 + 4 + 1 + 7 words from min_abs_eig to out_z
@@ -75,7 +68,7 @@ def test_integration_snippet_compiles_against_the_header():
 def test_hotpath_sets_the_fields():
     from gauss_amd import _lib, hotpath
     gm, gu = np.zeros((5, 8), dtype=np.uint8), np.zeros((3, 8), dtype=np.uint8)
-    mk = lambda prs: (lambda d: (d, hotpath._Win(d, 0, gm, gu, [0, 8], None, np.zeros(5), 0.1, 1e-5, False, prs=prs)))(_lib.WindowDesc())
+    mk = lambda prs: (lambda d: (d, hotpath._Win(d, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(5), lam=0.1, prs=prs))))(_lib.WindowDesc())
     d, w = mk(dict(n=1000))
     assert (d.prs_n_s, d.prs_n_lam, d.prs_max_sweeps, d.prs_n, d.prs_tol) == (4, 20, 100, 1000.0, 1e-4)
     assert [d.prs_s[k] for k in range(4)] == [0.2, 0.5, 0.9, 1.0]

@@ -14,7 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import small_panel, split_window
+from helpers import desc_layout, small_panel, split_window
 from loo_ref import window_b11
 from slct_ref import min_var_frac, planted_z, slct_by_definition, slct_recurrence
 
@@ -180,21 +180,12 @@ SLCT_FIELDS = ["slct_max", "slct_chi2_stop", "slct_min_var_frac", "slct_forced",
                "out_slct_zin", "out_slct_joint", "out_slct_zc", "out_slct_var"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     assert [n for n in names if "slct" in n] == SLCT_FIELDS
     assert _lib.SLCT_MAX == 32 and _lib.ST_SLCT_SKIPPED == 8
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu %d %d", sizeof(gauss_window_desc), GAUSS_SLCT_MAX, GAUSS_ST_SLCT_SKIPPED);\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in SLCT_FIELDS) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, kmax, bit, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, (kmax, bit) = desc_layout(SLCT_FIELDS, ["GAUSS_SLCT_MAX", "GAUSS_ST_SLCT_SKIPPED"])
     assert ctypes.sizeof(_lib.WindowDesc) == size and kmax == _lib.SLCT_MAX and bit == _lib.ST_SLCT_SKIPPED
     assert [getattr(_lib.WindowDesc, n).offset for n in SLCT_FIELDS] == offs
 

@@ -10,29 +10,22 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import desc_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUSIE_FIELDS = ["susie_L", "susie_coverage", "susie_prior_var", "susie_tol", "susie_min_abs_corr", "out_susie_pip", "out_susie_set",
                 "out_susie_set_pip", "out_susie_V", "out_susie_lse", "out_susie_mass", "out_susie_purity", "out_susie_size", "out_susie_kept",
                 "out_susie_alpha", "out_susie_mu", "out_susie_sweeps", "susie_max_sweeps", "susie_estimate_var", "susie_measured_only"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("susie_L")
     assert names[at: at + 20] == SUSIE_FIELDS and names[at + 20] == "geno_format" and names[at - 1] == "u_codings"
     assert [n for n in names if "susie_" in n] == SUSIE_FIELDS and names[-3:] == ["out_loo_z", "out_loo_info", "out_loo_t"]
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
     fields = ["u_codings"] + SUSIE_FIELDS + ["geno_format", "rows_m"]
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu", sizeof(gauss_window_desc));\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in fields) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, _ = desc_layout(fields)
     assert ctypes.sizeof(_lib.WindowDesc) == size
     assert [getattr(_lib.WindowDesc, n).offset for n in fields] == offs
     # u_codings and susie_L share a word, sixteen 8-byte fields, max_sweeps / estimate_var and measured_only / geno_format share two
@@ -74,7 +67,7 @@ def test_integration_snippet_compiles_against_the_header():
 def test_hotpath_sets_the_fields():
     from gauss_amd import _lib, hotpath
     gm, gu = np.zeros((5, 8), dtype=np.uint8), np.zeros((3, 8), dtype=np.uint8)
-    mk = lambda susie: (lambda d: (d, hotpath._Win(d, 0, gm, gu, [0, 8], None, np.zeros(5), 0.1, 1e-5, False, susie=susie)))(_lib.WindowDesc())
+    mk = lambda susie: (lambda d: (d, hotpath._Win(d, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(5), lam=0.1, susie=susie))))(_lib.WindowDesc())
     d, w = mk(dict())
     assert (d.susie_L, d.susie_max_sweeps, d.susie_estimate_var, d.susie_measured_only) == (10, 100, 1, 0)
     assert (d.susie_coverage, d.susie_prior_var, d.susie_tol, d.susie_min_abs_corr) == (0.95, 25.0, 1e-4, 0.5)

@@ -12,30 +12,21 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import small_panel, split_window
+from helpers import desc_layout, small_panel, split_window
 from traits_ref import traits_by_oracle, traits_closed_form
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRAITS_FIELDS = ["n_traits_more", "z_more", "out_z_more"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("n_traits_more")
     assert names[at:at + 3] == TRAITS_FIELDS and names[at + 3:] == ["out_loo_z", "out_loo_info", "out_loo_t"]
     assert not any("slct" in n for n in TRAITS_FIELDS)
     assert _lib.TRAITS_MORE_MAX == 63
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu %d", sizeof(gauss_window_desc), GAUSS_TRAITS_MORE_MAX);\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in TRAITS_FIELDS) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, tmax, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, (tmax,) = desc_layout(TRAITS_FIELDS, ["GAUSS_TRAITS_MORE_MAX"])
     assert ctypes.sizeof(_lib.WindowDesc) == size and tmax == _lib.TRAITS_MORE_MAX
     assert [getattr(_lib.WindowDesc, n).offset for n in TRAITS_FIELDS] == offs
 

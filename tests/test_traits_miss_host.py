@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import small_panel, split_window
+from helpers import desc_layout, small_panel, split_window
 from traits_miss_ref import miss_by_oracle, miss_closed_form, random_mask
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,23 +46,14 @@ def test_closed_form_equals_one_oracle_run_per_trait(mode, M, U, k):
     assert _err(got["info"][1], mats["info"]) <= 1e-12                 # the trait that lacks nothing: the window's own info
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("miss_more")
     assert names[at:at + 4] == MISS_FIELDS and names[at + 4] == "n_traits_more"       # the block sits in front of the traits block
     assert not any("slct" in n for n in MISS_FIELDS)
     assert _lib.TRAITS_MISS_MAX == 32 and _lib.TRAITS_MISS_UNION_MAX == 128
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu %d %d", sizeof(gauss_window_desc), GAUSS_TRAITS_MISS_MAX, GAUSS_TRAITS_MISS_UNION_MAX);\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in MISS_FIELDS + ["n_traits_more"]) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, kmax, emax, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, (kmax, emax) = desc_layout(MISS_FIELDS + ["n_traits_more"], ["GAUSS_TRAITS_MISS_MAX", "GAUSS_TRAITS_MISS_UNION_MAX"])
     assert ctypes.sizeof(_lib.WindowDesc) == size and (kmax, emax) == (_lib.TRAITS_MISS_MAX, _lib.TRAITS_MISS_UNION_MAX)
     assert [getattr(_lib.WindowDesc, n).offset for n in MISS_FIELDS + ["n_traits_more"]] == offs
 

@@ -10,27 +10,20 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import desc_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XS_FIELDS = ["xs_group", "xs_from_lead", "out_xs_V", "out_xs_purity", "out_xs_mu", "out_xs_n"]
 
 
-def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header(tmp_path):
+def test_window_descriptor_mirror_has_the_size_and_the_fields_of_the_header():
     from gauss_amd import _lib
     names = [f[0] for f in _lib.WindowDesc._fields_]
     at = names.index("xs_group")
     assert names[at: at + 6] == XS_FIELDS and names[at - 1] == "out_b21" and names[at + 6] == "kind"      # in front of the QCAT block
     assert [n for n in names if "xs_" in n] == XS_FIELDS
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    src = tmp_path / "sz.cpp"
     fields = ["out_b21"] + XS_FIELDS + ["kind"]
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "gauss_hip.h"\n'
-                   'int main() { std::printf("%zu", sizeof(gauss_window_desc));\n'
-                   + "".join(f'std::printf(" %zu", offsetof(gauss_window_desc, {n}));\n' for n in fields) + '}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, *offs = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, offs, _ = desc_layout(fields)
     assert ctypes.sizeof(_lib.WindowDesc) == size
     assert [getattr(_lib.WindowDesc, n).offset for n in fields] == offs
     # xs_group has a word of its own (padded), then five 8-byte fields, then kind
@@ -69,12 +62,12 @@ def test_integration_snippet_compiles_against_the_header():
 def test_hotpath_sets_the_fields_and_builds_the_maps():
     from gauss_amd import _lib, hotpath
     gm, gu = np.zeros((5, 8), dtype=np.uint8), np.zeros((3, 8), dtype=np.uint8)
-    mk = lambda susie: (lambda d: (d, hotpath._Win(d, 0, gm, gu, [0, 8], None, np.zeros(5), 0.1, 1e-5, False, susie=susie)))(_lib.WindowDesc())
-    d, w = mk(dict(L=3, group=2, _role="leader", _K=3, want_mu=True))
+    mk = lambda susie, xs=None: (lambda d: (d, hotpath._Win(d, dict(mode=0, geno_m=gm, geno_u=gu, pop_off=[0, 8], z1=np.zeros(5), lam=0.1, susie=susie), xs=xs)))(_lib.WindowDesc())
+    d, w = mk(dict(L=3, group=2, want_mu=True), xs=("leader", 3))
     assert d.xs_group == 2 and d.susie_L == 3 and d.out_susie_pip and d.out_xs_V and d.out_xs_purity and d.out_xs_mu and d.out_xs_n and not d.xs_from_lead
     r = w.result()
     assert r["xs_V"].shape == (3, 3) and r["xs_mu"].shape == (3, 3, 8) and r["xs_n"] == 0 and "susie_pip" in r
-    d, w = mk(dict(L=3, group=2, _role="peer", from_lead=[0, 1, -1, 7, 2, 3, 4, 5], tol=0.0, max_sweeps=9, measured_only=True))
+    d, w = mk(dict(L=3, group=2, from_lead=[0, 1, -1, 7, 2, 3, 4, 5], tol=0.0, max_sweeps=9, measured_only=True), xs=("peer", 3))
     assert d.xs_group == 2 and d.susie_L == 3 and d.susie_max_sweeps == 9 and d.susie_tol == 0.0 and d.susie_measured_only == 1
     assert d.xs_from_lead and [d.xs_from_lead[j] for j in range(8)] == [0, 1, -1, 7, 2, 3, 4, 5]
     assert not d.out_susie_pip and not d.out_xs_V and "susie_pip" not in w.result() and "xs_V" not in w.result()
