@@ -45,7 +45,7 @@ HOST_SYMBOLS = [
     "gauss_host_jepeg_gene_tail", "gauss_host_plan_cost",
     "gauss_host_jepeg_rank", "gauss_host_jepeg_genome", "gauss_prepared_jepeg_plan", "gauss_prepared_jepeg_finish",
     "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
-    "gauss_host_simulateLD", "gauss_host_simulate_draws",
+    "gauss_host_simulateLD", "gauss_host_simulate_draws", "gauss_host_clump",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
     "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_prs", "gauss_host_distmix_prs", "gauss_host_dist_ldscore", "gauss_host_distmix_ldscore", "gauss_host_dist_xsusie", "gauss_host_distmix_xsusie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
@@ -141,6 +141,7 @@ def load_host():
     h.gauss_host_dist_slct.argtypes = h.gauss_host_dist.argtypes[:-1] + slct_tail
     h.gauss_host_distmix_slct.argtypes = h.gauss_host_distmix.argtypes[:-1] + slct_tail
     h.gauss_host_slct_chi2.argtypes = [_dbl, _dp]
+    h.gauss_host_clump.argtypes = [_vp, C.c_int, _i64, _i64, _strs, _dp, C.c_int] + files4 + [_dbl, _dbl, _dbl, _dbl, _dbl, C.POINTER(_vp)]
     h.gauss_host_dist_cond.argtypes = h.gauss_host_dist_slct.argtypes
     h.gauss_host_distmix_cond.argtypes = h.gauss_host_distmix_slct.argtypes
     h.gauss_host_dist_cs.argtypes = h.gauss_host_dist_slct.argtypes[:-1] + [_dbl, _dbl, C.POINTER(_vp)]      # ..., coverage, prior_var, out
@@ -324,6 +325,28 @@ def simulateLD(chr, start_bp, end_bp, pop_wgt_df, sim_size, input_file, referenc
     if detail:
         res.update(_draws(named))
     return res
+
+
+def clump(chr, start_bp, end_bp, pop_wgt_df, input_file, reference_index_file, reference_data_file, reference_pop_desc_file,
+          p1=1e-4, p2=1e-2, r2=0.5, kb=250, af1_cutoff=None, ctx=None):
+    """LD clumping (PLINK's --clump, whose defaults these are) of a region of a mixed-ancestry study on the ancestry-weighted LD of
+    computeLD, on the GPU (gauss_host_clump): the SNPs are computeLD's for the same arguments; a SNP with p < p1 that no more
+    significant index has claimed leads a clump and takes every unclaimed SNP within kb with p < p2 and squared LD >= r2.  Returns the
+    frame rsid chr bp a1 a2 af1mix z pval clump index_rsid r2 (clump: rank of the SNP's clump, 0 for none); ``attrs["clumps"]`` is a
+    frame with one row per clump: index_row, size, bp_first, bp_last.  One region of at most 8 192 SNPs per call; clumps are cut at
+    the region's edges.  To clump imputed SNPs, write the imputed table out as the study file; pval takes its z at face value."""
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_clump(_ctx(ctx), int(chr), int(start_bp), int(end_bp), names, w.ctypes.data_as(_dp), n, _enc(input_file),
+                               _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
+                               float(p1), float(p2), float(r2), float(kb), C.byref(out)))
+    named = _named(h, out)
+    df, _ = _table(h, out)
+    cm = np.asarray(named["clumps"]).reshape(-1, 4).astype(np.int64)
+    import pandas as pd       # (the frame's attrs carry the clumps: this call needs pandas)
+    df.attrs["clumps"] = pd.DataFrame(dict(index_row=cm[:, 0], size=cm[:, 1], bp_first=cm[:, 2], bp_last=cm[:, 3]))
+    return df
 
 
 def simulate_draws(pop_wgt_df, sim_size, reference_pop_desc_file, seed=None):

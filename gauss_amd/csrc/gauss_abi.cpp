@@ -2,6 +2,7 @@
 #include "gauss_job.h"
 
 // the kernels' constants that include/gauss_hip.h states to the caller (gauss_internal.h does not see that header)
+static_assert(gauss::CLUMP_M_MAX == GAUSS_CLUMP_MAX_M && gauss::CLUMP_KEYS_MAX == GAUSS_CLUMP_MAX_KEYS, "clumping: gauss_internal.h and include/gauss_hip.h disagree");
 static_assert(gauss::LDS_C == GAUSS_LDS_MAX_ANNOT && gauss::LDS_CHUNK == GAUSS_LDS_CHUNK, "LD scores: gauss_internal.h and include/gauss_hip.h disagree");
 
 // entry points that need the job's context
@@ -366,6 +367,57 @@ int gauss_ld_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, in
                   int on_device, double* out_cor)
 {
     return ld_common(ctx, ld_spec_rows(mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop, diag), on_device, out_cor);
+}
+
+int gauss_ld_clump_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp,
+                        const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop, int on_device,
+                        const int32_t* bp, const double* key, int n_key, int64_t radius, double r2_min, double key_index, double key_member,
+                        int32_t* out_owner, int32_t* out_rank, double* out_r2, int32_t* out_n_clumps)
+{
+    if (!ctx || !store) return fail(GAUSS_E_INVALID, "bad arguments to gauss_ld_clump_rows");
+    if (!bp) return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: bp is NULL");
+    if (!key) return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: key is NULL");
+    if (!out_owner) return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: out_owner is NULL");
+    if (n_key < 1 || n_key > CLUMP_KEYS_MAX)
+        return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: n_key = %d; a call clumps 1 .. %d traits", n_key, CLUMP_KEYS_MAX);
+    if (n_snp < 1 || n_snp > CLUMP_M_MAX)
+        return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: n_snp = %d; a region holds 1 .. %d SNPs", n_snp, CLUMP_M_MAX);
+    for (int i = 1; i < n_snp; i++)
+        if (bp[i] < bp[i - 1]) return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: bp decreases at row %d (%d after %d)", i, bp[i], bp[i - 1]);
+    if (radius < 0) return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: radius = %lld is negative", (long long)radius);
+    if (!(r2_min >= 0.0 && r2_min <= 1.0)) return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: r2_min = %g is outside [0, 1]", r2_min);
+    if (!std::isfinite(key_index) || !std::isfinite(key_member))
+        return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: key_index = %g, key_member = %g; both thresholds must be finite", key_index, key_member);
+    if (key_member > key_index)
+        return fail(GAUSS_E_INVALID, "gauss_ld_clump_rows: key_member = %g is above key_index = %g", key_member, key_index);
+    JobGuard job(nullptr, job_free);
+    int rc = ld_job(ctx, ld_spec_rows(mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop, 1.0), on_device, job);
+    if (rc) return rc;
+    rc = job_run(job.get(), false);
+    if (rc) return rc;
+    // the matrix stays where the epilogue wrote it (out_ld, both triangles); the kernel runs behind the job on the same stream
+    hipStream_t st = ctx->stream;
+    const size_t M = (size_t)n_snp, TM = (size_t)n_key * M;
+    DevBuf d_bp, d_key, d_owner, d_rank, d_r2, d_n;
+    if (d_bp.alloc(ctx, sizeof(int) * M) != hipSuccess || d_key.alloc(ctx, sizeof(double) * TM) != hipSuccess ||
+        d_owner.alloc(ctx, sizeof(int) * TM) != hipSuccess || d_rank.alloc(ctx, sizeof(int) * TM) != hipSuccess ||
+        d_r2.alloc(ctx, sizeof(double) * TM) != hipSuccess || d_n.alloc(ctx, sizeof(int) * (size_t)n_key) != hipSuccess)
+        return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes of keys and clumps) failed", (sizeof(double) * 2 + sizeof(int) * 2) * TM);
+    HIPCHK(hipMemcpyAsync(d_bp.p, bp, sizeof(int) * M, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_key.p, key, sizeof(double) * TM, hipMemcpyHostToDevice, st));
+    ClumpArgs a;
+    a.R = job->plans[0].p.out_ld; a.bp = d_bp.as<int>(); a.key = d_key.as<double>();
+    a.owner = d_owner.as<int>(); a.rank = d_rank.as<int>(); a.r2 = d_r2.as<double>(); a.n_clumps = d_n.as<int>();
+    a.radius = (long long)std::min<int64_t>(radius, (int64_t)1 << 32);      // positions are 32-bit: 2^32 is every band already, and bp +- radius stays in range
+    a.r2_min = r2_min; a.key_index = key_index; a.key_member = key_member; a.M = n_snp;
+    launch_clump(a, n_key, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_owner, d_owner.p, sizeof(int) * TM, hipMemcpyDeviceToHost, st));
+    if (out_rank) HIPCHK(hipMemcpyAsync(out_rank, d_rank.p, sizeof(int) * TM, hipMemcpyDeviceToHost, st));
+    if (out_r2) HIPCHK(hipMemcpyAsync(out_r2, d_r2.p, sizeof(double) * TM, hipMemcpyDeviceToHost, st));
+    if (out_n_clumps) HIPCHK(hipMemcpyAsync(out_n_clumps, d_n.p, sizeof(int) * (size_t)n_key, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return job_fetch(job.get());
 }
 
 int gauss_ld_resampled_rows(gauss_ctx* ctx, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp,

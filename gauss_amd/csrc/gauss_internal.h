@@ -245,6 +245,9 @@ constexpr int LDS_C = 32;              // GAUSS_LDS_MAX_ANNOT: annotation catego
 constexpr int LDS_CHUNK = 64;          // GAUSS_LDS_CHUNK: rows of a chunk of ldscore_kernel's summation order
 constexpr int LDS_COLS = 64;           // targets of a workgroup of ldscore_kernel: one per lane of its wave
 constexpr int LDS_MAX_CHUNKS = 65535;  // chunks of a window: they are the y extent of ldscore_kernel's grid (the planner refuses more: 4.19 M rows)
+constexpr int CLUMP_T = 512;            // threads of clump_kernel: one workgroup per trait
+constexpr int CLUMP_M_MAX = 8192;      // GAUSS_CLUMP_MAX_M: keys, owner and bp of a region in LDS, 16 bytes a SNP (k_clump.hip)
+constexpr int CLUMP_KEYS_MAX = 64;     // GAUSS_CLUMP_MAX_KEYS: traits of one call, the x extent of clump_kernel's grid
 constexpr int lds_chunks(int M, int U) { return (M + LDS_CHUNK - 1) / LDS_CHUNK + (U + LDS_CHUNK - 1) / LDS_CHUNK; }      // measured rows' chunks, then the others'
 constexpr int susie_uld(int U) { return (U + 63) & ~63; }   // row pitch of W and Y
 // Prob::susie_ws in doubles.  Y = X C^T and W = X^T Y = B11^-1 B12 [Mld][uld], the window's; then one block per fitted trait (trait t
@@ -532,6 +535,21 @@ void launch_traits_impute(const Prob* d_probs, const int2* d_umap, int n_strips,
 void launch_traits_miss_solve(const Prob* d_probs, const int2* d_map, int n_blocks, const int2* d_tmap, int n_traits, hipStream_t s);
 void launch_traits_miss_apply(const Prob* d_probs, const int2* d_umap, int n_strips, hipStream_t s);
 void launch_counts(const Prob* d_probs, int prob, int npair, long long* d_out, hipStream_t s);
+// LD clumping (k_clump.hip) on a full M x M LD matrix in device memory (an LD-only job's out_ld): one workgroup per trait.  The
+// arguments travel by value; every pointer is a device pointer; rank, r2 and n_clumps may be null
+struct ClumpArgs {
+    const double* R;        // [M][M], both triangles
+    const int* bp;          // [M], never decreasing
+    const double* key;      // [n_key][M]
+    int* owner;             // [n_key][M]
+    int* rank;              // [n_key][M]
+    double* r2;             // [n_key][M]
+    int* n_clumps;          // [n_key]
+    long long radius;
+    double r2_min, key_index, key_member;
+    int M;
+};
+void launch_clump(const ClumpArgs& a, int n_key, hipStream_t s);
 void launch_pack2bit(const uint8_t* d_in, long long ld_in, uint8_t* d_out, long long ld_out, int n_snp,
                      const int* d_pop_off, const int* d_blk_off, int n_pop, hipStream_t s);
 void launch_h2d_copy(void* d_dst, const void* pinned_src, size_t bytes, hipStream_t s);

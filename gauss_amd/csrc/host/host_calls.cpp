@@ -1069,6 +1069,8 @@ int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, co
     Column& af = out.t->add("af1mix", GAUSS_COL_DBL);
     if (p) for (Snp* s : p->measured) af.d.push_back(s->af1mix);
     else for (int32_t vi : ow.w.measured) af.d.push_back(ow.w.v[(size_t)vi].af);
+    if (p) for (Snp* s : p->measured) out.z.push_back(s->z);
+    else for (int32_t vi : ow.w.measured) out.z.push_back(ow.w.v[(size_t)vi].z);
     return 0;
 }
 
@@ -1151,6 +1153,33 @@ int gauss_host_computeLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_
                       s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, 1.0, s.on_device,
                       t->matrix.data()) != 0) return herr("%s", gauss_last_error());
     *out = t.release();
+    return 0;
+}
+
+int gauss_host_clump(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                     int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                     const char* reference_pop_desc_file, double af1_cutoff, double p1, double p2, double r2, double kb, gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    ClumpKeys k;
+    if (clump_keys(p1, p2, r2, kb, k)) return -1;
+    LdRows s;
+    if (computeld_rows(ctx, chr, start_bp, end_bp, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file, reference_data_file,
+                       reference_pop_desc_file, af1_cutoff, s)) return -1;
+    const int M = s.M;
+    if (M > GAUSS_CLUMP_MAX_M)
+        return herr("clump: the region holds %d SNPs of the study; a call clumps at most %d (ask for a shorter region)", M, GAUSS_CLUMP_MAX_M);
+    const std::vector<int32_t>& bp = s.t->cols[2].i;                     // add_ident_columns: rsid chr bp a1 a2
+    std::vector<double> key((size_t)M), r2_out((size_t)M);
+    for (int i = 0; i < M; i++) key[(size_t)i] = s.z[(size_t)i] * s.z[(size_t)i];
+    std::vector<int32_t> owner((size_t)M), rank((size_t)M);
+    int32_t n = 0;
+    if (gauss_ld_clump_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
+                            s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, s.on_device,
+                            bp.data(), key.data(), 1, k.radius, k.r2_min, k.key_index, k.key_member, owner.data(), rank.data(), r2_out.data(),
+                            &n) != 0) return herr("%s", gauss_last_error());
+    clump_output(*s.t, s.z, owner.data(), rank.data(), r2_out.data(), n);
+    *out = s.t.release();
     return 0;
 }
 

@@ -747,6 +747,7 @@ int zmix_sup_groups(const Args& a, std::vector<int32_t>& pop_group, std::vector<
 // computeLD's measured SNPs and where their genotype rows are (host_calls.cpp), shared by computeLD and simulateLD
 struct LdRows {
     std::unique_ptr<gauss_table> t;     // the snplist columns: rsid chr bp a1 a2 af1mix
+    std::vector<double> z;              // [M] the study's Z-scores of the rows (computeLD and simulateLD do not read them; clump does)
     int M = 0;
     const uint8_t* store = nullptr;     // rows as gauss_ld_rows takes them
     int64_t ld = 0;
@@ -761,3 +762,13 @@ struct LdRows {
 int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
                    int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
                    const char* reference_pop_desc_file, double af1_cutoff, LdRows& out);
+// clump(): the thresholds of gauss_ld_clump_rows for key = z^2 from the call's p-values and distances (host_tables.cpp).  NaN (not
+// given) takes PLINK's value: p1 1e-4, p2 1e-2, r2 0.5, kb 250; key = slct_chi2_of(p), so a SNP is an index iff its two-sided p-value is
+// below p1.  -1 with the message set: p1 or p2 outside (0, 1], p2 < p1, r2 outside [0, 1], kb < 0 or not finite
+struct ClumpKeys { double key_index, key_member, r2_min; int64_t radius; };
+int clump_keys(double p1, double p2, double r2, double kb, ClumpKeys& out);
+// ... and its table: `t` holds computeLD's snplist columns (rsid chr bp a1 a2 af1mix); z pval clump index_rsid r2 are added -- pval =
+// 2 pnorm(-|z|), clump = the rank of the SNP's clump (0: none), index_rsid = the lead's rsid ("." for none), r2 = the squared LD to
+// it -- and the named matrix `clumps` [n_clumps x 4], one row per clump in rank order: index row (from 0), size, bp of the first
+// member, bp of the last.  owner / rank / r2 [M] as gauss_ld_clump_rows returned them
+void clump_output(gauss_table& t, const std::vector<double>& z, const int32_t* owner, const int32_t* rank, const double* r2, int n_clumps);

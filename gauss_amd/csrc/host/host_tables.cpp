@@ -699,6 +699,44 @@ double slct_chi2_of(double p)
     return hi_d;
 }
 
+int clump_keys(double p1, double p2, double r2, double kb, ClumpKeys& out)
+{
+    const double a = std::isnan(p1) ? 1e-4 : p1, b = std::isnan(p2) ? 1e-2 : p2;                                 // PLINK's --clump-p1 / --clump-p2
+    if (!(a > 0.0 && a <= 1.0)) return herr("clump: p1 = %g is outside (0, 1]", a);
+    if (!(b > 0.0 && b <= 1.0)) return herr("clump: p2 = %g is outside (0, 1]", b);
+    const double rr = std::isnan(r2) ? 0.5 : r2, k = std::isnan(kb) ? 250.0 : kb;                                // --clump-r2 / --clump-kb
+    if (b < a) return herr("clump: p2 = %g is below p1 = %g (a member's threshold is no stricter than an index SNP's)", b, a);
+    if (!(rr >= 0.0 && rr <= 1.0)) return herr("clump: r2 = %g is outside [0, 1]", rr);
+    if (!(k >= 0.0) || !std::isfinite(k) || k * 1000.0 > 4e9) return herr("clump: kb = %g; the distance is 0 .. 4 000 000 kb", k);
+    out.key_index = slct_chi2_of(a); out.key_member = slct_chi2_of(b); out.r2_min = rr;
+    out.radius = (int64_t)llround(k * 1000.0);
+    return 0;
+}
+
+void clump_output(gauss_table& t, const std::vector<double>& z, const int32_t* owner, const int32_t* rank, const double* r2, int n_clumps)
+{
+    const size_t M = z.size(), n = (size_t)std::max(n_clumps, 0);
+    t.widen(5);                                                         // room for the five columns: no add() below moves a column
+    Column &zc = t.add("z", GAUSS_COL_DBL), &pval = t.add("pval", GAUSS_COL_DBL), &clump = t.add("clump", GAUSS_COL_INT);
+    Column &lead = t.add("index_rsid", GAUSS_COL_STR), &rc = t.add("r2", GAUSS_COL_DBL);
+    const std::vector<std::string>& rsid = t.cols[0].s;                 // add_ident_columns: rsid chr bp a1 a2
+    const std::vector<int32_t>& bp = t.cols[2].i;
+    std::vector<double> cm(n * 4, 0.0);                                 // column-major [n x 4]: index row, size, first bp, last bp
+    for (size_t i = 0; i < M; i++) {
+        const int o = owner[i];
+        const int k = o >= 0 ? rank[(size_t)o] : 0;
+        zc.d.push_back(z[i]); pval.d.push_back(2 * pnorm_upper(fabs(z[i])));
+        clump.i.push_back(k); lead.s.emplace_back(o >= 0 ? rsid[(size_t)o] : "."); rc.d.push_back(r2[i]);
+        if (k < 1 || (size_t)k > n) continue;
+        const size_t c = (size_t)k - 1;
+        cm[c] = (double)o;
+        if (cm[n + c] == 0.0) cm[2 * n + c] = (double)bp[i];            // rows come in bp order: the first member seen is the first
+        cm[n + c] += 1.0;
+        cm[3 * n + c] = (double)bp[i];
+    }
+    t.put_named("clumps", (int)n, 4, std::move(cm));
+}
+
 gauss_table* qcat_output(gauss_prepared& p)     // qcat.cpp:94-131 / qcatmix.cpp:102-139
 {
     const bool mix = p.kind == GAUSS_KIND_QCATMIX;

@@ -230,6 +230,53 @@ def ld_matrix_rows(store, rows, pop_off, pop_wgt=None, mode=MODE_WEIGHTED, diag=
     return out
 
 
+# chi^2 (1 df) of PLINK's --clump-p1 1e-4 and --clump-p2 1e-2 (api.slct_chi2 of them): the default thresholds of a key that is z^2
+CLUMP_KEY_INDEX, CLUMP_KEY_MEMBER = 15.136705226623402, 6.634896601021217
+
+
+def _clump(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, key, radius, r2_min, key_index, key_member):
+    b = np.ascontiguousarray(bp, dtype=np.int32).reshape(-1)
+    k = np.ascontiguousarray(key, dtype=np.float64)
+    one = k.ndim == 1
+    k = k.reshape(1, -1) if one else k
+    if k.ndim != 2 or k.shape[1] != S or b.shape != (S,):
+        raise ValueError(f"bp has shape {b.shape} and key {np.shape(key)}: expected ({S},) and ({S},) or (T, {S})")
+    T = k.shape[0]
+    owner, rank = np.full((T, S), -2, dtype=np.int32), np.full((T, S), -2, dtype=np.int32)
+    r2, n = np.zeros((T, S)), np.full(T, -2, dtype=np.int32)
+    check(ctx.lib.gauss_ld_clump_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip), _lib.ptr(so, _ip),
+                                      _lib.ptr(w, _dp), len(po) - 1, on_dev, b.ctypes.data_as(_ip), k.ctypes.data_as(_dp), T, int(radius),
+                                      float(r2_min), float(key_index), float(key_member), owner.ctypes.data_as(_ip),
+                                      rank.ctypes.data_as(_ip), r2.ctypes.data_as(_dp), n.ctypes.data_as(_ip)))
+    if one:
+        return dict(owner=owner[0], rank=rank[0], r2=r2[0], n_clumps=int(n[0]))
+    return dict(owner=owner, rank=rank, r2=r2, n_clumps=n)
+
+
+def ld_clump(geno, pop_off, bp, key, pop_wgt=None, mode=MODE_WEIGHTED, radius=250_000, r2_min=0.5, key_index=CLUMP_KEY_INDEX,
+             key_member=CLUMP_KEY_MEMBER, ctx=None):
+    """gauss_ld_clump_rows on the rows of a byte matrix: LD clumping (PLINK's --clump rule) on the LD that ld_matrix would return,
+    which stays on the device.  bp [S] never decreases; key [S] or [T, S], the larger the more significant (z^2: clumping; minor-allele
+    frequency with key_index = key_member = 0: LD pruning).  Returns dict(owner, rank, r2, n_clumps): owner[i] the row that leads
+    SNP i's clump (-1: none), rank[i] = k where row i leads the k-th clump (else 0), r2[i] the squared LD to the lead (1 for a lead,
+    NaN for none).  A 1-D key gives 1-D outputs."""
+    ctx = ctx or default_context()
+    g = _lib.as_u8(geno)
+    po, w = _pops(pop_off, pop_wgt)
+    return _clump(ctx, g.ctypes.data, g.strides[0], _lib.GENO_U8, 0, None, g.shape[0], po, None, w, mode, bp, key, radius, r2_min,
+                  key_index, key_member)
+
+
+def ld_clump_rows(store, rows, pop_off, bp, key, pop_wgt=None, mode=MODE_WEIGHTED, radius=250_000, r2_min=0.5,
+                  key_index=CLUMP_KEY_INDEX, key_member=CLUMP_KEY_MEMBER, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
+    """ld_clump on the store rows `rows` (a numpy matrix of host rows, a RowStore or a raw device pointer, as ld_matrix_rows)."""
+    ctx = ctx or default_context()
+    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
+    po, w = _pops(pop_off, pop_wgt)
+    S = len(r) if r is not None else store.shape[0]
+    return _clump(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, key, radius, r2_min, key_index, key_member)
+
+
 def ld_resampled(store, rows, pop_off, draw_pop, draw_sample, n_cols, diag=1.0, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
     """gauss_ld_resampled_rows: pooled LD (CalCor, n = n_cols) of the store rows `rows` (None: rows 0 .. S-1 of a numpy matrix)
     over the drawn samples -- draw k is sample draw_sample[k] of population draw_pop[k] -- and n_cols - len(draws) zero columns

@@ -675,6 +675,38 @@ int gauss_ld_resampled_rows(gauss_ctx* ctx, const uint8_t* store, int64_t ld, in
                             const int32_t* draw_pop, const int32_t* draw_sample, int64_t n_drawn, int64_t n_cols,
                             double diag, int on_device, double* out_cor);
 
+/* LD clumping (PLINK's --clump rule) of the n_snp rows of a region on their LD, which is formed as gauss_ld_rows forms it (same rows,
+ * same bits) and never leaves the device: only owner, rank, r2 and n_clumps come back.  Rows as in gauss_ld_rows (U8 or 2-bit with
+ * pop_src_off, host or resident store, rows NULL: row s).  bp [n_snp]: positions, never decreasing.  key [n_key][n_snp]: one row per
+ * trait, the traits share the LD; a larger key is more significant; a row whose key is NaN is neither an index nor a member.
+ * For each trait t on its own, with R the LD matrix:
+ *     owner[i] = -1, rank[i] = 0, r2[i] = NaN for every i;  n = 0
+ *     order = rows with key_i >= key_index, by (key descending, row ascending)
+ *     for i in order:
+ *         if owner[i] != -1: continue                        (a SNP already clumped never leads)
+ *         n += 1;  owner[i] = i;  rank[i] = n;  r2[i] = 1.0
+ *         for j != i with |bp_j - bp_i| <= radius, owner[j] == -1, key_j >= key_member:
+ *             t2 = R_ij * R_ij                               (one rounded fp64 product of the LD entry as the LD step left it)
+ *             if t2 >= r2_min: owner[j] = i;  r2[j] = t2     (a NaN compares false)
+ *     n_clumps = n
+ * A SNP goes to the FIRST (most significant) index that claims it, not to the one it correlates with most: PLINK's rule.  The key is
+ * the caller's: with key = z^2 this is clumping; with key = minor-allele frequency, key_index = key_member = 0 it is LD pruning
+ * (the commoner SNP of a correlated pair stays).  No floating-point sum is formed anywhere: the outputs do not depend on the thread
+ * mapping, on the source format of the rows or on the run.  A monomorphic row (NaN LD) is never a member; where it leads, it leads
+ * alone.  out_owner, out_rank [n_key][n_snp] int32, out_r2 [n_key][n_snp], out_n_clumps [n_key]; all but out_owner may be NULL.
+ * Refused (GAUSS_E_INVALID, before anything is allocated): NULL bp / key / out_owner; n_key outside 1 .. GAUSS_CLUMP_MAX_KEYS; n_snp
+ * outside 1 .. GAUSS_CLUMP_MAX_M; a bp that decreases; radius < 0; r2_min outside [0, 1] or NaN; a threshold that is not finite;
+ * key_member > key_index; and whatever gauss_ld_rows refuses.  One region per call; clumps are cut at the region's edges (ask for
+ * `radius` more on each side); a radius above 2^32 is taken as 2^32 (positions are 32-bit: every band is the whole region already,
+ * so INT64_MAX may stand for "no limit"); the LD matrix takes 8 n_snp^2 bytes of device memory (0.5 GiB at the limit).  Blocking. */
+#define GAUSS_CLUMP_MAX_M    8192
+#define GAUSS_CLUMP_MAX_KEYS 64
+int gauss_ld_clump_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows,
+                        int n_snp, const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop,
+                        int on_device, const int32_t* bp, const double* key, int n_key, int64_t radius, double r2_min,
+                        double key_index, double key_member,
+                        int32_t* out_owner, int32_t* out_rank, double* out_r2, int32_t* out_n_clumps);
+
 /* Per-population Pearson correlations of every SNP pair (prep_zmix5, zmix.cpp:158-176: CalCor on each
  * population's genotype strings, util.cpp:153-169).  out is [n_pop][n_snp*(n_snp-1)/2], population-major,
  * pairs in the reference's row order (i ascending, then j > i): column k+1 of the reference's column-major

@@ -546,6 +546,23 @@ int gauss_host_simulateLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end
 int gauss_host_simulate_draws(const char* reference_pop_desc_file, const char* const* pop_names, const double* pop_wgts,
                               int n_pop_wgt, int64_t sim_size, int64_t seed, gauss_table** out);
 
+/* clump(): LD clumping (PLINK's --clump) of a region of a mixed-ancestry study on the ancestry-weighted LD of computeLD, which never
+ * leaves the GPU (gauss_ld_clump_rows, include/gauss_hip.h: the rule).  The arguments are gauss_host_computeLD's plus four thresholds;
+ * the SNPs are exactly computeLD's selection for the same arguments (same snplist, same "Not enough number of SNPs loaded" error).
+ * key = z^2; a SNP is an index iff its two-sided p-value is below p1 and a member iff it is below p2: key_index =
+ * gauss_host_slct_chi2(p1), key_member = gauss_host_slct_chi2(p2); r2: the smallest squared LD to the index; radius = kb * 1000 bp.
+ * A NaN threshold (not given) takes PLINK's default: 1e-4, 1e-2, 0.5, 250.  Refused: p1 or p2 outside (0, 1], p2 < p1, r2 outside
+ * [0, 1], kb < 0, a region of
+ * more than GAUSS_CLUMP_MAX_M (8 192) SNPs.  Result: one row per SNP, columns rsid chr bp a1 a2 af1mix z pval clump index_rsid r2
+ * (clump: the rank of the SNP's clump, 1 = the most significant index, 0 = in no clump; index_rsid "." and r2 NaN for none), and the
+ * named matrix "clumps" [n_clumps x 4], one row per clump in rank order: the index SNP's table row (from 0), the clump's size, the bp
+ * of its first and of its last member.  One region per call; clumps are cut at the region's edges (ask for kb more on each side); a bp
+ * radius only; the study file decides which SNPs exist -- to clump imputed SNPs write the imputed table out as the study file; pval
+ * is the file's z taken at face value (an imputed z has variance `info`). */
+int gauss_host_clump(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                     int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                     const char* reference_pop_desc_file, double af1_cutoff, double p1, double p2, double r2, double kb, gauss_table** out);
+
 #define GAUSS_ZMIX_POPULATION      0
 #define GAUSS_ZMIX_SUPERPOPULATION 1
 int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
