@@ -220,6 +220,13 @@ static inline int env_int(const char* name, int dflt) { const char* e = getenv(n
 constexpr int GEMM_SMALL_TILES = 1600;        // jobs with fewer 128-wide tiles of the closing product take 64-wide ones
 constexpr int OWN_PANEL_MAX_WINDOWS = 20;     // jobs of at most this many windows factor without panel launches
 constexpr int SOLVE_SPLIT_MIN = 2;            // rows of the inverse with at least this many early products are cut into class sums
+// Three size gates that live beside their kernels and that no ordinary test window crosses, each with the test that reaches its far side:
+//   SIMLD_LDS_MAX (gauss_internal.h; k_simld.hip: resample_pack_lds_bytes) -- a source row past 60 KB is gathered from global memory
+//     instead of staged in LDS: tests/test_gpu_simld.py (rows of 61 440, 61 441 and 65 440 bytes, 2-bit rows of 61 488);
+//   EPI_MAXP = 32 / ELP = 16 (k_pack_epilogue.hip: launch_epilogue, epilogue_b11_lite_tile) and slab16's P <= 32 (gauss_plan.cpp) --
+//     population tables in LDS or in global memory, in one table chunk or several: tests/test_gpu_epilogue_tables.py (P = 16, 17, 32, 33, 64);
+//   launch_h2d_copy (k_misc.hip) -- h2d_copy_kernel's unrolled loop runs only in a launch of more than 3 * 512 * 256 sixteen-byte words
+//     (6 MB), i.e. in upload_rows' 32 MB chunks by kernel: tests/test_gpu_upload_kernel.py.
 
 static const size_t PIN_CACHE_LIMIT = (size_t)1 << 30;
 static const size_t UPLOAD_CHUNK = (size_t)32 << 20;       // staging buffer of a row-store upload (upload_rows)

@@ -118,6 +118,8 @@ def test_asynchronous_row_store_upload(ctx, tmp_path):
     G, _ = synth.synth_genotypes(bp[:600], pops, seed=4)
     G = G[G.min(1) != G.max(1)][:512]
     packed, _ = panel.pack2bit(G, off)
+    # (the rows repeat every 512: a chunk or a word that landed a multiple of the period away would pass here -- where every byte
+    # lands is checked on unique rows in test_gpu_upload_kernel.py; this test is about the waits)
     rows = np.ascontiguousarray(np.tile(packed, (n_snp // 512 + 1, 1))[:n_snp])     # 100+ MB of 2-bit rows
     assert rows.nbytes > 3 * (32 << 20)
     w = rng.uniform(0.05, 0.3, len(pops))
