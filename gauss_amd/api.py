@@ -46,6 +46,7 @@ HOST_SYMBOLS = [
     "gauss_host_jepeg_rank", "gauss_host_jepeg_genome", "gauss_prepared_jepeg_plan", "gauss_prepared_jepeg_finish",
     "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
     "gauss_host_simulateLD", "gauss_host_simulate_draws", "gauss_host_clump",
+    "gauss_host_sumchi2", "gauss_host_sumchi2mix", "gauss_host_sumchi2_pval",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
     "gauss_host_dist_cs", "gauss_host_distmix_cs", "gauss_host_dist_susie", "gauss_host_distmix_susie", "gauss_host_dist_prs", "gauss_host_distmix_prs", "gauss_host_dist_ldscore", "gauss_host_distmix_ldscore", "gauss_host_dist_xsusie", "gauss_host_distmix_xsusie", "gauss_host_dist_coloc", "gauss_host_distmix_coloc",
@@ -107,6 +108,9 @@ def load_host():
     h.gauss_host_distmix.argtypes = [_vp, C.c_int, _i64, _i64, _i64, _strs, _dp, C.c_int] + files4 + [_dbl, C.POINTER(_vp)]
     h.gauss_host_jepeg.argtypes = [_vp, _cp, _cp] + files4 + [_dbl, C.POINTER(_vp)]
     h.gauss_host_jepegmix.argtypes = [_vp, _strs, _dp, C.c_int, _cp] + files4 + [_dbl, C.POINTER(_vp)]
+    h.gauss_host_sumchi2.argtypes = h.gauss_host_jepeg.argtypes[:-1] + [_dbl, C.POINTER(_vp)]            # ..., prune_r2, out
+    h.gauss_host_sumchi2mix.argtypes = h.gauss_host_jepegmix.argtypes[:-1] + [_dbl, C.POINTER(_vp)]
+    h.gauss_host_sumchi2_pval.argtypes = [_dp, C.c_int, _dbl, _dp, C.POINTER(C.c_int)]
     h.gauss_host_jepeg_rank.argtypes = [_vp, C.c_int, _cp, _strs, _dp, C.c_int, _cp] + files4 + [_dbl, C.c_int, C.c_int, C.POINTER(_vp)]
     h.gauss_host_jepeg_genome.argtypes = [_vp, C.c_int, C.c_int, _cp, _strs, _dp, C.c_int, _strs, _strs, _strs, _strs, _cp, _dbl, C.c_int, C.c_int,
                                           C.POINTER(_vp), C.POINTER(C.c_int32)]
@@ -1010,6 +1014,50 @@ def jepegmix(pop_wgt_df, input_file, annotation_file, reference_index_file, refe
                                   _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file),
                                   _af(af1_cutoff), C.byref(out)))
     return _table(h, out)[0]
+
+
+def _sumchi2_frame(h, out):
+    lam = np.asarray(_named(h, out)["lam"])
+    df, _ = _table(h, out)
+    df.attrs["lam"] = lam.reshape(len(df), 128)       # (the frame's attrs carry the eigenvalues: this call needs pandas)
+    return df
+
+
+def sumchi2(study_pop, input_file, annotation_file, reference_index_file, reference_data_file, reference_pop_desc_file,
+            af1_cutoff=None, prune_r2=0.9, ctx=None):
+    """The gene-based sum-of-chi2 test (fastBAT, VEGAS, MAGMA's SNP-wise mean model) of jepeg()'s genes on the pooled LD of
+    study_pop, on the GPU (gauss_host_sumchi2): per gene Q = sum z^2 over the SNPs that survive LD pruning at prune_r2 in position
+    order, against sum lambda_i chi2_1 with lambda the eigenvalues of the kept SNPs' LD.  Returns the frame geneid num_snp num_kept
+    chisq pval lam_max n_pos status top_snp top_snp_pval message, one row per gene; ``attrs["lam"]`` [n_gene, 128] holds the
+    eigenvalues.  At most 1 024 SNPs a gene and 128 after pruning (pval NaN and a message beyond); z is taken at face value (an
+    imputed z has variance `info`, not 1); pval is a saddlepoint approximation."""
+    h = load_host()
+    out = _vp()
+    _hcheck(h.gauss_host_sumchi2(_ctx(ctx), _enc(study_pop), _enc(input_file), _enc(annotation_file), _enc(reference_index_file),
+                                 _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
+                                 float("nan") if prune_r2 is None else float(prune_r2), C.byref(out)))
+    return _sumchi2_frame(h, out)
+
+
+def sumchi2mix(pop_wgt_df, input_file, annotation_file, reference_index_file, reference_data_file, reference_pop_desc_file,
+               af1_cutoff=None, prune_r2=0.9, ctx=None):
+    """sumchi2() of a mixed-ancestry study on the ancestry-weighted LD of jepegmix() (gauss_host_sumchi2mix)."""
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_sumchi2mix(_ctx(ctx), names, w.ctypes.data_as(_dp), n, _enc(input_file), _enc(annotation_file),
+                                    _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file),
+                                    _af(af1_cutoff), float("nan") if prune_r2 is None else float(prune_r2), C.byref(out)))
+    return _sumchi2_frame(h, out)
+
+
+def sumchi2_pval(lam, q, n_pos=False):
+    """gauss_host_sumchi2_pval (no GPU): P(sum lam_i chi2_1 > q); lam_i <= 0 or NaN are left out.  n_pos=True: (p, how many stay)."""
+    h = load_host()
+    l = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1)
+    p, k = C.c_double(), C.c_int()
+    _hcheck(h.gauss_host_sumchi2_pval(l.ctypes.data_as(_dp), len(l), float(q), C.byref(p), C.byref(k)))
+    return (p.value, k.value) if n_pos else p.value
 
 
 def jepeg_rank(kind, input_file, annotation_file, reference_index_file, reference_data_file, reference_pop_desc_file,

@@ -3,6 +3,8 @@
 
 // the kernels' constants that include/gauss_hip.h states to the caller (gauss_internal.h does not see that header)
 static_assert(gauss::CLUMP_M_MAX == GAUSS_CLUMP_MAX_M && gauss::CLUMP_KEYS_MAX == GAUSS_CLUMP_MAX_KEYS, "clumping: gauss_internal.h and include/gauss_hip.h disagree");
+static_assert(gauss::SC2_N_MAX == GAUSS_SUMCHI2_MAX_N && gauss::SC2_K_MAX == GAUSS_SUMCHI2_MAX_KEPT && gauss::SC2_TRAITS_MAX == GAUSS_SUMCHI2_MAX_TRAITS,
+              "sum of chi2: gauss_internal.h and include/gauss_hip.h disagree");
 static_assert(gauss::LDS_C == GAUSS_LDS_MAX_ANNOT && gauss::LDS_CHUNK == GAUSS_LDS_CHUNK, "LD scores: gauss_internal.h and include/gauss_hip.h disagree");
 
 // entry points that need the job's context
@@ -451,6 +453,87 @@ int gauss_gene_ld_batch_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int
     WinSpec w = ld_spec_rows(mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop, diag);
     w.gene_off = gene_off; w.n_gene = n_gene;
     return ld_common(ctx, w, on_device, out_blocks);
+}
+
+// gauss_gene_sumchi2[_rows]: the gene job of `w` (diag 1, gene blocks set by the caller), then sumchi2_kernel on its blocks
+static int sumchi2_common(gauss_ctx* ctx, const char* who, WinSpec w, int on_device, const double* z, int n_trait, double prune_r2,
+                          int32_t* out_kept, int32_t* out_n_kept, double* out_lam, double* out_q, int32_t* out_top,
+                          int32_t* out_status, int32_t* out_sweeps)
+{
+    if (!ctx || !w.geno_m) return fail(GAUSS_E_INVALID, "bad arguments to %s", who);
+    if (!w.gene_off || w.n_gene < 1) return fail(GAUSS_E_INVALID, "%s: gene_off is NULL or n_gene < 1", who);
+    if (!z) return fail(GAUSS_E_INVALID, "%s: z is NULL", who);
+    if (!out_kept) return fail(GAUSS_E_INVALID, "%s: out_kept is NULL", who);
+    if (!out_n_kept) return fail(GAUSS_E_INVALID, "%s: out_n_kept is NULL", who);
+    if (!out_lam) return fail(GAUSS_E_INVALID, "%s: out_lam is NULL", who);
+    if (!out_q) return fail(GAUSS_E_INVALID, "%s: out_q is NULL", who);
+    if (n_trait < 1 || n_trait > SC2_TRAITS_MAX)
+        return fail(GAUSS_E_INVALID, "%s: n_trait = %d; a call tests 1 .. %d traits", who, n_trait, SC2_TRAITS_MAX);
+    if (!(prune_r2 > 0.0 && prune_r2 <= 1.0)) return fail(GAUSS_E_INVALID, "%s: prune_r2 = %g is outside (0, 1]", who, prune_r2);
+    int max_n = 0;
+    for (int g = 0; g < w.n_gene; g++) {
+        const long long n = (long long)w.gene_off[g + 1] - w.gene_off[g];
+        if (n > SC2_N_MAX)
+            return fail(GAUSS_E_INVALID, "%s: gene %d holds %lld SNPs; a gene holds at most %d before pruning", who, g, n, SC2_N_MAX);
+        max_n = std::max(max_n, (int)std::max(n, 0ll));
+    }
+    JobGuard job(nullptr, job_free);
+    int rc = ld_job(ctx, w, on_device, job);
+    if (rc) return rc;
+    rc = job_run(job.get(), false);
+    if (rc) return rc;
+    // the blocks stay where the gene epilogue wrote them (out_ld, both triangles); the kernel runs behind the job on the same stream
+    hipStream_t st = ctx->stream;
+    const size_t S = (size_t)w.M, NG = (size_t)w.n_gene, T = (size_t)n_trait;
+    DevBuf d_z, d_kept, d_nk, d_lam, d_q, d_top, d_st, d_sw;
+    if (d_z.alloc(ctx, sizeof(double) * T * S) != hipSuccess || d_kept.alloc(ctx, sizeof(int) * S) != hipSuccess ||
+        d_nk.alloc(ctx, sizeof(int) * NG) != hipSuccess || d_lam.alloc(ctx, sizeof(double) * NG * SC2_K_MAX) != hipSuccess ||
+        d_q.alloc(ctx, sizeof(double) * T * NG) != hipSuccess || d_top.alloc(ctx, sizeof(int) * T * NG) != hipSuccess ||
+        d_st.alloc(ctx, sizeof(int) * NG) != hipSuccess || d_sw.alloc(ctx, sizeof(int) * NG) != hipSuccess)
+        return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes of Z-scores and eigenvalues) failed", sizeof(double) * (T * S + NG * SC2_K_MAX));
+    HIPCHK(hipMemcpyAsync(d_z.p, z, sizeof(double) * T * S, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_kept.p, 0, sizeof(int) * S, st));           // a row outside every gene is not kept
+    const Prob& p = job->plans[0].p;
+    Sumchi2Args a;
+    a.R = p.out_ld; a.gene_off = p.gene_off; a.gene_out_off = p.gene_out_off; a.z = d_z.as<double>();
+    a.kept = d_kept.as<int>(); a.n_kept = d_nk.as<int>(); a.lam = d_lam.as<double>(); a.q = d_q.as<double>();
+    a.top = d_top.as<int>(); a.status = d_st.as<int>(); a.sweeps = d_sw.as<int>();
+    a.prune_r2 = prune_r2; a.n_snp = w.M; a.n_gene = w.n_gene; a.n_trait = n_trait; a.m_lds = 0;
+    launch_sumchi2(a, max_n, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_kept, d_kept.p, sizeof(int) * S, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_n_kept, d_nk.p, sizeof(int) * NG, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_lam, d_lam.p, sizeof(double) * NG * SC2_K_MAX, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_q, d_q.p, sizeof(double) * T * NG, hipMemcpyDeviceToHost, st));
+    if (out_top) HIPCHK(hipMemcpyAsync(out_top, d_top.p, sizeof(int) * T * NG, hipMemcpyDeviceToHost, st));
+    if (out_status) HIPCHK(hipMemcpyAsync(out_status, d_st.p, sizeof(int) * NG, hipMemcpyDeviceToHost, st));
+    if (out_sweeps) HIPCHK(hipMemcpyAsync(out_sweeps, d_sw.p, sizeof(int) * NG, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return job_fetch(job.get());
+}
+
+int gauss_gene_sumchi2(gauss_ctx* ctx, int mode, const uint8_t* geno, int n_snp, int64_t ld,
+                       const int32_t* pop_off, const double* pop_wgt, int n_pop,
+                       const int32_t* gene_off, int n_gene, const double* z, int n_trait, double prune_r2,
+                       int32_t* out_kept, int32_t* out_n_kept, double* out_lam, double* out_q,
+                       int32_t* out_top, int32_t* out_status, int32_t* out_sweeps)
+{
+    WinSpec w = ld_spec(mode, geno, n_snp, ld, pop_off, pop_wgt, n_pop, 1.0);
+    w.gene_off = gene_off; w.n_gene = n_gene;
+    return sumchi2_common(ctx, "gauss_gene_sumchi2", w, 0, z, n_trait, prune_r2, out_kept, out_n_kept, out_lam, out_q, out_top,
+                          out_status, out_sweeps);
+}
+
+int gauss_gene_sumchi2_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows,
+                            int n_snp, const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop,
+                            const int32_t* gene_off, int n_gene, int on_device, const double* z, int n_trait, double prune_r2,
+                            int32_t* out_kept, int32_t* out_n_kept, double* out_lam, double* out_q,
+                            int32_t* out_top, int32_t* out_status, int32_t* out_sweeps)
+{
+    WinSpec w = ld_spec_rows(mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop, 1.0);
+    w.gene_off = gene_off; w.n_gene = n_gene;
+    return sumchi2_common(ctx, "gauss_gene_sumchi2_rows", w, on_device, z, n_trait, prune_r2, out_kept, out_n_kept, out_lam, out_q,
+                          out_top, out_status, out_sweeps);
 }
 
 // The per-population calls (gauss_ld_per_pop, _pairs, gauss_zmix_normal_eq) run the WEIGHTED layout with every weight 1: it keeps

@@ -248,6 +248,11 @@ constexpr int LDS_MAX_CHUNKS = 65535;  // chunks of a window: they are the y ext
 constexpr int CLUMP_T = 512;            // threads of clump_kernel: one workgroup per trait
 constexpr int CLUMP_M_MAX = 8192;      // GAUSS_CLUMP_MAX_M: keys, owner and bp of a region in LDS, 16 bytes a SNP (k_clump.hip)
 constexpr int CLUMP_KEYS_MAX = 64;     // GAUSS_CLUMP_MAX_KEYS: traits of one call, the x extent of clump_kernel's grid
+constexpr int SC2_T = 256;             // threads of sumchi2_kernel: one workgroup per gene
+constexpr int SC2_N_MAX = 1024;        // GAUSS_SUMCHI2_MAX_N: SNPs of a gene before pruning; flags and the kept list in LDS (k_sumchi2.hip)
+constexpr int SC2_K_MAX = 128;         // GAUSS_SUMCHI2_MAX_KEPT: order of the eigenvalue solve; the kept block in LDS, 129 doubles a row
+constexpr int SC2_TRAITS_MAX = 64;     // GAUSS_SUMCHI2_MAX_TRAITS: traits of one call, one thread each for Q
+constexpr int SC2_MAX_SWEEPS = 30;     // Jacobi sweeps before GAUSS_ST_NOCONV (fp64 Jacobi at order 128 takes 7 .. 9)
 constexpr int lds_chunks(int M, int U) { return (M + LDS_CHUNK - 1) / LDS_CHUNK + (U + LDS_CHUNK - 1) / LDS_CHUNK; }      // measured rows' chunks, then the others'
 constexpr int susie_uld(int U) { return (U + 63) & ~63; }   // row pitch of W and Y
 // Prob::susie_ws in doubles.  Y = X C^T and W = X^T Y = B11^-1 B12 [Mld][uld], the window's; then one block per fitted trait (trait t
@@ -550,6 +555,26 @@ struct ClumpArgs {
     int M;
 };
 void launch_clump(const ClumpArgs& a, int n_key, hipStream_t s);
+// Gene-based sum-of-chi2 (k_sumchi2.hip) on the blocks a gene job left in out_ld: one workgroup per gene.  The arguments travel by
+// value; every pointer is a device pointer and none is null
+struct Sumchi2Args {
+    const double* R;                // the gene job's out_ld: block g is n_g x n_g, both triangles, at gene_out_off[g]
+    const int* gene_off;            // [n_gene + 1] the job's
+    const long long* gene_out_off;  // [n_gene] the job's
+    const double* z;                // [n_trait][n_snp]
+    int* kept;                      // [n_snp] 0 / 1
+    int* n_kept;                    // [n_gene]
+    double* lam;                    // [n_gene][SC2_K_MAX]
+    double* q;                      // [n_trait][n_gene]
+    int* top;                       // [n_trait][n_gene]
+    int* status;                    // [n_gene]
+    int* sweeps;                    // [n_gene]
+    double prune_r2;
+    int n_snp, n_gene, n_trait;
+    int m_lds;                      // order of the kept block the launch's dynamic LDS holds (even, <= SC2_K_MAX)
+};
+// max_n: the largest gene's SNP count (it sizes the dynamic LDS)
+void launch_sumchi2(Sumchi2Args a, int max_n, hipStream_t s);
 void launch_pack2bit(const uint8_t* d_in, long long ld_in, uint8_t* d_out, long long ld_out, int n_snp,
                      const int* d_pop_off, const int* d_blk_off, int n_pop, hipStream_t s);
 void launch_h2d_copy(void* d_dst, const void* pinned_src, size_t bytes, hipStream_t s);

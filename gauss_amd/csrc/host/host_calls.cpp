@@ -1335,6 +1335,89 @@ int gauss_host_jepegmix(gauss_ctx* ctx, const char* const* pop_names, const doub
                      reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, 0, 1, out);
 }
 
+// sumchi2() / sumchi2mix(): jepeg's genes and SNPs (the same data layer, the same measured list and gene_off; categ and wgt are not
+// read), tested by the plain sum of chi2 on the GPU (gauss_gene_sumchi2[_rows]); the packed and byte paths are chosen as in run_jepeg
+static int run_sumchi2(gauss_ctx* ctx, int kind, const char* study_pop, const char* const* names, const double* wgts, int nw,
+                       const char* input, const char* annotation, const char* index, const char* data, const char* desc,
+                       double af1_cutoff, double prune_r2, gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    const double r2 = std::isnan(prune_r2) ? 0.9 : prune_r2;                       // fastBAT's default
+    if (!(r2 > 0.0 && r2 <= 1.0)) return herr("sumchi2: prune_r2 = %g is outside (0, 1]", r2);
+    gauss_prepared* p = nullptr;
+    CallArgs c = call_mix(kind, 0, 0, 0, 0, names, wgts, nw, input, index, data, desc, af1_cutoff);
+    c.study_pop = study_pop;
+    if (prepare_files(c, annotation, !env_flag("GAUSS_HOST_FULL_MAP", false), &p)) return -1;
+    std::unique_ptr<gauss_prepared> hold(p);
+    const Args& a = p->args;
+    const int ng = p->gene_off.empty() ? 0 : (int)p->gene_off.size() - 1;
+    const int S = ng > 0 ? p->gene_off[(size_t)ng] : 0;
+    // jepeg's sort by gene id (std::sort) leaves the order inside a gene open; the pruning is defined in position order, so each gene's
+    // rows are put in the order of the SNP list (chromosome, position), and the rows reach the GPU by index in that order
+    std::vector<int32_t> perm((size_t)S);
+    for (int i = 0; i < S; i++) perm[(size_t)i] = i;
+    for (int g = 0; g < ng; g++)
+        std::stable_sort(perm.begin() + p->gene_off[(size_t)g], perm.begin() + p->gene_off[(size_t)g + 1],
+                         [&](int32_t x, int32_t y) { return p->measured_rows[(size_t)x] < p->measured_rows[(size_t)y]; });
+    std::vector<std::string> geneid, rsid;
+    std::vector<double> z;
+    for (int i = 0; i < S; i++) { const Snp* s = p->measured[(size_t)perm[(size_t)i]]; rsid.push_back(s->rsid); z.push_back(s->z); }
+    for (int g = 0; g < ng; g++) {
+        const int r0 = p->gene_off[(size_t)g], n = p->gene_off[(size_t)g + 1] - r0;
+        geneid.push_back(n > 0 ? p->measured[(size_t)r0]->geneid : std::string());
+        if (n > GAUSS_SUMCHI2_MAX_N)
+            return herr("sumchi2: gene %s holds %d SNPs of the study; a gene holds at most %d", geneid.back().c_str(), n, GAUSS_SUMCHI2_MAX_N);
+    }
+    std::vector<int32_t> kept((size_t)std::max(S, 1)), n_kept((size_t)std::max(ng, 1), 0), top((size_t)std::max(ng, 1), -1);
+    std::vector<int32_t> status((size_t)std::max(ng, 1), GAUSS_ST_SUMCHI2_EMPTY);       // (no SNP at all: no GPU call, every gene is empty)
+    std::vector<double> lam((size_t)std::max(ng, 1) * GAUSS_SUMCHI2_MAX_KEPT, NAN), q((size_t)std::max(ng, 1), 0.0);
+    if (S > 0 && ng > 0) {
+        const int mode = (kind == GAUSS_KIND_JEPEG) ? GAUSS_MODE_POOLED : GAUSS_MODE_WEIGHTED;
+        const int n_pop = (int)p->pop_off.size() - 1;
+        int rc;
+        if (p->packed_rows) {
+            const uint8_t* store = nullptr;
+            int on_device = 0;
+            panel_rows(ctx, a.reference_data_file, *a.pk, &store, &on_device);
+            std::vector<int32_t> rows((size_t)S);
+            for (int i = 0; i < S; i++) rows[(size_t)i] = p->store_rows_m[(size_t)perm[(size_t)i]];
+            rc = gauss_gene_sumchi2_rows(ctx, mode, store, a.pk->row_bytes(), GAUSS_GENO_2BIT, rows.data(), S, p->pop_off.data(),
+                                         p->pop_src_off.data(), p->pop_wgt.data(), n_pop, p->gene_off.data(), ng, on_device, z.data(), 1, r2,
+                                         kept.data(), n_kept.data(), lam.data(), q.data(), top.data(), status.data(), nullptr);
+        } else      // the byte matrix of the measured SNPs as a host row store
+            rc = gauss_gene_sumchi2_rows(ctx, mode, p->gm.data(), p->ld, GAUSS_GENO_U8, perm.data(), S, p->pop_off.data(), nullptr,
+                                         p->pop_wgt.data(), n_pop, p->gene_off.data(), ng, 0, z.data(), 1, r2, kept.data(), n_kept.data(),
+                                         lam.data(), q.data(), top.data(), status.data(), nullptr);
+        if (rc != 0) return herr("%s", gauss_last_error());
+    }
+    *out = sumchi2_output(geneid, p->gene_off, rsid, z, n_kept.data(), lam.data(), q.data(), top.data(), status.data());
+    return 0;
+}
+
+int gauss_host_sumchi2(gauss_ctx* ctx, const char* study_pop, const char* input_file, const char* annotation_file,
+                       const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                       double af1_cutoff, double prune_r2, gauss_table** out)
+{
+    return run_sumchi2(ctx, GAUSS_KIND_JEPEG, study_pop, nullptr, nullptr, 0, input_file, annotation_file, reference_index_file,
+                       reference_data_file, reference_pop_desc_file, af1_cutoff, prune_r2, out);
+}
+
+int gauss_host_sumchi2mix(gauss_ctx* ctx, const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                          const char* input_file, const char* annotation_file, const char* reference_index_file,
+                          const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,
+                          double prune_r2, gauss_table** out)
+{
+    return run_sumchi2(ctx, GAUSS_KIND_JEPEGMIX, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file,
+                       reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, prune_r2, out);
+}
+
+int gauss_host_sumchi2_pval(const double* lam, int n, double q, double* p, int* n_pos)
+{
+    if (!lam || n < 0 || !p) return herr("bad arguments to gauss_host_sumchi2_pval");
+    *p = sumchi2_pval(lam, n, q, n_pos);
+    return 0;
+}
+
 int gauss_host_jepeg_rank(gauss_ctx* ctx, int kind, const char* study_pop, const char* const* pop_names, const double* pop_wgts,
                           int n_pop_wgt, const char* input_file, const char* annotation_file, const char* reference_index_file,
                           const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,

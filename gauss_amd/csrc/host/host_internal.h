@@ -772,3 +772,12 @@ int clump_keys(double p1, double p2, double r2, double kb, ClumpKeys& out);
 // it -- and the named matrix `clumps` [n_clumps x 4], one row per clump in rank order: index row (from 0), size, bp of the first
 // member, bp of the last.  owner / rank / r2 [M] as gauss_ld_clump_rows returned them
 void clump_output(gauss_table& t, const std::vector<double>& z, const int32_t* owner, const int32_t* rank, const double* r2, int n_clumps);
+// sumchi2(): P(sum lambda_i chi2_1 > q) (host_tables.cpp; the method: gauss_host_sumchi2_pval in include/gauss_host.h).  lambda_i <= 0
+// or NaN are left out; n_pos (may be null): how many stay
+double sumchi2_pval(const double* lam, int n, double q, int* n_pos);
+// ... and its table, one row per gene: geneid num_snp num_kept chisq pval lam_max n_pos status top_snp top_snp_pval message, and the
+// named matrix `lam` [n_gene x 128].  gene_off [n_gene + 1] into rsid / z (the measured list); n_kept, q, top, status [n_gene] and lam
+// [n_gene][128] as gauss_gene_sumchi2 returned them for one trait (null with n_gene = 0)
+gauss_table* sumchi2_output(const std::vector<std::string>& geneid, const std::vector<int32_t>& gene_off, const std::vector<std::string>& rsid,
+                            const std::vector<double>& z, const int32_t* n_kept, const double* lam, const double* q, const int32_t* top,
+                            const int32_t* status);

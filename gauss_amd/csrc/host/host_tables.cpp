@@ -737,6 +737,80 @@ void clump_output(gauss_table& t, const std::vector<double>& z, const int32_t* o
     t.put_named("clumps", (int)n, 4, std::move(cm));
 }
 
+// P(sum lambda_i chi2_1 > q): the exact normal tail for one lambda, else Kuonen's saddlepoint approximation (Biometrika 86, 1999), with
+// the one-term Edgeworth tail where the saddlepoint formula is 0 / 0 (q at the mean).  tests/sumchi2_ref.py holds the same steps.
+constexpr int SUMCHI2_BISECT = 100;         // halvings of the bracket of the saddlepoint
+constexpr double SUMCHI2_EDGE = 1e-3;       // |x| below which the Edgeworth tail stands in
+double sumchi2_pval(const double* lam, int n, double q, int* n_pos)
+{
+    std::vector<double> l;
+    for (int i = 0; i < n; i++) if (lam[i] > 0.0) l.push_back(lam[i]);              // (a NaN compares false)
+    const int k = (int)l.size();
+    if (n_pos) *n_pos = k;
+    if (k == 0 || std::isnan(q)) return NAN;
+    if (q <= 0.0) return 1.0;
+    if (k == 1) return 2 * pnorm_upper(sqrt(q / l[0]));
+    double s1 = 0, s2 = 0, s3 = 0, lmax = 0;
+    for (double v : l) { s1 += v; s2 += v * v; s3 += v * v * v; lmax = std::max(lmax, v); }
+    const double x = (q - s1) / sqrt(2 * s2);
+    if (fabs(x) < SUMCHI2_EDGE) {
+        const double k3 = 8 * s3 / ((2 * s2) * sqrt(2 * s2));
+        return pnorm_upper(x) + exp(-0.5 * x * x) / 2.5066282746310002 * (k3 / 6) * (x * x - 1);
+    }
+    // K'(zeta) = sum lambda / (1 - 2 zeta lambda) rises from 0 (zeta -> -inf) through sum lambda (zeta = 0) to +inf (zeta -> 1 / (2 lmax));
+    // below the mean K'(-k / (2 q)) < q, because every term is below 1 / (2 |zeta|)
+    double lo = q > s1 ? 0.0 : -0.5 * k / q, hi = q > s1 ? 0.5 / lmax : 0.0;
+    for (int it = 0; it < SUMCHI2_BISECT; it++) {
+        const double mid = 0.5 * (lo + hi);
+        double k1 = 0;
+        for (double v : l) k1 += v / (1 - 2 * mid * v);
+        if (k1 > q || !(1 - 2 * mid * lmax > 0)) hi = mid; else lo = mid;
+    }
+    const double zeta = 0.5 * (lo + hi);
+    double K = 0, K2 = 0;
+    for (double v : l) { const double d = 1 - 2 * zeta * v; K += log1p(-2 * zeta * v); K2 += 2 * v * v / (d * d); }
+    K *= -0.5;
+    const double w = (zeta < 0 ? -1.0 : 1.0) * sqrt(2 * (zeta * q - K)), v = zeta * sqrt(K2);
+    const double p = pnorm_upper(w + log(v / w) / w);
+    return std::isfinite(p) ? p : NAN;
+}
+
+gauss_table* sumchi2_output(const std::vector<std::string>& geneid, const std::vector<int32_t>& gene_off, const std::vector<std::string>& rsid,
+                            const std::vector<double>& z, const int32_t* n_kept, const double* lam, const double* q, const int32_t* top,
+                            const int32_t* status)
+{
+    const size_t ng = geneid.size(), K = GAUSS_SUMCHI2_MAX_KEPT;
+    std::unique_ptr<gauss_table> t(new gauss_table());
+    t->widen(11);
+    Column &gid = t->add("geneid", GAUSS_COL_STR), &ns = t->add("num_snp", GAUSS_COL_INT), &nk = t->add("num_kept", GAUSS_COL_INT);
+    Column &cq = t->add("chisq", GAUSS_COL_DBL), &pv = t->add("pval", GAUSS_COL_DBL), &lm = t->add("lam_max", GAUSS_COL_DBL);
+    Column &np = t->add("n_pos", GAUSS_COL_INT), &st = t->add("status", GAUSS_COL_INT), &ts = t->add("top_snp", GAUSS_COL_STR);
+    Column &tp = t->add("top_snp_pval", GAUSS_COL_DBL), &msg = t->add("message", GAUSS_COL_STR);
+    std::vector<double> cm(ng * K, NAN);                                // column-major [ng x 128]
+    for (size_t g = 0; g < ng; g++) {
+        const int r0 = gene_off[g], n = gene_off[g + 1] - r0;
+        const double* l = lam + g * K;
+        for (size_t c = 0; c < K; c++) cm[c * ng + g] = l[c];
+        int pos = 0;
+        const bool solved = status[g] == 0;
+        const double p = solved ? sumchi2_pval(l, (int)K, q[g], &pos) : NAN;
+        gid.s.push_back(geneid[g]); ns.i.push_back(n); nk.i.push_back(n_kept[g]); cq.d.push_back(q[g]); pv.d.push_back(p);
+        lm.d.push_back(solved ? l[0] : NAN); np.i.push_back(pos); st.i.push_back(status[g]);
+        const int tr = top[g];
+        const bool has = tr >= 0 && tr < n;
+        ts.s.emplace_back(has ? rsid[(size_t)(r0 + tr)] : ".");
+        tp.d.push_back(has ? 2 * pnorm_upper(fabs(z[(size_t)(r0 + tr)])) : NAN);
+        char why[160] = "";
+        if (status[g] & GAUSS_ST_SUMCHI2_TOOLARGE)
+            snprintf(why, sizeof why, "%d SNPs survive the pruning; the eigenvalue solve takes at most %d (prune harder)", n_kept[g], GAUSS_SUMCHI2_MAX_KEPT);
+        else if (status[g] & GAUSS_ST_SUMCHI2_EMPTY) snprintf(why, sizeof why, "no SNP of the gene is kept");
+        else if (status[g] & GAUSS_ST_NOCONV) snprintf(why, sizeof why, "the eigenvalue solve did not converge");
+        msg.s.emplace_back(why);
+    }
+    t->put_named("lam", (int)ng, (int)K, std::move(cm));
+    return t.release();
+}
+
 gauss_table* qcat_output(gauss_prepared& p)     // qcat.cpp:94-131 / qcatmix.cpp:102-139
 {
     const bool mix = p.kind == GAUSS_KIND_QCATMIX;

@@ -315,6 +315,55 @@ def gene_ld_batch_rows(store, rows, pop_off, gene_off, pop_wgt=None, mode=MODE_P
     return blocks
 
 
+def _sumchi2(call, S, gene_off, z, prune_r2):
+    """The trait and output arguments of gauss_gene_sumchi2[_rows] and the returned dict; `call(tail)` makes the call."""
+    go = np.ascontiguousarray(gene_off, dtype=np.int32)
+    za = np.ascontiguousarray(z, dtype=np.float64)
+    one = za.ndim == 1
+    za = za.reshape(1, -1) if one else za
+    if za.ndim != 2 or za.shape[1] != S:
+        raise ValueError(f"z has shape {np.shape(z)}: expected ({S},) or (T, {S})")
+    T, G = za.shape[0], len(go) - 1
+    kept, n_kept = np.full(S, -2, dtype=np.int32), np.full(max(G, 0), -2, dtype=np.int32)
+    lam, q = np.zeros((max(G, 0), _lib.SUMCHI2_MAX_KEPT)), np.zeros((T, max(G, 0)))
+    top, status, sweeps = np.full((T, max(G, 0)), -2, dtype=np.int32), np.full(max(G, 0), -2, dtype=np.int32), np.full(max(G, 0), -2, dtype=np.int32)
+    check(call([go.ctypes.data_as(_ip), G], [za.ctypes.data_as(_dp), T, float(prune_r2), kept.ctypes.data_as(_ip),
+                                             n_kept.ctypes.data_as(_ip), lam.ctypes.data_as(_dp), q.ctypes.data_as(_dp),
+                                             top.ctypes.data_as(_ip), status.ctypes.data_as(_ip), sweeps.ctypes.data_as(_ip)]))
+    from . import api       # (the p-value is the host library's: gauss_host_sumchi2_pval)
+    pval = np.array([[api.sumchi2_pval(lam[g], q[t, g]) if status[g] == 0 else np.nan for g in range(G)] for t in range(T)]).reshape(T, max(G, 0))
+    if one:
+        q, top, pval = q[0], top[0], pval[0]
+    return dict(kept=kept, n_kept=n_kept, lam=lam, q=q, top=top, status=status, sweeps=sweeps, pval=pval)
+
+
+def gene_sumchi2(geno, pop_off, gene_off, z, pop_wgt=None, mode=MODE_WEIGHTED, prune_r2=0.9, ctx=None):
+    """gauss_gene_sumchi2 on the rows of a byte matrix: the gene-based sum-of-chi2 test of every gene (rows gene_off[g] ..
+    gene_off[g+1]) on the LD blocks gene_ld_batch(diag=1) would return, which stay on the device.  z [S] or [T, S].  Returns
+    dict(kept [S] 0/1, n_kept [G], lam [G, 128] descending with NaN beyond n_kept, q [T, G], top [T, G] (row inside the gene, -1:
+    none), status [G], sweeps [G], pval [T, G] from gauss_host_sumchi2_pval; NaN where status is not 0).  A 1-D z gives 1-D q, top
+    and pval."""
+    ctx = ctx or default_context()
+    g = _lib.as_u8(geno)
+    po, w = _pops(pop_off, pop_wgt)
+    S = g.shape[0]
+    return _sumchi2(lambda genes, tail: ctx.lib.gauss_gene_sumchi2(ctx.handle, int(mode), g.ctypes.data, S, g.strides[0], po.ctypes.data_as(_ip),
+                                                                        _lib.ptr(w, _dp), len(po) - 1, *genes, *tail), S, gene_off, z, prune_r2)
+
+
+def gene_sumchi2_rows(store, rows, pop_off, gene_off, z, pop_wgt=None, mode=MODE_WEIGHTED, prune_r2=0.9, fmt=_lib.GENO_2BIT,
+                      pop_src_off=None, ctx=None):
+    """gene_sumchi2 on the store rows `rows` (a numpy matrix of host rows, a RowStore or a raw device pointer, as
+    gene_ld_batch_rows; rows None: rows 0 .. S-1 of a numpy matrix)."""
+    ctx = ctx or default_context()
+    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
+    po, w = _pops(pop_off, pop_wgt)
+    S = len(r) if r is not None else store.shape[0]
+    return _sumchi2(lambda genes, tail: ctx.lib.gauss_gene_sumchi2_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S,
+                                                                             po.ctypes.data_as(_ip), _lib.ptr(so, _ip), _lib.ptr(w, _dp),
+                                                                             len(po) - 1, *genes, on_dev, *tail), S, gene_off, z, prune_r2)
+
+
 # lassosum's grid: the default of prs=dict(...)
 PRS_S = (0.2, 0.5, 0.9, 1.0)
 PRS_LAM = tuple(float(v) for v in np.exp(np.linspace(np.log(0.1), np.log(0.001), 20)))

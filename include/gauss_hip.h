@@ -59,6 +59,8 @@ extern "C" {
 #define GAUSS_ST_SUSIE_NOCONV 16 /* multi-causal fit: susie_max_sweeps sweeps ran without delta < susie_tol (values of the last sweep) */
 #define GAUSS_ST_SUSIE_NOFIT  32 /* multi-causal fit: MakePosDef repaired B11 (GAUSS_ST_CLAMPED), the window is not fitted      */
 #define GAUSS_ST_PRS_NOCONV  64 /* polygenic score weights: a (s, lam) ran prs_max_sweeps sweeps without delta < prs_tol r_max (last sweep's values) */
+#define GAUSS_ST_SUMCHI2_TOOLARGE 128 /* gauss_gene_sumchi2: more than GAUSS_SUMCHI2_MAX_KEPT SNPs of the gene survive the pruning (eigenvalues NaN) */
+#define GAUSS_ST_SUMCHI2_EMPTY    256 /* gauss_gene_sumchi2: no SNP of the gene is kept (an empty gene, or every row NaN) */
 
 typedef struct gauss_ctx gauss_ctx;
 typedef struct gauss_job gauss_job;
@@ -706,6 +708,47 @@ int gauss_ld_clump_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t 
                         int on_device, const int32_t* bp, const double* key, int n_key, int64_t radius, double r2_min,
                         double key_index, double key_member,
                         int32_t* out_owner, int32_t* out_rank, double* out_r2, int32_t* out_n_clumps);
+
+/* Gene-based sum-of-chi2 test (the statistic of fastBAT, VEGAS and MAGMA's SNP-wise mean model) of n_gene genes on their LD
+ * blocks, which are formed as gauss_gene_ld_batch[_rows] forms them with diag = 1 (same rows, same bits) and never leave the
+ * device.  Gene g owns rows [gene_off[g], gene_off[g+1]), n of them, with block R.  z [n_trait][n_snp]: one row per trait, the
+ * traits share the LD, the pruning and the eigenvalues.  Per gene:
+ *     nanrow[i] = n > 1 and R_ij is NaN for every j != i        (a monomorphic SNP; in a gene of one SNP the row is kept)
+ *     for i = 0 .. n-1 in row order (never by z: pruning by significance would bias the test):
+ *         nanrow[i] or dropped[i]: continue
+ *         i is kept;  every j > i with R_ij * R_ij > prune_r2 is dropped    (one rounded fp64 product, strict; a NaN compares false)
+ *     k = kept rows;  out_kept[row] = 1 for a kept row, else 0;  out_n_kept[g] = k
+ *     lambda = eigenvalues of R[kept][kept], descending: out_lam[g][0 .. k), NaN beyond k
+ *     per trait t:  out_q[t][g] = sum of z_ti^2 over the kept rows, added in ascending row order (a NaN z of a kept row makes that
+ *                   trait's Q NaN);  out_top[t][g] = the row, counted inside the gene, with the largest z^2 among ALL n rows whose z is
+ *                   finite, kept or not (ties: the smaller row; none: -1)
+ * prune_r2 = 1 prunes nothing (r^2 > 1 never holds); fastBAT's default is 0.9.  Under the null Q ~ sum lambda_i chi2_1:
+ * gauss_host_sumchi2_pval (include/gauss_host.h) turns lambda and Q into a p-value.  The eigenvalues come from a cyclic two-sided
+ * Jacobi solve in LDS (k_sumchi2.hip states the rotation order, the skip rule |a_pq| <= 4 * 2^-52 ||A||_F and the summation order of
+ * the norm): every sum has a fixed order, so the outputs do not depend on the source format of the rows, on the other genes of the
+ * call or on the run.  The weighted LD estimator is not exactly positive semidefinite: a lambda may be slightly negative.
+ * out_status[g]: 0, or GAUSS_ST_SUMCHI2_EMPTY (k = 0: an empty gene, or every row NaN; Q = 0), GAUSS_ST_SUMCHI2_TOOLARGE (k >
+ * GAUSS_SUMCHI2_MAX_KEPT: every lambda NaN, out_n_kept = k, Q and top still written), GAUSS_ST_NOCONV (30 sweeps without
+ * convergence: every lambda NaN).  out_sweeps[g]: Jacobi sweeps made, the last, rotation-free one included (0 where nothing was
+ * solved).  out_kept [n_snp] int32, out_n_kept [n_gene], out_lam [n_gene][GAUSS_SUMCHI2_MAX_KEPT], out_q [n_trait][n_gene] are
+ * required; out_top [n_trait][n_gene], out_status [n_gene], out_sweeps [n_gene] may be NULL.
+ * Refused (GAUSS_E_INVALID, before anything is allocated): a NULL required pointer; n_trait outside 1 .. GAUSS_SUMCHI2_MAX_TRAITS;
+ * prune_r2 outside (0, 1] or NaN; a gene of more than GAUSS_SUMCHI2_MAX_N SNPs; and whatever gauss_gene_ld_batch[_rows] refuses.
+ * A row outside every gene gets out_kept 0.  Blocking. */
+#define GAUSS_SUMCHI2_MAX_N      1024   /* SNPs of one gene before pruning */
+#define GAUSS_SUMCHI2_MAX_KEPT    128
+#define GAUSS_SUMCHI2_MAX_TRAITS   64
+int gauss_gene_sumchi2(gauss_ctx* ctx, int mode, const uint8_t* geno, int n_snp, int64_t ld,
+                       const int32_t* pop_off, const double* pop_wgt, int n_pop,
+                       const int32_t* gene_off, int n_gene, const double* z, int n_trait, double prune_r2,
+                       int32_t* out_kept, int32_t* out_n_kept, double* out_lam, double* out_q,
+                       int32_t* out_top, int32_t* out_status, int32_t* out_sweeps);
+/* ... over rows of a row store: store / ld / geno_format / rows / pop_src_off / on_device as gauss_gene_ld_batch_rows */
+int gauss_gene_sumchi2_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows,
+                            int n_snp, const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop,
+                            const int32_t* gene_off, int n_gene, int on_device, const double* z, int n_trait, double prune_r2,
+                            int32_t* out_kept, int32_t* out_n_kept, double* out_lam, double* out_q,
+                            int32_t* out_top, int32_t* out_status, int32_t* out_sweeps);
 
 /* Per-population Pearson correlations of every SNP pair (prep_zmix5, zmix.cpp:158-176: CalCor on each
  * population's genotype strings, util.cpp:153-169).  out is [n_pop][n_snp*(n_snp-1)/2], population-major,

@@ -563,6 +563,35 @@ int gauss_host_clump(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, 
                      int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
                      const char* reference_pop_desc_file, double af1_cutoff, double p1, double p2, double r2, double kb, gauss_table** out);
 
+/* sumchi2() / sumchi2mix(): the gene-based sum-of-chi2 test (fastBAT, VEGAS, MAGMA's SNP-wise mean model) on the pooled /
+ * ancestry-weighted LD, which never leaves the GPU (gauss_gene_sumchi2, include/gauss_hip.h: the pruning and the eigenvalues).  The
+ * arguments are gauss_host_jepeg's / gauss_host_jepegmix's plus prune_r2 (NaN, not given: 0.9, fastBAT's default; outside (0, 1]:
+ * refused).  The genes and their SNPs are exactly jepeg's for the same files (the annotation's categ and wgt columns are not used).
+ * Inside a gene the SNPs are taken in position order (the order of the SNP list), whatever order jepeg's sort by gene id left them in.
+ * Q = sum z^2 over the gene's SNPs that survive the pruning in position order; under the null Q ~ sum lambda_i chi2_1 with lambda the
+ * eigenvalues of the kept SNPs' LD; pval = gauss_host_sumchi2_pval(lambda, Q).  Result: one row per gene, columns geneid num_snp
+ * num_kept chisq pval lam_max n_pos status top_snp top_snp_pval message (top_snp: the SNP with the largest z^2 among all the gene's
+ * SNPs, top_snp_pval = 2 pnorm(-|z|) of it; status: GAUSS_ST_* bits of gauss_gene_sumchi2; message: why pval is NaN, else empty),
+ * and the named matrix "lam" [n_gene x 128]: each gene's eigenvalues, descending, NaN beyond num_kept.  A gene of more than
+ * GAUSS_SUMCHI2_MAX_N (1 024) SNPs is refused; one whose pruned set exceeds GAUSS_SUMCHI2_MAX_KEPT (128), or whose solve did not
+ * converge, gets pval NaN and a message.  z is taken at face value (an imputed z has variance `info`, not 1).  One rank only. */
+int gauss_host_sumchi2(gauss_ctx* ctx, const char* study_pop, const char* input_file, const char* annotation_file,
+                       const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
+                       double af1_cutoff, double prune_r2, gauss_table** out);
+int gauss_host_sumchi2mix(gauss_ctx* ctx, const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
+                          const char* input_file, const char* annotation_file, const char* reference_index_file,
+                          const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,
+                          double prune_r2, gauss_table** out);
+/* P(sum_i lam_i chi2_1 > q), a pure function (no GPU).  lam [n]; lam_i <= 0 or NaN are left out (the weighted LD estimator is not
+ * exactly positive semidefinite) and *n_pos (may be NULL) reports how many stay.  None left, or q NaN: NaN.  q <= 0: 1.  One left: the
+ * exact tail 2 pnorm(-sqrt(q / lam)).  Else Kuonen's saddlepoint approximation (Biometrika 86, 1999): K(zeta) = -1/2 sum log1p(-2 zeta
+ * lam_i); K'(zeta) = q solved on zeta < 1 / (2 lam_max) by 100 halvings of the bracket [0, 1 / (2 lam_max)] (q above the mean sum lam)
+ * or [-n_pos / (2 q), 0] (below it); w = sign(zeta) sqrt(2 (zeta q - K)), v = zeta sqrt(K''), p = pnorm_upper(w + log(v / w) / w) in the
+ * library's own normal tail (1e-300 is reachable).  Where x = (q - sum lam) / sqrt(2 sum lam^2) has |x| < 1e-3 that formula is 0 / 0:
+ * there the one-term Edgeworth tail pnorm_upper(x) + dnorm(x) (kappa3 / 6) (x^2 - 1), kappa3 = 8 sum lam^3 / (2 sum lam^2)^1.5.  An
+ * approximation: DESIGN.md states its measured accuracy against numerical inversion. */
+int gauss_host_sumchi2_pval(const double* lam, int n, double q, double* p, int* n_pos);
+
 #define GAUSS_ZMIX_POPULATION      0
 #define GAUSS_ZMIX_SUPERPOPULATION 1
 int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
