@@ -43,23 +43,17 @@ static CallArgs call_pop(int kind, int chr, int64_t start_bp, int64_t end_bp, in
     return {kind, chr, start_bp, end_bp, wing, study_pop, nullptr, nullptr, 0, input, index, data, desc, af1_cutoff};
 }
 
-// The window of a one-window call on a sorted packed panel, built as the chromosome driver builds its windows (host_chrom.cpp:
-// LeanWindow -- a merge of the study's rows and the panel's SNP table instead of per-SNP objects in a map: ~0.1 ms against 0.7-1.0).
-// Returns 1 -- take the literal path, prepare_opened -- for an unsorted or text panel, a call over every chromosome or
-// GAUSS_HOST_FULL_MAP=1; errors come in prepare()'s order: arguments, description file, populations, study file.
-struct OneWindow {
-    ChromSetup cs;
-    LeanWindow w;                       // points into cs: a OneWindow stays where it was built
-};
-static int one_window_build(OneWindow& ow, const CallArgs& c, const std::string& panel_path, const std::shared_ptr<PackedPanel>& pk)
+// ... and of a gene call: no window, and both forms (the rank entry points take either): the kind says which one is read
+static CallArgs call_gene(int kind, const char* study_pop, const char* const* pop_names, const double* pop_wgts, int n_pop_wgt, const char* input,
+                          const char* index, const char* data, const char* desc, double af1_cutoff)
 {
-    if (c.chr <= 0 || env_flag("GAUSS_HOST_FULL_MAP", false) || !pk || !pk->header().sorted) return 1;
-    if (chrom_setup(ow.cs, c.kind, c.chr, c.wing, c.study_pop, c.pop_names, c.pop_wgts, c.n_pop_wgt, c.input, panel_path, c.desc, c.af1_cutoff, pk,
-                    nullptr)) return -1;
-    std::string err;
-    ow.cs.gw = load_gwas_cached(c.input, err);
-    if (!ow.cs.gw) return herr("%s", err.c_str());
-    return lean_window_build(ow.w, ow.cs, c.start_bp, c.end_bp) ? -1 : 0;
+    return {kind, 0, 0, 0, 0, study_pop, pop_names, pop_wgts, n_pop_wgt, input, index, data, desc, af1_cutoff};
+}
+
+static bool mix_kind(int kind)                               // the kinds that read pop_names / pop_wgts, not study_pop
+{
+    return kind == GAUSS_KIND_COMPUTELD || kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_JEPEGMIX || kind == GAUSS_KIND_QCATMIX ||
+           kind == GAUSS_KIND_PREP_RECESSIVE || kind == GAUSS_KIND_LDSCOREMIX;
 }
 
 // gauss_host_prepare on a panel that open_panel has resolved already (panel_path, pk: empty for a text panel)
@@ -79,9 +73,7 @@ static int prepare_opened(const CallArgs& c, const char* annotation_file, const 
     a.pk = pk;
     a.drop_wing_unmeasured = pk && (kind == GAUSS_KIND_DIST || kind == GAUSS_KIND_DISTMIX);
     a.af1_cutoff = std::isnan(c.af1_cutoff) ? (kind == GAUSS_KIND_QCAT ? 0.05 : 0.01) : c.af1_cutoff;   // dist.cpp:53-57, qcat.cpp:53-57
-    const bool mix = (kind == GAUSS_KIND_COMPUTELD || kind == GAUSS_KIND_DISTMIX || kind == GAUSS_KIND_JEPEGMIX ||
-                      kind == GAUSS_KIND_QCATMIX || kind == GAUSS_KIND_PREP_RECESSIVE || kind == GAUSS_KIND_LDSCOREMIX);
-    if (mix) {
+    if (mix_kind(kind)) {
         if (!c.pop_names || !c.pop_wgts || c.n_pop_wgt < 1) return herr("pop_wgt_df is empty");
         set_pop_wgt_map(a, c.pop_names, c.pop_wgts, c.n_pop_wgt);
     } else if (!c.study_pop) return herr("study_pop is NULL");
@@ -167,17 +159,19 @@ int gauss_prepared_qcat_counts(const gauss_prepared* p, int* n_head, int* n_pred
     return 0;
 }
 
-// genotype source of a window: host byte matrices, or row lists into the mmap'd packed panel
-static void set_geno(gauss_prepared* p, gauss_window_desc* d)
+// populations and genotype source of a prepared window: host byte matrices, or row lists into the mmap'd packed panel
+static void prepared_source(const gauss_prepared& p, gauss_window_desc& d)
 {
-    if (!p->packed_rows) { d->geno_m = p->gm.data(); d->geno_u = p->gu.data(); d->ld = p->ld; return; }
-    const PackedPanel& pk = *p->args.pk;
-    d->geno_format = GAUSS_GENO_2BIT;
-    d->geno_m = d->geno_u = pk.geno();
-    d->ld = pk.row_bytes();
-    d->rows_m = p->store_rows_m.data();
-    d->rows_u = p->store_rows_u.data();
-    d->pop_src_off = p->pop_src_off.data();
+    d.n_pop = (int)p.pop_off.size() - 1;
+    d.pop_off = p.pop_off.data(); d.pop_wgt = p.pop_wgt.data();
+    if (!p.packed_rows) { d.geno_m = p.gm.data(); d.geno_u = p.gu.data(); d.ld = p.ld; return; }
+    const PackedPanel& pk = *p.args.pk;
+    d.geno_format = GAUSS_GENO_2BIT;
+    d.geno_m = d.geno_u = pk.geno();
+    d.ld = pk.row_bytes();
+    d.rows_m = p.store_rows_m.data();
+    d.rows_u = p.store_rows_u.data();
+    d.pop_src_off = p.pop_src_off.data();
 }
 
 int gauss_prepared_window_desc(gauss_prepared* p, gauss_window_desc* d)
@@ -198,10 +192,8 @@ int gauss_prepared_window_desc(gauss_prepared* p, gauss_window_desc* d)
         memset(d, 0, sizeof(*d));
         d->kind = GAUSS_WIN_LD;
         d->mode = (p->kind == GAUSS_KIND_PREP_QCAT) ? GAUSS_MODE_POOLED : GAUSS_MODE_WEIGHTED;
-        d->n_pop = (int)p->pop_off.size() - 1;
-        d->pop_off = p->pop_off.data(); d->pop_wgt = p->pop_wgt.data();
         d->n_measured = M; d->n_unmeasured = U;
-        set_geno(p, d);
+        prepared_source(*p, *d);
         d->lambda = 0.0;                                       // B11(i,i) = 1.0 (prep_qcat.cpp:109)
         d->u_codings = (ncode == 3) ? (GAUSS_CODE_ADDITIVE | GAUSS_CODE_DOMINANT | GAUSS_CODE_RECESSIVE) : GAUSS_CODE_ADDITIVE;
         d->out_b11 = p->out_b11.data(); d->out_b21 = p->out_b21.data(); d->out_status = &p->status;
@@ -218,10 +210,8 @@ int gauss_prepared_window_desc(gauss_prepared* p, gauss_window_desc* d)
         memset(d, 0, sizeof(*d));
         d->kind = GAUSS_WIN_QCAT;
         d->mode = (p->kind == GAUSS_KIND_QCAT) ? GAUSS_MODE_POOLED : GAUSS_MODE_WEIGHTED;
-        d->n_pop = (int)p->pop_off.size() - 1;
-        d->pop_off = p->pop_off.data(); d->pop_wgt = p->pop_wgt.data();
         d->n_measured = M; d->n_unmeasured = U;
-        set_geno(p, d);
+        prepared_source(*p, *d);
         d->z1 = p->z1.data(); d->lambda = a.lambda; d->min_abs_eig = a.min_abs_eig;
         d->n_head_measured = p->n_head; d->n_pred_measured = p->n_predm; d->eig_cutoff = a.eig_cutoff;
         d->out_r = p->out_r.data(); d->out_num_eig = &p->num_eig; d->out_status = &p->status;
@@ -234,10 +224,8 @@ int gauss_prepared_window_desc(gauss_prepared* p, gauss_window_desc* d)
     p->out_z.assign(U, 0.0); p->out_info.assign(U, 0.0);
     memset(d, 0, sizeof(*d));
     d->mode = (p->kind == GAUSS_KIND_DIST) ? GAUSS_MODE_POOLED : GAUSS_MODE_WEIGHTED;
-    d->n_pop = (int)p->pop_off.size() - 1;
-    d->pop_off = p->pop_off.data(); d->pop_wgt = p->pop_wgt.data();
     d->n_measured = M; d->n_unmeasured = U;
-    set_geno(p, d);
+    prepared_source(*p, *d);
     d->z1 = p->z1.data(); d->lambda = a.lambda; d->min_abs_eig = a.min_abs_eig;
     d->out_z = p->out_z.data(); d->out_info = p->out_info.data(); d->out_status = &p->status;
     return 0;
@@ -269,57 +257,117 @@ int gauss_prepared_finish(gauss_prepared* p, gauss_table** out)
 
 // dist() / distmix() / qcat() / qcatmix(): ONE window per call, the reference's own usage (docs/articles/dist_example.md:144-153).
 //
-// On a sorted packed panel the window is a lean one (one_window_build), its genotype rows are read from the panel's resident copy in
-// HBM (panel_rows) instead of being gathered on the host and copied per call (24 MB a window), and the window runs as a job of one on
-// those rows.  Measured on the chr22 study, window after window (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.  Otherwise
-// the literal path: prepare_opened + gauss_impute_window on host rows.
+// CallWindow is the window of such a call, and the one place that knows which of two ways it was built:
+//   lean     on a sorted packed panel, as the chromosome driver builds its windows (host_chrom.cpp: LeanWindow -- a merge of the
+//            study's rows and the panel's SNP table instead of per-SNP objects in a map: ~0.1 ms against 0.7-1.0).  Its genotype rows
+//            are read from the panel's resident copy in HBM (panel_rows) instead of being gathered on the host and copied per call
+//            (24 MB a window), and it runs as a job on those rows.  Measured on the chr22 study, window after window
+//            (tools/window_calls_probe.py): 5.9 ms per call -> 2.5.
+//   literal  for an unsorted or text panel, a call over every chromosome, GAUSS_HOST_FULL_MAP=1 or a kind the lean window does not
+//            build: prepare() into a gauss_prepared, rows on the host.
+// Callers read it through the members.  It stays where it was built (w points into cs; the view and the descriptors point into it).
+struct CallWindow {
+    // errors come in prepare()'s order: arguments, description file, populations, study file
+    int build(const CallArgs& c, const std::string& panel_path, const std::shared_ptr<PackedPanel>& pk, bool lean_allowed = true);
+    bool lean() const { return !prep; }
+    const Args& args() const { return prep ? prep->args : cs.a; }
+    size_t n_measured() const { return prep ? prep->measured.size() : w.measured.size(); }
+    size_t n_unmeasured() const { return prep ? prep->unmeasured.size() : w.unmeasured.size(); }
+    ViewSnp measured(size_t i) const { return prep ? snp(*prep->measured[i]) : snp(w.v[(size_t)w.measured[i]]); }       // matrix row order
+    ViewSnp unmeasured(size_t i) const { return prep ? snp(*prep->unmeasured[i]) : snp(w.v[(size_t)w.unmeasured[i]]); }
+    void source(gauss_window_desc& d) const;            // populations, genotype format and rows; a lean window's geno_m / geno_u are run()'s
+    int desc(gauss_window_desc* d) { return prep ? gauss_prepared_window_desc(prep.get(), d) : lean_window_desc(w, d); }
+    int plain(gauss_table** t);                         // the call's own table: gauss_prepared_finish | lean_window_finish
+    WindowView view();                                  // what a rider reads; built only when asked for
+    int run(gauss_ctx* ctx, gauss_window_desc* d, int n = 1) const;
+    std::unique_ptr<gauss_prepared> release() { return std::move(prep); }      // a literal window's host rows, for who outlives it (LdRows)
 
-// The view a rider gets of either window (host_internal.h: WindowView); `plain` is left to the caller
-static int wing_of(long long bp, const CallArgs& c) { const int ibp = (int)bp; return ibp >= c.start_bp && ibp <= c.end_bp ? 0 : 1; }      // dist.cpp:92
-static WindowView view_of_lean(OneWindow& ow, const PackedPanel& pk, const CallArgs& c)
+private:
+    CallArgs c;
+    bool mix = false;
+    std::string path;
+    std::shared_ptr<PackedPanel> pk;
+    ChromSetup cs;
+    LeanWindow w;
+    std::unique_ptr<gauss_prepared> prep;
+    int wing_of(long long bp) const { const int ibp = (int)bp; return ibp >= c.start_bp && ibp <= c.end_bp ? 0 : 1; }      // dist.cpp:92
+    ViewSnp snp(const Snp& s) const { return {ident_of(s), mix ? s.af1mix : s.af1ref, s.z, wing_of(s.bp)}; }
+    ViewSnp snp(const LeanSnp& sn) const { return {ident_of(*pk, sn), sn.af, sn.z, wing_of(sn.bp)}; }
+};
+
+int CallWindow::build(const CallArgs& c_, const std::string& panel_path, const std::shared_ptr<PackedPanel>& pk_, bool lean_allowed)
 {
-    WindowView v;
-    v.mix = c.kind == GAUSS_KIND_DISTMIX;
-    LeanWindow& w = ow.w;
-    lean_table_count(w);                                      // out_row: the rows lean_window_finish will list
-    for (int32_t vi : w.measured) {
-        const LeanSnp& sn = w.v[(size_t)vi];
-        v.measured.push_back(ViewSnp{ident_of(pk, sn), sn.af, sn.z, wing_of(sn.bp, c)});
-        v.row_m.push_back(w.out_row[(size_t)vi]);
+    c = c_; mix = mix_kind(c.kind); path = panel_path; pk = pk_;
+    if (lean_allowed && c.chr > 0 && !env_flag("GAUSS_HOST_FULL_MAP", false) && pk && pk->header().sorted) {
+        if (chrom_setup(cs, c.kind, c.chr, c.wing, c.study_pop, c.pop_names, c.pop_wgts, c.n_pop_wgt, c.input, path, c.desc, c.af1_cutoff, pk,
+                        nullptr)) return -1;
+        std::string err;
+        cs.gw = load_gwas_cached(c.input, err);
+        if (!cs.gw) return herr("%s", err.c_str());
+        return lean_window_build(w, cs, c.start_bp, c.end_bp) ? -1 : 0;
     }
-    for (int32_t vi : w.unmeasured) v.row_u.push_back(w.out_row[(size_t)vi]);
-    return v;
+    gauss_prepared* p = nullptr;
+    if (prepare_opened(c, nullptr, path, pk, false, &p)) return -1;
+    prep.reset(p);
+    return 0;
 }
-static WindowView view_of_prepared(const gauss_prepared& p, const CallArgs& c)
+
+void CallWindow::source(gauss_window_desc& d) const
+{
+    if (prep) return prepared_source(*prep, d);
+    d.n_pop = (int)cs.pop_off.size() - 1;
+    d.pop_off = cs.pop_off.data(); d.pop_wgt = cs.pop_wgt.data();
+    d.geno_format = GAUSS_GENO_2BIT;
+    d.ld = pk->row_bytes();
+    d.rows_m = w.store_rows_m.data(); d.rows_u = w.store_rows_u.data();
+    d.pop_src_off = cs.pop_src_off.data();
+}
+
+int CallWindow::plain(gauss_table** t)
+{
+    if (prep) return gauss_prepared_finish(prep.get(), t);
+    *t = lean_window_finish(w);
+    return 0;
+}
+
+WindowView CallWindow::view()
 {
     WindowView v;
-    v.mix = c.kind == GAUSS_KIND_DISTMIX;
-    // dist_output's rows: the SNPs of the prediction window, snp_vec order
+    v.mix = mix;
+    v.plain = [this](gauss_table** t) { return plain(t); };
+    // the rows of the plain table: the SNPs of the prediction window, snp_vec order (dist_output; lean_table_count fills out_row)
     std::map<const Snp*, int32_t> row_of;
-    for (const Snp* sn : p.snp_vec) if (!wing_of(sn->bp, c)) { const int32_t r = (int32_t)row_of.size(); row_of[sn] = r; }
-    auto row = [&](const Snp* sn) { auto it = row_of.find(sn); return it == row_of.end() ? -1 : it->second; };
-    for (const Snp* s : p.measured) {
-        v.measured.push_back(ViewSnp{ident_of(*s), v.mix ? s->af1mix : s->af1ref, s->z, wing_of(s->bp, c)});
-        v.row_m.push_back(row(s));
-    }
-    for (const Snp* s : p.unmeasured) v.row_u.push_back(row(s));
+    if (prep) { for (const Snp* sn : prep->snp_vec) if (!wing_of(sn->bp)) { const int32_t r = (int32_t)row_of.size(); row_of[sn] = r; } }
+    else lean_table_count(w);
+    auto row = [&](bool m, size_t i) {
+        if (!prep) return w.out_row[(size_t)(m ? w.measured : w.unmeasured)[i]];
+        auto it = row_of.find((m ? prep->measured : prep->unmeasured)[i]);
+        return it == row_of.end() ? -1 : it->second;
+    };
+    for (size_t i = 0; i < n_measured(); i++) { v.measured.push_back(measured(i)); v.row_m.push_back(row(true, i)); }
+    for (size_t i = 0; i < n_unmeasured(); i++) v.row_u.push_back(row(false, i));
     return v;
 }
 
-// One window on the GPU: with `lean_pk` (a lean window) on the rows panel_rows names -- as a job of one on the resident panel, or,
-// for a panel too large to keep in HBM, the window's rows from the mapped file; otherwise the rows the descriptor already names
-static int run_window(gauss_ctx* ctx, gauss_window_desc& d, const std::string& panel_path, const PackedPanel* lean_pk)
+// d[0 .. n): this window's descriptor, then those of its peers, built the same way on the same panel (run_xsusie).  Lean windows run
+// on the rows panel_rows names -- as a job on the resident panel, or, for a panel too large to keep in HBM, on the rows of the
+// mapped file; literal ones on the rows their descriptors already name.  One window off the device is gauss_impute_window.
+int CallWindow::run(gauss_ctx* ctx, gauss_window_desc* d, int n) const
 {
     int on_device = 0;
-    if (lean_pk) { panel_rows(ctx, panel_path, *lean_pk, &d.geno_m, &on_device); d.geno_u = d.geno_m; }
+    if (!prep) {
+        const uint8_t* store = nullptr;
+        panel_rows(ctx, path, *pk, &store, &on_device);
+        for (int k = 0; k < n; k++) d[k].geno_m = d[k].geno_u = store;
+    }
     int rc;
-    if (on_device) {
+    if (on_device || n > 1) {
         gauss_job* job = nullptr;
-        rc = gauss_job_create(ctx, &d, 1, 1, &job);
+        rc = gauss_job_create(ctx, d, n, on_device, &job);
         if (rc == 0) rc = gauss_job_run(job);
         if (rc == 0) rc = gauss_job_fetch(job);
         if (job) gauss_job_destroy(job);
-    } else rc = gauss_impute_window(ctx, &d);
+    } else rc = gauss_impute_window(ctx, d);
     return rc ? herr("%s", gauss_last_error()) : 0;
 }
 
@@ -333,25 +381,14 @@ static int run_impute(gauss_ctx* ctx, const CallArgs& c, Rider* rider, gauss_tab
     std::string panel_path;
     std::shared_ptr<PackedPanel> pk;
     if (open_panel(c.index, c.data, c.desc, panel_path, pk)) return -1;
-    // the window, lean or literal, and its descriptor (which points into ow / prep)
-    const bool lean_kind = (c.kind == GAUSS_KIND_DIST || c.kind == GAUSS_KIND_DISTMIX || c.kind == GAUSS_KIND_QCAT || c.kind == GAUSS_KIND_QCATMIX);
-    OneWindow ow;
-    std::unique_ptr<gauss_prepared> prep;
-    const int lean = lean_kind ? one_window_build(ow, c, panel_path, pk) : 1;
-    if (lean < 0) return -1;
-    if (lean) {
-        gauss_prepared* p = nullptr;
-        if (prepare_opened(c, nullptr, panel_path, pk, false, &p)) return -1;
-        prep.reset(p);
-    }
+    CallWindow win;                                           // (the descriptor and the view point into it)
+    if (win.build(c, panel_path, pk, c.kind != GAUSS_KIND_PREP_QCAT && c.kind != GAUSS_KIND_PREP_RECESSIVE)) return -1;
     gauss_window_desc d;
-    if (lean ? gauss_prepared_window_desc(prep.get(), &d) : lean_window_desc(ow.w, &d)) return -1;
-    auto plain = [&](gauss_table** t) { if (lean) return gauss_prepared_finish(prep.get(), t); *t = lean_window_finish(ow.w); return 0; };
-    if (!rider) return run_window(ctx, d, panel_path, lean ? nullptr : pk.get()) ? -1 : plain(out);
-    WindowView v = lean ? view_of_prepared(*prep, c) : view_of_lean(ow, *pk, c);       // (points into ow / prep)
-    v.plain = plain;
+    if (win.desc(&d)) return -1;
+    if (!rider) return win.run(ctx, &d) ? -1 : win.plain(out);
+    WindowView v = win.view();
     if (rider->ask(d, v)) return -1;
-    if (run_window(ctx, d, panel_path, lean ? nullptr : pk.get())) return -1;
+    if (win.run(ctx, &d)) return -1;
     return rider->table(v, out);
 }
 
@@ -479,12 +516,10 @@ int gauss_host_distmix_susie(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t 
 // is built exactly as its own dist() / distmix() call builds it (run_impute), the maps come from the panel SNP each candidate is
 // (xs_build_map), and the K windows run as one job.  The table is study 1's *_susie table with the joint values (xsusie_output).
 struct XsStudy {
-    OneWindow ow;                        // (points into itself: built in place, never moved)
-    std::unique_ptr<gauss_prepared> prep;
+    CallWindow win;                      // (built in place, never moved)
     WindowView v;
     std::vector<int64_t> key;            // the panel SNP of every candidate, measured first
     std::vector<int32_t> from_lead;
-    int32_t status = 0;
 };
 static int run_xsusie(gauss_ctx* ctx, const std::vector<CallArgs>& calls, SusieRider& r, gauss_table** out)
 {
@@ -499,34 +534,22 @@ static int run_xsusie(gauss_ctx* ctx, const std::vector<CallArgs>& calls, SusieR
     if (open_panel(c0.index, c0.data, c0.desc, panel_path, pk)) return -1;
     std::vector<std::unique_ptr<XsStudy>> st;
     std::vector<gauss_window_desc> d((size_t)K);
+    std::vector<int32_t> status((size_t)K, 0);
     std::map<std::string, int64_t> snp_no;                                  // chr:bp:rsid -> one number per panel SNP
     auto key_of = [&](const SnpIdent& id) {
         const std::string s = std::to_string(id.chr) + ":" + std::to_string(id.bp) + ":" + (id.rsid ? id.rsid : "");
         return snp_no.emplace(s, (int64_t)snp_no.size()).first->second;
     };
-    int lean0 = 0;
     for (int k = 0; k < K; k++) {
-        const CallArgs& c = calls[(size_t)k];
         st.emplace_back(new XsStudy());
         XsStudy& s = *st.back();
-        const int lean = one_window_build(s.ow, c, panel_path, pk);         // (0: a lean window; 1: the literal path)
-        if (lean < 0) return -1;
-        if (k == 0) lean0 = lean;
-        else if (lean != lean0) return herr("study %d cannot be built the way study 1 is", k + 1);
-        if (lean) {
-            gauss_prepared* p = nullptr;
-            if (prepare_opened(c, nullptr, panel_path, pk, false, &p)) return -1;
-            s.prep.reset(p);
-        }
-        if (lean ? gauss_prepared_window_desc(s.prep.get(), &d[(size_t)k]) : lean_window_desc(s.ow.w, &d[(size_t)k])) return -1;
-        s.v = lean ? view_of_prepared(*s.prep, c) : view_of_lean(s.ow, *pk, c);
-        XsStudy* sp = &s;
-        const bool is_lean = !lean;
-        s.v.plain = [sp, is_lean](gauss_table** t) { if (!is_lean) return gauss_prepared_finish(sp->prep.get(), t); *t = lean_window_finish(sp->ow.w); return 0; };
+        if (s.win.build(calls[(size_t)k], panel_path, pk)) return -1;
+        if (s.win.lean() != st[0]->win.lean()) return herr("study %d cannot be built the way study 1 is", k + 1);
+        if (s.win.desc(&d[(size_t)k])) return -1;
+        s.v = s.win.view();
         for (const ViewSnp& m : s.v.measured) s.key.push_back(key_of(m.id));
-        if (lean) for (const Snp* u : s.prep->unmeasured) s.key.push_back(key_of(ident_of(*u)));
-        else for (int32_t vi : s.ow.w.unmeasured) s.key.push_back(key_of(ident_of(*pk, s.ow.w.v[(size_t)vi])));
-        d[(size_t)k].out_status = &s.status;
+        for (size_t i = 0; i < s.win.n_unmeasured(); i++) s.key.push_back(key_of(s.win.unmeasured(i).id));
+        d[(size_t)k].out_status = &status[(size_t)k];
     }
     // the leader asks for the fit; the peers take its arguments and their maps
     if (r.ask(d[0], st[0]->v)) return -1;
@@ -545,18 +568,8 @@ static int run_xsusie(gauss_ctx* ctx, const std::vector<CallArgs>& calls, SusieR
         for (size_t j = 0; j < TL; j++) if (s.from_lead[j] < 0) joint[j] = 0;
         q.xs_group = 1; q.xs_from_lead = s.from_lead.data();
     }
-    int on_device = 0;
-    if (!lean0)
-        for (int k = 0; k < K; k++) { panel_rows(ctx, panel_path, *pk, &d[(size_t)k].geno_m, &on_device); d[(size_t)k].geno_u = d[(size_t)k].geno_m; }
-    gauss_job* job = nullptr;
-    int rc = gauss_job_create(ctx, d.data(), K, on_device, &job);
-    if (rc == 0) rc = gauss_job_run(job);
-    if (rc == 0) rc = gauss_job_fetch(job);
-    if (job) gauss_job_destroy(job);
-    if (rc) return herr("%s", gauss_last_error());
+    if (st[0]->win.run(ctx, d.data(), K)) return -1;
     if (r.table(st[0]->v, out)) return -1;
-    std::vector<int32_t> status;
-    for (const auto& s : st) status.push_back(s->status);
     if (xsusie_output(**out, st[0]->v.row_m, st[0]->v.row_u, joint.data(), K, (int)L, xs_V.data(), xs_purity.data(), status.data())) {
         gauss_table_free(*out); *out = nullptr;
         return -1;
@@ -650,43 +663,20 @@ static int run_ldscore(gauss_ctx* ctx, const CallArgs& c, double n_arg, gauss_ta
     std::shared_ptr<PackedPanel> pk;
     if (open_panel(c.index, c.data, c.desc, panel_path, pk)) return -1;
     const bool mix = c.kind == GAUSS_KIND_LDSCOREMIX;
-    OneWindow ow;
-    std::unique_ptr<gauss_prepared> prep;
-    const int lean = one_window_build(ow, c, panel_path, pk);
-    if (lean < 0) return -1;
-    if (lean) {
-        gauss_prepared* p = nullptr;
-        if (prepare_opened(c, nullptr, panel_path, pk, false, &p)) return -1;
-        prep.reset(p);
-    }
-    std::vector<LdsRow> rows;
+    CallWindow win;
+    if (win.build(c, panel_path, pk)) return -1;
+    std::vector<ViewSnp> rows;
     std::vector<int32_t> bp_m, bp_u;
     int64_t n_ref = 0, n_ref_5_50 = 0;
     auto count = [&](double af) { n_ref++; if (std::min(af, 1.0 - af) > 0.05) n_ref_5_50++; };
+    for (size_t i = 0; i < win.n_measured(); i++) { rows.push_back(win.measured(i)); bp_m.push_back((int32_t)rows.back().id.bp); count(rows.back().af); }
+    for (size_t i = 0; i < win.n_unmeasured(); i++) { const ViewSnp s = win.unmeasured(i); bp_u.push_back((int32_t)s.id.bp); count(s.af); }
     gauss_window_desc d;
     memset(&d, 0, sizeof(d));
     d.kind = GAUSS_WIN_LD;
     d.mode = mix ? GAUSS_MODE_WEIGHTED : GAUSS_MODE_POOLED;
     d.lambda = 0.0; d.u_codings = GAUSS_CODE_ADDITIVE;
-    if (!lean) {
-        const LeanWindow& w = ow.w;
-        const ChromSetup& cs = ow.cs;
-        for (int32_t vi : w.measured) { const LeanSnp& sn = w.v[(size_t)vi]; rows.push_back(LdsRow{ident_of(*pk, sn), sn.af}); bp_m.push_back((int32_t)sn.bp); count(sn.af); }
-        for (int32_t vi : w.unmeasured) { const LeanSnp& sn = w.v[(size_t)vi]; bp_u.push_back((int32_t)sn.bp); count(sn.af); }
-        d.n_pop = (int)cs.pop_off.size() - 1;
-        d.pop_off = cs.pop_off.data(); d.pop_wgt = cs.pop_wgt.data();
-        d.geno_format = GAUSS_GENO_2BIT;
-        d.ld = pk->row_bytes();
-        d.rows_m = w.store_rows_m.data(); d.rows_u = w.store_rows_u.data();
-        d.pop_src_off = cs.pop_src_off.data();
-    } else {
-        gauss_prepared& p = *prep;
-        for (const Snp* s : p.measured) { const double af = mix ? s->af1mix : s->af1ref; rows.push_back(LdsRow{ident_of(*s), af}); bp_m.push_back((int32_t)s->bp); count(af); }
-        for (const Snp* s : p.unmeasured) { bp_u.push_back((int32_t)s->bp); count(mix ? s->af1mix : s->af1ref); }
-        d.n_pop = (int)p.pop_off.size() - 1;
-        d.pop_off = p.pop_off.data(); d.pop_wgt = p.pop_wgt.data();
-        set_geno(&p, &d);
-    }
+    win.source(d);
     const size_t M = rows.size(), U = bp_u.size();
     if (M == 0)
         return herr("LD scores: no SNP of '%s' is in the panel between %lld and %lld on chromosome %d: the window has no SNP to score", c.input,
@@ -701,7 +691,7 @@ static int run_ldscore(gauss_ctx* ctx, const CallArgs& c, double n_arg, gauss_ta
     d.lds_bp_m = bp_m.data(); d.lds_bp_u = U ? bp_u.data() : nullptr;
     d.out_lds_raw = raw.data(); d.out_lds_l2 = l2.data(); d.out_lds_mass = mass.data();
     // (out_b11 = out_b21 = NULL: the matrices stay on the device; out_status = NULL: an LD window raises no status bit)
-    if (run_window(ctx, d, panel_path, lean ? nullptr : pk.get())) return -1;
+    if (win.run(ctx, &d)) return -1;
     *out = ldscore_output(mix, rows, l2.data(), raw.data(), mass.data(), n_eff, n_ref, n_ref_5_50, c.wing);
     return 0;
 }
@@ -1031,7 +1021,7 @@ static int prep_zmix_variant(gauss_ctx* ctx, int variant, const char* input_file
 }
 
 // computeLD's SNP selection (computeLD.cpp:26-93, 134-149), shared with simulateLD (simulateLD.cpp:44-124, 226-245): a lean window
-// of measured SNPs only with rows from the resident panel where one_window_build allows, else the literal path (prepare_opened).
+// of measured SNPs only with rows from the resident panel where CallWindow builds one, else the literal path.
 int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
                    int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
                    const char* reference_pop_desc_file, double af1_cutoff, LdRows& out)
@@ -1041,36 +1031,30 @@ int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, co
     if (open_panel(reference_index_file, reference_data_file, reference_pop_desc_file, panel_path, out.pk)) return -1;
     const CallArgs c = call_mix(GAUSS_KIND_COMPUTELD, chr, start_bp, end_bp, 0, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file,
                                 reference_data_file, reference_pop_desc_file, af1_cutoff);
-    OneWindow ow;
-    const int lean = one_window_build(ow, c, panel_path, out.pk);
-    if (lean < 0) return -1;
-    gauss_prepared* p = nullptr;
-    if (lean == 1) {
-        if (prepare_opened(c, nullptr, panel_path, out.pk, false, &p)) return -1;
-        out.prep.reset(p);
-    }
-    out.a = p ? p->args : ow.cs.a;
-    out.M = (int)(p ? p->measured.size() : ow.w.measured.size());
+    CallWindow win;
+    if (win.build(c, panel_path, out.pk)) return -1;
+    out.a = win.args();
+    out.M = (int)win.n_measured();
     if (out.M <= out.a.min_num_measured_snp)                             // computeLD.cpp:89-93
         return herr("Not enough number of SNPs loaded - computeLD not performed (measured %d)", out.M);
-    out.pop_off = p ? p->pop_off : ow.cs.pop_off;
-    out.pop_wgt = p ? p->pop_wgt : ow.cs.pop_wgt;
-    if (!p || p->packed_rows) {
-        panel_rows(ctx, panel_path, *out.pk, &out.store, &out.on_device);
-        out.ld = out.pk->row_bytes(); out.geno_fmt = GAUSS_GENO_2BIT;
-        out.rows = p ? p->store_rows_m : ow.w.store_rows_m;
-        out.pop_src_off = p ? p->pop_src_off : ow.cs.pop_src_off;
-    } else {
-        out.store = p->gm.data(); out.ld = p->ld; out.geno_fmt = GAUSS_GENO_U8; out.on_device = 0;
+    gauss_window_desc d;
+    memset(&d, 0, sizeof(d));
+    win.source(d);
+    out.pop_off.assign(d.pop_off, d.pop_off + d.n_pop + 1);
+    out.pop_wgt.assign(d.pop_wgt, d.pop_wgt + d.n_pop);
+    if (d.geno_format == GAUSS_GENO_2BIT) {                              // rows of the packed panel, by index: from its resident copy
+        panel_rows(ctx, panel_path, *out.pk, &d.geno_m, &out.on_device);
+        out.rows.assign(d.rows_m, d.rows_m + out.M);
+        out.pop_src_off.assign(d.pop_src_off, d.pop_src_off + d.n_pop);
     }
+    out.store = d.geno_m; out.ld = d.ld; out.geno_fmt = d.geno_format;
+    std::vector<ViewSnp> m;
+    for (int i = 0; i < out.M; i++) m.push_back(win.measured((size_t)i));
     out.t.reset(new gauss_table());                                      // computeLD.cpp:134-149
-    if (p) add_ident_columns(*out.t, p->measured);
-    else add_ident_columns(*out.t, ow.w.measured.size(), [&](size_t i) { return ident_of(*out.pk, ow.w.v[(size_t)ow.w.measured[i]]); });
+    add_ident_columns(*out.t, m.size(), [&](size_t i) { return m[i].id; });
     Column& af = out.t->add("af1mix", GAUSS_COL_DBL);
-    if (p) for (Snp* s : p->measured) af.d.push_back(s->af1mix);
-    else for (int32_t vi : ow.w.measured) af.d.push_back(ow.w.v[(size_t)vi].af);
-    if (p) for (Snp* s : p->measured) out.z.push_back(s->z);
-    else for (int32_t vi : ow.w.measured) out.z.push_back(ow.w.v[(size_t)vi].z);
+    for (const ViewSnp& s : m) { af.d.push_back(s.af); out.z.push_back(s.z); }
+    out.prep = win.release();                                            // (a literal window's rows are `store`)
     return 0;
 }
 
@@ -1259,25 +1243,39 @@ int gauss_prepared_jepeg_finish(const gauss_prepared* p, int g0, int g1, const d
     return 0;
 }
 
-static int run_jepeg(gauss_ctx* ctx, int kind, const char* study_pop, const char* const* names, const double* wgts, int nw,
-                     const char* input, const char* annotation, const char* index, const char* data, const char* desc,
-                     double af1_cutoff, int rank, int world, gauss_table** out)
+// The head of the gene calls (jepeg, sumchi2): the data layer with the SNP map of annotated positions only.
+// The gene table is made of annotated SNPs alone, and every step of the data layer after ReadInputZ works on the entries of one
+// position at a time: only the study SNPs at positions the annotation names enter the SNP map (plus the positions the study
+// lists more than once or under equal alleles -- the only ones where the reference's duplicate check can fire, so a study that
+// fails there still fails).  A chromosome's study is four times its annotated SNPs: the data layer of a jepegmix() call
+// 3.9 -> 1.0 ms.  GAUSS_HOST_FULL_MAP=1: the whole study, as gauss_host_prepare enters it (same table, bit for bit:
+// tests/test_gpu_drivers.py).
+static int gene_prepare(const CallArgs& c, const char* annotation, std::unique_ptr<gauss_prepared>& out)
+{
+    gauss_prepared* p = nullptr;
+    if (prepare_files(c, annotation, !env_flag("GAUSS_HOST_FULL_MAP", false), &p)) return -1;
+    out.reset(p);
+    return 0;
+}
+// ... and where its measured rows are, as the *_rows entry points take them: the panel's 2-bit rows by index (panel_rows: the
+// resident copy) when the data layer kept row lists into a packed panel, else its byte matrix, rows 0 .. M - 1 (rows = NULL)
+struct GeneRows { const uint8_t* store; int64_t ld; int format, on_device; const int32_t *rows, *pop_src_off; };
+static GeneRows gene_rows(gauss_ctx* ctx, const gauss_prepared& p)
+{
+    if (!p.packed_rows) return {p.gm.data(), p.ld, GAUSS_GENO_U8, 0, nullptr, nullptr};
+    GeneRows r = {nullptr, p.args.pk->row_bytes(), GAUSS_GENO_2BIT, 0, p.store_rows_m.data(), p.pop_src_off.data()};
+    panel_rows(ctx, p.args.reference_data_file, *p.args.pk, &r.store, &r.on_device);
+    return r;
+}
+
+// c: call_pop / call_mix of kind GAUSS_KIND_JEPEG / GAUSS_KIND_JEPEGMIX without a window (the rank entry points fill both forms)
+static int run_jepeg(gauss_ctx* ctx, const CallArgs& c, const char* annotation, int rank, int world, gauss_table** out)
 {
     if (!ctx || !out) return herr("bad arguments");
     if (world < 1 || rank < 0 || rank >= world) return herr("rank %d of world %d", rank, world);
-    gauss_prepared* p = nullptr;
-    // The gene table is made of annotated SNPs alone, and every step of the data layer after ReadInputZ works on the entries of one
-    // position at a time: only the study SNPs at positions the annotation names enter the SNP map (plus the positions the study
-    // lists more than once or under equal alleles -- the only ones where the reference's duplicate check can fire, so a study that
-    // fails there still fails).  A chromosome's study is four times its annotated SNPs: the data layer of a jepegmix() call
-    // 3.9 -> 1.0 ms.  GAUSS_HOST_FULL_MAP=1: the whole study, as gauss_host_prepare enters it (same table, bit for bit:
-    // tests/test_gpu_drivers.py).
-    const bool full_map = env_flag("GAUSS_HOST_FULL_MAP", false);
     const double t_begin = now_s();
-    CallArgs c = call_mix(kind, 0, 0, 0, 0, names, wgts, nw, input, index, data, desc, af1_cutoff);
-    c.study_pop = study_pop;                                 // (the rank entry point takes both forms)
-    if (prepare_files(c, annotation, !full_map, &p)) return -1;
-    std::unique_ptr<gauss_prepared> hold(p);
+    std::unique_ptr<gauss_prepared> p;
+    if (gene_prepare(c, annotation, p)) return -1;
     const double t_prepared = now_s();
     const Args& a = p->args;
     std::vector<int32_t> first;
@@ -1297,18 +1295,14 @@ static int run_jepeg(gauss_ctx* ctx, int kind, const char* study_pop, const char
     std::vector<double> blocks(std::max<size_t>(tot, 1), 0.0);
     if (S > 0 && ng > 0) {
         // CorG of every gene of the range in one launch, diagonal 1 + lambda (gene.cpp:306-315 / 576-586)
-        const int mode = (kind == GAUSS_KIND_JEPEG) ? GAUSS_MODE_POOLED : GAUSS_MODE_WEIGHTED;
-        if (p->packed_rows) {
-            const uint8_t* store = nullptr;
-            int on_device = 0;
-            panel_rows(ctx, a.reference_data_file, *a.pk, &store, &on_device);
-            if (gauss_gene_ld_batch_rows(ctx, mode, store, a.pk->row_bytes(), GAUSS_GENO_2BIT, p->store_rows_m.data() + r0, S,
-                                         p->pop_off.data(), p->pop_src_off.data(), p->pop_wgt.data(), (int)p->pop_off.size() - 1,
-                                         goff.data(), ng, 1.0 + a.lambda, on_device, blocks.data()) != 0)
-                return herr("%s", gauss_last_error());
-        } else if (gauss_gene_ld_batch(ctx, mode, p->gm.data() + (size_t)r0 * (size_t)p->ld, S, p->ld, p->pop_off.data(), p->pop_wgt.data(),
-                                       (int)p->pop_off.size() - 1, goff.data(), ng, 1.0 + a.lambda, blocks.data()) != 0)
-            return herr("%s", gauss_last_error());
+        const int mode = (c.kind == GAUSS_KIND_JEPEG) ? GAUSS_MODE_POOLED : GAUSS_MODE_WEIGHTED;
+        const GeneRows g = gene_rows(ctx, *p);
+        const int rc = g.rows ? gauss_gene_ld_batch_rows(ctx, mode, g.store, g.ld, g.format, g.rows + r0, S, p->pop_off.data(), g.pop_src_off,
+                                                         p->pop_wgt.data(), (int)p->pop_off.size() - 1, goff.data(), ng, 1.0 + a.lambda,
+                                                         g.on_device, blocks.data())
+                              : gauss_gene_ld_batch(ctx, mode, g.store + (size_t)r0 * (size_t)g.ld, S, g.ld, p->pop_off.data(), p->pop_wgt.data(),
+                                                    (int)p->pop_off.size() - 1, goff.data(), ng, 1.0 + a.lambda, blocks.data());
+        if (rc != 0) return herr("%s", gauss_last_error());
     }
     const double t_ld = now_s();
     *out = jepeg_table(*p, g0, g1, blocks.data());
@@ -1322,8 +1316,8 @@ int gauss_host_jepeg(gauss_ctx* ctx, const char* study_pop, const char* input_fi
                      const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
                      double af1_cutoff, gauss_table** out)
 {
-    return run_jepeg(ctx, GAUSS_KIND_JEPEG, study_pop, nullptr, nullptr, 0, input_file, annotation_file, reference_index_file,
-                     reference_data_file, reference_pop_desc_file, af1_cutoff, 0, 1, out);
+    return run_jepeg(ctx, call_gene(GAUSS_KIND_JEPEG, study_pop, nullptr, nullptr, 0, input_file, reference_index_file, reference_data_file,
+                                    reference_pop_desc_file, af1_cutoff), annotation_file, 0, 1, out);
 }
 
 int gauss_host_jepegmix(gauss_ctx* ctx, const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
@@ -1331,25 +1325,19 @@ int gauss_host_jepegmix(gauss_ctx* ctx, const char* const* pop_names, const doub
                         const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,
                         gauss_table** out)
 {
-    return run_jepeg(ctx, GAUSS_KIND_JEPEGMIX, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file,
-                     reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, 0, 1, out);
+    return run_jepeg(ctx, call_gene(GAUSS_KIND_JEPEGMIX, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file,
+                                    reference_data_file, reference_pop_desc_file, af1_cutoff), annotation_file, 0, 1, out);
 }
 
 // sumchi2() / sumchi2mix(): jepeg's genes and SNPs (the same data layer, the same measured list and gene_off; categ and wgt are not
-// read), tested by the plain sum of chi2 on the GPU (gauss_gene_sumchi2[_rows]); the packed and byte paths are chosen as in run_jepeg
-static int run_sumchi2(gauss_ctx* ctx, int kind, const char* study_pop, const char* const* names, const double* wgts, int nw,
-                       const char* input, const char* annotation, const char* index, const char* data, const char* desc,
-                       double af1_cutoff, double prune_r2, gauss_table** out)
+// read), tested by the plain sum of chi2 on the GPU (gauss_gene_sumchi2[_rows]); the head and the row source are run_jepeg's
+static int run_sumchi2(gauss_ctx* ctx, const CallArgs& c, const char* annotation, double prune_r2, gauss_table** out)
 {
     if (!ctx || !out) return herr("bad arguments");
     const double r2 = std::isnan(prune_r2) ? 0.9 : prune_r2;                       // fastBAT's default
     if (!(r2 > 0.0 && r2 <= 1.0)) return herr("sumchi2: prune_r2 = %g is outside (0, 1]", r2);
-    gauss_prepared* p = nullptr;
-    CallArgs c = call_mix(kind, 0, 0, 0, 0, names, wgts, nw, input, index, data, desc, af1_cutoff);
-    c.study_pop = study_pop;
-    if (prepare_files(c, annotation, !env_flag("GAUSS_HOST_FULL_MAP", false), &p)) return -1;
-    std::unique_ptr<gauss_prepared> hold(p);
-    const Args& a = p->args;
+    std::unique_ptr<gauss_prepared> p;
+    if (gene_prepare(c, annotation, p)) return -1;
     const int ng = p->gene_off.empty() ? 0 : (int)p->gene_off.size() - 1;
     const int S = ng > 0 ? p->gene_off[(size_t)ng] : 0;
     // jepeg's sort by gene id (std::sort) leaves the order inside a gene open; the pruning is defined in position order, so each gene's
@@ -1372,23 +1360,13 @@ static int run_sumchi2(gauss_ctx* ctx, int kind, const char* study_pop, const ch
     std::vector<int32_t> status((size_t)std::max(ng, 1), GAUSS_ST_SUMCHI2_EMPTY);       // (no SNP at all: no GPU call, every gene is empty)
     std::vector<double> lam((size_t)std::max(ng, 1) * GAUSS_SUMCHI2_MAX_KEPT, NAN), q((size_t)std::max(ng, 1), 0.0);
     if (S > 0 && ng > 0) {
-        const int mode = (kind == GAUSS_KIND_JEPEG) ? GAUSS_MODE_POOLED : GAUSS_MODE_WEIGHTED;
-        const int n_pop = (int)p->pop_off.size() - 1;
-        int rc;
-        if (p->packed_rows) {
-            const uint8_t* store = nullptr;
-            int on_device = 0;
-            panel_rows(ctx, a.reference_data_file, *a.pk, &store, &on_device);
-            std::vector<int32_t> rows((size_t)S);
-            for (int i = 0; i < S; i++) rows[(size_t)i] = p->store_rows_m[(size_t)perm[(size_t)i]];
-            rc = gauss_gene_sumchi2_rows(ctx, mode, store, a.pk->row_bytes(), GAUSS_GENO_2BIT, rows.data(), S, p->pop_off.data(),
-                                         p->pop_src_off.data(), p->pop_wgt.data(), n_pop, p->gene_off.data(), ng, on_device, z.data(), 1, r2,
-                                         kept.data(), n_kept.data(), lam.data(), q.data(), top.data(), status.data(), nullptr);
-        } else      // the byte matrix of the measured SNPs as a host row store
-            rc = gauss_gene_sumchi2_rows(ctx, mode, p->gm.data(), p->ld, GAUSS_GENO_U8, perm.data(), S, p->pop_off.data(), nullptr,
-                                         p->pop_wgt.data(), n_pop, p->gene_off.data(), ng, 0, z.data(), 1, r2, kept.data(), n_kept.data(),
-                                         lam.data(), q.data(), top.data(), status.data(), nullptr);
-        if (rc != 0) return herr("%s", gauss_last_error());
+        const int mode = (c.kind == GAUSS_KIND_JEPEG) ? GAUSS_MODE_POOLED : GAUSS_MODE_WEIGHTED;
+        const GeneRows g = gene_rows(ctx, *p);
+        std::vector<int32_t> rows((size_t)S);                                          // (the byte matrix is a host row store: row i is row i)
+        for (int i = 0; i < S; i++) rows[(size_t)i] = g.rows ? g.rows[(size_t)perm[(size_t)i]] : perm[(size_t)i];
+        if (gauss_gene_sumchi2_rows(ctx, mode, g.store, g.ld, g.format, rows.data(), S, p->pop_off.data(), g.pop_src_off, p->pop_wgt.data(),
+                                    (int)p->pop_off.size() - 1, p->gene_off.data(), ng, g.on_device, z.data(), 1, r2, kept.data(), n_kept.data(),
+                                    lam.data(), q.data(), top.data(), status.data(), nullptr) != 0) return herr("%s", gauss_last_error());
     }
     *out = sumchi2_output(geneid, p->gene_off, rsid, z, n_kept.data(), lam.data(), q.data(), top.data(), status.data());
     return 0;
@@ -1398,8 +1376,8 @@ int gauss_host_sumchi2(gauss_ctx* ctx, const char* study_pop, const char* input_
                        const char* reference_index_file, const char* reference_data_file, const char* reference_pop_desc_file,
                        double af1_cutoff, double prune_r2, gauss_table** out)
 {
-    return run_sumchi2(ctx, GAUSS_KIND_JEPEG, study_pop, nullptr, nullptr, 0, input_file, annotation_file, reference_index_file,
-                       reference_data_file, reference_pop_desc_file, af1_cutoff, prune_r2, out);
+    return run_sumchi2(ctx, call_gene(GAUSS_KIND_JEPEG, study_pop, nullptr, nullptr, 0, input_file, reference_index_file, reference_data_file,
+                                      reference_pop_desc_file, af1_cutoff), annotation_file, prune_r2, out);
 }
 
 int gauss_host_sumchi2mix(gauss_ctx* ctx, const char* const* pop_names, const double* pop_wgts, int n_pop_wgt,
@@ -1407,8 +1385,8 @@ int gauss_host_sumchi2mix(gauss_ctx* ctx, const char* const* pop_names, const do
                           const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff,
                           double prune_r2, gauss_table** out)
 {
-    return run_sumchi2(ctx, GAUSS_KIND_JEPEGMIX, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file,
-                       reference_index_file, reference_data_file, reference_pop_desc_file, af1_cutoff, prune_r2, out);
+    return run_sumchi2(ctx, call_gene(GAUSS_KIND_JEPEGMIX, nullptr, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file,
+                                      reference_data_file, reference_pop_desc_file, af1_cutoff), annotation_file, prune_r2, out);
 }
 
 int gauss_host_sumchi2_pval(const double* lam, int n, double q, double* p, int* n_pos)
@@ -1424,8 +1402,8 @@ int gauss_host_jepeg_rank(gauss_ctx* ctx, int kind, const char* study_pop, const
                           int rank, int world, gauss_table** out)
 {
     if (kind != GAUSS_KIND_JEPEG && kind != GAUSS_KIND_JEPEGMIX) return herr("kind %d is not jepeg / jepegmix", kind);
-    return run_jepeg(ctx, kind, study_pop, pop_names, pop_wgts, n_pop_wgt, input_file, annotation_file, reference_index_file,
-                     reference_data_file, reference_pop_desc_file, af1_cutoff, rank, world, out);
+    return run_jepeg(ctx, call_gene(kind, study_pop, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file, reference_data_file,
+                                    reference_pop_desc_file, af1_cutoff), annotation_file, rank, world, out);
 }
 
 // Which rank runs which of n independent calls: longest first by `cost` onto the least loaded rank (ties: the lower index / rank).
@@ -1469,8 +1447,8 @@ int gauss_host_jepeg_genome(gauss_ctx* ctx, int kind, int n_calls, const char* s
         if (owner_out) owner_out[c] = owner[(size_t)c];
         if (owner[(size_t)c] != rank) continue;
         const char* idx = reference_index_files ? reference_index_files[c] : "(packed)";
-        if (run_jepeg(ctx, kind, study_pop, pop_names, pop_wgts, n_pop_wgt, input_files[c], annotation_files[c], idx ? idx : "(packed)",
-                      reference_data_files[c], reference_pop_desc_file, af1_cutoff, 0, 1, &out[c]) != 0) {
+        if (run_jepeg(ctx, call_gene(kind, study_pop, pop_names, pop_wgts, n_pop_wgt, input_files[c], idx ? idx : "(packed)", reference_data_files[c],
+                                     reference_pop_desc_file, af1_cutoff), annotation_files[c], 0, 1, &out[c]) != 0) {
             // a call that fails leaves out[c] = NULL; the others still run (as the chromosome driver isolates a failing window)
             if (!rc_all) first_err = gauss_host_last_error();
             rc_all = -1;

@@ -530,30 +530,34 @@ gauss_table* qcat_output(gauss_prepared& p);
 // index into the three leave-one-out arrays of gauss_window_desc)
 struct LooRow { SnpIdent id; double af, z; int idx; };
 gauss_table* loo_output(bool mix, const std::vector<LooRow>& rows, const double* loo_z, const double* loo_info, const double* loo_t);
+// One SNP of a window as the tables and the riders read it, whichever way the window was built (host_calls.cpp: CallWindow).  The
+// strings of `id` point into the window: a ViewSnp does not outlive it.
+struct ViewSnp { SnpIdent id; double af, z; int wing; };     // af: af1mix | af1ref; wing: 0 inside [start_bp, end_bp] (dist.cpp:92), else 1
+using SlctRow = ViewSnp;                                      // the names the stand-alone programs of the host tests build their rows under
+using LdsRow = ViewSnp;                                       // (id and af; ldscore_output reads no more)
 // dist_slct / distmix_slct: one row per measured SNP of the EXTENDED window, matrix row order (row i = index i of the selection's arrays)
-struct SlctRow { SnpIdent id; double af, z; int wing; };
-gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, const int32_t* idx, const double* zin, const double* joint,
+gauss_table* slct_output(bool mix, const std::vector<ViewSnp>& rows, int n_sel, const int32_t* idx, const double* zin, const double* joint,
                          const double* zc, const double* var_left);
 // dist_cond / distmix_cond: dist_output's table `t` of the same call, the measured SNPs of the wings appended (rows = every measured
 // SNP of the extended window as for slct_output; row_m[i] / row_u[i] = the table row of measured / unmeasured SNP i, -1 when the
 // table does not list it), the columns wing order z_cond pval_cond var_left added -- imputed rows carry cond_z / cond_var -- and the
 // named matrix `signals` [n_sel x 3]: table row (from 0), z_entry, z_joint.  -1 (message set, `t` untouched) when `t` has a column
 // that is not one of dist_output's
-int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+int cond_output(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int n_sel, const int32_t* idx, const double* zin, const double* joint, const double* zc, const double* var_left,
                  const double* cond_z, const double* cond_var);
 // dist_cs / distmix_cs: cond_output's table `t` of the same call (its `at` rows: every measured SNP has one), the columns pip cs
 // cs_pip added -- cs = the 1-based order of entry of the credible set that holds the SNP (the `order` column's numbering), 0 for none
 // -- and the named matrix `sets` [n_sel x 4]: table row of the lead SNP (from 0), size, mass, lse.  pip / set / set_pip are indexed by
 // candidate: the M = rows.size() measured SNPs first, then the unmeasured ones.  -1 (message set) when `t` is not cond_output's
-int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+int cs_output(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
               int n_sel, const int32_t* idx, const double* pip, const int32_t* set, const double* set_pip,
               const int32_t* size, const double* mass, const double* lse);
 // dist_susie / distmix_susie: the call's own table `t` with the wings' measured SNPs appended (cond_output's rows) and the columns wing
 // pip cs cs_pip added -- cs = the 1-based effect of the kept set that holds the SNP, 0 for none -- the named matrices `effects` [L x 7]
 // (table row of the SNP of largest alpha from 0, V, lse, size, mass, purity, kept) and `fit` [1 x 3] (sweeps, delta, converged), and a
 // message when the sweeps ran out or the window was not fitted.  pip / set / set_pip / alpha [L][T] are indexed by candidate
-int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+int susie_output(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const double* pip, const int32_t* set, const double* set_pip, const double* alpha, const double* V,
                  const double* lse, const int32_t* size, const double* mass, const double* purity, const int32_t* kept, const double* sweeps);
 // dist_xsusie / distmix_xsusie, the joint fit across studies.  xs_build_map: plain arrays in, plain array out -- key_lead [n_lead] and
@@ -578,12 +582,12 @@ struct SusieFit {                     // one trait's out_susie_* (first) or the 
     const int32_t *set, *size, *kept;
 };
 struct ColocMore { int k; SusieFit fit; const double* pp; const int32_t* hit; const double* hit_pp; const int32_t* n; };
-int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+int coloc_output(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const SusieFit& first, int n_more, const double* z_more, const double* out_z_more, const ColocMore& more);
 // dist_ldscore / distmix_ldscore: a table of its own, one row per target: rsid chr bp a1 a2 af1ref|af1mix l2 l2_raw n_band, and the named
 // matrix `ldscore` [1 x 4]: n_eff, M (reference rows of the window, targets included), M_5_50 (those with min(af, 1 - af) > 0.05), radius
-struct LdsRow { SnpIdent id; double af; };
-gauss_table* ldscore_output(bool mix, const std::vector<LdsRow>& rows, const double* l2, const double* raw, const double* mass, double n_eff,
+// (rows: id and af are read)
+gauss_table* ldscore_output(bool mix, const std::vector<ViewSnp>& rows, const double* l2, const double* raw, const double* mass, double n_eff,
                             int64_t n_ref, int64_t n_ref_5_50, int64_t radius);
 // Kish's effective size of a weighted panel: (sum w_p)^2 / sum (w_p^2 / n_p) over the populations of non-zero weight; sizes [P]
 double kish_n_eff(const double* w, const int32_t* pop_off, int P);
@@ -591,7 +595,7 @@ double kish_n_eff(const double* w, const int32_t* pop_off, int P);
 // (r = z / sqrt(n - 2 + z^2), 0 where z is not finite: such a SNP is frozen at weight 0), the named matrices `beta` [n_s n_lam x rows],
 // grid cell i_s n_lam + i_lam, and `grid` [n_s n_lam x 9]: s, lam, nnz, sweeps, delta, br, bg, kkt, converged; a message when a cell
 // ran its sweeps out and when the window was not fitted.  beta [n_s][n_lam][rows]
-gauss_table* prs_output(bool mix, const std::vector<SlctRow>& rows, double n, double tol, const std::vector<double>& s,
+gauss_table* prs_output(bool mix, const std::vector<ViewSnp>& rows, double n, double tol, const std::vector<double>& s,
                         const std::vector<double>& lam, const double* beta, const int32_t* nnz, const int32_t* sweeps, const double* delta,
                         const double* br, const double* bg, const double* kkt);
 // dist_traits / distmix_traits: the Z-scores of one further trait at the n measured SNPs of a window.  SNP i is at(i) -- position and
@@ -623,9 +627,8 @@ void traits_output(gauss_table& t, int n_more, const std::vector<int32_t>& row_m
 double slct_chi2_of(double p);
 
 // ---- the riders of a one-window call (host_riders.cpp; run by host_calls.cpp:run_impute) ----
-// What a rider reads of the window of its call, filled once from whichever source the call took (host_calls.cpp:view_of_lean, view_of_prepared -- the lean
-// window on a sorted packed panel, or gauss_prepared).  The strings of `id` point into that source: a view does not outlive it.
-struct ViewSnp { SnpIdent id; double af, z; int wing; };     // af: af1mix | af1ref; wing: 0 inside [start_bp, end_bp] (dist.cpp:92), else 1
+// What a rider reads of the window of its call, filled once by the window itself (host_calls.cpp: CallWindow::view -- the lean window
+// on a sorted packed panel, or gauss_prepared).  It points into the window: a view does not outlive it.
 struct WindowView {
     bool mix = false;
     std::vector<ViewSnp> measured;                  // the measured SNPs of the EXTENDED window, matrix row order

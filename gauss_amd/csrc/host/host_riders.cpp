@@ -58,14 +58,12 @@ int SlctRider::ask(gauss_window_desc& d, const WindowView& v)
 
 int SlctRider::table(const WindowView& v, gauss_table** out)
 {
-    std::vector<SlctRow> rows;
-    for (const ViewSnp& s : v.measured) rows.push_back(SlctRow{s.id, s.af, s.z, s.wing});
     if (!unmeasured) {
-        *out = slct_output(v.mix, rows, n, idx.data(), zin.data(), joint.data(), zc.data(), var.data());
+        *out = slct_output(v.mix, v.measured, n, idx.data(), zin.data(), joint.data(), zc.data(), var.data());
         return 0;
     }
     if (v.plain(out)) return -1;
-    if (cond_output(**out, rows, v.row_m, v.row_u, n, idx.data(), zin.data(), joint.data(), zc.data(), var.data(), cond_z.data(), cond_var.data())) {
+    if (cond_output(**out, v.measured, v.row_m, v.row_u, n, idx.data(), zin.data(), joint.data(), zc.data(), var.data(), cond_z.data(), cond_var.data())) {
         gauss_table_free(*out); *out = nullptr;
         return -1;
     }
@@ -89,9 +87,7 @@ int CsRider::ask(gauss_window_desc& d, const WindowView& v)
 int CsRider::table(const WindowView& v, gauss_table** out)
 {
     if (SlctRider::table(v, out)) return -1;
-    std::vector<SlctRow> rows;
-    for (const ViewSnp& s : v.measured) rows.push_back(SlctRow{s.id, s.af, s.z, s.wing});
-    if (cs_output(**out, rows, v.row_m, v.row_u, n, idx.data(), pip.data(), set.data(), set_pip.data(), size.data(), mass.data(), lse.data())) {
+    if (cs_output(**out, v.measured, v.row_m, v.row_u, n, idx.data(), pip.data(), set.data(), set_pip.data(), size.data(), mass.data(), lse.data())) {
         gauss_table_free(*out); *out = nullptr;
         return -1;
     }
@@ -129,9 +125,7 @@ int SusieRider::ask(gauss_window_desc& d, const WindowView&)
 int SusieRider::table(const WindowView& v, gauss_table** out)
 {
     if (v.plain(out)) return -1;
-    std::vector<SlctRow> rows;
-    for (const ViewSnp& s : v.measured) rows.push_back(SlctRow{s.id, s.af, s.z, s.wing});
-    if (susie_output(**out, rows, v.row_m, v.row_u, n_eff, tol_used, pip.data(), set.data(), set_pip.data(), alpha.data(), V.data(), lse.data(),
+    if (susie_output(**out, v.measured, v.row_m, v.row_u, n_eff, tol_used, pip.data(), set.data(), set_pip.data(), alpha.data(), V.data(), lse.data(),
                      size.data(), mass.data(), purity.data(), kept.data(), sweeps.data())) {
         gauss_table_free(*out); *out = nullptr;
         return -1;
@@ -173,9 +167,7 @@ int PrsRider::ask(gauss_window_desc& d, const WindowView&)
 
 int PrsRider::table(const WindowView& v, gauss_table** out)
 {
-    std::vector<SlctRow> rows;
-    for (const ViewSnp& q : v.measured) rows.push_back(SlctRow{q.id, q.af, q.z, q.wing});
-    *out = prs_output(v.mix, rows, n, tol_used, s, lam, beta.data(), nnz.data(), sweeps.data(), delta.data(), br.data(), bg.data(), kkt.data());
+    *out = prs_output(v.mix, v.measured, n, tol_used, s, lam, beta.data(), nnz.data(), sweeps.data(), delta.data(), br.data(), bg.data(), kkt.data());
     return 0;
 }
 
@@ -254,15 +246,13 @@ int ColocRider::ask(gauss_window_desc& d, const WindowView& v)
 int ColocRider::table(const WindowView& v, gauss_table** out)
 {
     if (v.plain(out)) return -1;
-    std::vector<SlctRow> rows;
-    for (const ViewSnp& s : v.measured) rows.push_back(SlctRow{s.id, s.af, s.z, s.wing});
     const SusieRider& s = susie;
     const SusieFit first = {s.pip.data(), s.set_pip.data(), s.alpha.data(), s.V.data(), s.lse.data(), s.mass.data(), s.purity.data(),
                             s.sweeps.data(), s.set.data(), s.size.data(), s.kept.data()};
     const ColocMore more = {traits.n_more, {pip.data(), set_pip.data(), alpha.data(), V.data(), lse.data(), mass.data(), purity.data(),
                                             sweeps.data(), set.data(), size.data(), kept.data()},
                             pp.data(), hit.data(), hit_pp.data(), n.data()};
-    if (coloc_output(**out, rows, v.row_m, v.row_u, s.n_eff, s.tol_used, first, traits.n_more, traits.z.data(), traits.out_z.data(), more)) {
+    if (coloc_output(**out, v.measured, v.row_m, v.row_u, s.n_eff, s.tol_used, first, traits.n_more, traits.z.data(), traits.out_z.data(), more)) {
         gauss_table_free(*out); *out = nullptr;
         return -1;
     }

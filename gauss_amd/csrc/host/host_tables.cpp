@@ -243,7 +243,7 @@ gauss_table* loo_output(bool mix, const std::vector<LooRow>& rows, const double*
 // rsid chr bp a1 a2 af1ref|af1mix z wing order z_entry z_joint z_cond pval_cond var_left: every measured SNP of the extended window
 // (wing = 1 outside the prediction window: a signal in a wing is conditioned on, not hidden); order = 1 .. n for the selected SNPs in
 // order of entry, 0 otherwise; z_entry / z_joint NaN unless selected; pval_cond = 2 pnorm(-|z_cond|)
-gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, const int32_t* idx, const double* zin, const double* joint,
+gauss_table* slct_output(bool mix, const std::vector<ViewSnp>& rows, int n_sel, const int32_t* idx, const double* zin, const double* joint,
                          const double* zc, const double* var_left)
 {
     gauss_table* t = new gauss_table();
@@ -270,7 +270,7 @@ gauss_table* slct_output(bool mix, const std::vector<SlctRow>& rows, int n_sel, 
 // holds a column this function does not know how to fill for a wing row (`t` is then left as it came).
 // The measured SNPs the call's own table does not list (the wings': row_m < 0) appended to it in matrix order, so that every measured SNP
 // has a row: `at` = table row of measured SNP i, `nrow` = rows afterwards.  `room` further columns must still fit.  -1: message set
-static int append_wing_rows(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, size_t room, const char* who,
+static int append_wing_rows(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, size_t room, const char* who,
                             std::vector<int32_t>& at, size_t& nrow)
 {
     static const char* const known[] = {"rsid", "chr", "bp", "a1", "a2", "af1ref", "af1mix", "z", "pval", "info", "type"};
@@ -283,7 +283,7 @@ static int append_wing_rows(gauss_table& t, const std::vector<SlctRow>& rows, co
     for (size_t i = 0; i < rows.size(); i++) {
         if (at[i] >= 0) continue;
         at[i] = (int32_t)nrow++;
-        const SlctRow& r = rows[i];
+        const ViewSnp& r = rows[i];
         for (Column& c : t.cols) {
             if (c.name == "rsid") c.s.emplace_back(r.id.rsid);
             else if (c.name == "a1") c.s.emplace_back(r.id.a1);
@@ -300,7 +300,7 @@ static int append_wing_rows(gauss_table& t, const std::vector<SlctRow>& rows, co
     return 0;
 }
 
-int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+int cond_output(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int n_sel, const int32_t* idx, const double* zin, const double* joint, const double* zc, const double* var_left,
                  const double* cond_z, const double* cond_var)
 {
@@ -333,7 +333,7 @@ int cond_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vec
 // dist_cs / distmix_cs: `t` is cond_output's table of the same call -- dist_output's rows, then the wings' measured SNPs in matrix order,
 // which is how the table row of a measured SNP the plain table does not list is found again.  Adds pip, cs (1-based order of entry of
 // the set that holds the SNP, 0: none) and cs_pip, and the named matrix `sets` [n x 4]: table row of the lead SNP, size, mass, lse.
-int cs_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+int cs_output(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
               int n_sel, const int32_t* idx, const double* pip, const int32_t* set, const double* set_pip,
               const int32_t* size, const double* mass, const double* lse)
 {
@@ -406,7 +406,7 @@ static void susie_trait_output(gauss_table& t, size_t nrow, const std::vector<in
 }
 
 // the wing column and the table row of every candidate, the measured SNPs (appended ones included) first
-static std::vector<int32_t> wing_column(gauss_table& t, size_t nrow, const std::vector<SlctRow>& rows, const std::vector<int32_t>& at,
+static std::vector<int32_t> wing_column(gauss_table& t, size_t nrow, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& at,
                                         const std::vector<int32_t>& row_u)
 {
     const size_t M = rows.size();
@@ -418,7 +418,7 @@ static std::vector<int32_t> wing_column(gauss_table& t, size_t nrow, const std::
     return row_of;
 }
 
-int susie_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+int susie_output(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const double* pip, const int32_t* set, const double* set_pip, const double* alpha, const double* V,
                  const double* lse, const int32_t* size, const double* mass, const double* purity, const int32_t* kept, const double* sweeps)
 {
@@ -478,7 +478,7 @@ int xsusie_output(gauss_table& t, const std::vector<int32_t>& row_m, const std::
     return 0;
 }
 
-int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
+int coloc_output(gauss_table& t, const std::vector<ViewSnp>& rows, const std::vector<int32_t>& row_m, const std::vector<int32_t>& row_u,
                  int L, double tol, const SusieFit& first, int n_more, const double* z_more, const double* out_z_more, const ColocMore& more)
 {
     std::vector<int32_t> at;
@@ -522,7 +522,7 @@ int coloc_output(gauss_table& t, const std::vector<SlctRow>& rows, const std::ve
 
 // dist_prs / distmix_prs: one row per measured SNP of the extended window; `beta` [n_s n_lam x rows] and `grid` [n_s n_lam x 9] as named
 // matrices (host_internal.h).  converged = delta < tol r_max (or r_max = 0), the kernel's own rule on the same r
-gauss_table* prs_output(bool mix, const std::vector<SlctRow>& rows, double n, double tol, const std::vector<double>& s,
+gauss_table* prs_output(bool mix, const std::vector<ViewSnp>& rows, double n, double tol, const std::vector<double>& s,
                         const std::vector<double>& lam, const double* beta, const int32_t* nnz, const int32_t* sweeps, const double* delta,
                         const double* br, const double* bg, const double* kkt)
 {
@@ -556,7 +556,7 @@ gauss_table* prs_output(bool mix, const std::vector<SlctRow>& rows, double n, do
 }
 
 // dist_ldscore / distmix_ldscore: one row per target (host_internal.h); n_band travels as the exact double the device summed
-gauss_table* ldscore_output(bool mix, const std::vector<LdsRow>& rows, const double* l2, const double* raw, const double* mass, double n_eff,
+gauss_table* ldscore_output(bool mix, const std::vector<ViewSnp>& rows, const double* l2, const double* raw, const double* mass, double n_eff,
                             int64_t n_ref, int64_t n_ref_5_50, int64_t radius)
 {
     gauss_table* t = new gauss_table();

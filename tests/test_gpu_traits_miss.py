@@ -586,3 +586,26 @@ def test_dist_traits_and_distmix_traits_impute_what_a_file_lacks(ctx, study, mix
     with pytest.raises(Exception, match=r"few.txt has ([0-9]|10) of the window's \d+ measured SNPs: a trait needs more than 10"):
         fn(*study["nwin"], who, [inp, study["few"]], idx, dat, desc, af1_cutoff=cutoff, ctx=ctx, missing="impute")
     assert ctx.counters() == c0
+
+
+def test_missing_impute_gives_one_frame_on_every_panel_form(ctx, study, monkeypatch):
+    """missing="impute" with three traits on WIN: the packed panel (a lean window), the packed panel with GAUSS_HOST_FULL_MAP=1 (the
+    literal data layer on packed rows) and the text panel give the same frame, bit for bit, for dist_traits and distmix_traits"""
+    from gauss_amd import api
+    inp, idx, dat, desc = study["files"]
+    for mix in (False, True):
+        fn = api.distmix_traits if mix else api.dist_traits
+        call = lambda index, data: fn(*WIN, WGT if mix else "EUR", [inp] + study["more"], index, data, desc, af1_cutoff=0.02 if mix else 0.01,
+                                      ctx=ctx, missing="impute")
+        packed = call("(unused)", study["packed"])
+        with monkeypatch.context() as m:
+            m.setenv("GAUSS_HOST_FULL_MAP", "1")
+            full = call("(unused)", study["packed"])
+        text = call(idx, dat)
+        assert len(packed) > 0 and max(packed.attrs["n_missing"]) >= 3
+        for other in (full, text):
+            assert list(other.columns) == list(packed.columns) and len(other) == len(packed)
+            for c in packed.columns:
+                a, b = packed[c], other[c]
+                assert np.array_equal(a.to_numpy(), b.to_numpy(), equal_nan=True) if a.dtype.kind == "f" else list(a) == list(b), (mix, c)
+            assert list(other.attrs["n_missing"]) == list(packed.attrs["n_missing"])

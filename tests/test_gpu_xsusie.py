@@ -376,3 +376,26 @@ def test_dist_xsusie_and_distmix_xsusie_end_to_end(ctx, two_studies, mix):
     assert all(np.array_equal(other.attrs["effects"][k], eff[k], equal_nan=True) for k in eff) and other.attrs["fit"] == fit
     with pytest.raises(Exception, match="2 .. 4 studies"):
         fn(*win, who[:1], inputs[:1], idx, dat, desc, af1_cutoff=cutoff, ctx=ctx)
+
+
+def test_the_whole_snp_map_on_a_packed_panel_gives_the_lean_windows_table(ctx, two_studies, monkeypatch):
+    """GAUSS_HOST_FULL_MAP=1 on the packed panel (every study's window built by the literal data layer, rows from the packed store)
+    against the same call without it (lean windows): the same frame, bit for bit, for dist_xsusie and distmix_xsusie"""
+    from gauss_amd import api
+    inp, _, _, desc = two_studies["files"]
+    inputs = [inp, two_studies["second"]]
+    for mix in (False, True):
+        fn = api.distmix_xsusie if mix else api.dist_xsusie
+        who = [cs_ref.WGT, WGT_B] if mix else ["EUR", "ASN"]
+        call = lambda: fn(*cs_ref.STUDY_WINDOW, who, inputs, "(unused)", two_studies["packed"], desc, af1_cutoff=0.02 if mix else 0.01, ctx=ctx,
+                          L=6, coverage=0.9, max_sweeps=40)
+        lean = call()
+        with monkeypatch.context() as m:
+            m.setenv("GAUSS_HOST_FULL_MAP", "1")
+            full = call()
+        assert list(full.columns) == list(lean.columns) and len(full) == len(lean) > 0
+        for c in lean.columns:
+            a, b = lean[c], full[c]
+            assert np.array_equal(a.to_numpy(), b.to_numpy(), equal_nan=True) if a.dtype.kind == "f" else list(a) == list(b), (mix, c)
+        assert all(np.array_equal(full.attrs["effects"][k], v, equal_nan=True) for k, v in lean.attrs["effects"].items()), mix
+        assert full.attrs["fit"] == lean.attrs["fit"]

@@ -233,3 +233,48 @@ def test_ask_sets_the_descriptor_and_refuses_what_the_window_shows(riders_output
     assert "bad more_input_files" in refused[3]
     assert "further traits: a call takes at most" in refused[4]
     assert lines[-1] == "plain 6"            # cond, traits and miss asked the view for the call's own table once each, and so did the test
+
+
+def test_one_window_calls_refuse_first_failure_first_on_every_panel_form(tmp_path, monkeypatch):
+    """Up to its descriptor a one-window call needs no GPU.  A description file that is not there, an unknown
+    population, a study file that is not there and a window with too few SNPs are refused in that order -- each call below has every
+    later fault too -- with the same text on the text panel, on the packed panel (a lean window) and on the packed panel under
+    GAUSS_HOST_FULL_MAP=1 (the literal data layer): by the plain call, a call with a rider, the joint fit, the LD scores and computeLD."""
+    import ctypes
+    import types
+    from gauss_amd import api, panel
+    pops = [("P00", 60, "EUR"), ("P01", 45, "ASN"), ("P02", 52, "EUR")]
+    p = panel.make_synthetic_study(str(tmp_path), pops, n_snp=300, bp_lo=1_000_000, bp_hi=2_000_000, frac_measured=0.4, seed=5)["paths"]
+    inp, idx, dat, desc = p["gwas.txt"], p["index.gz"], p["data.gz"], p["desc.txt"]
+    gpk = str(tmp_path / "p.gpk")
+    assert api.pack_panel(idx, dat, desc, gpk) > 0
+    fake = types.SimpleNamespace(handle=ctypes.c_void_p(1))      # never dereferenced: every call is refused before the GPU is asked
+    nofile, nodesc = str(tmp_path / "nothing.txt"), str(tmp_path / "nodesc.txt")
+    wgt, bad_wgt = (["P00", "P01"], [0.5, 0.5]), (["P00", "XYZ"], [0.5, 0.5])
+    empty = (22, 1_000_000, 1_000_001)                            # a window that holds no SNP
+    calls = {                                                     # (who, input, desc) -> the call on (index, data)
+        "dist": lambda who, f, d: lambda i, g: api.dist(*empty, 0, who[0], f, i, g, d, ctx=fake),
+        "dist_susie": lambda who, f, d: lambda i, g: api.dist_susie(*empty, 0, who[0], f, i, g, d, ctx=fake),
+        "distmix_traits": lambda who, f, d: lambda i, g: api.distmix_traits(*empty, 0, who[1], [f, f], i, g, d, ctx=fake),
+        "dist_xsusie": lambda who, f, d: lambda i, g: api.dist_xsusie(*empty, 0, [who[0], "ASN"], [f, f], i, g, d, ctx=fake),
+        "distmix_ldscore": lambda who, f, d: lambda i, g: api.distmix_ldscore(*empty, 0, who[1], f, i, g, d, ctx=fake),
+        "computeLD": lambda who, f, d: lambda i, g: api.computeLD(*empty, who[1], f, i, g, d, ctx=fake),
+    }
+    few = {"distmix_ldscore": "LD scores: no SNP of .* the window has no SNP to score", "computeLD": "computeLD not performed \\(measured 0\\)",
+           "distmix_traits": "Not enough number of SNPs loaded - DISTMIX not performed"}
+    stages = [("no description file", (("XYZ", bad_wgt)), nofile, nodesc, lambda name: "nodesc.txt"),
+              ("an unknown population", ("XYZ", bad_wgt), nofile, desc, lambda name: "XYZ"),
+              ("no study file", ("EUR", wgt), nofile, desc, lambda name: "nothing.txt"),
+              ("too few SNPs", ("EUR", wgt), inp, desc, lambda name: few.get(name, "Not enough number of SNPs loaded - DIST not performed"))]
+    for name, make in calls.items():
+        for what, who, f, d, want in stages:
+            if what == "an unknown population" and name in ("distmix_traits", "distmix_ldscore", "computeLD"):
+                continue                                          # (a weight under a name the panel lacks is ignored, not refused)
+            call = make(who, f, d)
+            said = []
+            for index, data, full in ((idx, dat, "0"), ("(unused)", gpk, "0"), ("(unused)", gpk, "1")):
+                monkeypatch.setenv("GAUSS_HOST_FULL_MAP", full)
+                with pytest.raises(Exception, match=want(name)) as e:
+                    call(index, data)
+                said.append(str(e.value))
+            assert said[0] == said[1] == said[2], (name, what, said)
