@@ -45,7 +45,7 @@ HOST_SYMBOLS = [
     "gauss_host_jepeg_gene_tail", "gauss_host_plan_cost",
     "gauss_host_jepeg_rank", "gauss_host_jepeg_genome", "gauss_prepared_jepeg_plan", "gauss_prepared_jepeg_finish",
     "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
-    "gauss_host_simulateLD", "gauss_host_simulate_draws", "gauss_host_clump",
+    "gauss_host_simulateLD", "gauss_host_simulate_draws", "gauss_host_clump", "gauss_host_ldsplit",
     "gauss_host_sumchi2", "gauss_host_sumchi2mix", "gauss_host_sumchi2_pval",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
@@ -146,6 +146,8 @@ def load_host():
     h.gauss_host_distmix_slct.argtypes = h.gauss_host_distmix.argtypes[:-1] + slct_tail
     h.gauss_host_slct_chi2.argtypes = [_dbl, _dp]
     h.gauss_host_clump.argtypes = [_vp, C.c_int, _i64, _i64, _strs, _dp, C.c_int] + files4 + [_dbl, _dbl, _dbl, _dbl, _dbl, C.POINTER(_vp)]
+    h.gauss_host_ldsplit.argtypes = [_vp, C.c_int, _i64, _i64, _strs, _dp, C.c_int] + files4 + [_dbl, _dbl, C.c_int, C.c_int, C.c_int, _dbl, _dbl,
+                                                                                                 C.POINTER(_vp)]
     h.gauss_host_dist_cond.argtypes = h.gauss_host_dist_slct.argtypes
     h.gauss_host_distmix_cond.argtypes = h.gauss_host_distmix_slct.argtypes
     h.gauss_host_dist_cs.argtypes = h.gauss_host_dist_slct.argtypes[:-1] + [_dbl, _dbl, C.POINTER(_vp)]      # ..., coverage, prior_var, out
@@ -351,6 +353,72 @@ def clump(chr, start_bp, end_bp, pop_wgt_df, input_file, reference_index_file, r
     import pandas as pd       # (the frame's attrs carry the clumps: this call needs pandas)
     df.attrs["clumps"] = pd.DataFrame(dict(index_row=cm[:, 0], size=cm[:, 1], bp_first=cm[:, 2], bp_last=cm[:, 3]))
     return df
+
+
+def ldsplit(chr, start_bp, end_bp, pop_wgt_df, input_file, reference_index_file, reference_data_file, reference_pop_desc_file,
+            thr_r2=0.02, min_size=50, max_size=1000, max_K=128, max_r2=0.3, kb=None, af1_cutoff=None, ctx=None):
+    """Approximately independent LD blocks of a region of a mixed-ancestry study, on the ancestry-weighted LD of computeLD, on the GPU
+    (gauss_host_ldsplit): the splits of the region's SNPs (computeLD's for the same arguments, in position order) into K = 1 .. max_K
+    contiguous blocks of min_size .. max_size SNPs that minimise the sum of r^2 over the pairs in different blocks.  A pair with r^2
+    below thr_r2, or further apart than kb (None: no limit), costs nothing; no pair with r^2 above max_r2 ends in two blocks (1: off).
+    Returns a frame with one row per K that has a split: n_block, cost, perc_kept (sum of size^2 / M^2: the share of the LD matrix
+    that the blocks keep), cost2 (sum of size^2), max_size_used.  ``attrs["snps"]``: computeLD's snplist frame; ``attrs["last"]``:
+    per row, the snplist row of every block's last SNP; ``attrs["max_r2_at"]`` [M + 1]: the largest r^2 cut by a boundary before SNP b;
+    ``attrs["n_nonfinite"]``: LD entries in the band that are not finite (counted as 0).  Which K to use is the caller's choice (a
+    small cost at a small cost2; bigsnpr's guide plots one against the other); ldsplit_blocks() turns a row into blocks.  One region
+    of at most 8 192 SNPs per call, blocks of at most 4 096, at most 128 of them; sizes in SNPs.  The result is held to the rule of
+    include/gauss_hip.h and its numpy statement (tests/ldsplit_ref.py), not to bigsnpr's snp_ldsplit output.  min_size, max_size and
+    max_K are taken as given: 0 is refused here (the C call reads 0 as "not given")."""
+    for name, v in (("min_size", min_size), ("max_size", max_size), ("max_K", max_K)):
+        if int(v) < 1:
+            raise GaussError(f"ldsplit: {name} = {int(v)}; it must be at least 1")
+    h = load_host()
+    names, w, n = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_ldsplit(_ctx(ctx), int(chr), int(start_bp), int(end_bp), names, w.ctypes.data_as(_dp), n, _enc(input_file),
+                                 _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
+                                 float(thr_r2), int(min_size), int(max_size), int(max_K), float(max_r2),
+                                 float("nan") if kb is None else float(kb), C.byref(out)))
+    named = _named(h, out)
+    snps, _ = _table(h, out)
+    import pandas as pd       # (the frame's attrs carry the SNPs and the splits: this call needs pandas)
+    sp = np.asarray(named["splits"]).reshape(-1, 5)
+    last = np.asarray(named["last"]).reshape(len(sp), -1).astype(np.int64) if len(sp) else np.zeros((0, 0), dtype=np.int64)
+    df = pd.DataFrame(dict(n_block=sp[:, 0].astype(np.int64), cost=sp[:, 1], perc_kept=sp[:, 2], cost2=sp[:, 3].astype(np.int64),
+                           max_size_used=sp[:, 4].astype(np.int64)))
+    df.attrs["snps"] = snps
+    df.attrs["last"] = [last[r, :int(sp[r, 0])].copy() for r in range(len(sp))]
+    df.attrs["max_r2_at"] = np.asarray(named["max_r2_at"]).reshape(-1)
+    df.attrs["n_nonfinite"] = int(np.asarray(named["n_nonfinite"]).reshape(-1)[0])
+    return df
+
+
+def ldsplit_blocks(res, K):
+    """The K blocks of an ldsplit() result as a frame, one row per block: block (from 1), first_row, last_row (snplist rows, inclusive),
+    size, first_rsid, last_rsid, start_bp, end_bp.  Consecutive blocks tile the region with no gap and no overlap: a block ends at
+    the midpoint between its last SNP and the next block's first (end_bp, inclusive; the next block's start_bp is end_bp + 1); the
+    first block starts at the first SNP, the last ends at the last SNP.  Loop a per-window call (distmix_susie, distmix_prs, clump)
+    over the rows' start_bp .. end_bp.  K must be one of res.n_block.  Refused: a split with a boundary between two SNPs at one
+    position -- no bp range can tell them apart, and a call over start_bp .. end_bp would hand the second SNP to the earlier block;
+    take another K, or work by first_row .. last_row of ``res.attrs["last"]``."""
+    import pandas as pd
+    rows = np.flatnonzero(res["n_block"].to_numpy() == int(K))
+    if len(rows) != 1:
+        raise GaussError(f"ldsplit_blocks: the result holds no split into {K} blocks (it has {list(res['n_block'])})")
+    snps = res.attrs["snps"]
+    last = np.asarray(res.attrs["last"][int(rows[0])], dtype=np.int64)
+    first = np.concatenate([[0], last[:-1] + 1])
+    bp = snps["bp"].to_numpy().astype(np.int64)
+    rsid = list(snps["rsid"])
+    tied = np.flatnonzero(bp[last[:-1]] == bp[first[1:]])
+    if len(tied):
+        k = int(tied[0])
+        raise GaussError(f"ldsplit_blocks: the boundary between blocks {k + 1} and {k + 2} of the split into {K} lies between two SNPs at bp "
+                         f"{int(bp[last[k]])} ({rsid[last[k]]}, {rsid[first[k + 1]]}): no bp range separates them")
+    end_bp = np.concatenate([(bp[last[:-1]] + bp[first[1:]]) // 2, bp[-1:]])
+    start_bp = np.concatenate([bp[:1], end_bp[:-1] + 1])
+    return pd.DataFrame(dict(block=np.arange(1, len(last) + 1), first_row=first, last_row=last, size=last - first + 1,
+                             first_rsid=[rsid[i] for i in first], last_rsid=[rsid[i] for i in last], start_bp=start_bp, end_bp=end_bp))
 
 
 def simulate_draws(pop_wgt_df, sim_size, reference_pop_desc_file, seed=None):

@@ -2,6 +2,8 @@
 #include "gauss_job.h"
 
 // the kernels' constants that include/gauss_hip.h states to the caller (gauss_internal.h does not see that header)
+static_assert(gauss::LDSPLIT_M_MAX == GAUSS_LDSPLIT_MAX_M && gauss::LDSPLIT_SIZE_MAX == GAUSS_LDSPLIT_MAX_SIZE && gauss::LDSPLIT_K_MAX == GAUSS_LDSPLIT_MAX_K,
+              "LD splitting: gauss_internal.h and include/gauss_hip.h disagree");
 static_assert(gauss::CLUMP_M_MAX == GAUSS_CLUMP_MAX_M && gauss::CLUMP_KEYS_MAX == GAUSS_CLUMP_MAX_KEYS, "clumping: gauss_internal.h and include/gauss_hip.h disagree");
 static_assert(gauss::SC2_N_MAX == GAUSS_SUMCHI2_MAX_N && gauss::SC2_K_MAX == GAUSS_SUMCHI2_MAX_KEPT && gauss::SC2_TRAITS_MAX == GAUSS_SUMCHI2_MAX_TRAITS,
               "sum of chi2: gauss_internal.h and include/gauss_hip.h disagree");
@@ -419,6 +421,65 @@ int gauss_ld_clump_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t 
     if (out_r2) HIPCHK(hipMemcpyAsync(out_r2, d_r2.p, sizeof(double) * TM, hipMemcpyDeviceToHost, st));
     if (out_n_clumps) HIPCHK(hipMemcpyAsync(out_n_clumps, d_n.p, sizeof(int) * (size_t)n_key, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return job_fetch(job.get());
+}
+
+int gauss_ld_split_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp,
+                        const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop, int on_device,
+                        const int32_t* bp, int64_t radius, double thr_r2, int min_size, int max_size, int max_K, double max_r2,
+                        double* out_cost, int32_t* out_prev, double* out_max_r2, int64_t* out_n_nonfinite)
+{
+    if (!ctx || !store) return fail(GAUSS_E_INVALID, "bad arguments to gauss_ld_split_rows");
+    if (!bp) return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: bp is NULL");
+    if (!out_cost) return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: out_cost is NULL");
+    if (n_snp < 1 || n_snp > LDSPLIT_M_MAX)
+        return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: n_snp = %d; a region holds 1 .. %d SNPs", n_snp, LDSPLIT_M_MAX);
+    if (max_size < 1 || max_size > LDSPLIT_SIZE_MAX)
+        return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: max_size = %d; a block holds 1 .. %d SNPs", max_size, LDSPLIT_SIZE_MAX);
+    if (min_size < 1 || min_size > max_size)
+        return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: min_size = %d is outside 1 .. max_size = %d", min_size, max_size);
+    if (max_K < 1 || max_K > LDSPLIT_K_MAX)
+        return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: max_K = %d; a call splits into 1 .. %d blocks", max_K, LDSPLIT_K_MAX);
+    for (int i = 1; i < n_snp; i++)
+        if (bp[i] < bp[i - 1]) return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: bp decreases at row %d (%d after %d)", i, bp[i], bp[i - 1]);
+    if (radius < 0) return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: radius = %lld is negative", (long long)radius);
+    if (!(thr_r2 >= 0.0 && thr_r2 <= 1.0)) return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: thr_r2 = %g is outside [0, 1]", thr_r2);
+    if (!(max_r2 >= 0.0 && max_r2 <= 1.0)) return fail(GAUSS_E_INVALID, "gauss_ld_split_rows: max_r2 = %g is outside [0, 1]", max_r2);
+    JobGuard job(nullptr, job_free);
+    int rc = ld_job(ctx, ld_spec_rows(mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop, 1.0), on_device, job);
+    if (rc) return rc;
+    rc = job_run(job.get(), false);
+    if (rc) return rc;
+    // the matrix stays where the epilogue wrote it (out_ld, both triangles); the kernels run behind the job on the same stream
+    hipStream_t st = ctx->stream;
+    const size_t M = (size_t)n_snp, Mp = M + 1, W = std::min((size_t)max_size, M), K = (size_t)max_K;
+    DevBuf d_bp, d_sd, d_smd, d_tk, d_c, d_cfin, d_mx, d_prev, d_n;
+    if (d_bp.alloc(ctx, sizeof(int) * M) != hipSuccess || d_sd.alloc(ctx, sizeof(double) * W * M) != hipSuccess ||
+        d_smd.alloc(ctx, sizeof(double) * W * M) != hipSuccess || d_tk.alloc(ctx, sizeof(double) * W * Mp) != hipSuccess ||
+        d_c.alloc(ctx, sizeof(double) * 2 * Mp) != hipSuccess || d_cfin.alloc(ctx, sizeof(double) * K) != hipSuccess ||
+        d_mx.alloc(ctx, sizeof(double) * Mp) != hipSuccess || d_prev.alloc(ctx, sizeof(int) * K * Mp) != hipSuccess ||
+        d_n.alloc(ctx, sizeof(unsigned long long)) != hipSuccess)
+        return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes of suffix sums, block costs and boundaries) failed",
+                    sizeof(double) * (2 * W * M + W * Mp + 3 * Mp + K) + sizeof(int) * (K * Mp + M));
+    HIPCHK(hipMemcpyAsync(d_bp.p, bp, sizeof(int) * M, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_n.p, 0, sizeof(unsigned long long), st));
+    LdSplitArgs a;
+    a.R = job->plans[0].p.out_ld; a.bp = d_bp.as<int>();
+    a.Sd = d_sd.as<double>(); a.SMd = d_smd.as<double>(); a.Tk = d_tk.as<double>();
+    a.C0 = d_c.as<double>(); a.C1 = d_c.as<double>() + Mp; a.cfin = d_cfin.as<double>(); a.mx = d_mx.as<double>();
+    a.prev = d_prev.as<int>(); a.n_nonfinite = d_n.as<unsigned long long>();
+    a.radius = (long long)std::min<int64_t>(radius, (int64_t)1 << 32);      // positions are 32-bit: 2^32 is every band already
+    a.thr_r2 = thr_r2; a.max_r2 = max_r2;
+    a.M = n_snp; a.W = (int)W; a.min_size = min_size; a.max_size = max_size; a.max_K = max_K;
+    launch_ldsplit(a, st);
+    HIPCHK(hipGetLastError());
+    unsigned long long n_bad = 0;
+    HIPCHK(hipMemcpyAsync(out_cost, d_cfin.p, sizeof(double) * K, hipMemcpyDeviceToHost, st));
+    if (out_prev) HIPCHK(hipMemcpyAsync(out_prev, d_prev.p, sizeof(int) * K * Mp, hipMemcpyDeviceToHost, st));
+    if (out_max_r2) HIPCHK(hipMemcpyAsync(out_max_r2, d_mx.p, sizeof(double) * Mp, hipMemcpyDeviceToHost, st));
+    if (out_n_nonfinite) HIPCHK(hipMemcpyAsync(&n_bad, d_n.p, sizeof(n_bad), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (out_n_nonfinite) *out_n_nonfinite = (int64_t)n_bad;
     return job_fetch(job.get());
 }
 

@@ -248,6 +248,14 @@ constexpr int LDS_MAX_CHUNKS = 65535;  // chunks of a window: they are the y ext
 constexpr int CLUMP_T = 512;            // threads of clump_kernel: one workgroup per trait
 constexpr int CLUMP_M_MAX = 8192;      // GAUSS_CLUMP_MAX_M: keys, owner and bp of a region in LDS, 16 bytes a SNP (k_clump.hip)
 constexpr int CLUMP_KEYS_MAX = 64;     // GAUSS_CLUMP_MAX_KEYS: traits of one call, the x extent of clump_kernel's grid
+constexpr int LDSPLIT_M_MAX = 8192;    // GAUSS_LDSPLIT_MAX_M: SNPs of a region that ldsplit_* split (k_ldsplit.hip)
+constexpr int LDSPLIT_SIZE_MAX = 4096; // GAUSS_LDSPLIT_MAX_SIZE: SNPs of a block; Sd, SMd and Tk are [min(max_size, M)][M] doubles each
+constexpr int LDSPLIT_K_MAX = 128;     // GAUSS_LDSPLIT_MAX_K: blocks of a split = launches of ldsplit_dp_kernel
+constexpr int LDSPLIT_ROWS = 64;       // rows of a tile of ldsplit_band_kernel: one per lane of its wave
+constexpr int LDSPLIT_OFFS = 64;       // offsets j - i of a tile of ldsplit_band_kernel: the chunk its scan walks out of LDS
+constexpr int LDSPLIT_COST_T = 64;     // threads of ldsplit_cost_kernel: one boundary each
+constexpr int LDSPLIT_DP_B = 64;       // boundaries of a workgroup of ldsplit_dp_kernel: one per lane
+constexpr int LDSPLIT_DP_NW = 16;      // waves of that workgroup: wave w takes every LDSPLIT_DP_NW-th block size from the w-th on
 constexpr int SC2_T = 256;             // threads of sumchi2_kernel: one workgroup per gene
 constexpr int SC2_N_MAX = 1024;        // GAUSS_SUMCHI2_MAX_N: SNPs of a gene before pruning; flags and the kept list in LDS (k_sumchi2.hip)
 constexpr int SC2_K_MAX = 128;         // GAUSS_SUMCHI2_MAX_KEPT: order of the eigenvalue solve; the kept block in LDS, 129 doubles a row
@@ -555,6 +563,23 @@ struct ClumpArgs {
     int M;
 };
 void launch_clump(const ClumpArgs& a, int n_key, hipStream_t s);
+// Optimal LD-block boundaries (k_ldsplit.hip) on a full M x M LD matrix in device memory (an LD-only job's out_ld).  W = min(max_size,
+// M); every pointer is a device pointer.  Sd[d - 1][i] = S[i][i + d], SMd likewise, d = 1 .. W, pitch M; Tk[k - 1][b] = T[b][k],
+// k = 1 .. min(W, b), pitch M + 1; C0 / C1 [M + 1] hold C[k - 1] and C[k] in turn; prev [max_K][M + 1]; cfin [max_K]; mx [M + 1]
+struct LdSplitArgs {
+    const double* R;        // [M][M], both triangles
+    const int* bp;          // [M], never decreasing
+    double *Sd, *SMd, *Tk;
+    double *C0, *C1;
+    double* cfin;
+    double* mx;
+    int* prev;
+    unsigned long long* n_nonfinite;      // one counter, zero before the launches
+    long long radius;
+    double thr_r2, max_r2;
+    int M, W, min_size, max_size, max_K;
+};
+void launch_ldsplit(const LdSplitArgs& a, hipStream_t s);      // band, cost, then max_K launches of the DP, all queued on s
 // Gene-based sum-of-chi2 (k_sumchi2.hip) on the blocks a gene job left in out_ld: one workgroup per gene.  The arguments travel by
 // value; every pointer is a device pointer and none is null
 struct Sumchi2Args {

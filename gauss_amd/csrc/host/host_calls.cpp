@@ -1167,6 +1167,33 @@ int gauss_host_clump(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, 
     return 0;
 }
 
+int gauss_host_ldsplit(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                       int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                       const char* reference_pop_desc_file, double af1_cutoff, double thr_r2, int min_size, int max_size, int max_K,
+                       double max_r2, double kb, gauss_table** out)
+{
+    if (!ctx || !out) return herr("bad arguments");
+    LdSplitParams k;
+    if (ldsplit_params(thr_r2, min_size, max_size, max_K, max_r2, kb, k)) return -1;
+    LdRows s;
+    if (computeld_rows(ctx, chr, start_bp, end_bp, pop_names, pop_wgts, n_pop_wgt, input_file, reference_index_file, reference_data_file,
+                       reference_pop_desc_file, af1_cutoff, s)) return -1;
+    const int M = s.M;
+    if (M > GAUSS_LDSPLIT_MAX_M)
+        return herr("ldsplit: the region holds %d SNPs of the study; a call splits at most %d (ask for a shorter region)", M, GAUSS_LDSPLIT_MAX_M);
+    const std::vector<int32_t>& bp = s.t->cols[2].i;                     // add_ident_columns: rsid chr bp a1 a2
+    std::vector<double> cost((size_t)k.max_K), mx((size_t)M + 1);
+    std::vector<int32_t> prev((size_t)k.max_K * ((size_t)M + 1));
+    int64_t n_bad = 0;
+    if (gauss_ld_split_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
+                            s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, s.on_device,
+                            bp.data(), k.radius, k.thr_r2, k.min_size, k.max_size, k.max_K, k.max_r2, cost.data(), prev.data(), mx.data(),
+                            &n_bad) != 0) return herr("%s", gauss_last_error());
+    ldsplit_output(*s.t, M, k.max_K, cost.data(), prev.data(), mx.data(), n_bad);
+    *out = s.t.release();
+    return 0;
+}
+
 // ---- jepeg() / jepegmix() over several ranks ("genes: contiguous gene ranges") ------------------------------
 // Genes are independent (jepeg.cpp:114-131: one Gene object per gene, nothing shared but the read-only SNP map; grouping at
 // gauss.cpp:1383-1439).  Every rank runs the same host data layer on the same files, derives the same plan -- contiguous gene

@@ -775,6 +775,16 @@ int clump_keys(double p1, double p2, double r2, double kb, ClumpKeys& out);
 // it -- and the named matrix `clumps` [n_clumps x 4], one row per clump in rank order: index row (from 0), size, bp of the first
 // member, bp of the last.  owner / rank / r2 [M] as gauss_ld_clump_rows returned them
 void clump_output(gauss_table& t, const std::vector<double>& z, const int32_t* owner, const int32_t* rank, const double* r2, int n_clumps);
+// ldsplit(): the arguments of gauss_ld_split_rows from the call's (host_tables.cpp).  NaN / 0 (not given) takes the default: thr_r2 0.02,
+// min_size 50, max_size 1000, max_K GAUSS_LDSPLIT_MAX_K, max_r2 0.3, kb none (the band is max_size alone).  -1 with the message set:
+// thr_r2 or max_r2 outside [0, 1], a size or max_K outside gauss_ld_split_rows' limits, min_size > max_size, kb < 0 or not finite
+struct LdSplitParams { double thr_r2, max_r2; int min_size, max_size, max_K; int64_t radius; };
+int ldsplit_params(double thr_r2, int min_size, int max_size, int max_K, double max_r2, double kb, LdSplitParams& out);
+// ... and its table: `t` holds computeLD's snplist columns and keeps them; four named matrices are added -- `splits` [n x 5], one row
+// per K that has a split, ascending: n_block, cost, perc_kept (sum of size^2 / M^2), cost2 (sum of size^2), max_size_used; `last`
+// [n x the largest such K]: the table row of every block's last SNP, -1 beyond the row's K; `max_r2_at` [M + 1 x 1]: Mx; `n_nonfinite`
+// [1 x 1].  cost [max_K], prev [max_K][M + 1], mx [M + 1] as gauss_ld_split_rows returned them; the splits are read backwards from prev
+void ldsplit_output(gauss_table& t, int M, int max_K, const double* cost, const int32_t* prev, const double* mx, int64_t n_nonfinite);
 // sumchi2(): P(sum lambda_i chi2_1 > q) (host_tables.cpp; the method: gauss_host_sumchi2_pval in include/gauss_host.h).  lambda_i <= 0
 // or NaN are left out; n_pos (may be null): how many stay
 double sumchi2_pval(const double* lam, int n, double q, int* n_pos);

@@ -811,6 +811,57 @@ gauss_table* sumchi2_output(const std::vector<std::string>& geneid, const std::v
     return t.release();
 }
 
+int ldsplit_params(double thr_r2, int min_size, int max_size, int max_K, double max_r2, double kb, LdSplitParams& out)
+{
+    out.thr_r2 = std::isnan(thr_r2) ? 0.02 : thr_r2;
+    out.max_r2 = std::isnan(max_r2) ? 0.3 : max_r2;
+    out.min_size = min_size == 0 ? 50 : min_size;
+    out.max_size = max_size == 0 ? 1000 : max_size;
+    out.max_K = max_K == 0 ? GAUSS_LDSPLIT_MAX_K : max_K;
+    if (!(out.thr_r2 >= 0.0 && out.thr_r2 <= 1.0)) return herr("ldsplit: thr_r2 = %g is outside [0, 1]", out.thr_r2);
+    if (!(out.max_r2 >= 0.0 && out.max_r2 <= 1.0)) return herr("ldsplit: max_r2 = %g is outside [0, 1]", out.max_r2);
+    if (out.max_size < 1 || out.max_size > GAUSS_LDSPLIT_MAX_SIZE)
+        return herr("ldsplit: max_size = %d; a block holds 1 .. %d SNPs", out.max_size, GAUSS_LDSPLIT_MAX_SIZE);
+    if (out.min_size < 1 || out.min_size > out.max_size)
+        return herr("ldsplit: min_size = %d is outside 1 .. max_size = %d", out.min_size, out.max_size);
+    if (out.max_K < 1 || out.max_K > GAUSS_LDSPLIT_MAX_K)
+        return herr("ldsplit: max_K = %d; a call splits into 1 .. %d blocks", out.max_K, GAUSS_LDSPLIT_MAX_K);
+    out.radius = (int64_t)1 << 32;                                      // no limit: positions are 32-bit
+    if (!std::isnan(kb)) {
+        if (!(kb >= 0.0) || !std::isfinite(kb) || kb * 1000.0 > 4e9) return herr("ldsplit: kb = %g; the distance is 0 .. 4 000 000 kb", kb);
+        out.radius = (int64_t)llround(kb * 1000.0);
+    }
+    return 0;
+}
+
+void ldsplit_output(gauss_table& t, int M, int max_K, const double* cost, const int32_t* prev, const double* mx, int64_t n_nonfinite)
+{
+    const size_t Mp = (size_t)M + 1;
+    std::vector<int> ks;
+    for (int K = 1; K <= max_K; K++)
+        if (std::isfinite(cost[K - 1])) ks.push_back(K);
+    const size_t n = ks.size(), kmax = n ? (size_t)ks.back() : 0;
+    std::vector<double> sp(n * 5, 0.0), last(n * kmax, -1.0);           // column-major
+    for (size_t r = 0; r < n; r++) {
+        const int K = ks[r];
+        double sum2 = 0.0, biggest = 0.0;
+        int b = M;
+        for (int k = K; k >= 1; k--) {                                  // block k is rows a .. b - 1
+            const int a = prev[(size_t)(k - 1) * Mp + (size_t)b];
+            const double size = (double)(b - a);
+            sum2 += size * size;
+            biggest = std::max(biggest, size);
+            last[(size_t)(k - 1) * n + r] = (double)(b - 1);
+            b = a;
+        }
+        sp[r] = (double)K; sp[n + r] = cost[K - 1]; sp[2 * n + r] = sum2 / ((double)M * (double)M); sp[3 * n + r] = sum2; sp[4 * n + r] = biggest;
+    }
+    t.put_named("splits", (int)n, 5, std::move(sp));
+    t.put_named("last", (int)n, (int)kmax, std::move(last));
+    t.put_named("max_r2_at", (int)Mp, 1, std::vector<double>(mx, mx + Mp));
+    t.put_named("n_nonfinite", 1, 1, std::vector<double>(1, (double)n_nonfinite));
+}
+
 gauss_table* qcat_output(gauss_prepared& p)     // qcat.cpp:94-131 / qcatmix.cpp:102-139
 {
     const bool mix = p.kind == GAUSS_KIND_QCATMIX;

@@ -277,6 +277,60 @@ def ld_clump_rows(store, rows, pop_off, bp, key, pop_wgt=None, mode=MODE_WEIGHTE
     return _clump(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, key, radius, r2_min, key_index, key_member)
 
 
+def ldsplit_backtrack(cost, prev, K):
+    """The boundaries b_1 < ... < b_K = M of the best K-block split (block k is rows b_{k-1} .. b_k - 1, b_0 = 0), read backwards from
+    prev [max_K, M + 1]; None where cost[K - 1] is +inf."""
+    if not np.isfinite(cost[K - 1]):
+        return None
+    b = prev.shape[1] - 1
+    ends = np.empty(K, dtype=np.int64)
+    for k in range(K, 0, -1):
+        ends[k - 1] = b
+        b = int(prev[k - 1, b])
+    assert b == 0
+    return ends
+
+
+def _split(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, radius, thr_r2, min_size, max_size, max_K, max_r2):
+    b = np.ascontiguousarray(bp, dtype=np.int32).reshape(-1)
+    if b.shape != (S,):
+        raise ValueError(f"bp has shape {b.shape}: expected ({S},)")
+    K = int(max_K)
+    cost, prev = np.full(max(K, 0), np.nan), np.full((max(K, 0), S + 1), -2, dtype=np.int32)
+    mx, n = np.full(S + 1, np.nan), np.full(1, -1, dtype=np.int64)
+    check(ctx.lib.gauss_ld_split_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip), _lib.ptr(so, _ip),
+                                      _lib.ptr(w, _dp), len(po) - 1, on_dev, b.ctypes.data_as(_ip), int(radius), float(thr_r2), int(min_size),
+                                      int(max_size), K, float(max_r2), cost.ctypes.data_as(_dp), prev.ctypes.data_as(_ip),
+                                      mx.ctypes.data_as(_dp), n.ctypes.data_as(C.POINTER(C.c_int64))))
+    return dict(cost=cost, prev=prev, max_r2=mx, n_nonfinite=int(n[0]),
+                splits={k: ldsplit_backtrack(cost, prev, k) for k in range(1, K + 1)})
+
+
+def ld_split(geno, pop_off, bp, pop_wgt=None, mode=MODE_WEIGHTED, radius=1 << 32, thr_r2=0.02, min_size=50, max_size=1000,
+             max_K=_lib.LDSPLIT_MAX_K, max_r2=0.3, ctx=None):
+    """gauss_ld_split_rows on the rows of a byte matrix: the splits of the rows (in position order; bp [S] never decreases) into
+    K = 1 .. max_K contiguous blocks of min_size .. max_size rows that minimise the sum of r^2 between blocks, on the LD that
+    ld_matrix would return, which stays on the device.  The defaults: a pair below thr_r2 costs nothing, blocks of 50 .. 1 000 rows,
+    up to GAUSS_LDSPLIT_MAX_K of them, no pair above max_r2 across a boundary, no distance limit beside max_size.  Returns
+    dict(cost [max_K] (+inf: no such split), prev [max_K, S + 1], max_r2 [S + 1], n_nonfinite, splits): splits[K] is the array of
+    the K blocks' end rows (exclusive, the last is S), or None.  Which K to use is the caller's choice."""
+    ctx = ctx or default_context()
+    g = _lib.as_u8(geno)
+    po, w = _pops(pop_off, pop_wgt)
+    return _split(ctx, g.ctypes.data, g.strides[0], _lib.GENO_U8, 0, None, g.shape[0], po, None, w, mode, bp, radius, thr_r2, min_size,
+                  max_size, max_K, max_r2)
+
+
+def ld_split_rows(store, rows, pop_off, bp, pop_wgt=None, mode=MODE_WEIGHTED, radius=1 << 32, thr_r2=0.02, min_size=50, max_size=1000,
+                  max_K=_lib.LDSPLIT_MAX_K, max_r2=0.3, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
+    """ld_split on the store rows `rows` (a numpy matrix of host rows, a RowStore or a raw device pointer, as ld_matrix_rows)."""
+    ctx = ctx or default_context()
+    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
+    po, w = _pops(pop_off, pop_wgt)
+    S = len(r) if r is not None else store.shape[0]
+    return _split(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, radius, thr_r2, min_size, max_size, max_K, max_r2)
+
+
 def ld_resampled(store, rows, pop_off, draw_pop, draw_sample, n_cols, diag=1.0, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
     """gauss_ld_resampled_rows: pooled LD (CalCor, n = n_cols) of the store rows `rows` (None: rows 0 .. S-1 of a numpy matrix)
     over the drawn samples -- draw k is sample draw_sample[k] of population draw_pop[k] -- and n_cols - len(draws) zero columns

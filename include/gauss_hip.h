@@ -709,6 +709,39 @@ int gauss_ld_clump_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t 
                         double key_index, double key_member,
                         int32_t* out_owner, int32_t* out_rank, double* out_r2, int32_t* out_n_clumps);
 
+/* Optimal LD-block boundaries of the n_snp rows of a region on their LD, which is formed as gauss_ld_rows forms it (same rows, same
+ * bits, diag 1) and never leaves the device: the split of rows 0 .. M - 1 (M = n_snp, in position order) into K contiguous blocks of
+ * min_size .. max_size rows that minimises the sum of r^2 over the pairs that land in different blocks, for every K = 1 .. max_K at
+ * once.  Rows as in gauss_ld_rows.  bp [n_snp]: positions, never decreasing.  With R the LD matrix and W = max_size:
+ *     pair value, i < j:  the pair is in the band iff j - i < W and bp_j - bp_i <= radius; a pair outside the band is never read
+ *                         (further apart than max_size it is cut by every split: a constant).  e_ij = R_ij * R_ij, one rounded fp64
+ *                         product; where R_ij is not finite the pair counts 0 everywhere and 1 in n_nonfinite
+ *     row suffix sums:    hi_i = one past row i's last band column;  S[i][hi_i] = 0;  S[i][b] = S[i][b + 1] + (e_ib < thr_r2 ? 0 : e_ib)
+ *                         for b = hi_i - 1 down to i + 1, in that order;  SM[i][b] = max(SM[i][b + 1], e_ib) likewise (no threshold)
+ *     block cost:         T[b][0] = 0;  T[b][k] = T[b][k - 1] + S[b - k][b], k = 1 .. min(W, b), in that order: the pairs between
+ *                         block [b - k, b) and everything to its right
+ *     boundaries:         Mx[b] = max over k of SM[b - k][b];  0 < b < M is admissible iff Mx[b] <= max_r2 (max_r2 = 1: all are)
+ *     the programme:      C[0][0] = 0, C[0][b] = +inf;  C[k][b] = min over a in [b - max_size, b - min_size], a >= 0, of
+ *                         C[k - 1][a] + T[b][b - a], ties to the smaller a, the minimiser in P[k][b];  C[k][b] = +inf, P[k][b] = -1
+ *                         where no candidate is finite or b < M is not admissible
+ * Every step is in a fixed order or does not depend on one: the outputs do not depend on the thread mapping, on the source format of
+ * the rows or on the run.  out_cost [max_K]: C[K][M], +inf where no split into K blocks exists (K min_size > M, K max_size < M, or
+ * max_r2 closes too many boundaries).  out_prev [max_K][n_snp + 1] int32: P[K][b]; the best K-block split is read backwards from
+ * b = M: b <- P[k][b] for k = K .. 1.  out_max_r2 [n_snp + 1]: Mx (0 at b = 0 and b = M).  out_n_nonfinite [1]: non-finite band
+ * entries.  All but out_cost may be NULL.
+ * Refused (GAUSS_E_INVALID, before anything is allocated or launched): NULL bp / out_cost; n_snp outside 1 .. GAUSS_LDSPLIT_MAX_M;
+ * max_size outside 1 .. GAUSS_LDSPLIT_MAX_SIZE; min_size < 1 or > max_size; max_K outside 1 .. GAUSS_LDSPLIT_MAX_K; a bp that
+ * decreases; radius < 0; thr_r2 or max_r2 outside [0, 1] or NaN; and whatever gauss_ld_rows refuses.  One region per call; a radius
+ * above 2^32 is taken as 2^32; beside the matrix (8 n_snp^2 bytes) the call takes 24 min(max_size, n_snp) n_snp bytes of device
+ * memory (0.8 GiB at the limits).  Blocking. */
+#define GAUSS_LDSPLIT_MAX_M    8192
+#define GAUSS_LDSPLIT_MAX_SIZE 4096
+#define GAUSS_LDSPLIT_MAX_K    128
+int gauss_ld_split_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows,
+                        int n_snp, const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop,
+                        int on_device, const int32_t* bp, int64_t radius, double thr_r2, int min_size, int max_size, int max_K,
+                        double max_r2, double* out_cost, int32_t* out_prev, double* out_max_r2, int64_t* out_n_nonfinite);
+
 /* Gene-based sum-of-chi2 test (the statistic of fastBAT, VEGAS and MAGMA's SNP-wise mean model) of n_gene genes on their LD
  * blocks, which are formed as gauss_gene_ld_batch[_rows] forms them with diag = 1 (same rows, same bits) and never leave the
  * device.  Gene g owns rows [gene_off[g], gene_off[g+1]), n of them, with block R.  z [n_trait][n_snp]: one row per trait, the

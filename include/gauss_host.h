@@ -592,6 +592,25 @@ int gauss_host_sumchi2mix(gauss_ctx* ctx, const char* const* pop_names, const do
  * approximation: DESIGN.md states its measured accuracy against numerical inversion. */
 int gauss_host_sumchi2_pval(const double* lam, int n, double q, double* p, int* n_pos);
 
+/* ldsplit(): approximately independent LD blocks of a region of a mixed-ancestry study -- the splits of the region's SNPs into
+ * K = 1 .. max_K contiguous blocks of min_size .. max_size SNPs that minimise the sum of r^2 between blocks -- on the ancestry-weighted
+ * LD of computeLD, which never leaves the GPU (gauss_ld_split_rows, include/gauss_hip.h: the rule).  The arguments are
+ * gauss_host_computeLD's plus the split's; the SNPs are exactly computeLD's selection for the same arguments (same snplist, same "Not
+ * enough number of SNPs loaded" error).  thr_r2: a pair with r^2 below it costs nothing; max_r2: no pair with r^2 above it may end in
+ * two blocks (1: off); kb: pairs further apart cost nothing.  NaN / 0 (not given) takes the default: thr_r2 0.02, min_size 50,
+ * max_size 1000, max_K GAUSS_LDSPLIT_MAX_K, max_r2 0.3, kb none.  Refused: thr_r2 or max_r2 outside [0, 1], max_size outside
+ * 1 .. GAUSS_LDSPLIT_MAX_SIZE (4 096), min_size outside 1 .. max_size, max_K outside 1 .. GAUSS_LDSPLIT_MAX_K (128), kb < 0, a region
+ * of more than GAUSS_LDSPLIT_MAX_M (8 192) SNPs.  Result: computeLD's snplist (one row per SNP: rsid chr bp a1 a2 af1mix) and four
+ * named matrices: "splits" [n x 5], one row per K that has a split, ascending: n_block, cost, perc_kept (sum of size^2 / M^2), cost2
+ * (sum of size^2), max_size_used; "last" [n x the largest such K]: the snplist row (from 0) of every block's last SNP, -1 beyond the
+ * row's K; "max_r2_at" [M + 1 x 1]: the largest r^2 that boundary b cuts; "n_nonfinite" [1 x 1]: band entries of the LD that are not
+ * finite (a monomorphic SNP) and count as 0.  Which K to use is the caller's choice.  One region per call; sizes in SNPs, not in bp
+ * or cM; the study file decides which SNPs exist. */
+int gauss_host_ldsplit(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                       int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,
+                       const char* reference_pop_desc_file, double af1_cutoff, double thr_r2, int min_size, int max_size, int max_K,
+                       double max_r2, double kb, gauss_table** out);
+
 #define GAUSS_ZMIX_POPULATION      0
 #define GAUSS_ZMIX_SUPERPOPULATION 1
 int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
