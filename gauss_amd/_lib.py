@@ -37,6 +37,8 @@ PRS_MAX_S, PRS_MAX_LAM, PRS_MAX_SWEEPS, PRS_MAX_M = 8, 32, 1000, 4096      # GAU
 LDS_MAX_ANNOT, LDS_CHUNK = 32, 64      # GAUSS_LDS_MAX_ANNOT, GAUSS_LDS_CHUNK
 CLUMP_MAX_M, CLUMP_MAX_KEYS = 8192, 64  # GAUSS_CLUMP_MAX_M, GAUSS_CLUMP_MAX_KEYS
 LDSPLIT_MAX_M, LDSPLIT_MAX_SIZE, LDSPLIT_MAX_K = 8192, 4096, 128      # GAUSS_LDSPLIT_MAX_*
+HESS_MAX_M, HESS_MAX_TRAITS, HESS_MAX_K = 4096, 64, 1024      # GAUSS_HESS_MAX_*
+ST_HESS_NOCONV = 512     # GAUSS_ST_HESS_NOCONV
 SUMCHI2_MAX_N, SUMCHI2_MAX_KEPT, SUMCHI2_MAX_TRAITS = 1024, 128, 64      # GAUSS_SUMCHI2_MAX_*
 ST_SUMCHI2_TOOLARGE, ST_SUMCHI2_EMPTY = 128, 256       # GAUSS_ST_SUMCHI2_*
 CODE_ADDITIVE, CODE_DOMINANT, CODE_RECESSIVE = 1, 2, 4
@@ -102,7 +104,7 @@ SYMBOLS = [
     "gauss_ld_rows", "gauss_gene_ld_batch_rows", "gauss_job_run", "gauss_job_fetch", "gauss_job_destroy", "gauss_job_span_ms", "gauss_job_profile",
     "gauss_job_profile_get", "gauss_job_work", "gauss_job_stats", "gauss_synth_device",
     "gauss_store_upload_async", "gauss_store_upload_fd_async", "gauss_store_wait", "gauss_store_alloc", "gauss_store_fill", "gauss_store_fill_fd", "gauss_store_upload_fd", "gauss_hip_context_id", "gauss_hip_add_destroy_hook", "gauss_hip_trim_cache", "gauss_hip_source_hash", "gauss_hip_counters", "gauss_job_counters", "gauss_hip_queues",
-    "gauss_pop_weights", "gauss_zmix_normal_eq", "gauss_ld_resampled_rows", "gauss_ld_clump_rows", "gauss_ld_split_rows",
+    "gauss_pop_weights", "gauss_zmix_normal_eq", "gauss_ld_resampled_rows", "gauss_ld_clump_rows", "gauss_ld_split_rows", "gauss_ld_hess_rows",
     "gauss_gene_sumchi2", "gauss_gene_sumchi2_rows",
 ]
 
@@ -181,6 +183,8 @@ def load():
                                         C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double, _ip, _ip, _dp, _ip]
     lib.gauss_ld_split_rows.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_int64, C.c_int, _ip, C.c_int, _ip, _ip, _dp, C.c_int, C.c_int, _ip,
                                         C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _ip, _dp, C.POINTER(C.c_int64)]
+    lib.gauss_ld_hess_rows.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_int64, C.c_int, _ip, C.c_int, _ip, _ip, _dp, C.c_int, C.c_int, _dp,
+                                       C.c_int, C.c_int, C.c_double, _dp, _dp, _ip, _ip, C.POINTER(C.c_int64), _ip, _dp, _ip]
     sc2_tail = [_dp, C.c_int, C.c_double, _ip, _ip, _dp, _dp, _ip, _ip, _ip]      # z, n_trait, prune_r2, then the seven outputs
     lib.gauss_gene_sumchi2.argtypes = lib.gauss_gene_ld_batch.argtypes[:-2] + sc2_tail
     lib.gauss_gene_sumchi2_rows.argtypes = lib.gauss_gene_ld_batch_rows.argtypes[:-3] + [C.c_int] + sc2_tail

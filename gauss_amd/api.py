@@ -45,7 +45,7 @@ HOST_SYMBOLS = [
     "gauss_host_jepeg_gene_tail", "gauss_host_plan_cost",
     "gauss_host_jepeg_rank", "gauss_host_jepeg_genome", "gauss_prepared_jepeg_plan", "gauss_prepared_jepeg_finish",
     "gauss_host_afmix", "gauss_host_cpw2", "gauss_host_popwgt_inputs", "gauss_host_zmix", "gauss_host_zmix_qp",
-    "gauss_host_simulateLD", "gauss_host_simulate_draws", "gauss_host_clump", "gauss_host_ldsplit",
+    "gauss_host_simulateLD", "gauss_host_simulate_draws", "gauss_host_clump", "gauss_host_ldsplit", "gauss_host_hess",
     "gauss_host_sumchi2", "gauss_host_sumchi2mix", "gauss_host_sumchi2_pval",
     "gauss_host_dist_loo", "gauss_host_distmix_loo",
     "gauss_host_dist_slct", "gauss_host_distmix_slct", "gauss_host_slct_chi2", "gauss_host_dist_cond", "gauss_host_distmix_cond",
@@ -148,6 +148,7 @@ def load_host():
     h.gauss_host_clump.argtypes = [_vp, C.c_int, _i64, _i64, _strs, _dp, C.c_int] + files4 + [_dbl, _dbl, _dbl, _dbl, _dbl, C.POINTER(_vp)]
     h.gauss_host_ldsplit.argtypes = [_vp, C.c_int, _i64, _i64, _strs, _dp, C.c_int] + files4 + [_dbl, _dbl, C.c_int, C.c_int, C.c_int, _dbl, _dbl,
                                                                                                  C.POINTER(_vp)]
+    h.gauss_host_hess.argtypes = [_vp, C.c_int, _i64, _i64, _strs, _dp, C.c_int, _strs, C.c_int, _cp, _cp, _cp, _dbl, C.c_int, _dbl, C.POINTER(_vp)]
     h.gauss_host_dist_cond.argtypes = h.gauss_host_dist_slct.argtypes
     h.gauss_host_distmix_cond.argtypes = h.gauss_host_distmix_slct.argtypes
     h.gauss_host_dist_cs.argtypes = h.gauss_host_dist_slct.argtypes[:-1] + [_dbl, _dbl, C.POINTER(_vp)]      # ..., coverage, prior_var, out
@@ -419,6 +420,134 @@ def ldsplit_blocks(res, K):
     start_bp = np.concatenate([bp[:1], end_bp[:-1] + 1])
     return pd.DataFrame(dict(block=np.arange(1, len(last) + 1), first_row=first, last_row=last, size=last - first + 1,
                              first_rsid=[rsid[i] for i in first], last_rsid=[rsid[i] for i in last], start_bp=start_bp, end_bp=end_bp))
+
+
+def hess(chr, start_bp, end_bp, pop_wgt_df, input_files, reference_index_file, reference_data_file, reference_pop_desc_file, n,
+         k=None, var_frac=0.99, k_max=256, eig_min=1e-6, overlap=None, af1_cutoff=None, ctx=None):
+    """Local heritability of one or more traits in an LD block of a mixed-ancestry study, and the local genetic covariance and
+    correlation of every pair of them (the statistics of HESS, rho-HESS and LAVA), on the ancestry-weighted LD of computeLD, which
+    stays on the GPU (gauss_host_hess): input_files names one study file per trait; the SNPs are computeLD's for the first file and
+    the same arguments, every further file must hold them all (swapped alleles flip the sign).  n: the traits' sample sizes (one
+    number, or one per file).  The block's LD is decomposed on the GPU (gauss_ld_hess_rows: all eigenvalues, the projections of every
+    trait on the first k_max eigenvectors); the estimators are hess_estimates' at the caller's k -- an integer, or the smallest k whose
+    eigenvalues hold var_frac of the trace (LAVA's 0.99) -- capped at min(k_max, n_pos); eig_min and overlap as hess_estimates.
+    Returns a frame with one row per trait: trait n k H h2 se n_snp n_pos var_kept.  attrs: pairs (a frame, one row per a < b: a b C
+    cov rg s), lam [M], curve [T, k_max] (H_t at every k: how the estimate moves with k), var_curve [k_max], snps (computeLD's snplist
+    frame), z [M, T], n_nonfinite, sweeps, status.  One block of at most 4 096 SNPs, 64 traits and k_max <= 1 024 per call: cut a
+    region with ldsplit() and ldsplit_blocks() first.  h2 is not bounded to [0, 1] and se is HESS's approximation; the values are held
+    to the rule of include/gauss_hip.h and the numpy statements of tests/hess_ref.py, not to the output of HESS, rho-HESS or LAVA."""
+    files = [os.fsencode(f) for f in input_files]
+    if not files:
+        raise ValueError("input_files: at least one study file")
+    if int(k_max) < 1:
+        raise GaussError(f"hess: k_max = {int(k_max)}; it must be at least 1")
+    h = load_host()
+    names, w, n_w = _pop_wgt(pop_wgt_df)
+    out = _vp()
+    _hcheck(h.gauss_host_hess(_ctx(ctx), int(chr), int(start_bp), int(end_bp), names, w.ctypes.data_as(_dp), n_w, (C.c_char_p * len(files))(*files),
+                              len(files), _enc(reference_index_file), _enc(reference_data_file), _enc(reference_pop_desc_file), _af(af1_cutoff),
+                              int(k_max), float(eig_min), C.byref(out)))
+    named = _named(h, out)
+    snps, _ = _table(h, out)
+    import pandas as pd       # (the frame's attrs carry the pairs and the SNPs: this call needs pandas)
+    T = len(files)
+    lam = np.asarray(named["lam"]).reshape(-1)
+    proj = np.asarray(named["proj"]).reshape(T, -1)
+    solve = np.asarray(named["solve"]).reshape(-1)
+    est = hess_estimates(lam, proj, n, k=k, var_frac=var_frac, overlap=overlap, eig_min=eig_min)
+    nn = np.broadcast_to(np.asarray(n, dtype=np.float64).reshape(-1), (T,))
+    df = pd.DataFrame(dict(trait=np.arange(1, T + 1), n=nn, k=est["k"], H=est["H"], h2=est["h2"], se=est["se"], n_snp=len(lam),
+                           n_pos=int(solve[0]), var_kept=est["var_kept"]))
+    pr = est["pairs"]
+    df.attrs.update(pairs=pd.DataFrame(dict(a=pr["a"] + 1, b=pr["b"] + 1, C=pr["C"], cov=pr["cov"], rg=pr["rg"], s=pr["s"])), lam=lam,
+                    curve=est["curve"], var_curve=est["var_curve"], snps=snps, z=np.asarray(named["z"]).reshape(len(lam), T),
+                    n_nonfinite=int(solve[2]), sweeps=int(solve[1]), status=int(solve[3]))
+    return df
+
+
+def hess_n_pos(lam, eig_min=1e-6):
+    """The number of eigenvalues a hess call projects on: lam_i > eig_min * lam_0 and lam_i > 0 (lam descending; 0 if one is not finite)."""
+    l = np.asarray(lam, dtype=np.float64).reshape(-1)
+    if not len(l) or not np.all(np.isfinite(l)):
+        return 0
+    return int(np.sum((l > float(eig_min) * l[0]) & (l > 0.0)))
+
+
+def hess_estimates(lam, proj, n, k=None, var_frac=0.99, overlap=None, eig_min=1e-6):
+    """The host arithmetic of hess() alone (no GPU): local heritability of each trait and genetic covariance / correlation of each pair
+    of traits from the eigenvalues lam [M] (descending) and the projections proj [T, k_max] that hotpath.ld_hess returns.  With p = proj,
+        H_t(k) = sum_{i<k} p[t,i]^2,  C_ab(k) = sum_{i<k} p[a,i] p[b,i]      (ascending i, plain fp64 adds)
+        h2_t   = (H_t(k) - k) / (n_t - k)
+        se_t^2 = (n_t / (n_t - k))^2 (2 k (1 - h2_t) / n_t + 4 h2_t) (1 - h2_t) / n_t
+        cov_ab = (C_ab(k) - k s_ab) / sqrt(n_a n_b),  rg_ab = cov_ab / sqrt(h2_a h2_b) (NaN unless both h2 > 0)
+    n: the traits' sample sizes (one number for all, or one per trait).  k: an integer, or (k=None) the smallest k whose share
+    sum_{i<k} lam / sum lam of the variance reaches var_frac (LAVA's 0.99); both are capped at min(k_max, n_pos), n_pos counted as
+    hess_n_pos does.  overlap: s_ab, the pair's intercept n_s rho_pheno / sqrt(n_a n_b) (None: 0; one number, or a [T, T] matrix).
+    Every product is of two projections on the same eigenvector, so no value depends on the eigenvectors' signs.  Returns dict(k, H, h2,
+    se [T], var_kept, n_pos, curve [T, k_max] (H_t at every k; NaN beyond the cap), var_curve [k_max], pairs: dict(a, b, C, s, cov, rg)
+    with one entry per a < b).  k = 0 (no positive eigenvalue): H = 0 and NaN estimates."""
+    l = np.asarray(lam, dtype=np.float64)
+    p = np.asarray(proj, dtype=np.float64)
+    if l.ndim != 1 or not len(l):
+        raise GaussError(f"hess_estimates: lam has shape {l.shape}; expected (M,) with M >= 1")
+    if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] < 1:
+        raise GaussError(f"hess_estimates: proj has shape {p.shape}; expected (T, k_max)")
+    T, k_max = p.shape
+    if np.any(l[1:] > l[:-1]):
+        raise GaussError("hess_estimates: lam is not in descending order")
+    nn = np.asarray(n, dtype=np.float64).reshape(-1)
+    if len(nn) == 1:
+        nn = np.repeat(nn, T)
+    if len(nn) != T:
+        raise GaussError(f"hess_estimates: n has {len(nn)} entries for {T} traits")
+    if not np.all(np.isfinite(nn)) or np.any(nn <= 0):
+        raise GaussError("hess_estimates: every n must be positive and finite")
+    if not (0.0 <= float(eig_min) < 1.0):
+        raise GaussError(f"hess_estimates: eig_min = {eig_min} is outside [0, 1)")
+    n_pos = hess_n_pos(l, eig_min)
+    cap = min(k_max, n_pos)
+    tot = np.cumsum(l)[-1]
+    var_curve = np.cumsum(l[:k_max]) / tot if tot > 0 else np.full(min(k_max, len(l)), np.nan)
+    if k is not None:
+        if int(k) != k or int(k) < 1:
+            raise GaussError(f"hess_estimates: k = {k}; it must be a whole number of at least 1")
+        kk = min(int(k), cap)
+    else:
+        if not (0.0 < float(var_frac) <= 1.0):
+            raise GaussError(f"hess_estimates: var_frac = {var_frac} is outside (0, 1]")
+        hit = np.flatnonzero(var_curve[:cap] >= float(var_frac))
+        kk = int(hit[0]) + 1 if len(hit) else cap
+    if np.any(nn <= kk):
+        raise GaussError(f"hess_estimates: n = {nn.min():g} is not above k = {kk}; the estimator needs n > k")
+    if overlap is None:
+        s = np.zeros((T, T))
+    else:
+        s = np.asarray(overlap, dtype=np.float64)
+        if s.ndim == 0:
+            s = np.full((T, T), float(s))
+        if s.shape != (T, T) or not np.all(np.isfinite(s)):
+            raise GaussError(f"hess_estimates: overlap has shape {s.shape}; expected one finite number or a finite ({T}, {T}) matrix")
+    curve = np.cumsum(p * p, axis=1)
+    curve[:, cap:] = np.nan
+    nan = np.full(T, np.nan)
+    if kk == 0:
+        H, h2, se = np.zeros(T), nan.copy(), nan.copy()
+    else:
+        H = curve[:, kk - 1].copy()
+        h2 = (H - kk) / (nn - kk)
+        se2 = (nn / (nn - kk)) ** 2 * (2.0 * kk * (1.0 - h2) / nn + 4.0 * h2) * (1.0 - h2) / nn
+        se = np.sqrt(np.where(se2 >= 0, se2, np.nan))
+    ia, ib = np.triu_indices(T, 1)
+    if kk == 0:
+        Cab = np.zeros(len(ia))
+        cov = rg = np.full(len(ia), np.nan)
+    else:
+        Cab = np.cumsum(p[ia, :kk] * p[ib, :kk], axis=1)[:, -1] if len(ia) else np.zeros(0)
+        cov = (Cab - kk * s[ia, ib]) / np.sqrt(nn[ia] * nn[ib])
+        ok = (h2[ia] > 0) & (h2[ib] > 0)
+        rg = np.where(ok, cov / np.sqrt(np.where(ok, h2[ia] * h2[ib], 1.0)), np.nan)
+    return dict(k=kk, H=H, h2=h2, se=se, var_kept=float(var_curve[kk - 1]) if kk else 0.0, n_pos=n_pos, curve=curve, var_curve=var_curve,
+                pairs=dict(a=ia, b=ib, C=Cab, s=s[ia, ib], cov=cov, rg=rg))
 
 
 def simulate_draws(pop_wgt_df, sim_size, reference_pop_desc_file, seed=None):

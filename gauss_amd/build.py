@@ -40,6 +40,7 @@ HIP_UNITS = {
     "k_ldscore.hip": ["-ffp-contract=off"],     # LD scores: one product and one add per row, the chunks' partials in a fixed order
     "k_clump.hip": ["-ffp-contract=off"],       # LD clumping: one product per pair, no sums at all
     "k_ldsplit.hip": ["-ffp-contract=off"],     # LD-block boundaries: one product per pair, the scans and the min-plus steps as written
+    "k_hess.hip": ["-ffp-contract=off"],        # block eigen-solver and projections: the rotations and the sums as written, MFMA chains in ascending k
     "k_sumchi2.hip": ["-ffp-contract=off"],     # gene-based sum of chi2: the Jacobi rotations and the sums as written, in a fixed order
     "k_xsusie.hip": ["-ffp-contract=off"],      # joint fine-mapping across studies: the fit's sums as written, in a fixed order
     "k_coloc.hip": ["-ffp-contract=off"],       # colocalisation of the fit's traits: the shifted sums as written, in a fixed order

@@ -1,7 +1,14 @@
 // libgauss_hip.so -- the C ABI of include/gauss_hip.h: jobs, the blocking window call, the LD entry points.
 #include "gauss_job.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
 
 // the kernels' constants that include/gauss_hip.h states to the caller (gauss_internal.h does not see that header)
+static_assert(gauss::HESS_M_MAX == GAUSS_HESS_MAX_M && gauss::HESS_TRAITS_MAX == GAUSS_HESS_MAX_TRAITS && gauss::HESS_K_MAX == GAUSS_HESS_MAX_K,
+              "hess: gauss_internal.h and include/gauss_hip.h disagree");
 static_assert(gauss::LDSPLIT_M_MAX == GAUSS_LDSPLIT_MAX_M && gauss::LDSPLIT_SIZE_MAX == GAUSS_LDSPLIT_MAX_SIZE && gauss::LDSPLIT_K_MAX == GAUSS_LDSPLIT_MAX_K,
               "LD splitting: gauss_internal.h and include/gauss_hip.h disagree");
 static_assert(gauss::CLUMP_M_MAX == GAUSS_CLUMP_MAX_M && gauss::CLUMP_KEYS_MAX == GAUSS_CLUMP_MAX_KEYS, "clumping: gauss_internal.h and include/gauss_hip.h disagree");
@@ -480,6 +487,98 @@ int gauss_ld_split_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t 
     if (out_n_nonfinite) HIPCHK(hipMemcpyAsync(&n_bad, d_n.p, sizeof(n_bad), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (out_n_nonfinite) *out_n_nonfinite = (int64_t)n_bad;
+    return job_fetch(job.get());
+}
+
+int gauss_ld_hess_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows, int n_snp,
+                       const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop, int on_device,
+                       const double* z, int n_trait, int k_max, double eig_min, double* out_lam, double* out_proj,
+                       int32_t* out_n_pos, int32_t* out_sweeps, int64_t* out_n_nonfinite, int32_t* out_status,
+                       double* out_vectors, int32_t* out_order)
+{
+    if (!ctx || !store) return fail(GAUSS_E_INVALID, "bad arguments to gauss_ld_hess_rows");
+    if (!z) return fail(GAUSS_E_INVALID, "gauss_ld_hess_rows: z is NULL");
+    if (!out_lam) return fail(GAUSS_E_INVALID, "gauss_ld_hess_rows: out_lam is NULL");
+    if (!out_proj) return fail(GAUSS_E_INVALID, "gauss_ld_hess_rows: out_proj is NULL");
+    if (n_snp < 1 || n_snp > HESS_M_MAX)
+        return fail(GAUSS_E_INVALID, "gauss_ld_hess_rows: n_snp = %d; a block holds 1 .. %d SNPs", n_snp, HESS_M_MAX);
+    if (n_trait < 1 || n_trait > HESS_TRAITS_MAX)
+        return fail(GAUSS_E_INVALID, "gauss_ld_hess_rows: n_trait = %d; a call takes 1 .. %d traits", n_trait, HESS_TRAITS_MAX);
+    if (k_max < 1 || k_max > HESS_K_MAX)
+        return fail(GAUSS_E_INVALID, "gauss_ld_hess_rows: k_max = %d; a call projects on 1 .. %d eigenvectors", k_max, HESS_K_MAX);
+    if (!(eig_min >= 0.0 && eig_min < 1.0)) return fail(GAUSS_E_INVALID, "gauss_ld_hess_rows: eig_min = %g is outside [0, 1)", eig_min);
+    JobGuard job(nullptr, job_free);
+    int rc = ld_job(ctx, ld_spec_rows(mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop, 1.0), on_device, job);
+    if (rc) return rc;
+    rc = job_run(job.get(), false);
+    if (rc) return rc;
+    // the matrix stays where the epilogue wrote it (out_ld, both triangles); the kernels run behind the job on the same stream
+    hipStream_t st = ctx->stream;
+    const size_t M = (size_t)n_snp, T = (size_t)n_trait, K = (size_t)k_max;
+    const size_t np = (M + HESS_PW - 1) / HESS_PW * HESS_PW, ldn = (M + HESS_RC - 1) / HESS_RC * HESS_RC;
+    DevBuf d_g, d_v, d_z, d_zr, d_mono, d_lam, d_ord, d_ls, d_proj, d_cnt;
+    if (d_g.alloc(ctx, sizeof(double) * np * ldn) != hipSuccess || d_v.alloc(ctx, sizeof(double) * np * ldn) != hipSuccess ||
+        d_z.alloc(ctx, sizeof(double) * T * M) != hipSuccess || d_zr.alloc(ctx, sizeof(double) * T * ldn) != hipSuccess ||
+        d_mono.alloc(ctx, sizeof(int) * M) != hipSuccess || d_lam.alloc(ctx, sizeof(double) * M) != hipSuccess ||
+        d_ord.alloc(ctx, sizeof(int) * K) != hipSuccess || d_ls.alloc(ctx, sizeof(double) * K) != hipSuccess ||
+        d_proj.alloc(ctx, sizeof(double) * T * K) != hipSuccess || d_cnt.alloc(ctx, 2 * sizeof(unsigned long long)) != hipSuccess)
+        return fail(GAUSS_E_NOMEM, "hipMalloc(%zu bytes of G, V, z and projections) failed",
+                    sizeof(double) * (2 * np * ldn + T * (M + ldn + K) + M + K) + sizeof(int) * (M + K));
+    HIPCHK(hipMemcpyAsync(d_z.p, z, sizeof(double) * T * M, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+    HessArgs a;
+    a.R = job->plans[0].p.out_ld; a.z = d_z.as<double>();
+    a.Gm = d_g.as<double>(); a.V = d_v.as<double>(); a.zr = d_zr.as<double>(); a.mono = d_mono.as<int>();
+    a.lam = d_lam.as<double>(); a.order = d_ord.as<int>(); a.lam_sorted = d_ls.as<double>(); a.proj = d_proj.as<double>();
+    a.n_nonfinite = d_cnt.as<unsigned long long>(); a.n_rot = reinterpret_cast<unsigned int*>(d_cnt.as<unsigned long long>() + 1);
+    a.M = n_snp; a.np = (int)np; a.ldn = (int)ldn; a.T = n_trait; a.kk = 0; a.k_max = k_max;
+    a.null2 = ((double)n_snp * 0x1p-52) * ((double)n_snp * 0x1p-52);
+    launch_hess_prep(a, st);
+    HIPCHK(hipGetLastError());
+    int sweeps = 0;
+    bool converged = false;
+    HIPCHK(hess_solve(a, st, &sweeps, &converged));
+    launch_hess_lambda(a, st);
+    HIPCHK(hipGetLastError());
+    // the M eigenvalues back (a few KB), sorted here: descending, a tie to the smaller solver column
+    std::vector<double> lam(M);
+    unsigned long long n_bad = 0;
+    HIPCHK(hipMemcpyAsync(lam.data(), d_lam.p, sizeof(double) * M, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&n_bad, d_cnt.p, sizeof(n_bad), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int> order(M);
+    for (size_t i = 0; i < M; i++) order[i] = (int)i;
+    bool finite = true;
+    for (size_t i = 0; i < M; i++) finite = finite && std::isfinite(lam[i]);
+    if (finite)       // (with a NaN among them the comparison is no ordering: the eigenvalues stay in solver order, n_pos = 0)
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return lam[x] > lam[y] || (lam[x] == lam[y] && x < y); });
+    for (size_t i = 0; i < M; i++) out_lam[i] = lam[order[i]];
+    int n_pos = 0;
+    const double floor = eig_min * out_lam[0];
+    for (size_t i = 0; i < M; i++) n_pos += (finite && out_lam[i] > 0.0 && out_lam[i] > floor) ? 1 : 0;      // (sorted: a prefix)
+    const int kk = std::min(n_pos, k_max);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t e = 0; e < T * K; e++) out_proj[e] = nan;
+    if (kk > 0) {
+        a.kk = kk;
+        HIPCHK(hipMemcpyAsync(d_ord.p, order.data(), sizeof(int) * kk, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_ls.p, out_lam, sizeof(double) * kk, hipMemcpyHostToDevice, st));
+        launch_hess_proj(a, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy2DAsync(out_proj, sizeof(double) * K, d_proj.p, sizeof(double) * K, sizeof(double) * kk, T, hipMemcpyDeviceToHost, st));
+    }
+    if (out_vectors) {      // the tests' export: row i = the eigenvector of out_lam[i]
+        std::vector<double> v(np * ldn);
+        HIPCHK(hipMemcpyAsync(v.data(), d_v.p, sizeof(double) * np * ldn, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < M; i++) std::memcpy(out_vectors + i * M, v.data() + (size_t)order[i] * ldn, sizeof(double) * M);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (out_order) for (size_t i = 0; i < M; i++) out_order[i] = order[i];
+    if (out_n_pos) *out_n_pos = n_pos;
+    if (out_sweeps) *out_sweeps = sweeps;
+    if (out_n_nonfinite) *out_n_nonfinite = (int64_t)n_bad;
+    if (out_status) *out_status = (converged ? 0 : GAUSS_ST_HESS_NOCONV) | ((n_bad || !finite) ? GAUSS_ST_NONFINITE : 0);
     return job_fetch(job.get());
 }
 

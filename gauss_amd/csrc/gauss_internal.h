@@ -256,6 +256,15 @@ constexpr int LDSPLIT_OFFS = 64;       // offsets j - i of a tile of ldsplit_ban
 constexpr int LDSPLIT_COST_T = 64;     // threads of ldsplit_cost_kernel: one boundary each
 constexpr int LDSPLIT_DP_B = 64;       // boundaries of a workgroup of ldsplit_dp_kernel: one per lane
 constexpr int LDSPLIT_DP_NW = 16;      // waves of that workgroup: wave w takes every LDSPLIT_DP_NW-th block size from the w-th on
+constexpr int HESS_M_MAX = 4096;       // GAUSS_HESS_MAX_M: SNPs of a block; G and V are [M to 32][M to 64] doubles each (k_hess.hip)
+constexpr int HESS_TRAITS_MAX = 64;    // GAUSS_HESS_MAX_TRAITS: traits of one call
+constexpr int HESS_K_MAX = 1024;       // GAUSS_HESS_MAX_K: projections per trait = workgroups of hess_proj_kernel
+constexpr int HESS_B = 16;             // columns of a block of hess_block_round_kernel; a workgroup rotates a pair of blocks
+constexpr int HESS_PW = 2 * HESS_B;    // the pair width: the columns are padded to a multiple of it, the order of the Gram matrix S
+constexpr int HESS_RC = 64;            // rows of a staged chunk of the pair's columns; the rows are padded to a multiple of it
+constexpr int HESS_T = 256;            // threads of every hess_* kernel
+constexpr int HESS_INNER_MAX = 1;      // sweeps of the two-sided Jacobi on S per visit (measured: k_hess.hip)
+constexpr int HESS_MAX_SWEEPS = 30;    // outer sweeps at the most: GAUSS_ST_HESS_NOCONV
 constexpr int SC2_T = 256;             // threads of sumchi2_kernel: one workgroup per gene
 constexpr int SC2_N_MAX = 1024;        // GAUSS_SUMCHI2_MAX_N: SNPs of a gene before pruning; flags and the kept list in LDS (k_sumchi2.hip)
 constexpr int SC2_K_MAX = 128;         // GAUSS_SUMCHI2_MAX_KEPT: order of the eigenvalue solve; the kept block in LDS, 129 doubles a row
@@ -580,6 +589,28 @@ struct LdSplitArgs {
     int M, W, min_size, max_size, max_K;
 };
 void launch_ldsplit(const LdSplitArgs& a, hipStream_t s);      // band, cost, then max_K launches of the DP, all queued on s
+// Eigen-decomposition of a block's LD and the traits' projections on it (k_hess.hip) on a full M x M LD matrix in device memory (an
+// LD-only job's out_ld).  np = M rounded up to HESS_PW columns, ldn = M rounded up to HESS_RC rows; Gm and V are column-major
+// [np][ldn]; zr [T][ldn] the repaired z; every pointer is a device pointer
+struct HessArgs {
+    const double* R;        // [M][M], both triangles
+    const double* z;        // [T][M] as the caller gave it
+    double *Gm, *V, *zr;
+    int* mono;              // [M] 1: a monomorphic SNP (every off-diagonal entry NaN)
+    double* lam;            // [M] v_j . g_j by solver column
+    const int* order;       // [kk] the solver column of the i-th largest eigenvalue
+    const double* lam_sorted;      // [kk]
+    double* proj;           // [T][k_max]
+    unsigned int* n_rot;    // one counter: block pairs rotated since it was last zeroed
+    unsigned long long* n_nonfinite;      // one counter, zero before the launches
+    double null2;           // (M 2^-52)^2: a column of G with a squared norm at or below it is numerically null, never rotated
+    int M, np, ldn, T, kk, k_max;
+};
+void launch_hess_prep(const HessArgs& a, hipStream_t s);       // mono, Gm = R', V = I, zr
+// the block rounds, a sweep at a time until one rotates nothing (the counter is read once per sweep: it waits for s); returns a HIP error
+hipError_t hess_solve(const HessArgs& a, hipStream_t s, int* sweeps, bool* converged);
+void launch_hess_lambda(const HessArgs& a, hipStream_t s);
+void launch_hess_proj(const HessArgs& a, hipStream_t s);
 // Gene-based sum-of-chi2 (k_sumchi2.hip) on the blocks a gene job left in out_ld: one workgroup per gene.  The arguments travel by
 // value; every pointer is a device pointer and none is null
 struct Sumchi2Args {

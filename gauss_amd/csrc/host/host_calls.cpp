@@ -1194,6 +1194,49 @@ int gauss_host_ldsplit(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp
     return 0;
 }
 
+int gauss_host_hess(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                    int n_pop_wgt, const char* const* input_files, int n_files, const char* reference_index_file,
+                    const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff, int k_max, double eig_min,
+                    gauss_table** out)
+{
+    if (!ctx || !out || !input_files) return herr("bad arguments");
+    if (n_files < 1 || n_files > GAUSS_HESS_MAX_TRAITS)
+        return herr("hess: %d study files; a call takes 1 .. %d (one trait each)", n_files, GAUSS_HESS_MAX_TRAITS);
+    const int K = k_max == 0 ? 256 : k_max;
+    const double em = std::isnan(eig_min) ? 1e-6 : eig_min;
+    if (K < 1 || K > GAUSS_HESS_MAX_K) return herr("hess: k_max = %d; a call projects on 1 .. %d eigenvectors", k_max, GAUSS_HESS_MAX_K);
+    if (!(em >= 0.0 && em < 1.0)) return herr("hess: eig_min = %g is outside [0, 1)", em);
+    for (int k = 0; k < n_files; k++) if (files_ok({input_files[k]})) return -1;
+    LdRows s;
+    if (computeld_rows(ctx, chr, start_bp, end_bp, pop_names, pop_wgts, n_pop_wgt, input_files[0], reference_index_file, reference_data_file,
+                       reference_pop_desc_file, af1_cutoff, s)) return -1;
+    const int M = s.M;
+    if (M > GAUSS_HESS_MAX_M)
+        return herr("hess: the block holds %d SNPs of the study; a call takes at most %d (ask for a shorter region)", M, GAUSS_HESS_MAX_M);
+    // the further files at the SNPs of the first, as dist_traits reads them: every SNP present, swapped alleles flip the sign
+    const gauss_table& t = *s.t;                                         // add_ident_columns: rsid chr bp a1 a2
+    std::vector<double> z((size_t)n_files * M);
+    std::copy(s.z.begin(), s.z.end(), z.begin());
+    for (int k = 1; k < n_files; k++) {
+        std::string err;
+        std::shared_ptr<const GwasCache> gw = load_gwas_cached(input_files[k], err);
+        if (!gw) return herr("%s", err.c_str());
+        if (traits_match(*gw, input_files[k], (size_t)M, [&](size_t i) {
+                return SnpIdent{t.cols[0].s[i].c_str(), t.cols[1].i[i], (long long)t.cols[2].i[i], t.cols[3].s[i].c_str(), t.cols[4].s[i].c_str()};
+            }, z.data() + (size_t)k * M)) return -1;
+    }
+    std::vector<double> lam((size_t)M), proj((size_t)n_files * K);
+    int32_t n_pos = 0, sweeps = 0, status = 0;
+    int64_t n_bad = 0;
+    if (gauss_ld_hess_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
+                           s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, s.on_device,
+                           z.data(), n_files, K, em, lam.data(), proj.data(), &n_pos, &sweeps, &n_bad, &status, nullptr, nullptr) != 0)
+        return herr("%s", gauss_last_error());
+    hess_output(*s.t, M, n_files, K, z.data(), lam.data(), proj.data(), n_pos, sweeps, n_bad, status);
+    *out = s.t.release();
+    return 0;
+}
+
 // ---- jepeg() / jepegmix() over several ranks ("genes: contiguous gene ranges") ------------------------------
 // Genes are independent (jepeg.cpp:114-131: one Gene object per gene, nothing shared but the read-only SNP map; grouping at
 // gauss.cpp:1383-1439).  Every rank runs the same host data layer on the same files, derives the same plan -- contiguous gene

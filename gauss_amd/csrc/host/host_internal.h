@@ -785,6 +785,11 @@ int ldsplit_params(double thr_r2, int min_size, int max_size, int max_K, double 
 // [n x the largest such K]: the table row of every block's last SNP, -1 beyond the row's K; `max_r2_at` [M + 1 x 1]: Mx; `n_nonfinite`
 // [1 x 1].  cost [max_K], prev [max_K][M + 1], mx [M + 1] as gauss_ld_split_rows returned them; the splits are read backwards from prev
 void ldsplit_output(gauss_table& t, int M, int max_K, const double* cost, const int32_t* prev, const double* mx, int64_t n_nonfinite);
+// hess(): its table (host_tables.cpp): `t` holds computeLD's snplist columns and keeps them; four named matrices are added -- `z`
+// [M x T], the traits' Z-scores at the SNPs (file k in column k, signs as the first file's alleles); `lam` [M x 1]; `proj` [T x k_max];
+// `solve` [1 x 4]: n_pos, sweeps, n_nonfinite, status.  z [T][M], lam [M], proj [T][k_max] as gauss_ld_hess_rows took and returned them
+void hess_output(gauss_table& t, int M, int T, int k_max, const double* z, const double* lam, const double* proj, int n_pos, int sweeps,
+                 int64_t n_nonfinite, int status);
 // sumchi2(): P(sum lambda_i chi2_1 > q) (host_tables.cpp; the method: gauss_host_sumchi2_pval in include/gauss_host.h).  lambda_i <= 0
 // or NaN are left out; n_pos (may be null): how many stay
 double sumchi2_pval(const double* lam, int n, double q, int* n_pos);

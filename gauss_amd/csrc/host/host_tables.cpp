@@ -862,6 +862,21 @@ void ldsplit_output(gauss_table& t, int M, int max_K, const double* cost, const 
     t.put_named("n_nonfinite", 1, 1, std::vector<double>(1, (double)n_nonfinite));
 }
 
+void hess_output(gauss_table& t, int M, int T, int k_max, const double* z, const double* lam, const double* proj, int n_pos, int sweeps,
+                 int64_t n_nonfinite, int status)
+{
+    std::vector<double> zm((size_t)M * T), pm((size_t)T * k_max);
+    for (int k = 0; k < T; k++)
+        for (int i = 0; i < M; i++) zm[(size_t)k * M + i] = z[(size_t)k * M + i];            // [M x T] column-major = [T][M] row-major
+    for (int k = 0; k < T; k++)
+        for (int i = 0; i < k_max; i++) pm[(size_t)i * T + k] = proj[(size_t)k * k_max + i];
+    t.put_named("z", M, T, std::move(zm));
+    t.put_named("lam", M, 1, std::vector<double>(lam, lam + M));
+    t.put_named("proj", T, k_max, std::move(pm));
+    t.put_named("solve", 1, 4, std::vector<double>{(double)n_pos, (double)sweeps, (double)n_nonfinite, (double)status});
+    if (status & GAUSS_ST_HESS_NOCONV) t.messages.push_back("hess: the eigen-solver ran its 30 sweeps out; the values are those of the last sweep");
+}
+
 gauss_table* qcat_output(gauss_prepared& p)     // qcat.cpp:94-131 / qcatmix.cpp:102-139
 {
     const bool mix = p.kind == GAUSS_KIND_QCATMIX;

@@ -331,6 +331,51 @@ def ld_split_rows(store, rows, pop_off, bp, pop_wgt=None, mode=MODE_WEIGHTED, ra
     return _split(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, radius, thr_r2, min_size, max_size, max_K, max_r2)
 
 
+def _hess(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, z_traits, k_max, eig_min, want_vectors):
+    z = np.ascontiguousarray(z_traits, dtype=np.float64)
+    if z.ndim == 1:
+        z = z.reshape(1, -1)
+    if z.ndim != 2 or z.shape[1] != S:
+        raise ValueError(f"z_traits has shape {z.shape}: expected (n_trait, {S})")
+    T, K = z.shape[0], int(k_max)
+    lam, proj = np.full(S, np.nan), np.full((T, max(K, 0)), np.nan)
+    out = np.full(3, -1, dtype=np.int32)                   # n_pos, sweeps, status
+    n = np.full(1, -1, dtype=np.int64)
+    vec = np.full((S, S), np.nan) if want_vectors else None
+    order = np.full(S, -1, dtype=np.int32) if want_vectors else None
+    o = out.ctypes.data
+    check(ctx.lib.gauss_ld_hess_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip), _lib.ptr(so, _ip),
+                                     _lib.ptr(w, _dp), len(po) - 1, on_dev, z.ctypes.data_as(_dp), T, K, float(eig_min),
+                                     lam.ctypes.data_as(_dp), proj.ctypes.data_as(_dp), C.cast(o, _ip), C.cast(o + 4, _ip),
+                                     n.ctypes.data_as(C.POINTER(C.c_int64)), C.cast(o + 8, _ip), _lib.ptr(vec, _dp), _lib.ptr(order, _ip)))
+    res = dict(lam=lam, proj=proj, n_pos=int(out[0]), sweeps=int(out[1]), status=int(out[2]), n_nonfinite=int(n[0]))
+    if want_vectors:
+        res.update(vectors=vec, order=order)
+    return res
+
+
+def ld_hess(geno, pop_off, z_traits, pop_wgt=None, mode=MODE_WEIGHTED, k_max=256, eig_min=1e-6, want_vectors=False, ctx=None):
+    """gauss_ld_hess_rows on the rows of a byte matrix: every eigenvalue of the LD that ld_matrix would return (repaired as the header
+    states; the matrix stays on the device) and the projections of the traits z_traits [T, S] on its leading eigenvectors.  Returns
+    dict(lam [S] descending, proj [T, k_max] = (v_i . z_t) / sqrt(lam_i) for i < min(k_max, n_pos) and NaN beyond, n_pos, sweeps,
+    status, n_nonfinite); api.hess_estimates turns lam and proj into h2, covariances and correlations on the host.
+    want_vectors=True (for the tests) adds vectors [S, S] (row i = v_i) and order [S] (the solver's column of lam_i)."""
+    ctx = ctx or default_context()
+    g = _lib.as_u8(geno)
+    po, w = _pops(pop_off, pop_wgt)
+    return _hess(ctx, g.ctypes.data, g.strides[0], _lib.GENO_U8, 0, None, g.shape[0], po, None, w, mode, z_traits, k_max, eig_min, want_vectors)
+
+
+def ld_hess_rows(store, rows, pop_off, z_traits, pop_wgt=None, mode=MODE_WEIGHTED, k_max=256, eig_min=1e-6, want_vectors=False,
+                 fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
+    """ld_hess on the store rows `rows` (a numpy matrix of host rows, a RowStore or a raw device pointer, as ld_matrix_rows)."""
+    ctx = ctx or default_context()
+    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
+    po, w = _pops(pop_off, pop_wgt)
+    S = len(r) if r is not None else store.shape[0]
+    return _hess(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, z_traits, k_max, eig_min, want_vectors)
+
+
 def ld_resampled(store, rows, pop_off, draw_pop, draw_sample, n_cols, diag=1.0, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
     """gauss_ld_resampled_rows: pooled LD (CalCor, n = n_cols) of the store rows `rows` (None: rows 0 .. S-1 of a numpy matrix)
     over the drawn samples -- draw k is sample draw_sample[k] of population draw_pop[k] -- and n_cols - len(draws) zero columns

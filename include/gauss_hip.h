@@ -61,6 +61,7 @@ extern "C" {
 #define GAUSS_ST_PRS_NOCONV  64 /* polygenic score weights: a (s, lam) ran prs_max_sweeps sweeps without delta < prs_tol r_max (last sweep's values) */
 #define GAUSS_ST_SUMCHI2_TOOLARGE 128 /* gauss_gene_sumchi2: more than GAUSS_SUMCHI2_MAX_KEPT SNPs of the gene survive the pruning (eigenvalues NaN) */
 #define GAUSS_ST_SUMCHI2_EMPTY    256 /* gauss_gene_sumchi2: no SNP of the gene is kept (an empty gene, or every row NaN) */
+#define GAUSS_ST_HESS_NOCONV      512 /* gauss_ld_hess_rows: 30 sweeps of the block Jacobi ran and the last still rotated (last sweep's values) */
 
 typedef struct gauss_ctx gauss_ctx;
 typedef struct gauss_job gauss_job;
@@ -741,6 +742,41 @@ int gauss_ld_split_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t 
                         int n_snp, const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop,
                         int on_device, const int32_t* bp, int64_t radius, double thr_r2, int min_size, int max_size, int max_K,
                         double max_r2, double* out_cost, int32_t* out_prev, double* out_max_r2, int64_t* out_n_nonfinite);
+
+/* Local heritability and genetic covariance of an LD block (the statistic of HESS, rho-HESS and LAVA): every eigenvalue of the
+ * block's LD and the traits' projections on its leading eigenvectors.  The LD matrix R (M = n_snp) is formed as gauss_ld_rows forms
+ * it (same rows, same bits, diag 1) and never leaves the device.  Rows as in gauss_ld_rows.  z [n_trait][n_snp]: one row per trait.
+ *     repair:      a SNP whose every off-diagonal entry of R is NaN (M > 1) is monomorphic: its row, its column AND its diagonal
+ *                  are set to 0 and its z is ignored (taken as 0).  Any other non-finite entry counts as 0 and, once per pair
+ *                  i <= j, in n_nonfinite.  A non-finite z value is taken as 0 for that trait.  R' is the repaired matrix.
+ *     eigenpairs:  R' = sum_i lam_i v_i v_i^T by block one-sided Jacobi (k_hess.hip), at most 30 sweeps; a sweep that rotates nothing
+ *                  ends the solve.  A column of R' V whose norm is at or below M 2^-52 (the largest eigenvalue is at most M) is
+ *                  numerically null and is not rotated: in a rank-deficient block (more SNPs than samples) the eigenvalues of the
+ *                  null space come back within M 2^-52 of 0, with orthonormal vectors.
+ *                  out_lam [n_snp]: all M eigenvalues, descending; a tie goes to the smaller column of the solver.
+ *     n_pos:       the number of i with lam_i > eig_min * lam_0 and lam_i > 0 (a prefix of the sorted order); 0 <= eig_min < 1.
+ *     projections: out_proj [n_trait][k_max]: proj[t][i] = (v_i^T z_t) / sqrt(lam_i) for i < min(k_max, n_pos), NaN beyond.  The
+ *                  sign of v_i is arbitrary; every quantity built from proj downstream (H_t(k) = sum_{i<k} proj[t][i]^2, C_ab(k) =
+ *                  sum_{i<k} proj[a][i] proj[b][i]) is a product of two projections on the same i and so does not depend on it.
+ *                  A trait's projections depend on its own z only.
+ * out_n_pos, out_sweeps (the last, rotation-free sweep counts), out_n_nonfinite, out_status [1] each: status = 0, or
+ * GAUSS_ST_HESS_NOCONV (30 sweeps ran and the last still rotated: the values are those of the last sweep), GAUSS_ST_NONFINITE
+ * (n_nonfinite > 0, or an eigenvalue is not finite: then n_pos = 0).  out_vectors [n_snp][n_snp] (row i = v_i) and out_order
+ * [n_snp] (the solver's column of lam_i) are for the tests.  Every output but out_lam and out_proj may be NULL.
+ * No floating-point atomics and every sum in a fixed order: the outputs do not depend on the source format of the rows, on a host
+ * or device store, on the launch form of the LD build or on the run.
+ * Refused (GAUSS_E_INVALID, before anything is allocated or launched): NULL z / out_lam / out_proj; n_snp outside 1 ..
+ * GAUSS_HESS_MAX_M; n_trait outside 1 .. GAUSS_HESS_MAX_TRAITS; k_max outside 1 .. GAUSS_HESS_MAX_K; eig_min outside [0, 1) or NaN;
+ * and whatever gauss_ld_rows refuses.  One block per call; beside the matrix (8 n_snp^2 bytes) the call takes 16 n_snp^2 bytes of
+ * device memory for G = R' V and V, n_snp rounded up to 64: 24 n_snp^2 in all, 0.4 GB at the limit.  Blocking. */
+#define GAUSS_HESS_MAX_M      4096
+#define GAUSS_HESS_MAX_TRAITS 64
+#define GAUSS_HESS_MAX_K      1024
+int gauss_ld_hess_rows(gauss_ctx* ctx, int mode, const uint8_t* store, int64_t ld, int geno_format, const int32_t* rows,
+                       int n_snp, const int32_t* pop_off, const int32_t* pop_src_off, const double* pop_wgt, int n_pop,
+                       int on_device, const double* z, int n_trait, int k_max, double eig_min, double* out_lam, double* out_proj,
+                       int32_t* out_n_pos, int32_t* out_sweeps, int64_t* out_n_nonfinite, int32_t* out_status,
+                       double* out_vectors, int32_t* out_order);
 
 /* Gene-based sum-of-chi2 test (the statistic of fastBAT, VEGAS and MAGMA's SNP-wise mean model) of n_gene genes on their LD
  * blocks, which are formed as gauss_gene_ld_batch[_rows] forms them with diag = 1 (same rows, same bits) and never leave the

@@ -611,6 +611,24 @@ int gauss_host_ldsplit(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp
                        const char* reference_pop_desc_file, double af1_cutoff, double thr_r2, int min_size, int max_size, int max_K,
                        double max_r2, double kb, gauss_table** out);
 
+/* hess(): the eigenvalues of the ancestry-weighted LD of a block and the projections of one or more traits on its leading
+ * eigenvectors -- what local heritability (HESS), local genetic covariance (rho-HESS) and LAVA's local correlation are computed
+ * from -- on the LD of computeLD, which never leaves the GPU (gauss_ld_hess_rows, include/gauss_hip.h: the rule, the repair of
+ * non-finite entries, n_pos and the projections).  The arguments are gauss_host_computeLD's with n_files study files in place of one:
+ * the SNPs are exactly computeLD's selection for the first file and the same arguments (same snplist, same "Not enough number of
+ * SNPs loaded" error); every further file is read as dist_traits reads its further files -- it must hold every selected SNP (refused
+ * with a message naming the file and the first SNP it lacks), swapped alleles flip the sign of z.  k_max: projections per trait (0:
+ * 256); eig_min: NaN takes 1e-6.  Refused: n_files outside 1 .. GAUSS_HESS_MAX_TRAITS (64), k_max outside 1 .. GAUSS_HESS_MAX_K
+ * (1 024), eig_min outside [0, 1), a block of more than GAUSS_HESS_MAX_M (4 096) SNPs.  Result: computeLD's snplist (one row per SNP:
+ * rsid chr bp a1 a2 af1mix) and four named matrices: "z" [M x n_files]; "lam" [M x 1], descending; "proj" [n_files x k_max], NaN
+ * beyond min(k_max, n_pos); "solve" [1 x 4]: n_pos, sweeps, n_nonfinite, status (GAUSS_ST_HESS_NOCONV / GAUSS_ST_NONFINITE).  The
+ * estimators -- h2, its standard error, covariance and correlation at the caller's k -- are a few sums over proj: api.hess_estimates
+ * states them; they are not computed here.  One block per call; cut a region with gauss_host_ldsplit first. */
+int gauss_host_hess(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
+                    int n_pop_wgt, const char* const* input_files, int n_files, const char* reference_index_file,
+                    const char* reference_data_file, const char* reference_pop_desc_file, double af1_cutoff, int k_max, double eig_min,
+                    gauss_table** out);
+
 #define GAUSS_ZMIX_POPULATION      0
 #define GAUSS_ZMIX_SUPERPOPULATION 1
 int gauss_host_zmix(gauss_ctx* ctx, const char* input_file, const char* reference_index_file, const char* reference_data_file,
