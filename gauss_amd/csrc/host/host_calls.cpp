@@ -1133,9 +1133,8 @@ int gauss_host_computeLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_
     std::unique_ptr<gauss_table> t = std::move(s.t);
     t->matrix.assign((size_t)M * M, 0.0);
     t->matrix_n = M;
-    if (gauss_ld_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
-                      s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, 1.0, s.on_device,
-                      t->matrix.data()) != 0) return herr("%s", gauss_last_error());
+    if (gauss_ld_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.row_ptr(), M, s.pop_off.data(), s.src_off_ptr(), s.pop_wgt.data(),
+                      s.n_pop(), 1.0, s.on_device, t->matrix.data()) != 0) return herr("%s", gauss_last_error());
     *out = t.release();
     return 0;
 }
@@ -1158,10 +1157,9 @@ int gauss_host_clump(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, 
     for (int i = 0; i < M; i++) key[(size_t)i] = s.z[(size_t)i] * s.z[(size_t)i];
     std::vector<int32_t> owner((size_t)M), rank((size_t)M);
     int32_t n = 0;
-    if (gauss_ld_clump_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
-                            s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, s.on_device,
-                            bp.data(), key.data(), 1, k.radius, k.r2_min, k.key_index, k.key_member, owner.data(), rank.data(), r2_out.data(),
-                            &n) != 0) return herr("%s", gauss_last_error());
+    if (gauss_ld_clump_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.row_ptr(), M, s.pop_off.data(), s.src_off_ptr(),
+                            s.pop_wgt.data(), s.n_pop(), s.on_device, bp.data(), key.data(), 1, k.radius, k.r2_min, k.key_index, k.key_member,
+                            owner.data(), rank.data(), r2_out.data(), &n) != 0) return herr("%s", gauss_last_error());
     clump_output(*s.t, s.z, owner.data(), rank.data(), r2_out.data(), n);
     *out = s.t.release();
     return 0;
@@ -1185,10 +1183,9 @@ int gauss_host_ldsplit(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp
     std::vector<double> cost((size_t)k.max_K), mx((size_t)M + 1);
     std::vector<int32_t> prev((size_t)k.max_K * ((size_t)M + 1));
     int64_t n_bad = 0;
-    if (gauss_ld_split_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
-                            s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, s.on_device,
-                            bp.data(), k.radius, k.thr_r2, k.min_size, k.max_size, k.max_K, k.max_r2, cost.data(), prev.data(), mx.data(),
-                            &n_bad) != 0) return herr("%s", gauss_last_error());
+    if (gauss_ld_split_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.row_ptr(), M, s.pop_off.data(), s.src_off_ptr(),
+                            s.pop_wgt.data(), s.n_pop(), s.on_device, bp.data(), k.radius, k.thr_r2, k.min_size, k.max_size, k.max_K, k.max_r2,
+                            cost.data(), prev.data(), mx.data(), &n_bad) != 0) return herr("%s", gauss_last_error());
     ldsplit_output(*s.t, M, k.max_K, cost.data(), prev.data(), mx.data(), n_bad);
     *out = s.t.release();
     return 0;
@@ -1228,10 +1225,9 @@ int gauss_host_hess(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, c
     std::vector<double> lam((size_t)M), proj((size_t)n_files * K);
     int32_t n_pos = 0, sweeps = 0, status = 0;
     int64_t n_bad = 0;
-    if (gauss_ld_hess_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
-                           s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), s.pop_wgt.data(), (int)s.pop_off.size() - 1, s.on_device,
-                           z.data(), n_files, K, em, lam.data(), proj.data(), &n_pos, &sweeps, &n_bad, &status, nullptr, nullptr) != 0)
-        return herr("%s", gauss_last_error());
+    if (gauss_ld_hess_rows(ctx, GAUSS_MODE_WEIGHTED, s.store, s.ld, s.geno_fmt, s.row_ptr(), M, s.pop_off.data(), s.src_off_ptr(),
+                           s.pop_wgt.data(), s.n_pop(), s.on_device, z.data(), n_files, K, em, lam.data(), proj.data(), &n_pos, &sweeps, &n_bad,
+                           &status, nullptr, nullptr) != 0) return herr("%s", gauss_last_error());
     hess_output(*s.t, M, n_files, K, z.data(), lam.data(), proj.data(), n_pos, sweeps, n_bad, status);
     *out = s.t.release();
     return 0;

@@ -761,6 +761,10 @@ struct LdRows {
     Args a;                             // population table, flags and weight map of the call
     std::shared_ptr<PackedPanel> pk;    // what keeps `store` alive
     std::unique_ptr<gauss_prepared> prep;
+    // the source as a C entry point takes it: NULL for "rows 0 .. M - 1" and for "no source offsets"
+    const int32_t* row_ptr() const { return rows.empty() ? nullptr : rows.data(); }
+    const int32_t* src_off_ptr() const { return pop_src_off.empty() ? nullptr : pop_src_off.data(); }
+    int n_pop() const { return (int)pop_off.size() - 1; }
 };
 int computeld_rows(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end_bp, const char* const* pop_names, const double* pop_wgts,
                    int n_pop_wgt, const char* input_file, const char* reference_index_file, const char* reference_data_file,

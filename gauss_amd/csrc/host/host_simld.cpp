@@ -123,7 +123,7 @@ int gauss_host_simulateLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end
     SimDraws d;
     if (simulate_draws(s.a, sim_size, seed, d)) return -1;
     // the draws index the selected populations, the same list and order the rows' pop_off describes
-    const int P = (int)s.pop_off.size() - 1;
+    const int P = s.n_pop();
     if ((int)d.pops.size() != P) return herr("simulateLD: %d weighted populations but %d selected for the rows", (int)d.pops.size(), P);
     for (int q = 0; q < P; q++)
         if (s.pop_off[(size_t)q + 1] - s.pop_off[(size_t)q] != s.a.ref_pop_size_vec[(size_t)d.pops[(size_t)q]])
@@ -133,9 +133,8 @@ int gauss_host_simulateLD(gauss_ctx* ctx, int chr, int64_t start_bp, int64_t end
     std::unique_ptr<gauss_table> t = std::move(s.t);
     t->matrix.assign((size_t)M * M, 0.0);
     t->matrix_n = M;
-    if (gauss_ld_resampled_rows(ctx, s.store, s.ld, s.geno_fmt, s.rows.empty() ? nullptr : s.rows.data(), M, s.pop_off.data(),
-                                s.pop_src_off.empty() ? nullptr : s.pop_src_off.data(), P, d.pop.data(), d.sample.data(), (int64_t)d.pop.size(),
-                                sim_size, 1.0, s.on_device, t->matrix.data()) != 0)
+    if (gauss_ld_resampled_rows(ctx, s.store, s.ld, s.geno_fmt, s.row_ptr(), M, s.pop_off.data(), s.src_off_ptr(), P, d.pop.data(), d.sample.data(),
+                                (int64_t)d.pop.size(), sim_size, 1.0, s.on_device, t->matrix.data()) != 0)
         return herr("%s", gauss_last_error());
     put_draws(*t, d);
     *out = t.release();

@@ -106,6 +106,43 @@ def _pops(pop_off, pop_wgt):
     return po, w
 
 
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+
+class _Source:
+    """The SNP rows of an LD-only call and the populations of their samples: the converted arrays (kept alive here), the number of
+    rows S, and the head of the arguments of a C entry point.  on_dev stands apart: its place differs between the entry points."""
+
+    def __init__(self, store, rows, pop_off, pop_wgt, mode, fmt, pop_src_off):
+        """The rows `rows` of a row store: a numpy matrix (host rows; rows None: all of them), a RowStore (resident rows) or a raw
+        (device pointer, row stride) pair."""
+        self.store, self.rows, self.so = store, _i32(rows), _i32(pop_src_off)
+        if isinstance(store, RowStore):
+            self.ptr, self.ld, self.on_dev = store.ptr, store.ld, 1
+        elif isinstance(store, np.ndarray):
+            self.ptr, self.ld, self.on_dev = store.ctypes.data, store.strides[0], 0
+        else:
+            (self.ptr, self.ld), self.on_dev = store, 1
+        self.S = len(self.rows) if self.rows is not None else store.shape[0]
+        self.po, self.w = _pops(pop_off, pop_wgt)
+        self.mode, self.fmt = int(mode), int(fmt)
+
+    @classmethod
+    def matrix(cls, geno, pop_off, pop_wgt, mode):
+        """Every row of a byte matrix."""
+        return cls(_lib.as_u8(geno), None, pop_off, pop_wgt, mode, _lib.GENO_U8, None)
+
+    def geno_head(self):
+        """mode, geno, n_snp, ld, pop_off, pop_wgt, n_pop: the head of an entry point on a byte matrix"""
+        return self.mode, self.ptr, self.S, self.ld, self.po.ctypes.data_as(_ip), _lib.ptr(self.w, _dp), len(self.po) - 1
+
+    def rows_head(self):
+        """mode, store, ld, geno_format, rows, n_snp, pop_off, pop_src_off, pop_wgt, n_pop: the head of a `_rows` entry point"""
+        return (self.mode, self.ptr, self.ld, self.fmt, _lib.ptr(self.rows, _ip), self.S, self.po.ctypes.data_as(_ip), _lib.ptr(self.so, _ip),
+                _lib.ptr(self.w, _dp), len(self.po) - 1)
+
+
 def gram_counts(geno, ctx=None):
     """Exact integer sum_n x_i[n] x_j[n] (util.cpp:62,114 `sumxy`), int64 (S, S)."""
     ctx = ctx or default_context()
@@ -124,13 +161,9 @@ def ld_matrix(geno, pop_off, pop_wgt=None, mode=MODE_WEIGHTED, diag=1.0, ctx=Non
     mode=MODE_POOLED, diag=1+lambda -> CorG of jepeg (gene.cpp:305-315)
     """
     ctx = ctx or default_context()
-    g = _lib.as_u8(geno)
-    S = g.shape[0]
-    po, w = _pops(pop_off, pop_wgt)
-    out = np.zeros((S, S), dtype=np.float64)
-    check(ctx.lib.gauss_ld(ctx.handle, int(mode), g.ctypes.data, S, g.strides[0],
-                           po.ctypes.data_as(_ip), _lib.ptr(w, _dp), len(po) - 1, float(diag),
-                           out.ctypes.data_as(_dp)))
+    src = _Source.matrix(geno, pop_off, pop_wgt, mode)
+    out = np.zeros((src.S, src.S), dtype=np.float64)
+    check(ctx.lib.gauss_ld(ctx.handle, *src.geno_head(), float(diag), out.ctypes.data_as(_dp)))
     return out
 
 
@@ -187,46 +220,32 @@ def pop_weights(x, interval_off, min_abs_eig=1e-5, ctx=None):
 def gene_ld_batch(geno, pop_off, gene_off, pop_wgt=None, mode=MODE_POOLED, diag=1.1, ctx=None):
     """LD blocks of all genes in one launch; returns a list of (n_g, n_g) arrays."""
     ctx = ctx or default_context()
-    g = _lib.as_u8(geno)
-    S = g.shape[0]
-    po, w = _pops(pop_off, pop_wgt)
+    src = _Source.matrix(geno, pop_off, pop_wgt, mode)
+    go, out, blocks = _gene_blocks(gene_off)
+    check(ctx.lib.gauss_gene_ld_batch(ctx.handle, *src.geno_head(), go.ctypes.data_as(_ip), len(go) - 1, float(diag), out.ctypes.data_as(_dp)))
+    return blocks
+
+
+def _gene_blocks(gene_off):
+    """(the int32 gene offsets, the flat output of a gene_ld_batch call, its (n_g, n_g) block of every gene)"""
     go = np.ascontiguousarray(gene_off, dtype=np.int32)
     sizes = np.diff(go).astype(np.int64)
     out = np.zeros(int((sizes * sizes).sum()), dtype=np.float64)
-    check(ctx.lib.gauss_gene_ld_batch(ctx.handle, int(mode), g.ctypes.data, S, g.strides[0],
-                                      po.ctypes.data_as(_ip), _lib.ptr(w, _dp), len(po) - 1,
-                                      go.ctypes.data_as(_ip), len(go) - 1, float(diag),
-                                      out.ctypes.data_as(_dp)))
     blocks, o = [], 0
     for n in sizes:
         blocks.append(out[o:o + n * n].reshape(n, n))
         o += n * n
-    return blocks
-
-
-def _row_args(store, rows, pop_src_off):
-    """(pointer, int32 row array or None, int32 offsets or None) of a row-store call; `store` is a numpy matrix
-    (host rows), a RowStore (resident rows) or a raw device pointer."""
-    r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
-    so = None if pop_src_off is None else np.ascontiguousarray(pop_src_off, dtype=np.int32)
-    if isinstance(store, RowStore):
-        return store.ptr, store.ld, 1, r, so
-    if isinstance(store, np.ndarray):
-        return store.ctypes.data, store.strides[0], 0, r, so
-    ptr, ld = store
-    return ptr, ld, 1, r, so
+    return go, out, blocks
 
 
 def ld_matrix_rows(store, rows, pop_off, pop_wgt=None, mode=MODE_WEIGHTED, diag=1.0, fmt=_lib.GENO_2BIT, pop_src_off=None,
                    ctx=None):
     """gauss_ld_rows: the LD matrix of the store rows `rows` (computeLD on a packed / resident panel)."""
     ctx = ctx or default_context()
-    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
-    po, w = _pops(pop_off, pop_wgt)
-    S = len(r)
-    out = np.zeros((S, S))
-    check(ctx.lib.gauss_ld_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip),
-                                _lib.ptr(so, _ip), _lib.ptr(w, _dp), len(po) - 1, float(diag), on_dev, out.ctypes.data_as(_dp)))
+    len(rows)                                              # (this call names its rows: None raises here, as it always did)
+    src = _Source(store, rows, pop_off, pop_wgt, mode, fmt, pop_src_off)
+    out = np.zeros((src.S, src.S))
+    check(ctx.lib.gauss_ld_rows(ctx.handle, *src.rows_head(), float(diag), src.on_dev, out.ctypes.data_as(_dp)))
     return out
 
 
@@ -234,7 +253,8 @@ def ld_matrix_rows(store, rows, pop_off, pop_wgt=None, mode=MODE_WEIGHTED, diag=
 CLUMP_KEY_INDEX, CLUMP_KEY_MEMBER = 15.136705226623402, 6.634896601021217
 
 
-def _clump(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, key, radius, r2_min, key_index, key_member):
+def _clump(ctx, src, bp, key, radius, r2_min, key_index, key_member):
+    S = src.S
     b = np.ascontiguousarray(bp, dtype=np.int32).reshape(-1)
     k = np.ascontiguousarray(key, dtype=np.float64)
     one = k.ndim == 1
@@ -244,8 +264,7 @@ def _clump(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, key, radius, r2
     T = k.shape[0]
     owner, rank = np.full((T, S), -2, dtype=np.int32), np.full((T, S), -2, dtype=np.int32)
     r2, n = np.zeros((T, S)), np.full(T, -2, dtype=np.int32)
-    check(ctx.lib.gauss_ld_clump_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip), _lib.ptr(so, _ip),
-                                      _lib.ptr(w, _dp), len(po) - 1, on_dev, b.ctypes.data_as(_ip), k.ctypes.data_as(_dp), T, int(radius),
+    check(ctx.lib.gauss_ld_clump_rows(ctx.handle, *src.rows_head(), src.on_dev, b.ctypes.data_as(_ip), k.ctypes.data_as(_dp), T, int(radius),
                                       float(r2_min), float(key_index), float(key_member), owner.ctypes.data_as(_ip),
                                       rank.ctypes.data_as(_ip), r2.ctypes.data_as(_dp), n.ctypes.data_as(_ip)))
     if one:
@@ -260,21 +279,14 @@ def ld_clump(geno, pop_off, bp, key, pop_wgt=None, mode=MODE_WEIGHTED, radius=25
     frequency with key_index = key_member = 0: LD pruning).  Returns dict(owner, rank, r2, n_clumps): owner[i] the row that leads
     SNP i's clump (-1: none), rank[i] = k where row i leads the k-th clump (else 0), r2[i] the squared LD to the lead (1 for a lead,
     NaN for none).  A 1-D key gives 1-D outputs."""
-    ctx = ctx or default_context()
-    g = _lib.as_u8(geno)
-    po, w = _pops(pop_off, pop_wgt)
-    return _clump(ctx, g.ctypes.data, g.strides[0], _lib.GENO_U8, 0, None, g.shape[0], po, None, w, mode, bp, key, radius, r2_min,
-                  key_index, key_member)
+    return _clump(ctx or default_context(), _Source.matrix(geno, pop_off, pop_wgt, mode), bp, key, radius, r2_min, key_index, key_member)
 
 
 def ld_clump_rows(store, rows, pop_off, bp, key, pop_wgt=None, mode=MODE_WEIGHTED, radius=250_000, r2_min=0.5,
                   key_index=CLUMP_KEY_INDEX, key_member=CLUMP_KEY_MEMBER, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
     """ld_clump on the store rows `rows` (a numpy matrix of host rows, a RowStore or a raw device pointer, as ld_matrix_rows)."""
-    ctx = ctx or default_context()
-    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
-    po, w = _pops(pop_off, pop_wgt)
-    S = len(r) if r is not None else store.shape[0]
-    return _clump(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, key, radius, r2_min, key_index, key_member)
+    return _clump(ctx or default_context(), _Source(store, rows, pop_off, pop_wgt, mode, fmt, pop_src_off), bp, key, radius, r2_min,
+                  key_index, key_member)
 
 
 def ldsplit_backtrack(cost, prev, K):
@@ -291,15 +303,15 @@ def ldsplit_backtrack(cost, prev, K):
     return ends
 
 
-def _split(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, radius, thr_r2, min_size, max_size, max_K, max_r2):
+def _split(ctx, src, bp, radius, thr_r2, min_size, max_size, max_K, max_r2):
+    S = src.S
     b = np.ascontiguousarray(bp, dtype=np.int32).reshape(-1)
     if b.shape != (S,):
         raise ValueError(f"bp has shape {b.shape}: expected ({S},)")
     K = int(max_K)
     cost, prev = np.full(max(K, 0), np.nan), np.full((max(K, 0), S + 1), -2, dtype=np.int32)
     mx, n = np.full(S + 1, np.nan), np.full(1, -1, dtype=np.int64)
-    check(ctx.lib.gauss_ld_split_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip), _lib.ptr(so, _ip),
-                                      _lib.ptr(w, _dp), len(po) - 1, on_dev, b.ctypes.data_as(_ip), int(radius), float(thr_r2), int(min_size),
+    check(ctx.lib.gauss_ld_split_rows(ctx.handle, *src.rows_head(), src.on_dev, b.ctypes.data_as(_ip), int(radius), float(thr_r2), int(min_size),
                                       int(max_size), K, float(max_r2), cost.ctypes.data_as(_dp), prev.ctypes.data_as(_ip),
                                       mx.ctypes.data_as(_dp), n.ctypes.data_as(C.POINTER(C.c_int64))))
     return dict(cost=cost, prev=prev, max_r2=mx, n_nonfinite=int(n[0]),
@@ -314,24 +326,18 @@ def ld_split(geno, pop_off, bp, pop_wgt=None, mode=MODE_WEIGHTED, radius=1 << 32
     up to GAUSS_LDSPLIT_MAX_K of them, no pair above max_r2 across a boundary, no distance limit beside max_size.  Returns
     dict(cost [max_K] (+inf: no such split), prev [max_K, S + 1], max_r2 [S + 1], n_nonfinite, splits): splits[K] is the array of
     the K blocks' end rows (exclusive, the last is S), or None.  Which K to use is the caller's choice."""
-    ctx = ctx or default_context()
-    g = _lib.as_u8(geno)
-    po, w = _pops(pop_off, pop_wgt)
-    return _split(ctx, g.ctypes.data, g.strides[0], _lib.GENO_U8, 0, None, g.shape[0], po, None, w, mode, bp, radius, thr_r2, min_size,
-                  max_size, max_K, max_r2)
+    return _split(ctx or default_context(), _Source.matrix(geno, pop_off, pop_wgt, mode), bp, radius, thr_r2, min_size, max_size, max_K, max_r2)
 
 
 def ld_split_rows(store, rows, pop_off, bp, pop_wgt=None, mode=MODE_WEIGHTED, radius=1 << 32, thr_r2=0.02, min_size=50, max_size=1000,
                   max_K=_lib.LDSPLIT_MAX_K, max_r2=0.3, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
     """ld_split on the store rows `rows` (a numpy matrix of host rows, a RowStore or a raw device pointer, as ld_matrix_rows)."""
-    ctx = ctx or default_context()
-    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
-    po, w = _pops(pop_off, pop_wgt)
-    S = len(r) if r is not None else store.shape[0]
-    return _split(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, bp, radius, thr_r2, min_size, max_size, max_K, max_r2)
+    return _split(ctx or default_context(), _Source(store, rows, pop_off, pop_wgt, mode, fmt, pop_src_off), bp, radius, thr_r2, min_size,
+                  max_size, max_K, max_r2)
 
 
-def _hess(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, z_traits, k_max, eig_min, want_vectors):
+def _hess(ctx, src, z_traits, k_max, eig_min, want_vectors):
+    S = src.S
     z = np.ascontiguousarray(z_traits, dtype=np.float64)
     if z.ndim == 1:
         z = z.reshape(1, -1)
@@ -344,8 +350,7 @@ def _hess(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, z_traits, k_max, eig
     vec = np.full((S, S), np.nan) if want_vectors else None
     order = np.full(S, -1, dtype=np.int32) if want_vectors else None
     o = out.ctypes.data
-    check(ctx.lib.gauss_ld_hess_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip), _lib.ptr(so, _ip),
-                                     _lib.ptr(w, _dp), len(po) - 1, on_dev, z.ctypes.data_as(_dp), T, K, float(eig_min),
+    check(ctx.lib.gauss_ld_hess_rows(ctx.handle, *src.rows_head(), src.on_dev, z.ctypes.data_as(_dp), T, K, float(eig_min),
                                      lam.ctypes.data_as(_dp), proj.ctypes.data_as(_dp), C.cast(o, _ip), C.cast(o + 4, _ip),
                                      n.ctypes.data_as(C.POINTER(C.c_int64)), C.cast(o + 8, _ip), _lib.ptr(vec, _dp), _lib.ptr(order, _ip)))
     res = dict(lam=lam, proj=proj, n_pos=int(out[0]), sweeps=int(out[1]), status=int(out[2]), n_nonfinite=int(n[0]))
@@ -360,20 +365,14 @@ def ld_hess(geno, pop_off, z_traits, pop_wgt=None, mode=MODE_WEIGHTED, k_max=256
     dict(lam [S] descending, proj [T, k_max] = (v_i . z_t) / sqrt(lam_i) for i < min(k_max, n_pos) and NaN beyond, n_pos, sweeps,
     status, n_nonfinite); api.hess_estimates turns lam and proj into h2, covariances and correlations on the host.
     want_vectors=True (for the tests) adds vectors [S, S] (row i = v_i) and order [S] (the solver's column of lam_i)."""
-    ctx = ctx or default_context()
-    g = _lib.as_u8(geno)
-    po, w = _pops(pop_off, pop_wgt)
-    return _hess(ctx, g.ctypes.data, g.strides[0], _lib.GENO_U8, 0, None, g.shape[0], po, None, w, mode, z_traits, k_max, eig_min, want_vectors)
+    return _hess(ctx or default_context(), _Source.matrix(geno, pop_off, pop_wgt, mode), z_traits, k_max, eig_min, want_vectors)
 
 
 def ld_hess_rows(store, rows, pop_off, z_traits, pop_wgt=None, mode=MODE_WEIGHTED, k_max=256, eig_min=1e-6, want_vectors=False,
                  fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
     """ld_hess on the store rows `rows` (a numpy matrix of host rows, a RowStore or a raw device pointer, as ld_matrix_rows)."""
-    ctx = ctx or default_context()
-    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
-    po, w = _pops(pop_off, pop_wgt)
-    S = len(r) if r is not None else store.shape[0]
-    return _hess(ctx, ptr, ld, fmt, on_dev, r, S, po, so, w, mode, z_traits, k_max, eig_min, want_vectors)
+    return _hess(ctx or default_context(), _Source(store, rows, pop_off, pop_wgt, mode, fmt, pop_src_off), z_traits, k_max, eig_min,
+                 want_vectors)
 
 
 def ld_resampled(store, rows, pop_off, draw_pop, draw_sample, n_cols, diag=1.0, fmt=_lib.GENO_2BIT, pop_src_off=None, ctx=None):
@@ -381,17 +380,16 @@ def ld_resampled(store, rows, pop_off, draw_pop, draw_sample, n_cols, diag=1.0, 
     over the drawn samples -- draw k is sample draw_sample[k] of population draw_pop[k] -- and n_cols - len(draws) zero columns
     (simulateLD)."""
     ctx = ctx or default_context()
-    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
-    po, _ = _pops(pop_off, None)
+    src = _Source(store, rows, pop_off, None, MODE_POOLED, fmt, pop_src_off)
     dp = np.ascontiguousarray(draw_pop, dtype=np.int32).reshape(-1)
     ds = np.ascontiguousarray(draw_sample, dtype=np.int32).reshape(-1)
     if dp.shape != ds.shape:
         raise ValueError(f"draw_pop has {dp.size} entries, draw_sample {ds.size}")
-    S = len(r) if r is not None else store.shape[0]
-    out = np.zeros((S, S))
-    check(ctx.lib.gauss_ld_resampled_rows(ctx.handle, ptr, ld, int(fmt), _lib.ptr(r, _ip), S, po.ctypes.data_as(_ip), _lib.ptr(so, _ip),
-                                          len(po) - 1, dp.ctypes.data_as(_ip), ds.ctypes.data_as(_ip), int(dp.size), int(n_cols),
-                                          float(diag), on_dev, out.ctypes.data_as(_dp)))
+    out = np.zeros((src.S, src.S))
+    # (pooled: the entry point takes neither a mode nor weights, so its head is spelled out)
+    check(ctx.lib.gauss_ld_resampled_rows(ctx.handle, src.ptr, src.ld, src.fmt, _lib.ptr(src.rows, _ip), src.S, src.po.ctypes.data_as(_ip),
+                                          _lib.ptr(src.so, _ip), len(src.po) - 1, dp.ctypes.data_as(_ip), ds.ctypes.data_as(_ip), int(dp.size),
+                                          int(n_cols), float(diag), src.on_dev, out.ctypes.data_as(_dp)))
     return out
 
 
@@ -399,23 +397,17 @@ def gene_ld_batch_rows(store, rows, pop_off, gene_off, pop_wgt=None, mode=MODE_P
                        pop_src_off=None, ctx=None):
     """gauss_gene_ld_batch_rows: LD blocks of all genes whose SNPs are the store rows `rows`."""
     ctx = ctx or default_context()
-    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
-    po, w = _pops(pop_off, pop_wgt)
-    go = np.ascontiguousarray(gene_off, dtype=np.int32)
-    sizes = np.diff(go).astype(np.int64)
-    out = np.zeros(int((sizes * sizes).sum()))
-    check(ctx.lib.gauss_gene_ld_batch_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), len(r), po.ctypes.data_as(_ip),
-                                           _lib.ptr(so, _ip), _lib.ptr(w, _dp), len(po) - 1, go.ctypes.data_as(_ip), len(go) - 1,
-                                           float(diag), on_dev, out.ctypes.data_as(_dp)))
-    blocks, o = [], 0
-    for n in sizes:
-        blocks.append(out[o:o + n * n].reshape(n, n))
-        o += n * n
+    len(rows)                                              # (this call names its rows: None raises here, as it always did)
+    src = _Source(store, rows, pop_off, pop_wgt, mode, fmt, pop_src_off)
+    go, out, blocks = _gene_blocks(gene_off)
+    check(ctx.lib.gauss_gene_ld_batch_rows(ctx.handle, *src.rows_head(), go.ctypes.data_as(_ip), len(go) - 1, float(diag), src.on_dev,
+                                           out.ctypes.data_as(_dp)))
     return blocks
 
 
-def _sumchi2(call, S, gene_off, z, prune_r2):
-    """The trait and output arguments of gauss_gene_sumchi2[_rows] and the returned dict; `call(tail)` makes the call."""
+def _sumchi2(ctx, src, by_rows, gene_off, z, prune_r2):
+    """gauss_gene_sumchi2_rows (by_rows) or gauss_gene_sumchi2 on the rows of src, and the returned dict."""
+    S = src.S
     go = np.ascontiguousarray(gene_off, dtype=np.int32)
     za = np.ascontiguousarray(z, dtype=np.float64)
     one = za.ndim == 1
@@ -426,9 +418,13 @@ def _sumchi2(call, S, gene_off, z, prune_r2):
     kept, n_kept = np.full(S, -2, dtype=np.int32), np.full(max(G, 0), -2, dtype=np.int32)
     lam, q = np.zeros((max(G, 0), _lib.SUMCHI2_MAX_KEPT)), np.zeros((T, max(G, 0)))
     top, status, sweeps = np.full((T, max(G, 0)), -2, dtype=np.int32), np.full(max(G, 0), -2, dtype=np.int32), np.full(max(G, 0), -2, dtype=np.int32)
-    check(call([go.ctypes.data_as(_ip), G], [za.ctypes.data_as(_dp), T, float(prune_r2), kept.ctypes.data_as(_ip),
-                                             n_kept.ctypes.data_as(_ip), lam.ctypes.data_as(_dp), q.ctypes.data_as(_dp),
-                                             top.ctypes.data_as(_ip), status.ctypes.data_as(_ip), sweeps.ctypes.data_as(_ip)]))
+    genes = (go.ctypes.data_as(_ip), G)
+    tail = (za.ctypes.data_as(_dp), T, float(prune_r2), kept.ctypes.data_as(_ip), n_kept.ctypes.data_as(_ip), lam.ctypes.data_as(_dp),
+            q.ctypes.data_as(_dp), top.ctypes.data_as(_ip), status.ctypes.data_as(_ip), sweeps.ctypes.data_as(_ip))
+    if by_rows:
+        check(ctx.lib.gauss_gene_sumchi2_rows(ctx.handle, *src.rows_head(), *genes, src.on_dev, *tail))
+    else:
+        check(ctx.lib.gauss_gene_sumchi2(ctx.handle, *src.geno_head(), *genes, *tail))
     from . import api       # (the p-value is the host library's: gauss_host_sumchi2_pval)
     pval = np.array([[api.sumchi2_pval(lam[g], q[t, g]) if status[g] == 0 else np.nan for g in range(G)] for t in range(T)]).reshape(T, max(G, 0))
     if one:
@@ -442,25 +438,14 @@ def gene_sumchi2(geno, pop_off, gene_off, z, pop_wgt=None, mode=MODE_WEIGHTED, p
     dict(kept [S] 0/1, n_kept [G], lam [G, 128] descending with NaN beyond n_kept, q [T, G], top [T, G] (row inside the gene, -1:
     none), status [G], sweeps [G], pval [T, G] from gauss_host_sumchi2_pval; NaN where status is not 0).  A 1-D z gives 1-D q, top
     and pval."""
-    ctx = ctx or default_context()
-    g = _lib.as_u8(geno)
-    po, w = _pops(pop_off, pop_wgt)
-    S = g.shape[0]
-    return _sumchi2(lambda genes, tail: ctx.lib.gauss_gene_sumchi2(ctx.handle, int(mode), g.ctypes.data, S, g.strides[0], po.ctypes.data_as(_ip),
-                                                                        _lib.ptr(w, _dp), len(po) - 1, *genes, *tail), S, gene_off, z, prune_r2)
+    return _sumchi2(ctx or default_context(), _Source.matrix(geno, pop_off, pop_wgt, mode), False, gene_off, z, prune_r2)
 
 
 def gene_sumchi2_rows(store, rows, pop_off, gene_off, z, pop_wgt=None, mode=MODE_WEIGHTED, prune_r2=0.9, fmt=_lib.GENO_2BIT,
                       pop_src_off=None, ctx=None):
     """gene_sumchi2 on the store rows `rows` (a numpy matrix of host rows, a RowStore or a raw device pointer, as
     gene_ld_batch_rows; rows None: rows 0 .. S-1 of a numpy matrix)."""
-    ctx = ctx or default_context()
-    ptr, ld, on_dev, r, so = _row_args(store, rows, pop_src_off)
-    po, w = _pops(pop_off, pop_wgt)
-    S = len(r) if r is not None else store.shape[0]
-    return _sumchi2(lambda genes, tail: ctx.lib.gauss_gene_sumchi2_rows(ctx.handle, int(mode), ptr, ld, int(fmt), _lib.ptr(r, _ip), S,
-                                                                             po.ctypes.data_as(_ip), _lib.ptr(so, _ip), _lib.ptr(w, _dp),
-                                                                             len(po) - 1, *genes, on_dev, *tail), S, gene_off, z, prune_r2)
+    return _sumchi2(ctx or default_context(), _Source(store, rows, pop_off, pop_wgt, mode, fmt, pop_src_off), True, gene_off, z, prune_r2)
 
 
 # lassosum's grid: the default of prs=dict(...)
@@ -495,10 +480,6 @@ def _field(prefix, key):
     if prefix == "susie_more":
         return "out_coloc_more_" + key
     return "out_coloc_lbf" if (prefix, key) == ("susie", "lbf") else f"out_{prefix}_{key}"
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
 
 
 def _xs_roles(windows):
